@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — frames/s of the per-frame point-cloud path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -18,10 +18,16 @@ steps overlap, so an event-bracketed stage inside them is no kernel duration.  `
 from a few EXTRA steps after the timed region, run one at a time with HIP events between the launches
 ("stage_ms_source": "separate timed steps"), next to a plain read stream over the same buffer (`k1_over_plain_stream`).
 
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, the configuration,
+the devices).  Everything else the line can hold - `stage_ms`, `roofline`, `floors`, the CPU baselines and oracle spot
+checks, `single_frame`, `pipelined`, `secondary`, `host_fed` - is measured only with --full (the --no-* options trim it).
+--dump-outputs DIR writes the per-frame results of the last timed step as float64 .npy files (result_arrays); the frames
+are generated from fixed seeds, so two builds can be compared output for output.
+
 PyTorch is plumbing here: device memory, the stream, the barrier and the max-reduce (torch.distributed over
 `gloo` on CPU tensors: the data path has no exchange step, so RCCL is never loaded).  The hot path is
 libssd_hip.so through its C ABI.  The CPU oracle is used only for the cpu_baseline leg and the parity
-spot check, both outside the timed region.
+spot check of --full, both outside the timed region.
 
 `python bench.py --gpus N` with N > 1 and no RANK in the environment launches the N ranks itself (a child
 `python -m torch.distributed.run ... bench.py --gpus N ...`, started before this process touches the GPU) and
@@ -339,6 +345,69 @@ def secondary_leg(ssd, scenes, torch, device, workload, steps, warmup, check_fra
     return out
 
 
+DUMP_LIMIT_BYTES = 60 * 1000 * 1000      # --dump-outputs: under 64 MB in all, .npy headers included
+
+
+def result_arrays(ssd, res, n):
+    """The results of one fetch of n frames (ssd_frame_result[n]) as the arrays a caller receives, copied out of the fetch buffer
+    (the next fetch of n frames reuses it): n_steps, status [n]; per step slot its height [n, MAX_STEPS] and quadrilateral
+    [n, MAX_STEPS, 4, 2] (front-left, front-right, back-left, back-right as x, y).  Slots past a frame's n_steps hold no result
+    and are zero here."""
+    import ctypes
+    import numpy as np
+    rec_t = np.dtype([("n_steps", "<i4"), ("status", "<i4"), ("steps", "<f8", (ssd.MAX_STEPS, 9))])
+    assert rec_t.itemsize == ctypes.sizeof(ssd.FrameResult)
+    rec = np.frombuffer(res, dtype=rec_t, count=n)
+    used = np.arange(ssd.MAX_STEPS)[None, :] < rec["n_steps"][:, None]
+    steps = np.where(used[:, :, None], rec["steps"], 0.0)
+    return {"n_steps": rec["n_steps"].astype(np.float64), "status": rec["status"].astype(np.float64),
+            "step_height": steps[:, :, 0].copy(), "step_quad": steps[:, :, 1:].reshape(n, ssd.MAX_STEPS, 4, 2)}
+
+
+def dump_outputs(out_dir, arrays, first_frame, world, rank):
+    """--dump-outputs: arrays -> out_dir/<name>.npy in float64 (<name>_rank<r>.npy with more than one rank), with frame_index
+    (global frame numbers).  At most DUMP_LIMIT_BYTES in all: a larger batch is cut to a fixed, seeded sample of its frames."""
+    import numpy as np
+    n = len(arrays["n_steps"])
+    per_frame = 8 + sum(a[0].nbytes for a in arrays.values())
+    keep = min(n, DUMP_LIMIT_BYTES // world // per_frame)
+    idx = np.arange(n) if keep == n else np.sort(np.random.default_rng(12345).choice(n, keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "_rank%d" % rank if world > 1 else ""
+    np.save(os.path.join(out_dir, "frame_index%s.npy" % suffix), (idx + first_frame).astype(np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, "%s%s.npy" % (name, suffix)), np.ascontiguousarray(a[idx], dtype=np.float64))
+
+
+def headline(args, world, F, W, H, fhd, dt_max, depth, prewarm, shards, n_steps):
+    """The part of the result line a plain run reports: the figure, its configuration and the devices that produced it."""
+    import numpy as np
+    out = {
+        "metric": METRIC_FHD if fhd else METRIC, "value": world * F * args.steps / dt_max, "unit": "frames/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt_max / args.steps * 1e3, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": ("BASELINE configs[4]: %d synthetic %dx%d frames (8 noisy steps, 5 %% outliers) resident in HBM; per GPU"
+                                if fhd else
+                                ("BASELINE configs[3]: %d-frame batch frame-sharded over %d GPUs; " % (F * world, world) if world > 1 else
+                                 "BASELINE configs[2]: ") +
+                                "batch of %d synthetic %dx%d frames (3-step staircases, randomised rise/"
+                                "tread/yaw/noise) resident in HBM, streamed through the whole per-frame path; per GPU") % (F, W, H),
+                   "frames_per_gpu_per_step": F, "width": W, "height": H, "input": args.input, "risers": bool(args.risers),
+                   "batches_in_flight": depth, "parallelism": "frame-sharded x%d, no collective" % world},
+        "prewarm": prewarm,
+    }
+    out["devices"] = [sh["where"] for sh in shards]
+    out["distinct_devices"] = distinct_devices(out["devices"])
+    if world > 1:
+        out["ranks"] = shards
+        if out["distinct_devices"] != world:
+            # said in the line, not raised: the other ranks are already waiting in the closing barrier
+            out["warning"] = "%d ranks on %d distinct GPU(s)%s: this is not an %d-GPU measurement" % (
+                world, out["distinct_devices"], " (SSD_BENCH_DEVICE puts every rank on one device: a test of the launcher)" if os.environ.get("SSD_BENCH_DEVICE") else "", world)
+    out["steps_histogram"] = {str(int(k)): int(c) for k, c in zip(*np.unique(n_steps, return_counts=True))}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -359,17 +428,24 @@ def main():
                     "input buffer lands, profiles/r06_box_spread.txt; a pad moves it); 0 = none")
     ap.add_argument("--prewarm-seconds", type=float, default=0.5,
                     help="untimed load in front of the W warm-up steps (an idle device needs more than a few steps to reach its clocks)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-hostfed", action="store_true", help="skip the host-fed (PCIe-inclusive) leg reported beside `value`")
-    ap.add_argument("--no-latency", action="store_true", help="skip the single-frame latency leg (profiling passes: its 56 one-frame "
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the per-frame results of the last timed step to DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline figure: per-stage device times and the roofline (extra steps after the timed "
+                         "region), CPU baselines and oracle spot checks, single-frame latency, ssd_pipeline_*, the secondary configurations "
+                         "and the host-fed leg; the --no-* options below trim it")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baselines and the oracle spot checks")
+    ap.add_argument("--no-hostfed", action="store_true", help="--full: skip the host-fed (PCIe-inclusive) leg reported beside `value`")
+    ap.add_argument("--no-latency", action="store_true", help="--full: skip the single-frame latency leg (profiling passes: its 56 one-frame "
                                                                "launches would be averaged into the per-kernel statistics)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary legs (BASELINE configs[4] = FHD stress, and 16-bit depth input) the default run times after the primary region")
+                    help="--full: skip the secondary legs (BASELINE configs[4] = FHD stress, and 16-bit depth input) timed after the primary region")
     ap.add_argument("--risers", action="store_true",
                     help="also gather the evidence of the vertical faces (extension beyond the reference, SURVEY 8f rank 4); off for the metric")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # not under a launcher: start the ranks as a child BEFORE anything here touches the GPU, exit with its code
@@ -469,6 +545,20 @@ def main():
     fence()
     dt = time.perf_counter() - t0
 
+    # the last timed step's results, copied before a further fetch of F frames reuses the buffer `res` points into
+    last = result_arrays(ssd, res, F)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, lo, world, rank)
+    if not args.full:
+        dt_max = ranks.max(dt)
+        shards = ranks.gather({"rank": rank, "device": device, "where": where, "frames": [lo, hi], "seconds": dt,
+                               "steps_found": int(last["n_steps"].sum())})
+        if rank == 0:
+            print(json.dumps(headline(args, world, F, W, H, fhd, dt_max, depth, prewarm, shards, last["n_steps"])), flush=True)
+        det.close()
+        ranks.close()
+        return
+
     # Per-stage device times: EXTRA steps after the timed region, one at a time (enqueue, fetch, then the next), HIP events
     # recorded between the launches on the stream the kernels run on.  The timed steps above overlap (depth batches in
     # flight), where an event-bracketed stage is a kernel's share of a machine it splits with the other batches' kernels.
@@ -517,7 +607,6 @@ def main():
 
     if rank == 0:
         lib_sha = file_sha256(ssd.LIB_PATH)
-        value = world * F * args.steps / dt_max
         achieved = alg_bytes / (k1_ms * 1e-3) / 1e9 if k1_ms > 0 else 0.0
         plain_ms = sum(stream_ms) / len(stream_ms) if stream_ms else None
         traffic = None
@@ -565,18 +654,8 @@ def main():
                 floors["source"], floors["stale"] = counters_stamp("pmc_issue.json", lib_sha)
             except Exception:
                 floors = None
-        out = {
-            "metric": METRIC_FHD if fhd else METRIC, "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": dt_max / args.steps * 1e3, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": ("BASELINE configs[4]: %d synthetic %dx%d frames (8 noisy steps, 5 %% outliers) resident in HBM; per GPU"
-                                    if fhd else
-                                    ("BASELINE configs[3]: %d-frame batch frame-sharded over %d GPUs; " % (F * world, world) if world > 1 else
-                                     "BASELINE configs[2]: ") +
-                                    "batch of %d synthetic %dx%d frames (3-step staircases, randomised rise/"
-                                    "tread/yaw/noise) resident in HBM, streamed through the whole per-frame path; per GPU") % (F, W, H),
-                       "frames_per_gpu_per_step": F, "width": W, "height": H, "input": args.input, "risers": bool(args.risers),
-                       "batches_in_flight": depth, "parallelism": "frame-sharded x%d, no collective" % world},
+        out = headline(args, world, F, W, H, fhd, dt_max, depth, prewarm, shards, last["n_steps"])
+        out.update({
             "roofline": {"bound": "hbm", "kernel": ("k_hist_planes (K1 of the single pass: transform+crop+bin+histogram+cell records, and the raster of "
                                                     "the step plateaus into planes)" if single_pass["ran"] else "k_hist (K1: transform+crop+bin+histogram)"),
                          "achieved": achieved,
@@ -603,7 +682,7 @@ def main():
                                     "note": "the same handle fed one batch at a time (no overlap; with the stage events): median of the %d extra passes, host clock around enqueue + fetch" % n_extra},
             "pipeline_bytes_moved": pipeline_moved,
             "pipeline_bytes_algorithmic_frac_of_peak": (alg_bytes * args.steps / dt_max / 1e9) / HBM_PEAK_GBS,
-        }
+        })
         # the dominant kernel's own issue floor: in the single pass K1 also rasters, and sits nearer to the vector-issue roof than to HBM's
         if os.path.exists(pi):
             try:
@@ -644,16 +723,6 @@ def main():
             except Exception:
                 pass
         out["library"] = {"path": os.path.relpath(ssd.LIB_PATH, ROOT), "sha256": lib_sha}
-        out["devices"] = [sh["where"] for sh in shards]
-        out["distinct_devices"] = distinct_devices(out["devices"])
-        if world > 1:
-            out["ranks"] = shards
-            if out["distinct_devices"] != world:
-                # said in the line, not raised: the other ranks are already waiting in the closing barrier
-                out["warning"] = "%d ranks on %d distinct GPU(s)%s: this is not an %d-GPU measurement" % (
-                    world, out["distinct_devices"], " (SSD_BENCH_DEVICE puts every rank on one device: a test of the launcher)" if os.environ.get("SSD_BENCH_DEVICE") else "", world)
-        steps_hist = [r.n_steps for r in res]
-        out["steps_histogram"] = {str(k): int(sum(1 for n in steps_hist if n == k)) for k in sorted(set(steps_hist))}
 
         if not args.no_cpu:
             import oracle_binding as ob

@@ -101,9 +101,9 @@ def test_compute_entry_points_fail_loudly_without_gpu(ssd):
     sc = ssd.make_scene(64, 48)
     with pytest.raises(ssd.SsdError, match="no HIP device"):
         ssd.synth_device([sc], 4096)                              # the frame source's device generator (libssd_source.so)
-    # the reference's main over this build (lib/detect-stairs-ref) ends with an error, not with a made-up line
+    # the reference's main over this build (oracle/_ref/detect-stairs-ref) ends with an error, not with a made-up line
     import subprocess
-    exe = os.path.join(os.path.dirname(ssd.LIB_PATH), "detect-stairs-ref")
+    exe = os.path.join(ROOT, "oracle", "_ref", "detect-stairs-ref")
     if os.path.exists(exe):
         p = subprocess.run([exe], capture_output=True, text=True, timeout=120, cwd=os.path.dirname(exe))
         assert p.returncode != 0 and "stairs" not in p.stdout

@@ -1,9 +1,9 @@
 """The C++ class surface (include/stairs/*.h -> libssd_hip.so, libssd_source.so) under the reference's OWN main.
 
 north_star: "keeping the existing Pointcloud/Stairs C++ class surface so detect-stairs.cpp ... link against it
-unchanged".  In the build container (where /root/reference exists) the reference's detect-stairs.cpp is compiled IN
-PLACE, UNMODIFIED, against this build's headers of the same names and linked against its libraries; on the GPU box the
-binary built here (lib/detect-stairs-ref, see __graft_entry__.build) is run and its stdout must be the oracle's lines.
+unchanged".  Where the reference tree exists the reference's detect-stairs.cpp is compiled IN PLACE, UNMODIFIED, against
+this build's headers of the same names and linked against its libraries; on the GPU the binary __graft_entry__.build()
+made of it (oracle/_ref/detect-stairs-ref, see oracle/Makefile) is run and its stdout must be the oracle's lines.
 The functors of GeometricTransformation are checked on the CPU against the same operation sequence in numpy."""
 import os
 import subprocess
@@ -16,6 +16,7 @@ import oracle_binding as ob
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_MAIN = "/root/reference/detect-stairs.cpp"
 INC = os.path.join(ROOT, "include", "stairs")
+REF_EXE = os.path.join(ROOT, "oracle", "_ref", "detect-stairs-ref")
 MARKS = np.array([[-0.35, 0.9, 0.004], [0.35, 0.9, 0.004], [0.2, 0.35, 0.004]])     # external-world marks (ssd.CALIBRATION_MARKS + z offset)
 
 
@@ -41,9 +42,8 @@ def test_reference_main_compiles_unmodified_against_this_build(ssd, tmp_path):
     undefined = subprocess.run(["nm", "-D", "--undefined-only", exe], check=True, capture_output=True, text=True).stdout
     for sym in ("Pointcloud", "GeometricCalibration", "Camera", "Window"):
         assert sym in undefined, sym                 # resolved from this build's libraries, not inlined stubs
-    # the binary kept next to the libraries (it travels to the GPU box) is this same translation unit
-    shipped = os.path.join(_libdir(ssd), "detect-stairs-ref")
-    assert os.path.exists(shipped), "__graft_entry__.build() did not build lib/detect-stairs-ref"
+    # the binary build() keeps under oracle/_ref/ (the GPU test runs it) is this same translation unit
+    assert os.path.exists(REF_EXE), "__graft_entry__.build() did not build oracle/_ref/detect-stairs-ref"
 
 
 def test_transformation_functors_follow_the_reference_operation_order(ssd, tmp_path):
@@ -77,13 +77,10 @@ def test_transformation_functors_follow_the_reference_operation_order(ssd, tmp_p
 
 @pytest.mark.gpu
 def test_reference_main_prints_the_oracles_lines(ssd, oracle, gpu_device, tmp_path):
-    """lib/detect-stairs-ref = /root/reference/detect-stairs.cpp, unmodified, over this build: run it on three synthetic
-    frames with the calibration files GeometricCalibration::load() reads; stdout must be the oracle's lines"""
-    exe = os.path.join(_libdir(ssd), "detect-stairs-ref")
-    if os.path.exists(REF_MAIN):
-        exe = str(tmp_path / "detect-stairs-ref")
-        _compile_reference_main(ssd, exe)
-    assert os.path.exists(exe), "lib/detect-stairs-ref missing: it is built by __graft_entry__.build() where /root/reference exists"
+    """oracle/_ref/detect-stairs-ref = the reference's detect-stairs.cpp, unmodified, over this build: run it on three
+    synthetic frames with the calibration files GeometricCalibration::load() reads; stdout must be the oracle's lines"""
+    exe = REF_EXE
+    assert os.path.exists(exe), "oracle/_ref/detect-stairs-ref missing: __graft_entry__.build() makes it where the reference tree exists"
     W, H, n, seed = 640, 480, 3, 4242
     import ctypes as C
     sc0 = ssd.Scene()

@@ -121,7 +121,7 @@ def test_bench_runs_two_ranks_on_this_gpu():
     env = dict(os.environ, SSD_BENCH_DEVICE="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--frames", "64", "--steps", "2", "--warmup", "1"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--frames", "64", "--steps", "2", "--warmup", "1", "--full"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -149,7 +149,7 @@ def test_bench_launcher_with_four_ranks_on_this_gpu():
     env = dict(os.environ, SSD_BENCH_DEVICE="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--frames", "64", "--steps", "2", "--warmup", "1"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--frames", "64", "--steps", "2", "--warmup", "1", "--full"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -178,7 +178,7 @@ def test_bench_config4_two_ranks_at_their_full_share_on_this_gpu():
     env = dict(os.environ, SSD_BENCH_DEVICE="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--frames", "2048", "--steps", "3", "--warmup", "1"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--frames", "2048", "--steps", "3", "--warmup", "1", "--full"],
                        env=env, capture_output=True, text=True, timeout=1500)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -213,6 +213,41 @@ def test_bench_refuses_two_ranks_without_two_gpus():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--frames", "8", "--steps", "1", "--warmup", "0", "--no-cpu"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode != 0 and "n_gpus" not in p.stdout
+
+
+def test_bench_plain_run_dumps_the_last_steps_results(ssd, gpu_device, tmp_path):
+    """`bench.py` without --full prints the headline line and measures nothing beside it; --dump-outputs writes the results
+    of its last timed step as float64 .npy files, and they are what a handle of the same configuration returns for the same
+    seeded frames (rank 0's of the metric's workload)."""
+    import bench
+    n, W, H = 64, 1024, 768
+    dump = tmp_path / "outputs"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--frames", str(n), "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "f64" and d["steps"] == 3
+    assert d["value"] == pytest.approx(n * 3 / (d["ms_per_step"] * 3 * 1e-3), rel=1e-6)
+    assert not {"stage_ms", "roofline", "floors", "cpu_baseline", "parity", "single_frame", "pipelined", "secondary", "host_fed"} & set(d)
+    got = {k: np.load(str(dump / (k + ".npy"))) for k in ("frame_index", "n_steps", "status", "step_height", "step_quad")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["frame_index"].tolist() == list(range(n)) and got["step_quad"].shape == (n, ssd.MAX_STEPS, 4, 2)
+    assert d["steps_histogram"] == {str(int(k)): int(c) for k, c in zip(*np.unique(got["n_steps"], return_counts=True))}
+    sc_list = scenes.batch_scenes(ssd, W, H, n, base_seed=100000, rng_seed=1000)
+    buf = ssd.DeviceBuffer(W * H * 12 * n, gpu_device)
+    ssd.synth_device(sc_list, buf.ptr, device=gpu_device)
+    det = ssd.Detector(ssd.default_config(W, H, max_frames_per_batch=n, batches_in_flight=ssd.BATCHES_IN_FLIGHT_THROUGHPUT),
+                       ssd.transformation_for_scene(sc_list[0]), gpu_device)
+    det.enqueue(buf.ptr, n)
+    want = bench.result_arrays(ssd, det.fetch(n), n)
+    det.close()
+    buf.free()
+    assert (want["n_steps"] >= 3).sum() >= n * 9 // 10
+    for k in ("n_steps", "status", "step_quad"):
+        assert np.array_equal(got[k], want[k]), k
+    assert np.abs(got["step_height"] - want["step_height"]).max() <= parity.TOL_HEIGHT
 
 
 def test_native_driver_shards_frames_over_device_threads(ssd):

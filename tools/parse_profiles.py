@@ -79,7 +79,7 @@ def main():
                     pass
                 dump({**keep, "kernel": r["Name"].split("(")[0].replace("void ", ""), "calls": int(r["Calls"]), "avg_launch_ms": avg_ms,
                       "algorithmic_bytes_per_launch": alg, "frac": alg / (avg_ms * 1e-3) / 8e12, "gpu": gpu,
-                      "summary": "profiles/%s_kernel_stats.csv (rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 5 --warmup 2 --batches-in-flight 1 ...)" % tag},
+                      "summary": "profiles/%s_kernel_stats.csv (rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 5 --warmup 2 --batches-in-flight 1 ...)" % tag},
                      os.path.join(dst, "k1_rocprof.json"), stamp)
                 break
     out = {"note": "per launch = per batch of 1024 frames of 1024x768 points; bytes", "kernels": {}}
@@ -153,7 +153,7 @@ def main():
             for k in per:
                 for c, v in per[k].items():
                     agg[k][c] = round(sum(v) / len(v), 3)
-        issue = {"note": "rocprofv3 --kernel-trace --pmc <set> -- python3 bench.py --steps 2 --warmup 1 --no-cpu (one pass per counter set, "
+        issue = {"note": "rocprofv3 --kernel-trace --pmc <set> -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu (one pass per counter set, "
                          "tools/pmc.sh); per launch = 1024 XGA frames", "kernels": {k: dict(sorted(v.items())) for k, v in sorted(agg.items())}}
         dump(issue, os.path.join(dst, tag + "_pmc_issue.json"), stamp)
         issue["source"] = "profiles/%s_pmc_issue.json" % tag

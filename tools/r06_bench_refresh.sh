@@ -11,8 +11,8 @@ h = hashlib.sha256(open("stair-step-detector_amd/lib/libssd_hip.so", "rb").read(
 if h != st["lib_sha256"]:
     sys.exit("lib/libssd_hip.so is not the stamped build")
 PY
-python3 bench.py > $OUT/bench.json 2> $OUT/bench.err && tail -c 300 $OUT/bench.json
-python3 bench.py --workload fhd_stress --cpu-frames 48 > $OUT/bench_fhd.json 2> $OUT/bench_fhd.err
-python3 bench.py --input depth16 --no-hostfed --cpu-frames 64 > $OUT/bench_depth16.json 2> $OUT/bench_depth16.err
-python3 bench.py --no-cpu --no-hostfed --no-latency --no-secondary --steps 24 > $OUT/bench_steps24.json 2> $OUT/bench_steps24.err
+python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err && tail -c 300 $OUT/bench.json
+python3 bench.py --full --workload fhd_stress --cpu-frames 48 > $OUT/bench_fhd.json 2> $OUT/bench_fhd.err
+python3 bench.py --full --input depth16 --no-hostfed --cpu-frames 64 > $OUT/bench_depth16.json 2> $OUT/bench_depth16.err
+python3 bench.py --full --no-cpu --no-hostfed --no-latency --no-secondary --steps 24 > $OUT/bench_steps24.json 2> $OUT/bench_steps24.err
 grep -o '"stale": [a-z]*' $OUT/bench.json $OUT/bench_fhd.json $OUT/bench_depth16.json | sort | uniq -c

@@ -4,7 +4,7 @@
 R=$GRAFT_REPO_ROOT; cd /tmp && export TMPDIR=/tmp
 for pad in "$@"; do
   OUT=$R/gpurun_out/prof_states/pad$pad; rm -rf $OUT; mkdir -p $OUT
-  rocprofv3 --kernel-trace --stats -d $OUT --output-format csv -- python3 $R/bench.py --steps 5 --warmup 2 --batches-in-flight 1 --no-cpu --no-hostfed --no-latency --no-secondary --pad-mib $pad > $OUT/log.txt 2>&1
+  rocprofv3 --kernel-trace --stats -d $OUT --output-format csv -- python3 $R/bench.py --full --steps 5 --warmup 2 --batches-in-flight 1 --no-cpu --no-hostfed --no-latency --no-secondary --pad-mib $pad > $OUT/log.txt 2>&1
   f=$(ls $OUT/*/*kernel_stats.csv | head -1)
   python3 - "$f" "$pad" <<'PY'
 import csv, sys

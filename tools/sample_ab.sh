@@ -2,7 +2,7 @@
 # tools/sample_ab.sh ROUNDS LIBDIR... — bench.py (three batches in flight, 24 steps) alternately on library builds: value, K1, predict, raster, frames covered
 N=$1; shift
 for r in $(seq 1 $N); do for d in "$@"; do
-  SSD_HIP_LIB=$GRAFT_REPO_ROOT/stair-step-detector_amd/$d/libssd_hip.so python3 bench.py --no-cpu --no-hostfed --no-latency --no-secondary --steps 24 2>/dev/null | python3 -c "
+  SSD_HIP_LIB=$PWD/stair-step-detector_amd/$d/libssd_hip.so python3 bench.py --full --no-cpu --no-hostfed --no-latency --no-secondary --steps 24 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().split('\n')[-1])
 sp=d['single_pass']
