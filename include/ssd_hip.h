@@ -28,7 +28,8 @@
  * handle's own.  ssd_process_host / ssd_process_depth_host always use two non-blocking streams of the handle's own (copy and
  * compute) and return when the results are on the host; they do not synchronise with the legacy default stream.
  * Configuration limits: max(|z_min|, |z_max|) < 2048 m and max|z| * width * height < 2^23 (the mean height of a step
- * is accumulated in 2^-40 m fixed point), 3..SSD_MAX_BINS histogram bins, width <= 8192, height <= 8064.
+ * is accumulated in 2^-40 m fixed point), 3..SSD_MAX_BINS histogram bins, width <= 3175 ((width - 1) / 25 + 2 scan columns
+ * <= SSD_MAX_SCANS), height <= 2560 ((height - 1) / 10 + 1 vertical-edge probe rows <= SSD_MAX_EDGE_PTS).
  */
 #ifndef SSD_HIP_H_
 #define SSD_HIP_H_

@@ -559,7 +559,13 @@ Outline detectOutline(Img &im, int minImgYExtent, double xyRatio, bool fastClose
   const Scans scansRight = scanColumns(im, minImgYExtent, xCenter, xStep);
   if(scansRight.empty())
     return outline;
-  const Scans scansLeft = scanColumns(im, minImgYExtent, xCenter - xStep, -xStep);
+  /* Scanner::scan asserts xStart >= 0 (:61): an image narrower than 2 * xStep has no left scan column (the reference's
+   * release build would read left of its image) */
+  Scans scansLeft;
+  if(xCenter - xStep >= 0)
+    scansLeft = scanColumns(im, minImgYExtent, xCenter - xStep, -xStep);
+  else
+    status |= SSDO_ST_ASSERT;
   if(dbg)
   {
     dbg->n_scans_right = int(scansRight.size());

@@ -375,6 +375,10 @@ static int make_params(const ssd_config &c, const ssd_calibration &k, Params &P)
   }
   if((c.width - 1) / 25 + 2 > SSD_MAX_SCANS)
     return fail(SSD_E_ARG, "config: width needs more scan columns than SSD_MAX_SCANS");
+  /* k_outline keeps one vertical-edge probe row per 10 image rows (detectEdge, segmentation.cpp:681-706) in LDS arrays of
+   * SSD_MAX_EDGE_PTS; the reference has no cap, so a taller image could give a step a different vertical edge */
+  if((c.height - 1) / 10 + 1 > SSD_MAX_EDGE_PTS)
+    return fail(SSD_E_ARG, "config: height needs more vertical-edge probe rows than SSD_MAX_EDGE_PTS");
   return SSD_OK;
 }
 

@@ -2389,7 +2389,7 @@ constexpr int kImgThreadsBatch = SSD_IMG_THREADS_BATCH, kImgThreadsFew = 512;   
 constexpr int kMaxImgWaves = (kImgThreadsBatch > kImgThreadsFew ? kImgThreadsBatch : kImgThreadsFew) / 64;
 constexpr int kImgFewFrames = 64;
 constexpr int kMaxCols = SSD_MAX_SCANS;      /* scan columns per image (W/25 + 1 <= 128) */
-constexpr int kMaxProbe = SSD_MAX_EDGE_PTS;  /* probe rows per vertical edge (H/10 + 1 <= 256) */
+constexpr int kMaxProbe = SSD_MAX_EDGE_PTS;  /* probe rows per vertical edge: (H - 1)/10 + 1 <= 256, make_params refuses H > 2560 */
 
 struct OutlineShared
 {
@@ -2627,6 +2627,10 @@ __global__ __launch_bounds__(T) void k_outline(Params P, FrameState *__restrict_
     {
       S.nRight = nR;
       S.nLeft = nL;
+      /* Scanner::scan asserts xStart >= 0 (segmentation.cpp:61): below 2 * xStep columns the left scans would start left of
+       * the image; there are none */
+      if(nR > 0 && xc < xStep)
+        S.status |= SSD_ST_ASSERT;
       if(found)
       {
         S.found = 1;

@@ -5,8 +5,10 @@ the identity rotation plus a shift of -0.5 m in z (camera z = world z + 0.5 > 0,
 import numpy as np
 import pytest
 
+import clouds
 import oracle_binding as ob
 import parity
+from clouds import Z_SHIFT, calibration
 
 pytestmark = pytest.mark.gpu
 
@@ -14,35 +16,8 @@ W, H = 640, 480
 
 
 def cloud(planes, extra=None, seed=0):
-    """planes: list of (z, n_points, (x0, x1), (y0, y1)) -> float32 [H, W, 3]; points of a plane lie on a regular
-    grid inside its rectangle (so that they rasterise to a solid block); the rest of the frame is invalid (0,0,0)."""
-    rng = np.random.default_rng(seed)
-    pts = []
-    for z, n, (x0, x1), (y0, y1) in planes:
-        nx = max(1, int(round(np.sqrt(n * (x1 - x0) / max(y1 - y0, 1e-9)))))
-        ny = (n + nx - 1) // nx
-        gx, gy = np.meshgrid(np.linspace(x0, x1, nx), np.linspace(y0, y1, ny))
-        p = np.stack([gx.ravel(), gy.ravel(), np.full(gx.size, z)], 1)[:n]
-        pts.append(p)
-    if extra is not None:
-        pts.append(np.asarray(extra, dtype=np.float64))
-    p = np.concatenate(pts) if pts else np.zeros((0, 3))
-    assert len(p) <= W * H
-    out = np.zeros((W * H, 3), dtype=np.float32)
-    idx = rng.permutation(W * H)[:len(p)]
-    p = p.copy()
-    p[:, 2] += Z_SHIFT                                  # world -> camera
-    out[np.sort(idx)] = p.astype(np.float32)
-    return out.reshape(H, W, 3)
-
-
-Z_SHIFT = 0.5
-
-
-def calibration(ssd):
-    t = ssd.GeometricTransformation()                   # identity (transformation.h:51-55) ...
-    t.constants.b[2] = -Z_SHIFT                         # ... with the camera half a metre below the world origin
-    return t
+    """planes: list of (z, n_points, (x0, x1), (y0, y1)) -> float32 [H, W, 3] (clouds.cloud at this module's resolution)"""
+    return clouds.cloud(planes, W, H, extra=extra, seed=seed)
 
 
 def run(ssd, oracle, gpu_device, xyz):
