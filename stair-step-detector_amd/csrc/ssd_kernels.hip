@@ -1204,7 +1204,11 @@ __device__ __forceinline__ void hist_block(HistLds &L, SPECLDS &SL, const float 
       if constexpr(CHECKS)
       {
         /* unless make_pre_xy() showed that larger inputs cannot read "inside" */
+#if defined(SSD_SABOTAGE_PRE) && (SSD_SABOTAGE_PRE & 16)  /* tools: inputs beyond PreXY::maxInput NOT handed to the doubles - the tests built for it must fail */
+        const unsigned long long mFar = 0ull;
+#else
         const unsigned long long mFar = Q.checkInput ? ~__ballot(M3 <= Q.maxInput) : 0ull;
+#endif
         mInxy &= ~mFar;
         mMaybexy |= mFar;
       }
@@ -1217,7 +1221,11 @@ __device__ __forceinline__ void hist_block(HistLds &L, SPECLDS &SL, const float 
       const unsigned long long mInz = __ballot(__float_as_uint(t) < Q.zTopBits);     /* +0 <= t < zTop on the bits (a negative t has the sign bit) */
       if constexpr(CHECKS)
       {
+#if defined(SSD_SABOTAGE_PRE) && (SSD_SABOTAGE_PRE & 8)   /* tools: the band at the top of a z range that ends mid-bin NOT handed to the doubles */
+        if(false)
+#else
         if(Q.zCheckTop)
+#endif
           mSurez &= __ballot(__builtin_fabsf(t - Q.zTop) > 0.5f - h);    /* the range's upper end is no bin edge: its own band */
       }
 #if defined(SSD_SABOTAGE_PRE) && (SSD_SABOTAGE_PRE & 1)   /* tools: the band around the bin edges NOT handed to the doubles - the tests built for it must fail */
@@ -3513,7 +3521,11 @@ __device__ __forceinline__ void inquad_block(InquadLds<FULL> &L, const float *__
       if constexpr(CHECKS)
       {
         /* (the rare configurations' tests, as K1's: launch_inquad picks the instantiation) */
+#if defined(SSD_SABOTAGE_PRE) && (SSD_SABOTAGE_PRE & 16)
+        const unsigned long long mFar = 0ull;
+#else
         const unsigned long long mFar = Q.checkInput ? ~__ballot(M3 <= Q.maxInput) : 0ull;
+#endif
         mInxy &= ~mFar;
         mMaybexy |= mFar;
       }
@@ -3524,7 +3536,11 @@ __device__ __forceinline__ void inquad_block(InquadLds<FULL> &L, const float *__
       const unsigned long long mInz = __ballot(__float_as_uint(t) < Q.zTopBits);
       if constexpr(CHECKS)
       {
+#if defined(SSD_SABOTAGE_PRE) && (SSD_SABOTAGE_PRE & 8)
+        if(false)
+#else
         if(Q.zCheckTop)
+#endif
           mSurez &= __ballot(__builtin_fabsf(t - Q.zTop) > 0.5f - h);
       }
 #if defined(SSD_SABOTAGE_PRE) && (SSD_SABOTAGE_PRE & 1)

@@ -23,8 +23,11 @@
  * differs from floor(t) only for an integer t, and then by -1: for a minimum that widens the box, for a maximum the box still
  * ends at (dMax + 1/2 + e), beyond the point by the slack in e.
  *
- * Inputs beyond R.  The x / y decision only matters for a point whose z test - in doubles, always - said "in range": then
- * |w_z - b_z| <= Z = max(|zMin - b_z|, |zMax - b_z|).  With sigma the smallest singular value of A (1 for a rotation),
+ * Inputs beyond R.  The x / y decision only matters for a point whose z test said "in range".  That test is single precision first
+ * (make_pre_z() below), and a SURE single-precision z decision is the doubles' at every magnitude: its bound e(M) is taken per point
+ * from M = max(|x|, |y|, |z|), not for inputs up to R, and the threshold h = 1/2 - e(M) goes negative when M overflows the bound (an
+ * infinity gives -inf), so such a point is never sure.  The other points take the doubles' z test.  Either way the doubles say
+ * "in range", so |w_z - b_z| <= Z = max(|zMin - b_z|, |zMax - b_z|).  With sigma the smallest singular value of A (1 for a rotation),
  * |A p| >= sigma |p|_2 >= sigma |p|_inf, so for |p|_inf = t > R one of |w_x - b_x|, |w_y - b_y| is at least
  * G(t) = sqrt((sigma^2 t^2 - Z^2) / 2), its |D| at least (G(t) - off) * smin with off = max(|b_x - x centre|, |b_y - y centre|)
  * and smin the smaller of the two 1 / (max - min), while d is off by at most 4.01 * 2^-24 (|c|_1 t + |c3|): a term that grows

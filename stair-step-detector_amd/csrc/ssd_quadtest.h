@@ -519,13 +519,21 @@ __host__ __device__ inline void build_quad_edges(const QuadTest &t, int okInside
 }
 
 /* +1: inside by the reference's test for sure, -1: outside for sure, 0: ask the doubles.  dBound = PreXY::dK * M + PreXY::dE0 for
- * the point's magnitude M = max(|x|, |y|, |z|) of the camera coordinates (k_inquad folds dE0 into its copy of m). */
+ * the point's magnitude M = max(|x|, |y|, |z|) of the camera coordinates (k_inquad folds dE0 into its copy of m).  A half-plane that
+ * reads NaN or an infinity (a NaN or overflowed d) gives 0: fminf would drop the NaN and read "inside for sure". */
 __host__ __device__ __forceinline__ int quad_edges_classify(const QuadEdgesF &E, float dx, float dy, float dBound)
 {
   float emin = INFINITY;
+  bool finite = true;
 #pragma unroll
   for(int s = 0; s < 4; s++)
-    emin = fminf(emin, __builtin_fmaf(E.gy[s], dy, __builtin_fmaf(E.gx[s], dx, E.g2[s])));
+  {
+    const float e = __builtin_fmaf(E.gy[s], dy, __builtin_fmaf(E.gx[s], dx, E.g2[s]));
+    emin = fminf(emin, e);
+    finite = finite && __builtin_isfinite(e);
+  }
+  if(!finite)
+    return 0;
   const float h = E.m + dBound;
   return emin > h ? 1 : (emin < -h ? -1 : 0);
 }

@@ -116,15 +116,26 @@ def compare_result(ssd, fr, res, report):
     report["line"] = line
 
 
-def check_frame(ssd, oracle, det, cfg, cal, xyz, images=True, report=None, depth_intr=None):
+def check_frame(ssd, oracle, det, cfg, cal, xyz, images=True, report=None, depth_intr=None, unaligned_buf=None):
     """Runs one frame through the HIP path (debug capture on) and the oracle and compares everything.
     With depth_intr, `xyz` is a uint16 depth frame: the HIP path deprojects on the fly (ssd_process_depth_host),
-    the oracle deprojects first.  Returns the report dict; raises Mismatch on the first difference."""
+    the oracle deprojects first.  With unaligned_buf (a DeviceBuffer of at least 12 W H + 4 bytes), the float frame
+    is read from 4 bytes into it at a stride of 12 W H + 4 bytes: the kernels' 12-byte loads.
+    Returns the report dict; raises Mismatch on the first difference."""
     report = {} if report is None else report
     ocfg, ocal = ob.to_oracle_config(cfg), ob.to_oracle_calibration(cal)
     if depth_intr is not None:
         det.set_intrinsics(depth_intr)
-    run = (lambda: det.process_depth_host(xyz)[0]) if depth_intr is not None else (lambda: det.process_host(xyz)[0])
+    if depth_intr is not None:
+        run = lambda: det.process_depth_host(xyz)[0]
+    elif unaligned_buf is not None:
+        unaligned_buf.upload(np.ascontiguousarray(xyz, dtype=np.float32), offset=4)
+
+        def run():
+            det.enqueue(unaligned_buf.ptr + 4, 1, stride_bytes=det.frame_bytes + 4)
+            return det.fetch_list(1)[0]
+    else:
+        run = lambda: det.process_host(xyz)[0]
     # records only: the kernels exactly as in production (k_inquad rasters only the ground pixels the bottom scan reads)
     det.set_debug(True, images=False)
     fr = run()

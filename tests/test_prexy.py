@@ -16,22 +16,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 ssd = importlib.import_module("stair-step-detector_amd")
 
-
-def _rotation(rng):
-    q = rng.normal(size=4)
-    q /= np.linalg.norm(q)
-    w, x, y, z = q
-    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
-                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
-                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
-
-
-def _chain(c_row, p):
-    """the kernel's three FMAs of one row on float32 inputs p [n, 3]; c_row = (c0, c1, c2, c3) float32"""
-    f = np.float64
-    r = (f(c_row[2]) * p[:, 2].astype(f) + f(c_row[3])).astype(np.float32)
-    r = (f(c_row[1]) * p[:, 1].astype(f) + r.astype(f)).astype(np.float32)
-    return (f(c_row[0]) * p[:, 0].astype(f) + r.astype(f)).astype(np.float32)
+import prefilter_model as pm  # noqa: E402
+from prefilter_model import chain as _chain, fma32 as _fma32, rotation as _rotation, sure as _sure, t_chain as _t_chain  # noqa: E402
 
 
 def _exact(a, b, lo, hi, p):
@@ -106,30 +92,50 @@ def test_large_inputs_read_outside_when_the_magnitude_test_is_dropped():
     assert far["check_input"] and skew["check_input"]
 
 
+def test_inputs_beyond_64_m_without_the_magnitude_test_decide_as_the_doubles():
+    """check_input == 0 and z_check_top == 0 (the common instantiation: no per-point magnitude test, no band at the top): inputs of
+    64 m .. 10^6 m, far out in the world's x / y plane with z in range and on bin edges, and in every direction.  The kernel's whole
+    decision (prefilter_model.kernel_decisions: x / y and z single precision first, the doubles for the rest) must be the doubles'
+    range decision and bin - the argument of ssd_prexy.h's "Inputs beyond R", which relies on a sure z decision being the doubles'
+    at every magnitude.  Many of these points are sure in z (a bound per point), the farthest are not (the threshold goes negative)."""
+    rng = np.random.default_rng(64)
+    lim = (-0.6, 0.6, 0.1, 1.3, -0.1, 1.1)
+    recip = 1.0 / 0.01
+    seen = 0
+    for trial in range(6):
+        a = _rotation(rng)
+        b = -a @ rng.uniform(-1.5, 1.5, 3)
+        Q = ssd.prexy_host(*lim, a, b)
+        Z = ssd.prez_host(*lim, a, b)
+        if Q["check_input"]:
+            continue
+        assert not Z["z_check_top"] and Z["z_h0"] > 0
+        seen += 1
+        n = 30000
+        r = 10.0 ** rng.uniform(np.log10(64.0), 6.0, n)
+        ang = rng.uniform(0, 2 * np.pi, n)
+        z = rng.uniform(-0.1, 1.1, n)
+        z[: n // 2] = -0.1 + (rng.integers(0, 121, n // 2) + rng.choice([0.0, 1e-9, -1e-9, 1e-6, -1e-6, 1e-4, -1e-4], n // 2)) / recip
+        w = np.stack([r * np.cos(ang), r * np.sin(ang), z], 1)
+        p = ((w - b) @ np.linalg.inv(a).T).astype(np.float32)
+        anyway = (rng.normal(size=(n, 3)) * (10.0 ** rng.uniform(np.log10(64.0), 6.0, n))[:, None]).astype(np.float32)
+        p = np.concatenate([p, anyway])
+        p = p[(np.abs(p).max(1) > 64.0) & (p[:, 2] > 0)]
+        inr, hbin, slow = pm.kernel_decisions(Q, Z, lim, a, b, recip, p)
+        ok, hb = pm.reference(lim, a, b, recip, p)
+        assert np.array_equal(inr, ok) and np.array_equal(hbin[ok], hb[ok])
+        M3 = pm.absmax3(p)
+        zsure = pm.sure(pm.t_chain(Z["zc"], p), M3, Z["z_neg_k"], Z["z_h0"])
+        assert zsure.sum() > len(p) // 4 and (~zsure).sum() > len(p) // 10
+    assert seen >= 4
+
+
 def test_a_calibration_single_precision_cannot_serve_sends_every_point_through_the_doubles():
     Q = ssd.prexy_host(-0.6, 0.6, 0.1, 1.3, -0.1, 1.1, np.eye(3) * 1e7, np.zeros(3))
     assert Q["lo"] < 0.0 and np.isinf(Q["hi"]) and Q["check_input"]
 
 
 # ---- round 6: the z row / height bin and the candidates' pixel in single precision first (make_pre_z, make_pre_pixel) ----
-
-def _fma32(a, x, c):
-    """fl32(a * x + c) on float32 operands: the product and the sum are formed in float64 and rounded once (the product of two
-    float32 values is exact in float64; the sum's own float64 rounding is 2^-29 of a float32 ulp)"""
-    return (np.float64(a) * x.astype(np.float64) + np.asarray(c, dtype=np.float32).astype(np.float64)).astype(np.float32)
-
-
-def _t_chain(zc, p):
-    return _fma32(zc[0], p[:, 0], _fma32(zc[1], p[:, 1], _fma32(zc[2], p[:, 2], np.full(len(p), zc[3], np.float32))))
-
-
-def _sure(t, M3, neg_k, h0):
-    """the kernel's certainty test: |fract(t) - 1/2| < h0 + neg_k * M3, all in float32; False for NaNs"""
-    with np.errstate(invalid="ignore", over="ignore"):
-        g = ((t - np.floor(t)).astype(np.float32) - np.float32(0.5)).astype(np.float32)
-        h = _fma32(neg_k, M3, np.full(len(t), h0, np.float32))
-        return np.abs(g) < h
-
 
 def _reference_z(a, b, z_min, z_max, recip, p):
     """pointcloud.cpp:150-178 / transformation.h:59-64 in the reference's doubles, operation by operation"""

@@ -178,6 +178,32 @@ def test_the_map_is_not_the_geometry_for_a_thin_tilted_quadrilateral(ssd, oracle
     assert np.isinf(out["m"]) and out["cls"][0] == 0
 
 
+def test_nan_and_infinite_points_are_never_sure(ssd):
+    """quad_edges_classify folds the four half-planes with fminf, which drops a NaN: a NaN coordinate read "inside for sure".  NaN and
+    infinite inputs (d NaN or infinite) must give 0 - ask the doubles -, whichever quadrilateral; the finite points beside them keep
+    their answers (some inside, some outside for sure)."""
+    rng = np.random.default_rng(9)
+    a, b = _calibration(rng)
+    quad = _tread(rng, 0.2)
+    inside = ((np.append(quad.mean(0), 0.5) - b) @ np.linalg.inv(a).T).astype(np.float32)
+    outside = ((np.array([quad[:, 0].max() + 0.3, quad[:, 1].mean(), 0.5]) - b) @ np.linalg.inv(a).T).astype(np.float32)
+    bad = []
+    for v in (np.nan, np.inf, -np.inf):
+        for axis in range(3):
+            for base in (inside, outside):
+                p = base.copy()
+                p[axis] = v
+                bad.append(p)
+    bad.append(np.full(3, np.nan, np.float32))
+    bad.append(np.array([np.inf, -np.inf, np.inf], np.float32))
+    pts = np.concatenate([np.array(bad, np.float32), [inside, outside]])
+    with np.errstate(invalid="ignore", over="ignore"):
+        r = ssd.quad_edges_host(quad.reshape(8), X_MIN, X_MAX, Y_MIN, Y_MAX, Z_MIN, Z_MAX, a, b, pts)
+    assert r["err"] == 0 and np.isfinite(r["m"])
+    assert list(r["cls"][-2:]) == [1, -1]
+    assert not np.any(r["cls"][:-2]), r["cls"][:-2].tolist()
+
+
 @pytest.mark.gpu
 def test_the_device_builds_the_same_table_and_switches_the_same_quadrilaterals_off(ssd, gpu_device):
     """k_quads' three steps on the device - the coefficients, the check of the map's nine cells dealt out to lanes, the margin - give the host's
