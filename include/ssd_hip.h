@@ -266,6 +266,32 @@ int ssd_set_risers(ssd_handle *h, int enable, double tolerance, int min_support)
  * ssd_process_host / ssd_process_depth_host call (collected slice by slice); nframes <= what that call processed.  While
  * risers are on, a handle with several workspaces runs its batches one after the other (the riser buffer is single). */
 int ssd_fetch_risers(ssd_handle *h, ssd_frame_risers *out, int nframes, void *stream);
+/* ---- per-pixel surface labels -----------------------------------------------------------------------------------
+ * EXTENSION: which camera pixels each reported surface came from.  Frame i's labels are W * H bytes, one per point (camera
+ * pixel (u, v) at v * W + u, for vertex and 16-bit depth input alike):
+ *   k + 1  the point is one of those whose mean is surface k of the frame's ssd_frame_result (k_final's order: the ground first
+ *          when emitted, then the valid steps ascending), i.e. pointsInQuadri of calcGround / calcStairStep
+ *          (pointcloud.cpp:528-558): z > 0, strictly inside the measuring range after CameraToWorld (the reference's doubles),
+ *          its height bin among those that feed that surface's plateau (ssd_debug_plateau eff_lo .. eff_hi), and
+ *          QuadrilateralTest::isPointWithin of that plateau's quadrilateral;
+ *   0      otherwise (SSD_LABEL_NONE).  Every label of a frame is 0 when its status has SSD_ST_THROW or n_steps == 0.
+ * So the count of label k + 1 is that surface's n_in_quad (the ground: ground_n_in_quad) and the mean of round(z * 2^40) over its
+ * pixels is its height less world_z, bit for bit.  Quirk Q6: a ground whose front edge is not found is reported as the all-zero
+ * surface (height world_z, quadrilateral zero); label 1 still marks the points the reference averaged for it (those inside the
+ * ground quadrilateral it tested them against: their count and mean are ssd_debug_frame's ground_n_in_quad / ground_mean_z).  An SSD_ST_OVERFLOW frame is labelled as its truncated result reports.
+ * The contracts are those of ssd_enqueue / ssd_enqueue_depth / ssd_process_host / ssd_process_depth_host.  Labels of frame i go
+ * to d_labels + i * label_stride_bytes (label_stride_bytes >= W * H); bytes past W * H of a stride and frames past nframes are
+ * not written.  They are complete when ssd_fetch / ssd_fetch_back of the batch returns (and for a stream made to wait with
+ * ssd_stream_wait).  The host variants fill labels[nframes * W * H] (pinned or pageable) and return when all of it is there.
+ * A handle that never asks for labels allocates and launches nothing for them. */
+#define SSD_LABEL_NONE 0   /* label k + 1 = the point counts toward surface k of the frame's ssd_frame_result */
+int ssd_enqueue_labels(ssd_handle *h, const void *d_xyz, size_t frame_stride_bytes, int nframes, void *stream,
+                       uint8_t *d_labels, size_t label_stride_bytes);
+int ssd_enqueue_depth_labels(ssd_handle *h, const void *d_depth, size_t frame_stride_bytes, int nframes, void *stream,
+                             uint8_t *d_labels, size_t label_stride_bytes);
+int ssd_process_host_labels(ssd_handle *h, const float *xyz, int nframes, ssd_frame_result *results, uint8_t *labels);
+int ssd_process_depth_host_labels(ssd_handle *h, const uint16_t *depth, int nframes, ssd_frame_result *results, uint8_t *labels);
+
 /* stage selector for profiling / roofline measurement: runs only the chosen stage(s) of the pipeline */
 #define SSD_STAGE_HIST 1       /* K1: transform + crop + bin + histogram */
 #define SSD_STAGE_PEAKS 2
@@ -288,6 +314,8 @@ int ssd_get_stage_times_back(ssd_handle *h, int back, float ms[7]);
 /* single-pass batches (section "Batches" below) run one kernel in front of the seven stages, k_predict: its time for the same enqueue
  * (0 when the enqueue did not run it) */
 int ssd_get_predict_time_back(ssd_handle *h, int back, float *ms);
+/* the label kernel's time for the same enqueue (0 when that enqueue wrote no labels) */
+int ssd_get_labels_time_back(ssd_handle *h, int back, float *ms);
 
 /* Stairs::serialize(): returns the text length, or SSD_E_CAP. A frame whose status has SSD_ST_THROW
  * serialises to the empty string (the reference process terminates instead of printing). */

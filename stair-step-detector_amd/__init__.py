@@ -148,6 +148,7 @@ EXPORTS = [
     "ssd_device_sync", "ssd_host_alloc", "ssd_host_free", "ssd_device_info_get", "ssd_bind_thread_to_device",
     "ssd_pipeline_create", "ssd_pipeline_destroy", "ssd_pipeline_submit", "ssd_pipeline_submit_after", "ssd_pipeline_next", "ssd_pipeline_pending", "ssd_pipeline_set_timing", "ssd_pipeline_stage_times",
     "ssd_pipeline_last_error",
+    "ssd_enqueue_labels", "ssd_enqueue_depth_labels", "ssd_process_host_labels", "ssd_process_depth_host_labels", "ssd_get_labels_time_back",
 ]
 # libssd_source.so — the frame source standing in for the camera (include/ssd_source.h)
 SOURCE_EXPORTS = [
@@ -205,6 +206,11 @@ def lib():
     L.ssd_get_stage_times.argtypes = [vp, C.POINTER(C.c_float)]
     L.ssd_get_stage_times_back.argtypes = [vp, i32, C.POINTER(C.c_float)]
     L.ssd_get_predict_time_back.argtypes = [vp, i32, C.POINTER(C.c_float)]
+    L.ssd_enqueue_labels.argtypes = [vp, vp, sz, i32, vp, vp, sz]
+    L.ssd_enqueue_depth_labels.argtypes = [vp, vp, sz, i32, vp, vp, sz]
+    L.ssd_process_host_labels.argtypes = [vp, vp, i32, C.POINTER(FrameResult), vp]
+    L.ssd_process_depth_host_labels.argtypes = [vp, vp, i32, C.POINTER(FrameResult), vp]
+    L.ssd_get_labels_time_back.argtypes = [vp, i32, C.POINTER(C.c_float)]
     L.ssd_serialize.argtypes = [C.POINTER(FrameResult), C.c_char_p, sz]
     L.ssd_set_debug.argtypes = [vp, i32]
     L.ssd_get_debug.argtypes = [vp, i32, C.POINTER(DebugFrame)]
@@ -468,6 +474,45 @@ class Detector:
     def enqueue(self, d_ptr, nframes, stride_bytes=None, stream=None, stages=STAGE_ALL):
         _check(lib().ssd_enqueue_stages(self._h, C.c_void_p(d_ptr), stride_bytes or self.frame_bytes, nframes,
                                         C.c_void_p(stream or 0), stages))
+
+    def enqueue_labels(self, d_ptr, nframes, d_labels, label_stride=None, stride_bytes=None, stream=None):
+        """ssd_enqueue plus per-pixel surface labels: frame i's W*H uint8 labels at d_labels + i*label_stride (default W*H),
+        complete when fetch() of this batch returns (include/ssd_hip.h: label k + 1 = surface k of the result, 0 = none)"""
+        _check(lib().ssd_enqueue_labels(self._h, C.c_void_p(d_ptr), stride_bytes or self.frame_bytes, nframes, C.c_void_p(stream or 0),
+                                        C.c_void_p(d_labels), label_stride or self.cfg.width * self.cfg.height))
+
+    def enqueue_depth_labels(self, d_ptr, nframes, d_labels, label_stride=None, stride_bytes=None, stream=None):
+        """ssd_enqueue_depth plus per-pixel surface labels (as enqueue_labels)"""
+        _check(lib().ssd_enqueue_depth_labels(self._h, C.c_void_p(d_ptr), stride_bytes or self.cfg.width * self.cfg.height * 2, nframes,
+                                              C.c_void_p(stream or 0), C.c_void_p(d_labels), label_stride or self.cfg.width * self.cfg.height))
+
+    def process_host_labels(self, xyz):
+        """process_host plus labels: -> (list of FrameResult, uint8 array [n, H, W])"""
+        a = np.ascontiguousarray(xyz, dtype=np.float32)
+        n = a.size // (self.cfg.width * self.cfg.height * 3)
+        if n * self.cfg.width * self.cfg.height * 3 != a.size or n < 1:
+            raise SsdError("process_host_labels: array does not hold whole frames")
+        res = (FrameResult * n)()
+        labels = np.empty((n, self.cfg.height, self.cfg.width), dtype=np.uint8)
+        _check(lib().ssd_process_host_labels(self._h, a.ctypes.data_as(C.c_void_p), n, res, labels.ctypes.data_as(C.c_void_p)))
+        return list(res), labels
+
+    def process_depth_host_labels(self, depth):
+        """process_depth_host plus labels: -> (list of FrameResult, uint8 array [n, H, W])"""
+        a = np.ascontiguousarray(depth, dtype=np.uint16)
+        n = a.size // (self.cfg.width * self.cfg.height)
+        if n * self.cfg.width * self.cfg.height != a.size or n < 1:
+            raise SsdError("process_depth_host_labels: array does not hold whole frames")
+        res = (FrameResult * n)()
+        labels = np.empty((n, self.cfg.height, self.cfg.width), dtype=np.uint8)
+        _check(lib().ssd_process_depth_host_labels(self._h, a.ctypes.data_as(C.c_void_p), n, res, labels.ctypes.data_as(C.c_void_p)))
+        return list(res), labels
+
+    def labels_time_ms(self, back=0):
+        """Device time of the label kernel of the enqueue `back` calls ago (0.0: it wrote no labels); timing must be on."""
+        ms = C.c_float(0.0)
+        _check(lib().ssd_get_labels_time_back(self._h, back, C.byref(ms)))
+        return float(ms.value)
 
     def fetch(self, nframes, stream=None, back=0):
         """Waits for the last enqueue (back = 1: the one before it, so that the next batch can already be running) and

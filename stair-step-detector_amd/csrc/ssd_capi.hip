@@ -574,6 +574,14 @@ int ssd_destroy(ssd_handle *h)
   if(h->dDebugImg) (void)hipFree(h->dDebugImg);
   for(hipEvent_t e : h->evPredict)
     if(e) (void)hipEventDestroy(e);
+  for(hipEvent_t e : h->evLabels)
+    (void)hipEventDestroy(e);
+  for(int k = 0; k < 2; k++)
+  {
+    if(h->labelStage[k]) (void)hipFree(h->labelStage[k]);
+    if(h->labelsCopied[k]) (void)hipEventDestroy(h->labelsCopied[k]);
+  }
+  if(h->labelsCopy) (void)hipStreamDestroy(h->labelsCopy);
   for(hipEvent_t e : h->ev)
     (void)hipEventDestroy(e);
   delete h;
@@ -820,7 +828,8 @@ static int choose_chunk(const ssd_tuning &tune, int nPoints, int nframes)
 }
 
 static constexpr int kDirectResultFrames = 64;
-static int enqueue_impl(ssd_handle *h, const void *d_xyz, size_t frame_stride_bytes, int nframes, void *stream, int stages, bool depthInput)
+static int enqueue_impl(ssd_handle *h, const void *d_xyz, size_t frame_stride_bytes, int nframes, void *stream, int stages, bool depthInput,
+                        unsigned char *labels = nullptr, size_t labelStride = 0)
 {
   if(!h || !d_xyz)
     return fail(SSD_E_ARG, "ssd_enqueue: null argument");
@@ -937,6 +946,25 @@ static int enqueue_impl(ssd_handle *h, const void *d_xyz, size_t frame_stride_by
   h->predictTimed[h->enqueueCount % SSD_TIMING_SLOTS] = planeImg != nullptr;
   const bool timing = h->timing && !h->ev.empty();
   const int timingSlot = static_cast<int>(h->enqueueCount % SSD_TIMING_SLOTS);
+  if(labels && timing && h->evLabels.empty())
+  {
+    /* the label kernel's events, on the first timed enqueue that labels */
+    std::vector<hipEvent_t> ev;
+    for(int i = 0; i < 2 * SSD_TIMING_SLOTS; i++)
+    {
+      hipEvent_t e;
+      const hipError_t rc = hipEventCreate(&e);
+      if(rc != hipSuccess)
+      {
+        for(hipEvent_t made : ev)
+          (void)hipEventDestroy(made);
+        return fail(SSD_E_HIP, std::string("hipEventCreate (labels): ") + hipGetErrorString(rc));
+      }
+      ev.push_back(e);
+    }
+    h->evLabels.swap(ev);
+  }
+  h->labelsTimed[timingSlot] = labels != nullptr && timing;
   int evi = timingSlot * 8;
 
   const int slot = static_cast<int>(h->finalCount % static_cast<unsigned long long>(h->nSlots));
@@ -985,6 +1013,13 @@ static int enqueue_impl(ssd_handle *h, const void *d_xyz, size_t frame_stride_by
         launch_risers(xyz, strideFloats, P, L.dState, L.dTileMasks, h->tileMaskStride, h->dRisers, nframes, chunk, depth, cs);
     }
     mk();
+    /* per-pixel labels: behind the seven stages (and their timing), in front of the batch's completion event */
+    if(labels)
+    {
+      if(marks) (void)hipEventRecord(h->evLabels[2 * timingSlot], cs);
+      launch_labels(xyz, strideFloats, P, L.dState, L.dTileMasks, h->tileMaskStride, nframes, chunk, depth, labels, labelStride, cs);
+      if(marks) (void)hipEventRecord(h->evLabels[2 * timingSlot + 1], cs);
+    }
   };
 
   /* (A call of a few frames replayed from a captured HIP graph — one submission instead of seven launches — was measured in
@@ -1067,6 +1102,31 @@ int ssd_enqueue_depth(ssd_handle *h, const void *d_depth, size_t frame_stride_by
   return enqueue_impl(h, d_depth, frame_stride_bytes, nframes, stream, SSD_STAGE_ALL, true);
 }
 
+static int check_labels_dest(const ssd_handle *h, const char *who, const uint8_t *d_labels, size_t label_stride_bytes)
+{
+  if(!h || !d_labels)
+    return fail(SSD_E_ARG, std::string(who) + ": null argument");
+  if(label_stride_bytes < static_cast<size_t>(h->P.nPoints))
+    return fail(SSD_E_ARG, std::string(who) + ": label stride smaller than width * height");
+  return SSD_OK;
+}
+
+int ssd_enqueue_labels(ssd_handle *h, const void *d_xyz, size_t frame_stride_bytes, int nframes, void *stream,
+                       uint8_t *d_labels, size_t label_stride_bytes)
+{
+  const int rc = check_labels_dest(h, "ssd_enqueue_labels", d_labels, label_stride_bytes);
+  if(rc) return rc;
+  return enqueue_impl(h, d_xyz, frame_stride_bytes, nframes, stream, SSD_STAGE_ALL, false, d_labels, label_stride_bytes);
+}
+
+int ssd_enqueue_depth_labels(ssd_handle *h, const void *d_depth, size_t frame_stride_bytes, int nframes, void *stream,
+                             uint8_t *d_labels, size_t label_stride_bytes)
+{
+  const int rc = check_labels_dest(h, "ssd_enqueue_depth_labels", d_labels, label_stride_bytes);
+  if(rc) return rc;
+  return enqueue_impl(h, d_depth, frame_stride_bytes, nframes, stream, SSD_STAGE_ALL, true, d_labels, label_stride_bytes);
+}
+
 /* rs2::pointcloud's maps (librealsense2 src/proc/pointcloud.cpp, pre_compute_x_y_map), float arithmetic */
 static void depth_maps(const ssd_intrinsics &in, int W, int H, std::vector<float> &maps)
 {
@@ -1147,6 +1207,24 @@ int ssd_get_predict_time_back(ssd_handle *h, int back, float *ms)
     return SSD_OK;
   HIP_TRY(hipEventSynchronize(h->ev[slot * 8 + 7]));
   HIP_TRY(hipEventElapsedTime(ms, h->evPredict[slot], h->ev[slot * 8]));
+  return SSD_OK;
+}
+
+/* k_labels' time for the same enqueue (0 for an enqueue that wrote no labels) */
+int ssd_get_labels_time_back(ssd_handle *h, int back, float *ms)
+{
+  if(!h || !ms)
+    return fail(SSD_E_ARG, "ssd_get_labels_time_back: null");
+  if(!h->timing || h->ev.empty() || back < 0 || back >= SSD_TIMING_SLOTS ||
+     h->enqueueCount < static_cast<unsigned long long>(back) + 1 || h->enqueueCount - 1 - back < h->timedFrom)
+    return fail(SSD_E_ARG, "ssd_get_labels_time_back: no timed enqueue at that position");
+  HIP_TRY(hipSetDevice(h->device));
+  const int slot = static_cast<int>((h->enqueueCount - 1 - back) % SSD_TIMING_SLOTS);
+  *ms = 0.0f;
+  if(!h->labelsTimed[slot] || h->evLabels.empty())
+    return SSD_OK;
+  HIP_TRY(hipEventSynchronize(h->evLabels[2 * slot + 1]));
+  HIP_TRY(hipEventElapsedTime(ms, h->evLabels[2 * slot], h->evLabels[2 * slot + 1]));
   return SSD_OK;
 }
 
@@ -1244,13 +1322,64 @@ static int ingest_prepare(ssd_handle *h, size_t sliceBytes)
   return SSD_OK;
 }
 
+/* the labels of the host entry points: two device buffers of a slice's labels and the stream that copies them out */
+static int labels_prepare(ssd_handle *h, size_t sliceBytes)
+{
+  if(!h->labelsCopy)
+  {
+    HIP_TRY(hipStreamCreateWithFlags(&h->labelsCopy, hipStreamNonBlocking));
+    for(int k = 0; k < 2; k++)
+      HIP_TRY(hipEventCreateWithFlags(&h->labelsCopied[k], hipEventDisableTiming));
+  }
+  if(h->labelStageCap < sliceBytes)
+  {
+    /* the buffers' users are this handle's: label kernels on its lanes' streams, their copies on labelsCopy */
+    for(int k = 0; k < h->depth; k++)
+      if(h->lane[k].haveLast)
+        HIP_TRY(hipEventSynchronize(h->lane[k].done));
+    HIP_TRY(hipStreamSynchronize(h->labelsCopy));
+    for(int k = 0; k < 2; k++)
+    {
+      if(h->labelStage[k]) (void)hipFree(h->labelStage[k]);
+      h->labelStage[k] = nullptr;
+    }
+    h->labelStageCap = 0;
+    HIP_TRY(hipMalloc(&h->labelStage[0], sliceBytes));
+    HIP_TRY(hipMalloc(&h->labelStage[1], sliceBytes));
+    h->labelStageCap = sliceBytes;
+  }
+  return SSD_OK;
+}
+
 static int process_host_impl(ssd_handle *h, const void *src, size_t srcFrameBytes, size_t devFrameBytes, int nframes,
-                             ssd_frame_result *results, bool depthInput)
+                             ssd_frame_result *results, bool depthInput, unsigned char *labels = nullptr)
 {
   HIP_TRY(hipSetDevice(h->device));
   const int slice = h->F < kIngestFrames ? h->F : kIngestFrames;
   int rc = ingest_prepare(h, static_cast<size_t>(slice) * devFrameBytes);
   if(rc) return rc;
+  const size_t labelBytes = static_cast<size_t>(h->P.nPoints);
+  if(labels)
+  {
+    rc = labels_prepare(h, static_cast<size_t>(slice) * labelBytes);
+    if(rc) return rc;
+  }
+  /* whatever path leaves this call, no copy into the caller's labels is still on its way afterwards */
+  struct CopiesDone
+  {
+    hipStream_t s;
+    ~CopiesDone() { if(s) (void)hipStreamSynchronize(s); }
+  } copiesDone{ labels ? h->labelsCopy : nullptr };
+  /* slice `at` of `n` frames, enqueued `back` enqueues ago, from staging buffer kk to the caller's labels, behind its kernels */
+  auto copyLabels = [&](int kk, int at, int n, int back)
+  {
+    int r = ssd_stream_wait(h, back, h->labelsCopy);
+    if(r) return r;
+    HIP_TRY(hipMemcpyAsync(labels + static_cast<size_t>(at) * labelBytes, h->labelStage[kk], static_cast<size_t>(n) * labelBytes,
+                           hipMemcpyDeviceToHost, h->labelsCopy));
+    HIP_TRY(hipEventRecord(h->labelsCopied[kk], h->labelsCopy));
+    return SSD_OK;
+  };
   const bool risers = h->P.risers && h->dRisers;
   if(risers && h->hRisersBatchCap < nframes)
   {
@@ -1294,7 +1423,10 @@ static int process_host_impl(ssd_handle *h, const void *src, size_t srcFrameByte
                                hipMemcpyHostToDevice, h->ingestCopy));
     HIP_TRY(hipEventRecord(h->ingestCopied[k], h->ingestCopy));
     HIP_TRY(hipStreamWaitEvent(h->ingestCompute, h->ingestCopied[k], 0));
-    rc = enqueue_impl(h, h->ingestBuf[k], devFrameBytes, n, h->ingestCompute, SSD_STAGE_ALL, depthInput);
+    if(labels && c >= 2)
+      HIP_TRY(hipStreamWaitEvent(h->ingestCompute, h->labelsCopied[k], 0));      /* the labels of slice c - 2 have left this buffer */
+    rc = enqueue_impl(h, h->ingestBuf[k], devFrameBytes, n, h->ingestCompute, SSD_STAGE_ALL, depthInput,
+                      labels ? h->labelStage[k] : nullptr, labelBytes);
     if(rc) return rc;
     /* "Consumed" is the end of the slice's kernels — on the stream they ran on (with several workspaces the lane's own; the
      * compute stream itself only orders a slice behind its copy, so the slices of a handle with several workspaces overlap
@@ -1311,6 +1443,11 @@ static int process_host_impl(ssd_handle *h, const void *src, size_t srcFrameByte
       HIP_TRY(hipEventRecord(h->ingestConsumed[k], h->lane[h->lastLane].lastStream));
     if(prevFrames)
     {
+      if(labels)
+      {
+        rc = copyLabels(k ^ 1, prevAt, prevFrames, 1);
+        if(rc) return rc;
+      }
       rc = ssd_fetch_back(h, results + prevAt, prevFrames, 1);
       if(rc) return rc;
     }
@@ -1318,8 +1455,15 @@ static int process_host_impl(ssd_handle *h, const void *src, size_t srcFrameByte
     prevAt = done;
     done += n;
   }
+  if(labels)
+  {
+    rc = copyLabels((c - 1) & 1, prevAt, prevFrames, 0);
+    if(rc) return rc;
+  }
   rc = ssd_fetch_back(h, results + prevAt, prevFrames, 0);
   if(rc) return rc;
+  if(labels)
+    HIP_TRY(hipStreamSynchronize(h->labelsCopy));
   h->hRisersBatchFrames = risers ? nframes : 0;
   return SSD_OK;
 }
@@ -1340,6 +1484,24 @@ int ssd_process_depth_host(ssd_handle *h, const uint16_t *depth, int nframes, ss
     return fail(SSD_E_ARG, "ssd_process_depth_host: call ssd_set_intrinsics first");
   const size_t frameElems = (static_cast<size_t>(h->P.nPoints) + 3) / 4 * 4;       /* device stride kept a multiple of 8 bytes */
   return process_host_impl(h, depth, static_cast<size_t>(h->P.nPoints) * 2, frameElems * 2, nframes, results, true);
+}
+
+int ssd_process_host_labels(ssd_handle *h, const float *xyz, int nframes, ssd_frame_result *results, uint8_t *labels)
+{
+  if(!h || !xyz || !results || !labels || nframes < 1)
+    return fail(SSD_E_ARG, "ssd_process_host_labels: bad argument");
+  const size_t frameBytes = static_cast<size_t>(h->P.nPoints) * 12;
+  return process_host_impl(h, xyz, frameBytes, frameBytes, nframes, results, false, labels);
+}
+
+int ssd_process_depth_host_labels(ssd_handle *h, const uint16_t *depth, int nframes, ssd_frame_result *results, uint8_t *labels)
+{
+  if(!h || !depth || !results || !labels || nframes < 1)
+    return fail(SSD_E_ARG, "ssd_process_depth_host_labels: bad argument");
+  if(!h->haveIntr)
+    return fail(SSD_E_ARG, "ssd_process_depth_host_labels: call ssd_set_intrinsics first");
+  const size_t frameElems = (static_cast<size_t>(h->P.nPoints) + 3) / 4 * 4;
+  return process_host_impl(h, depth, static_cast<size_t>(h->P.nPoints) * 2, frameElems * 2, nframes, results, true, labels);
 }
 
 /* pinned host memory for frames (DMA without a staging copy) */

@@ -107,6 +107,13 @@ struct ssd_handle
   std::vector<hipEvent_t> ev;     /* kTimingSlots x 8 */
   hipEvent_t evPredict[SSD_TIMING_SLOTS] = {};   /* recorded in front of k_predict (single-pass enqueues) */
   bool predictTimed[SSD_TIMING_SLOTS] = {};
+  /* per-pixel labels (ssd_enqueue_labels & co.): made on first use, so a handle that never labels holds none of them */
+  std::vector<hipEvent_t> evLabels;          /* SSD_TIMING_SLOTS x 2: around k_labels of a timed enqueue */
+  bool labelsTimed[SSD_TIMING_SLOTS] = {};
+  unsigned char *labelStage[2] = { nullptr, nullptr };   /* ssd_process_*_host_labels: a slice's labels, double-buffered */
+  size_t labelStageCap = 0;                 /* bytes per buffer */
+  hipStream_t labelsCopy = nullptr;         /* their copies to the host */
+  hipEvent_t labelsCopied[2] = { nullptr, nullptr };
   unsigned long long enqueueCount = 0;
   unsigned long long timedFrom = 0;
 };

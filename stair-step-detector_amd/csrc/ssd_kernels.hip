@@ -3274,6 +3274,130 @@ struct InquadLds
   int stripMax[kMaxGroundStrips];               /* FrameState::groundStripMax as the block found it, raised by its own centre-column pixels */
 };
 
+/* The per-point decision of k_inquad and k_labels, for one point slot of the wave: the live quadrilateral of the point's height bin
+ * (q; kMaxLive = none) and whether the point counts.  LABELS = false (k_inquad): a ground point inside the ground quadrilateral, a
+ * tread point outside its tread's; LABELS = true (k_labels): a point inside the quadrilateral of its bin, ground and treads alike.
+ * Also d (the point on K1's grid), M / M3 (the magnitudes the bounds use), mSlow (the lanes that went through the doubles) and
+ * mGround (the lanes whose bin is the ground's), which k_inquad's ground raster reads after it. */
+template<bool CHECKS, bool LABELS>
+__device__ __forceinline__ void quad_decide(const F3 &p, const PreXY &Q, const f32x2 c3xy, const float zc3, const float zh0,
+                                            const QuadEdgesF *edges, const unsigned char *lut, const QuadTest *qts, const K1Consts &kc,
+                                            const int gSlot, f32x2 &dOut, float &MOut, float &M3Out, unsigned int &qOut,
+                                            unsigned long long &mSlowOut, unsigned long long &mCountOut, unsigned long long &mGroundOut)
+{
+  /* Round 6: every decision in single precision first, as K1 takes them (ssd_prexy.h) - the x / y range, the z range and the
+   * height bin, then the quadrilateral as four half-planes on the same d (ssd_quadtest.h, build_quad_edges) - and kept as the
+   * wave's lane masks; the reference's doubles - all three rows, the compares, the bin, QuadrilateralTest with its box, map and
+   * segments - only for the points within a bound of a limit, a bin edge or a quadrilateral's edge: one wave-uniform block, a wave
+   * slot in twenty.  (Until here that test ran for every point of every cell an edge passes through, nested and divergent:
+   * 169 vector instructions per point slot, two thirds of the kernel - profiles/r06_k4_ground_kernel.txt.) */
+  const unsigned long long mValid = __ballot(p.z > 0.0f);
+  f32x2 d = pre_xy(Q, c3xy, p.x, p.y, p.z);
+  const float M = absmax2(d.x, d.y);
+  unsigned long long mInxy = __ballot(M < Q.lo);
+  unsigned long long mMaybexy = ~__ballot(M > Q.hi);
+  const float M3 = absmax3(p.x, p.y, p.z);
+  if constexpr(CHECKS)
+  {
+    /* (the rare configurations' tests, as K1's: launch_inquad picks the instantiation) */
+#if defined(SSD_SABOTAGE_PRE) && (SSD_SABOTAGE_PRE & 16)
+    const unsigned long long mFar = 0ull;
+#else
+    const unsigned long long mFar = Q.checkInput ? ~__ballot(M3 <= Q.maxInput) : 0ull;
+#endif
+    mInxy &= ~mFar;
+    mMaybexy |= mFar;
+  }
+  const float t = __builtin_fmaf(Q.zc[0], p.x, __builtin_fmaf(Q.zc[1], p.y, __builtin_fmaf(Q.zc[2], p.z, zc3)));
+  const float g = __builtin_amdgcn_fractf(t) - 0.5f;
+  const float h = __builtin_fmaf(M3, Q.zNegK, zh0);
+  unsigned long long mSurez = __ballot(__builtin_fabsf(g) < h);
+  const unsigned long long mInz = __ballot(__float_as_uint(t) < Q.zTopBits);
+  if constexpr(CHECKS)
+  {
+#if defined(SSD_SABOTAGE_PRE) && (SSD_SABOTAGE_PRE & 8)
+    if(false)
+#else
+    if(Q.zCheckTop)
+#endif
+      mSurez &= __ballot(__builtin_fabsf(t - Q.zTop) > 0.5f - h);
+  }
+#if defined(SSD_SABOTAGE_PRE) && (SSD_SABOTAGE_PRE & 1)
+  mSurez = ~0ull;
+#endif
+#if defined(SSD_SABOTAGE_PRE) && (SSD_SABOTAGE_PRE & 32)   /* tools: k_labels alone keeps the single-precision bin inside the bin band */
+  if(LABELS)
+    mSurez = ~0ull;
+#endif
+  const unsigned int b = cvt_u32_f32(t);
+  const unsigned long long mInSure = mValid & mInz & mInxy & mSurez;
+  unsigned long long mSlow = mValid & mMaybexy & (~mSurez | (mInz & ~mInxy));
+  /* the bin's quadrilateral (row kMaxLive: none) and its four edges on d */
+  unsigned int q = kMaxLive;
+  if(__builtin_amdgcn_inverse_ballot_w64(mInSure))
+    q = SSD_CHK(28, b, kMaxBins) ? lut[b] : kMaxLive;
+  const unsigned long long mLive = __ballot(q != static_cast<unsigned int>(kMaxLive));
+  const QuadEdgesF &E = edges[q];
+  const float4 gx = *reinterpret_cast<const float4 *>(E.gx), gy = *reinterpret_cast<const float4 *>(E.gy), g2 = *reinterpret_cast<const float4 *>(E.g2);
+  f32x2 e01 = __builtin_elementwise_fma(f32x2{ gx.x, gx.y }, f32x2{ d.x, d.x }, f32x2{ g2.x, g2.y });
+  f32x2 e23 = __builtin_elementwise_fma(f32x2{ gx.z, gx.w }, f32x2{ d.x, d.x }, f32x2{ g2.z, g2.w });
+  e01 = __builtin_elementwise_fma(f32x2{ gy.x, gy.y }, f32x2{ d.y, d.y }, e01);
+  e23 = __builtin_elementwise_fma(f32x2{ gy.z, gy.w }, f32x2{ d.y, d.y }, e23);
+  const float emin = min3_f32(e01.x, e01.y, min_f32(e23.x, e23.y));
+  const float hq = __builtin_fmaf(M3, Q.dK, E.m);              /* infinity for the row "none" and for a quadrilateral single precision does not serve */
+  /* (Measured and not kept: a flag on the list for the cells that lie wholly inside their quadrilaterals - the ground's interior,
+   * 58 % of the cells walked - and a wave-uniform branch around these twelve instructions: 0.62 -> 0.70 ms, the branch costs more
+   * than it skips.) */
+#if defined(SSD_SABOTAGE_PRE) && (SSD_SABOTAGE_PRE & 4)   /* tools: the band along the edges NOT handed to the doubles - the tests built for it must fail */
+  const unsigned long long mSureQ = mLive;
+#elif defined(SSD_SABOTAGE_PRE) && (SSD_SABOTAGE_PRE & 32)  /* tools: k_labels alone keeps the half-planes' answer inside the quadrilateral band */
+  const unsigned long long mSureQ = LABELS ? mLive : __ballot(__builtin_fabsf(emin) > hq);
+#else
+  const unsigned long long mSureQ = __ballot(__builtin_fabsf(emin) > hq);
+#endif
+  const unsigned long long mOutQ = __ballot(emin < 0.0f);
+  unsigned long long mGround = __ballot(q == static_cast<unsigned int>(gSlot));
+  /* k_inquad: for the ground the points inside its quadrilateral count, for treads the points outside theirs (k_raster summed
+   * the plateau whole); k_labels: the points inside, ground and treads alike */
+  unsigned long long mCount = mSureQ & (LABELS ? ~mOutQ : (mGround ^ mOutQ));
+  mSlow |= mLive & ~mSureQ;
+  if(__builtin_expect(mSlow != 0ull, 0))
+  {
+    /* rare, wave-uniform so that the masks stay scalars: the reference's arithmetic, all of it, for the lanes it is for */
+    const K1ConstsLds c = k1_consts(kc);
+    const double x = p.x, y = p.y, z = p.z;
+    double wx = (c->a[0] * x + c->a[1] * y) + c->a[2] * z;
+    double wy = (c->a[3] * x + c->a[4] * y) + c->a[5] * z;
+    double wz = (c->a[6] * x + c->a[7] * y) + c->a[8] * z;
+    wx = wx + c->b[0];
+    wy = wy + c->b[1];
+    wz = wz + c->b[2];
+    const bool mine = __builtin_amdgcn_inverse_ballot_w64(mSlow);
+    const bool inRange = (wx > c->xMin) & (wx < c->xMax) & (wy > c->yMin) & (wy < c->yMax) & (wz > c->zMin) & (wz < c->zMax);
+    unsigned int qD = kMaxLive;
+    bool counts = false;
+    if(mine && inRange)
+    {
+      const int bD = static_cast<int>((wz - c->zMin) * c->recip);                       /* height_bin */
+      qD = SSD_CHK(29, bD, kMaxBins) ? lut[bD] : kMaxLive;
+      if(qD != static_cast<unsigned int>(kMaxLive))
+      {
+        const QuadTest &tq = qts[qD];
+        const bool fast = wx >= tq.fx0 && wx < tq.fx1 && wy >= tq.fy0 && wy < tq.fy1;
+        const bool inside = fast || quad_test(tq, wx, wy);
+        counts = LABELS ? inside : inside == (qD == static_cast<unsigned int>(gSlot));
+      }
+    }
+    mCount = (mCount & ~mSlow) | __ballot(counts);
+    mGround = (mGround & ~mSlow) | __ballot(qD == static_cast<unsigned int>(gSlot));
+    q = mine ? qD : q;
+    d.x = mine ? static_cast<float>((wx - c->xMin) * c->boxX * 0.00390625 - 0.5) : d.x;      /* D rounded once: inside PreXY::dE0 */
+    d.y = mine ? static_cast<float>((wy - c->yMin) * c->boxY * 0.00390625 - 0.5) : d.y;
+  }
+  dOut = d; MOut = M; M3Out = M3; qOut = q;
+  mSlowOut = mSlow; mCountOut = mCount; mGroundOut = mGround;
+}
+
 template<int SRC, bool FULL, bool CHECKS>
 __device__ __forceinline__ void inquad_block(InquadLds<FULL> &L, const float *__restrict__ xyz, size_t strideFloats, const PointParams &P,
                                              const PreXY &Q, const PixelParams &X, FrameState *__restrict__ st,
@@ -3506,107 +3630,11 @@ __device__ __forceinline__ void inquad_block(InquadLds<FULL> &L, const float *__
     {
       key[j] = kNoPixel;
       const F3 p{ v[j].x, v[j].y, v[j].z };
-      /* Round 6: every decision in single precision first, as K1 takes them (ssd_prexy.h) - the x / y range, the z range and the
-       * height bin, then the quadrilateral as four half-planes on the same d (ssd_quadtest.h, build_quad_edges) - and kept as the
-       * wave's lane masks; the reference's doubles - all three rows, the compares, the bin, QuadrilateralTest with its box, map and
-       * segments - only for the points within a bound of a limit, a bin edge or a quadrilateral's edge: one wave-uniform block, a wave
-       * slot in twenty.  (Until here that test ran for every point of every cell an edge passes through, nested and divergent:
-       * 169 vector instructions per point slot, two thirds of the kernel - profiles/r06_k4_ground_kernel.txt.) */
-      const unsigned long long mValid = __ballot(p.z > 0.0f);
-      f32x2 d = pre_xy(Q, c3xy, p.x, p.y, p.z);
-      const float M = absmax2(d.x, d.y);
-      unsigned long long mInxy = __ballot(M < Q.lo);
-      unsigned long long mMaybexy = ~__ballot(M > Q.hi);
-      const float M3 = absmax3(p.x, p.y, p.z);
-      if constexpr(CHECKS)
-      {
-        /* (the rare configurations' tests, as K1's: launch_inquad picks the instantiation) */
-#if defined(SSD_SABOTAGE_PRE) && (SSD_SABOTAGE_PRE & 16)
-        const unsigned long long mFar = 0ull;
-#else
-        const unsigned long long mFar = Q.checkInput ? ~__ballot(M3 <= Q.maxInput) : 0ull;
-#endif
-        mInxy &= ~mFar;
-        mMaybexy |= mFar;
-      }
-      const float t = __builtin_fmaf(Q.zc[0], p.x, __builtin_fmaf(Q.zc[1], p.y, __builtin_fmaf(Q.zc[2], p.z, zc3)));
-      const float g = __builtin_amdgcn_fractf(t) - 0.5f;
-      const float h = __builtin_fmaf(M3, Q.zNegK, zh0);
-      unsigned long long mSurez = __ballot(__builtin_fabsf(g) < h);
-      const unsigned long long mInz = __ballot(__float_as_uint(t) < Q.zTopBits);
-      if constexpr(CHECKS)
-      {
-#if defined(SSD_SABOTAGE_PRE) && (SSD_SABOTAGE_PRE & 8)
-        if(false)
-#else
-        if(Q.zCheckTop)
-#endif
-          mSurez &= __ballot(__builtin_fabsf(t - Q.zTop) > 0.5f - h);
-      }
-#if defined(SSD_SABOTAGE_PRE) && (SSD_SABOTAGE_PRE & 1)
-      mSurez = ~0ull;
-#endif
-      const unsigned int b = cvt_u32_f32(t);
-      const unsigned long long mInSure = mValid & mInz & mInxy & mSurez;
-      unsigned long long mSlow = mValid & mMaybexy & (~mSurez | (mInz & ~mInxy));
-      /* the bin's quadrilateral (row kMaxLive: none) and its four edges on d */
-      unsigned int q = kMaxLive;
-      if(__builtin_amdgcn_inverse_ballot_w64(mInSure))
-        q = SSD_CHK(28, b, kMaxBins) ? lut[b] : kMaxLive;
-      const unsigned long long mLive = __ballot(q != static_cast<unsigned int>(kMaxLive));
-      const QuadEdgesF &E = L.edges[q];
-      const float4 gx = *reinterpret_cast<const float4 *>(E.gx), gy = *reinterpret_cast<const float4 *>(E.gy), g2 = *reinterpret_cast<const float4 *>(E.g2);
-      f32x2 e01 = __builtin_elementwise_fma(f32x2{ gx.x, gx.y }, f32x2{ d.x, d.x }, f32x2{ g2.x, g2.y });
-      f32x2 e23 = __builtin_elementwise_fma(f32x2{ gx.z, gx.w }, f32x2{ d.x, d.x }, f32x2{ g2.z, g2.w });
-      e01 = __builtin_elementwise_fma(f32x2{ gy.x, gy.y }, f32x2{ d.y, d.y }, e01);
-      e23 = __builtin_elementwise_fma(f32x2{ gy.z, gy.w }, f32x2{ d.y, d.y }, e23);
-      const float emin = min3_f32(e01.x, e01.y, min_f32(e23.x, e23.y));
-      const float hq = __builtin_fmaf(M3, Q.dK, E.m);              /* infinity for the row "none" and for a quadrilateral single precision does not serve */
-      /* (Measured and not kept: a flag on the list for the cells that lie wholly inside their quadrilaterals - the ground's interior,
-       * 58 % of the cells walked - and a wave-uniform branch around these twelve instructions: 0.62 -> 0.70 ms, the branch costs more
-       * than it skips.) */
-#if defined(SSD_SABOTAGE_PRE) && (SSD_SABOTAGE_PRE & 4)   /* tools: the band along the edges NOT handed to the doubles - the tests built for it must fail */
-      const unsigned long long mSureQ = mLive;
-#else
-      const unsigned long long mSureQ = __ballot(__builtin_fabsf(emin) > hq);
-#endif
-      const unsigned long long mOutQ = __ballot(emin < 0.0f);
-      unsigned long long mGround = __ballot(q == static_cast<unsigned int>(gSlot));
-      /* ground: the points inside its quadrilateral count; treads: the points outside theirs (k_raster summed the plateau whole) */
-      unsigned long long mCount = mSureQ & (mGround ^ mOutQ);
-      mSlow |= mLive & ~mSureQ;
-      if(__builtin_expect(mSlow != 0ull, 0))
-      {
-        /* rare, wave-uniform so that the masks stay scalars: the reference's arithmetic, all of it, for the lanes it is for */
-        const K1ConstsLds c = k1_consts(L.kc);
-        const double x = p.x, y = p.y, z = p.z;
-        double wx = (c->a[0] * x + c->a[1] * y) + c->a[2] * z;
-        double wy = (c->a[3] * x + c->a[4] * y) + c->a[5] * z;
-        double wz = (c->a[6] * x + c->a[7] * y) + c->a[8] * z;
-        wx = wx + c->b[0];
-        wy = wy + c->b[1];
-        wz = wz + c->b[2];
-        const bool mine = __builtin_amdgcn_inverse_ballot_w64(mSlow);
-        const bool inRange = (wx > c->xMin) & (wx < c->xMax) & (wy > c->yMin) & (wy < c->yMax) & (wz > c->zMin) & (wz < c->zMax);
-        unsigned int qD = kMaxLive;
-        bool counts = false;
-        if(mine && inRange)
-        {
-          const int bD = static_cast<int>((wz - c->zMin) * c->recip);                       /* height_bin */
-          qD = SSD_CHK(29, bD, kMaxBins) ? lut[bD] : kMaxLive;
-          if(qD != static_cast<unsigned int>(kMaxLive))
-          {
-            const QuadTest &tq = qts[qD];
-            const bool fast = wx >= tq.fx0 && wx < tq.fx1 && wy >= tq.fy0 && wy < tq.fy1;
-            counts = (fast || quad_test(tq, wx, wy)) == (qD == static_cast<unsigned int>(gSlot));
-          }
-        }
-        mCount = (mCount & ~mSlow) | __ballot(counts);
-        mGround = (mGround & ~mSlow) | __ballot(qD == static_cast<unsigned int>(gSlot));
-        q = mine ? qD : q;
-        d.x = mine ? static_cast<float>((wx - c->xMin) * c->boxX * 0.00390625 - 0.5) : d.x;      /* D rounded once: inside PreXY::dE0 */
-        d.y = mine ? static_cast<float>((wy - c->yMin) * c->boxY * 0.00390625 - 0.5) : d.y;
-      }
+      f32x2 d;
+      float M, M3;
+      unsigned int q;
+      unsigned long long mSlow, mCount, mGround;
+      quad_decide<CHECKS, false>(p, Q, c3xy, zc3, zh0, L.edges, lut, qts, L.kc, gSlot, d, M, M3, q, mSlow, mCount, mGround);
       if(__builtin_amdgcn_inverse_ballot_w64(mCount))
       {
         /* calcAverageZ's summand in the reference's doubles (world_z_flat's row) */
@@ -3772,6 +3800,150 @@ __global__ __launch_bounds__(kThreads, FULL ? 4 : SSD_K4_WAVES) void k_inquad(co
   const int nChunks = static_cast<int>(gridDim.y), first = max(1, nChunks / 8), by = static_cast<int>(blockIdx.y);
   const int chunkIdx = by < first ? nChunks - 1 - by : by - first;
   inquad_block<SRC, FULL, CHECKS>(L, xyz, strideFloats, P, Q, X, st, groundImg, tileMasks, tileMaskStride, chunkPoints, D, blockIdx.x, chunkIdx);
+}
+
+/* ========================================================================= */
+/* K7 (extension): per-pixel surface labels                                    */
+
+/* Label of point i of a frame (= camera pixel v W + u): k + 1 if the point is one of those whose mean is surface k of the frame's
+ * result (ground first, then the valid steps ascending: k_final's order), else 0 (include/ssd_hip.h, SSD_LABEL_NONE).  That is
+ * k_inquad's decision taken for every point of a live quadrilateral's bins: quad_decide<.., true>.  Runs after k_final (it reads
+ * the frame's status) on the same FrameState; writes every byte of [0, W H) of the frame's row once, nothing else. */
+struct LabelsLds
+{
+  QuadTest qts[kMaxLive];                       /* as InquadLds */
+  QuadEdgesF edges[kMaxLive + 1];
+  K1Consts kc;
+  unsigned char lut[kMaxBins];                  /* bin -> live slot, kMaxLive = none */
+  unsigned char label[kMaxLive + 1];            /* live slot -> label (the surface's place in the result + 1); row kMaxLive: 0 */
+  unsigned short cellList[kMaxCellsPerBlock];
+  unsigned int listScratch[2 * kWavesPerBlock];
+};
+
+/* four labels of the points idx .. idx + 3 (idx a multiple of 4): one 32-bit store where the row is 4-byte aligned and whole */
+__device__ __forceinline__ void store_labels4(unsigned char *__restrict__ row, bool aligned4, int idx, int nPoints, unsigned int word)
+{
+  if(aligned4 && idx + 4 <= nPoints)
+    *reinterpret_cast<unsigned int *>(row + idx) = word;
+  else
+  {
+#pragma unroll
+    for(int k = 0; k < 4; k++)
+      if(idx + k < nPoints)
+        row[idx + k] = static_cast<unsigned char>(word >> (8 * k));
+  }
+}
+
+template<int SRC, bool CHECKS>
+__global__ __launch_bounds__(kThreads) void k_labels(const float *__restrict__ xyz, size_t strideFloats, PointParams P, PreXY Q,
+                                                     const FrameState *__restrict__ st, const uint2 *__restrict__ tileMasks,
+                                                     size_t tileMaskStride, int chunkPoints, DepthSrc D,
+                                                     unsigned char *__restrict__ labels, size_t labelStride)
+{
+  __shared__ LabelsLds L;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int frame = blockIdx.x;
+  const FrameState &fs = st[frame];
+  /* nothing of a frame k_quads found no live quadrilateral in, or whose quadrilaterals the reference would have thrown on, is labelled */
+  const bool live = fs.anyActive != 0u && (fs.status & SSD_ST_THROW) == 0u;           /* block-uniform */
+  const unsigned int wanted = live ? fs.wantedQuads : 0u;
+  if(live)
+  {
+    const int nLive = fs.nLive;
+    const int gSlot = (nLive > 0 && fs.accActive[kGroundAcc]) ? nLive - 1 : -1;       /* the ground is the last live slot */
+    if(tid < kMaxBins)
+    {
+      const unsigned char s = fs.lutLive[tid];
+      L.lut[tid] = s == 0xff ? static_cast<unsigned char>(kMaxLive) : s;
+    }
+    if(tid <= kMaxLive)
+    {
+      /* slot order = accumulator order (treads ascending, the ground last); the result has the ground first */
+      int lab = 0;
+      if(tid < nLive)
+        lab = tid == gSlot ? 1 : tid + 1 + (gSlot >= 0 ? 1 : 0);
+      L.label[tid] = static_cast<unsigned char>(lab <= SSD_MAX_STEPS ? lab : 0);
+    }
+    constexpr int qtWords = kMaxLive * static_cast<int>(sizeof(QuadTest) / 4);
+    constexpr int egWords = kMaxLive * static_cast<int>(sizeof(QuadEdgesF) / 4);
+    for(int w = tid; w < qtWords; w += kThreads)
+      reinterpret_cast<unsigned int *>(L.qts)[w] = reinterpret_cast<const unsigned int *>(fs.qtLive)[w];
+    /* as k_inquad: m (word 12) with PreXY::dE0 folded in; the row behind the live ones answers "not for sure" to everything */
+    for(int w = tid; w < egWords + 16; w += kThreads)
+    {
+      const float e = w < egWords ? reinterpret_cast<const float *>(fs.edgeLive)[w] : 0.0f;
+      reinterpret_cast<float *>(L.edges)[w] = w < egWords ? ((w & 15) == 12 ? e + Q.dE0 : e) : ((w & 15) == 12 ? INFINITY : 0.0f);
+    }
+    if(tid == 0)
+    {
+      K1Consts &c = L.kc;
+      for(int i = 0; i < 9; i++)
+        c.a[i] = P.a[i];
+      c.b[0] = P.b[0]; c.b[1] = P.b[1]; c.b[2] = P.b[2];
+      c.xMin = P.xMin; c.xMax = P.xMax; c.yMin = P.yMin; c.yMax = P.yMax; c.zMin = P.zMin; c.zMax = P.zMax;
+      c.boxX = P.boxX; c.boxY = P.boxY;
+      c.recip = P.recip;
+      c.xToImage = 0.0; c.yToImage = 0.0;
+    }
+  }
+  __syncthreads();
+
+  const float *base = SRC == kSrcDepth16
+    ? reinterpret_cast<const float *>(reinterpret_cast<const unsigned short *>(xyz) + static_cast<size_t>(frame) * strideFloats)
+    : xyz + static_cast<size_t>(frame) * strideFloats;
+  unsigned char *row = labels + static_cast<size_t>(frame) * labelStride;
+  const int begin = blockIdx.y * chunkPoints;
+  const int end = min(begin + chunkPoints, P.nPoints);
+  const int cell0 = begin / kCell;
+  const int nCells = (end - begin + kCell - 1) / kCell;
+  const uint2 *cells = tileMasks + static_cast<size_t>(frame) * tileMaskStride + cell0;
+
+  /* the cells that hold no bin of a live quadrilateral: zeros, without a look at their points (16 bytes a lane where the row allows) */
+  const bool aligned16 = (reinterpret_cast<uintptr_t>(row) & 15u) == 0;
+  constexpr int kUnits = kCell / 16;
+  for(int u = tid; u < nCells * kUnits; u += kThreads)
+  {
+    const int c = u / kUnits;
+    if((cells[c].x & wanted) != 0u)
+      continue;
+    const int idx = (cell0 + c) * kCell + 16 * (u - c * kUnits);
+    if(aligned16 && idx + 16 <= P.nPoints)
+      *reinterpret_cast<uint4 *>(row + idx) = make_uint4(0u, 0u, 0u, 0u);
+    else
+      for(int k = 0; k < 16 && idx + k < P.nPoints; k++)
+        row[idx + k] = 0;
+  }
+  if(wanted == 0u)
+    return;
+
+  /* the others, in order (one column of cells: the list is the chunk's cells ascending), four cells per wave iteration */
+  const int count = cell_list_build(cells, nCells, 1, [&](const uint2 info) { return (info.x & wanted) != 0u; }, L.cellList, L.listScratch);
+  const bool aligned4 = (reinterpret_cast<uintptr_t>(row) & 3u) == 0;
+  float zc3 = Q.zc[3], zh0 = Q.zH0;
+  f32x2 c3xy = f32x2{ Q.c[3][0], Q.c[3][1] };
+  asm volatile("" : "+v"(zc3), "+v"(zh0), "+v"(c3xy));
+  const int nGroups = (count + 3) >> 2;
+  const int gEnd = ((tid >> 6) + 1) * nGroups / kWavesPerBlock;
+  for(int g = (tid >> 6) * nGroups / kWavesPerBlock; g < gEnd; g++)
+  {
+    const int entry = 4 * g + (lane >> 4);
+    F3 v[kPts];
+    load_cell<SRC>(base, cell0, L.cellList, entry, count, lane, P.nPoints, v, D);
+    unsigned int word = 0u;
+#pragma unroll
+    for(int j = 0; j < kPts; j++)
+    {
+      f32x2 d;
+      float M, M3;
+      unsigned int q;
+      unsigned long long mSlow, mIn, mGround;
+      quad_decide<CHECKS, true>(v[j], Q, c3xy, zc3, zh0, L.edges, L.lut, L.qts, L.kc, -1, d, M, M3, q, mSlow, mIn, mGround);
+      const unsigned int lab = __builtin_amdgcn_inverse_ballot_w64(mIn) ? L.label[min(q, static_cast<unsigned int>(kMaxLive))] : 0u;
+      word |= lab << (8 * j);
+    }
+    if(entry < count)
+      store_labels4(row, aligned4, (cell0 + static_cast<int>(L.cellList[entry])) * kCell + kPts * (lane & 15), P.nPoints, word);
+  }
 }
 
 /* ========================================================================= */
@@ -4484,6 +4656,30 @@ void launch_final(const Params &P, FrameState *st, unsigned long long *groundImg
     hipLaunchKernelGGL(k_final<kImgThreadsFew>, dim3(nframes), dim3(kImgThreadsFew), 0, s, P, st, groundImg, results, dbg, dbgImg);
   else
     hipLaunchKernelGGL(k_final<kImgThreadsBatch>, dim3(nframes), dim3(kImgThreadsBatch), 0, s, P, st, groundImg, results, dbg, dbgImg);
+}
+void launch_labels(const float *xyz, size_t strideFloats, const Params &P, const FrameState *st, const uint2 *tileMasks, size_t tileMaskStride,
+                   int nframes, int chunkPoints, const DepthSrc *depth, unsigned char *labels, size_t labelStride, hipStream_t s)
+{
+  dim3 grid(nframes, chunks_for(P.nPoints, chunkPoints));
+  const int src = depth ? kSrcDepth16 : aligned16(xyz, strideFloats, P.nPoints) ? kSrcF3Aligned : kSrcF3;
+  const DepthSrc D = depth ? *depth : DepthSrc{};
+#define SSD_LAUNCH_LABELS(SRC, CHECKS) \
+  hipLaunchKernelGGL((k_labels<SRC, CHECKS>), grid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.pre, st, tileMasks, tileMaskStride, chunkPoints, D, labels, labelStride)
+  /* the instantiations of launch_inquad: the rare configurations' per-point tests only where the configuration needs them */
+  const bool checks = P.pre.checkInput != 0 || P.pre.zCheckTop != 0;
+  if(checks)
+  {
+    if(src == kSrcDepth16) SSD_LAUNCH_LABELS(kSrcDepth16, true);
+    else if(src == kSrcF3Aligned) SSD_LAUNCH_LABELS(kSrcF3Aligned, true);
+    else SSD_LAUNCH_LABELS(kSrcF3, true);
+  }
+  else
+  {
+    if(src == kSrcDepth16) SSD_LAUNCH_LABELS(kSrcDepth16, false);
+    else if(src == kSrcF3Aligned) SSD_LAUNCH_LABELS(kSrcF3Aligned, false);
+    else SSD_LAUNCH_LABELS(kSrcF3, false);
+  }
+#undef SSD_LAUNCH_LABELS
 }
 void launch_risers(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, const uint2 *tileMasks, size_t tileMaskStride,
                    ssd_frame_risers *out, int nframes, int chunkPoints, const DepthSrc *depth, hipStream_t s)
