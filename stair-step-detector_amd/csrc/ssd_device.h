@@ -73,7 +73,8 @@ struct PointParams
  * single-precision FMAs, whose distance from the exact value is bounded by `e` for inputs of magnitude <= maxInput: a point
  * with max(|dx|, |dy|) < lo = 0.5 - e is inside whatever the doubles say, one with max(..) > hi = 0.5 + e outside; only the
  * band between them (and inputs beyond maxInput, NaNs) takes the double-precision rows.  d also gives the cells' bounding
- * boxes (grid cell = (d + 0.5 -+ e) * 256).  make_pre_xy() derives the constants and the bound (ssd_capi.hip). */
+ * boxes (grid cell = (d + 0.5 -+ e) * 256).  make_pre_xy() derives the constants and the bound (ssd_prexy.h, called by ssd_capi.hip);
+ * the device code that uses them is ssd_prefilter.h (pre_range, pre_pixel), shared by K1, k_inquad and k_labels. */
 struct PreXY
 {
   float c[4][2];                              /* (d.x, d.y) = c[0] * x + c[1] * y + c[2] * z + c[3], pairs (x row, y row): one packed FMA per input */

@@ -914,54 +914,8 @@ __device__ __forceinline__ void specwin_emit(unsigned long long *ww, SpecMiss &m
 /* The streaming kernels are written as block bodies over an explicit LDS struct, (frame, chunk) given by the caller:
  * the kernels below pass blockIdx (tools and experiments have paired two bodies in one launch: DESIGN.md section 3). */
 
-/* ---- round 5: K1's x / y range test in single precision first (PreXY, ssd_device.h; the bound: ssd_prexy.h) ---- */
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-/* (d.x, d.y): the point's world x / y, centred on the measuring range and divided by its extent - three packed FMAs */
-__device__ __forceinline__ f32x2 pre_xy(const PreXY &Q, const f32x2 c3, float x, float y, float z)
-{
-  f32x2 d = __builtin_elementwise_fma(f32x2{ Q.c[2][0], Q.c[2][1] }, f32x2{ z, z }, c3);
-  d = __builtin_elementwise_fma(f32x2{ Q.c[1][0], Q.c[1][1] }, f32x2{ y, y }, d);
-  d = __builtin_elementwise_fma(f32x2{ Q.c[0][0], Q.c[0][1] }, f32x2{ x, x }, d);
-  return d;
-}
-/* single instructions with |.| on the operands (as builtins the compiler canonicalises fmaxf's operands first: v_max x, x) */
-__device__ __forceinline__ float absmax2(float a, float b)
-{
-  float r;
-  asm("v_max_f32 %0, |%1|, |%2|" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-__device__ __forceinline__ float absmax3(float a, float b, float c)
-{
-  float r;
-  asm("v_max3_f32 %0, |%1|, |%2|, |%3|" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-  return r;
-}
-/* truncating conversion that saturates (negative and NaN: 0) instead of being undefined */
-__device__ __forceinline__ unsigned int cvt_u32_f32(float a)
-{
-  unsigned int r;
-  asm("v_cvt_u32_f32 %0, %1" : "=v"(r) : "v"(a));
-  return r;
-}
-__device__ __forceinline__ float min3_f32(float a, float b, float c)
-{
-  float r;
-  asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-  return r;
-}
-__device__ __forceinline__ float min_f32(float a, float b)
-{
-  float r;
-  asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-__device__ __forceinline__ float max_f32(float a, float b)
-{
-  float r;
-  asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
+#include "ssd_prefilter.h"   /* the per-point pre-filter: pre_range, the doubles' rows from K1Consts, pre_pixel, the edge table */
+
 /* the cell's five reductions over the 16 lanes of a DPP row (groups: OR; the box: two minima, two maxima of the lanes' d), in one
  * block of twenty instructions behind a two-cycle no-op, the five chains interleaved so that no DPP operand is read within two instructions of its write
  * (the wait states the hardware asks for; the compiler does not see into the block) */
@@ -1016,28 +970,6 @@ struct SpecLds
   unsigned long long ltot[kMaxPlanes][8];        /* sum of round(z * 2^40) per plane (this block's share) */
 };
 struct NoSpecLds {};
-
-/* The constants of K1's seldom-run piece - the double-precision x / y rows of a point the pre-filter cannot call - live in LDS,
- * copied there once per block: as kernel arguments of the plain k_hist they would sit in scalar registers through the whole
- * point loop for one lane in thousands (with them the loop's own constants were spilled and came back through a dozen
- * v_readlane per point). */
-struct K1Consts
-{
-  double a[9], b[3];                              /* CameraToWorld, all three rows */
-  double xMin, xMax, yMin, yMax, zMin, zMax;
-  double boxX, boxY;
-  double recip;
-  double xToImage, yToImage;                      /* SPEC: Projection2D, for the candidate whose pixel single precision cannot call */
-};
-/* the address of the block's copy, opaque to the compiler at every use: loads from it stay where they are written (hoisted
- * out of the point loop they would occupy thirty-two vector registers for its whole length) */
-typedef const K1Consts __attribute__((address_space(3))) *K1ConstsLds;
-__device__ __forceinline__ K1ConstsLds k1_consts(const K1Consts &c)
-{
-  K1ConstsLds p = (K1ConstsLds)(&c);
-  asm volatile("" : "+v"(p));
-  return p;
-}
 
 struct HistLds
 {
@@ -1099,18 +1031,7 @@ __device__ __forceinline__ void hist_block(HistLds &L, SPECLDS &SL, const float 
   if(tid == 0)
   {
     lNonZero = 0;
-    K1Consts &c = L.kc;
-#pragma unroll
-    for(int i = 0; i < 9; i++)
-      c.a[i] = P.a[i];
-    c.b[0] = P.b[0]; c.b[1] = P.b[1]; c.b[2] = P.b[2];
-    c.xMin = P.xMin; c.xMax = P.xMax; c.yMin = P.yMin; c.yMax = P.yMax; c.zMin = P.zMin; c.zMax = P.zMax;
-    c.boxX = P.boxX; c.boxY = P.boxY;
-    c.recip = P.recip;
-    if constexpr(SPEC)
-    {
-      c.xToImage = X.xToImage; c.yToImage = X.yToImage;
-    }
+    k1_consts_fill(L.kc, P, SPEC ? &X : nullptr);
   }
   __syncthreads();
 
@@ -1119,18 +1040,11 @@ __device__ __forceinline__ void hist_block(HistLds &L, SPECLDS &SL, const float 
   int it = 0;
   int nStore = -1;                                                    /* cell records to store (STRIPS), else it * kCellsPerTile */
 
-  /* the lane's copies of constants that are the SECOND scalar operand of an instruction (one is allowed): the z row's fourth
-   * coefficient, the threshold's offset, the x / y rows' fourth pair - without them a v_mov per use and point */
-  float zc3 = Q.zc[3], zh0 = Q.zH0;
-  f32x2 c3xy = f32x2{ Q.c[3][0], Q.c[3][1] };
-  asm volatile("" : "+v"(zc3), "+v"(zh0), "+v"(c3xy));
+  const PreLane lc(Q);
 
   /* SPEC: a point of a candidate bin (in range, its bin has plane `plane`): its share of the plane's z sum, its pixel key.
    * projectToBinaryImage (pointcloud.cpp:458-471) for a bin that may turn out a plateau's.  The z sum takes the reference's doubles
-   * (world_point_flat's z row).  The pixel (Projection2D::worldToImage, pointcloud.cpp:79-83) comes from the single-precision d of
-   * the range test where that is certain (round 6, make_pre_pixel()): px = (d.x + 1/2) W and py = (1/2 - d.y) H farther from every
-   * integer than the bound for this point's magnitude truncate to the reference's pixel - and lie inside the image, 0 and W / H
-   * being integers; the others take the reference's rows and pixel in doubles. */
+   * (world_point_flat's z row), the pixel is pre_pixel()'s. */
   auto candidatePoint = [&](const F3 &q, const f32x2 dj, const int plane) -> unsigned int
   {
     if constexpr(!SPEC)
@@ -1140,29 +1054,10 @@ __device__ __forceinline__ void hist_block(HistLds &L, SPECLDS &SL, const float 
     const double x = q.x, y = q.y, z = q.z;
     double wz = (P.a[6] * x + P.a[7] * y) + P.a[8] * z;
     wz = wz + P.b[2];
-    const float px = __builtin_fmaf(dj.x, X.fW, X.fHalfW), py = __builtin_fmaf(dj.y, X.fNegH, X.fHalfH);
-    const f32x2 gg = f32x2{ __builtin_amdgcn_fractf(px), __builtin_amdgcn_fractf(py) } + f32x2{ -0.5f, -0.5f };      /* one packed add */
-    const float hp = __builtin_fmaf(absmax3(q.x, q.y, q.z), X.pxNegK, X.pxH0);
-    unsigned int ix = cvt_u32_f32(px), iy = cvt_u32_f32(py);
-    bool inside = true;
-#if defined(SSD_SABOTAGE_PRE) && (SSD_SABOTAGE_PRE & 2)   /* tools: the band around the pixel edges NOT handed to the doubles */
-    if(false)
-#else
-    if(!(absmax2(gg.x, gg.y) < hp))
-#endif
-    {
-      /* rare: the doubles, and the image's bounds (quirk Q5) */
-      const K1ConstsLds c = k1_consts(L.kc);
-      double wx = (c->a[0] * x + c->a[1] * y) + c->a[2] * z;
-      double wy = (c->a[3] * x + c->a[4] * y) + c->a[5] * z;
-      wx = wx + c->b[0];
-      wy = wy + c->b[1];
-      ix = static_cast<unsigned int>(static_cast<int>((wx - c->xMin) * c->xToImage));
-      iy = static_cast<unsigned int>(static_cast<int>((c->yMax - wy) * c->yToImage));
-      inside = (ix < static_cast<unsigned int>(X.W)) & (iy < static_cast<unsigned int>(X.H));
-      if(!inside && SSD_CHK(14, plane, kMaxPlanes))
-        atomicAdd(&SL.oob[plane], 1u);                   /* quirk Q5 */
-    }
+    int ix, iy;
+    const bool inside = pre_pixel(q, dj, absmax3(q.x, q.y, q.z), X, L.kc, ix, iy);
+    if(!inside && SSD_CHK(14, plane, kMaxPlanes))
+      atomicAdd(&SL.oob[plane], 1u);                     /* quirk Q5 */
     if(plane != curT)
     {
       if(curT >= 0 && SSD_CHK(13, curT, kMaxPlanes))
@@ -1171,7 +1066,7 @@ __device__ __forceinline__ void hist_block(HistLds &L, SPECLDS &SL, const float 
       accT = 0;
     }
     accT += static_cast<unsigned long long>(z_plus_magic_bits(wz));      /* the bits of z + 6144; k_peaks takes the constant's share off (count x kMagicBits) */
-    return inside ? pixel_key(plane, static_cast<int>(iy), static_cast<int>(ix)) : kNoPixel;
+    return inside ? pixel_key(plane, iy, ix) : kNoPixel;
     }
   };
 
@@ -1189,73 +1084,24 @@ __device__ __forceinline__ void hist_block(HistLds &L, SPECLDS &SL, const float 
     for(int j = 0; j < kPts; j++)
     {
       const F3 p{ v[j].x, v[j].y, v[j].z };
-      /* The tests' outcomes are kept as the wave's 64-bit lane masks (one v_cmp each, straight into a scalar register pair) and combined
-       * on the scalar unit; as `bool`s the compiler evaluated two of them in BOTH polarities - a second v_cmp each, 25 M vector
-       * instructions per launch - where one s_andn2 does.  __builtin_amdgcn_inverse_ballot_w64 turns a mask back into the lanes' branch. */
-      /* pointcloud.cpp:143-146, counted per wave on the scalar unit */
-      const unsigned long long mValid = __ballot(p.z > 0.0f);
-      nz += static_cast<unsigned int>(__popcll(mValid));
-      /* x / y in single precision (round 5): inside for sure, outside for sure (M > hi), or the band between them (and NaNs) */
-      f32x2 d = pre_xy(Q, c3xy, p.x, p.y, p.z);
-      const float M = absmax2(d.x, d.y);
-      unsigned long long mInxy = __ballot(M < Q.lo);
-      unsigned long long mMaybexy = ~__ballot(M > Q.hi);
-      const float M3 = absmax3(p.x, p.y, p.z);
-      if constexpr(CHECKS)
-      {
-        /* unless make_pre_xy() showed that larger inputs cannot read "inside" */
-#if defined(SSD_SABOTAGE_PRE) && (SSD_SABOTAGE_PRE & 16)  /* tools: inputs beyond PreXY::maxInput NOT handed to the doubles - the tests built for it must fail */
-        const unsigned long long mFar = 0ull;
-#else
-        const unsigned long long mFar = Q.checkInput ? ~__ballot(M3 <= Q.maxInput) : 0ull;
-#endif
-        mInxy &= ~mFar;
-        mMaybexy |= mFar;
-      }
-      /* z in single precision (round 6, make_pre_z()): t = the height above zMin in bins.  Farther from every integer than the
-       * bound for this point's magnitude: the bin is floor(t) and the z range is 0 < t < zTop, as the doubles would say */
-      const float t = __builtin_fmaf(Q.zc[0], p.x, __builtin_fmaf(Q.zc[1], p.y, __builtin_fmaf(Q.zc[2], p.z, zc3)));
-      const float g = __builtin_amdgcn_fractf(t) - 0.5f;
-      const float h = __builtin_fmaf(M3, Q.zNegK, zh0);
-      unsigned long long mSurez = __ballot(__builtin_fabsf(g) < h);      /* not for a NaN, nor for a magnitude whose bound exceeds half a bin */
-      const unsigned long long mInz = __ballot(__float_as_uint(t) < Q.zTopBits);     /* +0 <= t < zTop on the bits (a negative t has the sign bit) */
-      if constexpr(CHECKS)
-      {
-#if defined(SSD_SABOTAGE_PRE) && (SSD_SABOTAGE_PRE & 8)   /* tools: the band at the top of a z range that ends mid-bin NOT handed to the doubles */
-        if(false)
-#else
-        if(Q.zCheckTop)
-#endif
-          mSurez &= __ballot(__builtin_fabsf(t - Q.zTop) > 0.5f - h);    /* the range's upper end is no bin edge: its own band */
-      }
-#if defined(SSD_SABOTAGE_PRE) && (SSD_SABOTAGE_PRE & 1)   /* tools: the band around the bin edges NOT handed to the doubles - the tests built for it must fail */
-      mSurez = ~0ull;
-#endif
-      unsigned int b = cvt_u32_f32(t);
-      /* in range for sure; or possibly in range - neither test says "outside for sure" - with a test unsure: those take the doubles */
-      const unsigned long long mInSure = mValid & mInz & mInxy & mSurez;
-      const unsigned long long mSlow = mValid & mMaybexy & (~mSurez | (mInz & ~mInxy));
-      unsigned long long mIn = mInSure;
-      if(mSlow != 0ull)
+      const PreRange r = pre_range<CHECKS, false>(p, Q, lc);
+      nz += static_cast<unsigned int>(__popcll(r.mValid));               /* pointcloud.cpp:143-146, counted per wave on the scalar unit */
+      unsigned int b = r.b;
+      f32x2 d = r.d;
+      unsigned long long mIn = r.mInSure;
+      if(r.mSlow != 0ull)
       {
         /* rare (one wave slot in fifty; a wave-uniform branch, so that the mask stays a scalar): the reference's arithmetic, all of it -
          * world_point_flat's rows and compares, height_bin - evaluated by the whole wave, taken by the lanes it is for */
         const K1ConstsLds c = k1_consts(L.kc);
-        const double x = p.x, y = p.y, z = p.z;
-        double wx = (c->a[0] * x + c->a[1] * y) + c->a[2] * z;
-        double wy = (c->a[3] * x + c->a[4] * y) + c->a[5] * z;
-        double wz = (c->a[6] * x + c->a[7] * y) + c->a[8] * z;
-        wx = wx + c->b[0];
-        wy = wy + c->b[1];
-        wz = wz + c->b[2];
-        mIn |= mSlow & __ballot((wx > c->xMin) & (wx < c->xMax) & (wy > c->yMin) & (wy < c->yMax) & (wz > c->zMin) & (wz < c->zMax));
-        const bool mine = __builtin_amdgcn_inverse_ballot_w64(mSlow);
-        const unsigned int bD = static_cast<unsigned int>(static_cast<int>((wz - c->zMin) * c->recip));      /* height_bin; meaningless for a point out of range, as is d */
-        const float dxD = static_cast<float>((wx - c->xMin) * c->boxX * 0.00390625 - 0.5);
-        const float dyD = static_cast<float>((wy - c->yMin) * c->boxY * 0.00390625 - 0.5);
+        const World3 w = world_rows(c, p);
+        mIn |= r.mSlow & __ballot(world_in_range(c, w));
+        const bool mine = __builtin_amdgcn_inverse_ballot_w64(r.mSlow);
+        const unsigned int bD = static_cast<unsigned int>(world_bin(c, w));
+        const f32x2 dD = d_from_world(c, w);
         b = mine ? bD : b;
-        d.x = mine ? dxD : d.x;
-        d.y = mine ? dyD : d.y;
+        d.x = mine ? dD.x : d.x;
+        d.y = mine ? dD.y : d.y;
       }
       if(__builtin_amdgcn_inverse_ballot_w64(mIn))
       {
@@ -1301,7 +1147,7 @@ __device__ __forceinline__ void hist_block(HistLds &L, SPECLDS &SL, const float 
           const int plane = static_cast<int>(planes[j]);
           unsigned int key = kNoPixel;
           if(plane != 0xff)
-            key = candidatePoint(v[j], kKeepD ? dk[j] : pre_xy(Q, c3xy, v[j].x, v[j].y, v[j].z), plane);
+            key = candidatePoint(v[j], kKeepD ? dk[j] : pre_xy(Q, lc.c3xy, v[j].x, v[j].y, v[j].z), plane);
           keys[j] = key;
         }
 #if defined(SSD_ABL) && SSD_ABL == 1                  /* tools: timing without the window (results are wrong) */
@@ -3280,8 +3126,8 @@ struct InquadLds
  * Also d (the point on K1's grid), M / M3 (the magnitudes the bounds use), mSlow (the lanes that went through the doubles) and
  * mGround (the lanes whose bin is the ground's), which k_inquad's ground raster reads after it. */
 template<bool CHECKS, bool LABELS>
-__device__ __forceinline__ void quad_decide(const F3 &p, const PreXY &Q, const f32x2 c3xy, const float zc3, const float zh0,
-                                            const QuadEdgesF *edges, const unsigned char *lut, const QuadTest *qts, const K1Consts &kc,
+__device__ __forceinline__ void quad_decide(const F3 &p, const PreXY &Q, const PreLane lc, const QuadEdgesF *edges,
+                                            const unsigned char *lut, const QuadTest *qts, const K1Consts &kc,
                                             const int gSlot, f32x2 &dOut, float &MOut, float &M3Out, unsigned int &qOut,
                                             unsigned long long &mSlowOut, unsigned long long &mCountOut, unsigned long long &mGroundOut)
 {
@@ -3291,51 +3137,14 @@ __device__ __forceinline__ void quad_decide(const F3 &p, const PreXY &Q, const f
    * segments - only for the points within a bound of a limit, a bin edge or a quadrilateral's edge: one wave-uniform block, a wave
    * slot in twenty.  (Until here that test ran for every point of every cell an edge passes through, nested and divergent:
    * 169 vector instructions per point slot, two thirds of the kernel - profiles/r06_k4_ground_kernel.txt.) */
-  const unsigned long long mValid = __ballot(p.z > 0.0f);
-  f32x2 d = pre_xy(Q, c3xy, p.x, p.y, p.z);
-  const float M = absmax2(d.x, d.y);
-  unsigned long long mInxy = __ballot(M < Q.lo);
-  unsigned long long mMaybexy = ~__ballot(M > Q.hi);
-  const float M3 = absmax3(p.x, p.y, p.z);
-  if constexpr(CHECKS)
-  {
-    /* (the rare configurations' tests, as K1's: launch_inquad picks the instantiation) */
-#if defined(SSD_SABOTAGE_PRE) && (SSD_SABOTAGE_PRE & 16)
-    const unsigned long long mFar = 0ull;
-#else
-    const unsigned long long mFar = Q.checkInput ? ~__ballot(M3 <= Q.maxInput) : 0ull;
-#endif
-    mInxy &= ~mFar;
-    mMaybexy |= mFar;
-  }
-  const float t = __builtin_fmaf(Q.zc[0], p.x, __builtin_fmaf(Q.zc[1], p.y, __builtin_fmaf(Q.zc[2], p.z, zc3)));
-  const float g = __builtin_amdgcn_fractf(t) - 0.5f;
-  const float h = __builtin_fmaf(M3, Q.zNegK, zh0);
-  unsigned long long mSurez = __ballot(__builtin_fabsf(g) < h);
-  const unsigned long long mInz = __ballot(__float_as_uint(t) < Q.zTopBits);
-  if constexpr(CHECKS)
-  {
-#if defined(SSD_SABOTAGE_PRE) && (SSD_SABOTAGE_PRE & 8)
-    if(false)
-#else
-    if(Q.zCheckTop)
-#endif
-      mSurez &= __ballot(__builtin_fabsf(t - Q.zTop) > 0.5f - h);
-  }
-#if defined(SSD_SABOTAGE_PRE) && (SSD_SABOTAGE_PRE & 1)
-  mSurez = ~0ull;
-#endif
-#if defined(SSD_SABOTAGE_PRE) && (SSD_SABOTAGE_PRE & 32)   /* tools: k_labels alone keeps the single-precision bin inside the bin band */
-  if(LABELS)
-    mSurez = ~0ull;
-#endif
-  const unsigned int b = cvt_u32_f32(t);
-  const unsigned long long mInSure = mValid & mInz & mInxy & mSurez;
-  unsigned long long mSlow = mValid & mMaybexy & (~mSurez | (mInz & ~mInxy));
+  const PreRange r = pre_range<CHECKS, LABELS>(p, Q, lc);
+  const float M3 = r.M3;
+  f32x2 d = r.d;
+  unsigned long long mSlow = r.mSlow;
   /* the bin's quadrilateral (row kMaxLive: none) and its four edges on d */
   unsigned int q = kMaxLive;
-  if(__builtin_amdgcn_inverse_ballot_w64(mInSure))
-    q = SSD_CHK(28, b, kMaxBins) ? lut[b] : kMaxLive;
+  if(__builtin_amdgcn_inverse_ballot_w64(r.mInSure))
+    q = SSD_CHK(28, r.b, kMaxBins) ? lut[r.b] : kMaxLive;
   const unsigned long long mLive = __ballot(q != static_cast<unsigned int>(kMaxLive));
   const QuadEdgesF &E = edges[q];
   const float4 gx = *reinterpret_cast<const float4 *>(E.gx), gy = *reinterpret_cast<const float4 *>(E.gy), g2 = *reinterpret_cast<const float4 *>(E.g2);
@@ -3365,36 +3174,32 @@ __device__ __forceinline__ void quad_decide(const F3 &p, const PreXY &Q, const f
   {
     /* rare, wave-uniform so that the masks stay scalars: the reference's arithmetic, all of it, for the lanes it is for */
     const K1ConstsLds c = k1_consts(kc);
-    const double x = p.x, y = p.y, z = p.z;
-    double wx = (c->a[0] * x + c->a[1] * y) + c->a[2] * z;
-    double wy = (c->a[3] * x + c->a[4] * y) + c->a[5] * z;
-    double wz = (c->a[6] * x + c->a[7] * y) + c->a[8] * z;
-    wx = wx + c->b[0];
-    wy = wy + c->b[1];
-    wz = wz + c->b[2];
+    const World3 w = world_rows(c, p);
     const bool mine = __builtin_amdgcn_inverse_ballot_w64(mSlow);
-    const bool inRange = (wx > c->xMin) & (wx < c->xMax) & (wy > c->yMin) & (wy < c->yMax) & (wz > c->zMin) & (wz < c->zMax);
+    const bool inRange = world_in_range(c, w);
     unsigned int qD = kMaxLive;
     bool counts = false;
     if(mine && inRange)
     {
-      const int bD = static_cast<int>((wz - c->zMin) * c->recip);                       /* height_bin */
+      const int bD = world_bin(c, w);
       qD = SSD_CHK(29, bD, kMaxBins) ? lut[bD] : kMaxLive;
       if(qD != static_cast<unsigned int>(kMaxLive))
       {
         const QuadTest &tq = qts[qD];
-        const bool fast = wx >= tq.fx0 && wx < tq.fx1 && wy >= tq.fy0 && wy < tq.fy1;
-        const bool inside = fast || quad_test(tq, wx, wy);
+        const bool fast = w.x >= tq.fx0 && w.x < tq.fx1 && w.y >= tq.fy0 && w.y < tq.fy1;
+        const bool inside = fast || quad_test(tq, w.x, w.y);
         counts = LABELS ? inside : inside == (qD == static_cast<unsigned int>(gSlot));
       }
     }
     mCount = (mCount & ~mSlow) | __ballot(counts);
     mGround = (mGround & ~mSlow) | __ballot(qD == static_cast<unsigned int>(gSlot));
     q = mine ? qD : q;
-    d.x = mine ? static_cast<float>((wx - c->xMin) * c->boxX * 0.00390625 - 0.5) : d.x;      /* D rounded once: inside PreXY::dE0 */
-    d.y = mine ? static_cast<float>((wy - c->yMin) * c->boxY * 0.00390625 - 0.5) : d.y;
+    /* (each component inside its own conditional, as written: taken whole in front of them the wave's rare block costs
+     * k_inquad four more vector registers) */
+    d.x = mine ? d_from_world(c, w).x : d.x;
+    d.y = mine ? d_from_world(c, w).y : d.y;
   }
-  dOut = d; MOut = M; M3Out = M3; qOut = q;
+  dOut = d; MOut = r.M; M3Out = M3; qOut = q;
   mSlowOut = mSlow; mCountOut = mCount; mGroundOut = mGround;
 }
 
@@ -3465,26 +3270,18 @@ __device__ __forceinline__ void inquad_block(InquadLds<FULL> &L, const float *__
     nLive = nLiveG;
     groundSlot = (nLiveG > 0 && groundActive) ? nLiveG - 1 : -1;     /* the ground is the last accumulator */
     L.nextGroup = 0;
-    K1Consts &c = L.kc;
-#pragma unroll
-    for(int i = 0; i < 9; i++)
-      c.a[i] = P.a[i];
-    c.b[0] = P.b[0]; c.b[1] = P.b[1]; c.b[2] = P.b[2];
-    c.xMin = P.xMin; c.xMax = P.xMax; c.yMin = P.yMin; c.yMax = P.yMax; c.zMin = P.zMin; c.zMax = P.zMax;
-    c.boxX = P.boxX; c.boxY = P.boxY;
-    c.recip = P.recip;
-    c.xToImage = X.xToImage; c.yToImage = X.yToImage;
+    k1_consts_fill(L.kc, P, &X);
   }
   if(tid < kMaxBins)
     lut[tid] = lutMine == 0xff ? static_cast<unsigned char>(kMaxLive) : lutMine;      /* bin -> slot of the live table, kMaxLive = nothing to do for this bin */
-  /* the edges for the single-precision test: a row per live quadrilateral, m (word 12) with the bound of d that does not depend on
-   * the point; the row behind them answers "not for sure" to everything - the row of a bin without quadrilateral */
+  /* the edges for the single-precision test: stage_quad_edges() by hand, because the words were asked for above, in the one round
+   * trip with everything else the block reads of the frame */
 #pragma unroll
   for(int k = 0; k < 2; k++)
   {
     const int w = tid + k * kThreads;
     if(w < egWords + 16)
-      reinterpret_cast<float *>(L.edges)[w] = w < egWords ? ((w & 15) == 12 ? edgeMine[k] + Q.dE0 : edgeMine[k]) : ((w & 15) == 12 ? INFINITY : 0.0f);
+      reinterpret_cast<float *>(L.edges)[w] = quad_edge_word(w, egWords, edgeMine[k], Q.dE0);
   }
   if(!FULL && tid < kMaxGroundStrips)
     L.stripMax[tid] = stripMaxMine;
@@ -3606,10 +3403,7 @@ __device__ __forceinline__ void inquad_block(InquadLds<FULL> &L, const float *__
   };
   int g = grab();
   F3 v[kPts], vn[kPts];
-  /* the lane's copies of constants that are the SECOND scalar operand of an instruction (one is allowed), as in K1 */
-  float zc3 = Q.zc[3], zh0 = Q.zH0;
-  f32x2 c3xy = f32x2{ Q.c[3][0], Q.c[3][1] };
-  asm volatile("" : "+v"(zc3), "+v"(zh0), "+v"(c3xy));
+  const PreLane lc(Q);
   /* the coarse test "can the bottom scan see this ground pixel, can it lie outside the image?" on d (see the loop): within two
    * pixels of the border; a row from the strips' first less one on; a column within 3.5 of a strip's centre (strip: 2.5 either
    * side), as the distance of (px + 2 - x0 + 50 - 2.5) / 50 from the nearest integer */
@@ -3634,7 +3428,7 @@ __device__ __forceinline__ void inquad_block(InquadLds<FULL> &L, const float *__
       float M, M3;
       unsigned int q;
       unsigned long long mSlow, mCount, mGround;
-      quad_decide<CHECKS, false>(p, Q, c3xy, zc3, zh0, L.edges, lut, qts, L.kc, gSlot, d, M, M3, q, mSlow, mCount, mGround);
+      quad_decide<CHECKS, false>(p, Q, lc, L.edges, lut, qts, L.kc, gSlot, d, M, M3, q, mSlow, mCount, mGround);
       if(__builtin_amdgcn_inverse_ballot_w64(mCount))
       {
         /* calcAverageZ's summand in the reference's doubles (world_z_flat's row) */
@@ -3667,30 +3461,8 @@ __device__ __forceinline__ void inquad_block(InquadLds<FULL> &L, const float *__
       {
         if(__builtin_amdgcn_inverse_ballot_w64(mPixel))
         {
-          /* the pixel from d where single precision is certain of it (make_pre_pixel(), as K1's candidates: farther from every
-           * pixel edge than the bound for this magnitude - such a pixel lies inside the image), else Projection2D::worldToImage
-           * in doubles with the image's bounds */
-          const float px = __builtin_fmaf(d.x, X.fW, X.fHalfW), py = __builtin_fmaf(d.y, X.fNegH, X.fHalfH);
-          const f32x2 gg = f32x2{ __builtin_amdgcn_fractf(px), __builtin_amdgcn_fractf(py) } + f32x2{ -0.5f, -0.5f };
-          const float hp = __builtin_fmaf(M3, X.pxNegK, X.pxH0);
-          int ix = static_cast<int>(cvt_u32_f32(px)), iy = static_cast<int>(cvt_u32_f32(py));
-          bool inside = true;
-#if defined(SSD_SABOTAGE_PRE) && (SSD_SABOTAGE_PRE & 2)
-          if(false)
-#else
-          if(!(absmax2(gg.x, gg.y) < hp))
-#endif
-          {
-            const K1ConstsLds c = k1_consts(L.kc);
-            const double x = p.x, y = p.y, z = p.z;
-            double wx = (c->a[0] * x + c->a[1] * y) + c->a[2] * z;
-            double wy = (c->a[3] * x + c->a[4] * y) + c->a[5] * z;
-            wx = wx + c->b[0];
-            wy = wy + c->b[1];
-            ix = static_cast<int>((wx - c->xMin) * c->xToImage);
-            iy = static_cast<int>((c->yMax - wy) * c->yToImage);
-            inside = (static_cast<unsigned int>(ix) < static_cast<unsigned int>(X.W)) & (static_cast<unsigned int>(iy) < static_cast<unsigned int>(X.H));
-          }
+          int ix, iy;
+          const bool inside = pre_pixel(p, d, M3, X, L.kc, ix, iy);
           oob += inside ? 0u : 1u;                              /* quirk Q5 */
           if(FULL)
             key[j] = inside ? pixel_key(0, iy, ix) : kNoPixel;
@@ -3868,14 +3640,10 @@ __global__ __launch_bounds__(kThreads) void k_labels(const float *__restrict__ x
     constexpr int egWords = kMaxLive * static_cast<int>(sizeof(QuadEdgesF) / 4);
     for(int w = tid; w < qtWords; w += kThreads)
       reinterpret_cast<unsigned int *>(L.qts)[w] = reinterpret_cast<const unsigned int *>(fs.qtLive)[w];
-    /* as k_inquad: m (word 12) with PreXY::dE0 folded in; the row behind the live ones answers "not for sure" to everything */
-    for(int w = tid; w < egWords + 16; w += kThreads)
-    {
-      const float e = w < egWords ? reinterpret_cast<const float *>(fs.edgeLive)[w] : 0.0f;
-      reinterpret_cast<float *>(L.edges)[w] = w < egWords ? ((w & 15) == 12 ? e + Q.dE0 : e) : ((w & 15) == 12 ? INFINITY : 0.0f);
-    }
+    stage_quad_edges(L.edges, fs.edgeLive, egWords, Q.dE0);
     if(tid == 0)
     {
+      /* k1_consts_fill(L.kc, P, nullptr) spelt out: through the helper this kernel takes 92 scalar registers for 71 */
       K1Consts &c = L.kc;
       for(int i = 0; i < 9; i++)
         c.a[i] = P.a[i];
@@ -3919,9 +3687,7 @@ __global__ __launch_bounds__(kThreads) void k_labels(const float *__restrict__ x
   /* the others, in order (one column of cells: the list is the chunk's cells ascending), four cells per wave iteration */
   const int count = cell_list_build(cells, nCells, 1, [&](const uint2 info) { return (info.x & wanted) != 0u; }, L.cellList, L.listScratch);
   const bool aligned4 = (reinterpret_cast<uintptr_t>(row) & 3u) == 0;
-  float zc3 = Q.zc[3], zh0 = Q.zH0;
-  f32x2 c3xy = f32x2{ Q.c[3][0], Q.c[3][1] };
-  asm volatile("" : "+v"(zc3), "+v"(zh0), "+v"(c3xy));
+  const PreLane lc(Q);
   const int nGroups = (count + 3) >> 2;
   const int gEnd = ((tid >> 6) + 1) * nGroups / kWavesPerBlock;
   for(int g = (tid >> 6) * nGroups / kWavesPerBlock; g < gEnd; g++)
@@ -3937,7 +3703,7 @@ __global__ __launch_bounds__(kThreads) void k_labels(const float *__restrict__ x
       float M, M3;
       unsigned int q;
       unsigned long long mSlow, mIn, mGround;
-      quad_decide<CHECKS, true>(v[j], Q, c3xy, zc3, zh0, L.edges, L.lut, L.qts, L.kc, -1, d, M, M3, q, mSlow, mIn, mGround);
+      quad_decide<CHECKS, true>(v[j], Q, lc, L.edges, L.lut, L.qts, L.kc, -1, d, M, M3, q, mSlow, mIn, mGround);
       const unsigned int lab = __builtin_amdgcn_inverse_ballot_w64(mIn) ? L.label[min(q, static_cast<unsigned int>(kMaxLive))] : 0u;
       word |= lab << (8 * j);
     }
@@ -4494,6 +4260,7 @@ __global__ void k_riser_results(Params P, const FrameState *__restrict__ st, ssd
 /* ========================================================================= */
 /* launchers (declared in ssd_launch.h)                                        */
 #include "ssd_launch.h"
+#include <type_traits>
 
 namespace ssd
 {
@@ -4510,77 +4277,61 @@ static inline bool aligned16(const float *xyz, size_t strideFloats, int nPoints)
 {
   return (reinterpret_cast<uintptr_t>(xyz) & 15u) == 0 && (strideFloats & 3u) == 0 && (nPoints & 3) == 0;
 }
+/* The point source of a launch as a compile-time constant: f(std::integral_constant<int, kSrc...>, the DepthSrc to pass) */
+template<typename F>
+static inline void with_src(const DepthSrc *depth, bool aligned, F f)
+{
+  if(depth)
+    f(std::integral_constant<int, kSrcDepth16>{}, *depth);
+  else if(aligned)
+    f(std::integral_constant<int, kSrcF3Aligned>{}, DepthSrc{});
+  else
+    f(std::integral_constant<int, kSrcF3>{}, DepthSrc{});
+}
+/* a run-time bool as std::true_type / std::false_type */
+template<typename F>
+static inline void with_bool(bool b, F f)
+{
+  if(b)
+    f(std::true_type{});
+  else
+    f(std::false_type{});
+}
+/* The rare configurations' per-point tests (inputs beyond PreXY::maxInput that could read "inside", a z range that does not end on
+ * a bin edge: ssd_prexy.h) live in instantiations of their own: as run-time flags they cost the common one two instructions per point */
+static inline bool needs_checks(const Params &P) { return P.pre.checkInput != 0 || P.pre.zCheckTop != 0; }
+
 
 void launch_predict(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, int nframes, const DepthSrc *depth,
                     int *fallback, int poolPlanes, int sabotage, hipStream_t s)
 {
   dim3 pgrid(nframes, kPredictParts);
-  if(depth)
-    hipLaunchKernelGGL(k_predict<kSrcDepth16>, pgrid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, st, *depth, P.minHeight, sabotage, fallback, poolPlanes);
-  else if(aligned16(xyz, strideFloats, P.nPoints))
-    hipLaunchKernelGGL(k_predict<kSrcF3Aligned>, pgrid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, st, DepthSrc{}, P.minHeight, sabotage, fallback, poolPlanes);
-  else
-    hipLaunchKernelGGL(k_predict<kSrcF3>, pgrid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, st, DepthSrc{}, P.minHeight, sabotage, fallback, poolPlanes);
+  with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &D)
+  {
+    hipLaunchKernelGGL(k_predict<decltype(src)::value>, pgrid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, st, D, P.minHeight, sabotage, fallback, poolPlanes);
+  });
 }
 void launch_hist(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, uint2 *tileMasks, size_t tileMaskStride,
                  int nframes, int chunkPoints, const DepthSrc *depth, unsigned long long *planeImg, hipStream_t s)
 {
   dim3 grid(nframes, chunks_for(P.nPoints, chunkPoints));
-  /* the rare configurations' per-point tests (inputs beyond PreXY::maxInput that could read "inside", a z range that does not end on
-   * a bin edge) live in instantiations of their own: as run-time flags they cost the common one two instructions per point */
-  const bool checks = P.pre.checkInput != 0 || P.pre.zCheckTop != 0;
-  if(planeImg)
+  /* the single pass - a tile a whole number of camera rows: the tile loop keeps every wave in its band of columns; else the sorted strips */
+  const bool strips = planeImg && kTile % P.W != 0;
+  with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &D)
   {
-    /* a tile a whole number of camera rows: the tile loop keeps every wave in its band of columns; else the sorted strips */
-    const bool strips = kTile % P.W != 0;
-#define SSD_LAUNCH_PLANES2(SRC, STRIPS, DEPTH)                                                                                          \
-    if(checks)                                                                                                                             \
-      hipLaunchKernelGGL((k_hist_planes<SRC, STRIPS, true>), grid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.pre, P.px, st, tileMasks, planeImg, tileMaskStride, chunkPoints, DEPTH); \
-    else                                                                                                                                   \
-      hipLaunchKernelGGL((k_hist_planes<SRC, STRIPS, false>), grid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.pre, P.px, st, tileMasks, planeImg, tileMaskStride, chunkPoints, DEPTH);
-#define SSD_LAUNCH_PLANES(SRC, DEPTH)                                                                                                    \
-    if(strips)                                                                                                                             \
-    {                                                                                                                                      \
-      SSD_LAUNCH_PLANES2(SRC, true, DEPTH)                                                                                                 \
-    }                                                                                                                                      \
-    else                                                                                                                                   \
-    {                                                                                                                                      \
-      SSD_LAUNCH_PLANES2(SRC, false, DEPTH)                                                                                                \
-    }
-    if(depth)
+    with_bool(needs_checks(P), [&](auto checks)
     {
-      SSD_LAUNCH_PLANES(kSrcDepth16, *depth)
-    }
-    else if(aligned16(xyz, strideFloats, P.nPoints))
-    {
-      SSD_LAUNCH_PLANES(kSrcF3Aligned, DepthSrc{})
-    }
-    else
-    {
-      SSD_LAUNCH_PLANES(kSrcF3, DepthSrc{})
-    }
-#undef SSD_LAUNCH_PLANES2
-#undef SSD_LAUNCH_PLANES
-    return;
-  }
-#define SSD_LAUNCH_HIST(SRC, DEPTH)                                                                                                      \
-  if(checks)                                                                                                                               \
-    hipLaunchKernelGGL((k_hist<SRC, true>), grid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.pre, st, tileMasks, tileMaskStride, chunkPoints, DEPTH); \
-  else                                                                                                                                     \
-    hipLaunchKernelGGL((k_hist<SRC, false>), grid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.pre, st, tileMasks, tileMaskStride, chunkPoints, DEPTH);
-  if(depth)
-  {
-    SSD_LAUNCH_HIST(kSrcDepth16, *depth)
-  }
-  else if(aligned16(xyz, strideFloats, P.nPoints))
-  {
-    SSD_LAUNCH_HIST(kSrcF3Aligned, DepthSrc{})
-  }
-  else
-  {
-    SSD_LAUNCH_HIST(kSrcF3, DepthSrc{})
-  }
-#undef SSD_LAUNCH_HIST
+      constexpr int SRC = decltype(src)::value;
+      constexpr bool CHECKS = decltype(checks)::value;
+      if(planeImg)
+        with_bool(strips, [&](auto sorted)
+        {
+          hipLaunchKernelGGL((k_hist_planes<SRC, decltype(sorted)::value, CHECKS>), grid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.pre, P.px, st, tileMasks, planeImg, tileMaskStride, chunkPoints, D);
+        });
+      else
+        hipLaunchKernelGGL((k_hist<SRC, CHECKS>), grid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.pre, st, tileMasks, tileMaskStride, chunkPoints, D);
+    });
+  });
 }
 void launch_peaks(const Params &P, FrameState *st, int nframes, DebugFrame *dbg, int *fallback, hipStream_t s)
 {
@@ -4590,21 +4341,13 @@ void launch_raster(const float *xyz, size_t strideFloats, const Params &P, Frame
                    const uint2 *tileMasks, size_t tileMaskStride, int nframes, int chunkPoints, const DepthSrc *depth, const int *fallback, hipStream_t s)
 {
   dim3 grid(fallback ? (nframes + 3) / 4 : nframes, chunks_for(P.nPoints, chunkPoints));
-  const DepthSrc D = depth ? *depth : DepthSrc{};
-#define SSD_LAUNCH_RASTER(SRC)                                                                                                                                           \
-  {                                                                                                                                                                      \
-    if(fallback)                                                                                                                                                         \
-      hipLaunchKernelGGL((k_raster<SRC, true>), grid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.px, st, stepImg, tileMasks, tileMaskStride, chunkPoints, D, fallback); \
-    else                                                                                                                                                                 \
-      hipLaunchKernelGGL((k_raster<SRC, false>), grid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.px, st, stepImg, tileMasks, tileMaskStride, chunkPoints, D, fallback); \
-  }
-  if(depth)
-    SSD_LAUNCH_RASTER(kSrcDepth16)
-  else if(aligned16(xyz, strideFloats, P.nPoints))
-    SSD_LAUNCH_RASTER(kSrcF3Aligned)
-  else
-    SSD_LAUNCH_RASTER(kSrcF3)
-#undef SSD_LAUNCH_RASTER
+  with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &D)
+  {
+    with_bool(fallback != nullptr, [&](auto listed)
+    {
+      hipLaunchKernelGGL((k_raster<decltype(src)::value, decltype(listed)::value>), grid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.px, st, stepImg, tileMasks, tileMaskStride, chunkPoints, D, fallback);
+    });
+  });
 }
 void launch_outline(const Params &P, FrameState *st, unsigned long long *stepImg, unsigned long long *planeImg, int nframes, DebugFrame *dbg, unsigned long long *dbgImg, hipStream_t s)
 {
@@ -4623,32 +4366,18 @@ void launch_inquad(const float *xyz, size_t strideFloats, const Params &P, Frame
                    const uint2 *tileMasks, size_t tileMaskStride, int nframes, int chunkPoints, const DepthSrc *depth, hipStream_t s)
 {
   dim3 grid(nframes, chunks_for(P.nPoints, chunkPoints));
-  const int src = depth ? kSrcDepth16 : aligned16(xyz, strideFloats, P.nPoints) ? kSrcF3Aligned : kSrcF3;
-  const DepthSrc D = depth ? *depth : DepthSrc{};
-#define SSD_LAUNCH_INQUAD(SRC, FULL, CHECKS) \
-  hipLaunchKernelGGL((k_inquad<SRC, FULL, CHECKS>), grid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.pre, P.px, st, groundImg, tileMasks, tileMaskStride, chunkPoints, D)
-  /* the instantiation with the rare configurations' per-point tests (a magnitude test of the input, a z range that does not end on a bin
-   * edge: ssd_prexy.h) only where the configuration needs them; debug capture (the whole ground image) always takes it */
-  const bool checks = P.pre.checkInput != 0 || P.pre.zCheckTop != 0;
+  auto launch = [&](auto full, auto checks)
+  {
+    with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &D)
+    {
+      hipLaunchKernelGGL((k_inquad<decltype(src)::value, decltype(full)::value, decltype(checks)::value>), grid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.pre, P.px, st, groundImg, tileMasks, tileMaskStride, chunkPoints, D);
+    });
+  };
+  /* debug capture (the whole ground image) always takes the instantiation with the rare configurations' tests */
   if(P.px.groundFull)
-  {
-    if(src == kSrcDepth16) SSD_LAUNCH_INQUAD(kSrcDepth16, true, true);
-    else if(src == kSrcF3Aligned) SSD_LAUNCH_INQUAD(kSrcF3Aligned, true, true);
-    else SSD_LAUNCH_INQUAD(kSrcF3, true, true);
-  }
-  else if(checks)
-  {
-    if(src == kSrcDepth16) SSD_LAUNCH_INQUAD(kSrcDepth16, false, true);
-    else if(src == kSrcF3Aligned) SSD_LAUNCH_INQUAD(kSrcF3Aligned, false, true);
-    else SSD_LAUNCH_INQUAD(kSrcF3, false, true);
-  }
+    launch(std::true_type{}, std::true_type{});
   else
-  {
-    if(src == kSrcDepth16) SSD_LAUNCH_INQUAD(kSrcDepth16, false, false);
-    else if(src == kSrcF3Aligned) SSD_LAUNCH_INQUAD(kSrcF3Aligned, false, false);
-    else SSD_LAUNCH_INQUAD(kSrcF3, false, false);
-  }
-#undef SSD_LAUNCH_INQUAD
+    with_bool(needs_checks(P), [&](auto checks) { launch(std::false_type{}, checks); });
 }
 void launch_final(const Params &P, FrameState *st, unsigned long long *groundImg, ssd_frame_result *results, int nframes, DebugFrame *dbg, unsigned long long *dbgImg, hipStream_t s)
 {
@@ -4661,36 +4390,22 @@ void launch_labels(const float *xyz, size_t strideFloats, const Params &P, const
                    int nframes, int chunkPoints, const DepthSrc *depth, unsigned char *labels, size_t labelStride, hipStream_t s)
 {
   dim3 grid(nframes, chunks_for(P.nPoints, chunkPoints));
-  const int src = depth ? kSrcDepth16 : aligned16(xyz, strideFloats, P.nPoints) ? kSrcF3Aligned : kSrcF3;
-  const DepthSrc D = depth ? *depth : DepthSrc{};
-#define SSD_LAUNCH_LABELS(SRC, CHECKS) \
-  hipLaunchKernelGGL((k_labels<SRC, CHECKS>), grid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.pre, st, tileMasks, tileMaskStride, chunkPoints, D, labels, labelStride)
-  /* the instantiations of launch_inquad: the rare configurations' per-point tests only where the configuration needs them */
-  const bool checks = P.pre.checkInput != 0 || P.pre.zCheckTop != 0;
-  if(checks)
+  with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &D)
   {
-    if(src == kSrcDepth16) SSD_LAUNCH_LABELS(kSrcDepth16, true);
-    else if(src == kSrcF3Aligned) SSD_LAUNCH_LABELS(kSrcF3Aligned, true);
-    else SSD_LAUNCH_LABELS(kSrcF3, true);
-  }
-  else
-  {
-    if(src == kSrcDepth16) SSD_LAUNCH_LABELS(kSrcDepth16, false);
-    else if(src == kSrcF3Aligned) SSD_LAUNCH_LABELS(kSrcF3Aligned, false);
-    else SSD_LAUNCH_LABELS(kSrcF3, false);
-  }
-#undef SSD_LAUNCH_LABELS
+    with_bool(needs_checks(P), [&](auto checks)
+    {
+      hipLaunchKernelGGL((k_labels<decltype(src)::value, decltype(checks)::value>), grid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.pre, st, tileMasks, tileMaskStride, chunkPoints, D, labels, labelStride);
+    });
+  });
 }
 void launch_risers(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, const uint2 *tileMasks, size_t tileMaskStride,
                    ssd_frame_risers *out, int nframes, int chunkPoints, const DepthSrc *depth, hipStream_t s)
 {
   dim3 grid(nframes, chunks_for(P.nPoints, chunkPoints));
-  if(depth)
-    hipLaunchKernelGGL(k_risers<kSrcDepth16>, grid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.riserTol, st, tileMasks, tileMaskStride, chunkPoints, P.px.cellCols, *depth);
-  else if(aligned16(xyz, strideFloats, P.nPoints))
-    hipLaunchKernelGGL(k_risers<kSrcF3Aligned>, grid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.riserTol, st, tileMasks, tileMaskStride, chunkPoints, P.px.cellCols, DepthSrc{});
-  else
-    hipLaunchKernelGGL(k_risers<kSrcF3>, grid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.riserTol, st, tileMasks, tileMaskStride, chunkPoints, P.px.cellCols, DepthSrc{});
+  with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &D)
+  {
+    hipLaunchKernelGGL(k_risers<decltype(src)::value>, grid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.riserTol, st, tileMasks, tileMaskStride, chunkPoints, P.px.cellCols, D);
+  });
   hipLaunchKernelGGL(k_riser_results, dim3((nframes + 63) / 64), dim3(64), 0, s, P, st, out, nframes);
 }
 

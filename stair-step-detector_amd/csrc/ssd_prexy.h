@@ -1,6 +1,7 @@
 /*
  * ssd_prexy.h — constants and error bound of K1's single-precision pre-filter of the x / y range test (PreXY, ssd_device.h),
- * as a plain host function: make_params() calls it, the test hook ssd_test_prexy hands it to the tests.
+ * as a plain host function: make_params() calls it, the test hook ssd_test_prexy hands it to the tests.  The device code these
+ * constants are for is ssd_prefilter.h (pre_range, pre_pixel); "K1" below stands for every kernel that calls it.
  *
  * The reference takes a point when its world x and y, computed in doubles (transformation.h:59-64), lie strictly inside the
  * measuring range (pointcloud.cpp:150-165).  Write the exact (real-number) value of the centred, normalised coordinate as

@@ -1,5 +1,5 @@
 """numpy restatement of the single-precision pre-filter that K1 (k_hist, k_hist_planes) and k_inquad run before the reference's
-doubles (csrc/ssd_prexy.h, csrc/ssd_kernels.hip hist_block / inquad_block), shared by tests/test_prexy.py and
+doubles (the constants: csrc/ssd_prexy.h; the device code: csrc/ssd_prefilter.h, pre_range and pre_pixel), shared by tests/test_prexy.py and
 tests/test_gpu_prefilter_regimes.py.
 
 Each FMA is an exact float64 product-and-sum rounded once to float32: the product of two float32 values is exact in float64 and
