@@ -292,6 +292,40 @@ int ssd_enqueue_depth_labels(ssd_handle *h, const void *d_depth, size_t frame_st
 int ssd_process_host_labels(ssd_handle *h, const float *xyz, int nframes, ssd_frame_result *results, uint8_t *labels);
 int ssd_process_depth_host_labels(ssd_handle *h, const uint16_t *depth, int nframes, ssd_frame_result *results, uint8_t *labels);
 
+/* ---- per-frame calibration: batches of frames from many cameras ------------------------------------------------------
+ * EXTENSION.  A handle may hold a table of cameras beside the calibration ssd_create gave it; a cameras
+ * batch names, frame by frame, the camera each frame comes from.  The cameras share the handle's ssd_config (resolution,
+ * measuring range, intervals); what a mounting and a sensor decide varies: CameraToWorld, ToExternalWorld, world_z and, for
+ * 16-bit depth input, the intrinsics.
+ *   ssd_set_cameras     waits for the handle's batches in flight and replaces the table (ncams = 0 frees it).  Each camera's
+ *                       constants are derived exactly as ssd_create / ssd_set_intrinsics derive a handle's.
+ *   ssd_enqueue_cameras as ssd_enqueue (input = SSD_INPUT_VERTICES) or ssd_enqueue_depth (SSD_INPUT_DEPTH16), with labels when
+ *                       d_labels is not NULL; camera_of_frame (HOST memory, nframes entries) is copied during the call.
+ *   ssd_process_host_cameras   as ssd_process_host / ssd_process_depth_host (and their _labels forms).
+ * Contract: frame i's result, labels, risers and debug record are byte for byte those a handle made by
+ * ssd_create(cfg, &cams[camera_of_frame[i]].cal) (with ssd_set_intrinsics(&...intr) for depth input) returns for that frame alone.
+ * Fetching (ssd_fetch, ssd_fetch_back, ssd_stream_wait, ssd_fetch_risers, ssd_get_debug*, the timing getters) is that of any
+ * other batch.  SSD_E_ARG, before anything is launched or copied: no table, an index >= ssd_camera_count, depth input naming a
+ * camera without intrinsics, ncams outside 0 .. SSD_MAX_CAMERAS, a null handle.  ssd_enqueue, ssd_process_host and the rest keep
+ * using ssd_create's calibration whatever the table holds; ssd_enqueue_stages and ssd_pipeline_* take no cameras.  A handle that
+ * never sets cameras allocates and launches nothing for them. */
+#define SSD_MAX_CAMERAS 4096
+#define SSD_INPUT_VERTICES 0
+#define SSD_INPUT_DEPTH16 1
+typedef struct
+{
+  ssd_calibration cal;
+  ssd_intrinsics intr;          /* read when has_intrinsics != 0 */
+  int32_t has_intrinsics;
+  int32_t reserved;
+} ssd_camera;
+int ssd_set_cameras(ssd_handle *h, const ssd_camera *cams, int ncams);
+int ssd_camera_count(const ssd_handle *h);
+int ssd_enqueue_cameras(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream,
+                        const uint16_t *camera_of_frame, int input, uint8_t *d_labels, size_t label_stride_bytes);
+int ssd_process_host_cameras(ssd_handle *h, const void *frames, int nframes, const uint16_t *camera_of_frame, int input,
+                             ssd_frame_result *results, uint8_t *labels);
+
 /* stage selector for profiling / roofline measurement: runs only the chosen stage(s) of the pipeline */
 #define SSD_STAGE_HIST 1       /* K1: transform + crop + bin + histogram */
 #define SSD_STAGE_PEAKS 2

@@ -121,6 +121,15 @@ class Intrinsics(C.Structure):
     _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("ppx", C.c_float), ("ppy", C.c_float), ("depth_units", C.c_float)]
 
 
+class Camera(C.Structure):
+    """ssd_camera: one camera of a handle's table (Detector.set_cameras): its calibration and, for depth input, its intrinsics"""
+    _fields_ = [("cal", Calibration), ("intr", Intrinsics), ("has_intrinsics", C.c_int32), ("reserved", C.c_int32)]
+
+
+MAX_CAMERAS = 4096
+INPUT_VERTICES, INPUT_DEPTH16 = 0, 1
+
+
 class Scene(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32),
                 ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
@@ -149,6 +158,7 @@ EXPORTS = [
     "ssd_pipeline_create", "ssd_pipeline_destroy", "ssd_pipeline_submit", "ssd_pipeline_submit_after", "ssd_pipeline_next", "ssd_pipeline_pending", "ssd_pipeline_set_timing", "ssd_pipeline_stage_times",
     "ssd_pipeline_last_error",
     "ssd_enqueue_labels", "ssd_enqueue_depth_labels", "ssd_process_host_labels", "ssd_process_depth_host_labels", "ssd_get_labels_time_back",
+    "ssd_set_cameras", "ssd_camera_count", "ssd_enqueue_cameras", "ssd_process_host_cameras",
 ]
 # libssd_source.so — the frame source standing in for the camera (include/ssd_source.h)
 SOURCE_EXPORTS = [
@@ -211,6 +221,10 @@ def lib():
     L.ssd_process_host_labels.argtypes = [vp, vp, i32, C.POINTER(FrameResult), vp]
     L.ssd_process_depth_host_labels.argtypes = [vp, vp, i32, C.POINTER(FrameResult), vp]
     L.ssd_get_labels_time_back.argtypes = [vp, i32, C.POINTER(C.c_float)]
+    L.ssd_set_cameras.argtypes = [vp, C.POINTER(Camera), i32]
+    L.ssd_camera_count.argtypes = [vp]
+    L.ssd_enqueue_cameras.argtypes = [vp, vp, sz, i32, vp, C.POINTER(C.c_uint16), i32, vp, sz]
+    L.ssd_process_host_cameras.argtypes = [vp, vp, i32, C.POINTER(C.c_uint16), i32, C.POINTER(FrameResult), vp]
     L.ssd_serialize.argtypes = [C.POINTER(FrameResult), C.c_char_p, sz]
     L.ssd_set_debug.argtypes = [vp, i32]
     L.ssd_get_debug.argtypes = [vp, i32, C.POINTER(DebugFrame)]
@@ -507,6 +521,58 @@ class Detector:
         labels = np.empty((n, self.cfg.height, self.cfg.width), dtype=np.uint8)
         _check(lib().ssd_process_depth_host_labels(self._h, a.ctypes.data_as(C.c_void_p), n, res, labels.ctypes.data_as(C.c_void_p)))
         return list(res), labels
+
+    # ---- per-frame calibration: batches of frames from many cameras (include/ssd_hip.h)
+    def set_cameras(self, cameras):
+        """The handle's camera table: a list of GeometricTransformation, Calibration, (either, Intrinsics) or Camera.  Waits for the
+        batches in flight; an empty list frees the table."""
+        arr = (Camera * max(1, len(cameras)))()
+        for i, c in enumerate(cameras):
+            if isinstance(c, Camera):
+                arr[i] = c
+                continue
+            trans, intr = c if isinstance(c, (tuple, list)) else (c, None)
+            arr[i].cal = trans.constants if isinstance(trans, GeometricTransformation) else trans
+            if intr is not None:
+                arr[i].intr = intr
+                arr[i].has_intrinsics = 1
+        _check(lib().ssd_set_cameras(self._h, arr, len(cameras)))
+
+    @property
+    def camera_count(self):
+        return lib().ssd_camera_count(self._h)
+
+    @staticmethod
+    def _camera_index(camera_of_frame, nframes):
+        idx = np.ascontiguousarray(camera_of_frame, dtype=np.uint16)
+        if idx.ndim != 1 or idx.size != nframes or np.any(np.asarray(camera_of_frame) != idx):
+            raise SsdError("camera_of_frame: one index 0..65535 per frame")
+        return idx
+
+    def enqueue_cameras(self, d_ptr, nframes, camera_of_frame, depth=False, d_labels=None, label_stride=None, stride_bytes=None, stream=None):
+        """ssd_enqueue_cameras: frame i is processed with camera camera_of_frame[i] of the table (the array is copied during the call);
+        depth = 16-bit depth input; d_labels as enqueue_labels.  fetch() and the rest as after any enqueue."""
+        idx = camera_of_frame if isinstance(camera_of_frame, np.ndarray) and camera_of_frame.dtype == np.uint16 and camera_of_frame.flags.c_contiguous \
+            and camera_of_frame.ndim == 1 and camera_of_frame.size == nframes else self._camera_index(camera_of_frame, nframes)
+        frame = self.cfg.width * self.cfg.height * (2 if depth else 12)
+        _check(lib().ssd_enqueue_cameras(self._h, C.c_void_p(d_ptr), stride_bytes or frame, nframes, C.c_void_p(stream or 0),
+                                         idx.ctypes.data_as(C.POINTER(C.c_uint16)), INPUT_DEPTH16 if depth else INPUT_VERTICES,
+                                         C.c_void_p(d_labels or 0), (label_stride or self.cfg.width * self.cfg.height) if d_labels else 0))
+
+    def process_host_cameras(self, frames, camera_of_frame, depth=False, labels=False):
+        """frames on the host (float32 [n, H, W, 3], or uint16 [n, H, W] with depth=True), one camera index per frame
+        -> list of FrameResult, or (list, uint8 labels [n, H, W]) with labels=True"""
+        a = np.ascontiguousarray(frames, dtype=np.uint16 if depth else np.float32) if not isinstance(frames, PinnedArray) else frames.array
+        per = self.cfg.width * self.cfg.height * (1 if depth else 3)
+        n = a.size // per
+        if n * per != a.size or n < 1:
+            raise SsdError("process_host_cameras: array does not hold whole frames")
+        idx = self._camera_index(camera_of_frame, n)
+        res = (FrameResult * n)()
+        lab = np.empty((n, self.cfg.height, self.cfg.width), dtype=np.uint8) if labels else None
+        _check(lib().ssd_process_host_cameras(self._h, a.ctypes.data_as(C.c_void_p), n, idx.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                              INPUT_DEPTH16 if depth else INPUT_VERTICES, res, lab.ctypes.data_as(C.c_void_p) if labels else None))
+        return (list(res), lab) if labels else list(res)
 
     def labels_time_ms(self, back=0):
         """Device time of the label kernel of the enqueue `back` calls ago (0.0: it wrote no labels); timing must be on."""

@@ -550,7 +550,12 @@ int ssd_destroy(ssd_handle *h)
     if(L.in) (void)hipEventDestroy(L.in);
     if(L.done) (void)hipEventDestroy(L.done);
     if(L.stream) (void)hipStreamDestroy(L.stream);
+    if(L.dCamIndex) (void)hipFree(L.dCamIndex);
+    if(L.hCamIndex) (void)hipHostFree(L.hCamIndex);
+    if(L.camCopied) (void)hipEventDestroy(L.camCopied);
   }
+  if(h->dCams) (void)hipFree(h->dCams);
+  if(h->dCamMaps) (void)hipFree(h->dCamMaps);
   if(h->hFallback) (void)hipHostFree(h->hFallback);
   if(h->dDepthMaps) (void)hipFree(h->dDepthMaps);
   if(h->dResults) (void)hipFree(h->dResults);
@@ -828,8 +833,17 @@ static int choose_chunk(const ssd_tuning &tune, int nPoints, int nframes)
 }
 
 static constexpr int kDirectResultFrames = 64;
+static int cameras_upload(ssd_handle *h, unsigned long long key, double tol);
+/* what a call decides for the whole handle and the cameras' device records carry (ssd_handle::camCallKey) */
+static unsigned long long cameras_call_key(const Params &P)
+{
+  return static_cast<unsigned long long>(P.px.groundFull != 0) | static_cast<unsigned long long>(P.risers != 0) << 1
+         | static_cast<unsigned long long>(static_cast<unsigned int>(P.riserMinSupport)) << 2;
+}
+
+/* camOf (host, nframes entries; ssd_enqueue_cameras has checked them): a cameras batch - frame i takes camera camOf[i] of the table */
 static int enqueue_impl(ssd_handle *h, const void *d_xyz, size_t frame_stride_bytes, int nframes, void *stream, int stages, bool depthInput,
-                        unsigned char *labels = nullptr, size_t labelStride = 0)
+                        unsigned char *labels = nullptr, size_t labelStride = 0, const uint16_t *camOf = nullptr)
 {
   if(!h || !d_xyz)
     return fail(SSD_E_ARG, "ssd_enqueue: null argument");
@@ -838,7 +852,7 @@ static int enqueue_impl(ssd_handle *h, const void *d_xyz, size_t frame_stride_by
   const size_t frameBytes = static_cast<size_t>(h->P.nPoints) * (depthInput ? 2 : 12);
   if(depthInput)
   {
-    if(!h->haveIntr)
+    if(!camOf && !h->haveIntr)
       return fail(SSD_E_ARG, "ssd_enqueue_depth: call ssd_set_intrinsics first");
     if(frame_stride_bytes < frameBytes || frame_stride_bytes % 8 != 0 || (reinterpret_cast<uintptr_t>(d_xyz) & 7u) != 0 || h->P.W % 4 != 0)
       return fail(SSD_E_ARG, "ssd_enqueue_depth: frames must be 8-byte aligned, stride a multiple of 8, width a multiple of 4");
@@ -880,6 +894,27 @@ static int enqueue_impl(ssd_handle *h, const void *d_xyz, size_t frame_stride_by
           HIP_TRY(hipStreamWaitEvent(s, h->lane[k].done, 0));
   }
   h->lastPinned = pinned;
+  /* A cameras batch: the index goes through the workspace's pinned slot to its device array, on the batch's stream in front of its
+   * kernels (the caller's array is free when this call returns; the slot is free once the previous copy out of it has run). */
+  CameraSel camSel{};
+  const CameraSel *cams = nullptr;
+  if(camOf)
+  {
+    if(!h->dCams || !L.dCamIndex || !L.hCamIndex || !L.camCopied)
+      return fail(SSD_E_HIP, "ssd_enqueue_cameras: the camera table is incomplete (internal)");
+    if(cameras_call_key(P) != h->camCallKey || P.riserTol != h->camCallTol)
+    {
+      const int rcUp = cameras_upload(h, cameras_call_key(P), P.riserTol);
+      if(rcUp) return rcUp;
+    }
+    HIP_TRY(hipEventSynchronize(L.camCopied));
+    for(int i = 0; i < nframes; i++)
+      L.hCamIndex[i] = camOf[i];
+    HIP_TRY(hipMemcpyAsync(L.dCamIndex, L.hCamIndex, sizeof(int) * static_cast<size_t>(nframes), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(L.camCopied, s));
+    camSel = CameraSel{ h->dCams, L.dCamIndex, h->camsNeedChecks };
+    cams = &camSel;
+  }
   const float *xyz = static_cast<const float *>(d_xyz);
   const size_t strideFloats = depthInput ? frame_stride_bytes / 2 : frame_stride_bytes / 4;    /* elements of the source type */
   const DepthSrc depthSrc{ h->dDepthMaps, h->dDepthMaps ? h->dDepthMaps + P.W : nullptr, h->intr.depth_units, P.W, P.H, depth_row_magic(P.W, P.H) };
@@ -938,7 +973,7 @@ static int enqueue_impl(ssd_handle *h, const void *d_xyz, size_t frame_stride_by
    * fails here, loudly, instead of faulting on the device at a null address */
   if(planeImg && !L.dFallback)
     return fail(SSD_E_HIP, "ssd_enqueue: the single pass's planes without their work list (internal)");
-  if(depthInput && (!depthSrc.xmap || !depthSrc.ymap))
+  if(depthInput && !cams && (!depthSrc.xmap || !depthSrc.ymap))
     return fail(SSD_E_HIP, "ssd_enqueue_depth: the deprojection maps are missing (ssd_set_intrinsics did not complete)");
   if(!L.dState || !L.dStepImg || !L.dGroundImg || !L.dTileMasks)
     return fail(SSD_E_HIP, "ssd_enqueue: the handle's workspace is incomplete (internal)");
@@ -980,26 +1015,26 @@ static int enqueue_impl(ssd_handle *h, const void *d_xyz, size_t frame_stride_by
     {
       /* k_predict in front of the seven stages, timed by itself (ssd_get_predict_time_back) */
       if(marks) (void)hipEventRecord(h->evPredict[timingSlot], cs);
-      launch_predict(xyz, strideFloats, P, L.dState, nframes, depth, L.dFallback, h->planePool, h->singlePassSabotage, cs);
+      launch_predict(xyz, strideFloats, P, L.dState, nframes, depth, L.dFallback, h->planePool, h->singlePassSabotage, cs, cams);
     }
     mk();
     if(stages & SSD_STAGE_HIST)
-      launch_hist(xyz, strideFloats, P, L.dState, L.dTileMasks, h->tileMaskStride, nframes, chunkHist, depth, planeImg, cs);
+      launch_hist(xyz, strideFloats, P, L.dState, L.dTileMasks, h->tileMaskStride, nframes, chunkHist, depth, planeImg, cs, cams);
     mk();
     if(stages & SSD_STAGE_PEAKS)
-      launch_peaks(P, L.dState, nframes, dbg, planeImg ? L.dFallback : nullptr, cs);
+      launch_peaks(P, L.dState, nframes, dbg, planeImg ? L.dFallback : nullptr, cs, cams);
     mk();
     if(stages & SSD_STAGE_RASTER)
-      launch_raster(xyz, strideFloats, P, L.dState, L.dStepImg, L.dTileMasks, h->tileMaskStride, nframes, chunkRaster, depth, planeImg ? L.dFallback : nullptr, cs);
+      launch_raster(xyz, strideFloats, P, L.dState, L.dStepImg, L.dTileMasks, h->tileMaskStride, nframes, chunkRaster, depth, planeImg ? L.dFallback : nullptr, cs, cams);
     mk();
     if(stages & SSD_STAGE_OUTLINE)
-      launch_outline(P, L.dState, L.dStepImg, planeImg, nframes, dbg, dbgImg, cs);
+      launch_outline(P, L.dState, L.dStepImg, planeImg, nframes, dbg, dbgImg, cs, cams);
     mk();
     if(stages & SSD_STAGE_QUADS)
-      launch_quads(P, L.dState, nframes, dbg, cs);
+      launch_quads(P, L.dState, nframes, dbg, cs, cams);
     mk();
     if(stages & SSD_STAGE_INQUAD)
-      launch_inquad(xyz, strideFloats, P, L.dState, L.dGroundImg, L.dTileMasks, h->tileMaskStride, nframes, chunkInquad, depth, cs);
+      launch_inquad(xyz, strideFloats, P, L.dState, L.dGroundImg, L.dTileMasks, h->tileMaskStride, nframes, chunkInquad, depth, cs, cams);
     mk();
     /* The results leave with the batch, into this enqueue's pinned slot (event for ssd_fetch / ssd_fetch_back).  A few frames:
      * k_final stores them there itself — a kilobyte per frame of posted writes, visible to the host once the event has
@@ -1008,16 +1043,16 @@ static int enqueue_impl(ssd_handle *h, const void *d_xyz, size_t frame_stride_by
     if(stages & SSD_STAGE_FINAL)
     {
       ssd_frame_result *out = (direct ? h->hResultsDev : h->dResults) + static_cast<size_t>(slot) * h->F;
-      launch_final(P, L.dState, L.dGroundImg, out, nframes, dbg, dbgImg, cs);
+      launch_final(P, L.dState, L.dGroundImg, out, nframes, dbg, dbgImg, cs, cams);
       if(P.risers)
-        launch_risers(xyz, strideFloats, P, L.dState, L.dTileMasks, h->tileMaskStride, h->dRisers, nframes, chunk, depth, cs);
+        launch_risers(xyz, strideFloats, P, L.dState, L.dTileMasks, h->tileMaskStride, h->dRisers, nframes, chunk, depth, cs, cams);
     }
     mk();
     /* per-pixel labels: behind the seven stages (and their timing), in front of the batch's completion event */
     if(labels)
     {
       if(marks) (void)hipEventRecord(h->evLabels[2 * timingSlot], cs);
-      launch_labels(xyz, strideFloats, P, L.dState, L.dTileMasks, h->tileMaskStride, nframes, chunk, depth, labels, labelStride, cs);
+      launch_labels(xyz, strideFloats, P, L.dState, L.dTileMasks, h->tileMaskStride, nframes, chunk, depth, labels, labelStride, cs, cams);
       if(marks) (void)hipEventRecord(h->evLabels[2 * timingSlot + 1], cs);
     }
   };
@@ -1352,7 +1387,7 @@ static int labels_prepare(ssd_handle *h, size_t sliceBytes)
 }
 
 static int process_host_impl(ssd_handle *h, const void *src, size_t srcFrameBytes, size_t devFrameBytes, int nframes,
-                             ssd_frame_result *results, bool depthInput, unsigned char *labels = nullptr)
+                             ssd_frame_result *results, bool depthInput, unsigned char *labels = nullptr, const uint16_t *camOf = nullptr)
 {
   HIP_TRY(hipSetDevice(h->device));
   const int slice = h->F < kIngestFrames ? h->F : kIngestFrames;
@@ -1426,7 +1461,7 @@ static int process_host_impl(ssd_handle *h, const void *src, size_t srcFrameByte
     if(labels && c >= 2)
       HIP_TRY(hipStreamWaitEvent(h->ingestCompute, h->labelsCopied[k], 0));      /* the labels of slice c - 2 have left this buffer */
     rc = enqueue_impl(h, h->ingestBuf[k], devFrameBytes, n, h->ingestCompute, SSD_STAGE_ALL, depthInput,
-                      labels ? h->labelStage[k] : nullptr, labelBytes);
+                      labels ? h->labelStage[k] : nullptr, labelBytes, camOf ? camOf + done : nullptr);     /* a slice takes its part of the index */
     if(rc) return rc;
     /* "Consumed" is the end of the slice's kernels — on the stream they ran on (with several workspaces the lane's own; the
      * compute stream itself only orders a slice behind its copy, so the slices of a handle with several workspaces overlap
@@ -1502,6 +1537,199 @@ int ssd_process_depth_host_labels(ssd_handle *h, const uint16_t *depth, int nfra
     return fail(SSD_E_ARG, "ssd_process_depth_host_labels: call ssd_set_intrinsics first");
   const size_t frameElems = (static_cast<size_t>(h->P.nPoints) + 3) / 4 * 4;
   return process_host_impl(h, depth, static_cast<size_t>(h->P.nPoints) * 2, frameElems * 2, nframes, results, true, labels);
+}
+
+/* ---- per-frame calibration: the camera table (include/ssd_hip.h) ------------------------------- */
+
+static void cameras_free(ssd_handle *h)
+{
+  for(int k = 0; k < kMaxLanes; k++)
+  {
+    ssd_lane &L = h->lane[k];
+    if(L.dCamIndex) (void)hipFree(L.dCamIndex);
+    if(L.hCamIndex) (void)hipHostFree(L.hCamIndex);
+    if(L.camCopied) (void)hipEventDestroy(L.camCopied);
+    L.dCamIndex = nullptr; L.hCamIndex = nullptr; L.camCopied = nullptr;
+  }
+  if(h->dCams) (void)hipFree(h->dCams);
+  if(h->dCamMaps) (void)hipFree(h->dCamMaps);
+  h->dCams = nullptr; h->dCamMaps = nullptr;
+  h->camParams.clear(); h->camHasIntr.clear(); h->camDepthUnits.clear();
+  h->camsNeedChecks = false;
+  h->camCallKey = ~0ull;
+  h->bytes -= h->camBytes;
+  h->camBytes = 0;
+}
+
+/* The device records: each camera's Params as make_params() made them, with what a call decides for the whole handle (as
+ * enqueue_impl does to its copy of the handle's Params), and the camera's DepthSrc.  Batches in flight read the table: they finish first. */
+static int cameras_upload(ssd_handle *h, unsigned long long key, double tol)
+{
+  for(int k = 0; k < h->depth; k++)
+    if(h->lane[k].haveLast)
+      HIP_TRY(hipEventSynchronize(h->lane[k].done));
+  const size_t n = h->camParams.size();
+  std::vector<CameraRec> recs(n);
+  const int W = h->P.W, H = h->P.H;
+  for(size_t i = 0; i < n; i++)
+  {
+    CameraRec &R = recs[i];
+    std::memset(&R, 0, sizeof(R));
+    R.P = h->camParams[i];
+    R.P.px.winShift = h->P.px.winShift;          /* the handle's (a tools build may have forced them) */
+    R.P.px.winShiftGround = h->P.px.winShiftGround;
+    R.P.px.groundFull = static_cast<int>(key & 1u);
+    R.P.risers = h->P.risers;
+    R.P.riserMinSupport = h->P.riserMinSupport;
+    R.P.riserTol = tol;
+    float *maps = h->camHasIntr[i] ? h->dCamMaps + i * (static_cast<size_t>(W) + H) : nullptr;
+    R.D = DepthSrc{ maps, maps ? maps + W : nullptr, h->camDepthUnits[i], W, H, depth_row_magic(W, H) };
+  }
+  HIP_TRY(hipMemcpy(h->dCams, recs.data(), sizeof(CameraRec) * n, hipMemcpyHostToDevice));
+  h->camCallKey = key;
+  h->camCallTol = tol;
+  return SSD_OK;
+}
+
+int ssd_set_cameras(ssd_handle *h, const ssd_camera *cams, int ncams)
+{
+  if(!h)
+    return fail(SSD_E_ARG, "ssd_set_cameras: null handle");
+  if(ncams < 0 || ncams > SSD_MAX_CAMERAS)
+    return fail(SSD_E_ARG, "ssd_set_cameras: ncams must be 0.." + std::to_string(SSD_MAX_CAMERAS));
+  if(ncams > 0 && !cams)
+    return fail(SSD_E_ARG, "ssd_set_cameras: null table");
+  /* every camera through make_params() first: a bad one leaves the handle's table as it was */
+  std::vector<Params> params(static_cast<size_t>(ncams));
+  bool anyIntr = false, checks = false;
+  for(int i = 0; i < ncams; i++)
+  {
+    params[i] = Params{};
+    const int rc = make_params(h->cfg, cams[i].cal, params[i]);
+    if(rc) return rc;
+    if(cams[i].has_intrinsics)
+    {
+      const ssd_intrinsics &in = cams[i].intr;
+      if(!(in.fx != 0.0f) || !(in.fy != 0.0f) || !(in.depth_units > 0.0f))
+        return fail(SSD_E_ARG, "ssd_set_cameras: bad intrinsics of camera " + std::to_string(i));
+      anyIntr = true;
+    }
+    checks = checks || needs_checks(params[i]);
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipDeviceSynchronize());            /* batches in flight read the table and the lanes' indices */
+  cameras_free(h);
+  if(ncams == 0)
+    return SSD_OK;
+  const int W = h->P.W, H = h->P.H;
+  const size_t recBytes = sizeof(CameraRec) * static_cast<size_t>(ncams);
+  const size_t mapBytes = anyIntr ? static_cast<size_t>(ncams) * (static_cast<size_t>(W) + H) * sizeof(float) : 0;
+  const size_t indexBytes = sizeof(int) * static_cast<size_t>(h->F);
+  auto bad = [&](hipError_t e, const char *what)
+  {
+    cameras_free(h);
+    (void)hipGetLastError();
+    return fail(e == hipErrorOutOfMemory ? SSD_E_NOMEM : SSD_E_HIP, std::string("ssd_set_cameras: ") + what + ": " + hipGetErrorString(e));
+  };
+  hipError_t e = hipMalloc(&h->dCams, recBytes);
+  if(e != hipSuccess) return bad(e, "hipMalloc of the table");
+  if(mapBytes)
+  {
+    e = hipMalloc(&h->dCamMaps, mapBytes);
+    if(e != hipSuccess) return bad(e, "hipMalloc of the deprojection maps");
+    std::vector<float> all(mapBytes / sizeof(float), 0.0f), maps;
+    for(int i = 0; i < ncams; i++)
+      if(cams[i].has_intrinsics)
+      {
+        depth_maps(cams[i].intr, W, H, maps);
+        std::memcpy(all.data() + static_cast<size_t>(i) * (static_cast<size_t>(W) + H), maps.data(), maps.size() * sizeof(float));
+      }
+    e = hipMemcpy(h->dCamMaps, all.data(), mapBytes, hipMemcpyHostToDevice);
+    if(e != hipSuccess) return bad(e, "upload of the deprojection maps");
+  }
+  for(int k = 0; k < h->depth; k++)
+  {
+    ssd_lane &L = h->lane[k];
+    e = hipMalloc(&L.dCamIndex, indexBytes);
+    if(e == hipSuccess) e = hipHostMalloc(&L.hCamIndex, indexBytes, hipHostMallocDefault);
+    if(e == hipSuccess) e = hipEventCreateWithFlags(&L.camCopied, hipEventDisableTiming);
+    if(e != hipSuccess) return bad(e, "a workspace's index");
+  }
+  h->camParams.swap(params);
+  h->camHasIntr.resize(static_cast<size_t>(ncams));
+  h->camDepthUnits.resize(static_cast<size_t>(ncams));
+  for(int i = 0; i < ncams; i++)
+  {
+    h->camHasIntr[i] = cams[i].has_intrinsics ? 1 : 0;
+    h->camDepthUnits[i] = cams[i].has_intrinsics ? cams[i].intr.depth_units : 0.0f;
+  }
+  h->camsNeedChecks = checks;
+  h->camBytes = recBytes + mapBytes + static_cast<size_t>(h->depth) * indexBytes;
+  h->bytes += h->camBytes;
+  Params P = h->P;
+  P.px.groundFull = h->debug == 1 ? 1 : 0;
+  const int rc = cameras_upload(h, cameras_call_key(P), P.riserTol);
+  if(rc)
+    cameras_free(h);
+  return rc;
+}
+
+int ssd_camera_count(const ssd_handle *h)
+{
+  return h ? static_cast<int>(h->camParams.size()) : 0;
+}
+
+/* the refusals of a cameras batch, before anything is launched or copied */
+static int check_cameras(const ssd_handle *h, const char *who, const uint16_t *camOf, int nframes, int input)
+{
+  if(!camOf)
+    return fail(SSD_E_ARG, std::string(who) + ": null camera_of_frame");
+  if(input != SSD_INPUT_VERTICES && input != SSD_INPUT_DEPTH16)
+    return fail(SSD_E_ARG, std::string(who) + ": input must be SSD_INPUT_VERTICES or SSD_INPUT_DEPTH16");
+  if(h->camParams.empty())
+    return fail(SSD_E_ARG, std::string(who) + ": the handle has no camera table (ssd_set_cameras)");
+  for(int i = 0; i < nframes; i++)
+  {
+    if(camOf[i] >= h->camParams.size())
+      return fail(SSD_E_ARG, std::string(who) + ": frame " + std::to_string(i) + " names camera " + std::to_string(camOf[i]) + " of " + std::to_string(h->camParams.size()));
+    if(input == SSD_INPUT_DEPTH16 && !h->camHasIntr[camOf[i]])
+      return fail(SSD_E_ARG, std::string(who) + ": depth input of frame " + std::to_string(i) + " names camera " + std::to_string(camOf[i]) + ", which has no intrinsics");
+  }
+  return SSD_OK;
+}
+
+int ssd_enqueue_cameras(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream,
+                        const uint16_t *camera_of_frame, int input, uint8_t *d_labels, size_t label_stride_bytes)
+{
+  if(!h || !d_frames)
+    return fail(SSD_E_ARG, "ssd_enqueue_cameras: null argument");
+  if(nframes < 1 || nframes > h->F)
+    return fail(SSD_E_ARG, "ssd_enqueue_cameras: nframes must be 1..max_frames_per_batch");
+  int rc = check_cameras(h, "ssd_enqueue_cameras", camera_of_frame, nframes, input);
+  if(rc) return rc;
+  if(d_labels)
+  {
+    rc = check_labels_dest(h, "ssd_enqueue_cameras", d_labels, label_stride_bytes);
+    if(rc) return rc;
+  }
+  return enqueue_impl(h, d_frames, frame_stride_bytes, nframes, stream, SSD_STAGE_ALL, input == SSD_INPUT_DEPTH16, d_labels, d_labels ? label_stride_bytes : 0,
+                      camera_of_frame);
+}
+
+int ssd_process_host_cameras(ssd_handle *h, const void *frames, int nframes, const uint16_t *camera_of_frame, int input,
+                             ssd_frame_result *results, uint8_t *labels)
+{
+  if(!h || !frames || !results || nframes < 1)
+    return fail(SSD_E_ARG, "ssd_process_host_cameras: bad argument");
+  const int rc = check_cameras(h, "ssd_process_host_cameras", camera_of_frame, nframes, input);
+  if(rc) return rc;
+  if(input == SSD_INPUT_DEPTH16)
+  {
+    const size_t frameElems = (static_cast<size_t>(h->P.nPoints) + 3) / 4 * 4;       /* as ssd_process_depth_host */
+    return process_host_impl(h, frames, static_cast<size_t>(h->P.nPoints) * 2, frameElems * 2, nframes, results, true, labels, camera_of_frame);
+  }
+  const size_t frameBytes = static_cast<size_t>(h->P.nPoints) * 12;
+  return process_host_impl(h, frames, frameBytes, frameBytes, nframes, results, false, labels, camera_of_frame);
 }
 
 /* pinned host memory for frames (DMA without a staging copy) */

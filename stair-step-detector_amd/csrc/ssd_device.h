@@ -153,6 +153,23 @@ struct Params
   double riserTol, heightInterval;
 };
 
+/* One camera of a handle's table (ssd_set_cameras): everything the kernels take by value for the handle's one
+ * calibration, as make_params() and depth_maps() make it for this camera.  A cameras batch passes the table and the batch's
+ * index (frame -> camera, 32-bit); each block fetches its frame's record with wave-uniform loads. */
+struct CameraRec
+{
+  Params P;
+  DepthSrc D;                                 /* xmap / ymap null: the camera has no intrinsics */
+};
+
+/* what a launcher needs of a cameras batch (null: the handle's one calibration, the by-value entry points) */
+struct CameraSel
+{
+  const CameraRec *table;                     /* device */
+  const int *index;                           /* device, one per frame of the batch */
+  bool checks;                                /* some camera of the table needs the CHECKS instantiations */
+};
+
 /* strict point-in-quadrilateral test prepared once per quadrilateral
  * (reference quadrilateralTest.cpp:275-451: 3x3 cell map, <= 2 segments tested per cell) */
 struct QuadTest

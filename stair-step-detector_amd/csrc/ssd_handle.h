@@ -42,6 +42,10 @@ struct ssd_lane
   hipEvent_t done = nullptr;                /* recorded behind the lane's last enqueue */
   hipStream_t lastStream = nullptr;         /* depth 1: the stream of the previous call (a switch is ordered by `done`) */
   bool haveLast = false;
+  /* cameras batches (ssd_enqueue_cameras): the batch's index frame -> camera, F ints each, made on the lane's first such batch */
+  int *dCamIndex = nullptr;
+  int *hCamIndex = nullptr;                 /* pinned: the caller's array is copied here during the call */
+  hipEvent_t camCopied = nullptr;           /* behind the copy pinned -> device: the slot may be written again */
   bool stepImagesDirty = false, groundImageDirty = false;   /* a partial run rastered without the stage that consumes (and clears) the bits */
   int dirtyFrames = 0;                      /* leading FrameStates whose K1 accumulators may be non-zero (k_peaks clears them) */
 };
@@ -116,6 +120,18 @@ struct ssd_handle
   hipEvent_t labelsCopied[2] = { nullptr, nullptr };
   unsigned long long enqueueCount = 0;
   unsigned long long timedFrom = 0;
+  /* the camera table (ssd_set_cameras; empty: none).  camParams are make_params()' as they were made; the device records also
+   * carry what a call decides for the whole handle (debug capture's groundFull, the riser settings): camCallKey is what the
+   * records on the device were made for, and an enqueue that finds another uploads them again behind the batches in flight */
+  std::vector<ssd::Params> camParams;
+  std::vector<unsigned char> camHasIntr;
+  std::vector<float> camDepthUnits;
+  ssd::CameraRec *dCams = nullptr;
+  float *dCamMaps = nullptr;                /* per camera xmap[W] then ymap[H] */
+  bool camsNeedChecks = false;              /* some camera needs_checks(): its batches run the CHECKS instantiations */
+  unsigned long long camCallKey = ~0ull;
+  double camCallTol = 0.0;
+  size_t camBytes = 0;                      /* the table's share of `bytes` */
 };
 
 #endif /* SSD_HANDLE_H_ */

@@ -24,6 +24,20 @@
  *   K3 k_outline      reads a covered plateau's plane(s) in place of its step image
  * Nothing the predictor says can change a result ("The single pass").
  */
+/* This file is compiled twice.  By itself it is the one-calibration path: every kernel takes the handle's constants by value.
+ * ssd_kernels_cams.hip defines SSD_CAMERAS_TU and includes it for the device code alone: the kernels whose body stands in the
+ * entry point itself become device functions there (SSD_ENTRY gives them their second name, SSD_BYVAL turns the by-value
+ * constants into references), and the cameras entry points call them with the frame's camera record.
+ * Without SSD_CAMERAS_TU both macros spell exactly what stood here before, so this translation unit's code does not change. */
+#ifndef SSD_CAMERAS_TU
+#define SSD_ENTRY(bounds, kernel, block) __global__ bounds void kernel
+#define SSD_BYVAL(T) T
+#else
+#define SSD_ENTRY(bounds, kernel, block) __device__ __forceinline__ void block
+#define SSD_BYVAL(T) const T &
+#undef SSD_PHASE_TIMING       /* the tools' clocks and counters are this file's own translation unit's */
+#undef SSD_COUNT
+#endif
 #include "ssd_device.h"
 #include "ssd_math.h"
 #include "ssd_quadtest.h"
@@ -1383,6 +1397,7 @@ __device__ __forceinline__ void hist_block(HistLds &L, SPECLDS &SL, const float 
   }
 }
 
+#ifndef SSD_CAMERAS_TU
 template<int SRC, bool CHECKS>
 __global__ __launch_bounds__(kThreads, 6) void k_hist(const float *__restrict__ xyz, size_t strideFloats, PointParams P, PreXY Q,
                                                    FrameState *__restrict__ st, uint2 *__restrict__ tileMasks,
@@ -1395,9 +1410,11 @@ __global__ __launch_bounds__(kThreads, 6) void k_hist(const float *__restrict__ 
 
 /* K1 of a single-pass batch: histogram, cell records AND the planes of the candidate bins.  31 KiB of LDS: five blocks per CU
  * (4 .. 6 measure the same). */
+#endif /* SSD_CAMERAS_TU */
 #ifndef SSD_K1S_WAVES
 #define SSD_K1S_WAVES 5
 #endif
+#ifndef SSD_CAMERAS_TU
 template<int SRC, bool STRIPS, bool CHECKS>
 __global__ __launch_bounds__(kThreads, SSD_K1S_WAVES) void k_hist_planes(const float *__restrict__ xyz, size_t strideFloats, PointParams P, PreXY Q, PixelParams X,
                                                    FrameState *__restrict__ st, uint2 *__restrict__ tileMasks,
@@ -1430,6 +1447,7 @@ __global__ __launch_bounds__(kThreads, SSD_K1S_WAVES) void k_hist_planes(const f
 #endif
   hist_block<SRC, true, STRIPS, CHECKS>(L, SL, xyz, strideFloats, P, Q, X, st, tileMasks, planeImg, tileMaskStride, chunkPoints, D, frameIdx, chunkIdx);
 }
+#endif /* SSD_CAMERAS_TU */
 
 /* K0 of a single-pass batch: which height bins may belong to a step plateau?  A histogram of one cell in every kSpecSample (a
  * different column of the camera image from row to row), the reference's peak filter (pointcloud.cpp:243-256) on it with
@@ -1439,8 +1457,8 @@ __global__ __launch_bounds__(kThreads, SSD_K1S_WAVES) void k_hist_planes(const f
  * Grid (frame, part): the blocks of a frame add their counts into FrameState::predHist; the last one to finish makes the table
  * and leaves the accumulators zero.  sabotage (tests): 1 = planes three bins above the right ones, 2 = no planes. */
 template<int SRC>
-__global__ __launch_bounds__(kThreads) void k_predict(const float *__restrict__ xyz, size_t strideFloats, PointParams P,
-                                                      FrameState *__restrict__ st, DepthSrc D, int minHeight, int sabotage, int *__restrict__ fallback, int poolPlanes)
+SSD_ENTRY(__launch_bounds__(kThreads), k_predict, predict_block)(const float *__restrict__ xyz, size_t strideFloats, SSD_BYVAL(PointParams) P,
+                                                      FrameState *__restrict__ st, SSD_BYVAL(DepthSrc) D, int minHeight, int sabotage, int *__restrict__ fallback, int poolPlanes)
 {
   __shared__ unsigned int sh[kMaxBins + 2];
   __shared__ unsigned int shc[kMaxBins * kHistCopies];        /* [bin][copy], as K1's: the lanes of a wave mostly vote for ONE bin */
@@ -1637,7 +1655,7 @@ __global__ __launch_bounds__(kThreads) void k_predict(const float *__restrict__ 
 
 /* one wave per frame: the histogram is staged in LDS, lane 0 walks it (the peak / plateau logic is a
  * sequential scan with carried state), all lanes write the tables out */
-__global__ __launch_bounds__(64) void k_peaks(Params P, FrameState *__restrict__ st, int nframes, DebugFrame *__restrict__ dbg, int spec, int *__restrict__ fallback)
+SSD_ENTRY(__launch_bounds__(64), k_peaks, peaks_block)(SSD_BYVAL(Params) P, FrameState *__restrict__ st, int nframes, DebugFrame *__restrict__ dbg, int spec, int *__restrict__ fallback)
 {
   __shared__ unsigned char sImgPlane[kMaxStepImages][2];
   __shared__ unsigned int sCovered;
@@ -2127,6 +2145,7 @@ __device__ __forceinline__ void raster_block(RasterLds &L, const float *__restri
  * small, backed-off or partial call takes - paid for the list's loop with 13 - 17 vector registers in scratch (round 4).  The
  * list's own instantiation runs a handful of frames per batch: built for five waves per SIMD, which leaves it the registers
  * its loop wants (no scratch either). */
+#ifndef SSD_CAMERAS_TU
 template<int SRC, bool LIST>
 __global__ __launch_bounds__(kThreads, LIST ? 5 : SSD_K2_WAVES) void k_raster(const float *__restrict__ xyz, size_t strideFloats, PointParams P,
                                                         PixelParams X, FrameState *__restrict__ st,
@@ -2147,6 +2166,7 @@ __global__ __launch_bounds__(kThreads, LIST ? 5 : SSD_K2_WAVES) void k_raster(co
   else
     raster_block<SRC>(L, xyz, strideFloats, P, X, st, stepImg, tileMasks, tileMaskStride, chunkPoints, D, blockIdx.x, blockIdx.y);
 }
+#endif /* SSD_CAMERAS_TU */
 
 /* ========================================================================= */
 /* BestLine (segmentation.cpp:409-487): a pair of points per lane, the waves dealt out over the lists */
@@ -2270,7 +2290,7 @@ struct OutlineShared
 };
 
 template<int T>
-__global__ __launch_bounds__(T) void k_outline(Params P, FrameState *__restrict__ st,
+SSD_ENTRY(__launch_bounds__(T), k_outline, outline_block)(SSD_BYVAL(Params) P, FrameState *__restrict__ st,
                                                       unsigned long long *__restrict__ stepImg,
                                                       unsigned long long *__restrict__ planeImg,
                                                       DebugFrame *__restrict__ dbg,
@@ -2879,7 +2899,7 @@ __device__ __forceinline__ int4 live_box_thresholds(const QuadTest &t, bool grou
 }
 
 /* one wave per frame: lane k < kMaxPlateaus builds the test of plateau k, lane kGroundAcc the ground's */
-__global__ __launch_bounds__(64) void k_quads(Params P, FrameState *__restrict__ st, int nframes, DebugFrame *__restrict__ dbg)
+SSD_ENTRY(__launch_bounds__(64), k_quads, quads_block)(SSD_BYVAL(Params) P, FrameState *__restrict__ st, int nframes, DebugFrame *__restrict__ dbg)
 {
   static_assert(kMaxPlateaus + 1 <= 64, "one lane per accumulator");
   const int frame = blockIdx.x, lane = threadIdx.x;
@@ -3559,6 +3579,7 @@ __device__ __forceinline__ void inquad_block(InquadLds<FULL> &L, const float *__
   ph.finish();
 }
 
+#ifndef SSD_CAMERAS_TU
 template<int SRC, bool FULL, bool CHECKS>
 __global__ __launch_bounds__(kThreads, FULL ? 4 : SSD_K4_WAVES) void k_inquad(const float *__restrict__ xyz, size_t strideFloats, PointParams P, PreXY Q,
                                                         PixelParams X, FrameState *__restrict__ st,
@@ -3573,6 +3594,7 @@ __global__ __launch_bounds__(kThreads, FULL ? 4 : SSD_K4_WAVES) void k_inquad(co
   const int chunkIdx = by < first ? nChunks - 1 - by : by - first;
   inquad_block<SRC, FULL, CHECKS>(L, xyz, strideFloats, P, Q, X, st, groundImg, tileMasks, tileMaskStride, chunkPoints, D, blockIdx.x, chunkIdx);
 }
+#endif /* SSD_CAMERAS_TU */
 
 /* ========================================================================= */
 /* K7 (extension): per-pixel surface labels                                    */
@@ -3607,9 +3629,9 @@ __device__ __forceinline__ void store_labels4(unsigned char *__restrict__ row, b
 }
 
 template<int SRC, bool CHECKS>
-__global__ __launch_bounds__(kThreads) void k_labels(const float *__restrict__ xyz, size_t strideFloats, PointParams P, PreXY Q,
+SSD_ENTRY(__launch_bounds__(kThreads), k_labels, labels_block)(const float *__restrict__ xyz, size_t strideFloats, SSD_BYVAL(PointParams) P, SSD_BYVAL(PreXY) Q,
                                                      const FrameState *__restrict__ st, const uint2 *__restrict__ tileMasks,
-                                                     size_t tileMaskStride, int chunkPoints, DepthSrc D,
+                                                     size_t tileMaskStride, int chunkPoints, SSD_BYVAL(DepthSrc) D,
                                                      unsigned char *__restrict__ labels, size_t labelStride)
 {
   __shared__ LabelsLds L;
@@ -3739,7 +3761,7 @@ struct FinalShared
 };
 
 template<int T>
-__global__ __launch_bounds__(T) void k_final(Params P, FrameState *__restrict__ st,
+SSD_ENTRY(__launch_bounds__(T), k_final, final_block)(SSD_BYVAL(Params) P, FrameState *__restrict__ st,
                                                     unsigned long long *__restrict__ groundImg,
                                                     ssd_frame_result *__restrict__ results,
                                                     DebugFrame *__restrict__ dbg,
@@ -4115,9 +4137,9 @@ __global__ __launch_bounds__(T) void k_final(Params P, FrameState *__restrict__ 
 /* K6 (extension): evidence of the vertical faces                              */
 
 template<int SRC>
-__global__ __launch_bounds__(kThreads, 8) void k_risers(const float *__restrict__ xyz, size_t strideFloats, PointParams P, double tol,
+SSD_ENTRY(__launch_bounds__(kThreads, 8), k_risers, risers_block)(const float *__restrict__ xyz, size_t strideFloats, SSD_BYVAL(PointParams) P, double tol,
                                                         FrameState *__restrict__ st, const uint2 *__restrict__ tileMasks,
-                                                        size_t tileMaskStride, int chunkPoints, int cellCols, DepthSrc D)
+                                                        size_t tileMaskStride, int chunkPoints, int cellCols, SSD_BYVAL(DepthSrc) D)
 {
   __shared__ unsigned short cellList[kMaxCellsPerBlock];
   __shared__ unsigned int listScratch[2 * kWavesPerBlock];
@@ -4222,7 +4244,7 @@ __global__ __launch_bounds__(kThreads, 8) void k_risers(const float *__restrict_
 }
 
 /* one thread per frame: the riser records in external world coordinates (ToExternalWorld as in k_final) */
-__global__ void k_riser_results(Params P, const FrameState *__restrict__ st, ssd_frame_risers *__restrict__ out, int nframes)
+SSD_ENTRY(, k_riser_results, riser_results_block)(SSD_BYVAL(Params) P, const FrameState *__restrict__ st, ssd_frame_risers *__restrict__ out, int nframes)
 {
   const int frame = blockIdx.x * blockDim.x + threadIdx.x;
   if(frame >= nframes)
@@ -4264,13 +4286,7 @@ __global__ void k_riser_results(Params P, const FrameState *__restrict__ st, ssd
 
 namespace ssd
 {
-
-/* Grid layout of every per-frame kernel: FRAME on the fast axis (blockIdx.x), chunk / image slot on the slow
- * one.  Workgroups are dealt round-robin over the 8 XCDs in linear-id order; with the chunk (or the image
- * slot) on the fast axis every XCD would always get the same chunk positions of every frame — the stairs
- * for some XCDs, the skipped ground for others (measured: +30 % on K2, and K3 running on half of the XCDs
- * because only slots 0..3 hold images).  Frame-fastest gives each XCD whole frames: balanced, and a frame's
- * state and images stay in one XCD's L2. */
+/* what the two translation units' launchers share */
 static inline int chunks_for(int nPoints, int chunkPoints) { return (nPoints + chunkPoints - 1) / chunkPoints; }
 
 static inline bool aligned16(const float *xyz, size_t strideFloats, int nPoints)
@@ -4297,14 +4313,25 @@ static inline void with_bool(bool b, F f)
   else
     f(std::false_type{});
 }
-/* The rare configurations' per-point tests (inputs beyond PreXY::maxInput that could read "inside", a z range that does not end on
- * a bin edge: ssd_prexy.h) live in instantiations of their own: as run-time flags they cost the common one two instructions per point */
-static inline bool needs_checks(const Params &P) { return P.pre.checkInput != 0 || P.pre.zCheckTop != 0; }
+} // namespace ssd
+
+#ifndef SSD_CAMERAS_TU
+namespace ssd
+{
+
+/* Grid layout of every per-frame kernel: FRAME on the fast axis (blockIdx.x), chunk / image slot on the slow
+ * one.  Workgroups are dealt round-robin over the 8 XCDs in linear-id order; with the chunk (or the image
+ * slot) on the fast axis every XCD would always get the same chunk positions of every frame — the stairs
+ * for some XCDs, the skipped ground for others (measured: +30 % on K2, and K3 running on half of the XCDs
+ * because only slots 0..3 hold images).  Frame-fastest gives each XCD whole frames: balanced, and a frame's
+ * state and images stay in one XCD's L2. */
 
 
 void launch_predict(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, int nframes, const DepthSrc *depth,
-                    int *fallback, int poolPlanes, int sabotage, hipStream_t s)
+                    int *fallback, int poolPlanes, int sabotage, hipStream_t s, const CameraSel *cams)
 {
+  if(cams)
+    return launch_predict_cams(xyz, strideFloats, P, st, nframes, depth, fallback, poolPlanes, sabotage, s, *cams);
   dim3 pgrid(nframes, kPredictParts);
   with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &D)
   {
@@ -4312,8 +4339,10 @@ void launch_predict(const float *xyz, size_t strideFloats, const Params &P, Fram
   });
 }
 void launch_hist(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, uint2 *tileMasks, size_t tileMaskStride,
-                 int nframes, int chunkPoints, const DepthSrc *depth, unsigned long long *planeImg, hipStream_t s)
+                 int nframes, int chunkPoints, const DepthSrc *depth, unsigned long long *planeImg, hipStream_t s, const CameraSel *cams)
 {
+  if(cams)
+    return launch_hist_cams(xyz, strideFloats, P, st, tileMasks, tileMaskStride, nframes, chunkPoints, depth, planeImg, s, *cams);
   dim3 grid(nframes, chunks_for(P.nPoints, chunkPoints));
   /* the single pass - a tile a whole number of camera rows: the tile loop keeps every wave in its band of columns; else the sorted strips */
   const bool strips = planeImg && kTile % P.W != 0;
@@ -4333,13 +4362,17 @@ void launch_hist(const float *xyz, size_t strideFloats, const Params &P, FrameSt
     });
   });
 }
-void launch_peaks(const Params &P, FrameState *st, int nframes, DebugFrame *dbg, int *fallback, hipStream_t s)
+void launch_peaks(const Params &P, FrameState *st, int nframes, DebugFrame *dbg, int *fallback, hipStream_t s, const CameraSel *cams)
 {
+  if(cams)
+    return launch_peaks_cams(P, st, nframes, dbg, fallback, s, *cams);
   hipLaunchKernelGGL(k_peaks, dim3(nframes), dim3(64), 0, s, P, st, nframes, dbg, fallback ? 1 : 0, fallback);
 }
 void launch_raster(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, unsigned long long *stepImg,
-                   const uint2 *tileMasks, size_t tileMaskStride, int nframes, int chunkPoints, const DepthSrc *depth, const int *fallback, hipStream_t s)
+                   const uint2 *tileMasks, size_t tileMaskStride, int nframes, int chunkPoints, const DepthSrc *depth, const int *fallback, hipStream_t s, const CameraSel *cams)
 {
+  if(cams)
+    return launch_raster_cams(xyz, strideFloats, P, st, stepImg, tileMasks, tileMaskStride, nframes, chunkPoints, depth, fallback, s, *cams);
   dim3 grid(fallback ? (nframes + 3) / 4 : nframes, chunks_for(P.nPoints, chunkPoints));
   with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &D)
   {
@@ -4349,8 +4382,10 @@ void launch_raster(const float *xyz, size_t strideFloats, const Params &P, Frame
     });
   });
 }
-void launch_outline(const Params &P, FrameState *st, unsigned long long *stepImg, unsigned long long *planeImg, int nframes, DebugFrame *dbg, unsigned long long *dbgImg, hipStream_t s)
+void launch_outline(const Params &P, FrameState *st, unsigned long long *stepImg, unsigned long long *planeImg, int nframes, DebugFrame *dbg, unsigned long long *dbgImg, hipStream_t s, const CameraSel *cams)
 {
+  if(cams)
+    return launch_outline_cams(P, st, stepImg, planeImg, nframes, dbg, dbgImg, s, *cams);
   dim3 grid(nframes, P.maxStepImages);
   /* while every image has a CU of its own, the block that gets through its phases soonest; beyond that the cheapest */
   if(nframes <= kImgFewFrames)
@@ -4358,13 +4393,17 @@ void launch_outline(const Params &P, FrameState *st, unsigned long long *stepImg
   else
     hipLaunchKernelGGL(k_outline<kImgThreadsBatch>, grid, dim3(kImgThreadsBatch), 0, s, P, st, stepImg, planeImg, dbg, dbgImg);
 }
-void launch_quads(const Params &P, FrameState *st, int nframes, DebugFrame *dbg, hipStream_t s)
+void launch_quads(const Params &P, FrameState *st, int nframes, DebugFrame *dbg, hipStream_t s, const CameraSel *cams)
 {
+  if(cams)
+    return launch_quads_cams(P, st, nframes, dbg, s, *cams);
   hipLaunchKernelGGL(k_quads, dim3(nframes), dim3(64), 0, s, P, st, nframes, dbg);
 }
 void launch_inquad(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, unsigned long long *groundImg,
-                   const uint2 *tileMasks, size_t tileMaskStride, int nframes, int chunkPoints, const DepthSrc *depth, hipStream_t s)
+                   const uint2 *tileMasks, size_t tileMaskStride, int nframes, int chunkPoints, const DepthSrc *depth, hipStream_t s, const CameraSel *cams)
 {
+  if(cams)
+    return launch_inquad_cams(xyz, strideFloats, P, st, groundImg, tileMasks, tileMaskStride, nframes, chunkPoints, depth, s, *cams);
   dim3 grid(nframes, chunks_for(P.nPoints, chunkPoints));
   auto launch = [&](auto full, auto checks)
   {
@@ -4379,16 +4418,20 @@ void launch_inquad(const float *xyz, size_t strideFloats, const Params &P, Frame
   else
     with_bool(needs_checks(P), [&](auto checks) { launch(std::false_type{}, checks); });
 }
-void launch_final(const Params &P, FrameState *st, unsigned long long *groundImg, ssd_frame_result *results, int nframes, DebugFrame *dbg, unsigned long long *dbgImg, hipStream_t s)
+void launch_final(const Params &P, FrameState *st, unsigned long long *groundImg, ssd_frame_result *results, int nframes, DebugFrame *dbg, unsigned long long *dbgImg, hipStream_t s, const CameraSel *cams)
 {
+  if(cams)
+    return launch_final_cams(P, st, groundImg, results, nframes, dbg, dbgImg, s, *cams);
   if(nframes <= kImgFewFrames)
     hipLaunchKernelGGL(k_final<kImgThreadsFew>, dim3(nframes), dim3(kImgThreadsFew), 0, s, P, st, groundImg, results, dbg, dbgImg);
   else
     hipLaunchKernelGGL(k_final<kImgThreadsBatch>, dim3(nframes), dim3(kImgThreadsBatch), 0, s, P, st, groundImg, results, dbg, dbgImg);
 }
 void launch_labels(const float *xyz, size_t strideFloats, const Params &P, const FrameState *st, const uint2 *tileMasks, size_t tileMaskStride,
-                   int nframes, int chunkPoints, const DepthSrc *depth, unsigned char *labels, size_t labelStride, hipStream_t s)
+                   int nframes, int chunkPoints, const DepthSrc *depth, unsigned char *labels, size_t labelStride, hipStream_t s, const CameraSel *cams)
 {
+  if(cams)
+    return launch_labels_cams(xyz, strideFloats, P, st, tileMasks, tileMaskStride, nframes, chunkPoints, depth, labels, labelStride, s, *cams);
   dim3 grid(nframes, chunks_for(P.nPoints, chunkPoints));
   with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &D)
   {
@@ -4399,8 +4442,10 @@ void launch_labels(const float *xyz, size_t strideFloats, const Params &P, const
   });
 }
 void launch_risers(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, const uint2 *tileMasks, size_t tileMaskStride,
-                   ssd_frame_risers *out, int nframes, int chunkPoints, const DepthSrc *depth, hipStream_t s)
+                   ssd_frame_risers *out, int nframes, int chunkPoints, const DepthSrc *depth, hipStream_t s, const CameraSel *cams)
 {
+  if(cams)
+    return launch_risers_cams(xyz, strideFloats, P, st, tileMasks, tileMaskStride, out, nframes, chunkPoints, depth, s, *cams);
   dim3 grid(nframes, chunks_for(P.nPoints, chunkPoints));
   with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &D)
   {
@@ -4423,3 +4468,4 @@ extern "C" int ssd_tools_k1_counters(unsigned long long *out)
 #endif
 
 #include "ssd_phase_readers.h"
+#endif /* SSD_CAMERAS_TU */

@@ -1,0 +1,296 @@
+/*
+ * ssd_kernels_cams.hip - the entry points of cameras batches (ssd_enqueue_cameras) and their launchers.
+ *
+ * A cameras batch names, frame by frame, the camera each frame comes from.  Every kernel of the chain already sits on one frame
+ * per block, so each entry point here takes the handle's camera table and the batch's index (frame -> camera) in place of the
+ * by-value constants, fetches the frame's CameraRec at block start and runs the SAME device body as its one-calibration sibling:
+ * this file includes ssd_kernels.hip with SSD_CAMERAS_TU defined, which gives the bodies without that file's entry points and
+ * launchers (see the note at its top).  A translation unit of its own, so that the one-calibration kernels' code is not touched
+ * by what is instantiated here.
+ */
+#define SSD_CAMERAS_TU
+#include "ssd_kernels.hip"
+
+namespace ssd
+{
+
+/* The frame's record.  Its address depends on the frame alone, so it is block-uniform: the loads below are scalar loads into
+ * SGPRs, what the kernel arguments of the one-calibration entry points are as well.  The streaming kernels copy the parts they
+ * use at block start, as their siblings get them by value. */
+__device__ __forceinline__ const CameraRec &camera_of(const CameraRec *__restrict__ cams, const int *__restrict__ camOf, int frame)
+{
+  return cams[camOf[frame]];
+}
+
+template<int SRC, bool CHECKS>
+__global__ __launch_bounds__(kThreads, 6) void k_hist_cams(const float *__restrict__ xyz, size_t strideFloats, const CameraRec *__restrict__ cams,
+                                                        const int *__restrict__ camOf, FrameState *__restrict__ st, uint2 *__restrict__ tileMasks,
+                                                        size_t tileMaskStride, int chunkPoints)
+{
+  __shared__ HistLds L;
+  NoSpecLds none;
+  const CameraRec &C = camera_of(cams, camOf, blockIdx.x);
+  const PointParams P = C.P.pt;
+  const PreXY Q = C.P.pre;
+  const DepthSrc D = C.D;
+  hist_block<SRC, false, false, CHECKS>(L, none, xyz, strideFloats, P, Q, PixelParams{}, st, tileMasks, nullptr, tileMaskStride, chunkPoints, D, blockIdx.x, blockIdx.y);
+}
+
+/* (the tools' other walks of the grid, SSD_K1_ROTATE / SSD_K1_ORDER, are the one-calibration entry point's alone) */
+template<int SRC, bool STRIPS, bool CHECKS>
+__global__ __launch_bounds__(kThreads, SSD_K1S_WAVES) void k_hist_planes_cams(const float *__restrict__ xyz, size_t strideFloats, const CameraRec *__restrict__ cams,
+                                                   const int *__restrict__ camOf, FrameState *__restrict__ st, uint2 *__restrict__ tileMasks,
+                                                   unsigned long long *__restrict__ planeImg, size_t tileMaskStride, int chunkPoints)
+{
+  __shared__ HistLds L;
+  __shared__ SpecLds SL;
+  const CameraRec &C = camera_of(cams, camOf, blockIdx.x);
+  const PointParams P = C.P.pt;
+  const PreXY Q = C.P.pre;
+  const PixelParams X = C.P.px;
+  const DepthSrc D = C.D;
+  hist_block<SRC, true, STRIPS, CHECKS>(L, SL, xyz, strideFloats, P, Q, X, st, tileMasks, planeImg, tileMaskStride, chunkPoints, D, blockIdx.x, blockIdx.y);
+}
+
+template<int SRC>
+__global__ __launch_bounds__(kThreads) void k_predict_cams(const float *__restrict__ xyz, size_t strideFloats, const CameraRec *__restrict__ cams,
+                                                           const int *__restrict__ camOf, FrameState *__restrict__ st, int sabotage, int *__restrict__ fallback, int poolPlanes)
+{
+  const CameraRec &C = camera_of(cams, camOf, blockIdx.x);
+  const PointParams P = C.P.pt;
+  const DepthSrc D = C.D;
+  predict_block<SRC>(xyz, strideFloats, P, st, D, C.P.minHeight, sabotage, fallback, poolPlanes);
+}
+
+__global__ __launch_bounds__(64) void k_peaks_cams(const CameraRec *__restrict__ cams, const int *__restrict__ camOf, FrameState *__restrict__ st, int nframes,
+                                                   DebugFrame *__restrict__ dbg, int spec, int *__restrict__ fallback)
+{
+  if(static_cast<int>(blockIdx.x) >= nframes)
+    return;
+  peaks_block(camera_of(cams, camOf, blockIdx.x).P, st, nframes, dbg, spec, fallback);
+}
+
+template<int SRC, bool LIST>
+__global__ __launch_bounds__(kThreads, LIST ? 5 : SSD_K2_WAVES) void k_raster_cams(const float *__restrict__ xyz, size_t strideFloats, const CameraRec *__restrict__ cams,
+                                                        const int *__restrict__ camOf, FrameState *__restrict__ st,
+                                                        unsigned long long *__restrict__ stepImg,
+                                                        const uint2 *__restrict__ tileMasks, size_t tileMaskStride, int chunkPoints,
+                                                        const int *__restrict__ fallback)
+{
+  __shared__ RasterLds L;
+  if constexpr(LIST)
+  {
+    const int n = fallback[0];
+    for(int e = blockIdx.x; e < n; e += gridDim.x)
+    {
+      const int frame = fallback[kFallbackList + e];
+      const CameraRec &C = camera_of(cams, camOf, frame);
+      const PointParams P = C.P.pt;
+      const PixelParams X = C.P.px;
+      const DepthSrc D = C.D;
+      raster_block<SRC>(L, xyz, strideFloats, P, X, st, stepImg, tileMasks, tileMaskStride, chunkPoints, D, frame, blockIdx.y);
+      __syncthreads();
+    }
+  }
+  else
+  {
+    const CameraRec &C = camera_of(cams, camOf, blockIdx.x);
+    const PointParams P = C.P.pt;
+    const PixelParams X = C.P.px;
+    const DepthSrc D = C.D;
+    raster_block<SRC>(L, xyz, strideFloats, P, X, st, stepImg, tileMasks, tileMaskStride, chunkPoints, D, blockIdx.x, blockIdx.y);
+  }
+}
+
+template<int T>
+__global__ __launch_bounds__(T) void k_outline_cams(const CameraRec *__restrict__ cams, const int *__restrict__ camOf, FrameState *__restrict__ st,
+                                                    unsigned long long *__restrict__ stepImg,
+                                                    unsigned long long *__restrict__ planeImg,
+                                                    DebugFrame *__restrict__ dbg,
+                                                    unsigned long long *__restrict__ dbgImg)
+{
+  outline_block<T>(camera_of(cams, camOf, blockIdx.x).P, st, stepImg, planeImg, dbg, dbgImg);
+}
+
+__global__ __launch_bounds__(64) void k_quads_cams(const CameraRec *__restrict__ cams, const int *__restrict__ camOf, FrameState *__restrict__ st, int nframes,
+                                                   DebugFrame *__restrict__ dbg)
+{
+  if(static_cast<int>(blockIdx.x) >= nframes)
+    return;
+  quads_block(camera_of(cams, camOf, blockIdx.x).P, st, nframes, dbg);
+}
+
+template<int SRC, bool FULL, bool CHECKS>
+__global__ __launch_bounds__(kThreads, FULL ? 4 : SSD_K4_WAVES) void k_inquad_cams(const float *__restrict__ xyz, size_t strideFloats, const CameraRec *__restrict__ cams,
+                                                        const int *__restrict__ camOf, FrameState *__restrict__ st,
+                                                        unsigned long long *__restrict__ groundImg,
+                                                        const uint2 *__restrict__ tileMasks, size_t tileMaskStride, int chunkPoints)
+{
+  __shared__ InquadLds<FULL> L;
+  const CameraRec &C = camera_of(cams, camOf, blockIdx.x);
+  const PointParams P = C.P.pt;
+  const PreXY Q = C.P.pre;
+  const PixelParams X = C.P.px;
+  const DepthSrc D = C.D;
+  const int nChunks = static_cast<int>(gridDim.y), first = max(1, nChunks / 8), by = static_cast<int>(blockIdx.y);    /* the order of k_inquad */
+  const int chunkIdx = by < first ? nChunks - 1 - by : by - first;
+  inquad_block<SRC, FULL, CHECKS>(L, xyz, strideFloats, P, Q, X, st, groundImg, tileMasks, tileMaskStride, chunkPoints, D, blockIdx.x, chunkIdx);
+}
+
+template<int T>
+__global__ __launch_bounds__(T) void k_final_cams(const CameraRec *__restrict__ cams, const int *__restrict__ camOf, FrameState *__restrict__ st,
+                                                  unsigned long long *__restrict__ groundImg,
+                                                  ssd_frame_result *__restrict__ results,
+                                                  DebugFrame *__restrict__ dbg,
+                                                  unsigned long long *__restrict__ dbgImg)
+{
+  final_block<T>(camera_of(cams, camOf, blockIdx.x).P, st, groundImg, results, dbg, dbgImg);
+}
+
+template<int SRC, bool CHECKS>
+__global__ __launch_bounds__(kThreads) void k_labels_cams(const float *__restrict__ xyz, size_t strideFloats, const CameraRec *__restrict__ cams,
+                                                          const int *__restrict__ camOf, const FrameState *__restrict__ st, const uint2 *__restrict__ tileMasks,
+                                                          size_t tileMaskStride, int chunkPoints,
+                                                          unsigned char *__restrict__ labels, size_t labelStride)
+{
+  const CameraRec &C = camera_of(cams, camOf, blockIdx.x);
+  const PointParams P = C.P.pt;
+  const PreXY Q = C.P.pre;
+  const DepthSrc D = C.D;
+  labels_block<SRC, CHECKS>(xyz, strideFloats, P, Q, st, tileMasks, tileMaskStride, chunkPoints, D, labels, labelStride);
+}
+
+template<int SRC>
+__global__ __launch_bounds__(kThreads, 8) void k_risers_cams(const float *__restrict__ xyz, size_t strideFloats, const CameraRec *__restrict__ cams,
+                                                             const int *__restrict__ camOf, FrameState *__restrict__ st, const uint2 *__restrict__ tileMasks,
+                                                             size_t tileMaskStride, int chunkPoints)
+{
+  const CameraRec &C = camera_of(cams, camOf, blockIdx.x);
+  const PointParams P = C.P.pt;
+  const DepthSrc D = C.D;
+  risers_block<SRC>(xyz, strideFloats, P, C.P.riserTol, st, tileMasks, tileMaskStride, chunkPoints, C.P.px.cellCols, D);
+}
+
+/* one thread per frame here, so the record is the thread's own (a few constants of it, once per frame) */
+__global__ void k_riser_results_cams(const CameraRec *__restrict__ cams, const int *__restrict__ camOf, const FrameState *__restrict__ st,
+                                     ssd_frame_risers *__restrict__ out, int nframes)
+{
+  const int frame = blockIdx.x * blockDim.x + threadIdx.x;
+  if(frame >= nframes)
+    return;
+  riser_results_block(cams[camOf[frame]].P, st, out, nframes);
+}
+
+
+/* ========================================================================= */
+/* launchers (declared in ssd_launch.h): grids, block sizes and instantiations are those of the one-calibration launchers */
+
+void launch_predict_cams(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, int nframes, const DepthSrc *depth,
+                         int *fallback, int poolPlanes, int sabotage, hipStream_t s, const CameraSel &cams)
+{
+  dim3 pgrid(nframes, kPredictParts);
+  with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &)
+  {
+    hipLaunchKernelGGL(k_predict_cams<decltype(src)::value>, pgrid, dim3(kThreads), 0, s, xyz, strideFloats, cams.table, cams.index, st, sabotage, fallback, poolPlanes);
+  });
+}
+void launch_hist_cams(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, uint2 *tileMasks, size_t tileMaskStride,
+                      int nframes, int chunkPoints, const DepthSrc *depth, unsigned long long *planeImg, hipStream_t s, const CameraSel &cams)
+{
+  dim3 grid(nframes, chunks_for(P.nPoints, chunkPoints));
+  const bool strips = planeImg && kTile % P.W != 0;
+  with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &)
+  {
+    with_bool(cams.checks, [&](auto checks)
+    {
+      constexpr int SRC = decltype(src)::value;
+      constexpr bool CHECKS = decltype(checks)::value;
+      if(planeImg)
+        with_bool(strips, [&](auto sorted)
+        {
+          hipLaunchKernelGGL((k_hist_planes_cams<SRC, decltype(sorted)::value, CHECKS>), grid, dim3(kThreads), 0, s, xyz, strideFloats, cams.table, cams.index, st, tileMasks, planeImg, tileMaskStride, chunkPoints);
+        });
+      else
+        hipLaunchKernelGGL((k_hist_cams<SRC, CHECKS>), grid, dim3(kThreads), 0, s, xyz, strideFloats, cams.table, cams.index, st, tileMasks, tileMaskStride, chunkPoints);
+    });
+  });
+}
+void launch_peaks_cams(const Params &, FrameState *st, int nframes, DebugFrame *dbg, int *fallback, hipStream_t s, const CameraSel &cams)
+{
+  hipLaunchKernelGGL(k_peaks_cams, dim3(nframes), dim3(64), 0, s, cams.table, cams.index, st, nframes, dbg, fallback ? 1 : 0, fallback);
+}
+void launch_raster_cams(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, unsigned long long *stepImg,
+                        const uint2 *tileMasks, size_t tileMaskStride, int nframes, int chunkPoints, const DepthSrc *depth, const int *fallback, hipStream_t s,
+                        const CameraSel &cams)
+{
+  dim3 grid(fallback ? (nframes + 3) / 4 : nframes, chunks_for(P.nPoints, chunkPoints));
+  with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &)
+  {
+    with_bool(fallback != nullptr, [&](auto listed)
+    {
+      hipLaunchKernelGGL((k_raster_cams<decltype(src)::value, decltype(listed)::value>), grid, dim3(kThreads), 0, s, xyz, strideFloats, cams.table, cams.index, st, stepImg, tileMasks, tileMaskStride, chunkPoints, fallback);
+    });
+  });
+}
+void launch_outline_cams(const Params &P, FrameState *st, unsigned long long *stepImg, unsigned long long *planeImg, int nframes, DebugFrame *dbg,
+                         unsigned long long *dbgImg, hipStream_t s, const CameraSel &cams)
+{
+  dim3 grid(nframes, P.maxStepImages);
+  if(nframes <= kImgFewFrames)
+    hipLaunchKernelGGL(k_outline_cams<kImgThreadsFew>, grid, dim3(kImgThreadsFew), 0, s, cams.table, cams.index, st, stepImg, planeImg, dbg, dbgImg);
+  else
+    hipLaunchKernelGGL(k_outline_cams<kImgThreadsBatch>, grid, dim3(kImgThreadsBatch), 0, s, cams.table, cams.index, st, stepImg, planeImg, dbg, dbgImg);
+}
+void launch_quads_cams(const Params &, FrameState *st, int nframes, DebugFrame *dbg, hipStream_t s, const CameraSel &cams)
+{
+  hipLaunchKernelGGL(k_quads_cams, dim3(nframes), dim3(64), 0, s, cams.table, cams.index, st, nframes, dbg);
+}
+void launch_inquad_cams(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, unsigned long long *groundImg,
+                        const uint2 *tileMasks, size_t tileMaskStride, int nframes, int chunkPoints, const DepthSrc *depth, hipStream_t s, const CameraSel &cams)
+{
+  dim3 grid(nframes, chunks_for(P.nPoints, chunkPoints));
+  auto launch = [&](auto full, auto checks)
+  {
+    with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &)
+    {
+      hipLaunchKernelGGL((k_inquad_cams<decltype(src)::value, decltype(full)::value, decltype(checks)::value>), grid, dim3(kThreads), 0, s, xyz, strideFloats, cams.table, cams.index, st, groundImg, tileMasks, tileMaskStride, chunkPoints);
+    });
+  };
+  /* debug capture (the whole ground image: the handle's, so the same for every camera) as launch_inquad */
+  if(P.px.groundFull)
+    launch(std::true_type{}, std::true_type{});
+  else
+    with_bool(cams.checks, [&](auto checks) { launch(std::false_type{}, checks); });
+}
+void launch_final_cams(const Params &, FrameState *st, unsigned long long *groundImg, ssd_frame_result *results, int nframes, DebugFrame *dbg,
+                       unsigned long long *dbgImg, hipStream_t s, const CameraSel &cams)
+{
+  if(nframes <= kImgFewFrames)
+    hipLaunchKernelGGL(k_final_cams<kImgThreadsFew>, dim3(nframes), dim3(kImgThreadsFew), 0, s, cams.table, cams.index, st, groundImg, results, dbg, dbgImg);
+  else
+    hipLaunchKernelGGL(k_final_cams<kImgThreadsBatch>, dim3(nframes), dim3(kImgThreadsBatch), 0, s, cams.table, cams.index, st, groundImg, results, dbg, dbgImg);
+}
+void launch_labels_cams(const float *xyz, size_t strideFloats, const Params &P, const FrameState *st, const uint2 *tileMasks, size_t tileMaskStride,
+                        int nframes, int chunkPoints, const DepthSrc *depth, unsigned char *labels, size_t labelStride, hipStream_t s, const CameraSel &cams)
+{
+  dim3 grid(nframes, chunks_for(P.nPoints, chunkPoints));
+  with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &)
+  {
+    with_bool(cams.checks, [&](auto checks)
+    {
+      hipLaunchKernelGGL((k_labels_cams<decltype(src)::value, decltype(checks)::value>), grid, dim3(kThreads), 0, s, xyz, strideFloats, cams.table, cams.index, st, tileMasks, tileMaskStride, chunkPoints, labels, labelStride);
+    });
+  });
+}
+void launch_risers_cams(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, const uint2 *tileMasks, size_t tileMaskStride,
+                        ssd_frame_risers *out, int nframes, int chunkPoints, const DepthSrc *depth, hipStream_t s, const CameraSel &cams)
+{
+  dim3 grid(nframes, chunks_for(P.nPoints, chunkPoints));
+  with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &)
+  {
+    hipLaunchKernelGGL(k_risers_cams<decltype(src)::value>, grid, dim3(kThreads), 0, s, xyz, strideFloats, cams.table, cams.index, st, tileMasks, tileMaskStride, chunkPoints);
+  });
+  hipLaunchKernelGGL(k_riser_results_cams, dim3((nframes + 63) / 64), dim3(64), 0, s, cams.table, cams.index, st, out, nframes);
+}
+
+} // namespace ssd

@@ -24,28 +24,45 @@ constexpr long long kSinglePassMinPoints = 64ll * 1024 * 768;
 inline bool single_pass_batch(int nframes, int nPoints) { return static_cast<long long>(nframes) * nPoints >= kSinglePassMinPoints; }
 constexpr int kSinglePassBackoff = 63;      /* batches run in two passes after one the single pass could not pay on (ssd_fetch_back) */
 constexpr int kPredictParts = 4;            /* blocks of k_predict per frame */
+/* The rare configurations' per-point tests (inputs beyond PreXY::maxInput that could read "inside", a z range that does not end on
+ * a bin edge: ssd_prexy.h) live in instantiations of their own: as run-time flags they cost the common one two instructions per point */
+inline bool needs_checks(const Params &P) { return P.pre.checkInput != 0 || P.pre.zCheckTop != 0; }
 inline bool single_pass_geometry(int W, int H) { return W >= 64 && W <= 8192 && H >= 16 && H <= 4096; }
 
 /* The single pass: launch_predict (k_predict; fallback = the batch's list of frames for k_raster - count, then indices: k_predict
  * resets it, k_peaks appends, k_raster reads; sabotage: see k_predict), then launch_hist with planeImg != nullptr (K1 rastering the
- * candidate bins' planes), launch_peaks / launch_raster with the list, launch_outline with the planes. */
+ * candidate bins' planes), launch_peaks / launch_raster with the list, launch_outline with the planes.
+ * cams (every launcher): a cameras batch - the *_cams entry points with the table and the batch's index, CHECKS by cams->checks; P then
+ * gives only what the cameras share (resolution, points, image slots), depth only says that the source is 16-bit depth. */
 void launch_predict(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, int nframes, const DepthSrc *depth,
-                    int *fallback, int poolPlanes, int sabotage, hipStream_t s);
+                    int *fallback, int poolPlanes, int sabotage, hipStream_t s, const CameraSel *cams = nullptr);
 void launch_hist(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, uint2 *tileMasks, size_t tileMaskStride,
-                 int nframes, int chunkPoints, const DepthSrc *depth, unsigned long long *planeImg, hipStream_t s);
-void launch_peaks(const Params &P, FrameState *st, int nframes, DebugFrame *dbg, int *fallback, hipStream_t s);
+                 int nframes, int chunkPoints, const DepthSrc *depth, unsigned long long *planeImg, hipStream_t s, const CameraSel *cams = nullptr);
+void launch_peaks(const Params &P, FrameState *st, int nframes, DebugFrame *dbg, int *fallback, hipStream_t s, const CameraSel *cams = nullptr);
 void launch_raster(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, unsigned long long *stepImg,
-                   const uint2 *tileMasks, size_t tileMaskStride, int nframes, int chunkPoints, const DepthSrc *depth, const int *fallback, hipStream_t s);
-void launch_outline(const Params &P, FrameState *st, unsigned long long *stepImg, unsigned long long *planeImg, int nframes, DebugFrame *dbg, unsigned long long *dbgImg, hipStream_t s);
-void launch_quads(const Params &P, FrameState *st, int nframes, DebugFrame *dbg, hipStream_t s);
+                   const uint2 *tileMasks, size_t tileMaskStride, int nframes, int chunkPoints, const DepthSrc *depth, const int *fallback, hipStream_t s, const CameraSel *cams = nullptr);
+void launch_outline(const Params &P, FrameState *st, unsigned long long *stepImg, unsigned long long *planeImg, int nframes, DebugFrame *dbg, unsigned long long *dbgImg, hipStream_t s, const CameraSel *cams = nullptr);
+void launch_quads(const Params &P, FrameState *st, int nframes, DebugFrame *dbg, hipStream_t s, const CameraSel *cams = nullptr);
 void launch_inquad(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, unsigned long long *groundImg,
-                   const uint2 *tileMasks, size_t tileMaskStride, int nframes, int chunkPoints, const DepthSrc *depth, hipStream_t s);
-void launch_final(const Params &P, FrameState *st, unsigned long long *groundImg, ssd_frame_result *results, int nframes, DebugFrame *dbg, unsigned long long *dbgImg, hipStream_t s);
+                   const uint2 *tileMasks, size_t tileMaskStride, int nframes, int chunkPoints, const DepthSrc *depth, hipStream_t s, const CameraSel *cams = nullptr);
+void launch_final(const Params &P, FrameState *st, unsigned long long *groundImg, ssd_frame_result *results, int nframes, DebugFrame *dbg, unsigned long long *dbgImg, hipStream_t s, const CameraSel *cams = nullptr);
 /* per-pixel surface labels (k_labels) after launch_final: frame i's W H labels at labels + i * labelStride; chunkPoints as launch_risers' */
 void launch_labels(const float *xyz, size_t strideFloats, const Params &P, const FrameState *st, const uint2 *tileMasks, size_t tileMaskStride,
-                   int nframes, int chunkPoints, const DepthSrc *depth, unsigned char *labels, size_t labelStride, hipStream_t s);
+                   int nframes, int chunkPoints, const DepthSrc *depth, unsigned char *labels, size_t labelStride, hipStream_t s, const CameraSel *cams = nullptr);
 void launch_risers(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, const uint2 *tileMasks, size_t tileMaskStride,
-                   ssd_frame_risers *out, int nframes, int chunkPoints, const DepthSrc *depth, hipStream_t s);
+                   ssd_frame_risers *out, int nframes, int chunkPoints, const DepthSrc *depth, hipStream_t s, const CameraSel *cams = nullptr);
+
+/* the launchers of the cameras entry points (ssd_kernels_cams.hip): what launch_*(..., cams) hands a cameras batch to */
+void launch_predict_cams(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, int nframes, const DepthSrc *depth, int *fallback, int poolPlanes, int sabotage, hipStream_t s, const CameraSel &cams);
+void launch_hist_cams(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, uint2 *tileMasks, size_t tileMaskStride, int nframes, int chunkPoints, const DepthSrc *depth, unsigned long long *planeImg, hipStream_t s, const CameraSel &cams);
+void launch_peaks_cams(const Params &P, FrameState *st, int nframes, DebugFrame *dbg, int *fallback, hipStream_t s, const CameraSel &cams);
+void launch_raster_cams(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, unsigned long long *stepImg, const uint2 *tileMasks, size_t tileMaskStride, int nframes, int chunkPoints, const DepthSrc *depth, const int *fallback, hipStream_t s, const CameraSel &cams);
+void launch_outline_cams(const Params &P, FrameState *st, unsigned long long *stepImg, unsigned long long *planeImg, int nframes, DebugFrame *dbg, unsigned long long *dbgImg, hipStream_t s, const CameraSel &cams);
+void launch_quads_cams(const Params &P, FrameState *st, int nframes, DebugFrame *dbg, hipStream_t s, const CameraSel &cams);
+void launch_inquad_cams(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, unsigned long long *groundImg, const uint2 *tileMasks, size_t tileMaskStride, int nframes, int chunkPoints, const DepthSrc *depth, hipStream_t s, const CameraSel &cams);
+void launch_final_cams(const Params &P, FrameState *st, unsigned long long *groundImg, ssd_frame_result *results, int nframes, DebugFrame *dbg, unsigned long long *dbgImg, hipStream_t s, const CameraSel &cams);
+void launch_labels_cams(const float *xyz, size_t strideFloats, const Params &P, const FrameState *st, const uint2 *tileMasks, size_t tileMaskStride, int nframes, int chunkPoints, const DepthSrc *depth, unsigned char *labels, size_t labelStride, hipStream_t s, const CameraSel &cams);
+void launch_risers_cams(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, const uint2 *tileMasks, size_t tileMaskStride, ssd_frame_risers *out, int nframes, int chunkPoints, const DepthSrc *depth, hipStream_t s, const CameraSel &cams);
 }
 
 #endif /* SSD_LAUNCH_H_ */
