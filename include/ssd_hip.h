@@ -326,6 +326,77 @@ int ssd_enqueue_cameras(ssd_handle *h, const void *d_frames, size_t frame_stride
 int ssd_process_host_cameras(ssd_handle *h, const void *frames, int nframes, const uint16_t *camera_of_frame, int input,
                              ssd_frame_result *results, uint8_t *labels);
 
+/* ---- ground fit: a camera's calibration refined from the floor in its own frames ------------------------------------
+ * EXTENSION.  CameraToWorld (a, b) is fully determined by the floor's plane in camera coordinates
+ * (ssd_calibration_from_points: z = -n0, y = normalize(0, -z.z / z.y, 1), x = y x z, b = (0, 0, n0 . p0)); only ToExternalWorld
+ * (r2, t2, world_z) needs surveyed marks.  Given frames and a rough prior calibration per frame, one streaming pass on the GPU
+ * gathers each frame's floor points into exact integer moments, and a small host solve turns the moments into a plane and a
+ * refined calibration (r2, t2, world_z carried over from the prior: the fit follows pitch, roll and height, not yaw or the
+ * translation over the floor).
+ * Floor points of a frame: a point (x, y, z) in float camera coordinates (16-bit depth input is deprojected first, bit-equal to
+ * ssd_deproject_host) is a floor point iff
+ *   z > 0;
+ *   w = A p + b lies strictly inside the handle's x and y measuring range, w in doubles as K1 computes it: each row
+ *     (a0 x + a1 y) + a2 z, then + b, no FMA;
+ *   -tol <= w.z && w.z <= tol;
+ *   each of qx, qy, qz has |q| < 2^20, q = llrint(double(v) * 65536.0): 2^-16 m fixed point, |v| < 16 m.
+ * A frame has fewer than 2^23 points and each product is below 2^40, so every sum stays below 2^63: the moments are exact
+ * integers, independent of the order of summation, and the device and ssd_ground_moments_host agree bit for bit. */
+#define SSD_GF_OK 0
+#define SSD_GF_FEW 1          /* fewer than min_points floor points */
+#define SSD_GF_DEGENERATE 2   /* points do not determine a plane, or the plane gives no calibration */
+#define SSD_GF_PLANARITY 16.0 /* DEGENERATE unless lambda_mid >= SSD_GF_PLANARITY * lambda_min */
+
+typedef struct
+{
+  int64_t n;          /* floor points */
+  int64_t s[3];       /* sum qx, qy, qz */
+  int64_t ss[6];      /* sum qx*qx, qx*qy, qx*qz, qy*qy, qy*qz, qz*qz */
+} ssd_ground_moments;
+
+typedef struct
+{
+  ssd_ground_moments m;
+  int32_t status, reserved;
+  double normal[3];   /* n0: unit, away from the camera (n0 . centroid > 0), camera coordinates */
+  double dist;        /* n0 . centroid = camera height above the fitted floor */
+  double rms;         /* sqrt(lambda_min): rms distance of the floor points from the plane, metres */
+  double tilt;        /* angle between n0 and the prior's (-a[6], -a[7], -a[8]), radians */
+  double height_delta;/* dist - prior b[2] */
+  ssd_calibration cal;/* a, b from (n0, dist) exactly as ssd_calibration_from_points derives them from n0 and dot(c0, n0);
+                         r2, t2, world_z copied from the prior.  status != OK: the prior, unchanged */
+} ssd_ground_fit;
+
+/* host only: the a / b half of ssd_calibration_from_points (the same code, shared), r2 / t2 / world_z copied from `prior`;
+ * SSD_E_ARG in the degenerate cases ssd_calibration_from_points rejects (dist <= 0, a plane that holds the camera's y axis) */
+int ssd_calibration_from_plane(const double n0[3], double dist, const ssd_calibration *prior, ssd_calibration *out);
+/* host restatement of the floor-point rule for ONE frame (no GPU needed): input = SSD_INPUT_VERTICES (width * height xyz floats)
+ * or SSD_INPUT_DEPTH16 (width * height uint16, prior->has_intrinsics required); tol in (0, 1] */
+int ssd_ground_moments_host(const ssd_config *cfg, const ssd_camera *prior, int input, const void *frame, double tol, ssd_ground_moments *out);
+/* host only: moments -> plane -> calibration.  The centred scatter N SS - S (x) S is formed exactly in 128-bit integers, converted
+ * once to double and scaled to m^2; its eigenvalues lambda_min <= lambda_mid <= lambda_max by cyclic Jacobi; n0 = the eigenvector
+ * of lambda_min, signed so that n0 . centroid > 0.  Status in this order: FEW (n < max(min_points, 1)), DEGENERATE (lambda_mid <= 0,
+ * or lambda_mid < SSD_GF_PLANARITY * lambda_min, or ssd_calibration_from_plane fails; an eigenvalue not above 64 eps lambda_max
+ * counts as 0: the rounding level of the solve), OK.  Unless OK: cal = the prior, the other doubles 0.  Always returns SSD_OK for
+ * non-null arguments. */
+int ssd_ground_fit_solve(const ssd_ground_moments *m, const ssd_calibration *prior, int min_points, ssd_ground_fit *out);
+/* The moments of frames resident in device memory (frame i at d_frames + i * frame_stride_bytes), on the caller's stream, in order,
+ * without synchronising - the stream contract of ssd_enqueue with one workspace, whatever batches_in_flight is.  npriors = 0: the
+ * handle's calibration (and its ssd_set_intrinsics for depth input); 1: priors[0] for every frame; nframes: one per frame.  Priors
+ * are HOST memory, copied during the call.  Uses none of the detection workspaces, neither disturbs nor waits for batches in flight
+ * and leaves the state ssd_fetch* read untouched.  SSD_E_ARG before anything is launched: npriors not 0, 1 or nframes, depth input
+ * without intrinsics, nframes outside 1 .. max_frames_per_batch, tol outside (0, 1], a null handle.  Its buffers (80 bytes per
+ * frame of max_frames_per_batch on the device and pinned, and the priors) are made on the first call and counted in
+ * ssd_workspace_bytes from then on; a handle that never fits allocates, creates and launches nothing for it. */
+int ssd_enqueue_ground_fit(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream, int input,
+                           const ssd_camera *priors, int npriors, double tol);
+/* waits for the last ssd_enqueue_ground_fit and runs ssd_ground_fit_solve per frame against that frame's prior; nframes <= its */
+int ssd_fetch_ground_fit(ssd_handle *h, ssd_ground_fit *out, int nframes, int min_points, void *stream);
+/* frames in host memory (pinned or pageable), any nframes >= 1: in slices through the staging buffers of ssd_process_host, the copy
+ * of a slice overlapping the kernel of the one before; returns when out[nframes] is filled */
+int ssd_process_host_ground_fit(ssd_handle *h, const void *frames, int nframes, int input, const ssd_camera *priors, int npriors,
+                                double tol, int min_points, ssd_ground_fit *out);
+
 /* stage selector for profiling / roofline measurement: runs only the chosen stage(s) of the pipeline */
 #define SSD_STAGE_HIST 1       /* K1: transform + crop + bin + histogram */
 #define SSD_STAGE_PEAKS 2

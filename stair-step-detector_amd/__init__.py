@@ -129,6 +129,20 @@ class Camera(C.Structure):
 MAX_CAMERAS = 4096
 INPUT_VERTICES, INPUT_DEPTH16 = 0, 1
 
+GF_OK, GF_FEW, GF_DEGENERATE = 0, 1, 2
+GF_PLANARITY = 16.0
+
+
+class GroundMoments(C.Structure):
+    """ssd_ground_moments: a frame's floor points as exact integer sums of q = rint(v * 65536) (ground fit)"""
+    _fields_ = [("n", C.c_int64), ("s", C.c_int64 * 3), ("ss", C.c_int64 * 6)]
+
+
+class GroundFit(C.Structure):
+    """ssd_ground_fit: the moments, the fitted plane and the refined calibration (status != GF_OK: cal is the prior)"""
+    _fields_ = [("m", GroundMoments), ("status", C.c_int32), ("reserved", C.c_int32), ("normal", C.c_double * 3), ("dist", C.c_double),
+                ("rms", C.c_double), ("tilt", C.c_double), ("height_delta", C.c_double), ("cal", Calibration)]
+
 
 class Scene(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32),
@@ -159,6 +173,8 @@ EXPORTS = [
     "ssd_pipeline_last_error",
     "ssd_enqueue_labels", "ssd_enqueue_depth_labels", "ssd_process_host_labels", "ssd_process_depth_host_labels", "ssd_get_labels_time_back",
     "ssd_set_cameras", "ssd_camera_count", "ssd_enqueue_cameras", "ssd_process_host_cameras",
+    "ssd_calibration_from_plane", "ssd_ground_moments_host", "ssd_ground_fit_solve", "ssd_enqueue_ground_fit", "ssd_fetch_ground_fit",
+    "ssd_process_host_ground_fit",
 ]
 # libssd_source.so — the frame source standing in for the camera (include/ssd_source.h)
 SOURCE_EXPORTS = [
@@ -225,6 +241,12 @@ def lib():
     L.ssd_camera_count.argtypes = [vp]
     L.ssd_enqueue_cameras.argtypes = [vp, vp, sz, i32, vp, C.POINTER(C.c_uint16), i32, vp, sz]
     L.ssd_process_host_cameras.argtypes = [vp, vp, i32, C.POINTER(C.c_uint16), i32, C.POINTER(FrameResult), vp]
+    L.ssd_calibration_from_plane.argtypes = [C.POINTER(C.c_double), C.c_double, C.POINTER(Calibration), C.POINTER(Calibration)]
+    L.ssd_ground_moments_host.argtypes = [C.POINTER(Config), C.POINTER(Camera), i32, vp, C.c_double, C.POINTER(GroundMoments)]
+    L.ssd_ground_fit_solve.argtypes = [C.POINTER(GroundMoments), C.POINTER(Calibration), i32, C.POINTER(GroundFit)]
+    L.ssd_enqueue_ground_fit.argtypes = [vp, vp, sz, i32, vp, i32, C.POINTER(Camera), i32, C.c_double]
+    L.ssd_fetch_ground_fit.argtypes = [vp, C.POINTER(GroundFit), i32, i32, vp]
+    L.ssd_process_host_ground_fit.argtypes = [vp, vp, i32, i32, C.POINTER(Camera), i32, C.c_double, i32, C.POINTER(GroundFit)]
     L.ssd_serialize.argtypes = [C.POINTER(FrameResult), C.c_char_p, sz]
     L.ssd_set_debug.argtypes = [vp, i32]
     L.ssd_get_debug.argtypes = [vp, i32, C.POINTER(DebugFrame)]
@@ -372,6 +394,64 @@ def default_config(width, height, max_frames_per_batch=64, max_step_plateaus=MAX
     return cfg
 
 
+# --------------------------------------------------------------------------- ground fit: host functions (no GPU needed)
+def _as_camera(prior, intr=None):
+    """a Camera from a Camera, GeometricTransformation, Calibration or (either, Intrinsics)"""
+    if isinstance(prior, Camera):
+        return prior
+    if isinstance(prior, (tuple, list)):
+        prior, intr = prior
+    cam = Camera()
+    cam.cal = prior.constants if isinstance(prior, GeometricTransformation) else prior
+    if intr is not None:
+        cam.intr = intr
+        cam.has_intrinsics = 1
+    return cam
+
+
+def _camera_array(priors):
+    """(ctypes array of Camera or None, count) from None, one prior or a list of priors"""
+    if priors is None:
+        return None, 0
+    if not isinstance(priors, (list, tuple)) or (len(priors) == 2 and isinstance(priors[1], Intrinsics)):
+        priors = [priors]
+    arr = (Camera * max(1, len(priors)))()
+    for i, p in enumerate(priors):
+        arr[i] = _as_camera(p)
+    return arr, len(priors)
+
+
+def calibration_from_plane(normal, dist, prior):
+    """ssd_calibration_from_plane: CameraToWorld from the floor's plane (unit normal away from the camera, camera height), the rest of
+    the calibration copied from `prior` -> Calibration"""
+    n0 = (C.c_double * 3)(*[float(v) for v in normal])
+    p = prior.constants if isinstance(prior, GeometricTransformation) else prior
+    out = Calibration()
+    _check(lib().ssd_calibration_from_plane(n0, float(dist), C.byref(p), C.byref(out)))
+    return out
+
+
+def ground_moments_host(cfg, prior, frame, tol, depth=False):
+    """ssd_ground_moments_host: one frame's floor points under `prior` (a Camera, or anything Detector.set_cameras takes) as exact
+    integer moments -> GroundMoments.  frame: float32 [H, W, 3], or uint16 [H, W] with depth=True."""
+    a = np.ascontiguousarray(frame, dtype=np.uint16 if depth else np.float32)
+    if a.size != cfg.width * cfg.height * (1 if depth else 3):
+        raise SsdError("ground_moments_host: the array is not one frame")
+    cam = _as_camera(prior)
+    out = GroundMoments()
+    _check(lib().ssd_ground_moments_host(C.byref(cfg), C.byref(cam), INPUT_DEPTH16 if depth else INPUT_VERTICES, a.ctypes.data_as(C.c_void_p),
+                                         float(tol), C.byref(out)))
+    return out
+
+
+def ground_fit_solve(moments, prior, min_points=2000):
+    """ssd_ground_fit_solve: moments -> plane -> refined calibration (GroundFit; status GF_OK / GF_FEW / GF_DEGENERATE)"""
+    p = prior.constants if isinstance(prior, GeometricTransformation) else prior.cal if isinstance(prior, Camera) else prior
+    out = GroundFit()
+    _check(lib().ssd_ground_fit_solve(C.byref(moments), C.byref(p), int(min_points), C.byref(out)))
+    return out
+
+
 # --------------------------------------------------------------------------- reference-shaped classes
 class GeometricTransformation:
     """reference transformation.h:102-126; constructor transformation.cpp:196-215."""
@@ -472,6 +552,7 @@ class Detector:
 
     def set_intrinsics(self, intr):
         _check(lib().ssd_set_intrinsics(self._h, C.byref(intr)))
+        self._intr = Intrinsics.from_buffer_copy(intr)
 
     def process_depth_host(self, depth):
         """depth: uint16 array [n, H, W] (or [H, W]) on the host -> list of FrameResult."""
@@ -573,6 +654,55 @@ class Detector:
         _check(lib().ssd_process_host_cameras(self._h, a.ctypes.data_as(C.c_void_p), n, idx.ctypes.data_as(C.POINTER(C.c_uint16)),
                                               INPUT_DEPTH16 if depth else INPUT_VERTICES, res, lab.ctypes.data_as(C.c_void_p) if labels else None))
         return (list(res), lab) if labels else list(res)
+
+    # ---- ground fit: a calibration refined from the floor in the frames (include/ssd_hip.h)
+    def enqueue_ground_fit(self, d_ptr, nframes, tol, priors=None, depth=False, stride_bytes=None, stream=None):
+        """ssd_enqueue_ground_fit: the floor moments of frames in device memory, on the caller's stream.  priors: None = the handle's
+        calibration, one prior for all frames, or a list of one per frame (each a Camera or anything set_cameras takes)."""
+        arr, n = _camera_array(priors)
+        frame = self.cfg.width * self.cfg.height * (2 if depth else 12)
+        _check(lib().ssd_enqueue_ground_fit(self._h, C.c_void_p(d_ptr), stride_bytes or frame, nframes, C.c_void_p(stream or 0),
+                                            INPUT_DEPTH16 if depth else INPUT_VERTICES, arr, n, float(tol)))
+
+    def fetch_ground_fit(self, nframes, min_points=2000, stream=None):
+        """ssd_fetch_ground_fit: waits for the last enqueue_ground_fit -> list of GroundFit (independent copies)"""
+        out = (GroundFit * nframes)()
+        _check(lib().ssd_fetch_ground_fit(self._h, out, nframes, int(min_points), C.c_void_p(stream or 0)))
+        return [GroundFit.from_buffer_copy(r) for r in out]
+
+    def process_host_ground_fit(self, frames, tol, priors=None, depth=False, min_points=2000):
+        """ssd_process_host_ground_fit: frames on the host (float32 [n, H, W, 3], or uint16 [n, H, W] with depth=True) -> list of GroundFit"""
+        a = np.ascontiguousarray(frames, dtype=np.uint16 if depth else np.float32) if not isinstance(frames, PinnedArray) else frames.array
+        per = self.cfg.width * self.cfg.height * (1 if depth else 3)
+        n = a.size // per
+        if n * per != a.size or n < 1:
+            raise SsdError("process_host_ground_fit: array does not hold whole frames")
+        arr, npriors = _camera_array(priors)
+        out = (GroundFit * n)()
+        _check(lib().ssd_process_host_ground_fit(self._h, a.ctypes.data_as(C.c_void_p), n, INPUT_DEPTH16 if depth else INPUT_VERTICES, arr, npriors,
+                                                 float(tol), int(min_points), out))
+        return [GroundFit.from_buffer_copy(r) for r in out]
+
+    def refine_calibration(self, frames, depth=False, prior=None, tolerances=(0.08, 0.03, 0.012), min_points=2000):
+        """One process_host_ground_fit per tolerance, each pass starting from the calibration the pass before gave that frame (riser feet
+        inside a wide band bias its plane: the band shrinks).  prior: None = the handle's calibration, one prior, or one per frame.  A
+        frame whose pass does not end GF_OK keeps its last good calibration and reports the failing status.  -> list of GroundFit"""
+        cams = None if prior is None else _camera_array(prior)[0]
+        fits = None
+        for tol in tolerances:
+            fits = self.process_host_ground_fit(frames, tol, priors=None if cams is None else list(cams), depth=depth, min_points=min_points)
+            if cams is None or len(cams) != len(fits):
+                first = cams[0] if cams is not None else None
+                cams = (Camera * len(fits))()
+                for i in range(len(fits)):
+                    if first is not None:
+                        cams[i] = first
+                    elif depth:                      # the handle's own intrinsics (the first pass ran with them)
+                        cams[i].intr = self._intr
+                        cams[i].has_intrinsics = 1
+            for i, f in enumerate(fits):
+                cams[i].cal = f.cal                 # status != GF_OK: the pass's prior, i.e. the last good calibration
+        return fits
 
     def labels_time_ms(self, back=0):
         """Device time of the label kernel of the enqueue `back` calls ago (0.0: it wrote no labels); timing must be on."""

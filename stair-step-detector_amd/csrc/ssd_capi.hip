@@ -8,7 +8,9 @@
 #include "ssd_launch.h"
 #include "ssd_handle.h"
 #include "ssd_prexy.h"
+#include "ssd_ground.h"
 
+#include <algorithm>
 #include <charconv>
 #include <cmath>
 #include <cstddef>
@@ -115,6 +117,43 @@ int ssd_calibration_identity(ssd_calibration *out)
   return SSD_OK;
 }
 
+/* CameraToWorld from the floor's plane in camera coordinates (unit normal n0 pointing away from the camera, dist = n0 . a point of
+ * the plane): the rest of Transformation_<3>(triangleInPlane), transformation.cpp:108-157, behind its normal.  Shared by
+ * ssd_calibration_from_points and ssd_calibration_from_plane (the ground fit); false in the degenerate cases (reference assert,
+ * transformation.cpp:153). */
+static bool camera_to_world_from_plane(double n0x, double n0y, double n0z, double dist, double a[9], double b[3])
+{
+  struct V3 { double x, y, z; };
+  auto cross = [](V3 p, V3 q) { return V3{ p.y * q.z - p.z * q.y, p.z * q.x - p.x * q.z, p.x * q.y - p.y * q.x }; };
+  auto norm = [](V3 p)
+  {
+    const double m2 = p.x * p.x + p.y * p.y + p.z * p.z;
+    const double rm = 1.0 / std::sqrt(m2);
+    return V3{ p.x * rm, p.y * rm, p.z * rm };
+  };
+  const V3 zB{ -n0x, -n0y, -n0z };
+  const V3 yB = norm(V3{ 0.0, -zB.z / zB.y, 1.0 });
+  const V3 xB = cross(yB, zB);
+  if(!(dist > 0.0) || !std::isfinite(yB.y) || !std::isfinite(xB.x))
+    return false;
+  a[0] = xB.x; a[1] = xB.y; a[2] = xB.z;
+  a[3] = yB.x; a[4] = yB.y; a[5] = yB.z;
+  a[6] = zB.x; a[7] = zB.y; a[8] = zB.z;
+  b[0] = 0.0; b[1] = 0.0; b[2] = dist;
+  return true;
+}
+
+int ssd_calibration_from_plane(const double n0[3], double dist, const ssd_calibration *prior, ssd_calibration *out)
+{
+  if(!n0 || !prior || !out)
+    return fail(SSD_E_ARG, "ssd_calibration_from_plane: null");
+  ssd_calibration r = *prior;                   /* r2, t2, world_z carried over */
+  if(!camera_to_world_from_plane(n0[0], n0[1], n0[2], dist, r.a, r.b))
+    return fail(SSD_E_ARG, "ssd_calibration_from_plane: degenerate plane (reference assert, transformation.cpp:153)");
+  *out = r;
+  return SSD_OK;
+}
+
 /* GeometricTransformation(worldPoints, cameraPoints), transformation.cpp:196-215.
  * Vector algebra as Boost.QVM evaluates it: products summed left to right,
  * normalized(v) = v * (1 / sqrt(dot(v, v))). */
@@ -136,16 +175,9 @@ int ssd_calibration_from_points(const double w[9], const double c[9], ssd_calibr
 
   /* Transformation_<3>(triangleInPlane), transformation.cpp:108-157 */
   const V3 n0 = norm(cross(sub(c1, c0), sub(c2, c0)));
-  const V3 zB{ -n0.x, -n0.y, -n0.z };
-  const V3 yB = norm(V3{ 0.0, -zB.z / zB.y, 1.0 });
-  const V3 xB = cross(yB, zB);
   const double dist = dot(c0, n0);
-  if(!(dist > 0.0) || !std::isfinite(yB.y) || !std::isfinite(xB.x))
+  if(!camera_to_world_from_plane(n0.x, n0.y, n0.z, dist, out->a, out->b))
     return fail(SSD_E_ARG, "ssd_calibration_from_points: degenerate triangle (reference assert, transformation.cpp:153)");
-  out->a[0] = xB.x; out->a[1] = xB.y; out->a[2] = xB.z;
-  out->a[3] = yB.x; out->a[4] = yB.y; out->a[5] = yB.z;
-  out->a[6] = zB.x; out->a[7] = zB.y; out->a[8] = zB.z;
-  out->b[0] = 0.0; out->b[1] = 0.0; out->b[2] = dist;
 
   /* Transformation_<2>({w0, w1}, {cameraToWorld(c0), cameraToWorld(c1)}), transformation.cpp:65-106 */
   auto c2w = [&](V3 p)
@@ -556,6 +588,12 @@ int ssd_destroy(ssd_handle *h)
   }
   if(h->dCams) (void)hipFree(h->dCams);
   if(h->dCamMaps) (void)hipFree(h->dCamMaps);
+  if(h->dGround) (void)hipFree(h->dGround);
+  if(h->hGround) (void)hipHostFree(h->hGround);
+  if(h->dGroundPriors) (void)hipFree(h->dGroundPriors);
+  if(h->hGroundPriors) (void)hipHostFree(h->hGroundPriors);
+  if(h->groundPriorsCopied) (void)hipEventDestroy(h->groundPriorsCopied);
+  if(h->groundDone) (void)hipEventDestroy(h->groundDone);
   if(h->hFallback) (void)hipHostFree(h->hFallback);
   if(h->dDepthMaps) (void)hipFree(h->dDepthMaps);
   if(h->dResults) (void)hipFree(h->dResults);
@@ -1730,6 +1768,352 @@ int ssd_process_host_cameras(ssd_handle *h, const void *frames, int nframes, con
   }
   const size_t frameBytes = static_cast<size_t>(h->P.nPoints) * 12;
   return process_host_impl(h, frames, frameBytes, frameBytes, nframes, results, false, labels, camera_of_frame);
+}
+
+/* ---- ground fit: a calibration refined from the floor in the frames (include/ssd_hip.h) ----------- */
+
+static bool good_intrinsics(const ssd_intrinsics &in)
+{
+  return in.fx != 0.0f && in.fy != 0.0f && in.depth_units > 0.0f;
+}
+
+static void ground_prior_fill(GroundPrior &g, const ssd_calibration &cal, const ssd_intrinsics *in)
+{
+  std::memset(&g, 0, sizeof(g));
+  for(int i = 0; i < 9; i++) g.a[i] = cal.a[i];
+  for(int i = 0; i < 3; i++) g.b[i] = cal.b[i];
+  if(in)
+  {
+    g.ppx = in->ppx; g.ppy = in->ppy; g.fx = in->fx; g.fy = in->fy; g.depthUnits = in->depth_units;
+  }
+}
+
+int ssd_ground_moments_host(const ssd_config *cfg, const ssd_camera *prior, int input, const void *frame, double tol, ssd_ground_moments *out)
+{
+  if(!cfg || !prior || !frame || !out || cfg->width <= 0 || cfg->height <= 0)
+    return fail(SSD_E_ARG, "ssd_ground_moments_host: bad argument");
+  if(input != SSD_INPUT_VERTICES && input != SSD_INPUT_DEPTH16)
+    return fail(SSD_E_ARG, "ssd_ground_moments_host: input must be SSD_INPUT_VERTICES or SSD_INPUT_DEPTH16");
+  if(!(tol > 0.0) || !(tol <= 1.0))
+    return fail(SSD_E_ARG, "ssd_ground_moments_host: tol must lie in (0, 1]");
+  const bool depth = input == SSD_INPUT_DEPTH16;
+  if(depth && (!prior->has_intrinsics || !good_intrinsics(prior->intr)))
+    return fail(SSD_E_ARG, "ssd_ground_moments_host: depth input needs the prior's intrinsics");
+  GroundPrior C;
+  ground_prior_fill(C, prior->cal, depth ? &prior->intr : nullptr);
+  const GroundRange R{ cfg->x_min, cfg->x_max, cfg->y_min, cfg->y_max, tol };
+  const int W = cfg->width, H = cfg->height;
+  long long acc[kGroundSums] = {};
+  if(depth)
+  {
+    const uint16_t *d16 = static_cast<const uint16_t *>(frame);
+    std::vector<float> xm(static_cast<size_t>(W));
+    for(int u = 0; u < W; u++)
+      xm[u] = ground_map_x(C, u);
+    for(int v = 0; v < H; v++)
+    {
+      const float ym = ground_map_y(C, v);
+      for(int u = 0; u < W; u++)
+      {
+        const float d = static_cast<float>(d16[static_cast<size_t>(v) * W + u]) * C.depthUnits;
+        ground_point(C, R, d * xm[u], d * ym, d, acc);
+      }
+    }
+  }
+  else
+  {
+    const float *xyz = static_cast<const float *>(frame);
+    for(size_t i = 0, n = static_cast<size_t>(W) * H; i < n; i++)
+      ground_point(C, R, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], acc);
+  }
+  static_assert(sizeof(ssd_ground_moments) == sizeof(long long) * kGroundSums, "ssd_ground_moments is the kernel's record");
+  std::memcpy(out, acc, sizeof(*out));
+  return SSD_OK;
+}
+
+/* eigenvalues (ascending) and eigenvectors (columns of v) of a symmetric 3 x 3 matrix: cyclic Jacobi */
+static void jacobi3(double a[3][3], double lambda[3], double v[3][3])
+{
+  for(int i = 0; i < 3; i++)
+    for(int j = 0; j < 3; j++)
+      v[i][j] = i == j ? 1.0 : 0.0;
+  for(int sweep = 0; sweep < 64; sweep++)
+  {
+    const double off = std::fabs(a[0][1]) + std::fabs(a[0][2]) + std::fabs(a[1][2]);
+    if(off == 0.0)
+      break;
+    for(int p = 0; p < 2; p++)
+      for(int q = p + 1; q < 3; q++)
+      {
+        if(a[p][q] == 0.0)
+          continue;
+        const double theta = (a[q][q] - a[p][p]) / (2.0 * a[p][q]);
+        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+        const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+        const double app = a[p][p], aqq = a[q][q], apq = a[p][q];
+        a[p][p] = app - t * apq;
+        a[q][q] = aqq + t * apq;
+        a[p][q] = a[q][p] = 0.0;
+        const int r = 3 - p - q;
+        const double arp = a[r][p], arq = a[r][q];
+        a[r][p] = a[p][r] = c * arp - s * arq;
+        a[r][q] = a[q][r] = s * arp + c * arq;
+        for(int k = 0; k < 3; k++)
+        {
+          const double vkp = v[k][p], vkq = v[k][q];
+          v[k][p] = c * vkp - s * vkq;
+          v[k][q] = s * vkp + c * vkq;
+        }
+      }
+  }
+  int order[3] = { 0, 1, 2 };
+  std::sort(order, order + 3, [&](int i, int j) { return a[i][i] < a[j][j]; });
+  double vv[3][3];
+  for(int k = 0; k < 3; k++)
+  {
+    lambda[k] = a[order[k]][order[k]];
+    for(int i = 0; i < 3; i++)
+      vv[i][k] = v[i][order[k]];
+  }
+  std::memcpy(v, vv, sizeof(vv));
+}
+
+int ssd_ground_fit_solve(const ssd_ground_moments *m, const ssd_calibration *prior, int min_points, ssd_ground_fit *out)
+{
+  if(!m || !prior || !out)
+    return fail(SSD_E_ARG, "ssd_ground_fit_solve: null");
+  std::memset(out, 0, sizeof(*out));
+  out->m = *m;
+  out->cal = *prior;
+  const int64_t n = m->n;
+  if(n < (min_points > 1 ? min_points : 1))
+  {
+    out->status = SSD_GF_FEW;
+    return SSD_OK;
+  }
+  /* the centred scatter N SS - S (x) S, exact: N < 2^23 and SS < 2^63, |S| < 2^43, so both products lie below 2^86 */
+  typedef __int128 i128;
+  static const int at[3][3] = { { 0, 1, 2 }, { 1, 3, 4 }, { 2, 4, 5 } };
+  const double scale = 1.0 / (static_cast<double>(n) * static_cast<double>(n) * kGroundScale * kGroundScale);
+  double c[3][3], lambda[3], v[3][3];
+  for(int i = 0; i < 3; i++)
+    for(int j = 0; j < 3; j++)
+      c[i][j] = static_cast<double>(static_cast<i128>(n) * m->ss[at[i][j]] - static_cast<i128>(m->s[i]) * m->s[j]) * scale;   /* m^2 */
+  jacobi3(c, lambda, v);
+  out->status = SSD_GF_DEGENERATE;
+  /* an eigenvalue at the rounding level of the largest one is zero (collinear points leave +-1e-17 lambda_max, of either sign) */
+  const double zero = 64.0 * 2.220446049250313e-16 * lambda[2];
+  const double lmin = lambda[0] > zero ? lambda[0] : 0.0, lmid = lambda[1] > zero ? lambda[1] : 0.0;
+  if(!(lmid > 0.0) || lmid < SSD_GF_PLANARITY * lmin)
+    return SSD_OK;
+  double n0[3] = { v[0][0], v[1][0], v[2][0] };
+  const double rn = 1.0 / std::sqrt(n0[0] * n0[0] + n0[1] * n0[1] + n0[2] * n0[2]);
+  double centroid[3];
+  for(int i = 0; i < 3; i++)
+  {
+    n0[i] *= rn;
+    centroid[i] = static_cast<double>(m->s[i]) / (static_cast<double>(n) * kGroundScale);
+  }
+  double dist = n0[0] * centroid[0] + n0[1] * centroid[1] + n0[2] * centroid[2];
+  if(dist < 0.0)
+  {
+    dist = -dist;
+    for(int i = 0; i < 3; i++)
+      n0[i] = -n0[i];
+  }
+  ssd_calibration cal = *prior;
+  if(!camera_to_world_from_plane(n0[0], n0[1], n0[2], dist, cal.a, cal.b))
+    return SSD_OK;
+  out->status = SSD_GF_OK;
+  out->cal = cal;
+  for(int i = 0; i < 3; i++)
+    out->normal[i] = n0[i];
+  out->dist = dist;
+  out->rms = std::sqrt(lambda[0] > 0.0 ? lambda[0] : 0.0);
+  const double p[3] = { -prior->a[6], -prior->a[7], -prior->a[8] };
+  const double cx = n0[1] * p[2] - n0[2] * p[1], cy = n0[2] * p[0] - n0[0] * p[2], cz = n0[0] * p[1] - n0[1] * p[0];
+  out->tilt = std::atan2(std::sqrt(cx * cx + cy * cy + cz * cz), n0[0] * p[0] + n0[1] * p[1] + n0[2] * p[2]);
+  out->height_delta = dist - prior->b[2];
+  return SSD_OK;
+}
+
+/* the buffers of the ground fit, on its first call */
+static int ground_prepare(ssd_handle *h)
+{
+  if(h->dGround)
+    return SSD_OK;
+  const size_t recBytes = sizeof(long long) * kGroundSums * static_cast<size_t>(h->F), priorBytes = sizeof(GroundPrior) * static_cast<size_t>(h->F);
+  hipError_t e = hipMalloc(&h->dGround, recBytes);
+  if(e == hipSuccess) e = hipHostMalloc(&h->hGround, recBytes, hipHostMallocDefault);
+  if(e == hipSuccess) e = hipMalloc(&h->dGroundPriors, priorBytes);
+  if(e == hipSuccess) e = hipHostMalloc(&h->hGroundPriors, priorBytes, hipHostMallocDefault);
+  if(e == hipSuccess) e = hipEventCreateWithFlags(&h->groundPriorsCopied, hipEventDisableTiming);
+  if(e == hipSuccess) e = hipEventCreateWithFlags(&h->groundDone, hipEventDisableTiming);
+  if(e != hipSuccess)
+  {
+    if(h->dGround) (void)hipFree(h->dGround);
+    if(h->hGround) (void)hipHostFree(h->hGround);
+    if(h->dGroundPriors) (void)hipFree(h->dGroundPriors);
+    if(h->hGroundPriors) (void)hipHostFree(h->hGroundPriors);
+    if(h->groundPriorsCopied) (void)hipEventDestroy(h->groundPriorsCopied);
+    if(h->groundDone) (void)hipEventDestroy(h->groundDone);
+    h->dGround = nullptr; h->hGround = nullptr; h->dGroundPriors = nullptr; h->hGroundPriors = nullptr;
+    h->groundPriorsCopied = nullptr; h->groundDone = nullptr;
+    (void)hipGetLastError();
+    return fail(e == hipErrorOutOfMemory ? SSD_E_NOMEM : SSD_E_HIP, std::string("ssd_enqueue_ground_fit: its buffers: ") + hipGetErrorString(e));
+  }
+  h->groundBytes = recBytes + priorBytes;
+  h->bytes += h->groundBytes;
+  return SSD_OK;
+}
+
+/* the refusals of a ground-fit call, before anything is launched or copied */
+static int check_ground_fit(const ssd_handle *h, const char *who, int input, const ssd_camera *priors, int npriors, int nframes, double tol)
+{
+  if(input != SSD_INPUT_VERTICES && input != SSD_INPUT_DEPTH16)
+    return fail(SSD_E_ARG, std::string(who) + ": input must be SSD_INPUT_VERTICES or SSD_INPUT_DEPTH16");
+  if(!(tol > 0.0) || !(tol <= 1.0))
+    return fail(SSD_E_ARG, std::string(who) + ": tol must lie in (0, 1]");
+  if(npriors != 0 && npriors != 1 && npriors != nframes)
+    return fail(SSD_E_ARG, std::string(who) + ": npriors must be 0, 1 or nframes");
+  if(npriors > 0 && !priors)
+    return fail(SSD_E_ARG, std::string(who) + ": null priors");
+  if(input == SSD_INPUT_DEPTH16)
+  {
+    if(npriors == 0 && !h->haveIntr)
+      return fail(SSD_E_ARG, std::string(who) + ": depth input with the handle's calibration: call ssd_set_intrinsics first");
+    for(int i = 0; i < npriors; i++)
+      if(!priors[i].has_intrinsics || !good_intrinsics(priors[i].intr))
+        return fail(SSD_E_ARG, std::string(who) + ": depth input, and prior " + std::to_string(i) + " has no (valid) intrinsics");
+  }
+  return SSD_OK;
+}
+
+/* arguments checked by the callers */
+static int enqueue_ground_fit_impl(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, hipStream_t s, int input,
+                                   const ssd_camera *priors, int npriors, double tol)
+{
+  const bool depth = input == SSD_INPUT_DEPTH16;
+  const size_t unit = depth ? 2 : 4, frameBytes = static_cast<size_t>(h->P.nPoints) * (depth ? 2 : 12);
+  if(reinterpret_cast<size_t>(d_frames) % unit != 0 || frame_stride_bytes % unit != 0 || (nframes > 1 && frame_stride_bytes < frameBytes))
+    return fail(SSD_E_ARG, "ssd_enqueue_ground_fit: frames must be aligned to their element and the stride must hold a frame");
+  HIP_TRY(hipSetDevice(h->device));
+  const int rc = ground_prepare(h);
+  if(rc) return rc;
+  if(h->groundHaveLast)
+  {
+    HIP_TRY(hipEventSynchronize(h->groundPriorsCopied));          /* the pinned priors of the previous call have gone over */
+    if(s != h->groundLastStream)
+      HIP_TRY(hipStreamWaitEvent(s, h->groundDone, 0));            /* another stream: behind the previous call */
+  }
+  const int np = npriors > 0 ? npriors : 1;
+  h->groundPriorCal.resize(static_cast<size_t>(np));
+  if(npriors == 0)
+  {
+    ssd_calibration &c = h->groundPriorCal[0];
+    for(int i = 0; i < 9; i++) c.a[i] = h->P.pt.a[i];
+    for(int i = 0; i < 3; i++) c.b[i] = h->P.pt.b[i];
+    for(int i = 0; i < 4; i++) c.r2[i] = h->P.r2[i];
+    c.t2[0] = h->P.t2[0]; c.t2[1] = h->P.t2[1];
+    c.world_z = h->P.worldZ;
+    ground_prior_fill(h->hGroundPriors[0], c, depth ? &h->intr : nullptr);
+  }
+  else
+    for(int i = 0; i < np; i++)
+    {
+      h->groundPriorCal[i] = priors[i].cal;
+      ground_prior_fill(h->hGroundPriors[i], priors[i].cal, depth ? &priors[i].intr : nullptr);
+    }
+  const size_t recBytes = sizeof(long long) * kGroundSums * static_cast<size_t>(nframes);
+  HIP_TRY(hipMemcpyAsync(h->dGroundPriors, h->hGroundPriors, sizeof(GroundPrior) * static_cast<size_t>(np), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipEventRecord(h->groundPriorsCopied, s));
+  HIP_TRY(hipMemsetAsync(h->dGround, 0, recBytes, s));
+  const GroundRange R{ h->cfg.x_min, h->cfg.x_max, h->cfg.y_min, h->cfg.y_max, tol };
+  launch_ground_moments(d_frames, frame_stride_bytes, h->P.W, h->P.H, nframes, depth, h->dGroundPriors, np > 1 ? 1 : 0, R, h->dGround, s);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(h->hGround, h->dGround, recBytes, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipEventRecord(h->groundDone, s));
+  h->groundLastStream = s;
+  h->groundHaveLast = true;
+  h->groundFrames = nframes;
+  return SSD_OK;
+}
+
+int ssd_enqueue_ground_fit(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream, int input,
+                           const ssd_camera *priors, int npriors, double tol)
+{
+  if(!h || !d_frames)
+    return fail(SSD_E_ARG, "ssd_enqueue_ground_fit: null argument");
+  if(nframes < 1 || nframes > h->F)
+    return fail(SSD_E_ARG, "ssd_enqueue_ground_fit: nframes must be 1..max_frames_per_batch");
+  const int rc = check_ground_fit(h, "ssd_enqueue_ground_fit", input, priors, npriors, nframes, tol);
+  if(rc) return rc;
+  return enqueue_ground_fit_impl(h, d_frames, frame_stride_bytes, nframes, static_cast<hipStream_t>(stream), input, priors, npriors, tol);
+}
+
+int ssd_fetch_ground_fit(ssd_handle *h, ssd_ground_fit *out, int nframes, int min_points, void *)
+{
+  if(!h || !out)
+    return fail(SSD_E_ARG, "ssd_fetch_ground_fit: null argument");
+  if(!h->groundHaveLast || nframes < 1 || nframes > h->groundFrames)
+    return fail(SSD_E_ARG, "ssd_fetch_ground_fit: nframes must be 1..the frames of the last ssd_enqueue_ground_fit");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipEventSynchronize(h->groundDone));
+  const bool each = h->groundPriorCal.size() > 1;
+  for(int i = 0; i < nframes; i++)
+  {
+    ssd_ground_moments m;
+    std::memcpy(&m, h->hGround + static_cast<size_t>(i) * kGroundSums, sizeof(m));
+    const int rc = ssd_ground_fit_solve(&m, &h->groundPriorCal[each ? i : 0], min_points, out + i);
+    if(rc) return rc;
+  }
+  return SSD_OK;
+}
+
+int ssd_process_host_ground_fit(ssd_handle *h, const void *frames, int nframes, int input, const ssd_camera *priors, int npriors,
+                                double tol, int min_points, ssd_ground_fit *out)
+{
+  if(!h || !frames || !out || nframes < 1)
+    return fail(SSD_E_ARG, "ssd_process_host_ground_fit: bad argument");
+  int rc = check_ground_fit(h, "ssd_process_host_ground_fit", input, priors, npriors, nframes, tol);
+  if(rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const bool depth = input == SSD_INPUT_DEPTH16;
+  const size_t srcFrameBytes = static_cast<size_t>(h->P.nPoints) * (depth ? 2 : 12);
+  const size_t devFrameBytes = (srcFrameBytes + 15) / 16 * 16;        /* every frame on a 16-byte boundary: the kernel's wide loads */
+  const int slice = h->F < kIngestFrames ? h->F : kIngestFrames;
+  rc = ingest_prepare(h, static_cast<size_t>(slice) * devFrameBytes);
+  if(rc) return rc;
+  const unsigned char *from = static_cast<const unsigned char *>(frames);
+  int prevFrames = 0, prevAt = 0, c = 0;
+  for(int done = 0; done < nframes; c++)
+  {
+    const int n = nframes - done < slice ? nframes - done : slice;
+    const int k = c & 1;
+    if(c >= 2)
+      HIP_TRY(hipStreamWaitEvent(h->ingestCopy, h->ingestConsumed[k], 0));        /* the kernel of slice c - 2 read this buffer */
+    const unsigned char *at = from + static_cast<size_t>(done) * srcFrameBytes;
+    if(srcFrameBytes == devFrameBytes)
+      HIP_TRY(hipMemcpyAsync(h->ingestBuf[k], at, static_cast<size_t>(n) * srcFrameBytes, hipMemcpyHostToDevice, h->ingestCopy));
+    else
+      HIP_TRY(hipMemcpy2DAsync(h->ingestBuf[k], devFrameBytes, at, srcFrameBytes, srcFrameBytes, n, hipMemcpyHostToDevice, h->ingestCopy));
+    HIP_TRY(hipEventRecord(h->ingestCopied[k], h->ingestCopy));
+    /* the records are one set: the slice before is solved (its kernel ran beside this slice's copy) before this one's kernel goes out */
+    if(prevFrames)
+    {
+      rc = ssd_fetch_ground_fit(h, out + prevAt, prevFrames, min_points, nullptr);
+      if(rc) return rc;
+    }
+    HIP_TRY(hipStreamWaitEvent(h->ingestCompute, h->ingestCopied[k], 0));
+    rc = enqueue_ground_fit_impl(h, h->ingestBuf[k], devFrameBytes, n, h->ingestCompute, input, npriors == nframes && npriors > 1 ? priors + done : priors,
+                                 npriors == nframes && npriors > 1 ? n : npriors, tol);
+    if(rc) return rc;
+    HIP_TRY(hipEventRecord(h->ingestConsumed[k], h->ingestCompute));
+    prevFrames = n;
+    prevAt = done;
+    done += n;
+  }
+  return ssd_fetch_ground_fit(h, out + prevAt, prevFrames, min_points, nullptr);
 }
 
 /* pinned host memory for frames (DMA without a staging copy) */

@@ -8,6 +8,8 @@
 #include "ssd_device.h"
 #include <vector>
 
+namespace ssd { struct GroundPrior; }          /* ssd_ground.h */
+
 /* Launch-geometry constants of a handle.  The product uses the compiled defaults below (each one measured: ssd_capi.hip,
  * choose_chunk / enqueue_impl).  Only a tools build (make EXTRA=-DSSD_TUNING OUT=../lib_tuning, tools/exp*.sh) reads
  * overrides from the environment (SSD_CHUNK_POINTS, SSD_TARGET_BLOCKS, SSD_K1_BLOCKS_PER_FRAME, SSD_K24_MIN_BLOCKS,
@@ -132,6 +134,19 @@ struct ssd_handle
   unsigned long long camCallKey = ~0ull;
   double camCallTol = 0.0;
   size_t camBytes = 0;                      /* the table's share of `bytes` */
+  /* the ground fit (ssd_enqueue_ground_fit & co.): made on its first call, so a handle that never fits holds
+   * none of them.  One set, used in stream order like a handle's one workspace; nothing of the lanes is touched. */
+  long long *dGround = nullptr;             /* F records of kGroundSums int64 (ssd_ground_moments) */
+  long long *hGround = nullptr;             /* pinned: a call's last step copies its records here */
+  ssd::GroundPrior *dGroundPriors = nullptr;   /* F */
+  ssd::GroundPrior *hGroundPriors = nullptr;   /* pinned: the caller's priors are restated here during the call */
+  hipEvent_t groundPriorsCopied = nullptr;  /* behind the copy pinned -> device: the pinned priors may be written again */
+  hipEvent_t groundDone = nullptr;          /* behind the call's last step */
+  hipStream_t groundLastStream = nullptr;   /* the stream of the previous call (a switch is ordered by groundDone) */
+  bool groundHaveLast = false;
+  int groundFrames = 0;                     /* frames of the last call */
+  std::vector<ssd_calibration> groundPriorCal;   /* its priors, one or one per frame: what ssd_fetch_ground_fit solves against */
+  size_t groundBytes = 0;                   /* their share of `bytes` */
 };
 
 #endif /* SSD_HANDLE_H_ */
