@@ -397,6 +397,77 @@ int ssd_fetch_ground_fit(ssd_handle *h, ssd_ground_fit *out, int nframes, int mi
 int ssd_process_host_ground_fit(ssd_handle *h, const void *frames, int nframes, int input, const ssd_camera *priors, int npriors,
                                 double tol, int min_points, ssd_ground_fit *out);
 
+/* ---- surface fit: plane, tilt and flatness of every reported surface ----------------------------------------------------
+ * EXTENSION.  The per-pixel labels say which points carry each reported surface; the ground fit turns points
+ * into exact integer moments and a plane.  Joined: one more pass behind k_final gathers, per frame, the moments of every surface of
+ * its ssd_frame_result - about 1.5 KB per frame instead of a byte per point - and a small host solve turns them into a plane each.
+ * The moments of surface k of a frame are the ten sums of ssd_ground_moments over exactly the points whose label (above) would be
+ * k + 1: q = llrint(double(v) * 65536.0) on the float camera coordinates (16-bit depth input is deprojected first, bit-equal to
+ * ssd_deproject_host); a labelled point with some |q| >= 2^20 (|v| >= 16 m) is left out of the sums and counted in n_far.  The
+ * overflow argument is the ground fit's: all sums are exact integers, independent of the order of summation, and the device and
+ * ssd_surface_moments_host agree bit for bit.  So m.n + n_far of surface k is its n_in_quad (the ground: ground_n_in_quad).
+ * Surface order is k_final's, as for labels; records at k >= n_surfaces are zero; a frame with SSD_ST_THROW or n_steps == 0 is all
+ * zero.  Surface 0's m of a frame with ground = 1 goes straight into ssd_ground_fit_solve: the detector's own ground points lie
+ * inside the ground quadrilateral, in front of the first riser, so a calibration can be polished or watched for drift in the same
+ * call that detects.
+ * Camera batches (ssd_enqueue_cameras, ssd_process_host_cameras) are out of scope: they have no surface moments. */
+typedef struct
+{
+  ssd_ground_moments m;
+  int64_t n_far;      /* labelled points left out of m: some |q| >= 2^20 */
+} ssd_surface_moments;
+
+typedef struct
+{
+  int32_t n_surfaces; /* the frame's n_steps */
+  int32_t ground;     /* 1: surface 0 is the ground (quirk Q6 included: the ground reported as the all-zero surface) */
+  ssd_surface_moments s[SSD_MAX_STEPS];
+} ssd_frame_moments;
+
+typedef struct
+{
+  int32_t status, reserved;   /* SSD_GF_OK / SSD_GF_FEW / SSD_GF_DEGENERATE */
+  int64_t n, n_far;
+  double normal[3];   /* unit, pointing up, external world coordinates (as ssd_step's corners) */
+  double centroid[3]; /* mean of the surface's points, external world: x, y as ssd_step's corners, z + world_z as ssd_step.height */
+  double tilt;        /* angle between normal and the vertical, radians */
+  double rms;         /* sqrt(lambda_min): rms distance of the points from the plane, metres */
+  double extent[2];   /* sqrt(lambda_max), sqrt(lambda_mid): rms half-extents of the points within the plane, metres */
+} ssd_surface_fit;
+
+typedef struct
+{
+  int32_t n_surfaces, ground;
+  ssd_surface_fit s[SSD_MAX_STEPS];
+} ssd_frame_surfaces;
+
+/* ssd_enqueue / ssd_enqueue_depth plus the frames' surface moments: frame i's record at d_out + i (device memory, nframes contiguous
+ * records).  The contracts are those of ssd_enqueue_labels: the pass runs behind k_final and in front of the batch's completion
+ * event, so the records are complete when ssd_fetch / ssd_fetch_back of the batch returns, and for a stream made to wait with
+ * ssd_stream_wait; with several workspaces the batches take them in turn like any others.  The records are zeroed on the batch's
+ * stream in front of the pass.  A null destination: SSD_E_ARG.  A handle that never asks for surface moments allocates and launches
+ * nothing for them. */
+int ssd_enqueue_surface_moments(ssd_handle *h, const void *d_xyz, size_t frame_stride_bytes, int nframes, void *stream, ssd_frame_moments *d_out);
+int ssd_enqueue_depth_surface_moments(ssd_handle *h, const void *d_depth, size_t frame_stride_bytes, int nframes, void *stream, ssd_frame_moments *d_out);
+/* the pass's device time for the same enqueue (0 when that enqueue gathered no surface moments); as ssd_get_labels_time_back */
+int ssd_get_surface_moments_time_back(ssd_handle *h, int back, float *ms);
+/* host only, no GPU needed: one frame's sums from a label array (width * height bytes, as the label entry points write them; a label
+ * above n_surfaces: SSD_E_ARG).  input = SSD_INPUT_VERTICES (width * height xyz floats) or SSD_INPUT_DEPTH16 (width * height uint16,
+ * intr required, else ignored).  n_surfaces (0 .. SSD_MAX_STEPS) and ground go into the record's header as given. */
+int ssd_surface_moments_host(const ssd_config *cfg, int input, const ssd_intrinsics *intr, const void *frame, const uint8_t *labels,
+                             int n_surfaces, int ground, ssd_frame_moments *out);
+/* host only: a frame's moments -> a plane per surface, by the solve of ssd_ground_fit_solve (the same code, shared: exact centred
+ * scatter, cyclic Jacobi, n0 = the eigenvector of lambda_min signed away from the camera).  Status per surface in this order: FEW
+ * (n < max(min_points, 1)), DEGENERATE (lambda_mid <= 0 or lambda_mid < SSD_GF_PLANARITY * lambda_min, eigenvalues at the rounding
+ * level counting as 0), OK.  normal = -(A n0), its x and y through r2; centroid through CameraToWorld and ToExternalWorld; tilt,
+ * rms, extent as above.  Unless OK the doubles are 0; n and n_far are always the moments'.  Records at k >= n_surfaces are zero. */
+int ssd_surface_fit_solve(const ssd_frame_moments *moments, const ssd_calibration *cal, int min_points, ssd_frame_surfaces *out);
+/* frames in host memory (input = SSD_INPUT_VERTICES: as ssd_process_host; SSD_INPUT_DEPTH16: as ssd_process_depth_host), through the
+ * same slices: fills results[nframes], out[nframes] (each frame's moments solved against the handle's calibration) and, when not
+ * NULL, moments[nframes]; returns when all of it is there. */
+int ssd_process_host_surfaces(ssd_handle *h, const void *frames, int nframes, int input, ssd_frame_result *results,
+                              ssd_frame_moments *moments, int min_points, ssd_frame_surfaces *out);
+
 /* stage selector for profiling / roofline measurement: runs only the chosen stage(s) of the pipeline */
 #define SSD_STAGE_HIST 1       /* K1: transform + crop + bin + histogram */
 #define SSD_STAGE_PEAKS 2

@@ -144,6 +144,27 @@ class GroundFit(C.Structure):
                 ("rms", C.c_double), ("tilt", C.c_double), ("height_delta", C.c_double), ("cal", Calibration)]
 
 
+class SurfaceMoments(C.Structure):
+    """ssd_surface_moments: the ten sums of the points of one surface, and the labelled points at or beyond 16 m left out of them"""
+    _fields_ = [("m", GroundMoments), ("n_far", C.c_int64)]
+
+
+class FrameMoments(C.Structure):
+    """ssd_frame_moments: a frame's surfaces (the order of its FrameResult) as exact integer moments (surface fit)"""
+    _fields_ = [("n_surfaces", C.c_int32), ("ground", C.c_int32), ("s", SurfaceMoments * MAX_STEPS)]
+
+
+class SurfaceFit(C.Structure):
+    """ssd_surface_fit: one surface's plane in external world coordinates (status != GF_OK: the doubles are 0)"""
+    _fields_ = [("status", C.c_int32), ("reserved", C.c_int32), ("n", C.c_int64), ("n_far", C.c_int64), ("normal", C.c_double * 3),
+                ("centroid", C.c_double * 3), ("tilt", C.c_double), ("rms", C.c_double), ("extent", C.c_double * 2)]
+
+
+class FrameSurfaces(C.Structure):
+    """ssd_frame_surfaces: the fitted plane of every surface of a frame"""
+    _fields_ = [("n_surfaces", C.c_int32), ("ground", C.c_int32), ("s", SurfaceFit * MAX_STEPS)]
+
+
 class Scene(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32),
                 ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
@@ -175,6 +196,8 @@ EXPORTS = [
     "ssd_set_cameras", "ssd_camera_count", "ssd_enqueue_cameras", "ssd_process_host_cameras",
     "ssd_calibration_from_plane", "ssd_ground_moments_host", "ssd_ground_fit_solve", "ssd_enqueue_ground_fit", "ssd_fetch_ground_fit",
     "ssd_process_host_ground_fit",
+    "ssd_enqueue_surface_moments", "ssd_enqueue_depth_surface_moments", "ssd_get_surface_moments_time_back", "ssd_surface_moments_host",
+    "ssd_surface_fit_solve", "ssd_process_host_surfaces",
 ]
 # libssd_source.so — the frame source standing in for the camera (include/ssd_source.h)
 SOURCE_EXPORTS = [
@@ -247,6 +270,12 @@ def lib():
     L.ssd_enqueue_ground_fit.argtypes = [vp, vp, sz, i32, vp, i32, C.POINTER(Camera), i32, C.c_double]
     L.ssd_fetch_ground_fit.argtypes = [vp, C.POINTER(GroundFit), i32, i32, vp]
     L.ssd_process_host_ground_fit.argtypes = [vp, vp, i32, i32, C.POINTER(Camera), i32, C.c_double, i32, C.POINTER(GroundFit)]
+    L.ssd_enqueue_surface_moments.argtypes = [vp, vp, sz, i32, vp, vp]
+    L.ssd_enqueue_depth_surface_moments.argtypes = [vp, vp, sz, i32, vp, vp]
+    L.ssd_get_surface_moments_time_back.argtypes = [vp, i32, C.POINTER(C.c_float)]
+    L.ssd_surface_moments_host.argtypes = [C.POINTER(Config), i32, C.POINTER(Intrinsics), vp, vp, i32, i32, C.POINTER(FrameMoments)]
+    L.ssd_surface_fit_solve.argtypes = [C.POINTER(FrameMoments), C.POINTER(Calibration), i32, C.POINTER(FrameSurfaces)]
+    L.ssd_process_host_surfaces.argtypes = [vp, vp, i32, i32, C.POINTER(FrameResult), C.POINTER(FrameMoments), i32, C.POINTER(FrameSurfaces)]
     L.ssd_serialize.argtypes = [C.POINTER(FrameResult), C.c_char_p, sz]
     L.ssd_set_debug.argtypes = [vp, i32]
     L.ssd_get_debug.argtypes = [vp, i32, C.POINTER(DebugFrame)]
@@ -449,6 +478,29 @@ def ground_fit_solve(moments, prior, min_points=2000):
     p = prior.constants if isinstance(prior, GeometricTransformation) else prior.cal if isinstance(prior, Camera) else prior
     out = GroundFit()
     _check(lib().ssd_ground_fit_solve(C.byref(moments), C.byref(p), int(min_points), C.byref(out)))
+    return out
+
+
+# --------------------------------------------------------------------------- surface fit: host functions (no GPU needed)
+def surface_moments_host(cfg, frame, labels, n_surfaces, ground, intr=None):
+    """ssd_surface_moments_host: one frame's per-surface sums from its labels (uint8 [H, W], label k + 1 = surface k) -> FrameMoments.
+    frame: float32 [H, W, 3], or uint16 [H, W] with intr (an Intrinsics: 16-bit depth input)."""
+    depth = intr is not None
+    a = np.ascontiguousarray(frame, dtype=np.uint16 if depth else np.float32)
+    lab = np.ascontiguousarray(labels, dtype=np.uint8)
+    if a.size != cfg.width * cfg.height * (1 if depth else 3) or lab.size != cfg.width * cfg.height:
+        raise SsdError("surface_moments_host: the arrays are not one frame")
+    out = FrameMoments()
+    _check(lib().ssd_surface_moments_host(C.byref(cfg), INPUT_DEPTH16 if depth else INPUT_VERTICES, C.byref(intr) if depth else None,
+                                          a.ctypes.data_as(C.c_void_p), lab.ctypes.data_as(C.c_void_p), int(n_surfaces), int(ground), C.byref(out)))
+    return out
+
+
+def surface_fit_solve(moments, cal, min_points=200):
+    """ssd_surface_fit_solve: a frame's moments -> a plane per surface (FrameSurfaces; per surface GF_OK / GF_FEW / GF_DEGENERATE)"""
+    c = cal.constants if isinstance(cal, GeometricTransformation) else cal.cal if isinstance(cal, Camera) else cal
+    out = FrameSurfaces()
+    _check(lib().ssd_surface_fit_solve(C.byref(moments), C.byref(c), int(min_points), C.byref(out)))
     return out
 
 
@@ -703,6 +755,33 @@ class Detector:
             for i, f in enumerate(fits):
                 cams[i].cal = f.cal                 # status != GF_OK: the pass's prior, i.e. the last good calibration
         return fits
+
+    # ---- surface fit: plane, tilt and flatness of every reported surface (include/ssd_hip.h)
+    def enqueue_surface_moments(self, d_ptr, nframes, d_moments, depth=False, stride_bytes=None, stream=None):
+        """ssd_enqueue (depth=True: ssd_enqueue_depth) plus the frames' surface moments: frame i's FrameMoments at
+        d_moments + i * sizeof(FrameMoments) in device memory, complete when fetch() of the batch returns"""
+        fn = lib().ssd_enqueue_depth_surface_moments if depth else lib().ssd_enqueue_surface_moments
+        frame = self.cfg.width * self.cfg.height * 2 if depth else self.frame_bytes
+        _check(fn(self._h, C.c_void_p(d_ptr), stride_bytes or frame, nframes, C.c_void_p(stream or 0), C.c_void_p(d_moments)))
+
+    def process_host_surfaces(self, frames, depth=False, min_points=200, moments=False):
+        """ssd_process_host_surfaces: frames on the host (float32 [n, H, W, 3], or uint16 [n, H, W] with depth=True)
+        -> (list of FrameResult, list of FrameSurfaces), with moments=True also the list of FrameMoments"""
+        a = np.ascontiguousarray(frames, dtype=np.uint16 if depth else np.float32)
+        per = self.cfg.width * self.cfg.height * (1 if depth else 3)
+        n = a.size // per
+        if n < 1 or n * per != a.size:
+            raise SsdError("process_host_surfaces: array does not hold whole frames")
+        res, mom, out = (FrameResult * n)(), (FrameMoments * n)(), (FrameSurfaces * n)()
+        _check(lib().ssd_process_host_surfaces(self._h, a.ctypes.data_as(C.c_void_p), n, INPUT_DEPTH16 if depth else INPUT_VERTICES, res,
+                                               mom if moments else None, int(min_points), out))
+        return (list(res), list(out), list(mom)) if moments else (list(res), list(out))
+
+    def surface_moments_time_ms(self, back=0):
+        """Device time of the surface-moments pass of the enqueue `back` calls ago (0.0: it gathered none); timing must be on."""
+        ms = C.c_float(0.0)
+        _check(lib().ssd_get_surface_moments_time_back(self._h, back, C.byref(ms)))
+        return float(ms.value)
 
     def labels_time_ms(self, back=0):
         """Device time of the label kernel of the enqueue `back` calls ago (0.0: it wrote no labels); timing must be on."""

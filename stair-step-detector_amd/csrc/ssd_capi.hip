@@ -617,6 +617,8 @@ int ssd_destroy(ssd_handle *h)
   if(h->dDebugImg) (void)hipFree(h->dDebugImg);
   for(hipEvent_t e : h->evPredict)
     if(e) (void)hipEventDestroy(e);
+  for(hipEvent_t e : h->evSurface)
+    (void)hipEventDestroy(e);
   for(hipEvent_t e : h->evLabels)
     (void)hipEventDestroy(e);
   for(int k = 0; k < 2; k++)
@@ -879,12 +881,35 @@ static unsigned long long cameras_call_key(const Params &P)
          | static_cast<unsigned long long>(static_cast<unsigned int>(P.riserMinSupport)) << 2;
 }
 
-/* camOf (host, nframes entries; ssd_enqueue_cameras has checked them): a cameras batch - frame i takes camera camOf[i] of the table */
+/* SSD_TIMING_SLOTS pairs of events around an optional pass (k_labels, k_surface_moments) of a timed enqueue: all of them or none */
+static int timing_event_pairs(std::vector<hipEvent_t> &out, const char *who)
+{
+  std::vector<hipEvent_t> ev;
+  for(int i = 0; i < 2 * SSD_TIMING_SLOTS; i++)
+  {
+    hipEvent_t e;
+    const hipError_t rc = hipEventCreate(&e);
+    if(rc != hipSuccess)
+    {
+      for(hipEvent_t made : ev)
+        (void)hipEventDestroy(made);
+      return fail(SSD_E_HIP, std::string(who) + hipGetErrorString(rc));
+    }
+    ev.push_back(e);
+  }
+  out.swap(ev);
+  return SSD_OK;
+}
+
+/* camOf (host, nframes entries; ssd_enqueue_cameras has checked them): a cameras batch - frame i takes camera camOf[i] of the table;
+ * moments (device, nframes records): the surface moments of the batch (the handle's one calibration only) */
 static int enqueue_impl(ssd_handle *h, const void *d_xyz, size_t frame_stride_bytes, int nframes, void *stream, int stages, bool depthInput,
-                        unsigned char *labels = nullptr, size_t labelStride = 0, const uint16_t *camOf = nullptr)
+                        unsigned char *labels = nullptr, size_t labelStride = 0, const uint16_t *camOf = nullptr, ssd_frame_moments *moments = nullptr)
 {
   if(!h || !d_xyz)
     return fail(SSD_E_ARG, "ssd_enqueue: null argument");
+  if(moments && (camOf || stages != SSD_STAGE_ALL))
+    return fail(SSD_E_ARG, "ssd_enqueue_surface_moments: camera batches and partial runs have no surface moments");
   if(nframes < 1 || nframes > h->F)
     return fail(SSD_E_ARG, "ssd_enqueue: nframes must be 1..max_frames_per_batch");
   const size_t frameBytes = static_cast<size_t>(h->P.nPoints) * (depthInput ? 2 : 12);
@@ -1022,22 +1047,16 @@ static int enqueue_impl(ssd_handle *h, const void *d_xyz, size_t frame_stride_by
   if(labels && timing && h->evLabels.empty())
   {
     /* the label kernel's events, on the first timed enqueue that labels */
-    std::vector<hipEvent_t> ev;
-    for(int i = 0; i < 2 * SSD_TIMING_SLOTS; i++)
-    {
-      hipEvent_t e;
-      const hipError_t rc = hipEventCreate(&e);
-      if(rc != hipSuccess)
-      {
-        for(hipEvent_t made : ev)
-          (void)hipEventDestroy(made);
-        return fail(SSD_E_HIP, std::string("hipEventCreate (labels): ") + hipGetErrorString(rc));
-      }
-      ev.push_back(e);
-    }
-    h->evLabels.swap(ev);
+    const int rcEv = timing_event_pairs(h->evLabels, "hipEventCreate (labels): ");
+    if(rcEv) return rcEv;
   }
   h->labelsTimed[timingSlot] = labels != nullptr && timing;
+  if(moments && timing && h->evSurface.empty())
+  {
+    const int rcEv = timing_event_pairs(h->evSurface, "hipEventCreate (surface moments): ");
+    if(rcEv) return rcEv;
+  }
+  h->surfaceTimed[timingSlot] = moments != nullptr && timing;
   int evi = timingSlot * 8;
 
   const int slot = static_cast<int>(h->finalCount % static_cast<unsigned long long>(h->nSlots));
@@ -1092,6 +1111,14 @@ static int enqueue_impl(ssd_handle *h, const void *d_xyz, size_t frame_stride_by
       if(marks) (void)hipEventRecord(h->evLabels[2 * timingSlot], cs);
       launch_labels(xyz, strideFloats, P, L.dState, L.dTileMasks, h->tileMaskStride, nframes, chunk, depth, labels, labelStride, cs, cams);
       if(marks) (void)hipEventRecord(h->evLabels[2 * timingSlot + 1], cs);
+    }
+    /* per-surface moments: likewise; the records are zeroed on the batch's stream in front of the kernel, which only adds */
+    if(moments)
+    {
+      if(marks) (void)hipEventRecord(h->evSurface[2 * timingSlot], cs);
+      (void)hipMemsetAsync(moments, 0, sizeof(ssd_frame_moments) * static_cast<size_t>(nframes), cs);
+      launch_surface_moments(xyz, strideFloats, P, L.dState, L.dTileMasks, h->tileMaskStride, nframes, chunk, depth, moments, cs);
+      if(marks) (void)hipEventRecord(h->evSurface[2 * timingSlot + 1], cs);
     }
   };
 
@@ -1200,6 +1227,20 @@ int ssd_enqueue_depth_labels(ssd_handle *h, const void *d_depth, size_t frame_st
   return enqueue_impl(h, d_depth, frame_stride_bytes, nframes, stream, SSD_STAGE_ALL, true, d_labels, label_stride_bytes);
 }
 
+int ssd_enqueue_surface_moments(ssd_handle *h, const void *d_xyz, size_t frame_stride_bytes, int nframes, void *stream, ssd_frame_moments *d_out)
+{
+  if(!h || !d_out)
+    return fail(SSD_E_ARG, "ssd_enqueue_surface_moments: null argument");
+  return enqueue_impl(h, d_xyz, frame_stride_bytes, nframes, stream, SSD_STAGE_ALL, false, nullptr, 0, nullptr, d_out);
+}
+
+int ssd_enqueue_depth_surface_moments(ssd_handle *h, const void *d_depth, size_t frame_stride_bytes, int nframes, void *stream, ssd_frame_moments *d_out)
+{
+  if(!h || !d_out)
+    return fail(SSD_E_ARG, "ssd_enqueue_depth_surface_moments: null argument");
+  return enqueue_impl(h, d_depth, frame_stride_bytes, nframes, stream, SSD_STAGE_ALL, true, nullptr, 0, nullptr, d_out);
+}
+
 /* rs2::pointcloud's maps (librealsense2 src/proc/pointcloud.cpp, pre_compute_x_y_map), float arithmetic */
 static void depth_maps(const ssd_intrinsics &in, int W, int H, std::vector<float> &maps)
 {
@@ -1298,6 +1339,24 @@ int ssd_get_labels_time_back(ssd_handle *h, int back, float *ms)
     return SSD_OK;
   HIP_TRY(hipEventSynchronize(h->evLabels[2 * slot + 1]));
   HIP_TRY(hipEventElapsedTime(ms, h->evLabels[2 * slot], h->evLabels[2 * slot + 1]));
+  return SSD_OK;
+}
+
+/* k_surface_moments' time (with the memset in front of it) for the same enqueue (0 for an enqueue that gathered none) */
+int ssd_get_surface_moments_time_back(ssd_handle *h, int back, float *ms)
+{
+  if(!h || !ms)
+    return fail(SSD_E_ARG, "ssd_get_surface_moments_time_back: null");
+  if(!h->timing || h->ev.empty() || back < 0 || back >= SSD_TIMING_SLOTS ||
+     h->enqueueCount < static_cast<unsigned long long>(back) + 1 || h->enqueueCount - 1 - back < h->timedFrom)
+    return fail(SSD_E_ARG, "ssd_get_surface_moments_time_back: no timed enqueue at that position");
+  HIP_TRY(hipSetDevice(h->device));
+  const int slot = static_cast<int>((h->enqueueCount - 1 - back) % SSD_TIMING_SLOTS);
+  *ms = 0.0f;
+  if(!h->surfaceTimed[slot] || h->evSurface.empty())
+    return SSD_OK;
+  HIP_TRY(hipEventSynchronize(h->evSurface[2 * slot + 1]));
+  HIP_TRY(hipEventElapsedTime(ms, h->evSurface[2 * slot], h->evSurface[2 * slot + 1]));
   return SSD_OK;
 }
 
@@ -1425,13 +1484,16 @@ static int labels_prepare(ssd_handle *h, size_t sliceBytes)
 }
 
 static int process_host_impl(ssd_handle *h, const void *src, size_t srcFrameBytes, size_t devFrameBytes, int nframes,
-                             ssd_frame_result *results, bool depthInput, unsigned char *labels = nullptr, const uint16_t *camOf = nullptr)
+                             ssd_frame_result *results, bool depthInput, unsigned char *labels = nullptr, const uint16_t *camOf = nullptr,
+                             bool labelsAreMoments = false)
 {
+  /* labelsAreMoments: `labels` receives the slices' ssd_frame_moments instead (ssd_process_host_surfaces) - one record per frame where
+   * labels are a byte per point, through the same staging buffers, copy stream and events */
   HIP_TRY(hipSetDevice(h->device));
   const int slice = h->F < kIngestFrames ? h->F : kIngestFrames;
   int rc = ingest_prepare(h, static_cast<size_t>(slice) * devFrameBytes);
   if(rc) return rc;
-  const size_t labelBytes = static_cast<size_t>(h->P.nPoints);
+  const size_t labelBytes = labelsAreMoments ? sizeof(ssd_frame_moments) : static_cast<size_t>(h->P.nPoints);
   if(labels)
   {
     rc = labels_prepare(h, static_cast<size_t>(slice) * labelBytes);
@@ -1499,7 +1561,8 @@ static int process_host_impl(ssd_handle *h, const void *src, size_t srcFrameByte
     if(labels && c >= 2)
       HIP_TRY(hipStreamWaitEvent(h->ingestCompute, h->labelsCopied[k], 0));      /* the labels of slice c - 2 have left this buffer */
     rc = enqueue_impl(h, h->ingestBuf[k], devFrameBytes, n, h->ingestCompute, SSD_STAGE_ALL, depthInput,
-                      labels ? h->labelStage[k] : nullptr, labelBytes, camOf ? camOf + done : nullptr);     /* a slice takes its part of the index */
+                      labels && !labelsAreMoments ? h->labelStage[k] : nullptr, labelBytes, camOf ? camOf + done : nullptr,     /* a slice takes its part of the index */
+                      labels && labelsAreMoments ? reinterpret_cast<ssd_frame_moments *>(h->labelStage[k]) : nullptr);
     if(rc) return rc;
     /* "Consumed" is the end of the slice's kernels — on the stream they ran on (with several workspaces the lane's own; the
      * compute stream itself only orders a slice behind its copy, so the slices of a handle with several workspaces overlap
@@ -1878,37 +1941,38 @@ static void jacobi3(double a[3][3], double lambda[3], double v[3][3])
   std::memcpy(v, vv, sizeof(vv));
 }
 
-int ssd_ground_fit_solve(const ssd_ground_moments *m, const ssd_calibration *prior, int min_points, ssd_ground_fit *out)
+/* The core of the solve, shared by the ground fit and the surface fit: moments -> the centred scatter N SS - S (x) S, exact in 128-bit
+ * integers, converted once to double and scaled to m^2; its eigenvalues ascending (cyclic Jacobi); n0 = the unit eigenvector of
+ * lambda_min signed away from the camera (dist = n0 . centroid >= 0).  Returns FEW, DEGENERATE (the points determine no plane) or OK. */
+struct PlaneOfMoments
 {
-  if(!m || !prior || !out)
-    return fail(SSD_E_ARG, "ssd_ground_fit_solve: null");
-  std::memset(out, 0, sizeof(*out));
-  out->m = *m;
-  out->cal = *prior;
+  double lambda[3], n0[3], centroid[3], dist;
+};
+
+static int plane_of_moments(const ssd_ground_moments *m, int min_points, PlaneOfMoments &pl)
+{
   const int64_t n = m->n;
   if(n < (min_points > 1 ? min_points : 1))
-  {
-    out->status = SSD_GF_FEW;
-    return SSD_OK;
-  }
+    return SSD_GF_FEW;
   /* the centred scatter N SS - S (x) S, exact: N < 2^23 and SS < 2^63, |S| < 2^43, so both products lie below 2^86 */
   typedef __int128 i128;
   static const int at[3][3] = { { 0, 1, 2 }, { 1, 3, 4 }, { 2, 4, 5 } };
   const double scale = 1.0 / (static_cast<double>(n) * static_cast<double>(n) * kGroundScale * kGroundScale);
-  double c[3][3], lambda[3], v[3][3];
+  double c[3][3], v[3][3];
+  double (&lambda)[3] = pl.lambda;
   for(int i = 0; i < 3; i++)
     for(int j = 0; j < 3; j++)
       c[i][j] = static_cast<double>(static_cast<i128>(n) * m->ss[at[i][j]] - static_cast<i128>(m->s[i]) * m->s[j]) * scale;   /* m^2 */
   jacobi3(c, lambda, v);
-  out->status = SSD_GF_DEGENERATE;
   /* an eigenvalue at the rounding level of the largest one is zero (collinear points leave +-1e-17 lambda_max, of either sign) */
   const double zero = 64.0 * 2.220446049250313e-16 * lambda[2];
   const double lmin = lambda[0] > zero ? lambda[0] : 0.0, lmid = lambda[1] > zero ? lambda[1] : 0.0;
   if(!(lmid > 0.0) || lmid < SSD_GF_PLANARITY * lmin)
-    return SSD_OK;
-  double n0[3] = { v[0][0], v[1][0], v[2][0] };
+    return SSD_GF_DEGENERATE;
+  double (&n0)[3] = pl.n0;
+  n0[0] = v[0][0]; n0[1] = v[1][0]; n0[2] = v[2][0];
   const double rn = 1.0 / std::sqrt(n0[0] * n0[0] + n0[1] * n0[1] + n0[2] * n0[2]);
-  double centroid[3];
+  double (&centroid)[3] = pl.centroid;
   for(int i = 0; i < 3; i++)
   {
     n0[i] *= rn;
@@ -1921,6 +1985,24 @@ int ssd_ground_fit_solve(const ssd_ground_moments *m, const ssd_calibration *pri
     for(int i = 0; i < 3; i++)
       n0[i] = -n0[i];
   }
+  pl.dist = dist;
+  return SSD_GF_OK;
+}
+
+int ssd_ground_fit_solve(const ssd_ground_moments *m, const ssd_calibration *prior, int min_points, ssd_ground_fit *out)
+{
+  if(!m || !prior || !out)
+    return fail(SSD_E_ARG, "ssd_ground_fit_solve: null");
+  std::memset(out, 0, sizeof(*out));
+  out->m = *m;
+  out->cal = *prior;
+  PlaneOfMoments pl;
+  out->status = plane_of_moments(m, min_points, pl);
+  if(out->status != SSD_GF_OK)
+    return SSD_OK;
+  out->status = SSD_GF_DEGENERATE;
+  const double (&n0)[3] = pl.n0;
+  const double dist = pl.dist;
   ssd_calibration cal = *prior;
   if(!camera_to_world_from_plane(n0[0], n0[1], n0[2], dist, cal.a, cal.b))
     return SSD_OK;
@@ -1929,11 +2011,149 @@ int ssd_ground_fit_solve(const ssd_ground_moments *m, const ssd_calibration *pri
   for(int i = 0; i < 3; i++)
     out->normal[i] = n0[i];
   out->dist = dist;
-  out->rms = std::sqrt(lambda[0] > 0.0 ? lambda[0] : 0.0);
+  out->rms = std::sqrt(pl.lambda[0] > 0.0 ? pl.lambda[0] : 0.0);
   const double p[3] = { -prior->a[6], -prior->a[7], -prior->a[8] };
   const double cx = n0[1] * p[2] - n0[2] * p[1], cy = n0[2] * p[0] - n0[0] * p[2], cz = n0[0] * p[1] - n0[1] * p[0];
   out->tilt = std::atan2(std::sqrt(cx * cx + cy * cy + cz * cz), n0[0] * p[0] + n0[1] * p[1] + n0[2] * p[2]);
   out->height_delta = dist - prior->b[2];
+  return SSD_OK;
+}
+
+/* ---- surface fit (include/ssd_hip.h): host side ---------------------------------------------------------- */
+
+int ssd_surface_moments_host(const ssd_config *cfg, int input, const ssd_intrinsics *intr, const void *frame, const uint8_t *labels,
+                             int n_surfaces, int ground, ssd_frame_moments *out)
+{
+  if(!cfg || !frame || !labels || !out || cfg->width <= 0 || cfg->height <= 0)
+    return fail(SSD_E_ARG, "ssd_surface_moments_host: bad argument");
+  if(input != SSD_INPUT_VERTICES && input != SSD_INPUT_DEPTH16)
+    return fail(SSD_E_ARG, "ssd_surface_moments_host: input must be SSD_INPUT_VERTICES or SSD_INPUT_DEPTH16");
+  if(n_surfaces < 0 || n_surfaces > SSD_MAX_STEPS)
+    return fail(SSD_E_ARG, "ssd_surface_moments_host: n_surfaces must lie in 0 .. SSD_MAX_STEPS");
+  const bool depth = input == SSD_INPUT_DEPTH16;
+  if(depth && (!intr || !good_intrinsics(*intr)))
+    return fail(SSD_E_ARG, "ssd_surface_moments_host: depth input needs intrinsics");
+  const int W = cfg->width, H = cfg->height;
+  const size_t nPoints = static_cast<size_t>(W) * H;
+  for(size_t i = 0; i < nPoints; i++)
+    if(labels[i] > n_surfaces)
+      return fail(SSD_E_ARG, "ssd_surface_moments_host: a label above n_surfaces");
+  std::vector<float> deprojected;
+  const float *xyz = static_cast<const float *>(frame);
+  if(depth)
+  {
+    deprojected.resize(3 * nPoints);
+    const int rc = ssd_deproject_host(intr, W, H, static_cast<const uint16_t *>(frame), deprojected.data());
+    if(rc) return rc;
+    xyz = deprojected.data();
+  }
+  static_assert(sizeof(ssd_surface_moments) == sizeof(long long) * (kGroundSums + 1), "ssd_surface_moments is the ten sums and n_far");
+  long long acc[SSD_MAX_STEPS][kGroundSums + 1] = {};
+  for(size_t i = 0; i < nPoints; i++)
+  {
+    if(labels[i] == SSD_LABEL_NONE)
+      continue;
+    long long (&a)[kGroundSums + 1] = acc[labels[i] - 1];
+    const double rx = moment_round(xyz[3 * i]), ry = moment_round(xyz[3 * i + 1]), rz = moment_round(xyz[3 * i + 2]);
+    if(moment_near(rx) && moment_near(ry) && moment_near(rz))
+      moment_add(rx, ry, rz, a);
+    else
+      a[kGroundSums] += 1;
+  }
+  std::memset(out, 0, sizeof(*out));
+  out->n_surfaces = n_surfaces;
+  out->ground = ground ? 1 : 0;
+  std::memcpy(out->s, acc, sizeof(acc));
+  return SSD_OK;
+}
+
+int ssd_surface_fit_solve(const ssd_frame_moments *moments, const ssd_calibration *cal, int min_points, ssd_frame_surfaces *out)
+{
+  if(!moments || !cal || !out)
+    return fail(SSD_E_ARG, "ssd_surface_fit_solve: null");
+  if(moments->n_surfaces < 0 || moments->n_surfaces > SSD_MAX_STEPS)
+    return fail(SSD_E_ARG, "ssd_surface_fit_solve: n_surfaces must lie in 0 .. SSD_MAX_STEPS");
+  std::memset(out, 0, sizeof(*out));
+  out->n_surfaces = moments->n_surfaces;
+  out->ground = moments->ground;
+  for(int k = 0; k < moments->n_surfaces; k++)
+  {
+    const ssd_surface_moments &sm = moments->s[k];
+    ssd_surface_fit &f = out->s[k];
+    f.n = sm.m.n;
+    f.n_far = sm.n_far;
+    PlaneOfMoments pl;
+    f.status = plane_of_moments(&sm.m, min_points, pl);
+    if(f.status != SSD_GF_OK)
+      continue;
+    /* the plane's normal towards the camera, in camera-dependent world coordinates (the rotation alone), then ToExternalWorld's
+     * rotation of x and y; the centroid as a point: CameraToWorld, then ToExternalWorld (transformation.cpp:209-211) */
+    double up[3], w[3];
+    for(int i = 0; i < 3; i++)
+    {
+      up[i] = -((cal->a[3 * i] * pl.n0[0] + cal->a[3 * i + 1] * pl.n0[1]) + cal->a[3 * i + 2] * pl.n0[2]);
+      w[i] = ((cal->a[3 * i] * pl.centroid[0] + cal->a[3 * i + 1] * pl.centroid[1]) + cal->a[3 * i + 2] * pl.centroid[2]) + cal->b[i];
+    }
+    f.normal[0] = cal->r2[0] * up[0] + cal->r2[1] * up[1];
+    f.normal[1] = cal->r2[2] * up[0] + cal->r2[3] * up[1];
+    f.normal[2] = up[2];
+    f.centroid[0] = (cal->r2[0] * w[0] + cal->r2[1] * w[1]) + cal->t2[0];
+    f.centroid[1] = (cal->r2[2] * w[0] + cal->r2[3] * w[1]) + cal->t2[1];
+    f.centroid[2] = w[2] + cal->world_z;
+    f.tilt = std::atan2(std::sqrt(f.normal[0] * f.normal[0] + f.normal[1] * f.normal[1]), f.normal[2]);
+    f.rms = std::sqrt(pl.lambda[0] > 0.0 ? pl.lambda[0] : 0.0);
+    f.extent[0] = std::sqrt(pl.lambda[2]);
+    f.extent[1] = std::sqrt(pl.lambda[1]);
+  }
+  return SSD_OK;
+}
+
+/* the calibration ssd_create gave the handle, as its kernels' constants hold it */
+static ssd_calibration handle_calibration(const ssd_handle *h)
+{
+  ssd_calibration c;
+  for(int i = 0; i < 9; i++) c.a[i] = h->P.pt.a[i];
+  for(int i = 0; i < 3; i++) c.b[i] = h->P.pt.b[i];
+  for(int i = 0; i < 4; i++) c.r2[i] = h->P.r2[i];
+  c.t2[0] = h->P.t2[0]; c.t2[1] = h->P.t2[1];
+  c.world_z = h->P.worldZ;
+  return c;
+}
+
+int ssd_process_host_surfaces(ssd_handle *h, const void *frames, int nframes, int input, ssd_frame_result *results,
+                              ssd_frame_moments *moments, int min_points, ssd_frame_surfaces *out)
+{
+  if(!h || !frames || !results || !out || nframes < 1)
+    return fail(SSD_E_ARG, "ssd_process_host_surfaces: bad argument");
+  if(input != SSD_INPUT_VERTICES && input != SSD_INPUT_DEPTH16)
+    return fail(SSD_E_ARG, "ssd_process_host_surfaces: input must be SSD_INPUT_VERTICES or SSD_INPUT_DEPTH16");
+  if(input == SSD_INPUT_DEPTH16 && !h->haveIntr)
+    return fail(SSD_E_ARG, "ssd_process_host_surfaces: call ssd_set_intrinsics first");
+  std::vector<ssd_frame_moments> own;
+  if(!moments)
+  {
+    own.resize(static_cast<size_t>(nframes));
+    moments = own.data();
+  }
+  int rc;
+  if(input == SSD_INPUT_DEPTH16)
+  {
+    const size_t frameElems = (static_cast<size_t>(h->P.nPoints) + 3) / 4 * 4;
+    rc = process_host_impl(h, frames, static_cast<size_t>(h->P.nPoints) * 2, frameElems * 2, nframes, results, true,
+                           reinterpret_cast<unsigned char *>(moments), nullptr, true);
+  }
+  else
+  {
+    const size_t frameBytes = static_cast<size_t>(h->P.nPoints) * 12;
+    rc = process_host_impl(h, frames, frameBytes, frameBytes, nframes, results, false, reinterpret_cast<unsigned char *>(moments), nullptr, true);
+  }
+  if(rc) return rc;
+  const ssd_calibration cal = handle_calibration(h);
+  for(int i = 0; i < nframes; i++)
+  {
+    rc = ssd_surface_fit_solve(moments + i, &cal, min_points, out + i);
+    if(rc) return rc;
+  }
   return SSD_OK;
 }
 
@@ -2011,11 +2231,7 @@ static int enqueue_ground_fit_impl(ssd_handle *h, const void *d_frames, size_t f
   if(npriors == 0)
   {
     ssd_calibration &c = h->groundPriorCal[0];
-    for(int i = 0; i < 9; i++) c.a[i] = h->P.pt.a[i];
-    for(int i = 0; i < 3; i++) c.b[i] = h->P.pt.b[i];
-    for(int i = 0; i < 4; i++) c.r2[i] = h->P.r2[i];
-    c.t2[0] = h->P.t2[0]; c.t2[1] = h->P.t2[1];
-    c.world_z = h->P.worldZ;
+    c = handle_calibration(h);
     ground_prior_fill(h->hGroundPriors[0], c, depth ? &h->intr : nullptr);
   }
   else

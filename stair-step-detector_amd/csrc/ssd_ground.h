@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
+#include "ssd_moments.h"
+
 namespace ssd
 {
 
@@ -26,12 +28,8 @@ struct GroundRange
   double xMin, xMax, yMin, yMax, tol;
 };
 
-constexpr int kGroundSums = 10;               /* ssd_ground_moments as 10 int64: n, s[3], ss[6] */
-constexpr double kGroundScale = 65536.0;      /* 2^-16 m fixed point */
-constexpr double kGroundLimit = 1048576.0;    /* |q| < 2^20, |v| < 16 m */
-
-/* One point into a lane's / the host's sums.  Overflow: |q| < 2^20, so a product is below 2^40; a frame has at most
- * 3175 * 2560 < 2^23 points (ssd_hip.h, configuration limits), so every sum stays below 2^63: int64 is exact, whatever the order. */
+/* One point into a lane's / the host's sums, by the fixed-point rule of ssd_moments.h (kGroundSums, moment_round, moment_near,
+ * moment_add: the overflow argument stands there) */
 __host__ __device__ inline void ground_point(const GroundPrior &C, const GroundRange &R, float fx, float fy, float fz, long long (&acc)[kGroundSums])
 {
   if(!(fz > 0.0f))
@@ -44,18 +42,13 @@ __host__ __device__ inline void ground_point(const GroundPrior &C, const GroundR
   wx = wx + C.b[0];
   wy = wy + C.b[1];
   wz = wz + C.b[2];
-  /* q = llrint(v * 2^16) on the rounded double (the product is exact: a power of two), so that no conversion is out of range */
-  const double rx = __builtin_rint(x * kGroundScale), ry = __builtin_rint(y * kGroundScale), rz = __builtin_rint(z * kGroundScale);
+  const double rx = moment_round(x), ry = moment_round(y), rz = moment_round(z);
+  const bool nx = moment_near(rx), ny = moment_near(ry), nz = moment_near(rz);
   const bool floor = (wx > R.xMin) & (wx < R.xMax) & (wy > R.yMin) & (wy < R.yMax) & (wz >= -R.tol) & (wz <= R.tol) &
-                     (__builtin_fabs(rx) < kGroundLimit) & (__builtin_fabs(ry) < kGroundLimit) & (__builtin_fabs(rz) < kGroundLimit);
+                     nx & ny & nz;
   if(!floor)
     return;
-  const long long qx = static_cast<int>(rx), qy = static_cast<int>(ry), qz = static_cast<int>(rz);
-  acc[0] += 1;
-  acc[1] += qx; acc[2] += qy; acc[3] += qz;
-  acc[4] += qx * qx; acc[5] += qx * qy; acc[6] += qx * qz;
-  acc[7] += qy * qy; acc[8] += qy * qz;
-  acc[9] += qz * qz;
+  moment_add(rx, ry, rz, acc);
 }
 
 /* rs2::pointcloud's maps as ssd_deproject_host computes them (float arithmetic, one correctly rounded division each) */

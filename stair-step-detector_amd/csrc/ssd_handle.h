@@ -120,6 +120,10 @@ struct ssd_handle
   size_t labelStageCap = 0;                 /* bytes per buffer */
   hipStream_t labelsCopy = nullptr;         /* their copies to the host */
   hipEvent_t labelsCopied[2] = { nullptr, nullptr };
+  /* surface moments (ssd_enqueue_surface_moments & co.): the events around k_surface_moments of a timed enqueue, made on the first one;
+   * the host entry point stages a slice's records in labelStage and copies them out on labelsCopy, as labels are */
+  std::vector<hipEvent_t> evSurface;         /* SSD_TIMING_SLOTS x 2 */
+  bool surfaceTimed[SSD_TIMING_SLOTS] = {};
   unsigned long long enqueueCount = 0;
   unsigned long long timedFrom = 0;
   /* the camera table (ssd_set_cameras; empty: none).  camParams are make_params()' as they were made; the device records also

@@ -39,6 +39,7 @@
 #undef SSD_COUNT
 #endif
 #include "ssd_device.h"
+#include "ssd_moments.h"
 #include "ssd_math.h"
 #include "ssd_quadtest.h"
 #include "ssd_closing.h"
@@ -3734,6 +3735,192 @@ SSD_ENTRY(__launch_bounds__(kThreads), k_labels, labels_block)(const float *__re
   }
 }
 
+#ifndef SSD_CAMERAS_TU
+/* ========================================================================= */
+/* K8 (extension): per-surface integer moments (the surface fit)                */
+
+/* k_labels' sibling: the same cells, the same decision (quad_decide<.., true>), and in place of a byte per point the ten integer sums
+ * of ssd_ground_moments (ssd_moments.h) per surface - surface k's over exactly the points k_labels gives label k + 1 - plus n_far, the
+ * labelled points the fixed-point rule leaves out.  A cell holding no bin of a live quadrilateral is neither read nor touched.
+ * A lane keeps the sums of ONE surface in registers, the wave's current one (wave-uniform; rows of the camera image mostly lie on one
+ * surface).  When no lane of a point slot has the current surface and some have another, the wave's sums go to the block's LDS table
+ * (shuffles, then 64-bit LDS adds by lane 0) and the wave changes over; the lanes of a mixed slot that hold another surface than the
+ * current one add their point to the LDS table directly.  At the block's end one 64-bit atomicAdd per non-zero entry of the table goes
+ * to the frame's record, which the caller zeroed on the stream.  Integer addition throughout: no result depends on an order.
+ * Camera batches have no instantiation of it (include/ssd_hip.h). */
+constexpr int kSurfaceSums = kGroundSums + 1;       /* ssd_surface_moments as 11 int64: the ten sums, n_far */
+static_assert(sizeof(ssd_surface_moments) == 8 * kSurfaceSums && sizeof(ssd_frame_moments) == 8 + SSD_MAX_STEPS * 8 * kSurfaceSums,
+              "ssd_frame_moments is the kernel's record: a header of two int32, then kSurfaceSums int64 per surface");
+static_assert(SSD_MAX_STEPS * kSurfaceSums <= kThreads, "one thread per entry of the block's table");
+
+struct SurfaceLds
+{
+  LabelsLds l;
+  unsigned long long sums[SSD_MAX_STEPS][kSurfaceSums];
+};
+
+/* the wave's sums of surface `surface` into the block's table */
+__device__ __forceinline__ void surface_flush(long long (&acc)[kSurfaceSums], unsigned long long (*sums)[kSurfaceSums], int surface, int lane)
+{
+#pragma unroll
+  for(int i = 0; i < kSurfaceSums; i++)
+  {
+#pragma unroll
+    for(int o = 32; o >= 1; o >>= 1)
+      acc[i] += __shfl_xor(acc[i], o);
+  }
+  if(lane == 0)
+  {
+#pragma unroll
+    for(int i = 0; i < kSurfaceSums; i++)
+      if(acc[i] != 0)
+        atomicAdd(&sums[surface][i], static_cast<unsigned long long>(acc[i]));
+  }
+#pragma unroll
+  for(int i = 0; i < kSurfaceSums; i++)
+    acc[i] = 0;
+}
+
+template<int SRC, bool CHECKS>
+__global__ __launch_bounds__(kThreads) void k_surface_moments(const float *__restrict__ xyz, size_t strideFloats, PointParams P, PreXY Q,
+                                                              const FrameState *__restrict__ st, const uint2 *__restrict__ tileMasks,
+                                                              size_t tileMaskStride, int chunkPoints, DepthSrc D,
+                                                              ssd_frame_moments *__restrict__ out)
+{
+  __shared__ SurfaceLds S;
+  LabelsLds &L = S.l;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int frame = blockIdx.x;
+  /* the frame's state into LDS exactly as k_labels takes it (spelt out again, not shared through a helper: moved into one, k_labels'
+   * own code changes - 71 scalar registers become 95) */
+  const FrameState &fs = st[frame];
+  /* nothing of a frame k_quads found no live quadrilateral in, or whose quadrilaterals the reference would have thrown on, is labelled */
+  const bool live = fs.anyActive != 0u && (fs.status & SSD_ST_THROW) == 0u;           /* block-uniform */
+  const unsigned int wanted = live ? fs.wantedQuads : 0u;
+  if(live)
+  {
+    const int nLive = fs.nLive;
+    const int gSlot = (nLive > 0 && fs.accActive[kGroundAcc]) ? nLive - 1 : -1;       /* the ground is the last live slot */
+    if(tid < kMaxBins)
+    {
+      const unsigned char s = fs.lutLive[tid];
+      L.lut[tid] = s == 0xff ? static_cast<unsigned char>(kMaxLive) : s;
+    }
+    if(tid <= kMaxLive)
+    {
+      /* slot order = accumulator order (treads ascending, the ground last); the result has the ground first */
+      int lab = 0;
+      if(tid < nLive)
+        lab = tid == gSlot ? 1 : tid + 1 + (gSlot >= 0 ? 1 : 0);
+      L.label[tid] = static_cast<unsigned char>(lab <= SSD_MAX_STEPS ? lab : 0);
+    }
+    constexpr int qtWords = kMaxLive * static_cast<int>(sizeof(QuadTest) / 4);
+    constexpr int egWords = kMaxLive * static_cast<int>(sizeof(QuadEdgesF) / 4);
+    for(int w = tid; w < qtWords; w += kThreads)
+      reinterpret_cast<unsigned int *>(L.qts)[w] = reinterpret_cast<const unsigned int *>(fs.qtLive)[w];
+    stage_quad_edges(L.edges, fs.edgeLive, egWords, Q.dE0);
+    if(tid == 0)
+    {
+      /* k1_consts_fill(L.kc, P, nullptr) spelt out: through the helper this kernel takes 92 scalar registers for 71 */
+      K1Consts &c = L.kc;
+      for(int i = 0; i < 9; i++)
+        c.a[i] = P.a[i];
+      c.b[0] = P.b[0]; c.b[1] = P.b[1]; c.b[2] = P.b[2];
+      c.xMin = P.xMin; c.xMax = P.xMax; c.yMin = P.yMin; c.yMax = P.yMax; c.zMin = P.zMin; c.zMax = P.zMax;
+      c.boxX = P.boxX; c.boxY = P.boxY;
+      c.recip = P.recip;
+      c.xToImage = 0.0; c.yToImage = 0.0;
+      /* the record's header, by the frame's first block: the surfaces labels can name, and whether the first is the ground */
+      if(blockIdx.y == 0)
+      {
+        out[frame].n_surfaces = min(nLive, SSD_MAX_STEPS);
+        out[frame].ground = gSlot >= 0 ? 1 : 0;
+      }
+    }
+  }
+  if(tid < SSD_MAX_STEPS * kSurfaceSums)
+    (&S.sums[0][0])[tid] = 0ull;
+  __syncthreads();
+  if(wanted == 0u)
+    return;
+
+  const float *base = SRC == kSrcDepth16
+    ? reinterpret_cast<const float *>(reinterpret_cast<const unsigned short *>(xyz) + static_cast<size_t>(frame) * strideFloats)
+    : xyz + static_cast<size_t>(frame) * strideFloats;
+  const int begin = blockIdx.y * chunkPoints;
+  const int end = min(begin + chunkPoints, P.nPoints);
+  const int cell0 = begin / kCell;
+  const int nCells = (end - begin + kCell - 1) / kCell;
+  const uint2 *cells = tileMasks + static_cast<size_t>(frame) * tileMaskStride + cell0;
+
+  const int count = cell_list_build(cells, nCells, 1, [&](const uint2 info) { return (info.x & wanted) != 0u; }, L.cellList, L.listScratch);
+  const PreLane lc(Q);
+  const int nGroups = (count + 3) >> 2;
+  const int gEnd = ((tid >> 6) + 1) * nGroups / kWavesPerBlock;
+  long long acc[kSurfaceSums] = {};
+  int cur = 0;                                   /* the label whose sums the wave's registers hold (0: none yet) */
+  for(int g = (tid >> 6) * nGroups / kWavesPerBlock; g < gEnd; g++)
+  {
+    const int entry = 4 * g + (lane >> 4);
+    F3 v[kPts];
+    load_cell<SRC>(base, cell0, L.cellList, entry, count, lane, P.nPoints, v, D);
+#pragma unroll
+    for(int j = 0; j < kPts; j++)
+    {
+      f32x2 d;
+      float M, M3;
+      unsigned int q;
+      unsigned long long mSlow, mIn, mGround;
+      quad_decide<CHECKS, true>(v[j], Q, lc, L.edges, L.lut, L.qts, L.kc, -1, d, M, M3, q, mSlow, mIn, mGround);
+      const int lab = (__builtin_amdgcn_inverse_ballot_w64(mIn) && entry < count) ? L.label[min(q, static_cast<unsigned int>(kMaxLive))] : 0;
+      const unsigned long long mLab = __ballot(lab != 0);
+      if(mLab == 0ull)                           /* wave-uniform: a slot none of whose points counts */
+        continue;
+      if(cur == 0 || __ballot(lab == cur) == 0ull)
+      {
+        if(cur != 0)
+          surface_flush(acc, S.sums, cur - 1, lane);
+        cur = __builtin_amdgcn_readlane(lab, __ffsll(static_cast<long long>(mLab)) - 1);
+      }
+      /* the fixed-point rule (ssd_moments.h) on the float camera coordinates */
+      const double rx = moment_round(static_cast<double>(v[j].x)), ry = moment_round(static_cast<double>(v[j].y)), rz = moment_round(static_cast<double>(v[j].z));
+      const bool fits = moment_near(rx) && moment_near(ry) && moment_near(rz);
+      if(lab == cur)
+      {
+        if(fits)
+          moment_add(rx, ry, rz, acc);
+        else
+          acc[kGroundSums] += 1;
+      }
+      else if(lab != 0)
+      {
+        /* another surface than the wave's current one in the same slot (a cell two surfaces share): rare, straight to the table */
+        unsigned long long *t = S.sums[lab - 1];
+        if(fits)
+        {
+          long long one[kGroundSums] = {};
+          moment_add(rx, ry, rz, one);
+#pragma unroll
+          for(int i = 0; i < kGroundSums; i++)
+            atomicAdd(&t[i], static_cast<unsigned long long>(one[i]));
+        }
+        else
+          atomicAdd(&t[kGroundSums], 1ull);
+      }
+    }
+  }
+  if(cur != 0)
+    surface_flush(acc, S.sums, cur - 1, lane);
+  __syncthreads();
+  if(tid < SSD_MAX_STEPS * kSurfaceSums)
+  {
+    const unsigned long long t = (&S.sums[0][0])[tid];
+    if(t != 0ull)
+      atomicAdd(reinterpret_cast<unsigned long long *>(out + frame) + 1 + tid, t);
+  }
+}
+#endif /* SSD_CAMERAS_TU */
+
 /* ========================================================================= */
 /* K5: ground front edge and the per-frame result — one workgroup per frame     */
 
@@ -4438,6 +4625,18 @@ void launch_labels(const float *xyz, size_t strideFloats, const Params &P, const
     with_bool(needs_checks(P), [&](auto checks)
     {
       hipLaunchKernelGGL((k_labels<decltype(src)::value, decltype(checks)::value>), grid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.pre, st, tileMasks, tileMaskStride, chunkPoints, D, labels, labelStride);
+    });
+  });
+}
+void launch_surface_moments(const float *xyz, size_t strideFloats, const Params &P, const FrameState *st, const uint2 *tileMasks, size_t tileMaskStride,
+                            int nframes, int chunkPoints, const DepthSrc *depth, ssd_frame_moments *out, hipStream_t s)
+{
+  dim3 grid(nframes, chunks_for(P.nPoints, chunkPoints));
+  with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &D)
+  {
+    with_bool(needs_checks(P), [&](auto checks)
+    {
+      hipLaunchKernelGGL((k_surface_moments<decltype(src)::value, decltype(checks)::value>), grid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.pre, st, tileMasks, tileMaskStride, chunkPoints, D, out);
     });
   });
 }
