@@ -410,7 +410,8 @@ int ssd_process_host_ground_fit(ssd_handle *h, const void *frames, int nframes, 
  * zero.  Surface 0's m of a frame with ground = 1 goes straight into ssd_ground_fit_solve: the detector's own ground points lie
  * inside the ground quadrilateral, in front of the first riser, so a calibration can be polished or watched for drift in the same
  * call that detects.
- * Camera batches (ssd_enqueue_cameras, ssd_process_host_cameras) are out of scope: they have no surface moments. */
+ * Camera batches have their own entry points (ssd_enqueue_cameras_surface_moments, ssd_process_host_cameras_surfaces, below): each
+ * frame's moments under its own camera, and ssd_camera_drift_fold on top of them. */
 typedef struct
 {
   ssd_ground_moments m;
@@ -467,6 +468,42 @@ int ssd_surface_fit_solve(const ssd_frame_moments *moments, const ssd_calibratio
  * NULL, moments[nframes]; returns when all of it is there. */
 int ssd_process_host_surfaces(ssd_handle *h, const void *frames, int nframes, int input, ssd_frame_result *results,
                               ssd_frame_moments *moments, int min_points, ssd_frame_surfaces *out);
+
+/* ---- surface fit of cameras batches, and drift per camera ---------------------------------------------------------------
+ * EXTENSION: the contract of per-frame calibration, extended to the surface fit.
+ *   ssd_enqueue_cameras_surface_moments  as ssd_enqueue_cameras (no labels) plus the frames' surface moments at d_out + i.
+ *   ssd_process_host_cameras_surfaces    as ssd_process_host_surfaces, through the slices of ssd_process_host_cameras.
+ * Contract: frame i's ssd_frame_moments is byte for byte what a handle made by ssd_create(cfg, &cams[camera_of_frame[i]].cal) (with
+ * ssd_set_intrinsics(&...intr) for depth input) returns for that frame alone, and out[i] is
+ * ssd_surface_fit_solve(moments + i, &cams[camera_of_frame[i]].cal, min_points, ..).  Stream, completion, zeroing, several
+ * workspaces and ssd_get_surface_moments_time_back are those of ssd_enqueue_surface_moments; camera_of_frame (HOST memory) is copied
+ * during the call.  SSD_E_ARG, before anything is launched or copied: what ssd_enqueue_cameras refuses, and a null destination.  A
+ * handle that never asks allocates and launches nothing more. */
+int ssd_enqueue_cameras_surface_moments(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream,
+                                        const uint16_t *camera_of_frame, int input, ssd_frame_moments *d_out);
+int ssd_process_host_cameras_surfaces(ssd_handle *h, const void *frames, int nframes, const uint16_t *camera_of_frame, int input,
+                                      ssd_frame_result *results, ssd_frame_moments *moments, int min_points, ssd_frame_surfaces *out);
+
+/* Drift per camera: the ground moments (surface 0 of a frame with ground = 1) of all of a camera's frames in a batch, added exactly,
+ * and one ssd_ground_fit_solve per camera against its table entry: fit.tilt and fit.height_delta say how far the mounting has moved
+ * from what the table holds, fit.cal is the refined entry.  Frames are folded in index order; a frame is added whole or not at all:
+ * when any of its ten sums or n_far would carry an int64 sum past its range the frame is counted in frames_left and skipped (a later,
+ * smaller frame may still fit).  The sums are exact integers, so the record does not depend on the order of the folded frames unless
+ * the order changes which frames fit. */
+typedef struct
+{
+  int32_t camera, frames;        /* table index; frames of the batch that name it */
+  int32_t frames_ground;         /* ... of those, folded: ground == 1 and n_surfaces >= 1 */
+  int32_t frames_left;           /* ... with a ground, NOT folded: adding them would overflow an int64 sum */
+  ssd_ground_moments m;          /* exact sum of s[0].m over the folded frames */
+  int64_t n_far;
+  ssd_ground_fit fit;            /* ssd_ground_fit_solve(&m, &cams[camera].cal, min_points, ..): tilt, height_delta, rms, refined cal */
+} ssd_camera_drift;
+
+/* host only, no GPU needed: out[ncams], one record per camera of the table (a camera no frame names: frames = 0, fit.status =
+ * SSD_GF_FEW).  SSD_E_ARG: a null pointer, ncams outside 1 .. SSD_MAX_CAMERAS, nframes < 0, an index >= ncams (out is then untouched). */
+int ssd_camera_drift_fold(const ssd_frame_moments *moments, const uint16_t *camera_of_frame, int nframes,
+                          const ssd_camera *cams, int ncams, int min_points, ssd_camera_drift *out /* ncams records */);
 
 /* stage selector for profiling / roofline measurement: runs only the chosen stage(s) of the pipeline */
 #define SSD_STAGE_HIST 1       /* K1: transform + crop + bin + histogram */

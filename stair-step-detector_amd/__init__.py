@@ -165,6 +165,13 @@ class FrameSurfaces(C.Structure):
     _fields_ = [("n_surfaces", C.c_int32), ("ground", C.c_int32), ("s", SurfaceFit * MAX_STEPS)]
 
 
+class CameraDrift(C.Structure):
+    """ssd_camera_drift: a camera's ground moments over the frames of a batch that name it, added exactly, and the ground fit of the
+    sum against its table entry (fit.tilt, fit.height_delta: how far the mounting has moved)"""
+    _fields_ = [("camera", C.c_int32), ("frames", C.c_int32), ("frames_ground", C.c_int32), ("frames_left", C.c_int32),
+                ("m", GroundMoments), ("n_far", C.c_int64), ("fit", GroundFit)]
+
+
 class Scene(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32),
                 ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
@@ -198,6 +205,7 @@ EXPORTS = [
     "ssd_process_host_ground_fit",
     "ssd_enqueue_surface_moments", "ssd_enqueue_depth_surface_moments", "ssd_get_surface_moments_time_back", "ssd_surface_moments_host",
     "ssd_surface_fit_solve", "ssd_process_host_surfaces",
+    "ssd_enqueue_cameras_surface_moments", "ssd_process_host_cameras_surfaces", "ssd_camera_drift_fold",
 ]
 # libssd_source.so — the frame source standing in for the camera (include/ssd_source.h)
 SOURCE_EXPORTS = [
@@ -276,6 +284,10 @@ def lib():
     L.ssd_surface_moments_host.argtypes = [C.POINTER(Config), i32, C.POINTER(Intrinsics), vp, vp, i32, i32, C.POINTER(FrameMoments)]
     L.ssd_surface_fit_solve.argtypes = [C.POINTER(FrameMoments), C.POINTER(Calibration), i32, C.POINTER(FrameSurfaces)]
     L.ssd_process_host_surfaces.argtypes = [vp, vp, i32, i32, C.POINTER(FrameResult), C.POINTER(FrameMoments), i32, C.POINTER(FrameSurfaces)]
+    L.ssd_enqueue_cameras_surface_moments.argtypes = [vp, vp, sz, i32, vp, C.POINTER(C.c_uint16), i32, vp]
+    L.ssd_process_host_cameras_surfaces.argtypes = [vp, vp, i32, C.POINTER(C.c_uint16), i32, C.POINTER(FrameResult), C.POINTER(FrameMoments), i32,
+                                                    C.POINTER(FrameSurfaces)]
+    L.ssd_camera_drift_fold.argtypes = [C.POINTER(FrameMoments), C.POINTER(C.c_uint16), i32, C.POINTER(Camera), i32, i32, C.POINTER(CameraDrift)]
     L.ssd_serialize.argtypes = [C.POINTER(FrameResult), C.c_char_p, sz]
     L.ssd_set_debug.argtypes = [vp, i32]
     L.ssd_get_debug.argtypes = [vp, i32, C.POINTER(DebugFrame)]
@@ -504,6 +516,22 @@ def surface_fit_solve(moments, cal, min_points=200):
     return out
 
 
+def camera_drift_fold(moments, camera_of_frame, cameras, min_points=2000):
+    """ssd_camera_drift_fold: per camera of `cameras` (a list of anything Detector.set_cameras takes), the ground moments of the frames
+    that name it (moments: FrameMoments per frame, as the cameras surface-fit calls return them) added exactly, and the ground fit of
+    the sum against that camera's calibration -> list of CameraDrift, one per camera"""
+    n = len(moments)
+    idx = np.ascontiguousarray(camera_of_frame, dtype=np.uint16)
+    if idx.ndim != 1 or idx.size != n or np.any(np.asarray(camera_of_frame) != idx):
+        raise SsdError("camera_of_frame: one index 0..65535 per frame")
+    mom = moments if isinstance(moments, C.Array) and moments._type_ is FrameMoments else (FrameMoments * max(1, n))(*moments)
+    cams = cameras if isinstance(cameras, C.Array) and cameras._type_ is Camera else _camera_array(list(cameras))[0]
+    ncams = len(cameras)
+    out = (CameraDrift * max(1, ncams))()
+    _check(lib().ssd_camera_drift_fold(mom, idx.ctypes.data_as(C.POINTER(C.c_uint16)), n, cams, ncams, int(min_points), out))
+    return [CameraDrift.from_buffer_copy(out[i]) for i in range(ncams)]
+
+
 # --------------------------------------------------------------------------- reference-shaped classes
 class GeometricTransformation:
     """reference transformation.h:102-126; constructor transformation.cpp:196-215."""
@@ -670,6 +698,7 @@ class Detector:
                 arr[i].intr = intr
                 arr[i].has_intrinsics = 1
         _check(lib().ssd_set_cameras(self._h, arr, len(cameras)))
+        self._cameras = [Camera.from_buffer_copy(arr[i]) for i in range(len(cameras))]      # what camera_drift folds against
 
     @property
     def camera_count(self):
@@ -776,6 +805,38 @@ class Detector:
         _check(lib().ssd_process_host_surfaces(self._h, a.ctypes.data_as(C.c_void_p), n, INPUT_DEPTH16 if depth else INPUT_VERTICES, res,
                                                mom if moments else None, int(min_points), out))
         return (list(res), list(out), list(mom)) if moments else (list(res), list(out))
+
+    # ---- surface fit of cameras batches, drift per camera (include/ssd_hip.h)
+    def enqueue_cameras_surface_moments(self, d_ptr, nframes, camera_of_frame, d_moments, depth=False, stride_bytes=None, stream=None):
+        """ssd_enqueue_cameras_surface_moments: enqueue_cameras (no labels) plus frame i's FrameMoments, under camera
+        camera_of_frame[i], at d_moments + i * sizeof(FrameMoments) in device memory; complete when fetch() of the batch returns"""
+        idx = self._camera_index(camera_of_frame, nframes)
+        frame = self.cfg.width * self.cfg.height * (2 if depth else 12)
+        _check(lib().ssd_enqueue_cameras_surface_moments(self._h, C.c_void_p(d_ptr), stride_bytes or frame, nframes, C.c_void_p(stream or 0),
+                                                         idx.ctypes.data_as(C.POINTER(C.c_uint16)), INPUT_DEPTH16 if depth else INPUT_VERTICES,
+                                                         C.c_void_p(d_moments)))
+
+    def process_host_cameras_surfaces(self, frames, camera_of_frame, depth=False, min_points=200, moments=False):
+        """ssd_process_host_cameras_surfaces: frames on the host (float32 [n, H, W, 3], or uint16 [n, H, W] with depth=True), one camera
+        index per frame -> (list of FrameResult, list of FrameSurfaces), with moments=True also the list of FrameMoments"""
+        a = np.ascontiguousarray(frames, dtype=np.uint16 if depth else np.float32) if not isinstance(frames, PinnedArray) else frames.array
+        per = self.cfg.width * self.cfg.height * (1 if depth else 3)
+        n = a.size // per
+        if n < 1 or n * per != a.size:
+            raise SsdError("process_host_cameras_surfaces: array does not hold whole frames")
+        idx = self._camera_index(camera_of_frame, n)
+        res, mom, out = (FrameResult * n)(), (FrameMoments * n)(), (FrameSurfaces * n)()
+        _check(lib().ssd_process_host_cameras_surfaces(self._h, a.ctypes.data_as(C.c_void_p), n, idx.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                                       INPUT_DEPTH16 if depth else INPUT_VERTICES, res, mom if moments else None, int(min_points), out))
+        return (list(res), list(out), list(mom)) if moments else (list(res), list(out))
+
+    def camera_drift(self, frames, camera_of_frame, depth=False, min_points=2000):
+        """process_host_cameras_surfaces, then camera_drift_fold of its moments against the handle's camera table
+        -> (list of FrameResult, list of CameraDrift, one per camera of the table)"""
+        if not getattr(self, "_cameras", None):
+            raise SsdError("camera_drift: the handle has no camera table (set_cameras)")
+        res, _, mom = self.process_host_cameras_surfaces(frames, camera_of_frame, depth=depth, moments=True)
+        return res, camera_drift_fold(mom, camera_of_frame, self._cameras, min_points=min_points)
 
     def surface_moments_time_ms(self, back=0):
         """Device time of the surface-moments pass of the enqueue `back` calls ago (0.0: it gathered none); timing must be on."""

@@ -902,14 +902,14 @@ static int timing_event_pairs(std::vector<hipEvent_t> &out, const char *who)
 }
 
 /* camOf (host, nframes entries; ssd_enqueue_cameras has checked them): a cameras batch - frame i takes camera camOf[i] of the table;
- * moments (device, nframes records): the surface moments of the batch (the handle's one calibration only) */
+ * moments (device, nframes records): the surface moments of the batch (of a cameras batch too: each frame under its own camera) */
 static int enqueue_impl(ssd_handle *h, const void *d_xyz, size_t frame_stride_bytes, int nframes, void *stream, int stages, bool depthInput,
                         unsigned char *labels = nullptr, size_t labelStride = 0, const uint16_t *camOf = nullptr, ssd_frame_moments *moments = nullptr)
 {
   if(!h || !d_xyz)
     return fail(SSD_E_ARG, "ssd_enqueue: null argument");
-  if(moments && (camOf || stages != SSD_STAGE_ALL))
-    return fail(SSD_E_ARG, "ssd_enqueue_surface_moments: camera batches and partial runs have no surface moments");
+  if(moments && stages != SSD_STAGE_ALL)
+    return fail(SSD_E_ARG, "ssd_enqueue_surface_moments: partial runs have no surface moments");
   if(nframes < 1 || nframes > h->F)
     return fail(SSD_E_ARG, "ssd_enqueue: nframes must be 1..max_frames_per_batch");
   const size_t frameBytes = static_cast<size_t>(h->P.nPoints) * (depthInput ? 2 : 12);
@@ -1117,7 +1117,7 @@ static int enqueue_impl(ssd_handle *h, const void *d_xyz, size_t frame_stride_by
     {
       if(marks) (void)hipEventRecord(h->evSurface[2 * timingSlot], cs);
       (void)hipMemsetAsync(moments, 0, sizeof(ssd_frame_moments) * static_cast<size_t>(nframes), cs);
-      launch_surface_moments(xyz, strideFloats, P, L.dState, L.dTileMasks, h->tileMaskStride, nframes, chunk, depth, moments, cs);
+      launch_surface_moments(xyz, strideFloats, P, L.dState, L.dTileMasks, h->tileMaskStride, nframes, chunk, depth, moments, cs, cams);
       if(marks) (void)hipEventRecord(h->evSurface[2 * timingSlot + 1], cs);
     }
   };
@@ -1817,6 +1817,18 @@ int ssd_enqueue_cameras(ssd_handle *h, const void *d_frames, size_t frame_stride
                       camera_of_frame);
 }
 
+int ssd_enqueue_cameras_surface_moments(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream,
+                                        const uint16_t *camera_of_frame, int input, ssd_frame_moments *d_out)
+{
+  if(!h || !d_frames || !d_out)
+    return fail(SSD_E_ARG, "ssd_enqueue_cameras_surface_moments: null argument");
+  if(nframes < 1 || nframes > h->F)
+    return fail(SSD_E_ARG, "ssd_enqueue_cameras_surface_moments: nframes must be 1..max_frames_per_batch");
+  const int rc = check_cameras(h, "ssd_enqueue_cameras_surface_moments", camera_of_frame, nframes, input);
+  if(rc) return rc;
+  return enqueue_impl(h, d_frames, frame_stride_bytes, nframes, stream, SSD_STAGE_ALL, input == SSD_INPUT_DEPTH16, nullptr, 0, camera_of_frame, d_out);
+}
+
 int ssd_process_host_cameras(ssd_handle *h, const void *frames, int nframes, const uint16_t *camera_of_frame, int input,
                              ssd_frame_result *results, uint8_t *labels)
 {
@@ -2108,16 +2120,22 @@ int ssd_surface_fit_solve(const ssd_frame_moments *moments, const ssd_calibratio
   return SSD_OK;
 }
 
-/* the calibration ssd_create gave the handle, as its kernels' constants hold it */
-static ssd_calibration handle_calibration(const ssd_handle *h)
+/* the calibration a set of kernel constants was made from (make_params), as the constants hold it */
+static ssd_calibration calibration_of(const Params &P)
 {
   ssd_calibration c;
-  for(int i = 0; i < 9; i++) c.a[i] = h->P.pt.a[i];
-  for(int i = 0; i < 3; i++) c.b[i] = h->P.pt.b[i];
-  for(int i = 0; i < 4; i++) c.r2[i] = h->P.r2[i];
-  c.t2[0] = h->P.t2[0]; c.t2[1] = h->P.t2[1];
-  c.world_z = h->P.worldZ;
+  for(int i = 0; i < 9; i++) c.a[i] = P.pt.a[i];
+  for(int i = 0; i < 3; i++) c.b[i] = P.pt.b[i];
+  for(int i = 0; i < 4; i++) c.r2[i] = P.r2[i];
+  c.t2[0] = P.t2[0]; c.t2[1] = P.t2[1];
+  c.world_z = P.worldZ;
   return c;
+}
+
+/* the calibration ssd_create gave the handle */
+static ssd_calibration handle_calibration(const ssd_handle *h)
+{
+  return calibration_of(h->P);
 }
 
 int ssd_process_host_surfaces(ssd_handle *h, const void *frames, int nframes, int input, ssd_frame_result *results,
@@ -2152,6 +2170,92 @@ int ssd_process_host_surfaces(ssd_handle *h, const void *frames, int nframes, in
   for(int i = 0; i < nframes; i++)
   {
     rc = ssd_surface_fit_solve(moments + i, &cal, min_points, out + i);
+    if(rc) return rc;
+  }
+  return SSD_OK;
+}
+
+/* ---- surface fit of cameras batches and drift per camera (include/ssd_hip.h) ---------------------------- */
+
+int ssd_process_host_cameras_surfaces(ssd_handle *h, const void *frames, int nframes, const uint16_t *camera_of_frame, int input,
+                                      ssd_frame_result *results, ssd_frame_moments *moments, int min_points, ssd_frame_surfaces *out)
+{
+  if(!h || !frames || !results || !out || nframes < 1)
+    return fail(SSD_E_ARG, "ssd_process_host_cameras_surfaces: bad argument");
+  int rc = check_cameras(h, "ssd_process_host_cameras_surfaces", camera_of_frame, nframes, input);
+  if(rc) return rc;
+  std::vector<ssd_frame_moments> own;
+  if(!moments)
+  {
+    own.resize(static_cast<size_t>(nframes));
+    moments = own.data();
+  }
+  if(input == SSD_INPUT_DEPTH16)
+  {
+    const size_t frameElems = (static_cast<size_t>(h->P.nPoints) + 3) / 4 * 4;       /* as ssd_process_depth_host */
+    rc = process_host_impl(h, frames, static_cast<size_t>(h->P.nPoints) * 2, frameElems * 2, nframes, results, true,
+                           reinterpret_cast<unsigned char *>(moments), camera_of_frame, true);
+  }
+  else
+  {
+    const size_t frameBytes = static_cast<size_t>(h->P.nPoints) * 12;
+    rc = process_host_impl(h, frames, frameBytes, frameBytes, nframes, results, false, reinterpret_cast<unsigned char *>(moments), camera_of_frame, true);
+  }
+  if(rc) return rc;
+  for(int i = 0; i < nframes; i++)
+  {
+    const ssd_calibration cal = calibration_of(h->camParams[camera_of_frame[i]]);
+    rc = ssd_surface_fit_solve(moments + i, &cal, min_points, out + i);
+    if(rc) return rc;
+  }
+  return SSD_OK;
+}
+
+/* host only: no handle, no device */
+int ssd_camera_drift_fold(const ssd_frame_moments *moments, const uint16_t *camera_of_frame, int nframes, const ssd_camera *cams, int ncams,
+                          int min_points, ssd_camera_drift *out)
+{
+  if(!moments || !camera_of_frame || !cams || !out || nframes < 0)
+    return fail(SSD_E_ARG, "ssd_camera_drift_fold: bad argument");
+  if(ncams < 1 || ncams > SSD_MAX_CAMERAS)
+    return fail(SSD_E_ARG, "ssd_camera_drift_fold: ncams must be 1.." + std::to_string(SSD_MAX_CAMERAS));
+  for(int i = 0; i < nframes; i++)
+    if(camera_of_frame[i] >= ncams)
+      return fail(SSD_E_ARG, "ssd_camera_drift_fold: frame " + std::to_string(i) + " names camera " + std::to_string(camera_of_frame[i]) + " of " + std::to_string(ncams));
+  constexpr int kSums = static_cast<int>(sizeof(ssd_surface_moments) / sizeof(int64_t));     /* the ten sums of m, then n_far */
+  static_assert(sizeof(ssd_surface_moments) == sizeof(int64_t) * (kGroundSums + 1) && offsetof(ssd_surface_moments, n_far) == sizeof(ssd_ground_moments),
+                "ssd_surface_moments is the ten sums and n_far, contiguous");
+  std::memset(out, 0, sizeof(ssd_camera_drift) * static_cast<size_t>(ncams));
+  for(int c = 0; c < ncams; c++)
+    out[c].camera = c;
+  /* in index order; a frame whole or not at all: every sum is tried before any is taken */
+  for(int i = 0; i < nframes; i++)
+  {
+    ssd_camera_drift &d = out[camera_of_frame[i]];
+    d.frames++;
+    const ssd_frame_moments &fm = moments[i];
+    if(fm.ground != 1 || fm.n_surfaces < 1)
+      continue;
+    int64_t have[kSums], sum[kSums];
+    std::memcpy(have, &d.m, sizeof(d.m));
+    have[kSums - 1] = d.n_far;
+    const int64_t *add = reinterpret_cast<const int64_t *>(&fm.s[0]);
+    bool fits = true;
+    for(int k = 0; k < kSums; k++)
+      if(__builtin_add_overflow(have[k], add[k], &sum[k]))
+        fits = false;
+    if(!fits)
+    {
+      d.frames_left++;
+      continue;
+    }
+    std::memcpy(&d.m, sum, sizeof(d.m));
+    d.n_far = sum[kSums - 1];
+    d.frames_ground++;
+  }
+  for(int c = 0; c < ncams; c++)
+  {
+    const int rc = ssd_ground_fit_solve(&out[c].m, &cams[c].cal, min_points, &out[c].fit);
     if(rc) return rc;
   }
   return SSD_OK;

@@ -3735,7 +3735,6 @@ SSD_ENTRY(__launch_bounds__(kThreads), k_labels, labels_block)(const float *__re
   }
 }
 
-#ifndef SSD_CAMERAS_TU
 /* ========================================================================= */
 /* K8 (extension): per-surface integer moments (the surface fit)                */
 
@@ -3747,7 +3746,7 @@ SSD_ENTRY(__launch_bounds__(kThreads), k_labels, labels_block)(const float *__re
  * (shuffles, then 64-bit LDS adds by lane 0) and the wave changes over; the lanes of a mixed slot that hold another surface than the
  * current one add their point to the LDS table directly.  At the block's end one 64-bit atomicAdd per non-zero entry of the table goes
  * to the frame's record, which the caller zeroed on the stream.  Integer addition throughout: no result depends on an order.
- * Camera batches have no instantiation of it (include/ssd_hip.h). */
+ * Camera batches: k_surface_moments_cams (ssd_kernels_cams.hip) runs this body with the frame's own constants. */
 constexpr int kSurfaceSums = kGroundSums + 1;       /* ssd_surface_moments as 11 int64: the ten sums, n_far */
 static_assert(sizeof(ssd_surface_moments) == 8 * kSurfaceSums && sizeof(ssd_frame_moments) == 8 + SSD_MAX_STEPS * 8 * kSurfaceSums,
               "ssd_frame_moments is the kernel's record: a header of two int32, then kSurfaceSums int64 per surface");
@@ -3782,9 +3781,9 @@ __device__ __forceinline__ void surface_flush(long long (&acc)[kSurfaceSums], un
 }
 
 template<int SRC, bool CHECKS>
-__global__ __launch_bounds__(kThreads) void k_surface_moments(const float *__restrict__ xyz, size_t strideFloats, PointParams P, PreXY Q,
+SSD_ENTRY(__launch_bounds__(kThreads), k_surface_moments, surface_moments_block)(const float *__restrict__ xyz, size_t strideFloats, SSD_BYVAL(PointParams) P, SSD_BYVAL(PreXY) Q,
                                                               const FrameState *__restrict__ st, const uint2 *__restrict__ tileMasks,
-                                                              size_t tileMaskStride, int chunkPoints, DepthSrc D,
+                                                              size_t tileMaskStride, int chunkPoints, SSD_BYVAL(DepthSrc) D,
                                                               ssd_frame_moments *__restrict__ out)
 {
   __shared__ SurfaceLds S;
@@ -3919,7 +3918,6 @@ __global__ __launch_bounds__(kThreads) void k_surface_moments(const float *__res
       atomicAdd(reinterpret_cast<unsigned long long *>(out + frame) + 1 + tid, t);
   }
 }
-#endif /* SSD_CAMERAS_TU */
 
 /* ========================================================================= */
 /* K5: ground front edge and the per-frame result — one workgroup per frame     */
@@ -4629,8 +4627,10 @@ void launch_labels(const float *xyz, size_t strideFloats, const Params &P, const
   });
 }
 void launch_surface_moments(const float *xyz, size_t strideFloats, const Params &P, const FrameState *st, const uint2 *tileMasks, size_t tileMaskStride,
-                            int nframes, int chunkPoints, const DepthSrc *depth, ssd_frame_moments *out, hipStream_t s)
+                            int nframes, int chunkPoints, const DepthSrc *depth, ssd_frame_moments *out, hipStream_t s, const CameraSel *cams)
 {
+  if(cams)
+    return launch_surface_moments_cams(xyz, strideFloats, P, st, tileMasks, tileMaskStride, nframes, chunkPoints, depth, out, s, *cams);
   dim3 grid(nframes, chunks_for(P.nPoints, chunkPoints));
   with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &D)
   {

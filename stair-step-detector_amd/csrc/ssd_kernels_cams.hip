@@ -160,6 +160,18 @@ __global__ __launch_bounds__(kThreads) void k_labels_cams(const float *__restric
   labels_block<SRC, CHECKS>(xyz, strideFloats, P, Q, st, tileMasks, tileMaskStride, chunkPoints, D, labels, labelStride);
 }
 
+template<int SRC, bool CHECKS>
+__global__ __launch_bounds__(kThreads) void k_surface_moments_cams(const float *__restrict__ xyz, size_t strideFloats, const CameraRec *__restrict__ cams,
+                                                                   const int *__restrict__ camOf, const FrameState *__restrict__ st, const uint2 *__restrict__ tileMasks,
+                                                                   size_t tileMaskStride, int chunkPoints, ssd_frame_moments *__restrict__ out)
+{
+  const CameraRec &C = camera_of(cams, camOf, blockIdx.x);
+  const PointParams P = C.P.pt;
+  const PreXY Q = C.P.pre;
+  const DepthSrc D = C.D;
+  surface_moments_block<SRC, CHECKS>(xyz, strideFloats, P, Q, st, tileMasks, tileMaskStride, chunkPoints, D, out);
+}
+
 template<int SRC>
 __global__ __launch_bounds__(kThreads, 8) void k_risers_cams(const float *__restrict__ xyz, size_t strideFloats, const CameraRec *__restrict__ cams,
                                                              const int *__restrict__ camOf, FrameState *__restrict__ st, const uint2 *__restrict__ tileMasks,
@@ -279,6 +291,18 @@ void launch_labels_cams(const float *xyz, size_t strideFloats, const Params &P, 
     with_bool(cams.checks, [&](auto checks)
     {
       hipLaunchKernelGGL((k_labels_cams<decltype(src)::value, decltype(checks)::value>), grid, dim3(kThreads), 0, s, xyz, strideFloats, cams.table, cams.index, st, tileMasks, tileMaskStride, chunkPoints, labels, labelStride);
+    });
+  });
+}
+void launch_surface_moments_cams(const float *xyz, size_t strideFloats, const Params &P, const FrameState *st, const uint2 *tileMasks, size_t tileMaskStride,
+                                 int nframes, int chunkPoints, const DepthSrc *depth, ssd_frame_moments *out, hipStream_t s, const CameraSel &cams)
+{
+  dim3 grid(nframes, chunks_for(P.nPoints, chunkPoints));
+  with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &)
+  {
+    with_bool(cams.checks, [&](auto checks)
+    {
+      hipLaunchKernelGGL((k_surface_moments_cams<decltype(src)::value, decltype(checks)::value>), grid, dim3(kThreads), 0, s, xyz, strideFloats, cams.table, cams.index, st, tileMasks, tileMaskStride, chunkPoints, out);
     });
   });
 }

@@ -47,9 +47,9 @@ void launch_inquad(const float *xyz, size_t strideFloats, const Params &P, Frame
                    const uint2 *tileMasks, size_t tileMaskStride, int nframes, int chunkPoints, const DepthSrc *depth, hipStream_t s, const CameraSel *cams = nullptr);
 void launch_final(const Params &P, FrameState *st, unsigned long long *groundImg, ssd_frame_result *results, int nframes, DebugFrame *dbg, unsigned long long *dbgImg, hipStream_t s, const CameraSel *cams = nullptr);
 /* per-surface moments (k_surface_moments) after launch_final: frame i's record at out + i, zeroed by the caller on the stream in front of
- * the launch; chunkPoints as launch_labels'.  The handle's one calibration only: camera batches have none. */
+ * the launch; chunkPoints as launch_labels' */
 void launch_surface_moments(const float *xyz, size_t strideFloats, const Params &P, const FrameState *st, const uint2 *tileMasks, size_t tileMaskStride,
-                            int nframes, int chunkPoints, const DepthSrc *depth, ssd_frame_moments *out, hipStream_t s);
+                            int nframes, int chunkPoints, const DepthSrc *depth, ssd_frame_moments *out, hipStream_t s, const CameraSel *cams = nullptr);
 /* per-pixel surface labels (k_labels) after launch_final: frame i's W H labels at labels + i * labelStride; chunkPoints as launch_risers' */
 void launch_labels(const float *xyz, size_t strideFloats, const Params &P, const FrameState *st, const uint2 *tileMasks, size_t tileMaskStride,
                    int nframes, int chunkPoints, const DepthSrc *depth, unsigned char *labels, size_t labelStride, hipStream_t s, const CameraSel *cams = nullptr);
@@ -66,6 +66,7 @@ void launch_quads_cams(const Params &P, FrameState *st, int nframes, DebugFrame 
 void launch_inquad_cams(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, unsigned long long *groundImg, const uint2 *tileMasks, size_t tileMaskStride, int nframes, int chunkPoints, const DepthSrc *depth, hipStream_t s, const CameraSel &cams);
 void launch_final_cams(const Params &P, FrameState *st, unsigned long long *groundImg, ssd_frame_result *results, int nframes, DebugFrame *dbg, unsigned long long *dbgImg, hipStream_t s, const CameraSel &cams);
 void launch_labels_cams(const float *xyz, size_t strideFloats, const Params &P, const FrameState *st, const uint2 *tileMasks, size_t tileMaskStride, int nframes, int chunkPoints, const DepthSrc *depth, unsigned char *labels, size_t labelStride, hipStream_t s, const CameraSel &cams);
+void launch_surface_moments_cams(const float *xyz, size_t strideFloats, const Params &P, const FrameState *st, const uint2 *tileMasks, size_t tileMaskStride, int nframes, int chunkPoints, const DepthSrc *depth, ssd_frame_moments *out, hipStream_t s, const CameraSel &cams);
 void launch_risers_cams(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, const uint2 *tileMasks, size_t tileMaskStride, ssd_frame_risers *out, int nframes, int chunkPoints, const DepthSrc *depth, hipStream_t s, const CameraSel &cams);
 }
 
