@@ -505,6 +505,71 @@ typedef struct
 int ssd_camera_drift_fold(const ssd_frame_moments *moments, const uint16_t *camera_of_frame, int nframes,
                           const ssd_camera *cams, int ncams, int min_points, ssd_camera_drift *out /* ncams records */);
 
+/* ---- riser fit: plane, lean and going of every vertical face ------------------------------------------------------------------
+ * EXTENSION: what the surface fit does for the treads, for the risers between them.  While the riser moments
+ * are on, the riser pass (ssd_set_risers) gathers in the SAME walk, beside the count and the mean offset of every riser, the exact
+ * integer moments of its evidence points, and a small host solve turns them into a plane per riser: is the face vertical (lean), is it
+ * parallel to the front edge the detector drew (skew), and how far is it from the next face (going: the tread depth a stair-climbing
+ * consumer needs beside the rise).
+ * Evidence point of riser i: exactly the points ssd_riser.n_points counts (above).  The riser moments of a frame are an
+ * ssd_frame_moments: n_surfaces = the frame's n_risers, ground = 0, s[i] = riser i, records at i >= n_risers zero.  s[i].m holds the
+ * ten sums of ssd_ground_moments over riser i's evidence points, q = llrint(double(v) * 65536.0) on the float camera coordinates
+ * (16-bit depth input is deprojected first, bit-equal to ssd_deproject_host); an evidence point with some |q| >= 2^20 is left out of
+ * the sums and counted in s[i].n_far, so s[i].m.n + s[i].n_far == risers[i].n_points.  The overflow argument is the ground fit's: all
+ * sums are exact integers, independent of the order of summation; the device and ssd_surface_moments_host over the riser labels of a
+ * host restatement agree bit for bit.
+ *   ssd_set_riser_moments    waits for the handle's batches in flight.  While it is on AND risers are on, every riser pass of a whole
+ *                            run (ssd_enqueue*, ssd_process_*, the cameras entry points) also gathers the moments; it may be set while
+ *                            risers are off and takes effect when they come on.  Results, risers and debug records do not change.
+ *                            Its device and pinned buffers (one ssd_frame_moments per frame of max_frames_per_batch each) are made on
+ *                            the first enable and counted in ssd_workspace_bytes from then on; a handle that never enables it
+ *                            allocates and launches nothing more.  Not part of ssd_enqueue_stages or ssd_pipeline_*.
+ *   ssd_fetch_riser_moments  the contract of ssd_fetch_risers: the last enqueue, or the whole batch of the last host call (collected
+ *                            slice by slice).  SSD_E_ARG when the last pass gathered none or nframes exceeds what it processed.
+ * Camera batches: frame i's riser moments are byte for byte those of a handle made by ssd_create(cfg, &cams[camera_of_frame[i]].cal)
+ * (with its intrinsics for depth input) for that frame alone. */
+typedef struct
+{
+  int32_t status, reserved;   /* SSD_GF_OK / SSD_GF_FEW / SSD_GF_DEGENERATE */
+  int64_t n, n_far;           /* as in the moments */
+  double normal[3];   /* unit, external world coordinates, out of the face toward the camera: -(A n0), x and y through r2 */
+  double centroid[3]; /* mean of the evidence points, external world (as ssd_surface_fit.centroid) */
+  double lean;        /* asin(normal z), signed: the angle of the face from the vertical, positive when the face looks upward */
+  double skew;        /* asin(|h . u|) in [0, pi/2], h = the unit horizontal projection of normal, u = the unit direction left -> right of
+                         the riser's ssd_riser: the angle between the fitted face and the front edge the detector drew */
+  double rms;         /* sqrt(lambda_min): rms distance of the points from the plane, metres */
+  double extent[2];   /* sqrt(lambda_max), sqrt(lambda_mid): rms half-extents of the points within the plane, metres */
+  double rise;        /* height_top - height_bottom of the ssd_riser (whatever the status) */
+  double going;       /* this riser and the next both OK: |(centroid[i + 1] - centroid[i]) . h_i|, the horizontal distance from this
+                         face to the next = the depth of the tread between them; otherwise 0 */
+} ssd_riser_fit;
+
+typedef struct
+{
+  int32_t n_risers, reserved;
+  ssd_riser_fit r[SSD_MAX_RISERS];
+} ssd_frame_riser_fits;
+
+int ssd_set_riser_moments(ssd_handle *h, int enable);
+int ssd_fetch_riser_moments(ssd_handle *h, ssd_frame_moments *out, int nframes, void *stream);
+/* host only, no GPU needed: a frame's riser moments and riser records -> a plane per riser, by the solve of ssd_ground_fit_solve (the
+ * same code, shared).  Status per riser in this order: FEW (n < max(min_points, 1)), DEGENERATE (the shared SSD_GF_PLANARITY rule), OK.
+ * Unless OK the doubles other than rise are 0; n and n_far are always the moments'.  A horizontal normal or a drawn edge of length 0
+ * gives skew 0.  Records at i >= n_risers are zero.  SSD_E_ARG: a null pointer, n_surfaces outside 0 .. SSD_MAX_RISERS or not the
+ * risers' n_risers. */
+int ssd_riser_fit_solve(const ssd_frame_moments *moments, const ssd_frame_risers *risers, const ssd_calibration *cal, int min_points,
+                        ssd_frame_riser_fits *out);
+/* frames in host memory through the slices of ssd_process_host / ssd_process_depth_host (input as ssd_process_host_surfaces) resp.
+ * ssd_process_host_cameras: fills results[nframes], risers[nframes], out[nframes] (out[i] = ssd_riser_fit_solve under the frame's own
+ * calibration) and, when not NULL, moments[nframes].  Risers must be on (ssd_set_risers), else SSD_E_ARG before anything is copied; the
+ * riser moments are switched on for the call and the previous setting is restored. */
+int ssd_process_host_riser_fits(ssd_handle *h, const void *frames, int nframes, int input, ssd_frame_result *results,
+                                ssd_frame_risers *risers, ssd_frame_moments *moments /* may be NULL */, int min_points,
+                                ssd_frame_riser_fits *out);
+int ssd_process_host_cameras_riser_fits(ssd_handle *h, const void *frames, int nframes, const uint16_t *camera_of_frame, int input,
+                                        ssd_frame_result *results, ssd_frame_risers *risers, ssd_frame_moments *moments /* may be NULL */,
+                                        int min_points, ssd_frame_riser_fits *out);
+
 /* stage selector for profiling / roofline measurement: runs only the chosen stage(s) of the pipeline */
 #define SSD_STAGE_HIST 1       /* K1: transform + crop + bin + histogram */
 #define SSD_STAGE_PEAKS 2

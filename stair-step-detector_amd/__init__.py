@@ -165,6 +165,21 @@ class FrameSurfaces(C.Structure):
     _fields_ = [("n_surfaces", C.c_int32), ("ground", C.c_int32), ("s", SurfaceFit * MAX_STEPS)]
 
 
+MAX_RISERS = MAX_STEPS - 1
+
+
+class RiserFit(C.Structure):
+    """ssd_riser_fit: one riser's plane in external world coordinates (status != GF_OK: the doubles other than rise are 0)"""
+    _fields_ = [("status", C.c_int32), ("reserved", C.c_int32), ("n", C.c_int64), ("n_far", C.c_int64), ("normal", C.c_double * 3),
+                ("centroid", C.c_double * 3), ("lean", C.c_double), ("skew", C.c_double), ("rms", C.c_double), ("extent", C.c_double * 2),
+                ("rise", C.c_double), ("going", C.c_double)]
+
+
+class FrameRiserFits(C.Structure):
+    """ssd_frame_riser_fits: the fitted plane, lean, skew and going of every riser of a frame (riser fit)"""
+    _fields_ = [("n_risers", C.c_int32), ("reserved", C.c_int32), ("r", RiserFit * MAX_RISERS)]
+
+
 class CameraDrift(C.Structure):
     """ssd_camera_drift: a camera's ground moments over the frames of a batch that name it, added exactly, and the ground fit of the
     sum against its table entry (fit.tilt, fit.height_delta: how far the mounting has moved)"""
@@ -206,6 +221,8 @@ EXPORTS = [
     "ssd_enqueue_surface_moments", "ssd_enqueue_depth_surface_moments", "ssd_get_surface_moments_time_back", "ssd_surface_moments_host",
     "ssd_surface_fit_solve", "ssd_process_host_surfaces",
     "ssd_enqueue_cameras_surface_moments", "ssd_process_host_cameras_surfaces", "ssd_camera_drift_fold",
+    "ssd_set_riser_moments", "ssd_fetch_riser_moments", "ssd_riser_fit_solve", "ssd_process_host_riser_fits",
+    "ssd_process_host_cameras_riser_fits",
 ]
 # libssd_source.so — the frame source standing in for the camera (include/ssd_source.h)
 SOURCE_EXPORTS = [
@@ -288,6 +305,13 @@ def lib():
     L.ssd_process_host_cameras_surfaces.argtypes = [vp, vp, i32, C.POINTER(C.c_uint16), i32, C.POINTER(FrameResult), C.POINTER(FrameMoments), i32,
                                                     C.POINTER(FrameSurfaces)]
     L.ssd_camera_drift_fold.argtypes = [C.POINTER(FrameMoments), C.POINTER(C.c_uint16), i32, C.POINTER(Camera), i32, i32, C.POINTER(CameraDrift)]
+    L.ssd_set_riser_moments.argtypes = [vp, i32]
+    L.ssd_fetch_riser_moments.argtypes = [vp, C.POINTER(FrameMoments), i32, vp]
+    L.ssd_riser_fit_solve.argtypes = [C.POINTER(FrameMoments), C.POINTER(FrameRisers), C.POINTER(Calibration), i32, C.POINTER(FrameRiserFits)]
+    L.ssd_process_host_riser_fits.argtypes = [vp, vp, i32, i32, C.POINTER(FrameResult), C.POINTER(FrameRisers), C.POINTER(FrameMoments), i32,
+                                              C.POINTER(FrameRiserFits)]
+    L.ssd_process_host_cameras_riser_fits.argtypes = [vp, vp, i32, C.POINTER(C.c_uint16), i32, C.POINTER(FrameResult), C.POINTER(FrameRisers),
+                                                      C.POINTER(FrameMoments), i32, C.POINTER(FrameRiserFits)]
     L.ssd_serialize.argtypes = [C.POINTER(FrameResult), C.c_char_p, sz]
     L.ssd_set_debug.argtypes = [vp, i32]
     L.ssd_get_debug.argtypes = [vp, i32, C.POINTER(DebugFrame)]
@@ -513,6 +537,16 @@ def surface_fit_solve(moments, cal, min_points=200):
     c = cal.constants if isinstance(cal, GeometricTransformation) else cal.cal if isinstance(cal, Camera) else cal
     out = FrameSurfaces()
     _check(lib().ssd_surface_fit_solve(C.byref(moments), C.byref(c), int(min_points), C.byref(out)))
+    return out
+
+
+def riser_fit_solve(moments, risers, cal, min_points=100):
+    """ssd_riser_fit_solve: a frame's riser moments (FrameMoments, record i = riser i) and its FrameRisers -> a plane per riser
+    (FrameRiserFits; per riser GF_OK / GF_FEW / GF_DEGENERATE, lean, skew, rise and going)"""
+    c = cal.constants if isinstance(cal, GeometricTransformation) else cal.cal if isinstance(cal, Camera) else cal
+    out = FrameRiserFits()
+    _check(lib().ssd_riser_fit_solve(C.byref(moments) if moments is not None else None, C.byref(risers) if risers is not None else None,
+                                     C.byref(c) if c is not None else None, int(min_points), C.byref(out)))
     return out
 
 
@@ -876,6 +910,44 @@ class Detector:
         arr = (FrameRisers * nframes)()
         _check(lib().ssd_fetch_risers(self._h, arr, nframes, C.c_void_p(stream or 0)))
         return [FrameRisers.from_buffer_copy(bytes(r)) for r in arr]
+
+    # ---- riser fit: plane, lean and going of every vertical face (include/ssd_hip.h)
+    def set_riser_moments(self, on=True):
+        """ssd_set_riser_moments: while on (and risers are on) every riser pass also gathers each riser's exact integer moments"""
+        _check(lib().ssd_set_riser_moments(self._h, 1 if on else 0))
+
+    def fetch_riser_moments(self, nframes, stream=None):
+        """-> list of FrameMoments (independent copies; record i = riser i) of the last enqueue / host batch"""
+        arr = (FrameMoments * max(1, nframes))()
+        _check(lib().ssd_fetch_riser_moments(self._h, arr, nframes, C.c_void_p(stream or 0)))
+        return [FrameMoments.from_buffer_copy(arr[i]) for i in range(nframes)]
+
+    def _host_riser_fits(self, who, frames, camera_of_frame, depth, min_points, moments):
+        a = np.ascontiguousarray(frames, dtype=np.uint16 if depth else np.float32) if not isinstance(frames, PinnedArray) else frames.array
+        per = self.cfg.width * self.cfg.height * (1 if depth else 3)
+        n = a.size // per
+        if n < 1 or n * per != a.size:
+            raise SsdError("%s: array does not hold whole frames" % who)
+        res, ris, mom, out = (FrameResult * n)(), (FrameRisers * n)(), (FrameMoments * n)(), (FrameRiserFits * n)()
+        inp = INPUT_DEPTH16 if depth else INPUT_VERTICES
+        if camera_of_frame is None:
+            _check(lib().ssd_process_host_riser_fits(self._h, a.ctypes.data_as(C.c_void_p), n, inp, res, ris, mom if moments else None,
+                                                     int(min_points), out))
+        else:
+            idx = self._camera_index(camera_of_frame, n)
+            _check(lib().ssd_process_host_cameras_riser_fits(self._h, a.ctypes.data_as(C.c_void_p), n, idx.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                                             inp, res, ris, mom if moments else None, int(min_points), out))
+        return (list(res), list(ris), list(out), list(mom)) if moments else (list(res), list(ris), list(out))
+
+    def process_host_riser_fits(self, frames, depth=False, min_points=100, moments=False):
+        """ssd_process_host_riser_fits (risers must be on): frames on the host (float32 [n, H, W, 3], or uint16 [n, H, W] with depth=True)
+        -> (list of FrameResult, list of FrameRisers, list of FrameRiserFits), with moments=True also the list of FrameMoments"""
+        return self._host_riser_fits("process_host_riser_fits", frames, None, depth, min_points, moments)
+
+    def process_host_cameras_riser_fits(self, frames, camera_of_frame, depth=False, min_points=100, moments=False):
+        """ssd_process_host_cameras_riser_fits: the same for a cameras batch, one camera index per frame, each frame solved under its own
+        camera's calibration"""
+        return self._host_riser_fits("process_host_cameras_riser_fits", frames, camera_of_frame, depth, min_points, moments)
 
     def set_timing(self, on=True):
         _check(lib().ssd_set_timing(self._h, 1 if on else 0))

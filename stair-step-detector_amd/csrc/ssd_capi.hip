@@ -613,6 +613,9 @@ int ssd_destroy(ssd_handle *h)
   if(h->dRisers) (void)hipFree(h->dRisers);
   if(h->hRisers) (void)hipHostFree(h->hRisers);
   if(h->hRisersBatch) (void)hipHostFree(h->hRisersBatch);
+  if(h->dRiserMoments) (void)hipFree(h->dRiserMoments);
+  if(h->hRiserMoments) (void)hipHostFree(h->hRiserMoments);
+  if(h->hRiserMomentsBatch) (void)hipHostFree(h->hRiserMomentsBatch);
   if(h->dDebug) (void)hipFree(h->dDebug);
   if(h->dDebugImg) (void)hipFree(h->dDebugImg);
   for(hipEvent_t e : h->evPredict)
@@ -798,6 +801,60 @@ int ssd_fetch_risers(ssd_handle *h, ssd_frame_risers *out, int nframes, void *st
   HIP_TRY(hipMemcpyAsync(h->hRisers, h->dRisers, sizeof(ssd_frame_risers) * nframes, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   std::memcpy(out, h->hRisers, sizeof(ssd_frame_risers) * nframes);
+  return SSD_OK;
+}
+
+int ssd_set_riser_moments(ssd_handle *h, int enable)
+{
+  if(!h)
+    return fail(SSD_E_ARG, "ssd_set_riser_moments: null handle");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipDeviceSynchronize());            /* the batches in flight keep the kernel they were enqueued with */
+  if(enable && (!h->dRiserMoments || !h->hRiserMoments))
+  {
+    const size_t bytes = sizeof(ssd_frame_moments) * h->F;
+    ssd_frame_moments *d = nullptr, *hh = nullptr;
+    HIP_TRY(hipMalloc(&d, bytes));
+    hipError_t e = hipMemset(d, 0, bytes);
+    if(e == hipSuccess)
+      e = hipHostMalloc(&hh, bytes, hipHostMallocDefault);
+    if(e != hipSuccess)
+    {
+      (void)hipFree(d);
+      return fail(e == hipErrorOutOfMemory ? SSD_E_NOMEM : SSD_E_HIP, std::string("ssd_set_riser_moments: ") + hipGetErrorString(e));
+    }
+    h->dRiserMoments = d;
+    h->hRiserMoments = hh;
+    h->bytes += bytes;
+  }
+  h->riserMoments = enable != 0;
+  return SSD_OK;
+}
+
+int ssd_fetch_riser_moments(ssd_handle *h, ssd_frame_moments *out, int nframes, void *stream)
+{
+  if(!h || !out)
+    return fail(SSD_E_ARG, "ssd_fetch_riser_moments: null argument");
+  HIP_TRY(hipSetDevice(h->device));
+  if(h->hRiserMomentsBatchFrames > 0)
+  {
+    /* the last call was a host-fed batch: its riser moments were collected slice by slice */
+    if(nframes < 1 || nframes > h->hRiserMomentsBatchFrames)
+      return fail(SSD_E_ARG, "ssd_fetch_riser_moments: nframes exceeds what the last call processed");
+    HIP_TRY(hipStreamSynchronize(h->ingestCompute));
+    std::memcpy(out, h->hRiserMomentsBatch, sizeof(ssd_frame_moments) * nframes);
+    return SSD_OK;
+  }
+  if(h->riserMomentsFrames < 1 || !h->dRiserMoments || !h->hRiserMoments)
+    return fail(SSD_E_ARG, "ssd_fetch_riser_moments: the last pass gathered none (ssd_set_risers and ssd_set_riser_moments before the enqueue)");
+  if(nframes < 1 || nframes > h->riserMomentsFrames)
+    return fail(SSD_E_ARG, "ssd_fetch_riser_moments: nframes exceeds what the last enqueue processed");
+  /* single like the riser buffer: enqueues with risers on all run in lane 0, whose `done` event covers the last one */
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  HIP_TRY(hipStreamWaitEvent(s, h->lane[h->lastLane].done, 0));
+  HIP_TRY(hipMemcpyAsync(h->hRiserMoments, h->dRiserMoments, sizeof(ssd_frame_moments) * nframes, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  std::memcpy(out, h->hRiserMoments, sizeof(ssd_frame_moments) * nframes);
   return SSD_OK;
 }
 
@@ -1058,6 +1115,8 @@ static int enqueue_impl(ssd_handle *h, const void *d_xyz, size_t frame_stride_by
   }
   h->surfaceTimed[timingSlot] = moments != nullptr && timing;
   int evi = timingSlot * 8;
+  /* riser moments: whole runs only (ssd_enqueue_stages takes none), and only with the riser pass they ride on */
+  const bool riserMoments = P.risers && h->riserMoments && h->dRiserMoments && h->dRisers && stages == SSD_STAGE_ALL;
 
   const int slot = static_cast<int>(h->finalCount % static_cast<unsigned long long>(h->nSlots));
   const bool direct = nframes <= kDirectResultFrames && h->hResultsDev != nullptr;
@@ -1101,7 +1160,13 @@ static int enqueue_impl(ssd_handle *h, const void *d_xyz, size_t frame_stride_by
     {
       ssd_frame_result *out = (direct ? h->hResultsDev : h->dResults) + static_cast<size_t>(slot) * h->F;
       launch_final(P, L.dState, L.dGroundImg, out, nframes, dbg, dbgImg, cs, cams);
-      if(P.risers)
+      if(P.risers && riserMoments)
+      {
+        /* the riser fit: k_riser_moments in place of k_risers - one walk, both results; the records are zeroed in front of it, it only adds */
+        (void)hipMemsetAsync(h->dRiserMoments, 0, sizeof(ssd_frame_moments) * static_cast<size_t>(nframes), cs);
+        launch_riser_moments(xyz, strideFloats, P, L.dState, L.dTileMasks, h->tileMaskStride, h->dRisers, h->dRiserMoments, nframes, chunk, depth, cs, cams);
+      }
+      else if(P.risers)
         launch_risers(xyz, strideFloats, P, L.dState, L.dTileMasks, h->tileMaskStride, h->dRisers, nframes, chunk, depth, cs, cams);
     }
     mk();
@@ -1183,6 +1248,8 @@ static int enqueue_impl(ssd_handle *h, const void *d_xyz, size_t frame_stride_by
   h->lastFrames = nframes;
   h->lastLane = li;
   h->hRisersBatchFrames = 0;
+  h->riserMomentsFrames = riserMoments ? nframes : 0;
+  h->hRiserMomentsBatchFrames = 0;
   h->enqueueCount++;
   return SSD_OK;
 }
@@ -1526,6 +1593,16 @@ static int process_host_impl(ssd_handle *h, const void *src, size_t srcFrameByte
     HIP_TRY(hipHostMalloc(&h->hRisersBatch, sizeof(ssd_frame_risers) * static_cast<size_t>(nframes), hipHostMallocDefault));
     h->hRisersBatchCap = nframes;
   }
+  const bool riserMoments = risers && h->riserMoments && h->dRiserMoments;
+  if(riserMoments && h->hRiserMomentsBatchCap < nframes)
+  {
+    HIP_TRY(hipStreamSynchronize(h->ingestCompute));
+    if(h->hRiserMomentsBatch) (void)hipHostFree(h->hRiserMomentsBatch);
+    h->hRiserMomentsBatch = nullptr;
+    h->hRiserMomentsBatchCap = 0;
+    HIP_TRY(hipHostMalloc(&h->hRiserMomentsBatch, sizeof(ssd_frame_moments) * static_cast<size_t>(nframes), hipHostMallocDefault));
+    h->hRiserMomentsBatchCap = nframes;
+  }
   const unsigned char *from = static_cast<const unsigned char *>(src);
   int prevFrames = 0, prevAt = 0, c = 0;
   for(int done = 0; done < nframes; c++)
@@ -1573,6 +1650,8 @@ static int process_host_impl(ssd_handle *h, const void *src, size_t srcFrameByte
       rc = ssd_stream_wait(h, 0, h->ingestCompute);
       if(rc) return rc;
       HIP_TRY(hipMemcpyAsync(h->hRisersBatch + done, h->dRisers, sizeof(ssd_frame_risers) * n, hipMemcpyDeviceToHost, h->ingestCompute));
+      if(riserMoments)
+        HIP_TRY(hipMemcpyAsync(h->hRiserMomentsBatch + done, h->dRiserMoments, sizeof(ssd_frame_moments) * n, hipMemcpyDeviceToHost, h->ingestCompute));
       HIP_TRY(hipEventRecord(h->ingestConsumed[k], h->ingestCompute));
     }
     else
@@ -1601,6 +1680,7 @@ static int process_host_impl(ssd_handle *h, const void *src, size_t srcFrameByte
   if(labels)
     HIP_TRY(hipStreamSynchronize(h->labelsCopy));
   h->hRisersBatchFrames = risers ? nframes : 0;
+  h->hRiserMomentsBatchFrames = riserMoments ? nframes : 0;
   return SSD_OK;
 }
 
@@ -2209,6 +2289,134 @@ int ssd_process_host_cameras_surfaces(ssd_handle *h, const void *frames, int nfr
     if(rc) return rc;
   }
   return SSD_OK;
+}
+
+/* ---- riser fit (include/ssd_hip.h): host side ------------------------------------------------------------ */
+
+int ssd_riser_fit_solve(const ssd_frame_moments *moments, const ssd_frame_risers *risers, const ssd_calibration *cal, int min_points,
+                        ssd_frame_riser_fits *out)
+{
+  if(!moments || !risers || !cal || !out)
+    return fail(SSD_E_ARG, "ssd_riser_fit_solve: null");
+  if(moments->n_surfaces < 0 || moments->n_surfaces > SSD_MAX_RISERS || moments->n_surfaces != risers->n_risers)
+    return fail(SSD_E_ARG, "ssd_riser_fit_solve: n_surfaces must lie in 0 .. SSD_MAX_RISERS and be the risers' n_risers");
+  std::memset(out, 0, sizeof(*out));
+  const int nR = moments->n_surfaces;
+  out->n_risers = nR;
+  double hdir[SSD_MAX_RISERS][2] = {};      /* the unit horizontal projection of each OK normal (0, 0: horizontal normal) */
+  for(int i = 0; i < nR; i++)
+  {
+    const ssd_surface_moments &sm = moments->s[i];
+    const ssd_riser &q = risers->risers[i];
+    ssd_riser_fit &f = out->r[i];
+    f.n = sm.m.n;
+    f.n_far = sm.n_far;
+    f.rise = q.height_top - q.height_bottom;
+    PlaneOfMoments pl;
+    f.status = plane_of_moments(&sm.m, min_points, pl);
+    if(f.status != SSD_GF_OK)
+      continue;
+    /* normal and centroid exactly as ssd_surface_fit_solve takes them: n0 points away from the camera, so -(A n0) looks at it */
+    double nw[3], w[3];
+    for(int k = 0; k < 3; k++)
+    {
+      nw[k] = -((cal->a[3 * k] * pl.n0[0] + cal->a[3 * k + 1] * pl.n0[1]) + cal->a[3 * k + 2] * pl.n0[2]);
+      w[k] = ((cal->a[3 * k] * pl.centroid[0] + cal->a[3 * k + 1] * pl.centroid[1]) + cal->a[3 * k + 2] * pl.centroid[2]) + cal->b[k];
+    }
+    f.normal[0] = cal->r2[0] * nw[0] + cal->r2[1] * nw[1];
+    f.normal[1] = cal->r2[2] * nw[0] + cal->r2[3] * nw[1];
+    f.normal[2] = nw[2];
+    f.centroid[0] = (cal->r2[0] * w[0] + cal->r2[1] * w[1]) + cal->t2[0];
+    f.centroid[1] = (cal->r2[2] * w[0] + cal->r2[3] * w[1]) + cal->t2[1];
+    f.centroid[2] = w[2] + cal->world_z;
+    const double nz = f.normal[2] > 1.0 ? 1.0 : f.normal[2] < -1.0 ? -1.0 : f.normal[2];
+    f.lean = std::asin(nz);
+    const double hl = std::sqrt(f.normal[0] * f.normal[0] + f.normal[1] * f.normal[1]);
+    const double ex = q.right[0] - q.left[0], ey = q.right[1] - q.left[1];
+    const double el = std::sqrt(ex * ex + ey * ey);
+    if(hl > 0.0)
+    {
+      hdir[i][0] = f.normal[0] / hl;
+      hdir[i][1] = f.normal[1] / hl;
+    }
+    if(hl > 0.0 && el > 0.0)
+    {
+      const double d = std::fabs(hdir[i][0] * (ex / el) + hdir[i][1] * (ey / el));
+      f.skew = std::asin(d > 1.0 ? 1.0 : d);
+    }
+    f.rms = std::sqrt(pl.lambda[0] > 0.0 ? pl.lambda[0] : 0.0);
+    f.extent[0] = std::sqrt(pl.lambda[2]);
+    f.extent[1] = std::sqrt(pl.lambda[1]);
+  }
+  for(int i = 0; i + 1 < nR; i++)
+  {
+    const ssd_riser_fit &a = out->r[i], &b = out->r[i + 1];
+    if(a.status == SSD_GF_OK && b.status == SSD_GF_OK)
+      out->r[i].going = std::fabs((b.centroid[0] - a.centroid[0]) * hdir[i][0] + (b.centroid[1] - a.centroid[1]) * hdir[i][1]);
+  }
+  return SSD_OK;
+}
+
+/* both host entry points: the batch through process_host_impl with the riser moments on, then the riser records, the moments, the solve */
+static int process_host_riser_fits_impl(ssd_handle *h, const char *who, const void *frames, int nframes, const uint16_t *camOf, int input,
+                                        ssd_frame_result *results, ssd_frame_risers *risers, ssd_frame_moments *moments, int min_points,
+                                        ssd_frame_riser_fits *out)
+{
+  if(!h->P.risers || !h->dRisers)
+    return fail(SSD_E_ARG, std::string(who) + ": call ssd_set_risers(h, 1, ...) first");
+  std::vector<ssd_frame_moments> own;
+  if(!moments)
+  {
+    own.resize(static_cast<size_t>(nframes));
+    moments = own.data();
+  }
+  const bool was = h->riserMoments;
+  int rc = ssd_set_riser_moments(h, 1);
+  if(rc) return rc;
+  if(input == SSD_INPUT_DEPTH16)
+  {
+    const size_t frameElems = (static_cast<size_t>(h->P.nPoints) + 3) / 4 * 4;       /* as ssd_process_depth_host */
+    rc = process_host_impl(h, frames, static_cast<size_t>(h->P.nPoints) * 2, frameElems * 2, nframes, results, true, nullptr, camOf);
+  }
+  else
+  {
+    const size_t frameBytes = static_cast<size_t>(h->P.nPoints) * 12;
+    rc = process_host_impl(h, frames, frameBytes, frameBytes, nframes, results, false, nullptr, camOf);
+  }
+  if(!rc) rc = ssd_fetch_risers(h, risers, nframes, nullptr);
+  if(!rc) rc = ssd_fetch_riser_moments(h, moments, nframes, nullptr);
+  h->riserMoments = was;                      /* the call has returned its batches: nothing is in flight */
+  if(rc) return rc;
+  for(int i = 0; i < nframes; i++)
+  {
+    const ssd_calibration cal = camOf ? calibration_of(h->camParams[camOf[i]]) : handle_calibration(h);
+    rc = ssd_riser_fit_solve(moments + i, risers + i, &cal, min_points, out + i);
+    if(rc) return rc;
+  }
+  return SSD_OK;
+}
+
+int ssd_process_host_riser_fits(ssd_handle *h, const void *frames, int nframes, int input, ssd_frame_result *results,
+                                ssd_frame_risers *risers, ssd_frame_moments *moments, int min_points, ssd_frame_riser_fits *out)
+{
+  if(!h || !frames || !results || !risers || !out || nframes < 1)
+    return fail(SSD_E_ARG, "ssd_process_host_riser_fits: bad argument");
+  if(input != SSD_INPUT_VERTICES && input != SSD_INPUT_DEPTH16)
+    return fail(SSD_E_ARG, "ssd_process_host_riser_fits: input must be SSD_INPUT_VERTICES or SSD_INPUT_DEPTH16");
+  if(input == SSD_INPUT_DEPTH16 && !h->haveIntr)
+    return fail(SSD_E_ARG, "ssd_process_host_riser_fits: call ssd_set_intrinsics first");
+  return process_host_riser_fits_impl(h, "ssd_process_host_riser_fits", frames, nframes, nullptr, input, results, risers, moments, min_points, out);
+}
+
+int ssd_process_host_cameras_riser_fits(ssd_handle *h, const void *frames, int nframes, const uint16_t *camera_of_frame, int input,
+                                        ssd_frame_result *results, ssd_frame_risers *risers, ssd_frame_moments *moments, int min_points,
+                                        ssd_frame_riser_fits *out)
+{
+  if(!h || !frames || !results || !risers || !out || nframes < 1)
+    return fail(SSD_E_ARG, "ssd_process_host_cameras_riser_fits: bad argument");
+  const int rc = check_cameras(h, "ssd_process_host_cameras_riser_fits", camera_of_frame, nframes, input);
+  if(rc) return rc;
+  return process_host_riser_fits_impl(h, "ssd_process_host_cameras_riser_fits", frames, nframes, camera_of_frame, input, results, risers, moments, min_points, out);
 }
 
 /* host only: no handle, no device */

@@ -94,6 +94,15 @@ struct ssd_handle
   /* risers of a host-fed batch, slice by slice (the device buffer holds one enqueue's) */
   ssd_frame_risers *hRisersBatch = nullptr; /* pinned */
   int hRisersBatchCap = 0, hRisersBatchFrames = 0;
+  /* riser moments (ssd_set_riser_moments): made on the first enable, so a handle that never asks holds none of
+   * them.  Single like the riser buffer (enqueues with risers on all run in the first workspace); a host-fed batch collects them slice
+   * by slice as hRisersBatch does */
+  bool riserMoments = false;
+  ssd_frame_moments *dRiserMoments = nullptr;     /* F records */
+  ssd_frame_moments *hRiserMoments = nullptr;     /* pinned */
+  ssd_frame_moments *hRiserMomentsBatch = nullptr;   /* pinned */
+  int hRiserMomentsBatchCap = 0, hRiserMomentsBatchFrames = 0;
+  int riserMomentsFrames = 0;               /* frames whose riser moments the last enqueue gathered (0: none) */
   ssd::DebugFrame *dDebug = nullptr;
   unsigned long long *dDebugImg = nullptr;
   int debug = 0;                  /* 0 off, 1 records + images (the whole ground image is rastered for it), 2 records only */

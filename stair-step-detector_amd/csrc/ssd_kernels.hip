@@ -4428,6 +4428,185 @@ SSD_ENTRY(__launch_bounds__(kThreads, 8), k_risers, risers_block)(const float *_
   }
 }
 
+/* k_risers' sibling (the riser fit): the same cells, the same evidence rule in the same arithmetic, walked ONCE,
+ * and beside the count and the offset sum of every riser the ten integer sums of ssd_ground_moments (ssd_moments.h) over its evidence
+ * points plus n_far, the evidence points the fixed-point rule leaves out - riser i's in record s[i] of the frame's ssd_frame_moments.
+ * Accumulation is k_surface_moments': a lane keeps the sums of ONE riser in registers, the wave's current one (wave-uniform); when no
+ * lane of a point slot holds the current riser and some hold another, the wave's sums go to the block's LDS table (shuffles, then 64-bit
+ * LDS adds by lane 0) and the wave changes over; the lanes of a mixed slot that hold another riser than the current one add their point
+ * to the table directly.  At the block's end one 64-bit atomicAdd per non-zero entry goes to the frame's record, which the caller zeroed
+ * on the stream, and to k_risers' own rSum / rCnt (the count is n + n_far).  Integer addition throughout: no result depends on an
+ * order, and rSum / rCnt are what k_risers leaves.  A body of its own rather than a switch in risers_block, so that k_risers' code
+ * object stays what it is.  Camera batches: k_riser_moments_cams (ssd_kernels_cams.hip) runs this body with the frame's own constants. */
+constexpr int kRiserSums = kSurfaceSums + 1;        /* the eleven int64 of ssd_surface_moments, then the offset sum (2^-40 m) */
+constexpr int kRiserOffsetSum = kSurfaceSums;
+static_assert(kMaxRisers <= SSD_MAX_STEPS, "riser i's sums are record s[i] of an ssd_frame_moments");
+static_assert(kMaxRisers * kRiserSums <= kThreads, "one thread per entry of the block's table");
+
+struct RiserMomentsLds
+{
+  unsigned short cellList[kMaxCellsPerBlock];
+  unsigned int listScratch[2 * kWavesPerBlock];
+  RiserState rs[kMaxRisers];
+  signed char riserOfBin[kMaxBins];
+  unsigned long long sums[kMaxRisers][kRiserSums];
+};
+
+/* the wave's sums of riser `riser` into the block's table (surface_flush with one more sum) */
+__device__ __forceinline__ void riser_flush(long long (&acc)[kRiserSums], unsigned long long (*sums)[kRiserSums], int riser, int lane)
+{
+#pragma unroll
+  for(int i = 0; i < kRiserSums; i++)
+  {
+#pragma unroll
+    for(int o = 32; o >= 1; o >>= 1)
+      acc[i] += __shfl_xor(acc[i], o);
+  }
+  if(lane == 0)
+  {
+#pragma unroll
+    for(int i = 0; i < kRiserSums; i++)
+      if(acc[i] != 0)
+        atomicAdd(&sums[riser][i], static_cast<unsigned long long>(acc[i]));
+  }
+#pragma unroll
+  for(int i = 0; i < kRiserSums; i++)
+    acc[i] = 0;
+}
+
+template<int SRC>
+SSD_ENTRY(__launch_bounds__(kThreads), k_riser_moments, riser_moments_block)(const float *__restrict__ xyz, size_t strideFloats, SSD_BYVAL(PointParams) P, double tol,
+                                                        FrameState *__restrict__ st, const uint2 *__restrict__ tileMasks,
+                                                        size_t tileMaskStride, int chunkPoints, int cellCols, SSD_BYVAL(DepthSrc) D,
+                                                        ssd_frame_moments *__restrict__ out)
+{
+  __shared__ RiserMomentsLds S;
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int frame = blockIdx.x;
+  FrameState &fs = st[frame];
+  const int nR = min(fs.nRisers, kMaxRisers);
+  /* the record's header, by the frame's first block (also of a frame none of whose cells holds a riser's bin) */
+  if(blockIdx.y == 0 && tid == 0)
+  {
+    out[frame].n_surfaces = nR;
+    out[frame].ground = 0;
+  }
+  const unsigned int wanted = fs.wantedRisers;
+  if(wanted == 0u)                                          /* block-uniform: set by k_final */
+    return;
+  if(tid < kMaxBins)
+    S.riserOfBin[tid] = fs.riserOfBin[tid];
+  if(tid < nR)
+    S.rs[tid] = fs.riser[tid];
+  if(tid < kMaxRisers * kRiserSums)
+    (&S.sums[0][0])[tid] = 0ull;
+  __syncthreads();
+
+  const float *base = SRC == kSrcDepth16
+    ? reinterpret_cast<const float *>(reinterpret_cast<const unsigned short *>(xyz) + static_cast<size_t>(frame) * strideFloats)
+    : xyz + static_cast<size_t>(frame) * strideFloats;
+  const int begin = blockIdx.y * chunkPoints;
+  const int end = min(begin + chunkPoints, P.nPoints);
+
+  /* only the cells that hold a bin of a riser are walked (as k_risers) */
+  const int cell0 = begin / kCell;
+  const int nCells = (end - begin + kCell - 1) / kCell;
+  const int count = cell_list_build(tileMasks + static_cast<size_t>(frame) * tileMaskStride + cell0, nCells, cellCols,
+                                    [&](const uint2 info) { return (info.x & wanted) != 0u; }, S.cellList, S.listScratch);
+  const int nGroups = (count + 3) >> 2;
+  const int gEnd = ((tid >> 6) + 1) * nGroups / kWavesPerBlock;
+  long long acc[kRiserSums] = {};
+  int cur = -1;                                  /* the riser whose sums the wave's registers hold (-1: none yet) */
+  for(int g = (tid >> 6) * nGroups / kWavesPerBlock; g < gEnd; g++)
+  {
+    F3 v[kPts];
+    load_cell<SRC>(base, cell0, S.cellList, 4 * g + (lane >> 4), count, lane, P.nPoints, v, D);
+#pragma unroll
+    for(int j = 0; j < kPts; j++)
+    {
+      /* k_risers' evidence rule, expression for expression; r = the point's riser, -1: no evidence */
+      int r = -1;
+      long long sdFix = 0;
+      double wx, wy, wz;
+      if(world_z(P, v[j], wz))
+      {
+        const int rb = S.riserOfBin[height_bin(P, wz)];
+        if(rb >= 0)
+        {
+          const RiserState &R = S.rs[rb];
+          if(wz > R.zLo && wz < R.zHi && world_xy(P, v[j], wx, wy))
+          {
+            const double a = wx - R.ox, b = wy - R.oy;
+            const double sd = b * R.ux - a * R.uy;                 /* signed distance from the edge line */
+            const double t = a * R.ux + b * R.uy;                  /* position along the edge */
+            if(fabs(sd) <= tol && t >= 0.0 && t <= R.len)
+            {
+              r = rb;
+              sdFix = z_to_fixed(sd);
+            }
+          }
+        }
+      }
+      const unsigned long long mEv = __ballot(r >= 0);
+      if(mEv == 0ull)                            /* wave-uniform: a slot none of whose points is evidence */
+        continue;
+      if(cur < 0 || __ballot(r == cur) == 0ull)
+      {
+        if(cur >= 0)
+          riser_flush(acc, S.sums, cur, lane);
+        cur = __builtin_amdgcn_readlane(r, __ffsll(static_cast<long long>(mEv)) - 1);
+      }
+      /* the fixed-point rule (ssd_moments.h) on the float camera coordinates */
+      const double rx = moment_round(static_cast<double>(v[j].x)), ry = moment_round(static_cast<double>(v[j].y)), rz = moment_round(static_cast<double>(v[j].z));
+      const bool fits = moment_near(rx) && moment_near(ry) && moment_near(rz);
+      if(r == cur)
+      {
+        if(fits)
+          moment_add(rx, ry, rz, acc);
+        else
+          acc[kGroundSums] += 1;
+        acc[kRiserOffsetSum] += sdFix;
+      }
+      else if(r >= 0)
+      {
+        /* another riser than the wave's current one in the same slot (a cell two risers share): rare, straight to the table */
+        unsigned long long *t = S.sums[r];
+        if(fits)
+        {
+          long long one[kGroundSums] = {};
+          moment_add(rx, ry, rz, one);
+#pragma unroll
+          for(int i = 0; i < kGroundSums; i++)
+            atomicAdd(&t[i], static_cast<unsigned long long>(one[i]));
+        }
+        else
+          atomicAdd(&t[kGroundSums], 1ull);
+        atomicAdd(&t[kRiserOffsetSum], static_cast<unsigned long long>(sdFix));
+      }
+    }
+  }
+  if(cur >= 0)
+    riser_flush(acc, S.sums, cur, lane);
+  __syncthreads();
+  if(tid < kMaxRisers * kRiserSums)
+  {
+    const int r = tid / kRiserSums, i = tid - r * kRiserSums;
+    const unsigned long long t = S.sums[r][i];
+    if(t != 0ull && r < nR)
+    {
+      if(i == kRiserOffsetSum)
+        atomicAdd(reinterpret_cast<unsigned long long *>(&fs.rSum[r]), t);
+      else
+      {
+        atomicAdd(reinterpret_cast<unsigned long long *>(out + frame) + 1 + r * kSurfaceSums + i, t);
+        if(i == 0 || i == kGroundSums)             /* every evidence point is in n or in n_far */
+          atomicAdd(&fs.rCnt[r], static_cast<unsigned int>(t));
+      }
+    }
+  }
+}
+
 /* one thread per frame: the riser records in external world coordinates (ToExternalWorld as in k_final) */
 SSD_ENTRY(, k_riser_results, riser_results_block)(SSD_BYVAL(Params) P, const FrameState *__restrict__ st, ssd_frame_risers *__restrict__ out, int nframes)
 {
@@ -4649,6 +4828,18 @@ void launch_risers(const float *xyz, size_t strideFloats, const Params &P, Frame
   with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &D)
   {
     hipLaunchKernelGGL(k_risers<decltype(src)::value>, grid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.riserTol, st, tileMasks, tileMaskStride, chunkPoints, P.px.cellCols, D);
+  });
+  hipLaunchKernelGGL(k_riser_results, dim3((nframes + 63) / 64), dim3(64), 0, s, P, st, out, nframes);
+}
+void launch_riser_moments(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, const uint2 *tileMasks, size_t tileMaskStride,
+                          ssd_frame_risers *out, ssd_frame_moments *moments, int nframes, int chunkPoints, const DepthSrc *depth, hipStream_t s, const CameraSel *cams)
+{
+  if(cams)
+    return launch_riser_moments_cams(xyz, strideFloats, P, st, tileMasks, tileMaskStride, out, moments, nframes, chunkPoints, depth, s, *cams);
+  dim3 grid(nframes, chunks_for(P.nPoints, chunkPoints));
+  with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &D)
+  {
+    hipLaunchKernelGGL(k_riser_moments<decltype(src)::value>, grid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.riserTol, st, tileMasks, tileMaskStride, chunkPoints, P.px.cellCols, D, moments);
   });
   hipLaunchKernelGGL(k_riser_results, dim3((nframes + 63) / 64), dim3(64), 0, s, P, st, out, nframes);
 }

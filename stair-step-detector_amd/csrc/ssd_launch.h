@@ -55,6 +55,10 @@ void launch_labels(const float *xyz, size_t strideFloats, const Params &P, const
                    int nframes, int chunkPoints, const DepthSrc *depth, unsigned char *labels, size_t labelStride, hipStream_t s, const CameraSel *cams = nullptr);
 void launch_risers(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, const uint2 *tileMasks, size_t tileMaskStride,
                    ssd_frame_risers *out, int nframes, int chunkPoints, const DepthSrc *depth, hipStream_t s, const CameraSel *cams = nullptr);
+/* launch_risers with the riser fit's moments (k_riser_moments in place of k_risers: one walk, both results): frame i's record at
+ * moments + i, zeroed by the caller on the stream in front of the launch */
+void launch_riser_moments(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, const uint2 *tileMasks, size_t tileMaskStride,
+                          ssd_frame_risers *out, ssd_frame_moments *moments, int nframes, int chunkPoints, const DepthSrc *depth, hipStream_t s, const CameraSel *cams = nullptr);
 
 /* the launchers of the cameras entry points (ssd_kernels_cams.hip): what launch_*(..., cams) hands a cameras batch to */
 void launch_predict_cams(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, int nframes, const DepthSrc *depth, int *fallback, int poolPlanes, int sabotage, hipStream_t s, const CameraSel &cams);
@@ -68,6 +72,7 @@ void launch_final_cams(const Params &P, FrameState *st, unsigned long long *grou
 void launch_labels_cams(const float *xyz, size_t strideFloats, const Params &P, const FrameState *st, const uint2 *tileMasks, size_t tileMaskStride, int nframes, int chunkPoints, const DepthSrc *depth, unsigned char *labels, size_t labelStride, hipStream_t s, const CameraSel &cams);
 void launch_surface_moments_cams(const float *xyz, size_t strideFloats, const Params &P, const FrameState *st, const uint2 *tileMasks, size_t tileMaskStride, int nframes, int chunkPoints, const DepthSrc *depth, ssd_frame_moments *out, hipStream_t s, const CameraSel &cams);
 void launch_risers_cams(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, const uint2 *tileMasks, size_t tileMaskStride, ssd_frame_risers *out, int nframes, int chunkPoints, const DepthSrc *depth, hipStream_t s, const CameraSel &cams);
+void launch_riser_moments_cams(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, const uint2 *tileMasks, size_t tileMaskStride, ssd_frame_risers *out, ssd_frame_moments *moments, int nframes, int chunkPoints, const DepthSrc *depth, hipStream_t s, const CameraSel &cams);
 }
 
 #endif /* SSD_LAUNCH_H_ */
