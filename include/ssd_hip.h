@@ -570,6 +570,80 @@ int ssd_process_host_cameras_riser_fits(ssd_handle *h, const void *frames, int n
                                         ssd_frame_result *results, ssd_frame_risers *risers, ssd_frame_moments *moments /* may be NULL */,
                                         int min_points, ssd_frame_riser_fits *out);
 
+/* ---- trimmed surface refit: the moments of the points near each fitted plane ------------------------------------------------------
+ * EXTENSION.  A surface's points are a band of height bins inside its quadrilateral; where the band reaches a
+ * riser's foot or a tread's rim those points tilt the fitted plane: the surface fit's error is bias, not noise.  The remedy is a
+ * trimmed refit: the moments gathered again over the SAME labelled points, keeping only those within a gate of the plane the fit
+ * before found.  A gate is a plane in float camera coordinates and a half-width; a frame has one per surface.
+ * Refit moments of surface k of a frame: the ten sums of ssd_ground_moments and n_far, by the fixed-point rule of the surface fit
+ * exactly as it stands, over the points that would carry label k + 1 AND satisfy
+ *     fabs(((n[0] * x + n[1] * y) + n[2] * z) - dist) <= gate
+ * with x, y, z the point's float camera coordinates widened to double, the products and sums in that order, no FMA.  A surface whose
+ * gate is not a finite number above 0, or at k >= the gates' n_surfaces, gathers nothing (a NaN in its plane: likewise, no point
+ * passes).  n_far counts the labelled points INSIDE the gate that the fixed-point rule leaves out; a point trimmed by the gate is
+ * counted nowhere, so m.n + n_far is the points kept.  The record's header (n_surfaces, ground) is the first pass's; records at
+ * k >= n_surfaces are zero; a frame with SSD_ST_THROW or n_steps == 0 is all zero.  All sums are exact integers: the device and
+ * ssd_surface_refit_moments_host agree bit for bit, and a refit record goes wherever a first-pass record goes - ssd_surface_fit_solve,
+ * ssd_ground_fit_solve on surface 0, ssd_camera_drift_fold - unchanged.
+ * Out of scope: camera batches, the riser fit, ssd_pipeline_*, a solve on the device, and a gate that reaches points outside the
+ * labelled set (the bias of a band cut askew by a wrong calibration is only partly answered). */
+typedef struct
+{
+  double n[3];        /* the plane's normal, camera coordinates (unit when made by ssd_surface_gates_from_moments) */
+  double dist;        /* n . p of the plane's points */
+  double gate;        /* half-width: a point is kept iff |n . p - dist| <= gate; not a finite number above 0: nothing is kept */
+} ssd_plane_gate;     /* camera coordinates */
+
+typedef struct
+{
+  int32_t n_surfaces, reserved;
+  ssd_plane_gate g[SSD_MAX_STEPS];
+} ssd_frame_gates;
+
+/* host only, no GPU needed: a frame's moments -> a gate per surface, through the solve the fits share (plane_of_moments): n = n0
+ * (unit, away from the camera), dist = n0 . centroid, gate = max(k_sigma * rms, gate_min), rms = sqrt(lambda_min).  A surface whose
+ * status is not SSD_GF_OK (FEW by min_points, DEGENERATE) gets an all-zero gate and so gathers nothing; gates at k >= n_surfaces are
+ * zero.  A perfectly flat surface (rms 0) with gate_min 0 also gets gate 0: give a gate_min of a few fixed-point steps (2^-16 m) to keep
+ * it.  SSD_E_ARG: a null pointer, n_surfaces outside 0 .. SSD_MAX_STEPS, k_sigma not in (0, 16], gate_min not in [0, 1]. */
+int ssd_surface_gates_from_moments(const ssd_frame_moments *m, int min_points, double k_sigma, double gate_min, ssd_frame_gates *out);
+/* host only, no GPU needed: ssd_surface_moments_host with the gate (one walk, shared: the arguments, the deprojection and the
+ * fixed-point rule are that function's); gates: one frame's, SSD_E_ARG when null */
+int ssd_surface_refit_moments_host(const ssd_config *cfg, int input, const ssd_intrinsics *intr, const void *frame, const uint8_t *labels,
+                                   const ssd_frame_gates *gates, int n_surfaces, int ground, ssd_frame_moments *out);
+/* The refit pass alone (k_surface_refit), against the workspace of the handle's last WHOLE enqueue - whichever of ssd_enqueue,
+ * ssd_enqueue_depth or their _surface_moments / _labels forms ran last - behind it on that batch's stream and in front of a completion
+ * event of its own: frame i's record at d_out + i (device memory, nframes contiguous records), zeroed on the stream in front of the
+ * pass.  d_frames, frame_stride_bytes, nframes and input (SSD_INPUT_VERTICES / SSD_INPUT_DEPTH16) must be that enqueue's, and the
+ * frames must still be untouched: the pass reads the cell records and quadrilaterals the enqueue left and the points again.  gates:
+ * HOST memory, nframes records, copied during the call.  It may be repeated (each pass gated by the planes of the one before) until
+ * the next enqueue takes the workspace; a later enqueue on any stream is ordered behind it.  It leaves results, result slots, risers
+ * and debug records, and everything ssd_fetch* reads, untouched.  The device gates are one set per handle: refit passes run in the
+ * order of their calls, each behind the one before, also where they follow batches of different workspaces (enqueue A, refit A,
+ * enqueue B, refit B without a fetch between is fine; refit B starts when refit A has ended).  ssd_set_intrinsics between an enqueue
+ * and its refit withdraws the enqueue (the pass would deproject with other maps): the refit is then refused.
+ * SSD_E_ARG, before anything is launched or copied: no such enqueue (none yet, or the last one was a partial ssd_enqueue_stages run or
+ * a cameras batch), other frames, stride, nframes or input than it had, a null pointer, depth input without intrinsics.
+ * The pinned and device gate buffers (one ssd_frame_gates per frame of max_frames_per_batch each) are made on the first call and
+ * counted in ssd_workspace_bytes from then on; a handle that never refits allocates and launches nothing more. */
+int ssd_enqueue_surface_refit(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream,
+                              int input, const ssd_frame_gates *gates /* HOST, nframes, copied during the call */,
+                              ssd_frame_moments *d_out);
+/* waits for the last ssd_enqueue_surface_refit (SSD_E_ARG: there was none) and, as passes run in the order of their calls, for every
+ * one before it: the records of all refit calls so far are complete when it returns */
+int ssd_fetch_surface_refit(ssd_handle *h, void *stream);
+/* the device time of the last refit pass, the memset in front of it included (0 when timing was off for it); enable timing before */
+int ssd_get_surface_refit_time(ssd_handle *h, float *ms);
+/* frames in host memory (input as ssd_process_host_surfaces), in the slices of ssd_process_host.  Per slice, while it is still in
+ * its staging buffer: detection and the first moments, fetch, gates on the host (ssd_surface_gates_from_moments with min_points,
+ * k_sigma, gate_min), the refit pass, fetch - the last three `passes` times (1 .. 4), each pass gated by the planes of the one
+ * before.  So a slice is FINISHED before the next one's kernels go out (only its copy overlaps the slice before): the gates need the
+ * host between the passes.  Fills results[nframes] (byte for byte ssd_process_host's), out[nframes] (ssd_surface_fit_solve of the last
+ * pass against the handle's calibration) and, when not NULL, first[nframes] (the first pass's records) and refit[nframes] (the last
+ * pass's).  SSD_E_ARG before anything is copied: a null pointer, passes outside 1 .. 4, what ssd_surface_gates_from_moments refuses. */
+int ssd_process_host_surfaces_refit(ssd_handle *h, const void *frames, int nframes, int input, ssd_frame_result *results,
+                                    ssd_frame_moments *first /* may be NULL */, ssd_frame_moments *refit /* may be NULL */,
+                                    int min_points, double k_sigma, double gate_min, int passes /* 1..4 */, ssd_frame_surfaces *out);
+
 /* stage selector for profiling / roofline measurement: runs only the chosen stage(s) of the pipeline */
 #define SSD_STAGE_HIST 1       /* K1: transform + crop + bin + histogram */
 #define SSD_STAGE_PEAKS 2

@@ -165,6 +165,17 @@ class FrameSurfaces(C.Structure):
     _fields_ = [("n_surfaces", C.c_int32), ("ground", C.c_int32), ("s", SurfaceFit * MAX_STEPS)]
 
 
+class PlaneGate(C.Structure):
+    """ssd_plane_gate: a plane in camera coordinates and a half-width; a point is kept iff |n . p - dist| <= gate (trimmed surface
+    refit)"""
+    _fields_ = [("n", C.c_double * 3), ("dist", C.c_double), ("gate", C.c_double)]
+
+
+class FrameGates(C.Structure):
+    """ssd_frame_gates: a frame's gates, one per surface (the order of its FrameMoments)"""
+    _fields_ = [("n_surfaces", C.c_int32), ("reserved", C.c_int32), ("g", PlaneGate * MAX_STEPS)]
+
+
 MAX_RISERS = MAX_STEPS - 1
 
 
@@ -223,6 +234,8 @@ EXPORTS = [
     "ssd_enqueue_cameras_surface_moments", "ssd_process_host_cameras_surfaces", "ssd_camera_drift_fold",
     "ssd_set_riser_moments", "ssd_fetch_riser_moments", "ssd_riser_fit_solve", "ssd_process_host_riser_fits",
     "ssd_process_host_cameras_riser_fits",
+    "ssd_surface_gates_from_moments", "ssd_surface_refit_moments_host", "ssd_enqueue_surface_refit", "ssd_fetch_surface_refit",
+    "ssd_get_surface_refit_time", "ssd_process_host_surfaces_refit",
 ]
 # libssd_source.so — the frame source standing in for the camera (include/ssd_source.h)
 SOURCE_EXPORTS = [
@@ -305,6 +318,14 @@ def lib():
     L.ssd_process_host_cameras_surfaces.argtypes = [vp, vp, i32, C.POINTER(C.c_uint16), i32, C.POINTER(FrameResult), C.POINTER(FrameMoments), i32,
                                                     C.POINTER(FrameSurfaces)]
     L.ssd_camera_drift_fold.argtypes = [C.POINTER(FrameMoments), C.POINTER(C.c_uint16), i32, C.POINTER(Camera), i32, i32, C.POINTER(CameraDrift)]
+    L.ssd_surface_gates_from_moments.argtypes = [C.POINTER(FrameMoments), i32, C.c_double, C.c_double, C.POINTER(FrameGates)]
+    L.ssd_surface_refit_moments_host.argtypes = [C.POINTER(Config), i32, C.POINTER(Intrinsics), vp, vp, C.POINTER(FrameGates), i32, i32,
+                                                 C.POINTER(FrameMoments)]
+    L.ssd_enqueue_surface_refit.argtypes = [vp, vp, sz, i32, vp, i32, C.POINTER(FrameGates), vp]
+    L.ssd_fetch_surface_refit.argtypes = [vp, vp]
+    L.ssd_get_surface_refit_time.argtypes = [vp, C.POINTER(C.c_float)]
+    L.ssd_process_host_surfaces_refit.argtypes = [vp, vp, i32, i32, C.POINTER(FrameResult), C.POINTER(FrameMoments), C.POINTER(FrameMoments), i32,
+                                                  C.c_double, C.c_double, i32, C.POINTER(FrameSurfaces)]
     L.ssd_set_riser_moments.argtypes = [vp, i32]
     L.ssd_fetch_riser_moments.argtypes = [vp, C.POINTER(FrameMoments), i32, vp]
     L.ssd_riser_fit_solve.argtypes = [C.POINTER(FrameMoments), C.POINTER(FrameRisers), C.POINTER(Calibration), i32, C.POINTER(FrameRiserFits)]
@@ -537,6 +558,29 @@ def surface_fit_solve(moments, cal, min_points=200):
     c = cal.constants if isinstance(cal, GeometricTransformation) else cal.cal if isinstance(cal, Camera) else cal
     out = FrameSurfaces()
     _check(lib().ssd_surface_fit_solve(C.byref(moments), C.byref(c), int(min_points), C.byref(out)))
+    return out
+
+
+def surface_gates_from_moments(moments, min_points=200, k_sigma=2.5, gate_min=0.0):
+    """ssd_surface_gates_from_moments: a frame's moments -> a gate per surface (FrameGates): the fitted plane in camera coordinates
+    and max(k_sigma * rms, gate_min); gate 0 for a surface whose fit is not GF_OK"""
+    out = FrameGates()
+    _check(lib().ssd_surface_gates_from_moments(C.byref(moments) if moments is not None else None, int(min_points), float(k_sigma),
+                                                float(gate_min), C.byref(out)))
+    return out
+
+
+def surface_refit_moments_host(cfg, frame, labels, gates, n_surfaces, ground, intr=None):
+    """ssd_surface_refit_moments_host: surface_moments_host over the labelled points inside their surface's gate -> FrameMoments"""
+    depth = intr is not None
+    a = np.ascontiguousarray(frame, dtype=np.uint16 if depth else np.float32)
+    lab = np.ascontiguousarray(labels, dtype=np.uint8)
+    if a.size != cfg.width * cfg.height * (1 if depth else 3) or lab.size != cfg.width * cfg.height:
+        raise SsdError("surface_refit_moments_host: the arrays are not one frame")
+    out = FrameMoments()
+    _check(lib().ssd_surface_refit_moments_host(C.byref(cfg), INPUT_DEPTH16 if depth else INPUT_VERTICES, C.byref(intr) if depth else None,
+                                                a.ctypes.data_as(C.c_void_p), lab.ctypes.data_as(C.c_void_p),
+                                                C.byref(gates) if gates is not None else None, int(n_surfaces), int(ground), C.byref(out)))
     return out
 
 
@@ -839,6 +883,45 @@ class Detector:
         _check(lib().ssd_process_host_surfaces(self._h, a.ctypes.data_as(C.c_void_p), n, INPUT_DEPTH16 if depth else INPUT_VERTICES, res,
                                                mom if moments else None, int(min_points), out))
         return (list(res), list(out), list(mom)) if moments else (list(res), list(out))
+
+    # ---- trimmed surface refit (include/ssd_hip.h)
+    def enqueue_surface_refit(self, d_ptr, nframes, gates, d_moments, depth=False, stride_bytes=None, stream=None):
+        """ssd_enqueue_surface_refit: the refit pass alone, behind the handle's last whole enqueue of the same frames: frame i's
+        FrameMoments over the labelled points inside gates[i] (FrameGates per frame, host) at d_moments + i * sizeof(FrameMoments) in
+        device memory; complete when fetch_surface_refit() returns"""
+        frame = self.cfg.width * self.cfg.height * (2 if depth else 12)
+        arr = None
+        if gates is not None:
+            arr = gates if isinstance(gates, C.Array) and gates._type_ is FrameGates else (FrameGates * max(1, len(gates)))(*gates)
+            if len(arr) < nframes:
+                raise SsdError("enqueue_surface_refit: fewer gates than frames")
+        _check(lib().ssd_enqueue_surface_refit(self._h, C.c_void_p(d_ptr), stride_bytes or frame, nframes, C.c_void_p(stream or 0),
+                                               INPUT_DEPTH16 if depth else INPUT_VERTICES, arr, C.c_void_p(d_moments)))
+
+    def fetch_surface_refit(self, stream=None):
+        """ssd_fetch_surface_refit: waits for the last enqueue_surface_refit"""
+        _check(lib().ssd_fetch_surface_refit(self._h, C.c_void_p(stream or 0)))
+
+    def surface_refit_time_ms(self):
+        """Device time of the last refit pass (0.0: timing was off for it)"""
+        ms = C.c_float(0.0)
+        _check(lib().ssd_get_surface_refit_time(self._h, C.byref(ms)))
+        return ms.value
+
+    def process_host_surfaces_refit(self, frames, depth=False, min_points=200, k_sigma=2.5, gate_min=0.0, passes=1, moments=False):
+        """ssd_process_host_surfaces_refit: frames on the host (float32 [n, H, W, 3], or uint16 [n, H, W] with depth=True)
+        -> (list of FrameResult, list of FrameSurfaces of the last refit pass), with moments=True also the lists of FrameMoments of
+        the first pass and of the last refit pass"""
+        a = np.ascontiguousarray(frames, dtype=np.uint16 if depth else np.float32)
+        per = self.cfg.width * self.cfg.height * (1 if depth else 3)
+        n = a.size // per
+        if n < 1 or a.size != n * per:
+            raise SsdError("process_host_surfaces_refit: array does not hold whole frames")
+        res, first, refit, out = (FrameResult * n)(), (FrameMoments * n)(), (FrameMoments * n)(), (FrameSurfaces * n)()
+        _check(lib().ssd_process_host_surfaces_refit(self._h, a.ctypes.data_as(C.c_void_p), n, INPUT_DEPTH16 if depth else INPUT_VERTICES, res,
+                                                     first if moments else None, refit if moments else None, int(min_points),
+                                                     float(k_sigma), float(gate_min), int(passes), out))
+        return (list(res), list(out), list(first), list(refit)) if moments else (list(res), list(out))
 
     # ---- surface fit of cameras batches, drift per camera (include/ssd_hip.h, DESIGN.md section 7e)
     def enqueue_cameras_surface_moments(self, d_ptr, nframes, camera_of_frame, d_moments, depth=False, stride_bytes=None, stream=None):

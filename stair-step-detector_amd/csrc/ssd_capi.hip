@@ -9,6 +9,7 @@
 #include "ssd_handle.h"
 #include "ssd_prexy.h"
 #include "ssd_ground.h"
+#include "ssd_refit.h"
 
 #include <algorithm>
 #include <charconv>
@@ -594,6 +595,12 @@ int ssd_destroy(ssd_handle *h)
   if(h->hGroundPriors) (void)hipHostFree(h->hGroundPriors);
   if(h->groundPriorsCopied) (void)hipEventDestroy(h->groundPriorsCopied);
   if(h->groundDone) (void)hipEventDestroy(h->groundDone);
+  if(h->dRefitGates) (void)hipFree(h->dRefitGates);
+  if(h->hRefitGates) (void)hipHostFree(h->hRefitGates);
+  if(h->refitGatesCopied) (void)hipEventDestroy(h->refitGatesCopied);
+  if(h->refitDone) (void)hipEventDestroy(h->refitDone);
+  for(hipEvent_t e : h->evRefit)
+    if(e) (void)hipEventDestroy(e);
   if(h->hFallback) (void)hipHostFree(h->hFallback);
   if(h->dDepthMaps) (void)hipFree(h->dDepthMaps);
   if(h->dResults) (void)hipFree(h->dResults);
@@ -985,6 +992,7 @@ static int enqueue_impl(ssd_handle *h, const void *d_xyz, size_t frame_stride_by
       return fail(SSD_E_ARG, "ssd_enqueue: frame pointer must be 4-byte aligned");
   }
   HIP_TRY(hipSetDevice(h->device));
+  h->wholeKind = 0;                            /* what a refit may be held to (ssd_enqueue_surface_refit): set again when this call has gone out whole */
   Params P = h->P;
   P.px.groundFull = h->debug == 1 ? 1 : 0;     /* image capture compares the whole ground image; otherwise only what k_final reads is rastered */
   /* Which workspace.  A handle with one runs on the caller's stream (a switch of streams is ordered by the lane's event: the
@@ -1251,6 +1259,13 @@ static int enqueue_impl(ssd_handle *h, const void *d_xyz, size_t frame_stride_by
   h->riserMomentsFrames = riserMoments ? nframes : 0;
   h->hRiserMomentsBatchFrames = 0;
   h->enqueueCount++;
+  if(stages == SSD_STAGE_ALL)
+  {
+    h->wholeKind = camOf ? 2 : 1;
+    h->wholeDepth = depthInput;
+    h->wholeFrames = d_xyz;
+    h->wholeStride = frame_stride_bytes;
+  }
   return SSD_OK;
 }
 
@@ -1335,6 +1350,7 @@ int ssd_set_intrinsics(ssd_handle *h, const ssd_intrinsics *intr)
   HIP_TRY(hipMemcpy(h->dDepthMaps, maps.data(), maps.size() * 4, hipMemcpyHostToDevice));
   h->intr = *intr;
   h->haveIntr = true;
+  h->wholeKind = 0;                            /* a refit would deproject with other maps than the enqueue it follows did */
   return SSD_OK;
 }
 
@@ -2113,23 +2129,25 @@ int ssd_ground_fit_solve(const ssd_ground_moments *m, const ssd_calibration *pri
 
 /* ---- surface fit (include/ssd_hip.h): host side ---------------------------------------------------------- */
 
-int ssd_surface_moments_host(const ssd_config *cfg, int input, const ssd_intrinsics *intr, const void *frame, const uint8_t *labels,
-                             int n_surfaces, int ground, ssd_frame_moments *out)
+/* The walk of ssd_surface_moments_host (gates == nullptr: every labelled point) and of ssd_surface_refit_moments_host (a labelled point
+ * outside its surface's gate is skipped whole: ssd_refit.h) */
+static int surface_moments_walk(const std::string &who, const ssd_config *cfg, int input, const ssd_intrinsics *intr, const void *frame,
+                                const uint8_t *labels, const ssd_frame_gates *gates, int n_surfaces, int ground, ssd_frame_moments *out)
 {
   if(!cfg || !frame || !labels || !out || cfg->width <= 0 || cfg->height <= 0)
-    return fail(SSD_E_ARG, "ssd_surface_moments_host: bad argument");
+    return fail(SSD_E_ARG, who + ": bad argument");
   if(input != SSD_INPUT_VERTICES && input != SSD_INPUT_DEPTH16)
-    return fail(SSD_E_ARG, "ssd_surface_moments_host: input must be SSD_INPUT_VERTICES or SSD_INPUT_DEPTH16");
+    return fail(SSD_E_ARG, who + ": input must be SSD_INPUT_VERTICES or SSD_INPUT_DEPTH16");
   if(n_surfaces < 0 || n_surfaces > SSD_MAX_STEPS)
-    return fail(SSD_E_ARG, "ssd_surface_moments_host: n_surfaces must lie in 0 .. SSD_MAX_STEPS");
+    return fail(SSD_E_ARG, who + ": n_surfaces must lie in 0 .. SSD_MAX_STEPS");
   const bool depth = input == SSD_INPUT_DEPTH16;
   if(depth && (!intr || !good_intrinsics(*intr)))
-    return fail(SSD_E_ARG, "ssd_surface_moments_host: depth input needs intrinsics");
+    return fail(SSD_E_ARG, who + ": depth input needs intrinsics");
   const int W = cfg->width, H = cfg->height;
   const size_t nPoints = static_cast<size_t>(W) * H;
   for(size_t i = 0; i < nPoints; i++)
     if(labels[i] > n_surfaces)
-      return fail(SSD_E_ARG, "ssd_surface_moments_host: a label above n_surfaces");
+      return fail(SSD_E_ARG, who + ": a label above n_surfaces");
   std::vector<float> deprojected;
   const float *xyz = static_cast<const float *>(frame);
   if(depth)
@@ -2145,6 +2163,8 @@ int ssd_surface_moments_host(const ssd_config *cfg, int input, const ssd_intrins
   {
     if(labels[i] == SSD_LABEL_NONE)
       continue;
+    if(gates && !refit_keeps(*gates, labels[i] - 1, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]))
+      continue;
     long long (&a)[kGroundSums + 1] = acc[labels[i] - 1];
     const double rx = moment_round(xyz[3 * i]), ry = moment_round(xyz[3 * i + 1]), rz = moment_round(xyz[3 * i + 2]);
     if(moment_near(rx) && moment_near(ry) && moment_near(rz))
@@ -2157,6 +2177,12 @@ int ssd_surface_moments_host(const ssd_config *cfg, int input, const ssd_intrins
   out->ground = ground ? 1 : 0;
   std::memcpy(out->s, acc, sizeof(acc));
   return SSD_OK;
+}
+
+int ssd_surface_moments_host(const ssd_config *cfg, int input, const ssd_intrinsics *intr, const void *frame, const uint8_t *labels,
+                             int n_surfaces, int ground, ssd_frame_moments *out)
+{
+  return surface_moments_walk("ssd_surface_moments_host", cfg, input, intr, frame, labels, nullptr, n_surfaces, ground, out);
 }
 
 int ssd_surface_fit_solve(const ssd_frame_moments *moments, const ssd_calibration *cal, int min_points, ssd_frame_surfaces *out)
@@ -2251,6 +2277,273 @@ int ssd_process_host_surfaces(ssd_handle *h, const void *frames, int nframes, in
   {
     rc = ssd_surface_fit_solve(moments + i, &cal, min_points, out + i);
     if(rc) return rc;
+  }
+  return SSD_OK;
+}
+
+/* ---- trimmed surface refit (include/ssd_hip.h) ---------------------------------------------------------- */
+
+static int check_gate_rule(const char *who, double k_sigma, double gate_min)
+{
+  if(!(k_sigma > 0.0) || !(k_sigma <= 16.0))
+    return fail(SSD_E_ARG, std::string(who) + ": k_sigma must lie in (0, 16]");
+  if(!(gate_min >= 0.0) || !(gate_min <= 1.0))
+    return fail(SSD_E_ARG, std::string(who) + ": gate_min must lie in [0, 1]");
+  return SSD_OK;
+}
+
+int ssd_surface_gates_from_moments(const ssd_frame_moments *m, int min_points, double k_sigma, double gate_min, ssd_frame_gates *out)
+{
+  if(!m || !out)
+    return fail(SSD_E_ARG, "ssd_surface_gates_from_moments: null");
+  if(m->n_surfaces < 0 || m->n_surfaces > SSD_MAX_STEPS)
+    return fail(SSD_E_ARG, "ssd_surface_gates_from_moments: n_surfaces must lie in 0 .. SSD_MAX_STEPS");
+  const int rc = check_gate_rule("ssd_surface_gates_from_moments", k_sigma, gate_min);
+  if(rc) return rc;
+  std::memset(out, 0, sizeof(*out));
+  out->n_surfaces = m->n_surfaces;
+  for(int k = 0; k < m->n_surfaces; k++)
+  {
+    PlaneOfMoments pl;
+    if(plane_of_moments(&m->s[k].m, min_points, pl) != SSD_GF_OK)
+      continue;                                  /* an all-zero gate: the surface gathers nothing */
+    ssd_plane_gate &g = out->g[k];
+    for(int i = 0; i < 3; i++)
+      g.n[i] = pl.n0[i];
+    g.dist = pl.dist;
+    const double rms = std::sqrt(pl.lambda[0] > 0.0 ? pl.lambda[0] : 0.0), wide = k_sigma * rms;
+    g.gate = wide > gate_min ? wide : gate_min;
+  }
+  return SSD_OK;
+}
+
+int ssd_surface_refit_moments_host(const ssd_config *cfg, int input, const ssd_intrinsics *intr, const void *frame, const uint8_t *labels,
+                                   const ssd_frame_gates *gates, int n_surfaces, int ground, ssd_frame_moments *out)
+{
+  if(!gates)
+    return fail(SSD_E_ARG, "ssd_surface_refit_moments_host: null gates");
+  return surface_moments_walk("ssd_surface_refit_moments_host", cfg, input, intr, frame, labels, gates, n_surfaces, ground, out);
+}
+
+/* the buffers and events of the refit, on its first call */
+static int refit_prepare(ssd_handle *h)
+{
+  if(h->dRefitGates)
+    return SSD_OK;
+  const size_t bytes = sizeof(ssd_frame_gates) * static_cast<size_t>(h->F);
+  hipError_t e = hipMalloc(&h->dRefitGates, bytes);
+  if(e == hipSuccess) e = hipHostMalloc(&h->hRefitGates, bytes, hipHostMallocDefault);
+  if(e == hipSuccess) e = hipEventCreateWithFlags(&h->refitGatesCopied, hipEventDisableTiming);
+  if(e == hipSuccess) e = hipEventCreateWithFlags(&h->refitDone, hipEventDisableTiming);
+  if(e != hipSuccess)
+  {
+    if(h->dRefitGates) (void)hipFree(h->dRefitGates);
+    if(h->hRefitGates) (void)hipHostFree(h->hRefitGates);
+    if(h->refitGatesCopied) (void)hipEventDestroy(h->refitGatesCopied);
+    if(h->refitDone) (void)hipEventDestroy(h->refitDone);
+    h->dRefitGates = nullptr; h->hRefitGates = nullptr; h->refitGatesCopied = nullptr; h->refitDone = nullptr;
+    (void)hipGetLastError();
+    return fail(e == hipErrorOutOfMemory ? SSD_E_NOMEM : SSD_E_HIP, std::string("ssd_enqueue_surface_refit: its buffers: ") + hipGetErrorString(e));
+  }
+  h->refitBytes = 2 * bytes;
+  h->bytes += h->refitBytes;
+  return SSD_OK;
+}
+
+int ssd_enqueue_surface_refit(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream,
+                              int input, const ssd_frame_gates *gates, ssd_frame_moments *d_out)
+{
+  if(!h || !d_frames || !gates || !d_out)
+    return fail(SSD_E_ARG, "ssd_enqueue_surface_refit: null argument");
+  if(input != SSD_INPUT_VERTICES && input != SSD_INPUT_DEPTH16)
+    return fail(SSD_E_ARG, "ssd_enqueue_surface_refit: input must be SSD_INPUT_VERTICES or SSD_INPUT_DEPTH16");
+  const bool depthInput = input == SSD_INPUT_DEPTH16;
+  if(depthInput && !h->haveIntr)
+    return fail(SSD_E_ARG, "ssd_enqueue_surface_refit: depth input: call ssd_set_intrinsics first");
+  if(h->wholeKind == 2)
+    return fail(SSD_E_ARG, "ssd_enqueue_surface_refit: the last enqueue was a cameras batch (no refit for those)");
+  if(h->wholeKind != 1)
+    return fail(SSD_E_ARG, "ssd_enqueue_surface_refit: no whole enqueue to refit (none yet, or the last one was a partial run)");
+  if(nframes != h->lastFrames)
+    return fail(SSD_E_ARG, "ssd_enqueue_surface_refit: nframes is not the last enqueue's");
+  if(depthInput != h->wholeDepth || d_frames != h->wholeFrames || frame_stride_bytes != h->wholeStride)
+    return fail(SSD_E_ARG, "ssd_enqueue_surface_refit: input, frames or stride are not the last enqueue's");
+  ssd_lane &L = h->lane[h->lastLane];
+  if(!L.haveLast || !L.dState || !L.dTileMasks || (depthInput && !h->dDepthMaps))
+    return fail(SSD_E_HIP, "ssd_enqueue_surface_refit: the handle's workspace is incomplete (internal)");
+  HIP_TRY(hipSetDevice(h->device));
+  int rc = refit_prepare(h);
+  if(rc) return rc;
+  const bool timing = h->timing && !h->ev.empty();
+  if(timing && !h->evRefit[0])
+  {
+    HIP_TRY(hipEventCreate(&h->evRefit[0]));
+    HIP_TRY(hipEventCreate(&h->evRefit[1]));
+  }
+  /* behind the batch, on the stream it ran on: the caller's with one workspace (a switch of streams is ordered by the lane's event),
+   * the lane's own with several (behind what the caller's stream holds now, as an enqueue is) */
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if(h->depth == 1)
+  {
+    if(s != L.lastStream)
+      HIP_TRY(hipStreamWaitEvent(s, L.done, 0));
+  }
+  else
+  {
+    HIP_TRY(hipEventRecord(L.in, s));
+    s = L.stream;
+    HIP_TRY(hipStreamWaitEvent(s, L.in, 0));
+  }
+  if(h->refitHaveLast)
+  {
+    HIP_TRY(hipEventSynchronize(h->refitGatesCopied));              /* the pinned gates of the previous call have gone over */
+    /* the device gates are one set: on another stream than the previous pass's (another workspace's, or the caller changed streams) this
+     * call goes behind that pass, which still reads them - so refits run in the order of their calls, whatever workspace they follow */
+    if(s != h->refitLastStream)
+      HIP_TRY(hipStreamWaitEvent(s, h->refitDone, 0));
+  }
+  std::memcpy(h->hRefitGates, gates, sizeof(ssd_frame_gates) * static_cast<size_t>(nframes));
+  HIP_TRY(hipMemcpyAsync(h->dRefitGates, h->hRefitGates, sizeof(ssd_frame_gates) * static_cast<size_t>(nframes), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipEventRecord(h->refitGatesCopied, s));
+  h->refitHaveLast = true;
+  h->refitLastStream = s;
+  const Params &P = h->P;
+  const float *xyz = static_cast<const float *>(d_frames);
+  const size_t strideFloats = depthInput ? frame_stride_bytes / 2 : frame_stride_bytes / 4;
+  const DepthSrc depthSrc{ h->dDepthMaps, h->dDepthMaps ? h->dDepthMaps + P.W : nullptr, h->intr.depth_units, P.W, P.H, depth_row_magic(P.W, P.H) };
+  const int chunk = choose_chunk(h->tune, P.nPoints, nframes);      /* the first pass's */
+  if(timing) HIP_TRY(hipEventRecord(h->evRefit[0], s));
+  HIP_TRY(hipMemsetAsync(d_out, 0, sizeof(ssd_frame_moments) * static_cast<size_t>(nframes), s));
+  launch_surface_refit(xyz, strideFloats, P, L.dState, L.dTileMasks, h->tileMaskStride, nframes, chunk, depthInput ? &depthSrc : nullptr,
+                       h->dRefitGates, d_out, s);
+  HIP_TRY(hipGetLastError());
+  if(timing) HIP_TRY(hipEventRecord(h->evRefit[1], s));
+  h->refitTimed = timing;
+  HIP_TRY(hipEventRecord(h->refitDone, s));
+  /* the workspace is in use until here: whatever takes it next, on whichever stream, goes behind the pass */
+  HIP_TRY(hipEventRecord(L.done, s));
+  L.lastStream = s;
+  return SSD_OK;
+}
+
+int ssd_fetch_surface_refit(ssd_handle *h, void *)
+{
+  if(!h)
+    return fail(SSD_E_ARG, "ssd_fetch_surface_refit: null handle");
+  if(!h->refitHaveLast)
+    return fail(SSD_E_ARG, "ssd_fetch_surface_refit: no ssd_enqueue_surface_refit to wait for");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipEventSynchronize(h->refitDone));
+  return SSD_OK;
+}
+
+int ssd_get_surface_refit_time(ssd_handle *h, float *ms)
+{
+  if(!h || !ms)
+    return fail(SSD_E_ARG, "ssd_get_surface_refit_time: null");
+  if(!h->refitHaveLast)
+    return fail(SSD_E_ARG, "ssd_get_surface_refit_time: no ssd_enqueue_surface_refit yet");
+  *ms = 0.0f;
+  if(!h->refitTimed)
+    return SSD_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipEventSynchronize(h->evRefit[1]));
+  HIP_TRY(hipEventElapsedTime(ms, h->evRefit[0], h->evRefit[1]));
+  return SSD_OK;
+}
+
+int ssd_process_host_surfaces_refit(ssd_handle *h, const void *frames, int nframes, int input, ssd_frame_result *results,
+                                    ssd_frame_moments *first, ssd_frame_moments *refit, int min_points, double k_sigma, double gate_min,
+                                    int passes, ssd_frame_surfaces *out)
+{
+  if(!h || !frames || !results || !out || nframes < 1)
+    return fail(SSD_E_ARG, "ssd_process_host_surfaces_refit: bad argument");
+  if(input != SSD_INPUT_VERTICES && input != SSD_INPUT_DEPTH16)
+    return fail(SSD_E_ARG, "ssd_process_host_surfaces_refit: input must be SSD_INPUT_VERTICES or SSD_INPUT_DEPTH16");
+  if(input == SSD_INPUT_DEPTH16 && !h->haveIntr)
+    return fail(SSD_E_ARG, "ssd_process_host_surfaces_refit: call ssd_set_intrinsics first");
+  if(passes < 1 || passes > 4)
+    return fail(SSD_E_ARG, "ssd_process_host_surfaces_refit: passes must lie in 1 .. 4");
+  int rc = check_gate_rule("ssd_process_host_surfaces_refit", k_sigma, gate_min);
+  if(rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const bool depth = input == SSD_INPUT_DEPTH16;
+  /* the slices and the device layout of ssd_process_host / ssd_process_depth_host */
+  const size_t srcFrameBytes = static_cast<size_t>(h->P.nPoints) * (depth ? 2 : 12);
+  const size_t devFrameBytes = depth ? (static_cast<size_t>(h->P.nPoints) + 3) / 4 * 4 * 2 : srcFrameBytes;
+  const int slice = h->F < kIngestFrames ? h->F : kIngestFrames;
+  rc = ingest_prepare(h, static_cast<size_t>(slice) * devFrameBytes);
+  if(rc) return rc;
+  /* the records of a slice on the device: the first pass's in the first label staging buffer, a refit pass's in the second */
+  rc = labels_prepare(h, static_cast<size_t>(slice) * sizeof(ssd_frame_moments));
+  if(rc) return rc;
+  ssd_frame_moments *dFirst = reinterpret_cast<ssd_frame_moments *>(h->labelStage[0]), *dRefit = reinterpret_cast<ssd_frame_moments *>(h->labelStage[1]);
+  std::vector<ssd_frame_moments> cur(static_cast<size_t>(slice));
+  std::vector<ssd_frame_gates> gates(static_cast<size_t>(slice));
+  const ssd_calibration cal = handle_calibration(h);
+  const unsigned char *from = static_cast<const unsigned char *>(frames);
+  auto copyIn = [&](int k, int at, int n)
+  {
+    if(srcFrameBytes == devFrameBytes)
+      HIP_TRY(hipMemcpyAsync(h->ingestBuf[k], from + static_cast<size_t>(at) * srcFrameBytes, static_cast<size_t>(n) * srcFrameBytes, hipMemcpyHostToDevice, h->ingestCopy));
+    else
+      HIP_TRY(hipMemcpy2DAsync(h->ingestBuf[k], devFrameBytes, from + static_cast<size_t>(at) * srcFrameBytes, srcFrameBytes, srcFrameBytes, n,
+                               hipMemcpyHostToDevice, h->ingestCopy));
+    HIP_TRY(hipEventRecord(h->ingestCopied[k], h->ingestCopy));
+    return static_cast<int>(SSD_OK);
+  };
+  /* the records of the pass that ran last on the slice's stream, to the host */
+  auto records = [&](const ssd_frame_moments *d, int n)
+  {
+    hipStream_t s = h->lane[h->lastLane].lastStream;
+    HIP_TRY(hipMemcpyAsync(cur.data(), d, sizeof(ssd_frame_moments) * static_cast<size_t>(n), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return static_cast<int>(SSD_OK);
+  };
+  rc = copyIn(0, 0, nframes < slice ? nframes : slice);
+  if(rc) return rc;
+  int c = 0;
+  for(int done = 0; done < nframes; c++)
+  {
+    const int n = nframes - done < slice ? nframes - done : slice;
+    const int k = c & 1;
+    /* the next slice's copy beside this slice's kernels: its buffer is free, the slice before is finished */
+    if(done + n < nframes)
+    {
+      rc = copyIn(k ^ 1, done + n, nframes - done - n < slice ? nframes - done - n : slice);
+      if(rc) return rc;
+    }
+    HIP_TRY(hipStreamWaitEvent(h->ingestCompute, h->ingestCopied[k], 0));
+    rc = enqueue_impl(h, h->ingestBuf[k], devFrameBytes, n, h->ingestCompute, SSD_STAGE_ALL, depth, nullptr, 0, nullptr, dFirst);
+    if(rc) return rc;
+    rc = ssd_fetch_back(h, results + done, n, 0);
+    if(rc) return rc;
+    rc = records(dFirst, n);
+    if(rc) return rc;
+    if(first)
+      std::memcpy(first + done, cur.data(), sizeof(ssd_frame_moments) * static_cast<size_t>(n));
+    for(int pass = 0; pass < passes; pass++)
+    {
+      for(int i = 0; i < n; i++)
+      {
+        rc = ssd_surface_gates_from_moments(&cur[i], min_points, k_sigma, gate_min, &gates[i]);
+        if(rc) return rc;
+      }
+      rc = ssd_enqueue_surface_refit(h, h->ingestBuf[k], devFrameBytes, n, h->ingestCompute, input, gates.data(), dRefit);
+      if(rc) return rc;
+      rc = ssd_fetch_surface_refit(h, nullptr);
+      if(rc) return rc;
+      rc = records(dRefit, n);
+      if(rc) return rc;
+    }
+    if(refit)
+      std::memcpy(refit + done, cur.data(), sizeof(ssd_frame_moments) * static_cast<size_t>(n));
+    for(int i = 0; i < n; i++)
+    {
+      rc = ssd_surface_fit_solve(&cur[i], &cal, min_points, out + done + i);
+      if(rc) return rc;
+    }
+    done += n;
   }
   return SSD_OK;
 }

@@ -160,6 +160,21 @@ struct ssd_handle
   int groundFrames = 0;                     /* frames of the last call */
   std::vector<ssd_calibration> groundPriorCal;   /* its priors, one or one per frame: what ssd_fetch_ground_fit solves against */
   size_t groundBytes = 0;                   /* their share of `bytes` */
+  /* the trimmed surface refit (ssd_enqueue_surface_refit).  What the last enqueue was, so that a refit can be held
+   * to it: wholeKind 0 = none / a partial run / a failed one, 1 = a whole run under the handle's calibration, 2 = a cameras batch */
+  int wholeKind = 0;
+  bool wholeDepth = false;                  /* its input was 16-bit depth */
+  const void *wholeFrames = nullptr;        /* its frames and their stride */
+  size_t wholeStride = 0;
+  /* the gates of a call, made on the first one, so a handle that never refits holds none of them.  One set, like the ground fit's */
+  ssd_frame_gates *dRefitGates = nullptr;   /* F */
+  ssd_frame_gates *hRefitGates = nullptr;   /* pinned: the caller's gates are copied here during the call */
+  hipEvent_t refitGatesCopied = nullptr;    /* behind the copy pinned -> device: the pinned gates may be written again */
+  hipEvent_t refitDone = nullptr;           /* behind the pass */
+  hipStream_t refitLastStream = nullptr;    /* the stream of the previous pass (a switch is ordered by refitDone: the device gates are single) */
+  hipEvent_t evRefit[2] = { nullptr, nullptr };   /* around the pass of a timed call, made on the first one */
+  bool refitHaveLast = false, refitTimed = false;
+  size_t refitBytes = 0;                    /* their share of `bytes` */
 };
 
 #endif /* SSD_HANDLE_H_ */
