@@ -585,8 +585,9 @@ int ssd_process_host_cameras_riser_fits(ssd_handle *h, const void *frames, int n
  * k >= n_surfaces are zero; a frame with SSD_ST_THROW or n_steps == 0 is all zero.  All sums are exact integers: the device and
  * ssd_surface_refit_moments_host agree bit for bit, and a refit record goes wherever a first-pass record goes - ssd_surface_fit_solve,
  * ssd_ground_fit_solve on surface 0, ssd_camera_drift_fold - unchanged.
- * Out of scope: camera batches, the riser fit, ssd_pipeline_*, a solve on the device, and a gate that reaches points outside the
- * labelled set (the bias of a band cut askew by a wrong calibration is only partly answered). */
+ * Camera batches have their own entry points (ssd_enqueue_cameras_surface_refit, ssd_process_host_cameras_surfaces_refit, below).
+ * Out of scope: the riser fit, ssd_pipeline_*, a solve on the device, and a gate that reaches points outside the labelled set (the
+ * bias of a band cut askew by a wrong calibration is only partly answered). */
 typedef struct
 {
   double n[3];        /* the plane's normal, camera coordinates (unit when made by ssd_surface_gates_from_moments) */
@@ -622,7 +623,8 @@ int ssd_surface_refit_moments_host(const ssd_config *cfg, int input, const ssd_i
  * enqueue B, refit B without a fetch between is fine; refit B starts when refit A has ended).  ssd_set_intrinsics between an enqueue
  * and its refit withdraws the enqueue (the pass would deproject with other maps): the refit is then refused.
  * SSD_E_ARG, before anything is launched or copied: no such enqueue (none yet, or the last one was a partial ssd_enqueue_stages run or
- * a cameras batch), other frames, stride, nframes or input than it had, a null pointer, depth input without intrinsics.
+ * a cameras batch: ssd_enqueue_cameras_surface_refit refits those), other frames, stride, nframes or input than it had, a null pointer,
+ * depth input without intrinsics.
  * The pinned and device gate buffers (one ssd_frame_gates per frame of max_frames_per_batch each) are made on the first call and
  * counted in ssd_workspace_bytes from then on; a handle that never refits allocates and launches nothing more. */
 int ssd_enqueue_surface_refit(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream,
@@ -643,6 +645,51 @@ int ssd_get_surface_refit_time(ssd_handle *h, float *ms);
 int ssd_process_host_surfaces_refit(ssd_handle *h, const void *frames, int nframes, int input, ssd_frame_result *results,
                                     ssd_frame_moments *first /* may be NULL */, ssd_frame_moments *refit /* may be NULL */,
                                     int min_points, double k_sigma, double gate_min, int passes /* 1..4 */, ssd_frame_surfaces *out);
+
+/* ---- trimmed refit of cameras batches, and the drift watch on refit records ------------------------------------------------------
+ * EXTENSION: the contract of per-frame calibration, extended to the trimmed refit, so that the records
+ * ssd_camera_drift_fold folds can be refit records.
+ *   ssd_enqueue_cameras_surface_refit        ssd_enqueue_surface_refit where the handle's last whole enqueue was a cameras batch -
+ *                                            ssd_enqueue_cameras with or without labels, or ssd_enqueue_cameras_surface_moments.
+ *   ssd_process_host_cameras_surfaces_refit  ssd_process_host_surfaces_refit through the slices of ssd_process_host_cameras.
+ *   ssd_camera_ground_gates                  host only: every frame's ground gate from its CAMERA's folded floor plane.
+ * Contract: frame i's record is byte for byte what a handle made by ssd_create(cfg, &cams[camera_of_frame[i]].cal) (with
+ * ssd_set_intrinsics(&...intr) for depth input) gives from ssd_enqueue_surface_refit for that frame alone under gates[i]; hence it is
+ * bit for bit ssd_surface_refit_moments_host over that frame's labels.  The gates go by FRAME (gates[i], HOST memory, copied during the
+ * call), never by camera: two frames of one camera may carry different gates.  The pass takes no camera index of its own: it reads the
+ * index the enqueue left in its workspace's device array, and the handle's table.  Everything else is ssd_enqueue_surface_refit's and is
+ * shared with it: the stream and the completion event of its own, ssd_fetch_surface_refit and ssd_get_surface_refit_time, the zeroing in
+ * front of the pass, the one set of device gates per handle (passes of either kind run in the order of their calls, across workspaces),
+ * the gate buffers made on the first call of either kind and counted in ssd_workspace_bytes, and that nothing ssd_fetch* reads is
+ * touched.  ssd_set_cameras between a cameras enqueue and its refit withdraws the enqueue (the table, the index arrays and the maps
+ * would be other ones): the refit is then refused.
+ * SSD_E_ARG, before anything is launched or copied: the last enqueue was not a whole cameras batch (none yet, a partial run, a withdrawn
+ * one - or a whole one-calibration enqueue, which the message names as such), other frames, stride, nframes or input than that enqueue
+ * had, a null pointer. */
+int ssd_enqueue_cameras_surface_refit(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream,
+                                      int input, const ssd_frame_gates *gates /* HOST, nframes, copied during the call */,
+                                      ssd_frame_moments *d_out);
+/* Per slice, while it is still in its staging buffer: a cameras enqueue with the first moments, fetch, gates on the host per frame
+ * (ssd_surface_gates_from_moments), the refit pass, fetch - the last three `passes` times.  Fills results[nframes] (byte for byte
+ * ssd_process_host_cameras'), out[nframes] (out[i] = ssd_surface_fit_solve of the last pass's record i against
+ * cams[camera_of_frame[i]].cal) and, when not NULL, first[nframes] (ssd_process_host_cameras_surfaces' records) and refit[nframes] (the
+ * last pass's: what ssd_camera_drift_fold takes).  SSD_E_ARG before anything is copied: what ssd_process_host_cameras_surfaces and
+ * ssd_process_host_surfaces_refit refuse. */
+int ssd_process_host_cameras_surfaces_refit(ssd_handle *h, const void *frames, int nframes, const uint16_t *camera_of_frame, int input,
+                                            ssd_frame_result *results, ssd_frame_moments *first /* may be NULL */,
+                                            ssd_frame_moments *refit /* may be NULL */, int min_points, double k_sigma, double gate_min,
+                                            int passes /* 1..4 */, ssd_frame_surfaces *out);
+/* host only, no GPU needed.  The floor's plane in CAMERA coordinates is a property of the mounting: all frames of a camera share it, and
+ * the fold's plane (ssd_camera_drift_fold) is the best estimate a batch holds.  For every frame i with moments[i].ground == 1,
+ * moments[i].n_surfaces >= 1 and drift[camera_of_frame[i]].fit.status == SSD_GF_OK, gates[i].g[0] becomes n = fit.normal,
+ * dist = fit.dist, gate = max(k_sigma * fit.rms, gate_min), and gates[i].n_surfaces is raised to at least 1; every other gate and every
+ * other frame is left as given (make `gates` with ssd_surface_gates_from_moments first).  So a frame whose own ground fit was FEW or
+ * DEGENERATE still contributes its floor points to the next fold, and all of a camera's frames are trimmed against one plane.
+ * SSD_E_ARG, gates untouched: a null pointer, ncams outside 1 .. SSD_MAX_CAMERAS, nframes < 0, an index >= ncams, k_sigma not in
+ * (0, 16], gate_min not in [0, 1]. */
+int ssd_camera_ground_gates(const ssd_frame_moments *moments, const uint16_t *camera_of_frame, int nframes,
+                            const ssd_camera_drift *drift /* ncams records */, int ncams, double k_sigma, double gate_min,
+                            ssd_frame_gates *gates /* in/out, nframes */);
 
 /* stage selector for profiling / roofline measurement: runs only the chosen stage(s) of the pipeline */
 #define SSD_STAGE_HIST 1       /* K1: transform + crop + bin + histogram */

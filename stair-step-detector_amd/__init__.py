@@ -236,6 +236,7 @@ EXPORTS = [
     "ssd_process_host_cameras_riser_fits",
     "ssd_surface_gates_from_moments", "ssd_surface_refit_moments_host", "ssd_enqueue_surface_refit", "ssd_fetch_surface_refit",
     "ssd_get_surface_refit_time", "ssd_process_host_surfaces_refit",
+    "ssd_enqueue_cameras_surface_refit", "ssd_process_host_cameras_surfaces_refit", "ssd_camera_ground_gates",
 ]
 # libssd_source.so — the frame source standing in for the camera (include/ssd_source.h)
 SOURCE_EXPORTS = [
@@ -326,6 +327,11 @@ def lib():
     L.ssd_get_surface_refit_time.argtypes = [vp, C.POINTER(C.c_float)]
     L.ssd_process_host_surfaces_refit.argtypes = [vp, vp, i32, i32, C.POINTER(FrameResult), C.POINTER(FrameMoments), C.POINTER(FrameMoments), i32,
                                                   C.c_double, C.c_double, i32, C.POINTER(FrameSurfaces)]
+    L.ssd_enqueue_cameras_surface_refit.argtypes = [vp, vp, sz, i32, vp, i32, C.POINTER(FrameGates), vp]
+    L.ssd_process_host_cameras_surfaces_refit.argtypes = [vp, vp, i32, C.POINTER(C.c_uint16), i32, C.POINTER(FrameResult), C.POINTER(FrameMoments),
+                                                          C.POINTER(FrameMoments), i32, C.c_double, C.c_double, i32, C.POINTER(FrameSurfaces)]
+    L.ssd_camera_ground_gates.argtypes = [C.POINTER(FrameMoments), C.POINTER(C.c_uint16), i32, C.POINTER(CameraDrift), i32, C.c_double, C.c_double,
+                                          C.POINTER(FrameGates)]
     L.ssd_set_riser_moments.argtypes = [vp, i32]
     L.ssd_fetch_riser_moments.argtypes = [vp, C.POINTER(FrameMoments), i32, vp]
     L.ssd_riser_fit_solve.argtypes = [C.POINTER(FrameMoments), C.POINTER(FrameRisers), C.POINTER(Calibration), i32, C.POINTER(FrameRiserFits)]
@@ -608,6 +614,24 @@ def camera_drift_fold(moments, camera_of_frame, cameras, min_points=2000):
     out = (CameraDrift * max(1, ncams))()
     _check(lib().ssd_camera_drift_fold(mom, idx.ctypes.data_as(C.POINTER(C.c_uint16)), n, cams, ncams, int(min_points), out))
     return [CameraDrift.from_buffer_copy(out[i]) for i in range(ncams)]
+
+
+def camera_ground_gates(moments, camera_of_frame, drift, gates, k_sigma=2.5, gate_min=0.0):
+    """ssd_camera_ground_gates: the ground gate (g[0]) of every frame with a ground whose camera's folded fit (drift: the list
+    camera_drift_fold returns, one CameraDrift per camera) is GF_OK becomes that fit's plane with max(k_sigma * fit.rms, gate_min);
+    gates: a FrameGates per frame, as surface_gates_from_moments made them -> the list of FrameGates, the others as given"""
+    n = len(moments)
+    idx = np.ascontiguousarray(camera_of_frame, dtype=np.uint16)
+    if idx.ndim != 1 or idx.size != n or np.any(np.asarray(camera_of_frame) != idx):
+        raise SsdError("camera_of_frame: one index 0..65535 per frame")
+    if len(gates) != n:
+        raise SsdError("camera_ground_gates: one FrameGates per frame")
+    mom = moments if isinstance(moments, C.Array) and moments._type_ is FrameMoments else (FrameMoments * max(1, n))(*moments)
+    ncams = len(drift)
+    dr = drift if isinstance(drift, C.Array) and drift._type_ is CameraDrift else (CameraDrift * max(1, ncams))(*drift)
+    arr = (FrameGates * max(1, n))(*gates)
+    _check(lib().ssd_camera_ground_gates(mom, idx.ctypes.data_as(C.POINTER(C.c_uint16)), n, dr, ncams, float(k_sigma), float(gate_min), arr))
+    return [FrameGates.from_buffer_copy(arr[i]) for i in range(n)]
 
 
 # --------------------------------------------------------------------------- reference-shaped classes
@@ -947,13 +971,49 @@ class Detector:
                                                        INPUT_DEPTH16 if depth else INPUT_VERTICES, res, mom if moments else None, int(min_points), out))
         return (list(res), list(out), list(mom)) if moments else (list(res), list(out))
 
-    def camera_drift(self, frames, camera_of_frame, depth=False, min_points=2000):
+    def camera_drift(self, frames, camera_of_frame, depth=False, min_points=2000, passes=0, k_sigma=2.5, gate_min=0.0):
         """process_host_cameras_surfaces, then camera_drift_fold of its moments against the handle's camera table
-        -> (list of FrameResult, list of CameraDrift, one per camera of the table)"""
+        -> (list of FrameResult, list of CameraDrift, one per camera of the table).  passes >= 1: the fold of the last refit pass's
+        records of process_host_cameras_surfaces_refit(passes, k_sigma, gate_min) instead of the first pass's"""
         if not getattr(self, "_cameras", None):
             raise SsdError("camera_drift: the handle has no camera table (set_cameras)")
-        res, _, mom = self.process_host_cameras_surfaces(frames, camera_of_frame, depth=depth, moments=True)
+        if passes:
+            res, _, _, mom = self.process_host_cameras_surfaces_refit(frames, camera_of_frame, depth=depth, k_sigma=k_sigma, gate_min=gate_min,
+                                                                      passes=passes, moments=True)
+        else:
+            res, _, mom = self.process_host_cameras_surfaces(frames, camera_of_frame, depth=depth, moments=True)
         return res, camera_drift_fold(mom, camera_of_frame, self._cameras, min_points=min_points)
+
+    # ---- trimmed refit of cameras batches (include/ssd_hip.h, DESIGN.md section 7h)
+    def enqueue_cameras_surface_refit(self, d_ptr, nframes, gates, d_moments, depth=False, stride_bytes=None, stream=None):
+        """ssd_enqueue_cameras_surface_refit: enqueue_surface_refit behind the handle's last whole CAMERAS enqueue of the same frames:
+        frame i under the camera that enqueue named for it and under gates[i]; complete when fetch_surface_refit() returns"""
+        frame = self.cfg.width * self.cfg.height * (2 if depth else 12)
+        arr = None
+        if gates is not None:
+            arr = gates if isinstance(gates, C.Array) and gates._type_ is FrameGates else (FrameGates * max(1, len(gates)))(*gates)
+            if len(arr) < nframes:
+                raise SsdError("enqueue_cameras_surface_refit: fewer gates than frames")
+        _check(lib().ssd_enqueue_cameras_surface_refit(self._h, C.c_void_p(d_ptr), stride_bytes or frame, nframes, C.c_void_p(stream or 0),
+                                                       INPUT_DEPTH16 if depth else INPUT_VERTICES, arr, C.c_void_p(d_moments)))
+
+    def process_host_cameras_surfaces_refit(self, frames, camera_of_frame, depth=False, min_points=200, k_sigma=2.5, gate_min=0.0, passes=1,
+                                            moments=False):
+        """ssd_process_host_cameras_surfaces_refit: process_host_surfaces_refit with one camera index per frame
+        -> (list of FrameResult, list of FrameSurfaces of the last refit pass), with moments=True also the lists of FrameMoments of
+        the first pass and of the last refit pass"""
+        a = np.ascontiguousarray(frames, dtype=np.uint16 if depth else np.float32) if not isinstance(frames, PinnedArray) else frames.array
+        per = self.cfg.width * self.cfg.height * (1 if depth else 3)
+        n = a.size // per
+        if n < 1 or a.size != n * per:
+            raise SsdError("process_host_cameras_surfaces_refit: array does not hold whole frames")
+        idx = self._camera_index(camera_of_frame, n)
+        res, first, refit, out = (FrameResult * n)(), (FrameMoments * n)(), (FrameMoments * n)(), (FrameSurfaces * n)()
+        _check(lib().ssd_process_host_cameras_surfaces_refit(self._h, a.ctypes.data_as(C.c_void_p), n, idx.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                                             INPUT_DEPTH16 if depth else INPUT_VERTICES, res, first if moments else None,
+                                                             refit if moments else None, int(min_points), float(k_sigma), float(gate_min),
+                                                             int(passes), out))
+        return (list(res), list(out), list(first), list(refit)) if moments else (list(res), list(out))
 
     def surface_moments_time_ms(self, back=0):
         """Device time of the surface-moments pass of the enqueue `back` calls ago (0.0: it gathered none); timing must be on."""

@@ -1815,6 +1815,8 @@ int ssd_set_cameras(ssd_handle *h, const ssd_camera *cams, int ncams)
   }
   HIP_TRY(hipSetDevice(h->device));
   HIP_TRY(hipDeviceSynchronize());            /* batches in flight read the table and the lanes' indices */
+  if(h->wholeKind == 2)
+    h->wholeKind = 0;                          /* a refit of the last cameras batch would read another table, index array and maps */
   cameras_free(h);
   if(ncams == 0)
     return SSD_OK;
@@ -2350,27 +2352,40 @@ static int refit_prepare(ssd_handle *h)
   return SSD_OK;
 }
 
-int ssd_enqueue_surface_refit(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream,
+/* both refit entry points: `cameras` = behind a whole cameras batch (wholeKind 2), under the table and the index that batch left in its
+ * workspace; otherwise behind a whole run under the handle's calibration (wholeKind 1) */
+static int refit_enqueue_impl(ssd_handle *h, const char *who, bool cameras, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream,
                               int input, const ssd_frame_gates *gates, ssd_frame_moments *d_out)
 {
+  const std::string me(who);
   if(!h || !d_frames || !gates || !d_out)
-    return fail(SSD_E_ARG, "ssd_enqueue_surface_refit: null argument");
+    return fail(SSD_E_ARG, me + ": null argument");
   if(input != SSD_INPUT_VERTICES && input != SSD_INPUT_DEPTH16)
-    return fail(SSD_E_ARG, "ssd_enqueue_surface_refit: input must be SSD_INPUT_VERTICES or SSD_INPUT_DEPTH16");
+    return fail(SSD_E_ARG, me + ": input must be SSD_INPUT_VERTICES or SSD_INPUT_DEPTH16");
   const bool depthInput = input == SSD_INPUT_DEPTH16;
-  if(depthInput && !h->haveIntr)
-    return fail(SSD_E_ARG, "ssd_enqueue_surface_refit: depth input: call ssd_set_intrinsics first");
-  if(h->wholeKind == 2)
-    return fail(SSD_E_ARG, "ssd_enqueue_surface_refit: the last enqueue was a cameras batch (no refit for those)");
-  if(h->wholeKind != 1)
-    return fail(SSD_E_ARG, "ssd_enqueue_surface_refit: no whole enqueue to refit (none yet, or the last one was a partial run)");
+  if(cameras)
+  {
+    if(h->wholeKind == 1)
+      return fail(SSD_E_ARG, me + ": the last enqueue was a one-calibration batch, not a cameras batch (ssd_enqueue_surface_refit refits those)");
+    if(h->wholeKind != 2)
+      return fail(SSD_E_ARG, me + ": no whole cameras enqueue to refit (none yet, the last one was a partial run, or ssd_set_cameras withdrew it)");
+  }
+  else
+  {
+    if(depthInput && !h->haveIntr)
+      return fail(SSD_E_ARG, me + ": depth input: call ssd_set_intrinsics first");
+    if(h->wholeKind == 2)
+      return fail(SSD_E_ARG, me + ": the last enqueue was a cameras batch (ssd_enqueue_cameras_surface_refit refits those)");
+    if(h->wholeKind != 1)
+      return fail(SSD_E_ARG, me + ": no whole enqueue to refit (none yet, or the last one was a partial run)");
+  }
   if(nframes != h->lastFrames)
-    return fail(SSD_E_ARG, "ssd_enqueue_surface_refit: nframes is not the last enqueue's");
+    return fail(SSD_E_ARG, me + ": nframes is not the last enqueue's");
   if(depthInput != h->wholeDepth || d_frames != h->wholeFrames || frame_stride_bytes != h->wholeStride)
-    return fail(SSD_E_ARG, "ssd_enqueue_surface_refit: input, frames or stride are not the last enqueue's");
+    return fail(SSD_E_ARG, me + ": input, frames or stride are not the last enqueue's");
   ssd_lane &L = h->lane[h->lastLane];
-  if(!L.haveLast || !L.dState || !L.dTileMasks || (depthInput && !h->dDepthMaps))
-    return fail(SSD_E_HIP, "ssd_enqueue_surface_refit: the handle's workspace is incomplete (internal)");
+  if(!L.haveLast || !L.dState || !L.dTileMasks || (!cameras && depthInput && !h->dDepthMaps) || (cameras && (!h->dCams || !L.dCamIndex)))
+    return fail(SSD_E_HIP, me + ": the handle's workspace is incomplete (internal)");
   HIP_TRY(hipSetDevice(h->device));
   int rc = refit_prepare(h);
   if(rc) return rc;
@@ -2414,8 +2429,12 @@ int ssd_enqueue_surface_refit(ssd_handle *h, const void *d_frames, size_t frame_
   const int chunk = choose_chunk(h->tune, P.nPoints, nframes);      /* the first pass's */
   if(timing) HIP_TRY(hipEventRecord(h->evRefit[0], s));
   HIP_TRY(hipMemsetAsync(d_out, 0, sizeof(ssd_frame_moments) * static_cast<size_t>(nframes), s));
-  launch_surface_refit(xyz, strideFloats, P, L.dState, L.dTileMasks, h->tileMaskStride, nframes, chunk, depthInput ? &depthSrc : nullptr,
-                       h->dRefitGates, d_out, s);
+  if(cameras)                                  /* the table as the batch read it, the index where the batch's own copy left it */
+    launch_surface_refit_cams(xyz, strideFloats, P, L.dState, L.dTileMasks, h->tileMaskStride, nframes, chunk, depthInput ? &depthSrc : nullptr,
+                              h->dRefitGates, d_out, s, CameraSel{ h->dCams, L.dCamIndex, h->camsNeedChecks });
+  else
+    launch_surface_refit(xyz, strideFloats, P, L.dState, L.dTileMasks, h->tileMaskStride, nframes, chunk, depthInput ? &depthSrc : nullptr,
+                         h->dRefitGates, d_out, s);
   HIP_TRY(hipGetLastError());
   if(timing) HIP_TRY(hipEventRecord(h->evRefit[1], s));
   h->refitTimed = timing;
@@ -2424,6 +2443,18 @@ int ssd_enqueue_surface_refit(ssd_handle *h, const void *d_frames, size_t frame_
   HIP_TRY(hipEventRecord(L.done, s));
   L.lastStream = s;
   return SSD_OK;
+}
+
+int ssd_enqueue_surface_refit(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream,
+                              int input, const ssd_frame_gates *gates, ssd_frame_moments *d_out)
+{
+  return refit_enqueue_impl(h, "ssd_enqueue_surface_refit", false, d_frames, frame_stride_bytes, nframes, stream, input, gates, d_out);
+}
+
+int ssd_enqueue_cameras_surface_refit(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream,
+                                      int input, const ssd_frame_gates *gates, ssd_frame_moments *d_out)
+{
+  return refit_enqueue_impl(h, "ssd_enqueue_cameras_surface_refit", true, d_frames, frame_stride_bytes, nframes, stream, input, gates, d_out);
 }
 
 int ssd_fetch_surface_refit(ssd_handle *h, void *)
@@ -2452,19 +2483,15 @@ int ssd_get_surface_refit_time(ssd_handle *h, float *ms)
   return SSD_OK;
 }
 
-int ssd_process_host_surfaces_refit(ssd_handle *h, const void *frames, int nframes, int input, ssd_frame_result *results,
-                                    ssd_frame_moments *first, ssd_frame_moments *refit, int min_points, double k_sigma, double gate_min,
-                                    int passes, ssd_frame_surfaces *out)
+/* both host entry points, the caller's own refusals behind them: camOf (checked by check_cameras) = a cameras batch, each slice with its
+ * part of the index, its refit passes under the cameras, each frame solved against its own camera */
+static int process_host_refit_impl(ssd_handle *h, const char *who, const void *frames, int nframes, const uint16_t *camOf, int input,
+                                   ssd_frame_result *results, ssd_frame_moments *first, ssd_frame_moments *refit, int min_points,
+                                   double k_sigma, double gate_min, int passes, ssd_frame_surfaces *out)
 {
-  if(!h || !frames || !results || !out || nframes < 1)
-    return fail(SSD_E_ARG, "ssd_process_host_surfaces_refit: bad argument");
-  if(input != SSD_INPUT_VERTICES && input != SSD_INPUT_DEPTH16)
-    return fail(SSD_E_ARG, "ssd_process_host_surfaces_refit: input must be SSD_INPUT_VERTICES or SSD_INPUT_DEPTH16");
-  if(input == SSD_INPUT_DEPTH16 && !h->haveIntr)
-    return fail(SSD_E_ARG, "ssd_process_host_surfaces_refit: call ssd_set_intrinsics first");
   if(passes < 1 || passes > 4)
-    return fail(SSD_E_ARG, "ssd_process_host_surfaces_refit: passes must lie in 1 .. 4");
-  int rc = check_gate_rule("ssd_process_host_surfaces_refit", k_sigma, gate_min);
+    return fail(SSD_E_ARG, std::string(who) + ": passes must lie in 1 .. 4");
+  int rc = check_gate_rule(who, k_sigma, gate_min);
   if(rc) return rc;
   HIP_TRY(hipSetDevice(h->device));
   const bool depth = input == SSD_INPUT_DEPTH16;
@@ -2514,7 +2541,7 @@ int ssd_process_host_surfaces_refit(ssd_handle *h, const void *frames, int nfram
       if(rc) return rc;
     }
     HIP_TRY(hipStreamWaitEvent(h->ingestCompute, h->ingestCopied[k], 0));
-    rc = enqueue_impl(h, h->ingestBuf[k], devFrameBytes, n, h->ingestCompute, SSD_STAGE_ALL, depth, nullptr, 0, nullptr, dFirst);
+    rc = enqueue_impl(h, h->ingestBuf[k], devFrameBytes, n, h->ingestCompute, SSD_STAGE_ALL, depth, nullptr, 0, camOf ? camOf + done : nullptr, dFirst);
     if(rc) return rc;
     rc = ssd_fetch_back(h, results + done, n, 0);
     if(rc) return rc;
@@ -2529,7 +2556,7 @@ int ssd_process_host_surfaces_refit(ssd_handle *h, const void *frames, int nfram
         rc = ssd_surface_gates_from_moments(&cur[i], min_points, k_sigma, gate_min, &gates[i]);
         if(rc) return rc;
       }
-      rc = ssd_enqueue_surface_refit(h, h->ingestBuf[k], devFrameBytes, n, h->ingestCompute, input, gates.data(), dRefit);
+      rc = refit_enqueue_impl(h, who, camOf != nullptr, h->ingestBuf[k], devFrameBytes, n, h->ingestCompute, input, gates.data(), dRefit);
       if(rc) return rc;
       rc = ssd_fetch_surface_refit(h, nullptr);
       if(rc) return rc;
@@ -2540,12 +2567,27 @@ int ssd_process_host_surfaces_refit(ssd_handle *h, const void *frames, int nfram
       std::memcpy(refit + done, cur.data(), sizeof(ssd_frame_moments) * static_cast<size_t>(n));
     for(int i = 0; i < n; i++)
     {
-      rc = ssd_surface_fit_solve(&cur[i], &cal, min_points, out + done + i);
+      const ssd_calibration own = camOf ? calibration_of(h->camParams[camOf[done + i]]) : cal;
+      rc = ssd_surface_fit_solve(&cur[i], &own, min_points, out + done + i);
       if(rc) return rc;
     }
     done += n;
   }
   return SSD_OK;
+}
+
+int ssd_process_host_surfaces_refit(ssd_handle *h, const void *frames, int nframes, int input, ssd_frame_result *results,
+                                    ssd_frame_moments *first, ssd_frame_moments *refit, int min_points, double k_sigma, double gate_min,
+                                    int passes, ssd_frame_surfaces *out)
+{
+  if(!h || !frames || !results || !out || nframes < 1)
+    return fail(SSD_E_ARG, "ssd_process_host_surfaces_refit: bad argument");
+  if(input != SSD_INPUT_VERTICES && input != SSD_INPUT_DEPTH16)
+    return fail(SSD_E_ARG, "ssd_process_host_surfaces_refit: input must be SSD_INPUT_VERTICES or SSD_INPUT_DEPTH16");
+  if(input == SSD_INPUT_DEPTH16 && !h->haveIntr)
+    return fail(SSD_E_ARG, "ssd_process_host_surfaces_refit: call ssd_set_intrinsics first");
+  return process_host_refit_impl(h, "ssd_process_host_surfaces_refit", frames, nframes, nullptr, input, results, first, refit, min_points, k_sigma,
+                                 gate_min, passes, out);
 }
 
 /* ---- surface fit of cameras batches and drift per camera (include/ssd_hip.h) ---------------------------- */
@@ -2580,6 +2622,50 @@ int ssd_process_host_cameras_surfaces(ssd_handle *h, const void *frames, int nfr
     const ssd_calibration cal = calibration_of(h->camParams[camera_of_frame[i]]);
     rc = ssd_surface_fit_solve(moments + i, &cal, min_points, out + i);
     if(rc) return rc;
+  }
+  return SSD_OK;
+}
+
+/* ---- trimmed refit of cameras batches (include/ssd_hip.h) -------------------------------------------------- */
+
+int ssd_process_host_cameras_surfaces_refit(ssd_handle *h, const void *frames, int nframes, const uint16_t *camera_of_frame, int input,
+                                            ssd_frame_result *results, ssd_frame_moments *first, ssd_frame_moments *refit, int min_points,
+                                            double k_sigma, double gate_min, int passes, ssd_frame_surfaces *out)
+{
+  if(!h || !frames || !results || !out || nframes < 1)
+    return fail(SSD_E_ARG, "ssd_process_host_cameras_surfaces_refit: bad argument");
+  int rc = check_cameras(h, "ssd_process_host_cameras_surfaces_refit", camera_of_frame, nframes, input);
+  if(rc) return rc;
+  return process_host_refit_impl(h, "ssd_process_host_cameras_surfaces_refit", frames, nframes, camera_of_frame, input, results, first, refit,
+                                 min_points, k_sigma, gate_min, passes, out);
+}
+
+/* host only: no handle, no device */
+int ssd_camera_ground_gates(const ssd_frame_moments *moments, const uint16_t *camera_of_frame, int nframes, const ssd_camera_drift *drift,
+                            int ncams, double k_sigma, double gate_min, ssd_frame_gates *gates)
+{
+  if(!moments || !camera_of_frame || !drift || !gates || nframes < 0)
+    return fail(SSD_E_ARG, "ssd_camera_ground_gates: bad argument");
+  if(ncams < 1 || ncams > SSD_MAX_CAMERAS)
+    return fail(SSD_E_ARG, "ssd_camera_ground_gates: ncams must be 1.." + std::to_string(SSD_MAX_CAMERAS));
+  for(int i = 0; i < nframes; i++)
+    if(camera_of_frame[i] >= ncams)
+      return fail(SSD_E_ARG, "ssd_camera_ground_gates: frame " + std::to_string(i) + " names camera " + std::to_string(camera_of_frame[i]) + " of " + std::to_string(ncams));
+  const int rc = check_gate_rule("ssd_camera_ground_gates", k_sigma, gate_min);
+  if(rc) return rc;
+  for(int i = 0; i < nframes; i++)
+  {
+    const ssd_ground_fit &fit = drift[camera_of_frame[i]].fit;
+    if(moments[i].ground != 1 || moments[i].n_surfaces < 1 || fit.status != SSD_GF_OK)
+      continue;
+    ssd_plane_gate &g = gates[i].g[0];
+    for(int k = 0; k < 3; k++)
+      g.n[k] = fit.normal[k];
+    g.dist = fit.dist;
+    const double wide = k_sigma * fit.rms;
+    g.gate = wide > gate_min ? wide : gate_min;
+    if(gates[i].n_surfaces < 1)
+      gates[i].n_surfaces = 1;
   }
   return SSD_OK;
 }

@@ -170,6 +170,14 @@ struct CameraSel
   bool checks;                                /* some camera of the table needs the CHECKS instantiations */
 };
 
+/* The frame's record (the cameras entry points: ssd_kernels_cams.hip, ssd_kernels_refit.hip).  Its address depends on the frame
+ * alone, so it is block-uniform: the loads are scalar loads into SGPRs, what the kernel arguments of the one-calibration entry
+ * points are as well. */
+__device__ __forceinline__ const CameraRec &camera_of(const CameraRec *__restrict__ cams, const int *__restrict__ camOf, int frame)
+{
+  return cams[camOf[frame]];
+}
+
 /* strict point-in-quadrilateral test prepared once per quadrilateral
  * (reference quadrilateralTest.cpp:275-451: 3x3 cell map, <= 2 segments tested per cell) */
 struct QuadTest

@@ -160,8 +160,10 @@ struct ssd_handle
   int groundFrames = 0;                     /* frames of the last call */
   std::vector<ssd_calibration> groundPriorCal;   /* its priors, one or one per frame: what ssd_fetch_ground_fit solves against */
   size_t groundBytes = 0;                   /* their share of `bytes` */
-  /* the trimmed surface refit (ssd_enqueue_surface_refit).  What the last enqueue was, so that a refit can be held
-   * to it: wholeKind 0 = none / a partial run / a failed one, 1 = a whole run under the handle's calibration, 2 = a cameras batch */
+  /* the trimmed surface refit (ssd_enqueue_surface_refit; ssd_enqueue_cameras_surface_refit, section 7h).  What the
+   * last enqueue was, so that a refit can be held to it: wholeKind 0 = none / a partial run / a failed one / one withdrawn by
+   * ssd_set_intrinsics (kind 1) or ssd_set_cameras (kind 2), 1 = a whole run under the handle's calibration, 2 = a cameras batch (its
+   * index stays in its workspace's dCamIndex until the next cameras batch takes that workspace) */
   int wholeKind = 0;
   bool wholeDepth = false;                  /* its input was 16-bit depth */
   const void *wholeFrames = nullptr;        /* its frames and their stride */

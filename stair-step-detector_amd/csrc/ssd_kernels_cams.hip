@@ -14,14 +14,8 @@
 namespace ssd
 {
 
-/* The frame's record.  Its address depends on the frame alone, so it is block-uniform: the loads below are scalar loads into
- * SGPRs, what the kernel arguments of the one-calibration entry points are as well.  The streaming kernels copy the parts they
- * use at block start, as their siblings get them by value. */
-__device__ __forceinline__ const CameraRec &camera_of(const CameraRec *__restrict__ cams, const int *__restrict__ camOf, int frame)
-{
-  return cams[camOf[frame]];
-}
-
+/* camera_of (ssd_device.h) gives the frame's record; the streaming kernels copy the parts they use at block start, as their siblings
+ * get them by value. */
 template<int SRC, bool CHECKS>
 __global__ __launch_bounds__(kThreads, 6) void k_hist_cams(const float *__restrict__ xyz, size_t strideFloats, const CameraRec *__restrict__ cams,
                                                         const int *__restrict__ camOf, FrameState *__restrict__ st, uint2 *__restrict__ tileMasks,

@@ -1,6 +1,7 @@
 /*
  * ssd_refit.h — the trimmed surface refit's gate rule (include/ssd_hip.h), stated once for the device
- * (k_surface_refit, ssd_kernels_refit.hip) and the host (ssd_surface_refit_moments_host, ssd_capi.hip), and the kernel's launcher.
+ * (k_surface_refit and k_surface_refit_cams, ssd_kernels_refit.hip) and the host (ssd_surface_refit_moments_host, ssd_capi.hip), and the
+ * kernels' launchers.
  * Both sides are compiled without FMA contraction; the gate decides only WHICH points are summed, and everything summed is an
  * integer by the fixed-point rule of ssd_moments.h: they agree bit for bit.
  */
@@ -35,6 +36,11 @@ __host__ __device__ inline bool refit_keeps(const ssd_frame_gates &G, int k, flo
  * (device memory); frame i's record at out + i, zeroed by the caller on the stream in front of the launch */
 void launch_surface_refit(const float *xyz, size_t strideFloats, const Params &P, const FrameState *st, const uint2 *tileMasks, size_t tileMaskStride,
                           int nframes, int chunkPoints, const DepthSrc *depth, const ssd_frame_gates *gates, ssd_frame_moments *out, hipStream_t s);
+/* k_surface_refit_cams after a whole cameras batch on the same workspace (ssd_enqueue_cameras_surface_refit): the
+ * same, with the handle's table and that workspace's index in place of P's constants; gates[i] is still frame i's */
+void launch_surface_refit_cams(const float *xyz, size_t strideFloats, const Params &P, const FrameState *st, const uint2 *tileMasks, size_t tileMaskStride,
+                               int nframes, int chunkPoints, const DepthSrc *depth, const ssd_frame_gates *gates, ssd_frame_moments *out, hipStream_t s,
+                               const CameraSel &cams);
 
 } // namespace ssd
 
