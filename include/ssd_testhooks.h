@@ -76,6 +76,10 @@ int ssd_test_single_pass_frame(ssd_handle *h, int frame, uint8_t *plane_of_bin, 
 int ssd_test_single_pass_sample(ssd_handle *h, int frame, uint32_t *sample);
 /* the predictor's table as csrc/ssd_predict.h states it (host; no GPU): sample[SSD_MAX_BINS] -> plane_of_bin[SSD_MAX_BINS], returns the planes */
 int ssd_test_predict_table_host(const uint32_t *sample, int n_bins, int min_height, int sabotage, uint8_t *plane_of_bin);
+/* k_predict's sample of a vertex frame as csrc/ssd_predict.h states it (host; no GPU): the frame's first byte at the address base_address
+ * (only its place within a 128-byte line matters), n_points points (1 .. 2^26).  Returns the number of groups; first[g] / count[g]
+ * (g below cap; cap = 0: only the number is asked for) = the sampled points of group g: count[g] consecutive points from first[g] on */
+int ssd_test_predict_sample_host(unsigned long long base_address, int n_points, int32_t *first, int32_t *count, int cap);
 /* The constants of K1's single-precision pre-filter of the x / y range test (csrc/ssd_prexy.h: make_pre_xy) for a measuring range and a
  * calibration, on the host: out[0..7] = the four coefficient pairs (x row, y row), out[8] = lo, out[9] = hi, out[10] = the largest input
  * the bound holds for, out[11] / out[12] = the boxes' two offsets, out[13] = 1 when K1 tests the input's magnitude per point, 0 when

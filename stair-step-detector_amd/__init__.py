@@ -246,7 +246,7 @@ SOURCE_EXPORTS = [
 # libssd_testhooks.so — test infrastructure (include/ssd_testhooks.h)
 HOOK_EXPORTS = [
     "ssd_test_hypot_host", "ssd_test_hypot_device", "ssd_test_frame_state", "ssd_test_ground_image", "ssd_test_line_host", "ssd_test_intersect_host", "ssd_test_quad_device", "ssd_test_quad_host", "ssd_test_closing_host", "ssd_test_best_line_host", "ssd_test_grid_boxes_device", "ssd_test_sort_host",
-    "ssd_test_sort_device", "ssd_test_stream_read", "ssd_test_empty_quadrilateral", "ssd_test_single_pass", "ssd_test_plane_pool", "ssd_test_single_pass_stats", "ssd_test_single_pass_frame", "ssd_test_single_pass_sample", "ssd_test_predict_table_host", "ssd_test_prexy_host", "ssd_test_prez_host", "ssd_test_quad_edges_host", "ssd_test_quad_edges_device", "ssd_test_record_offset", "ssd_test_record_realloc", "ssd_test_record_realloc_sized", "ssd_test_record_release", "ssd_testhooks_last_error",
+    "ssd_test_sort_device", "ssd_test_stream_read", "ssd_test_empty_quadrilateral", "ssd_test_single_pass", "ssd_test_plane_pool", "ssd_test_single_pass_stats", "ssd_test_single_pass_frame", "ssd_test_single_pass_sample", "ssd_test_predict_table_host", "ssd_test_predict_sample_host", "ssd_test_prexy_host", "ssd_test_prez_host", "ssd_test_quad_edges_host", "ssd_test_quad_edges_device", "ssd_test_record_offset", "ssd_test_record_realloc", "ssd_test_record_realloc_sized", "ssd_test_record_release", "ssd_testhooks_last_error",
 ]
 SOURCE_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libssd_source.so")
 HOOKS_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libssd_testhooks.so")
@@ -416,6 +416,7 @@ def hooks_lib():
     L.ssd_test_single_pass_frame.argtypes = [vp, i32, vp, vp]
     L.ssd_test_single_pass_sample.argtypes = [vp, i32, vp]
     L.ssd_test_predict_table_host.argtypes = [vp, i32, i32, i32, vp]
+    L.ssd_test_predict_sample_host.argtypes = [C.c_ulonglong, i32, vp, vp, i32]
     L.ssd_test_prexy_host.argtypes = [vp, vp, vp, vp]
     L.ssd_test_prez_host.argtypes = [vp, vp, vp, C.c_double, i32, i32, vp]
     L.ssd_test_quad_edges_host.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]
@@ -453,6 +454,17 @@ def predict_table_host(sample, n_bins, min_height, sabotage=0):
     out = np.zeros(MAX_BINS, dtype=np.uint8)
     n = _check(hooks_lib().ssd_test_predict_table_host(a.ctypes.data_as(C.c_void_p), n_bins, min_height, sabotage, out.ctypes.data_as(C.c_void_p)), "hooks")
     return out, n
+
+
+def predict_sample_host(base_address, n_points):
+    """test hook (host, no GPU): k_predict's sample of a vertex frame of n_points points whose first byte lies at base_address, as
+    csrc/ssd_predict.h states it; returns (first, count), int32 arrays with an entry per group of lines: the sampled points of
+    group g are first[g] .. first[g] + count[g] - 1"""
+    groups = _check(hooks_lib().ssd_test_predict_sample_host(int(base_address), int(n_points), None, None, 0), "hooks")
+    first, count = np.zeros(groups, dtype=np.int32), np.zeros(groups, dtype=np.int32)
+    _check(hooks_lib().ssd_test_predict_sample_host(int(base_address), int(n_points), first.ctypes.data_as(C.c_void_p),
+                                                    count.ctypes.data_as(C.c_void_p), groups), "hooks")
+    return first, count
 
 
 def device_info(device):

@@ -30,7 +30,8 @@ constexpr int kMaxLive = kMaxStepImages + 1;      /* quadrilaterals a frame can 
 constexpr int kZFixShift = 40;                    /* mean z accumulates round(z * 2^40) in int64 */
 /* single pass: planes (one bit image per predicted height bin) a frame can have; beyond, the frame is rastered by k_raster */
 constexpr int kMaxPlanes = SSD_MAX_PLANES;
-/* k_predict samples one cell (64 consecutive points) of every kSpecSample */
+/* k_predict samples one point in kSpecSample: vertex input one whole 128-byte line (ten points) of every fifteen, depth input one run
+ * of 16 pixels of every sixteen (ssd_predict.h: predict_sample_run; its thresholds are written for this ratio) */
 #ifndef SSD_SPEC_SAMPLE
 #define SSD_SPEC_SAMPLE 16
 #endif

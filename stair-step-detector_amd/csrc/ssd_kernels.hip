@@ -45,6 +45,7 @@
 #include "ssd_closing.h"
 #include "ssd_bestline.h"
 #include "ssd_sort.h"
+#include "ssd_predict.h"    /* k_predict's sample rule (predict_sample_run), shared with the tests */
 
 namespace ssd
 {
@@ -1450,19 +1451,22 @@ __global__ __launch_bounds__(kThreads, SSD_K1S_WAVES) void k_hist_planes(const f
 }
 #endif /* SSD_CAMERAS_TU */
 
-/* K0 of a single-pass batch: which height bins may belong to a step plateau?  A histogram of one cell in every kSpecSample (a
- * different column of the camera image from row to row), the reference's peak filter (pointcloud.cpp:243-256) on it with
+/* K0 of a single-pass batch: which height bins may belong to a step plateau?  A histogram of a sample of the frame (vertex input: one
+ * whole 128-byte line of every fifteen, at a place in its group that changes from group to group - ssd_predict.h; depth input: one run
+ * of 16 pixels of every sixteen), the reference's peak filter (pointcloud.cpp:243-256) on it with
  * slack, a plane for each candidate peak's bin and its two neighbours (the plateau takes the peak bin and the fuller
  * neighbour: only the complete histogram decides which).  Nothing here has to be right: k_peaks checks the planes against the
  * plateaus it finds in the complete histogram, and a frame whose plateaus are not covered is rastered by k_raster.
  * Grid (frame, part): the blocks of a frame add their counts into FrameState::predHist; the last one to finish makes the table
- * and leaves the accumulators zero.  sabotage (tests): 1 = planes three bins above the right ones, 2 = no planes. */
-template<int SRC>
-SSD_ENTRY(__launch_bounds__(kThreads), k_predict, predict_block)(const float *__restrict__ xyz, size_t strideFloats, SSD_BYVAL(PointParams) P,
-                                                      FrameState *__restrict__ st, SSD_BYVAL(DepthSrc) D, int minHeight, int sabotage, int *__restrict__ fallback, int poolPlanes)
+ * and leaves the accumulators zero.  sabotage (tests): 1 = planes three bins above the right ones, 2 = no planes.
+ * CHECKS: the pre-filter's tests of the rare configurations, as K1's (vertex input; the depth loop asks the doubles about every point). */
+template<int SRC, bool CHECKS>
+__device__ __forceinline__ void predict_block(const float *__restrict__ xyz, size_t strideFloats, const PointParams &P, const PreXY &Q,
+                                              FrameState *__restrict__ st, const DepthSrc &D, int minHeight, int sabotage, int *__restrict__ fallback, int poolPlanes)
 {
   __shared__ unsigned int sh[kMaxBins + 2];
-  __shared__ unsigned int shc[kMaxBins * kHistCopies];        /* [bin][copy], as K1's: the lanes of a wave mostly vote for ONE bin */
+  alignas(16) __shared__ unsigned int shc[kMaxBins * kHistCopies];        /* [bin][copy], as K1's: the lanes of a wave mostly vote for ONE bin */
+  __shared__ K1Consts kc;                                                 /* vertex input: the doubles' constants, as K1 keeps them */
   __shared__ int sLast;
   const int frame = blockIdx.x, part = blockIdx.y, nParts = gridDim.y, tid = threadIdx.x;
   const float *base = SRC == kSrcDepth16
@@ -1470,31 +1474,89 @@ SSD_ENTRY(__launch_bounds__(kThreads), k_predict, predict_block)(const float *__
     : xyz + static_cast<size_t>(frame) * strideFloats;
   if(tid < kMaxBins + 2)
     sh[tid] = 0u;
-  for(int i = tid; i < kMaxBins * kHistCopies; i += kThreads)
-    shc[i] = 0u;
+  for(int i = tid; i < kMaxBins * kHistCopies / 4; i += kThreads)
+    reinterpret_cast<uint4 *>(shc)[i] = make_uint4(0u, 0u, 0u, 0u);
+  if(SRC != kSrcDepth16 && tid == 0)
+    k1_consts_fill(kc, P, nullptr);
   __syncthreads();
   unsigned int *mine = shc + (tid & (kHistCopies - 1));
-  /* the sample: runs of 16 consecutive points (four lanes' loads, 192 B), one of every kSpecSample runs, at a place in its group
-   * of runs that changes from group to group.  (Whole cells of 64 points were tried first: neighbouring pixels share a height
-   * bin, so a bin's count is really a count of runs - with 64-point runs a background bin's 150 samples were five runs and
-   * one bin in six passed the peak filter by chance.) */
+  if constexpr(SRC != kSrcDepth16)
+  {
+    /* The sample: whole 128-byte lines (ssd_predict.h).  One point per lane by a 12-byte load, ten lanes to a line, six lines to a
+     * wave instruction (four lanes idle); a block takes 24 groups per step, the frame's blocks take turns.  A lane requests the points
+     * of four steps before it looks at the first (a single dependent read pays the whole way to HBM; at most 24 lines per wave, 768 per
+     * CU where eight blocks are resident - the residency is not measured): addresses clamped into the frame, no branch between the loads and their use; a lane without a point -
+     * a line cut by the frame's ends, a group beyond the last - reads the frame's last point and blanks it (z = 0: no measurement).
+     * The four are requested and counted within one trip of the loop: carried round it in registers, the compiler moves the loaded
+     * y and z at the loop's head (pre_xy's packed FMAs want y in an even register) behind a wait for every load in flight.
+     * The decisions are K1's: single precision first (pre_range), the band it cannot call through the reference's doubles by the
+     * whole wave - the count is exact.  The price: 54 vector registers where the round-4 loop had 40 (still eight waves a SIMD), and
+     * four lanes in 64 that issue for nothing. */
+    constexpr int kLines = 64 / kPredictLinePoints, kDepth = 4;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int slot = lane / kPredictLinePoints, k = lane - slot * kPredictLinePoints;
+    const bool live = slot < kLines;
+    const int step = nParts * (kThreads / 64) * kLines;
+    const int gWave = (part * (kThreads / 64) + wave) * kLines;                  /* the wave's first group: wave-uniform, the loop's bound */
+    const unsigned long long addr = reinterpret_cast<unsigned long long>(base);
+    const int nGroups = predict_sample_groups(addr, P.nPoints);
+    const PreLane lc(Q);
+    for(int s = 0; gWave + s * step < nGroups; s += kDepth)
+    {
+      F3 v[kDepth];
+      bool has[kDepth];
+#pragma unroll
+      for(int d = 0; d < kDepth; d++)
+      {
+        const PredictRun r = predict_sample_run(addr, P.nPoints, gWave + slot + (s + d) * step);
+        has[d] = live & (k < r.count);
+        v[d] = *reinterpret_cast<const F3 *>(base + 3 * static_cast<size_t>(min(r.first + k, P.nPoints - 1)));
+      }
+#pragma unroll
+      for(int d = 0; d < kDepth; d++)
+      {
+        const F3 p{ v[d].x, v[d].y, has[d] ? v[d].z : 0.0f };
+        const PreRange r = pre_range<CHECKS, false>(p, Q, lc);
+        unsigned int b = r.b;
+        unsigned long long mIn = r.mInSure;
+        if(r.mSlow != 0ull)
+        {
+          /* rare, wave-uniform: the reference's rows, compares and bin (hist_block) */
+          const K1ConstsLds c = k1_consts(kc);
+          const World3 w = world_rows(c, p);
+          mIn |= r.mSlow & __ballot(world_in_range(c, w));
+          b = __builtin_amdgcn_inverse_ballot_w64(r.mSlow) ? static_cast<unsigned int>(world_bin(c, w)) : b;
+        }
+        if(__builtin_amdgcn_inverse_ballot_w64(mIn))
+          if(SSD_CHK(32, b, P.nBins))
+            atomicAdd(mine + b * kHistCopies, 1u);
+      }
+    }
+  }
+  else
+  {
+    /* depth input (not the product's path: it keeps two passes there): runs of 16 consecutive pixels (four lanes' loads), one of every
+     * kSpecSample runs, at a place in its group of runs that changes from group to group.  (Whole cells of 64 points were tried first:
+     * neighbouring pixels share a height bin, so a bin's count is really a count of runs - with 64-point runs a background bin's 150
+     * samples were five runs and one bin in six passed the peak filter by chance.) */
 #ifndef SSD_K0_RUN
 #define SSD_K0_RUN 16
 #endif
-  constexpr int kRun = SSD_K0_RUN, kLanesPerRun = kRun / kPts;
-  const int nRuns = (P.nPoints + kRun - 1) / kRun;
-  const int nGroups = (nRuns + kSpecSample - 1) / kSpecSample;
-  for(int g = part * (kThreads / kLanesPerRun) + tid / kLanesPerRun; g < nGroups; g += nParts * (kThreads / kLanesPerRun))
-  {
-    const int run = g * kSpecSample + ((g * 5) & (kSpecSample - 1));
-    F3 v[kPts];
-    load_points<SRC>(base, run * kRun + kPts * (tid % kLanesPerRun), P.nPoints, v, D);
-#pragma unroll
-    for(int j = 0; j < kPts; j++)
+    constexpr int kRun = SSD_K0_RUN, kLanesPerRun = kRun / kPts;
+    const int nRuns = (P.nPoints + kRun - 1) / kRun;
+    const int nGroups = (nRuns + kSpecSample - 1) / kSpecSample;
+    for(int g = part * (kThreads / kLanesPerRun) + tid / kLanesPerRun; g < nGroups; g += nParts * (kThreads / kLanesPerRun))
     {
-      double wx, wy, wz;
-      if(world_point_flat(P, v[j], wx, wy, wz))
-        atomicAdd(mine + height_bin(P, wz) * kHistCopies, 1u);
+      const int run = g * kSpecSample + ((g * 5) & (kSpecSample - 1));
+      F3 v[kPts];
+      load_points<SRC>(base, run * kRun + kPts * (tid % kLanesPerRun), P.nPoints, v, D);
+#pragma unroll
+      for(int j = 0; j < kPts; j++)
+      {
+        double wx, wy, wz;
+        if(world_point_flat(P, v[j], wx, wy, wz))
+          atomicAdd(mine + height_bin(P, wz) * kHistCopies, 1u);
+      }
     }
   }
   __syncthreads();
@@ -1650,6 +1712,22 @@ SSD_ENTRY(__launch_bounds__(kThreads), k_predict, predict_block)(const float *__
     }
   }
 }
+
+/* the entry points of the one-calibration chain; launch_predict picks by needs_checks(), as launch_hist does */
+#ifndef SSD_CAMERAS_TU
+template<int SRC>
+__global__ __launch_bounds__(kThreads) void k_predict(const float *__restrict__ xyz, size_t strideFloats, PointParams P, PreXY Q, FrameState *__restrict__ st, DepthSrc D,
+                                                      int minHeight, int sabotage, int *__restrict__ fallback, int poolPlanes)
+{
+  predict_block<SRC, false>(xyz, strideFloats, P, Q, st, D, minHeight, sabotage, fallback, poolPlanes);
+}
+template<int SRC>
+__global__ __launch_bounds__(kThreads) void k_predict_checks(const float *__restrict__ xyz, size_t strideFloats, PointParams P, PreXY Q, FrameState *__restrict__ st, DepthSrc D,
+                                                             int minHeight, int sabotage, int *__restrict__ fallback, int poolPlanes)
+{
+  predict_block<SRC, true>(xyz, strideFloats, P, Q, st, D, minHeight, sabotage, fallback, poolPlanes);
+}
+#endif /* SSD_CAMERAS_TU */
 
 /* ========================================================================= */
 /* K1b: peaks, plateaus, LUT — one thread per frame (121 bins: trivial)        */
@@ -4699,7 +4777,14 @@ void launch_predict(const float *xyz, size_t strideFloats, const Params &P, Fram
   dim3 pgrid(nframes, kPredictParts);
   with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &D)
   {
-    hipLaunchKernelGGL(k_predict<decltype(src)::value>, pgrid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, st, D, P.minHeight, sabotage, fallback, poolPlanes);
+    constexpr int SRC = decltype(src)::value;
+    if constexpr(SRC != kSrcDepth16)          /* (the depth loop has no pre-filter: one instantiation) */
+      if(needs_checks(P))
+      {
+        hipLaunchKernelGGL(k_predict_checks<SRC>, pgrid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.pre, st, D, P.minHeight, sabotage, fallback, poolPlanes);
+        return;
+      }
+    hipLaunchKernelGGL(k_predict<SRC>, pgrid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.pre, st, D, P.minHeight, sabotage, fallback, poolPlanes);
   });
 }
 void launch_hist(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, uint2 *tileMasks, size_t tileMaskStride,

@@ -46,14 +46,15 @@ __global__ __launch_bounds__(kThreads, SSD_K1S_WAVES) void k_hist_planes_cams(co
   hist_block<SRC, true, STRIPS, CHECKS>(L, SL, xyz, strideFloats, P, Q, X, st, tileMasks, planeImg, tileMaskStride, chunkPoints, D, blockIdx.x, blockIdx.y);
 }
 
-template<int SRC>
+template<int SRC, bool CHECKS>
 __global__ __launch_bounds__(kThreads) void k_predict_cams(const float *__restrict__ xyz, size_t strideFloats, const CameraRec *__restrict__ cams,
                                                            const int *__restrict__ camOf, FrameState *__restrict__ st, int sabotage, int *__restrict__ fallback, int poolPlanes)
 {
   const CameraRec &C = camera_of(cams, camOf, blockIdx.x);
   const PointParams P = C.P.pt;
+  const PreXY Q = C.P.pre;
   const DepthSrc D = C.D;
-  predict_block<SRC>(xyz, strideFloats, P, st, D, C.P.minHeight, sabotage, fallback, poolPlanes);
+  predict_block<SRC, CHECKS>(xyz, strideFloats, P, Q, st, D, C.P.minHeight, sabotage, fallback, poolPlanes);
 }
 
 __global__ __launch_bounds__(64) void k_peaks_cams(const CameraRec *__restrict__ cams, const int *__restrict__ camOf, FrameState *__restrict__ st, int nframes,
@@ -208,7 +209,14 @@ void launch_predict_cams(const float *xyz, size_t strideFloats, const Params &P,
   dim3 pgrid(nframes, kPredictParts);
   with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &)
   {
-    hipLaunchKernelGGL(k_predict_cams<decltype(src)::value>, pgrid, dim3(kThreads), 0, s, xyz, strideFloats, cams.table, cams.index, st, sabotage, fallback, poolPlanes);
+    constexpr int SRC = decltype(src)::value;
+    if constexpr(SRC == kSrcDepth16)         /* the depth loop has no pre-filter: one instantiation */
+      hipLaunchKernelGGL((k_predict_cams<SRC, false>), pgrid, dim3(kThreads), 0, s, xyz, strideFloats, cams.table, cams.index, st, sabotage, fallback, poolPlanes);
+    else
+      with_bool(cams.checks, [&](auto checks)
+      {
+        hipLaunchKernelGGL((k_predict_cams<SRC, decltype(checks)::value>), pgrid, dim3(kThreads), 0, s, xyz, strideFloats, cams.table, cams.index, st, sabotage, fallback, poolPlanes);
+      });
   });
 }
 void launch_hist_cams(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, uint2 *tileMasks, size_t tileMaskStride,

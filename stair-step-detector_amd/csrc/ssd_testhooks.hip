@@ -404,6 +404,20 @@ int ssd_test_predict_table_host(const uint32_t *sample, int n_bins, int min_heig
   return predict_table(sample, n_bins, min_height, sabotage, plane_of_bin);
 }
 
+int ssd_test_predict_sample_host(unsigned long long base_address, int n_points, int32_t *first, int32_t *count, int cap)
+{
+  if(n_points < 1 || n_points > (1 << 26) || cap < 0 || (cap > 0 && (!first || !count)))
+    return fail(SSD_E_ARG, "ssd_test_predict_sample_host: bad argument");
+  const int groups = predict_sample_groups(base_address, n_points);
+  for(int g = 0; g < groups && g < cap; g++)
+  {
+    const PredictRun r = predict_sample_run(base_address, n_points, g);
+    first[g] = r.first;
+    count[g] = r.count;
+  }
+  return groups;
+}
+
 int ssd_test_prexy_host(const double range[6], const double a[9], const double b[3], float out[14])
 {
   if(!range || !a || !b || !out)
