@@ -586,7 +586,8 @@ int ssd_process_host_cameras_riser_fits(ssd_handle *h, const void *frames, int n
  * ssd_surface_refit_moments_host agree bit for bit, and a refit record goes wherever a first-pass record goes - ssd_surface_fit_solve,
  * ssd_ground_fit_solve on surface 0, ssd_camera_drift_fold - unchanged.
  * Camera batches have their own entry points (ssd_enqueue_cameras_surface_refit, ssd_process_host_cameras_surfaces_refit, below).
- * Out of scope: the riser fit, ssd_pipeline_*, a solve on the device, and a gate that reaches points outside the labelled set (the
+ * The gates can also be made on the device (ssd_enqueue_surface_refit_device, DESIGN.md section 7i, below).
+ * Out of scope: the riser fit, ssd_pipeline_*, and a gate that reaches points outside the labelled set (the
  * bias of a band cut askew by a wrong calibration is only partly answered). */
 typedef struct
 {
@@ -690,6 +691,53 @@ int ssd_process_host_cameras_surfaces_refit(ssd_handle *h, const void *frames, i
 int ssd_camera_ground_gates(const ssd_frame_moments *moments, const uint16_t *camera_of_frame, int nframes,
                             const ssd_camera_drift *drift /* ncams records */, int ncams, double k_sigma, double gate_min,
                             ssd_frame_gates *gates /* in/out, nframes */);
+
+/* ---- surface gates on the device: refit passes chained with no host round trip ----------------------------------------------------
+ * EXTENSION.  Between two refit passes stands one step, ssd_surface_gates_from_moments - a 3 x 3 eigen-solve per
+ * surface.  Made on the host it costs a wait, a copy down and a copy up per pass, and a caller who enqueues ahead of its fetches loses
+ * that the moment it asks for a refit.  k_surface_gates makes the gates on the device, from records in device memory, by the same text
+ * as the host function (csrc/ssd_solve.h, both sides without FMA contraction).
+ * Contract: frame i's ssd_frame_gates is byte for byte what ssd_surface_gates_from_moments(&rec[i], min_points, k_sigma, gate_min, ..)
+ * fills, all 688 bytes of it (the header, zero gates at k >= n_surfaces and for FEW / DEGENERATE surfaces); moments at k >= n_surfaces
+ * are not read.  A record whose n_surfaces lies outside 0 .. SSD_MAX_STEPS - which the host function refuses - gives the all-zero
+ * record (n_surfaces = 0): the device has nobody to refuse to.
+ *   ssd_enqueue_surface_gates                 records on the device -> gates on the device, on `stream`, without synchronising; the
+ *                                             handle gives the device and the limit of nframes, nothing of it is touched.  d_gates
+ *                                             must not overlap d_moments (not checked).
+ *   ssd_enqueue_surface_refit_device          ssd_enqueue_surface_refit whose gates are made from d_prev (nframes records in device
+ *   ssd_enqueue_cameras_surface_refit_device  memory: the first pass's, or a refit pass's) by k_surface_gates on the pass's stream, in
+ *                                             front of the zeroing: no host copy, no wait.  d_prev == d_out is allowed.
+ * The chain: ssd_enqueue_surface_moments(.., d_first); .._refit_device(d_prev = d_first, d_out); .._refit_device(d_prev = d_out, d_out);
+ * no fetch between; with one workspace and with several (the pass runs on the stream its batch ran on, behind it).  Everything else
+ * is ssd_enqueue_surface_refit's, shared: the "last whole enqueue" checks, the one set of device gates per handle (passes of every
+ * kind run in the order of their calls, across workspaces), ssd_fetch_surface_refit, ssd_get_surface_refit_time (which includes the
+ * gates kernel), the gate buffers made on the first call of any kind and counted in ssd_workspace_bytes.  The gates depend on camera
+ * coordinates alone: the cameras form launches the same kernel.
+ * SSD_E_ARG, before anything is launched or copied: what ssd_enqueue_surface_refit / ssd_enqueue_cameras_surface_refit refuse, k_sigma
+ * not in (0, 16], gate_min not in [0, 1], a null d_prev, d_moments or d_gates, nframes outside 1 .. max_frames_per_batch.
+ * A handle that never calls any of these allocates and launches nothing more.
+ * Limits: the riser fit has no refit; ssd_pipeline_* does not refit; ssd_camera_ground_gates stays on the host (it needs the fold), and
+ * so does ssd_surface_fit_solve; the host paths below still finish a slice before the next one's kernels go out. */
+int ssd_enqueue_surface_gates(ssd_handle *h, const ssd_frame_moments *d_moments, int nframes, void *stream,
+                              int min_points, double k_sigma, double gate_min, ssd_frame_gates *d_gates /* DEVICE, nframes */);
+int ssd_enqueue_surface_refit_device(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream, int input,
+                                     const ssd_frame_moments *d_prev /* DEVICE, nframes */, int min_points, double k_sigma, double gate_min,
+                                     ssd_frame_moments *d_out);
+int ssd_enqueue_cameras_surface_refit_device(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream, int input,
+                                             const ssd_frame_moments *d_prev /* DEVICE, nframes */, int min_points, double k_sigma,
+                                             double gate_min, ssd_frame_moments *d_out);
+/* ssd_process_host_surfaces_refit / ssd_process_host_cameras_surfaces_refit with the gates made on the device: per slice an enqueue with
+ * the first moments, `passes` device-gated refits behind it (the first from the first pass's records, later ones in place), then the
+ * results and the records - the passes of a slice are waited for once (the copies of the records each end in a wait of their own,
+ * behind it) where the host-gated functions wait once per pass.  Arguments,
+ * refusals and every output (results, first, refit, out) are those functions', byte for byte. */
+int ssd_process_host_surfaces_refit_device(ssd_handle *h, const void *frames, int nframes, int input, ssd_frame_result *results,
+                                           ssd_frame_moments *first /* may be NULL */, ssd_frame_moments *refit /* may be NULL */,
+                                           int min_points, double k_sigma, double gate_min, int passes /* 1..4 */, ssd_frame_surfaces *out);
+int ssd_process_host_cameras_surfaces_refit_device(ssd_handle *h, const void *frames, int nframes, const uint16_t *camera_of_frame, int input,
+                                                   ssd_frame_result *results, ssd_frame_moments *first /* may be NULL */,
+                                                   ssd_frame_moments *refit /* may be NULL */, int min_points, double k_sigma,
+                                                   double gate_min, int passes /* 1..4 */, ssd_frame_surfaces *out);
 
 /* stage selector for profiling / roofline measurement: runs only the chosen stage(s) of the pipeline */
 #define SSD_STAGE_HIST 1       /* K1: transform + crop + bin + histogram */

@@ -237,6 +237,8 @@ EXPORTS = [
     "ssd_surface_gates_from_moments", "ssd_surface_refit_moments_host", "ssd_enqueue_surface_refit", "ssd_fetch_surface_refit",
     "ssd_get_surface_refit_time", "ssd_process_host_surfaces_refit",
     "ssd_enqueue_cameras_surface_refit", "ssd_process_host_cameras_surfaces_refit", "ssd_camera_ground_gates",
+    "ssd_enqueue_surface_gates", "ssd_enqueue_surface_refit_device", "ssd_enqueue_cameras_surface_refit_device",
+    "ssd_process_host_surfaces_refit_device", "ssd_process_host_cameras_surfaces_refit_device",
 ]
 # libssd_source.so — the frame source standing in for the camera (include/ssd_source.h)
 SOURCE_EXPORTS = [
@@ -330,6 +332,11 @@ def lib():
     L.ssd_enqueue_cameras_surface_refit.argtypes = [vp, vp, sz, i32, vp, i32, C.POINTER(FrameGates), vp]
     L.ssd_process_host_cameras_surfaces_refit.argtypes = [vp, vp, i32, C.POINTER(C.c_uint16), i32, C.POINTER(FrameResult), C.POINTER(FrameMoments),
                                                           C.POINTER(FrameMoments), i32, C.c_double, C.c_double, i32, C.POINTER(FrameSurfaces)]
+    L.ssd_enqueue_surface_gates.argtypes = [vp, vp, i32, vp, i32, C.c_double, C.c_double, vp]
+    L.ssd_enqueue_surface_refit_device.argtypes = [vp, vp, sz, i32, vp, i32, vp, i32, C.c_double, C.c_double, vp]
+    L.ssd_enqueue_cameras_surface_refit_device.argtypes = L.ssd_enqueue_surface_refit_device.argtypes
+    L.ssd_process_host_surfaces_refit_device.argtypes = L.ssd_process_host_surfaces_refit.argtypes
+    L.ssd_process_host_cameras_surfaces_refit_device.argtypes = L.ssd_process_host_cameras_surfaces_refit.argtypes
     L.ssd_camera_ground_gates.argtypes = [C.POINTER(FrameMoments), C.POINTER(C.c_uint16), i32, C.POINTER(CameraDrift), i32, C.c_double, C.c_double,
                                           C.POINTER(FrameGates)]
     L.ssd_set_riser_moments.argtypes = [vp, i32]
@@ -944,19 +951,21 @@ class Detector:
         _check(lib().ssd_get_surface_refit_time(self._h, C.byref(ms)))
         return ms.value
 
-    def process_host_surfaces_refit(self, frames, depth=False, min_points=200, k_sigma=2.5, gate_min=0.0, passes=1, moments=False):
+    def process_host_surfaces_refit(self, frames, depth=False, min_points=200, k_sigma=2.5, gate_min=0.0, passes=1, moments=False,
+                                    device_gates=False):
         """ssd_process_host_surfaces_refit: frames on the host (float32 [n, H, W, 3], or uint16 [n, H, W] with depth=True)
         -> (list of FrameResult, list of FrameSurfaces of the last refit pass), with moments=True also the lists of FrameMoments of
-        the first pass and of the last refit pass"""
+        the first pass and of the last refit pass.  device_gates=True: ssd_process_host_surfaces_refit_device (the gates made on the
+        device between the passes; the same outputs)"""
         a = np.ascontiguousarray(frames, dtype=np.uint16 if depth else np.float32)
         per = self.cfg.width * self.cfg.height * (1 if depth else 3)
         n = a.size // per
         if n < 1 or a.size != n * per:
             raise SsdError("process_host_surfaces_refit: array does not hold whole frames")
         res, first, refit, out = (FrameResult * n)(), (FrameMoments * n)(), (FrameMoments * n)(), (FrameSurfaces * n)()
-        _check(lib().ssd_process_host_surfaces_refit(self._h, a.ctypes.data_as(C.c_void_p), n, INPUT_DEPTH16 if depth else INPUT_VERTICES, res,
-                                                     first if moments else None, refit if moments else None, int(min_points),
-                                                     float(k_sigma), float(gate_min), int(passes), out))
+        fn = lib().ssd_process_host_surfaces_refit_device if device_gates else lib().ssd_process_host_surfaces_refit
+        _check(fn(self._h, a.ctypes.data_as(C.c_void_p), n, INPUT_DEPTH16 if depth else INPUT_VERTICES, res, first if moments else None,
+                  refit if moments else None, int(min_points), float(k_sigma), float(gate_min), int(passes), out))
         return (list(res), list(out), list(first), list(refit)) if moments else (list(res), list(out))
 
     # ---- surface fit of cameras batches, drift per camera (include/ssd_hip.h, DESIGN.md section 7e)
@@ -983,15 +992,15 @@ class Detector:
                                                        INPUT_DEPTH16 if depth else INPUT_VERTICES, res, mom if moments else None, int(min_points), out))
         return (list(res), list(out), list(mom)) if moments else (list(res), list(out))
 
-    def camera_drift(self, frames, camera_of_frame, depth=False, min_points=2000, passes=0, k_sigma=2.5, gate_min=0.0):
+    def camera_drift(self, frames, camera_of_frame, depth=False, min_points=2000, passes=0, k_sigma=2.5, gate_min=0.0, device_gates=False):
         """process_host_cameras_surfaces, then camera_drift_fold of its moments against the handle's camera table
         -> (list of FrameResult, list of CameraDrift, one per camera of the table).  passes >= 1: the fold of the last refit pass's
-        records of process_host_cameras_surfaces_refit(passes, k_sigma, gate_min) instead of the first pass's"""
+        records of process_host_cameras_surfaces_refit(passes, k_sigma, gate_min, device_gates) instead of the first pass's"""
         if not getattr(self, "_cameras", None):
             raise SsdError("camera_drift: the handle has no camera table (set_cameras)")
         if passes:
             res, _, _, mom = self.process_host_cameras_surfaces_refit(frames, camera_of_frame, depth=depth, k_sigma=k_sigma, gate_min=gate_min,
-                                                                      passes=passes, moments=True)
+                                                                      passes=passes, moments=True, device_gates=device_gates)
         else:
             res, _, mom = self.process_host_cameras_surfaces(frames, camera_of_frame, depth=depth, moments=True)
         return res, camera_drift_fold(mom, camera_of_frame, self._cameras, min_points=min_points)
@@ -1010,10 +1019,10 @@ class Detector:
                                                        INPUT_DEPTH16 if depth else INPUT_VERTICES, arr, C.c_void_p(d_moments)))
 
     def process_host_cameras_surfaces_refit(self, frames, camera_of_frame, depth=False, min_points=200, k_sigma=2.5, gate_min=0.0, passes=1,
-                                            moments=False):
+                                            moments=False, device_gates=False):
         """ssd_process_host_cameras_surfaces_refit: process_host_surfaces_refit with one camera index per frame
         -> (list of FrameResult, list of FrameSurfaces of the last refit pass), with moments=True also the lists of FrameMoments of
-        the first pass and of the last refit pass"""
+        the first pass and of the last refit pass.  device_gates=True: ssd_process_host_cameras_surfaces_refit_device"""
         a = np.ascontiguousarray(frames, dtype=np.uint16 if depth else np.float32) if not isinstance(frames, PinnedArray) else frames.array
         per = self.cfg.width * self.cfg.height * (1 if depth else 3)
         n = a.size // per
@@ -1021,11 +1030,34 @@ class Detector:
             raise SsdError("process_host_cameras_surfaces_refit: array does not hold whole frames")
         idx = self._camera_index(camera_of_frame, n)
         res, first, refit, out = (FrameResult * n)(), (FrameMoments * n)(), (FrameMoments * n)(), (FrameSurfaces * n)()
-        _check(lib().ssd_process_host_cameras_surfaces_refit(self._h, a.ctypes.data_as(C.c_void_p), n, idx.ctypes.data_as(C.POINTER(C.c_uint16)),
-                                                             INPUT_DEPTH16 if depth else INPUT_VERTICES, res, first if moments else None,
-                                                             refit if moments else None, int(min_points), float(k_sigma), float(gate_min),
-                                                             int(passes), out))
+        fn = lib().ssd_process_host_cameras_surfaces_refit_device if device_gates else lib().ssd_process_host_cameras_surfaces_refit
+        _check(fn(self._h, a.ctypes.data_as(C.c_void_p), n, idx.ctypes.data_as(C.POINTER(C.c_uint16)), INPUT_DEPTH16 if depth else INPUT_VERTICES, res,
+                  first if moments else None, refit if moments else None, int(min_points), float(k_sigma), float(gate_min), int(passes), out))
         return (list(res), list(out), list(first), list(refit)) if moments else (list(res), list(out))
+
+    # ---- surface gates on the device (include/ssd_hip.h)
+    def enqueue_surface_gates(self, d_moments, nframes, d_gates, min_points=200, k_sigma=2.5, gate_min=0.0, stream=None):
+        """ssd_enqueue_surface_gates: nframes FrameMoments in device memory -> nframes FrameGates in device memory (frame i's = what
+        surface_gates_from_moments gives for record i, byte for byte), on `stream`, without synchronising"""
+        _check(lib().ssd_enqueue_surface_gates(self._h, C.c_void_p(d_moments), nframes, C.c_void_p(stream or 0), int(min_points), float(k_sigma),
+                                               float(gate_min), C.c_void_p(d_gates)))
+
+    def enqueue_surface_refit_device(self, d_ptr, nframes, d_prev, d_moments, min_points=200, k_sigma=2.5, gate_min=0.0, depth=False,
+                                     stride_bytes=None, stream=None):
+        """ssd_enqueue_surface_refit_device: enqueue_surface_refit whose gates are made on the device from the nframes FrameMoments at
+        d_prev (device memory: the first pass's records, or a refit pass's - d_prev == d_moments is allowed), no host copy, no wait"""
+        frame = self.cfg.width * self.cfg.height * (2 if depth else 12)
+        _check(lib().ssd_enqueue_surface_refit_device(self._h, C.c_void_p(d_ptr), stride_bytes or frame, nframes, C.c_void_p(stream or 0),
+                                                      INPUT_DEPTH16 if depth else INPUT_VERTICES, C.c_void_p(d_prev), int(min_points),
+                                                      float(k_sigma), float(gate_min), C.c_void_p(d_moments)))
+
+    def enqueue_cameras_surface_refit_device(self, d_ptr, nframes, d_prev, d_moments, min_points=200, k_sigma=2.5, gate_min=0.0, depth=False,
+                                             stride_bytes=None, stream=None):
+        """ssd_enqueue_cameras_surface_refit_device: enqueue_surface_refit_device behind the handle's last whole CAMERAS enqueue"""
+        frame = self.cfg.width * self.cfg.height * (2 if depth else 12)
+        _check(lib().ssd_enqueue_cameras_surface_refit_device(self._h, C.c_void_p(d_ptr), stride_bytes or frame, nframes, C.c_void_p(stream or 0),
+                                                              INPUT_DEPTH16 if depth else INPUT_VERTICES, C.c_void_p(d_prev), int(min_points),
+                                                              float(k_sigma), float(gate_min), C.c_void_p(d_moments)))
 
     def surface_moments_time_ms(self, back=0):
         """Device time of the surface-moments pass of the enqueue `back` calls ago (0.0: it gathered none); timing must be on."""

@@ -10,6 +10,7 @@
 #include "ssd_prexy.h"
 #include "ssd_ground.h"
 #include "ssd_refit.h"
+#include "ssd_solve.h"
 
 #include <algorithm>
 #include <charconv>
@@ -2004,100 +2005,8 @@ int ssd_ground_moments_host(const ssd_config *cfg, const ssd_camera *prior, int 
   return SSD_OK;
 }
 
-/* eigenvalues (ascending) and eigenvectors (columns of v) of a symmetric 3 x 3 matrix: cyclic Jacobi */
-static void jacobi3(double a[3][3], double lambda[3], double v[3][3])
-{
-  for(int i = 0; i < 3; i++)
-    for(int j = 0; j < 3; j++)
-      v[i][j] = i == j ? 1.0 : 0.0;
-  for(int sweep = 0; sweep < 64; sweep++)
-  {
-    const double off = std::fabs(a[0][1]) + std::fabs(a[0][2]) + std::fabs(a[1][2]);
-    if(off == 0.0)
-      break;
-    for(int p = 0; p < 2; p++)
-      for(int q = p + 1; q < 3; q++)
-      {
-        if(a[p][q] == 0.0)
-          continue;
-        const double theta = (a[q][q] - a[p][p]) / (2.0 * a[p][q]);
-        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
-        const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
-        const double app = a[p][p], aqq = a[q][q], apq = a[p][q];
-        a[p][p] = app - t * apq;
-        a[q][q] = aqq + t * apq;
-        a[p][q] = a[q][p] = 0.0;
-        const int r = 3 - p - q;
-        const double arp = a[r][p], arq = a[r][q];
-        a[r][p] = a[p][r] = c * arp - s * arq;
-        a[r][q] = a[q][r] = s * arp + c * arq;
-        for(int k = 0; k < 3; k++)
-        {
-          const double vkp = v[k][p], vkq = v[k][q];
-          v[k][p] = c * vkp - s * vkq;
-          v[k][q] = s * vkp + c * vkq;
-        }
-      }
-  }
-  int order[3] = { 0, 1, 2 };
-  std::sort(order, order + 3, [&](int i, int j) { return a[i][i] < a[j][j]; });
-  double vv[3][3];
-  for(int k = 0; k < 3; k++)
-  {
-    lambda[k] = a[order[k]][order[k]];
-    for(int i = 0; i < 3; i++)
-      vv[i][k] = v[i][order[k]];
-  }
-  std::memcpy(v, vv, sizeof(vv));
-}
-
-/* The core of the solve, shared by the ground fit and the surface fit: moments -> the centred scatter N SS - S (x) S, exact in 128-bit
- * integers, converted once to double and scaled to m^2; its eigenvalues ascending (cyclic Jacobi); n0 = the unit eigenvector of
- * lambda_min signed away from the camera (dist = n0 . centroid >= 0).  Returns FEW, DEGENERATE (the points determine no plane) or OK. */
-struct PlaneOfMoments
-{
-  double lambda[3], n0[3], centroid[3], dist;
-};
-
-static int plane_of_moments(const ssd_ground_moments *m, int min_points, PlaneOfMoments &pl)
-{
-  const int64_t n = m->n;
-  if(n < (min_points > 1 ? min_points : 1))
-    return SSD_GF_FEW;
-  /* the centred scatter N SS - S (x) S, exact: N < 2^23 and SS < 2^63, |S| < 2^43, so both products lie below 2^86 */
-  typedef __int128 i128;
-  static const int at[3][3] = { { 0, 1, 2 }, { 1, 3, 4 }, { 2, 4, 5 } };
-  const double scale = 1.0 / (static_cast<double>(n) * static_cast<double>(n) * kGroundScale * kGroundScale);
-  double c[3][3], v[3][3];
-  double (&lambda)[3] = pl.lambda;
-  for(int i = 0; i < 3; i++)
-    for(int j = 0; j < 3; j++)
-      c[i][j] = static_cast<double>(static_cast<i128>(n) * m->ss[at[i][j]] - static_cast<i128>(m->s[i]) * m->s[j]) * scale;   /* m^2 */
-  jacobi3(c, lambda, v);
-  /* an eigenvalue at the rounding level of the largest one is zero (collinear points leave +-1e-17 lambda_max, of either sign) */
-  const double zero = 64.0 * 2.220446049250313e-16 * lambda[2];
-  const double lmin = lambda[0] > zero ? lambda[0] : 0.0, lmid = lambda[1] > zero ? lambda[1] : 0.0;
-  if(!(lmid > 0.0) || lmid < SSD_GF_PLANARITY * lmin)
-    return SSD_GF_DEGENERATE;
-  double (&n0)[3] = pl.n0;
-  n0[0] = v[0][0]; n0[1] = v[1][0]; n0[2] = v[2][0];
-  const double rn = 1.0 / std::sqrt(n0[0] * n0[0] + n0[1] * n0[1] + n0[2] * n0[2]);
-  double (&centroid)[3] = pl.centroid;
-  for(int i = 0; i < 3; i++)
-  {
-    n0[i] *= rn;
-    centroid[i] = static_cast<double>(m->s[i]) / (static_cast<double>(n) * kGroundScale);
-  }
-  double dist = n0[0] * centroid[0] + n0[1] * centroid[1] + n0[2] * centroid[2];
-  if(dist < 0.0)
-  {
-    dist = -dist;
-    for(int i = 0; i < 3; i++)
-      n0[i] = -n0[i];
-  }
-  pl.dist = dist;
-  return SSD_GF_OK;
-}
+/* jacobi3, PlaneOfMoments and plane_of_moments - the core of the solve, shared by the ground fit, the surface fit, the riser fit and
+ * the gates - are ssd_solve.h's: the device runs the same text (k_surface_gates) */
 
 int ssd_ground_fit_solve(const ssd_ground_moments *m, const ssd_calibration *prior, int min_points, ssd_ground_fit *out)
 {
@@ -2305,17 +2214,7 @@ int ssd_surface_gates_from_moments(const ssd_frame_moments *m, int min_points, d
   std::memset(out, 0, sizeof(*out));
   out->n_surfaces = m->n_surfaces;
   for(int k = 0; k < m->n_surfaces; k++)
-  {
-    PlaneOfMoments pl;
-    if(plane_of_moments(&m->s[k].m, min_points, pl) != SSD_GF_OK)
-      continue;                                  /* an all-zero gate: the surface gathers nothing */
-    ssd_plane_gate &g = out->g[k];
-    for(int i = 0; i < 3; i++)
-      g.n[i] = pl.n0[i];
-    g.dist = pl.dist;
-    const double rms = std::sqrt(pl.lambda[0] > 0.0 ? pl.lambda[0] : 0.0), wide = k_sigma * rms;
-    g.gate = wide > gate_min ? wide : gate_min;
-  }
+    out->g[k] = gate_of_moments(&m->s[k].m, min_points, k_sigma, gate_min);      /* ssd_solve.h; all zero unless the fit is OK */
   return SSD_OK;
 }
 
@@ -2352,14 +2251,28 @@ static int refit_prepare(ssd_handle *h)
   return SSD_OK;
 }
 
-/* both refit entry points: `cameras` = behind a whole cameras batch (wholeKind 2), under the table and the index that batch left in its
+/* where a pass's gates come from */
+struct GateSource
+{
+  const ssd_frame_gates *host;                   /* the caller's gates, host memory: copied through the pinned buffer - or */
+  const ssd_frame_moments *dPrev;                /* records in device memory, solved by k_surface_gates on the pass's stream (section 7i) */
+  int minPoints;                                 /* ... under this rule */
+  double kSigma, gateMin;
+};
+
+/* all refit entry points: `cameras` = behind a whole cameras batch (wholeKind 2), under the table and the index that batch left in its
  * workspace; otherwise behind a whole run under the handle's calibration (wholeKind 1) */
 static int refit_enqueue_impl(ssd_handle *h, const char *who, bool cameras, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream,
-                              int input, const ssd_frame_gates *gates, ssd_frame_moments *d_out)
+                              int input, const GateSource &gates, ssd_frame_moments *d_out)
 {
   const std::string me(who);
-  if(!h || !d_frames || !gates || !d_out)
+  if(!h || !d_frames || (!gates.host && !gates.dPrev) || !d_out)
     return fail(SSD_E_ARG, me + ": null argument");
+  if(gates.dPrev)
+  {
+    const int rule = check_gate_rule(who, gates.kSigma, gates.gateMin);
+    if(rule) return rule;
+  }
   if(input != SSD_INPUT_VERTICES && input != SSD_INPUT_DEPTH16)
     return fail(SSD_E_ARG, me + ": input must be SSD_INPUT_VERTICES or SSD_INPUT_DEPTH16");
   const bool depthInput = input == SSD_INPUT_DEPTH16;
@@ -2411,15 +2324,26 @@ static int refit_enqueue_impl(ssd_handle *h, const char *who, bool cameras, cons
   }
   if(h->refitHaveLast)
   {
-    HIP_TRY(hipEventSynchronize(h->refitGatesCopied));              /* the pinned gates of the previous call have gone over */
+    if(gates.host)
+      HIP_TRY(hipEventSynchronize(h->refitGatesCopied));            /* the pinned gates of the previous call have gone over */
     /* the device gates are one set: on another stream than the previous pass's (another workspace's, or the caller changed streams) this
      * call goes behind that pass, which still reads them - so refits run in the order of their calls, whatever workspace they follow */
     if(s != h->refitLastStream)
       HIP_TRY(hipStreamWaitEvent(s, h->refitDone, 0));
   }
-  std::memcpy(h->hRefitGates, gates, sizeof(ssd_frame_gates) * static_cast<size_t>(nframes));
-  HIP_TRY(hipMemcpyAsync(h->dRefitGates, h->hRefitGates, sizeof(ssd_frame_gates) * static_cast<size_t>(nframes), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipEventRecord(h->refitGatesCopied, s));
+  if(gates.host)
+  {
+    std::memcpy(h->hRefitGates, gates.host, sizeof(ssd_frame_gates) * static_cast<size_t>(nframes));
+    HIP_TRY(hipMemcpyAsync(h->dRefitGates, h->hRefitGates, sizeof(ssd_frame_gates) * static_cast<size_t>(nframes), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(h->refitGatesCopied, s));
+  }
+  else
+  {
+    /* the gates on the device, in front of the zeroing (d_prev may be d_out): no copy, no wait; the pass's time includes the kernel */
+    if(timing) HIP_TRY(hipEventRecord(h->evRefit[0], s));
+    launch_surface_gates(gates.dPrev, nframes, gates.minPoints, gates.kSigma, gates.gateMin, h->dRefitGates, s);
+    HIP_TRY(hipGetLastError());
+  }
   h->refitHaveLast = true;
   h->refitLastStream = s;
   const Params &P = h->P;
@@ -2427,7 +2351,7 @@ static int refit_enqueue_impl(ssd_handle *h, const char *who, bool cameras, cons
   const size_t strideFloats = depthInput ? frame_stride_bytes / 2 : frame_stride_bytes / 4;
   const DepthSrc depthSrc{ h->dDepthMaps, h->dDepthMaps ? h->dDepthMaps + P.W : nullptr, h->intr.depth_units, P.W, P.H, depth_row_magic(P.W, P.H) };
   const int chunk = choose_chunk(h->tune, P.nPoints, nframes);      /* the first pass's */
-  if(timing) HIP_TRY(hipEventRecord(h->evRefit[0], s));
+  if(timing && gates.host) HIP_TRY(hipEventRecord(h->evRefit[0], s));
   HIP_TRY(hipMemsetAsync(d_out, 0, sizeof(ssd_frame_moments) * static_cast<size_t>(nframes), s));
   if(cameras)                                  /* the table as the batch read it, the index where the batch's own copy left it */
     launch_surface_refit_cams(xyz, strideFloats, P, L.dState, L.dTileMasks, h->tileMaskStride, nframes, chunk, depthInput ? &depthSrc : nullptr,
@@ -2448,13 +2372,47 @@ static int refit_enqueue_impl(ssd_handle *h, const char *who, bool cameras, cons
 int ssd_enqueue_surface_refit(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream,
                               int input, const ssd_frame_gates *gates, ssd_frame_moments *d_out)
 {
-  return refit_enqueue_impl(h, "ssd_enqueue_surface_refit", false, d_frames, frame_stride_bytes, nframes, stream, input, gates, d_out);
+  return refit_enqueue_impl(h, "ssd_enqueue_surface_refit", false, d_frames, frame_stride_bytes, nframes, stream, input,
+                            GateSource{ gates, nullptr, 0, 0.0, 0.0 }, d_out);
 }
 
 int ssd_enqueue_cameras_surface_refit(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream,
                                       int input, const ssd_frame_gates *gates, ssd_frame_moments *d_out)
 {
-  return refit_enqueue_impl(h, "ssd_enqueue_cameras_surface_refit", true, d_frames, frame_stride_bytes, nframes, stream, input, gates, d_out);
+  return refit_enqueue_impl(h, "ssd_enqueue_cameras_surface_refit", true, d_frames, frame_stride_bytes, nframes, stream, input,
+                            GateSource{ gates, nullptr, 0, 0.0, 0.0 }, d_out);
+}
+
+/* ---- surface gates on the device (include/ssd_hip.h) ---------------------------------------------------- */
+
+int ssd_enqueue_surface_gates(ssd_handle *h, const ssd_frame_moments *d_moments, int nframes, void *stream, int min_points, double k_sigma,
+                              double gate_min, ssd_frame_gates *d_gates)
+{
+  if(!h || !d_moments || !d_gates)
+    return fail(SSD_E_ARG, "ssd_enqueue_surface_gates: null argument");
+  if(nframes < 1 || nframes > h->F)
+    return fail(SSD_E_ARG, "ssd_enqueue_surface_gates: nframes must lie in 1 .. max_frames_per_batch");
+  const int rc = check_gate_rule("ssd_enqueue_surface_gates", k_sigma, gate_min);
+  if(rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  launch_surface_gates(d_moments, nframes, min_points, k_sigma, gate_min, d_gates, static_cast<hipStream_t>(stream));
+  HIP_TRY(hipGetLastError());
+  return SSD_OK;
+}
+
+int ssd_enqueue_surface_refit_device(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream, int input,
+                                     const ssd_frame_moments *d_prev, int min_points, double k_sigma, double gate_min, ssd_frame_moments *d_out)
+{
+  return refit_enqueue_impl(h, "ssd_enqueue_surface_refit_device", false, d_frames, frame_stride_bytes, nframes, stream, input,
+                            GateSource{ nullptr, d_prev, min_points, k_sigma, gate_min }, d_out);
+}
+
+int ssd_enqueue_cameras_surface_refit_device(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream, int input,
+                                             const ssd_frame_moments *d_prev, int min_points, double k_sigma, double gate_min,
+                                             ssd_frame_moments *d_out)
+{
+  return refit_enqueue_impl(h, "ssd_enqueue_cameras_surface_refit_device", true, d_frames, frame_stride_bytes, nframes, stream, input,
+                            GateSource{ nullptr, d_prev, min_points, k_sigma, gate_min }, d_out);
 }
 
 int ssd_fetch_surface_refit(ssd_handle *h, void *)
@@ -2487,7 +2445,7 @@ int ssd_get_surface_refit_time(ssd_handle *h, float *ms)
  * part of the index, its refit passes under the cameras, each frame solved against its own camera */
 static int process_host_refit_impl(ssd_handle *h, const char *who, const void *frames, int nframes, const uint16_t *camOf, int input,
                                    ssd_frame_result *results, ssd_frame_moments *first, ssd_frame_moments *refit, int min_points,
-                                   double k_sigma, double gate_min, int passes, ssd_frame_surfaces *out)
+                                   double k_sigma, double gate_min, int passes, ssd_frame_surfaces *out, bool deviceGates)
 {
   if(passes < 1 || passes > 4)
     return fail(SSD_E_ARG, std::string(who) + ": passes must lie in 1 .. 4");
@@ -2543,25 +2501,50 @@ static int process_host_refit_impl(ssd_handle *h, const char *who, const void *f
     HIP_TRY(hipStreamWaitEvent(h->ingestCompute, h->ingestCopied[k], 0));
     rc = enqueue_impl(h, h->ingestBuf[k], devFrameBytes, n, h->ingestCompute, SSD_STAGE_ALL, depth, nullptr, 0, camOf ? camOf + done : nullptr, dFirst);
     if(rc) return rc;
-    rc = ssd_fetch_back(h, results + done, n, 0);
-    if(rc) return rc;
-    rc = records(dFirst, n);
-    if(rc) return rc;
-    if(first)
-      std::memcpy(first + done, cur.data(), sizeof(ssd_frame_moments) * static_cast<size_t>(n));
-    for(int pass = 0; pass < passes; pass++)
+    if(deviceGates)
     {
-      for(int i = 0; i < n; i++)
+      /* section 7i: the passes go out behind the enqueue with no host step between - the first gated by dFirst's planes into dRefit,
+       * the later ones in place.  Then the slice's results and, behind the last pass on its stream, its records */
+      for(int pass = 0; pass < passes; pass++)
       {
-        rc = ssd_surface_gates_from_moments(&cur[i], min_points, k_sigma, gate_min, &gates[i]);
+        rc = refit_enqueue_impl(h, who, camOf != nullptr, h->ingestBuf[k], devFrameBytes, n, h->ingestCompute, input,
+                                GateSource{ nullptr, pass == 0 ? dFirst : dRefit, min_points, k_sigma, gate_min }, dRefit);
         if(rc) return rc;
       }
-      rc = refit_enqueue_impl(h, who, camOf != nullptr, h->ingestBuf[k], devFrameBytes, n, h->ingestCompute, input, gates.data(), dRefit);
+      rc = ssd_fetch_back(h, results + done, n, 0);
       if(rc) return rc;
-      rc = ssd_fetch_surface_refit(h, nullptr);
-      if(rc) return rc;
+      if(first)
+      {
+        rc = records(dFirst, n);
+        if(rc) return rc;
+        std::memcpy(first + done, cur.data(), sizeof(ssd_frame_moments) * static_cast<size_t>(n));
+      }
       rc = records(dRefit, n);
       if(rc) return rc;
+    }
+    else
+    {
+      rc = ssd_fetch_back(h, results + done, n, 0);
+      if(rc) return rc;
+      rc = records(dFirst, n);
+      if(rc) return rc;
+      if(first)
+        std::memcpy(first + done, cur.data(), sizeof(ssd_frame_moments) * static_cast<size_t>(n));
+      for(int pass = 0; pass < passes; pass++)
+      {
+        for(int i = 0; i < n; i++)
+        {
+          rc = ssd_surface_gates_from_moments(&cur[i], min_points, k_sigma, gate_min, &gates[i]);
+          if(rc) return rc;
+        }
+        rc = refit_enqueue_impl(h, who, camOf != nullptr, h->ingestBuf[k], devFrameBytes, n, h->ingestCompute, input,
+                                GateSource{ gates.data(), nullptr, 0, 0.0, 0.0 }, dRefit);
+        if(rc) return rc;
+        rc = ssd_fetch_surface_refit(h, nullptr);
+        if(rc) return rc;
+        rc = records(dRefit, n);
+        if(rc) return rc;
+      }
     }
     if(refit)
       std::memcpy(refit + done, cur.data(), sizeof(ssd_frame_moments) * static_cast<size_t>(n));
@@ -2587,7 +2570,21 @@ int ssd_process_host_surfaces_refit(ssd_handle *h, const void *frames, int nfram
   if(input == SSD_INPUT_DEPTH16 && !h->haveIntr)
     return fail(SSD_E_ARG, "ssd_process_host_surfaces_refit: call ssd_set_intrinsics first");
   return process_host_refit_impl(h, "ssd_process_host_surfaces_refit", frames, nframes, nullptr, input, results, first, refit, min_points, k_sigma,
-                                 gate_min, passes, out);
+                                 gate_min, passes, out, false);
+}
+
+int ssd_process_host_surfaces_refit_device(ssd_handle *h, const void *frames, int nframes, int input, ssd_frame_result *results,
+                                           ssd_frame_moments *first, ssd_frame_moments *refit, int min_points, double k_sigma, double gate_min,
+                                           int passes, ssd_frame_surfaces *out)
+{
+  if(!h || !frames || !results || !out || nframes < 1)
+    return fail(SSD_E_ARG, "ssd_process_host_surfaces_refit_device: bad argument");
+  if(input != SSD_INPUT_VERTICES && input != SSD_INPUT_DEPTH16)
+    return fail(SSD_E_ARG, "ssd_process_host_surfaces_refit_device: input must be SSD_INPUT_VERTICES or SSD_INPUT_DEPTH16");
+  if(input == SSD_INPUT_DEPTH16 && !h->haveIntr)
+    return fail(SSD_E_ARG, "ssd_process_host_surfaces_refit_device: call ssd_set_intrinsics first");
+  return process_host_refit_impl(h, "ssd_process_host_surfaces_refit_device", frames, nframes, nullptr, input, results, first, refit, min_points,
+                                 k_sigma, gate_min, passes, out, true);
 }
 
 /* ---- surface fit of cameras batches and drift per camera (include/ssd_hip.h) ---------------------------- */
@@ -2637,7 +2634,19 @@ int ssd_process_host_cameras_surfaces_refit(ssd_handle *h, const void *frames, i
   int rc = check_cameras(h, "ssd_process_host_cameras_surfaces_refit", camera_of_frame, nframes, input);
   if(rc) return rc;
   return process_host_refit_impl(h, "ssd_process_host_cameras_surfaces_refit", frames, nframes, camera_of_frame, input, results, first, refit,
-                                 min_points, k_sigma, gate_min, passes, out);
+                                 min_points, k_sigma, gate_min, passes, out, false);
+}
+
+int ssd_process_host_cameras_surfaces_refit_device(ssd_handle *h, const void *frames, int nframes, const uint16_t *camera_of_frame, int input,
+                                                   ssd_frame_result *results, ssd_frame_moments *first, ssd_frame_moments *refit, int min_points,
+                                                   double k_sigma, double gate_min, int passes, ssd_frame_surfaces *out)
+{
+  if(!h || !frames || !results || !out || nframes < 1)
+    return fail(SSD_E_ARG, "ssd_process_host_cameras_surfaces_refit_device: bad argument");
+  int rc = check_cameras(h, "ssd_process_host_cameras_surfaces_refit_device", camera_of_frame, nframes, input);
+  if(rc) return rc;
+  return process_host_refit_impl(h, "ssd_process_host_cameras_surfaces_refit_device", frames, nframes, camera_of_frame, input, results, first, refit,
+                                 min_points, k_sigma, gate_min, passes, out, true);
 }
 
 /* host only: no handle, no device */

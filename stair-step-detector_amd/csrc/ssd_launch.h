@@ -61,6 +61,9 @@ void launch_riser_moments(const float *xyz, size_t strideFloats, const Params &P
                           ssd_frame_risers *out, ssd_frame_moments *moments, int nframes, int chunkPoints, const DepthSrc *depth, hipStream_t s, const CameraSel *cams = nullptr);
 
 /* the launchers of the cameras entry points (ssd_kernels_cams.hip): what launch_*(..., cams) hands a cameras batch to */
+/* k_surface_gates (ssd_kernels_solve.hip): rec[i] -> out[i] for nframes >= 1 records, both in device memory and not
+ * overlapping, on stream s; every byte of out[0 .. nframes) is written, nothing behind them */
+void launch_surface_gates(const ssd_frame_moments *rec, int nframes, int min_points, double k_sigma, double gate_min, ssd_frame_gates *out, hipStream_t s);
 void launch_predict_cams(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, int nframes, const DepthSrc *depth, int *fallback, int poolPlanes, int sabotage, hipStream_t s, const CameraSel &cams);
 void launch_hist_cams(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, uint2 *tileMasks, size_t tileMaskStride, int nframes, int chunkPoints, const DepthSrc *depth, unsigned long long *planeImg, hipStream_t s, const CameraSel &cams);
 void launch_peaks_cams(const Params &P, FrameState *st, int nframes, DebugFrame *dbg, int *fallback, hipStream_t s, const CameraSel &cams);
