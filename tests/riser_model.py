@@ -24,8 +24,9 @@ SIGMAS = (0.001, 0.003)
 OFFSET_FIX = float(1 << 40)
 
 
-def emitted(rec):
-    """the emitted surfaces in k_final's order: [(z, front-left x, y, front-right x, y)] in camera-dependent world coordinates"""
+def emitted(rec, limit=ob.MAX_STEPS):
+    """the emitted surfaces in k_final's order: [(z, front-left x, y, front-right x, y)] in camera-dependent world coordinates; limit:
+    the surfaces the record's maker can report (the oracle: all of them; a handle: SSD_MAX_STEPS, which shows on an overflowing frame)"""
     if (rec.status & ob.ST_THROW) or rec.first_valid_ind < 0:
         return []
     out = []
@@ -37,12 +38,12 @@ def emitted(rec):
         if pl.valid:
             q = list(pl.quad_world)
             out.append((pl.mean_z, q[0], q[1], q[2], q[3]))
-    return out[:ob.MAX_STEPS]
+    return out[:limit]
 
 
-def risers_of(cfg, rec):
+def risers_of(cfg, rec, limit=ob.MAX_STEPS):
     """-> ([dict(ox, oy, ux, uy, len, zLo, zHi)] per riser, riser_of_bin as an int array of n_bins entries, -1 = none)"""
-    surf = emitted(rec)
+    surf = emitted(rec, limit)
     n_bins = rec.n_bins
     recip = 1.0 / cfg.height_interval
     free = np.ones(n_bins, dtype=bool)                      # the bins of no plateau
@@ -67,12 +68,12 @@ def risers_of(cfg, rec):
     return out, of_bin
 
 
-def evidence(cfg, cal, rec, xyz, tol):
+def evidence(cfg, cal, rec, xyz, tol, limit=ob.MAX_STEPS):
     """-> (labels uint8 [W H]: i + 1 = evidence of riser i, s float64 [W H]: the point's signed distance from its riser's edge line)"""
     p = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
     labels = np.zeros(len(p), dtype=np.uint8)
     off = np.zeros(len(p), dtype=np.float64)
-    rs, of_bin = risers_of(cfg, rec)
+    rs, of_bin = risers_of(cfg, rec, limit)
     if not rs:
         return labels, off
     wx, wy, wz = world(cal, p)
@@ -92,9 +93,9 @@ def evidence(cfg, cal, rec, xyz, tol):
     return labels, off
 
 
-def riser_labels(cfg, cal, rec, xyz, tol):
+def riser_labels(cfg, cal, rec, xyz, tol, limit=ob.MAX_STEPS):
     """uint8 [W H]: label i + 1 = the point is evidence of riser i of the frame whose record is `rec`, 0 = of none"""
-    return evidence(cfg, cal, rec, xyz, tol)[0]
+    return evidence(cfg, cal, rec, xyz, tol, limit)[0]
 
 
 def counts_and_offsets(labels, off, n):
