@@ -1538,6 +1538,140 @@ static int ingest_prepare(ssd_handle *h, size_t sliceBytes)
   return SSD_OK;
 }
 
+/* The frames of a host batch: packed where the caller holds them, at devFrameBytes apart in a staging buffer.  The pipeline keeps a depth
+ * frame's device stride a multiple of 8 bytes (four elements; a vertex frame is one of 4 as it is); the ground fit's kernel loads 16 bytes
+ * wide, so there every frame starts on such a boundary. */
+struct HostFrames
+{
+  bool depth;
+  size_t srcFrameBytes, devFrameBytes;
+};
+enum FrameUser { kForPipeline, kForGroundFit };
+
+static HostFrames host_frames(const ssd_handle *h, int input, FrameUser user)
+{
+  const bool depth = input == SSD_INPUT_DEPTH16;
+  const size_t src = static_cast<size_t>(h->P.nPoints) * (depth ? 2 : 12);
+  const size_t align = user == kForGroundFit ? 16 : depth ? 8 : 4;
+  return HostFrames{ depth, src, (src + align - 1) / align * align };
+}
+
+/* the refusals of a cameras batch (include/ssd_hip.h), before anything is launched or copied */
+static int check_cameras(const ssd_handle *h, const char *who, const uint16_t *camOf, int nframes, int input)
+{
+  if(!camOf)
+    return fail(SSD_E_ARG, std::string(who) + ": null camera_of_frame");
+  if(input != SSD_INPUT_VERTICES && input != SSD_INPUT_DEPTH16)
+    return fail(SSD_E_ARG, std::string(who) + ": input must be SSD_INPUT_VERTICES or SSD_INPUT_DEPTH16");
+  if(h->camParams.empty())
+    return fail(SSD_E_ARG, std::string(who) + ": the handle has no camera table (ssd_set_cameras)");
+  for(int i = 0; i < nframes; i++)
+  {
+    if(camOf[i] >= h->camParams.size())
+      return fail(SSD_E_ARG, std::string(who) + ": frame " + std::to_string(i) + " names camera " + std::to_string(camOf[i]) + " of " + std::to_string(h->camParams.size()));
+    if(input == SSD_INPUT_DEPTH16 && !h->camHasIntr[camOf[i]])
+      return fail(SSD_E_ARG, std::string(who) + ": depth input of frame " + std::to_string(i) + " names camera " + std::to_string(camOf[i]) + ", which has no intrinsics");
+  }
+  return SSD_OK;
+}
+
+/* The refusals every ssd_process_*host* entry point begins with, before anything is launched or copied.  `pointers`: the handle, the frames
+ * and whatever else that entry point cannot do without are there.  Then what the frames are read under: the handle's calibration (depth
+ * needs its intrinsics), the camera table (check_cameras), or priors of the call's own, which the caller checks behind this. */
+enum HostCal { kHandleCal, kCameraTable, kOwnPriors };
+
+static int check_host_batch(const ssd_handle *h, const char *who, bool pointers, int nframes, int input, HostCal cal, const uint16_t *camOf = nullptr)
+{
+  if(!pointers || nframes < 1)
+    return fail(SSD_E_ARG, std::string(who) + ": bad argument");
+  if(cal == kCameraTable)
+    return check_cameras(h, who, camOf, nframes, input);
+  if(input != SSD_INPUT_VERTICES && input != SSD_INPUT_DEPTH16)
+    return fail(SSD_E_ARG, std::string(who) + ": input must be SSD_INPUT_VERTICES or SSD_INPUT_DEPTH16");
+  if(cal == kHandleCal && input == SSD_INPUT_DEPTH16 && !h->haveIntr)
+    return fail(SSD_E_ARG, std::string(who) + ": call ssd_set_intrinsics first");
+  return SSD_OK;
+}
+
+/* One host batch on its way through ingestBuf[2]: everything about getting slice c into buffer c & 1, nothing about what is done with it.
+ * stage(c) issues the copy on ingestCopy (the second half of a large slice on ingestCopy2) with ingestCopied / ingestCopied2 behind it;
+ * ready(c) makes ingestCompute wait for those; consumed(c, s) records ingestConsumed on the stream the slice's last reader ran on, and
+ * from slice 2 on stage() makes the copy streams wait for it before they write the buffer again.  A body calls stage(c) at the top of
+ * its own iteration - or one slice ahead, in front of a step that blocks -, then ready(c), its kernels, consumed(c, ...).  Between calls
+ * nothing is owed: every entry point returns with its last slice's results read, which is behind that slice's kernels. */
+struct SliceFeed
+{
+  ssd_handle *h;
+  HostFrames f;
+  const void *frames;
+  int nframes;
+  int slice = 0;                              /* frames per slice */
+  int staged = 0;                             /* slices whose copy has gone out */
+  bool split[2] = { false, false };           /* the slice in that buffer went over in two halves */
+
+  int prepare()
+  {
+    slice = h->F < kIngestFrames ? h->F : kIngestFrames;
+    return ingest_prepare(h, static_cast<size_t>(slice) * f.devFrameBytes);
+  }
+  int slices() const { return (nframes - 1) / slice + 1; }
+  int first(int c) const { return c * slice; }
+  int count(int c) const { return nframes - first(c) < slice ? nframes - first(c) : slice; }
+
+  /* slice c's copy; nothing if it has gone out already or the batch has no such slice */
+  int stage(int c)
+  {
+    if(c < staged || c >= slices())
+      return SSD_OK;
+    const int k = c & 1, n = count(c);
+    const unsigned char *src = static_cast<const unsigned char *>(frames) + static_cast<size_t>(first(c)) * f.srcFrameBytes;
+    /* A slice of 16 MB and more goes over in two halves on two copy streams: one copy of a pinned source runs on ONE copy engine, at 42 GB/s
+     * on the boxes of rounds 5 and 6, while the runtime's own staging of a pageable source reached 55 (bench.py: host_fed, both
+     * orders, two warm-up calls) - the pinned source was the slower one. */
+    const size_t bytes = static_cast<size_t>(n) * f.srcFrameBytes, half = (bytes / 2) & ~static_cast<size_t>(4095);
+    const bool packed = f.srcFrameBytes == f.devFrameBytes;
+    split[k] = packed && half >= (static_cast<size_t>(8) << 20);
+    if(c >= 2)
+    {
+      HIP_TRY(hipStreamWaitEvent(h->ingestCopy, h->ingestConsumed[k], 0));        /* the readers of slice c - 2 are through with this buffer */
+      if(split[k])
+        HIP_TRY(hipStreamWaitEvent(h->ingestCopy2, h->ingestConsumed[k], 0));
+    }
+    if(split[k])
+    {
+      HIP_TRY(hipMemcpyAsync(static_cast<unsigned char *>(h->ingestBuf[k]) + half, src + half, bytes - half, hipMemcpyHostToDevice, h->ingestCopy2));
+      HIP_TRY(hipEventRecord(h->ingestCopied2[k], h->ingestCopy2));
+    }
+    if(packed)
+      HIP_TRY(hipMemcpyAsync(h->ingestBuf[k], src, split[k] ? half : bytes, hipMemcpyHostToDevice, h->ingestCopy));
+    else
+      HIP_TRY(hipMemcpy2DAsync(h->ingestBuf[k], f.devFrameBytes, src, f.srcFrameBytes, f.srcFrameBytes, n, hipMemcpyHostToDevice, h->ingestCopy));
+    HIP_TRY(hipEventRecord(h->ingestCopied[k], h->ingestCopy));
+    staged = c + 1;
+    return SSD_OK;
+  }
+
+  /* slice c, staged before: its buffer, first frame and count, with ingestCompute behind its copy */
+  int ready(int c, const void *&buf, int &at, int &n)
+  {
+    const int k = c & 1;
+    if(split[k])
+      HIP_TRY(hipStreamWaitEvent(h->ingestCompute, h->ingestCopied2[k], 0));
+    HIP_TRY(hipStreamWaitEvent(h->ingestCompute, h->ingestCopied[k], 0));
+    buf = h->ingestBuf[k];
+    at = first(c);
+    n = count(c);
+    return SSD_OK;
+  }
+
+  /* whatever read slice c's buffer ends on stream s with what s holds now */
+  int consumed(int c, hipStream_t s)
+  {
+    HIP_TRY(hipEventRecord(h->ingestConsumed[c & 1], s));
+    return SSD_OK;
+  }
+};
+
 /* the labels of the host entry points: two device buffers of a slice's labels and the stream that copies them out */
 static int labels_prepare(ssd_handle *h, size_t sliceBytes)
 {
@@ -1567,96 +1701,91 @@ static int labels_prepare(ssd_handle *h, size_t sliceBytes)
   return SSD_OK;
 }
 
-static int process_host_impl(ssd_handle *h, const void *src, size_t srcFrameBytes, size_t devFrameBytes, int nframes,
-                             ssd_frame_result *results, bool depthInput, unsigned char *labels = nullptr, const uint16_t *camOf = nullptr,
-                             bool labelsAreMoments = false)
+/* What a slice leaves in labelStage[c & 1] beside its results, and where it goes: a byte per point for enqueue_impl's `labels`, or one
+ * ssd_frame_moments per frame for its `moments` - the same staging buffers, copy stream and events either way.  host == nullptr: nothing. */
+struct StagedOut
 {
-  /* labelsAreMoments: `labels` receives the slices' ssd_frame_moments instead (ssd_process_host_surfaces) - one record per frame where
-   * labels are a byte per point, through the same staging buffers, copy stream and events */
+  enum Kind { kLabels, kMoments } kind;
+  void *host;
+  size_t frameBytes;
+};
+static StagedOut staged_labels(const ssd_handle *h, uint8_t *labels)
+{
+  return StagedOut{ StagedOut::kLabels, labels, static_cast<size_t>(h->P.nPoints) };
+}
+static StagedOut staged_moments(ssd_frame_moments *moments)
+{
+  return StagedOut{ StagedOut::kMoments, moments, sizeof(ssd_frame_moments) };
+}
+
+/* a pinned buffer of one record per frame of a host batch (the device buffer holds one enqueue's), grown to nframes */
+extern "C++"
+{
+template<typename T>
+static int grow_pinned_batch(ssd_handle *h, T *&buf, int &cap, int nframes)
+{
+  if(cap >= nframes)
+    return SSD_OK;
+  HIP_TRY(hipStreamSynchronize(h->ingestCompute));
+  if(buf) (void)hipHostFree(buf);
+  buf = nullptr;
+  cap = 0;
+  HIP_TRY(hipHostMalloc(&buf, sizeof(T) * static_cast<size_t>(nframes), hipHostMallocDefault));
+  cap = nframes;
+  return SSD_OK;
+}
+}
+
+/* arguments checked by the callers (check_host_batch) */
+static int process_host_impl(ssd_handle *h, const void *frames, int nframes, int input, ssd_frame_result *results,
+                             const StagedOut &out = StagedOut{}, const uint16_t *camOf = nullptr)
+{
   HIP_TRY(hipSetDevice(h->device));
-  const int slice = h->F < kIngestFrames ? h->F : kIngestFrames;
-  int rc = ingest_prepare(h, static_cast<size_t>(slice) * devFrameBytes);
+  SliceFeed feed{ h, host_frames(h, input, kForPipeline), frames, nframes };
+  int rc = feed.prepare();
   if(rc) return rc;
-  const size_t labelBytes = labelsAreMoments ? sizeof(ssd_frame_moments) : static_cast<size_t>(h->P.nPoints);
-  if(labels)
+  if(out.host)
   {
-    rc = labels_prepare(h, static_cast<size_t>(slice) * labelBytes);
+    rc = labels_prepare(h, static_cast<size_t>(feed.slice) * out.frameBytes);
     if(rc) return rc;
   }
-  /* whatever path leaves this call, no copy into the caller's labels is still on its way afterwards */
+  /* whatever path leaves this call, no copy into the caller's memory is still on its way afterwards */
   struct CopiesDone
   {
     hipStream_t s;
     ~CopiesDone() { if(s) (void)hipStreamSynchronize(s); }
-  } copiesDone{ labels ? h->labelsCopy : nullptr };
-  /* slice `at` of `n` frames, enqueued `back` enqueues ago, from staging buffer kk to the caller's labels, behind its kernels */
-  auto copyLabels = [&](int kk, int at, int n, int back)
+  } copiesDone{ out.host ? h->labelsCopy : nullptr };
+  /* slice c, enqueued `back` enqueues ago, from its staging buffer to the caller's memory, behind its kernels */
+  auto copyOut = [&](int c, int back)
   {
     int r = ssd_stream_wait(h, back, h->labelsCopy);
     if(r) return r;
-    HIP_TRY(hipMemcpyAsync(labels + static_cast<size_t>(at) * labelBytes, h->labelStage[kk], static_cast<size_t>(n) * labelBytes,
-                           hipMemcpyDeviceToHost, h->labelsCopy));
-    HIP_TRY(hipEventRecord(h->labelsCopied[kk], h->labelsCopy));
+    HIP_TRY(hipMemcpyAsync(static_cast<unsigned char *>(out.host) + static_cast<size_t>(feed.first(c)) * out.frameBytes, h->labelStage[c & 1],
+                           static_cast<size_t>(feed.count(c)) * out.frameBytes, hipMemcpyDeviceToHost, h->labelsCopy));
+    HIP_TRY(hipEventRecord(h->labelsCopied[c & 1], h->labelsCopy));
     return SSD_OK;
   };
-  const bool risers = h->P.risers && h->dRisers;
-  if(risers && h->hRisersBatchCap < nframes)
+  const bool risers = h->P.risers && h->dRisers, riserMoments = risers && h->riserMoments && h->dRiserMoments;
+  if(risers)
+    rc = grow_pinned_batch(h, h->hRisersBatch, h->hRisersBatchCap, nframes);
+  if(!rc && riserMoments)
+    rc = grow_pinned_batch(h, h->hRiserMomentsBatch, h->hRiserMomentsBatchCap, nframes);
+  if(rc) return rc;
+  const int last = feed.slices() - 1;
+  for(int c = 0; c <= last; c++)
   {
-    /* the risers of the whole batch, slice by slice (the device buffer holds one enqueue's) */
-    HIP_TRY(hipStreamSynchronize(h->ingestCompute));
-    if(h->hRisersBatch) (void)hipHostFree(h->hRisersBatch);
-    h->hRisersBatch = nullptr;
-    h->hRisersBatchCap = 0;
-    HIP_TRY(hipHostMalloc(&h->hRisersBatch, sizeof(ssd_frame_risers) * static_cast<size_t>(nframes), hipHostMallocDefault));
-    h->hRisersBatchCap = nframes;
-  }
-  const bool riserMoments = risers && h->riserMoments && h->dRiserMoments;
-  if(riserMoments && h->hRiserMomentsBatchCap < nframes)
-  {
-    HIP_TRY(hipStreamSynchronize(h->ingestCompute));
-    if(h->hRiserMomentsBatch) (void)hipHostFree(h->hRiserMomentsBatch);
-    h->hRiserMomentsBatch = nullptr;
-    h->hRiserMomentsBatchCap = 0;
-    HIP_TRY(hipHostMalloc(&h->hRiserMomentsBatch, sizeof(ssd_frame_moments) * static_cast<size_t>(nframes), hipHostMallocDefault));
-    h->hRiserMomentsBatchCap = nframes;
-  }
-  const unsigned char *from = static_cast<const unsigned char *>(src);
-  int prevFrames = 0, prevAt = 0, c = 0;
-  for(int done = 0; done < nframes; c++)
-  {
-    const int n = nframes - done < slice ? nframes - done : slice;
     const int k = c & 1;
-    if(c >= 2)
-      HIP_TRY(hipStreamWaitEvent(h->ingestCopy, h->ingestConsumed[k], 0));        /* the kernels of slice c - 2 read this buffer */
-    /* A slice of 16 MB and more goes over in two halves on two copy streams: one copy of a pinned source runs on ONE copy engine, at 42 GB/s
-     * on the boxes of rounds 5 and 6, while the runtime's own staging of a pageable source reached 55 (bench.py: host_fed, both
-     * orders, two warm-up calls) - the pinned source was the slower one. */
-    bool split = false;
-    if(srcFrameBytes == devFrameBytes)
-    {
-      const size_t bytes = static_cast<size_t>(n) * srcFrameBytes, half = (bytes / 2) & ~static_cast<size_t>(4095);
-      split = half >= (static_cast<size_t>(8) << 20);
-      const unsigned char *at = from + static_cast<size_t>(done) * srcFrameBytes;
-      if(split)
-      {
-        if(c >= 2)
-          HIP_TRY(hipStreamWaitEvent(h->ingestCopy2, h->ingestConsumed[k], 0));
-        HIP_TRY(hipMemcpyAsync(static_cast<unsigned char *>(h->ingestBuf[k]) + half, at + half, bytes - half, hipMemcpyHostToDevice, h->ingestCopy2));
-        HIP_TRY(hipEventRecord(h->ingestCopied2[k], h->ingestCopy2));
-        HIP_TRY(hipStreamWaitEvent(h->ingestCompute, h->ingestCopied2[k], 0));
-      }
-      HIP_TRY(hipMemcpyAsync(h->ingestBuf[k], at, split ? half : bytes, hipMemcpyHostToDevice, h->ingestCopy));
-    }
-    else
-      HIP_TRY(hipMemcpy2DAsync(h->ingestBuf[k], devFrameBytes, from + static_cast<size_t>(done) * srcFrameBytes, srcFrameBytes, srcFrameBytes, n,
-                               hipMemcpyHostToDevice, h->ingestCopy));
-    HIP_TRY(hipEventRecord(h->ingestCopied[k], h->ingestCopy));
-    HIP_TRY(hipStreamWaitEvent(h->ingestCompute, h->ingestCopied[k], 0));
-    if(labels && c >= 2)
-      HIP_TRY(hipStreamWaitEvent(h->ingestCompute, h->labelsCopied[k], 0));      /* the labels of slice c - 2 have left this buffer */
-    rc = enqueue_impl(h, h->ingestBuf[k], devFrameBytes, n, h->ingestCompute, SSD_STAGE_ALL, depthInput,
-                      labels && !labelsAreMoments ? h->labelStage[k] : nullptr, labelBytes, camOf ? camOf + done : nullptr,     /* a slice takes its part of the index */
-                      labels && labelsAreMoments ? reinterpret_cast<ssd_frame_moments *>(h->labelStage[k]) : nullptr);
+    const void *buf;
+    int at, n;
+    rc = feed.stage(c);
+    if(!rc) rc = feed.ready(c, buf, at, n);
+    if(rc) return rc;
+    if(out.host && c >= 2)
+      HIP_TRY(hipStreamWaitEvent(h->ingestCompute, h->labelsCopied[k], 0));      /* what slice c - 2 staged has left this buffer */
+    rc = enqueue_impl(h, buf, feed.f.devFrameBytes, n, h->ingestCompute, SSD_STAGE_ALL, feed.f.depth,
+                      out.host && out.kind == StagedOut::kLabels ? h->labelStage[k] : nullptr, out.frameBytes,
+                      camOf ? camOf + at : nullptr,                                 /* a slice takes its part of the index */
+                      out.host && out.kind == StagedOut::kMoments ? reinterpret_cast<ssd_frame_moments *>(h->labelStage[k]) : nullptr);
     if(rc) return rc;
     /* "Consumed" is the end of the slice's kernels — on the stream they ran on (with several workspaces the lane's own; the
      * compute stream itself only orders a slice behind its copy, so the slices of a handle with several workspaces overlap
@@ -1666,35 +1795,31 @@ static int process_host_impl(ssd_handle *h, const void *src, size_t srcFrameByte
       /* the riser buffer is single (enqueues with risers on all run in the first workspace): its copy follows the slice */
       rc = ssd_stream_wait(h, 0, h->ingestCompute);
       if(rc) return rc;
-      HIP_TRY(hipMemcpyAsync(h->hRisersBatch + done, h->dRisers, sizeof(ssd_frame_risers) * n, hipMemcpyDeviceToHost, h->ingestCompute));
+      HIP_TRY(hipMemcpyAsync(h->hRisersBatch + at, h->dRisers, sizeof(ssd_frame_risers) * n, hipMemcpyDeviceToHost, h->ingestCompute));
       if(riserMoments)
-        HIP_TRY(hipMemcpyAsync(h->hRiserMomentsBatch + done, h->dRiserMoments, sizeof(ssd_frame_moments) * n, hipMemcpyDeviceToHost, h->ingestCompute));
-      HIP_TRY(hipEventRecord(h->ingestConsumed[k], h->ingestCompute));
+        HIP_TRY(hipMemcpyAsync(h->hRiserMomentsBatch + at, h->dRiserMoments, sizeof(ssd_frame_moments) * n, hipMemcpyDeviceToHost, h->ingestCompute));
     }
-    else
-      HIP_TRY(hipEventRecord(h->ingestConsumed[k], h->lane[h->lastLane].lastStream));
-    if(prevFrames)
+    rc = feed.consumed(c, risers ? h->ingestCompute : h->lane[h->lastLane].lastStream);
+    if(rc) return rc;
+    if(c >= 1)
     {
-      if(labels)
+      if(out.host)
       {
-        rc = copyLabels(k ^ 1, prevAt, prevFrames, 1);
+        rc = copyOut(c - 1, 1);
         if(rc) return rc;
       }
-      rc = ssd_fetch_back(h, results + prevAt, prevFrames, 1);
+      rc = ssd_fetch_back(h, results + feed.first(c - 1), feed.count(c - 1), 1);
       if(rc) return rc;
     }
-    prevFrames = n;
-    prevAt = done;
-    done += n;
   }
-  if(labels)
+  if(out.host)
   {
-    rc = copyLabels((c - 1) & 1, prevAt, prevFrames, 0);
+    rc = copyOut(last, 0);
     if(rc) return rc;
   }
-  rc = ssd_fetch_back(h, results + prevAt, prevFrames, 0);
+  rc = ssd_fetch_back(h, results + feed.first(last), feed.count(last), 0);
   if(rc) return rc;
-  if(labels)
+  if(out.host)
     HIP_TRY(hipStreamSynchronize(h->labelsCopy));
   h->hRisersBatchFrames = risers ? nframes : 0;
   h->hRiserMomentsBatchFrames = riserMoments ? nframes : 0;
@@ -1703,38 +1828,26 @@ static int process_host_impl(ssd_handle *h, const void *src, size_t srcFrameByte
 
 int ssd_process_host(ssd_handle *h, const float *xyz, int nframes, ssd_frame_result *results)
 {
-  if(!h || !xyz || !results || nframes < 1)
-    return fail(SSD_E_ARG, "ssd_process_host: bad argument");
-  const size_t frameBytes = static_cast<size_t>(h->P.nPoints) * 12;
-  return process_host_impl(h, xyz, frameBytes, frameBytes, nframes, results, false);
+  const int rc = check_host_batch(h, "ssd_process_host", h && xyz && results, nframes, SSD_INPUT_VERTICES, kHandleCal);
+  return rc ? rc : process_host_impl(h, xyz, nframes, SSD_INPUT_VERTICES, results);
 }
 
 int ssd_process_depth_host(ssd_handle *h, const uint16_t *depth, int nframes, ssd_frame_result *results)
 {
-  if(!h || !depth || !results || nframes < 1)
-    return fail(SSD_E_ARG, "ssd_process_depth_host: bad argument");
-  if(!h->haveIntr)
-    return fail(SSD_E_ARG, "ssd_process_depth_host: call ssd_set_intrinsics first");
-  const size_t frameElems = (static_cast<size_t>(h->P.nPoints) + 3) / 4 * 4;       /* device stride kept a multiple of 8 bytes */
-  return process_host_impl(h, depth, static_cast<size_t>(h->P.nPoints) * 2, frameElems * 2, nframes, results, true);
+  const int rc = check_host_batch(h, "ssd_process_depth_host", h && depth && results, nframes, SSD_INPUT_DEPTH16, kHandleCal);
+  return rc ? rc : process_host_impl(h, depth, nframes, SSD_INPUT_DEPTH16, results);
 }
 
 int ssd_process_host_labels(ssd_handle *h, const float *xyz, int nframes, ssd_frame_result *results, uint8_t *labels)
 {
-  if(!h || !xyz || !results || !labels || nframes < 1)
-    return fail(SSD_E_ARG, "ssd_process_host_labels: bad argument");
-  const size_t frameBytes = static_cast<size_t>(h->P.nPoints) * 12;
-  return process_host_impl(h, xyz, frameBytes, frameBytes, nframes, results, false, labels);
+  const int rc = check_host_batch(h, "ssd_process_host_labels", h && xyz && results && labels, nframes, SSD_INPUT_VERTICES, kHandleCal);
+  return rc ? rc : process_host_impl(h, xyz, nframes, SSD_INPUT_VERTICES, results, staged_labels(h, labels));
 }
 
 int ssd_process_depth_host_labels(ssd_handle *h, const uint16_t *depth, int nframes, ssd_frame_result *results, uint8_t *labels)
 {
-  if(!h || !depth || !results || !labels || nframes < 1)
-    return fail(SSD_E_ARG, "ssd_process_depth_host_labels: bad argument");
-  if(!h->haveIntr)
-    return fail(SSD_E_ARG, "ssd_process_depth_host_labels: call ssd_set_intrinsics first");
-  const size_t frameElems = (static_cast<size_t>(h->P.nPoints) + 3) / 4 * 4;
-  return process_host_impl(h, depth, static_cast<size_t>(h->P.nPoints) * 2, frameElems * 2, nframes, results, true, labels);
+  const int rc = check_host_batch(h, "ssd_process_depth_host_labels", h && depth && results && labels, nframes, SSD_INPUT_DEPTH16, kHandleCal);
+  return rc ? rc : process_host_impl(h, depth, nframes, SSD_INPUT_DEPTH16, results, staged_labels(h, labels));
 }
 
 /* ---- per-frame calibration: the camera table (include/ssd_hip.h) ------------------------------- */
@@ -1879,25 +1992,6 @@ int ssd_camera_count(const ssd_handle *h)
   return h ? static_cast<int>(h->camParams.size()) : 0;
 }
 
-/* the refusals of a cameras batch, before anything is launched or copied */
-static int check_cameras(const ssd_handle *h, const char *who, const uint16_t *camOf, int nframes, int input)
-{
-  if(!camOf)
-    return fail(SSD_E_ARG, std::string(who) + ": null camera_of_frame");
-  if(input != SSD_INPUT_VERTICES && input != SSD_INPUT_DEPTH16)
-    return fail(SSD_E_ARG, std::string(who) + ": input must be SSD_INPUT_VERTICES or SSD_INPUT_DEPTH16");
-  if(h->camParams.empty())
-    return fail(SSD_E_ARG, std::string(who) + ": the handle has no camera table (ssd_set_cameras)");
-  for(int i = 0; i < nframes; i++)
-  {
-    if(camOf[i] >= h->camParams.size())
-      return fail(SSD_E_ARG, std::string(who) + ": frame " + std::to_string(i) + " names camera " + std::to_string(camOf[i]) + " of " + std::to_string(h->camParams.size()));
-    if(input == SSD_INPUT_DEPTH16 && !h->camHasIntr[camOf[i]])
-      return fail(SSD_E_ARG, std::string(who) + ": depth input of frame " + std::to_string(i) + " names camera " + std::to_string(camOf[i]) + ", which has no intrinsics");
-  }
-  return SSD_OK;
-}
-
 int ssd_enqueue_cameras(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream,
                         const uint16_t *camera_of_frame, int input, uint8_t *d_labels, size_t label_stride_bytes)
 {
@@ -1931,17 +2025,8 @@ int ssd_enqueue_cameras_surface_moments(ssd_handle *h, const void *d_frames, siz
 int ssd_process_host_cameras(ssd_handle *h, const void *frames, int nframes, const uint16_t *camera_of_frame, int input,
                              ssd_frame_result *results, uint8_t *labels)
 {
-  if(!h || !frames || !results || nframes < 1)
-    return fail(SSD_E_ARG, "ssd_process_host_cameras: bad argument");
-  const int rc = check_cameras(h, "ssd_process_host_cameras", camera_of_frame, nframes, input);
-  if(rc) return rc;
-  if(input == SSD_INPUT_DEPTH16)
-  {
-    const size_t frameElems = (static_cast<size_t>(h->P.nPoints) + 3) / 4 * 4;       /* as ssd_process_depth_host */
-    return process_host_impl(h, frames, static_cast<size_t>(h->P.nPoints) * 2, frameElems * 2, nframes, results, true, labels, camera_of_frame);
-  }
-  const size_t frameBytes = static_cast<size_t>(h->P.nPoints) * 12;
-  return process_host_impl(h, frames, frameBytes, frameBytes, nframes, results, false, labels, camera_of_frame);
+  const int rc = check_host_batch(h, "ssd_process_host_cameras", h && frames && results, nframes, input, kCameraTable, camera_of_frame);
+  return rc ? rc : process_host_impl(h, frames, nframes, input, results, staged_labels(h, labels), camera_of_frame);
 }
 
 /* ---- ground fit: a calibration refined from the floor in the frames (include/ssd_hip.h) ----------- */
@@ -2155,41 +2240,41 @@ static ssd_calibration handle_calibration(const ssd_handle *h)
   return calibration_of(h->P);
 }
 
+/* frame i's: its camera's in a cameras batch (camOf, checked by check_cameras), the handle's otherwise */
+static ssd_calibration frame_calibration(const ssd_handle *h, const uint16_t *camOf, int i)
+{
+  return camOf ? calibration_of(h->camParams[camOf[i]]) : handle_calibration(h);
+}
+
+/* the caller's records, or - it asked for none, the solve needs them - a vector of the call's own */
+static ssd_frame_moments *moments_or_own(ssd_frame_moments *callers, std::vector<ssd_frame_moments> &own, int nframes)
+{
+  if(callers)
+    return callers;
+  own.resize(static_cast<size_t>(nframes));
+  return own.data();
+}
+
+/* both host entry points of the surface fit, their refusals behind them: the batch with its moments staged out, then the solve */
+static int process_host_surfaces_impl(ssd_handle *h, const void *frames, int nframes, const uint16_t *camOf, int input, ssd_frame_result *results,
+                                      ssd_frame_moments *moments, int min_points, ssd_frame_surfaces *out)
+{
+  std::vector<ssd_frame_moments> own;
+  moments = moments_or_own(moments, own, nframes);
+  int rc = process_host_impl(h, frames, nframes, input, results, staged_moments(moments), camOf);
+  for(int i = 0; i < nframes && !rc; i++)
+  {
+    const ssd_calibration cal = frame_calibration(h, camOf, i);
+    rc = ssd_surface_fit_solve(moments + i, &cal, min_points, out + i);
+  }
+  return rc;
+}
+
 int ssd_process_host_surfaces(ssd_handle *h, const void *frames, int nframes, int input, ssd_frame_result *results,
                               ssd_frame_moments *moments, int min_points, ssd_frame_surfaces *out)
 {
-  if(!h || !frames || !results || !out || nframes < 1)
-    return fail(SSD_E_ARG, "ssd_process_host_surfaces: bad argument");
-  if(input != SSD_INPUT_VERTICES && input != SSD_INPUT_DEPTH16)
-    return fail(SSD_E_ARG, "ssd_process_host_surfaces: input must be SSD_INPUT_VERTICES or SSD_INPUT_DEPTH16");
-  if(input == SSD_INPUT_DEPTH16 && !h->haveIntr)
-    return fail(SSD_E_ARG, "ssd_process_host_surfaces: call ssd_set_intrinsics first");
-  std::vector<ssd_frame_moments> own;
-  if(!moments)
-  {
-    own.resize(static_cast<size_t>(nframes));
-    moments = own.data();
-  }
-  int rc;
-  if(input == SSD_INPUT_DEPTH16)
-  {
-    const size_t frameElems = (static_cast<size_t>(h->P.nPoints) + 3) / 4 * 4;
-    rc = process_host_impl(h, frames, static_cast<size_t>(h->P.nPoints) * 2, frameElems * 2, nframes, results, true,
-                           reinterpret_cast<unsigned char *>(moments), nullptr, true);
-  }
-  else
-  {
-    const size_t frameBytes = static_cast<size_t>(h->P.nPoints) * 12;
-    rc = process_host_impl(h, frames, frameBytes, frameBytes, nframes, results, false, reinterpret_cast<unsigned char *>(moments), nullptr, true);
-  }
-  if(rc) return rc;
-  const ssd_calibration cal = handle_calibration(h);
-  for(int i = 0; i < nframes; i++)
-  {
-    rc = ssd_surface_fit_solve(moments + i, &cal, min_points, out + i);
-    if(rc) return rc;
-  }
-  return SSD_OK;
+  const int rc = check_host_batch(h, "ssd_process_host_surfaces", h && frames && results && out, nframes, input, kHandleCal);
+  return rc ? rc : process_host_surfaces_impl(h, frames, nframes, nullptr, input, results, moments, min_points, out);
 }
 
 /* ---- trimmed surface refit (include/ssd_hip.h) ---------------------------------------------------------- */
@@ -2452,31 +2537,15 @@ static int process_host_refit_impl(ssd_handle *h, const char *who, const void *f
   int rc = check_gate_rule(who, k_sigma, gate_min);
   if(rc) return rc;
   HIP_TRY(hipSetDevice(h->device));
-  const bool depth = input == SSD_INPUT_DEPTH16;
-  /* the slices and the device layout of ssd_process_host / ssd_process_depth_host */
-  const size_t srcFrameBytes = static_cast<size_t>(h->P.nPoints) * (depth ? 2 : 12);
-  const size_t devFrameBytes = depth ? (static_cast<size_t>(h->P.nPoints) + 3) / 4 * 4 * 2 : srcFrameBytes;
-  const int slice = h->F < kIngestFrames ? h->F : kIngestFrames;
-  rc = ingest_prepare(h, static_cast<size_t>(slice) * devFrameBytes);
+  SliceFeed feed{ h, host_frames(h, input, kForPipeline), frames, nframes };
+  rc = feed.prepare();
   if(rc) return rc;
   /* the records of a slice on the device: the first pass's in the first label staging buffer, a refit pass's in the second */
-  rc = labels_prepare(h, static_cast<size_t>(slice) * sizeof(ssd_frame_moments));
+  rc = labels_prepare(h, static_cast<size_t>(feed.slice) * sizeof(ssd_frame_moments));
   if(rc) return rc;
   ssd_frame_moments *dFirst = reinterpret_cast<ssd_frame_moments *>(h->labelStage[0]), *dRefit = reinterpret_cast<ssd_frame_moments *>(h->labelStage[1]);
-  std::vector<ssd_frame_moments> cur(static_cast<size_t>(slice));
-  std::vector<ssd_frame_gates> gates(static_cast<size_t>(slice));
-  const ssd_calibration cal = handle_calibration(h);
-  const unsigned char *from = static_cast<const unsigned char *>(frames);
-  auto copyIn = [&](int k, int at, int n)
-  {
-    if(srcFrameBytes == devFrameBytes)
-      HIP_TRY(hipMemcpyAsync(h->ingestBuf[k], from + static_cast<size_t>(at) * srcFrameBytes, static_cast<size_t>(n) * srcFrameBytes, hipMemcpyHostToDevice, h->ingestCopy));
-    else
-      HIP_TRY(hipMemcpy2DAsync(h->ingestBuf[k], devFrameBytes, from + static_cast<size_t>(at) * srcFrameBytes, srcFrameBytes, srcFrameBytes, n,
-                               hipMemcpyHostToDevice, h->ingestCopy));
-    HIP_TRY(hipEventRecord(h->ingestCopied[k], h->ingestCopy));
-    return static_cast<int>(SSD_OK);
-  };
+  std::vector<ssd_frame_moments> cur(static_cast<size_t>(feed.slice));
+  std::vector<ssd_frame_gates> gates(static_cast<size_t>(feed.slice));
   /* the records of the pass that ran last on the slice's stream, to the host */
   auto records = [&](const ssd_frame_moments *d, int n)
   {
@@ -2485,21 +2554,16 @@ static int process_host_refit_impl(ssd_handle *h, const char *who, const void *f
     HIP_TRY(hipStreamSynchronize(s));
     return static_cast<int>(SSD_OK);
   };
-  rc = copyIn(0, 0, nframes < slice ? nframes : slice);
-  if(rc) return rc;
-  int c = 0;
-  for(int done = 0; done < nframes; c++)
+  for(int c = 0; c < feed.slices(); c++)
   {
-    const int n = nframes - done < slice ? nframes - done : slice;
-    const int k = c & 1;
-    /* the next slice's copy beside this slice's kernels: its buffer is free, the slice before is finished */
-    if(done + n < nframes)
-    {
-      rc = copyIn(k ^ 1, done + n, nframes - done - n < slice ? nframes - done - n : slice);
-      if(rc) return rc;
-    }
-    HIP_TRY(hipStreamWaitEvent(h->ingestCompute, h->ingestCopied[k], 0));
-    rc = enqueue_impl(h, h->ingestBuf[k], devFrameBytes, n, h->ingestCompute, SSD_STAGE_ALL, depth, nullptr, 0, camOf ? camOf + done : nullptr, dFirst);
+    const void *buf;
+    int done, n;
+    /* the body blocks on every pass, so the next slice's copy goes out in front of it, beside this slice's kernels */
+    rc = feed.stage(c);
+    if(!rc) rc = feed.stage(c + 1);
+    if(!rc) rc = feed.ready(c, buf, done, n);
+    if(rc) return rc;
+    rc = enqueue_impl(h, buf, feed.f.devFrameBytes, n, h->ingestCompute, SSD_STAGE_ALL, feed.f.depth, nullptr, 0, camOf ? camOf + done : nullptr, dFirst);
     if(rc) return rc;
     if(deviceGates)
     {
@@ -2507,7 +2571,7 @@ static int process_host_refit_impl(ssd_handle *h, const char *who, const void *f
        * the later ones in place.  Then the slice's results and, behind the last pass on its stream, its records */
       for(int pass = 0; pass < passes; pass++)
       {
-        rc = refit_enqueue_impl(h, who, camOf != nullptr, h->ingestBuf[k], devFrameBytes, n, h->ingestCompute, input,
+        rc = refit_enqueue_impl(h, who, camOf != nullptr, buf, feed.f.devFrameBytes, n, h->ingestCompute, input,
                                 GateSource{ nullptr, pass == 0 ? dFirst : dRefit, min_points, k_sigma, gate_min }, dRefit);
         if(rc) return rc;
       }
@@ -2537,7 +2601,7 @@ static int process_host_refit_impl(ssd_handle *h, const char *who, const void *f
           rc = ssd_surface_gates_from_moments(&cur[i], min_points, k_sigma, gate_min, &gates[i]);
           if(rc) return rc;
         }
-        rc = refit_enqueue_impl(h, who, camOf != nullptr, h->ingestBuf[k], devFrameBytes, n, h->ingestCompute, input,
+        rc = refit_enqueue_impl(h, who, camOf != nullptr, buf, feed.f.devFrameBytes, n, h->ingestCompute, input,
                                 GateSource{ gates.data(), nullptr, 0, 0.0, 0.0 }, dRefit);
         if(rc) return rc;
         rc = ssd_fetch_surface_refit(h, nullptr);
@@ -2546,15 +2610,17 @@ static int process_host_refit_impl(ssd_handle *h, const char *who, const void *f
         if(rc) return rc;
       }
     }
+    /* the buffer's last reader was the last pass, on the slice's stream (which the body has waited for: the record costs nothing) */
+    rc = feed.consumed(c, h->lane[h->lastLane].lastStream);
+    if(rc) return rc;
     if(refit)
       std::memcpy(refit + done, cur.data(), sizeof(ssd_frame_moments) * static_cast<size_t>(n));
     for(int i = 0; i < n; i++)
     {
-      const ssd_calibration own = camOf ? calibration_of(h->camParams[camOf[done + i]]) : cal;
+      const ssd_calibration own = frame_calibration(h, camOf, done + i);
       rc = ssd_surface_fit_solve(&cur[i], &own, min_points, out + done + i);
       if(rc) return rc;
     }
-    done += n;
   }
   return SSD_OK;
 }
@@ -2563,28 +2629,18 @@ int ssd_process_host_surfaces_refit(ssd_handle *h, const void *frames, int nfram
                                     ssd_frame_moments *first, ssd_frame_moments *refit, int min_points, double k_sigma, double gate_min,
                                     int passes, ssd_frame_surfaces *out)
 {
-  if(!h || !frames || !results || !out || nframes < 1)
-    return fail(SSD_E_ARG, "ssd_process_host_surfaces_refit: bad argument");
-  if(input != SSD_INPUT_VERTICES && input != SSD_INPUT_DEPTH16)
-    return fail(SSD_E_ARG, "ssd_process_host_surfaces_refit: input must be SSD_INPUT_VERTICES or SSD_INPUT_DEPTH16");
-  if(input == SSD_INPUT_DEPTH16 && !h->haveIntr)
-    return fail(SSD_E_ARG, "ssd_process_host_surfaces_refit: call ssd_set_intrinsics first");
-  return process_host_refit_impl(h, "ssd_process_host_surfaces_refit", frames, nframes, nullptr, input, results, first, refit, min_points, k_sigma,
-                                 gate_min, passes, out, false);
+  const int rc = check_host_batch(h, "ssd_process_host_surfaces_refit", h && frames && results && out, nframes, input, kHandleCal);
+  return rc ? rc : process_host_refit_impl(h, "ssd_process_host_surfaces_refit", frames, nframes, nullptr, input, results, first, refit, min_points, k_sigma,
+                                           gate_min, passes, out, false);
 }
 
 int ssd_process_host_surfaces_refit_device(ssd_handle *h, const void *frames, int nframes, int input, ssd_frame_result *results,
                                            ssd_frame_moments *first, ssd_frame_moments *refit, int min_points, double k_sigma, double gate_min,
                                            int passes, ssd_frame_surfaces *out)
 {
-  if(!h || !frames || !results || !out || nframes < 1)
-    return fail(SSD_E_ARG, "ssd_process_host_surfaces_refit_device: bad argument");
-  if(input != SSD_INPUT_VERTICES && input != SSD_INPUT_DEPTH16)
-    return fail(SSD_E_ARG, "ssd_process_host_surfaces_refit_device: input must be SSD_INPUT_VERTICES or SSD_INPUT_DEPTH16");
-  if(input == SSD_INPUT_DEPTH16 && !h->haveIntr)
-    return fail(SSD_E_ARG, "ssd_process_host_surfaces_refit_device: call ssd_set_intrinsics first");
-  return process_host_refit_impl(h, "ssd_process_host_surfaces_refit_device", frames, nframes, nullptr, input, results, first, refit, min_points,
-                                 k_sigma, gate_min, passes, out, true);
+  const int rc = check_host_batch(h, "ssd_process_host_surfaces_refit_device", h && frames && results && out, nframes, input, kHandleCal);
+  return rc ? rc : process_host_refit_impl(h, "ssd_process_host_surfaces_refit_device", frames, nframes, nullptr, input, results, first, refit, min_points,
+                                           k_sigma, gate_min, passes, out, true);
 }
 
 /* ---- surface fit of cameras batches and drift per camera (include/ssd_hip.h) ---------------------------- */
@@ -2592,35 +2648,8 @@ int ssd_process_host_surfaces_refit_device(ssd_handle *h, const void *frames, in
 int ssd_process_host_cameras_surfaces(ssd_handle *h, const void *frames, int nframes, const uint16_t *camera_of_frame, int input,
                                       ssd_frame_result *results, ssd_frame_moments *moments, int min_points, ssd_frame_surfaces *out)
 {
-  if(!h || !frames || !results || !out || nframes < 1)
-    return fail(SSD_E_ARG, "ssd_process_host_cameras_surfaces: bad argument");
-  int rc = check_cameras(h, "ssd_process_host_cameras_surfaces", camera_of_frame, nframes, input);
-  if(rc) return rc;
-  std::vector<ssd_frame_moments> own;
-  if(!moments)
-  {
-    own.resize(static_cast<size_t>(nframes));
-    moments = own.data();
-  }
-  if(input == SSD_INPUT_DEPTH16)
-  {
-    const size_t frameElems = (static_cast<size_t>(h->P.nPoints) + 3) / 4 * 4;       /* as ssd_process_depth_host */
-    rc = process_host_impl(h, frames, static_cast<size_t>(h->P.nPoints) * 2, frameElems * 2, nframes, results, true,
-                           reinterpret_cast<unsigned char *>(moments), camera_of_frame, true);
-  }
-  else
-  {
-    const size_t frameBytes = static_cast<size_t>(h->P.nPoints) * 12;
-    rc = process_host_impl(h, frames, frameBytes, frameBytes, nframes, results, false, reinterpret_cast<unsigned char *>(moments), camera_of_frame, true);
-  }
-  if(rc) return rc;
-  for(int i = 0; i < nframes; i++)
-  {
-    const ssd_calibration cal = calibration_of(h->camParams[camera_of_frame[i]]);
-    rc = ssd_surface_fit_solve(moments + i, &cal, min_points, out + i);
-    if(rc) return rc;
-  }
-  return SSD_OK;
+  const int rc = check_host_batch(h, "ssd_process_host_cameras_surfaces", h && frames && results && out, nframes, input, kCameraTable, camera_of_frame);
+  return rc ? rc : process_host_surfaces_impl(h, frames, nframes, camera_of_frame, input, results, moments, min_points, out);
 }
 
 /* ---- trimmed refit of cameras batches (include/ssd_hip.h) -------------------------------------------------- */
@@ -2629,24 +2658,18 @@ int ssd_process_host_cameras_surfaces_refit(ssd_handle *h, const void *frames, i
                                             ssd_frame_result *results, ssd_frame_moments *first, ssd_frame_moments *refit, int min_points,
                                             double k_sigma, double gate_min, int passes, ssd_frame_surfaces *out)
 {
-  if(!h || !frames || !results || !out || nframes < 1)
-    return fail(SSD_E_ARG, "ssd_process_host_cameras_surfaces_refit: bad argument");
-  int rc = check_cameras(h, "ssd_process_host_cameras_surfaces_refit", camera_of_frame, nframes, input);
-  if(rc) return rc;
-  return process_host_refit_impl(h, "ssd_process_host_cameras_surfaces_refit", frames, nframes, camera_of_frame, input, results, first, refit,
-                                 min_points, k_sigma, gate_min, passes, out, false);
+  const int rc = check_host_batch(h, "ssd_process_host_cameras_surfaces_refit", h && frames && results && out, nframes, input, kCameraTable, camera_of_frame);
+  return rc ? rc : process_host_refit_impl(h, "ssd_process_host_cameras_surfaces_refit", frames, nframes, camera_of_frame, input, results, first, refit,
+                                           min_points, k_sigma, gate_min, passes, out, false);
 }
 
 int ssd_process_host_cameras_surfaces_refit_device(ssd_handle *h, const void *frames, int nframes, const uint16_t *camera_of_frame, int input,
                                                    ssd_frame_result *results, ssd_frame_moments *first, ssd_frame_moments *refit, int min_points,
                                                    double k_sigma, double gate_min, int passes, ssd_frame_surfaces *out)
 {
-  if(!h || !frames || !results || !out || nframes < 1)
-    return fail(SSD_E_ARG, "ssd_process_host_cameras_surfaces_refit_device: bad argument");
-  int rc = check_cameras(h, "ssd_process_host_cameras_surfaces_refit_device", camera_of_frame, nframes, input);
-  if(rc) return rc;
-  return process_host_refit_impl(h, "ssd_process_host_cameras_surfaces_refit_device", frames, nframes, camera_of_frame, input, results, first, refit,
-                                 min_points, k_sigma, gate_min, passes, out, true);
+  const int rc = check_host_batch(h, "ssd_process_host_cameras_surfaces_refit_device", h && frames && results && out, nframes, input, kCameraTable, camera_of_frame);
+  return rc ? rc : process_host_refit_impl(h, "ssd_process_host_cameras_surfaces_refit_device", frames, nframes, camera_of_frame, input, results, first, refit,
+                                           min_points, k_sigma, gate_min, passes, out, true);
 }
 
 /* host only: no handle, no device */
@@ -2753,31 +2776,18 @@ static int process_host_riser_fits_impl(ssd_handle *h, const char *who, const vo
   if(!h->P.risers || !h->dRisers)
     return fail(SSD_E_ARG, std::string(who) + ": call ssd_set_risers(h, 1, ...) first");
   std::vector<ssd_frame_moments> own;
-  if(!moments)
-  {
-    own.resize(static_cast<size_t>(nframes));
-    moments = own.data();
-  }
+  moments = moments_or_own(moments, own, nframes);
   const bool was = h->riserMoments;
   int rc = ssd_set_riser_moments(h, 1);
   if(rc) return rc;
-  if(input == SSD_INPUT_DEPTH16)
-  {
-    const size_t frameElems = (static_cast<size_t>(h->P.nPoints) + 3) / 4 * 4;       /* as ssd_process_depth_host */
-    rc = process_host_impl(h, frames, static_cast<size_t>(h->P.nPoints) * 2, frameElems * 2, nframes, results, true, nullptr, camOf);
-  }
-  else
-  {
-    const size_t frameBytes = static_cast<size_t>(h->P.nPoints) * 12;
-    rc = process_host_impl(h, frames, frameBytes, frameBytes, nframes, results, false, nullptr, camOf);
-  }
+  rc = process_host_impl(h, frames, nframes, input, results, StagedOut{}, camOf);
   if(!rc) rc = ssd_fetch_risers(h, risers, nframes, nullptr);
   if(!rc) rc = ssd_fetch_riser_moments(h, moments, nframes, nullptr);
   h->riserMoments = was;                      /* the call has returned its batches: nothing is in flight */
   if(rc) return rc;
   for(int i = 0; i < nframes; i++)
   {
-    const ssd_calibration cal = camOf ? calibration_of(h->camParams[camOf[i]]) : handle_calibration(h);
+    const ssd_calibration cal = frame_calibration(h, camOf, i);
     rc = ssd_riser_fit_solve(moments + i, risers + i, &cal, min_points, out + i);
     if(rc) return rc;
   }
@@ -2787,24 +2797,16 @@ static int process_host_riser_fits_impl(ssd_handle *h, const char *who, const vo
 int ssd_process_host_riser_fits(ssd_handle *h, const void *frames, int nframes, int input, ssd_frame_result *results,
                                 ssd_frame_risers *risers, ssd_frame_moments *moments, int min_points, ssd_frame_riser_fits *out)
 {
-  if(!h || !frames || !results || !risers || !out || nframes < 1)
-    return fail(SSD_E_ARG, "ssd_process_host_riser_fits: bad argument");
-  if(input != SSD_INPUT_VERTICES && input != SSD_INPUT_DEPTH16)
-    return fail(SSD_E_ARG, "ssd_process_host_riser_fits: input must be SSD_INPUT_VERTICES or SSD_INPUT_DEPTH16");
-  if(input == SSD_INPUT_DEPTH16 && !h->haveIntr)
-    return fail(SSD_E_ARG, "ssd_process_host_riser_fits: call ssd_set_intrinsics first");
-  return process_host_riser_fits_impl(h, "ssd_process_host_riser_fits", frames, nframes, nullptr, input, results, risers, moments, min_points, out);
+  const int rc = check_host_batch(h, "ssd_process_host_riser_fits", h && frames && results && risers && out, nframes, input, kHandleCal);
+  return rc ? rc : process_host_riser_fits_impl(h, "ssd_process_host_riser_fits", frames, nframes, nullptr, input, results, risers, moments, min_points, out);
 }
 
 int ssd_process_host_cameras_riser_fits(ssd_handle *h, const void *frames, int nframes, const uint16_t *camera_of_frame, int input,
                                         ssd_frame_result *results, ssd_frame_risers *risers, ssd_frame_moments *moments, int min_points,
                                         ssd_frame_riser_fits *out)
 {
-  if(!h || !frames || !results || !risers || !out || nframes < 1)
-    return fail(SSD_E_ARG, "ssd_process_host_cameras_riser_fits: bad argument");
-  const int rc = check_cameras(h, "ssd_process_host_cameras_riser_fits", camera_of_frame, nframes, input);
-  if(rc) return rc;
-  return process_host_riser_fits_impl(h, "ssd_process_host_cameras_riser_fits", frames, nframes, camera_of_frame, input, results, risers, moments, min_points, out);
+  const int rc = check_host_batch(h, "ssd_process_host_cameras_riser_fits", h && frames && results && risers && out, nframes, input, kCameraTable, camera_of_frame);
+  return rc ? rc : process_host_riser_fits_impl(h, "ssd_process_host_cameras_riser_fits", frames, nframes, camera_of_frame, input, results, risers, moments, min_points, out);
 }
 
 /* host only: no handle, no device */
@@ -2914,7 +2916,7 @@ static int enqueue_ground_fit_impl(ssd_handle *h, const void *d_frames, size_t f
                                    const ssd_camera *priors, int npriors, double tol)
 {
   const bool depth = input == SSD_INPUT_DEPTH16;
-  const size_t unit = depth ? 2 : 4, frameBytes = static_cast<size_t>(h->P.nPoints) * (depth ? 2 : 12);
+  const size_t unit = depth ? 2 : 4, frameBytes = host_frames(h, input, kForGroundFit).srcFrameBytes;
   if(reinterpret_cast<size_t>(d_frames) % unit != 0 || frame_stride_bytes % unit != 0 || (nframes > 1 && frame_stride_bytes < frameBytes))
     return fail(SSD_E_ARG, "ssd_enqueue_ground_fit: frames must be aligned to their element and the stride must hold a frame");
   HIP_TRY(hipSetDevice(h->device));
@@ -2989,47 +2991,35 @@ int ssd_fetch_ground_fit(ssd_handle *h, ssd_ground_fit *out, int nframes, int mi
 int ssd_process_host_ground_fit(ssd_handle *h, const void *frames, int nframes, int input, const ssd_camera *priors, int npriors,
                                 double tol, int min_points, ssd_ground_fit *out)
 {
-  if(!h || !frames || !out || nframes < 1)
-    return fail(SSD_E_ARG, "ssd_process_host_ground_fit: bad argument");
-  int rc = check_ground_fit(h, "ssd_process_host_ground_fit", input, priors, npriors, nframes, tol);
+  int rc = check_host_batch(h, "ssd_process_host_ground_fit", h && frames && out, nframes, input, kOwnPriors);
+  if(!rc) rc = check_ground_fit(h, "ssd_process_host_ground_fit", input, priors, npriors, nframes, tol);
   if(rc) return rc;
   HIP_TRY(hipSetDevice(h->device));
-  const bool depth = input == SSD_INPUT_DEPTH16;
-  const size_t srcFrameBytes = static_cast<size_t>(h->P.nPoints) * (depth ? 2 : 12);
-  const size_t devFrameBytes = (srcFrameBytes + 15) / 16 * 16;        /* every frame on a 16-byte boundary: the kernel's wide loads */
-  const int slice = h->F < kIngestFrames ? h->F : kIngestFrames;
-  rc = ingest_prepare(h, static_cast<size_t>(slice) * devFrameBytes);
+  SliceFeed feed{ h, host_frames(h, input, kForGroundFit), frames, nframes };
+  rc = feed.prepare();
   if(rc) return rc;
-  const unsigned char *from = static_cast<const unsigned char *>(frames);
-  int prevFrames = 0, prevAt = 0, c = 0;
-  for(int done = 0; done < nframes; c++)
+  const bool each = npriors == nframes && npriors > 1;             /* a prior per frame: a slice takes its part of them */
+  const int last = feed.slices() - 1;
+  for(int c = 0; c <= last; c++)
   {
-    const int n = nframes - done < slice ? nframes - done : slice;
-    const int k = c & 1;
-    if(c >= 2)
-      HIP_TRY(hipStreamWaitEvent(h->ingestCopy, h->ingestConsumed[k], 0));        /* the kernel of slice c - 2 read this buffer */
-    const unsigned char *at = from + static_cast<size_t>(done) * srcFrameBytes;
-    if(srcFrameBytes == devFrameBytes)
-      HIP_TRY(hipMemcpyAsync(h->ingestBuf[k], at, static_cast<size_t>(n) * srcFrameBytes, hipMemcpyHostToDevice, h->ingestCopy));
-    else
-      HIP_TRY(hipMemcpy2DAsync(h->ingestBuf[k], devFrameBytes, at, srcFrameBytes, srcFrameBytes, n, hipMemcpyHostToDevice, h->ingestCopy));
-    HIP_TRY(hipEventRecord(h->ingestCopied[k], h->ingestCopy));
+    const void *buf;
+    int at, n;
+    rc = feed.stage(c);
+    if(rc) return rc;
     /* the records are one set: the slice before is solved (its kernel ran beside this slice's copy) before this one's kernel goes out */
-    if(prevFrames)
+    if(c >= 1)
     {
-      rc = ssd_fetch_ground_fit(h, out + prevAt, prevFrames, min_points, nullptr);
+      rc = ssd_fetch_ground_fit(h, out + feed.first(c - 1), feed.count(c - 1), min_points, nullptr);
       if(rc) return rc;
     }
-    HIP_TRY(hipStreamWaitEvent(h->ingestCompute, h->ingestCopied[k], 0));
-    rc = enqueue_ground_fit_impl(h, h->ingestBuf[k], devFrameBytes, n, h->ingestCompute, input, npriors == nframes && npriors > 1 ? priors + done : priors,
-                                 npriors == nframes && npriors > 1 ? n : npriors, tol);
+    rc = feed.ready(c, buf, at, n);
     if(rc) return rc;
-    HIP_TRY(hipEventRecord(h->ingestConsumed[k], h->ingestCompute));
-    prevFrames = n;
-    prevAt = done;
-    done += n;
+    rc = enqueue_ground_fit_impl(h, buf, feed.f.devFrameBytes, n, h->ingestCompute, input, each ? priors + at : priors, each ? n : npriors, tol);
+    if(rc) return rc;
+    rc = feed.consumed(c, h->ingestCompute);
+    if(rc) return rc;
   }
-  return ssd_fetch_ground_fit(h, out + prevAt, prevFrames, min_points, nullptr);
+  return ssd_fetch_ground_fit(h, out + feed.first(last), feed.count(last), min_points, nullptr);
 }
 
 /* pinned host memory for frames (DMA without a staging copy) */
