@@ -716,8 +716,9 @@ int ssd_camera_ground_gates(const ssd_frame_moments *moments, const uint16_t *ca
  * SSD_E_ARG, before anything is launched or copied: what ssd_enqueue_surface_refit / ssd_enqueue_cameras_surface_refit refuse, k_sigma
  * not in (0, 16], gate_min not in [0, 1], a null d_prev, d_moments or d_gates, nframes outside 1 .. max_frames_per_batch.
  * A handle that never calls any of these allocates and launches nothing more.
- * Limits: the riser fit has no refit; ssd_pipeline_* does not refit; ssd_camera_ground_gates stays on the host (it needs the fold), and
- * so does ssd_surface_fit_solve; the host paths below still finish a slice before the next one's kernels go out. */
+ * Limits: the riser fit has no refit; ssd_pipeline_* does not refit; ssd_surface_fit_solve stays on the host (the camera's gate has a
+ * device form of its own: ssd_enqueue_camera_ground_gates, below); the host paths below still finish a slice before the next one's
+ * kernels go out. */
 int ssd_enqueue_surface_gates(ssd_handle *h, const ssd_frame_moments *d_moments, int nframes, void *stream,
                               int min_points, double k_sigma, double gate_min, ssd_frame_gates *d_gates /* DEVICE, nframes */);
 int ssd_enqueue_surface_refit_device(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream, int input,
@@ -738,6 +739,67 @@ int ssd_process_host_cameras_surfaces_refit_device(ssd_handle *h, const void *fr
                                                    ssd_frame_result *results, ssd_frame_moments *first /* may be NULL */,
                                                    ssd_frame_moments *refit /* may be NULL */, int min_points, double k_sigma,
                                                    double gate_min, int passes /* 1..4 */, ssd_frame_surfaces *out);
+
+/* ---- camera fold on the device: the camera's gate and the drift in one chain ------------------------------------------------------
+ * EXTENSION.  ssd_camera_drift_fold was the one link of the drift watch that lived on the host alone, so the
+ * camera's gate (ssd_camera_ground_gates: the best configuration profiles/camera_drift_refit_accuracy.txt records) cost a resident-frames
+ * caller a wait, 1.5 KB per frame down and 688 bytes per frame up between two passes.  k_camera_fold folds records in device memory
+ * by the host's own step (csrc/ssd_fold.h), k_camera_ground_gates solves each camera's sum and overlays its plane on the frames' gates
+ * by the host's own text (csrc/ssd_solve.h, both sides without FMA contraction).
+ *
+ * ssd_camera_fold is the head of ssd_camera_drift, field for field: everything of it that needs no calibration. */
+typedef struct
+{
+  int32_t camera, frames, frames_ground, frames_left;
+  ssd_ground_moments m;
+  int64_t n_far;
+} ssd_camera_fold;               /* 104 bytes */
+
+/* ssd_enqueue_camera_fold: d_fold[c] (DEVICE, ncams records) is byte for byte the first 104 bytes of out[c] of ssd_camera_drift_fold over
+ * the same records (d_moments: DEVICE, nframes) and the same index (d_camera_of_frame: DEVICE, one int32 per frame - the form a
+ * workspace keeps its own index in).  accumulate == 0: all 104 bytes of all ncams records are written, whatever was there, and nothing
+ * behind them.  accumulate != 0: d_fold holds the records of earlier calls and the frames are folded on top in index order: two calls
+ * equal one call over the concatenation, frames_left included.  A frame whose index lies outside 0 .. ncams - 1 - which the host function
+ * refuses - is counted nowhere: the device has nobody to refuse to.  Moments at s[1..], and s[0] of a frame without a ground, are not
+ * read.  Launches on `stream` without synchronising; the handle gives the device and the limit of nframes, nothing of it is touched.
+ * SSD_E_ARG before anything is launched: a null pointer, nframes outside 1 .. max_frames_per_batch, ncams outside 1 .. SSD_MAX_CAMERAS. */
+int ssd_enqueue_camera_fold(ssd_handle *h, const ssd_frame_moments *d_moments, const int32_t *d_camera_of_frame, int nframes, int ncams,
+                            int accumulate, void *stream, ssd_camera_fold *d_fold /* DEVICE, ncams */);
+/* ssd_enqueue_camera_ground_gates: d_gates (DEVICE, nframes, in/out) afterwards is byte for byte what ssd_camera_ground_gates leaves, given
+ * drift[c].fit = ssd_ground_fit_solve(&d_fold[c].m, .., fold_min_points, ..): g[0] of frame i becomes n = normal, dist, gate =
+ * max(k_sigma * rms, gate_min) and n_surfaces is raised to at least 1 when the frame has a ground (ground == 1, n_surfaces >= 1) and its
+ * camera's status is SSD_GF_OK; every other byte stays as given.  normal, dist, rms and the status do not depend on the prior's
+ * calibration, so the call takes no table; fit.tilt stays on the host.  A frame whose index lies outside 0 .. ncams - 1 is left as given.
+ * Stream and handle as ssd_enqueue_camera_fold.  SSD_E_ARG before anything is launched: what ssd_enqueue_camera_fold refuses, k_sigma not
+ * in (0, 16], gate_min not in [0, 1]. */
+int ssd_enqueue_camera_ground_gates(ssd_handle *h, const ssd_frame_moments *d_moments, const int32_t *d_camera_of_frame, int nframes,
+                                    const ssd_camera_fold *d_fold /* DEVICE, ncams */, int ncams, int fold_min_points, double k_sigma,
+                                    double gate_min, void *stream, ssd_frame_gates *d_gates /* DEVICE, nframes, in/out */);
+/* ssd_enqueue_cameras_surface_refit_device with the camera's gate: in front of the zeroing, on the pass's stream, k_surface_gates(d_prev)
+ * into the handle's device gates, the fold of d_prev under the batch's own index and the table's count into a fold buffer of the handle's
+ * (made on the first call, counted in ssd_workspace_bytes, one per handle like the device gates), and the overlay.  Frame i's record is
+ * byte for byte ssd_enqueue_cameras_surface_refit under the gates ssd_surface_gates_from_moments, ssd_camera_drift_fold(fold_min_points)
+ * and ssd_camera_ground_gates make from the downloaded d_prev.  d_prev == d_out is allowed.  Everything else - the refusals, streams and
+ * workspaces, ssd_fetch_surface_refit, ssd_get_surface_refit_time (which includes the three kernels) - is that function's. */
+int ssd_enqueue_cameras_surface_refit_folded(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream, int input,
+                                             const ssd_frame_moments *d_prev /* DEVICE, nframes */, int min_points, double k_sigma,
+                                             double gate_min, int fold_min_points, ssd_frame_moments *d_out);
+/* host only, no GPU needed: the head copied, then ssd_ground_fit_solve(&fold[c].m, &cams[c].cal, min_points, ..) per camera.  out is byte
+ * for byte ssd_camera_drift_fold's over the records that made the fold.  SSD_E_ARG (out untouched): a null pointer, ncams outside
+ * 1 .. SSD_MAX_CAMERAS, fold[c].camera != c. */
+int ssd_camera_drift_from_fold(const ssd_camera_fold *fold, const ssd_camera *cams, int ncams, int min_points, ssd_camera_drift *out /* ncams */);
+/* The drift watch on host frames with no per-frame record on the host.  Through the slices of ssd_process_host_cameras; per slice a
+ * cameras enqueue with the first moments, `passes` (0 .. 4) device-gated refits (min_points, k_sigma, gate_min: those of
+ * ssd_process_host_cameras_surfaces_refit_device) and an accumulating fold of the last records on the slice's stream; after the last slice
+ * one copy of table-count x 104 bytes, then ssd_camera_drift_from_fold(fold_min_points).  results[nframes] is byte for byte
+ * ssd_process_host_cameras', out[table count] byte for byte ssd_camera_drift_fold over the last pass's records of
+ * ssd_process_host_cameras_surfaces_refit_device (passes == 0: over ssd_process_host_cameras_surfaces' records).
+ * Per-frame gates only: a slice does not hold a camera's batch, and a refit needs the points again - the camera's gate is for resident
+ * frames (ssd_enqueue_cameras_surface_refit_folded).  A slice is finished before the next one's kernels go out.
+ * SSD_E_ARG before anything is copied: what ssd_process_host_cameras refuses, a null out, passes outside 0 .. 4, the gate rule. */
+int ssd_process_host_cameras_drift(ssd_handle *h, const void *frames, int nframes, const uint16_t *camera_of_frame, int input,
+                                   ssd_frame_result *results, int min_points, double k_sigma, double gate_min, int passes /* 0..4 */,
+                                   int fold_min_points, ssd_camera_drift *out /* table count */);
 
 /* stage selector for profiling / roofline measurement: runs only the chosen stage(s) of the pipeline */
 #define SSD_STAGE_HIST 1       /* K1: transform + crop + bin + histogram */

@@ -198,6 +198,12 @@ class CameraDrift(C.Structure):
                 ("m", GroundMoments), ("n_far", C.c_int64), ("fit", GroundFit)]
 
 
+class CameraFold(C.Structure):
+    """ssd_camera_fold: the head of ssd_camera_drift, field for field - what k_camera_fold makes on the device"""
+    _fields_ = [("camera", C.c_int32), ("frames", C.c_int32), ("frames_ground", C.c_int32), ("frames_left", C.c_int32),
+                ("m", GroundMoments), ("n_far", C.c_int64)]
+
+
 class Scene(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32),
                 ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
@@ -239,6 +245,8 @@ EXPORTS = [
     "ssd_enqueue_cameras_surface_refit", "ssd_process_host_cameras_surfaces_refit", "ssd_camera_ground_gates",
     "ssd_enqueue_surface_gates", "ssd_enqueue_surface_refit_device", "ssd_enqueue_cameras_surface_refit_device",
     "ssd_process_host_surfaces_refit_device", "ssd_process_host_cameras_surfaces_refit_device",
+    "ssd_enqueue_camera_fold", "ssd_enqueue_camera_ground_gates", "ssd_enqueue_cameras_surface_refit_folded", "ssd_camera_drift_from_fold",
+    "ssd_process_host_cameras_drift",
 ]
 # libssd_source.so — the frame source standing in for the camera (include/ssd_source.h)
 SOURCE_EXPORTS = [
@@ -339,6 +347,12 @@ def lib():
     L.ssd_process_host_cameras_surfaces_refit_device.argtypes = L.ssd_process_host_cameras_surfaces_refit.argtypes
     L.ssd_camera_ground_gates.argtypes = [C.POINTER(FrameMoments), C.POINTER(C.c_uint16), i32, C.POINTER(CameraDrift), i32, C.c_double, C.c_double,
                                           C.POINTER(FrameGates)]
+    L.ssd_enqueue_camera_fold.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
+    L.ssd_enqueue_camera_ground_gates.argtypes = [vp, vp, vp, i32, vp, i32, i32, C.c_double, C.c_double, vp, vp]
+    L.ssd_enqueue_cameras_surface_refit_folded.argtypes = [vp, vp, sz, i32, vp, i32, vp, i32, C.c_double, C.c_double, i32, vp]
+    L.ssd_camera_drift_from_fold.argtypes = [C.POINTER(CameraFold), C.POINTER(Camera), i32, i32, C.POINTER(CameraDrift)]
+    L.ssd_process_host_cameras_drift.argtypes = [vp, vp, i32, C.POINTER(C.c_uint16), i32, C.POINTER(FrameResult), i32, C.c_double, C.c_double, i32, i32,
+                                                 C.POINTER(CameraDrift)]
     L.ssd_set_riser_moments.argtypes = [vp, i32]
     L.ssd_fetch_riser_moments.argtypes = [vp, C.POINTER(FrameMoments), i32, vp]
     L.ssd_riser_fit_solve.argtypes = [C.POINTER(FrameMoments), C.POINTER(FrameRisers), C.POINTER(Calibration), i32, C.POINTER(FrameRiserFits)]
@@ -651,6 +665,20 @@ def camera_ground_gates(moments, camera_of_frame, drift, gates, k_sigma=2.5, gat
     arr = (FrameGates * max(1, n))(*gates)
     _check(lib().ssd_camera_ground_gates(mom, idx.ctypes.data_as(C.POINTER(C.c_uint16)), n, dr, ncams, float(k_sigma), float(gate_min), arr))
     return [FrameGates.from_buffer_copy(arr[i]) for i in range(n)]
+
+
+def camera_drift_from_fold(fold, cameras, min_points=2000):
+    """ssd_camera_drift_from_fold: CameraFold records (one per camera of `cameras`, as Detector.enqueue_camera_fold makes them on the
+    device, or the heads of CameraDrift records) -> list of CameraDrift: the head copied, the ground fit of its sums against that
+    camera's calibration.  Byte for byte camera_drift_fold over the records that made the fold"""
+    ncams = len(cameras)
+    if len(fold) != ncams:
+        raise SsdError("camera_drift_from_fold: one CameraFold per camera")
+    arr = fold if isinstance(fold, C.Array) and fold._type_ is CameraFold else (CameraFold * max(1, ncams))(*fold)
+    cams = cameras if isinstance(cameras, C.Array) and cameras._type_ is Camera else _camera_array(list(cameras))[0]
+    out = (CameraDrift * max(1, ncams))()
+    _check(lib().ssd_camera_drift_from_fold(arr, cams, ncams, int(min_points), out))
+    return [CameraDrift.from_buffer_copy(out[i]) for i in range(ncams)]
 
 
 # --------------------------------------------------------------------------- reference-shaped classes
@@ -992,12 +1020,28 @@ class Detector:
                                                        INPUT_DEPTH16 if depth else INPUT_VERTICES, res, mom if moments else None, int(min_points), out))
         return (list(res), list(out), list(mom)) if moments else (list(res), list(out))
 
-    def camera_drift(self, frames, camera_of_frame, depth=False, min_points=2000, passes=0, k_sigma=2.5, gate_min=0.0, device_gates=False):
+    def camera_drift(self, frames, camera_of_frame, depth=False, min_points=2000, passes=0, k_sigma=2.5, gate_min=0.0, device_gates=False,
+                     device_fold=False):
         """process_host_cameras_surfaces, then camera_drift_fold of its moments against the handle's camera table
         -> (list of FrameResult, list of CameraDrift, one per camera of the table).  passes >= 1: the fold of the last refit pass's
-        records of process_host_cameras_surfaces_refit(passes, k_sigma, gate_min, device_gates) instead of the first pass's"""
+        records of process_host_cameras_surfaces_refit(passes, k_sigma, gate_min, device_gates) instead of the first pass's.
+        device_fold=True: ssd_process_host_cameras_drift - device gates and the fold on the device, slice by slice, no per-frame record on
+        the host; the same outputs as device_gates=True, byte for byte"""
         if not getattr(self, "_cameras", None):
             raise SsdError("camera_drift: the handle has no camera table (set_cameras)")
+        if device_fold:
+            a = np.ascontiguousarray(frames, dtype=np.uint16 if depth else np.float32) if not isinstance(frames, PinnedArray) else frames.array
+            per = self.cfg.width * self.cfg.height * (1 if depth else 3)
+            n = a.size // per
+            if n < 1 or a.size != n * per:
+                raise SsdError("camera_drift: array does not hold whole frames")
+            idx = self._camera_index(camera_of_frame, n)
+            ncams = len(self._cameras)
+            res, out = (FrameResult * n)(), (CameraDrift * ncams)()
+            _check(lib().ssd_process_host_cameras_drift(self._h, a.ctypes.data_as(C.c_void_p), n, idx.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                                        INPUT_DEPTH16 if depth else INPUT_VERTICES, res, 200, float(k_sigma), float(gate_min),
+                                                        int(passes), int(min_points), out))
+            return list(res), [CameraDrift.from_buffer_copy(out[i]) for i in range(ncams)]
         if passes:
             res, _, _, mom = self.process_host_cameras_surfaces_refit(frames, camera_of_frame, depth=depth, k_sigma=k_sigma, gate_min=gate_min,
                                                                       passes=passes, moments=True, device_gates=device_gates)
@@ -1058,6 +1102,68 @@ class Detector:
         _check(lib().ssd_enqueue_cameras_surface_refit_device(self._h, C.c_void_p(d_ptr), stride_bytes or frame, nframes, C.c_void_p(stream or 0),
                                                               INPUT_DEPTH16 if depth else INPUT_VERTICES, C.c_void_p(d_prev), int(min_points),
                                                               float(k_sigma), float(gate_min), C.c_void_p(d_moments)))
+
+    # ---- camera fold on the device (include/ssd_hip.h)
+    def enqueue_camera_fold(self, d_moments, d_camera_of_frame, nframes, ncams, d_fold, accumulate=False, stream=None):
+        """ssd_enqueue_camera_fold: nframes FrameMoments and one int32 camera index per frame, both in device memory -> ncams CameraFold
+        in device memory (record c = the head of camera_drift_fold's record c, byte for byte; accumulate: on top of what d_fold holds),
+        on `stream`, without synchronising"""
+        _check(lib().ssd_enqueue_camera_fold(self._h, C.c_void_p(d_moments), C.c_void_p(d_camera_of_frame), int(nframes), int(ncams),
+                                             1 if accumulate else 0, C.c_void_p(stream or 0), C.c_void_p(d_fold)))
+
+    def enqueue_camera_ground_gates(self, d_moments, d_camera_of_frame, nframes, d_fold, ncams, d_gates, fold_min_points=2000, k_sigma=2.5,
+                                    gate_min=0.0, stream=None):
+        """ssd_enqueue_camera_ground_gates: camera_ground_gates on the device - g[0] of every frame with a ground whose camera's fold
+        (d_fold, ncams CameraFold in device memory) solves GF_OK under fold_min_points becomes that plane with
+        max(k_sigma * rms, gate_min); d_gates: nframes FrameGates in device memory, in/out"""
+        _check(lib().ssd_enqueue_camera_ground_gates(self._h, C.c_void_p(d_moments), C.c_void_p(d_camera_of_frame), int(nframes), C.c_void_p(d_fold),
+                                                     int(ncams), int(fold_min_points), float(k_sigma), float(gate_min), C.c_void_p(stream or 0),
+                                                     C.c_void_p(d_gates)))
+
+    def enqueue_cameras_surface_refit_folded(self, d_ptr, nframes, d_prev, d_moments, min_points=200, k_sigma=2.5, gate_min=0.0,
+                                             fold_min_points=2000, depth=False, stride_bytes=None, stream=None):
+        """ssd_enqueue_cameras_surface_refit_folded: enqueue_cameras_surface_refit_device with the camera's gate - the records at d_prev
+        are also folded per camera on the device and every frame's ground gate becomes its camera's plane, no host copy, no wait"""
+        frame = self.cfg.width * self.cfg.height * (2 if depth else 12)
+        _check(lib().ssd_enqueue_cameras_surface_refit_folded(self._h, C.c_void_p(d_ptr), stride_bytes or frame, nframes, C.c_void_p(stream or 0),
+                                                              INPUT_DEPTH16 if depth else INPUT_VERTICES, C.c_void_p(d_prev), int(min_points),
+                                                              float(k_sigma), float(gate_min), int(fold_min_points), C.c_void_p(d_moments)))
+
+    def camera_drift_resident(self, d_ptr, nframes, camera_of_frame, depth=False, min_points=200, fold_min_points=2000, passes=2, k_sigma=2.5,
+                              gate_min=0.0, camera_gate=True):
+        """The drift watch on frames in device memory, no per-frame record on the host: enqueue_cameras_surface_moments, `passes`
+        device-gated refits behind it - the last one with the camera's gate (enqueue_cameras_surface_refit_folded) when camera_gate -,
+        the fold of the last records on the device, one fetch of the table's CameraFold records and camera_drift_from_fold
+        -> (list of FrameResult, list of CameraDrift, one per camera of the table)"""
+        if not getattr(self, "_cameras", None):
+            raise SsdError("camera_drift_resident: the handle has no camera table (set_cameras)")
+        idx = self._camera_index(camera_of_frame, nframes)
+        ncams, dev, rec = len(self._cameras), self.device, C.sizeof(FrameMoments) * nframes
+        bufs = []
+        try:
+            for nbytes in (rec, rec, 4 * nframes, C.sizeof(CameraFold) * ncams):
+                p = C.c_void_p()
+                _check(lib().ssd_device_alloc(dev, nbytes, C.byref(p)))
+                bufs.append(p)
+            d_first, d_refit, d_idx, d_fold = (b.value for b in bufs)
+            idx32 = idx.astype(np.int32)
+            _check(lib().ssd_device_upload(dev, C.c_void_p(d_idx), idx32.ctypes.data_as(C.c_void_p), idx32.nbytes))
+            self.enqueue_cameras_surface_moments(d_ptr, nframes, idx, d_first, depth=depth)
+            for p in range(passes):
+                refit = self.enqueue_cameras_surface_refit_folded if camera_gate and p == passes - 1 else self.enqueue_cameras_surface_refit_device
+                kw = dict(fold_min_points=fold_min_points) if camera_gate and p == passes - 1 else {}
+                refit(d_ptr, nframes, d_first if p == 0 else d_refit, d_refit, min_points=min_points, k_sigma=k_sigma, gate_min=gate_min, depth=depth, **kw)
+            res = self.fetch_list(nframes)
+            if passes:
+                self.fetch_surface_refit()          # the pass ran on its workspace's stream: the fold below goes behind it
+            self.enqueue_camera_fold(d_refit if passes else d_first, d_idx, nframes, ncams, d_fold)
+            fold = (CameraFold * ncams)()
+            _check(lib().ssd_device_download(dev, fold, C.c_void_p(d_fold), C.sizeof(fold)))
+            return res, camera_drift_from_fold(fold, self._cameras, min_points=fold_min_points)
+        finally:
+            lib().ssd_device_sync(dev)              # nothing enqueued above still reads the buffers
+            for b in bufs:
+                lib().ssd_device_free(dev, b)
 
     def surface_moments_time_ms(self, back=0):
         """Device time of the surface-moments pass of the enqueue `back` calls ago (0.0: it gathered none); timing must be on."""

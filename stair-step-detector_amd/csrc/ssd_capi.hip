@@ -11,6 +11,7 @@
 #include "ssd_ground.h"
 #include "ssd_refit.h"
 #include "ssd_solve.h"
+#include "ssd_fold.h"
 
 #include <algorithm>
 #include <charconv>
@@ -119,31 +120,8 @@ int ssd_calibration_identity(ssd_calibration *out)
   return SSD_OK;
 }
 
-/* CameraToWorld from the floor's plane in camera coordinates (unit normal n0 pointing away from the camera, dist = n0 . a point of
- * the plane): the rest of Transformation_<3>(triangleInPlane), transformation.cpp:108-157, behind its normal.  Shared by
- * ssd_calibration_from_points and ssd_calibration_from_plane (the ground fit); false in the degenerate cases (reference assert,
- * transformation.cpp:153). */
-static bool camera_to_world_from_plane(double n0x, double n0y, double n0z, double dist, double a[9], double b[3])
-{
-  struct V3 { double x, y, z; };
-  auto cross = [](V3 p, V3 q) { return V3{ p.y * q.z - p.z * q.y, p.z * q.x - p.x * q.z, p.x * q.y - p.y * q.x }; };
-  auto norm = [](V3 p)
-  {
-    const double m2 = p.x * p.x + p.y * p.y + p.z * p.z;
-    const double rm = 1.0 / std::sqrt(m2);
-    return V3{ p.x * rm, p.y * rm, p.z * rm };
-  };
-  const V3 zB{ -n0x, -n0y, -n0z };
-  const V3 yB = norm(V3{ 0.0, -zB.z / zB.y, 1.0 });
-  const V3 xB = cross(yB, zB);
-  if(!(dist > 0.0) || !std::isfinite(yB.y) || !std::isfinite(xB.x))
-    return false;
-  a[0] = xB.x; a[1] = xB.y; a[2] = xB.z;
-  a[3] = yB.x; a[4] = yB.y; a[5] = yB.z;
-  a[6] = zB.x; a[7] = zB.y; a[8] = zB.z;
-  b[0] = 0.0; b[1] = 0.0; b[2] = dist;
-  return true;
-}
+/* camera_to_world_from_plane - CameraToWorld from the floor's plane in camera coordinates, shared by ssd_calibration_from_points,
+ * ssd_calibration_from_plane and the ground fit - is ssd_solve.h's: the device asks it too (k_camera_ground_gates) */
 
 int ssd_calibration_from_plane(const double n0[3], double dist, const ssd_calibration *prior, ssd_calibration *out)
 {
@@ -600,6 +578,7 @@ int ssd_destroy(ssd_handle *h)
   if(h->hRefitGates) (void)hipHostFree(h->hRefitGates);
   if(h->refitGatesCopied) (void)hipEventDestroy(h->refitGatesCopied);
   if(h->refitDone) (void)hipEventDestroy(h->refitDone);
+  if(h->dCamFold) (void)hipFree(h->dCamFold);
   for(hipEvent_t e : h->evRefit)
     if(e) (void)hipEventDestroy(e);
   if(h->hFallback) (void)hipHostFree(h->hFallback);
@@ -2343,7 +2322,28 @@ struct GateSource
   const ssd_frame_moments *dPrev;                /* records in device memory, solved by k_surface_gates on the pass's stream (section 7i) */
   int minPoints;                                 /* ... under this rule */
   double kSigma, gateMin;
+  bool cameraGate;                               /* ... and the ground gates overlaid with each camera's folded plane (section 7j), */
+  int foldMinPoints;                             /* solved under this one */
 };
+
+/* the fold buffer of ssd_enqueue_cameras_surface_refit_folded and ssd_process_host_cameras_drift, on the first call of either: one record
+ * per camera a table can hold, so that ssd_set_cameras never has to remake it.  One per handle, like the device gates */
+static int fold_prepare(ssd_handle *h)
+{
+  if(h->dCamFold)
+    return SSD_OK;
+  const size_t bytes = sizeof(ssd_camera_fold) * static_cast<size_t>(SSD_MAX_CAMERAS);
+  const hipError_t e = hipMalloc(&h->dCamFold, bytes);
+  if(e != hipSuccess)
+  {
+    h->dCamFold = nullptr;
+    (void)hipGetLastError();
+    return fail(e == hipErrorOutOfMemory ? SSD_E_NOMEM : SSD_E_HIP, std::string("the camera fold's buffer: ") + hipGetErrorString(e));
+  }
+  h->camFoldBytes = bytes;
+  h->bytes += bytes;
+  return SSD_OK;
+}
 
 /* all refit entry points: `cameras` = behind a whole cameras batch (wholeKind 2), under the table and the index that batch left in its
  * workspace; otherwise behind a whole run under the handle's calibration (wholeKind 1) */
@@ -2387,6 +2387,11 @@ static int refit_enqueue_impl(ssd_handle *h, const char *who, bool cameras, cons
   HIP_TRY(hipSetDevice(h->device));
   int rc = refit_prepare(h);
   if(rc) return rc;
+  if(gates.cameraGate)
+  {
+    rc = fold_prepare(h);
+    if(rc) return rc;
+  }
   const bool timing = h->timing && !h->ev.empty();
   if(timing && !h->evRefit[0])
   {
@@ -2428,6 +2433,16 @@ static int refit_enqueue_impl(ssd_handle *h, const char *who, bool cameras, cons
     if(timing) HIP_TRY(hipEventRecord(h->evRefit[0], s));
     launch_surface_gates(gates.dPrev, nframes, gates.minPoints, gates.kSigma, gates.gateMin, h->dRefitGates, s);
     HIP_TRY(hipGetLastError());
+    if(gates.cameraGate)
+    {
+      /* section 7j: the fold of the same records under the batch's own index and the table's count, then each camera's plane over its
+       * frames' ground gates.  The fold buffer is single like the gates, and ordered with them */
+      const int ncams = static_cast<int>(h->camParams.size());
+      launch_camera_fold(gates.dPrev, L.dCamIndex, nframes, ncams, false, h->dCamFold, s);
+      HIP_TRY(hipGetLastError());
+      launch_camera_ground_gates(gates.dPrev, L.dCamIndex, nframes, h->dCamFold, ncams, gates.foldMinPoints, gates.kSigma, gates.gateMin, h->dRefitGates, s);
+      HIP_TRY(hipGetLastError());
+    }
   }
   h->refitHaveLast = true;
   h->refitLastStream = s;
@@ -2458,14 +2473,14 @@ int ssd_enqueue_surface_refit(ssd_handle *h, const void *d_frames, size_t frame_
                               int input, const ssd_frame_gates *gates, ssd_frame_moments *d_out)
 {
   return refit_enqueue_impl(h, "ssd_enqueue_surface_refit", false, d_frames, frame_stride_bytes, nframes, stream, input,
-                            GateSource{ gates, nullptr, 0, 0.0, 0.0 }, d_out);
+                            GateSource{ gates, nullptr, 0, 0.0, 0.0, false, 0 }, d_out);
 }
 
 int ssd_enqueue_cameras_surface_refit(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream,
                                       int input, const ssd_frame_gates *gates, ssd_frame_moments *d_out)
 {
   return refit_enqueue_impl(h, "ssd_enqueue_cameras_surface_refit", true, d_frames, frame_stride_bytes, nframes, stream, input,
-                            GateSource{ gates, nullptr, 0, 0.0, 0.0 }, d_out);
+                            GateSource{ gates, nullptr, 0, 0.0, 0.0, false, 0 }, d_out);
 }
 
 /* ---- surface gates on the device (include/ssd_hip.h) ---------------------------------------------------- */
@@ -2489,7 +2504,7 @@ int ssd_enqueue_surface_refit_device(ssd_handle *h, const void *d_frames, size_t
                                      const ssd_frame_moments *d_prev, int min_points, double k_sigma, double gate_min, ssd_frame_moments *d_out)
 {
   return refit_enqueue_impl(h, "ssd_enqueue_surface_refit_device", false, d_frames, frame_stride_bytes, nframes, stream, input,
-                            GateSource{ nullptr, d_prev, min_points, k_sigma, gate_min }, d_out);
+                            GateSource{ nullptr, d_prev, min_points, k_sigma, gate_min, false, 0 }, d_out);
 }
 
 int ssd_enqueue_cameras_surface_refit_device(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream, int input,
@@ -2497,7 +2512,53 @@ int ssd_enqueue_cameras_surface_refit_device(ssd_handle *h, const void *d_frames
                                              ssd_frame_moments *d_out)
 {
   return refit_enqueue_impl(h, "ssd_enqueue_cameras_surface_refit_device", true, d_frames, frame_stride_bytes, nframes, stream, input,
-                            GateSource{ nullptr, d_prev, min_points, k_sigma, gate_min }, d_out);
+                            GateSource{ nullptr, d_prev, min_points, k_sigma, gate_min, false, 0 }, d_out);
+}
+
+/* ---- camera fold on the device (include/ssd_hip.h) -------------------------------------------------------- */
+
+static int check_fold_args(const ssd_handle *h, const char *who, bool pointers, int nframes, int ncams)
+{
+  if(!pointers)
+    return fail(SSD_E_ARG, std::string(who) + ": null argument");
+  if(nframes < 1 || nframes > h->F)
+    return fail(SSD_E_ARG, std::string(who) + ": nframes must lie in 1 .. max_frames_per_batch");
+  if(ncams < 1 || ncams > SSD_MAX_CAMERAS)
+    return fail(SSD_E_ARG, std::string(who) + ": ncams must be 1.." + std::to_string(SSD_MAX_CAMERAS));
+  return SSD_OK;
+}
+
+int ssd_enqueue_camera_fold(ssd_handle *h, const ssd_frame_moments *d_moments, const int32_t *d_camera_of_frame, int nframes, int ncams,
+                            int accumulate, void *stream, ssd_camera_fold *d_fold)
+{
+  const int rc = check_fold_args(h, "ssd_enqueue_camera_fold", h && d_moments && d_camera_of_frame && d_fold, nframes, ncams);
+  if(rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  launch_camera_fold(d_moments, d_camera_of_frame, nframes, ncams, accumulate != 0, d_fold, static_cast<hipStream_t>(stream));
+  HIP_TRY(hipGetLastError());
+  return SSD_OK;
+}
+
+int ssd_enqueue_camera_ground_gates(ssd_handle *h, const ssd_frame_moments *d_moments, const int32_t *d_camera_of_frame, int nframes,
+                                    const ssd_camera_fold *d_fold, int ncams, int fold_min_points, double k_sigma, double gate_min,
+                                    void *stream, ssd_frame_gates *d_gates)
+{
+  int rc = check_fold_args(h, "ssd_enqueue_camera_ground_gates", h && d_moments && d_camera_of_frame && d_fold && d_gates, nframes, ncams);
+  if(!rc) rc = check_gate_rule("ssd_enqueue_camera_ground_gates", k_sigma, gate_min);
+  if(rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  launch_camera_ground_gates(d_moments, d_camera_of_frame, nframes, d_fold, ncams, fold_min_points, k_sigma, gate_min, d_gates,
+                             static_cast<hipStream_t>(stream));
+  HIP_TRY(hipGetLastError());
+  return SSD_OK;
+}
+
+int ssd_enqueue_cameras_surface_refit_folded(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream, int input,
+                                             const ssd_frame_moments *d_prev, int min_points, double k_sigma, double gate_min,
+                                             int fold_min_points, ssd_frame_moments *d_out)
+{
+  return refit_enqueue_impl(h, "ssd_enqueue_cameras_surface_refit_folded", true, d_frames, frame_stride_bytes, nframes, stream, input,
+                            GateSource{ nullptr, d_prev, min_points, k_sigma, gate_min, true, fold_min_points }, d_out);
 }
 
 int ssd_fetch_surface_refit(ssd_handle *h, void *)
@@ -2572,7 +2633,7 @@ static int process_host_refit_impl(ssd_handle *h, const char *who, const void *f
       for(int pass = 0; pass < passes; pass++)
       {
         rc = refit_enqueue_impl(h, who, camOf != nullptr, buf, feed.f.devFrameBytes, n, h->ingestCompute, input,
-                                GateSource{ nullptr, pass == 0 ? dFirst : dRefit, min_points, k_sigma, gate_min }, dRefit);
+                                GateSource{ nullptr, pass == 0 ? dFirst : dRefit, min_points, k_sigma, gate_min, false, 0 }, dRefit);
         if(rc) return rc;
       }
       rc = ssd_fetch_back(h, results + done, n, 0);
@@ -2602,7 +2663,7 @@ static int process_host_refit_impl(ssd_handle *h, const char *who, const void *f
           if(rc) return rc;
         }
         rc = refit_enqueue_impl(h, who, camOf != nullptr, buf, feed.f.devFrameBytes, n, h->ingestCompute, input,
-                                GateSource{ gates.data(), nullptr, 0, 0.0, 0.0 }, dRefit);
+                                GateSource{ gates.data(), nullptr, 0, 0.0, 0.0, false, 0 }, dRefit);
         if(rc) return rc;
         rc = ssd_fetch_surface_refit(h, nullptr);
         if(rc) return rc;
@@ -2670,6 +2731,71 @@ int ssd_process_host_cameras_surfaces_refit_device(ssd_handle *h, const void *fr
   const int rc = check_host_batch(h, "ssd_process_host_cameras_surfaces_refit_device", h && frames && results && out, nframes, input, kCameraTable, camera_of_frame);
   return rc ? rc : process_host_refit_impl(h, "ssd_process_host_cameras_surfaces_refit_device", frames, nframes, camera_of_frame, input, results, first, refit,
                                            min_points, k_sigma, gate_min, passes, out, true);
+}
+
+/* The drift watch with the fold on the device: process_host_refit_impl's device-gated slices with an accumulating
+ * k_camera_fold behind each slice's last pass where that function copies the records out, and one copy of the table's fold at the end */
+int ssd_process_host_cameras_drift(ssd_handle *h, const void *frames, int nframes, const uint16_t *camera_of_frame, int input,
+                                   ssd_frame_result *results, int min_points, double k_sigma, double gate_min, int passes, int fold_min_points,
+                                   ssd_camera_drift *out)
+{
+  const char *who = "ssd_process_host_cameras_drift";
+  int rc = check_host_batch(h, who, h && frames && results && out, nframes, input, kCameraTable, camera_of_frame);
+  if(rc) return rc;
+  if(passes < 0 || passes > 4)
+    return fail(SSD_E_ARG, std::string(who) + ": passes must lie in 0 .. 4");
+  rc = check_gate_rule(who, k_sigma, gate_min);
+  if(rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  SliceFeed feed{ h, host_frames(h, input, kForPipeline), frames, nframes };
+  rc = feed.prepare();
+  if(rc) return rc;
+  rc = labels_prepare(h, static_cast<size_t>(feed.slice) * sizeof(ssd_frame_moments));
+  if(!rc) rc = fold_prepare(h);
+  if(rc) return rc;
+  if(h->refitHaveLast)
+    HIP_TRY(hipEventSynchronize(h->refitDone));                     /* a folded pass still on its way owns the fold buffer */
+  ssd_frame_moments *dFirst = reinterpret_cast<ssd_frame_moments *>(h->labelStage[0]), *dRefit = reinterpret_cast<ssd_frame_moments *>(h->labelStage[1]);
+  const int ncams = static_cast<int>(h->camParams.size());
+  hipStream_t s = nullptr;
+  for(int c = 0; c < feed.slices(); c++)
+  {
+    const void *buf;
+    int done, n;
+    rc = feed.stage(c);
+    if(!rc) rc = feed.stage(c + 1);
+    if(!rc) rc = feed.ready(c, buf, done, n);
+    if(rc) return rc;
+    rc = enqueue_impl(h, buf, feed.f.devFrameBytes, n, h->ingestCompute, SSD_STAGE_ALL, feed.f.depth, nullptr, 0, camera_of_frame + done, dFirst);
+    if(rc) return rc;
+    for(int pass = 0; pass < passes; pass++)
+    {
+      rc = refit_enqueue_impl(h, who, true, buf, feed.f.devFrameBytes, n, h->ingestCompute, input,
+                              GateSource{ nullptr, pass == 0 ? dFirst : dRefit, min_points, k_sigma, gate_min, false, 0 }, dRefit);
+      if(rc) return rc;
+    }
+    /* the slice's last records onto the table's fold, behind them on the stream they were made on, under the index the enqueue left in
+     * its workspace.  The slice is then waited for: the next one writes the same two record buffers, and folds into the same records */
+    const ssd_lane &L = h->lane[h->lastLane];
+    s = L.lastStream;
+    launch_camera_fold(passes ? dRefit : dFirst, L.dCamIndex, n, ncams, c > 0, h->dCamFold, s);
+    HIP_TRY(hipGetLastError());
+    rc = ssd_fetch_back(h, results + done, n, 0);
+    if(rc) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    rc = feed.consumed(c, s);
+    if(rc) return rc;
+  }
+  std::vector<ssd_camera_fold> fold(static_cast<size_t>(ncams));
+  HIP_TRY(hipMemcpyAsync(fold.data(), h->dCamFold, sizeof(ssd_camera_fold) * fold.size(), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  std::vector<ssd_camera> cams(static_cast<size_t>(ncams));
+  for(int c = 0; c < ncams; c++)
+  {
+    std::memset(&cams[c], 0, sizeof(ssd_camera));
+    cams[c].cal = calibration_of(h->camParams[c]);
+  }
+  return ssd_camera_drift_from_fold(fold.data(), cams.data(), ncams, fold_min_points, out);
 }
 
 /* host only: no handle, no device */
@@ -2820,40 +2946,40 @@ int ssd_camera_drift_fold(const ssd_frame_moments *moments, const uint16_t *came
   for(int i = 0; i < nframes; i++)
     if(camera_of_frame[i] >= ncams)
       return fail(SSD_E_ARG, "ssd_camera_drift_fold: frame " + std::to_string(i) + " names camera " + std::to_string(camera_of_frame[i]) + " of " + std::to_string(ncams));
-  constexpr int kSums = static_cast<int>(sizeof(ssd_surface_moments) / sizeof(int64_t));     /* the ten sums of m, then n_far */
-  static_assert(sizeof(ssd_surface_moments) == sizeof(int64_t) * (kGroundSums + 1) && offsetof(ssd_surface_moments, n_far) == sizeof(ssd_ground_moments),
-                "ssd_surface_moments is the ten sums and n_far, contiguous");
+  static_assert(kFoldSums == kGroundSums + 1, "the fold's sums are the ground fit's ten and n_far");
   std::memset(out, 0, sizeof(ssd_camera_drift) * static_cast<size_t>(ncams));
   for(int c = 0; c < ncams; c++)
     out[c].camera = c;
-  /* in index order; a frame whole or not at all: every sum is tried before any is taken */
+  /* in index order; a frame whole or not at all: ssd_fold.h's step, which k_camera_fold runs too */
   for(int i = 0; i < nframes; i++)
-  {
-    ssd_camera_drift &d = out[camera_of_frame[i]];
-    d.frames++;
-    const ssd_frame_moments &fm = moments[i];
-    if(fm.ground != 1 || fm.n_surfaces < 1)
-      continue;
-    int64_t have[kSums], sum[kSums];
-    std::memcpy(have, &d.m, sizeof(d.m));
-    have[kSums - 1] = d.n_far;
-    const int64_t *add = reinterpret_cast<const int64_t *>(&fm.s[0]);
-    bool fits = true;
-    for(int k = 0; k < kSums; k++)
-      if(__builtin_add_overflow(have[k], add[k], &sum[k]))
-        fits = false;
-    if(!fits)
-    {
-      d.frames_left++;
-      continue;
-    }
-    std::memcpy(&d.m, sum, sizeof(d.m));
-    d.n_far = sum[kSums - 1];
-    d.frames_ground++;
-  }
+    fold_step(out[camera_of_frame[i]], moments[i]);
   for(int c = 0; c < ncams; c++)
   {
     const int rc = ssd_ground_fit_solve(&out[c].m, &cams[c].cal, min_points, &out[c].fit);
+    if(rc) return rc;
+  }
+  return SSD_OK;
+}
+
+/* host only: no handle, no device */
+int ssd_camera_drift_from_fold(const ssd_camera_fold *fold, const ssd_camera *cams, int ncams, int min_points, ssd_camera_drift *out)
+{
+  if(!fold || !cams || !out)
+    return fail(SSD_E_ARG, "ssd_camera_drift_from_fold: null");
+  if(ncams < 1 || ncams > SSD_MAX_CAMERAS)
+    return fail(SSD_E_ARG, "ssd_camera_drift_from_fold: ncams must be 1.." + std::to_string(SSD_MAX_CAMERAS));
+  for(int c = 0; c < ncams; c++)
+    if(fold[c].camera != c)
+      return fail(SSD_E_ARG, "ssd_camera_drift_from_fold: record " + std::to_string(c) + " names camera " + std::to_string(fold[c].camera));
+  static_assert(offsetof(ssd_camera_drift, fit) == sizeof(ssd_camera_fold), "ssd_camera_fold is the head of ssd_camera_drift");
+  std::memset(out, 0, sizeof(ssd_camera_drift) * static_cast<size_t>(ncams));
+  for(int c = 0; c < ncams; c++)
+  {
+    ssd_camera_drift &d = out[c];
+    d.camera = fold[c].camera; d.frames = fold[c].frames; d.frames_ground = fold[c].frames_ground; d.frames_left = fold[c].frames_left;
+    d.m = fold[c].m;
+    d.n_far = fold[c].n_far;
+    const int rc = ssd_ground_fit_solve(&d.m, &cams[c].cal, min_points, &d.fit);
     if(rc) return rc;
   }
   return SSD_OK;

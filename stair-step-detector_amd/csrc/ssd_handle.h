@@ -177,6 +177,10 @@ struct ssd_handle
   hipEvent_t evRefit[2] = { nullptr, nullptr };   /* around the pass of a timed call, made on the first one */
   bool refitHaveLast = false, refitTimed = false;
   size_t refitBytes = 0;                    /* their share of `bytes` */
+  /* the camera fold (ssd_enqueue_cameras_surface_refit_folded, ssd_process_host_cameras_drift): SSD_MAX_CAMERAS
+   * records, made on the first call of either.  One set: the refit orders its users as it orders the device gates' */
+  ssd_camera_fold *dCamFold = nullptr;
+  size_t camFoldBytes = 0;                  /* its share of `bytes` */
 };
 
 #endif /* SSD_HANDLE_H_ */

@@ -64,6 +64,12 @@ void launch_riser_moments(const float *xyz, size_t strideFloats, const Params &P
 /* k_surface_gates (ssd_kernels_solve.hip): rec[i] -> out[i] for nframes >= 1 records, both in device memory and not
  * overlapping, on stream s; every byte of out[0 .. nframes) is written, nothing behind them */
 void launch_surface_gates(const ssd_frame_moments *rec, int nframes, int min_points, double k_sigma, double gate_min, ssd_frame_gates *out, hipStream_t s);
+/* k_camera_fold and k_camera_ground_gates (ssd_kernels_fold.hip), on stream s, everything in device memory:
+ * rec[0 .. nframes) under the index camOf (one int per frame) -> out[0 .. ncams), all 104 bytes of each, on top of what they hold when
+ * `accumulate`; and the camera's gate from fold[0 .. ncams) over g[0] of gates[0 .. nframes), every other byte left as it is */
+void launch_camera_fold(const ssd_frame_moments *rec, const int *camOf, int nframes, int ncams, bool accumulate, ssd_camera_fold *out, hipStream_t s);
+void launch_camera_ground_gates(const ssd_frame_moments *rec, const int *camOf, int nframes, const ssd_camera_fold *fold, int ncams, int min_points,
+                                double k_sigma, double gate_min, ssd_frame_gates *gates, hipStream_t s);
 void launch_predict_cams(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, int nframes, const DepthSrc *depth, int *fallback, int poolPlanes, int sabotage, hipStream_t s, const CameraSel &cams);
 void launch_hist_cams(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, uint2 *tileMasks, size_t tileMaskStride, int nframes, int chunkPoints, const DepthSrc *depth, unsigned long long *planeImg, hipStream_t s, const CameraSel &cams);
 void launch_peaks_cams(const Params &P, FrameState *st, int nframes, DebugFrame *dbg, int *fallback, hipStream_t s, const CameraSel &cams);

@@ -1,8 +1,9 @@
 /*
  * ssd_solve.h — the solve the fits share (DESIGN.md sections 7c, 7d, 7g and 7i): integer moments -> the centred scatter, exact in
  * 128-bit integers -> its eigenvalues and eigenvectors (cyclic Jacobi) -> the plane of lambda_min, and the trimmed refit's gate rule
- * on top of it.  Stated once for the host (ssd_ground_fit_solve, ssd_surface_fit_solve, ssd_riser_fit_solve,
- * ssd_surface_gates_from_moments: ssd_capi.hip) and the device (k_surface_gates: ssd_kernels_solve.hip).
+ * on top of it; and camera_to_world_from_plane, the pose a floor's plane gives (section 7j).  Stated once for the host
+ * (ssd_ground_fit_solve, ssd_surface_fit_solve, ssd_riser_fit_solve, ssd_surface_gates_from_moments, the calibrations from a plane
+ * and from points: ssd_capi.hip) and the device (k_surface_gates: ssd_kernels_solve.hip, k_camera_ground_gates: ssd_kernels_fold.hip).
  * Both sides are compiled without FMA contraction; every operation is +, -, *, /, sqrt or a comparison of doubles, each correctly
  * rounded on both sides, in one order: they agree bit for bit (tests/golden/solve_goldens.json holds the host to the text this was
  * moved from, tests/test_gpu_surface_gates.py the device to the host).  Nothing transcendental is here: atan2 and asin stay in the
@@ -147,6 +148,32 @@ __host__ __device__ inline int plane_of_moments(const ssd_ground_moments *m, int
   }
   pl.dist = dist;
   return SSD_GF_OK;
+}
+
+/* CameraToWorld from the floor's plane in camera coordinates (unit normal n0 pointing away from the camera, dist = n0 . a point of
+ * the plane): the rest of Transformation_<3>(triangleInPlane), transformation.cpp:108-157, behind its normal.  Shared by
+ * ssd_calibration_from_points, ssd_calibration_from_plane and ssd_ground_fit_solve on the host and by k_camera_ground_gates on the
+ * device (which needs only whether it succeeds: section 7j); false in the degenerate cases (reference assert, transformation.cpp:153). */
+__host__ __device__ inline bool camera_to_world_from_plane(double n0x, double n0y, double n0z, double dist, double a[9], double b[3])
+{
+  struct V3 { double x, y, z; };
+  auto cross = [](V3 p, V3 q) { return V3{ p.y * q.z - p.z * q.y, p.z * q.x - p.x * q.z, p.x * q.y - p.y * q.x }; };
+  auto norm = [](V3 p)
+  {
+    const double m2 = p.x * p.x + p.y * p.y + p.z * p.z;
+    const double rm = 1.0 / sqrt(m2);
+    return V3{ p.x * rm, p.y * rm, p.z * rm };
+  };
+  const V3 zB{ -n0x, -n0y, -n0z };
+  const V3 yB = norm(V3{ 0.0, -zB.z / zB.y, 1.0 });
+  const V3 xB = cross(yB, zB);
+  if(!(dist > 0.0) || !std::isfinite(yB.y) || !std::isfinite(xB.x))
+    return false;
+  a[0] = xB.x; a[1] = xB.y; a[2] = xB.z;
+  a[3] = yB.x; a[4] = yB.y; a[5] = yB.z;
+  a[6] = zB.x; a[7] = zB.y; a[8] = zB.z;
+  b[0] = 0.0; b[1] = 0.0; b[2] = dist;
+  return true;
 }
 
 /* The gate rule of the trimmed refit (ssd_surface_gates_from_moments, k_surface_gates): the fitted plane in camera coordinates and
