@@ -46,6 +46,42 @@ int fail(int code, const std::string &msg)
       return fail(SSD_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));                        \
   } while(0)
 
+/* a failed HIP call as a return code: SSD_E_NOMEM or SSD_E_HIP (ssd_owned.h), `what` in front of HIP's text */
+int hip_fail(hipError_t e, const std::string &what)
+{
+  return fail(hip_error_code(e), what + hipGetErrorString(e));
+}
+
+/* the riser pass's records and the riser moments': a zeroed device buffer (counted) and its pinned mirror, both or neither */
+template<typename T>
+hipError_t make_records(ssd_handle *h, DeviceBuf<T> &dev, PinnedBuf<T> &pinned, size_t bytes)
+{
+  DeviceBuf<T> d;
+  PinnedBuf<T> p;
+  hipError_t e = d.alloc(bytes, &h->bytes);
+  if(e == hipSuccess) e = hipMemset(d, 0, bytes);
+  if(e == hipSuccess) e = p.alloc(bytes);
+  if(e != hipSuccess)
+    return e;
+  dev = std::move(d);
+  pinned = std::move(p);
+  return hipSuccess;
+}
+
+/* a pinned buffer of one record per frame of a host batch (the device buffer holds one enqueue's), grown to nframes */
+template<typename T>
+int grow_pinned_batch(ssd_handle *h, PinnedBuf<T> &buf, int &cap, int nframes)
+{
+  if(cap >= nframes)
+    return SSD_OK;
+  HIP_TRY(hipStreamSynchronize(h->ingestCompute));
+  buf.reset();
+  cap = 0;
+  HIP_TRY(buf.alloc(sizeof(T) * static_cast<size_t>(nframes)));
+  cap = nframes;
+  return SSD_OK;
+}
+
 #ifdef SSD_TUNING
 /* tools builds only (see ssd_tuning, ssd_handle.h): overrides from the environment, read once per handle */
 int env_int(const char *name, int dflt)
@@ -438,15 +474,14 @@ int ssd_create(const ssd_config *cfg, const ssd_calibration *cal, int device, ss
   const size_t planeBytes = single_pass_geometry(P.W, P.H) && single_pass_batch(h->F, P.nPoints)
                             ? static_cast<size_t>(plane_pool_size(h->F, h->P.nPoints)) * h->imgWords * 8 : 0;
   h->planePool = static_cast<int>(plane_pool_size(h->F, h->P.nPoints));
-  auto cleanup = [&]() { ssd_destroy(h); };
 #define HIP_TRY_H(expr)                                                                                 \
   do                                                                                                    \
   {                                                                                                     \
     const hipError_t e_ = (expr);                                                                       \
     if(e_ != hipSuccess)                                                                                \
     {                                                                                                   \
-      cleanup();                                                                                        \
-      return fail(e_ == hipErrorOutOfMemory ? SSD_E_NOMEM : SSD_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+      ssd_destroy(h);                                                                                   \
+      return hip_fail(e_, #expr ": ");                                                                  \
     }                                                                                                   \
   } while(0)
   h->tileMaskStride = (static_cast<size_t>(P.nPoints) + kTileHost - 1) / kTileHost * (kTileHost / kCellHost)      /* cell records per frame */
@@ -456,26 +491,26 @@ int ssd_create(const ssd_config *cfg, const ssd_calibration *cal, int device, ss
   for(int k = 0; k < depth; k++)
   {
     ssd_lane &L = h->lane[k];
-    HIP_TRY_H(hipMalloc(&L.dState, sizeof(FrameState) * h->F));
-    HIP_TRY_H(hipMalloc(&L.dStepImg, stepBytes));
-    HIP_TRY_H(hipMalloc(&L.dGroundImg, groundBytes));
-    HIP_TRY_H(hipMalloc(&L.dTileMasksBase, maskBytes));
+    HIP_TRY_H(L.dState.alloc(sizeof(FrameState) * h->F, &h->bytes));
+    HIP_TRY_H(L.dStepImg.alloc(stepBytes, &h->bytes));
+    HIP_TRY_H(L.dGroundImg.alloc(groundBytes, &h->bytes));
+    HIP_TRY_H(L.dTileMasksBase.alloc(maskBytes, &h->bytes));
     L.dTileMasks = L.dTileMasksBase;
-    HIP_TRY_H(hipEventCreateWithFlags(&L.in, hipEventDisableTiming));
-    HIP_TRY_H(hipEventCreateWithFlags(&L.done, hipEventDisableTiming));
+    HIP_TRY_H(L.in.create(hipEventDisableTiming));
+    HIP_TRY_H(L.done.create(hipEventDisableTiming));
     if(depth > 1)
-      HIP_TRY_H(hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
+      HIP_TRY_H(L.stream.create(hipStreamNonBlocking));
     HIP_TRY_H(hipMemset(L.dState, 0, sizeof(FrameState) * h->F));
     HIP_TRY_H(hipMemset(L.dStepImg, 0, stepBytes));
     HIP_TRY_H(hipMemset(L.dGroundImg, 0, groundBytes));
   }
   const size_t resBytes = sizeof(ssd_frame_result) * h->F * h->nSlots;
-  HIP_TRY_H(hipMalloc(&h->dResults, resBytes));
-  HIP_TRY_H(hipHostMalloc(&h->hResults, resBytes, hipHostMallocDefault));
+  HIP_TRY_H(h->dResults.alloc(resBytes, &h->bytes));
+  HIP_TRY_H(h->hResults.alloc(resBytes));
   std::memset(h->hResults, 0, resBytes);
   HIP_TRY_H(hipHostGetDevicePointer(reinterpret_cast<void **>(&h->hResultsDev), h->hResults, 0));
   for(int k = 0; k < h->nSlots; k++)
-    HIP_TRY_H(hipEventCreateWithFlags(&h->resultsReady[k], hipEventDisableTiming));
+    HIP_TRY_H(h->resultsReady[k].create(hipEventDisableTiming));
   HIP_TRY_H(hipMemset(h->dResults, 0, resBytes));
   /* The planes of the single pass are an optimisation (results are the same without them): when they do not fit beside the
    * rest - a larger batch, more workspaces, memory shared with the caller's frames - the handle gives up the planes of ALL its
@@ -484,63 +519,20 @@ int ssd_create(const ssd_config *cfg, const ssd_calibration *cal, int device, ss
    * followed them used to fail the whole handle.  SSD_MAX_PLANE_BYTES (environment) bounds what a handle may take for the planes
    * of all its workspaces together - for a GPU shared with other tenants; a workspace whose planes would cross it counts as one
    * whose allocation failed.  Why a handle has no planes is kept for ssd_last_error() (ssd_create still returns SSD_OK). */
-  size_t planeBytesHeld = 0;
   if(planeBytes)
   {
-    bool ok = true;
-    std::string why;
     unsigned long long cap = ~0ull;
     if(const char *e = std::getenv("SSD_MAX_PLANE_BYTES"))
       cap = std::strtoull(e, nullptr, 10);
-    for(int k = 0; k < depth && ok; k++)
+    std::string why;
+    if(planes_make(h, cap, true, why) != hipSuccess)
     {
-      ssd_lane &L = h->lane[k];
-      if(static_cast<unsigned long long>(k + 1) * planeBytes > cap)
-      {
-        ok = false;
-        why = "SSD_MAX_PLANE_BYTES = " + std::to_string(cap) + " < " + std::to_string(static_cast<unsigned long long>(depth) * planeBytes);
-        break;
-      }
-      const hipError_t e1 = hipMalloc(&L.dPlaneImg, planeBytes);
-      const hipError_t e2 = e1 == hipSuccess ? hipMalloc(&L.dFallback, sizeof(int) * (kFallbackList + static_cast<size_t>(h->F))) : e1;
-      if(e2 != hipSuccess)
-      {
-        ok = false;
-        why = std::string("hipMalloc of ") + std::to_string(planeBytes) + " bytes for workspace " + std::to_string(k) + ": " + hipGetErrorString(e2);
-      }
-    }
-    if(ok && hipHostMalloc(&h->hFallback, sizeof(int) * 2 * kMaxLanes, hipHostMallocDefault) != hipSuccess)
-    {
-      ok = false;
-      why = "hipHostMalloc of the work lists' counters failed";
-    }
-    if(!ok)
-    {
-      (void)hipGetLastError();                   /* the failed allocation's error is not the handle's */
       g_err = "ssd_create: no planes for the single pass (" + why + "): the handle runs two passes";
-      for(int k = 0; k < depth; k++)
-      {
-        ssd_lane &L = h->lane[k];
-        if(L.dPlaneImg) { (void)hipFree(L.dPlaneImg); L.dPlaneImg = nullptr; }
-        if(L.dFallback) { (void)hipFree(L.dFallback); L.dFallback = nullptr; }
-      }
-      if(h->hFallback) { (void)hipHostFree(h->hFallback); h->hFallback = nullptr; }
       h->singlePassMode = 0;
-    }
-    else
-    {
-      for(int k = 0; k < depth; k++)
-      {
-        HIP_TRY_H(hipMemset(h->lane[k].dPlaneImg, 0, planeBytes));
-        HIP_TRY_H(hipMemset(h->lane[k].dFallback, 0, sizeof(int) * (kFallbackList + static_cast<size_t>(h->F))));
-      }
-      std::memset(h->hFallback, 0, sizeof(int) * 2 * kMaxLanes);
-      planeBytesHeld = planeBytes;
     }
   }
   HIP_TRY_H(hipDeviceSynchronize());
 #undef HIP_TRY_H
-  h->bytes = static_cast<size_t>(depth) * (sizeof(FrameState) * h->F + stepBytes + groundBytes + planeBytesHeld + maskBytes) + resBytes;
   *out = h;
   return SSD_OK;
 }
@@ -551,75 +543,7 @@ int ssd_destroy(ssd_handle *h)
     return SSD_OK;
   (void)hipSetDevice(h->device);
   (void)hipDeviceSynchronize();               /* nothing of this handle is in flight any more (lanes run on their own streams) */
-  for(ssd_lane &L : h->lane)
-  {
-    if(L.dState) (void)hipFree(L.dState);
-    if(L.dStepImg) (void)hipFree(L.dStepImg);
-    if(L.dGroundImg) (void)hipFree(L.dGroundImg);
-    if(L.dPlaneImg) (void)hipFree(L.dPlaneImg);
-    if(L.dFallback) (void)hipFree(L.dFallback);
-    if(L.dTileMasksBase) (void)hipFree(L.dTileMasksBase);
-    if(L.in) (void)hipEventDestroy(L.in);
-    if(L.done) (void)hipEventDestroy(L.done);
-    if(L.stream) (void)hipStreamDestroy(L.stream);
-    if(L.dCamIndex) (void)hipFree(L.dCamIndex);
-    if(L.hCamIndex) (void)hipHostFree(L.hCamIndex);
-    if(L.camCopied) (void)hipEventDestroy(L.camCopied);
-  }
-  if(h->dCams) (void)hipFree(h->dCams);
-  if(h->dCamMaps) (void)hipFree(h->dCamMaps);
-  if(h->dGround) (void)hipFree(h->dGround);
-  if(h->hGround) (void)hipHostFree(h->hGround);
-  if(h->dGroundPriors) (void)hipFree(h->dGroundPriors);
-  if(h->hGroundPriors) (void)hipHostFree(h->hGroundPriors);
-  if(h->groundPriorsCopied) (void)hipEventDestroy(h->groundPriorsCopied);
-  if(h->groundDone) (void)hipEventDestroy(h->groundDone);
-  if(h->dRefitGates) (void)hipFree(h->dRefitGates);
-  if(h->hRefitGates) (void)hipHostFree(h->hRefitGates);
-  if(h->refitGatesCopied) (void)hipEventDestroy(h->refitGatesCopied);
-  if(h->refitDone) (void)hipEventDestroy(h->refitDone);
-  if(h->dCamFold) (void)hipFree(h->dCamFold);
-  for(hipEvent_t e : h->evRefit)
-    if(e) (void)hipEventDestroy(e);
-  if(h->hFallback) (void)hipHostFree(h->hFallback);
-  if(h->dDepthMaps) (void)hipFree(h->dDepthMaps);
-  if(h->dResults) (void)hipFree(h->dResults);
-  if(h->hResults) (void)hipHostFree(h->hResults);
-  for(hipEvent_t e : h->resultsReady)
-    if(e) (void)hipEventDestroy(e);
-  for(int k = 0; k < 2; k++)
-  {
-    if(h->ingestBuf[k]) (void)hipFree(h->ingestBuf[k]);
-    if(h->ingestCopied[k]) (void)hipEventDestroy(h->ingestCopied[k]);
-    if(h->ingestCopied2[k]) (void)hipEventDestroy(h->ingestCopied2[k]);
-    if(h->ingestConsumed[k]) (void)hipEventDestroy(h->ingestConsumed[k]);
-  }
-  if(h->ingestCopy) (void)hipStreamDestroy(h->ingestCopy);
-  if(h->ingestCopy2) (void)hipStreamDestroy(h->ingestCopy2);
-  if(h->ingestCompute) (void)hipStreamDestroy(h->ingestCompute);
-  if(h->dRisers) (void)hipFree(h->dRisers);
-  if(h->hRisers) (void)hipHostFree(h->hRisers);
-  if(h->hRisersBatch) (void)hipHostFree(h->hRisersBatch);
-  if(h->dRiserMoments) (void)hipFree(h->dRiserMoments);
-  if(h->hRiserMoments) (void)hipHostFree(h->hRiserMoments);
-  if(h->hRiserMomentsBatch) (void)hipHostFree(h->hRiserMomentsBatch);
-  if(h->dDebug) (void)hipFree(h->dDebug);
-  if(h->dDebugImg) (void)hipFree(h->dDebugImg);
-  for(hipEvent_t e : h->evPredict)
-    if(e) (void)hipEventDestroy(e);
-  for(hipEvent_t e : h->evSurface)
-    (void)hipEventDestroy(e);
-  for(hipEvent_t e : h->evLabels)
-    (void)hipEventDestroy(e);
-  for(int k = 0; k < 2; k++)
-  {
-    if(h->labelStage[k]) (void)hipFree(h->labelStage[k]);
-    if(h->labelsCopied[k]) (void)hipEventDestroy(h->labelsCopied[k]);
-  }
-  if(h->labelsCopy) (void)hipStreamDestroy(h->labelsCopy);
-  for(hipEvent_t e : h->ev)
-    (void)hipEventDestroy(e);
-  delete h;
+  delete h;                                    /* every resource is a member that frees itself (ssd_owned.h) */
   return SSD_OK;
 }
 
@@ -634,60 +558,27 @@ int ssd_set_single_pass(ssd_handle *h, int enable)
     return fail(SSD_E_ARG, "ssd_set_single_pass: null handle");
   HIP_TRY(hipSetDevice(h->device));
   HIP_TRY(hipDeviceSynchronize());            /* the planes of batches in flight are in use */
-  const size_t planeBytes = static_cast<size_t>(plane_pool_size(h->F, h->P.nPoints)) * h->imgWords * 8;
-  const size_t listBytes = sizeof(int) * (kFallbackList + static_cast<size_t>(h->F));
   if(!enable)
   {
-    for(int k = 0; k < h->depth; k++)
-    {
-      ssd_lane &L = h->lane[k];
-      if(L.dPlaneImg)
-      {
-        (void)hipFree(L.dPlaneImg);
-        L.dPlaneImg = nullptr;
-        h->bytes -= planeBytes;
-      }
-      if(L.dFallback)
-      {
-        (void)hipFree(L.dFallback);
-        L.dFallback = nullptr;
-      }
-    }
+    planes_drop(h);
     h->singlePassMode = 0;
     return SSD_OK;
   }
   if(single_pass_geometry(h->P.W, h->P.H) && single_pass_batch(h->F, h->P.nPoints))
   {
-    for(int k = 0; k < h->depth; k++)
+    if(!h->lane[0].dPlaneImg)
     {
-      ssd_lane &L = h->lane[k];
-      if(!L.dPlaneImg)
+      unsigned long long cap = ~0ull;
+      if(const char *ev = std::getenv("SSD_MAX_PLANE_BYTES"))
+        cap = std::strtoull(ev, nullptr, 10);
+      std::string why;
+      const hipError_t e = planes_make(h, cap, true, why);
+      if(e != hipSuccess)
       {
-        unsigned long long cap = ~0ull;
-        if(const char *ev = std::getenv("SSD_MAX_PLANE_BYTES"))
-          cap = std::strtoull(ev, nullptr, 10);
-        const hipError_t e = static_cast<unsigned long long>(k + 1) * planeBytes > cap ? hipErrorOutOfMemory : hipMalloc(&L.dPlaneImg, planeBytes);
-        if(e != hipSuccess)
-        {
-          /* asked for explicitly, so said loudly - but the handle stays whole: on two passes, with no plane of any workspace */
-          L.dPlaneImg = nullptr;
-          (void)hipGetLastError();
-          (void)ssd_set_single_pass(h, 0);
-          return fail(e == hipErrorOutOfMemory ? SSD_E_NOMEM : SSD_E_HIP, std::string("ssd_set_single_pass: ") + hipGetErrorString(e) + " (the handle stays on two passes)");
-        }
-        HIP_TRY(hipMemset(L.dPlaneImg, 0, planeBytes));
-        h->bytes += planeBytes;
+        /* asked for explicitly, so said loudly - but the handle stays whole: on two passes, with no plane of any workspace */
+        h->singlePassMode = 0;
+        return fail(hip_error_code(e), std::string("ssd_set_single_pass: ") + hipGetErrorString(e) + " (the handle stays on two passes)");
       }
-      if(!L.dFallback)
-      {
-        HIP_TRY(hipMalloc(&L.dFallback, listBytes));
-        HIP_TRY(hipMemset(L.dFallback, 0, listBytes));
-      }
-    }
-    if(!h->hFallback)
-    {
-      HIP_TRY(hipHostMalloc(&h->hFallback, sizeof(int) * 2 * kMaxLanes, hipHostMallocDefault));
-      std::memset(h->hFallback, 0, sizeof(int) * 2 * kMaxLanes);
     }
     HIP_TRY(hipDeviceSynchronize());
   }
@@ -707,25 +598,15 @@ int ssd_set_debug(ssd_handle *h, int enable)
     /* the records always; the image buffer (F x (images + 1) x 2 whole images) only for capture WITH images — and then both
      * or neither: a failed second allocation must not leave the first behind as "debug is set up" */
     const size_t imgBytes = static_cast<size_t>(h->F) * (h->P.maxStepImages + 1) * 2 * h->imgWords * 8;
-    DebugFrame *d = h->dDebug;
-    unsigned long long *di = h->dDebugImg;
-    if(!d)
-      HIP_TRY(hipMalloc(&d, sizeof(DebugFrame) * h->F));
-    if(wantImages && !di)
-    {
-      const hipError_t e = hipMalloc(&di, imgBytes);
-      if(e != hipSuccess)
-      {
-        if(!h->dDebug)
-          (void)hipFree(d);
-        return fail(e == hipErrorOutOfMemory ? SSD_E_NOMEM : SSD_E_HIP, std::string("ssd_set_debug: ") + hipGetErrorString(e));
-      }
-      h->bytes += imgBytes;
-    }
-    if(!h->dDebug)
-      h->bytes += sizeof(DebugFrame) * h->F;
-    h->dDebug = d;
-    h->dDebugImg = di;
+    DeviceBuf<DebugFrame> d;
+    DeviceBuf<unsigned long long> di;
+    hipError_t e = h->dDebug ? hipSuccess : d.alloc(sizeof(DebugFrame) * h->F, &h->bytes);
+    if(e == hipSuccess && wantImages && !h->dDebugImg)
+      e = di.alloc(imgBytes, &h->bytes);
+    if(e != hipSuccess)
+      return hip_fail(e, "ssd_set_debug: ");
+    if(d) h->dDebug = std::move(d);
+    if(di) h->dDebugImg = std::move(di);
   }
   h->debug = enable == 0 ? 0 : enable == 2 ? 2 : 1;
   return SSD_OK;
@@ -740,20 +621,9 @@ int ssd_set_risers(ssd_handle *h, int enable, double tolerance, int min_support)
   HIP_TRY(hipSetDevice(h->device));
   if(enable && (!h->dRisers || !h->hRisers))
   {
-    const size_t bytes = sizeof(ssd_frame_risers) * h->F;
-    ssd_frame_risers *d = nullptr, *hh = nullptr;
-    HIP_TRY(hipMalloc(&d, bytes));
-    hipError_t e = hipMemset(d, 0, bytes);
-    if(e == hipSuccess)
-      e = hipHostMalloc(&hh, bytes, hipHostMallocDefault);
+    const hipError_t e = make_records(h, h->dRisers, h->hRisers, sizeof(ssd_frame_risers) * h->F);
     if(e != hipSuccess)
-    {
-      (void)hipFree(d);
-      return fail(e == hipErrorOutOfMemory ? SSD_E_NOMEM : SSD_E_HIP, std::string("ssd_set_risers: ") + hipGetErrorString(e));
-    }
-    h->dRisers = d;
-    h->hRisers = hh;
-    h->bytes += bytes;
+      return hip_fail(e, "ssd_set_risers: ");
   }
   h->P.risers = enable ? 1 : 0;
   if(enable)
@@ -799,20 +669,9 @@ int ssd_set_riser_moments(ssd_handle *h, int enable)
   HIP_TRY(hipDeviceSynchronize());            /* the batches in flight keep the kernel they were enqueued with */
   if(enable && (!h->dRiserMoments || !h->hRiserMoments))
   {
-    const size_t bytes = sizeof(ssd_frame_moments) * h->F;
-    ssd_frame_moments *d = nullptr, *hh = nullptr;
-    HIP_TRY(hipMalloc(&d, bytes));
-    hipError_t e = hipMemset(d, 0, bytes);
-    if(e == hipSuccess)
-      e = hipHostMalloc(&hh, bytes, hipHostMallocDefault);
+    const hipError_t e = make_records(h, h->dRiserMoments, h->hRiserMoments, sizeof(ssd_frame_moments) * h->F);
     if(e != hipSuccess)
-    {
-      (void)hipFree(d);
-      return fail(e == hipErrorOutOfMemory ? SSD_E_NOMEM : SSD_E_HIP, std::string("ssd_set_riser_moments: ") + hipGetErrorString(e));
-    }
-    h->dRiserMoments = d;
-    h->hRiserMoments = hh;
-    h->bytes += bytes;
+      return hip_fail(e, "ssd_set_riser_moments: ");
   }
   h->riserMoments = enable != 0;
   return SSD_OK;
@@ -852,35 +711,17 @@ int ssd_set_timing(ssd_handle *h, int enable)
   HIP_TRY(hipSetDevice(h->device));
   if(enable && h->ev.empty())
   {
-    std::vector<hipEvent_t> ev;
-    ev.reserve(static_cast<size_t>(SSD_TIMING_SLOTS) * 8);
-    for(size_t i = 0; i < static_cast<size_t>(SSD_TIMING_SLOTS) * 8; i++)
-    {
-      hipEvent_t e;
-      const hipError_t rc = hipEventCreate(&e);
-      if(rc != hipSuccess)
-      {
-        for(hipEvent_t made : ev)
-          (void)hipEventDestroy(made);
-        return fail(SSD_E_HIP, std::string("hipEventCreate: ") + hipGetErrorString(rc));
-      }
-      ev.push_back(e);
-    }
-    /* k_predict's events before anything is handed to the handle: a failure leaves it as it was (no half-made set that a later
-     * call would take for complete) */
-    hipEvent_t pred[SSD_TIMING_SLOTS] = {};
-    for(int i = 0; i < SSD_TIMING_SLOTS; i++)
-      if(hipEventCreate(&pred[i]) != hipSuccess)
-      {
-        for(int k = 0; k < i; k++)
-          (void)hipEventDestroy(pred[k]);
-        for(hipEvent_t made : ev)
-          (void)hipEventDestroy(made);
-        return fail(SSD_E_HIP, "hipEventCreate (predict)");
-      }
-    for(int i = 0; i < SSD_TIMING_SLOTS; i++)
-      h->evPredict[i] = pred[i];
+    /* the stages' events and k_predict's, all of them before anything is handed to the handle: a failure leaves it as it was (no
+     * half-made set that a later call would take for complete) */
+    std::vector<Event> ev, pred;
+    hipError_t rc = make_events(ev, static_cast<size_t>(SSD_TIMING_SLOTS) * 8, hipEventDefault);
+    if(rc != hipSuccess)
+      return fail(SSD_E_HIP, std::string("hipEventCreate: ") + hipGetErrorString(rc));
+    rc = make_events(pred, SSD_TIMING_SLOTS, hipEventDefault);
+    if(rc != hipSuccess)
+      return fail(SSD_E_HIP, "hipEventCreate (predict)");
     h->ev.swap(ev);
+    h->evPredict.swap(pred);
   }
   h->timing = enable != 0;
   h->timedFrom = h->enqueueCount;
@@ -926,23 +767,10 @@ static unsigned long long cameras_call_key(const Params &P)
 }
 
 /* SSD_TIMING_SLOTS pairs of events around an optional pass (k_labels, k_surface_moments) of a timed enqueue: all of them or none */
-static int timing_event_pairs(std::vector<hipEvent_t> &out, const char *who)
+static int timing_event_pairs(std::vector<Event> &out, const char *who)
 {
-  std::vector<hipEvent_t> ev;
-  for(int i = 0; i < 2 * SSD_TIMING_SLOTS; i++)
-  {
-    hipEvent_t e;
-    const hipError_t rc = hipEventCreate(&e);
-    if(rc != hipSuccess)
-    {
-      for(hipEvent_t made : ev)
-        (void)hipEventDestroy(made);
-      return fail(SSD_E_HIP, std::string(who) + hipGetErrorString(rc));
-    }
-    ev.push_back(e);
-  }
-  out.swap(ev);
-  return SSD_OK;
+  const hipError_t rc = make_events(out, 2 * SSD_TIMING_SLOTS, hipEventDefault);
+  return rc == hipSuccess ? SSD_OK : fail(SSD_E_HIP, std::string(who) + hipGetErrorString(rc));
 }
 
 /* camOf (host, nframes entries; ssd_enqueue_cameras has checked them): a cameras batch - frame i takes camera camOf[i] of the table;
@@ -1321,7 +1149,7 @@ int ssd_set_intrinsics(ssd_handle *h, const ssd_intrinsics *intr)
   std::vector<float> maps;
   depth_maps(*intr, h->P.W, h->P.H, maps);
   if(!h->dDepthMaps)
-    HIP_TRY(hipMalloc(&h->dDepthMaps, maps.size() * 4));
+    HIP_TRY(h->dDepthMaps.alloc(maps.size() * 4));
   /* depth batches still running (on the lanes' non-blocking streams, which a null-stream copy does not wait for) read the maps
    * in K1, K2 and K4: let every lane finish before they change */
   for(int k = 0; k < h->depth; k++)
@@ -1491,27 +1319,34 @@ static int ingest_prepare(ssd_handle *h, size_t sliceBytes)
 {
   if(!h->ingestCopy)
   {
-    HIP_TRY(hipStreamCreateWithFlags(&h->ingestCopy, hipStreamNonBlocking));
-    HIP_TRY(hipStreamCreateWithFlags(&h->ingestCopy2, hipStreamNonBlocking));
-    HIP_TRY(hipStreamCreateWithFlags(&h->ingestCompute, hipStreamNonBlocking));
+    /* the three streams and six events are one group, the two buffers another (ssd_owned.h): SliceFeed finds all of a group or none */
+    Stream s[3];
+    Event ev[6];
+    hipError_t e = hipSuccess;
+    for(Stream &x : s)
+      if(e == hipSuccess) e = x.create(hipStreamNonBlocking);
+    for(Event &x : ev)
+      if(e == hipSuccess) e = x.create(hipEventDisableTiming);
+    if(e != hipSuccess)
+      return fail(SSD_E_HIP, std::string("the host feed's streams and events: ") + hipGetErrorString(e));
+    h->ingestCopy = std::move(s[0]); h->ingestCopy2 = std::move(s[1]); h->ingestCompute = std::move(s[2]);
     for(int k = 0; k < 2; k++)
     {
-      HIP_TRY(hipEventCreateWithFlags(&h->ingestCopied[k], hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&h->ingestCopied2[k], hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&h->ingestConsumed[k], hipEventDisableTiming));
+      h->ingestCopied[k] = std::move(ev[k]); h->ingestCopied2[k] = std::move(ev[2 + k]); h->ingestConsumed[k] = std::move(ev[4 + k]);
     }
   }
   if(h->ingestCap < sliceBytes)
   {
     HIP_TRY(hipDeviceSynchronize());
     for(int k = 0; k < 2; k++)
-    {
-      if(h->ingestBuf[k]) (void)hipFree(h->ingestBuf[k]);
-      h->ingestBuf[k] = nullptr;
-    }
+      h->ingestBuf[k].reset();
     h->ingestCap = 0;
-    HIP_TRY(hipMalloc(&h->ingestBuf[0], sliceBytes));
-    HIP_TRY(hipMalloc(&h->ingestBuf[1], sliceBytes));
+    DeviceBuf<void> buf[2];
+    hipError_t e = buf[0].alloc(sliceBytes);
+    if(e == hipSuccess) e = buf[1].alloc(sliceBytes);
+    if(e != hipSuccess)
+      return fail(SSD_E_HIP, std::string("the host feed's staging buffers: ") + hipGetErrorString(e));
+    h->ingestBuf[0] = std::move(buf[0]); h->ingestBuf[1] = std::move(buf[1]);
     h->ingestCap = sliceBytes;
   }
   return SSD_OK;
@@ -1618,7 +1453,7 @@ struct SliceFeed
     }
     if(split[k])
     {
-      HIP_TRY(hipMemcpyAsync(static_cast<unsigned char *>(h->ingestBuf[k]) + half, src + half, bytes - half, hipMemcpyHostToDevice, h->ingestCopy2));
+      HIP_TRY(hipMemcpyAsync(static_cast<unsigned char *>(h->ingestBuf[k].get()) + half, src + half, bytes - half, hipMemcpyHostToDevice, h->ingestCopy2));
       HIP_TRY(hipEventRecord(h->ingestCopied2[k], h->ingestCopy2));
     }
     if(packed)
@@ -1656,9 +1491,14 @@ static int labels_prepare(ssd_handle *h, size_t sliceBytes)
 {
   if(!h->labelsCopy)
   {
-    HIP_TRY(hipStreamCreateWithFlags(&h->labelsCopy, hipStreamNonBlocking));
-    for(int k = 0; k < 2; k++)
-      HIP_TRY(hipEventCreateWithFlags(&h->labelsCopied[k], hipEventDisableTiming));
+    Stream copy;
+    Event copied[2];
+    hipError_t e = copy.create(hipStreamNonBlocking);
+    if(e == hipSuccess) e = copied[0].create(hipEventDisableTiming);
+    if(e == hipSuccess) e = copied[1].create(hipEventDisableTiming);
+    if(e != hipSuccess)
+      return fail(SSD_E_HIP, std::string("the staged output's stream and events: ") + hipGetErrorString(e));
+    h->labelsCopy = std::move(copy); h->labelsCopied[0] = std::move(copied[0]); h->labelsCopied[1] = std::move(copied[1]);
   }
   if(h->labelStageCap < sliceBytes)
   {
@@ -1668,13 +1508,14 @@ static int labels_prepare(ssd_handle *h, size_t sliceBytes)
         HIP_TRY(hipEventSynchronize(h->lane[k].done));
     HIP_TRY(hipStreamSynchronize(h->labelsCopy));
     for(int k = 0; k < 2; k++)
-    {
-      if(h->labelStage[k]) (void)hipFree(h->labelStage[k]);
-      h->labelStage[k] = nullptr;
-    }
+      h->labelStage[k].reset();
     h->labelStageCap = 0;
-    HIP_TRY(hipMalloc(&h->labelStage[0], sliceBytes));
-    HIP_TRY(hipMalloc(&h->labelStage[1], sliceBytes));
+    DeviceBuf<unsigned char> buf[2];
+    hipError_t e = buf[0].alloc(sliceBytes);
+    if(e == hipSuccess) e = buf[1].alloc(sliceBytes);
+    if(e != hipSuccess)
+      return fail(SSD_E_HIP, std::string("the staged output's buffers: ") + hipGetErrorString(e));
+    h->labelStage[0] = std::move(buf[0]); h->labelStage[1] = std::move(buf[1]);
     h->labelStageCap = sliceBytes;
   }
   return SSD_OK;
@@ -1695,24 +1536,6 @@ static StagedOut staged_labels(const ssd_handle *h, uint8_t *labels)
 static StagedOut staged_moments(ssd_frame_moments *moments)
 {
   return StagedOut{ StagedOut::kMoments, moments, sizeof(ssd_frame_moments) };
-}
-
-/* a pinned buffer of one record per frame of a host batch (the device buffer holds one enqueue's), grown to nframes */
-extern "C++"
-{
-template<typename T>
-static int grow_pinned_batch(ssd_handle *h, T *&buf, int &cap, int nframes)
-{
-  if(cap >= nframes)
-    return SSD_OK;
-  HIP_TRY(hipStreamSynchronize(h->ingestCompute));
-  if(buf) (void)hipHostFree(buf);
-  buf = nullptr;
-  cap = 0;
-  HIP_TRY(hipHostMalloc(&buf, sizeof(T) * static_cast<size_t>(nframes), hipHostMallocDefault));
-  cap = nframes;
-  return SSD_OK;
-}
 }
 
 /* arguments checked by the callers (check_host_batch) */
@@ -1764,7 +1587,7 @@ static int process_host_impl(ssd_handle *h, const void *frames, int nframes, int
     rc = enqueue_impl(h, buf, feed.f.devFrameBytes, n, h->ingestCompute, SSD_STAGE_ALL, feed.f.depth,
                       out.host && out.kind == StagedOut::kLabels ? h->labelStage[k] : nullptr, out.frameBytes,
                       camOf ? camOf + at : nullptr,                                 /* a slice takes its part of the index */
-                      out.host && out.kind == StagedOut::kMoments ? reinterpret_cast<ssd_frame_moments *>(h->labelStage[k]) : nullptr);
+                      out.host && out.kind == StagedOut::kMoments ? reinterpret_cast<ssd_frame_moments *>(h->labelStage[k].get()) : nullptr);
     if(rc) return rc;
     /* "Consumed" is the end of the slice's kernels — on the stream they ran on (with several workspaces the lane's own; the
      * compute stream itself only orders a slice behind its copy, so the slices of a handle with several workspaces overlap
@@ -1833,22 +1656,15 @@ int ssd_process_depth_host_labels(ssd_handle *h, const uint16_t *depth, int nfra
 
 static void cameras_free(ssd_handle *h)
 {
-  for(int k = 0; k < kMaxLanes; k++)
+  for(ssd_lane &L : h->lane)
   {
-    ssd_lane &L = h->lane[k];
-    if(L.dCamIndex) (void)hipFree(L.dCamIndex);
-    if(L.hCamIndex) (void)hipHostFree(L.hCamIndex);
-    if(L.camCopied) (void)hipEventDestroy(L.camCopied);
-    L.dCamIndex = nullptr; L.hCamIndex = nullptr; L.camCopied = nullptr;
+    L.dCamIndex.reset(); L.hCamIndex.reset(); L.camCopied.reset();
   }
-  if(h->dCams) (void)hipFree(h->dCams);
-  if(h->dCamMaps) (void)hipFree(h->dCamMaps);
-  h->dCams = nullptr; h->dCamMaps = nullptr;
+  h->dCams.reset();
+  h->dCamMaps.reset();
   h->camParams.clear(); h->camHasIntr.clear(); h->camDepthUnits.clear();
   h->camsNeedChecks = false;
   h->camCallKey = ~0ull;
-  h->bytes -= h->camBytes;
-  h->camBytes = 0;
 }
 
 /* The device records: each camera's Params as make_params() made them, with what a call decides for the whole handle (as
@@ -1917,17 +1733,18 @@ int ssd_set_cameras(ssd_handle *h, const ssd_camera *cams, int ncams)
   const size_t recBytes = sizeof(CameraRec) * static_cast<size_t>(ncams);
   const size_t mapBytes = anyIntr ? static_cast<size_t>(ncams) * (static_cast<size_t>(W) + H) * sizeof(float) : 0;
   const size_t indexBytes = sizeof(int) * static_cast<size_t>(h->F);
-  auto bad = [&](hipError_t e, const char *what)
-  {
-    cameras_free(h);
-    (void)hipGetLastError();
-    return fail(e == hipErrorOutOfMemory ? SSD_E_NOMEM : SSD_E_HIP, std::string("ssd_set_cameras: ") + what + ": " + hipGetErrorString(e));
-  };
-  hipError_t e = hipMalloc(&h->dCams, recBytes);
+  /* the table, its maps and every workspace's index as one group: a failure leaves the handle with no table, as cameras_free left it */
+  auto bad = [&](hipError_t e, const char *what) { return hip_fail(e, std::string("ssd_set_cameras: ") + what + ": "); };
+  DeviceBuf<CameraRec> dCams;
+  DeviceBuf<float> dCamMaps;
+  DeviceBuf<int> dIndex[kMaxLanes];
+  PinnedBuf<int> hIndex[kMaxLanes];
+  Event copied[kMaxLanes];
+  hipError_t e = dCams.alloc(recBytes, &h->bytes);
   if(e != hipSuccess) return bad(e, "hipMalloc of the table");
   if(mapBytes)
   {
-    e = hipMalloc(&h->dCamMaps, mapBytes);
+    e = dCamMaps.alloc(mapBytes, &h->bytes);
     if(e != hipSuccess) return bad(e, "hipMalloc of the deprojection maps");
     std::vector<float> all(mapBytes / sizeof(float), 0.0f), maps;
     for(int i = 0; i < ncams; i++)
@@ -1936,16 +1753,22 @@ int ssd_set_cameras(ssd_handle *h, const ssd_camera *cams, int ncams)
         depth_maps(cams[i].intr, W, H, maps);
         std::memcpy(all.data() + static_cast<size_t>(i) * (static_cast<size_t>(W) + H), maps.data(), maps.size() * sizeof(float));
       }
-    e = hipMemcpy(h->dCamMaps, all.data(), mapBytes, hipMemcpyHostToDevice);
+    e = hipMemcpy(dCamMaps, all.data(), mapBytes, hipMemcpyHostToDevice);
     if(e != hipSuccess) return bad(e, "upload of the deprojection maps");
   }
   for(int k = 0; k < h->depth; k++)
   {
-    ssd_lane &L = h->lane[k];
-    e = hipMalloc(&L.dCamIndex, indexBytes);
-    if(e == hipSuccess) e = hipHostMalloc(&L.hCamIndex, indexBytes, hipHostMallocDefault);
-    if(e == hipSuccess) e = hipEventCreateWithFlags(&L.camCopied, hipEventDisableTiming);
+    e = dIndex[k].alloc(indexBytes, &h->bytes);
+    if(e == hipSuccess) e = hIndex[k].alloc(indexBytes);
+    if(e == hipSuccess) e = copied[k].create(hipEventDisableTiming);
     if(e != hipSuccess) return bad(e, "a workspace's index");
+  }
+  h->dCams = std::move(dCams);
+  h->dCamMaps = std::move(dCamMaps);
+  for(int k = 0; k < h->depth; k++)
+  {
+    ssd_lane &L = h->lane[k];
+    L.dCamIndex = std::move(dIndex[k]); L.hCamIndex = std::move(hIndex[k]); L.camCopied = std::move(copied[k]);
   }
   h->camParams.swap(params);
   h->camHasIntr.resize(static_cast<size_t>(ncams));
@@ -1956,8 +1779,6 @@ int ssd_set_cameras(ssd_handle *h, const ssd_camera *cams, int ncams)
     h->camDepthUnits[i] = cams[i].has_intrinsics ? cams[i].intr.depth_units : 0.0f;
   }
   h->camsNeedChecks = checks;
-  h->camBytes = recBytes + mapBytes + static_cast<size_t>(h->depth) * indexBytes;
-  h->bytes += h->camBytes;
   Params P = h->P;
   P.px.groundFull = h->debug == 1 ? 1 : 0;
   const int rc = cameras_upload(h, cameras_call_key(P), P.riserTol);
@@ -2296,22 +2117,17 @@ static int refit_prepare(ssd_handle *h)
   if(h->dRefitGates)
     return SSD_OK;
   const size_t bytes = sizeof(ssd_frame_gates) * static_cast<size_t>(h->F);
-  hipError_t e = hipMalloc(&h->dRefitGates, bytes);
-  if(e == hipSuccess) e = hipHostMalloc(&h->hRefitGates, bytes, hipHostMallocDefault);
-  if(e == hipSuccess) e = hipEventCreateWithFlags(&h->refitGatesCopied, hipEventDisableTiming);
-  if(e == hipSuccess) e = hipEventCreateWithFlags(&h->refitDone, hipEventDisableTiming);
+  DeviceBuf<ssd_frame_gates> d;
+  PinnedBuf<ssd_frame_gates> hh;
+  Event copied, done;
+  hipError_t e = d.alloc(bytes, &h->bytes);
+  if(e == hipSuccess) e = hh.alloc(bytes, &h->bytes);
+  if(e == hipSuccess) e = copied.create(hipEventDisableTiming);
+  if(e == hipSuccess) e = done.create(hipEventDisableTiming);
   if(e != hipSuccess)
-  {
-    if(h->dRefitGates) (void)hipFree(h->dRefitGates);
-    if(h->hRefitGates) (void)hipHostFree(h->hRefitGates);
-    if(h->refitGatesCopied) (void)hipEventDestroy(h->refitGatesCopied);
-    if(h->refitDone) (void)hipEventDestroy(h->refitDone);
-    h->dRefitGates = nullptr; h->hRefitGates = nullptr; h->refitGatesCopied = nullptr; h->refitDone = nullptr;
-    (void)hipGetLastError();
-    return fail(e == hipErrorOutOfMemory ? SSD_E_NOMEM : SSD_E_HIP, std::string("ssd_enqueue_surface_refit: its buffers: ") + hipGetErrorString(e));
-  }
-  h->refitBytes = 2 * bytes;
-  h->bytes += h->refitBytes;
+    return hip_fail(e, "ssd_enqueue_surface_refit: its buffers: ");
+  h->dRefitGates = std::move(d); h->hRefitGates = std::move(hh);
+  h->refitGatesCopied = std::move(copied); h->refitDone = std::move(done);
   return SSD_OK;
 }
 
@@ -2332,17 +2148,8 @@ static int fold_prepare(ssd_handle *h)
 {
   if(h->dCamFold)
     return SSD_OK;
-  const size_t bytes = sizeof(ssd_camera_fold) * static_cast<size_t>(SSD_MAX_CAMERAS);
-  const hipError_t e = hipMalloc(&h->dCamFold, bytes);
-  if(e != hipSuccess)
-  {
-    h->dCamFold = nullptr;
-    (void)hipGetLastError();
-    return fail(e == hipErrorOutOfMemory ? SSD_E_NOMEM : SSD_E_HIP, std::string("the camera fold's buffer: ") + hipGetErrorString(e));
-  }
-  h->camFoldBytes = bytes;
-  h->bytes += bytes;
-  return SSD_OK;
+  const hipError_t e = h->dCamFold.alloc(sizeof(ssd_camera_fold) * static_cast<size_t>(SSD_MAX_CAMERAS), &h->bytes);
+  return e == hipSuccess ? SSD_OK : hip_fail(e, "the camera fold's buffer: ");
 }
 
 /* all refit entry points: `cameras` = behind a whole cameras batch (wholeKind 2), under the table and the index that batch left in its
@@ -2393,11 +2200,8 @@ static int refit_enqueue_impl(ssd_handle *h, const char *who, bool cameras, cons
     if(rc) return rc;
   }
   const bool timing = h->timing && !h->ev.empty();
-  if(timing && !h->evRefit[0])
-  {
-    HIP_TRY(hipEventCreate(&h->evRefit[0]));
-    HIP_TRY(hipEventCreate(&h->evRefit[1]));
-  }
+  if(timing && h->evRefit.empty())
+    HIP_TRY(make_events(h->evRefit, 2, hipEventDefault));
   /* behind the batch, on the stream it ran on: the caller's with one workspace (a switch of streams is ordered by the lane's event),
    * the lane's own with several (behind what the caller's stream holds now, as an enqueue is) */
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -2604,7 +2408,7 @@ static int process_host_refit_impl(ssd_handle *h, const char *who, const void *f
   /* the records of a slice on the device: the first pass's in the first label staging buffer, a refit pass's in the second */
   rc = labels_prepare(h, static_cast<size_t>(feed.slice) * sizeof(ssd_frame_moments));
   if(rc) return rc;
-  ssd_frame_moments *dFirst = reinterpret_cast<ssd_frame_moments *>(h->labelStage[0]), *dRefit = reinterpret_cast<ssd_frame_moments *>(h->labelStage[1]);
+  ssd_frame_moments *dFirst = reinterpret_cast<ssd_frame_moments *>(h->labelStage[0].get()), *dRefit = reinterpret_cast<ssd_frame_moments *>(h->labelStage[1].get());
   std::vector<ssd_frame_moments> cur(static_cast<size_t>(feed.slice));
   std::vector<ssd_frame_gates> gates(static_cast<size_t>(feed.slice));
   /* the records of the pass that ran last on the slice's stream, to the host */
@@ -2755,7 +2559,7 @@ int ssd_process_host_cameras_drift(ssd_handle *h, const void *frames, int nframe
   if(rc) return rc;
   if(h->refitHaveLast)
     HIP_TRY(hipEventSynchronize(h->refitDone));                     /* a folded pass still on its way owns the fold buffer */
-  ssd_frame_moments *dFirst = reinterpret_cast<ssd_frame_moments *>(h->labelStage[0]), *dRefit = reinterpret_cast<ssd_frame_moments *>(h->labelStage[1]);
+  ssd_frame_moments *dFirst = reinterpret_cast<ssd_frame_moments *>(h->labelStage[0].get()), *dRefit = reinterpret_cast<ssd_frame_moments *>(h->labelStage[1].get());
   const int ncams = static_cast<int>(h->camParams.size());
   hipStream_t s = nullptr;
   for(int c = 0; c < feed.slices(); c++)
@@ -2991,27 +2795,22 @@ static int ground_prepare(ssd_handle *h)
   if(h->dGround)
     return SSD_OK;
   const size_t recBytes = sizeof(long long) * kGroundSums * static_cast<size_t>(h->F), priorBytes = sizeof(GroundPrior) * static_cast<size_t>(h->F);
-  hipError_t e = hipMalloc(&h->dGround, recBytes);
-  if(e == hipSuccess) e = hipHostMalloc(&h->hGround, recBytes, hipHostMallocDefault);
-  if(e == hipSuccess) e = hipMalloc(&h->dGroundPriors, priorBytes);
-  if(e == hipSuccess) e = hipHostMalloc(&h->hGroundPriors, priorBytes, hipHostMallocDefault);
-  if(e == hipSuccess) e = hipEventCreateWithFlags(&h->groundPriorsCopied, hipEventDisableTiming);
-  if(e == hipSuccess) e = hipEventCreateWithFlags(&h->groundDone, hipEventDisableTiming);
+  DeviceBuf<long long> d;
+  PinnedBuf<long long> hh;
+  DeviceBuf<GroundPrior> dPriors;
+  PinnedBuf<GroundPrior> hPriors;
+  Event copied, done;
+  hipError_t e = d.alloc(recBytes, &h->bytes);
+  if(e == hipSuccess) e = hh.alloc(recBytes);
+  if(e == hipSuccess) e = dPriors.alloc(priorBytes, &h->bytes);
+  if(e == hipSuccess) e = hPriors.alloc(priorBytes);
+  if(e == hipSuccess) e = copied.create(hipEventDisableTiming);
+  if(e == hipSuccess) e = done.create(hipEventDisableTiming);
   if(e != hipSuccess)
-  {
-    if(h->dGround) (void)hipFree(h->dGround);
-    if(h->hGround) (void)hipHostFree(h->hGround);
-    if(h->dGroundPriors) (void)hipFree(h->dGroundPriors);
-    if(h->hGroundPriors) (void)hipHostFree(h->hGroundPriors);
-    if(h->groundPriorsCopied) (void)hipEventDestroy(h->groundPriorsCopied);
-    if(h->groundDone) (void)hipEventDestroy(h->groundDone);
-    h->dGround = nullptr; h->hGround = nullptr; h->dGroundPriors = nullptr; h->hGroundPriors = nullptr;
-    h->groundPriorsCopied = nullptr; h->groundDone = nullptr;
-    (void)hipGetLastError();
-    return fail(e == hipErrorOutOfMemory ? SSD_E_NOMEM : SSD_E_HIP, std::string("ssd_enqueue_ground_fit: its buffers: ") + hipGetErrorString(e));
-  }
-  h->groundBytes = recBytes + priorBytes;
-  h->bytes += h->groundBytes;
+    return hip_fail(e, "ssd_enqueue_ground_fit: its buffers: ");
+  h->dGround = std::move(d); h->hGround = std::move(hh);
+  h->dGroundPriors = std::move(dPriors); h->hGroundPriors = std::move(hPriors);
+  h->groundPriorsCopied = std::move(copied); h->groundDone = std::move(done);
   return SSD_OK;
 }
 
@@ -3158,7 +2957,7 @@ int ssd_host_alloc(size_t bytes, void **ptr)
   *ptr = nullptr;
   const hipError_t e = hipHostMalloc(ptr, bytes, hipHostMallocDefault);
   if(e != hipSuccess)
-    return fail(e == hipErrorOutOfMemory ? SSD_E_NOMEM : SSD_E_HIP, std::string("hipHostMalloc: ") + hipGetErrorString(e));
+    return hip_fail(e, "hipHostMalloc: ");
   return SSD_OK;
 }
 

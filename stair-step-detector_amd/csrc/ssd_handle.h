@@ -6,6 +6,9 @@
 #define SSD_HANDLE_H_
 
 #include "ssd_device.h"
+#include "ssd_owned.h"
+#include <cstring>
+#include <string>
 #include <vector>
 
 namespace ssd { struct GroundPrior; }          /* ssd_ground.h */
@@ -31,23 +34,23 @@ struct ssd_tuning
  * of one batch fill the gaps the one-block-per-frame kernels of the others leave. */
 struct ssd_lane
 {
-  ssd::FrameState *dState = nullptr;
-  unsigned long long *dStepImg = nullptr;
-  unsigned long long *dGroundImg = nullptr;
-  int *dFallback = nullptr;                 /* single pass: kFallbackList + F ints: frames listed for k_raster, frames without step plateaus, the list */
-  unsigned long long *dPlaneImg = nullptr;  /* single pass: [F][kMaxPlanes] bit images, one per candidate height bin (null: the handle never runs it) */
+  ssd::DeviceBuf<ssd::FrameState> dState;
+  ssd::DeviceBuf<unsigned long long> dStepImg;
+  ssd::DeviceBuf<unsigned long long> dGroundImg;
+  ssd::DeviceBuf<int> dFallback;            /* single pass: kFallbackList + F ints: frames listed for k_raster, frames without step plateaus, the list */
+  ssd::DeviceBuf<unsigned long long> dPlaneImg;   /* single pass: [F][kMaxPlanes] bit images, one per candidate height bin (null: the handle never runs it) */
   uint2 *dTileMasks = nullptr;             /* per cell (64 points): which groups of 4 height bins occur; K1 -> K2, K4, K6 */
-  uint2 *dTileMasksBase = nullptr;         /* the allocation dTileMasks lies in (the tools' placement hooks put the records elsewhere in a larger one) */
+  ssd::DeviceBuf<uint2> dTileMasksBase;    /* the allocation dTileMasks lies in (the tools' placement hooks put the records elsewhere in a larger one) */
   size_t recordSlack = 0;                   /* bytes of that allocation beyond the records (0 unless a tools hook allocated it) */
-  hipStream_t stream = nullptr;             /* the lane's own stream (depth > 1 only; depth 1 runs on the caller's stream) */
-  hipEvent_t in = nullptr;                  /* recorded on the caller's stream at the enqueue: the lane's work starts behind it */
-  hipEvent_t done = nullptr;                /* recorded behind the lane's last enqueue */
+  ssd::Stream stream;                       /* the lane's own stream (depth > 1 only; depth 1 runs on the caller's stream) */
+  ssd::Event in;                            /* recorded on the caller's stream at the enqueue: the lane's work starts behind it */
+  ssd::Event done;                          /* recorded behind the lane's last enqueue */
   hipStream_t lastStream = nullptr;         /* depth 1: the stream of the previous call (a switch is ordered by `done`) */
   bool haveLast = false;
   /* cameras batches (ssd_enqueue_cameras): the batch's index frame -> camera, F ints each, made on the lane's first such batch */
-  int *dCamIndex = nullptr;
-  int *hCamIndex = nullptr;                 /* pinned: the caller's array is copied here during the call */
-  hipEvent_t camCopied = nullptr;           /* behind the copy pinned -> device: the slot may be written again */
+  ssd::DeviceBuf<int> dCamIndex;
+  ssd::PinnedBuf<int> hCamIndex;            /* pinned: the caller's array is copied here during the call */
+  ssd::Event camCopied;                     /* behind the copy pinned -> device: the slot may be written again */
   bool stepImagesDirty = false, groundImageDirty = false;   /* a partial run rastered without the stage that consumes (and clears) the bits */
   int dirtyFrames = 0;                      /* leading FrameStates whose K1 accumulators may be non-zero (k_peaks clears them) */
 };
@@ -69,42 +72,42 @@ struct ssd_handle
   bool lastPinned = false;        /* the last enqueue was held in lane 0 (debug capture, risers, partial stages) */
   size_t tileMaskStride = 0;      /* cell records per frame */
   size_t recordBytes = 0;         /* one workspace's cell records */
-  float *dDepthMaps = nullptr;              /* xmap[W] then ymap[H] (ssd_set_intrinsics) */
+  ssd::DeviceBuf<float> dDepthMaps;         /* xmap[W] then ymap[H] (ssd_set_intrinsics) */
   ssd_intrinsics intr{};
   bool haveIntr = false;
   /* result slots (max(2, depth)), used in turn by the enqueues that run the last stage: the device -> pinned-host copy of
    * a batch's results is part of its enqueue, so that the next batches can be enqueued before the results are read */
   int nSlots = 2;
-  ssd_frame_result *dResults = nullptr;     /* nSlots x F */
-  ssd_frame_result *hResults = nullptr;     /* nSlots x F, pinned */
+  ssd::DeviceBuf<ssd_frame_result> dResults;   /* nSlots x F */
+  ssd::PinnedBuf<ssd_frame_result> hResults;   /* nSlots x F, pinned */
   ssd_frame_result *hResultsDev = nullptr;  /* the same memory as the kernels address it (small batches write it directly) */
-  hipEvent_t resultsReady[kMaxLanes] = {};
+  ssd::Event resultsReady[kMaxLanes];
   int resultsFrames[kMaxLanes] = {};
   int resultsLane[kMaxLanes] = {};
   unsigned long long finalCount = 0;        /* enqueues that produced results */
-  ssd_frame_risers *dRisers = nullptr;      /* vertical faces (extension), allocated by ssd_set_risers */
-  ssd_frame_risers *hRisers = nullptr;      /* pinned */
+  ssd::DeviceBuf<ssd_frame_risers> dRisers; /* vertical faces (extension), allocated by ssd_set_risers */
+  ssd::PinnedBuf<ssd_frame_risers> hRisers; /* pinned */
   /* ssd_process_host / ssd_process_depth_host: two device staging buffers, a copy and a compute stream (ssd_capi.hip) */
-  void *ingestBuf[2] = { nullptr, nullptr };
+  ssd::DeviceBuf<void> ingestBuf[2];
   size_t ingestCap = 0;                     /* bytes per buffer */
-  hipStream_t ingestCopy = nullptr, ingestCompute = nullptr;
-  hipStream_t ingestCopy2 = nullptr;            /* the second half of a large slice: two copy engines (round 6) */
-  hipEvent_t ingestCopied[2] = { nullptr, nullptr }, ingestConsumed[2] = { nullptr, nullptr };
-  hipEvent_t ingestCopied2[2] = { nullptr, nullptr };
+  ssd::Stream ingestCopy, ingestCompute;
+  ssd::Stream ingestCopy2;                  /* the second half of a large slice: two copy engines (round 6) */
+  ssd::Event ingestCopied[2], ingestConsumed[2];
+  ssd::Event ingestCopied2[2];
   /* risers of a host-fed batch, slice by slice (the device buffer holds one enqueue's) */
-  ssd_frame_risers *hRisersBatch = nullptr; /* pinned */
+  ssd::PinnedBuf<ssd_frame_risers> hRisersBatch;   /* pinned */
   int hRisersBatchCap = 0, hRisersBatchFrames = 0;
   /* riser moments (ssd_set_riser_moments): made on the first enable, so a handle that never asks holds none of
    * them.  Single like the riser buffer (enqueues with risers on all run in the first workspace); a host-fed batch collects them slice
    * by slice as hRisersBatch does */
   bool riserMoments = false;
-  ssd_frame_moments *dRiserMoments = nullptr;     /* F records */
-  ssd_frame_moments *hRiserMoments = nullptr;     /* pinned */
-  ssd_frame_moments *hRiserMomentsBatch = nullptr;   /* pinned */
+  ssd::DeviceBuf<ssd_frame_moments> dRiserMoments;   /* F records */
+  ssd::PinnedBuf<ssd_frame_moments> hRiserMoments;   /* pinned */
+  ssd::PinnedBuf<ssd_frame_moments> hRiserMomentsBatch;   /* pinned */
   int hRiserMomentsBatchCap = 0, hRiserMomentsBatchFrames = 0;
   int riserMomentsFrames = 0;               /* frames whose riser moments the last enqueue gathered (0: none) */
-  ssd::DebugFrame *dDebug = nullptr;
-  unsigned long long *dDebugImg = nullptr;
+  ssd::DeviceBuf<ssd::DebugFrame> dDebug;
+  ssd::DeviceBuf<unsigned long long> dDebugImg;
   int debug = 0;                  /* 0 off, 1 records + images (the whole ground image is rastered for it), 2 records only */
   int lastFrames = 0;
   /* single pass (k_hist rasters the step plateaus itself): -1 = whenever a call qualifies (whole pipeline, a batch of at least
@@ -113,25 +116,25 @@ struct ssd_handle
   int singlePassMode = -1, singlePassSabotage = 0;
   int planePool = 0;               /* planes k_predict may hand out per batch (plane_pool_size(F), what each workspace holds; a test hook lowers it) */
   bool lastSinglePass = false;    /* the last enqueue ran it */
-  int *hFallback = nullptr;       /* pinned, two per result slot: frames of that batch k_raster had to do, frames without step plateaus (copied with the results) */
+  ssd::PinnedBuf<int> hFallback;  /* pinned, two per result slot: frames of that batch k_raster had to do, frames without step plateaus (copied with the results) */
   int resultsFallback[kMaxLanes] = {};      /* -1: that slot's batch ran two passes; 0: count on its way; 1: seen by ssd_fetch_back */
   int singlePassBackoff = 0;      /* qualifying batches still to run two passes after a batch the predictor did not cover */
-  size_t bytes = 0;
+  size_t bytes = 0;               /* what ssd_workspace_bytes reports: the ledger of the buffers allocated with it (ssd_owned.h) */
   /* per-stage timing: a ring of event sets, one per enqueue, so that a timed loop never has to synchronise */
   bool timing = false;
-  std::vector<hipEvent_t> ev;     /* kTimingSlots x 8 */
-  hipEvent_t evPredict[SSD_TIMING_SLOTS] = {};   /* recorded in front of k_predict (single-pass enqueues) */
+  std::vector<ssd::Event> ev;     /* kTimingSlots x 8 */
+  std::vector<ssd::Event> evPredict;   /* SSD_TIMING_SLOTS, made with ev: recorded in front of k_predict (single-pass enqueues) */
   bool predictTimed[SSD_TIMING_SLOTS] = {};
   /* per-pixel labels (ssd_enqueue_labels & co.): made on first use, so a handle that never labels holds none of them */
-  std::vector<hipEvent_t> evLabels;          /* SSD_TIMING_SLOTS x 2: around k_labels of a timed enqueue */
+  std::vector<ssd::Event> evLabels;          /* SSD_TIMING_SLOTS x 2: around k_labels of a timed enqueue */
   bool labelsTimed[SSD_TIMING_SLOTS] = {};
-  unsigned char *labelStage[2] = { nullptr, nullptr };   /* ssd_process_*_host_labels: a slice's labels, double-buffered */
+  ssd::DeviceBuf<unsigned char> labelStage[2];   /* ssd_process_*_host_labels: a slice's labels, double-buffered */
   size_t labelStageCap = 0;                 /* bytes per buffer */
-  hipStream_t labelsCopy = nullptr;         /* their copies to the host */
-  hipEvent_t labelsCopied[2] = { nullptr, nullptr };
+  ssd::Stream labelsCopy;                   /* their copies to the host */
+  ssd::Event labelsCopied[2];
   /* surface moments (ssd_enqueue_surface_moments & co.): the events around k_surface_moments of a timed enqueue, made on the first one;
    * the host entry point stages a slice's records in labelStage and copies them out on labelsCopy, as labels are */
-  std::vector<hipEvent_t> evSurface;         /* SSD_TIMING_SLOTS x 2 */
+  std::vector<ssd::Event> evSurface;         /* SSD_TIMING_SLOTS x 2 */
   bool surfaceTimed[SSD_TIMING_SLOTS] = {};
   unsigned long long enqueueCount = 0;
   unsigned long long timedFrom = 0;
@@ -141,25 +144,23 @@ struct ssd_handle
   std::vector<ssd::Params> camParams;
   std::vector<unsigned char> camHasIntr;
   std::vector<float> camDepthUnits;
-  ssd::CameraRec *dCams = nullptr;
-  float *dCamMaps = nullptr;                /* per camera xmap[W] then ymap[H] */
+  ssd::DeviceBuf<ssd::CameraRec> dCams;
+  ssd::DeviceBuf<float> dCamMaps;           /* per camera xmap[W] then ymap[H] */
   bool camsNeedChecks = false;              /* some camera needs_checks(): its batches run the CHECKS instantiations */
   unsigned long long camCallKey = ~0ull;
   double camCallTol = 0.0;
-  size_t camBytes = 0;                      /* the table's share of `bytes` */
   /* the ground fit (ssd_enqueue_ground_fit & co.): made on its first call, so a handle that never fits holds
    * none of them.  One set, used in stream order like a handle's one workspace; nothing of the lanes is touched. */
-  long long *dGround = nullptr;             /* F records of kGroundSums int64 (ssd_ground_moments) */
-  long long *hGround = nullptr;             /* pinned: a call's last step copies its records here */
-  ssd::GroundPrior *dGroundPriors = nullptr;   /* F */
-  ssd::GroundPrior *hGroundPriors = nullptr;   /* pinned: the caller's priors are restated here during the call */
-  hipEvent_t groundPriorsCopied = nullptr;  /* behind the copy pinned -> device: the pinned priors may be written again */
-  hipEvent_t groundDone = nullptr;          /* behind the call's last step */
+  ssd::DeviceBuf<long long> dGround;        /* F records of kGroundSums int64 (ssd_ground_moments) */
+  ssd::PinnedBuf<long long> hGround;        /* pinned: a call's last step copies its records here */
+  ssd::DeviceBuf<ssd::GroundPrior> dGroundPriors;   /* F */
+  ssd::PinnedBuf<ssd::GroundPrior> hGroundPriors;   /* pinned: the caller's priors are restated here during the call */
+  ssd::Event groundPriorsCopied;            /* behind the copy pinned -> device: the pinned priors may be written again */
+  ssd::Event groundDone;                    /* behind the call's last step */
   hipStream_t groundLastStream = nullptr;   /* the stream of the previous call (a switch is ordered by groundDone) */
   bool groundHaveLast = false;
   int groundFrames = 0;                     /* frames of the last call */
   std::vector<ssd_calibration> groundPriorCal;   /* its priors, one or one per frame: what ssd_fetch_ground_fit solves against */
-  size_t groundBytes = 0;                   /* their share of `bytes` */
   /* the trimmed surface refit (ssd_enqueue_surface_refit; ssd_enqueue_cameras_surface_refit, section 7h).  What the
    * last enqueue was, so that a refit can be held to it: wholeKind 0 = none / a partial run / a failed one / one withdrawn by
    * ssd_set_intrinsics (kind 1) or ssd_set_cameras (kind 2), 1 = a whole run under the handle's calibration, 2 = a cameras batch (its
@@ -169,18 +170,73 @@ struct ssd_handle
   const void *wholeFrames = nullptr;        /* its frames and their stride */
   size_t wholeStride = 0;
   /* the gates of a call, made on the first one, so a handle that never refits holds none of them.  One set, like the ground fit's */
-  ssd_frame_gates *dRefitGates = nullptr;   /* F */
-  ssd_frame_gates *hRefitGates = nullptr;   /* pinned: the caller's gates are copied here during the call */
-  hipEvent_t refitGatesCopied = nullptr;    /* behind the copy pinned -> device: the pinned gates may be written again */
-  hipEvent_t refitDone = nullptr;           /* behind the pass */
+  ssd::DeviceBuf<ssd_frame_gates> dRefitGates;   /* F */
+  ssd::PinnedBuf<ssd_frame_gates> hRefitGates;   /* pinned: the caller's gates are copied here during the call */
+  ssd::Event refitGatesCopied;              /* behind the copy pinned -> device: the pinned gates may be written again */
+  ssd::Event refitDone;                     /* behind the pass */
   hipStream_t refitLastStream = nullptr;    /* the stream of the previous pass (a switch is ordered by refitDone: the device gates are single) */
-  hipEvent_t evRefit[2] = { nullptr, nullptr };   /* around the pass of a timed call, made on the first one */
+  std::vector<ssd::Event> evRefit;          /* both or none: around the pass of a timed call, made on the first one */
   bool refitHaveLast = false, refitTimed = false;
-  size_t refitBytes = 0;                    /* their share of `bytes` */
   /* the camera fold (ssd_enqueue_cameras_surface_refit_folded, ssd_process_host_cameras_drift): SSD_MAX_CAMERAS
    * records, made on the first call of either.  One set: the refit orders its users as it orders the device gates' */
-  ssd_camera_fold *dCamFold = nullptr;
-  size_t camFoldBytes = 0;                  /* its share of `bytes` */
+  ssd::DeviceBuf<ssd_camera_fold> dCamFold;
 };
+
+/* The single pass's planes - dPlaneImg and dFallback of every workspace and the pinned hFallback, zeroed - for ALL workspaces of the
+ * handle or for none (ssd_create, ssd_set_single_pass, the test hook ssd_test_single_pass; here because the hook library does not link
+ * the product).  cap: what the planes of all workspaces together may take (the caller's reading of SSD_MAX_PLANE_BYTES, ~0ull: no
+ * bound); a handle that would cross it counts as one whose allocation failed.  counted: the planes go into `bytes` (the hook's do
+ * not).  On failure the handle is as it was, and `why` says what did not fit. */
+inline hipError_t planes_make(ssd_handle *h, unsigned long long cap, bool counted, std::string &why)
+{
+  const size_t planeBytes = static_cast<size_t>(ssd::plane_pool_size(h->F, h->P.nPoints)) * h->imgWords * 8;
+  const size_t listBytes = sizeof(int) * (ssd::kFallbackList + static_cast<size_t>(h->F)), counterBytes = sizeof(int) * 2 * kMaxLanes;
+  if(static_cast<unsigned long long>(h->depth) * planeBytes > cap)
+  {
+    why = "SSD_MAX_PLANE_BYTES = " + std::to_string(cap) + " < " + std::to_string(static_cast<unsigned long long>(h->depth) * planeBytes);
+    return hipErrorOutOfMemory;
+  }
+  ssd::DeviceBuf<unsigned long long> planes[kMaxLanes];
+  ssd::DeviceBuf<int> lists[kMaxLanes];
+  ssd::PinnedBuf<int> counters;
+  hipError_t e = hipSuccess;
+  for(int k = 0; k < h->depth && e == hipSuccess; k++)
+  {
+    e = planes[k].alloc(planeBytes, counted ? &h->bytes : nullptr);
+    if(e == hipSuccess) e = lists[k].alloc(listBytes);
+    if(e == hipSuccess) e = hipMemset(planes[k], 0, planeBytes);
+    if(e == hipSuccess) e = hipMemset(lists[k], 0, listBytes);
+    if(e != hipSuccess)
+      why = std::string("hipMalloc of ") + std::to_string(planeBytes) + " bytes for workspace " + std::to_string(k) + ": " + hipGetErrorString(e);
+  }
+  if(e == hipSuccess && !h->hFallback && (e = counters.alloc(counterBytes)) != hipSuccess)
+    why = "hipHostMalloc of the work lists' counters failed";
+  if(e != hipSuccess)
+  {
+    (void)hipGetLastError();                   /* the failed allocation's error is not the handle's */
+    return e;
+  }
+  if(counters)
+  {
+    std::memset(counters, 0, counterBytes);
+    h->hFallback = std::move(counters);
+  }
+  for(int k = 0; k < h->depth; k++)
+  {
+    h->lane[k].dPlaneImg = std::move(planes[k]);
+    h->lane[k].dFallback = std::move(lists[k]);
+  }
+  return hipSuccess;
+}
+
+/* ... and given back: every workspace's (hFallback stays: the counts of batches not yet fetched are read from it) */
+inline void planes_drop(ssd_handle *h)
+{
+  for(ssd_lane &L : h->lane)
+  {
+    L.dPlaneImg.reset();
+    L.dFallback.reset();
+  }
+}
 
 #endif /* SSD_HANDLE_H_ */

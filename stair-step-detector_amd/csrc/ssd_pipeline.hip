@@ -7,8 +7,7 @@
  * (64 frames per batch 126 k -> 199 k frames/s, 1024: 247 k -> 255 k).  Built purely on the handle
  * entry points; results come back in submission order.
  */
-#include "../../include/ssd_hip.h"
-#include <hip/hip_runtime.h>
+#include "ssd_owned.h"
 
 #include <string>
 #include <vector>
@@ -17,8 +16,8 @@ struct ssd_pipeline
 {
   int device = 0, depth = 0;
   std::vector<ssd_handle *> handles;
-  std::vector<hipStream_t> streams;
-  std::vector<hipEvent_t> produced;       /* ssd_pipeline_submit_after: recorded on the producer's stream */
+  std::vector<ssd::Stream> streams;
+  std::vector<ssd::Event> produced;       /* ssd_pipeline_submit_after: recorded on the producer's stream */
   std::vector<int> frames;                /* frames of the batch each handle holds, 0 = idle */
   unsigned long long submitted = 0, fetched = 0;
   int lastFetched = -1;                   /* handle of the batch ssd_pipeline_next returned last */
@@ -49,11 +48,7 @@ int ssd_pipeline_destroy(ssd_pipeline *p)
   (void)hipSetDevice(p->device);
   for(ssd_handle *h : p->handles)
     ssd_destroy(h);
-  for(hipStream_t s : p->streams)
-    if(s) (void)hipStreamDestroy(s);
-  for(hipEvent_t e : p->produced)
-    if(e) (void)hipEventDestroy(e);
-  delete p;
+  delete p;                                /* its streams and events free themselves (ssd_owned.h) */
   return SSD_OK;
 }
 
@@ -78,20 +73,20 @@ int ssd_pipeline_create(const ssd_config *cfg, const ssd_calibration *cal, int d
       return rc;                            /* ssd_last_error() has the reason */
     }
     p->handles.push_back(h);
-    hipStream_t s = nullptr;
-    if(hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess)
+    ssd::Stream s;
+    if(s.create(hipStreamNonBlocking) != hipSuccess)
     {
       ssd_pipeline_destroy(p);
       return pfail(SSD_E_HIP, "ssd_pipeline_create: hipStreamCreateWithFlags failed");
     }
-    p->streams.push_back(s);
-    hipEvent_t e = nullptr;
-    if(hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess)
+    p->streams.push_back(std::move(s));
+    ssd::Event e;
+    if(e.create(hipEventDisableTiming) != hipSuccess)
     {
       ssd_pipeline_destroy(p);
       return pfail(SSD_E_HIP, "ssd_pipeline_create: hipEventCreateWithFlags failed");
     }
-    p->produced.push_back(e);
+    p->produced.push_back(std::move(e));
     p->frames.push_back(0);
   }
   *out = p;

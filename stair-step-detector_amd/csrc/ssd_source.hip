@@ -5,6 +5,7 @@
  * neither links nor needs it.
  */
 #include "ssd_synth.h"
+#include "ssd_owned.h"
 
 #include <charconv>
 #include <cmath>
@@ -131,19 +132,18 @@ int ssd_synth_generate_device(const ssd_scene *scenes, int nframes, void *d_xyz,
     return fail(SSD_E_NODEVICE, "ssd_synth_generate_device: no HIP device");
   HIP_TRY(hipSetDevice(device));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  ssd_scene *dScenes = nullptr;
-  HIP_TRY(hipMalloc(&dScenes, sizeof(ssd_scene) * nframes));
+  ssd::DeviceBuf<ssd_scene> dScenes;
+  HIP_TRY(dScenes.alloc(sizeof(ssd_scene) * nframes));
   hipError_t e = hipMemcpyAsync(dScenes, scenes, sizeof(ssd_scene) * nframes, hipMemcpyHostToDevice, s);
   if(e == hipSuccess)
   {
     int bx = (nPoints + kThreads * 4 - 1) / (kThreads * 4);
     bx = bx > 2048 ? 2048 : bx < 1 ? 1 : bx;
-    hipLaunchKernelGGL(k_synth, dim3(bx, nframes), dim3(kThreads), 0, s, dScenes, static_cast<float *>(d_xyz), frame_stride_bytes / 4);
+    hipLaunchKernelGGL(k_synth, dim3(bx, nframes), dim3(kThreads), 0, s, dScenes.get(), static_cast<float *>(d_xyz), frame_stride_bytes / 4);
     e = hipGetLastError();
   }
   if(e == hipSuccess)
     e = hipStreamSynchronize(s);
-  (void)hipFree(dScenes);
   if(e != hipSuccess)
     return fail(SSD_E_HIP, std::string("ssd_synth_generate_device: ") + hipGetErrorString(e));
   return SSD_OK;
@@ -180,19 +180,18 @@ int ssd_synth_depth_device(const ssd_scene *scenes, int nframes, float depth_uni
     return fail(SSD_E_NODEVICE, "ssd_synth_depth_device: no HIP device");
   HIP_TRY(hipSetDevice(device));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  ssd_scene *dScenes = nullptr;
-  HIP_TRY(hipMalloc(&dScenes, sizeof(ssd_scene) * nframes));
+  ssd::DeviceBuf<ssd_scene> dScenes;
+  HIP_TRY(dScenes.alloc(sizeof(ssd_scene) * nframes));
   hipError_t e = hipMemcpyAsync(dScenes, scenes, sizeof(ssd_scene) * nframes, hipMemcpyHostToDevice, s);
   if(e == hipSuccess)
   {
     int bx = (nPoints + kThreads * 4 - 1) / (kThreads * 4);
     bx = bx > 2048 ? 2048 : bx < 1 ? 1 : bx;
-    hipLaunchKernelGGL(k_synth_depth, dim3(bx, nframes), dim3(kThreads), 0, s, dScenes, static_cast<unsigned short *>(d_depth), frame_stride_bytes / 2, depth_units);
+    hipLaunchKernelGGL(k_synth_depth, dim3(bx, nframes), dim3(kThreads), 0, s, dScenes.get(), static_cast<unsigned short *>(d_depth), frame_stride_bytes / 2, depth_units);
     e = hipGetLastError();
   }
   if(e == hipSuccess)
     e = hipStreamSynchronize(s);
-  (void)hipFree(dScenes);
   if(e != hipSuccess)
     return fail(SSD_E_HIP, std::string("ssd_synth_depth_device: ") + hipGetErrorString(e));
   return SSD_OK;

@@ -230,7 +230,7 @@ int ssd_test_record_offset(ssd_handle *h, size_t offset_bytes)
   return SSD_OK;
 }
 
-static std::vector<void *> g_recordKeep;
+static std::vector<DeviceBuf<uint2>> g_recordKeep;
 unsigned long long ssd_test_record_realloc_sized(ssd_handle *h, size_t extra_bytes, size_t offset_bytes);
 unsigned long long ssd_test_record_realloc(ssd_handle *h)
 {
@@ -242,30 +242,25 @@ unsigned long long ssd_test_record_realloc_sized(ssd_handle *h, size_t extra_byt
     return 0ull;
   if(hipSetDevice(h->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
     return 0ull;
-  const size_t bytes = h->recordBytes + extra_bytes;
-  void *p = nullptr;
-  if(hipMalloc(&p, bytes) != hipSuccess)
-    return 0ull;
-  g_recordKeep.push_back(h->lane[0].dTileMasksBase);        /* the old one stays allocated: the next hipMalloc cannot reuse its place */
-  h->lane[0].dTileMasksBase = static_cast<uint2 *>(p);
+  /* every workspace's new records first (the first one's with the extra bytes, the others plain), then the switch: the old ones stay
+   * allocated in g_recordKeep, so that the next hipMalloc cannot reuse their place */
+  DeviceBuf<uint2> fresh[kMaxLanes];
+  for(int k = 0; k < h->depth; k++)
+    if(fresh[k].alloc(h->recordBytes + (k == 0 ? extra_bytes : 0)) != hipSuccess)
+      return 0ull;
+  for(int k = 0; k < h->depth; k++)
+  {
+    ssd_lane &L = h->lane[k];
+    g_recordKeep.emplace_back(L.dTileMasksBase.release());
+    L.dTileMasksBase = std::move(fresh[k]);
+    L.dTileMasks = L.dTileMasksBase;
+  }
   h->lane[0].recordSlack = extra_bytes;
   h->lane[0].dTileMasks = h->lane[0].dTileMasksBase + offset_bytes / 8;
-  /* the other workspaces of the handle likewise (plain allocations) */
-  for(int k = 1; k < h->depth; k++)
-  {
-    void *q = nullptr;
-    if(hipMalloc(&q, h->recordBytes) != hipSuccess)
-      return 0ull;
-    g_recordKeep.push_back(h->lane[k].dTileMasksBase);
-    h->lane[k].dTileMasksBase = static_cast<uint2 *>(q);
-    h->lane[k].dTileMasks = h->lane[k].dTileMasksBase;
-  }
-  return reinterpret_cast<unsigned long long>(p) + offset_bytes;
+  return reinterpret_cast<unsigned long long>(h->lane[0].dTileMasksBase.get()) + offset_bytes;
 }
 int ssd_test_record_release(void)
 {
-  for(void *p : g_recordKeep)
-    (void)hipFree(p);
   g_recordKeep.clear();
   return SSD_OK;
 }
@@ -308,25 +303,14 @@ int ssd_test_single_pass(ssd_handle *h, int mode, int sabotage)
   {
     if(!single_pass_geometry(h->P.W, h->P.H))
       return fail(SSD_E_ARG, "ssd_test_single_pass: a tile of 1024 points is not a whole number of this geometry's camera rows");
-    const size_t planeBytes = static_cast<size_t>(plane_pool_size(h->F, h->P.nPoints)) * h->imgWords * 8;
     h->planePool = static_cast<int>(plane_pool_size(h->F, h->P.nPoints));
-    for(int k = 0; k < h->depth; k++)
-      if(!h->lane[k].dPlaneImg)
-      {
-        HIP_TRY(hipMalloc(&h->lane[k].dPlaneImg, planeBytes));
-        HIP_TRY(hipMemset(h->lane[k].dPlaneImg, 0, planeBytes));
-        HIP_TRY(hipMalloc(&h->lane[k].dFallback, sizeof(int) * (kFallbackList + static_cast<size_t>(h->F))));
-        HIP_TRY(hipMemset(h->lane[k].dFallback, 0, sizeof(int) * (kFallbackList + static_cast<size_t>(h->F))));
-      }
+    std::string why;
+    if(!h->lane[0].dPlaneImg && planes_make(h, ~0ull, false, why) != hipSuccess)
+      return fail(SSD_E_HIP, "ssd_test_single_pass: " + why);
   }
   h->singlePassMode = mode;
   h->singlePassSabotage = sabotage;
   h->singlePassBackoff = 0;
-  if(mode == 1 && !h->hFallback)
-  {
-    HIP_TRY(hipHostMalloc(&h->hFallback, sizeof(int) * 2 * kMaxLanes, hipHostMallocDefault));
-    std::memset(h->hFallback, 0, sizeof(int) * 2 * kMaxLanes);
-  }
   return SSD_OK;
 }
 
@@ -554,15 +538,14 @@ int ssd_test_sort_device(int device, const double *dist, int n, int32_t *perm)
   if(device_count() <= 0)
     return fail(SSD_E_NODEVICE, "ssd_test_sort_device: no HIP device");
   HIP_TRY(hipSetDevice(device));
-  double *dd = nullptr;
-  int *di = nullptr;
-  HIP_TRY(hipMalloc(&dd, static_cast<size_t>(n) * sizeof(double)));
-  HIP_TRY(hipMalloc(&di, static_cast<size_t>(n) * sizeof(int)));
+  DeviceBuf<double> dd;
+  DeviceBuf<int> di;
+  HIP_TRY(dd.alloc(static_cast<size_t>(n) * sizeof(double)));
+  HIP_TRY(di.alloc(static_cast<size_t>(n) * sizeof(int)));
   HIP_TRY(hipMemcpy(dd, dist, static_cast<size_t>(n) * sizeof(double), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_sorttest, dim3(1), dim3(64), 0, nullptr, dd, di, n);
+  hipLaunchKernelGGL(k_sorttest, dim3(1), dim3(64), 0, nullptr, dd.get(), di.get(), n);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(perm, di, static_cast<size_t>(n) * sizeof(int), hipMemcpyDeviceToHost));
-  (void)hipFree(dd); (void)hipFree(di);
   return SSD_OK;
 }
 
@@ -573,16 +556,15 @@ int ssd_test_quad_edges_device(int device, const double *quads, int n, const dou
   if(device_count() <= 0)
     return fail(SSD_E_NODEVICE, "ssd_test_quad_edges_device: no HIP device");
   HIP_TRY(hipSetDevice(device));
-  double *dq = nullptr;
-  float *dout = nullptr;
-  HIP_TRY(hipMalloc(&dq, static_cast<size_t>(n) * 8 * sizeof(double)));
-  HIP_TRY(hipMalloc(&dout, static_cast<size_t>(n) * 13 * sizeof(float)));
+  DeviceBuf<double> dq;
+  DeviceBuf<float> dout;
+  HIP_TRY(dq.alloc(static_cast<size_t>(n) * 8 * sizeof(double)));
+  HIP_TRY(dout.alloc(static_cast<size_t>(n) * 13 * sizeof(float)));
   HIP_TRY(hipMemcpy(dq, quads, static_cast<size_t>(n) * 8 * sizeof(double), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_quadedges, dim3(n), dim3(64), 0, nullptr, dq, n, range_xy[0], range_xy[1], range_xy[2], range_xy[3],
-                     256.0 / (range_xy[1] - range_xy[0]), 256.0 / (range_xy[3] - range_xy[2]), dout);
+  hipLaunchKernelGGL(k_quadedges, dim3(n), dim3(64), 0, nullptr, dq.get(), n, range_xy[0], range_xy[1], range_xy[2], range_xy[3],
+                     256.0 / (range_xy[1] - range_xy[0]), 256.0 / (range_xy[3] - range_xy[2]), dout.get());
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(out, dout, static_cast<size_t>(n) * 13 * sizeof(float), hipMemcpyDeviceToHost));
-  (void)hipFree(dq); (void)hipFree(dout);
   return SSD_OK;
 }
 
@@ -593,21 +575,20 @@ int ssd_test_quad_device(int device, const double quad[8], const double *pts_xy,
   if(device_count() <= 0)
     return fail(SSD_E_NODEVICE, "ssd_test_quad_device: no HIP device");
   HIP_TRY(hipSetDevice(device));
-  double *dq = nullptr, *dp = nullptr;
-  unsigned char *di = nullptr;
-  int *de = nullptr;
-  HIP_TRY(hipMalloc(&dq, 8 * sizeof(double)));
-  HIP_TRY(hipMalloc(&dp, static_cast<size_t>(n) * 2 * sizeof(double)));
-  HIP_TRY(hipMalloc(&di, static_cast<size_t>(n)));
-  HIP_TRY(hipMalloc(&de, sizeof(int)));
+  DeviceBuf<double> dq, dp;
+  DeviceBuf<unsigned char> di;
+  DeviceBuf<int> de;
+  HIP_TRY(dq.alloc(8 * sizeof(double)));
+  HIP_TRY(dp.alloc(static_cast<size_t>(n) * 2 * sizeof(double)));
+  HIP_TRY(di.alloc(static_cast<size_t>(n)));
+  HIP_TRY(de.alloc(sizeof(int)));
   HIP_TRY(hipMemcpy(dq, quad, 8 * sizeof(double), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(dp, pts_xy, static_cast<size_t>(n) * 2 * sizeof(double), hipMemcpyHostToDevice));
   HIP_TRY(hipMemset(di, 0, static_cast<size_t>(n)));
-  hipLaunchKernelGGL(k_quadtest, dim3(n > 4096 ? 16 : 1), dim3(256), 0, nullptr, dq, dp, n, di, de);
+  hipLaunchKernelGGL(k_quadtest, dim3(n > 4096 ? 16 : 1), dim3(256), 0, nullptr, dq.get(), dp.get(), n, di.get(), de.get());
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(inside, di, static_cast<size_t>(n), hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(err, de, sizeof(int), hipMemcpyDeviceToHost));
-  (void)hipFree(dq); (void)hipFree(dp); (void)hipFree(di); (void)hipFree(de);
   return SSD_OK;
 }
 
@@ -718,21 +699,20 @@ int ssd_test_grid_boxes_device(int device, const double quad[8], double x_min, d
   if(device_count() <= 0)
     return fail(SSD_E_NODEVICE, "ssd_test_grid_boxes_device: no HIP device");
   HIP_TRY(hipSetDevice(device));
-  double *dq = nullptr;
-  int *db = nullptr, *du = nullptr;
-  unsigned char *di = nullptr;
-  HIP_TRY(hipMalloc(&dq, 8 * sizeof(double)));
-  HIP_TRY(hipMalloc(&db, static_cast<size_t>(n) * 4 * sizeof(int)));
-  HIP_TRY(hipMalloc(&di, static_cast<size_t>(n)));
-  HIP_TRY(hipMalloc(&du, sizeof(int)));
+  DeviceBuf<double> dq;
+  DeviceBuf<int> db, du;
+  DeviceBuf<unsigned char> di;
+  HIP_TRY(dq.alloc(8 * sizeof(double)));
+  HIP_TRY(db.alloc(static_cast<size_t>(n) * 4 * sizeof(int)));
+  HIP_TRY(di.alloc(static_cast<size_t>(n)));
+  HIP_TRY(du.alloc(sizeof(int)));
   HIP_TRY(hipMemcpy(dq, quad, 8 * sizeof(double), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(db, boxes, static_cast<size_t>(n) * 4 * sizeof(int), hipMemcpyHostToDevice));
   HIP_TRY(hipMemset(di, 0, static_cast<size_t>(n)));
-  hipLaunchKernelGGL(k_gridboxes, dim3(1), dim3(256), 0, nullptr, dq, x_min, y_min, box_x, box_y, db, n, di, du);
+  hipLaunchKernelGGL(k_gridboxes, dim3(1), dim3(256), 0, nullptr, dq.get(), x_min, y_min, box_x, box_y, db.get(), n, di.get(), du.get());
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(inside, di, static_cast<size_t>(n), hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(usable, du, sizeof(int), hipMemcpyDeviceToHost));
-  (void)hipFree(dq); (void)hipFree(db); (void)hipFree(di); (void)hipFree(du);
   return SSD_OK;
 }
 
@@ -741,15 +721,14 @@ int ssd_test_hypot_device(int device, const double *a, const double *b, double *
   if(device_count() <= 0)
     return fail(SSD_E_NODEVICE, "ssd_test_hypot_device: no HIP device");
   HIP_TRY(hipSetDevice(device));
-  double *da = nullptr, *db = nullptr, *dout = nullptr;
-  HIP_TRY(hipMalloc(&da, 8 * static_cast<size_t>(n)));
-  HIP_TRY(hipMalloc(&db, 8 * static_cast<size_t>(n)));
-  HIP_TRY(hipMalloc(&dout, 8 * static_cast<size_t>(n)));
+  DeviceBuf<double> da, db, dout;
+  HIP_TRY(da.alloc(8 * static_cast<size_t>(n)));
+  HIP_TRY(db.alloc(8 * static_cast<size_t>(n)));
+  HIP_TRY(dout.alloc(8 * static_cast<size_t>(n)));
   HIP_TRY(hipMemcpy(da, a, 8 * static_cast<size_t>(n), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(db, b, 8 * static_cast<size_t>(n), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_hypot, dim3((n + 255) / 256), dim3(256), 0, nullptr, da, db, dout, n);
+  hipLaunchKernelGGL(k_hypot, dim3((n + 255) / 256), dim3(256), 0, nullptr, da.get(), db.get(), dout.get(), n);
   HIP_TRY(hipMemcpy(out, dout, 8 * static_cast<size_t>(n), hipMemcpyDeviceToHost));
-  (void)hipFree(da); (void)hipFree(db); (void)hipFree(dout);
   return SSD_OK;
 }
 
@@ -764,22 +743,20 @@ int ssd_test_stream_read(int device, const void *d_ptr, size_t bytes, int reps, 
   const size_t nVec = bytes / 12288 * 768;                    /* whole block iterations only */
   const int chunkVec = 768 * 32;                              /* 32 iterations per block, as K1's chunks */
   const unsigned int blocks = static_cast<unsigned int>((nVec + chunkVec - 1) / chunkVec);
-  float *out = nullptr;
-  HIP_TRY(hipMalloc(&out, 16));
-  hipEvent_t e0, e1;
-  HIP_TRY(hipEventCreate(&e0));
-  HIP_TRY(hipEventCreate(&e1));
-  hipLaunchKernelGGL(k_stream_read, dim3(blocks), dim3(256), 0, s, static_cast<const float4 *>(d_ptr), nVec, chunkVec, out);
+  DeviceBuf<float> out;
+  HIP_TRY(out.alloc(16));
+  Event e0, e1;
+  HIP_TRY(e0.create(hipEventDefault));
+  HIP_TRY(e1.create(hipEventDefault));
+  hipLaunchKernelGGL(k_stream_read, dim3(blocks), dim3(256), 0, s, static_cast<const float4 *>(d_ptr), nVec, chunkVec, out.get());
   HIP_TRY(hipEventRecord(e0, s));
   for(int r = 0; r < reps; r++)
-    hipLaunchKernelGGL(k_stream_read, dim3(blocks), dim3(256), 0, s, static_cast<const float4 *>(d_ptr), nVec, chunkVec, out);
+    hipLaunchKernelGGL(k_stream_read, dim3(blocks), dim3(256), 0, s, static_cast<const float4 *>(d_ptr), nVec, chunkVec, out.get());
   HIP_TRY(hipEventRecord(e1, s));
   HIP_TRY(hipEventSynchronize(e1));
   float ms = 0.0f;
   HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
   *ms_avg = ms / static_cast<float>(reps);
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  (void)hipFree(out);
   return SSD_OK;
 }
 
