@@ -291,6 +291,33 @@ int ssd_enqueue_depth_labels(ssd_handle *h, const void *d_depth, size_t frame_st
                              uint8_t *d_labels, size_t label_stride_bytes);
 int ssd_process_host_labels(ssd_handle *h, const float *xyz, int nframes, ssd_frame_result *results, uint8_t *labels);
 int ssd_process_depth_host_labels(ssd_handle *h, const uint16_t *depth, int nframes, ssd_frame_result *results, uint8_t *labels);
+/* ---- riser labels: the evidence pixels of every vertical face, in the same mask ------------------------------------------
+ * EXTENSION.  A surface label needs a height bin among a plateau's effective bins, riser evidence a bin of no
+ * plateau: no point can be both, so one byte per pixel still suffices and no label value above moves.
+ *   ssd_set_riser_labels  waits for the handle's batches in flight.  While it is on AND risers are on (ssd_set_risers), every call that
+ *                         writes labels - ssd_enqueue_labels, ssd_enqueue_depth_labels, ssd_enqueue_cameras with d_labels,
+ *                         ssd_process_host_labels, ssd_process_depth_host_labels, ssd_process_host_cameras with labels - writes,
+ *                         beside the surface labels, SSD_LABEL_RISER_BASE + i into the byte of every evidence point of riser i of the
+ *                         frame's ssd_frame_risers: exactly the points ssd_riser.n_points counts (above), of risers with
+ *                         detected == 0 too.  So the count of label SSD_LABEL_RISER_BASE + i in a frame is risers[i].n_points, and
+ *                         with riser moments also on, ssd_surface_moments_host over the riser half of ssd_labels_split is the frame's
+ *                         ssd_fetch_riser_moments record, byte for byte.  It may be set while risers are off and takes effect when they
+ *                         come on.  While it is off, or risers are off, or a call writes no labels, nothing more is launched and every
+ *                         byte is what it is without this section; results, risers, riser moments, debug records and the surface
+ *                         labels never change.  A frame whose status has SSD_ST_THROW or with fewer than two emitted surfaces carries
+ *                         no riser label; an SSD_ST_OVERFLOW frame is labelled as its truncated riser record reports.  Bytes past W * H
+ *                         of a stride and frames past nframes are not written.  Not part of ssd_enqueue_stages or ssd_pipeline_*.  No
+ *                         buffer is allocated: a pair of events per timing slot, on the first enable.
+ *   ssd_labels_split      host only, no GPU needed: surfaces[k] = labels[k] where labels[k] <= SSD_MAX_STEPS, else 0; risers[k] =
+ *                         labels[k] - SSD_LABEL_RISER_BASE + 1 where the label lies in SSD_LABEL_RISER_BASE .. SSD_LABEL_RISER_BASE +
+ *                         SSD_MAX_RISERS - 1, else 0 - each in the form ssd_surface_moments_host and ssd_surface_refit_moments_host
+ *                         accept (n_surfaces = the frame's n_steps and n_risers).  Either output may be NULL, either may be `labels`
+ *                         itself.  SSD_E_ARG, before anything is written: a label in neither range, null labels with n > 0.
+ * Camera batches: frame i's label bytes are byte for byte those of a handle made by ssd_create(cfg, &cams[camera_of_frame[i]].cal)
+ * (with its intrinsics for depth input) for that frame alone. */
+#define SSD_LABEL_RISER_BASE 32   /* label SSD_LABEL_RISER_BASE + i = the point is evidence of riser i of the frame's ssd_frame_risers */
+int ssd_set_riser_labels(ssd_handle *h, int enable);
+int ssd_labels_split(const uint8_t *labels, size_t n, uint8_t *surfaces /* may be NULL */, uint8_t *risers /* may be NULL */);
 
 /* ---- per-frame calibration: batches of frames from many cameras ------------------------------------------------------
  * EXTENSION.  A handle may hold a table of cameras beside the calibration ssd_create gave it; a cameras
@@ -517,7 +544,7 @@ int ssd_camera_drift_fold(const ssd_frame_moments *moments, const uint16_t *came
  * (16-bit depth input is deprojected first, bit-equal to ssd_deproject_host); an evidence point with some |q| >= 2^20 is left out of
  * the sums and counted in s[i].n_far, so s[i].m.n + s[i].n_far == risers[i].n_points.  The overflow argument is the ground fit's: all
  * sums are exact integers, independent of the order of summation; the device and ssd_surface_moments_host over the riser labels of a
- * host restatement agree bit for bit.
+ * host restatement agree bit for bit (the device's own riser labels, ssd_set_riser_labels and ssd_labels_split above, are such labels).
  *   ssd_set_riser_moments    waits for the handle's batches in flight.  While it is on AND risers are on, every riser pass of a whole
  *                            run (ssd_enqueue*, ssd_process_*, the cameras entry points) also gathers the moments; it may be set while
  *                            risers are off and takes effect when they come on.  Results, risers and debug records do not change.
@@ -825,6 +852,9 @@ int ssd_get_stage_times_back(ssd_handle *h, int back, float ms[7]);
 int ssd_get_predict_time_back(ssd_handle *h, int back, float *ms);
 /* the label kernel's time for the same enqueue (0 when that enqueue wrote no labels) */
 int ssd_get_labels_time_back(ssd_handle *h, int back, float *ms);
+/* its twin for the riser labels' kernel, which runs behind the event that closes the label kernel's time (0 when that enqueue
+ * marked nothing: riser labels or risers off, or no labels written) */
+int ssd_get_riser_labels_time_back(ssd_handle *h, int back, float *ms);
 
 /* Stairs::serialize(): returns the text length, or SSD_E_CAP. A frame whose status has SSD_ST_THROW
  * serialises to the empty string (the reference process terminates instead of printing). */

@@ -34,6 +34,7 @@ def plane_pool_size(frames, points_per_frame):
     per = 16 if points_per_frame < 600000 else POOL_PLANES_PER_FRAME
     return max(frames * per + 2 * MAX_PLANES, min(frames, 8) * MAX_PLANES)
 MAX_STEPS = MAX_STEP_IMAGES + 1
+LABEL_RISER_BASE = 32                # SSD_LABEL_RISER_BASE: label LABEL_RISER_BASE + i = evidence of riser i (Detector.set_riser_labels)
 MAX_SCANS = 128
 MAX_EDGE_PTS = 256
 LINE_CAP = 4096
@@ -247,6 +248,7 @@ EXPORTS = [
     "ssd_process_host_surfaces_refit_device", "ssd_process_host_cameras_surfaces_refit_device",
     "ssd_enqueue_camera_fold", "ssd_enqueue_camera_ground_gates", "ssd_enqueue_cameras_surface_refit_folded", "ssd_camera_drift_from_fold",
     "ssd_process_host_cameras_drift",
+    "ssd_set_riser_labels", "ssd_get_riser_labels_time_back", "ssd_labels_split",
 ]
 # libssd_source.so — the frame source standing in for the camera (include/ssd_source.h)
 SOURCE_EXPORTS = [
@@ -355,6 +357,9 @@ def lib():
                                                  C.POINTER(CameraDrift)]
     L.ssd_set_riser_moments.argtypes = [vp, i32]
     L.ssd_fetch_riser_moments.argtypes = [vp, C.POINTER(FrameMoments), i32, vp]
+    L.ssd_set_riser_labels.argtypes = [vp, i32]
+    L.ssd_get_riser_labels_time_back.argtypes = [vp, i32, C.POINTER(C.c_float)]
+    L.ssd_labels_split.argtypes = [vp, sz, vp, vp]
     L.ssd_riser_fit_solve.argtypes = [C.POINTER(FrameMoments), C.POINTER(FrameRisers), C.POINTER(Calibration), i32, C.POINTER(FrameRiserFits)]
     L.ssd_process_host_riser_fits.argtypes = [vp, vp, i32, i32, C.POINTER(FrameResult), C.POINTER(FrameRisers), C.POINTER(FrameMoments), i32,
                                               C.POINTER(FrameRiserFits)]
@@ -590,6 +595,16 @@ def surface_moments_host(cfg, frame, labels, n_surfaces, ground, intr=None):
     _check(lib().ssd_surface_moments_host(C.byref(cfg), INPUT_DEPTH16 if depth else INPUT_VERTICES, C.byref(intr) if depth else None,
                                           a.ctypes.data_as(C.c_void_p), lab.ctypes.data_as(C.c_void_p), int(n_surfaces), int(ground), C.byref(out)))
     return out
+
+
+def labels_split(labels):
+    """ssd_labels_split: a label mask with riser labels (Detector.set_riser_labels) -> (surfaces, risers), uint8 arrays of its shape:
+    surfaces keeps the labels 0 .. MAX_STEPS, risers holds i + 1 where the label is LABEL_RISER_BASE + i; each is in the form
+    surface_moments_host accepts.  A label in neither range raises SsdError."""
+    lab = np.ascontiguousarray(labels, dtype=np.uint8)
+    surfaces, risers = np.empty_like(lab), np.empty_like(lab)
+    _check(lib().ssd_labels_split(lab.ctypes.data_as(C.c_void_p), lab.size, surfaces.ctypes.data_as(C.c_void_p), risers.ctypes.data_as(C.c_void_p)))
+    return surfaces, risers
 
 
 def surface_fit_solve(moments, cal, min_points=200):
@@ -1208,6 +1223,17 @@ class Detector:
     def set_riser_moments(self, on=True):
         """ssd_set_riser_moments: while on (and risers are on) every riser pass also gathers each riser's exact integer moments"""
         _check(lib().ssd_set_riser_moments(self._h, 1 if on else 0))
+
+    def set_riser_labels(self, on=True):
+        """ssd_set_riser_labels: while on (and risers are on) every call that writes labels also writes LABEL_RISER_BASE + i into the
+        byte of every evidence point of riser i"""
+        _check(lib().ssd_set_riser_labels(self._h, 1 if on else 0))
+
+    def riser_labels_time_ms(self, back=0):
+        """Device time of the riser labels' kernel of the enqueue `back` calls ago (0.0: it marked nothing); timing must be on."""
+        ms = C.c_float()
+        _check(lib().ssd_get_riser_labels_time_back(self._h, back, C.byref(ms)))
+        return float(ms.value)
 
     def fetch_riser_moments(self, nframes, stream=None):
         """-> list of FrameMoments (independent copies; record i = riser i) of the last enqueue / host batch"""

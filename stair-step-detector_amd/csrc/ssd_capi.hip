@@ -704,6 +704,23 @@ int ssd_fetch_riser_moments(ssd_handle *h, ssd_frame_moments *out, int nframes, 
   return SSD_OK;
 }
 
+static int timing_event_pairs(std::vector<Event> &out, const char *who);
+
+int ssd_set_riser_labels(ssd_handle *h, int enable)
+{
+  if(!h)
+    return fail(SSD_E_ARG, "ssd_set_riser_labels: null handle");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipDeviceSynchronize());            /* the batches in flight keep the labels they were enqueued for */
+  if(enable && h->evRiserLabels.empty())
+  {
+    const int rc = timing_event_pairs(h->evRiserLabels, "hipEventCreate (riser labels): ");
+    if(rc) return rc;
+  }
+  h->riserLabels = enable != 0;
+  return SSD_OK;
+}
+
 int ssd_set_timing(ssd_handle *h, int enable)
 {
   if(!h)
@@ -933,6 +950,9 @@ static int enqueue_impl(ssd_handle *h, const void *d_xyz, size_t frame_stride_by
   int evi = timingSlot * 8;
   /* riser moments: whole runs only (ssd_enqueue_stages takes none), and only with the riser pass they ride on */
   const bool riserMoments = P.risers && h->riserMoments && h->dRiserMoments && h->dRisers && stages == SSD_STAGE_ALL;
+  /* riser labels: only where labels are written, and only with the riser pass (k_final refreshes wantedRisers / riserOfBin only then) */
+  const bool riserLabels = labels != nullptr && P.risers && h->riserLabels && !h->evRiserLabels.empty() && stages == SSD_STAGE_ALL;
+  h->riserLabelsTimed[timingSlot] = riserLabels && timing;
 
   const int slot = static_cast<int>(h->finalCount % static_cast<unsigned long long>(h->nSlots));
   const bool direct = nframes <= kDirectResultFrames && h->hResultsDev != nullptr;
@@ -992,6 +1012,13 @@ static int enqueue_impl(ssd_handle *h, const void *d_xyz, size_t frame_stride_by
       if(marks) (void)hipEventRecord(h->evLabels[2 * timingSlot], cs);
       launch_labels(xyz, strideFloats, P, L.dState, L.dTileMasks, h->tileMaskStride, nframes, chunk, depth, labels, labelStride, cs, cams);
       if(marks) (void)hipEventRecord(h->evLabels[2 * timingSlot + 1], cs);
+      /* the riser labels: behind k_labels (which has written every byte) and behind the riser pass above, outside k_labels' timing */
+      if(riserLabels)
+      {
+        if(marks) (void)hipEventRecord(h->evRiserLabels[2 * timingSlot], cs);
+        launch_riser_labels(xyz, strideFloats, P, L.dState, L.dTileMasks, h->tileMaskStride, nframes, chunk, depth, labels, labelStride, cs, cams);
+        if(marks) (void)hipEventRecord(h->evRiserLabels[2 * timingSlot + 1], cs);
+      }
     }
     /* per-surface moments: likewise; the records are zeroed on the batch's stream in front of the kernel, which only adds */
     if(moments)
@@ -1230,6 +1257,24 @@ int ssd_get_labels_time_back(ssd_handle *h, int back, float *ms)
     return SSD_OK;
   HIP_TRY(hipEventSynchronize(h->evLabels[2 * slot + 1]));
   HIP_TRY(hipEventElapsedTime(ms, h->evLabels[2 * slot], h->evLabels[2 * slot + 1]));
+  return SSD_OK;
+}
+
+/* k_riser_labels' time for the same enqueue (0 for an enqueue that marked nothing) */
+int ssd_get_riser_labels_time_back(ssd_handle *h, int back, float *ms)
+{
+  if(!h || !ms)
+    return fail(SSD_E_ARG, "ssd_get_riser_labels_time_back: null");
+  if(!h->timing || h->ev.empty() || back < 0 || back >= SSD_TIMING_SLOTS ||
+     h->enqueueCount < static_cast<unsigned long long>(back) + 1 || h->enqueueCount - 1 - back < h->timedFrom)
+    return fail(SSD_E_ARG, "ssd_get_riser_labels_time_back: no timed enqueue at that position");
+  HIP_TRY(hipSetDevice(h->device));
+  const int slot = static_cast<int>((h->enqueueCount - 1 - back) % SSD_TIMING_SLOTS);
+  *ms = 0.0f;
+  if(!h->riserLabelsTimed[slot] || h->evRiserLabels.empty())
+    return SSD_OK;
+  HIP_TRY(hipEventSynchronize(h->evRiserLabels[2 * slot + 1]));
+  HIP_TRY(hipEventElapsedTime(ms, h->evRiserLabels[2 * slot], h->evRiserLabels[2 * slot + 1]));
   return SSD_OK;
 }
 
@@ -1972,6 +2017,27 @@ static int surface_moments_walk(const std::string &who, const ssd_config *cfg, i
   out->n_surfaces = n_surfaces;
   out->ground = ground ? 1 : 0;
   std::memcpy(out->s, acc, sizeof(acc));
+  return SSD_OK;
+}
+
+/* a label mask with riser labels (ssd_set_riser_labels) into the two forms the host walks above accept; no GPU, no handle */
+int ssd_labels_split(const uint8_t *labels, size_t n, uint8_t *surfaces, uint8_t *risers)
+{
+  if(!labels && n > 0)
+    return fail(SSD_E_ARG, "ssd_labels_split: null labels");
+  /* decided before anything is written: an output may be the input */
+  for(size_t k = 0; k < n; k++)
+    if(labels[k] > SSD_MAX_STEPS && (labels[k] < SSD_LABEL_RISER_BASE || labels[k] >= SSD_LABEL_RISER_BASE + SSD_MAX_RISERS))
+      return fail(SSD_E_ARG, "ssd_labels_split: a label that is neither a surface's nor a riser's");
+  for(size_t k = 0; k < n; k++)
+  {
+    const uint8_t l = labels[k];                 /* read once: either store below may overwrite it */
+    const bool surface = l <= SSD_MAX_STEPS;
+    if(surfaces)
+      surfaces[k] = surface ? l : static_cast<uint8_t>(0);
+    if(risers)
+      risers[k] = surface ? static_cast<uint8_t>(0) : static_cast<uint8_t>(l - SSD_LABEL_RISER_BASE + 1);
+  }
   return SSD_OK;
 }
 

@@ -106,6 +106,11 @@ struct ssd_handle
   ssd::PinnedBuf<ssd_frame_moments> hRiserMomentsBatch;   /* pinned */
   int hRiserMomentsBatchCap = 0, hRiserMomentsBatchFrames = 0;
   int riserMomentsFrames = 0;               /* frames whose riser moments the last enqueue gathered (0: none) */
+  /* riser labels (ssd_set_riser_labels): a switch and the events around k_riser_labels of a timed enqueue, made on
+   * the first enable; no buffer - the kernel writes into the caller's labels */
+  bool riserLabels = false;
+  std::vector<ssd::Event> evRiserLabels;     /* SSD_TIMING_SLOTS x 2 */
+  bool riserLabelsTimed[SSD_TIMING_SLOTS] = {};
   ssd::DeviceBuf<ssd::DebugFrame> dDebug;
   ssd::DeviceBuf<unsigned long long> dDebugImg;
   int debug = 0;                  /* 0 off, 1 records + images (the whole ground image is rastered for it), 2 records only */

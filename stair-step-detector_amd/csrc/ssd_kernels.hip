@@ -4685,6 +4685,87 @@ SSD_ENTRY(__launch_bounds__(kThreads), k_riser_moments, riser_moments_block)(con
   }
 }
 
+/* The riser labels (ssd_set_riser_labels): k_risers' cells and k_risers' evidence rule, expression for expression,
+ * and in place of any sum one byte per evidence point, SSD_LABEL_RISER_BASE + r, at the index k_labels gives the point.  It runs behind
+ * k_labels on the same stream, which has written every byte of the frame; an evidence point's bin is a bin of no plateau, so its byte
+ * is a zero of k_labels' and belongs to this lane alone: single byte stores, nothing read, nothing else rewritten (the neighbouring
+ * bytes are other lanes').  No sums, no atomics, no LDS beyond the frame's riser state and the cell list.  A body of its own rather
+ * than a switch in risers_block / riser_moments_block, so that their code objects stay what they are.  Camera batches:
+ * k_riser_labels_cams (ssd_kernels_cams.hip) runs this body with the frame's own constants. */
+static_assert(SSD_LABEL_RISER_BASE > SSD_MAX_STEPS && SSD_LABEL_RISER_BASE + kMaxRisers - 1 <= 0xff, "surface and riser labels share a byte");
+
+template<int SRC>
+SSD_ENTRY(__launch_bounds__(kThreads, 8), k_riser_labels, riser_labels_block)(const float *__restrict__ xyz, size_t strideFloats, SSD_BYVAL(PointParams) P, double tol,
+                                                        const FrameState *__restrict__ st, const uint2 *__restrict__ tileMasks,
+                                                        size_t tileMaskStride, int chunkPoints, int cellCols, SSD_BYVAL(DepthSrc) D,
+                                                        unsigned char *__restrict__ labels, size_t labelStride)
+{
+  __shared__ unsigned short cellList[kMaxCellsPerBlock];
+  __shared__ unsigned int listScratch[2 * kWavesPerBlock];
+  __shared__ RiserState rs[kMaxRisers];
+  __shared__ signed char riserOfBin[kMaxBins];
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int frame = blockIdx.x;
+  const FrameState &fs = st[frame];
+  const unsigned int wanted = fs.wantedRisers;
+  if(wanted == 0u)                                          /* block-uniform: set by k_final */
+    return;
+  const int nR = min(fs.nRisers, kMaxRisers);
+  if(tid < kMaxBins)
+    riserOfBin[tid] = fs.riserOfBin[tid];
+  if(tid < nR)
+    rs[tid] = fs.riser[tid];
+  __syncthreads();
+
+  const float *base = SRC == kSrcDepth16
+    ? reinterpret_cast<const float *>(reinterpret_cast<const unsigned short *>(xyz) + static_cast<size_t>(frame) * strideFloats)
+    : xyz + static_cast<size_t>(frame) * strideFloats;
+  unsigned char *row = labels + static_cast<size_t>(frame) * labelStride;
+  const int begin = blockIdx.y * chunkPoints;
+  const int end = min(begin + chunkPoints, P.nPoints);
+
+  /* only the cells that hold a bin of a riser are walked (as k_risers) */
+  const int cell0 = begin / kCell;
+  const int nCells = (end - begin + kCell - 1) / kCell;
+  const int count = cell_list_build(tileMasks + static_cast<size_t>(frame) * tileMaskStride + cell0, nCells, cellCols,
+                                    [&](const uint2 info) { return (info.x & wanted) != 0u; }, cellList, listScratch);
+  const int nGroups = (count + 3) >> 2;
+  const int gEnd = ((tid >> 6) + 1) * nGroups / kWavesPerBlock;
+  for(int g = (tid >> 6) * nGroups / kWavesPerBlock; g < gEnd; g++)
+  {
+    const int entry = 4 * g + (lane >> 4);
+    F3 v[kPts];
+    load_cell<SRC>(base, cell0, cellList, entry, count, lane, P.nPoints, v, D);
+    if(entry >= count)                                      /* a row past the end of the list: its points are invalid, its cell is nobody's */
+      continue;
+    const int idx = (cell0 + static_cast<int>(cellList[entry])) * kCell + kPts * (lane & 15);
+    #pragma unroll
+    for(int j = 0; j < kPts; j++)
+    {
+      double wx, wy, wz;
+      if(!world_z(P, v[j], wz))
+        continue;
+      const int r = riserOfBin[height_bin(P, wz)];
+      if(r < 0)
+        continue;
+      const RiserState &R = rs[r];
+      if(!(wz > R.zLo && wz < R.zHi))
+        continue;
+      if(!world_xy(P, v[j], wx, wy))
+        continue;
+      const double a = wx - R.ox, b = wy - R.oy;
+      const double sd = b * R.ux - a * R.uy;                 /* signed distance from the edge line */
+      const double t = a * R.ux + b * R.uy;                  /* position along the edge */
+      if(!(fabs(sd) <= tol && t >= 0.0 && t <= R.len))
+        continue;
+      /* (load_points gives a point beyond nPoints z = 0, and world_z has dropped it: an evidence point lies inside the frame) */
+      if(SSD_CHK(33, idx + j, P.nPoints))
+        row[idx + j] = static_cast<unsigned char>(SSD_LABEL_RISER_BASE + r);
+    }
+  }
+}
+
 /* one thread per frame: the riser records in external world coordinates (ToExternalWorld as in k_final) */
 SSD_ENTRY(, k_riser_results, riser_results_block)(SSD_BYVAL(Params) P, const FrameState *__restrict__ st, ssd_frame_risers *__restrict__ out, int nframes)
 {
@@ -4927,6 +5008,17 @@ void launch_riser_moments(const float *xyz, size_t strideFloats, const Params &P
     hipLaunchKernelGGL(k_riser_moments<decltype(src)::value>, grid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.riserTol, st, tileMasks, tileMaskStride, chunkPoints, P.px.cellCols, D, moments);
   });
   hipLaunchKernelGGL(k_riser_results, dim3((nframes + 63) / 64), dim3(64), 0, s, P, st, out, nframes);
+}
+void launch_riser_labels(const float *xyz, size_t strideFloats, const Params &P, const FrameState *st, const uint2 *tileMasks, size_t tileMaskStride,
+                         int nframes, int chunkPoints, const DepthSrc *depth, unsigned char *labels, size_t labelStride, hipStream_t s, const CameraSel *cams)
+{
+  if(cams)
+    return launch_riser_labels_cams(xyz, strideFloats, P, st, tileMasks, tileMaskStride, nframes, chunkPoints, depth, labels, labelStride, s, *cams);
+  dim3 grid(nframes, chunks_for(P.nPoints, chunkPoints));
+  with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &D)
+  {
+    hipLaunchKernelGGL(k_riser_labels<decltype(src)::value>, grid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.riserTol, st, tileMasks, tileMaskStride, chunkPoints, P.px.cellCols, D, labels, labelStride);
+  });
 }
 
 } // namespace ssd

@@ -189,6 +189,18 @@ __global__ __launch_bounds__(kThreads) void k_riser_moments_cams(const float *__
   riser_moments_block<SRC>(xyz, strideFloats, P, C.P.riserTol, st, tileMasks, tileMaskStride, chunkPoints, C.P.px.cellCols, D, out);
 }
 
+template<int SRC>
+__global__ __launch_bounds__(kThreads, 8) void k_riser_labels_cams(const float *__restrict__ xyz, size_t strideFloats, const CameraRec *__restrict__ cams,
+                                                                   const int *__restrict__ camOf, const FrameState *__restrict__ st, const uint2 *__restrict__ tileMasks,
+                                                                   size_t tileMaskStride, int chunkPoints,
+                                                                   unsigned char *__restrict__ labels, size_t labelStride)
+{
+  const CameraRec &C = camera_of(cams, camOf, blockIdx.x);
+  const PointParams P = C.P.pt;
+  const DepthSrc D = C.D;
+  riser_labels_block<SRC>(xyz, strideFloats, P, C.P.riserTol, st, tileMasks, tileMaskStride, chunkPoints, C.P.px.cellCols, D, labels, labelStride);
+}
+
 /* one thread per frame here, so the record is the thread's own (a few constants of it, once per frame) */
 __global__ void k_riser_results_cams(const CameraRec *__restrict__ cams, const int *__restrict__ camOf, const FrameState *__restrict__ st,
                                      ssd_frame_risers *__restrict__ out, int nframes)
@@ -338,6 +350,15 @@ void launch_riser_moments_cams(const float *xyz, size_t strideFloats, const Para
     hipLaunchKernelGGL(k_riser_moments_cams<decltype(src)::value>, grid, dim3(kThreads), 0, s, xyz, strideFloats, cams.table, cams.index, st, tileMasks, tileMaskStride, chunkPoints, moments);
   });
   hipLaunchKernelGGL(k_riser_results_cams, dim3((nframes + 63) / 64), dim3(64), 0, s, cams.table, cams.index, st, out, nframes);
+}
+void launch_riser_labels_cams(const float *xyz, size_t strideFloats, const Params &P, const FrameState *st, const uint2 *tileMasks, size_t tileMaskStride,
+                              int nframes, int chunkPoints, const DepthSrc *depth, unsigned char *labels, size_t labelStride, hipStream_t s, const CameraSel &cams)
+{
+  dim3 grid(nframes, chunks_for(P.nPoints, chunkPoints));
+  with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &)
+  {
+    hipLaunchKernelGGL(k_riser_labels_cams<decltype(src)::value>, grid, dim3(kThreads), 0, s, xyz, strideFloats, cams.table, cams.index, st, tileMasks, tileMaskStride, chunkPoints, labels, labelStride);
+  });
 }
 
 } // namespace ssd

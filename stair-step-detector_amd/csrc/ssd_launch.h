@@ -59,6 +59,11 @@ void launch_risers(const float *xyz, size_t strideFloats, const Params &P, Frame
  * moments + i, zeroed by the caller on the stream in front of the launch */
 void launch_riser_moments(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, const uint2 *tileMasks, size_t tileMaskStride,
                           ssd_frame_risers *out, ssd_frame_moments *moments, int nframes, int chunkPoints, const DepthSrc *depth, hipStream_t s, const CameraSel *cams = nullptr);
+/* the riser labels (k_riser_labels) behind launch_labels AND launch_risers / launch_riser_moments of the same batch on the same stream,
+ * only while P.risers (k_final refreshes the state it reads only then): SSD_LABEL_RISER_BASE + i into the byte of every evidence point
+ * of riser i, labels and labelStride as launch_labels'; grid and chunkPoints as launch_risers' */
+void launch_riser_labels(const float *xyz, size_t strideFloats, const Params &P, const FrameState *st, const uint2 *tileMasks, size_t tileMaskStride,
+                         int nframes, int chunkPoints, const DepthSrc *depth, unsigned char *labels, size_t labelStride, hipStream_t s, const CameraSel *cams = nullptr);
 
 /* the launchers of the cameras entry points (ssd_kernels_cams.hip): what launch_*(..., cams) hands a cameras batch to */
 /* k_surface_gates (ssd_kernels_solve.hip): rec[i] -> out[i] for nframes >= 1 records, both in device memory and not
@@ -82,6 +87,7 @@ void launch_labels_cams(const float *xyz, size_t strideFloats, const Params &P, 
 void launch_surface_moments_cams(const float *xyz, size_t strideFloats, const Params &P, const FrameState *st, const uint2 *tileMasks, size_t tileMaskStride, int nframes, int chunkPoints, const DepthSrc *depth, ssd_frame_moments *out, hipStream_t s, const CameraSel &cams);
 void launch_risers_cams(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, const uint2 *tileMasks, size_t tileMaskStride, ssd_frame_risers *out, int nframes, int chunkPoints, const DepthSrc *depth, hipStream_t s, const CameraSel &cams);
 void launch_riser_moments_cams(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, const uint2 *tileMasks, size_t tileMaskStride, ssd_frame_risers *out, ssd_frame_moments *moments, int nframes, int chunkPoints, const DepthSrc *depth, hipStream_t s, const CameraSel &cams);
+void launch_riser_labels_cams(const float *xyz, size_t strideFloats, const Params &P, const FrameState *st, const uint2 *tileMasks, size_t tileMaskStride, int nframes, int chunkPoints, const DepthSrc *depth, unsigned char *labels, size_t labelStride, hipStream_t s, const CameraSel &cams);
 }
 
 #endif /* SSD_LAUNCH_H_ */
