@@ -704,7 +704,7 @@ int ssd_fetch_riser_moments(ssd_handle *h, ssd_frame_moments *out, int nframes, 
   return SSD_OK;
 }
 
-static int timing_event_pairs(std::vector<Event> &out, const char *who);
+static int timed_pass_make(ssd_timed_pass &pass, const char *who);
 
 int ssd_set_riser_labels(ssd_handle *h, int enable)
 {
@@ -712,9 +712,9 @@ int ssd_set_riser_labels(ssd_handle *h, int enable)
     return fail(SSD_E_ARG, "ssd_set_riser_labels: null handle");
   HIP_TRY(hipSetDevice(h->device));
   HIP_TRY(hipDeviceSynchronize());            /* the batches in flight keep the labels they were enqueued for */
-  if(enable && h->evRiserLabels.empty())
+  if(enable)
   {
-    const int rc = timing_event_pairs(h->evRiserLabels, "hipEventCreate (riser labels): ");
+    const int rc = timed_pass_make(h->riserLabelsPass, "hipEventCreate (riser labels): ");
     if(rc) return rc;
   }
   h->riserLabels = enable != 0;
@@ -783,11 +783,21 @@ static unsigned long long cameras_call_key(const Params &P)
          | static_cast<unsigned long long>(static_cast<unsigned int>(P.riserMinSupport)) << 2;
 }
 
-/* SSD_TIMING_SLOTS pairs of events around an optional pass (k_labels, k_surface_moments) of a timed enqueue: all of them or none */
-static int timing_event_pairs(std::vector<Event> &out, const char *who)
+/* the events of an optional pass (ssd_timed_pass), on its first use */
+static int timed_pass_make(ssd_timed_pass &pass, const char *who)
 {
-  const hipError_t rc = make_events(out, 2 * SSD_TIMING_SLOTS, hipEventDefault);
+  const hipError_t rc = pass.make();
   return rc == hipSuccess ? SSD_OK : fail(SSD_E_HIP, std::string(who) + hipGetErrorString(rc));
+}
+
+/* The Batch (ssd_launch.h) of a call on workspace L: the frames as the kernels take them, the handle's deprojection, the workspace's
+ * per-frame state.  P: the constants of the call (the handle's, or a copy the call has adjusted), which must outlive the record. */
+static Batch make_batch(const ssd_handle *h, const Params &P, ssd_lane &L, const void *d_frames, size_t frame_stride_bytes, int nframes, bool depthInput,
+                        hipStream_t s, const CameraSel *cams)
+{
+  return Batch{ P, static_cast<const float *>(d_frames), depthInput ? frame_stride_bytes / 2 : frame_stride_bytes / 4, depthInput,
+                DepthSrc{ h->dDepthMaps, h->dDepthMaps ? h->dDepthMaps + P.W : nullptr, h->intr.depth_units, P.W, P.H, depth_row_magic(P.W, P.H) },
+                L.dState, L.dTileMasks, h->tileMaskStride, nframes, s, cams };
 }
 
 /* camOf (host, nframes entries; ssd_enqueue_cameras has checked them): a cameras batch - frame i takes camera camOf[i] of the table;
@@ -868,10 +878,7 @@ static int enqueue_impl(ssd_handle *h, const void *d_xyz, size_t frame_stride_by
     camSel = CameraSel{ h->dCams, L.dCamIndex, h->camsNeedChecks };
     cams = &camSel;
   }
-  const float *xyz = static_cast<const float *>(d_xyz);
-  const size_t strideFloats = depthInput ? frame_stride_bytes / 2 : frame_stride_bytes / 4;    /* elements of the source type */
-  const DepthSrc depthSrc{ h->dDepthMaps, h->dDepthMaps ? h->dDepthMaps + P.W : nullptr, h->intr.depth_units, P.W, P.H, depth_row_magic(P.W, P.H) };
-  const DepthSrc *depth = depthInput ? &depthSrc : nullptr;
+  const Batch B = make_batch(h, P, L, d_xyz, frame_stride_bytes, nframes, depthInput, s, cams);
   const int chunk = choose_chunk(h->tune, P.nPoints, nframes);
   /* K2 and K4 walk cell columns: the taller a block's chunk, the fewer window flushes and block starts per cell (below) */
   /* K1 ends every block with up to 121 global atomics into the frame's histogram: with one-tile chunks (single frames) 768
@@ -926,7 +933,7 @@ static int enqueue_impl(ssd_handle *h, const void *d_xyz, size_t frame_stride_by
    * fails here, loudly, instead of faulting on the device at a null address */
   if(planeImg && !L.dFallback)
     return fail(SSD_E_HIP, "ssd_enqueue: the single pass's planes without their work list (internal)");
-  if(depthInput && !cams && (!depthSrc.xmap || !depthSrc.ymap))
+  if(depthInput && !cams && (!B.depth.xmap || !B.depth.ymap))
     return fail(SSD_E_HIP, "ssd_enqueue_depth: the deprojection maps are missing (ssd_set_intrinsics did not complete)");
   if(!L.dState || !L.dStepImg || !L.dGroundImg || !L.dTileMasks)
     return fail(SSD_E_HIP, "ssd_enqueue: the handle's workspace is incomplete (internal)");
@@ -934,59 +941,59 @@ static int enqueue_impl(ssd_handle *h, const void *d_xyz, size_t frame_stride_by
   h->predictTimed[h->enqueueCount % SSD_TIMING_SLOTS] = planeImg != nullptr;
   const bool timing = h->timing && !h->ev.empty();
   const int timingSlot = static_cast<int>(h->enqueueCount % SSD_TIMING_SLOTS);
-  if(labels && timing && h->evLabels.empty())
+  if(labels && timing)
   {
     /* the label kernel's events, on the first timed enqueue that labels */
-    const int rcEv = timing_event_pairs(h->evLabels, "hipEventCreate (labels): ");
+    const int rcEv = timed_pass_make(h->labelsPass, "hipEventCreate (labels): ");
     if(rcEv) return rcEv;
   }
-  h->labelsTimed[timingSlot] = labels != nullptr && timing;
-  if(moments && timing && h->evSurface.empty())
+  h->labelsPass.timed[timingSlot] = labels != nullptr && timing;
+  if(moments && timing)
   {
-    const int rcEv = timing_event_pairs(h->evSurface, "hipEventCreate (surface moments): ");
+    const int rcEv = timed_pass_make(h->surfacePass, "hipEventCreate (surface moments): ");
     if(rcEv) return rcEv;
   }
-  h->surfaceTimed[timingSlot] = moments != nullptr && timing;
+  h->surfacePass.timed[timingSlot] = moments != nullptr && timing;
   int evi = timingSlot * 8;
   /* riser moments: whole runs only (ssd_enqueue_stages takes none), and only with the riser pass they ride on */
   const bool riserMoments = P.risers && h->riserMoments && h->dRiserMoments && h->dRisers && stages == SSD_STAGE_ALL;
   /* riser labels: only where labels are written, and only with the riser pass (k_final refreshes wantedRisers / riserOfBin only then) */
-  const bool riserLabels = labels != nullptr && P.risers && h->riserLabels && !h->evRiserLabels.empty() && stages == SSD_STAGE_ALL;
-  h->riserLabelsTimed[timingSlot] = riserLabels && timing;
+  const bool riserLabels = labels != nullptr && P.risers && h->riserLabels && !h->riserLabelsPass.ev.empty() && stages == SSD_STAGE_ALL;
+  h->riserLabelsPass.timed[timingSlot] = riserLabels && timing;
 
   const int slot = static_cast<int>(h->finalCount % static_cast<unsigned long long>(h->nSlots));
   const bool direct = nframes <= kDirectResultFrames && h->hResultsDev != nullptr;
   if((stages & SSD_STAGE_FINAL) && h->depth > 1 && h->resultsLane[slot] != li && h->lane[h->resultsLane[slot]].haveLast)
     HIP_TRY(hipStreamWaitEvent(s, h->lane[h->resultsLane[slot]].done, 0));     /* the slot's previous writer was another lane */
 
-  /* the kernels of the chosen stages on stream cs, in order */
-  auto chain = [&](hipStream_t cs, bool marks)
+  /* the kernels of the chosen stages on the batch's stream, in order */
+  auto chain = [&](bool marks)
   {
-    auto mk = [&]() { if(marks) (void)hipEventRecord(h->ev[evi++], cs); };
+    auto mk = [&]() { if(marks) (void)hipEventRecord(h->ev[evi++], s); };
     if(planeImg)
     {
       /* k_predict in front of the seven stages, timed by itself (ssd_get_predict_time_back) */
-      if(marks) (void)hipEventRecord(h->evPredict[timingSlot], cs);
-      launch_predict(xyz, strideFloats, P, L.dState, nframes, depth, L.dFallback, h->planePool, h->singlePassSabotage, cs, cams);
+      if(marks) (void)hipEventRecord(h->evPredict[timingSlot], s);
+      launch_predict(B, L.dFallback, h->planePool, h->singlePassSabotage);
     }
     mk();
     if(stages & SSD_STAGE_HIST)
-      launch_hist(xyz, strideFloats, P, L.dState, L.dTileMasks, h->tileMaskStride, nframes, chunkHist, depth, planeImg, cs, cams);
+      launch_hist(B, chunkHist, planeImg);
     mk();
     if(stages & SSD_STAGE_PEAKS)
-      launch_peaks(P, L.dState, nframes, dbg, planeImg ? L.dFallback : nullptr, cs, cams);
+      launch_peaks(B, dbg, planeImg ? L.dFallback : nullptr);
     mk();
     if(stages & SSD_STAGE_RASTER)
-      launch_raster(xyz, strideFloats, P, L.dState, L.dStepImg, L.dTileMasks, h->tileMaskStride, nframes, chunkRaster, depth, planeImg ? L.dFallback : nullptr, cs, cams);
+      launch_raster(B, chunkRaster, L.dStepImg, planeImg ? L.dFallback : nullptr);
     mk();
     if(stages & SSD_STAGE_OUTLINE)
-      launch_outline(P, L.dState, L.dStepImg, planeImg, nframes, dbg, dbgImg, cs, cams);
+      launch_outline(B, L.dStepImg, planeImg, dbg, dbgImg);
     mk();
     if(stages & SSD_STAGE_QUADS)
-      launch_quads(P, L.dState, nframes, dbg, cs, cams);
+      launch_quads(B, dbg);
     mk();
     if(stages & SSD_STAGE_INQUAD)
-      launch_inquad(xyz, strideFloats, P, L.dState, L.dGroundImg, L.dTileMasks, h->tileMaskStride, nframes, chunkInquad, depth, cs, cams);
+      launch_inquad(B, chunkInquad, L.dGroundImg);
     mk();
     /* The results leave with the batch, into this enqueue's pinned slot (event for ssd_fetch / ssd_fetch_back).  A few frames:
      * k_final stores them there itself — a kilobyte per frame of posted writes, visible to the host once the event has
@@ -995,38 +1002,38 @@ static int enqueue_impl(ssd_handle *h, const void *d_xyz, size_t frame_stride_by
     if(stages & SSD_STAGE_FINAL)
     {
       ssd_frame_result *out = (direct ? h->hResultsDev : h->dResults) + static_cast<size_t>(slot) * h->F;
-      launch_final(P, L.dState, L.dGroundImg, out, nframes, dbg, dbgImg, cs, cams);
+      launch_final(B, L.dGroundImg, out, dbg, dbgImg);
       if(P.risers && riserMoments)
       {
         /* the riser fit: k_riser_moments in place of k_risers - one walk, both results; the records are zeroed in front of it, it only adds */
-        (void)hipMemsetAsync(h->dRiserMoments, 0, sizeof(ssd_frame_moments) * static_cast<size_t>(nframes), cs);
-        launch_riser_moments(xyz, strideFloats, P, L.dState, L.dTileMasks, h->tileMaskStride, h->dRisers, h->dRiserMoments, nframes, chunk, depth, cs, cams);
+        (void)hipMemsetAsync(h->dRiserMoments, 0, sizeof(ssd_frame_moments) * static_cast<size_t>(nframes), s);
+        launch_riser_moments(B, chunk, h->dRisers, h->dRiserMoments);
       }
       else if(P.risers)
-        launch_risers(xyz, strideFloats, P, L.dState, L.dTileMasks, h->tileMaskStride, h->dRisers, nframes, chunk, depth, cs, cams);
+        launch_risers(B, chunk, h->dRisers);
     }
     mk();
     /* per-pixel labels: behind the seven stages (and their timing), in front of the batch's completion event */
     if(labels)
     {
-      if(marks) (void)hipEventRecord(h->evLabels[2 * timingSlot], cs);
-      launch_labels(xyz, strideFloats, P, L.dState, L.dTileMasks, h->tileMaskStride, nframes, chunk, depth, labels, labelStride, cs, cams);
-      if(marks) (void)hipEventRecord(h->evLabels[2 * timingSlot + 1], cs);
+      if(marks) h->labelsPass.begin(timingSlot, s);
+      launch_labels(B, chunk, labels, labelStride);
+      if(marks) h->labelsPass.end(timingSlot, s);
       /* the riser labels: behind k_labels (which has written every byte) and behind the riser pass above, outside k_labels' timing */
       if(riserLabels)
       {
-        if(marks) (void)hipEventRecord(h->evRiserLabels[2 * timingSlot], cs);
-        launch_riser_labels(xyz, strideFloats, P, L.dState, L.dTileMasks, h->tileMaskStride, nframes, chunk, depth, labels, labelStride, cs, cams);
-        if(marks) (void)hipEventRecord(h->evRiserLabels[2 * timingSlot + 1], cs);
+        if(marks) h->riserLabelsPass.begin(timingSlot, s);
+        launch_riser_labels(B, chunk, labels, labelStride);
+        if(marks) h->riserLabelsPass.end(timingSlot, s);
       }
     }
     /* per-surface moments: likewise; the records are zeroed on the batch's stream in front of the kernel, which only adds */
     if(moments)
     {
-      if(marks) (void)hipEventRecord(h->evSurface[2 * timingSlot], cs);
-      (void)hipMemsetAsync(moments, 0, sizeof(ssd_frame_moments) * static_cast<size_t>(nframes), cs);
-      launch_surface_moments(xyz, strideFloats, P, L.dState, L.dTileMasks, h->tileMaskStride, nframes, chunk, depth, moments, cs, cams);
-      if(marks) (void)hipEventRecord(h->evSurface[2 * timingSlot + 1], cs);
+      if(marks) h->surfacePass.begin(timingSlot, s);
+      (void)hipMemsetAsync(moments, 0, sizeof(ssd_frame_moments) * static_cast<size_t>(nframes), s);
+      launch_surface_moments(B, chunk, moments);
+      if(marks) h->surfacePass.end(timingSlot, s);
     }
   };
 
@@ -1056,7 +1063,7 @@ static int enqueue_impl(ssd_handle *h, const void *d_xyz, size_t frame_stride_by
       if(dbg)
         HIP_TRY(hipMemsetAsync(dbg, 0, sizeof(DebugFrame) * nframes, s));
     }
-    chain(s, timing);
+    chain(timing);
   }
   if(stages & SSD_STAGE_HIST)
     L.dirtyFrames = nframes;
@@ -1207,33 +1214,51 @@ int ssd_deproject_host(const ssd_intrinsics *intr, int width, int height, const 
   return SSD_OK;
 }
 
-/* milliseconds of the 7 stages of a timed enqueue; `back` = 0 is the last one, 1 the one before, ...
- * (at most SSD_TIMING_SLOTS - 1 back, and not before timing was switched on); waits for that enqueue */
-int ssd_get_stage_times_back(ssd_handle *h, int back, float ms[7])
+/* The getters of a timed enqueue's times: their arguments, and the ring slot of the enqueue at `back` (0 is the last one, 1 the one
+ * before, ...: at most SSD_TIMING_SLOTS - 1 back, and not before timing was switched on) */
+static int timed_slot(ssd_handle *h, int back, const void *out, const char *who, int *slot)
 {
-  if(!h || !ms)
-    return fail(SSD_E_ARG, "ssd_get_stage_times: null");
+  if(!h || !out)
+    return fail(SSD_E_ARG, std::string(who) + ": null");
   if(!h->timing || h->ev.empty() || back < 0 || back >= SSD_TIMING_SLOTS ||
      h->enqueueCount < static_cast<unsigned long long>(back) + 1 || h->enqueueCount - 1 - back < h->timedFrom)
-    return fail(SSD_E_ARG, "ssd_get_stage_times: no timed enqueue at that position");
+    return fail(SSD_E_ARG, std::string(who) + ": no timed enqueue at that position");
   HIP_TRY(hipSetDevice(h->device));
-  const int base = static_cast<int>((h->enqueueCount - 1 - back) % SSD_TIMING_SLOTS) * 8;
+  *slot = static_cast<int>((h->enqueueCount - 1 - back) % SSD_TIMING_SLOTS);
+  return SSD_OK;
+}
+
+/* ... of an optional pass: 0 for an enqueue that did not run it; waits for that enqueue's pass */
+static int timed_pass_back(ssd_handle *h, int back, float *ms, const char *who, ssd_timed_pass ssd_handle::*pass)
+{
+  int slot = 0;
+  const int rc = timed_slot(h, back, ms, who, &slot);
+  if(rc) return rc;
+  *ms = 0.0f;
+  HIP_TRY((h->*pass).elapsed(slot, ms));
+  return SSD_OK;
+}
+
+/* milliseconds of the 7 stages of a timed enqueue; waits for that enqueue */
+int ssd_get_stage_times_back(ssd_handle *h, int back, float ms[7])
+{
+  int slot = 0;
+  const int rc = timed_slot(h, back, ms, "ssd_get_stage_times", &slot);
+  if(rc) return rc;
+  const int base = slot * 8;
   HIP_TRY(hipEventSynchronize(h->ev[base + 7]));
   for(int i = 0; i < 7; i++)
     HIP_TRY(hipEventElapsedTime(&ms[i], h->ev[base + i], h->ev[base + i + 1]));
   return SSD_OK;
 }
 
-/* k_predict's time, the kernel in front of the seven stages of a single-pass batch (0 for an enqueue that did not run it) */
+/* k_predict's time, the kernel in front of the seven stages of a single-pass batch (0 for an enqueue that did not run it): one event,
+ * ended by the first of the stages' */
 int ssd_get_predict_time_back(ssd_handle *h, int back, float *ms)
 {
-  if(!h || !ms)
-    return fail(SSD_E_ARG, "ssd_get_predict_time_back: null");
-  if(!h->timing || h->ev.empty() || back < 0 || back >= SSD_TIMING_SLOTS ||
-     h->enqueueCount < static_cast<unsigned long long>(back) + 1 || h->enqueueCount - 1 - back < h->timedFrom)
-    return fail(SSD_E_ARG, "ssd_get_predict_time_back: no timed enqueue at that position");
-  HIP_TRY(hipSetDevice(h->device));
-  const int slot = static_cast<int>((h->enqueueCount - 1 - back) % SSD_TIMING_SLOTS);
+  int slot = 0;
+  const int rc = timed_slot(h, back, ms, "ssd_get_predict_time_back", &slot);
+  if(rc) return rc;
   *ms = 0.0f;
   if(!h->predictTimed[slot])
     return SSD_OK;
@@ -1245,55 +1270,19 @@ int ssd_get_predict_time_back(ssd_handle *h, int back, float *ms)
 /* k_labels' time for the same enqueue (0 for an enqueue that wrote no labels) */
 int ssd_get_labels_time_back(ssd_handle *h, int back, float *ms)
 {
-  if(!h || !ms)
-    return fail(SSD_E_ARG, "ssd_get_labels_time_back: null");
-  if(!h->timing || h->ev.empty() || back < 0 || back >= SSD_TIMING_SLOTS ||
-     h->enqueueCount < static_cast<unsigned long long>(back) + 1 || h->enqueueCount - 1 - back < h->timedFrom)
-    return fail(SSD_E_ARG, "ssd_get_labels_time_back: no timed enqueue at that position");
-  HIP_TRY(hipSetDevice(h->device));
-  const int slot = static_cast<int>((h->enqueueCount - 1 - back) % SSD_TIMING_SLOTS);
-  *ms = 0.0f;
-  if(!h->labelsTimed[slot] || h->evLabels.empty())
-    return SSD_OK;
-  HIP_TRY(hipEventSynchronize(h->evLabels[2 * slot + 1]));
-  HIP_TRY(hipEventElapsedTime(ms, h->evLabels[2 * slot], h->evLabels[2 * slot + 1]));
-  return SSD_OK;
+  return timed_pass_back(h, back, ms, "ssd_get_labels_time_back", &ssd_handle::labelsPass);
 }
 
 /* k_riser_labels' time for the same enqueue (0 for an enqueue that marked nothing) */
 int ssd_get_riser_labels_time_back(ssd_handle *h, int back, float *ms)
 {
-  if(!h || !ms)
-    return fail(SSD_E_ARG, "ssd_get_riser_labels_time_back: null");
-  if(!h->timing || h->ev.empty() || back < 0 || back >= SSD_TIMING_SLOTS ||
-     h->enqueueCount < static_cast<unsigned long long>(back) + 1 || h->enqueueCount - 1 - back < h->timedFrom)
-    return fail(SSD_E_ARG, "ssd_get_riser_labels_time_back: no timed enqueue at that position");
-  HIP_TRY(hipSetDevice(h->device));
-  const int slot = static_cast<int>((h->enqueueCount - 1 - back) % SSD_TIMING_SLOTS);
-  *ms = 0.0f;
-  if(!h->riserLabelsTimed[slot] || h->evRiserLabels.empty())
-    return SSD_OK;
-  HIP_TRY(hipEventSynchronize(h->evRiserLabels[2 * slot + 1]));
-  HIP_TRY(hipEventElapsedTime(ms, h->evRiserLabels[2 * slot], h->evRiserLabels[2 * slot + 1]));
-  return SSD_OK;
+  return timed_pass_back(h, back, ms, "ssd_get_riser_labels_time_back", &ssd_handle::riserLabelsPass);
 }
 
 /* k_surface_moments' time (with the memset in front of it) for the same enqueue (0 for an enqueue that gathered none) */
 int ssd_get_surface_moments_time_back(ssd_handle *h, int back, float *ms)
 {
-  if(!h || !ms)
-    return fail(SSD_E_ARG, "ssd_get_surface_moments_time_back: null");
-  if(!h->timing || h->ev.empty() || back < 0 || back >= SSD_TIMING_SLOTS ||
-     h->enqueueCount < static_cast<unsigned long long>(back) + 1 || h->enqueueCount - 1 - back < h->timedFrom)
-    return fail(SSD_E_ARG, "ssd_get_surface_moments_time_back: no timed enqueue at that position");
-  HIP_TRY(hipSetDevice(h->device));
-  const int slot = static_cast<int>((h->enqueueCount - 1 - back) % SSD_TIMING_SLOTS);
-  *ms = 0.0f;
-  if(!h->surfaceTimed[slot] || h->evSurface.empty())
-    return SSD_OK;
-  HIP_TRY(hipEventSynchronize(h->evSurface[2 * slot + 1]));
-  HIP_TRY(hipEventElapsedTime(ms, h->evSurface[2 * slot], h->evSurface[2 * slot + 1]));
-  return SSD_OK;
+  return timed_pass_back(h, back, ms, "ssd_get_surface_moments_time_back", &ssd_handle::surfacePass);
 }
 
 int ssd_get_stage_times(ssd_handle *h, float ms[7])
@@ -2316,19 +2305,13 @@ static int refit_enqueue_impl(ssd_handle *h, const char *who, bool cameras, cons
   }
   h->refitHaveLast = true;
   h->refitLastStream = s;
-  const Params &P = h->P;
-  const float *xyz = static_cast<const float *>(d_frames);
-  const size_t strideFloats = depthInput ? frame_stride_bytes / 2 : frame_stride_bytes / 4;
-  const DepthSrc depthSrc{ h->dDepthMaps, h->dDepthMaps ? h->dDepthMaps + P.W : nullptr, h->intr.depth_units, P.W, P.H, depth_row_magic(P.W, P.H) };
-  const int chunk = choose_chunk(h->tune, P.nPoints, nframes);      /* the first pass's */
+  /* a cameras batch: the table as the batch read it, the index where the batch's own copy left it */
+  const CameraSel camSel{ h->dCams, L.dCamIndex, h->camsNeedChecks };
+  const Batch B = make_batch(h, h->P, L, d_frames, frame_stride_bytes, nframes, depthInput, s, cameras ? &camSel : nullptr);
+  const int chunk = choose_chunk(h->tune, h->P.nPoints, nframes);   /* the first pass's */
   if(timing && gates.host) HIP_TRY(hipEventRecord(h->evRefit[0], s));
   HIP_TRY(hipMemsetAsync(d_out, 0, sizeof(ssd_frame_moments) * static_cast<size_t>(nframes), s));
-  if(cameras)                                  /* the table as the batch read it, the index where the batch's own copy left it */
-    launch_surface_refit_cams(xyz, strideFloats, P, L.dState, L.dTileMasks, h->tileMaskStride, nframes, chunk, depthInput ? &depthSrc : nullptr,
-                              h->dRefitGates, d_out, s, CameraSel{ h->dCams, L.dCamIndex, h->camsNeedChecks });
-  else
-    launch_surface_refit(xyz, strideFloats, P, L.dState, L.dTileMasks, h->tileMaskStride, nframes, chunk, depthInput ? &depthSrc : nullptr,
-                         h->dRefitGates, d_out, s);
+  launch_surface_refit(B, chunk, h->dRefitGates, d_out);
   HIP_TRY(hipGetLastError());
   if(timing) HIP_TRY(hipEventRecord(h->evRefit[1], s));
   h->refitTimed = timing;

@@ -29,6 +29,25 @@ struct ssd_tuning
   int recordPad = 0;              /* cell records per frame added to the stride between the frames' record arrays */
 };
 
+/* The events around an optional pass (k_labels, k_riser_labels, k_surface_moments) of the timed enqueues: a ring of SSD_TIMING_SLOTS pairs,
+ * all of them or none, and whether the enqueue of a slot ran the pass between its pair */
+struct ssd_timed_pass
+{
+  std::vector<ssd::Event> ev;               /* SSD_TIMING_SLOTS x 2, or empty */
+  bool timed[SSD_TIMING_SLOTS] = {};
+  hipError_t make() { return ev.empty() ? ssd::make_events(ev, 2 * SSD_TIMING_SLOTS, hipEventDefault) : hipSuccess; }   /* on first use */
+  void begin(int slot, hipStream_t s) { (void)hipEventRecord(ev[2 * slot], s); }
+  void end(int slot, hipStream_t s) { (void)hipEventRecord(ev[2 * slot + 1], s); }
+  /* the pass's milliseconds at that slot, once it has run; *ms left as it is where the slot's enqueue did not time the pass */
+  hipError_t elapsed(int slot, float *ms)
+  {
+    if(!timed[slot] || ev.empty())
+      return hipSuccess;
+    const hipError_t e = hipEventSynchronize(ev[2 * slot + 1]);
+    return e != hipSuccess ? e : hipEventElapsedTime(ms, ev[2 * slot], ev[2 * slot + 1]);
+  }
+};
+
 /* One complete workspace of a handle: everything a batch in flight owns on the device.  A handle has `depth` of them
  * (ssd_config::batches_in_flight); successive enqueues take them in turn, each on the lane's own stream, so that the launches
  * of one batch fill the gaps the one-block-per-frame kernels of the others leave. */
@@ -109,8 +128,7 @@ struct ssd_handle
   /* riser labels (ssd_set_riser_labels): a switch and the events around k_riser_labels of a timed enqueue, made on
    * the first enable; no buffer - the kernel writes into the caller's labels */
   bool riserLabels = false;
-  std::vector<ssd::Event> evRiserLabels;     /* SSD_TIMING_SLOTS x 2 */
-  bool riserLabelsTimed[SSD_TIMING_SLOTS] = {};
+  ssd_timed_pass riserLabelsPass;
   ssd::DeviceBuf<ssd::DebugFrame> dDebug;
   ssd::DeviceBuf<unsigned long long> dDebugImg;
   int debug = 0;                  /* 0 off, 1 records + images (the whole ground image is rastered for it), 2 records only */
@@ -131,16 +149,14 @@ struct ssd_handle
   std::vector<ssd::Event> evPredict;   /* SSD_TIMING_SLOTS, made with ev: recorded in front of k_predict (single-pass enqueues) */
   bool predictTimed[SSD_TIMING_SLOTS] = {};
   /* per-pixel labels (ssd_enqueue_labels & co.): made on first use, so a handle that never labels holds none of them */
-  std::vector<ssd::Event> evLabels;          /* SSD_TIMING_SLOTS x 2: around k_labels of a timed enqueue */
-  bool labelsTimed[SSD_TIMING_SLOTS] = {};
+  ssd_timed_pass labelsPass;                /* around k_labels of a timed enqueue */
   ssd::DeviceBuf<unsigned char> labelStage[2];   /* ssd_process_*_host_labels: a slice's labels, double-buffered */
   size_t labelStageCap = 0;                 /* bytes per buffer */
   ssd::Stream labelsCopy;                   /* their copies to the host */
   ssd::Event labelsCopied[2];
   /* surface moments (ssd_enqueue_surface_moments & co.): the events around k_surface_moments of a timed enqueue, made on the first one;
    * the host entry point stages a slice's records in labelStage and copies them out on labelsCopy, as labels are */
-  std::vector<ssd::Event> evSurface;         /* SSD_TIMING_SLOTS x 2 */
-  bool surfaceTimed[SSD_TIMING_SLOTS] = {};
+  ssd_timed_pass surfacePass;
   unsigned long long enqueueCount = 0;
   unsigned long long timedFrom = 0;
   /* the camera table (ssd_set_cameras; empty: none).  camParams are make_params()' as they were made; the device records also

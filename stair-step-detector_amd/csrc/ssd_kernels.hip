@@ -4809,24 +4809,29 @@ SSD_ENTRY(, k_riser_results, riser_results_block)(SSD_BYVAL(Params) P, const Fra
 
 namespace ssd
 {
-/* what the two translation units' launchers share */
+/* What the three translation units' launchers share: every launch rule once, over the Batch.  A launcher below, in ssd_kernels_cams.hip
+ * or in ssd_kernels_refit.hip names its __global__ and that kernel's arguments, nothing else.
+ *
+ * Grid layout of every per-frame kernel: FRAME on the fast axis (blockIdx.x), chunk / image slot on the slow
+ * one.  Workgroups are dealt round-robin over the 8 XCDs in linear-id order; with the chunk (or the image
+ * slot) on the fast axis every XCD would always get the same chunk positions of every frame — the stairs
+ * for some XCDs, the skipped ground for others (measured: +30 % on K2, and K3 running on half of the XCDs
+ * because only slots 0..3 hold images).  Frame-fastest gives each XCD whole frames: balanced, and a frame's
+ * state and images stay in one XCD's L2. */
 static inline int chunks_for(int nPoints, int chunkPoints) { return (nPoints + chunkPoints - 1) / chunkPoints; }
+static inline dim3 grid_frames(const Batch &B) { return dim3(B.nframes); }                          /* a block per frame */
+static inline dim3 grid_frame_threads(const Batch &B) { return dim3((B.nframes + 63) / 64); }      /* a thread per frame, blocks of 64 */
+static inline dim3 grid_predict(const Batch &B) { return dim3(B.nframes, kPredictParts); }
+static inline dim3 grid_images(const Batch &B) { return dim3(B.nframes, B.P.maxStepImages); }
+static inline dim3 grid_stream(const Batch &B, int chunkPoints) { return dim3(B.nframes, chunks_for(B.P.nPoints, chunkPoints)); }
+/* k_raster with the single pass's list: a block takes every fourth listed frame in turn */
+static inline dim3 grid_raster(const Batch &B, int chunkPoints, bool listed)
+{
+  return dim3(listed ? (B.nframes + 3) / 4 : B.nframes, chunks_for(B.P.nPoints, chunkPoints));
+}
+/* K1 in the single pass - a tile a whole number of camera rows: the tile loop keeps every wave in its band of columns; else the sorted strips */
+static inline bool hist_strips(const Batch &B, const unsigned long long *planeImg) { return planeImg && kTile % B.P.W != 0; }
 
-static inline bool aligned16(const float *xyz, size_t strideFloats, int nPoints)
-{
-  return (reinterpret_cast<uintptr_t>(xyz) & 15u) == 0 && (strideFloats & 3u) == 0 && (nPoints & 3) == 0;
-}
-/* The point source of a launch as a compile-time constant: f(std::integral_constant<int, kSrc...>, the DepthSrc to pass) */
-template<typename F>
-static inline void with_src(const DepthSrc *depth, bool aligned, F f)
-{
-  if(depth)
-    f(std::integral_constant<int, kSrcDepth16>{}, *depth);
-  else if(aligned)
-    f(std::integral_constant<int, kSrcF3Aligned>{}, DepthSrc{});
-  else
-    f(std::integral_constant<int, kSrcF3>{}, DepthSrc{});
-}
 /* a run-time bool as std::true_type / std::false_type */
 template<typename F>
 static inline void with_bool(bool b, F f)
@@ -4836,188 +4841,215 @@ static inline void with_bool(bool b, F f)
   else
     f(std::false_type{});
 }
+/* The point source of a launch as a compile-time constant: f(std::integral_constant<int, kSrc...>, the DepthSrc to pass) */
+template<typename F>
+static inline void with_src(const Batch &B, F f)
+{
+  if(B.depthInput)
+    f(std::integral_constant<int, kSrcDepth16>{}, B.depth);
+  else if((reinterpret_cast<uintptr_t>(B.xyz) & 15u) == 0 && (B.strideFloats & 3u) == 0 && (B.P.nPoints & 3) == 0)
+    f(std::integral_constant<int, kSrcF3Aligned>{}, DepthSrc{});
+  else
+    f(std::integral_constant<int, kSrcF3>{}, DepthSrc{});
+}
+/* ... and CHECKS with it, f(src, checks, DepthSrc): a cameras batch by its table, a one-calibration batch by its constants */
+template<typename F>
+static inline void with_src_checks(const Batch &B, F f)
+{
+  with_src(B, [&](auto src, const DepthSrc &D) { with_bool(B.cams ? B.cams->checks : needs_checks(B.P), [&](auto checks) { f(src, checks, D); }); });
+}
+/* k_predict's: the depth loop has no pre-filter, so it has the one instantiation without CHECKS */
+template<typename F>
+static inline void with_predict(const Batch &B, F f)
+{
+  with_src_checks(B, [&](auto src, auto checks, const DepthSrc &D)
+  {
+    if constexpr(decltype(src)::value == kSrcDepth16)
+      f(src, std::false_type{}, D);
+    else
+      f(src, checks, D);
+  });
+}
+/* k_inquad's, f(src, full, checks, DepthSrc): debug capture (the whole ground image: the handle's, so the same for every camera) always
+ * takes the instantiation with the rare configurations' tests */
+template<typename F>
+static inline void with_inquad(const Batch &B, F f)
+{
+  with_src_checks(B, [&](auto src, auto checks, const DepthSrc &D)
+  {
+    if(B.P.px.groundFull)
+      f(src, std::true_type{}, std::true_type{}, D);
+    else
+      f(src, std::false_type{}, checks, D);
+  });
+}
+/* k_outline's and k_final's threads, f(std::integral_constant<int, T>): while every image has a CU of its own, the block that gets
+ * through its phases soonest; beyond that the cheapest */
+template<typename F>
+static inline void with_img_threads(const Batch &B, F f)
+{
+  if(B.nframes <= kImgFewFrames)
+    f(std::integral_constant<int, kImgThreadsFew>{});
+  else
+    f(std::integral_constant<int, kImgThreadsBatch>{});
+}
+
+/* the launchers of the cameras entry points (ssd_kernels_cams.hip): what launch_*(B, ...) hands a batch with B.cams to */
+void launch_predict_cams(const Batch &B, int *fallback, int poolPlanes, int sabotage);
+void launch_hist_cams(const Batch &B, int chunkPoints, unsigned long long *planeImg);
+void launch_peaks_cams(const Batch &B, DebugFrame *dbg, int *fallback);
+void launch_raster_cams(const Batch &B, int chunkPoints, unsigned long long *stepImg, const int *fallback);
+void launch_outline_cams(const Batch &B, unsigned long long *stepImg, unsigned long long *planeImg, DebugFrame *dbg, unsigned long long *dbgImg);
+void launch_quads_cams(const Batch &B, DebugFrame *dbg);
+void launch_inquad_cams(const Batch &B, int chunkPoints, unsigned long long *groundImg);
+void launch_final_cams(const Batch &B, unsigned long long *groundImg, ssd_frame_result *results, DebugFrame *dbg, unsigned long long *dbgImg);
+void launch_surface_moments_cams(const Batch &B, int chunkPoints, ssd_frame_moments *out);
+void launch_labels_cams(const Batch &B, int chunkPoints, unsigned char *labels, size_t labelStride);
+void launch_risers_cams(const Batch &B, int chunkPoints, ssd_frame_risers *out);
+void launch_riser_moments_cams(const Batch &B, int chunkPoints, ssd_frame_risers *out, ssd_frame_moments *moments);
+void launch_riser_labels_cams(const Batch &B, int chunkPoints, unsigned char *labels, size_t labelStride);
 } // namespace ssd
 
 #ifndef SSD_CAMERAS_TU
 namespace ssd
 {
 
-/* Grid layout of every per-frame kernel: FRAME on the fast axis (blockIdx.x), chunk / image slot on the slow
- * one.  Workgroups are dealt round-robin over the 8 XCDs in linear-id order; with the chunk (or the image
- * slot) on the fast axis every XCD would always get the same chunk positions of every frame — the stairs
- * for some XCDs, the skipped ground for others (measured: +30 % on K2, and K3 running on half of the XCDs
- * because only slots 0..3 hold images).  Frame-fastest gives each XCD whole frames: balanced, and a frame's
- * state and images stay in one XCD's L2. */
-
-
-void launch_predict(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, int nframes, const DepthSrc *depth,
-                    int *fallback, int poolPlanes, int sabotage, hipStream_t s, const CameraSel *cams)
+void launch_predict(const Batch &B, int *fallback, int poolPlanes, int sabotage)
 {
-  if(cams)
-    return launch_predict_cams(xyz, strideFloats, P, st, nframes, depth, fallback, poolPlanes, sabotage, s, *cams);
-  dim3 pgrid(nframes, kPredictParts);
-  with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &D)
+  if(B.cams)
+    return launch_predict_cams(B, fallback, poolPlanes, sabotage);
+  const Params &P = B.P;
+  with_predict(B, [&](auto src, auto checks, const DepthSrc &D)
   {
     constexpr int SRC = decltype(src)::value;
-    if constexpr(SRC != kSrcDepth16)          /* (the depth loop has no pre-filter: one instantiation) */
-      if(needs_checks(P))
-      {
-        hipLaunchKernelGGL(k_predict_checks<SRC>, pgrid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.pre, st, D, P.minHeight, sabotage, fallback, poolPlanes);
-        return;
-      }
-    hipLaunchKernelGGL(k_predict<SRC>, pgrid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.pre, st, D, P.minHeight, sabotage, fallback, poolPlanes);
+    if constexpr(decltype(checks)::value)
+      hipLaunchKernelGGL(k_predict_checks<SRC>, grid_predict(B), dim3(kThreads), 0, B.s, B.xyz, B.strideFloats, P.pt, P.pre, B.st, D, P.minHeight, sabotage, fallback, poolPlanes);
+    else
+      hipLaunchKernelGGL(k_predict<SRC>, grid_predict(B), dim3(kThreads), 0, B.s, B.xyz, B.strideFloats, P.pt, P.pre, B.st, D, P.minHeight, sabotage, fallback, poolPlanes);
   });
 }
-void launch_hist(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, uint2 *tileMasks, size_t tileMaskStride,
-                 int nframes, int chunkPoints, const DepthSrc *depth, unsigned long long *planeImg, hipStream_t s, const CameraSel *cams)
+void launch_hist(const Batch &B, int chunkPoints, unsigned long long *planeImg)
 {
-  if(cams)
-    return launch_hist_cams(xyz, strideFloats, P, st, tileMasks, tileMaskStride, nframes, chunkPoints, depth, planeImg, s, *cams);
-  dim3 grid(nframes, chunks_for(P.nPoints, chunkPoints));
-  /* the single pass - a tile a whole number of camera rows: the tile loop keeps every wave in its band of columns; else the sorted strips */
-  const bool strips = planeImg && kTile % P.W != 0;
-  with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &D)
+  if(B.cams)
+    return launch_hist_cams(B, chunkPoints, planeImg);
+  const Params &P = B.P;
+  with_src_checks(B, [&](auto src, auto checks, const DepthSrc &D)
   {
-    with_bool(needs_checks(P), [&](auto checks)
-    {
-      constexpr int SRC = decltype(src)::value;
-      constexpr bool CHECKS = decltype(checks)::value;
-      if(planeImg)
-        with_bool(strips, [&](auto sorted)
-        {
-          hipLaunchKernelGGL((k_hist_planes<SRC, decltype(sorted)::value, CHECKS>), grid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.pre, P.px, st, tileMasks, planeImg, tileMaskStride, chunkPoints, D);
-        });
-      else
-        hipLaunchKernelGGL((k_hist<SRC, CHECKS>), grid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.pre, st, tileMasks, tileMaskStride, chunkPoints, D);
-    });
+    constexpr int SRC = decltype(src)::value;
+    constexpr bool CHECKS = decltype(checks)::value;
+    if(planeImg)
+      with_bool(hist_strips(B, planeImg), [&](auto sorted)
+      {
+        hipLaunchKernelGGL((k_hist_planes<SRC, decltype(sorted)::value, CHECKS>), grid_stream(B, chunkPoints), dim3(kThreads), 0, B.s, B.xyz, B.strideFloats, P.pt, P.pre, P.px, B.st, B.tileMasks, planeImg, B.tileMaskStride, chunkPoints, D);
+      });
+    else
+      hipLaunchKernelGGL((k_hist<SRC, CHECKS>), grid_stream(B, chunkPoints), dim3(kThreads), 0, B.s, B.xyz, B.strideFloats, P.pt, P.pre, B.st, B.tileMasks, B.tileMaskStride, chunkPoints, D);
   });
 }
-void launch_peaks(const Params &P, FrameState *st, int nframes, DebugFrame *dbg, int *fallback, hipStream_t s, const CameraSel *cams)
+void launch_peaks(const Batch &B, DebugFrame *dbg, int *fallback)
 {
-  if(cams)
-    return launch_peaks_cams(P, st, nframes, dbg, fallback, s, *cams);
-  hipLaunchKernelGGL(k_peaks, dim3(nframes), dim3(64), 0, s, P, st, nframes, dbg, fallback ? 1 : 0, fallback);
+  if(B.cams)
+    return launch_peaks_cams(B, dbg, fallback);
+  hipLaunchKernelGGL(k_peaks, grid_frames(B), dim3(64), 0, B.s, B.P, B.st, B.nframes, dbg, fallback ? 1 : 0, fallback);
 }
-void launch_raster(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, unsigned long long *stepImg,
-                   const uint2 *tileMasks, size_t tileMaskStride, int nframes, int chunkPoints, const DepthSrc *depth, const int *fallback, hipStream_t s, const CameraSel *cams)
+void launch_raster(const Batch &B, int chunkPoints, unsigned long long *stepImg, const int *fallback)
 {
-  if(cams)
-    return launch_raster_cams(xyz, strideFloats, P, st, stepImg, tileMasks, tileMaskStride, nframes, chunkPoints, depth, fallback, s, *cams);
-  dim3 grid(fallback ? (nframes + 3) / 4 : nframes, chunks_for(P.nPoints, chunkPoints));
-  with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &D)
+  if(B.cams)
+    return launch_raster_cams(B, chunkPoints, stepImg, fallback);
+  with_src(B, [&](auto src, const DepthSrc &D)
   {
     with_bool(fallback != nullptr, [&](auto listed)
     {
-      hipLaunchKernelGGL((k_raster<decltype(src)::value, decltype(listed)::value>), grid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.px, st, stepImg, tileMasks, tileMaskStride, chunkPoints, D, fallback);
+      hipLaunchKernelGGL((k_raster<decltype(src)::value, decltype(listed)::value>), grid_raster(B, chunkPoints, fallback != nullptr), dim3(kThreads), 0, B.s, B.xyz, B.strideFloats, B.P.pt, B.P.px, B.st, stepImg, B.tileMasks, B.tileMaskStride, chunkPoints, D, fallback);
     });
   });
 }
-void launch_outline(const Params &P, FrameState *st, unsigned long long *stepImg, unsigned long long *planeImg, int nframes, DebugFrame *dbg, unsigned long long *dbgImg, hipStream_t s, const CameraSel *cams)
+void launch_outline(const Batch &B, unsigned long long *stepImg, unsigned long long *planeImg, DebugFrame *dbg, unsigned long long *dbgImg)
 {
-  if(cams)
-    return launch_outline_cams(P, st, stepImg, planeImg, nframes, dbg, dbgImg, s, *cams);
-  dim3 grid(nframes, P.maxStepImages);
-  /* while every image has a CU of its own, the block that gets through its phases soonest; beyond that the cheapest */
-  if(nframes <= kImgFewFrames)
-    hipLaunchKernelGGL(k_outline<kImgThreadsFew>, grid, dim3(kImgThreadsFew), 0, s, P, st, stepImg, planeImg, dbg, dbgImg);
-  else
-    hipLaunchKernelGGL(k_outline<kImgThreadsBatch>, grid, dim3(kImgThreadsBatch), 0, s, P, st, stepImg, planeImg, dbg, dbgImg);
-}
-void launch_quads(const Params &P, FrameState *st, int nframes, DebugFrame *dbg, hipStream_t s, const CameraSel *cams)
-{
-  if(cams)
-    return launch_quads_cams(P, st, nframes, dbg, s, *cams);
-  hipLaunchKernelGGL(k_quads, dim3(nframes), dim3(64), 0, s, P, st, nframes, dbg);
-}
-void launch_inquad(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, unsigned long long *groundImg,
-                   const uint2 *tileMasks, size_t tileMaskStride, int nframes, int chunkPoints, const DepthSrc *depth, hipStream_t s, const CameraSel *cams)
-{
-  if(cams)
-    return launch_inquad_cams(xyz, strideFloats, P, st, groundImg, tileMasks, tileMaskStride, nframes, chunkPoints, depth, s, *cams);
-  dim3 grid(nframes, chunks_for(P.nPoints, chunkPoints));
-  auto launch = [&](auto full, auto checks)
+  if(B.cams)
+    return launch_outline_cams(B, stepImg, planeImg, dbg, dbgImg);
+  with_img_threads(B, [&](auto t)
   {
-    with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &D)
-    {
-      hipLaunchKernelGGL((k_inquad<decltype(src)::value, decltype(full)::value, decltype(checks)::value>), grid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.pre, P.px, st, groundImg, tileMasks, tileMaskStride, chunkPoints, D);
-    });
-  };
-  /* debug capture (the whole ground image) always takes the instantiation with the rare configurations' tests */
-  if(P.px.groundFull)
-    launch(std::true_type{}, std::true_type{});
-  else
-    with_bool(needs_checks(P), [&](auto checks) { launch(std::false_type{}, checks); });
-}
-void launch_final(const Params &P, FrameState *st, unsigned long long *groundImg, ssd_frame_result *results, int nframes, DebugFrame *dbg, unsigned long long *dbgImg, hipStream_t s, const CameraSel *cams)
-{
-  if(cams)
-    return launch_final_cams(P, st, groundImg, results, nframes, dbg, dbgImg, s, *cams);
-  if(nframes <= kImgFewFrames)
-    hipLaunchKernelGGL(k_final<kImgThreadsFew>, dim3(nframes), dim3(kImgThreadsFew), 0, s, P, st, groundImg, results, dbg, dbgImg);
-  else
-    hipLaunchKernelGGL(k_final<kImgThreadsBatch>, dim3(nframes), dim3(kImgThreadsBatch), 0, s, P, st, groundImg, results, dbg, dbgImg);
-}
-void launch_labels(const float *xyz, size_t strideFloats, const Params &P, const FrameState *st, const uint2 *tileMasks, size_t tileMaskStride,
-                   int nframes, int chunkPoints, const DepthSrc *depth, unsigned char *labels, size_t labelStride, hipStream_t s, const CameraSel *cams)
-{
-  if(cams)
-    return launch_labels_cams(xyz, strideFloats, P, st, tileMasks, tileMaskStride, nframes, chunkPoints, depth, labels, labelStride, s, *cams);
-  dim3 grid(nframes, chunks_for(P.nPoints, chunkPoints));
-  with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &D)
-  {
-    with_bool(needs_checks(P), [&](auto checks)
-    {
-      hipLaunchKernelGGL((k_labels<decltype(src)::value, decltype(checks)::value>), grid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.pre, st, tileMasks, tileMaskStride, chunkPoints, D, labels, labelStride);
-    });
+    hipLaunchKernelGGL(k_outline<decltype(t)::value>, grid_images(B), dim3(decltype(t)::value), 0, B.s, B.P, B.st, stepImg, planeImg, dbg, dbgImg);
   });
 }
-void launch_surface_moments(const float *xyz, size_t strideFloats, const Params &P, const FrameState *st, const uint2 *tileMasks, size_t tileMaskStride,
-                            int nframes, int chunkPoints, const DepthSrc *depth, ssd_frame_moments *out, hipStream_t s, const CameraSel *cams)
+void launch_quads(const Batch &B, DebugFrame *dbg)
 {
-  if(cams)
-    return launch_surface_moments_cams(xyz, strideFloats, P, st, tileMasks, tileMaskStride, nframes, chunkPoints, depth, out, s, *cams);
-  dim3 grid(nframes, chunks_for(P.nPoints, chunkPoints));
-  with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &D)
+  if(B.cams)
+    return launch_quads_cams(B, dbg);
+  hipLaunchKernelGGL(k_quads, grid_frames(B), dim3(64), 0, B.s, B.P, B.st, B.nframes, dbg);
+}
+void launch_inquad(const Batch &B, int chunkPoints, unsigned long long *groundImg)
+{
+  if(B.cams)
+    return launch_inquad_cams(B, chunkPoints, groundImg);
+  const Params &P = B.P;
+  with_inquad(B, [&](auto src, auto full, auto checks, const DepthSrc &D)
   {
-    with_bool(needs_checks(P), [&](auto checks)
-    {
-      hipLaunchKernelGGL((k_surface_moments<decltype(src)::value, decltype(checks)::value>), grid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.pre, st, tileMasks, tileMaskStride, chunkPoints, D, out);
-    });
+    hipLaunchKernelGGL((k_inquad<decltype(src)::value, decltype(full)::value, decltype(checks)::value>), grid_stream(B, chunkPoints), dim3(kThreads), 0, B.s, B.xyz, B.strideFloats, P.pt, P.pre, P.px, B.st, groundImg, B.tileMasks, B.tileMaskStride, chunkPoints, D);
   });
 }
-void launch_risers(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, const uint2 *tileMasks, size_t tileMaskStride,
-                   ssd_frame_risers *out, int nframes, int chunkPoints, const DepthSrc *depth, hipStream_t s, const CameraSel *cams)
+void launch_final(const Batch &B, unsigned long long *groundImg, ssd_frame_result *results, DebugFrame *dbg, unsigned long long *dbgImg)
 {
-  if(cams)
-    return launch_risers_cams(xyz, strideFloats, P, st, tileMasks, tileMaskStride, out, nframes, chunkPoints, depth, s, *cams);
-  dim3 grid(nframes, chunks_for(P.nPoints, chunkPoints));
-  with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &D)
+  if(B.cams)
+    return launch_final_cams(B, groundImg, results, dbg, dbgImg);
+  with_img_threads(B, [&](auto t)
   {
-    hipLaunchKernelGGL(k_risers<decltype(src)::value>, grid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.riserTol, st, tileMasks, tileMaskStride, chunkPoints, P.px.cellCols, D);
+    hipLaunchKernelGGL(k_final<decltype(t)::value>, grid_frames(B), dim3(decltype(t)::value), 0, B.s, B.P, B.st, groundImg, results, dbg, dbgImg);
   });
-  hipLaunchKernelGGL(k_riser_results, dim3((nframes + 63) / 64), dim3(64), 0, s, P, st, out, nframes);
 }
-void launch_riser_moments(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, const uint2 *tileMasks, size_t tileMaskStride,
-                          ssd_frame_risers *out, ssd_frame_moments *moments, int nframes, int chunkPoints, const DepthSrc *depth, hipStream_t s, const CameraSel *cams)
+void launch_labels(const Batch &B, int chunkPoints, unsigned char *labels, size_t labelStride)
 {
-  if(cams)
-    return launch_riser_moments_cams(xyz, strideFloats, P, st, tileMasks, tileMaskStride, out, moments, nframes, chunkPoints, depth, s, *cams);
-  dim3 grid(nframes, chunks_for(P.nPoints, chunkPoints));
-  with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &D)
+  if(B.cams)
+    return launch_labels_cams(B, chunkPoints, labels, labelStride);
+  with_src_checks(B, [&](auto src, auto checks, const DepthSrc &D)
   {
-    hipLaunchKernelGGL(k_riser_moments<decltype(src)::value>, grid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.riserTol, st, tileMasks, tileMaskStride, chunkPoints, P.px.cellCols, D, moments);
+    hipLaunchKernelGGL((k_labels<decltype(src)::value, decltype(checks)::value>), grid_stream(B, chunkPoints), dim3(kThreads), 0, B.s, B.xyz, B.strideFloats, B.P.pt, B.P.pre, B.st, B.tileMasks, B.tileMaskStride, chunkPoints, D, labels, labelStride);
   });
-  hipLaunchKernelGGL(k_riser_results, dim3((nframes + 63) / 64), dim3(64), 0, s, P, st, out, nframes);
 }
-void launch_riser_labels(const float *xyz, size_t strideFloats, const Params &P, const FrameState *st, const uint2 *tileMasks, size_t tileMaskStride,
-                         int nframes, int chunkPoints, const DepthSrc *depth, unsigned char *labels, size_t labelStride, hipStream_t s, const CameraSel *cams)
+void launch_surface_moments(const Batch &B, int chunkPoints, ssd_frame_moments *out)
 {
-  if(cams)
-    return launch_riser_labels_cams(xyz, strideFloats, P, st, tileMasks, tileMaskStride, nframes, chunkPoints, depth, labels, labelStride, s, *cams);
-  dim3 grid(nframes, chunks_for(P.nPoints, chunkPoints));
-  with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &D)
+  if(B.cams)
+    return launch_surface_moments_cams(B, chunkPoints, out);
+  with_src_checks(B, [&](auto src, auto checks, const DepthSrc &D)
   {
-    hipLaunchKernelGGL(k_riser_labels<decltype(src)::value>, grid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.riserTol, st, tileMasks, tileMaskStride, chunkPoints, P.px.cellCols, D, labels, labelStride);
+    hipLaunchKernelGGL((k_surface_moments<decltype(src)::value, decltype(checks)::value>), grid_stream(B, chunkPoints), dim3(kThreads), 0, B.s, B.xyz, B.strideFloats, B.P.pt, B.P.pre, B.st, B.tileMasks, B.tileMaskStride, chunkPoints, D, out);
+  });
+}
+static void launch_riser_results(const Batch &B, ssd_frame_risers *out)
+{
+  hipLaunchKernelGGL(k_riser_results, grid_frame_threads(B), dim3(64), 0, B.s, B.P, B.st, out, B.nframes);
+}
+void launch_risers(const Batch &B, int chunkPoints, ssd_frame_risers *out)
+{
+  if(B.cams)
+    return launch_risers_cams(B, chunkPoints, out);
+  const Params &P = B.P;
+  with_src(B, [&](auto src, const DepthSrc &D)
+  {
+    hipLaunchKernelGGL(k_risers<decltype(src)::value>, grid_stream(B, chunkPoints), dim3(kThreads), 0, B.s, B.xyz, B.strideFloats, P.pt, P.riserTol, B.st, B.tileMasks, B.tileMaskStride, chunkPoints, P.px.cellCols, D);
+  });
+  launch_riser_results(B, out);
+}
+void launch_riser_moments(const Batch &B, int chunkPoints, ssd_frame_risers *out, ssd_frame_moments *moments)
+{
+  if(B.cams)
+    return launch_riser_moments_cams(B, chunkPoints, out, moments);
+  const Params &P = B.P;
+  with_src(B, [&](auto src, const DepthSrc &D)
+  {
+    hipLaunchKernelGGL(k_riser_moments<decltype(src)::value>, grid_stream(B, chunkPoints), dim3(kThreads), 0, B.s, B.xyz, B.strideFloats, P.pt, P.riserTol, B.st, B.tileMasks, B.tileMaskStride, chunkPoints, P.px.cellCols, D, moments);
+  });
+  launch_riser_results(B, out);
+}
+void launch_riser_labels(const Batch &B, int chunkPoints, unsigned char *labels, size_t labelStride)
+{
+  if(B.cams)
+    return launch_riser_labels_cams(B, chunkPoints, labels, labelStride);
+  const Params &P = B.P;
+  with_src(B, [&](auto src, const DepthSrc &D)
+  {
+    hipLaunchKernelGGL(k_riser_labels<decltype(src)::value>, grid_stream(B, chunkPoints), dim3(kThreads), 0, B.s, B.xyz, B.strideFloats, P.pt, P.riserTol, B.st, B.tileMasks, B.tileMaskStride, chunkPoints, P.px.cellCols, D, labels, labelStride);
   });
 }
 

@@ -213,151 +213,109 @@ __global__ void k_riser_results_cams(const CameraRec *__restrict__ cams, const i
 
 
 /* ========================================================================= */
-/* launchers (declared in ssd_launch.h): grids, block sizes and instantiations are those of the one-calibration launchers */
+/* launchers (declared with the launch rules in ssd_kernels.hip, which the one-calibration launchers share with these: the same grids,
+ * block sizes and instantiations by construction) */
 
-void launch_predict_cams(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, int nframes, const DepthSrc *depth,
-                         int *fallback, int poolPlanes, int sabotage, hipStream_t s, const CameraSel &cams)
+void launch_predict_cams(const Batch &B, int *fallback, int poolPlanes, int sabotage)
 {
-  dim3 pgrid(nframes, kPredictParts);
-  with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &)
+  with_predict(B, [&](auto src, auto checks, const DepthSrc &)
+  {
+    hipLaunchKernelGGL((k_predict_cams<decltype(src)::value, decltype(checks)::value>), grid_predict(B), dim3(kThreads), 0, B.s, B.xyz, B.strideFloats, B.cams->table, B.cams->index, B.st, sabotage, fallback, poolPlanes);
+  });
+}
+void launch_hist_cams(const Batch &B, int chunkPoints, unsigned long long *planeImg)
+{
+  with_src_checks(B, [&](auto src, auto checks, const DepthSrc &)
   {
     constexpr int SRC = decltype(src)::value;
-    if constexpr(SRC == kSrcDepth16)         /* the depth loop has no pre-filter: one instantiation */
-      hipLaunchKernelGGL((k_predict_cams<SRC, false>), pgrid, dim3(kThreads), 0, s, xyz, strideFloats, cams.table, cams.index, st, sabotage, fallback, poolPlanes);
-    else
-      with_bool(cams.checks, [&](auto checks)
+    constexpr bool CHECKS = decltype(checks)::value;
+    if(planeImg)
+      with_bool(hist_strips(B, planeImg), [&](auto sorted)
       {
-        hipLaunchKernelGGL((k_predict_cams<SRC, decltype(checks)::value>), pgrid, dim3(kThreads), 0, s, xyz, strideFloats, cams.table, cams.index, st, sabotage, fallback, poolPlanes);
+        hipLaunchKernelGGL((k_hist_planes_cams<SRC, decltype(sorted)::value, CHECKS>), grid_stream(B, chunkPoints), dim3(kThreads), 0, B.s, B.xyz, B.strideFloats, B.cams->table, B.cams->index, B.st, B.tileMasks, planeImg, B.tileMaskStride, chunkPoints);
       });
+    else
+      hipLaunchKernelGGL((k_hist_cams<SRC, CHECKS>), grid_stream(B, chunkPoints), dim3(kThreads), 0, B.s, B.xyz, B.strideFloats, B.cams->table, B.cams->index, B.st, B.tileMasks, B.tileMaskStride, chunkPoints);
   });
 }
-void launch_hist_cams(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, uint2 *tileMasks, size_t tileMaskStride,
-                      int nframes, int chunkPoints, const DepthSrc *depth, unsigned long long *planeImg, hipStream_t s, const CameraSel &cams)
+void launch_peaks_cams(const Batch &B, DebugFrame *dbg, int *fallback)
 {
-  dim3 grid(nframes, chunks_for(P.nPoints, chunkPoints));
-  const bool strips = planeImg && kTile % P.W != 0;
-  with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &)
-  {
-    with_bool(cams.checks, [&](auto checks)
-    {
-      constexpr int SRC = decltype(src)::value;
-      constexpr bool CHECKS = decltype(checks)::value;
-      if(planeImg)
-        with_bool(strips, [&](auto sorted)
-        {
-          hipLaunchKernelGGL((k_hist_planes_cams<SRC, decltype(sorted)::value, CHECKS>), grid, dim3(kThreads), 0, s, xyz, strideFloats, cams.table, cams.index, st, tileMasks, planeImg, tileMaskStride, chunkPoints);
-        });
-      else
-        hipLaunchKernelGGL((k_hist_cams<SRC, CHECKS>), grid, dim3(kThreads), 0, s, xyz, strideFloats, cams.table, cams.index, st, tileMasks, tileMaskStride, chunkPoints);
-    });
-  });
+  hipLaunchKernelGGL(k_peaks_cams, grid_frames(B), dim3(64), 0, B.s, B.cams->table, B.cams->index, B.st, B.nframes, dbg, fallback ? 1 : 0, fallback);
 }
-void launch_peaks_cams(const Params &, FrameState *st, int nframes, DebugFrame *dbg, int *fallback, hipStream_t s, const CameraSel &cams)
+void launch_raster_cams(const Batch &B, int chunkPoints, unsigned long long *stepImg, const int *fallback)
 {
-  hipLaunchKernelGGL(k_peaks_cams, dim3(nframes), dim3(64), 0, s, cams.table, cams.index, st, nframes, dbg, fallback ? 1 : 0, fallback);
-}
-void launch_raster_cams(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, unsigned long long *stepImg,
-                        const uint2 *tileMasks, size_t tileMaskStride, int nframes, int chunkPoints, const DepthSrc *depth, const int *fallback, hipStream_t s,
-                        const CameraSel &cams)
-{
-  dim3 grid(fallback ? (nframes + 3) / 4 : nframes, chunks_for(P.nPoints, chunkPoints));
-  with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &)
+  with_src(B, [&](auto src, const DepthSrc &)
   {
     with_bool(fallback != nullptr, [&](auto listed)
     {
-      hipLaunchKernelGGL((k_raster_cams<decltype(src)::value, decltype(listed)::value>), grid, dim3(kThreads), 0, s, xyz, strideFloats, cams.table, cams.index, st, stepImg, tileMasks, tileMaskStride, chunkPoints, fallback);
+      hipLaunchKernelGGL((k_raster_cams<decltype(src)::value, decltype(listed)::value>), grid_raster(B, chunkPoints, fallback != nullptr), dim3(kThreads), 0, B.s, B.xyz, B.strideFloats, B.cams->table, B.cams->index, B.st, stepImg, B.tileMasks, B.tileMaskStride, chunkPoints, fallback);
     });
   });
 }
-void launch_outline_cams(const Params &P, FrameState *st, unsigned long long *stepImg, unsigned long long *planeImg, int nframes, DebugFrame *dbg,
-                         unsigned long long *dbgImg, hipStream_t s, const CameraSel &cams)
+void launch_outline_cams(const Batch &B, unsigned long long *stepImg, unsigned long long *planeImg, DebugFrame *dbg, unsigned long long *dbgImg)
 {
-  dim3 grid(nframes, P.maxStepImages);
-  if(nframes <= kImgFewFrames)
-    hipLaunchKernelGGL(k_outline_cams<kImgThreadsFew>, grid, dim3(kImgThreadsFew), 0, s, cams.table, cams.index, st, stepImg, planeImg, dbg, dbgImg);
-  else
-    hipLaunchKernelGGL(k_outline_cams<kImgThreadsBatch>, grid, dim3(kImgThreadsBatch), 0, s, cams.table, cams.index, st, stepImg, planeImg, dbg, dbgImg);
-}
-void launch_quads_cams(const Params &, FrameState *st, int nframes, DebugFrame *dbg, hipStream_t s, const CameraSel &cams)
-{
-  hipLaunchKernelGGL(k_quads_cams, dim3(nframes), dim3(64), 0, s, cams.table, cams.index, st, nframes, dbg);
-}
-void launch_inquad_cams(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, unsigned long long *groundImg,
-                        const uint2 *tileMasks, size_t tileMaskStride, int nframes, int chunkPoints, const DepthSrc *depth, hipStream_t s, const CameraSel &cams)
-{
-  dim3 grid(nframes, chunks_for(P.nPoints, chunkPoints));
-  auto launch = [&](auto full, auto checks)
+  with_img_threads(B, [&](auto t)
   {
-    with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &)
-    {
-      hipLaunchKernelGGL((k_inquad_cams<decltype(src)::value, decltype(full)::value, decltype(checks)::value>), grid, dim3(kThreads), 0, s, xyz, strideFloats, cams.table, cams.index, st, groundImg, tileMasks, tileMaskStride, chunkPoints);
-    });
-  };
-  /* debug capture (the whole ground image: the handle's, so the same for every camera) as launch_inquad */
-  if(P.px.groundFull)
-    launch(std::true_type{}, std::true_type{});
-  else
-    with_bool(cams.checks, [&](auto checks) { launch(std::false_type{}, checks); });
-}
-void launch_final_cams(const Params &, FrameState *st, unsigned long long *groundImg, ssd_frame_result *results, int nframes, DebugFrame *dbg,
-                       unsigned long long *dbgImg, hipStream_t s, const CameraSel &cams)
-{
-  if(nframes <= kImgFewFrames)
-    hipLaunchKernelGGL(k_final_cams<kImgThreadsFew>, dim3(nframes), dim3(kImgThreadsFew), 0, s, cams.table, cams.index, st, groundImg, results, dbg, dbgImg);
-  else
-    hipLaunchKernelGGL(k_final_cams<kImgThreadsBatch>, dim3(nframes), dim3(kImgThreadsBatch), 0, s, cams.table, cams.index, st, groundImg, results, dbg, dbgImg);
-}
-void launch_labels_cams(const float *xyz, size_t strideFloats, const Params &P, const FrameState *st, const uint2 *tileMasks, size_t tileMaskStride,
-                        int nframes, int chunkPoints, const DepthSrc *depth, unsigned char *labels, size_t labelStride, hipStream_t s, const CameraSel &cams)
-{
-  dim3 grid(nframes, chunks_for(P.nPoints, chunkPoints));
-  with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &)
-  {
-    with_bool(cams.checks, [&](auto checks)
-    {
-      hipLaunchKernelGGL((k_labels_cams<decltype(src)::value, decltype(checks)::value>), grid, dim3(kThreads), 0, s, xyz, strideFloats, cams.table, cams.index, st, tileMasks, tileMaskStride, chunkPoints, labels, labelStride);
-    });
+    hipLaunchKernelGGL(k_outline_cams<decltype(t)::value>, grid_images(B), dim3(decltype(t)::value), 0, B.s, B.cams->table, B.cams->index, B.st, stepImg, planeImg, dbg, dbgImg);
   });
 }
-void launch_surface_moments_cams(const float *xyz, size_t strideFloats, const Params &P, const FrameState *st, const uint2 *tileMasks, size_t tileMaskStride,
-                                 int nframes, int chunkPoints, const DepthSrc *depth, ssd_frame_moments *out, hipStream_t s, const CameraSel &cams)
+void launch_quads_cams(const Batch &B, DebugFrame *dbg)
 {
-  dim3 grid(nframes, chunks_for(P.nPoints, chunkPoints));
-  with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &)
+  hipLaunchKernelGGL(k_quads_cams, grid_frames(B), dim3(64), 0, B.s, B.cams->table, B.cams->index, B.st, B.nframes, dbg);
+}
+void launch_inquad_cams(const Batch &B, int chunkPoints, unsigned long long *groundImg)
+{
+  with_inquad(B, [&](auto src, auto full, auto checks, const DepthSrc &)
   {
-    with_bool(cams.checks, [&](auto checks)
-    {
-      hipLaunchKernelGGL((k_surface_moments_cams<decltype(src)::value, decltype(checks)::value>), grid, dim3(kThreads), 0, s, xyz, strideFloats, cams.table, cams.index, st, tileMasks, tileMaskStride, chunkPoints, out);
-    });
+    hipLaunchKernelGGL((k_inquad_cams<decltype(src)::value, decltype(full)::value, decltype(checks)::value>), grid_stream(B, chunkPoints), dim3(kThreads), 0, B.s, B.xyz, B.strideFloats, B.cams->table, B.cams->index, B.st, groundImg, B.tileMasks, B.tileMaskStride, chunkPoints);
   });
 }
-void launch_risers_cams(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, const uint2 *tileMasks, size_t tileMaskStride,
-                        ssd_frame_risers *out, int nframes, int chunkPoints, const DepthSrc *depth, hipStream_t s, const CameraSel &cams)
+void launch_final_cams(const Batch &B, unsigned long long *groundImg, ssd_frame_result *results, DebugFrame *dbg, unsigned long long *dbgImg)
 {
-  dim3 grid(nframes, chunks_for(P.nPoints, chunkPoints));
-  with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &)
+  with_img_threads(B, [&](auto t)
   {
-    hipLaunchKernelGGL(k_risers_cams<decltype(src)::value>, grid, dim3(kThreads), 0, s, xyz, strideFloats, cams.table, cams.index, st, tileMasks, tileMaskStride, chunkPoints);
+    hipLaunchKernelGGL(k_final_cams<decltype(t)::value>, grid_frames(B), dim3(decltype(t)::value), 0, B.s, B.cams->table, B.cams->index, B.st, groundImg, results, dbg, dbgImg);
   });
-  hipLaunchKernelGGL(k_riser_results_cams, dim3((nframes + 63) / 64), dim3(64), 0, s, cams.table, cams.index, st, out, nframes);
 }
-void launch_riser_moments_cams(const float *xyz, size_t strideFloats, const Params &P, FrameState *st, const uint2 *tileMasks, size_t tileMaskStride,
-                               ssd_frame_risers *out, ssd_frame_moments *moments, int nframes, int chunkPoints, const DepthSrc *depth, hipStream_t s, const CameraSel &cams)
+void launch_labels_cams(const Batch &B, int chunkPoints, unsigned char *labels, size_t labelStride)
 {
-  dim3 grid(nframes, chunks_for(P.nPoints, chunkPoints));
-  with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &)
+  with_src_checks(B, [&](auto src, auto checks, const DepthSrc &)
   {
-    hipLaunchKernelGGL(k_riser_moments_cams<decltype(src)::value>, grid, dim3(kThreads), 0, s, xyz, strideFloats, cams.table, cams.index, st, tileMasks, tileMaskStride, chunkPoints, moments);
+    hipLaunchKernelGGL((k_labels_cams<decltype(src)::value, decltype(checks)::value>), grid_stream(B, chunkPoints), dim3(kThreads), 0, B.s, B.xyz, B.strideFloats, B.cams->table, B.cams->index, B.st, B.tileMasks, B.tileMaskStride, chunkPoints, labels, labelStride);
   });
-  hipLaunchKernelGGL(k_riser_results_cams, dim3((nframes + 63) / 64), dim3(64), 0, s, cams.table, cams.index, st, out, nframes);
 }
-void launch_riser_labels_cams(const float *xyz, size_t strideFloats, const Params &P, const FrameState *st, const uint2 *tileMasks, size_t tileMaskStride,
-                              int nframes, int chunkPoints, const DepthSrc *depth, unsigned char *labels, size_t labelStride, hipStream_t s, const CameraSel &cams)
+void launch_surface_moments_cams(const Batch &B, int chunkPoints, ssd_frame_moments *out)
 {
-  dim3 grid(nframes, chunks_for(P.nPoints, chunkPoints));
-  with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &)
+  with_src_checks(B, [&](auto src, auto checks, const DepthSrc &)
   {
-    hipLaunchKernelGGL(k_riser_labels_cams<decltype(src)::value>, grid, dim3(kThreads), 0, s, xyz, strideFloats, cams.table, cams.index, st, tileMasks, tileMaskStride, chunkPoints, labels, labelStride);
+    hipLaunchKernelGGL((k_surface_moments_cams<decltype(src)::value, decltype(checks)::value>), grid_stream(B, chunkPoints), dim3(kThreads), 0, B.s, B.xyz, B.strideFloats, B.cams->table, B.cams->index, B.st, B.tileMasks, B.tileMaskStride, chunkPoints, out);
+  });
+}
+static void launch_riser_results_cams(const Batch &B, ssd_frame_risers *out)
+{
+  hipLaunchKernelGGL(k_riser_results_cams, grid_frame_threads(B), dim3(64), 0, B.s, B.cams->table, B.cams->index, B.st, out, B.nframes);
+}
+void launch_risers_cams(const Batch &B, int chunkPoints, ssd_frame_risers *out)
+{
+  with_src(B, [&](auto src, const DepthSrc &)
+  {
+    hipLaunchKernelGGL(k_risers_cams<decltype(src)::value>, grid_stream(B, chunkPoints), dim3(kThreads), 0, B.s, B.xyz, B.strideFloats, B.cams->table, B.cams->index, B.st, B.tileMasks, B.tileMaskStride, chunkPoints);
+  });
+  launch_riser_results_cams(B, out);
+}
+void launch_riser_moments_cams(const Batch &B, int chunkPoints, ssd_frame_risers *out, ssd_frame_moments *moments)
+{
+  with_src(B, [&](auto src, const DepthSrc &)
+  {
+    hipLaunchKernelGGL(k_riser_moments_cams<decltype(src)::value>, grid_stream(B, chunkPoints), dim3(kThreads), 0, B.s, B.xyz, B.strideFloats, B.cams->table, B.cams->index, B.st, B.tileMasks, B.tileMaskStride, chunkPoints, moments);
+  });
+  launch_riser_results_cams(B, out);
+}
+void launch_riser_labels_cams(const Batch &B, int chunkPoints, unsigned char *labels, size_t labelStride)
+{
+  with_src(B, [&](auto src, const DepthSrc &)
+  {
+    hipLaunchKernelGGL(k_riser_labels_cams<decltype(src)::value>, grid_stream(B, chunkPoints), dim3(kThreads), 0, B.s, B.xyz, B.strideFloats, B.cams->table, B.cams->index, B.st, B.tileMasks, B.tileMaskStride, chunkPoints, labels, labelStride);
   });
 }
 

@@ -332,33 +332,18 @@ __global__ __launch_bounds__(kThreads) void k_surface_refit_cams(const float *__
   surface_refit_block<SRC, CHECKS>(xyz, strideFloats, P, Q, st, tileMasks, tileMaskStride, chunkPoints, D, gates, out);
 }
 
-/* grid, block size and instantiations are launch_surface_moments' */
-void launch_surface_refit(const float *xyz, size_t strideFloats, const Params &P, const FrameState *st, const uint2 *tileMasks, size_t tileMaskStride,
-                          int nframes, int chunkPoints, const DepthSrc *depth, const ssd_frame_gates *gates, ssd_frame_moments *out, hipStream_t s)
+/* grid, block size and instantiations are launch_surface_moments' (the launch rules of ssd_kernels.hip); a cameras batch: CHECKS by the
+ * table, and B.depthInput only says that the source is 16-bit depth - each frame's DepthSrc is its camera's */
+void launch_surface_refit(const Batch &B, int chunkPoints, const ssd_frame_gates *gates, ssd_frame_moments *out)
 {
-  dim3 grid(nframes, chunks_for(P.nPoints, chunkPoints));
-  with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &D)
+  with_src_checks(B, [&](auto src, auto checks, const DepthSrc &D)
   {
-    with_bool(needs_checks(P), [&](auto checks)
-    {
-      hipLaunchKernelGGL((k_surface_refit<decltype(src)::value, decltype(checks)::value>), grid, dim3(kThreads), 0, s, xyz, strideFloats, P.pt, P.pre, st, tileMasks, tileMaskStride, chunkPoints, D, gates, out);
-    });
-  });
-}
-
-/* launch_surface_refit's grid and instantiations, CHECKS by the table (as launch_surface_moments_cams); depth only says that the source
- * is 16-bit depth: each frame's DepthSrc is its camera's */
-void launch_surface_refit_cams(const float *xyz, size_t strideFloats, const Params &P, const FrameState *st, const uint2 *tileMasks, size_t tileMaskStride,
-                               int nframes, int chunkPoints, const DepthSrc *depth, const ssd_frame_gates *gates, ssd_frame_moments *out, hipStream_t s,
-                               const CameraSel &cams)
-{
-  dim3 grid(nframes, chunks_for(P.nPoints, chunkPoints));
-  with_src(depth, aligned16(xyz, strideFloats, P.nPoints), [&](auto src, const DepthSrc &)
-  {
-    with_bool(cams.checks, [&](auto checks)
-    {
-      hipLaunchKernelGGL((k_surface_refit_cams<decltype(src)::value, decltype(checks)::value>), grid, dim3(kThreads), 0, s, xyz, strideFloats, cams.table, cams.index, st, tileMasks, tileMaskStride, chunkPoints, gates, out);
-    });
+    constexpr int SRC = decltype(src)::value;
+    constexpr bool CHECKS = decltype(checks)::value;
+    if(B.cams)
+      hipLaunchKernelGGL((k_surface_refit_cams<SRC, CHECKS>), grid_stream(B, chunkPoints), dim3(kThreads), 0, B.s, B.xyz, B.strideFloats, B.cams->table, B.cams->index, B.st, B.tileMasks, B.tileMaskStride, chunkPoints, gates, out);
+    else
+      hipLaunchKernelGGL((k_surface_refit<SRC, CHECKS>), grid_stream(B, chunkPoints), dim3(kThreads), 0, B.s, B.xyz, B.strideFloats, B.P.pt, B.P.pre, B.st, B.tileMasks, B.tileMaskStride, chunkPoints, D, gates, out);
   });
 }
 

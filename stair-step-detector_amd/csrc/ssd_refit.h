@@ -32,15 +32,11 @@ __host__ __device__ inline bool refit_keeps(const ssd_frame_gates &G, int k, flo
   return refit_gate_open(g.gate) && __builtin_fabs(r) <= g.gate;
 }
 
-/* k_surface_refit after a whole run of the chain on the same workspace: launch_surface_moments' arguments, and gates[i] = frame i's
- * (device memory); frame i's record at out + i, zeroed by the caller on the stream in front of the launch */
-void launch_surface_refit(const float *xyz, size_t strideFloats, const Params &P, const FrameState *st, const uint2 *tileMasks, size_t tileMaskStride,
-                          int nframes, int chunkPoints, const DepthSrc *depth, const ssd_frame_gates *gates, ssd_frame_moments *out, hipStream_t s);
-/* k_surface_refit_cams after a whole cameras batch on the same workspace (ssd_enqueue_cameras_surface_refit): the
- * same, with the handle's table and that workspace's index in place of P's constants; gates[i] is still frame i's */
-void launch_surface_refit_cams(const float *xyz, size_t strideFloats, const Params &P, const FrameState *st, const uint2 *tileMasks, size_t tileMaskStride,
-                               int nframes, int chunkPoints, const DepthSrc *depth, const ssd_frame_gates *gates, ssd_frame_moments *out, hipStream_t s,
-                               const CameraSel &cams);
+/* k_surface_refit after a whole run of the chain on the same workspace (k_surface_refit_cams after a whole cameras batch, under the table
+ * and that workspace's index: DESIGN.md section 7h): launch_surface_moments' arguments, and gates[i] = frame i's (device memory); frame i's
+ * record at out + i, zeroed by the caller on the stream in front of the launch */
+struct Batch;                                 /* ssd_launch.h */
+void launch_surface_refit(const Batch &B, int chunkPoints, const ssd_frame_gates *gates, ssd_frame_moments *out);
 
 } // namespace ssd
 

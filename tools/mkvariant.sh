@@ -1,7 +1,8 @@
 #!/bin/bash
 # tools/mkvariant.sh NAME [GIT_REV] [EXTRA_FLAGS] [SED_EXPR] — builds stair-step-detector_amd/lib_NAME/libssd_hip.so for A/B runs (tools/ab.sh,
-# tools/ab_inflight.py): the current tree, with csrc/ssd_kernels.hip taken from GIT_REV when given (the kernels' launch interface
-# must still match the current ssd_launch.h).  SED_EXPR, when given, is applied to the copy of ssd_kernels.hip
+# tools/ab_inflight.py): the current tree, with csrc/ssd_kernels.hip taken from GIT_REV when given (its launchers must still be
+# the current ssd_launch.h's - launch_x(const Batch &, ...) - and its launch rules those ssd_kernels_cams.hip / ssd_kernels_refit.hip
+# call: a GIT_REV from before the Batch record does not build).  SED_EXPR, when given, is applied to the copy of ssd_kernels.hip
 # (experiments that are not worth a macro in the source).  Tools only; lib_* is git-ignored and travels to the GPU box.
 set -e
 NAME=$1; REV=$2; EXTRA=$3; SEDX=$4
