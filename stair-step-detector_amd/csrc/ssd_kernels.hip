@@ -28,7 +28,10 @@
  * ssd_kernels_cams.hip defines SSD_CAMERAS_TU and includes it for the device code alone: the kernels whose body stands in the
  * entry point itself become device functions there (SSD_ENTRY gives them their second name, SSD_BYVAL turns the by-value
  * constants into references), and the cameras entry points call them with the frame's camera record.
- * Without SSD_CAMERAS_TU both macros spell exactly what stood here before, so this translation unit's code does not change. */
+ * Without SSD_CAMERAS_TU both macros spell exactly what stood here before, so this translation unit's code does not change.
+ * That rule - a kernel's code object stays byte for byte what it was - holds for the chain K0 - K5, which bench.py measures.  The
+ * extension kernels K6 - K8 (labels, surface moments, the refit, the three riser passes) are written from shared pieces and held to
+ * their results, their resources and their time instead: DESIGN.md section 7l. */
 #ifndef SSD_CAMERAS_TU
 #define SSD_ENTRY(bounds, kernel, block) __global__ bounds void kernel
 #define SSD_BYVAL(T) T
@@ -46,6 +49,7 @@
 #include "ssd_bestline.h"
 #include "ssd_sort.h"
 #include "ssd_predict.h"    /* k_predict's sample rule (predict_sample_run), shared with the tests */
+#include "ssd_refit.h"      /* the refit's gate rule (refit_keeps), shared with the host */
 
 namespace ssd
 {
@@ -3707,6 +3711,102 @@ __device__ __forceinline__ void store_labels4(unsigned char *__restrict__ row, b
   }
 }
 
+/* ---- what K6 - K8 share (the labels, the surface moments and the refit here; the three riser passes below) ---- */
+
+/* A block's chunk of a frame: the frame's points, and K1's records of the chunk's cells. */
+struct Chunk
+{
+  const float *base;
+  const uint2 *cells;
+  int cell0, nCells;
+};
+template<int SRC>
+__device__ __forceinline__ Chunk chunk_of(const float *__restrict__ xyz, size_t strideFloats, const uint2 *__restrict__ tileMasks, size_t tileMaskStride,
+                                          int chunkPoints, int nPoints)
+{
+  const int frame = blockIdx.x;
+  Chunk c;
+  c.base = SRC == kSrcDepth16
+    ? reinterpret_cast<const float *>(reinterpret_cast<const unsigned short *>(xyz) + static_cast<size_t>(frame) * strideFloats)
+    : xyz + static_cast<size_t>(frame) * strideFloats;
+  const int begin = blockIdx.y * chunkPoints;
+  const int end = min(begin + chunkPoints, nPoints);
+  c.cell0 = begin / kCell;
+  c.nCells = (end - begin + kCell - 1) / kCell;
+  c.cells = tileMasks + static_cast<size_t>(frame) * tileMaskStride + c.cell0;
+  return c;
+}
+
+/* The chunk's cells that hold a bin of `wanted`, listed in order, and the wave's share of the list: groups g .. gEnd - 1 of four cells,
+ * entry 4 g + (lane >> 4) of the list for each row of sixteen lanes (load_cell). */
+struct CellWalk { int count, g, gEnd; };
+__device__ __forceinline__ CellWalk wanted_cells(const Chunk &c, int cols, unsigned int wanted, unsigned short *cellList, unsigned int *listScratch)
+{
+  CellWalk w;
+  w.count = cell_list_build(c.cells, c.nCells, cols, [&](const uint2 info) { return (info.x & wanted) != 0u; }, cellList, listScratch);
+  const int nGroups = (w.count + 3) >> 2, wave = threadIdx.x >> 6;
+  w.g = wave * nGroups / kWavesPerBlock;
+  w.gEnd = (wave + 1) * nGroups / kWavesPerBlock;
+  return w;
+}
+
+/* The frame's live state into the block's LabelsLds, for every kernel that takes k_inquad's decision once more (quad_decide<.., true>);
+ * the caller's barrier follows.  Nothing of a frame k_quads found no live quadrilateral in, or whose quadrilaterals the reference would
+ * have thrown on, is labelled: wanted = 0 then (block-uniform), and nothing is staged. */
+struct LiveFrame
+{
+  bool live;
+  unsigned int wanted;                          /* the bin groups of the live quadrilaterals */
+  int nLive, gSlot;                             /* the live slots, and the ground's among them (-1: none) */
+};
+__device__ __forceinline__ LiveFrame labels_stage(LabelsLds &L, const FrameState &fs, const PointParams &P, const PreXY &Q)
+{
+  const int tid = threadIdx.x;
+  LiveFrame f;
+  f.live = fs.anyActive != 0u && (fs.status & SSD_ST_THROW) == 0u;
+  f.wanted = f.live ? fs.wantedQuads : 0u;
+  f.nLive = 0;
+  f.gSlot = -1;
+  if(f.live)
+  {
+    f.nLive = fs.nLive;
+    f.gSlot = (f.nLive > 0 && fs.accActive[kGroundAcc]) ? f.nLive - 1 : -1;           /* the ground is the last live slot */
+    if(tid < kMaxBins)
+    {
+      const unsigned char s = fs.lutLive[tid];
+      L.lut[tid] = s == 0xff ? static_cast<unsigned char>(kMaxLive) : s;
+    }
+    if(tid <= kMaxLive)
+    {
+      /* slot order = accumulator order (treads ascending, the ground last); the result has the ground first */
+      int lab = 0;
+      if(tid < f.nLive)
+        lab = tid == f.gSlot ? 1 : tid + 1 + (f.gSlot >= 0 ? 1 : 0);
+      L.label[tid] = static_cast<unsigned char>(lab <= SSD_MAX_STEPS ? lab : 0);
+    }
+    constexpr int qtWords = kMaxLive * static_cast<int>(sizeof(QuadTest) / 4);
+    constexpr int egWords = kMaxLive * static_cast<int>(sizeof(QuadEdgesF) / 4);
+    for(int w = tid; w < qtWords; w += kThreads)
+      reinterpret_cast<unsigned int *>(L.qts)[w] = reinterpret_cast<const unsigned int *>(fs.qtLive)[w];
+    stage_quad_edges(L.edges, fs.edgeLive, egWords, Q.dE0);
+    if(tid == 0)
+      k1_consts_fill(L.kc, P, nullptr);
+  }
+  return f;
+}
+
+/* the point's label by the decision of quad_decide<.., true>: the live slot's, 0 where the point is in none */
+template<bool CHECKS>
+__device__ __forceinline__ unsigned int label_of(const F3 &p, const PreXY &Q, const PreLane lc, const LabelsLds &L)
+{
+  f32x2 d;
+  float M, M3;
+  unsigned int q;
+  unsigned long long mSlow, mIn, mGround;
+  quad_decide<CHECKS, true>(p, Q, lc, L.edges, L.lut, L.qts, L.kc, -1, d, M, M3, q, mSlow, mIn, mGround);
+  return __builtin_amdgcn_inverse_ballot_w64(mIn) ? L.label[min(q, static_cast<unsigned int>(kMaxLive))] : 0u;
+}
+
 template<int SRC, bool CHECKS>
 SSD_ENTRY(__launch_bounds__(kThreads), k_labels, labels_block)(const float *__restrict__ xyz, size_t strideFloats, SSD_BYVAL(PointParams) P, SSD_BYVAL(PreXY) Q,
                                                      const FrameState *__restrict__ st, const uint2 *__restrict__ tileMasks,
@@ -3716,14 +3816,15 @@ SSD_ENTRY(__launch_bounds__(kThreads), k_labels, labels_block)(const float *__re
   __shared__ LabelsLds L;
   const int tid = threadIdx.x, lane = tid & 63;
   const int frame = blockIdx.x;
+  /* labels_stage's text, and not a call of it: staged through the function this kernel takes 95 scalar registers for 71 and its
+   * 16-bit depth instantiations 5 to 8 % longer on an MI355X (profiles/extension_kernels_shared.txt) */
   const FrameState &fs = st[frame];
-  /* nothing of a frame k_quads found no live quadrilateral in, or whose quadrilaterals the reference would have thrown on, is labelled */
-  const bool live = fs.anyActive != 0u && (fs.status & SSD_ST_THROW) == 0u;           /* block-uniform */
+  const bool live = fs.anyActive != 0u && (fs.status & SSD_ST_THROW) == 0u;
   const unsigned int wanted = live ? fs.wantedQuads : 0u;
   if(live)
   {
     const int nLive = fs.nLive;
-    const int gSlot = (nLive > 0 && fs.accActive[kGroundAcc]) ? nLive - 1 : -1;       /* the ground is the last live slot */
+    const int gSlot = (nLive > 0 && fs.accActive[kGroundAcc]) ? nLive - 1 : -1;
     if(tid < kMaxBins)
     {
       const unsigned char s = fs.lutLive[tid];
@@ -3731,7 +3832,6 @@ SSD_ENTRY(__launch_bounds__(kThreads), k_labels, labels_block)(const float *__re
     }
     if(tid <= kMaxLive)
     {
-      /* slot order = accumulator order (treads ascending, the ground last); the result has the ground first */
       int lab = 0;
       if(tid < nLive)
         lab = tid == gSlot ? 1 : tid + 1 + (gSlot >= 0 ? 1 : 0);
@@ -3744,7 +3844,6 @@ SSD_ENTRY(__launch_bounds__(kThreads), k_labels, labels_block)(const float *__re
     stage_quad_edges(L.edges, fs.edgeLive, egWords, Q.dE0);
     if(tid == 0)
     {
-      /* k1_consts_fill(L.kc, P, nullptr) spelt out: through the helper this kernel takes 92 scalar registers for 71 */
       K1Consts &c = L.kc;
       for(int i = 0; i < 9; i++)
         c.a[i] = P.a[i];
@@ -3757,25 +3856,18 @@ SSD_ENTRY(__launch_bounds__(kThreads), k_labels, labels_block)(const float *__re
   }
   __syncthreads();
 
-  const float *base = SRC == kSrcDepth16
-    ? reinterpret_cast<const float *>(reinterpret_cast<const unsigned short *>(xyz) + static_cast<size_t>(frame) * strideFloats)
-    : xyz + static_cast<size_t>(frame) * strideFloats;
+  const Chunk c = chunk_of<SRC>(xyz, strideFloats, tileMasks, tileMaskStride, chunkPoints, P.nPoints);
   unsigned char *row = labels + static_cast<size_t>(frame) * labelStride;
-  const int begin = blockIdx.y * chunkPoints;
-  const int end = min(begin + chunkPoints, P.nPoints);
-  const int cell0 = begin / kCell;
-  const int nCells = (end - begin + kCell - 1) / kCell;
-  const uint2 *cells = tileMasks + static_cast<size_t>(frame) * tileMaskStride + cell0;
 
   /* the cells that hold no bin of a live quadrilateral: zeros, without a look at their points (16 bytes a lane where the row allows) */
   const bool aligned16 = (reinterpret_cast<uintptr_t>(row) & 15u) == 0;
   constexpr int kUnits = kCell / 16;
-  for(int u = tid; u < nCells * kUnits; u += kThreads)
+  for(int u = tid; u < c.nCells * kUnits; u += kThreads)
   {
-    const int c = u / kUnits;
-    if((cells[c].x & wanted) != 0u)
+    const int cell = u / kUnits;
+    if((c.cells[cell].x & wanted) != 0u)
       continue;
-    const int idx = (cell0 + c) * kCell + 16 * (u - c * kUnits);
+    const int idx = (c.cell0 + cell) * kCell + 16 * (u - cell * kUnits);
     if(aligned16 && idx + 16 <= P.nPoints)
       *reinterpret_cast<uint4 *>(row + idx) = make_uint4(0u, 0u, 0u, 0u);
     else
@@ -3786,30 +3878,20 @@ SSD_ENTRY(__launch_bounds__(kThreads), k_labels, labels_block)(const float *__re
     return;
 
   /* the others, in order (one column of cells: the list is the chunk's cells ascending), four cells per wave iteration */
-  const int count = cell_list_build(cells, nCells, 1, [&](const uint2 info) { return (info.x & wanted) != 0u; }, L.cellList, L.listScratch);
+  const CellWalk w = wanted_cells(c, 1, wanted, L.cellList, L.listScratch);
   const bool aligned4 = (reinterpret_cast<uintptr_t>(row) & 3u) == 0;
   const PreLane lc(Q);
-  const int nGroups = (count + 3) >> 2;
-  const int gEnd = ((tid >> 6) + 1) * nGroups / kWavesPerBlock;
-  for(int g = (tid >> 6) * nGroups / kWavesPerBlock; g < gEnd; g++)
+  for(int g = w.g; g < w.gEnd; g++)
   {
     const int entry = 4 * g + (lane >> 4);
     F3 v[kPts];
-    load_cell<SRC>(base, cell0, L.cellList, entry, count, lane, P.nPoints, v, D);
+    load_cell<SRC>(c.base, c.cell0, L.cellList, entry, w.count, lane, P.nPoints, v, D);
     unsigned int word = 0u;
 #pragma unroll
     for(int j = 0; j < kPts; j++)
-    {
-      f32x2 d;
-      float M, M3;
-      unsigned int q;
-      unsigned long long mSlow, mIn, mGround;
-      quad_decide<CHECKS, true>(v[j], Q, lc, L.edges, L.lut, L.qts, L.kc, -1, d, M, M3, q, mSlow, mIn, mGround);
-      const unsigned int lab = __builtin_amdgcn_inverse_ballot_w64(mIn) ? L.label[min(q, static_cast<unsigned int>(kMaxLive))] : 0u;
-      word |= lab << (8 * j);
-    }
-    if(entry < count)
-      store_labels4(row, aligned4, (cell0 + static_cast<int>(L.cellList[entry])) * kCell + kPts * (lane & 15), P.nPoints, word);
+      word |= label_of<CHECKS>(v[j], Q, lc, L) << (8 * j);
+    if(entry < w.count)
+      store_labels4(row, aligned4, (c.cell0 + static_cast<int>(L.cellList[entry])) * kCell + kPts * (lane & 15), P.nPoints, word);
   }
 }
 
@@ -3836,166 +3918,174 @@ struct SurfaceLds
   unsigned long long sums[SSD_MAX_STEPS][kSurfaceSums];
 };
 
-/* the wave's sums of surface `surface` into the block's table */
-__device__ __forceinline__ void surface_flush(long long (&acc)[kSurfaceSums], unsigned long long (*sums)[kSurfaceSums], int surface, int lane)
+/* Integer sums keyed by a wave-uniform current key (a surface, a riser), for k_surface_moments, k_surface_refit and k_riser_moments: N
+ * sums per key, the first kGroundSums those of ssd_ground_moments, then n_far; what lies behind is the caller's.  A lane's key is
+ * 0 .. or -1 for a point that counts nowhere. */
+template<int N>
+struct KeyedSums
 {
-#pragma unroll
-  for(int i = 0; i < kSurfaceSums; i++)
+  long long acc[N] = {};
+  int cur = -1;                                  /* the key whose sums the wave's registers hold (-1: none yet) */
+
+  /* the wave's sums into the block's table: shuffles, then lane 0's 64-bit LDS adds */
+  __device__ __forceinline__ void flush(unsigned long long (*table)[N], int lane)
   {
+    if(cur < 0)
+      return;
 #pragma unroll
-    for(int o = 32; o >= 1; o >>= 1)
-      acc[i] += __shfl_xor(acc[i], o);
+    for(int i = 0; i < N; i++)
+    {
+#pragma unroll
+      for(int o = 32; o >= 1; o >>= 1)
+        acc[i] += __shfl_xor(acc[i], o);
+    }
+    if(lane == 0)
+    {
+#pragma unroll
+      for(int i = 0; i < N; i++)
+        if(acc[i] != 0)
+          atomicAdd(&table[cur][i], static_cast<unsigned long long>(acc[i]));
+    }
+#pragma unroll
+    for(int i = 0; i < N; i++)
+      acc[i] = 0;
   }
-  if(lane == 0)
+
+  /* a point slot some of whose lanes hold a key (mKeyed, not 0): when none of them holds the current one, the wave changes over */
+  __device__ __forceinline__ void changeover(int key, unsigned long long mKeyed, unsigned long long (*table)[N], int lane)
   {
-#pragma unroll
-    for(int i = 0; i < kSurfaceSums; i++)
-      if(acc[i] != 0)
-        atomicAdd(&sums[surface][i], static_cast<unsigned long long>(acc[i]));
+    if(cur < 0 || __ballot(key == cur) == 0ull)
+    {
+      flush(table, lane);
+      cur = __builtin_amdgcn_readlane(key, __ffsll(static_cast<long long>(mKeyed)) - 1);
+    }
   }
+
+  /* the lane's point by the fixed-point rule (ssd_moments.h) on the float camera coordinates: to the wave's sums under the current key,
+   * straight to the table under another (a cell two keys share: rare), nowhere for key < 0 */
+  __device__ __forceinline__ void add(int key, const F3 &p, unsigned long long (*table)[N])
+  {
+    const double rx = moment_round(static_cast<double>(p.x)), ry = moment_round(static_cast<double>(p.y)), rz = moment_round(static_cast<double>(p.z));
+    const bool fits = moment_near(rx) && moment_near(ry) && moment_near(rz);
+    if(key == cur)
+    {
+      if(fits)
+        moment_add(rx, ry, rz, acc);
+      else
+        acc[kGroundSums] += 1;
+    }
+    else if(key >= 0)
+    {
+      unsigned long long *t = table[key];
+      if(fits)
+      {
+        long long one[kGroundSums] = {};
+        moment_add(rx, ry, rz, one);
 #pragma unroll
-  for(int i = 0; i < kSurfaceSums; i++)
-    acc[i] = 0;
+        for(int i = 0; i < kGroundSums; i++)
+          atomicAdd(&t[i], static_cast<unsigned long long>(one[i]));
+      }
+      else
+        atomicAdd(&t[kGroundSums], 1ull);
+    }
+  }
+};
+
+/* the block's end, behind a barrier: a thread per entry of the table, give(key, i, sum) for every one that is not 0 */
+template<int N, typename Give>
+__device__ __forceinline__ void keyed_sums_give(const unsigned long long (*table)[N], int nKeys, Give give)
+{
+  const int tid = threadIdx.x;
+  if(tid < nKeys * N)
+  {
+    const int key = tid / N, i = tid - key * N;
+    const unsigned long long t = table[key][i];
+    if(t != 0ull)
+      give(key, i, t);
+  }
 }
 
-template<int SRC, bool CHECKS>
-SSD_ENTRY(__launch_bounds__(kThreads), k_surface_moments, surface_moments_block)(const float *__restrict__ xyz, size_t strideFloats, SSD_BYVAL(PointParams) P, SSD_BYVAL(PreXY) Q,
-                                                              const FrameState *__restrict__ st, const uint2 *__restrict__ tileMasks,
-                                                              size_t tileMaskStride, int chunkPoints, SSD_BYVAL(DepthSrc) D,
-                                                              ssd_frame_moments *__restrict__ out)
+/* The body of k_surface_moments and, GATED, of k_surface_refit (ssd_kernels_refit.hip), for one calibration and for
+ * camera batches alike.  GATED: `gates` is the batch's, G the block's copy of the frame's in LDS, and on the lane's own label the gate
+ * test of ssd_refit.h - a labelled point outside its surface's gate becomes an unlabelled one BEHIND the wave-uniform skip of the slots
+ * that label nothing, so the three double products are spent only where some lane has a label; a point trimmed so is counted nowhere. */
+template<int SRC, bool CHECKS, bool GATED>
+__device__ __forceinline__ void labelled_moments_block(SurfaceLds &S, ssd_frame_gates *G, const float *__restrict__ xyz, size_t strideFloats,
+                                                       const PointParams &P, const PreXY &Q, const FrameState *__restrict__ st,
+                                                       const uint2 *__restrict__ tileMasks, size_t tileMaskStride, int chunkPoints, const DepthSrc &D,
+                                                       const ssd_frame_gates *__restrict__ gates, ssd_frame_moments *__restrict__ out)
 {
-  __shared__ SurfaceLds S;
   LabelsLds &L = S.l;
   const int tid = threadIdx.x, lane = tid & 63;
   const int frame = blockIdx.x;
-  /* the frame's state into LDS exactly as k_labels takes it (spelt out again, not shared through a helper: moved into one, k_labels'
-   * own code changes - 71 scalar registers become 95) */
-  const FrameState &fs = st[frame];
-  /* nothing of a frame k_quads found no live quadrilateral in, or whose quadrilaterals the reference would have thrown on, is labelled */
-  const bool live = fs.anyActive != 0u && (fs.status & SSD_ST_THROW) == 0u;           /* block-uniform */
-  const unsigned int wanted = live ? fs.wantedQuads : 0u;
-  if(live)
+  const LiveFrame f = labels_stage(L, st[frame], P, Q);
+  if(f.live)
   {
-    const int nLive = fs.nLive;
-    const int gSlot = (nLive > 0 && fs.accActive[kGroundAcc]) ? nLive - 1 : -1;       /* the ground is the last live slot */
-    if(tid < kMaxBins)
+    if constexpr(GATED)
     {
-      const unsigned char s = fs.lutLive[tid];
-      L.lut[tid] = s == 0xff ? static_cast<unsigned char>(kMaxLive) : s;
+      /* the frame's gates: 86 words, once per block */
+      static_assert(sizeof(ssd_frame_gates) % 8 == 0 && sizeof(ssd_frame_gates) / 8 <= kThreads, "one thread per 64-bit word of the frame's gates");
+      if(tid < static_cast<int>(sizeof(ssd_frame_gates) / 8))
+        reinterpret_cast<unsigned long long *>(G)[tid] = reinterpret_cast<const unsigned long long *>(gates + frame)[tid];
     }
-    if(tid <= kMaxLive)
+    /* the record's header, by the frame's first block: the surfaces labels can name, and whether the first is the ground */
+    if(tid == 0 && blockIdx.y == 0)
     {
-      /* slot order = accumulator order (treads ascending, the ground last); the result has the ground first */
-      int lab = 0;
-      if(tid < nLive)
-        lab = tid == gSlot ? 1 : tid + 1 + (gSlot >= 0 ? 1 : 0);
-      L.label[tid] = static_cast<unsigned char>(lab <= SSD_MAX_STEPS ? lab : 0);
-    }
-    constexpr int qtWords = kMaxLive * static_cast<int>(sizeof(QuadTest) / 4);
-    constexpr int egWords = kMaxLive * static_cast<int>(sizeof(QuadEdgesF) / 4);
-    for(int w = tid; w < qtWords; w += kThreads)
-      reinterpret_cast<unsigned int *>(L.qts)[w] = reinterpret_cast<const unsigned int *>(fs.qtLive)[w];
-    stage_quad_edges(L.edges, fs.edgeLive, egWords, Q.dE0);
-    if(tid == 0)
-    {
-      /* k1_consts_fill(L.kc, P, nullptr) spelt out: through the helper this kernel takes 92 scalar registers for 71 */
-      K1Consts &c = L.kc;
-      for(int i = 0; i < 9; i++)
-        c.a[i] = P.a[i];
-      c.b[0] = P.b[0]; c.b[1] = P.b[1]; c.b[2] = P.b[2];
-      c.xMin = P.xMin; c.xMax = P.xMax; c.yMin = P.yMin; c.yMax = P.yMax; c.zMin = P.zMin; c.zMax = P.zMax;
-      c.boxX = P.boxX; c.boxY = P.boxY;
-      c.recip = P.recip;
-      c.xToImage = 0.0; c.yToImage = 0.0;
-      /* the record's header, by the frame's first block: the surfaces labels can name, and whether the first is the ground */
-      if(blockIdx.y == 0)
-      {
-        out[frame].n_surfaces = min(nLive, SSD_MAX_STEPS);
-        out[frame].ground = gSlot >= 0 ? 1 : 0;
-      }
+      out[frame].n_surfaces = min(f.nLive, SSD_MAX_STEPS);
+      out[frame].ground = f.gSlot >= 0 ? 1 : 0;
     }
   }
   if(tid < SSD_MAX_STEPS * kSurfaceSums)
     (&S.sums[0][0])[tid] = 0ull;
   __syncthreads();
-  if(wanted == 0u)
+  if(f.wanted == 0u)
     return;
 
-  const float *base = SRC == kSrcDepth16
-    ? reinterpret_cast<const float *>(reinterpret_cast<const unsigned short *>(xyz) + static_cast<size_t>(frame) * strideFloats)
-    : xyz + static_cast<size_t>(frame) * strideFloats;
-  const int begin = blockIdx.y * chunkPoints;
-  const int end = min(begin + chunkPoints, P.nPoints);
-  const int cell0 = begin / kCell;
-  const int nCells = (end - begin + kCell - 1) / kCell;
-  const uint2 *cells = tileMasks + static_cast<size_t>(frame) * tileMaskStride + cell0;
-
-  const int count = cell_list_build(cells, nCells, 1, [&](const uint2 info) { return (info.x & wanted) != 0u; }, L.cellList, L.listScratch);
+  const Chunk c = chunk_of<SRC>(xyz, strideFloats, tileMasks, tileMaskStride, chunkPoints, P.nPoints);
+  const CellWalk w = wanted_cells(c, 1, f.wanted, L.cellList, L.listScratch);
   const PreLane lc(Q);
-  const int nGroups = (count + 3) >> 2;
-  const int gEnd = ((tid >> 6) + 1) * nGroups / kWavesPerBlock;
-  long long acc[kSurfaceSums] = {};
-  int cur = 0;                                   /* the label whose sums the wave's registers hold (0: none yet) */
-  for(int g = (tid >> 6) * nGroups / kWavesPerBlock; g < gEnd; g++)
+  KeyedSums<kSurfaceSums> sums;                  /* keyed by the surface: the label - 1 */
+  for(int g = w.g; g < w.gEnd; g++)
   {
     const int entry = 4 * g + (lane >> 4);
     F3 v[kPts];
-    load_cell<SRC>(base, cell0, L.cellList, entry, count, lane, P.nPoints, v, D);
+    load_cell<SRC>(c.base, c.cell0, L.cellList, entry, w.count, lane, P.nPoints, v, D);
 #pragma unroll
     for(int j = 0; j < kPts; j++)
     {
-      f32x2 d;
-      float M, M3;
-      unsigned int q;
-      unsigned long long mSlow, mIn, mGround;
-      quad_decide<CHECKS, true>(v[j], Q, lc, L.edges, L.lut, L.qts, L.kc, -1, d, M, M3, q, mSlow, mIn, mGround);
-      const int lab = (__builtin_amdgcn_inverse_ballot_w64(mIn) && entry < count) ? L.label[min(q, static_cast<unsigned int>(kMaxLive))] : 0;
-      const unsigned long long mLab = __ballot(lab != 0);
-      if(mLab == 0ull)                           /* wave-uniform: a slot none of whose points counts */
+      const unsigned int lab = label_of<CHECKS>(v[j], Q, lc, L);
+      int k = entry < w.count ? static_cast<int>(lab) - 1 : -1;
+      if(__ballot(k >= 0) == 0ull)               /* wave-uniform: a slot none of whose points is labelled */
         continue;
-      if(cur == 0 || __ballot(lab == cur) == 0ull)
-      {
-        if(cur != 0)
-          surface_flush(acc, S.sums, cur - 1, lane);
-        cur = __builtin_amdgcn_readlane(lab, __ffsll(static_cast<long long>(mLab)) - 1);
-      }
-      /* the fixed-point rule (ssd_moments.h) on the float camera coordinates */
-      const double rx = moment_round(static_cast<double>(v[j].x)), ry = moment_round(static_cast<double>(v[j].y)), rz = moment_round(static_cast<double>(v[j].z));
-      const bool fits = moment_near(rx) && moment_near(ry) && moment_near(rz);
-      if(lab == cur)
-      {
-        if(fits)
-          moment_add(rx, ry, rz, acc);
-        else
-          acc[kGroundSums] += 1;
-      }
-      else if(lab != 0)
-      {
-        /* another surface than the wave's current one in the same slot (a cell two surfaces share): rare, straight to the table */
-        unsigned long long *t = S.sums[lab - 1];
-        if(fits)
-        {
-          long long one[kGroundSums] = {};
-          moment_add(rx, ry, rz, one);
-#pragma unroll
-          for(int i = 0; i < kGroundSums; i++)
-            atomicAdd(&t[i], static_cast<unsigned long long>(one[i]));
-        }
-        else
-          atomicAdd(&t[kGroundSums], 1ull);
-      }
+      if constexpr(GATED)
+        k = (k >= 0 && refit_keeps(*G, k, v[j].x, v[j].y, v[j].z)) ? k : -1;
+      const unsigned long long mKeyed = __ballot(k >= 0);
+      if(mKeyed == 0ull)                         /* wave-uniform: every labelled point of the slot was trimmed */
+        continue;
+      sums.changeover(k, mKeyed, S.sums, lane);
+      sums.add(k, v[j], S.sums);
     }
   }
-  if(cur != 0)
-    surface_flush(acc, S.sums, cur - 1, lane);
+  sums.flush(S.sums, lane);
   __syncthreads();
-  if(tid < SSD_MAX_STEPS * kSurfaceSums)
+  /* one 64-bit atomicAdd per non-zero entry to the frame's record, which the caller zeroed on the stream */
+  keyed_sums_give<kSurfaceSums>(S.sums, SSD_MAX_STEPS, [&](int k, int i, unsigned long long t)
   {
-    const unsigned long long t = (&S.sums[0][0])[tid];
-    if(t != 0ull)
-      atomicAdd(reinterpret_cast<unsigned long long *>(out + frame) + 1 + tid, t);
-  }
+    atomicAdd(reinterpret_cast<unsigned long long *>(out + frame) + 1 + k * kSurfaceSums + i, t);
+  });
 }
+
+#ifndef SSD_CAMERAS_TU
+template<int SRC, bool CHECKS>
+__global__ __launch_bounds__(kThreads) void k_surface_moments(const float *__restrict__ xyz, size_t strideFloats, PointParams P, PreXY Q,
+                                                              const FrameState *__restrict__ st, const uint2 *__restrict__ tileMasks,
+                                                              size_t tileMaskStride, int chunkPoints, DepthSrc D,
+                                                              ssd_frame_moments *__restrict__ out)
+{
+  __shared__ SurfaceLds S;
+  labelled_moments_block<SRC, CHECKS, false>(S, nullptr, xyz, strideFloats, P, Q, st, tileMasks, tileMaskStride, chunkPoints, D, nullptr, out);
+}
+#endif /* SSD_CAMERAS_TU */
 
 /* ========================================================================= */
 /* K5: ground front edge and the per-frame result — one workgroup per frame     */
@@ -4399,43 +4489,85 @@ SSD_ENTRY(__launch_bounds__(T), k_final, final_block)(SSD_BYVAL(Params) P, Frame
 /* ========================================================================= */
 /* K6 (extension): evidence of the vertical faces                              */
 
+/* What the three riser passes share: the block's copy of the frame's riser state with the cell list, the way into the walk, and the
+ * evidence rule.  Each kernel's own table lies beside or behind the record. */
+struct RiserLds
+{
+  unsigned short cellList[kMaxCellsPerBlock];
+  unsigned int listScratch[2 * kWavesPerBlock];
+  RiserState rs[kMaxRisers];
+  signed char riserOfBin[kMaxBins];
+};
+
+/* false for a frame without risers (block-uniform: wantedRisers is set by k_final); else the frame's riser state in L, behind a barrier
+ * (what the caller zeroed in front of the call is zero behind it), and the chunk's cells that hold a bin of a riser, which alone are
+ * walked (as k_raster / k_inquad).  fs.nRisers is k_final's count of emitted surfaces less one: at most kMaxRisers. */
+template<int SRC>
+__device__ __forceinline__ bool riser_walk(RiserLds &L, const FrameState &fs, const float *__restrict__ xyz, size_t strideFloats, int nPoints,
+                                           const uint2 *__restrict__ tileMasks, size_t tileMaskStride, int chunkPoints, int cellCols, Chunk &c, CellWalk &w)
+{
+  const int tid = threadIdx.x;
+  const unsigned int wanted = fs.wantedRisers;
+  if(wanted == 0u)
+    return false;
+  if(tid < kMaxBins)
+    L.riserOfBin[tid] = fs.riserOfBin[tid];
+  if(tid < fs.nRisers)
+    L.rs[tid] = fs.riser[tid];
+  __syncthreads();
+  c = chunk_of<SRC>(xyz, strideFloats, tileMasks, tileMaskStride, chunkPoints, nPoints);
+  w = wanted_cells(c, cellCols, wanted, L.cellList, L.listScratch);
+  return true;
+}
+
+/* The evidence rule: then(r, sd) for a point that is evidence of riser r, sd its signed distance from the riser's edge line; nothing
+ * for any other point.  The point's height lies in a bin of the riser (a bin of no plateau between the two surfaces) and strictly inside
+ * its band, the point within tol of the edge line and along the edge.  (load_points gives a point beyond nPoints z = 0, and world_z
+ * drops it: an evidence point lies inside the frame.)  The caller's continuation and not a returned index: returned, the 16-bit depth
+ * k_risers spills 42 scalar registers to lanes for 27 and runs a third longer (profiles/extension_kernels_shared.txt). */
+template<typename Then>
+__device__ __forceinline__ void riser_evidence(const PointParams &P, const F3 &p, const RiserLds &L, double tol, Then then)
+{
+  double wx, wy, wz;
+  if(!world_z(P, p, wz))
+    return;
+  const int r = L.riserOfBin[height_bin(P, wz)];
+  if(r < 0)
+    return;
+  const RiserState &R = L.rs[r];
+  if(!(wz > R.zLo && wz < R.zHi))
+    return;
+  if(!world_xy(P, p, wx, wy))
+    return;
+  const double a = wx - R.ox, b = wy - R.oy;
+  const double sd = b * R.ux - a * R.uy;                 /* signed distance from the edge line */
+  const double t = a * R.ux + b * R.uy;                  /* position along the edge */
+  if(fabs(sd) <= tol && t >= 0.0 && t <= R.len)
+    then(r, sd);
+}
+
 template<int SRC>
 SSD_ENTRY(__launch_bounds__(kThreads, 8), k_risers, risers_block)(const float *__restrict__ xyz, size_t strideFloats, SSD_BYVAL(PointParams) P, double tol,
                                                         FrameState *__restrict__ st, const uint2 *__restrict__ tileMasks,
                                                         size_t tileMaskStride, int chunkPoints, int cellCols, SSD_BYVAL(DepthSrc) D)
 {
-  __shared__ unsigned short cellList[kMaxCellsPerBlock];
-  __shared__ unsigned int listScratch[2 * kWavesPerBlock];
-  __shared__ RiserState rs[kMaxRisers];
-  __shared__ signed char riserOfBin[kMaxBins];
+  __shared__ RiserLds L;
   __shared__ unsigned long long lsum[kMaxRisers][8];
   __shared__ unsigned int lcnt[kMaxRisers][8];
 
   const int tid = threadIdx.x, lane = tid & 63;
-  const int frame = blockIdx.x;
-  FrameState &fs = st[frame];
-  const unsigned int wanted = fs.wantedRisers;
-  if(wanted == 0u)                                          /* block-uniform: set by k_final */
-    return;
-  const int nR = fs.nRisers;
-  if(tid < kMaxBins)
-    riserOfBin[tid] = fs.riserOfBin[tid];
-  if(tid < nR)
-    rs[tid] = fs.riser[tid];
+  FrameState &fs = st[blockIdx.x];
   for(int i = tid; i < kMaxRisers * 8; i += kThreads)
   {
     (&lsum[0][0])[i] = 0ull;
     (&lcnt[0][0])[i] = 0u;
   }
-  __syncthreads();
+  Chunk c;
+  CellWalk w;
+  if(!riser_walk<SRC>(L, fs, xyz, strideFloats, P.nPoints, tileMasks, tileMaskStride, chunkPoints, cellCols, c, w))
+    return;
 
-  const float *base = SRC == kSrcDepth16
-    ? reinterpret_cast<const float *>(reinterpret_cast<const unsigned short *>(xyz) + static_cast<size_t>(frame) * strideFloats)
-    : xyz + static_cast<size_t>(frame) * strideFloats;
-  const int begin = blockIdx.y * chunkPoints;
-  const int end = min(begin + chunkPoints, P.nPoints);
   const int copy = lane & 7;
-
   int curR = -1;
   long long accS = 0;
   unsigned int accN = 0;
@@ -4447,75 +4579,51 @@ SSD_ENTRY(__launch_bounds__(kThreads, 8), k_risers, risers_block)(const float *_
       atomicAdd(&lcnt[curR][copy], accN);
     }
   };
-
-  /* only the cells that hold a bin of a riser are walked (as k_raster / k_inquad) */
-  const int cell0 = begin / kCell;
-  const int nCells = (end - begin + kCell - 1) / kCell;
-  const int count = cell_list_build(tileMasks + static_cast<size_t>(frame) * tileMaskStride + cell0, nCells, cellCols,
-                                    [&](const uint2 info) { return (info.x & wanted) != 0u; }, cellList, listScratch);
-  const int nGroups = (count + 3) >> 2;
-  const int gEnd = ((tid >> 6) + 1) * nGroups / kWavesPerBlock;
-  for(int g = (tid >> 6) * nGroups / kWavesPerBlock; g < gEnd; g++)
+  for(int g = w.g; g < w.gEnd; g++)
   {
     F3 v[kPts];
-    load_cell<SRC>(base, cell0, cellList, 4 * g + (lane >> 4), count, lane, P.nPoints, v, D);
+    load_cell<SRC>(c.base, c.cell0, L.cellList, 4 * g + (lane >> 4), w.count, lane, P.nPoints, v, D);
     #pragma unroll
     for(int j = 0; j < kPts; j++)
     {
-      double wx, wy, wz;
-      if(!world_z(P, v[j], wz))
-        continue;
-      const int r = riserOfBin[height_bin(P, wz)];
-      if(r < 0)
-        continue;
-      const RiserState &R = rs[r];
-      if(!(wz > R.zLo && wz < R.zHi))
-        continue;
-      if(!world_xy(P, v[j], wx, wy))
-        continue;
-      const double a = wx - R.ox, b = wy - R.oy;
-      const double sd = b * R.ux - a * R.uy;                 /* signed distance from the edge line */
-      const double t = a * R.ux + b * R.uy;                  /* position along the edge */
-      if(!(fabs(sd) <= tol && t >= 0.0 && t <= R.len))
-        continue;
-      if(r != curR)
+      riser_evidence(P, v[j], L, tol, [&](int r, double sd)
       {
-        flushAcc();
-        curR = r; accS = 0; accN = 0;
-      }
-      accS += z_to_fixed(sd);
-      accN++;
+        if(r != curR)
+        {
+          flushAcc();
+          curR = r; accS = 0; accN = 0;
+        }
+        accS += z_to_fixed(sd);
+        accN++;
+      });
     }
   }
   flushAcc();
   __syncthreads();
-  if(tid < nR)
+  if(tid < fs.nRisers)
   {
     unsigned long long sum = 0;
-    unsigned int c = 0;
+    unsigned int n = 0;
     for(int k = 0; k < 8; k++)
     {
       sum += lsum[tid][k];
-      c += lcnt[tid][k];
+      n += lcnt[tid][k];
     }
-    if(c)
+    if(n)
     {
       atomicAdd(reinterpret_cast<unsigned long long *>(&fs.rSum[tid]), sum);
-      atomicAdd(&fs.rCnt[tid], c);
+      atomicAdd(&fs.rCnt[tid], n);
     }
   }
 }
 
-/* k_risers' sibling (the riser fit): the same cells, the same evidence rule in the same arithmetic, walked ONCE,
- * and beside the count and the offset sum of every riser the ten integer sums of ssd_ground_moments (ssd_moments.h) over its evidence
+/* k_risers' sibling (the riser fit): the same walk (riser_walk) and the same evidence rule (riser_evidence), walked
+ * ONCE, and beside the count and the offset sum of every riser the ten integer sums of ssd_ground_moments (ssd_moments.h) over its evidence
  * points plus n_far, the evidence points the fixed-point rule leaves out - riser i's in record s[i] of the frame's ssd_frame_moments.
- * Accumulation is k_surface_moments': a lane keeps the sums of ONE riser in registers, the wave's current one (wave-uniform); when no
- * lane of a point slot holds the current riser and some hold another, the wave's sums go to the block's LDS table (shuffles, then 64-bit
- * LDS adds by lane 0) and the wave changes over; the lanes of a mixed slot that hold another riser than the current one add their point
- * to the table directly.  At the block's end one 64-bit atomicAdd per non-zero entry goes to the frame's record, which the caller zeroed
- * on the stream, and to k_risers' own rSum / rCnt (the count is n + n_far).  Integer addition throughout: no result depends on an
- * order, and rSum / rCnt are what k_risers leaves.  A body of its own rather than a switch in risers_block, so that k_risers' code
- * object stays what it is.  Camera batches: k_riser_moments_cams (ssd_kernels_cams.hip) runs this body with the frame's own constants. */
+ * Accumulation is k_surface_moments' (KeyedSums, keyed by the riser) with one more sum, the offset's.  At the block's end one 64-bit
+ * atomicAdd per non-zero entry goes to the frame's record, which the caller zeroed on the stream, and to k_risers' own rSum / rCnt (the
+ * count is n + n_far).  Integer addition throughout: no result depends on an order, and rSum / rCnt are what k_risers leaves.
+ * Camera batches: k_riser_moments_cams (ssd_kernels_cams.hip) runs this body with the frame's own constants. */
 constexpr int kRiserSums = kSurfaceSums + 1;        /* the eleven int64 of ssd_surface_moments, then the offset sum (2^-40 m) */
 constexpr int kRiserOffsetSum = kSurfaceSums;
 static_assert(kMaxRisers <= SSD_MAX_STEPS, "riser i's sums are record s[i] of an ssd_frame_moments");
@@ -4523,34 +4631,9 @@ static_assert(kMaxRisers * kRiserSums <= kThreads, "one thread per entry of the 
 
 struct RiserMomentsLds
 {
-  unsigned short cellList[kMaxCellsPerBlock];
-  unsigned int listScratch[2 * kWavesPerBlock];
-  RiserState rs[kMaxRisers];
-  signed char riserOfBin[kMaxBins];
+  RiserLds r;
   unsigned long long sums[kMaxRisers][kRiserSums];
 };
-
-/* the wave's sums of riser `riser` into the block's table (surface_flush with one more sum) */
-__device__ __forceinline__ void riser_flush(long long (&acc)[kRiserSums], unsigned long long (*sums)[kRiserSums], int riser, int lane)
-{
-#pragma unroll
-  for(int i = 0; i < kRiserSums; i++)
-  {
-#pragma unroll
-    for(int o = 32; o >= 1; o >>= 1)
-      acc[i] += __shfl_xor(acc[i], o);
-  }
-  if(lane == 0)
-  {
-#pragma unroll
-    for(int i = 0; i < kRiserSums; i++)
-      if(acc[i] != 0)
-        atomicAdd(&sums[riser][i], static_cast<unsigned long long>(acc[i]));
-  }
-#pragma unroll
-  for(int i = 0; i < kRiserSums; i++)
-    acc[i] = 0;
-}
 
 template<int SRC>
 SSD_ENTRY(__launch_bounds__(kThreads), k_riser_moments, riser_moments_block)(const float *__restrict__ xyz, size_t strideFloats, SSD_BYVAL(PointParams) P, double tol,
@@ -4563,134 +4646,64 @@ SSD_ENTRY(__launch_bounds__(kThreads), k_riser_moments, riser_moments_block)(con
   const int tid = threadIdx.x, lane = tid & 63;
   const int frame = blockIdx.x;
   FrameState &fs = st[frame];
-  const int nR = min(fs.nRisers, kMaxRisers);
+  const int nR = fs.nRisers;
   /* the record's header, by the frame's first block (also of a frame none of whose cells holds a riser's bin) */
   if(blockIdx.y == 0 && tid == 0)
   {
     out[frame].n_surfaces = nR;
     out[frame].ground = 0;
   }
-  const unsigned int wanted = fs.wantedRisers;
-  if(wanted == 0u)                                          /* block-uniform: set by k_final */
-    return;
-  if(tid < kMaxBins)
-    S.riserOfBin[tid] = fs.riserOfBin[tid];
-  if(tid < nR)
-    S.rs[tid] = fs.riser[tid];
   if(tid < kMaxRisers * kRiserSums)
     (&S.sums[0][0])[tid] = 0ull;
-  __syncthreads();
+  Chunk c;
+  CellWalk w;
+  if(!riser_walk<SRC>(S.r, fs, xyz, strideFloats, P.nPoints, tileMasks, tileMaskStride, chunkPoints, cellCols, c, w))
+    return;
 
-  const float *base = SRC == kSrcDepth16
-    ? reinterpret_cast<const float *>(reinterpret_cast<const unsigned short *>(xyz) + static_cast<size_t>(frame) * strideFloats)
-    : xyz + static_cast<size_t>(frame) * strideFloats;
-  const int begin = blockIdx.y * chunkPoints;
-  const int end = min(begin + chunkPoints, P.nPoints);
-
-  /* only the cells that hold a bin of a riser are walked (as k_risers) */
-  const int cell0 = begin / kCell;
-  const int nCells = (end - begin + kCell - 1) / kCell;
-  const int count = cell_list_build(tileMasks + static_cast<size_t>(frame) * tileMaskStride + cell0, nCells, cellCols,
-                                    [&](const uint2 info) { return (info.x & wanted) != 0u; }, S.cellList, S.listScratch);
-  const int nGroups = (count + 3) >> 2;
-  const int gEnd = ((tid >> 6) + 1) * nGroups / kWavesPerBlock;
-  long long acc[kRiserSums] = {};
-  int cur = -1;                                  /* the riser whose sums the wave's registers hold (-1: none yet) */
-  for(int g = (tid >> 6) * nGroups / kWavesPerBlock; g < gEnd; g++)
+  KeyedSums<kRiserSums> sums;                    /* keyed by the riser */
+  for(int g = w.g; g < w.gEnd; g++)
   {
     F3 v[kPts];
-    load_cell<SRC>(base, cell0, S.cellList, 4 * g + (lane >> 4), count, lane, P.nPoints, v, D);
+    load_cell<SRC>(c.base, c.cell0, S.r.cellList, 4 * g + (lane >> 4), w.count, lane, P.nPoints, v, D);
 #pragma unroll
     for(int j = 0; j < kPts; j++)
     {
-      /* k_risers' evidence rule, expression for expression; r = the point's riser, -1: no evidence */
-      int r = -1;
+      int r = -1;                                /* the point's riser, -1: no evidence */
       long long sdFix = 0;
-      double wx, wy, wz;
-      if(world_z(P, v[j], wz))
-      {
-        const int rb = S.riserOfBin[height_bin(P, wz)];
-        if(rb >= 0)
-        {
-          const RiserState &R = S.rs[rb];
-          if(wz > R.zLo && wz < R.zHi && world_xy(P, v[j], wx, wy))
-          {
-            const double a = wx - R.ox, b = wy - R.oy;
-            const double sd = b * R.ux - a * R.uy;                 /* signed distance from the edge line */
-            const double t = a * R.ux + b * R.uy;                  /* position along the edge */
-            if(fabs(sd) <= tol && t >= 0.0 && t <= R.len)
-            {
-              r = rb;
-              sdFix = z_to_fixed(sd);
-            }
-          }
-        }
-      }
+      riser_evidence(P, v[j], S.r, tol, [&](int rb, double sd) { r = rb; sdFix = z_to_fixed(sd); });
       const unsigned long long mEv = __ballot(r >= 0);
       if(mEv == 0ull)                            /* wave-uniform: a slot none of whose points is evidence */
         continue;
-      if(cur < 0 || __ballot(r == cur) == 0ull)
-      {
-        if(cur >= 0)
-          riser_flush(acc, S.sums, cur, lane);
-        cur = __builtin_amdgcn_readlane(r, __ffsll(static_cast<long long>(mEv)) - 1);
-      }
-      /* the fixed-point rule (ssd_moments.h) on the float camera coordinates */
-      const double rx = moment_round(static_cast<double>(v[j].x)), ry = moment_round(static_cast<double>(v[j].y)), rz = moment_round(static_cast<double>(v[j].z));
-      const bool fits = moment_near(rx) && moment_near(ry) && moment_near(rz);
-      if(r == cur)
-      {
-        if(fits)
-          moment_add(rx, ry, rz, acc);
-        else
-          acc[kGroundSums] += 1;
-        acc[kRiserOffsetSum] += sdFix;
-      }
+      sums.changeover(r, mEv, S.sums, lane);
+      sums.add(r, v[j], S.sums);
+      /* the offset sum beside the moments */
+      if(r == sums.cur)
+        sums.acc[kRiserOffsetSum] += sdFix;
       else if(r >= 0)
-      {
-        /* another riser than the wave's current one in the same slot (a cell two risers share): rare, straight to the table */
-        unsigned long long *t = S.sums[r];
-        if(fits)
-        {
-          long long one[kGroundSums] = {};
-          moment_add(rx, ry, rz, one);
-#pragma unroll
-          for(int i = 0; i < kGroundSums; i++)
-            atomicAdd(&t[i], static_cast<unsigned long long>(one[i]));
-        }
-        else
-          atomicAdd(&t[kGroundSums], 1ull);
-        atomicAdd(&t[kRiserOffsetSum], static_cast<unsigned long long>(sdFix));
-      }
+        atomicAdd(&S.sums[r][kRiserOffsetSum], static_cast<unsigned long long>(sdFix));
     }
   }
-  if(cur >= 0)
-    riser_flush(acc, S.sums, cur, lane);
+  sums.flush(S.sums, lane);
   __syncthreads();
-  if(tid < kMaxRisers * kRiserSums)
+  /* one 64-bit atomicAdd per non-zero entry to the frame's record, which the caller zeroed on the stream, and to k_risers' own sums */
+  keyed_sums_give<kRiserSums>(S.sums, nR, [&](int r, int i, unsigned long long t)
   {
-    const int r = tid / kRiserSums, i = tid - r * kRiserSums;
-    const unsigned long long t = S.sums[r][i];
-    if(t != 0ull && r < nR)
+    if(i == kRiserOffsetSum)
+      atomicAdd(reinterpret_cast<unsigned long long *>(&fs.rSum[r]), t);
+    else
     {
-      if(i == kRiserOffsetSum)
-        atomicAdd(reinterpret_cast<unsigned long long *>(&fs.rSum[r]), t);
-      else
-      {
-        atomicAdd(reinterpret_cast<unsigned long long *>(out + frame) + 1 + r * kSurfaceSums + i, t);
-        if(i == 0 || i == kGroundSums)             /* every evidence point is in n or in n_far */
-          atomicAdd(&fs.rCnt[r], static_cast<unsigned int>(t));
-      }
+      atomicAdd(reinterpret_cast<unsigned long long *>(out + frame) + 1 + r * kSurfaceSums + i, t);
+      if(i == 0 || i == kGroundSums)             /* every evidence point is in n or in n_far */
+        atomicAdd(&fs.rCnt[r], static_cast<unsigned int>(t));
     }
-  }
+  });
 }
 
-/* The riser labels (ssd_set_riser_labels): k_risers' cells and k_risers' evidence rule, expression for expression,
+/* The riser labels (ssd_set_riser_labels): k_risers' cells (riser_walk) and k_risers' evidence rule (riser_evidence),
  * and in place of any sum one byte per evidence point, SSD_LABEL_RISER_BASE + r, at the index k_labels gives the point.  It runs behind
  * k_labels on the same stream, which has written every byte of the frame; an evidence point's bin is a bin of no plateau, so its byte
  * is a zero of k_labels' and belongs to this lane alone: single byte stores, nothing read, nothing else rewritten (the neighbouring
- * bytes are other lanes').  No sums, no atomics, no LDS beyond the frame's riser state and the cell list.  A body of its own rather
- * than a switch in risers_block / riser_moments_block, so that their code objects stay what they are.  Camera batches:
+ * bytes are other lanes').  No sums, no atomics, no LDS beyond the frame's riser state and the cell list.  Camera batches:
  * k_riser_labels_cams (ssd_kernels_cams.hip) runs this body with the frame's own constants. */
 static_assert(SSD_LABEL_RISER_BASE > SSD_MAX_STEPS && SSD_LABEL_RISER_BASE + kMaxRisers - 1 <= 0xff, "surface and riser labels share a byte");
 
@@ -4700,68 +4713,31 @@ SSD_ENTRY(__launch_bounds__(kThreads, 8), k_riser_labels, riser_labels_block)(co
                                                         size_t tileMaskStride, int chunkPoints, int cellCols, SSD_BYVAL(DepthSrc) D,
                                                         unsigned char *__restrict__ labels, size_t labelStride)
 {
-  __shared__ unsigned short cellList[kMaxCellsPerBlock];
-  __shared__ unsigned int listScratch[2 * kWavesPerBlock];
-  __shared__ RiserState rs[kMaxRisers];
-  __shared__ signed char riserOfBin[kMaxBins];
+  __shared__ RiserLds L;
 
-  const int tid = threadIdx.x, lane = tid & 63;
+  const int lane = threadIdx.x & 63;
   const int frame = blockIdx.x;
-  const FrameState &fs = st[frame];
-  const unsigned int wanted = fs.wantedRisers;
-  if(wanted == 0u)                                          /* block-uniform: set by k_final */
+  Chunk c;
+  CellWalk w;
+  if(!riser_walk<SRC>(L, st[frame], xyz, strideFloats, P.nPoints, tileMasks, tileMaskStride, chunkPoints, cellCols, c, w))
     return;
-  const int nR = min(fs.nRisers, kMaxRisers);
-  if(tid < kMaxBins)
-    riserOfBin[tid] = fs.riserOfBin[tid];
-  if(tid < nR)
-    rs[tid] = fs.riser[tid];
-  __syncthreads();
-
-  const float *base = SRC == kSrcDepth16
-    ? reinterpret_cast<const float *>(reinterpret_cast<const unsigned short *>(xyz) + static_cast<size_t>(frame) * strideFloats)
-    : xyz + static_cast<size_t>(frame) * strideFloats;
   unsigned char *row = labels + static_cast<size_t>(frame) * labelStride;
-  const int begin = blockIdx.y * chunkPoints;
-  const int end = min(begin + chunkPoints, P.nPoints);
-
-  /* only the cells that hold a bin of a riser are walked (as k_risers) */
-  const int cell0 = begin / kCell;
-  const int nCells = (end - begin + kCell - 1) / kCell;
-  const int count = cell_list_build(tileMasks + static_cast<size_t>(frame) * tileMaskStride + cell0, nCells, cellCols,
-                                    [&](const uint2 info) { return (info.x & wanted) != 0u; }, cellList, listScratch);
-  const int nGroups = (count + 3) >> 2;
-  const int gEnd = ((tid >> 6) + 1) * nGroups / kWavesPerBlock;
-  for(int g = (tid >> 6) * nGroups / kWavesPerBlock; g < gEnd; g++)
+  for(int g = w.g; g < w.gEnd; g++)
   {
     const int entry = 4 * g + (lane >> 4);
     F3 v[kPts];
-    load_cell<SRC>(base, cell0, cellList, entry, count, lane, P.nPoints, v, D);
-    if(entry >= count)                                      /* a row past the end of the list: its points are invalid, its cell is nobody's */
+    load_cell<SRC>(c.base, c.cell0, L.cellList, entry, w.count, lane, P.nPoints, v, D);
+    if(entry >= w.count)                                    /* a row past the end of the list: its points are invalid, its cell is nobody's */
       continue;
-    const int idx = (cell0 + static_cast<int>(cellList[entry])) * kCell + kPts * (lane & 15);
+    const int idx = (c.cell0 + static_cast<int>(L.cellList[entry])) * kCell + kPts * (lane & 15);
     #pragma unroll
     for(int j = 0; j < kPts; j++)
     {
-      double wx, wy, wz;
-      if(!world_z(P, v[j], wz))
-        continue;
-      const int r = riserOfBin[height_bin(P, wz)];
-      if(r < 0)
-        continue;
-      const RiserState &R = rs[r];
-      if(!(wz > R.zLo && wz < R.zHi))
-        continue;
-      if(!world_xy(P, v[j], wx, wy))
-        continue;
-      const double a = wx - R.ox, b = wy - R.oy;
-      const double sd = b * R.ux - a * R.uy;                 /* signed distance from the edge line */
-      const double t = a * R.ux + b * R.uy;                  /* position along the edge */
-      if(!(fabs(sd) <= tol && t >= 0.0 && t <= R.len))
-        continue;
-      /* (load_points gives a point beyond nPoints z = 0, and world_z has dropped it: an evidence point lies inside the frame) */
-      if(SSD_CHK(33, idx + j, P.nPoints))
-        row[idx + j] = static_cast<unsigned char>(SSD_LABEL_RISER_BASE + r);
+      riser_evidence(P, v[j], L, tol, [&](int r, double)
+      {
+        if(SSD_CHK(33, idx + j, P.nPoints))
+          row[idx + j] = static_cast<unsigned char>(SSD_LABEL_RISER_BASE + r);
+      });
     }
   }
 }

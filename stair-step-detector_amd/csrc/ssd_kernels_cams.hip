@@ -160,11 +160,12 @@ __global__ __launch_bounds__(kThreads) void k_surface_moments_cams(const float *
                                                                    const int *__restrict__ camOf, const FrameState *__restrict__ st, const uint2 *__restrict__ tileMasks,
                                                                    size_t tileMaskStride, int chunkPoints, ssd_frame_moments *__restrict__ out)
 {
+  __shared__ SurfaceLds S;
   const CameraRec &C = camera_of(cams, camOf, blockIdx.x);
   const PointParams P = C.P.pt;
   const PreXY Q = C.P.pre;
   const DepthSrc D = C.D;
-  surface_moments_block<SRC, CHECKS>(xyz, strideFloats, P, Q, st, tileMasks, tileMaskStride, chunkPoints, D, out);
+  labelled_moments_block<SRC, CHECKS, false>(S, nullptr, xyz, strideFloats, P, Q, st, tileMasks, tileMaskStride, chunkPoints, D, nullptr, out);
 }
 
 template<int SRC>

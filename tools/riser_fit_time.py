@@ -47,7 +47,7 @@ def main():
         (det.enqueue_depth if inp == "depth16" else det.enqueue)(bufs[inp].ptr, F)
         res = [bytes(r) for r in det.fetch_list(F)]
         ris = [bytes(r) for r in det.fetch_risers(F)] if setting != "off" else None
-        return float(det.stage_times_ms(0)[6]), res, ris
+        return float(det.stage_times_ms(0)["final"]), res, ris
 
     lines = ["# tools/riser_fit_time.py %d: one XGA x %d batch resident in device memory, one workspace, tolerance 0.03 m; device time of the last"
              % (rounds, F), "# stage (k_final + the riser pass) per setting, ms; inputs and settings alternated"]

@@ -14,6 +14,13 @@ tools/cameras_kernel_resources.py does) and compares, translation unit by transl
 By symbol and not by the files' bytes, because the compiler emits kernels in the order in which the HOST code first names them: a
 launcher that is only rearranged moves them around in the code object and leaves every one of them as it was.
 Prints a line per translation unit and a verdict; exit status 0 only for "identical".
+
+    python tools/same_kernels.py PARENT/libssd_hip.so THIS/libssd_hip.so --may-differ 'k_(labels|risers)' > profiles/extension_kernels_same_kernels.txt
+
+--may-differ REGEX: for a change that rewrites SOME kernels.  A symbol whose demangled name (without "void ssd::" and the argument list)
+the pattern matches may differ; for each that does, the two resource rows are printed in the form of tools/riser_labels_kernel_resources.py
+(VGPR, AGPR, SGPR, LDS, scratch, waves per SIMD, code size), and it still counts as DIFFERENT if it has scratch, other LDS bytes than in A
+or fewer waves per SIMD than in A.  Exit status 0 only if every other symbol is identical and the symbol sets are equal.
 """
 import os
 import re
@@ -21,6 +28,9 @@ import shutil
 import subprocess
 import sys
 import tempfile
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import cameras_kernel_resources as ckr  # noqa: E402
 
 LLVM = os.environ.get("ROCM_LLVM", "/opt/rocm/lib/llvm/bin")
 ARCH = "gfx950"
@@ -110,8 +120,27 @@ def label(unit):
     return "%3d kernels, %3d symbols (%s ...)" % (len(unit[1]), len(unit[0]), re.sub(r"\(.*$", "", re.sub(r"^void ", "", d))[:48])
 
 
-def compare(a, b):
-    """-> (lines, symbols that differ, whether the sets of symbols differ)"""
+def resources(record, instructions):
+    """a kernel's record for ckr.row out of its metadata lines, and '.code_bytes' out of its instructions' encodings"""
+    k = {f: 0 for f in ckr.FIELDS}
+    for line in record or []:
+        m = re.match(r"^(?:  - |    )(\.[a-z_]+):\s*(\d+)\s*$", line)
+        if m and m.group(1) in k:
+            k[m.group(1)] = int(m.group(2))
+    k[".code_bytes"] = 4 * sum(len(re.findall(r"\b[0-9A-Fa-f]{8}\b", line.split("//")[-1])) for line in instructions)
+    return k
+
+
+def row(k):
+    return "%s code%-6d" % (ckr.row(k), k[".code_bytes"])
+
+
+def waves(k):
+    return int(ckr.occupancy(k).split("w/SIMD")[0])
+
+
+def compare(a, b, may_differ=None):
+    """-> (lines, symbols that differ and may not, whether the sets of symbols differ); may_differ: a compiled pattern (see above)"""
     lines, differ, sets = [], 0, False
     if len(a) != len(b):
         sa, sb = set().union(*[set(u[0]) for u in a] or [set()]), set().union(*[set(u[0]) for u in b] or [set()])
@@ -122,22 +151,39 @@ def compare(a, b):
         only_a, only_b = sorted(set(ua[0]) - set(ub[0])), sorted(set(ub[0]) - set(ua[0]))
         only_a += [k for k in sorted(set(ua[1]) - set(ub[1])) if k not in only_a]
         only_b += [k for k in sorted(set(ub[1]) - set(ua[1])) if k not in only_b]
-        bad = []
+        bad, allowed = [], []
         for s in sorted(set(ua[0]) & set(ub[0])):
             what = []
             if ua[0][s] != ub[0][s]:
                 what.append("instructions")
             if s in ua[1] and s in ub[1] and ua[1][s] != ub[1][s]:
                 what.append("metadata")
-            if what:
+            if not what:
+                continue
+            name = ckr.short(ckr.demangle([s])[s]) if may_differ else s
+            if not (may_differ and may_differ.search(name)):
                 bad.append("%s: %s" % (s, " and ".join(what)))
+                continue
+            ka, kb = resources(ua[1].get(s), ua[0][s]), resources(ub[1].get(s), ub[0][s])
+            broken = []
+            if kb[".private_segment_fixed_size"] != 0:
+                broken.append("SCRATCH")
+            if kb[".group_segment_fixed_size"] != ka[".group_segment_fixed_size"]:
+                broken.append("LDS BYTES")
+            if s in ua[1] and waves(kb) < waves(ka):
+                broken.append("FEWER WAVES")
+            allowed.append("%-44s %s | %s%s" % (name[:44], row(ka), row(kb), "   <-- " + ", ".join(broken) if broken else ""))
+            if broken:
+                bad.append("%s: %s" % (s, ", ".join(broken).lower()))
         n_ins = sum(len(v) for v in ua[0].values())
-        verdict = "identical" if not (bad or only_a or only_b) else "DIFFERENT"
+        verdict = "DIFFERENT" if (bad or only_a or only_b) else "identical but for %d symbols that may differ" % len(allowed) if allowed else "identical"
         lines.append("unit %d: %s: %d instructions compared: %s" % (i, label(ua), n_ins, verdict))
         for s in only_a:
             lines.append("    only in A: " + s)
         for s in only_b:
             lines.append("    only in B: " + s)
+        for s in allowed:
+            lines.append("    may differ: " + s)
         for s in bad:
             lines.append("    differs: " + s)
         differ += len(bad)
@@ -146,18 +192,30 @@ def compare(a, b):
 
 
 def main():
-    if len(sys.argv) != 3:
+    argv, pattern = sys.argv[1:], None
+    if "--may-differ" in argv[:-1]:
+        at = argv.index("--may-differ")
+        pattern = re.compile(argv[at + 1])
+        del argv[at:at + 2]
+    if len(argv) != 2:
         sys.exit(__doc__)
     if not tools_present():
         sys.exit("the ROCm llvm tools (%s) are not under %s" % (", ".join(TOOLS), LLVM))
-    a, b = units(sys.argv[1]), units(sys.argv[2])
-    lines, differ, sets = compare(a, b)
-    print("# device code of two builds, %s code objects, symbol by symbol: A = %s | B = %s" % (ARCH, sys.argv[1], sys.argv[2]))
+    a, b = units(argv[0]), units(argv[1])
+    lines, differ, sets = compare(a, b, pattern)
+    allowed = sum(1 for l in lines if l.startswith("    may differ: "))
+    print("# device code of two builds, %s code objects, symbol by symbol: A = %s | B = %s" % (ARCH, argv[0], argv[1]))
+    if pattern:
+        print("# may differ: %s; their rows A | B: v = VGPRs, a = AGPRs, s = SGPRs, lds / scr = bytes of LDS / scratch per workgroup / lane," % pattern.pattern)
+        print("# occupancy by arithmetic (tools/cameras_kernel_resources.py), code = bytes of the symbol's instructions")
     print("\n".join(lines))
     if sets:
         print("verdict: DIFFERENT SETS of symbols")
     elif differ:
         print("verdict: DIFFERENT (%d symbols)" % differ)
+    elif allowed:
+        print("verdict: identical but for %d symbols that may differ, each without scratch, with A's LDS bytes and no fewer waves per SIMD (%d symbols in all)"
+              % (allowed, sum(len(u[0]) for u in a)))
     else:
         print("verdict: identical (%d translation units, %d kernels, every instruction, encoding and metadata record)" % (len(a), sum(len(u[1]) for u in a)))
     return 1 if (sets or differ) else 0
