@@ -828,6 +828,97 @@ int ssd_process_host_cameras_drift(ssd_handle *h, const void *frames, int nframe
                                    ssd_frame_result *results, int min_points, double k_sigma, double gate_min, int passes /* 0..4 */,
                                    int fold_min_points, ssd_camera_drift *out /* table count */);
 
+/* ---- tread clearance: what stands on each reported surface, and where --------------------------------------------------------------
+ * EXTENSION.  A result says where every tread is; it does not say whether the tread is FREE.  A box, a foot or a
+ * bag on a step lies in the points of no plateau, which the reference drops (pointcloud.cpp:285-294).  One more pass gathers, per reported
+ * surface, the points that stand on it.  The rule is stated on public data only - the frame's ssd_frame_result, the calibration, the
+ * points - in doubles without FMA contraction, in the order written; one text for host and device (csrc/ssd_clearance.h).
+ * A frame whose status has SSD_ST_THROW, or with n_steps == 0, has no occupant.  Otherwise a point is an OCCUPANT OF SURFACE k (k in the
+ * result's order) iff
+ *   1. it is valid and in range exactly as a labelled point is: z > 0 on the float camera point (16-bit depth deprojected first, bit-equal
+ *      to ssd_deproject_host), and w = A p + b - each row (a0 x + a1 y) + a2 z, then + b - strictly inside the measuring range;
+ *   2. with ex = (r2[0] wx + r2[1] wy) + t2[0], ey = (r2[2] wx + r2[3] wy) + t2[1], ez = wz + world_z:
+ *   3. fabs(ez - steps[j].height) > lo for EVERY j < n_steps - a slab around every reported height belongs to the surfaces, whatever
+ *      their quadrilaterals say;
+ *   4. k is the lowest index with ez > steps[k].height + lo && ez < steps[k].height + hi and (ex, ey) inside surface k's quadrilateral
+ *      shrunk by margin:  ring FL, FR, BR, BL = quad[0..1], [2..3], [6..7], [4..5];  A2 = ((t0 + t1) + t2) + t3, t_i = x_i y_(i+1) -
+ *      x_(i+1) y_i;  A2 == 0 or unordered: the surface takes nothing (quirk Q6's all-zero ground);  o = A2 > 0 ? 1 : -1;  per side
+ *      dx = x_(i+1) - x_i, dy = y_(i+1) - y_i, c = o (dx (ey - y_i) - dy (ex - x_i));  kept iff c >= 0 && c c >= (margin margin)
+ *      (dx dx + dy dy) on all four sides.  No square root, no division; a NaN corner keeps nothing.
+ * The margin keeps the riser faces that hang over a tread's rim out (DESIGN.md section 7m has the figures).
+ * Clearance moments of a frame: an ssd_frame_moments - the header as the surface moments' (n_surfaces = n_steps, ground), s[k] the ten sums
+ * and n_far over surface k's occupants by the fixed-point rule of the surface fit as it stands; records at k >= n_surfaces are zero.
+ * Clearance mask: width * height bytes per frame, k + 1 on an occupant of surface k, 0 elsewhere - a buffer of its own, NOT the label
+ * mask, in the form ssd_surface_moments_host accepts: the host sums over the device's mask equal the device's moments byte for byte.
+ * Out of scope: ssd_pipeline_* and ssd_enqueue_stages; the label mask (untouched); the tallest occupant point (a maximum, not a sum);
+ * occupants inside the slabs of item 3 (an object lower than lo is not seen). */
+typedef struct
+{
+  double margin;      /* [0, 1] m: how far inside the quadrilateral's sides an occupant must lie */
+  double lo;          /* (0, 1] m: half-width of the slab around every reported height, and the band's lower end above the surface */
+  double hi;          /* (lo, 8] m: the band's upper end above the surface */
+} ssd_clearance_rule;
+
+#define SSD_CL_FREE 0
+#define SSD_CL_OCCUPIED 1
+typedef struct
+{
+  int32_t status, reserved;   /* SSD_CL_FREE / SSD_CL_OCCUPIED */
+  int64_t n, n_far;           /* the moments' */
+  double centroid[3];         /* mean of the occupants, external world (as ssd_surface_fit's) */
+  double height_mean;         /* centroid z - the step's height */
+  double height_rms;          /* rms spread of the occupants along the world's up axis, metres */
+  double from_front;          /* the centroid's distance behind the surface's front edge (FL -> FR), positive towards the back, metres */
+  double along_front;         /* ... and its position along that edge from FL, metres */
+  double extent[3];           /* square roots of the scatter's eigenvalues, descending, metres */
+} ssd_clearance;              /* 104 bytes */
+
+typedef struct
+{
+  int32_t n_surfaces, ground;
+  ssd_clearance s[SSD_MAX_STEPS];
+} ssd_frame_clearance;
+
+/* The pass alone (k_clearance), against the workspace of the handle's last WHOLE enqueue, behind it on that batch's stream and in front
+ * of a completion event of its own - every check, stream rule and withdrawal of ssd_enqueue_surface_refit (ssd_enqueue_cameras_clearance:
+ * of ssd_enqueue_cameras_surface_refit; frame i is byte for byte a one-camera handle's).  d_out: nframes contiguous records; d_mask (may
+ * be NULL): frame i's bytes at d_mask + i * mask_stride; both device memory, zeroed on the stream in front of the pass - of the mask only
+ * the width * height bytes of every stride.  The pass reads the results k_final left, the state and the cell records, and writes the
+ * caller's two buffers alone: nothing ssd_fetch* reads changes.  It may be repeated, with other rules, until the next enqueue takes the
+ * workspace.  The first call makes events only: ssd_workspace_bytes does not move, and a handle that never calls it allocates and
+ * launches nothing.  SSD_E_ARG before anything is launched: the refit's refusals, a null rule or destination, a rule outside the ranges
+ * above, mask_stride < width * height with a mask. */
+int ssd_enqueue_clearance(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream, int input,
+                          const ssd_clearance_rule *rule, ssd_frame_moments *d_out, uint8_t *d_mask /* may be NULL */, size_t mask_stride);
+int ssd_enqueue_cameras_clearance(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream, int input,
+                                  const ssd_clearance_rule *rule, ssd_frame_moments *d_out, uint8_t *d_mask /* may be NULL */, size_t mask_stride);
+/* waits for the last clearance pass (SSD_E_ARG: there was none) */
+int ssd_fetch_clearance(ssd_handle *h, void *stream);
+/* the device time of the last clearance pass, the zeroing in front of it included (0 when timing was off for it) */
+int ssd_get_clearance_time(ssd_handle *h, float *ms);
+/* host only, no GPU needed: one frame's occupants by the shared text.  input, intr and frame as ssd_surface_moments_host; result: the
+ * frame's; ground goes into the record's header as given.  out and mask (width * height bytes) may each be NULL.  SSD_E_ARG: a null
+ * cfg, cal, frame, result or rule, a bad input, depth without good intrinsics, n_steps outside 0 .. SSD_MAX_STEPS, a rule outside its ranges. */
+int ssd_clearance_host(const ssd_config *cfg, const ssd_calibration *cal, int input, const ssd_intrinsics *intr, const void *frame,
+                       const ssd_frame_result *result, int ground, const ssd_clearance_rule *rule, ssd_frame_moments *out /* may be NULL */,
+                       uint8_t *mask /* may be NULL */);
+/* host only: a frame's clearance moments -> what stands on each surface.  Per surface k < n_surfaces: status OCCUPIED iff n + n_far >=
+ * max(min_support, 1); n, n_far always; the doubles (0 unless occupied with n > 0): centroid formed as ssd_surface_fit_solve forms it,
+ * height_mean = centroid z - steps[k].height, height_rms = sqrt of the exact centred scatter's variance along row 3 of cal->a,
+ * from_front / along_front against the front edge quad[0..1] -> quad[2..3] (0 where that edge has no length), extent by the shared
+ * Jacobi.  Records at k >= n_surfaces are zero.  SSD_E_ARG: a null pointer, n_surfaces outside 0 .. SSD_MAX_STEPS. */
+int ssd_clearance_solve(const ssd_frame_moments *moments, const ssd_frame_result *result, const ssd_calibration *cal, int min_support,
+                        ssd_frame_clearance *out);
+/* frames in host memory through the slices of ssd_process_host (ssd_process_host_cameras): per slice enqueue, pass, fetch, solve.  Fills
+ * results[nframes] (byte for byte ssd_process_host's / ssd_process_host_cameras'), out[nframes] (each frame solved against the handle's
+ * calibration / its camera's) and, when not NULL, moments[nframes] and mask (nframes x width * height bytes, packed). */
+int ssd_process_host_clearance(ssd_handle *h, const void *frames, int nframes, int input, const ssd_clearance_rule *rule, int min_support,
+                               ssd_frame_result *results, ssd_frame_moments *moments /* may be NULL */, uint8_t *mask /* may be NULL */,
+                               ssd_frame_clearance *out);
+int ssd_process_host_cameras_clearance(ssd_handle *h, const void *frames, int nframes, const uint16_t *camera_of_frame, int input,
+                                       const ssd_clearance_rule *rule, int min_support, ssd_frame_result *results,
+                                       ssd_frame_moments *moments /* may be NULL */, uint8_t *mask /* may be NULL */, ssd_frame_clearance *out);
+
 /* stage selector for profiling / roofline measurement: runs only the chosen stage(s) of the pipeline */
 #define SSD_STAGE_HIST 1       /* K1: transform + crop + bin + histogram */
 #define SSD_STAGE_PEAKS 2

@@ -177,6 +177,30 @@ class FrameGates(C.Structure):
     _fields_ = [("n_surfaces", C.c_int32), ("reserved", C.c_int32), ("g", PlaneGate * MAX_STEPS)]
 
 
+class ClearanceRule(C.Structure):
+    """ssd_clearance_rule: how far inside a surface's sides (margin) and how high above it (lo, hi) an occupant lies, metres (tread
+    clearance)"""
+    _fields_ = [("margin", C.c_double), ("lo", C.c_double), ("hi", C.c_double)]
+
+    def __init__(self, margin=0.03, lo=0.03, hi=0.5):
+        super().__init__(float(margin), float(lo), float(hi))
+
+
+CL_FREE, CL_OCCUPIED = 0, 1
+
+
+class Clearance(C.Structure):
+    """ssd_clearance: what stands on one surface, external world coordinates (status CL_FREE: the doubles are 0)"""
+    _fields_ = [("status", C.c_int32), ("reserved", C.c_int32), ("n", C.c_int64), ("n_far", C.c_int64), ("centroid", C.c_double * 3),
+                ("height_mean", C.c_double), ("height_rms", C.c_double), ("from_front", C.c_double), ("along_front", C.c_double),
+                ("extent", C.c_double * 3)]
+
+
+class FrameClearance(C.Structure):
+    """ssd_frame_clearance: the occupants of every surface of a frame"""
+    _fields_ = [("n_surfaces", C.c_int32), ("ground", C.c_int32), ("s", Clearance * MAX_STEPS)]
+
+
 MAX_RISERS = MAX_STEPS - 1
 
 
@@ -249,6 +273,8 @@ EXPORTS = [
     "ssd_enqueue_camera_fold", "ssd_enqueue_camera_ground_gates", "ssd_enqueue_cameras_surface_refit_folded", "ssd_camera_drift_from_fold",
     "ssd_process_host_cameras_drift",
     "ssd_set_riser_labels", "ssd_get_riser_labels_time_back", "ssd_labels_split",
+    "ssd_enqueue_clearance", "ssd_enqueue_cameras_clearance", "ssd_fetch_clearance", "ssd_get_clearance_time", "ssd_clearance_host",
+    "ssd_clearance_solve", "ssd_process_host_clearance", "ssd_process_host_cameras_clearance",
 ]
 # libssd_source.so — the frame source standing in for the camera (include/ssd_source.h)
 SOURCE_EXPORTS = [
@@ -351,6 +377,17 @@ def lib():
                                           C.POINTER(FrameGates)]
     L.ssd_enqueue_camera_fold.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     L.ssd_enqueue_camera_ground_gates.argtypes = [vp, vp, vp, i32, vp, i32, i32, C.c_double, C.c_double, vp, vp]
+    L.ssd_enqueue_clearance.argtypes = [vp, vp, sz, i32, vp, i32, C.POINTER(ClearanceRule), vp, vp, sz]
+    L.ssd_enqueue_cameras_clearance.argtypes = L.ssd_enqueue_clearance.argtypes
+    L.ssd_fetch_clearance.argtypes = [vp, vp]
+    L.ssd_get_clearance_time.argtypes = [vp, C.POINTER(C.c_float)]
+    L.ssd_clearance_host.argtypes = [C.POINTER(Config), C.POINTER(Calibration), i32, C.POINTER(Intrinsics), vp, C.POINTER(FrameResult), i32,
+                                     C.POINTER(ClearanceRule), C.POINTER(FrameMoments), vp]
+    L.ssd_clearance_solve.argtypes = [C.POINTER(FrameMoments), C.POINTER(FrameResult), C.POINTER(Calibration), i32, C.POINTER(FrameClearance)]
+    L.ssd_process_host_clearance.argtypes = [vp, vp, i32, i32, C.POINTER(ClearanceRule), i32, C.POINTER(FrameResult), C.POINTER(FrameMoments), vp,
+                                             C.POINTER(FrameClearance)]
+    L.ssd_process_host_cameras_clearance.argtypes = [vp, vp, i32, C.POINTER(C.c_uint16), i32, C.POINTER(ClearanceRule), i32, C.POINTER(FrameResult),
+                                                     C.POINTER(FrameMoments), vp, C.POINTER(FrameClearance)]
     L.ssd_enqueue_cameras_surface_refit_folded.argtypes = [vp, vp, sz, i32, vp, i32, vp, i32, C.c_double, C.c_double, i32, vp]
     L.ssd_camera_drift_from_fold.argtypes = [C.POINTER(CameraFold), C.POINTER(Camera), i32, i32, C.POINTER(CameraDrift)]
     L.ssd_process_host_cameras_drift.argtypes = [vp, vp, i32, C.POINTER(C.c_uint16), i32, C.POINTER(FrameResult), i32, C.c_double, C.c_double, i32, i32,
@@ -635,6 +672,35 @@ def surface_refit_moments_host(cfg, frame, labels, gates, n_surfaces, ground, in
     _check(lib().ssd_surface_refit_moments_host(C.byref(cfg), INPUT_DEPTH16 if depth else INPUT_VERTICES, C.byref(intr) if depth else None,
                                                 a.ctypes.data_as(C.c_void_p), lab.ctypes.data_as(C.c_void_p),
                                                 C.byref(gates) if gates is not None else None, int(n_surfaces), int(ground), C.byref(out)))
+    return out
+
+
+def _calibration_of(cal):
+    return cal.constants if isinstance(cal, GeometricTransformation) else cal.cal if isinstance(cal, Camera) else cal
+
+
+def clearance_host(cfg, cal, frame, result, ground, rule=None, intr=None, mask=True):
+    """ssd_clearance_host: one frame's occupants by the rule of DESIGN.md section 7m -> (FrameMoments, uint8 [H, W] mask with k + 1 on an
+    occupant of surface k; None with mask=False).  frame: float32 [H, W, 3], or uint16 [H, W] with intr (16-bit depth input)."""
+    depth = intr is not None
+    a = np.ascontiguousarray(frame, dtype=np.uint16 if depth else np.float32)
+    if a.size != cfg.width * cfg.height * (1 if depth else 3):
+        raise SsdError("clearance_host: the array is not one frame")
+    rule = ClearanceRule() if rule is None else rule
+    c = _calibration_of(cal)
+    out = FrameMoments()
+    m = np.empty((cfg.height, cfg.width), dtype=np.uint8) if mask else None
+    _check(lib().ssd_clearance_host(C.byref(cfg), C.byref(c), INPUT_DEPTH16 if depth else INPUT_VERTICES, C.byref(intr) if depth else None,
+                                    a.ctypes.data_as(C.c_void_p), C.byref(result), int(ground), C.byref(rule), C.byref(out),
+                                    m.ctypes.data_as(C.c_void_p) if mask else None))
+    return out, m
+
+
+def clearance_solve(moments, result, cal, min_support=50):
+    """ssd_clearance_solve: a frame's clearance moments -> what stands on each surface (FrameClearance; per surface CL_FREE / CL_OCCUPIED)"""
+    c = _calibration_of(cal)
+    out = FrameClearance()
+    _check(lib().ssd_clearance_solve(C.byref(moments), C.byref(result), C.byref(c), int(min_support), C.byref(out)))
     return out
 
 
@@ -1010,6 +1076,63 @@ class Detector:
         _check(fn(self._h, a.ctypes.data_as(C.c_void_p), n, INPUT_DEPTH16 if depth else INPUT_VERTICES, res, first if moments else None,
                   refit if moments else None, int(min_points), float(k_sigma), float(gate_min), int(passes), out))
         return (list(res), list(out), list(first), list(refit)) if moments else (list(res), list(out))
+
+    # ---- tread clearance (include/ssd_hip.h)
+    def enqueue_clearance(self, d_ptr, nframes, d_moments, rule=None, d_mask=None, mask_stride=None, depth=False, stride_bytes=None, stream=None,
+                          cameras=False):
+        """ssd_enqueue_clearance: the clearance pass alone, behind the handle's last whole enqueue of the same frames: frame i's
+        FrameMoments over its occupants at d_moments + i * sizeof(FrameMoments) and, with d_mask, its W * H mask bytes at
+        d_mask + i * mask_stride, both device memory; complete when fetch_clearance() returns"""
+        frame = self.cfg.width * self.cfg.height * (2 if depth else 12)
+        rule = ClearanceRule() if rule is None else rule
+        fn = lib().ssd_enqueue_cameras_clearance if cameras else lib().ssd_enqueue_clearance
+        _check(fn(self._h, C.c_void_p(d_ptr), stride_bytes or frame, nframes, C.c_void_p(stream or 0), INPUT_DEPTH16 if depth else INPUT_VERTICES,
+                  C.byref(rule), C.c_void_p(d_moments), C.c_void_p(d_mask or 0), mask_stride or self.cfg.width * self.cfg.height))
+
+    def enqueue_cameras_clearance(self, d_ptr, nframes, d_moments, rule=None, d_mask=None, mask_stride=None, depth=False, stride_bytes=None,
+                                  stream=None):
+        """ssd_enqueue_cameras_clearance: enqueue_clearance behind the handle's last whole CAMERAS enqueue of the same frames"""
+        self.enqueue_clearance(d_ptr, nframes, d_moments, rule, d_mask, mask_stride, depth, stride_bytes, stream, cameras=True)
+
+    def fetch_clearance(self, stream=None):
+        """ssd_fetch_clearance: waits for the last enqueue_clearance"""
+        _check(lib().ssd_fetch_clearance(self._h, C.c_void_p(stream or 0)))
+
+    def clearance_time_ms(self):
+        """Device time of the last clearance pass (0.0: timing was off for it)"""
+        ms = C.c_float(0.0)
+        _check(lib().ssd_get_clearance_time(self._h, C.byref(ms)))
+        return ms.value
+
+    def process_host_clearance(self, frames, rule=None, min_support=50, depth=False, moments=False, mask=False, camera_of_frame=None):
+        """ssd_process_host_clearance: frames on the host (float32 [n, H, W, 3], or uint16 [n, H, W] with depth=True)
+        -> (list of FrameResult, list of FrameClearance), with moments=True also the list of FrameMoments, with mask=True also the
+        masks (uint8 [n, H, W])"""
+        a = np.ascontiguousarray(frames, dtype=np.uint16 if depth else np.float32)
+        per = self.cfg.width * self.cfg.height * (1 if depth else 3)
+        n = a.size // per
+        if n < 1 or a.size != n * per:
+            raise SsdError("process_host_clearance: array does not hold whole frames")
+        rule = ClearanceRule() if rule is None else rule
+        res, mom, out = (FrameResult * n)(), (FrameMoments * n)(), (FrameClearance * n)()
+        m = np.empty((n, self.cfg.height, self.cfg.width), dtype=np.uint8) if mask else None
+        tail = (C.byref(rule), int(min_support), res, mom if moments else None, m.ctypes.data_as(C.c_void_p) if mask else None, out)
+        inp = INPUT_DEPTH16 if depth else INPUT_VERTICES
+        if camera_of_frame is None:
+            _check(lib().ssd_process_host_clearance(self._h, a.ctypes.data_as(C.c_void_p), n, inp, *tail))
+        else:
+            idx = self._camera_index(camera_of_frame, n)
+            _check(lib().ssd_process_host_cameras_clearance(self._h, a.ctypes.data_as(C.c_void_p), n, idx.ctypes.data_as(C.POINTER(C.c_uint16)), inp, *tail))
+        ret = [list(res), list(out)]
+        if moments:
+            ret.append(list(mom))
+        if mask:
+            ret.append(m)
+        return tuple(ret)
+
+    def process_host_cameras_clearance(self, frames, camera_of_frame, rule=None, min_support=50, depth=False, moments=False, mask=False):
+        """ssd_process_host_cameras_clearance: process_host_clearance with one camera index per frame"""
+        return self.process_host_clearance(frames, rule, min_support, depth, moments, mask, camera_of_frame=camera_of_frame)
 
     # ---- surface fit of cameras batches, drift per camera (include/ssd_hip.h, DESIGN.md section 7e)
     def enqueue_cameras_surface_moments(self, d_ptr, nframes, camera_of_frame, d_moments, depth=False, stride_bytes=None, stream=None):

@@ -10,6 +10,7 @@
 #include "ssd_prexy.h"
 #include "ssd_ground.h"
 #include "ssd_refit.h"
+#include "ssd_clearance.h"
 #include "ssd_solve.h"
 #include "ssd_fold.h"
 
@@ -1107,6 +1108,7 @@ static int enqueue_impl(ssd_handle *h, const void *d_xyz, size_t frame_stride_by
     h->wholeDepth = depthInput;
     h->wholeFrames = d_xyz;
     h->wholeStride = frame_stride_bytes;
+    h->wholeResults = (direct ? h->hResultsDev : h->dResults) + static_cast<size_t>(slot) * h->F;   /* where k_final left its records */
   }
   return SSD_OK;
 }
@@ -2207,59 +2209,51 @@ static int fold_prepare(ssd_handle *h)
   return e == hipSuccess ? SSD_OK : hip_fail(e, "the camera fold's buffer: ");
 }
 
-/* all refit entry points: `cameras` = behind a whole cameras batch (wholeKind 2), under the table and the index that batch left in its
- * workspace; otherwise behind a whole run under the handle's calibration (wholeKind 1) */
-static int refit_enqueue_impl(ssd_handle *h, const char *who, bool cameras, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream,
-                              int input, const GateSource &gates, ssd_frame_moments *d_out)
+/* What a pass behind the handle's last whole enqueue is held to - the refit (section 7g, 7h) and the clearance pass (section 7m) alike:
+ * `cameras` = behind a whole cameras batch (wholeKind 2), under the table and the index that batch left in its workspace; otherwise behind
+ * a whole run under the handle's calibration (wholeKind 1).  verb: what the pass does to the enqueue, oneCal / cams: the entry points of
+ * either kind, for the messages.  SSD_E_ARG before anything is launched or copied. */
+struct BehindWhole
 {
-  const std::string me(who);
-  if(!h || !d_frames || (!gates.host && !gates.dPrev) || !d_out)
-    return fail(SSD_E_ARG, me + ": null argument");
-  if(gates.dPrev)
-  {
-    const int rule = check_gate_rule(who, gates.kSigma, gates.gateMin);
-    if(rule) return rule;
-  }
+  const char *verb, *oneCal, *cams;
+};
+static int check_behind_whole(const ssd_handle *h, const std::string &me, const BehindWhole &w, bool cameras, const void *d_frames,
+                              size_t frame_stride_bytes, int nframes, int input)
+{
   if(input != SSD_INPUT_VERTICES && input != SSD_INPUT_DEPTH16)
     return fail(SSD_E_ARG, me + ": input must be SSD_INPUT_VERTICES or SSD_INPUT_DEPTH16");
   const bool depthInput = input == SSD_INPUT_DEPTH16;
   if(cameras)
   {
     if(h->wholeKind == 1)
-      return fail(SSD_E_ARG, me + ": the last enqueue was a one-calibration batch, not a cameras batch (ssd_enqueue_surface_refit refits those)");
+      return fail(SSD_E_ARG, me + ": the last enqueue was a one-calibration batch, not a cameras batch (" + w.oneCal + " " + w.verb + "s those)");
     if(h->wholeKind != 2)
-      return fail(SSD_E_ARG, me + ": no whole cameras enqueue to refit (none yet, the last one was a partial run, or ssd_set_cameras withdrew it)");
+      return fail(SSD_E_ARG, me + ": no whole cameras enqueue to " + w.verb + " (none yet, the last one was a partial run, or ssd_set_cameras withdrew it)");
   }
   else
   {
     if(depthInput && !h->haveIntr)
       return fail(SSD_E_ARG, me + ": depth input: call ssd_set_intrinsics first");
     if(h->wholeKind == 2)
-      return fail(SSD_E_ARG, me + ": the last enqueue was a cameras batch (ssd_enqueue_cameras_surface_refit refits those)");
+      return fail(SSD_E_ARG, me + ": the last enqueue was a cameras batch (" + w.cams + " " + w.verb + "s those)");
     if(h->wholeKind != 1)
-      return fail(SSD_E_ARG, me + ": no whole enqueue to refit (none yet, or the last one was a partial run)");
+      return fail(SSD_E_ARG, me + ": no whole enqueue to " + w.verb + " (none yet, or the last one was a partial run)");
   }
   if(nframes != h->lastFrames)
     return fail(SSD_E_ARG, me + ": nframes is not the last enqueue's");
   if(depthInput != h->wholeDepth || d_frames != h->wholeFrames || frame_stride_bytes != h->wholeStride)
     return fail(SSD_E_ARG, me + ": input, frames or stride are not the last enqueue's");
-  ssd_lane &L = h->lane[h->lastLane];
+  const ssd_lane &L = h->lane[h->lastLane];
   if(!L.haveLast || !L.dState || !L.dTileMasks || (!cameras && depthInput && !h->dDepthMaps) || (cameras && (!h->dCams || !L.dCamIndex)))
     return fail(SSD_E_HIP, me + ": the handle's workspace is incomplete (internal)");
-  HIP_TRY(hipSetDevice(h->device));
-  int rc = refit_prepare(h);
-  if(rc) return rc;
-  if(gates.cameraGate)
-  {
-    rc = fold_prepare(h);
-    if(rc) return rc;
-  }
-  const bool timing = h->timing && !h->ev.empty();
-  if(timing && h->evRefit.empty())
-    HIP_TRY(make_events(h->evRefit, 2, hipEventDefault));
-  /* behind the batch, on the stream it ran on: the caller's with one workspace (a switch of streams is ordered by the lane's event),
-   * the lane's own with several (behind what the caller's stream holds now, as an enqueue is) */
-  hipStream_t s = static_cast<hipStream_t>(stream);
+  return SSD_OK;
+}
+
+/* ... and the stream it runs on, behind the batch: the caller's with one workspace (a switch of streams is ordered by the lane's event),
+ * the lane's own with several (behind what the caller's stream holds now, as an enqueue is) */
+static int stream_behind_whole(ssd_handle *h, ssd_lane &L, void *stream, hipStream_t &s)
+{
+  s = static_cast<hipStream_t>(stream);
   if(h->depth == 1)
   {
     if(s != L.lastStream)
@@ -2271,6 +2265,41 @@ static int refit_enqueue_impl(ssd_handle *h, const char *who, bool cameras, cons
     s = L.stream;
     HIP_TRY(hipStreamWaitEvent(s, L.in, 0));
   }
+  return SSD_OK;
+}
+
+static const BehindWhole kRefitBehind{ "refit", "ssd_enqueue_surface_refit", "ssd_enqueue_cameras_surface_refit" };
+
+/* all refit entry points */
+static int refit_enqueue_impl(ssd_handle *h, const char *who, bool cameras, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream,
+                              int input, const GateSource &gates, ssd_frame_moments *d_out)
+{
+  const std::string me(who);
+  if(!h || !d_frames || (!gates.host && !gates.dPrev) || !d_out)
+    return fail(SSD_E_ARG, me + ": null argument");
+  if(gates.dPrev)
+  {
+    const int rule = check_gate_rule(who, gates.kSigma, gates.gateMin);
+    if(rule) return rule;
+  }
+  int rc = check_behind_whole(h, me, kRefitBehind, cameras, d_frames, frame_stride_bytes, nframes, input);
+  if(rc) return rc;
+  const bool depthInput = input == SSD_INPUT_DEPTH16;
+  ssd_lane &L = h->lane[h->lastLane];
+  HIP_TRY(hipSetDevice(h->device));
+  rc = refit_prepare(h);
+  if(rc) return rc;
+  if(gates.cameraGate)
+  {
+    rc = fold_prepare(h);
+    if(rc) return rc;
+  }
+  const bool timing = h->timing && !h->ev.empty();
+  if(timing && h->evRefit.empty())
+    HIP_TRY(make_events(h->evRefit, 2, hipEventDefault));
+  hipStream_t s;
+  rc = stream_behind_whole(h, L, stream, s);
+  if(rc) return rc;
   if(h->refitHaveLast)
   {
     if(gates.host)
@@ -2679,6 +2708,323 @@ int ssd_camera_ground_gates(const ssd_frame_moments *moments, const uint16_t *ca
       gates[i].n_surfaces = 1;
   }
   return SSD_OK;
+}
+
+/* ---- tread clearance (include/ssd_hip.h) ------------------------------------------------------------------ */
+
+static int check_clearance_rule(const std::string &who, const ssd_clearance_rule *rule)
+{
+  if(!rule)
+    return fail(SSD_E_ARG, who + ": null rule");
+  if(!clearance_rule_ok(*rule))
+    return fail(SSD_E_ARG, who + ": the rule must have margin in [0, 1], lo in (0, 1] and hi in (lo, 8]");
+  return SSD_OK;
+}
+
+/* host only: the rule of ssd_clearance.h over one frame, point by point in the order of the text */
+int ssd_clearance_host(const ssd_config *cfg, const ssd_calibration *cal, int input, const ssd_intrinsics *intr, const void *frame,
+                       const ssd_frame_result *result, int ground, const ssd_clearance_rule *rule, ssd_frame_moments *out, uint8_t *mask)
+{
+  const std::string who("ssd_clearance_host");
+  if(!cfg || !cal || !frame || !result || cfg->width <= 0 || cfg->height <= 0)
+    return fail(SSD_E_ARG, who + ": bad argument");
+  if(input != SSD_INPUT_VERTICES && input != SSD_INPUT_DEPTH16)
+    return fail(SSD_E_ARG, who + ": input must be SSD_INPUT_VERTICES or SSD_INPUT_DEPTH16");
+  const bool depth = input == SSD_INPUT_DEPTH16;
+  if(depth && (!intr || !good_intrinsics(*intr)))
+    return fail(SSD_E_ARG, who + ": depth input needs intrinsics");
+  if(result->n_steps < 0 || result->n_steps > SSD_MAX_STEPS)
+    return fail(SSD_E_ARG, who + ": n_steps must lie in 0 .. SSD_MAX_STEPS");
+  int rc = check_clearance_rule(who, rule);
+  if(rc) return rc;
+  const int W = cfg->width, H = cfg->height;
+  const size_t nPoints = static_cast<size_t>(W) * H;
+  std::vector<float> deprojected;
+  const float *xyz = static_cast<const float *>(frame);
+  if(depth)
+  {
+    deprojected.resize(3 * nPoints);
+    rc = ssd_deproject_host(intr, W, H, static_cast<const uint16_t *>(frame), deprojected.data());
+    if(rc) return rc;
+    xyz = deprojected.data();
+  }
+  if(out)
+    std::memset(out, 0, sizeof(*out));
+  if(mask)
+    std::memset(mask, 0, nPoints);
+  const int n = (result->status & SSD_ST_THROW) ? 0 : result->n_steps;
+  if(n == 0)
+    return SSD_OK;                               /* no occupant: an all-zero record, as the surface moments' */
+  ClearanceSurface S[SSD_MAX_STEPS];
+  for(int k = 0; k < n; k++)
+    clearance_surface(result->steps[k], rule->margin, S[k]);
+  const ClearanceWorld X{ { cal->r2[0], cal->r2[1], cal->r2[2], cal->r2[3] }, { cal->t2[0], cal->t2[1] }, cal->world_z };
+  const double *a = cal->a, *b = cal->b;
+  long long acc[SSD_MAX_STEPS][kGroundSums + 1] = {};
+  for(size_t i = 0; i < nPoints; i++)
+  {
+    const float fx = xyz[3 * i], fy = xyz[3 * i + 1], fz = xyz[3 * i + 2];
+    if(!(fz > 0.0f))
+      continue;
+    const double x = fx, y = fy, z = fz;
+    const double wx = ((a[0] * x + a[1] * y) + a[2] * z) + b[0];
+    const double wy = ((a[3] * x + a[4] * y) + a[5] * z) + b[1];
+    const double wz = ((a[6] * x + a[7] * y) + a[8] * z) + b[2];
+    if(!(wx > cfg->x_min && wx < cfg->x_max && wy > cfg->y_min && wy < cfg->y_max && wz > cfg->z_min && wz < cfg->z_max))
+      continue;
+    const double ez = wz + X.worldZ;
+    if(clearance_in_slab(S, n, ez, rule->lo))
+      continue;
+    double ex, ey;
+    clearance_external(X, wx, wy, ex, ey);
+    const int k = clearance_lowest(S, (1u << n) - 1u, ex, ey, ez, rule->lo, rule->hi);      /* every surface is a candidate; n <= 17 */
+    if(k < 0)
+      continue;
+    if(mask)
+      mask[i] = static_cast<uint8_t>(k + 1);
+    const double rx = moment_round(x), ry = moment_round(y), rz = moment_round(z);
+    if(moment_near(rx) && moment_near(ry) && moment_near(rz))
+      moment_add(rx, ry, rz, acc[k]);
+    else
+      acc[k][kGroundSums] += 1;
+  }
+  if(out)
+  {
+    out->n_surfaces = n;
+    out->ground = ground ? 1 : 0;
+    std::memcpy(out->s, acc, sizeof(acc));
+  }
+  return SSD_OK;
+}
+
+int ssd_clearance_solve(const ssd_frame_moments *moments, const ssd_frame_result *result, const ssd_calibration *cal, int min_support,
+                        ssd_frame_clearance *out)
+{
+  if(!moments || !result || !cal || !out)
+    return fail(SSD_E_ARG, "ssd_clearance_solve: null");
+  if(moments->n_surfaces < 0 || moments->n_surfaces > SSD_MAX_STEPS)
+    return fail(SSD_E_ARG, "ssd_clearance_solve: n_surfaces must lie in 0 .. SSD_MAX_STEPS");
+  std::memset(out, 0, sizeof(*out));
+  out->n_surfaces = moments->n_surfaces;
+  out->ground = moments->ground;
+  for(int k = 0; k < moments->n_surfaces; k++)
+  {
+    const ssd_ground_moments &m = moments->s[k].m;
+    ssd_clearance &f = out->s[k];
+    f.n = m.n;
+    f.n_far = moments->s[k].n_far;
+    f.status = f.n + f.n_far >= (min_support > 1 ? min_support : 1) ? SSD_CL_OCCUPIED : SSD_CL_FREE;
+    if(f.status != SSD_CL_OCCUPIED || m.n < 1)
+      continue;
+    /* the centroid as ssd_surface_fit_solve forms it: camera coordinates, CameraToWorld, ToExternalWorld */
+    const double nd = static_cast<double>(m.n);
+    double c[3], w[3];
+    for(int i = 0; i < 3; i++)
+      c[i] = static_cast<double>(m.s[i]) / (nd * kGroundScale);
+    for(int i = 0; i < 3; i++)
+      w[i] = ((cal->a[3 * i] * c[0] + cal->a[3 * i + 1] * c[1]) + cal->a[3 * i + 2] * c[2]) + cal->b[i];
+    f.centroid[0] = (cal->r2[0] * w[0] + cal->r2[1] * w[1]) + cal->t2[0];
+    f.centroid[1] = (cal->r2[2] * w[0] + cal->r2[3] * w[1]) + cal->t2[1];
+    f.centroid[2] = w[2] + cal->world_z;
+    const ssd_step &st = result->steps[k];
+    f.height_mean = f.centroid[2] - st.height;
+    /* the centred scatter N SS - S (x) S, exact in 128-bit integers, in m^2 (plane_of_moments' statement: ssd_solve.h) */
+    typedef __int128 i128;
+    const double scale = 1.0 / (nd * nd * kGroundScale * kGroundScale);
+    const int64_t ss[3][3] = { { m.ss[0], m.ss[1], m.ss[2] }, { m.ss[1], m.ss[3], m.ss[4] }, { m.ss[2], m.ss[4], m.ss[5] } };
+    double sc[3][3], lambda[3], v[3][3];
+    for(int i = 0; i < 3; i++)
+      for(int j = 0; j < 3; j++)
+        sc[i][j] = static_cast<double>(static_cast<i128>(m.n) * ss[i][j] - static_cast<i128>(m.s[i]) * m.s[j]) * scale;
+    /* the variance along the world's up axis: row 3 of a */
+    const double *up = cal->a + 6;
+    double var = 0.0;
+    for(int i = 0; i < 3; i++)
+      var += up[i] * ((sc[i][0] * up[0] + sc[i][1] * up[1]) + sc[i][2] * up[2]);
+    f.height_rms = std::sqrt(var > 0.0 ? var : 0.0);
+    /* against the front edge FL -> FR: along it from FL, and behind it (towards the ring's inside) */
+    const double dx = st.quad[2] - st.quad[0], dy = st.quad[3] - st.quad[1], len = std::sqrt(dx * dx + dy * dy);
+    ClearanceSurface S;
+    clearance_surface(st, 0.0, S);
+    if(len > 0.0)
+    {
+      const double px = f.centroid[0] - st.quad[0], py = f.centroid[1] - st.quad[1];
+      f.along_front = (px * dx + py * dy) / len;
+      f.from_front = S.o * (dx * py - dy * px) / len;
+    }
+    jacobi3(sc, lambda, v);
+    for(int i = 0; i < 3; i++)
+      f.extent[i] = std::sqrt(lambda[2 - i] > 0.0 ? lambda[2 - i] : 0.0);
+  }
+  return SSD_OK;
+}
+
+static const BehindWhole kClearanceBehind{ "clear", "ssd_enqueue_clearance", "ssd_enqueue_cameras_clearance" };
+
+/* both entry points of the pass: the refit's refusals (check_behind_whole), then the pass's own, before anything is launched */
+static int clearance_enqueue_impl(ssd_handle *h, const char *who, bool cameras, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream,
+                                  int input, const ssd_clearance_rule *rule, ssd_frame_moments *d_out, uint8_t *d_mask, size_t mask_stride)
+{
+  const std::string me(who);
+  if(!h || !d_frames || !d_out)
+    return fail(SSD_E_ARG, me + ": null argument");
+  int rc = check_clearance_rule(me, rule);
+  if(rc) return rc;
+  if(d_mask && mask_stride < static_cast<size_t>(h->P.nPoints))
+    return fail(SSD_E_ARG, me + ": mask_stride is smaller than width * height");
+  rc = check_behind_whole(h, me, kClearanceBehind, cameras, d_frames, frame_stride_bytes, nframes, input);
+  if(rc) return rc;
+  if(!h->wholeResults)
+    return fail(SSD_E_HIP, me + ": the last enqueue's result records are missing (internal)");
+  const bool depthInput = input == SSD_INPUT_DEPTH16;
+  ssd_lane &L = h->lane[h->lastLane];
+  HIP_TRY(hipSetDevice(h->device));
+  if(!h->clearDone)
+  {
+    Event done;
+    const hipError_t e = done.create(hipEventDisableTiming);
+    if(e != hipSuccess)
+      return hip_fail(e, me + ": its event: ");
+    h->clearDone = std::move(done);
+  }
+  const bool timing = h->timing && !h->ev.empty();
+  if(timing && h->evClear.empty())
+    HIP_TRY(make_events(h->evClear, 2, hipEventDefault));
+  hipStream_t s;
+  rc = stream_behind_whole(h, L, stream, s);
+  if(rc) return rc;
+  /* a pass on another stream than the one before goes behind it: the last pass's event then covers every pass so far */
+  if(h->clearHaveLast && s != h->clearLastStream)
+    HIP_TRY(hipStreamWaitEvent(s, h->clearDone, 0));
+  h->clearHaveLast = true;
+  h->clearLastStream = s;
+  const CameraSel camSel{ h->dCams, L.dCamIndex, h->camsNeedChecks };
+  const Batch B = make_batch(h, h->P, L, d_frames, frame_stride_bytes, nframes, depthInput, s, cameras ? &camSel : nullptr);
+  const int chunk = choose_chunk(h->tune, h->P.nPoints, nframes);   /* the labels' and the refit's */
+  if(timing) HIP_TRY(hipEventRecord(h->evClear[0], s));
+  HIP_TRY(hipMemsetAsync(d_out, 0, sizeof(ssd_frame_moments) * static_cast<size_t>(nframes), s));
+  if(d_mask)
+  {
+    /* only the bytes below width * height of every stride are the pass's */
+    if(mask_stride == static_cast<size_t>(h->P.nPoints))
+      HIP_TRY(hipMemsetAsync(d_mask, 0, mask_stride * static_cast<size_t>(nframes), s));
+    else
+      HIP_TRY(hipMemset2DAsync(d_mask, mask_stride, 0, static_cast<size_t>(h->P.nPoints), static_cast<size_t>(nframes), s));
+  }
+  launch_clearance(B, chunk, h->wholeResults, *rule, d_out, d_mask, mask_stride);
+  HIP_TRY(hipGetLastError());
+  if(timing) HIP_TRY(hipEventRecord(h->evClear[1], s));
+  h->clearTimed = timing;
+  HIP_TRY(hipEventRecord(h->clearDone, s));
+  /* the workspace is in use until here: whatever takes it next, on whichever stream, goes behind the pass */
+  HIP_TRY(hipEventRecord(L.done, s));
+  L.lastStream = s;
+  return SSD_OK;
+}
+
+int ssd_enqueue_clearance(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream, int input,
+                          const ssd_clearance_rule *rule, ssd_frame_moments *d_out, uint8_t *d_mask, size_t mask_stride)
+{
+  return clearance_enqueue_impl(h, "ssd_enqueue_clearance", false, d_frames, frame_stride_bytes, nframes, stream, input, rule, d_out, d_mask, mask_stride);
+}
+
+int ssd_enqueue_cameras_clearance(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream, int input,
+                                  const ssd_clearance_rule *rule, ssd_frame_moments *d_out, uint8_t *d_mask, size_t mask_stride)
+{
+  return clearance_enqueue_impl(h, "ssd_enqueue_cameras_clearance", true, d_frames, frame_stride_bytes, nframes, stream, input, rule, d_out, d_mask, mask_stride);
+}
+
+int ssd_fetch_clearance(ssd_handle *h, void *)
+{
+  if(!h)
+    return fail(SSD_E_ARG, "ssd_fetch_clearance: null handle");
+  if(!h->clearHaveLast)
+    return fail(SSD_E_ARG, "ssd_fetch_clearance: no ssd_enqueue_clearance to wait for");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipEventSynchronize(h->clearDone));
+  return SSD_OK;
+}
+
+int ssd_get_clearance_time(ssd_handle *h, float *ms)
+{
+  if(!h || !ms)
+    return fail(SSD_E_ARG, "ssd_get_clearance_time: null");
+  if(!h->clearHaveLast)
+    return fail(SSD_E_ARG, "ssd_get_clearance_time: no ssd_enqueue_clearance yet");
+  *ms = 0.0f;
+  if(!h->clearTimed)
+    return SSD_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipEventSynchronize(h->evClear[1]));
+  HIP_TRY(hipEventElapsedTime(ms, h->evClear[0], h->evClear[1]));
+  return SSD_OK;
+}
+
+/* both host entry points, the callers' own refusals behind them: per slice, while it is still in its staging buffer, the enqueue, the
+ * pass, both fetches and the solve; the records go out through the first label staging buffer, the mask through the second */
+static int process_host_clearance_impl(ssd_handle *h, const char *who, const void *frames, int nframes, const uint16_t *camOf, int input,
+                                       const ssd_clearance_rule *rule, int min_support, ssd_frame_result *results, ssd_frame_moments *moments,
+                                       uint8_t *mask, ssd_frame_clearance *out)
+{
+  int rc = check_clearance_rule(who, rule);
+  if(rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  SliceFeed feed{ h, host_frames(h, input, kForPipeline), frames, nframes };
+  rc = feed.prepare();
+  if(rc) return rc;
+  const size_t nPoints = static_cast<size_t>(h->P.nPoints);
+  const size_t recordBytes = static_cast<size_t>(feed.slice) * sizeof(ssd_frame_moments), maskBytes = mask ? static_cast<size_t>(feed.slice) * nPoints : 0;
+  rc = labels_prepare(h, recordBytes > maskBytes ? recordBytes : maskBytes);
+  if(rc) return rc;
+  ssd_frame_moments *dRecords = reinterpret_cast<ssd_frame_moments *>(h->labelStage[0].get());
+  uint8_t *dMask = mask ? h->labelStage[1].get() : nullptr;
+  std::vector<ssd_frame_moments> own;
+  moments = moments_or_own(moments, own, nframes);
+  for(int c = 0; c < feed.slices(); c++)
+  {
+    const void *buf;
+    int done, n;
+    /* the body blocks on the pass, so the next slice's copy goes out in front of it, beside this slice's kernels */
+    rc = feed.stage(c);
+    if(!rc) rc = feed.stage(c + 1);
+    if(!rc) rc = feed.ready(c, buf, done, n);
+    if(rc) return rc;
+    rc = enqueue_impl(h, buf, feed.f.devFrameBytes, n, h->ingestCompute, SSD_STAGE_ALL, feed.f.depth, nullptr, 0, camOf ? camOf + done : nullptr);
+    if(!rc) rc = clearance_enqueue_impl(h, who, camOf != nullptr, buf, feed.f.devFrameBytes, n, h->ingestCompute, input, rule, dRecords, dMask, nPoints);
+    if(!rc) rc = ssd_fetch_back(h, results + done, n, 0);
+    if(rc) return rc;
+    /* behind the pass on the stream it ran on; the body waits, so the staging buffers are free for the next slice */
+    hipStream_t s = h->lane[h->lastLane].lastStream;
+    HIP_TRY(hipMemcpyAsync(moments + done, dRecords, sizeof(ssd_frame_moments) * static_cast<size_t>(n), hipMemcpyDeviceToHost, s));
+    if(mask)
+      HIP_TRY(hipMemcpyAsync(mask + static_cast<size_t>(done) * nPoints, dMask, static_cast<size_t>(n) * nPoints, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    rc = feed.consumed(c, s);
+    if(rc) return rc;
+    for(int i = 0; i < n; i++)
+    {
+      const ssd_calibration cal = frame_calibration(h, camOf, done + i);
+      rc = ssd_clearance_solve(moments + done + i, results + done + i, &cal, min_support, out + done + i);
+      if(rc) return rc;
+    }
+  }
+  return SSD_OK;
+}
+
+int ssd_process_host_clearance(ssd_handle *h, const void *frames, int nframes, int input, const ssd_clearance_rule *rule, int min_support,
+                               ssd_frame_result *results, ssd_frame_moments *moments, uint8_t *mask, ssd_frame_clearance *out)
+{
+  const int rc = check_host_batch(h, "ssd_process_host_clearance", h && frames && results && out, nframes, input, kHandleCal);
+  return rc ? rc : process_host_clearance_impl(h, "ssd_process_host_clearance", frames, nframes, nullptr, input, rule, min_support, results, moments, mask, out);
+}
+
+int ssd_process_host_cameras_clearance(ssd_handle *h, const void *frames, int nframes, const uint16_t *camera_of_frame, int input,
+                                       const ssd_clearance_rule *rule, int min_support, ssd_frame_result *results, ssd_frame_moments *moments,
+                                       uint8_t *mask, ssd_frame_clearance *out)
+{
+  const int rc = check_host_batch(h, "ssd_process_host_cameras_clearance", h && frames && results && out, nframes, input, kCameraTable, camera_of_frame);
+  return rc ? rc : process_host_clearance_impl(h, "ssd_process_host_cameras_clearance", frames, nframes, camera_of_frame, input, rule, min_support, results,
+                                               moments, mask, out);
 }
 
 /* ---- riser fit (include/ssd_hip.h): host side ------------------------------------------------------------ */

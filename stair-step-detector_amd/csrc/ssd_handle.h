@@ -190,6 +190,7 @@ struct ssd_handle
   bool wholeDepth = false;                  /* its input was 16-bit depth */
   const void *wholeFrames = nullptr;        /* its frames and their stride */
   size_t wholeStride = 0;
+  const ssd_frame_result *wholeResults = nullptr;   /* its result records as the kernels address them (the slot k_final wrote) */
   /* the gates of a call, made on the first one, so a handle that never refits holds none of them.  One set, like the ground fit's */
   ssd::DeviceBuf<ssd_frame_gates> dRefitGates;   /* F */
   ssd::PinnedBuf<ssd_frame_gates> hRefitGates;   /* pinned: the caller's gates are copied here during the call */
@@ -201,6 +202,12 @@ struct ssd_handle
   /* the camera fold (ssd_enqueue_cameras_surface_refit_folded, ssd_process_host_cameras_drift): SSD_MAX_CAMERAS
    * records, made on the first call of either.  One set: the refit orders its users as it orders the device gates' */
   ssd::DeviceBuf<ssd_camera_fold> dCamFold;
+  /* the tread clearance pass (ssd_enqueue_clearance): events only, made on the first call - the pass writes the
+   * caller's buffers and owns none.  Passes on different streams are ordered by clearDone, so that the last one's event covers all */
+  ssd::Event clearDone;                     /* behind the pass */
+  hipStream_t clearLastStream = nullptr;
+  std::vector<ssd::Event> evClear;          /* both or none: around the pass of a timed call, made on the first one */
+  bool clearHaveLast = false, clearTimed = false;
 };
 
 /* The single pass's planes - dPlaneImg and dFallback of every workspace and the pinned hFallback, zeroed - for ALL workspaces of the

@@ -66,3 +66,6 @@ void launch_surface_refit(const Batch &B, int chunkPoints, const ssd_frame_gates
 }
 
 } // namespace ssd
+
+/* the other pass behind a whole enqueue, the tread clearance, in this translation unit: one parse of ssd_kernels.hip */
+#include "ssd_kernels_clearance.hip"

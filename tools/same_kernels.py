@@ -21,6 +21,11 @@ Prints a line per translation unit and a verdict; exit status 0 only for "identi
 the pattern matches may differ; for each that does, the two resource rows are printed in the form of tools/riser_labels_kernel_resources.py
 (VGPR, AGPR, SGPR, LDS, scratch, waves per SIMD, code size), and it still counts as DIFFERENT if it has scratch, other LDS bytes than in A
 or fewer waves per SIMD than in A.  Exit status 0 only if every other symbol is identical and the symbol sets are equal.
+
+    python tools/same_kernels.py PARENT/libssd_hip.so THIS/libssd_hip.so --new '^k_clearance' > profiles/clearance_same_kernels.txt
+
+--new REGEX: for a change that ADDS kernels to a translation unit.  A symbol that only B holds and whose demangled name the pattern matches
+is listed with its resource row and does not make the sets differ; every symbol of A must still be there, identical.
 """
 import os
 import re
@@ -139,8 +144,8 @@ def waves(k):
     return int(ckr.occupancy(k).split("w/SIMD")[0])
 
 
-def compare(a, b, may_differ=None):
-    """-> (lines, symbols that differ and may not, whether the sets of symbols differ); may_differ: a compiled pattern (see above)"""
+def compare(a, b, may_differ=None, new=None):
+    """-> (lines, symbols that differ and may not, whether the sets of symbols differ); may_differ, new: compiled patterns (see above)"""
     lines, differ, sets = [], 0, False
     if len(a) != len(b):
         sa, sb = set().union(*[set(u[0]) for u in a] or [set()]), set().union(*[set(u[0]) for u in b] or [set()])
@@ -151,6 +156,8 @@ def compare(a, b, may_differ=None):
         only_a, only_b = sorted(set(ua[0]) - set(ub[0])), sorted(set(ub[0]) - set(ua[0]))
         only_a += [k for k in sorted(set(ua[1]) - set(ub[1])) if k not in only_a]
         only_b += [k for k in sorted(set(ub[1]) - set(ua[1])) if k not in only_b]
+        added = [k for k in only_b if new and new.search(ckr.short(ckr.demangle([k])[k]))]
+        only_b = [k for k in only_b if k not in added]
         bad, allowed = [], []
         for s in sorted(set(ua[0]) & set(ub[0])):
             what = []
@@ -182,6 +189,8 @@ def compare(a, b, may_differ=None):
             lines.append("    only in A: " + s)
         for s in only_b:
             lines.append("    only in B: " + s)
+        for s in added:
+            lines.append("    new in B: %-46s %s" % (ckr.short(ckr.demangle([s])[s])[:46], row(resources(ub[1].get(s), ub[0].get(s, [])))))
         for s in allowed:
             lines.append("    may differ: " + s)
         for s in bad:
@@ -192,19 +201,27 @@ def compare(a, b, may_differ=None):
 
 
 def main():
-    argv, pattern = sys.argv[1:], None
+    argv, pattern, new = sys.argv[1:], None, None
     if "--may-differ" in argv[:-1]:
         at = argv.index("--may-differ")
         pattern = re.compile(argv[at + 1])
+        del argv[at:at + 2]
+    if "--new" in argv[:-1]:
+        at = argv.index("--new")
+        new = re.compile(argv[at + 1])
         del argv[at:at + 2]
     if len(argv) != 2:
         sys.exit(__doc__)
     if not tools_present():
         sys.exit("the ROCm llvm tools (%s) are not under %s" % (", ".join(TOOLS), LLVM))
     a, b = units(argv[0]), units(argv[1])
-    lines, differ, sets = compare(a, b, pattern)
+    lines, differ, sets = compare(a, b, pattern, new)
     allowed = sum(1 for l in lines if l.startswith("    may differ: "))
+    added = sum(1 for l in lines if l.startswith("    new in B: "))
     print("# device code of two builds, %s code objects, symbol by symbol: A = %s | B = %s" % (ARCH, argv[0], argv[1]))
+    if new:
+        print("# new in B: %s; their rows: v = VGPRs, a = AGPRs, s = SGPRs, lds / scr = bytes of LDS / scratch per workgroup / lane," % new.pattern)
+        print("# occupancy by arithmetic (tools/cameras_kernel_resources.py), code = bytes of the symbol's instructions")
     if pattern:
         print("# may differ: %s; their rows A | B: v = VGPRs, a = AGPRs, s = SGPRs, lds / scr = bytes of LDS / scratch per workgroup / lane," % pattern.pattern)
         print("# occupancy by arithmetic (tools/cameras_kernel_resources.py), code = bytes of the symbol's instructions")
@@ -216,6 +233,9 @@ def main():
     elif allowed:
         print("verdict: identical but for %d symbols that may differ, each without scratch, with A's LDS bytes and no fewer waves per SIMD (%d symbols in all)"
               % (allowed, sum(len(u[0]) for u in a)))
+    elif added:
+        print("verdict: every symbol of A identical (%d translation units, %d kernels, every instruction, encoding and metadata record); %d new symbols in B"
+              % (len(a), sum(len(u[1]) for u in a), added))
     else:
         print("verdict: identical (%d translation units, %d kernels, every instruction, encoding and metadata record)" % (len(a), sum(len(u[1]) for u in a)))
     return 1 if (sets or differ) else 0
