@@ -919,6 +919,108 @@ int ssd_process_host_cameras_clearance(ssd_handle *h, const void *frames, int nf
                                        const ssd_clearance_rule *rule, int min_support, ssd_frame_result *results,
                                        ssd_frame_moments *moments /* may be NULL */, uint8_t *mask /* may be NULL */, ssd_frame_clearance *out);
 
+/* ---- tread grid: free, occupied and unseen cells per tread, and a foothold ---------------------------------------------------------
+ * EXTENSION.  A clearance record is one centroid per tread: it cannot say WHERE on the tread to step.  Two
+ * objects give a centroid between them; an occupant hides the tread behind it, which is then neither occupied nor known to be free; and
+ * whether something can be stepped over is a maximum, not a sum.  This pass lays a small top-down grid over every reported surface, in
+ * the surface's own frame - SSD_TG_COLS cells along its front edge, SSD_TG_ROWS behind it - and counts per cell the tread points seen
+ * there, the occupants there, and the tallest occupant.  The rule is stated on public data only, in doubles without FMA contraction, in
+ * the order written; sqrt and / are correctly rounded; one text for host and device (csrc/ssd_treadgrid.h, on csrc/ssd_clearance.h).
+ * A frame whose status has SSD_ST_THROW, or with n_steps == 0, gives a record that is zero apart from its header.  Otherwise
+ *   1. validity and range are item 1 of the clearance rule; ex, ey, ez as in its item 2;
+ *   2. a point is an OCCUPANT of surface k exactly as ssd_enqueue_clearance decides under rule.clearance (its items 3 and 4);
+ *   3. otherwise it is a TREAD POINT of surface k iff k is the lowest index with !(fabs(ez - steps[k].height) > lo) and (ex, ey) inside
+ *      surface k's quadrilateral shrunk by margin (the clearance rule's test).  No point is both;
+ *   4. its cell on surface k: side 0 of the ring (FL -> FR) x0, y0, dx, dy, o as the clearance rule has them, L = sqrt(dx dx + dy dy);
+ *      the grid is live iff o != 0 && L > 0;  ax = ex - x0, ay = ey - y0;  u = (dx ax + dy ay) / L;  v = (o (dx ay - dy ax)) / L
+ *      (behind the front edge, positive inside for either ring orientation);  u0 = the least u of the ring's corners: 0 for FL, then
+ *      if(ui < u0) u0 = ui for FR, BR, BL;  c = floor((u - u0) / cell), r = floor(v / cell) as doubles; in the grid iff
+ *      c >= 0 && c < SSD_TG_COLS && r >= 0 && r < SSD_TG_ROWS, compared as doubles before any conversion (a NaN is out);
+ *   5. a tread point in the grid adds 1 to seen[r][c], outside it (or on a grid that is not live) to n_seen_out; an occupant adds 1 to
+ *      occ[r][c] or n_occ_out and raises top[r][c] or top_out to (int32_t)rint((ez - steps[k].height) 65536): units of 2^-16 m.
+ * So for every frame and surface sum(occ) + n_occ_out equals n + n_far of the clearance record under the same rule.
+ * Out of scope: ssd_pipeline_* and ssd_enqueue_stages; a mask; grids that follow a tread's curved sides; objects lower than lo. */
+#define SSD_TG_COLS 32   /* cells along the front edge */
+#define SSD_TG_ROWS 8    /* cells behind it */
+typedef struct
+{
+  ssd_clearance_rule clearance;
+  double cell;        /* [0.005, 1] m: a cell's side */
+} ssd_tread_grid_rule;
+
+typedef struct
+{
+  uint32_t n_seen_out, n_occ_out;   /* tread points / occupants of the surface that fall outside the grid */
+  int32_t top_out, reserved;        /* the tallest of those occupants (units of 2^-16 m), 0 if none */
+  uint32_t seen[SSD_TG_ROWS][SSD_TG_COLS];
+  uint32_t occ[SSD_TG_ROWS][SSD_TG_COLS];
+  int32_t top[SSD_TG_ROWS][SSD_TG_COLS];
+} ssd_tread_grid;                   /* 3088 bytes */
+
+typedef struct
+{
+  int32_t n_surfaces, ground;       /* as the clearance record's */
+  ssd_tread_grid s[SSD_MAX_STEPS];
+} ssd_frame_tread_grid;             /* 52504 bytes */
+
+#define SSD_TG_OUT 0        /* the cell's centre is not inside the shrunk quadrilateral */
+#define SSD_TG_FREE 1       /* tread seen, nothing on it */
+#define SSD_TG_OCCUPIED 2
+#define SSD_TG_UNSEEN 3     /* inside, but neither: hidden behind an occupant, or no data */
+typedef struct
+{
+  uint8_t state[SSD_TG_ROWS][SSD_TG_COLS];
+  int32_t n_free, n_occupied, n_unseen;
+  int32_t foothold;                 /* 1: the rectangle below exists */
+  int32_t col0, row0, cols, rows;   /* the best free rectangle, in cells (all 0 without a foothold) */
+  double tallest;                   /* the tallest occupant of the surface, metres above it (0: none) */
+  double centre[2];                 /* the rectangle's centre, external world x, y */
+  double size[2];                   /* cols cell, rows cell: metres along the front edge and behind it */
+} ssd_foothold;                     /* 328 bytes */
+
+typedef struct
+{
+  int32_t n_surfaces, ground;
+  ssd_foothold s[SSD_MAX_STEPS];
+} ssd_frame_footholds;
+
+/* The pass alone (k_tread_grid), against the workspace of the handle's last WHOLE enqueue, behind it on that batch's stream and in front
+ * of a completion event of its own - every check, stream rule and withdrawal of ssd_enqueue_clearance (ssd_enqueue_cameras_tread_grid: of
+ * ssd_enqueue_cameras_clearance; frame i is byte for byte a one-camera handle's).  d_out: nframes contiguous records in device memory,
+ * zeroed on the stream in front of the kernel; records past nframes are not written.  It may be repeated, with other rules, until the
+ * next enqueue takes the workspace.  The first call makes events only: ssd_workspace_bytes does not move, and a handle that never calls
+ * it allocates and launches nothing.  SSD_E_ARG before anything is launched: the refit's refusals, a null rule or destination, a
+ * clearance rule outside its ranges, cell outside [0.005, 1] or NaN. */
+int ssd_enqueue_tread_grid(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream, int input,
+                           const ssd_tread_grid_rule *rule, ssd_frame_tread_grid *d_out);
+int ssd_enqueue_cameras_tread_grid(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream, int input,
+                                   const ssd_tread_grid_rule *rule, ssd_frame_tread_grid *d_out);
+/* waits for the last tread grid pass (SSD_E_ARG: there was none) */
+int ssd_fetch_tread_grid(ssd_handle *h, void *stream);
+/* the device time of the last tread grid pass, the zeroing in front of it included (0 when timing was off for it) */
+int ssd_get_tread_grid_time(ssd_handle *h, float *ms);
+/* host only, no GPU needed: one frame's grids by the shared text.  Arguments and refusals as ssd_clearance_host's (out may not be NULL),
+ * plus the rule's cell. */
+int ssd_tread_grid_host(const ssd_config *cfg, const ssd_calibration *cal, int input, const ssd_intrinsics *intr, const void *frame,
+                        const ssd_frame_result *result, int ground, const ssd_tread_grid_rule *rule, ssd_frame_tread_grid *out);
+/* host only: a frame's grids -> the state of every cell and a foothold per surface k < n_surfaces.  A cell is OUT iff its centre, mapped
+ * back by FL + ((u0 + (c + .5) cell) / L) e + (((r + .5) cell) / L) o (-dy, dx), is not inside the shrunk quadrilateral; else OCCUPIED
+ * iff occ >= max(min_occ, 1); else FREE iff seen >= max(min_seen, 1); else UNSEEN.  tallest = max(top, top_out) / 65536.  The best
+ * rectangle is the all-FREE axis-aligned rectangle of the largest area with cols >= ceil(foot_along / cell) and rows >=
+ * ceil(foot_deep / cell) (a foot size of 0: at least one cell); ties go to the smallest row0, then the smallest col0, then the most
+ * cols; none: foothold = 0 and the rectangle's fields are zero.  Records at k >= n_surfaces are zero.  SSD_E_ARG: a null pointer,
+ * n_surfaces outside 0 .. SSD_MAX_STEPS, a rule outside its ranges, a negative or NaN foot size. */
+int ssd_tread_grid_solve(const ssd_frame_tread_grid *grid, const ssd_frame_result *result, const ssd_tread_grid_rule *rule, int min_seen,
+                         int min_occ, double foot_along, double foot_deep, ssd_frame_footholds *out);
+/* frames in host memory through the slices of ssd_process_host (ssd_process_host_cameras): per slice enqueue, pass, fetch, solve.  Fills
+ * results[nframes] (byte for byte ssd_process_host's / ssd_process_host_cameras'), out[nframes] and, when not NULL, grids[nframes]. */
+int ssd_process_host_tread_grid(ssd_handle *h, const void *frames, int nframes, int input, const ssd_tread_grid_rule *rule, int min_seen,
+                                int min_occ, double foot_along, double foot_deep, ssd_frame_result *results,
+                                ssd_frame_tread_grid *grids /* may be NULL */, ssd_frame_footholds *out);
+int ssd_process_host_cameras_tread_grid(ssd_handle *h, const void *frames, int nframes, const uint16_t *camera_of_frame, int input,
+                                        const ssd_tread_grid_rule *rule, int min_seen, int min_occ, double foot_along, double foot_deep,
+                                        ssd_frame_result *results, ssd_frame_tread_grid *grids /* may be NULL */, ssd_frame_footholds *out);
+
 /* stage selector for profiling / roofline measurement: runs only the chosen stage(s) of the pipeline */
 #define SSD_STAGE_HIST 1       /* K1: transform + crop + bin + histogram */
 #define SSD_STAGE_PEAKS 2

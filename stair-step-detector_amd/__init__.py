@@ -201,6 +201,43 @@ class FrameClearance(C.Structure):
     _fields_ = [("n_surfaces", C.c_int32), ("ground", C.c_int32), ("s", Clearance * MAX_STEPS)]
 
 
+TG_COLS, TG_ROWS = 32, 8
+TG_OUT, TG_FREE, TG_OCCUPIED, TG_UNSEEN = 0, 1, 2, 3
+
+
+class TreadGridRule(C.Structure):
+    """ssd_tread_grid_rule: the clearance rule that decides which points stand on which surface, and the side of a grid cell, metres
+    (tread grid)"""
+    _fields_ = [("clearance", ClearanceRule), ("cell", C.c_double)]
+
+    def __init__(self, margin=0.03, lo=0.03, hi=0.5, cell=0.02):
+        super().__init__(ClearanceRule(margin, lo, hi), float(cell))
+
+
+class TreadGrid(C.Structure):
+    """ssd_tread_grid: one surface's grid - per cell [row behind the front edge][column along it] the tread points seen, the occupants
+    and the tallest occupant (units of 2^-16 m); the *_out fields hold what falls outside the grid"""
+    _fields_ = [("n_seen_out", C.c_uint32), ("n_occ_out", C.c_uint32), ("top_out", C.c_int32), ("reserved", C.c_int32),
+                ("seen", C.c_uint32 * TG_COLS * TG_ROWS), ("occ", C.c_uint32 * TG_COLS * TG_ROWS), ("top", C.c_int32 * TG_COLS * TG_ROWS)]
+
+
+class FrameTreadGrid(C.Structure):
+    """ssd_frame_tread_grid: the grids of every surface of a frame"""
+    _fields_ = [("n_surfaces", C.c_int32), ("ground", C.c_int32), ("s", TreadGrid * MAX_STEPS)]
+
+
+class Foothold(C.Structure):
+    """ssd_foothold: one surface's cells (TG_OUT / TG_FREE / TG_OCCUPIED / TG_UNSEEN) and the best free rectangle on it"""
+    _fields_ = [("state", C.c_uint8 * TG_COLS * TG_ROWS), ("n_free", C.c_int32), ("n_occupied", C.c_int32), ("n_unseen", C.c_int32),
+                ("foothold", C.c_int32), ("col0", C.c_int32), ("row0", C.c_int32), ("cols", C.c_int32), ("rows", C.c_int32),
+                ("tallest", C.c_double), ("centre", C.c_double * 2), ("size", C.c_double * 2)]
+
+
+class FrameFootholds(C.Structure):
+    """ssd_frame_footholds: the cells and the foothold of every surface of a frame"""
+    _fields_ = [("n_surfaces", C.c_int32), ("ground", C.c_int32), ("s", Foothold * MAX_STEPS)]
+
+
 MAX_RISERS = MAX_STEPS - 1
 
 
@@ -275,6 +312,8 @@ EXPORTS = [
     "ssd_set_riser_labels", "ssd_get_riser_labels_time_back", "ssd_labels_split",
     "ssd_enqueue_clearance", "ssd_enqueue_cameras_clearance", "ssd_fetch_clearance", "ssd_get_clearance_time", "ssd_clearance_host",
     "ssd_clearance_solve", "ssd_process_host_clearance", "ssd_process_host_cameras_clearance",
+    "ssd_enqueue_tread_grid", "ssd_enqueue_cameras_tread_grid", "ssd_fetch_tread_grid", "ssd_get_tread_grid_time", "ssd_tread_grid_host",
+    "ssd_tread_grid_solve", "ssd_process_host_tread_grid", "ssd_process_host_cameras_tread_grid",
 ]
 # libssd_source.so — the frame source standing in for the camera (include/ssd_source.h)
 SOURCE_EXPORTS = [
@@ -388,6 +427,18 @@ def lib():
                                              C.POINTER(FrameClearance)]
     L.ssd_process_host_cameras_clearance.argtypes = [vp, vp, i32, C.POINTER(C.c_uint16), i32, C.POINTER(ClearanceRule), i32, C.POINTER(FrameResult),
                                                      C.POINTER(FrameMoments), vp, C.POINTER(FrameClearance)]
+    L.ssd_enqueue_tread_grid.argtypes = [vp, vp, sz, i32, vp, i32, C.POINTER(TreadGridRule), vp]
+    L.ssd_enqueue_cameras_tread_grid.argtypes = L.ssd_enqueue_tread_grid.argtypes
+    L.ssd_fetch_tread_grid.argtypes = [vp, vp]
+    L.ssd_get_tread_grid_time.argtypes = [vp, C.POINTER(C.c_float)]
+    L.ssd_tread_grid_host.argtypes = [C.POINTER(Config), C.POINTER(Calibration), i32, C.POINTER(Intrinsics), vp, C.POINTER(FrameResult), i32,
+                                      C.POINTER(TreadGridRule), C.POINTER(FrameTreadGrid)]
+    L.ssd_tread_grid_solve.argtypes = [C.POINTER(FrameTreadGrid), C.POINTER(FrameResult), C.POINTER(TreadGridRule), i32, i32, C.c_double, C.c_double,
+                                       C.POINTER(FrameFootholds)]
+    L.ssd_process_host_tread_grid.argtypes = [vp, vp, i32, i32, C.POINTER(TreadGridRule), i32, i32, C.c_double, C.c_double, C.POINTER(FrameResult),
+                                              C.POINTER(FrameTreadGrid), C.POINTER(FrameFootholds)]
+    L.ssd_process_host_cameras_tread_grid.argtypes = [vp, vp, i32, C.POINTER(C.c_uint16), i32, C.POINTER(TreadGridRule), i32, i32, C.c_double, C.c_double,
+                                                      C.POINTER(FrameResult), C.POINTER(FrameTreadGrid), C.POINTER(FrameFootholds)]
     L.ssd_enqueue_cameras_surface_refit_folded.argtypes = [vp, vp, sz, i32, vp, i32, vp, i32, C.c_double, C.c_double, i32, vp]
     L.ssd_camera_drift_from_fold.argtypes = [C.POINTER(CameraFold), C.POINTER(Camera), i32, i32, C.POINTER(CameraDrift)]
     L.ssd_process_host_cameras_drift.argtypes = [vp, vp, i32, C.POINTER(C.c_uint16), i32, C.POINTER(FrameResult), i32, C.c_double, C.c_double, i32, i32,
@@ -701,6 +752,30 @@ def clearance_solve(moments, result, cal, min_support=50):
     c = _calibration_of(cal)
     out = FrameClearance()
     _check(lib().ssd_clearance_solve(C.byref(moments), C.byref(result), C.byref(c), int(min_support), C.byref(out)))
+    return out
+
+
+def tread_grid_host(cfg, cal, frame, result, ground, rule=None, intr=None):
+    """ssd_tread_grid_host: one frame's grids by the rule of DESIGN.md section 7n -> FrameTreadGrid.  frame: float32 [H, W, 3], or
+    uint16 [H, W] with intr (16-bit depth input)."""
+    depth = intr is not None
+    a = np.ascontiguousarray(frame, dtype=np.uint16 if depth else np.float32)
+    if a.size != cfg.width * cfg.height * (1 if depth else 3):
+        raise SsdError("tread_grid_host: the array is not one frame")
+    rule = TreadGridRule() if rule is None else rule
+    c = _calibration_of(cal)
+    out = FrameTreadGrid()
+    _check(lib().ssd_tread_grid_host(C.byref(cfg), C.byref(c), INPUT_DEPTH16 if depth else INPUT_VERTICES, C.byref(intr) if depth else None,
+                                     a.ctypes.data_as(C.c_void_p), C.byref(result), int(ground), C.byref(rule), C.byref(out)))
+    return out
+
+
+def tread_grid_solve(grid, result, rule=None, min_seen=1, min_occ=1, foot_along=0.0, foot_deep=0.0):
+    """ssd_tread_grid_solve: a frame's grids -> every cell's state and the best free rectangle per surface (FrameFootholds)"""
+    rule = TreadGridRule() if rule is None else rule
+    out = FrameFootholds()
+    _check(lib().ssd_tread_grid_solve(C.byref(grid), C.byref(result), C.byref(rule), int(min_seen), int(min_occ), float(foot_along),
+                                      float(foot_deep), C.byref(out)))
     return out
 
 
@@ -1133,6 +1208,56 @@ class Detector:
     def process_host_cameras_clearance(self, frames, camera_of_frame, rule=None, min_support=50, depth=False, moments=False, mask=False):
         """ssd_process_host_cameras_clearance: process_host_clearance with one camera index per frame"""
         return self.process_host_clearance(frames, rule, min_support, depth, moments, mask, camera_of_frame=camera_of_frame)
+
+    # ---- tread grid (include/ssd_hip.h, DESIGN.md section 7n)
+    def enqueue_tread_grid(self, d_ptr, nframes, d_grids, rule=None, depth=False, stride_bytes=None, stream=None, cameras=False):
+        """ssd_enqueue_tread_grid: the tread grid pass alone, behind the handle's last whole enqueue of the same frames: frame i's
+        FrameTreadGrid at d_grids + i * sizeof(FrameTreadGrid), device memory; complete when fetch_tread_grid() returns"""
+        frame = self.cfg.width * self.cfg.height * (2 if depth else 12)
+        rule = TreadGridRule() if rule is None else rule
+        fn = lib().ssd_enqueue_cameras_tread_grid if cameras else lib().ssd_enqueue_tread_grid
+        _check(fn(self._h, C.c_void_p(d_ptr), stride_bytes or frame, nframes, C.c_void_p(stream or 0), INPUT_DEPTH16 if depth else INPUT_VERTICES,
+                  C.byref(rule), C.c_void_p(d_grids)))
+
+    def enqueue_cameras_tread_grid(self, d_ptr, nframes, d_grids, rule=None, depth=False, stride_bytes=None, stream=None):
+        """ssd_enqueue_cameras_tread_grid: enqueue_tread_grid behind the handle's last whole CAMERAS enqueue of the same frames"""
+        self.enqueue_tread_grid(d_ptr, nframes, d_grids, rule, depth, stride_bytes, stream, cameras=True)
+
+    def fetch_tread_grid(self, stream=None):
+        """ssd_fetch_tread_grid: waits for the last enqueue_tread_grid"""
+        _check(lib().ssd_fetch_tread_grid(self._h, C.c_void_p(stream or 0)))
+
+    def tread_grid_time_ms(self):
+        """Device time of the last tread grid pass (0.0: timing was off for it)"""
+        ms = C.c_float(0.0)
+        _check(lib().ssd_get_tread_grid_time(self._h, C.byref(ms)))
+        return ms.value
+
+    def process_host_tread_grid(self, frames, rule=None, min_seen=1, min_occ=1, foot_along=0.0, foot_deep=0.0, depth=False, grids=False,
+                                camera_of_frame=None):
+        """ssd_process_host_tread_grid: frames on the host (float32 [n, H, W, 3], or uint16 [n, H, W] with depth=True)
+        -> (list of FrameResult, list of FrameFootholds), with grids=True also the list of FrameTreadGrid"""
+        a = np.ascontiguousarray(frames, dtype=np.uint16 if depth else np.float32)
+        per = self.cfg.width * self.cfg.height * (1 if depth else 3)
+        n = a.size // per
+        if n < 1 or a.size != n * per:
+            raise SsdError("process_host_tread_grid: array does not hold whole frames")
+        rule = TreadGridRule() if rule is None else rule
+        res, out = (FrameResult * n)(), (FrameFootholds * n)()
+        g = (FrameTreadGrid * n)() if grids else None
+        tail = (C.byref(rule), int(min_seen), int(min_occ), float(foot_along), float(foot_deep), res, g, out)
+        inp = INPUT_DEPTH16 if depth else INPUT_VERTICES
+        if camera_of_frame is None:
+            _check(lib().ssd_process_host_tread_grid(self._h, a.ctypes.data_as(C.c_void_p), n, inp, *tail))
+        else:
+            idx = self._camera_index(camera_of_frame, n)
+            _check(lib().ssd_process_host_cameras_tread_grid(self._h, a.ctypes.data_as(C.c_void_p), n, idx.ctypes.data_as(C.POINTER(C.c_uint16)), inp, *tail))
+        return (list(res), list(out), list(g)) if grids else (list(res), list(out))
+
+    def process_host_cameras_tread_grid(self, frames, camera_of_frame, rule=None, min_seen=1, min_occ=1, foot_along=0.0, foot_deep=0.0, depth=False,
+                                        grids=False):
+        """ssd_process_host_cameras_tread_grid: process_host_tread_grid with one camera index per frame"""
+        return self.process_host_tread_grid(frames, rule, min_seen, min_occ, foot_along, foot_deep, depth, grids, camera_of_frame=camera_of_frame)
 
     # ---- surface fit of cameras batches, drift per camera (include/ssd_hip.h, DESIGN.md section 7e)
     def enqueue_cameras_surface_moments(self, d_ptr, nframes, camera_of_frame, d_moments, depth=False, stride_bytes=None, stream=None):

@@ -11,6 +11,7 @@
 #include "ssd_ground.h"
 #include "ssd_refit.h"
 #include "ssd_clearance.h"
+#include "ssd_treadgrid.h"
 #include "ssd_solve.h"
 #include "ssd_fold.h"
 
@@ -3025,6 +3026,377 @@ int ssd_process_host_cameras_clearance(ssd_handle *h, const void *frames, int nf
   const int rc = check_host_batch(h, "ssd_process_host_cameras_clearance", h && frames && results && out, nframes, input, kCameraTable, camera_of_frame);
   return rc ? rc : process_host_clearance_impl(h, "ssd_process_host_cameras_clearance", frames, nframes, camera_of_frame, input, rule, min_support, results,
                                                moments, mask, out);
+}
+
+/* ---- tread grid (include/ssd_hip.h) ----------------------------------------------------------------------- */
+
+static int check_tread_grid_rule(const std::string &who, const ssd_tread_grid_rule *rule)
+{
+  if(!rule)
+    return fail(SSD_E_ARG, who + ": null rule");
+  const int rc = check_clearance_rule(who, &rule->clearance);
+  if(rc) return rc;
+  if(!tread_grid_rule_ok(*rule))
+    return fail(SSD_E_ARG, who + ": the rule must have cell in [0.005, 1]");
+  return SSD_OK;
+}
+
+/* host only: the rule of ssd_treadgrid.h over one frame, point by point in the order of the text */
+int ssd_tread_grid_host(const ssd_config *cfg, const ssd_calibration *cal, int input, const ssd_intrinsics *intr, const void *frame,
+                        const ssd_frame_result *result, int ground, const ssd_tread_grid_rule *rule, ssd_frame_tread_grid *out)
+{
+  const std::string who("ssd_tread_grid_host");
+  if(!cfg || !cal || !frame || !result || !out || cfg->width <= 0 || cfg->height <= 0)
+    return fail(SSD_E_ARG, who + ": bad argument");
+  if(input != SSD_INPUT_VERTICES && input != SSD_INPUT_DEPTH16)
+    return fail(SSD_E_ARG, who + ": input must be SSD_INPUT_VERTICES or SSD_INPUT_DEPTH16");
+  const bool depth = input == SSD_INPUT_DEPTH16;
+  if(depth && (!intr || !good_intrinsics(*intr)))
+    return fail(SSD_E_ARG, who + ": depth input needs intrinsics");
+  if(result->n_steps < 0 || result->n_steps > SSD_MAX_STEPS)
+    return fail(SSD_E_ARG, who + ": n_steps must lie in 0 .. SSD_MAX_STEPS");
+  int rc = check_tread_grid_rule(who, rule);
+  if(rc) return rc;
+  const int W = cfg->width, H = cfg->height;
+  const size_t nPoints = static_cast<size_t>(W) * H;
+  std::vector<float> deprojected;
+  const float *xyz = static_cast<const float *>(frame);
+  if(depth)
+  {
+    deprojected.resize(3 * nPoints);
+    rc = ssd_deproject_host(intr, W, H, static_cast<const uint16_t *>(frame), deprojected.data());
+    if(rc) return rc;
+    xyz = deprojected.data();
+  }
+  std::memset(out, 0, sizeof(*out));
+  const int n = (result->status & SSD_ST_THROW) ? 0 : result->n_steps;
+  if(n == 0)
+    return SSD_OK;                               /* nothing counted: an all-zero record, as the clearance moments' */
+  out->n_surfaces = n;
+  out->ground = ground ? 1 : 0;
+  const double lo = rule->clearance.lo, hi = rule->clearance.hi;
+  ClearanceSurface S[SSD_MAX_STEPS];
+  TreadGridAxes G[SSD_MAX_STEPS];
+  for(int k = 0; k < n; k++)
+  {
+    clearance_surface(result->steps[k], rule->clearance.margin, S[k]);
+    tread_grid_axes(S[k], G[k]);
+  }
+  const ClearanceWorld X{ { cal->r2[0], cal->r2[1], cal->r2[2], cal->r2[3] }, { cal->t2[0], cal->t2[1] }, cal->world_z };
+  const double *a = cal->a, *b = cal->b;
+  const unsigned int all = (1u << n) - 1u;       /* every surface is a candidate; n <= 17 */
+  for(size_t i = 0; i < nPoints; i++)
+  {
+    const float fx = xyz[3 * i], fy = xyz[3 * i + 1], fz = xyz[3 * i + 2];
+    if(!(fz > 0.0f))
+      continue;
+    const double x = fx, y = fy, z = fz;
+    const double wx = ((a[0] * x + a[1] * y) + a[2] * z) + b[0];
+    const double wy = ((a[3] * x + a[4] * y) + a[5] * z) + b[1];
+    const double wz = ((a[6] * x + a[7] * y) + a[8] * z) + b[2];
+    if(!(wx > cfg->x_min && wx < cfg->x_max && wy > cfg->y_min && wy < cfg->y_max && wz > cfg->z_min && wz < cfg->z_max))
+      continue;
+    const double ez = wz + X.worldZ;
+    double ex, ey;
+    clearance_external(X, wx, wy, ex, ey);
+    const bool tread = clearance_in_slab(S, n, ez, lo);
+    const int k = tread ? tread_grid_lowest(S, all, ex, ey, ez, lo) : clearance_lowest(S, all, ex, ey, ez, lo, hi);
+    if(k < 0)
+      continue;
+    ssd_tread_grid &g = out->s[k];
+    int row, col;
+    const bool in = tread_grid_cell(G[k], rule->cell, ex, ey, row, col);
+    if(tread)
+      (in ? g.seen[row][col] : g.n_seen_out) += 1u;
+    else
+    {
+      (in ? g.occ[row][col] : g.n_occ_out) += 1u;
+      const int32_t t = tread_grid_top(ez, S[k].height);
+      int32_t &top = in ? g.top[row][col] : g.top_out;
+      if(t > top)
+        top = t;
+    }
+  }
+  return SSD_OK;
+}
+
+int ssd_tread_grid_solve(const ssd_frame_tread_grid *grid, const ssd_frame_result *result, const ssd_tread_grid_rule *rule, int min_seen,
+                         int min_occ, double foot_along, double foot_deep, ssd_frame_footholds *out)
+{
+  const std::string who("ssd_tread_grid_solve");
+  if(!grid || !result || !out)
+    return fail(SSD_E_ARG, who + ": null");
+  if(grid->n_surfaces < 0 || grid->n_surfaces > SSD_MAX_STEPS)
+    return fail(SSD_E_ARG, who + ": n_surfaces must lie in 0 .. SSD_MAX_STEPS");
+  const int rc = check_tread_grid_rule(who, rule);
+  if(rc) return rc;
+  if(!(foot_along >= 0.0) || !(foot_deep >= 0.0))
+    return fail(SSD_E_ARG, who + ": a foot size must be 0 or more");
+  std::memset(out, 0, sizeof(*out));
+  out->n_surfaces = grid->n_surfaces;
+  out->ground = grid->ground;
+  const double cell = rule->cell;
+  /* the least rectangle that holds the foot, in cells (as doubles: a foot no grid holds finds nothing) */
+  const double needCols = std::fmax(std::ceil(foot_along / cell), 1.0), needRows = std::fmax(std::ceil(foot_deep / cell), 1.0);
+  const uint32_t minSeen = min_seen > 1 ? static_cast<uint32_t>(min_seen) : 1u, minOcc = min_occ > 1 ? static_cast<uint32_t>(min_occ) : 1u;
+  for(int k = 0; k < grid->n_surfaces; k++)
+  {
+    const ssd_tread_grid &g = grid->s[k];
+    ssd_foothold &f = out->s[k];
+    ClearanceSurface S;
+    TreadGridAxes G;
+    clearance_surface(result->steps[k], rule->clearance.margin, S);
+    tread_grid_axes(S, G);
+    int32_t top = g.top_out;
+    for(int r = 0; r < SSD_TG_ROWS; r++)
+      for(int c = 0; c < SSD_TG_COLS; c++)
+      {
+        double x, y;
+        tread_grid_world(G, cell, r + 0.5, c + 0.5, x, y);
+        uint8_t s = SSD_TG_UNSEEN;
+        if(!G.live || !clearance_inside(S, x, y))
+          s = SSD_TG_OUT;
+        else if(g.occ[r][c] >= minOcc)
+          s = SSD_TG_OCCUPIED;
+        else if(g.seen[r][c] >= minSeen)
+          s = SSD_TG_FREE;
+        f.state[r][c] = s;
+        f.n_free += s == SSD_TG_FREE;
+        f.n_occupied += s == SSD_TG_OCCUPIED;
+        f.n_unseen += s == SSD_TG_UNSEEN;
+        if(g.top[r][c] > top)
+          top = g.top[r][c];
+      }
+    f.tallest = static_cast<double>(top) / 65536.0;
+    /* the largest all-FREE rectangle: for every first row and height the columns free in all its rows, and their maximal runs - the
+     * best rectangle is a maximal run of its rows (a shorter one has less area).  Ties: the smallest row0 (the outer loop's order
+     * with a strict comparison), then the smallest col0, then the most cols */
+    int bestArea = 0;
+    for(int r0 = 0; r0 < SSD_TG_ROWS; r0++)
+    {
+      bool freeCol[SSD_TG_COLS];
+      for(int c = 0; c < SSD_TG_COLS; c++)
+        freeCol[c] = true;
+      for(int rows = 1; r0 + rows <= SSD_TG_ROWS; rows++)
+      {
+        for(int c = 0; c < SSD_TG_COLS; c++)
+          freeCol[c] = freeCol[c] && f.state[r0 + rows - 1][c] == SSD_TG_FREE;
+        if(static_cast<double>(rows) < needRows)
+          continue;
+        for(int c = 0; c < SSD_TG_COLS;)
+        {
+          if(!freeCol[c])
+          {
+            c++;
+            continue;
+          }
+          int end = c;
+          while(end < SSD_TG_COLS && freeCol[end])
+            end++;
+          const int cols = end - c, area = cols * rows;
+          if(static_cast<double>(cols) >= needCols)
+          {
+            const bool better = area > bestArea
+              || (area == bestArea && r0 == f.row0 && (c < f.col0 || (c == f.col0 && cols > f.cols)));
+            if(better)
+            {
+              bestArea = area;
+              f.row0 = r0; f.col0 = c; f.rows = rows; f.cols = cols;
+            }
+          }
+          c = end;
+        }
+      }
+    }
+    if(bestArea > 0)
+    {
+      f.foothold = 1;
+      tread_grid_world(G, cell, f.row0 + 0.5 * f.rows, f.col0 + 0.5 * f.cols, f.centre[0], f.centre[1]);
+      f.size[0] = f.cols * cell;
+      f.size[1] = f.rows * cell;
+    }
+  }
+  return SSD_OK;
+}
+
+static const BehindWhole kTreadGridBehind{ "grid", "ssd_enqueue_tread_grid", "ssd_enqueue_cameras_tread_grid" };
+
+/* both entry points of the pass: its own refusals, then the refit's (check_behind_whole), before anything is launched */
+static int tread_grid_enqueue_impl(ssd_handle *h, const char *who, bool cameras, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream,
+                                   int input, const ssd_tread_grid_rule *rule, ssd_frame_tread_grid *d_out)
+{
+  const std::string me(who);
+  if(!h || !d_frames || !d_out)
+    return fail(SSD_E_ARG, me + ": null argument");
+  int rc = check_tread_grid_rule(me, rule);
+  if(rc) return rc;
+  rc = check_behind_whole(h, me, kTreadGridBehind, cameras, d_frames, frame_stride_bytes, nframes, input);
+  if(rc) return rc;
+  if(!h->wholeResults)
+    return fail(SSD_E_HIP, me + ": the last enqueue's result records are missing (internal)");
+  const bool depthInput = input == SSD_INPUT_DEPTH16;
+  ssd_lane &L = h->lane[h->lastLane];
+  HIP_TRY(hipSetDevice(h->device));
+  if(!h->gridDone)
+  {
+    Event done;
+    const hipError_t e = done.create(hipEventDisableTiming);
+    if(e != hipSuccess)
+      return hip_fail(e, me + ": its event: ");
+    h->gridDone = std::move(done);
+  }
+  const bool timing = h->timing && !h->ev.empty();
+  if(timing && h->evGrid.empty())
+    HIP_TRY(make_events(h->evGrid, 2, hipEventDefault));
+  hipStream_t s;
+  rc = stream_behind_whole(h, L, stream, s);
+  if(rc) return rc;
+  /* a pass on another stream than the one before goes behind it: the last pass's event then covers every pass so far */
+  if(h->gridHaveLast && s != h->gridLastStream)
+    HIP_TRY(hipStreamWaitEvent(s, h->gridDone, 0));
+  h->gridHaveLast = true;
+  h->gridLastStream = s;
+  const CameraSel camSel{ h->dCams, L.dCamIndex, h->camsNeedChecks };
+  const Batch B = make_batch(h, h->P, L, d_frames, frame_stride_bytes, nframes, depthInput, s, cameras ? &camSel : nullptr);
+  const int chunk = choose_chunk(h->tune, h->P.nPoints, nframes);   /* the labels', the refit's and the clearance pass's */
+  if(timing) HIP_TRY(hipEventRecord(h->evGrid[0], s));
+  HIP_TRY(hipMemsetAsync(d_out, 0, sizeof(ssd_frame_tread_grid) * static_cast<size_t>(nframes), s));
+  launch_tread_grid(B, chunk, h->wholeResults, *rule, d_out);
+  HIP_TRY(hipGetLastError());
+  if(timing) HIP_TRY(hipEventRecord(h->evGrid[1], s));
+  h->gridTimed = timing;
+  HIP_TRY(hipEventRecord(h->gridDone, s));
+  /* the workspace is in use until here: whatever takes it next, on whichever stream, goes behind the pass */
+  HIP_TRY(hipEventRecord(L.done, s));
+  L.lastStream = s;
+  return SSD_OK;
+}
+
+int ssd_enqueue_tread_grid(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream, int input,
+                           const ssd_tread_grid_rule *rule, ssd_frame_tread_grid *d_out)
+{
+  return tread_grid_enqueue_impl(h, "ssd_enqueue_tread_grid", false, d_frames, frame_stride_bytes, nframes, stream, input, rule, d_out);
+}
+
+int ssd_enqueue_cameras_tread_grid(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream, int input,
+                                   const ssd_tread_grid_rule *rule, ssd_frame_tread_grid *d_out)
+{
+  return tread_grid_enqueue_impl(h, "ssd_enqueue_cameras_tread_grid", true, d_frames, frame_stride_bytes, nframes, stream, input, rule, d_out);
+}
+
+int ssd_fetch_tread_grid(ssd_handle *h, void *)
+{
+  if(!h)
+    return fail(SSD_E_ARG, "ssd_fetch_tread_grid: null handle");
+  if(!h->gridHaveLast)
+    return fail(SSD_E_ARG, "ssd_fetch_tread_grid: no ssd_enqueue_tread_grid to wait for");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipEventSynchronize(h->gridDone));
+  return SSD_OK;
+}
+
+int ssd_get_tread_grid_time(ssd_handle *h, float *ms)
+{
+  if(!h || !ms)
+    return fail(SSD_E_ARG, "ssd_get_tread_grid_time: null");
+  if(!h->gridHaveLast)
+    return fail(SSD_E_ARG, "ssd_get_tread_grid_time: no ssd_enqueue_tread_grid yet");
+  *ms = 0.0f;
+  if(!h->gridTimed)
+    return SSD_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipEventSynchronize(h->evGrid[1]));
+  HIP_TRY(hipEventElapsedTime(ms, h->evGrid[0], h->evGrid[1]));
+  return SSD_OK;
+}
+
+/* where a slice's records are staged: the first label staging buffer if it holds them as it stands, else a buffer of the pass's own
+ * (every user of either has been waited for: the bodies of the host entry points block on their slices) */
+static int tread_grid_stage(ssd_handle *h, int slice, ssd_frame_tread_grid *&dRecords)
+{
+  if(h->labelStage[0] && h->labelStageCap >= static_cast<size_t>(slice) * sizeof(ssd_frame_tread_grid))
+  {
+    dRecords = reinterpret_cast<ssd_frame_tread_grid *>(h->labelStage[0].get());
+    return SSD_OK;
+  }
+  if(h->gridStageFrames < slice)
+  {
+    DeviceBuf<ssd_frame_tread_grid> buf;
+    const hipError_t e = buf.alloc(static_cast<size_t>(slice) * sizeof(ssd_frame_tread_grid));
+    if(e != hipSuccess)
+      return hip_fail(e, "the tread grid's staging buffer: ");
+    h->gridStage = std::move(buf);
+    h->gridStageFrames = slice;
+  }
+  dRecords = h->gridStage;
+  return SSD_OK;
+}
+
+/* both host entry points, the callers' own refusals behind them: per slice, while it is still in its staging buffer, the enqueue, the
+ * pass, both fetches and the solve */
+static int process_host_tread_grid_impl(ssd_handle *h, const char *who, const void *frames, int nframes, const uint16_t *camOf, int input,
+                                        const ssd_tread_grid_rule *rule, int min_seen, int min_occ, double foot_along, double foot_deep,
+                                        ssd_frame_result *results, ssd_frame_tread_grid *grids, ssd_frame_footholds *out)
+{
+  int rc = check_tread_grid_rule(who, rule);
+  if(rc) return rc;
+  if(!(foot_along >= 0.0) || !(foot_deep >= 0.0))
+    return fail(SSD_E_ARG, std::string(who) + ": a foot size must be 0 or more");
+  HIP_TRY(hipSetDevice(h->device));
+  SliceFeed feed{ h, host_frames(h, input, kForPipeline), frames, nframes };
+  rc = feed.prepare();
+  if(rc) return rc;
+  ssd_frame_tread_grid *dRecords = nullptr;
+  rc = tread_grid_stage(h, feed.slice, dRecords);
+  if(rc) return rc;
+  std::vector<ssd_frame_tread_grid> own;
+  if(!grids)
+    own.resize(static_cast<size_t>(feed.slice));
+  for(int c = 0; c < feed.slices(); c++)
+  {
+    const void *buf;
+    int done, n;
+    /* the body blocks on the pass, so the next slice's copy goes out in front of it, beside this slice's kernels */
+    rc = feed.stage(c);
+    if(!rc) rc = feed.stage(c + 1);
+    if(!rc) rc = feed.ready(c, buf, done, n);
+    if(rc) return rc;
+    rc = enqueue_impl(h, buf, feed.f.devFrameBytes, n, h->ingestCompute, SSD_STAGE_ALL, feed.f.depth, nullptr, 0, camOf ? camOf + done : nullptr);
+    if(!rc) rc = tread_grid_enqueue_impl(h, who, camOf != nullptr, buf, feed.f.devFrameBytes, n, h->ingestCompute, input, rule, dRecords);
+    if(!rc) rc = ssd_fetch_back(h, results + done, n, 0);
+    if(rc) return rc;
+    /* behind the pass on the stream it ran on; the body waits, so the staging buffer is free for the next slice */
+    hipStream_t s = h->lane[h->lastLane].lastStream;
+    ssd_frame_tread_grid *to = grids ? grids + done : own.data();
+    HIP_TRY(hipMemcpyAsync(to, dRecords, sizeof(ssd_frame_tread_grid) * static_cast<size_t>(n), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    rc = feed.consumed(c, s);
+    if(rc) return rc;
+    for(int i = 0; i < n; i++)
+    {
+      rc = ssd_tread_grid_solve(to + i, results + done + i, rule, min_seen, min_occ, foot_along, foot_deep, out + done + i);
+      if(rc) return rc;
+    }
+  }
+  return SSD_OK;
+}
+
+int ssd_process_host_tread_grid(ssd_handle *h, const void *frames, int nframes, int input, const ssd_tread_grid_rule *rule, int min_seen,
+                                int min_occ, double foot_along, double foot_deep, ssd_frame_result *results, ssd_frame_tread_grid *grids,
+                                ssd_frame_footholds *out)
+{
+  const int rc = check_host_batch(h, "ssd_process_host_tread_grid", h && frames && results && out, nframes, input, kHandleCal);
+  return rc ? rc : process_host_tread_grid_impl(h, "ssd_process_host_tread_grid", frames, nframes, nullptr, input, rule, min_seen, min_occ, foot_along,
+                                                foot_deep, results, grids, out);
+}
+
+int ssd_process_host_cameras_tread_grid(ssd_handle *h, const void *frames, int nframes, const uint16_t *camera_of_frame, int input,
+                                        const ssd_tread_grid_rule *rule, int min_seen, int min_occ, double foot_along, double foot_deep,
+                                        ssd_frame_result *results, ssd_frame_tread_grid *grids, ssd_frame_footholds *out)
+{
+  const int rc = check_host_batch(h, "ssd_process_host_cameras_tread_grid", h && frames && results && out, nframes, input, kCameraTable, camera_of_frame);
+  return rc ? rc : process_host_tread_grid_impl(h, "ssd_process_host_cameras_tread_grid", frames, nframes, camera_of_frame, input, rule, min_seen, min_occ,
+                                                foot_along, foot_deep, results, grids, out);
 }
 
 /* ---- riser fit (include/ssd_hip.h): host side ------------------------------------------------------------ */

@@ -208,6 +208,15 @@ struct ssd_handle
   hipStream_t clearLastStream = nullptr;
   std::vector<ssd::Event> evClear;          /* both or none: around the pass of a timed call, made on the first one */
   bool clearHaveLast = false, clearTimed = false;
+  /* the tread grid pass (ssd_enqueue_tread_grid): events only, as the clearance pass's, made on the first call */
+  ssd::Event gridDone;                      /* behind the pass */
+  hipStream_t gridLastStream = nullptr;
+  std::vector<ssd::Event> evGrid;           /* both or none: around the pass of a timed call */
+  bool gridHaveLast = false, gridTimed = false;
+  /* ssd_process_host_tread_grid: a slice's records where the label staging buffers do not hold them (a record is 52.5 KB, more than
+   * the width * height bytes of a small frame that those are sized by); made on first use, not counted as workspace like those */
+  ssd::DeviceBuf<ssd_frame_tread_grid> gridStage;
+  int gridStageFrames = 0;
 };
 
 /* The single pass's planes - dPlaneImg and dFallback of every workspace and the pinned hFallback, zeroed - for ALL workspaces of the

@@ -69,3 +69,5 @@ void launch_surface_refit(const Batch &B, int chunkPoints, const ssd_frame_gates
 
 /* the other pass behind a whole enqueue, the tread clearance, in this translation unit: one parse of ssd_kernels.hip */
 #include "ssd_kernels_clearance.hip"
+/* ... and the tread grid (section 7n), which is built on it */
+#include "ssd_kernels_treadgrid.hip"
