@@ -561,6 +561,18 @@ def _check(rc, which="hip"):
     return rc
 
 
+def _input_code(depth):
+    """the `input` argument of the C entry points: 16-bit depth, or vertices"""
+    return INPUT_DEPTH16 if depth else INPUT_VERTICES
+
+
+def _time_ms(getter, *args):
+    """a time getter of the C API (its last argument a float *) -> milliseconds"""
+    ms = C.c_float(0.0)
+    _check(getter(*args, C.byref(ms)))
+    return float(ms.value)
+
+
 def predict_table_host(sample, n_bins, min_height, sabotage=0):
     """test hook (host, no GPU): the single pass's bin -> plane table as csrc/ssd_predict.h states it; returns (uint8[MAX_BINS], planes)"""
     a = np.ascontiguousarray(sample, dtype=np.uint32)
@@ -657,7 +669,7 @@ def ground_moments_host(cfg, prior, frame, tol, depth=False):
         raise SsdError("ground_moments_host: the array is not one frame")
     cam = _as_camera(prior)
     out = GroundMoments()
-    _check(lib().ssd_ground_moments_host(C.byref(cfg), C.byref(cam), INPUT_DEPTH16 if depth else INPUT_VERTICES, a.ctypes.data_as(C.c_void_p),
+    _check(lib().ssd_ground_moments_host(C.byref(cfg), C.byref(cam), _input_code(depth), a.ctypes.data_as(C.c_void_p),
                                          float(tol), C.byref(out)))
     return out
 
@@ -680,7 +692,7 @@ def surface_moments_host(cfg, frame, labels, n_surfaces, ground, intr=None):
     if a.size != cfg.width * cfg.height * (1 if depth else 3) or lab.size != cfg.width * cfg.height:
         raise SsdError("surface_moments_host: the arrays are not one frame")
     out = FrameMoments()
-    _check(lib().ssd_surface_moments_host(C.byref(cfg), INPUT_DEPTH16 if depth else INPUT_VERTICES, C.byref(intr) if depth else None,
+    _check(lib().ssd_surface_moments_host(C.byref(cfg), _input_code(depth), C.byref(intr) if depth else None,
                                           a.ctypes.data_as(C.c_void_p), lab.ctypes.data_as(C.c_void_p), int(n_surfaces), int(ground), C.byref(out)))
     return out
 
@@ -720,7 +732,7 @@ def surface_refit_moments_host(cfg, frame, labels, gates, n_surfaces, ground, in
     if a.size != cfg.width * cfg.height * (1 if depth else 3) or lab.size != cfg.width * cfg.height:
         raise SsdError("surface_refit_moments_host: the arrays are not one frame")
     out = FrameMoments()
-    _check(lib().ssd_surface_refit_moments_host(C.byref(cfg), INPUT_DEPTH16 if depth else INPUT_VERTICES, C.byref(intr) if depth else None,
+    _check(lib().ssd_surface_refit_moments_host(C.byref(cfg), _input_code(depth), C.byref(intr) if depth else None,
                                                 a.ctypes.data_as(C.c_void_p), lab.ctypes.data_as(C.c_void_p),
                                                 C.byref(gates) if gates is not None else None, int(n_surfaces), int(ground), C.byref(out)))
     return out
@@ -741,7 +753,7 @@ def clearance_host(cfg, cal, frame, result, ground, rule=None, intr=None, mask=T
     c = _calibration_of(cal)
     out = FrameMoments()
     m = np.empty((cfg.height, cfg.width), dtype=np.uint8) if mask else None
-    _check(lib().ssd_clearance_host(C.byref(cfg), C.byref(c), INPUT_DEPTH16 if depth else INPUT_VERTICES, C.byref(intr) if depth else None,
+    _check(lib().ssd_clearance_host(C.byref(cfg), C.byref(c), _input_code(depth), C.byref(intr) if depth else None,
                                     a.ctypes.data_as(C.c_void_p), C.byref(result), int(ground), C.byref(rule), C.byref(out),
                                     m.ctypes.data_as(C.c_void_p) if mask else None))
     return out, m
@@ -765,7 +777,7 @@ def tread_grid_host(cfg, cal, frame, result, ground, rule=None, intr=None):
     rule = TreadGridRule() if rule is None else rule
     c = _calibration_of(cal)
     out = FrameTreadGrid()
-    _check(lib().ssd_tread_grid_host(C.byref(cfg), C.byref(c), INPUT_DEPTH16 if depth else INPUT_VERTICES, C.byref(intr) if depth else None,
+    _check(lib().ssd_tread_grid_host(C.byref(cfg), C.byref(c), _input_code(depth), C.byref(intr) if depth else None,
                                      a.ctypes.data_as(C.c_void_p), C.byref(result), int(ground), C.byref(rule), C.byref(out)))
     return out
 
@@ -925,12 +937,19 @@ class Detector:
         """makes `stream` wait for the batch `back` enqueues ago (ssd_stream_wait)"""
         _check(lib().ssd_stream_wait(self._h, back, C.c_void_p(stream or 0)))
 
+    def _frames_arg(self, who, frames, depth):
+        """the frames argument of a host-fed method (float32 [n, H, W, 3], or uint16 [n, H, W] with depth; a PinnedArray as it is)
+        -> (contiguous array, n, the C `input` code)"""
+        a = frames.array if isinstance(frames, PinnedArray) else np.ascontiguousarray(frames, dtype=np.uint16 if depth else np.float32)
+        per = self.cfg.width * self.cfg.height * (1 if depth else 3)
+        n = a.size // per
+        if n < 1 or n * per != a.size:
+            raise SsdError("%s: array does not hold whole frames" % who)
+        return a, n, _input_code(depth)
+
     def process_host(self, xyz):
         """xyz: float32 array [n, H, W, 3] (or [H, W, 3]) on the host -> list of FrameResult."""
-        a = np.ascontiguousarray(xyz, dtype=np.float32)
-        n = a.size // (self.cfg.width * self.cfg.height * 3)
-        if n * self.cfg.width * self.cfg.height * 3 != a.size or n < 1:
-            raise SsdError("process_host: array does not hold whole frames")
+        a, n, _ = self._frames_arg("process_host", xyz, False)
         res = (FrameResult * n)()
         _check(lib().ssd_process_host(self._h, a.ctypes.data_as(C.c_void_p), n, res))
         return list(res)
@@ -968,10 +987,7 @@ class Detector:
 
     def process_host_labels(self, xyz):
         """process_host plus labels: -> (list of FrameResult, uint8 array [n, H, W])"""
-        a = np.ascontiguousarray(xyz, dtype=np.float32)
-        n = a.size // (self.cfg.width * self.cfg.height * 3)
-        if n * self.cfg.width * self.cfg.height * 3 != a.size or n < 1:
-            raise SsdError("process_host_labels: array does not hold whole frames")
+        a, n, _ = self._frames_arg("process_host_labels", xyz, False)
         res = (FrameResult * n)()
         labels = np.empty((n, self.cfg.height, self.cfg.width), dtype=np.uint8)
         _check(lib().ssd_process_host_labels(self._h, a.ctypes.data_as(C.c_void_p), n, res, labels.ctypes.data_as(C.c_void_p)))
@@ -979,10 +995,7 @@ class Detector:
 
     def process_depth_host_labels(self, depth):
         """process_depth_host plus labels: -> (list of FrameResult, uint8 array [n, H, W])"""
-        a = np.ascontiguousarray(depth, dtype=np.uint16)
-        n = a.size // (self.cfg.width * self.cfg.height)
-        if n * self.cfg.width * self.cfg.height != a.size or n < 1:
-            raise SsdError("process_depth_host_labels: array does not hold whole frames")
+        a, n, _ = self._frames_arg("process_depth_host_labels", depth, True)
         res = (FrameResult * n)()
         labels = np.empty((n, self.cfg.height, self.cfg.width), dtype=np.uint8)
         _check(lib().ssd_process_depth_host_labels(self._h, a.ctypes.data_as(C.c_void_p), n, res, labels.ctypes.data_as(C.c_void_p)))
@@ -1023,22 +1036,18 @@ class Detector:
             and camera_of_frame.ndim == 1 and camera_of_frame.size == nframes else self._camera_index(camera_of_frame, nframes)
         frame = self.cfg.width * self.cfg.height * (2 if depth else 12)
         _check(lib().ssd_enqueue_cameras(self._h, C.c_void_p(d_ptr), stride_bytes or frame, nframes, C.c_void_p(stream or 0),
-                                         idx.ctypes.data_as(C.POINTER(C.c_uint16)), INPUT_DEPTH16 if depth else INPUT_VERTICES,
+                                         idx.ctypes.data_as(C.POINTER(C.c_uint16)), _input_code(depth),
                                          C.c_void_p(d_labels or 0), (label_stride or self.cfg.width * self.cfg.height) if d_labels else 0))
 
     def process_host_cameras(self, frames, camera_of_frame, depth=False, labels=False):
         """frames on the host (float32 [n, H, W, 3], or uint16 [n, H, W] with depth=True), one camera index per frame
         -> list of FrameResult, or (list, uint8 labels [n, H, W]) with labels=True"""
-        a = np.ascontiguousarray(frames, dtype=np.uint16 if depth else np.float32) if not isinstance(frames, PinnedArray) else frames.array
-        per = self.cfg.width * self.cfg.height * (1 if depth else 3)
-        n = a.size // per
-        if n * per != a.size or n < 1:
-            raise SsdError("process_host_cameras: array does not hold whole frames")
+        a, n, inp = self._frames_arg("process_host_cameras", frames, depth)
         idx = self._camera_index(camera_of_frame, n)
         res = (FrameResult * n)()
         lab = np.empty((n, self.cfg.height, self.cfg.width), dtype=np.uint8) if labels else None
         _check(lib().ssd_process_host_cameras(self._h, a.ctypes.data_as(C.c_void_p), n, idx.ctypes.data_as(C.POINTER(C.c_uint16)),
-                                              INPUT_DEPTH16 if depth else INPUT_VERTICES, res, lab.ctypes.data_as(C.c_void_p) if labels else None))
+                                              inp, res, lab.ctypes.data_as(C.c_void_p) if labels else None))
         return (list(res), lab) if labels else list(res)
 
     # ---- ground fit: a calibration refined from the floor in the frames (include/ssd_hip.h, DESIGN.md section 7c)
@@ -1048,7 +1057,7 @@ class Detector:
         arr, n = _camera_array(priors)
         frame = self.cfg.width * self.cfg.height * (2 if depth else 12)
         _check(lib().ssd_enqueue_ground_fit(self._h, C.c_void_p(d_ptr), stride_bytes or frame, nframes, C.c_void_p(stream or 0),
-                                            INPUT_DEPTH16 if depth else INPUT_VERTICES, arr, n, float(tol)))
+                                            _input_code(depth), arr, n, float(tol)))
 
     def fetch_ground_fit(self, nframes, min_points=2000, stream=None):
         """ssd_fetch_ground_fit: waits for the last enqueue_ground_fit -> list of GroundFit (independent copies)"""
@@ -1058,14 +1067,10 @@ class Detector:
 
     def process_host_ground_fit(self, frames, tol, priors=None, depth=False, min_points=2000):
         """ssd_process_host_ground_fit: frames on the host (float32 [n, H, W, 3], or uint16 [n, H, W] with depth=True) -> list of GroundFit"""
-        a = np.ascontiguousarray(frames, dtype=np.uint16 if depth else np.float32) if not isinstance(frames, PinnedArray) else frames.array
-        per = self.cfg.width * self.cfg.height * (1 if depth else 3)
-        n = a.size // per
-        if n * per != a.size or n < 1:
-            raise SsdError("process_host_ground_fit: array does not hold whole frames")
+        a, n, inp = self._frames_arg("process_host_ground_fit", frames, depth)
         arr, npriors = _camera_array(priors)
         out = (GroundFit * n)()
-        _check(lib().ssd_process_host_ground_fit(self._h, a.ctypes.data_as(C.c_void_p), n, INPUT_DEPTH16 if depth else INPUT_VERTICES, arr, npriors,
+        _check(lib().ssd_process_host_ground_fit(self._h, a.ctypes.data_as(C.c_void_p), n, inp, arr, npriors,
                                                  float(tol), int(min_points), out))
         return [GroundFit.from_buffer_copy(r) for r in out]
 
@@ -1101,13 +1106,9 @@ class Detector:
     def process_host_surfaces(self, frames, depth=False, min_points=200, moments=False):
         """ssd_process_host_surfaces: frames on the host (float32 [n, H, W, 3], or uint16 [n, H, W] with depth=True)
         -> (list of FrameResult, list of FrameSurfaces), with moments=True also the list of FrameMoments"""
-        a = np.ascontiguousarray(frames, dtype=np.uint16 if depth else np.float32)
-        per = self.cfg.width * self.cfg.height * (1 if depth else 3)
-        n = a.size // per
-        if n < 1 or n * per != a.size:
-            raise SsdError("process_host_surfaces: array does not hold whole frames")
+        a, n, inp = self._frames_arg("process_host_surfaces", frames, depth)
         res, mom, out = (FrameResult * n)(), (FrameMoments * n)(), (FrameSurfaces * n)()
-        _check(lib().ssd_process_host_surfaces(self._h, a.ctypes.data_as(C.c_void_p), n, INPUT_DEPTH16 if depth else INPUT_VERTICES, res,
+        _check(lib().ssd_process_host_surfaces(self._h, a.ctypes.data_as(C.c_void_p), n, inp, res,
                                                mom if moments else None, int(min_points), out))
         return (list(res), list(out), list(mom)) if moments else (list(res), list(out))
 
@@ -1123,7 +1124,7 @@ class Detector:
             if len(arr) < nframes:
                 raise SsdError("enqueue_surface_refit: fewer gates than frames")
         _check(lib().ssd_enqueue_surface_refit(self._h, C.c_void_p(d_ptr), stride_bytes or frame, nframes, C.c_void_p(stream or 0),
-                                               INPUT_DEPTH16 if depth else INPUT_VERTICES, arr, C.c_void_p(d_moments)))
+                                               _input_code(depth), arr, C.c_void_p(d_moments)))
 
     def fetch_surface_refit(self, stream=None):
         """ssd_fetch_surface_refit: waits for the last enqueue_surface_refit"""
@@ -1131,9 +1132,7 @@ class Detector:
 
     def surface_refit_time_ms(self):
         """Device time of the last refit pass (0.0: timing was off for it)"""
-        ms = C.c_float(0.0)
-        _check(lib().ssd_get_surface_refit_time(self._h, C.byref(ms)))
-        return ms.value
+        return _time_ms(lib().ssd_get_surface_refit_time, self._h)
 
     def process_host_surfaces_refit(self, frames, depth=False, min_points=200, k_sigma=2.5, gate_min=0.0, passes=1, moments=False,
                                     device_gates=False):
@@ -1141,14 +1140,10 @@ class Detector:
         -> (list of FrameResult, list of FrameSurfaces of the last refit pass), with moments=True also the lists of FrameMoments of
         the first pass and of the last refit pass.  device_gates=True: ssd_process_host_surfaces_refit_device (the gates made on the
         device between the passes; the same outputs)"""
-        a = np.ascontiguousarray(frames, dtype=np.uint16 if depth else np.float32)
-        per = self.cfg.width * self.cfg.height * (1 if depth else 3)
-        n = a.size // per
-        if n < 1 or a.size != n * per:
-            raise SsdError("process_host_surfaces_refit: array does not hold whole frames")
+        a, n, inp = self._frames_arg("process_host_surfaces_refit", frames, depth)
         res, first, refit, out = (FrameResult * n)(), (FrameMoments * n)(), (FrameMoments * n)(), (FrameSurfaces * n)()
         fn = lib().ssd_process_host_surfaces_refit_device if device_gates else lib().ssd_process_host_surfaces_refit
-        _check(fn(self._h, a.ctypes.data_as(C.c_void_p), n, INPUT_DEPTH16 if depth else INPUT_VERTICES, res, first if moments else None,
+        _check(fn(self._h, a.ctypes.data_as(C.c_void_p), n, inp, res, first if moments else None,
                   refit if moments else None, int(min_points), float(k_sigma), float(gate_min), int(passes), out))
         return (list(res), list(out), list(first), list(refit)) if moments else (list(res), list(out))
 
@@ -1161,7 +1156,7 @@ class Detector:
         frame = self.cfg.width * self.cfg.height * (2 if depth else 12)
         rule = ClearanceRule() if rule is None else rule
         fn = lib().ssd_enqueue_cameras_clearance if cameras else lib().ssd_enqueue_clearance
-        _check(fn(self._h, C.c_void_p(d_ptr), stride_bytes or frame, nframes, C.c_void_p(stream or 0), INPUT_DEPTH16 if depth else INPUT_VERTICES,
+        _check(fn(self._h, C.c_void_p(d_ptr), stride_bytes or frame, nframes, C.c_void_p(stream or 0), _input_code(depth),
                   C.byref(rule), C.c_void_p(d_moments), C.c_void_p(d_mask or 0), mask_stride or self.cfg.width * self.cfg.height))
 
     def enqueue_cameras_clearance(self, d_ptr, nframes, d_moments, rule=None, d_mask=None, mask_stride=None, depth=False, stride_bytes=None,
@@ -1175,24 +1170,17 @@ class Detector:
 
     def clearance_time_ms(self):
         """Device time of the last clearance pass (0.0: timing was off for it)"""
-        ms = C.c_float(0.0)
-        _check(lib().ssd_get_clearance_time(self._h, C.byref(ms)))
-        return ms.value
+        return _time_ms(lib().ssd_get_clearance_time, self._h)
 
     def process_host_clearance(self, frames, rule=None, min_support=50, depth=False, moments=False, mask=False, camera_of_frame=None):
         """ssd_process_host_clearance: frames on the host (float32 [n, H, W, 3], or uint16 [n, H, W] with depth=True)
         -> (list of FrameResult, list of FrameClearance), with moments=True also the list of FrameMoments, with mask=True also the
         masks (uint8 [n, H, W])"""
-        a = np.ascontiguousarray(frames, dtype=np.uint16 if depth else np.float32)
-        per = self.cfg.width * self.cfg.height * (1 if depth else 3)
-        n = a.size // per
-        if n < 1 or a.size != n * per:
-            raise SsdError("process_host_clearance: array does not hold whole frames")
+        a, n, inp = self._frames_arg("process_host_clearance", frames, depth)
         rule = ClearanceRule() if rule is None else rule
         res, mom, out = (FrameResult * n)(), (FrameMoments * n)(), (FrameClearance * n)()
         m = np.empty((n, self.cfg.height, self.cfg.width), dtype=np.uint8) if mask else None
         tail = (C.byref(rule), int(min_support), res, mom if moments else None, m.ctypes.data_as(C.c_void_p) if mask else None, out)
-        inp = INPUT_DEPTH16 if depth else INPUT_VERTICES
         if camera_of_frame is None:
             _check(lib().ssd_process_host_clearance(self._h, a.ctypes.data_as(C.c_void_p), n, inp, *tail))
         else:
@@ -1216,7 +1204,7 @@ class Detector:
         frame = self.cfg.width * self.cfg.height * (2 if depth else 12)
         rule = TreadGridRule() if rule is None else rule
         fn = lib().ssd_enqueue_cameras_tread_grid if cameras else lib().ssd_enqueue_tread_grid
-        _check(fn(self._h, C.c_void_p(d_ptr), stride_bytes or frame, nframes, C.c_void_p(stream or 0), INPUT_DEPTH16 if depth else INPUT_VERTICES,
+        _check(fn(self._h, C.c_void_p(d_ptr), stride_bytes or frame, nframes, C.c_void_p(stream or 0), _input_code(depth),
                   C.byref(rule), C.c_void_p(d_grids)))
 
     def enqueue_cameras_tread_grid(self, d_ptr, nframes, d_grids, rule=None, depth=False, stride_bytes=None, stream=None):
@@ -1229,24 +1217,17 @@ class Detector:
 
     def tread_grid_time_ms(self):
         """Device time of the last tread grid pass (0.0: timing was off for it)"""
-        ms = C.c_float(0.0)
-        _check(lib().ssd_get_tread_grid_time(self._h, C.byref(ms)))
-        return ms.value
+        return _time_ms(lib().ssd_get_tread_grid_time, self._h)
 
     def process_host_tread_grid(self, frames, rule=None, min_seen=1, min_occ=1, foot_along=0.0, foot_deep=0.0, depth=False, grids=False,
                                 camera_of_frame=None):
         """ssd_process_host_tread_grid: frames on the host (float32 [n, H, W, 3], or uint16 [n, H, W] with depth=True)
         -> (list of FrameResult, list of FrameFootholds), with grids=True also the list of FrameTreadGrid"""
-        a = np.ascontiguousarray(frames, dtype=np.uint16 if depth else np.float32)
-        per = self.cfg.width * self.cfg.height * (1 if depth else 3)
-        n = a.size // per
-        if n < 1 or a.size != n * per:
-            raise SsdError("process_host_tread_grid: array does not hold whole frames")
+        a, n, inp = self._frames_arg("process_host_tread_grid", frames, depth)
         rule = TreadGridRule() if rule is None else rule
         res, out = (FrameResult * n)(), (FrameFootholds * n)()
         g = (FrameTreadGrid * n)() if grids else None
         tail = (C.byref(rule), int(min_seen), int(min_occ), float(foot_along), float(foot_deep), res, g, out)
-        inp = INPUT_DEPTH16 if depth else INPUT_VERTICES
         if camera_of_frame is None:
             _check(lib().ssd_process_host_tread_grid(self._h, a.ctypes.data_as(C.c_void_p), n, inp, *tail))
         else:
@@ -1266,21 +1247,17 @@ class Detector:
         idx = self._camera_index(camera_of_frame, nframes)
         frame = self.cfg.width * self.cfg.height * (2 if depth else 12)
         _check(lib().ssd_enqueue_cameras_surface_moments(self._h, C.c_void_p(d_ptr), stride_bytes or frame, nframes, C.c_void_p(stream or 0),
-                                                         idx.ctypes.data_as(C.POINTER(C.c_uint16)), INPUT_DEPTH16 if depth else INPUT_VERTICES,
+                                                         idx.ctypes.data_as(C.POINTER(C.c_uint16)), _input_code(depth),
                                                          C.c_void_p(d_moments)))
 
     def process_host_cameras_surfaces(self, frames, camera_of_frame, depth=False, min_points=200, moments=False):
         """ssd_process_host_cameras_surfaces: frames on the host (float32 [n, H, W, 3], or uint16 [n, H, W] with depth=True), one camera
         index per frame -> (list of FrameResult, list of FrameSurfaces), with moments=True also the list of FrameMoments"""
-        a = np.ascontiguousarray(frames, dtype=np.uint16 if depth else np.float32) if not isinstance(frames, PinnedArray) else frames.array
-        per = self.cfg.width * self.cfg.height * (1 if depth else 3)
-        n = a.size // per
-        if n < 1 or n * per != a.size:
-            raise SsdError("process_host_cameras_surfaces: array does not hold whole frames")
+        a, n, inp = self._frames_arg("process_host_cameras_surfaces", frames, depth)
         idx = self._camera_index(camera_of_frame, n)
         res, mom, out = (FrameResult * n)(), (FrameMoments * n)(), (FrameSurfaces * n)()
         _check(lib().ssd_process_host_cameras_surfaces(self._h, a.ctypes.data_as(C.c_void_p), n, idx.ctypes.data_as(C.POINTER(C.c_uint16)),
-                                                       INPUT_DEPTH16 if depth else INPUT_VERTICES, res, mom if moments else None, int(min_points), out))
+                                                       inp, res, mom if moments else None, int(min_points), out))
         return (list(res), list(out), list(mom)) if moments else (list(res), list(out))
 
     def camera_drift(self, frames, camera_of_frame, depth=False, min_points=2000, passes=0, k_sigma=2.5, gate_min=0.0, device_gates=False,
@@ -1293,16 +1270,12 @@ class Detector:
         if not getattr(self, "_cameras", None):
             raise SsdError("camera_drift: the handle has no camera table (set_cameras)")
         if device_fold:
-            a = np.ascontiguousarray(frames, dtype=np.uint16 if depth else np.float32) if not isinstance(frames, PinnedArray) else frames.array
-            per = self.cfg.width * self.cfg.height * (1 if depth else 3)
-            n = a.size // per
-            if n < 1 or a.size != n * per:
-                raise SsdError("camera_drift: array does not hold whole frames")
+            a, n, inp = self._frames_arg("camera_drift", frames, depth)
             idx = self._camera_index(camera_of_frame, n)
             ncams = len(self._cameras)
             res, out = (FrameResult * n)(), (CameraDrift * ncams)()
             _check(lib().ssd_process_host_cameras_drift(self._h, a.ctypes.data_as(C.c_void_p), n, idx.ctypes.data_as(C.POINTER(C.c_uint16)),
-                                                        INPUT_DEPTH16 if depth else INPUT_VERTICES, res, 200, float(k_sigma), float(gate_min),
+                                                        inp, res, 200, float(k_sigma), float(gate_min),
                                                         int(passes), int(min_points), out))
             return list(res), [CameraDrift.from_buffer_copy(out[i]) for i in range(ncams)]
         if passes:
@@ -1323,22 +1296,18 @@ class Detector:
             if len(arr) < nframes:
                 raise SsdError("enqueue_cameras_surface_refit: fewer gates than frames")
         _check(lib().ssd_enqueue_cameras_surface_refit(self._h, C.c_void_p(d_ptr), stride_bytes or frame, nframes, C.c_void_p(stream or 0),
-                                                       INPUT_DEPTH16 if depth else INPUT_VERTICES, arr, C.c_void_p(d_moments)))
+                                                       _input_code(depth), arr, C.c_void_p(d_moments)))
 
     def process_host_cameras_surfaces_refit(self, frames, camera_of_frame, depth=False, min_points=200, k_sigma=2.5, gate_min=0.0, passes=1,
                                             moments=False, device_gates=False):
         """ssd_process_host_cameras_surfaces_refit: process_host_surfaces_refit with one camera index per frame
         -> (list of FrameResult, list of FrameSurfaces of the last refit pass), with moments=True also the lists of FrameMoments of
         the first pass and of the last refit pass.  device_gates=True: ssd_process_host_cameras_surfaces_refit_device"""
-        a = np.ascontiguousarray(frames, dtype=np.uint16 if depth else np.float32) if not isinstance(frames, PinnedArray) else frames.array
-        per = self.cfg.width * self.cfg.height * (1 if depth else 3)
-        n = a.size // per
-        if n < 1 or a.size != n * per:
-            raise SsdError("process_host_cameras_surfaces_refit: array does not hold whole frames")
+        a, n, inp = self._frames_arg("process_host_cameras_surfaces_refit", frames, depth)
         idx = self._camera_index(camera_of_frame, n)
         res, first, refit, out = (FrameResult * n)(), (FrameMoments * n)(), (FrameMoments * n)(), (FrameSurfaces * n)()
         fn = lib().ssd_process_host_cameras_surfaces_refit_device if device_gates else lib().ssd_process_host_cameras_surfaces_refit
-        _check(fn(self._h, a.ctypes.data_as(C.c_void_p), n, idx.ctypes.data_as(C.POINTER(C.c_uint16)), INPUT_DEPTH16 if depth else INPUT_VERTICES, res,
+        _check(fn(self._h, a.ctypes.data_as(C.c_void_p), n, idx.ctypes.data_as(C.POINTER(C.c_uint16)), inp, res,
                   first if moments else None, refit if moments else None, int(min_points), float(k_sigma), float(gate_min), int(passes), out))
         return (list(res), list(out), list(first), list(refit)) if moments else (list(res), list(out))
 
@@ -1355,7 +1324,7 @@ class Detector:
         d_prev (device memory: the first pass's records, or a refit pass's - d_prev == d_moments is allowed), no host copy, no wait"""
         frame = self.cfg.width * self.cfg.height * (2 if depth else 12)
         _check(lib().ssd_enqueue_surface_refit_device(self._h, C.c_void_p(d_ptr), stride_bytes or frame, nframes, C.c_void_p(stream or 0),
-                                                      INPUT_DEPTH16 if depth else INPUT_VERTICES, C.c_void_p(d_prev), int(min_points),
+                                                      _input_code(depth), C.c_void_p(d_prev), int(min_points),
                                                       float(k_sigma), float(gate_min), C.c_void_p(d_moments)))
 
     def enqueue_cameras_surface_refit_device(self, d_ptr, nframes, d_prev, d_moments, min_points=200, k_sigma=2.5, gate_min=0.0, depth=False,
@@ -1363,7 +1332,7 @@ class Detector:
         """ssd_enqueue_cameras_surface_refit_device: enqueue_surface_refit_device behind the handle's last whole CAMERAS enqueue"""
         frame = self.cfg.width * self.cfg.height * (2 if depth else 12)
         _check(lib().ssd_enqueue_cameras_surface_refit_device(self._h, C.c_void_p(d_ptr), stride_bytes or frame, nframes, C.c_void_p(stream or 0),
-                                                              INPUT_DEPTH16 if depth else INPUT_VERTICES, C.c_void_p(d_prev), int(min_points),
+                                                              _input_code(depth), C.c_void_p(d_prev), int(min_points),
                                                               float(k_sigma), float(gate_min), C.c_void_p(d_moments)))
 
     # ---- camera fold on the device (include/ssd_hip.h, DESIGN.md section 7j)
@@ -1389,7 +1358,7 @@ class Detector:
         are also folded per camera on the device and every frame's ground gate becomes its camera's plane, no host copy, no wait"""
         frame = self.cfg.width * self.cfg.height * (2 if depth else 12)
         _check(lib().ssd_enqueue_cameras_surface_refit_folded(self._h, C.c_void_p(d_ptr), stride_bytes or frame, nframes, C.c_void_p(stream or 0),
-                                                              INPUT_DEPTH16 if depth else INPUT_VERTICES, C.c_void_p(d_prev), int(min_points),
+                                                              _input_code(depth), C.c_void_p(d_prev), int(min_points),
                                                               float(k_sigma), float(gate_min), int(fold_min_points), C.c_void_p(d_moments)))
 
     def camera_drift_resident(self, d_ptr, nframes, camera_of_frame, depth=False, min_points=200, fold_min_points=2000, passes=2, k_sigma=2.5,
@@ -1430,15 +1399,11 @@ class Detector:
 
     def surface_moments_time_ms(self, back=0):
         """Device time of the surface-moments pass of the enqueue `back` calls ago (0.0: it gathered none); timing must be on."""
-        ms = C.c_float(0.0)
-        _check(lib().ssd_get_surface_moments_time_back(self._h, back, C.byref(ms)))
-        return float(ms.value)
+        return _time_ms(lib().ssd_get_surface_moments_time_back, self._h, back)
 
     def labels_time_ms(self, back=0):
         """Device time of the label kernel of the enqueue `back` calls ago (0.0: it wrote no labels); timing must be on."""
-        ms = C.c_float(0.0)
-        _check(lib().ssd_get_labels_time_back(self._h, back, C.byref(ms)))
-        return float(ms.value)
+        return _time_ms(lib().ssd_get_labels_time_back, self._h, back)
 
     def fetch(self, nframes, stream=None, back=0):
         """Waits for the last enqueue (back = 1: the one before it, so that the next batch can already be running) and
@@ -1479,9 +1444,7 @@ class Detector:
 
     def riser_labels_time_ms(self, back=0):
         """Device time of the riser labels' kernel of the enqueue `back` calls ago (0.0: it marked nothing); timing must be on."""
-        ms = C.c_float()
-        _check(lib().ssd_get_riser_labels_time_back(self._h, back, C.byref(ms)))
-        return float(ms.value)
+        return _time_ms(lib().ssd_get_riser_labels_time_back, self._h, back)
 
     def fetch_riser_moments(self, nframes, stream=None):
         """-> list of FrameMoments (independent copies; record i = riser i) of the last enqueue / host batch"""
@@ -1490,13 +1453,8 @@ class Detector:
         return [FrameMoments.from_buffer_copy(arr[i]) for i in range(nframes)]
 
     def _host_riser_fits(self, who, frames, camera_of_frame, depth, min_points, moments):
-        a = np.ascontiguousarray(frames, dtype=np.uint16 if depth else np.float32) if not isinstance(frames, PinnedArray) else frames.array
-        per = self.cfg.width * self.cfg.height * (1 if depth else 3)
-        n = a.size // per
-        if n < 1 or n * per != a.size:
-            raise SsdError("%s: array does not hold whole frames" % who)
+        a, n, inp = self._frames_arg(who, frames, depth)
         res, ris, mom, out = (FrameResult * n)(), (FrameRisers * n)(), (FrameMoments * n)(), (FrameRiserFits * n)()
-        inp = INPUT_DEPTH16 if depth else INPUT_VERTICES
         if camera_of_frame is None:
             _check(lib().ssd_process_host_riser_fits(self._h, a.ctypes.data_as(C.c_void_p), n, inp, res, ris, mom if moments else None,
                                                      int(min_points), out))
@@ -1527,9 +1485,7 @@ class Detector:
 
     def predict_time_ms(self, back=0):
         """Device time of k_predict, the kernel in front of the stages of a single-pass batch (0.0: the enqueue did not run it)."""
-        ms = C.c_float(0.0)
-        _check(lib().ssd_get_predict_time_back(self._h, back, C.byref(ms)))
-        return float(ms.value)
+        return _time_ms(lib().ssd_get_predict_time_back, self._h, back)
 
     def set_debug(self, on=True, images=True):
         """debug capture: records + images (the whole ground image is rastered for it), or records only (images=False:

@@ -23,6 +23,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <optional>
 #include <string>
 #include <vector>
 #include <sched.h>
@@ -1962,34 +1963,104 @@ int ssd_ground_fit_solve(const ssd_ground_moments *m, const ssd_calibration *pri
 
 /* ---- surface fit (include/ssd_hip.h): host side ---------------------------------------------------------- */
 
+/* A frame's points as the host statements of the passes see them.  First the refusals the statements share: `pointers` = the caller's
+ * own pointers are there, count = the frame's surfaces (`noun`: what the caller calls them), refused before the intrinsics where
+ * countFirst (the two moment walks) and behind them otherwise (the clearance pass, the tread grid) */
+static int host_frame_check(const std::string &who, bool pointers, const ssd_config *cfg, int input, const ssd_intrinsics *intr, const void *frame,
+                            int count, const char *noun, bool countFirst)
+{
+  if(!pointers || !cfg || !frame || cfg->width <= 0 || cfg->height <= 0)
+    return fail(SSD_E_ARG, who + ": bad argument");
+  if(input != SSD_INPUT_VERTICES && input != SSD_INPUT_DEPTH16)
+    return fail(SSD_E_ARG, who + ": input must be SSD_INPUT_VERTICES or SSD_INPUT_DEPTH16");
+  const bool countBad = count < 0 || count > SSD_MAX_STEPS;
+  if(countFirst && countBad)
+    return fail(SSD_E_ARG, who + ": " + noun + " must lie in 0 .. SSD_MAX_STEPS");
+  if(input == SSD_INPUT_DEPTH16 && (!intr || !good_intrinsics(*intr)))
+    return fail(SSD_E_ARG, who + ": depth input needs intrinsics");
+  if(countBad)
+    return fail(SSD_E_ARG, who + ": " + noun + " must lie in 0 .. SSD_MAX_STEPS");
+  return SSD_OK;
+}
+
+/* ... then the frame as vertices: the caller's, or depth deprojected into `scratch` */
+static int host_frame_xyz(const ssd_config *cfg, int input, const ssd_intrinsics *intr, const void *frame, std::vector<float> &scratch, const float *&xyz)
+{
+  xyz = static_cast<const float *>(frame);
+  if(input != SSD_INPUT_DEPTH16)
+    return SSD_OK;
+  scratch.resize(3 * static_cast<size_t>(cfg->width) * cfg->height);
+  xyz = scratch.data();
+  return ssd_deproject_host(intr, cfg->width, cfg->height, static_cast<const uint16_t *>(frame), scratch.data());
+}
+
+extern "C++"
+{
+/* ... and every point with z > 0 inside the configured range, in pixel order: f(pixel, x, y, z, wx, wy, wz), camera frame then world.
+ * The transform is ((a0 x + a1 y) + a2 z) + b in double, as the kernels' (their records are compared byte for byte) */
+template<class F>
+static void host_frame_walk(const ssd_config *cfg, const ssd_calibration *cal, const float *xyz, F f)
+{
+  const size_t nPoints = static_cast<size_t>(cfg->width) * cfg->height;
+  const double *a = cal->a, *b = cal->b;
+  for(size_t i = 0; i < nPoints; i++)
+  {
+    const float fx = xyz[3 * i], fy = xyz[3 * i + 1], fz = xyz[3 * i + 2];
+    if(!(fz > 0.0f))
+      continue;
+    const double x = fx, y = fy, z = fz;
+    const double wx = ((a[0] * x + a[1] * y) + a[2] * z) + b[0];
+    const double wy = ((a[3] * x + a[4] * y) + a[5] * z) + b[1];
+    const double wz = ((a[6] * x + a[7] * y) + a[8] * z) + b[2];
+    if(wx > cfg->x_min && wx < cfg->x_max && wy > cfg->y_min && wy < cfg->y_max && wz > cfg->z_min && wz < cfg->z_max)
+      f(i, x, y, z, wx, wy, wz);
+  }
+}
+
+/* What the clearance pass and the tread grid make of a frame's result before they walk it: the surfaces that can hold something (none
+ * for a frame that threw), each with the rule's margin, and the calibration's external frame */
+struct HostSurfaces
+{
+  int n;
+  ClearanceSurface S[SSD_MAX_STEPS];
+  ClearanceWorld X;
+  HostSurfaces(const ssd_frame_result *result, const ssd_calibration *cal, double margin)
+    : n((result->status & SSD_ST_THROW) ? 0 : result->n_steps),
+      X{ { cal->r2[0], cal->r2[1], cal->r2[2], cal->r2[3] }, { cal->t2[0], cal->t2[1] }, cal->world_z }
+  {
+    for(int k = 0; k < n; k++)
+      clearance_surface(result->steps[k], margin, S[k]);
+  }
+  /* their walk: f(pixel, x, y, z, ex, ey, ez), camera frame then external world */
+  template<class F>
+  void walk(const ssd_config *cfg, const ssd_calibration *cal, const float *xyz, F f) const
+  {
+    host_frame_walk(cfg, cal, xyz, [&](size_t i, double x, double y, double z, double wx, double wy, double wz)
+    {
+      double ex, ey;
+      clearance_external(X, wx, wy, ex, ey);
+      f(i, x, y, z, ex, ey, wz + X.worldZ);
+    });
+  }
+};
+
+} // extern "C++"
+
 /* The walk of ssd_surface_moments_host (gates == nullptr: every labelled point) and of ssd_surface_refit_moments_host (a labelled point
  * outside its surface's gate is skipped whole: ssd_refit.h) */
 static int surface_moments_walk(const std::string &who, const ssd_config *cfg, int input, const ssd_intrinsics *intr, const void *frame,
                                 const uint8_t *labels, const ssd_frame_gates *gates, int n_surfaces, int ground, ssd_frame_moments *out)
 {
-  if(!cfg || !frame || !labels || !out || cfg->width <= 0 || cfg->height <= 0)
-    return fail(SSD_E_ARG, who + ": bad argument");
-  if(input != SSD_INPUT_VERTICES && input != SSD_INPUT_DEPTH16)
-    return fail(SSD_E_ARG, who + ": input must be SSD_INPUT_VERTICES or SSD_INPUT_DEPTH16");
-  if(n_surfaces < 0 || n_surfaces > SSD_MAX_STEPS)
-    return fail(SSD_E_ARG, who + ": n_surfaces must lie in 0 .. SSD_MAX_STEPS");
-  const bool depth = input == SSD_INPUT_DEPTH16;
-  if(depth && (!intr || !good_intrinsics(*intr)))
-    return fail(SSD_E_ARG, who + ": depth input needs intrinsics");
-  const int W = cfg->width, H = cfg->height;
-  const size_t nPoints = static_cast<size_t>(W) * H;
+  int rc = host_frame_check(who, labels && out, cfg, input, intr, frame, n_surfaces, "n_surfaces", true);
+  if(rc) return rc;
+  const size_t nPoints = static_cast<size_t>(cfg->width) * cfg->height;
   for(size_t i = 0; i < nPoints; i++)
     if(labels[i] > n_surfaces)
       return fail(SSD_E_ARG, who + ": a label above n_surfaces");
   std::vector<float> deprojected;
-  const float *xyz = static_cast<const float *>(frame);
-  if(depth)
-  {
-    deprojected.resize(3 * nPoints);
-    const int rc = ssd_deproject_host(intr, W, H, static_cast<const uint16_t *>(frame), deprojected.data());
-    if(rc) return rc;
-    xyz = deprojected.data();
-  }
+  const float *xyz;
+  rc = host_frame_xyz(cfg, input, intr, frame, deprojected, xyz);
+  if(rc) return rc;
   static_assert(sizeof(ssd_surface_moments) == sizeof(long long) * (kGroundSums + 1), "ssd_surface_moments is the ten sums and n_far");
   long long acc[SSD_MAX_STEPS][kGroundSums + 1] = {};
   for(size_t i = 0; i < nPoints; i++)
@@ -2169,7 +2240,7 @@ int ssd_surface_refit_moments_host(const ssd_config *cfg, int input, const ssd_i
   return surface_moments_walk("ssd_surface_refit_moments_host", cfg, input, intr, frame, labels, gates, n_surfaces, ground, out);
 }
 
-/* the buffers and events of the refit, on its first call */
+/* the buffers of the refit and the event behind their copy, on its first call */
 static int refit_prepare(ssd_handle *h)
 {
   if(h->dRefitGates)
@@ -2177,15 +2248,14 @@ static int refit_prepare(ssd_handle *h)
   const size_t bytes = sizeof(ssd_frame_gates) * static_cast<size_t>(h->F);
   DeviceBuf<ssd_frame_gates> d;
   PinnedBuf<ssd_frame_gates> hh;
-  Event copied, done;
+  Event copied;
   hipError_t e = d.alloc(bytes, &h->bytes);
   if(e == hipSuccess) e = hh.alloc(bytes, &h->bytes);
   if(e == hipSuccess) e = copied.create(hipEventDisableTiming);
-  if(e == hipSuccess) e = done.create(hipEventDisableTiming);
   if(e != hipSuccess)
     return hip_fail(e, "ssd_enqueue_surface_refit: its buffers: ");
   h->dRefitGates = std::move(d); h->hRefitGates = std::move(hh);
-  h->refitGatesCopied = std::move(copied); h->refitDone = std::move(done);
+  h->refitGatesCopied = std::move(copied);
   return SSD_OK;
 }
 
@@ -2210,16 +2280,112 @@ static int fold_prepare(ssd_handle *h)
   return e == hipSuccess ? SSD_OK : hip_fail(e, "the camera fold's buffer: ");
 }
 
-/* What a pass behind the handle's last whole enqueue is held to - the refit (section 7g, 7h) and the clearance pass (section 7m) alike:
- * `cameras` = behind a whole cameras batch (wholeKind 2), under the table and the index that batch left in its workspace; otherwise behind
- * a whole run under the handle's calibration (wholeKind 1).  verb: what the pass does to the enqueue, oneCal / cams: the entry points of
- * either kind, for the messages.  SSD_E_ARG before anything is launched or copied. */
+/* ---- passes the handle keeps in call order (ssd_ordered_pass) ---------------------------------------------- */
+
+/* the record's events, on first use: the one behind a call, and for a timed call the two around its span (on failure the record is as it was) */
+static int pass_make(ssd_ordered_pass &p, bool timing, const std::string &me)
+{
+  if(!p.done)
+  {
+    Event done;
+    const hipError_t e = done.create(hipEventDisableTiming);
+    if(e != hipSuccess)
+      return hip_fail(e, me + ": its event: ");
+    p.done = std::move(done);
+  }
+  if(timing && p.ev.empty())
+    HIP_TRY(make_events(p.ev, 2, hipEventDefault));
+  return SSD_OK;
+}
+
+/* a call on stream s: on another stream than the call before it goes behind that one, so that calls run in the order they were made and
+ * the last call's event covers every call so far */
+static int pass_open(ssd_ordered_pass &p, hipStream_t s, bool timing, const std::string &me)
+{
+  const int rc = pass_make(p, timing, me);
+  if(rc) return rc;
+  if(p.haveLast && s != p.lastStream)
+    HIP_TRY(hipStreamWaitEvent(s, p.done, 0));
+  p.haveLast = true;
+  p.lastStream = s;
+  return SSD_OK;
+}
+
+/* where the timed span of a timed call starts */
+static int pass_start(ssd_ordered_pass &p, hipStream_t s, bool timing)
+{
+  if(timing) HIP_TRY(hipEventRecord(p.ev[0], s));
+  return SSD_OK;
+}
+
+/* ... and the call's end */
+static int pass_close(ssd_ordered_pass &p, hipStream_t s, bool timing)
+{
+  if(timing) HIP_TRY(hipEventRecord(p.ev[1], s));
+  p.timed = timing;
+  HIP_TRY(hipEventRecord(p.done, s));
+  return SSD_OK;
+}
+
+/* the host waits for the last call (ssd_fetch_*; `none`: the refusal where there was no call) */
+static int pass_wait(ssd_handle *h, ssd_ordered_pass ssd_handle::*pass, const char *who, const char *none)
+{
+  if(!h)
+    return fail(SSD_E_ARG, std::string(who) + ": null handle");
+  if(!(h->*pass).haveLast)
+    return fail(SSD_E_ARG, std::string(who) + ": " + none);
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipEventSynchronize((h->*pass).done));
+  return SSD_OK;
+}
+
+/* the milliseconds of the last call's timed span, 0 where it was not timed (ssd_get_*_time; enqueue: the pass's entry point, for the refusal) */
+static int pass_time(ssd_handle *h, ssd_ordered_pass ssd_handle::*pass, const char *who, const char *enqueue, float *ms)
+{
+  if(!h || !ms)
+    return fail(SSD_E_ARG, std::string(who) + ": null");
+  ssd_ordered_pass &p = h->*pass;
+  if(!p.haveLast)
+    return fail(SSD_E_ARG, std::string(who) + ": no " + enqueue + " yet");
+  *ms = 0.0f;
+  if(!p.timed)
+    return SSD_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipEventSynchronize(p.ev[1]));
+  HIP_TRY(hipEventElapsedTime(ms, p.ev[0], p.ev[1]));
+  return SSD_OK;
+}
+
+/* What a pass behind the handle's last whole enqueue is held to - the refit (section 7g, 7h), the clearance pass (section 7m) and the tread
+ * grid (section 7n) alike: `cameras` = behind a whole cameras batch (wholeKind 2), under the table and the index that batch left in its
+ * workspace; otherwise behind a whole run under the handle's calibration (wholeKind 1).  verb: what the pass does to the enqueue, oneCal /
+ * cams: the entry points of either kind, for the messages; needResults: the pass reads the batch's result records. */
 struct BehindWhole
 {
   const char *verb, *oneCal, *cams;
+  bool needResults;
 };
-static int check_behind_whole(const ssd_handle *h, const std::string &me, const BehindWhole &w, bool cameras, const void *d_frames,
-                              size_t frame_stride_bytes, int nframes, int input)
+
+/* what the entry of such a pass hands to its launches */
+struct FollowPass
+{
+  ssd_lane *L;                                   /* the workspace of the batch */
+  hipStream_t s;                                 /* the stream the pass runs on */
+  bool timing;                                   /* this call is timed */
+  CameraSel camSel;                              /* (B points into it) */
+  std::optional<Batch> B;                        /* set by follow_enter */
+  int chunk;                                     /* the labels' */
+};
+
+extern "C++"
+{
+/* The entry of a pass behind the handle's last whole enqueue, the pass's own refusals behind it.  The refusals (SSD_E_ARG, or SSD_E_HIP
+ * for a handle that is not whole, before anything is launched or copied), the record's events on first use, then the stream: the caller's
+ * with one workspace (a switch of streams is ordered by the lane's event), the lane's own with several (behind what the caller's stream
+ * holds now, as an enqueue is).  `first(s)`, if any, is the pass's own first-use work and waits, in front of pass_open on that stream. */
+template<class First>
+static int follow_enter(ssd_handle *h, const std::string &me, const BehindWhole &w, ssd_ordered_pass ssd_handle::*pass, bool cameras, const void *d_frames,
+                        size_t frame_stride_bytes, int nframes, void *stream, int input, FollowPass &f, First first)
 {
   if(input != SSD_INPUT_VERTICES && input != SSD_INPUT_DEPTH16)
     return fail(SSD_E_ARG, me + ": input must be SSD_INPUT_VERTICES or SSD_INPUT_DEPTH16");
@@ -2244,32 +2410,54 @@ static int check_behind_whole(const ssd_handle *h, const std::string &me, const 
     return fail(SSD_E_ARG, me + ": nframes is not the last enqueue's");
   if(depthInput != h->wholeDepth || d_frames != h->wholeFrames || frame_stride_bytes != h->wholeStride)
     return fail(SSD_E_ARG, me + ": input, frames or stride are not the last enqueue's");
-  const ssd_lane &L = h->lane[h->lastLane];
+  ssd_lane &L = h->lane[h->lastLane];
   if(!L.haveLast || !L.dState || !L.dTileMasks || (!cameras && depthInput && !h->dDepthMaps) || (cameras && (!h->dCams || !L.dCamIndex)))
     return fail(SSD_E_HIP, me + ": the handle's workspace is incomplete (internal)");
-  return SSD_OK;
-}
-
-/* ... and the stream it runs on, behind the batch: the caller's with one workspace (a switch of streams is ordered by the lane's event),
- * the lane's own with several (behind what the caller's stream holds now, as an enqueue is) */
-static int stream_behind_whole(ssd_handle *h, ssd_lane &L, void *stream, hipStream_t &s)
-{
-  s = static_cast<hipStream_t>(stream);
+  if(w.needResults && !h->wholeResults)
+    return fail(SSD_E_HIP, me + ": the last enqueue's result records are missing (internal)");
+  HIP_TRY(hipSetDevice(h->device));
+  f.L = &L;
+  f.timing = h->timing && !h->ev.empty();
+  int rc = pass_make(h->*pass, f.timing, me);
+  if(rc) return rc;
+  f.s = static_cast<hipStream_t>(stream);
   if(h->depth == 1)
   {
-    if(s != L.lastStream)
-      HIP_TRY(hipStreamWaitEvent(s, L.done, 0));
+    if(f.s != L.lastStream)
+      HIP_TRY(hipStreamWaitEvent(f.s, L.done, 0));
   }
   else
   {
-    HIP_TRY(hipEventRecord(L.in, s));
-    s = L.stream;
-    HIP_TRY(hipStreamWaitEvent(s, L.in, 0));
+    HIP_TRY(hipEventRecord(L.in, f.s));
+    f.s = L.stream;
+    HIP_TRY(hipStreamWaitEvent(f.s, L.in, 0));
   }
+  rc = first(f.s);
+  if(!rc) rc = pass_open(h->*pass, f.s, f.timing, me);
+  if(rc) return rc;
+  /* a cameras batch: the table as the batch read it, the index where the batch's own copy left it */
+  f.camSel = CameraSel{ h->dCams, L.dCamIndex, h->camsNeedChecks };
+  f.B.emplace(make_batch(h, h->P, L, d_frames, frame_stride_bytes, nframes, depthInput, f.s, cameras ? &f.camSel : nullptr));
+  f.chunk = choose_chunk(h->tune, h->P.nPoints, nframes);
   return SSD_OK;
 }
 
-static const BehindWhole kRefitBehind{ "refit", "ssd_enqueue_surface_refit", "ssd_enqueue_cameras_surface_refit" };
+} // extern "C++"
+
+/* ... and its exit, behind the pass's last launch.  The workspace is in use until here: whatever takes it next, on whichever stream, goes
+ * behind the pass */
+static int follow_leave(ssd_handle *h, ssd_ordered_pass ssd_handle::*pass, const FollowPass &f)
+{
+  const int rc = pass_close(h->*pass, f.s, f.timing);
+  if(rc) return rc;
+  HIP_TRY(hipEventRecord(f.L->done, f.s));
+  f.L->lastStream = f.s;
+  return SSD_OK;
+}
+
+static int no_first_use(hipStream_t) { return SSD_OK; }
+
+static const BehindWhole kRefitBehind{ "refit", "ssd_enqueue_surface_refit", "ssd_enqueue_cameras_surface_refit", false };
 
 /* all refit entry points */
 static int refit_enqueue_impl(ssd_handle *h, const char *who, bool cameras, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream,
@@ -2283,43 +2471,36 @@ static int refit_enqueue_impl(ssd_handle *h, const char *who, bool cameras, cons
     const int rule = check_gate_rule(who, gates.kSigma, gates.gateMin);
     if(rule) return rule;
   }
-  int rc = check_behind_whole(h, me, kRefitBehind, cameras, d_frames, frame_stride_bytes, nframes, input);
-  if(rc) return rc;
-  const bool depthInput = input == SSD_INPUT_DEPTH16;
-  ssd_lane &L = h->lane[h->lastLane];
-  HIP_TRY(hipSetDevice(h->device));
-  rc = refit_prepare(h);
-  if(rc) return rc;
-  if(gates.cameraGate)
+  ssd_ordered_pass &P = h->refitPass;
+  FollowPass f;
+  /* The device gates are one set, which is why the refit is an ordered pass: on another stream than the previous pass's (another
+   * workspace's, or the caller changed streams) this call goes behind that pass, which still reads them - so refits run in the order of
+   * their calls, whatever workspace they follow.  Its own: the buffers, and the pinned gates of the previous call gone over */
+  int rc = follow_enter(h, me, kRefitBehind, &ssd_handle::refitPass, cameras, d_frames, frame_stride_bytes, nframes, stream, input, f, [&](hipStream_t)
   {
-    rc = fold_prepare(h);
-    if(rc) return rc;
-  }
-  const bool timing = h->timing && !h->ev.empty();
-  if(timing && h->evRefit.empty())
-    HIP_TRY(make_events(h->evRefit, 2, hipEventDefault));
-  hipStream_t s;
-  rc = stream_behind_whole(h, L, stream, s);
+    int own = refit_prepare(h);
+    if(!own && gates.cameraGate) own = fold_prepare(h);
+    if(own) return own;
+    if(P.haveLast && gates.host)
+      HIP_TRY(hipEventSynchronize(h->refitGatesCopied));
+    return static_cast<int>(SSD_OK);
+  });
   if(rc) return rc;
-  if(h->refitHaveLast)
-  {
-    if(gates.host)
-      HIP_TRY(hipEventSynchronize(h->refitGatesCopied));            /* the pinned gates of the previous call have gone over */
-    /* the device gates are one set: on another stream than the previous pass's (another workspace's, or the caller changed streams) this
-     * call goes behind that pass, which still reads them - so refits run in the order of their calls, whatever workspace they follow */
-    if(s != h->refitLastStream)
-      HIP_TRY(hipStreamWaitEvent(s, h->refitDone, 0));
-  }
+  ssd_lane &L = *f.L;
+  hipStream_t s = f.s;
   if(gates.host)
   {
     std::memcpy(h->hRefitGates, gates.host, sizeof(ssd_frame_gates) * static_cast<size_t>(nframes));
     HIP_TRY(hipMemcpyAsync(h->dRefitGates, h->hRefitGates, sizeof(ssd_frame_gates) * static_cast<size_t>(nframes), hipMemcpyHostToDevice, s));
     HIP_TRY(hipEventRecord(h->refitGatesCopied, s));
+    rc = pass_start(P, s, f.timing);
+    if(rc) return rc;
   }
   else
   {
     /* the gates on the device, in front of the zeroing (d_prev may be d_out): no copy, no wait; the pass's time includes the kernel */
-    if(timing) HIP_TRY(hipEventRecord(h->evRefit[0], s));
+    rc = pass_start(P, s, f.timing);
+    if(rc) return rc;
     launch_surface_gates(gates.dPrev, nframes, gates.minPoints, gates.kSigma, gates.gateMin, h->dRefitGates, s);
     HIP_TRY(hipGetLastError());
     if(gates.cameraGate)
@@ -2333,23 +2514,10 @@ static int refit_enqueue_impl(ssd_handle *h, const char *who, bool cameras, cons
       HIP_TRY(hipGetLastError());
     }
   }
-  h->refitHaveLast = true;
-  h->refitLastStream = s;
-  /* a cameras batch: the table as the batch read it, the index where the batch's own copy left it */
-  const CameraSel camSel{ h->dCams, L.dCamIndex, h->camsNeedChecks };
-  const Batch B = make_batch(h, h->P, L, d_frames, frame_stride_bytes, nframes, depthInput, s, cameras ? &camSel : nullptr);
-  const int chunk = choose_chunk(h->tune, h->P.nPoints, nframes);   /* the first pass's */
-  if(timing && gates.host) HIP_TRY(hipEventRecord(h->evRefit[0], s));
   HIP_TRY(hipMemsetAsync(d_out, 0, sizeof(ssd_frame_moments) * static_cast<size_t>(nframes), s));
-  launch_surface_refit(B, chunk, h->dRefitGates, d_out);
+  launch_surface_refit(*f.B, f.chunk, h->dRefitGates, d_out);
   HIP_TRY(hipGetLastError());
-  if(timing) HIP_TRY(hipEventRecord(h->evRefit[1], s));
-  h->refitTimed = timing;
-  HIP_TRY(hipEventRecord(h->refitDone, s));
-  /* the workspace is in use until here: whatever takes it next, on whichever stream, goes behind the pass */
-  HIP_TRY(hipEventRecord(L.done, s));
-  L.lastStream = s;
-  return SSD_OK;
+  return follow_leave(h, &ssd_handle::refitPass, f);
 }
 
 int ssd_enqueue_surface_refit(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream,
@@ -2446,28 +2614,12 @@ int ssd_enqueue_cameras_surface_refit_folded(ssd_handle *h, const void *d_frames
 
 int ssd_fetch_surface_refit(ssd_handle *h, void *)
 {
-  if(!h)
-    return fail(SSD_E_ARG, "ssd_fetch_surface_refit: null handle");
-  if(!h->refitHaveLast)
-    return fail(SSD_E_ARG, "ssd_fetch_surface_refit: no ssd_enqueue_surface_refit to wait for");
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipEventSynchronize(h->refitDone));
-  return SSD_OK;
+  return pass_wait(h, &ssd_handle::refitPass, "ssd_fetch_surface_refit", "no ssd_enqueue_surface_refit to wait for");
 }
 
 int ssd_get_surface_refit_time(ssd_handle *h, float *ms)
 {
-  if(!h || !ms)
-    return fail(SSD_E_ARG, "ssd_get_surface_refit_time: null");
-  if(!h->refitHaveLast)
-    return fail(SSD_E_ARG, "ssd_get_surface_refit_time: no ssd_enqueue_surface_refit yet");
-  *ms = 0.0f;
-  if(!h->refitTimed)
-    return SSD_OK;
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipEventSynchronize(h->evRefit[1]));
-  HIP_TRY(hipEventElapsedTime(ms, h->evRefit[0], h->evRefit[1]));
-  return SSD_OK;
+  return pass_time(h, &ssd_handle::refitPass, "ssd_get_surface_refit_time", "ssd_enqueue_surface_refit", ms);
 }
 
 /* both host entry points, the caller's own refusals behind them: camOf (checked by check_cameras) = a cameras batch, each slice with its
@@ -2636,8 +2788,8 @@ int ssd_process_host_cameras_drift(ssd_handle *h, const void *frames, int nframe
   rc = labels_prepare(h, static_cast<size_t>(feed.slice) * sizeof(ssd_frame_moments));
   if(!rc) rc = fold_prepare(h);
   if(rc) return rc;
-  if(h->refitHaveLast)
-    HIP_TRY(hipEventSynchronize(h->refitDone));                     /* a folded pass still on its way owns the fold buffer */
+  if(h->refitPass.haveLast)
+    HIP_TRY(hipEventSynchronize(h->refitPass.done));                /* a folded pass still on its way owns the fold buffer */
   ssd_frame_moments *dFirst = reinterpret_cast<ssd_frame_moments *>(h->labelStage[0].get()), *dRefit = reinterpret_cast<ssd_frame_moments *>(h->labelStage[1].get());
   const int ncams = static_cast<int>(h->camParams.size());
   hipStream_t s = nullptr;
@@ -2727,60 +2879,29 @@ int ssd_clearance_host(const ssd_config *cfg, const ssd_calibration *cal, int in
                        const ssd_frame_result *result, int ground, const ssd_clearance_rule *rule, ssd_frame_moments *out, uint8_t *mask)
 {
   const std::string who("ssd_clearance_host");
-  if(!cfg || !cal || !frame || !result || cfg->width <= 0 || cfg->height <= 0)
-    return fail(SSD_E_ARG, who + ": bad argument");
-  if(input != SSD_INPUT_VERTICES && input != SSD_INPUT_DEPTH16)
-    return fail(SSD_E_ARG, who + ": input must be SSD_INPUT_VERTICES or SSD_INPUT_DEPTH16");
-  const bool depth = input == SSD_INPUT_DEPTH16;
-  if(depth && (!intr || !good_intrinsics(*intr)))
-    return fail(SSD_E_ARG, who + ": depth input needs intrinsics");
-  if(result->n_steps < 0 || result->n_steps > SSD_MAX_STEPS)
-    return fail(SSD_E_ARG, who + ": n_steps must lie in 0 .. SSD_MAX_STEPS");
-  int rc = check_clearance_rule(who, rule);
+  int rc = host_frame_check(who, cal && result, cfg, input, intr, frame, result ? result->n_steps : 0, "n_steps", false);
+  if(!rc) rc = check_clearance_rule(who, rule);
   if(rc) return rc;
-  const int W = cfg->width, H = cfg->height;
-  const size_t nPoints = static_cast<size_t>(W) * H;
   std::vector<float> deprojected;
-  const float *xyz = static_cast<const float *>(frame);
-  if(depth)
-  {
-    deprojected.resize(3 * nPoints);
-    rc = ssd_deproject_host(intr, W, H, static_cast<const uint16_t *>(frame), deprojected.data());
-    if(rc) return rc;
-    xyz = deprojected.data();
-  }
+  const float *xyz;
+  rc = host_frame_xyz(cfg, input, intr, frame, deprojected, xyz);
+  if(rc) return rc;
   if(out)
     std::memset(out, 0, sizeof(*out));
   if(mask)
-    std::memset(mask, 0, nPoints);
-  const int n = (result->status & SSD_ST_THROW) ? 0 : result->n_steps;
+    std::memset(mask, 0, static_cast<size_t>(cfg->width) * cfg->height);
+  const HostSurfaces T(result, cal, rule->margin);
+  const int n = T.n;
   if(n == 0)
     return SSD_OK;                               /* no occupant: an all-zero record, as the surface moments' */
-  ClearanceSurface S[SSD_MAX_STEPS];
-  for(int k = 0; k < n; k++)
-    clearance_surface(result->steps[k], rule->margin, S[k]);
-  const ClearanceWorld X{ { cal->r2[0], cal->r2[1], cal->r2[2], cal->r2[3] }, { cal->t2[0], cal->t2[1] }, cal->world_z };
-  const double *a = cal->a, *b = cal->b;
   long long acc[SSD_MAX_STEPS][kGroundSums + 1] = {};
-  for(size_t i = 0; i < nPoints; i++)
+  T.walk(cfg, cal, xyz, [&](size_t i, double x, double y, double z, double ex, double ey, double ez)
   {
-    const float fx = xyz[3 * i], fy = xyz[3 * i + 1], fz = xyz[3 * i + 2];
-    if(!(fz > 0.0f))
-      continue;
-    const double x = fx, y = fy, z = fz;
-    const double wx = ((a[0] * x + a[1] * y) + a[2] * z) + b[0];
-    const double wy = ((a[3] * x + a[4] * y) + a[5] * z) + b[1];
-    const double wz = ((a[6] * x + a[7] * y) + a[8] * z) + b[2];
-    if(!(wx > cfg->x_min && wx < cfg->x_max && wy > cfg->y_min && wy < cfg->y_max && wz > cfg->z_min && wz < cfg->z_max))
-      continue;
-    const double ez = wz + X.worldZ;
-    if(clearance_in_slab(S, n, ez, rule->lo))
-      continue;
-    double ex, ey;
-    clearance_external(X, wx, wy, ex, ey);
-    const int k = clearance_lowest(S, (1u << n) - 1u, ex, ey, ez, rule->lo, rule->hi);      /* every surface is a candidate; n <= 17 */
+    if(clearance_in_slab(T.S, n, ez, rule->lo))
+      return;
+    const int k = clearance_lowest(T.S, (1u << n) - 1u, ex, ey, ez, rule->lo, rule->hi);      /* every surface is a candidate; n <= 17 */
     if(k < 0)
-      continue;
+      return;
     if(mask)
       mask[i] = static_cast<uint8_t>(k + 1);
     const double rx = moment_round(x), ry = moment_round(y), rz = moment_round(z);
@@ -2788,7 +2909,7 @@ int ssd_clearance_host(const ssd_config *cfg, const ssd_calibration *cal, int in
       moment_add(rx, ry, rz, acc[k]);
     else
       acc[k][kGroundSums] += 1;
-  }
+  });
   if(out)
   {
     out->n_surfaces = n;
@@ -2860,9 +2981,9 @@ int ssd_clearance_solve(const ssd_frame_moments *moments, const ssd_frame_result
   return SSD_OK;
 }
 
-static const BehindWhole kClearanceBehind{ "clear", "ssd_enqueue_clearance", "ssd_enqueue_cameras_clearance" };
+static const BehindWhole kClearanceBehind{ "clear", "ssd_enqueue_clearance", "ssd_enqueue_cameras_clearance", true };
 
-/* both entry points of the pass: the refit's refusals (check_behind_whole), then the pass's own, before anything is launched */
+/* both entry points of the pass: its own refusals, then the shared entry's, before anything is launched */
 static int clearance_enqueue_impl(ssd_handle *h, const char *who, bool cameras, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream,
                                   int input, const ssd_clearance_rule *rule, ssd_frame_moments *d_out, uint8_t *d_mask, size_t mask_stride)
 {
@@ -2873,54 +2994,22 @@ static int clearance_enqueue_impl(ssd_handle *h, const char *who, bool cameras, 
   if(rc) return rc;
   if(d_mask && mask_stride < static_cast<size_t>(h->P.nPoints))
     return fail(SSD_E_ARG, me + ": mask_stride is smaller than width * height");
-  rc = check_behind_whole(h, me, kClearanceBehind, cameras, d_frames, frame_stride_bytes, nframes, input);
+  FollowPass f;
+  rc = follow_enter(h, me, kClearanceBehind, &ssd_handle::clearPass, cameras, d_frames, frame_stride_bytes, nframes, stream, input, f, no_first_use);
+  if(!rc) rc = pass_start(h->clearPass, f.s, f.timing);
   if(rc) return rc;
-  if(!h->wholeResults)
-    return fail(SSD_E_HIP, me + ": the last enqueue's result records are missing (internal)");
-  const bool depthInput = input == SSD_INPUT_DEPTH16;
-  ssd_lane &L = h->lane[h->lastLane];
-  HIP_TRY(hipSetDevice(h->device));
-  if(!h->clearDone)
-  {
-    Event done;
-    const hipError_t e = done.create(hipEventDisableTiming);
-    if(e != hipSuccess)
-      return hip_fail(e, me + ": its event: ");
-    h->clearDone = std::move(done);
-  }
-  const bool timing = h->timing && !h->ev.empty();
-  if(timing && h->evClear.empty())
-    HIP_TRY(make_events(h->evClear, 2, hipEventDefault));
-  hipStream_t s;
-  rc = stream_behind_whole(h, L, stream, s);
-  if(rc) return rc;
-  /* a pass on another stream than the one before goes behind it: the last pass's event then covers every pass so far */
-  if(h->clearHaveLast && s != h->clearLastStream)
-    HIP_TRY(hipStreamWaitEvent(s, h->clearDone, 0));
-  h->clearHaveLast = true;
-  h->clearLastStream = s;
-  const CameraSel camSel{ h->dCams, L.dCamIndex, h->camsNeedChecks };
-  const Batch B = make_batch(h, h->P, L, d_frames, frame_stride_bytes, nframes, depthInput, s, cameras ? &camSel : nullptr);
-  const int chunk = choose_chunk(h->tune, h->P.nPoints, nframes);   /* the labels' and the refit's */
-  if(timing) HIP_TRY(hipEventRecord(h->evClear[0], s));
-  HIP_TRY(hipMemsetAsync(d_out, 0, sizeof(ssd_frame_moments) * static_cast<size_t>(nframes), s));
+  HIP_TRY(hipMemsetAsync(d_out, 0, sizeof(ssd_frame_moments) * static_cast<size_t>(nframes), f.s));
   if(d_mask)
   {
     /* only the bytes below width * height of every stride are the pass's */
     if(mask_stride == static_cast<size_t>(h->P.nPoints))
-      HIP_TRY(hipMemsetAsync(d_mask, 0, mask_stride * static_cast<size_t>(nframes), s));
+      HIP_TRY(hipMemsetAsync(d_mask, 0, mask_stride * static_cast<size_t>(nframes), f.s));
     else
-      HIP_TRY(hipMemset2DAsync(d_mask, mask_stride, 0, static_cast<size_t>(h->P.nPoints), static_cast<size_t>(nframes), s));
+      HIP_TRY(hipMemset2DAsync(d_mask, mask_stride, 0, static_cast<size_t>(h->P.nPoints), static_cast<size_t>(nframes), f.s));
   }
-  launch_clearance(B, chunk, h->wholeResults, *rule, d_out, d_mask, mask_stride);
+  launch_clearance(*f.B, f.chunk, h->wholeResults, *rule, d_out, d_mask, mask_stride);
   HIP_TRY(hipGetLastError());
-  if(timing) HIP_TRY(hipEventRecord(h->evClear[1], s));
-  h->clearTimed = timing;
-  HIP_TRY(hipEventRecord(h->clearDone, s));
-  /* the workspace is in use until here: whatever takes it next, on whichever stream, goes behind the pass */
-  HIP_TRY(hipEventRecord(L.done, s));
-  L.lastStream = s;
-  return SSD_OK;
+  return follow_leave(h, &ssd_handle::clearPass, f);
 }
 
 int ssd_enqueue_clearance(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream, int input,
@@ -2937,32 +3026,51 @@ int ssd_enqueue_cameras_clearance(ssd_handle *h, const void *d_frames, size_t fr
 
 int ssd_fetch_clearance(ssd_handle *h, void *)
 {
-  if(!h)
-    return fail(SSD_E_ARG, "ssd_fetch_clearance: null handle");
-  if(!h->clearHaveLast)
-    return fail(SSD_E_ARG, "ssd_fetch_clearance: no ssd_enqueue_clearance to wait for");
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipEventSynchronize(h->clearDone));
-  return SSD_OK;
+  return pass_wait(h, &ssd_handle::clearPass, "ssd_fetch_clearance", "no ssd_enqueue_clearance to wait for");
 }
 
 int ssd_get_clearance_time(ssd_handle *h, float *ms)
 {
-  if(!h || !ms)
-    return fail(SSD_E_ARG, "ssd_get_clearance_time: null");
-  if(!h->clearHaveLast)
-    return fail(SSD_E_ARG, "ssd_get_clearance_time: no ssd_enqueue_clearance yet");
-  *ms = 0.0f;
-  if(!h->clearTimed)
-    return SSD_OK;
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipEventSynchronize(h->evClear[1]));
-  HIP_TRY(hipEventElapsedTime(ms, h->evClear[0], h->evClear[1]));
+  return pass_time(h, &ssd_handle::clearPass, "ssd_get_clearance_time", "ssd_enqueue_clearance", ms);
+}
+
+extern "C++"
+{
+/* The host-fed loop of a pass behind each slice's whole enqueue (the clearance pass, the tread grid).  Per slice, while it is still in its
+ * staging buffer: the enqueue, pass(buf, n) on the compute stream, the results, copy(first, n, s) - the pass's staged records to the host,
+ * behind the pass on the stream it ran on - and solve(first, i) for each of its n frames.  The body blocks on the pass, so the next slice's
+ * copy goes out in front of it, beside this slice's kernels, and the staging buffers are free for the next slice */
+template<class Pass, class Copy, class Solve>
+static int process_host_follow(ssd_handle *h, SliceFeed &feed, const uint16_t *camOf, ssd_frame_result *results, Pass pass, Copy copy, Solve solve)
+{
+  for(int c = 0; c < feed.slices(); c++)
+  {
+    const void *buf;
+    int done, n;
+    int rc = feed.stage(c);
+    if(!rc) rc = feed.stage(c + 1);
+    if(!rc) rc = feed.ready(c, buf, done, n);
+    if(rc) return rc;
+    rc = enqueue_impl(h, buf, feed.f.devFrameBytes, n, h->ingestCompute, SSD_STAGE_ALL, feed.f.depth, nullptr, 0, camOf ? camOf + done : nullptr);
+    if(!rc) rc = pass(buf, n);
+    if(!rc) rc = ssd_fetch_back(h, results + done, n, 0);
+    if(rc) return rc;
+    hipStream_t s = h->lane[h->lastLane].lastStream;
+    rc = copy(done, n, s);
+    if(rc) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    rc = feed.consumed(c, s);
+    for(int i = 0; i < n && !rc; i++)
+      rc = solve(done, i);
+    if(rc) return rc;
+  }
   return SSD_OK;
 }
 
-/* both host entry points, the callers' own refusals behind them: per slice, while it is still in its staging buffer, the enqueue, the
- * pass, both fetches and the solve; the records go out through the first label staging buffer, the mask through the second */
+} // extern "C++"
+
+/* both host entry points, the callers' own refusals behind them: the records go out through the first label staging buffer, the mask
+ * through the second */
 static int process_host_clearance_impl(ssd_handle *h, const char *who, const void *frames, int nframes, const uint16_t *camOf, int input,
                                        const ssd_clearance_rule *rule, int min_support, ssd_frame_result *results, ssd_frame_moments *moments,
                                        uint8_t *mask, ssd_frame_clearance *out)
@@ -2981,35 +3089,23 @@ static int process_host_clearance_impl(ssd_handle *h, const char *who, const voi
   uint8_t *dMask = mask ? h->labelStage[1].get() : nullptr;
   std::vector<ssd_frame_moments> own;
   moments = moments_or_own(moments, own, nframes);
-  for(int c = 0; c < feed.slices(); c++)
-  {
-    const void *buf;
-    int done, n;
-    /* the body blocks on the pass, so the next slice's copy goes out in front of it, beside this slice's kernels */
-    rc = feed.stage(c);
-    if(!rc) rc = feed.stage(c + 1);
-    if(!rc) rc = feed.ready(c, buf, done, n);
-    if(rc) return rc;
-    rc = enqueue_impl(h, buf, feed.f.devFrameBytes, n, h->ingestCompute, SSD_STAGE_ALL, feed.f.depth, nullptr, 0, camOf ? camOf + done : nullptr);
-    if(!rc) rc = clearance_enqueue_impl(h, who, camOf != nullptr, buf, feed.f.devFrameBytes, n, h->ingestCompute, input, rule, dRecords, dMask, nPoints);
-    if(!rc) rc = ssd_fetch_back(h, results + done, n, 0);
-    if(rc) return rc;
-    /* behind the pass on the stream it ran on; the body waits, so the staging buffers are free for the next slice */
-    hipStream_t s = h->lane[h->lastLane].lastStream;
-    HIP_TRY(hipMemcpyAsync(moments + done, dRecords, sizeof(ssd_frame_moments) * static_cast<size_t>(n), hipMemcpyDeviceToHost, s));
-    if(mask)
-      HIP_TRY(hipMemcpyAsync(mask + static_cast<size_t>(done) * nPoints, dMask, static_cast<size_t>(n) * nPoints, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    rc = feed.consumed(c, s);
-    if(rc) return rc;
-    for(int i = 0; i < n; i++)
+  return process_host_follow(h, feed, camOf, results,
+    [&](const void *buf, int n)
     {
-      const ssd_calibration cal = frame_calibration(h, camOf, done + i);
-      rc = ssd_clearance_solve(moments + done + i, results + done + i, &cal, min_support, out + done + i);
-      if(rc) return rc;
-    }
-  }
-  return SSD_OK;
+      return clearance_enqueue_impl(h, who, camOf != nullptr, buf, feed.f.devFrameBytes, n, h->ingestCompute, input, rule, dRecords, dMask, nPoints);
+    },
+    [&](int first, int n, hipStream_t s)
+    {
+      HIP_TRY(hipMemcpyAsync(moments + first, dRecords, sizeof(ssd_frame_moments) * static_cast<size_t>(n), hipMemcpyDeviceToHost, s));
+      if(mask)
+        HIP_TRY(hipMemcpyAsync(mask + static_cast<size_t>(first) * nPoints, dMask, static_cast<size_t>(n) * nPoints, hipMemcpyDeviceToHost, s));
+      return static_cast<int>(SSD_OK);
+    },
+    [&](int first, int i)
+    {
+      const ssd_calibration cal = frame_calibration(h, camOf, first + i);
+      return ssd_clearance_solve(moments + first + i, results + first + i, &cal, min_support, out + first + i);
+    });
 }
 
 int ssd_process_host_clearance(ssd_handle *h, const void *frames, int nframes, int input, const ssd_clearance_rule *rule, int min_support,
@@ -3046,63 +3142,31 @@ int ssd_tread_grid_host(const ssd_config *cfg, const ssd_calibration *cal, int i
                         const ssd_frame_result *result, int ground, const ssd_tread_grid_rule *rule, ssd_frame_tread_grid *out)
 {
   const std::string who("ssd_tread_grid_host");
-  if(!cfg || !cal || !frame || !result || !out || cfg->width <= 0 || cfg->height <= 0)
-    return fail(SSD_E_ARG, who + ": bad argument");
-  if(input != SSD_INPUT_VERTICES && input != SSD_INPUT_DEPTH16)
-    return fail(SSD_E_ARG, who + ": input must be SSD_INPUT_VERTICES or SSD_INPUT_DEPTH16");
-  const bool depth = input == SSD_INPUT_DEPTH16;
-  if(depth && (!intr || !good_intrinsics(*intr)))
-    return fail(SSD_E_ARG, who + ": depth input needs intrinsics");
-  if(result->n_steps < 0 || result->n_steps > SSD_MAX_STEPS)
-    return fail(SSD_E_ARG, who + ": n_steps must lie in 0 .. SSD_MAX_STEPS");
-  int rc = check_tread_grid_rule(who, rule);
+  int rc = host_frame_check(who, cal && result && out, cfg, input, intr, frame, result ? result->n_steps : 0, "n_steps", false);
+  if(!rc) rc = check_tread_grid_rule(who, rule);
   if(rc) return rc;
-  const int W = cfg->width, H = cfg->height;
-  const size_t nPoints = static_cast<size_t>(W) * H;
   std::vector<float> deprojected;
-  const float *xyz = static_cast<const float *>(frame);
-  if(depth)
-  {
-    deprojected.resize(3 * nPoints);
-    rc = ssd_deproject_host(intr, W, H, static_cast<const uint16_t *>(frame), deprojected.data());
-    if(rc) return rc;
-    xyz = deprojected.data();
-  }
+  const float *xyz;
+  rc = host_frame_xyz(cfg, input, intr, frame, deprojected, xyz);
+  if(rc) return rc;
   std::memset(out, 0, sizeof(*out));
-  const int n = (result->status & SSD_ST_THROW) ? 0 : result->n_steps;
+  const HostSurfaces T(result, cal, rule->clearance.margin);
+  const int n = T.n;
   if(n == 0)
     return SSD_OK;                               /* nothing counted: an all-zero record, as the clearance moments' */
   out->n_surfaces = n;
   out->ground = ground ? 1 : 0;
   const double lo = rule->clearance.lo, hi = rule->clearance.hi;
-  ClearanceSurface S[SSD_MAX_STEPS];
   TreadGridAxes G[SSD_MAX_STEPS];
   for(int k = 0; k < n; k++)
-  {
-    clearance_surface(result->steps[k], rule->clearance.margin, S[k]);
-    tread_grid_axes(S[k], G[k]);
-  }
-  const ClearanceWorld X{ { cal->r2[0], cal->r2[1], cal->r2[2], cal->r2[3] }, { cal->t2[0], cal->t2[1] }, cal->world_z };
-  const double *a = cal->a, *b = cal->b;
+    tread_grid_axes(T.S[k], G[k]);
   const unsigned int all = (1u << n) - 1u;       /* every surface is a candidate; n <= 17 */
-  for(size_t i = 0; i < nPoints; i++)
+  T.walk(cfg, cal, xyz, [&](size_t, double, double, double, double ex, double ey, double ez)
   {
-    const float fx = xyz[3 * i], fy = xyz[3 * i + 1], fz = xyz[3 * i + 2];
-    if(!(fz > 0.0f))
-      continue;
-    const double x = fx, y = fy, z = fz;
-    const double wx = ((a[0] * x + a[1] * y) + a[2] * z) + b[0];
-    const double wy = ((a[3] * x + a[4] * y) + a[5] * z) + b[1];
-    const double wz = ((a[6] * x + a[7] * y) + a[8] * z) + b[2];
-    if(!(wx > cfg->x_min && wx < cfg->x_max && wy > cfg->y_min && wy < cfg->y_max && wz > cfg->z_min && wz < cfg->z_max))
-      continue;
-    const double ez = wz + X.worldZ;
-    double ex, ey;
-    clearance_external(X, wx, wy, ex, ey);
-    const bool tread = clearance_in_slab(S, n, ez, lo);
-    const int k = tread ? tread_grid_lowest(S, all, ex, ey, ez, lo) : clearance_lowest(S, all, ex, ey, ez, lo, hi);
+    const bool tread = clearance_in_slab(T.S, n, ez, lo);
+    const int k = tread ? tread_grid_lowest(T.S, all, ex, ey, ez, lo) : clearance_lowest(T.S, all, ex, ey, ez, lo, hi);
     if(k < 0)
-      continue;
+      return;
     ssd_tread_grid &g = out->s[k];
     int row, col;
     const bool in = tread_grid_cell(G[k], rule->cell, ex, ey, row, col);
@@ -3111,12 +3175,12 @@ int ssd_tread_grid_host(const ssd_config *cfg, const ssd_calibration *cal, int i
     else
     {
       (in ? g.occ[row][col] : g.n_occ_out) += 1u;
-      const int32_t t = tread_grid_top(ez, S[k].height);
+      const int32_t t = tread_grid_top(ez, T.S[k].height);
       int32_t &top = in ? g.top[row][col] : g.top_out;
       if(t > top)
         top = t;
     }
-  }
+  });
   return SSD_OK;
 }
 
@@ -3219,9 +3283,9 @@ int ssd_tread_grid_solve(const ssd_frame_tread_grid *grid, const ssd_frame_resul
   return SSD_OK;
 }
 
-static const BehindWhole kTreadGridBehind{ "grid", "ssd_enqueue_tread_grid", "ssd_enqueue_cameras_tread_grid" };
+static const BehindWhole kTreadGridBehind{ "grid", "ssd_enqueue_tread_grid", "ssd_enqueue_cameras_tread_grid", true };
 
-/* both entry points of the pass: its own refusals, then the refit's (check_behind_whole), before anything is launched */
+/* both entry points of the pass: its own refusals, then the shared entry's, before anything is launched */
 static int tread_grid_enqueue_impl(ssd_handle *h, const char *who, bool cameras, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream,
                                    int input, const ssd_tread_grid_rule *rule, ssd_frame_tread_grid *d_out)
 {
@@ -3230,46 +3294,14 @@ static int tread_grid_enqueue_impl(ssd_handle *h, const char *who, bool cameras,
     return fail(SSD_E_ARG, me + ": null argument");
   int rc = check_tread_grid_rule(me, rule);
   if(rc) return rc;
-  rc = check_behind_whole(h, me, kTreadGridBehind, cameras, d_frames, frame_stride_bytes, nframes, input);
+  FollowPass f;
+  rc = follow_enter(h, me, kTreadGridBehind, &ssd_handle::gridPass, cameras, d_frames, frame_stride_bytes, nframes, stream, input, f, no_first_use);
+  if(!rc) rc = pass_start(h->gridPass, f.s, f.timing);
   if(rc) return rc;
-  if(!h->wholeResults)
-    return fail(SSD_E_HIP, me + ": the last enqueue's result records are missing (internal)");
-  const bool depthInput = input == SSD_INPUT_DEPTH16;
-  ssd_lane &L = h->lane[h->lastLane];
-  HIP_TRY(hipSetDevice(h->device));
-  if(!h->gridDone)
-  {
-    Event done;
-    const hipError_t e = done.create(hipEventDisableTiming);
-    if(e != hipSuccess)
-      return hip_fail(e, me + ": its event: ");
-    h->gridDone = std::move(done);
-  }
-  const bool timing = h->timing && !h->ev.empty();
-  if(timing && h->evGrid.empty())
-    HIP_TRY(make_events(h->evGrid, 2, hipEventDefault));
-  hipStream_t s;
-  rc = stream_behind_whole(h, L, stream, s);
-  if(rc) return rc;
-  /* a pass on another stream than the one before goes behind it: the last pass's event then covers every pass so far */
-  if(h->gridHaveLast && s != h->gridLastStream)
-    HIP_TRY(hipStreamWaitEvent(s, h->gridDone, 0));
-  h->gridHaveLast = true;
-  h->gridLastStream = s;
-  const CameraSel camSel{ h->dCams, L.dCamIndex, h->camsNeedChecks };
-  const Batch B = make_batch(h, h->P, L, d_frames, frame_stride_bytes, nframes, depthInput, s, cameras ? &camSel : nullptr);
-  const int chunk = choose_chunk(h->tune, h->P.nPoints, nframes);   /* the labels', the refit's and the clearance pass's */
-  if(timing) HIP_TRY(hipEventRecord(h->evGrid[0], s));
-  HIP_TRY(hipMemsetAsync(d_out, 0, sizeof(ssd_frame_tread_grid) * static_cast<size_t>(nframes), s));
-  launch_tread_grid(B, chunk, h->wholeResults, *rule, d_out);
+  HIP_TRY(hipMemsetAsync(d_out, 0, sizeof(ssd_frame_tread_grid) * static_cast<size_t>(nframes), f.s));
+  launch_tread_grid(*f.B, f.chunk, h->wholeResults, *rule, d_out);
   HIP_TRY(hipGetLastError());
-  if(timing) HIP_TRY(hipEventRecord(h->evGrid[1], s));
-  h->gridTimed = timing;
-  HIP_TRY(hipEventRecord(h->gridDone, s));
-  /* the workspace is in use until here: whatever takes it next, on whichever stream, goes behind the pass */
-  HIP_TRY(hipEventRecord(L.done, s));
-  L.lastStream = s;
-  return SSD_OK;
+  return follow_leave(h, &ssd_handle::gridPass, f);
 }
 
 int ssd_enqueue_tread_grid(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream, int input,
@@ -3286,28 +3318,12 @@ int ssd_enqueue_cameras_tread_grid(ssd_handle *h, const void *d_frames, size_t f
 
 int ssd_fetch_tread_grid(ssd_handle *h, void *)
 {
-  if(!h)
-    return fail(SSD_E_ARG, "ssd_fetch_tread_grid: null handle");
-  if(!h->gridHaveLast)
-    return fail(SSD_E_ARG, "ssd_fetch_tread_grid: no ssd_enqueue_tread_grid to wait for");
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipEventSynchronize(h->gridDone));
-  return SSD_OK;
+  return pass_wait(h, &ssd_handle::gridPass, "ssd_fetch_tread_grid", "no ssd_enqueue_tread_grid to wait for");
 }
 
 int ssd_get_tread_grid_time(ssd_handle *h, float *ms)
 {
-  if(!h || !ms)
-    return fail(SSD_E_ARG, "ssd_get_tread_grid_time: null");
-  if(!h->gridHaveLast)
-    return fail(SSD_E_ARG, "ssd_get_tread_grid_time: no ssd_enqueue_tread_grid yet");
-  *ms = 0.0f;
-  if(!h->gridTimed)
-    return SSD_OK;
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipEventSynchronize(h->evGrid[1]));
-  HIP_TRY(hipEventElapsedTime(ms, h->evGrid[0], h->evGrid[1]));
-  return SSD_OK;
+  return pass_time(h, &ssd_handle::gridPass, "ssd_get_tread_grid_time", "ssd_enqueue_tread_grid", ms);
 }
 
 /* where a slice's records are staged: the first label staging buffer if it holds them as it stands, else a buffer of the pass's own
@@ -3332,8 +3348,7 @@ static int tread_grid_stage(ssd_handle *h, int slice, ssd_frame_tread_grid *&dRe
   return SSD_OK;
 }
 
-/* both host entry points, the callers' own refusals behind them: per slice, while it is still in its staging buffer, the enqueue, the
- * pass, both fetches and the solve */
+/* both host entry points, the callers' own refusals behind them */
 static int process_host_tread_grid_impl(ssd_handle *h, const char *who, const void *frames, int nframes, const uint16_t *camOf, int input,
                                         const ssd_tread_grid_rule *rule, int min_seen, int min_occ, double foot_along, double foot_deep,
                                         ssd_frame_result *results, ssd_frame_tread_grid *grids, ssd_frame_footholds *out)
@@ -3349,36 +3364,24 @@ static int process_host_tread_grid_impl(ssd_handle *h, const char *who, const vo
   ssd_frame_tread_grid *dRecords = nullptr;
   rc = tread_grid_stage(h, feed.slice, dRecords);
   if(rc) return rc;
+  /* a caller that asks for no records: a slice's, solved before the next slice's replace them */
   std::vector<ssd_frame_tread_grid> own;
   if(!grids)
     own.resize(static_cast<size_t>(feed.slice));
-  for(int c = 0; c < feed.slices(); c++)
-  {
-    const void *buf;
-    int done, n;
-    /* the body blocks on the pass, so the next slice's copy goes out in front of it, beside this slice's kernels */
-    rc = feed.stage(c);
-    if(!rc) rc = feed.stage(c + 1);
-    if(!rc) rc = feed.ready(c, buf, done, n);
-    if(rc) return rc;
-    rc = enqueue_impl(h, buf, feed.f.devFrameBytes, n, h->ingestCompute, SSD_STAGE_ALL, feed.f.depth, nullptr, 0, camOf ? camOf + done : nullptr);
-    if(!rc) rc = tread_grid_enqueue_impl(h, who, camOf != nullptr, buf, feed.f.devFrameBytes, n, h->ingestCompute, input, rule, dRecords);
-    if(!rc) rc = ssd_fetch_back(h, results + done, n, 0);
-    if(rc) return rc;
-    /* behind the pass on the stream it ran on; the body waits, so the staging buffer is free for the next slice */
-    hipStream_t s = h->lane[h->lastLane].lastStream;
-    ssd_frame_tread_grid *to = grids ? grids + done : own.data();
-    HIP_TRY(hipMemcpyAsync(to, dRecords, sizeof(ssd_frame_tread_grid) * static_cast<size_t>(n), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    rc = feed.consumed(c, s);
-    if(rc) return rc;
-    for(int i = 0; i < n; i++)
+  return process_host_follow(h, feed, camOf, results,
+    [&](const void *buf, int n)
     {
-      rc = ssd_tread_grid_solve(to + i, results + done + i, rule, min_seen, min_occ, foot_along, foot_deep, out + done + i);
-      if(rc) return rc;
-    }
-  }
-  return SSD_OK;
+      return tread_grid_enqueue_impl(h, who, camOf != nullptr, buf, feed.f.devFrameBytes, n, h->ingestCompute, input, rule, dRecords);
+    },
+    [&](int first, int n, hipStream_t s)
+    {
+      HIP_TRY(hipMemcpyAsync(grids ? grids + first : own.data(), dRecords, sizeof(ssd_frame_tread_grid) * static_cast<size_t>(n), hipMemcpyDeviceToHost, s));
+      return static_cast<int>(SSD_OK);
+    },
+    [&](int first, int i)
+    {
+      return ssd_tread_grid_solve(grids ? grids + first + i : own.data() + i, results + first + i, rule, min_seen, min_occ, foot_along, foot_deep, out + first + i);
+    });
 }
 
 int ssd_process_host_tread_grid(ssd_handle *h, const void *frames, int nframes, int input, const ssd_tread_grid_rule *rule, int min_seen,
@@ -3566,18 +3569,17 @@ static int ground_prepare(ssd_handle *h)
   PinnedBuf<long long> hh;
   DeviceBuf<GroundPrior> dPriors;
   PinnedBuf<GroundPrior> hPriors;
-  Event copied, done;
+  Event copied;
   hipError_t e = d.alloc(recBytes, &h->bytes);
   if(e == hipSuccess) e = hh.alloc(recBytes);
   if(e == hipSuccess) e = dPriors.alloc(priorBytes, &h->bytes);
   if(e == hipSuccess) e = hPriors.alloc(priorBytes);
   if(e == hipSuccess) e = copied.create(hipEventDisableTiming);
-  if(e == hipSuccess) e = done.create(hipEventDisableTiming);
   if(e != hipSuccess)
     return hip_fail(e, "ssd_enqueue_ground_fit: its buffers: ");
   h->dGround = std::move(d); h->hGround = std::move(hh);
   h->dGroundPriors = std::move(dPriors); h->hGroundPriors = std::move(hPriors);
-  h->groundPriorsCopied = std::move(copied); h->groundDone = std::move(done);
+  h->groundPriorsCopied = std::move(copied);
   return SSD_OK;
 }
 
@@ -3612,14 +3614,12 @@ static int enqueue_ground_fit_impl(ssd_handle *h, const void *d_frames, size_t f
   if(reinterpret_cast<size_t>(d_frames) % unit != 0 || frame_stride_bytes % unit != 0 || (nframes > 1 && frame_stride_bytes < frameBytes))
     return fail(SSD_E_ARG, "ssd_enqueue_ground_fit: frames must be aligned to their element and the stride must hold a frame");
   HIP_TRY(hipSetDevice(h->device));
-  const int rc = ground_prepare(h);
+  int rc = ground_prepare(h);
   if(rc) return rc;
-  if(h->groundHaveLast)
-  {
+  if(h->groundPass.haveLast)
     HIP_TRY(hipEventSynchronize(h->groundPriorsCopied));          /* the pinned priors of the previous call have gone over */
-    if(s != h->groundLastStream)
-      HIP_TRY(hipStreamWaitEvent(s, h->groundDone, 0));            /* another stream: behind the previous call */
-  }
+  rc = pass_open(h->groundPass, s, false, "ssd_enqueue_ground_fit");   /* another stream: behind the previous call */
+  if(rc) return rc;
   const int np = npriors > 0 ? npriors : 1;
   h->groundPriorCal.resize(static_cast<size_t>(np));
   if(npriors == 0)
@@ -3642,11 +3642,8 @@ static int enqueue_ground_fit_impl(ssd_handle *h, const void *d_frames, size_t f
   launch_ground_moments(d_frames, frame_stride_bytes, h->P.W, h->P.H, nframes, depth, h->dGroundPriors, np > 1 ? 1 : 0, R, h->dGround, s);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(h->hGround, h->dGround, recBytes, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipEventRecord(h->groundDone, s));
-  h->groundLastStream = s;
-  h->groundHaveLast = true;
   h->groundFrames = nframes;
-  return SSD_OK;
+  return pass_close(h->groundPass, s, false);
 }
 
 int ssd_enqueue_ground_fit(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream, int input,
@@ -3665,10 +3662,10 @@ int ssd_fetch_ground_fit(ssd_handle *h, ssd_ground_fit *out, int nframes, int mi
 {
   if(!h || !out)
     return fail(SSD_E_ARG, "ssd_fetch_ground_fit: null argument");
-  if(!h->groundHaveLast || nframes < 1 || nframes > h->groundFrames)
+  if(!h->groundPass.haveLast || nframes < 1 || nframes > h->groundFrames)
     return fail(SSD_E_ARG, "ssd_fetch_ground_fit: nframes must be 1..the frames of the last ssd_enqueue_ground_fit");
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipEventSynchronize(h->groundDone));
+  const int wait = pass_wait(h, &ssd_handle::groundPass, "ssd_fetch_ground_fit", "");
+  if(wait) return wait;
   const bool each = h->groundPriorCal.size() > 1;
   for(int i = 0; i < nframes; i++)
   {

@@ -48,6 +48,19 @@ struct ssd_timed_pass
   }
 };
 
+/* A pass the handle keeps in call order (the ground fit, the trimmed refit, the clearance pass, the tread grid: DESIGN.md section 7o):
+ * the event behind the last call and the stream it ran on, so that a call on another stream goes behind it and the last call's event
+ * covers every call so far; and, for the passes that time, the events around the last call's timed span.  Only pass_open, pass_start,
+ * pass_close, pass_wait and pass_time (ssd_capi.hip) touch it */
+struct ssd_ordered_pass
+{
+  ssd::Event done;                          /* behind the last call, made on the first one */
+  hipStream_t lastStream = nullptr;         /* the stream of the last call (a switch is ordered by `done`) */
+  bool haveLast = false;                    /* there was one */
+  std::vector<ssd::Event> ev;               /* both or none: around the timed span of a timed call, made on the first one */
+  bool timed = false;                       /* the last call was timed */
+};
+
 /* One complete workspace of a handle: everything a batch in flight owns on the device.  A handle has `depth` of them
  * (ssd_config::batches_in_flight); successive enqueues take them in turn, each on the lane's own stream, so that the launches
  * of one batch fill the gaps the one-block-per-frame kernels of the others leave. */
@@ -177,9 +190,7 @@ struct ssd_handle
   ssd::DeviceBuf<ssd::GroundPrior> dGroundPriors;   /* F */
   ssd::PinnedBuf<ssd::GroundPrior> hGroundPriors;   /* pinned: the caller's priors are restated here during the call */
   ssd::Event groundPriorsCopied;            /* behind the copy pinned -> device: the pinned priors may be written again */
-  ssd::Event groundDone;                    /* behind the call's last step */
-  hipStream_t groundLastStream = nullptr;   /* the stream of the previous call (a switch is ordered by groundDone) */
-  bool groundHaveLast = false;
+  ssd_ordered_pass groundPass;              /* behind the call's last step; never timed */
   int groundFrames = 0;                     /* frames of the last call */
   std::vector<ssd_calibration> groundPriorCal;   /* its priors, one or one per frame: what ssd_fetch_ground_fit solves against */
   /* the trimmed surface refit (ssd_enqueue_surface_refit; ssd_enqueue_cameras_surface_refit, section 7h).  What the
@@ -195,24 +206,15 @@ struct ssd_handle
   ssd::DeviceBuf<ssd_frame_gates> dRefitGates;   /* F */
   ssd::PinnedBuf<ssd_frame_gates> hRefitGates;   /* pinned: the caller's gates are copied here during the call */
   ssd::Event refitGatesCopied;              /* behind the copy pinned -> device: the pinned gates may be written again */
-  ssd::Event refitDone;                     /* behind the pass */
-  hipStream_t refitLastStream = nullptr;    /* the stream of the previous pass (a switch is ordered by refitDone: the device gates are single) */
-  std::vector<ssd::Event> evRefit;          /* both or none: around the pass of a timed call, made on the first one */
-  bool refitHaveLast = false, refitTimed = false;
+  ssd_ordered_pass refitPass;               /* a switch of streams is ordered by it: the device gates are single */
   /* the camera fold (ssd_enqueue_cameras_surface_refit_folded, ssd_process_host_cameras_drift): SSD_MAX_CAMERAS
    * records, made on the first call of either.  One set: the refit orders its users as it orders the device gates' */
   ssd::DeviceBuf<ssd_camera_fold> dCamFold;
   /* the tread clearance pass (ssd_enqueue_clearance): events only, made on the first call - the pass writes the
-   * caller's buffers and owns none.  Passes on different streams are ordered by clearDone, so that the last one's event covers all */
-  ssd::Event clearDone;                     /* behind the pass */
-  hipStream_t clearLastStream = nullptr;
-  std::vector<ssd::Event> evClear;          /* both or none: around the pass of a timed call, made on the first one */
-  bool clearHaveLast = false, clearTimed = false;
+   * caller's buffers and owns none.  Passes on different streams are ordered by clearPass, so that the last one's event covers all */
+  ssd_ordered_pass clearPass;
   /* the tread grid pass (ssd_enqueue_tread_grid): events only, as the clearance pass's, made on the first call */
-  ssd::Event gridDone;                      /* behind the pass */
-  hipStream_t gridLastStream = nullptr;
-  std::vector<ssd::Event> evGrid;           /* both or none: around the pass of a timed call */
-  bool gridHaveLast = false, gridTimed = false;
+  ssd_ordered_pass gridPass;
   /* ssd_process_host_tread_grid: a slice's records where the label staging buffers do not hold them (a record is 52.5 KB, more than
    * the width * height bytes of a small frame that those are sized by); made on first use, not counted as workspace like those */
   ssd::DeviceBuf<ssd_frame_tread_grid> gridStage;
