@@ -1021,6 +1021,83 @@ int ssd_process_host_cameras_tread_grid(ssd_handle *h, const void *frames, int n
                                         const ssd_tread_grid_rule *rule, int min_seen, int min_occ, double foot_along, double foot_deep,
                                         ssd_frame_result *results, ssd_frame_tread_grid *grids /* may be NULL */, ssd_frame_footholds *out);
 
+/* ---- stair map: the tread grids of many frames and cameras on one staircase --------------------------------------------------------
+ * EXTENSION.  A frame's tread grid is laid in the frame of that frame's OWN quadrilaterals, which move from frame
+ * to frame, so the grids of two frames cannot be added; and what one camera cannot see behind an occupant (SSD_TG_UNSEEN) another camera,
+ * or the same one a moment later, can.  A STAIR MAP is a staircase the caller gives, in the external world that ssd_set_cameras' cameras
+ * share; this pass runs the tread grid's rule, unchanged, with that staircase in place of each frame's own result and adds every frame
+ * that names the map into ONE record, an ssd_frame_tread_grid as it stands.  Everything counted is an integer sum or an integer
+ * maximum, so the record is exact and independent of the order of frames, blocks and calls.
+ *
+ * The record of map m after a call with accumulate == 0 is, byte for byte, the fold (ssd_tread_grid_add) of
+ *   ssd_tread_grid_host(cfg, cal_i, input, intr_i, frame_i, &maps[m].stairs, maps[m].ground, rule, &g_i)
+ * over the frames i with map_of_frame[i] == m, in any order: the header is g_i's (n_surfaces = the map's n_steps and ground != 0; both 0
+ * for a map with SSD_ST_THROW or n_steps == 0, whose record is all zero), every uint32_t is added, every int32_t top is maximised.
+ * cal_i / intr_i are the handle's, or for a cameras batch those of frame i's camera.  A map no frame names: the header and zeros.  The
+ * frame's own result, status and debug record are NOT read: a frame too poor for a detection of its own contributes like any other.
+ * accumulate != 0: the same is added on top of what d_out holds, and the headers are rewritten - two calls equal one call over the
+ * concatenation of their frames.
+ * Out of scope: ssd_pipeline_* and ssd_enqueue_stages; a mask; a count of contributing frames per map (the caller holds map_of_frame);
+ * choosing a frame's map on the device. */
+#define SSD_MAX_STAIR_MAPS 64        /* 64 records of 52,504 bytes = 3.4 MB: what the host path stages */
+#define SSD_STAIR_MAP_NONE 0xffff    /* a frame that names no map adds nothing */
+
+typedef struct
+{
+  ssd_frame_result stairs;   /* the staircase, external world: n_steps, steps[]; read exactly as ssd_tread_grid_host reads a result */
+  int32_t ground, reserved;  /* ground goes into the record's header as ssd_tread_grid_host's `ground` does */
+} ssd_stair_map;             /* 1240 bytes */
+
+/* host only: the fold's step.  acc's header becomes in's, every count of in is added to acc's, every top of acc is raised to in's.  If
+ * any count would pass 2^32 - 1: SSD_E_CAP, and acc is untouched - a record whole or not at all.  SSD_E_ARG: a null pointer. */
+int ssd_tread_grid_add(const ssd_frame_tread_grid *in, ssd_frame_tread_grid *acc);
+/* host only: a reference staircase from a run of results.  Used frames: no SSD_ST_THROW, no SSD_ST_OVERFLOW, 0 < n_steps <=
+ * SSD_MAX_STEPS, and the height and the eight quadrilateral coordinates of every step below n_steps finite.  Of those only the frames
+ * with the most frequent n_steps are kept (ties go to the larger n_steps); per step, the height and each of the eight coordinates are
+ * the LOWER MEDIAN over the kept frames (the value at index (n - 1) / 2 of the sorted values): no arithmetic, so the result is exact
+ * and independent of the frames' order.  out is zeroed first; out->ground = ground as given; *n_used (may be NULL) = the kept frames.
+ * No usable frame: n_steps = 0, *n_used = 0, SSD_OK.  SSD_E_ARG: a null results or out, nframes < 0. */
+int ssd_stair_map_from_results(const ssd_frame_result *results, int nframes, int ground, ssd_stair_map *out, int *n_used);
+
+/* The pass alone (k_stair_map; ssd_enqueue_cameras_stair_map: k_stair_map_cams), a fifth pass behind the handle's last WHOLE enqueue:
+ * it needs that enqueue's cell records, its depth maps and its camera index, but not its results.  Refusals, stream rule, withdrawals
+ * and the completion event of its own are ssd_enqueue_tread_grid's; it runs on one workspace and on several.
+ * maps: nmaps records in HOST memory; map_of_frame: nframes entries in HOST memory, each below nmaps or SSD_STAIR_MAP_NONE (NULL: every
+ * frame names map 0).  Both are copied during the call, through pinned buffers of the handle's own that the first call makes and
+ * ssd_workspace_bytes counts from then on (a call waits for the previous call's copy before it refills them); a handle that never calls
+ * this allocates and launches nothing.  d_out: nmaps contiguous records in DEVICE memory.  accumulate == 0 zeroes them on the stream in
+ * front of the kernel; records past nmaps are not written.
+ * SSD_E_ARG before anything is launched or copied: what ssd_enqueue_tread_grid refuses; null maps or d_out; nmaps outside 1 ..
+ * SSD_MAX_STAIR_MAPS; a map's n_steps outside 0 .. SSD_MAX_STEPS (ssd_tread_grid_host refuses it); an index that is neither below nmaps
+ * nor SSD_STAIR_MAP_NONE; a call in which (frames naming one map) x width x height exceeds 2^32 - 1 (computed in 64 bits), so that no
+ * count can overflow within one call (an enqueue takes at most max_frames_per_batch frames, so only a handle made for tens of
+ * thousands of frames can meet this bound here; the host forms, whose calls have no such limit, are where it bites).
+ * ACROSS accumulating calls that bound is the caller's to keep: the device adds modulo 2^32 and does not report a carry. */
+int ssd_enqueue_stair_map(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream, int input,
+                          const ssd_stair_map *maps /* HOST, nmaps, copied during the call */, int nmaps,
+                          const uint16_t *map_of_frame /* HOST, nframes; NULL: every frame names map 0 */,
+                          const ssd_tread_grid_rule *rule, int accumulate, ssd_frame_tread_grid *d_out /* DEVICE, nmaps */);
+int ssd_enqueue_cameras_stair_map(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream, int input,
+                                  const ssd_stair_map *maps, int nmaps, const uint16_t *map_of_frame, const ssd_tread_grid_rule *rule,
+                                  int accumulate, ssd_frame_tread_grid *d_out);
+/* waits for the last stair map pass (SSD_E_ARG: there was none) */
+int ssd_fetch_stair_map(ssd_handle *h, void *stream);
+/* the device time of the last stair map pass, the zeroing in front of it included (0 when timing was off for it) */
+int ssd_get_stair_map_time(ssd_handle *h, float *ms);
+/* frames in host memory through the slices of ssd_process_host (ssd_process_host_cameras): per slice an enqueue and the pass,
+ * accumulate = 0 for the first slice and 1 after, into a buffer of the pass's own; nothing per frame is copied up.  Behind the last
+ * slice one copy of nmaps records, then ssd_tread_grid_solve(grids + m, &maps[m].stairs, rule, ..) -> out[m] per map.  Fills
+ * results[nframes] (byte for byte ssd_process_host's / ssd_process_host_cameras'), out[nmaps] and, when not NULL, grids[nmaps].  The
+ * refusals are the enqueue's, the overflow bound held over the WHOLE call, and ssd_tread_grid_solve's for the foot sizes. */
+int ssd_process_host_stair_map(ssd_handle *h, const void *frames, int nframes, int input, const ssd_stair_map *maps, int nmaps,
+                               const uint16_t *map_of_frame, const ssd_tread_grid_rule *rule, int min_seen, int min_occ,
+                               double foot_along, double foot_deep, ssd_frame_result *results,
+                               ssd_frame_tread_grid *grids /* nmaps, may be NULL */, ssd_frame_footholds *out /* nmaps */);
+int ssd_process_host_cameras_stair_map(ssd_handle *h, const void *frames, int nframes, const uint16_t *camera_of_frame, int input,
+                                       const ssd_stair_map *maps, int nmaps, const uint16_t *map_of_frame, const ssd_tread_grid_rule *rule,
+                                       int min_seen, int min_occ, double foot_along, double foot_deep, ssd_frame_result *results,
+                                       ssd_frame_tread_grid *grids /* nmaps, may be NULL */, ssd_frame_footholds *out /* nmaps */);
+
 /* stage selector for profiling / roofline measurement: runs only the chosen stage(s) of the pipeline */
 #define SSD_STAGE_HIST 1       /* K1: transform + crop + bin + histogram */
 #define SSD_STAGE_PEAKS 2

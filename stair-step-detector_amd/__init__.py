@@ -226,6 +226,16 @@ class FrameTreadGrid(C.Structure):
     _fields_ = [("n_surfaces", C.c_int32), ("ground", C.c_int32), ("s", TreadGrid * MAX_STEPS)]
 
 
+MAX_STAIR_MAPS = 64          # SSD_MAX_STAIR_MAPS
+STAIR_MAP_NONE = 0xffff      # SSD_STAIR_MAP_NONE: a frame that names no map
+
+
+class StairMap(C.Structure):
+    """ssd_stair_map: a staircase the caller gives, in the external world the cameras share (stairs: a FrameResult, read as
+    tread_grid_host reads a result), and the ground flag of its record's header"""
+    _fields_ = [("stairs", FrameResult), ("ground", C.c_int32), ("reserved", C.c_int32)]
+
+
 class Foothold(C.Structure):
     """ssd_foothold: one surface's cells (TG_OUT / TG_FREE / TG_OCCUPIED / TG_UNSEEN) and the best free rectangle on it"""
     _fields_ = [("state", C.c_uint8 * TG_COLS * TG_ROWS), ("n_free", C.c_int32), ("n_occupied", C.c_int32), ("n_unseen", C.c_int32),
@@ -314,6 +324,8 @@ EXPORTS = [
     "ssd_clearance_solve", "ssd_process_host_clearance", "ssd_process_host_cameras_clearance",
     "ssd_enqueue_tread_grid", "ssd_enqueue_cameras_tread_grid", "ssd_fetch_tread_grid", "ssd_get_tread_grid_time", "ssd_tread_grid_host",
     "ssd_tread_grid_solve", "ssd_process_host_tread_grid", "ssd_process_host_cameras_tread_grid",
+    "ssd_tread_grid_add", "ssd_stair_map_from_results", "ssd_enqueue_stair_map", "ssd_enqueue_cameras_stair_map", "ssd_fetch_stair_map",
+    "ssd_get_stair_map_time", "ssd_process_host_stair_map", "ssd_process_host_cameras_stair_map",
 ]
 # libssd_source.so — the frame source standing in for the camera (include/ssd_source.h)
 SOURCE_EXPORTS = [
@@ -439,6 +451,17 @@ def lib():
                                               C.POINTER(FrameTreadGrid), C.POINTER(FrameFootholds)]
     L.ssd_process_host_cameras_tread_grid.argtypes = [vp, vp, i32, C.POINTER(C.c_uint16), i32, C.POINTER(TreadGridRule), i32, i32, C.c_double, C.c_double,
                                                       C.POINTER(FrameResult), C.POINTER(FrameTreadGrid), C.POINTER(FrameFootholds)]
+    L.ssd_tread_grid_add.argtypes = [C.POINTER(FrameTreadGrid), C.POINTER(FrameTreadGrid)]
+    L.ssd_stair_map_from_results.argtypes = [C.POINTER(FrameResult), i32, i32, C.POINTER(StairMap), C.POINTER(i32)]
+    L.ssd_enqueue_stair_map.argtypes = [vp, vp, sz, i32, vp, i32, C.POINTER(StairMap), i32, C.POINTER(C.c_uint16), C.POINTER(TreadGridRule), i32, vp]
+    L.ssd_enqueue_cameras_stair_map.argtypes = L.ssd_enqueue_stair_map.argtypes
+    L.ssd_fetch_stair_map.argtypes = [vp, vp]
+    L.ssd_get_stair_map_time.argtypes = [vp, C.POINTER(C.c_float)]
+    L.ssd_process_host_stair_map.argtypes = [vp, vp, i32, i32, C.POINTER(StairMap), i32, C.POINTER(C.c_uint16), C.POINTER(TreadGridRule), i32, i32,
+                                             C.c_double, C.c_double, C.POINTER(FrameResult), C.POINTER(FrameTreadGrid), C.POINTER(FrameFootholds)]
+    L.ssd_process_host_cameras_stair_map.argtypes = [vp, vp, i32, C.POINTER(C.c_uint16), i32, C.POINTER(StairMap), i32, C.POINTER(C.c_uint16),
+                                                     C.POINTER(TreadGridRule), i32, i32, C.c_double, C.c_double, C.POINTER(FrameResult),
+                                                     C.POINTER(FrameTreadGrid), C.POINTER(FrameFootholds)]
     L.ssd_enqueue_cameras_surface_refit_folded.argtypes = [vp, vp, sz, i32, vp, i32, vp, i32, C.c_double, C.c_double, i32, vp]
     L.ssd_camera_drift_from_fold.argtypes = [C.POINTER(CameraFold), C.POINTER(Camera), i32, i32, C.POINTER(CameraDrift)]
     L.ssd_process_host_cameras_drift.argtypes = [vp, vp, i32, C.POINTER(C.c_uint16), i32, C.POINTER(FrameResult), i32, C.c_double, C.c_double, i32, i32,
@@ -789,6 +812,47 @@ def tread_grid_solve(grid, result, rule=None, min_seen=1, min_occ=1, foot_along=
     _check(lib().ssd_tread_grid_solve(C.byref(grid), C.byref(result), C.byref(rule), int(min_seen), int(min_occ), float(foot_along),
                                       float(foot_deep), C.byref(out)))
     return out
+
+
+def tread_grid_add(grid, acc):
+    """ssd_tread_grid_add: the stair map's fold step - acc's header becomes grid's, grid's counts are added to acc's, acc's tops raised to
+    grid's; SsdError (SSD_E_CAP) and acc untouched if a count would pass 2^32 - 1.  Returns acc."""
+    _check(lib().ssd_tread_grid_add(C.byref(grid) if grid is not None else None, C.byref(acc) if acc is not None else None))
+    return acc
+
+
+def _stair_maps(maps):
+    """one StairMap, a FrameResult (ground flag 1) or a sequence of either -> (StairMap array, count)"""
+    if isinstance(maps, (StairMap, FrameResult)):
+        maps = [maps]
+    maps = list(maps)
+    arr = (StairMap * max(len(maps), 1))()
+    for i, m in enumerate(maps):
+        if isinstance(m, FrameResult):
+            C.memmove(C.byref(arr[i].stairs), C.byref(m), C.sizeof(FrameResult))
+            arr[i].ground = 1
+        else:
+            C.memmove(C.byref(arr[i]), C.byref(m), C.sizeof(StairMap))
+    return arr, len(maps)
+
+
+def _map_index(map_of_frame, nframes):
+    if map_of_frame is None:
+        return None
+    idx = np.ascontiguousarray(map_of_frame, dtype=np.uint16)
+    if idx.ndim != 1 or idx.size != nframes or np.any(np.asarray(map_of_frame) != idx):
+        raise SsdError("map_of_frame: one index 0..65535 per frame")
+    return idx
+
+
+def stair_map_from_results(results, ground=1):
+    """ssd_stair_map_from_results: a reference staircase from a run of FrameResults - per step the lower median of the height and of each
+    quadrilateral coordinate over the usable frames with the most frequent n_steps -> (StairMap, frames used)"""
+    results = list(results)
+    arr = (FrameResult * max(len(results), 1))(*results)
+    out, used = StairMap(), C.c_int32(0)
+    _check(lib().ssd_stair_map_from_results(arr, len(results), int(ground), C.byref(out), C.byref(used)))
+    return out, int(used.value)
 
 
 def riser_fit_solve(moments, risers, cal, min_points=100):
@@ -1239,6 +1303,59 @@ class Detector:
                                         grids=False):
         """ssd_process_host_cameras_tread_grid: process_host_tread_grid with one camera index per frame"""
         return self.process_host_tread_grid(frames, rule, min_seen, min_occ, foot_along, foot_deep, depth, grids, camera_of_frame=camera_of_frame)
+
+    # ---- stair map (include/ssd_hip.h, DESIGN.md section 7p)
+    def enqueue_stair_map(self, d_ptr, nframes, maps, d_grids, map_of_frame=None, rule=None, accumulate=False, depth=False, stride_bytes=None,
+                          stream=None, cameras=False):
+        """ssd_enqueue_stair_map: the tread grid's rule against the caller's staircases, behind the handle's last whole enqueue of the same
+        frames: every frame i adds to the FrameTreadGrid of map map_of_frame[i] (None: map 0; STAIR_MAP_NONE: nothing) at d_grids +
+        m * sizeof(FrameTreadGrid), device memory, zeroed first unless accumulate; complete when fetch_stair_map() returns.
+        maps: StairMap, FrameResult or a sequence of them (host; copied during the call)"""
+        frame = self.cfg.width * self.cfg.height * (2 if depth else 12)
+        rule = TreadGridRule() if rule is None else rule
+        arr, nmaps = _stair_maps(maps)
+        idx = _map_index(map_of_frame, nframes)
+        fn = lib().ssd_enqueue_cameras_stair_map if cameras else lib().ssd_enqueue_stair_map
+        _check(fn(self._h, C.c_void_p(d_ptr), stride_bytes or frame, nframes, C.c_void_p(stream or 0), _input_code(depth), arr, nmaps,
+                  idx.ctypes.data_as(C.POINTER(C.c_uint16)) if idx is not None else None, C.byref(rule), 1 if accumulate else 0,
+                  C.c_void_p(d_grids)))
+
+    def enqueue_cameras_stair_map(self, d_ptr, nframes, maps, d_grids, map_of_frame=None, rule=None, accumulate=False, depth=False,
+                                  stride_bytes=None, stream=None):
+        """ssd_enqueue_cameras_stair_map: enqueue_stair_map behind the handle's last whole CAMERAS enqueue of the same frames"""
+        self.enqueue_stair_map(d_ptr, nframes, maps, d_grids, map_of_frame, rule, accumulate, depth, stride_bytes, stream, cameras=True)
+
+    def fetch_stair_map(self, stream=None):
+        """ssd_fetch_stair_map: waits for the last enqueue_stair_map"""
+        _check(lib().ssd_fetch_stair_map(self._h, C.c_void_p(stream or 0)))
+
+    def stair_map_time_ms(self):
+        """Device time of the last stair map pass (0.0: timing was off for it)"""
+        return _time_ms(lib().ssd_get_stair_map_time, self._h)
+
+    def process_host_stair_map(self, frames, maps, map_of_frame=None, rule=None, min_seen=1, min_occ=1, foot_along=0.0, foot_deep=0.0, depth=False,
+                               camera_of_frame=None, grids=False):
+        """ssd_process_host_stair_map: frames on the host (float32 [n, H, W, 3], or uint16 [n, H, W] with depth=True) folded into one
+        record per map -> (list of FrameResult per frame, list of FrameFootholds per map), with grids=True also the FrameTreadGrid per map"""
+        a, n, inp = self._frames_arg("process_host_stair_map", frames, depth)
+        rule = TreadGridRule() if rule is None else rule
+        arr, nmaps = _stair_maps(maps)
+        idx = _map_index(map_of_frame, n)
+        res, out = (FrameResult * n)(), (FrameFootholds * max(nmaps, 1))()
+        g = (FrameTreadGrid * max(nmaps, 1))() if grids else None
+        tail = (arr, nmaps, idx.ctypes.data_as(C.POINTER(C.c_uint16)) if idx is not None else None, C.byref(rule), int(min_seen), int(min_occ),
+                float(foot_along), float(foot_deep), res, g, out)
+        if camera_of_frame is None:
+            _check(lib().ssd_process_host_stair_map(self._h, a.ctypes.data_as(C.c_void_p), n, inp, *tail))
+        else:
+            cam = self._camera_index(camera_of_frame, n)
+            _check(lib().ssd_process_host_cameras_stair_map(self._h, a.ctypes.data_as(C.c_void_p), n, cam.ctypes.data_as(C.POINTER(C.c_uint16)), inp, *tail))
+        return (list(res), list(out)[:nmaps], list(g)[:nmaps]) if grids else (list(res), list(out)[:nmaps])
+
+    def process_host_cameras_stair_map(self, frames, camera_of_frame, maps, map_of_frame=None, rule=None, min_seen=1, min_occ=1, foot_along=0.0,
+                                       foot_deep=0.0, depth=False, grids=False):
+        """ssd_process_host_cameras_stair_map: process_host_stair_map with one camera index per frame"""
+        return self.process_host_stair_map(frames, maps, map_of_frame, rule, min_seen, min_occ, foot_along, foot_deep, depth, camera_of_frame, grids)
 
     # ---- surface fit of cameras batches, drift per camera (include/ssd_hip.h, DESIGN.md section 7e)
     def enqueue_cameras_surface_moments(self, d_ptr, nframes, camera_of_frame, d_moments, depth=False, stride_bytes=None, stream=None):

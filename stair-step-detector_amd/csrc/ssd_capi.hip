@@ -3037,7 +3037,7 @@ int ssd_get_clearance_time(ssd_handle *h, float *ms)
 extern "C++"
 {
 /* The host-fed loop of a pass behind each slice's whole enqueue (the clearance pass, the tread grid).  Per slice, while it is still in its
- * staging buffer: the enqueue, pass(buf, n) on the compute stream, the results, copy(first, n, s) - the pass's staged records to the host,
+ * staging buffer: the enqueue, pass(buf, first, n) on the compute stream, the results, copy(first, n, s) - the pass's staged records to the host,
  * behind the pass on the stream it ran on - and solve(first, i) for each of its n frames.  The body blocks on the pass, so the next slice's
  * copy goes out in front of it, beside this slice's kernels, and the staging buffers are free for the next slice */
 template<class Pass, class Copy, class Solve>
@@ -3052,7 +3052,7 @@ static int process_host_follow(ssd_handle *h, SliceFeed &feed, const uint16_t *c
     if(!rc) rc = feed.ready(c, buf, done, n);
     if(rc) return rc;
     rc = enqueue_impl(h, buf, feed.f.devFrameBytes, n, h->ingestCompute, SSD_STAGE_ALL, feed.f.depth, nullptr, 0, camOf ? camOf + done : nullptr);
-    if(!rc) rc = pass(buf, n);
+    if(!rc) rc = pass(buf, done, n);
     if(!rc) rc = ssd_fetch_back(h, results + done, n, 0);
     if(rc) return rc;
     hipStream_t s = h->lane[h->lastLane].lastStream;
@@ -3090,7 +3090,7 @@ static int process_host_clearance_impl(ssd_handle *h, const char *who, const voi
   std::vector<ssd_frame_moments> own;
   moments = moments_or_own(moments, own, nframes);
   return process_host_follow(h, feed, camOf, results,
-    [&](const void *buf, int n)
+    [&](const void *buf, int, int n)
     {
       return clearance_enqueue_impl(h, who, camOf != nullptr, buf, feed.f.devFrameBytes, n, h->ingestCompute, input, rule, dRecords, dMask, nPoints);
     },
@@ -3369,7 +3369,7 @@ static int process_host_tread_grid_impl(ssd_handle *h, const char *who, const vo
   if(!grids)
     own.resize(static_cast<size_t>(feed.slice));
   return process_host_follow(h, feed, camOf, results,
-    [&](const void *buf, int n)
+    [&](const void *buf, int, int n)
     {
       return tread_grid_enqueue_impl(h, who, camOf != nullptr, buf, feed.f.devFrameBytes, n, h->ingestCompute, input, rule, dRecords);
     },
@@ -3400,6 +3400,273 @@ int ssd_process_host_cameras_tread_grid(ssd_handle *h, const void *frames, int n
   const int rc = check_host_batch(h, "ssd_process_host_cameras_tread_grid", h && frames && results && out, nframes, input, kCameraTable, camera_of_frame);
   return rc ? rc : process_host_tread_grid_impl(h, "ssd_process_host_cameras_tread_grid", frames, nframes, camera_of_frame, input, rule, min_seen, min_occ,
                                                 foot_along, foot_deep, results, grids, out);
+}
+
+/* ---- stair map (include/ssd_hip.h) ------------------------------------------------------------------------ */
+
+int ssd_tread_grid_add(const ssd_frame_tread_grid *in, ssd_frame_tread_grid *acc)
+{
+  if(!in || !acc)
+    return fail(SSD_E_ARG, "ssd_tread_grid_add: null");
+  if(!tread_grid_add(*in, *acc))
+    return fail(SSD_E_CAP, "ssd_tread_grid_add: a count would pass 2^32 - 1; the record is as it was");
+  return SSD_OK;
+}
+
+int ssd_stair_map_from_results(const ssd_frame_result *results, int nframes, int ground, ssd_stair_map *out, int *n_used)
+{
+  if(!results || !out || nframes < 0)
+    return fail(SSD_E_ARG, "ssd_stair_map_from_results: null, or nframes below 0");
+  std::memset(out, 0, sizeof(*out));
+  out->ground = ground;
+  if(n_used)
+    *n_used = 0;
+  /* the usable frames, and how often each n_steps occurs among them */
+  std::vector<int> usable;
+  int votes[SSD_MAX_STEPS + 1] = {};
+  for(int i = 0; i < nframes; i++)
+  {
+    const ssd_frame_result &r = results[i];
+    if((r.status & (SSD_ST_THROW | SSD_ST_OVERFLOW)) != 0 || r.n_steps <= 0 || r.n_steps > SSD_MAX_STEPS)
+      continue;
+    bool finite = true;
+    for(int k = 0; k < r.n_steps && finite; k++)
+    {
+      finite = std::isfinite(r.steps[k].height);
+      for(int j = 0; j < 8 && finite; j++)
+        finite = std::isfinite(r.steps[k].quad[j]);
+    }
+    if(!finite)
+      continue;
+    usable.push_back(i);
+    votes[r.n_steps]++;
+  }
+  int mode = 0;
+  for(int n = 1; n <= SSD_MAX_STEPS; n++)
+    if(votes[n] > 0 && votes[n] >= votes[mode])       /* ties go to the larger */
+      mode = n;
+  if(mode == 0)
+    return SSD_OK;
+  std::vector<double> v;
+  /* the lower median of one field over the kept frames: the values only, sorted - finite, so the order is total */
+  auto median = [&](auto field)
+  {
+    v.clear();
+    for(int i : usable)
+      if(results[i].n_steps == mode)
+        v.push_back(field(results[i]));
+    std::sort(v.begin(), v.end());
+    return v[(v.size() - 1) / 2];
+  };
+  out->stairs.n_steps = mode;
+  for(int k = 0; k < mode; k++)
+  {
+    out->stairs.steps[k].height = median([k](const ssd_frame_result &r) { return r.steps[k].height; });
+    for(int j = 0; j < 8; j++)
+      out->stairs.steps[k].quad[j] = median([k, j](const ssd_frame_result &r) { return r.steps[k].quad[j]; });
+  }
+  if(n_used)
+    *n_used = votes[mode];
+  return SSD_OK;
+}
+
+/* the refusals about the maps and the index that the enqueue and the host forms share: nframes is the whole call's, so that the bound
+ * on a map's count holds over all of it */
+static int check_stair_maps(const std::string &me, const ssd_handle *h, const ssd_stair_map *maps, int nmaps, const uint16_t *map_of_frame, int nframes)
+{
+  if(!maps)
+    return fail(SSD_E_ARG, me + ": null maps");
+  if(nmaps < 1 || nmaps > SSD_MAX_STAIR_MAPS)
+    return fail(SSD_E_ARG, me + ": nmaps must lie in 1 .. SSD_MAX_STAIR_MAPS");
+  for(int m = 0; m < nmaps; m++)
+    if(maps[m].stairs.n_steps < 0 || maps[m].stairs.n_steps > SSD_MAX_STEPS)
+      return fail(SSD_E_ARG, me + ": a map's n_steps must lie in 0 .. SSD_MAX_STEPS");
+  unsigned long long named[SSD_MAX_STAIR_MAPS] = {};
+  for(int i = 0; i < nframes; i++)
+  {
+    const unsigned int m = map_of_frame ? map_of_frame[i] : 0u;
+    if(m == SSD_STAIR_MAP_NONE)
+      continue;
+    if(m >= static_cast<unsigned int>(nmaps))
+      return fail(SSD_E_ARG, me + ": map_of_frame holds an index that is neither below nmaps nor SSD_STAIR_MAP_NONE");
+    named[m]++;
+  }
+  /* no count of a record can pass 2^32 - 1 within the call: a frame adds at most its points to one word */
+  for(int m = 0; m < nmaps; m++)
+    if(named[m] * static_cast<unsigned long long>(h->P.nPoints) > 0xffffffffull)
+      return fail(SSD_E_ARG, me + ": the frames that name one map hold more than 2^32 - 1 points");
+  return SSD_OK;
+}
+
+/* the buffers of the pass and the event behind their copy, on its first call */
+static int stair_map_prepare(ssd_handle *h)
+{
+  if(h->dStairMaps)
+    return SSD_OK;
+  const size_t mapBytes = sizeof(ssd_stair_map) * static_cast<size_t>(SSD_MAX_STAIR_MAPS), indexBytes = sizeof(int) * static_cast<size_t>(h->F);
+  DeviceBuf<ssd_stair_map> dm;
+  PinnedBuf<ssd_stair_map> hm;
+  DeviceBuf<int> di;
+  PinnedBuf<int> hi;
+  Event copied;
+  hipError_t e = dm.alloc(mapBytes, &h->bytes);
+  if(e == hipSuccess) e = hm.alloc(mapBytes, &h->bytes);
+  if(e == hipSuccess) e = di.alloc(indexBytes, &h->bytes);
+  if(e == hipSuccess) e = hi.alloc(indexBytes, &h->bytes);
+  if(e == hipSuccess) e = copied.create(hipEventDisableTiming);
+  if(e != hipSuccess)
+    return hip_fail(e, "ssd_enqueue_stair_map: its buffers: ");
+  h->dStairMaps = std::move(dm); h->hStairMaps = std::move(hm);
+  h->dMapIndex = std::move(di); h->hMapIndex = std::move(hi);
+  h->mapsCopied = std::move(copied);
+  return SSD_OK;
+}
+
+static const BehindWhole kStairMapBehind{ "map", "ssd_enqueue_stair_map", "ssd_enqueue_cameras_stair_map", false };
+
+/* both entry points of the pass and the slices of the host forms (checked: the caller has held the maps and the whole call's index to
+ * check_stair_maps): its own refusals, then the shared entry's, before anything is launched or copied */
+static int stair_map_enqueue_impl(ssd_handle *h, const char *who, bool cameras, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream,
+                                  int input, const ssd_stair_map *maps, int nmaps, const uint16_t *map_of_frame, const ssd_tread_grid_rule *rule,
+                                  int accumulate, ssd_frame_tread_grid *d_out, bool checked)
+{
+  const std::string me(who);
+  if(!h || !d_frames || !d_out)
+    return fail(SSD_E_ARG, me + ": null argument");
+  int rc = check_tread_grid_rule(me, rule);
+  if(rc) return rc;
+  if(nframes < 1 || nframes > h->F)
+    return fail(SSD_E_ARG, me + ": nframes is not the last enqueue's");
+  if(!checked)
+  {
+    rc = check_stair_maps(me, h, maps, nmaps, map_of_frame, nframes);
+    if(rc) return rc;
+  }
+  ssd_ordered_pass &P = h->mapPass;
+  FollowPass f;
+  /* The device maps and index are one set, so the pass is an ordered one: on another stream than the previous pass's this call goes
+   * behind that pass, which still reads them.  Its own: the buffers, and the pinned side of the previous call gone over */
+  rc = follow_enter(h, me, kStairMapBehind, &ssd_handle::mapPass, cameras, d_frames, frame_stride_bytes, nframes, stream, input, f, [&](hipStream_t)
+  {
+    const int own = stair_map_prepare(h);
+    if(own) return own;
+    if(P.haveLast)
+      HIP_TRY(hipEventSynchronize(h->mapsCopied));
+    return static_cast<int>(SSD_OK);
+  });
+  if(rc) return rc;
+  hipStream_t s = f.s;
+  std::memcpy(h->hStairMaps, maps, sizeof(ssd_stair_map) * static_cast<size_t>(nmaps));
+  for(int i = 0; i < nframes; i++)
+    h->hMapIndex[i] = map_of_frame ? static_cast<int>(map_of_frame[i]) : 0;
+  HIP_TRY(hipMemcpyAsync(h->dStairMaps, h->hStairMaps, sizeof(ssd_stair_map) * static_cast<size_t>(nmaps), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(h->dMapIndex, h->hMapIndex, sizeof(int) * static_cast<size_t>(nframes), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipEventRecord(h->mapsCopied, s));
+  rc = pass_start(P, s, f.timing);
+  if(rc) return rc;
+  if(!accumulate)
+    HIP_TRY(hipMemsetAsync(d_out, 0, sizeof(ssd_frame_tread_grid) * static_cast<size_t>(nmaps), s));
+  launch_stair_map(*f.B, f.chunk, h->dStairMaps, h->dMapIndex, nmaps, *rule, d_out);
+  HIP_TRY(hipGetLastError());
+  return follow_leave(h, &ssd_handle::mapPass, f);
+}
+
+int ssd_enqueue_stair_map(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream, int input,
+                          const ssd_stair_map *maps, int nmaps, const uint16_t *map_of_frame, const ssd_tread_grid_rule *rule, int accumulate,
+                          ssd_frame_tread_grid *d_out)
+{
+  return stair_map_enqueue_impl(h, "ssd_enqueue_stair_map", false, d_frames, frame_stride_bytes, nframes, stream, input, maps, nmaps, map_of_frame, rule,
+                                accumulate, d_out, false);
+}
+
+int ssd_enqueue_cameras_stair_map(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream, int input,
+                                  const ssd_stair_map *maps, int nmaps, const uint16_t *map_of_frame, const ssd_tread_grid_rule *rule, int accumulate,
+                                  ssd_frame_tread_grid *d_out)
+{
+  return stair_map_enqueue_impl(h, "ssd_enqueue_cameras_stair_map", true, d_frames, frame_stride_bytes, nframes, stream, input, maps, nmaps, map_of_frame,
+                                rule, accumulate, d_out, false);
+}
+
+int ssd_fetch_stair_map(ssd_handle *h, void *)
+{
+  return pass_wait(h, &ssd_handle::mapPass, "ssd_fetch_stair_map", "no ssd_enqueue_stair_map to wait for");
+}
+
+int ssd_get_stair_map_time(ssd_handle *h, float *ms)
+{
+  return pass_time(h, &ssd_handle::mapPass, "ssd_get_stair_map_time", "ssd_enqueue_stair_map", ms);
+}
+
+/* Both host entry points, the callers' own refusals behind them: the rule, then the maps and the WHOLE call's index and bound, then the
+ * foot sizes - all before a byte of `frames` is read or anything is allocated.  process_host_follow fits: its pass is a slice's enqueue
+ * under the slice's part of the index (the loop hands it the slice's first frame), with accumulate on from the second slice; its copy
+ * does nothing until the last slice and then takes the nmaps records; and nothing is solved per frame - the maps are solved behind the
+ * loop, whose last iteration has waited for the copy */
+static int process_host_stair_map_impl(ssd_handle *h, const char *who, const void *frames, int nframes, const uint16_t *camOf, int input,
+                                       const ssd_stair_map *maps, int nmaps, const uint16_t *map_of_frame, const ssd_tread_grid_rule *rule, int min_seen,
+                                       int min_occ, double foot_along, double foot_deep, ssd_frame_result *results, ssd_frame_tread_grid *grids,
+                                       ssd_frame_footholds *out)
+{
+  int rc = check_tread_grid_rule(who, rule);
+  if(rc) return rc;
+  rc = check_stair_maps(who, h, maps, nmaps, map_of_frame, nframes);
+  if(rc) return rc;
+  if(!(foot_along >= 0.0) || !(foot_deep >= 0.0))
+    return fail(SSD_E_ARG, std::string(who) + ": a foot size must be 0 or more");
+  HIP_TRY(hipSetDevice(h->device));
+  SliceFeed feed{ h, host_frames(h, input, kForPipeline), frames, nframes };
+  rc = feed.prepare();
+  if(rc) return rc;
+  if(!h->mapStage)
+  {
+    DeviceBuf<ssd_frame_tread_grid> buf;
+    const hipError_t e = buf.alloc(sizeof(ssd_frame_tread_grid) * static_cast<size_t>(SSD_MAX_STAIR_MAPS));
+    if(e != hipSuccess)
+      return hip_fail(e, "the stair map's staging buffer: ");
+    h->mapStage = std::move(buf);
+  }
+  ssd_frame_tread_grid *dRecords = h->mapStage;
+  std::vector<ssd_frame_tread_grid> own;
+  if(!grids)
+  {
+    own.resize(static_cast<size_t>(nmaps));
+    grids = own.data();
+  }
+  rc = process_host_follow(h, feed, camOf, results,
+    [&](const void *buf, int first, int n)
+    {
+      return stair_map_enqueue_impl(h, who, camOf != nullptr, buf, feed.f.devFrameBytes, n, h->ingestCompute, input, maps, nmaps,
+                                    map_of_frame ? map_of_frame + first : nullptr, rule, first != 0, dRecords, true);
+    },
+    [&](int first, int n, hipStream_t s)
+    {
+      if(first + n == nframes)
+        HIP_TRY(hipMemcpyAsync(grids, dRecords, sizeof(ssd_frame_tread_grid) * static_cast<size_t>(nmaps), hipMemcpyDeviceToHost, s));
+      return static_cast<int>(SSD_OK);
+    },
+    [](int, int) { return static_cast<int>(SSD_OK); });
+  for(int m = 0; m < nmaps && !rc; m++)
+    rc = ssd_tread_grid_solve(grids + m, &maps[m].stairs, rule, min_seen, min_occ, foot_along, foot_deep, out + m);
+  return rc;
+}
+
+int ssd_process_host_stair_map(ssd_handle *h, const void *frames, int nframes, int input, const ssd_stair_map *maps, int nmaps,
+                               const uint16_t *map_of_frame, const ssd_tread_grid_rule *rule, int min_seen, int min_occ, double foot_along,
+                               double foot_deep, ssd_frame_result *results, ssd_frame_tread_grid *grids, ssd_frame_footholds *out)
+{
+  const int rc = check_host_batch(h, "ssd_process_host_stair_map", h && frames && results && out, nframes, input, kHandleCal);
+  return rc ? rc : process_host_stair_map_impl(h, "ssd_process_host_stair_map", frames, nframes, nullptr, input, maps, nmaps, map_of_frame, rule, min_seen,
+                                               min_occ, foot_along, foot_deep, results, grids, out);
+}
+
+int ssd_process_host_cameras_stair_map(ssd_handle *h, const void *frames, int nframes, const uint16_t *camera_of_frame, int input,
+                                       const ssd_stair_map *maps, int nmaps, const uint16_t *map_of_frame, const ssd_tread_grid_rule *rule,
+                                       int min_seen, int min_occ, double foot_along, double foot_deep, ssd_frame_result *results,
+                                       ssd_frame_tread_grid *grids, ssd_frame_footholds *out)
+{
+  const int rc = check_host_batch(h, "ssd_process_host_cameras_stair_map", h && frames && results && out, nframes, input, kCameraTable, camera_of_frame);
+  return rc ? rc : process_host_stair_map_impl(h, "ssd_process_host_cameras_stair_map", frames, nframes, camera_of_frame, input, maps, nmaps, map_of_frame,
+                                               rule, min_seen, min_occ, foot_along, foot_deep, results, grids, out);
 }
 
 /* ---- riser fit (include/ssd_hip.h): host side ------------------------------------------------------------ */

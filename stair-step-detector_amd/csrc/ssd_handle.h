@@ -219,6 +219,18 @@ struct ssd_handle
    * the width * height bytes of a small frame that those are sized by); made on first use, not counted as workspace like those */
   ssd::DeviceBuf<ssd_frame_tread_grid> gridStage;
   int gridStageFrames = 0;
+  /* the stair map pass (ssd_enqueue_stair_map): the caller's maps (SSD_MAX_STAIR_MAPS records) and the batch's index
+   * frame -> map (F ints), each pinned and on the device, made on the first call and counted as workspace.  One set, like the refit's gates:
+   * mapPass orders the passes that read it, and a call waits for mapsCopied before it refills the pinned side */
+  ssd::DeviceBuf<ssd_stair_map> dStairMaps;
+  ssd::PinnedBuf<ssd_stair_map> hStairMaps;
+  ssd::DeviceBuf<int> dMapIndex;
+  ssd::PinnedBuf<int> hMapIndex;
+  ssd::Event mapsCopied;                    /* behind the copies pinned -> device: the pinned side may be written again */
+  ssd_ordered_pass mapPass;
+  /* ssd_process_host_stair_map: the records its slices accumulate into (SSD_MAX_STAIR_MAPS of them), made on its first call; staging
+   * like gridStage, not counted as workspace */
+  ssd::DeviceBuf<ssd_frame_tread_grid> mapStage;
 };
 
 /* The single pass's planes - dPlaneImg and dFallback of every workspace and the pinned hFallback, zeroed - for ALL workspaces of the

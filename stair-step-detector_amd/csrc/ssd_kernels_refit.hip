@@ -71,3 +71,5 @@ void launch_surface_refit(const Batch &B, int chunkPoints, const ssd_frame_gates
 #include "ssd_kernels_clearance.hip"
 /* ... and the tread grid (section 7n), which is built on it */
 #include "ssd_kernels_treadgrid.hip"
+/* ... and the stair map (section 7p), which is the tread grid's walk with another source and destination */
+#include "ssd_kernels_stairmap.hip"

@@ -84,31 +84,51 @@ __device__ __forceinline__ void tread_grid_count(unsigned int *counts, int (&key
 #endif
 }
 
-/* The body of k_tread_grid and k_tread_grid_cams.
+/* Where a block's staircase comes from and where its counts go (tread_grid_block's `where`): index(frame) = which result and which record
+ * of the body's `results` and `out` are the block's (below 0: none, the block adds nothing; kEveryFrame: that cannot be), header(..) writes
+ * what the pass owes the records' headers, result(..) is the staircase.  The tread grid's own: the frame's result record, the frame's
+ * record of the caller's; the record's header as k_clearance writes its own.  The stair map's: ssd_kernels_stairmap.hip */
+struct TreadGridOwnFrame
+{
+  static constexpr bool kEveryFrame = true;
+  static constexpr bool kSharedRecord = false;   /* a record is one frame's: its few occupants send their heights as they come */
+  const FrameState *__restrict__ st;
+  __device__ __forceinline__ int index(int frame) const { return frame; }
+  __device__ __forceinline__ void header(int frame, int tid, ssd_frame_tread_grid *__restrict__ out) const
+  {
+    const FrameState &fs = st[frame];
+    const bool live = fs.anyActive != 0u && (fs.status & SSD_ST_THROW) == 0u;
+    if(live && tid == 0 && blockIdx.y == 0)
+    {
+      const int nLive = fs.nLive;
+      out[frame].n_surfaces = min(nLive, SSD_MAX_STEPS);
+      out[frame].ground = (nLive > 0 && fs.accActive[kGroundAcc]) ? 1 : 0;
+    }
+  }
+  __device__ __forceinline__ const ssd_frame_result &result(const ssd_frame_result *__restrict__ results, int at) const { return results[at]; }
+};
+
+/* The body of k_tread_grid and k_tread_grid_cams, and of k_stair_map and k_stair_map_cams (ssd_kernels_stairmap.hip): `where` says whose
+ * staircase the block reads and which record of `out` it adds to, and writes the headers.
  * Prologue: clearance's - a thread per reported surface turns its step into the rule's record and its own frame (LDS); a thread per
  * height bin gathers the surfaces whose band, and those whose slab (height - lo .. height + lo), widened by one bin at each end,
  * overlaps the bin - supersets: the per-point rule decides; a surface whose height is a NaN holds every point in its slab (the rule's
  * comparison is negated) and is a slab candidate of every bin.
  * Per point, cheapest test first: world_z, the two tables, the slabs, then world_xy, the sides, and last the divisions for the cell. */
-template<int SRC>
+template<int SRC, class Where>
 __device__ __forceinline__ void tread_grid_block(TreadGridLds &L, const float *__restrict__ xyz, size_t strideFloats, const PointParams &P,
-                                                 const ClearanceWorld &X, const FrameState *__restrict__ st, const uint2 *__restrict__ tileMasks,
+                                                 const ClearanceWorld &X, const Where &where, const uint2 *__restrict__ tileMasks,
                                                  size_t tileMaskStride, int chunkPoints, const DepthSrc &D, const ssd_frame_result *__restrict__ results,
                                                  const ssd_tread_grid_rule &rule, ssd_frame_tread_grid *__restrict__ out)
 {
   const int tid = threadIdx.x, lane = tid & 63;
   const int frame = blockIdx.x;
-  const FrameState &fs = st[frame];
-  const ssd_frame_result &res = results[frame];
+  const int at = where.index(frame);
   const double lo = rule.clearance.lo, hi = rule.clearance.hi;
-  /* the record's header as k_clearance writes its own */
-  const bool live = fs.anyActive != 0u && (fs.status & SSD_ST_THROW) == 0u;
-  if(live && tid == 0 && blockIdx.y == 0)
-  {
-    const int nLive = fs.nLive;
-    out[frame].n_surfaces = min(nLive, SSD_MAX_STEPS);
-    out[frame].ground = (nLive > 0 && fs.accActive[kGroundAcc]) ? 1 : 0;
-  }
+  where.header(frame, tid, out);
+  if(!Where::kEveryFrame && at < 0)
+    return;
+  const ssd_frame_result &res = where.result(results, at);
   const int nSteps = (res.status & SSD_ST_THROW) ? 0 : min(max(res.n_steps, 0), SSD_MAX_STEPS);
   if(nSteps == 0)
     return;
@@ -207,22 +227,26 @@ __device__ __forceinline__ void tread_grid_block(TreadGridLds &L, const float *_
         /* the count in LDS beside the tread points'; the maximum straight to the record's word, which lies at the slot's place in the
          * surface's top plane (top_out for the slot behind the cells): occupants are rare */
         const int k = occKey / kTgSlots, cell = occKey - k * kTgSlots;
-        ssd_tread_grid &G = out[frame].s[k];
+        ssd_tread_grid &G = out[at].s[k];
         atomicAdd(&L.counts[occKey], 0x10000u);
-        atomicMax(cell < kTgCells ? &G.top[0][0] + cell : &G.top_out, topUnits);
+        int *const top = cell < kTgCells ? &G.top[0][0] + cell : &G.top_out;
+        /* a record that many frames' blocks share (the stair map): the word is read first and the atomic sent only for a height above
+         * it - a maximum only rises, so a stale read costs a redundant atomic and never a wrong byte */
+        if(!Where::kSharedRecord || __hip_atomic_load(top, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < topUnits)
+          atomicMax(top, topUnits);
       }
     }
     tread_grid_count(L.counts, seenKeys, lane, nSlots);
   }
   __syncthreads();
-  /* one global atomic per non-zero count or maximum to the frame's record, which the caller zeroed on the stream */
+  /* one global atomic per non-zero count or maximum to the block's record, which the caller zeroed on the stream (the stair map: or adds to) */
   for(int i = tid; i < nSlots; i += kThreads)
   {
     const unsigned int n = L.counts[i];
     if(n == 0u)
       continue;
     const int k = i / kTgSlots, cell = i - k * kTgSlots;
-    ssd_tread_grid &G = out[frame].s[k];
+    ssd_tread_grid &G = out[at].s[k];
     const bool in = cell < kTgCells;
     const unsigned int seen = n & 0xffffu, occ = n >> 16;
     if(seen != 0u)
@@ -240,7 +264,7 @@ __global__ __launch_bounds__(kThreads) void k_tread_grid(const float *__restrict
                                                          ssd_frame_tread_grid *__restrict__ out)
 {
   __shared__ TreadGridLds L;
-  tread_grid_block<SRC>(L, xyz, strideFloats, P, X, st, tileMasks, tileMaskStride, chunkPoints, D, results, rule, out);
+  tread_grid_block<SRC>(L, xyz, strideFloats, P, X, TreadGridOwnFrame{ st }, tileMasks, tileMaskStride, chunkPoints, D, results, rule, out);
 }
 
 /* The cameras batch's entry point, shaped like k_clearance_cams: the frame's record by scalar loads at block start, the same body. */
@@ -256,7 +280,7 @@ __global__ __launch_bounds__(kThreads) void k_tread_grid_cams(const float *__res
   const PointParams P = C.P.pt;
   const ClearanceWorld X{ { C.P.r2[0], C.P.r2[1], C.P.r2[2], C.P.r2[3] }, { C.P.t2[0], C.P.t2[1] }, C.P.worldZ };
   const DepthSrc D = C.D;
-  tread_grid_block<SRC>(L, xyz, strideFloats, P, X, st, tileMasks, tileMaskStride, chunkPoints, D, results, rule, out);
+  tread_grid_block<SRC>(L, xyz, strideFloats, P, X, TreadGridOwnFrame{ st }, tileMasks, tileMaskStride, chunkPoints, D, results, rule, out);
 }
 
 /* grid and block size are launch_clearance's */

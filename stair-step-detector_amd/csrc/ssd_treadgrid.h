@@ -105,6 +105,45 @@ inline void tread_grid_world(const TreadGridAxes &G, double cell, double row, do
 struct Batch;                                 /* ssd_launch.h */
 void launch_tread_grid(const Batch &B, int chunkPoints, const ssd_frame_result *results, const ssd_tread_grid_rule &rule, ssd_frame_tread_grid *out);
 
+/* k_stair_map / k_stair_map_cams (ssd_kernels_stairmap.hip) in the same place: the same walk against the caller's
+ * staircases.  maps: nmaps records, device; mapOf: the batch's index frame -> map, device, an int per frame (anything not below nmaps: the
+ * frame adds nothing); out: nmaps records, which the launch only adds to and raises, and whose headers it writes */
+void launch_stair_map(const Batch &B, int chunkPoints, const ssd_stair_map *maps, const int *mapOf, int nmaps, const ssd_tread_grid_rule &rule,
+                      ssd_frame_tread_grid *out);
+
+/* The fold's step over two records (ssd_tread_grid_add): false, and acc as it was, if a count would pass 2^32 - 1 */
+inline bool tread_grid_add(const ssd_frame_tread_grid &in, ssd_frame_tread_grid &acc)
+{
+  for(int k = 0; k < SSD_MAX_STEPS; k++)
+  {
+    const ssd_tread_grid &a = in.s[k], &b = acc.s[k];
+    bool over = a.n_seen_out > 0xffffffffu - b.n_seen_out || a.n_occ_out > 0xffffffffu - b.n_occ_out;
+    for(int i = 0; i < kTgCells && !over; i++)
+      over = (&a.seen[0][0])[i] > 0xffffffffu - (&b.seen[0][0])[i] || (&a.occ[0][0])[i] > 0xffffffffu - (&b.occ[0][0])[i];
+    if(over)
+      return false;
+  }
+  acc.n_surfaces = in.n_surfaces;
+  acc.ground = in.ground;
+  for(int k = 0; k < SSD_MAX_STEPS; k++)
+  {
+    const ssd_tread_grid &a = in.s[k];
+    ssd_tread_grid &b = acc.s[k];
+    b.n_seen_out += a.n_seen_out;
+    b.n_occ_out += a.n_occ_out;
+    if(a.top_out > b.top_out)
+      b.top_out = a.top_out;
+    for(int i = 0; i < kTgCells; i++)
+    {
+      (&b.seen[0][0])[i] += (&a.seen[0][0])[i];
+      (&b.occ[0][0])[i] += (&a.occ[0][0])[i];
+      if((&a.top[0][0])[i] > (&b.top[0][0])[i])
+        (&b.top[0][0])[i] = (&a.top[0][0])[i];
+    }
+  }
+  return true;
+}
+
 } // namespace ssd
 
 #endif /* SSD_TREADGRID_H_ */
