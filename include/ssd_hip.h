@@ -1098,6 +1098,127 @@ int ssd_process_host_cameras_stair_map(ssd_handle *h, const void *frames, int nf
                                        int min_seen, int min_occ, double foot_along, double foot_deep, ssd_frame_result *results,
                                        ssd_frame_tread_grid *grids /* nmaps, may be NULL */, ssd_frame_footholds *out /* nmaps */);
 
+/* ---- stair pose: a camera located against a stair map from its treads and risers ------------------------------------------------------
+ * EXTENSION.  The ground fit refines CameraToWorld (a, b) from the floor and carries ToExternalWorld (r2, t2,
+ * world_z) over from the prior; a camera that sees no floor, or whose yaw or place in the shared world is off, has no tool.  A stair map
+ * has what is missing: its treads are horizontal planes at known heights (height, pitch, roll), its risers vertical planes under known
+ * front edges (yaw, the place along the going).  One streaming pass sorts every point of a frame onto the MAP's planes and sums each
+ * class into the exact integer moments of ssd_ground_moments; a host solve turns the moments of many frames into one rigid correction
+ * and a whole ssd_calibration.  The frame's own detection is not read: every frame counts, as for the stair map.
+ *
+ * A point (float camera coordinates; 16-bit depth is deprojected first, bit-equal to ssd_deproject_host, under the prior's intrinsics) is
+ * valid when z > 0; w = A p + b as K1's doubles form it (each row (a0 x + a1 y) + a2 z, then + b, no FMA); it is in range when w lies
+ * strictly inside the x and y measuring range; (ex, ey) = r2 w_xy + t2 row sums left to right, ez = w.z + world_z.  A valid, in-range
+ * point belongs to the first class that applies:
+ *   tread k   the lowest k < n_steps with !(fabs(ez - h_k) > band) and (ex, ey) inside step k's quadrilateral shrunk by margin (the tread
+ *             grid's tread point, against the map);
+ *   riser i   the lowest i in 0 .. n_steps - 2 with ez > h_i + clear && ez < h_(i+1) - clear and, FL -> FR the front edge of step i + 1,
+ *             (dx, dy) = FR - FL, L2 = dx dx + dy dy, a = ex - FL.x, b = ey - FL.y, c = b dx - a dy, t = a dx + b dy:
+ *             c c <= (reach reach) L2 && t >= 0 && t <= L2 - no square root, no division; L2 == 0 or any NaN takes nothing;
+ *   otherwise none.
+ * A classified point adds the ten sums to its class (q = llrint(double(v) * 65536.0) per camera coordinate); one with some |q| >= 2^20
+ * adds 1 to the class's n_far instead.  Everything summed is an integer: the device and ssd_stair_pose_host agree bit for bit.
+ * The record is one per FRAME (a frame's sums cannot overflow - the ground fit's argument; a sum over frames can, so the fold over frames
+ * is the host's, where overflow is caught): treads.n_surfaces = n_steps, treads.ground = the map's ground != 0, risers.n_surfaces =
+ * max(n_steps - 1, 0), risers.ground = 0, classes past the counts zero.  A map with SSD_ST_THROW or n_steps == 0, and a frame that names
+ * SSD_STAIR_MAP_NONE, give an all-zero record.
+ *
+ * The solve (ssd_stair_pose_solve) is ONE Gauss-Newton step of point-to-plane alignment formed from the moments alone.  A class takes part
+ * when n >= max(min_points, 1), a tread also when its ring has an orientation (twice its signed area != 0), a riser when L2 > 0.  Tread k's
+ * plane is normal (0, 0, 1), offset h_k; riser i's normal (-dy, dx, 0) / sqrt(L2), offset normal . FL.  With e = T p + c the prior's affine
+ * map camera -> external world, the residual is r = n . e - d and the correction e' = Rot(w)(e - E) + E + t, E the centroid of all used
+ * points; r and the Jacobian row [(e - E) x n ; n] are affine in p, so the 6 x 6 normal matrix and its right-hand side follow from each
+ * class's n, s, ss - centroid and centred scatter exact in 128-bit integers, doubles after that.  The rotation columns are scaled by rho,
+ * the rms distance of the used points from E, so that the six eigenvalues (cyclic Jacobi, divided by the point count) are comparable;
+ * the directions with lambda_j >= observable * lambda_max, and above the 64 eps lambda_max rounding level, are kept and the step is
+ * solved in their span.  A STRAIGHT staircase does not observe the translation along its edges: the expected dof is 5 (6 with risers in
+ * two directions, 3 from treads alone).
+ * SSD_SP_OBSERVABLE is the geometric mean of two ratios lambda / lambda_max from the spectra profiles/stair_pose_accuracy.txt records on the
+ * median map of the 3-step scene: the largest of the direction a straight staircase does not observe - 0 there, the map's drawn edges
+ * being exactly parallel, so the solve's rounding level 64 eps = 1.421e-14 stands in for it - and 8.533e-02, the smallest of a direction
+ * it does observe.  A map whose edges are a little out of parallel lifts the unobserved direction above this default: a caller who
+ * knows its staircase straight passes an `observable` of its own. */
+#define SSD_SP_OBSERVABLE 3.5e-8
+#define SSD_SP_MARGIN 0.03     /* the defaults of ssd_stair_pose_rule, metres: the tread grid's margin and slab, ... */
+#define SSD_SP_BAND 0.03
+#define SSD_SP_CLEAR 0.03      /* ... a riser point stays this far from the treads above and below it, ... */
+#define SSD_SP_REACH 0.04      /* ... and within this of the plane under the front edge */
+
+typedef struct
+{
+  double margin;   /* [0, 1]: how far inside a tread's sides a tread point lies */
+  double band;     /* (0, 1]: |ez - h_k| <= band */
+  double clear;    /* (0, 1]: a riser point lies in (h_i + clear, h_(i+1) - clear) */
+  double reach;    /* (0, 1]: ... and within reach of the vertical plane under the front edge of step i + 1 */
+} ssd_stair_pose_rule;
+
+typedef struct
+{
+  ssd_camera prior;      /* the calibration the frames are read under (and the intrinsics, for 16-bit depth) */
+  ssd_stair_map map;     /* the staircase, external world */
+} ssd_stair_pose_target;
+
+typedef struct
+{
+  ssd_frame_moments treads;   /* s[k]: tread k */
+  ssd_frame_moments risers;   /* s[i]: the riser between steps i and i + 1 */
+} ssd_stair_pose_moments;     /* 3008 bytes */
+
+typedef struct
+{
+  int32_t status;             /* in this order: SSD_GF_FEW (no class used), SSD_GF_DEGENERATE (no direction kept, or no calibration), SSD_GF_OK */
+  int32_t dof;                /* directions kept */
+  uint32_t treads_used, risers_used;   /* bit k: tread k / riser k took part */
+  int64_t n, n_far;           /* over the used classes */
+  double rotation[3];         /* w, radians, external axes */
+  double translation[3];      /* t, metres */
+  double centre[3];           /* E */
+  double eig[6];              /* of the scaled normal matrix over n, ascending */
+  double rms_before;          /* of r over the used points */
+  double rms_after;           /* ... as the linear model predicts it behind the step */
+  ssd_calibration cal;        /* with R' = Rot(w) T (Rodrigues) and c' = Rot(w)(c - E) + E + t: the floor plane n0 = -row3(R'), dist = c'_z -
+                                 world_z gives a, b (ssd_calibration_from_plane's code); r2 = R'[0:2,:] a[0:2,:]^T, t2 = c'_xy, world_z the
+                                 prior's.  Unless status is SSD_GF_OK: the prior, and the doubles above 0 */
+} ssd_stair_pose;
+
+/* host only, no GPU needed: the rule restated for ONE frame.  input = SSD_INPUT_VERTICES (width * height xyz floats) or SSD_INPUT_DEPTH16
+ * (width * height uint16; the prior's intrinsics are required).  SSD_E_ARG: a null pointer, a bad input, a rule outside its ranges (a NaN
+ * fails), the map's n_steps outside 0 .. SSD_MAX_STEPS, depth input without valid intrinsics. */
+int ssd_stair_pose_host(const ssd_config *cfg, const ssd_stair_pose_target *target, int input, const void *frame,
+                        const ssd_stair_pose_rule *rule, ssd_stair_pose_moments *out);
+/* host only: the fold's step.  acc's headers become in's and every int64 of in is added to acc's; if a sum would leave int64: SSD_E_CAP,
+ * and acc is untouched - a record whole or not at all.  SSD_E_ARG: a null pointer. */
+int ssd_stair_pose_add(const ssd_stair_pose_moments *in, ssd_stair_pose_moments *acc);
+/* host only: the solve above.  moments: a frame's record or a fold of many.  Always SSD_OK for non-null arguments and a map whose n_steps
+ * lies in 0 .. SSD_MAX_STEPS (else SSD_E_ARG). */
+int ssd_stair_pose_solve(const ssd_stair_pose_moments *moments, const ssd_stair_pose_target *target, int min_points, double observable,
+                         ssd_stair_pose *out);
+/* The pass (k_stair_pose) over frames resident in device memory, on the caller's stream, in order, without synchronising: the ground
+ * fit's contract - no detection workspace, nothing ssd_fetch* reads is touched; calls on different streams run in call order.
+ * targets: ntargets records in HOST memory, 1 .. SSD_MAX_STAIR_MAPS; target_of_frame: nframes entries in HOST memory, each below
+ * ntargets or SSD_STAIR_MAP_NONE (NULL: every frame names target 0); both are copied during the call.  The buffers (a record per frame
+ * of max_frames_per_batch on the device and pinned, the targets, the index) are made on the first call and counted in
+ * ssd_workspace_bytes from then on; a handle that never calls this allocates and launches nothing for it.
+ * SSD_E_ARG before anything is launched or copied: the ground fit's refusals (null handle or frames, nframes outside 1 ..
+ * max_frames_per_batch, a bad input, frames off their element's alignment or a stride that holds no frame), a null or bad rule, null
+ * targets, ntargets out of range, a map's n_steps outside 0 .. SSD_MAX_STEPS, a bad index, depth input with a target without valid
+ * intrinsics. */
+int ssd_enqueue_stair_pose(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream, int input,
+                           const ssd_stair_pose_target *targets /* HOST, ntargets */, int ntargets,
+                           const uint16_t *target_of_frame /* HOST, nframes; NULL: 0 */, const ssd_stair_pose_rule *rule);
+/* waits for the last ssd_enqueue_stair_pose and hands over its records, byte for byte ssd_stair_pose_host's; nframes <= its */
+int ssd_fetch_stair_pose_moments(ssd_handle *h, ssd_stair_pose_moments *out, int nframes, void *stream);
+/* waits likewise; per target of the last call the fold (ssd_stair_pose_add, frame order) of the records of the frames that name it,
+ * then ssd_stair_pose_solve against that target.  out: that call's ntargets records.  SSD_E_CAP: a fold left int64. */
+int ssd_fetch_stair_pose(ssd_handle *h, ssd_stair_pose *out, int min_points, double observable, void *stream);
+/* the device time of the last pass, the zeroing in front of it and the copy of its records behind it included (0 when timing was off for it) */
+int ssd_get_stair_pose_time(ssd_handle *h, float *ms);
+/* frames in host memory (pinned or pageable), any nframes >= 1, in slices through the staging buffers of ssd_process_host; the records
+ * are folded across the slices on the host.  moments (may be NULL): nframes records; out: ntargets. */
+int ssd_process_host_stair_pose(ssd_handle *h, const void *frames, int nframes, int input, const ssd_stair_pose_target *targets, int ntargets,
+                                const uint16_t *target_of_frame, const ssd_stair_pose_rule *rule, int min_points, double observable,
+                                ssd_stair_pose_moments *moments /* may be NULL */, ssd_stair_pose *out /* ntargets */);
+
 /* stage selector for profiling / roofline measurement: runs only the chosen stage(s) of the pipeline */
 #define SSD_STAGE_HIST 1       /* K1: transform + crop + bin + histogram */
 #define SSD_STAGE_PEAKS 2

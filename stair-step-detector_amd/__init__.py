@@ -236,6 +236,39 @@ class StairMap(C.Structure):
     _fields_ = [("stairs", FrameResult), ("ground", C.c_int32), ("reserved", C.c_int32)]
 
 
+SP_OBSERVABLE = 3.5e-8       # SSD_SP_OBSERVABLE
+SP_MARGIN, SP_BAND, SP_CLEAR, SP_REACH = 0.03, 0.03, 0.03, 0.04   # SSD_SP_*: the defaults of StairPoseRule
+
+
+class StairPoseRule(C.Structure):
+    """ssd_stair_pose_rule: how far inside a tread's sides (margin) and how near its height (band) a tread point lies, how far from the
+    treads above and below (clear) and how near the plane under the front edge (reach) a riser point, metres (stair pose, DESIGN.md
+    section 7q)"""
+    _fields_ = [("margin", C.c_double), ("band", C.c_double), ("clear", C.c_double), ("reach", C.c_double)]
+
+    def __init__(self, margin=SP_MARGIN, band=SP_BAND, clear=SP_CLEAR, reach=SP_REACH):
+        super().__init__(float(margin), float(band), float(clear), float(reach))
+
+
+class StairPoseTarget(C.Structure):
+    """ssd_stair_pose_target: the prior the frames are read under and the staircase they are held against"""
+    _fields_ = [("prior", Camera), ("map", StairMap)]
+
+
+class StairPoseMoments(C.Structure):
+    """ssd_stair_pose_moments: a frame's points on the map's treads (treads.s[k]) and risers (risers.s[i]: between steps i and i + 1)
+    as exact integer moments"""
+    _fields_ = [("treads", FrameMoments), ("risers", FrameMoments)]
+
+
+class StairPose(C.Structure):
+    """ssd_stair_pose: one Gauss-Newton step of the camera against the map and the calibration it gives (status != GF_OK: cal is the
+    prior, the doubles are 0)"""
+    _fields_ = [("status", C.c_int32), ("dof", C.c_int32), ("treads_used", C.c_uint32), ("risers_used", C.c_uint32), ("n", C.c_int64),
+                ("n_far", C.c_int64), ("rotation", C.c_double * 3), ("translation", C.c_double * 3), ("centre", C.c_double * 3),
+                ("eig", C.c_double * 6), ("rms_before", C.c_double), ("rms_after", C.c_double), ("cal", Calibration)]
+
+
 class Foothold(C.Structure):
     """ssd_foothold: one surface's cells (TG_OUT / TG_FREE / TG_OCCUPIED / TG_UNSEEN) and the best free rectangle on it"""
     _fields_ = [("state", C.c_uint8 * TG_COLS * TG_ROWS), ("n_free", C.c_int32), ("n_occupied", C.c_int32), ("n_unseen", C.c_int32),
@@ -326,6 +359,8 @@ EXPORTS = [
     "ssd_tread_grid_solve", "ssd_process_host_tread_grid", "ssd_process_host_cameras_tread_grid",
     "ssd_tread_grid_add", "ssd_stair_map_from_results", "ssd_enqueue_stair_map", "ssd_enqueue_cameras_stair_map", "ssd_fetch_stair_map",
     "ssd_get_stair_map_time", "ssd_process_host_stair_map", "ssd_process_host_cameras_stair_map",
+    "ssd_stair_pose_host", "ssd_stair_pose_add", "ssd_stair_pose_solve", "ssd_enqueue_stair_pose", "ssd_fetch_stair_pose_moments",
+    "ssd_fetch_stair_pose", "ssd_get_stair_pose_time", "ssd_process_host_stair_pose",
 ]
 # libssd_source.so — the frame source standing in for the camera (include/ssd_source.h)
 SOURCE_EXPORTS = [
@@ -462,6 +497,15 @@ def lib():
     L.ssd_process_host_cameras_stair_map.argtypes = [vp, vp, i32, C.POINTER(C.c_uint16), i32, C.POINTER(StairMap), i32, C.POINTER(C.c_uint16),
                                                      C.POINTER(TreadGridRule), i32, i32, C.c_double, C.c_double, C.POINTER(FrameResult),
                                                      C.POINTER(FrameTreadGrid), C.POINTER(FrameFootholds)]
+    L.ssd_stair_pose_host.argtypes = [C.POINTER(Config), C.POINTER(StairPoseTarget), i32, vp, C.POINTER(StairPoseRule), C.POINTER(StairPoseMoments)]
+    L.ssd_stair_pose_add.argtypes = [C.POINTER(StairPoseMoments), C.POINTER(StairPoseMoments)]
+    L.ssd_stair_pose_solve.argtypes = [C.POINTER(StairPoseMoments), C.POINTER(StairPoseTarget), i32, C.c_double, C.POINTER(StairPose)]
+    L.ssd_enqueue_stair_pose.argtypes = [vp, vp, sz, i32, vp, i32, C.POINTER(StairPoseTarget), i32, C.POINTER(C.c_uint16), C.POINTER(StairPoseRule)]
+    L.ssd_fetch_stair_pose_moments.argtypes = [vp, C.POINTER(StairPoseMoments), i32, vp]
+    L.ssd_fetch_stair_pose.argtypes = [vp, C.POINTER(StairPose), i32, C.c_double, vp]
+    L.ssd_get_stair_pose_time.argtypes = [vp, C.POINTER(C.c_float)]
+    L.ssd_process_host_stair_pose.argtypes = [vp, vp, i32, i32, C.POINTER(StairPoseTarget), i32, C.POINTER(C.c_uint16), C.POINTER(StairPoseRule), i32,
+                                              C.c_double, C.POINTER(StairPoseMoments), C.POINTER(StairPose)]
     L.ssd_enqueue_cameras_surface_refit_folded.argtypes = [vp, vp, sz, i32, vp, i32, vp, i32, C.c_double, C.c_double, i32, vp]
     L.ssd_camera_drift_from_fold.argtypes = [C.POINTER(CameraFold), C.POINTER(Camera), i32, i32, C.POINTER(CameraDrift)]
     L.ssd_process_host_cameras_drift.argtypes = [vp, vp, i32, C.POINTER(C.c_uint16), i32, C.POINTER(FrameResult), i32, C.c_double, C.c_double, i32, i32,
@@ -853,6 +897,54 @@ def stair_map_from_results(results, ground=1):
     out, used = StairMap(), C.c_int32(0)
     _check(lib().ssd_stair_map_from_results(arr, len(results), int(ground), C.byref(out), C.byref(used)))
     return out, int(used.value)
+
+
+# --------------------------------------------------------------------------- stair pose: host functions (no GPU needed)
+def stair_pose_target(prior, stair_map, intr=None):
+    """a StairPoseTarget from a prior (a Camera, or anything Detector.set_cameras takes) and a StairMap or FrameResult (ground flag 1)"""
+    if isinstance(prior, StairPoseTarget):
+        return prior
+    t = StairPoseTarget()
+    t.prior = _as_camera(prior, intr)
+    t.map = _stair_maps(stair_map)[0][0]
+    return t
+
+
+def _pose_targets(targets):
+    """one StairPoseTarget, one (prior, map) pair or a sequence of either -> (StairPoseTarget array, count)"""
+    if isinstance(targets, StairPoseTarget) or (isinstance(targets, tuple) and len(targets) == 2 and isinstance(targets[1], (StairMap, FrameResult))):
+        targets = [targets]
+    targets = [t if isinstance(t, StairPoseTarget) else stair_pose_target(*t) for t in targets]
+    arr = (StairPoseTarget * max(len(targets), 1))()
+    for i, t in enumerate(targets):
+        C.memmove(C.byref(arr[i]), C.byref(t), C.sizeof(StairPoseTarget))
+    return arr, len(targets)
+
+
+def stair_pose_host(cfg, target, frame, rule=None, depth=False):
+    """ssd_stair_pose_host: one frame's points on the target's treads and risers -> StairPoseMoments.  frame: float32 [H, W, 3], or
+    uint16 [H, W] with depth=True (the target's prior then carries the intrinsics)."""
+    a = np.ascontiguousarray(frame, dtype=np.uint16 if depth else np.float32)
+    if a.size != cfg.width * cfg.height * (1 if depth else 3):
+        raise SsdError("stair_pose_host: the array is not one frame")
+    out = StairPoseMoments()
+    rule = rule or StairPoseRule()
+    _check(lib().ssd_stair_pose_host(C.byref(cfg), C.byref(target), _input_code(depth), a.ctypes.data_as(C.c_void_p), C.byref(rule), C.byref(out)))
+    return out
+
+
+def stair_pose_add(moments, acc):
+    """ssd_stair_pose_add: the fold's step - acc's headers become moments', every sum is added; SsdError (SSD_E_CAP) and acc untouched
+    if a sum would leave int64.  Returns acc."""
+    _check(lib().ssd_stair_pose_add(C.byref(moments) if moments is not None else None, C.byref(acc) if acc is not None else None))
+    return acc
+
+
+def stair_pose_solve(moments, target, min_points=200, observable=SP_OBSERVABLE):
+    """ssd_stair_pose_solve: a frame's record, or a fold of many, -> one Gauss-Newton step against the target's map (StairPose)"""
+    out = StairPose()
+    _check(lib().ssd_stair_pose_solve(C.byref(moments), C.byref(target), int(min_points), float(observable), C.byref(out)))
+    return out
 
 
 def riser_fit_solve(moments, risers, cal, min_points=100):
@@ -1356,6 +1448,69 @@ class Detector:
                                        foot_deep=0.0, depth=False, grids=False):
         """ssd_process_host_cameras_stair_map: process_host_stair_map with one camera index per frame"""
         return self.process_host_stair_map(frames, maps, map_of_frame, rule, min_seen, min_occ, foot_along, foot_deep, depth, camera_of_frame, grids)
+
+    # ---- stair pose: a camera located against a stair map from its treads and risers (include/ssd_hip.h, DESIGN.md section 7q)
+    def enqueue_stair_pose(self, d_ptr, nframes, targets, target_of_frame=None, rule=None, depth=False, stride_bytes=None, stream=None):
+        """ssd_enqueue_stair_pose: every frame's points sorted onto its target's treads and risers, on the caller's stream.  targets: a
+        StairPoseTarget, a (prior, map) pair or a sequence of either (host; copied during the call); target_of_frame: None = target 0, or
+        one index per frame (STAIR_MAP_NONE: the frame adds nothing)."""
+        arr, n = _pose_targets(targets)
+        idx = _map_index(target_of_frame, nframes)
+        rule = rule or StairPoseRule()
+        frame = self.cfg.width * self.cfg.height * (2 if depth else 12)
+        _check(lib().ssd_enqueue_stair_pose(self._h, C.c_void_p(d_ptr), stride_bytes or frame, nframes, C.c_void_p(stream or 0), _input_code(depth),
+                                            arr, n, None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_uint16)), C.byref(rule)))
+        self._pose_targets = n
+
+    def fetch_stair_pose_moments(self, nframes, stream=None):
+        """ssd_fetch_stair_pose_moments: waits for the last enqueue_stair_pose -> list of StairPoseMoments (independent copies)"""
+        out = (StairPoseMoments * nframes)()
+        _check(lib().ssd_fetch_stair_pose_moments(self._h, out, nframes, C.c_void_p(stream or 0)))
+        return [StairPoseMoments.from_buffer_copy(r) for r in out]
+
+    def fetch_stair_pose(self, min_points=200, observable=SP_OBSERVABLE, stream=None):
+        """ssd_fetch_stair_pose: waits likewise; per target the fold of its frames' records, solved -> list of StairPose"""
+        n = getattr(self, "_pose_targets", 0)                         # the last call's targets (process_host_stair_pose's slices are calls too)
+        out = (StairPose * MAX_STAIR_MAPS)()
+        _check(lib().ssd_fetch_stair_pose(self._h, out, int(min_points), float(observable), C.c_void_p(stream or 0)))
+        return [StairPose.from_buffer_copy(out[i]) for i in range(n)]
+
+    def stair_pose_time_ms(self):
+        """the device time of the last stair pose pass, its zeroing and its records' copy included (0 unless set_timing was on)"""
+        return _time_ms(lib().ssd_get_stair_pose_time, self._h)
+
+    def process_host_stair_pose(self, frames, targets, target_of_frame=None, rule=None, min_points=200, observable=SP_OBSERVABLE, depth=False,
+                                moments=False):
+        """ssd_process_host_stair_pose: frames on the host (float32 [n, H, W, 3], or uint16 [n, H, W] with depth=True) -> list of StairPose,
+        one per target (with moments=True: (that, list of StairPoseMoments, one per frame))"""
+        a, n, inp = self._frames_arg("process_host_stair_pose", frames, depth)
+        arr, nt = _pose_targets(targets)
+        idx = _map_index(target_of_frame, n)
+        rule = rule or StairPoseRule()
+        out = (StairPose * max(nt, 1))()
+        recs = (StairPoseMoments * n)() if moments else None
+        _check(lib().ssd_process_host_stair_pose(self._h, a.ctypes.data_as(C.c_void_p), n, inp, arr, nt,
+                                                 None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_uint16)), C.byref(rule), int(min_points),
+                                                 float(observable), recs, out))
+        self._pose_targets = nt
+        poses = [StairPose.from_buffer_copy(out[i]) for i in range(nt)]
+        return (poses, [StairPoseMoments.from_buffer_copy(r) for r in recs]) if moments else poses
+
+    def locate_camera(self, frames, prior, stair_map, passes=3, rule=None, min_points=200, observable=SP_OBSERVABLE, depth=False):
+        """process_host_stair_pose `passes` times over the same frames of ONE camera, each pass starting from the calibration the pass
+        before gave (as refine_calibration chains the ground fit).  A pass that does not end GF_OK ends the chain: the last good
+        calibration stays in .cal of the returned record, which reports the failing status.  -> (StairPose of the last pass run, the
+        list of every pass's StairPose)"""
+        cam = Camera.from_buffer_copy(_as_camera(prior))
+        maps = _stair_maps(stair_map)[0][0]
+        chain = []
+        for _ in range(max(int(passes), 1)):
+            pose = self.process_host_stair_pose(frames, stair_pose_target(cam, maps), None, rule, min_points, observable, depth)[0]
+            chain.append(pose)
+            if pose.status != GF_OK:
+                break
+            cam.cal = pose.cal
+        return chain[-1], chain
 
     # ---- surface fit of cameras batches, drift per camera (include/ssd_hip.h, DESIGN.md section 7e)
     def enqueue_cameras_surface_moments(self, d_ptr, nframes, camera_of_frame, d_moments, depth=False, stride_bytes=None, stream=None):

@@ -9,6 +9,7 @@
 #include "ssd_handle.h"
 #include "ssd_prexy.h"
 #include "ssd_ground.h"
+#include "ssd_pose.h"
 #include "ssd_refit.h"
 #include "ssd_clearance.h"
 #include "ssd_treadgrid.h"
@@ -3976,6 +3977,580 @@ int ssd_process_host_ground_fit(ssd_handle *h, const void *frames, int nframes, 
     if(rc) return rc;
   }
   return ssd_fetch_ground_fit(h, out + feed.first(last), feed.count(last), min_points, nullptr);
+}
+
+/* ---- stair pose: a camera located against a stair map (include/ssd_hip.h) ------------------------------------ */
+
+/* the refusals about the rule, the targets and the index that the host statement, the enqueue and the host form share */
+static int check_pose_rule(const std::string &me, const ssd_stair_pose_rule *rule)
+{
+  if(!rule)
+    return fail(SSD_E_ARG, me + ": null rule");
+  if(!pose_rule_ok(*rule))
+    return fail(SSD_E_ARG, me + ": margin must lie in [0, 1], band, clear and reach in (0, 1]");
+  return SSD_OK;
+}
+
+static int check_pose_targets(const std::string &me, const ssd_stair_pose_target *targets, int ntargets, const uint16_t *target_of_frame, int nframes, int input)
+{
+  if(!targets)
+    return fail(SSD_E_ARG, me + ": null targets");
+  if(ntargets < 1 || ntargets > SSD_MAX_STAIR_MAPS)
+    return fail(SSD_E_ARG, me + ": ntargets must lie in 1 .. SSD_MAX_STAIR_MAPS");
+  for(int t = 0; t < ntargets; t++)
+  {
+    if(targets[t].map.stairs.n_steps < 0 || targets[t].map.stairs.n_steps > SSD_MAX_STEPS)
+      return fail(SSD_E_ARG, me + ": a map's n_steps must lie in 0 .. SSD_MAX_STEPS");
+    if(input == SSD_INPUT_DEPTH16 && (!targets[t].prior.has_intrinsics || !good_intrinsics(targets[t].prior.intr)))
+      return fail(SSD_E_ARG, me + ": depth input, and target " + std::to_string(t) + " has no (valid) intrinsics");
+  }
+  for(int i = 0; i < nframes && target_of_frame; i++)
+    if(target_of_frame[i] != SSD_STAIR_MAP_NONE && target_of_frame[i] >= ntargets)
+      return fail(SSD_E_ARG, me + ": target_of_frame holds an index that is neither below ntargets nor SSD_STAIR_MAP_NONE");
+  return SSD_OK;
+}
+
+int ssd_stair_pose_host(const ssd_config *cfg, const ssd_stair_pose_target *target, int input, const void *frame, const ssd_stair_pose_rule *rule,
+                        ssd_stair_pose_moments *out)
+{
+  const std::string me("ssd_stair_pose_host");
+  if(!cfg || !target || !frame || !out || cfg->width <= 0 || cfg->height <= 0)
+    return fail(SSD_E_ARG, me + ": bad argument");
+  if(input != SSD_INPUT_VERTICES && input != SSD_INPUT_DEPTH16)
+    return fail(SSD_E_ARG, me + ": input must be SSD_INPUT_VERTICES or SSD_INPUT_DEPTH16");
+  int rc = check_pose_rule(me, rule);
+  if(!rc) rc = check_pose_targets(me, target, 1, nullptr, 0, input);
+  if(rc) return rc;
+  const bool depth = input == SSD_INPUT_DEPTH16;
+  PoseTarget T;
+  pose_target_fill(T, *target, depth, *rule);
+  std::memset(out, 0, sizeof(*out));
+  if(T.nSteps == 0)
+    return SSD_OK;
+  const PoseRange R{ cfg->x_min, cfg->x_max, cfg->y_min, cfg->y_max };
+  const int W = cfg->width, H = cfg->height;
+  long long acc[kPoseClasses][kPoseSums] = {};
+  auto take = [&](float x, float y, float z)
+  {
+    const int c = pose_class(T.cam, T.world, T, R, x, y, z);
+    if(c >= 0)
+      pose_add(x, y, z, acc[c]);
+  };
+  if(depth)
+  {
+    const uint16_t *d16 = static_cast<const uint16_t *>(frame);
+    std::vector<float> xm(static_cast<size_t>(W));
+    for(int u = 0; u < W; u++)
+      xm[u] = ground_map_x(T.cam, u);
+    for(int v = 0; v < H; v++)
+    {
+      const float ym = ground_map_y(T.cam, v);
+      for(int u = 0; u < W; u++)
+      {
+        const float d = static_cast<float>(d16[static_cast<size_t>(v) * W + u]) * T.cam.depthUnits;
+        take(d * xm[u], d * ym, d);
+      }
+    }
+  }
+  else
+  {
+    const float *xyz = static_cast<const float *>(frame);
+    for(size_t i = 0, n = static_cast<size_t>(W) * H; i < n; i++)
+      take(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]);
+  }
+  int64_t *rec = reinterpret_cast<int64_t *>(out);
+  for(int c = 0; c < kPoseClasses; c++)
+    for(int j = 0; j < kPoseSums; j++)
+      rec[pose_word(c) + j] = acc[c][j];
+  int32_t head[4];
+  pose_headers(T.nSteps, T.ground, head);
+  out->treads.n_surfaces = head[0]; out->treads.ground = head[1];
+  out->risers.n_surfaces = head[2]; out->risers.ground = head[3];
+  return SSD_OK;
+}
+
+int ssd_stair_pose_add(const ssd_stair_pose_moments *in, ssd_stair_pose_moments *acc)
+{
+  if(!in || !acc)
+    return fail(SSD_E_ARG, "ssd_stair_pose_add: null");
+  if(!pose_fold(*in, *acc))
+    return fail(SSD_E_CAP, "ssd_stair_pose_add: a sum would leave int64; acc is untouched");
+  return SSD_OK;
+}
+
+/* eigenvalues (ascending) and eigenvectors (columns of v) of a symmetric 6 x 6 matrix: cyclic Jacobi with jacobi3's rotation, host only
+ * (ssd_solve.h is the device's too and stays as it is).  An off-diagonal entry that no longer changes either of its diagonal
+ * neighbours when added to them is set to zero. */
+static void jacobi6(double a[6][6], double lambda[6], double v[6][6])
+{
+  for(int i = 0; i < 6; i++)
+    for(int j = 0; j < 6; j++)
+      v[i][j] = i == j ? 1.0 : 0.0;
+  for(int sweep = 0; sweep < 64; sweep++)
+  {
+    double off = 0.0;
+    for(int p = 0; p < 5; p++)
+      for(int q = p + 1; q < 6; q++)
+        off += std::fabs(a[p][q]);
+    if(off == 0.0)
+      break;
+    for(int p = 0; p < 5; p++)
+      for(int q = p + 1; q < 6; q++)
+      {
+        const double apq = a[p][q], app = a[p][p], aqq = a[q][q];
+        if(apq == 0.0)
+          continue;
+        if(std::fabs(app) + std::fabs(apq) == std::fabs(app) && std::fabs(aqq) + std::fabs(apq) == std::fabs(aqq))
+        {
+          a[p][q] = a[q][p] = 0.0;
+          continue;
+        }
+        const double theta = (aqq - app) / (2.0 * apq);
+        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+        const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+        a[p][p] = app - t * apq;
+        a[q][q] = aqq + t * apq;
+        a[p][q] = a[q][p] = 0.0;
+        for(int r = 0; r < 6; r++)
+        {
+          if(r != p && r != q)
+          {
+            const double arp = a[r][p], arq = a[r][q];
+            a[r][p] = a[p][r] = c * arp - s * arq;
+            a[r][q] = a[q][r] = s * arp + c * arq;
+          }
+          const double vrp = v[r][p], vrq = v[r][q];
+          v[r][p] = c * vrp - s * vrq;
+          v[r][q] = s * vrp + c * vrq;
+        }
+      }
+  }
+  int order[6] = { 0, 1, 2, 3, 4, 5 };
+  for(int i = 1; i < 6; i++)                       /* a stable insertion sort of the diagonal by < */
+    for(int j = i; j > 0 && a[order[j]][order[j]] < a[order[j - 1]][order[j - 1]]; j--)
+      std::swap(order[j], order[j - 1]);
+  double vv[6][6];
+  for(int k = 0; k < 6; k++)
+  {
+    lambda[k] = a[order[k]][order[k]];
+    for(int i = 0; i < 6; i++)
+      vv[i][k] = v[i][order[k]];
+  }
+  std::memcpy(v, vv, sizeof(vv));
+}
+
+/* one class of the solve: its points' count, centroid and centred covariance in the external world, and its plane */
+struct PoseClassFit
+{
+  double n, e[3], S[3][3], nrm[3], d;
+};
+
+/* a class's moments under the prior's affine map e = T p + c: the centroid and the centred scatter exact in 128-bit integers
+ * (plane_of_moments' statement: ssd_solve.h), doubles from there on */
+static void pose_class_fit(const ssd_ground_moments &m, const double T[3][3], const double c[3], PoseClassFit &f)
+{
+  typedef __int128 i128;
+  const double nd = static_cast<double>(m.n);
+  const double scale = 1.0 / (nd * nd * kGroundScale * kGroundScale);
+  const int64_t s[3] = { m.s[0], m.s[1], m.s[2] };
+  const int64_t ss[3][3] = { { m.ss[0], m.ss[1], m.ss[2] }, { m.ss[1], m.ss[3], m.ss[4] }, { m.ss[2], m.ss[4], m.ss[5] } };
+  double pc[3], cc[3][3], tc[3][3];
+  for(int i = 0; i < 3; i++)
+  {
+    pc[i] = static_cast<double>(s[i]) / (nd * kGroundScale);
+    for(int j = 0; j < 3; j++)
+      cc[i][j] = static_cast<double>(static_cast<i128>(m.n) * ss[i][j] - static_cast<i128>(s[i]) * s[j]) * scale;
+  }
+  f.n = nd;
+  for(int i = 0; i < 3; i++)
+  {
+    f.e[i] = ((T[i][0] * pc[0] + T[i][1] * pc[1]) + T[i][2] * pc[2]) + c[i];
+    for(int j = 0; j < 3; j++)
+      tc[i][j] = (T[i][0] * cc[0][j] + T[i][1] * cc[1][j]) + T[i][2] * cc[2][j];
+  }
+  for(int i = 0; i < 3; i++)
+    for(int j = 0; j < 3; j++)
+      f.S[i][j] = (tc[i][0] * T[j][0] + tc[i][1] * T[j][1]) + tc[i][2] * T[j][2];
+}
+
+/* Rot(w) by Rodrigues' formula: I + A [w]x + B [w]x^2, A = sin(th) / th, B = (1 - cos(th)) / th^2 (their limits 1 and 1/2 below 1e-8 rad) */
+static void rodrigues(const double w[3], double R[3][3])
+{
+  const double t2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2], th = std::sqrt(t2);
+  const double A = th < 1e-8 ? 1.0 : std::sin(th) / th, B = th < 1e-8 ? 0.5 : (1.0 - std::cos(th)) / t2;
+  const double K[3][3] = { { 0.0, -w[2], w[1] }, { w[2], 0.0, -w[0] }, { -w[1], w[0], 0.0 } };
+  for(int i = 0; i < 3; i++)
+    for(int j = 0; j < 3; j++)
+    {
+      const double k2 = (K[i][0] * K[0][j] + K[i][1] * K[1][j]) + K[i][2] * K[2][j];
+      R[i][j] = (i == j ? 1.0 : 0.0) + A * K[i][j] + B * k2;
+    }
+}
+
+int ssd_stair_pose_solve(const ssd_stair_pose_moments *moments, const ssd_stair_pose_target *target, int min_points, double observable,
+                         ssd_stair_pose *out)
+{
+  if(!moments || !target || !out)
+    return fail(SSD_E_ARG, "ssd_stair_pose_solve: null");
+  const ssd_frame_result &st = target->map.stairs;
+  if(st.n_steps < 0 || st.n_steps > SSD_MAX_STEPS)
+    return fail(SSD_E_ARG, "ssd_stair_pose_solve: the map's n_steps must lie in 0 .. SSD_MAX_STEPS");
+  if(!(observable >= 0.0) || !(observable <= 1.0))
+    return fail(SSD_E_ARG, "ssd_stair_pose_solve: observable must lie in [0, 1]");
+  const ssd_calibration &prior = target->prior.cal;
+  std::memset(out, 0, sizeof(*out));
+  out->cal = prior;
+  out->status = SSD_GF_FEW;
+  const int64_t need = min_points > 1 ? min_points : 1;
+  const int nSteps = (st.status & SSD_ST_THROW) ? 0 : st.n_steps;
+  /* e = T p + c: ToExternalWorld behind CameraToWorld */
+  double T[3][3], c[3];
+  for(int j = 0; j < 3; j++)
+  {
+    T[0][j] = prior.r2[0] * prior.a[j] + prior.r2[1] * prior.a[3 + j];
+    T[1][j] = prior.r2[2] * prior.a[j] + prior.r2[3] * prior.a[3 + j];
+    T[2][j] = prior.a[6 + j];
+  }
+  c[0] = (prior.r2[0] * prior.b[0] + prior.r2[1] * prior.b[1]) + prior.t2[0];
+  c[1] = (prior.r2[2] * prior.b[0] + prior.r2[3] * prior.b[1]) + prior.t2[1];
+  c[2] = prior.b[2] + prior.world_z;
+  std::vector<PoseClassFit> used;
+  for(int k = 0; k < nSteps; k++)
+  {
+    const ssd_surface_moments &sm = moments->treads.s[k];
+    ClearanceSurface ring;
+    clearance_surface(st.steps[k], 0.0, ring);
+    if(sm.m.n < need || ring.o == 0.0)
+      continue;
+    PoseClassFit f;
+    pose_class_fit(sm.m, T, c, f);
+    f.nrm[0] = 0.0; f.nrm[1] = 0.0; f.nrm[2] = 1.0;
+    f.d = st.steps[k].height;
+    used.push_back(f);
+    out->treads_used |= 1u << k;
+    out->n += sm.m.n;
+    out->n_far += sm.n_far;
+  }
+  for(int i = 0; i + 1 < nSteps; i++)
+  {
+    const ssd_surface_moments &sm = moments->risers.s[i];
+    const ssd_step &up = st.steps[i + 1];
+    const double dx = up.quad[2] - up.quad[0], dy = up.quad[3] - up.quad[1], l2 = dx * dx + dy * dy;
+    if(sm.m.n < need || !(l2 > 0.0))
+      continue;
+    PoseClassFit f;
+    pose_class_fit(sm.m, T, c, f);
+    const double len = std::sqrt(l2);
+    f.nrm[0] = -dy / len; f.nrm[1] = dx / len; f.nrm[2] = 0.0;
+    f.d = f.nrm[0] * up.quad[0] + f.nrm[1] * up.quad[1];
+    used.push_back(f);
+    out->risers_used |= 1u << i;
+    out->n += sm.m.n;
+    out->n_far += sm.n_far;
+  }
+  if(used.empty())
+    return SSD_OK;
+  out->status = SSD_GF_DEGENERATE;
+  /* the centroid of all used points, and their mean squared distance from it */
+  double N = 0.0, E[3] = { 0.0, 0.0, 0.0 };
+  for(const PoseClassFit &f : used)
+  {
+    N += f.n;
+    for(int i = 0; i < 3; i++)
+      E[i] += f.n * f.e[i];
+  }
+  for(int i = 0; i < 3; i++)
+    E[i] /= N;
+  double rho2 = 0.0;
+  for(const PoseClassFit &f : used)
+  {
+    const double m[3] = { f.e[0] - E[0], f.e[1] - E[1], f.e[2] - E[2] };
+    rho2 += f.n * (((f.S[0][0] + f.S[1][1]) + f.S[2][2]) + ((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]));
+  }
+  rho2 /= N;
+  const double rho = std::sqrt(rho2);
+  if(!(rho > 0.0) || !std::isfinite(rho))
+    return SSD_OK;
+  /* per class, with q = e - e_c (mean 0, covariance S) and m = e_c - E: the row J = M q + j0, M = [K; 0], K q = q x n, j0 = [m x n; n], and
+   * r = n . q + r_c - so sum J J^T = n (M S M^T + j0 j0^T), sum J r = n (M S n + j0 r_c), sum r r = n (n . S n + r_c r_c) */
+  double Hm[6][6] = {}, g[6] = {}, rr = 0.0;
+  for(const PoseClassFit &f : used)
+  {
+    const double *n = f.nrm;
+    const double m[3] = { f.e[0] - E[0], f.e[1] - E[1], f.e[2] - E[2] };
+    const double K[3][3] = { { 0.0, n[2], -n[1] }, { -n[2], 0.0, n[0] }, { n[1], -n[0], 0.0 } };
+    const double j0[6] = { m[1] * n[2] - m[2] * n[1], m[2] * n[0] - m[0] * n[2], m[0] * n[1] - m[1] * n[0], n[0], n[1], n[2] };
+    const double rc = ((n[0] * f.e[0] + n[1] * f.e[1]) + n[2] * f.e[2]) - f.d;
+    double KS[3][3], KSK[3][3], Sn[3], KSn[3];
+    for(int i = 0; i < 3; i++)
+    {
+      Sn[i] = (f.S[i][0] * n[0] + f.S[i][1] * n[1]) + f.S[i][2] * n[2];
+      for(int j = 0; j < 3; j++)
+        KS[i][j] = (K[i][0] * f.S[0][j] + K[i][1] * f.S[1][j]) + K[i][2] * f.S[2][j];
+    }
+    for(int i = 0; i < 3; i++)
+    {
+      KSn[i] = (KS[i][0] * n[0] + KS[i][1] * n[1]) + KS[i][2] * n[2];
+      for(int j = 0; j < 3; j++)
+        KSK[i][j] = (KS[i][0] * K[j][0] + KS[i][1] * K[j][1]) + KS[i][2] * K[j][2];
+    }
+    for(int i = 0; i < 6; i++)
+    {
+      for(int j = 0; j < 6; j++)
+        Hm[i][j] += f.n * ((i < 3 && j < 3 ? KSK[i][j] : 0.0) + j0[i] * j0[j]);
+      g[i] += f.n * ((i < 3 ? KSn[i] : 0.0) + j0[i] * rc);
+    }
+    rr += f.n * (((n[0] * Sn[0] + n[1] * Sn[1]) + n[2] * Sn[2]) + rc * rc);
+  }
+  /* the rotation columns over rho, everything over the point count: six comparable eigenvalues */
+  double Hs[6][6], gs[6], lambda[6], V[6][6];
+  for(int i = 0; i < 6; i++)
+  {
+    const double di = i < 3 ? 1.0 / rho : 1.0;
+    gs[i] = g[i] * di / N;
+    for(int j = 0; j < 6; j++)
+      Hs[i][j] = Hm[i][j] * di * (j < 3 ? 1.0 / rho : 1.0) / N;
+  }
+  for(int i = 0; i < 6; i++)                      /* exactly symmetric for the rotations */
+    for(int j = i + 1; j < 6; j++)
+      Hs[i][j] = Hs[j][i] = 0.5 * (Hs[i][j] + Hs[j][i]);
+  jacobi6(Hs, lambda, V);
+  const double lmax = lambda[5], zero = 64.0 * 2.220446049250313e-16 * lmax;
+  double y[6] = {}, gain = 0.0;
+  int dof = 0;
+  for(int k = 0; k < 6; k++)
+  {
+    if(!(lmax > 0.0) || !(lambda[k] >= observable * lmax) || !(lambda[k] > zero))
+      continue;
+    double p = 0.0;
+    for(int i = 0; i < 6; i++)
+      p += V[i][k] * gs[i];
+    for(int i = 0; i < 6; i++)
+      y[i] -= V[i][k] * (p / lambda[k]);
+    gain += p * p / lambda[k];
+    dof++;
+  }
+  if(dof == 0)
+    return SSD_OK;
+  const double w[3] = { y[0] / rho, y[1] / rho, y[2] / rho }, tau[3] = { y[3], y[4], y[5] };
+  double Rw[3][3], Rp[3][3], cp[3];
+  rodrigues(w, Rw);
+  for(int i = 0; i < 3; i++)
+  {
+    for(int j = 0; j < 3; j++)
+      Rp[i][j] = (Rw[i][0] * T[0][j] + Rw[i][1] * T[1][j]) + Rw[i][2] * T[2][j];
+    cp[i] = (((Rw[i][0] * (c[0] - E[0]) + Rw[i][1] * (c[1] - E[1])) + Rw[i][2] * (c[2] - E[2])) + E[i]) + tau[i];
+  }
+  ssd_calibration cal = prior;
+  if(!camera_to_world_from_plane(-Rp[2][0], -Rp[2][1], -Rp[2][2], cp[2] - prior.world_z, cal.a, cal.b))
+    return SSD_OK;
+  for(int i = 0; i < 2; i++)
+    for(int j = 0; j < 2; j++)
+      cal.r2[2 * i + j] = (Rp[i][0] * cal.a[3 * j] + Rp[i][1] * cal.a[3 * j + 1]) + Rp[i][2] * cal.a[3 * j + 2];
+  cal.t2[0] = cp[0];
+  cal.t2[1] = cp[1];
+  bool finite = std::isfinite(cal.t2[0]) && std::isfinite(cal.t2[1]);
+  for(int i = 0; i < 4; i++)
+    finite = finite && std::isfinite(cal.r2[i]);
+  if(!finite)
+    return SSD_OK;
+  out->status = SSD_GF_OK;
+  out->dof = dof;
+  out->cal = cal;
+  for(int i = 0; i < 3; i++)
+  {
+    out->rotation[i] = w[i];
+    out->translation[i] = tau[i];
+    out->centre[i] = E[i];
+  }
+  for(int k = 0; k < 6; k++)
+    out->eig[k] = lambda[k];
+  const double before = rr / N, after = before - gain;
+  out->rms_before = std::sqrt(before > 0.0 ? before : 0.0);
+  out->rms_after = std::sqrt(after > 0.0 ? after : 0.0);
+  return SSD_OK;
+}
+
+/* the buffers of the pass and the event behind their copy, on its first call */
+static int stair_pose_prepare(ssd_handle *h)
+{
+  if(h->dPose)
+    return SSD_OK;
+  const size_t recBytes = sizeof(ssd_stair_pose_moments) * static_cast<size_t>(h->F), indexBytes = sizeof(int) * static_cast<size_t>(h->F);
+  const size_t targetBytes = sizeof(PoseTarget) * static_cast<size_t>(SSD_MAX_STAIR_MAPS);
+  DeviceBuf<ssd_stair_pose_moments> d;
+  PinnedBuf<ssd_stair_pose_moments> hh;
+  DeviceBuf<PoseTarget> dt;
+  PinnedBuf<PoseTarget> ht;
+  DeviceBuf<int> di;
+  PinnedBuf<int> hi;
+  Event copied;
+  hipError_t e = d.alloc(recBytes, &h->bytes);
+  if(e == hipSuccess) e = hh.alloc(recBytes, &h->bytes);
+  if(e == hipSuccess) e = dt.alloc(targetBytes, &h->bytes);
+  if(e == hipSuccess) e = ht.alloc(targetBytes, &h->bytes);
+  if(e == hipSuccess) e = di.alloc(indexBytes, &h->bytes);
+  if(e == hipSuccess) e = hi.alloc(indexBytes, &h->bytes);
+  if(e == hipSuccess) e = copied.create(hipEventDisableTiming);
+  if(e != hipSuccess)
+    return hip_fail(e, "ssd_enqueue_stair_pose: its buffers: ");
+  h->dPose = std::move(d); h->hPose = std::move(hh);
+  h->dPoseTargets = std::move(dt); h->hPoseTargets = std::move(ht);
+  h->dPoseIndex = std::move(di); h->hPoseIndex = std::move(hi);
+  h->poseCopied = std::move(copied);
+  return SSD_OK;
+}
+
+/* arguments checked by the callers */
+static int enqueue_stair_pose_impl(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, hipStream_t s, int input,
+                                   const ssd_stair_pose_target *targets, int ntargets, const uint16_t *target_of_frame, const ssd_stair_pose_rule &rule)
+{
+  const bool depth = input == SSD_INPUT_DEPTH16;
+  const size_t unit = depth ? 2 : 4, frameBytes = host_frames(h, input, kForGroundFit).srcFrameBytes;
+  if(reinterpret_cast<size_t>(d_frames) % unit != 0 || frame_stride_bytes % unit != 0 || (nframes > 1 && frame_stride_bytes < frameBytes))
+    return fail(SSD_E_ARG, "ssd_enqueue_stair_pose: frames must be aligned to their element and the stride must hold a frame");
+  HIP_TRY(hipSetDevice(h->device));
+  int rc = stair_pose_prepare(h);
+  if(rc) return rc;
+  if(h->posePass.haveLast)
+    HIP_TRY(hipEventSynchronize(h->poseCopied));                  /* the pinned side of the previous call has gone over */
+  const bool timing = h->timing;
+  rc = pass_open(h->posePass, s, timing, "ssd_enqueue_stair_pose");   /* another stream: behind the previous call */
+  if(rc) return rc;
+  h->poseTargets.assign(targets, targets + ntargets);
+  h->poseIndex.resize(static_cast<size_t>(nframes));
+  for(int t = 0; t < ntargets; t++)
+    pose_target_fill(h->hPoseTargets[t], targets[t], depth, rule);
+  for(int i = 0; i < nframes; i++)
+    h->hPoseIndex[i] = h->poseIndex[i] = target_of_frame ? static_cast<int>(target_of_frame[i]) : 0;
+  const size_t recBytes = sizeof(ssd_stair_pose_moments) * static_cast<size_t>(nframes);
+  HIP_TRY(hipMemcpyAsync(h->dPoseTargets, h->hPoseTargets, sizeof(PoseTarget) * static_cast<size_t>(ntargets), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(h->dPoseIndex, h->hPoseIndex, sizeof(int) * static_cast<size_t>(nframes), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipEventRecord(h->poseCopied, s));
+  rc = pass_start(h->posePass, s, timing);
+  if(rc) return rc;
+  HIP_TRY(hipMemsetAsync(h->dPose, 0, recBytes, s));
+  const PoseRange R{ h->cfg.x_min, h->cfg.x_max, h->cfg.y_min, h->cfg.y_max };
+  launch_stair_pose(d_frames, frame_stride_bytes, h->P.W, h->P.H, nframes, depth, h->dPoseTargets, ntargets, h->dPoseIndex, R, h->dPose, s);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(h->hPose, h->dPose, recBytes, hipMemcpyDeviceToHost, s));
+  h->poseFrames = nframes;
+  return pass_close(h->posePass, s, timing);
+}
+
+int ssd_enqueue_stair_pose(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream, int input,
+                           const ssd_stair_pose_target *targets, int ntargets, const uint16_t *target_of_frame, const ssd_stair_pose_rule *rule)
+{
+  const std::string me("ssd_enqueue_stair_pose");
+  if(!h || !d_frames)
+    return fail(SSD_E_ARG, me + ": null argument");
+  if(nframes < 1 || nframes > h->F)
+    return fail(SSD_E_ARG, me + ": nframes must be 1..max_frames_per_batch");
+  if(input != SSD_INPUT_VERTICES && input != SSD_INPUT_DEPTH16)
+    return fail(SSD_E_ARG, me + ": input must be SSD_INPUT_VERTICES or SSD_INPUT_DEPTH16");
+  int rc = check_pose_rule(me, rule);
+  if(!rc) rc = check_pose_targets(me, targets, ntargets, target_of_frame, nframes, input);
+  if(rc) return rc;
+  return enqueue_stair_pose_impl(h, d_frames, frame_stride_bytes, nframes, static_cast<hipStream_t>(stream), input, targets, ntargets, target_of_frame, *rule);
+}
+
+int ssd_fetch_stair_pose_moments(ssd_handle *h, ssd_stair_pose_moments *out, int nframes, void *)
+{
+  if(!h || !out)
+    return fail(SSD_E_ARG, "ssd_fetch_stair_pose_moments: null argument");
+  if(!h->posePass.haveLast || nframes < 1 || nframes > h->poseFrames)
+    return fail(SSD_E_ARG, "ssd_fetch_stair_pose_moments: nframes must be 1..the frames of the last ssd_enqueue_stair_pose");
+  const int wait = pass_wait(h, &ssd_handle::posePass, "ssd_fetch_stair_pose_moments", "");
+  if(wait) return wait;
+  std::memcpy(out, h->hPose, sizeof(ssd_stair_pose_moments) * static_cast<size_t>(nframes));
+  return SSD_OK;
+}
+
+/* frames' records onto their targets' folds, in frame order (index: an int per frame; anything not below ntargets names none) */
+static int pose_fold_frames(const char *who, const ssd_stair_pose_moments *records, const int *index, int nframes, std::vector<ssd_stair_pose_moments> &folds)
+{
+  for(int i = 0; i < nframes; i++)
+  {
+    if(index[i] < 0 || index[i] >= static_cast<int>(folds.size()))
+      continue;
+    if(!pose_fold(records[i], folds[static_cast<size_t>(index[i])]))
+      return fail(SSD_E_CAP, std::string(who) + ": the fold of target " + std::to_string(index[i]) + " would leave int64 at frame " + std::to_string(i));
+  }
+  return SSD_OK;
+}
+
+int ssd_fetch_stair_pose(ssd_handle *h, ssd_stair_pose *out, int min_points, double observable, void *)
+{
+  if(!h || !out)
+    return fail(SSD_E_ARG, "ssd_fetch_stair_pose: null argument");
+  if(!h->posePass.haveLast)
+    return fail(SSD_E_ARG, "ssd_fetch_stair_pose: no ssd_enqueue_stair_pose to wait for");
+  const int wait = pass_wait(h, &ssd_handle::posePass, "ssd_fetch_stair_pose", "");
+  if(wait) return wait;
+  std::vector<ssd_stair_pose_moments> folds(h->poseTargets.size());
+  std::memset(folds.data(), 0, sizeof(ssd_stair_pose_moments) * folds.size());
+  int rc = pose_fold_frames("ssd_fetch_stair_pose", h->hPose, h->poseIndex.data(), h->poseFrames, folds);
+  for(size_t t = 0; t < folds.size() && !rc; t++)
+    rc = ssd_stair_pose_solve(&folds[t], &h->poseTargets[t], min_points, observable, out + t);
+  return rc;
+}
+
+int ssd_get_stair_pose_time(ssd_handle *h, float *ms)
+{
+  return pass_time(h, &ssd_handle::posePass, "ssd_get_stair_pose_time", "ssd_enqueue_stair_pose", ms);
+}
+
+int ssd_process_host_stair_pose(ssd_handle *h, const void *frames, int nframes, int input, const ssd_stair_pose_target *targets, int ntargets,
+                                const uint16_t *target_of_frame, const ssd_stair_pose_rule *rule, int min_points, double observable,
+                                ssd_stair_pose_moments *moments, ssd_stair_pose *out)
+{
+  const std::string me("ssd_process_host_stair_pose");
+  int rc = check_host_batch(h, "ssd_process_host_stair_pose", h && frames && out, nframes, input, kOwnPriors);
+  if(!rc) rc = check_pose_rule(me, rule);
+  if(!rc) rc = check_pose_targets(me, targets, ntargets, target_of_frame, nframes, input);
+  if(!rc && (!(observable >= 0.0) || !(observable <= 1.0)))
+    rc = fail(SSD_E_ARG, me + ": observable must lie in [0, 1]");
+  if(rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  SliceFeed feed{ h, host_frames(h, input, kForGroundFit), frames, nframes };
+  rc = feed.prepare();
+  if(rc) return rc;
+  std::vector<ssd_stair_pose_moments> folds(static_cast<size_t>(ntargets)), own;
+  std::memset(folds.data(), 0, sizeof(ssd_stair_pose_moments) * folds.size());
+  if(!moments)
+    own.resize(static_cast<size_t>(feed.slice));
+  /* slice c's records, behind its kernel: to the caller's array or the call's own, and onto the folds - frame order, slice by slice */
+  auto collect = [&](int c)
+  {
+    const int at = feed.first(c), n = feed.count(c);
+    ssd_stair_pose_moments *dst = moments ? moments + at : own.data();
+    const int got = ssd_fetch_stair_pose_moments(h, dst, n, nullptr);
+    return got ? got : pose_fold_frames("ssd_process_host_stair_pose", dst, h->poseIndex.data(), n, folds);
+  };
+  const int last = feed.slices() - 1;
+  for(int c = 0; c <= last; c++)
+  {
+    const void *buf;
+    int at, n;
+    rc = feed.stage(c);
+    if(rc) return rc;
+    /* the records are one set: the slice before is collected (its kernel ran beside this slice's copy) before this one's kernel goes out */
+    if(c >= 1)
+    {
+      rc = collect(c - 1);
+      if(rc) return rc;
+    }
+    rc = feed.ready(c, buf, at, n);
+    if(rc) return rc;
+    rc = enqueue_stair_pose_impl(h, buf, feed.f.devFrameBytes, n, h->ingestCompute, input, targets, ntargets, target_of_frame ? target_of_frame + at : nullptr, *rule);
+    if(rc) return rc;
+    rc = feed.consumed(c, h->ingestCompute);
+    if(rc) return rc;
+  }
+  rc = collect(last);
+  for(int t = 0; t < ntargets && !rc; t++)
+    rc = ssd_stair_pose_solve(&folds[static_cast<size_t>(t)], targets + t, min_points, observable, out + t);
+  return rc;
 }
 
 /* pinned host memory for frames (DMA without a staging copy) */

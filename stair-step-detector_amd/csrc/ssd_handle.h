@@ -12,6 +12,7 @@
 #include <vector>
 
 namespace ssd { struct GroundPrior; }          /* ssd_ground.h */
+namespace ssd { struct PoseTarget; }           /* ssd_pose.h */
 
 /* Launch-geometry constants of a handle.  The product uses the compiled defaults below (each one measured: ssd_capi.hip,
  * choose_chunk / enqueue_impl).  Only a tools build (make EXTRA=-DSSD_TUNING OUT=../lib_tuning, tools/exp*.sh) reads
@@ -231,6 +232,20 @@ struct ssd_handle
   /* ssd_process_host_stair_map: the records its slices accumulate into (SSD_MAX_STAIR_MAPS of them), made on its first call; staging
    * like gridStage, not counted as workspace */
   ssd::DeviceBuf<ssd_frame_tread_grid> mapStage;
+  /* the stair pose pass (ssd_enqueue_stair_pose & co.): a record per frame (F, on the device and pinned), the
+   * call's targets as the kernel reads them (SSD_MAX_STAIR_MAPS) and its index frame -> target (F ints), each pinned and on the device,
+   * made on the first call and counted as workspace.  One set, used in call order like the ground fit's; nothing of the lanes is touched */
+  ssd::DeviceBuf<ssd_stair_pose_moments> dPose;
+  ssd::PinnedBuf<ssd_stair_pose_moments> hPose;  /* pinned: a call's last step copies its records here */
+  ssd::DeviceBuf<ssd::PoseTarget> dPoseTargets;
+  ssd::PinnedBuf<ssd::PoseTarget> hPoseTargets;
+  ssd::DeviceBuf<int> dPoseIndex;
+  ssd::PinnedBuf<int> hPoseIndex;
+  ssd::Event poseCopied;                    /* behind the copies pinned -> device: the pinned side may be written again */
+  ssd_ordered_pass posePass;
+  int poseFrames = 0;                       /* frames of the last call */
+  std::vector<ssd_stair_pose_target> poseTargets;   /* its targets and its index: what ssd_fetch_stair_pose folds and solves against */
+  std::vector<int> poseIndex;
 };
 
 /* The single pass's planes - dPlaneImg and dFallback of every workspace and the pinned hFallback, zeroed - for ALL workspaces of the

@@ -159,3 +159,6 @@ void launch_ground_moments(const void *frames, size_t strideBytes, int W, int H,
 }
 
 } // namespace ssd
+
+/* k_stair_pose stands on this kernel's skeleton and shares its translation unit */
+#include "ssd_kernels_pose.hip"
