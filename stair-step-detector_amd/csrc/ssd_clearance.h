@@ -1,6 +1,6 @@
 /*
  * ssd_clearance.h — the tread clearance rule (include/ssd_hip.h), stated once for the device (k_clearance and
- * k_clearance_cams, ssd_kernels_clearance.hip) and the host (ssd_clearance_host, ssd_capi.hip), and the kernels' launcher.
+ * k_clearance_cams, ssd_kernels_clearance.hip) and the host (ssd_clearance_host, ssd_host.cpp), and the kernels' launcher.
  * The rule speaks of public data only: a frame's ssd_frame_result, the calibration, the point.  Both sides are compiled without FMA
  * contraction and every operation is +, -, * or a comparison of doubles in one order; the rule decides only WHICH points are summed, and
  * everything summed is an integer by the fixed-point rule of ssd_moments.h: they agree bit for bit.

@@ -1,6 +1,6 @@
 /*
  * ssd_fold.h — the step of the camera fold (DESIGN.md sections 7e and 7j): one frame's record onto its camera's record.  Stated once
- * for the host (ssd_camera_drift_fold: ssd_capi.hip) and the device (k_camera_fold: ssd_kernels_fold.hip).  Integers only, so the two
+ * for the host (ssd_camera_drift_fold: ssd_host.cpp) and the device (k_camera_fold: ssd_kernels_fold.hip).  Integers only, so the two
  * sides agree by construction; what has to be kept is the order - frames in index order - and the rule "whole or not at all".
  */
 #ifndef SSD_FOLD_H_

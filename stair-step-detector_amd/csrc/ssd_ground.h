@@ -1,6 +1,6 @@
 /*
  * ssd_ground.h — the ground fit's floor-point rule (include/ssd_hip.h), stated once for the device
- * (k_ground_moments, ssd_kernels_ground.hip) and the host (ssd_ground_moments_host, ssd_capi.hip), and the kernel's launcher.
+ * (k_ground_moments, ssd_kernels_ground.hip) and the host (ssd_ground_moments_host, ssd_host.cpp), and the kernel's launcher.
  * Both sides are compiled without FMA contraction, and everything summed is an integer: they agree bit for bit.
  */
 #ifndef SSD_GROUND_H_

@@ -1,6 +1,6 @@
 /*
  * ssd_pose.h — the stair pose's rule (include/ssd_hip.h), stated once for the device (k_stair_pose,
- * ssd_kernels_pose.hip) and the host (ssd_stair_pose_host, ssd_capi.hip), the fold's step, and the kernel's launcher.  Built on
+ * ssd_kernels_pose.hip) and the host (ssd_stair_pose_host, ssd_host.cpp), the fold's step, and the kernel's launcher.  Built on
  * ssd_ground.h (the prior as the kernel reads it, the depth maps), ssd_clearance.h (the external world of a point, a tread's shrunk
  * quadrilateral) and ssd_moments.h (the fixed-point sums), which stay as they are.  Both sides are compiled without FMA contraction and
  * every operation is +, -, * or a comparison of doubles in one order; the rule decides only WHICH class a point is summed into, and

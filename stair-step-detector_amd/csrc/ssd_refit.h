@@ -1,6 +1,6 @@
 /*
  * ssd_refit.h — the trimmed surface refit's gate rule (include/ssd_hip.h), stated once for the device
- * (k_surface_refit and k_surface_refit_cams, ssd_kernels_refit.hip) and the host (ssd_surface_refit_moments_host, ssd_capi.hip), and the
+ * (k_surface_refit and k_surface_refit_cams, ssd_kernels_refit.hip) and the host (ssd_surface_refit_moments_host, ssd_host.cpp), and the
  * kernels' launchers.
  * Both sides are compiled without FMA contraction; the gate decides only WHICH points are summed, and everything summed is an
  * integer by the fixed-point rule of ssd_moments.h: they agree bit for bit.

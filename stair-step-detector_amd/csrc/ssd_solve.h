@@ -3,7 +3,7 @@
  * 128-bit integers -> its eigenvalues and eigenvectors (cyclic Jacobi) -> the plane of lambda_min, and the trimmed refit's gate rule
  * on top of it; and camera_to_world_from_plane, the pose a floor's plane gives (section 7j).  Stated once for the host
  * (ssd_ground_fit_solve, ssd_surface_fit_solve, ssd_riser_fit_solve, ssd_surface_gates_from_moments, the calibrations from a plane
- * and from points: ssd_capi.hip) and the device (k_surface_gates: ssd_kernels_solve.hip, k_camera_ground_gates: ssd_kernels_fold.hip).
+ * and from points: ssd_host.cpp) and the device (k_surface_gates: ssd_kernels_solve.hip, k_camera_ground_gates: ssd_kernels_fold.hip).
  * Both sides are compiled without FMA contraction; every operation is +, -, *, /, sqrt or a comparison of doubles, each correctly
  * rounded on both sides, in one order: they agree bit for bit (tests/golden/solve_goldens.json holds the host to the text this was
  * moved from, tests/test_gpu_surface_gates.py the device to the host).  Nothing transcendental is here: atan2 and asin stay in the

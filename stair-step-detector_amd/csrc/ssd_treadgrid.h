@@ -1,6 +1,6 @@
 /*
  * ssd_treadgrid.h — the tread grid rule (include/ssd_hip.h), stated once for the device (k_tread_grid and
- * k_tread_grid_cams, ssd_kernels_treadgrid.hip) and the host (ssd_tread_grid_host, ssd_tread_grid_solve: ssd_capi.hip), and the kernels'
+ * k_tread_grid_cams, ssd_kernels_treadgrid.hip) and the host (ssd_tread_grid_host, ssd_tread_grid_solve: ssd_host.cpp), and the kernels'
  * launcher.  Built on ssd_clearance.h, whose functions decide which points stand on which surface and stay as they are; this text adds
  * the tread points of a surface and the cell of a point in the surface's own frame.  Both sides are compiled without FMA contraction;
  * sqrt and / are correctly rounded on both (ssd_math.h relies on the same); everything counted or maximised is an integer: they agree
