@@ -25,7 +25,7 @@ TWO_PASSES, SINGLE_PASS, NO_PLANES = (0, 0), (1, 0), (1, 2)     # Detector.singl
 class Resident:
     """frames resident on the device behind one detector; every pass into freshly poisoned buffers"""
 
-    def __init__(self, ssd, device, cfg, trans, frames, depth=False, intr=None, mode=None, cameras=None, order=None):
+    def __init__(self, ssd, device, cfg, trans, frames, depth=False, intr=None, mode=None, cameras=None, order=None, pad=None):
         self.ssd, self.cfg, self.depth, self.intr, self.order = ssd, cfg, depth, intr, order
         self.frames, self.n, self.wh = frames, len(frames), cfg.width * cfg.height
         self.cal = trans.constants
@@ -39,7 +39,7 @@ class Resident:
         if mode is not None:
             self.det.single_pass(*mode)
         fb = frames[0].nbytes
-        self.stride = fb + (8 if depth else 4)
+        self.stride = fb + ((8 if depth else 4) if pad is None else pad)       # pad: for a frame size that + 8 brings to a multiple of 16
         assert self.stride % 16 != 0
         self.src = ssd.DeviceBuffer(self.stride * self.n, device)
         self.bufs.append(self.src)
@@ -89,12 +89,14 @@ class Resident:
     def cal_of(self, i):
         return self.cal if self.order is None else self.cameras_cal[self.order[i]]
 
-    def check(self, rule, recs, masks, res=None, frames=None):
-        """records and masks byte for byte the host's on the handle's own results; the host sums over the device's mask = the records"""
+    def check(self, rule, recs, masks, res=None, frames=None, ground=None):
+        """records and masks byte for byte the host's on the handle's own results; the host sums over the device's mask = the records.
+        ground: per frame whether its surface 0 is the ground (None: every live frame's is, as in this file's scenes)"""
         ssd, res, frames = self.ssd, res or self.res, frames or self.frames
         for i, r in enumerate(recs):
             live = res[i].n_steps > 0 and not (res[i].status & ssd.ST_THROW)
-            want, wmask = ssd.clearance_host(self.cfg, self.cal_of(i), frames[i], res[i], 1 if live else 0, cm.rule_of(ssd, rule), intr=self.intr_of(i))
+            flag = (1 if live else 0) if ground is None else ground[i]
+            want, wmask = ssd.clearance_host(self.cfg, self.cal_of(i), frames[i], res[i], flag, cm.rule_of(ssd, rule), intr=self.intr_of(i))
             assert bytes(r) == bytes(want), (i, cm.sums_of_record(r, ssd.MAX_STEPS), cm.sums_of_record(want, ssd.MAX_STEPS))
             if masks is not None:
                 assert np.array_equal(masks[i], wmask.reshape(-1)), i

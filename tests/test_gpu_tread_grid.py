@@ -40,12 +40,13 @@ class GridResident(Resident):
         assert np.all(raw[self.grec * n:] == POISON), "a record past nframes was written"
         return list((self.ssd.FrameTreadGrid * n).from_buffer_copy(raw[:self.grec * n].tobytes()))
 
-    def check_grid(self, rule, recs, res=None, frames=None):
-        """records byte for byte the host's on the handle's own results"""
+    def check_grid(self, rule, recs, res=None, frames=None, ground=None):
+        """records byte for byte the host's on the handle's own results; ground: as Resident.check's"""
         ssd, res, frames = self.ssd, res or self.res, frames or self.frames
         for i, r in enumerate(recs):
             live = res[i].n_steps > 0 and not (res[i].status & ssd.ST_THROW)
-            want = ssd.tread_grid_host(self.cfg, self.cal_of(i), frames[i], res[i], 1 if live else 0, tg.rule_of(ssd, rule), intr=self.intr_of(i))
+            flag = (1 if live else 0) if ground is None else ground[i]
+            want = ssd.tread_grid_host(self.cfg, self.cal_of(i), frames[i], res[i], flag, tg.rule_of(ssd, rule), intr=self.intr_of(i))
             if bytes(r) != bytes(want):
                 bad = [k for k in range(ssd.MAX_STEPS) if not tg.same_grid(tg.grid_of_record(r, k), tg.grid_of_record(want, k))]
                 raise AssertionError((i, (r.n_surfaces, r.ground), (want.n_surfaces, want.ground), bad))
