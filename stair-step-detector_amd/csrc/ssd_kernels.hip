@@ -24,912 +24,19 @@
  *   K3 k_outline      reads a covered plateau's plane(s) in place of its step image
  * Nothing the predictor says can change a result ("The single pass").
  */
-/* This file is compiled twice.  By itself it is the one-calibration path: every kernel takes the handle's constants by value.
- * ssd_kernels_cams.hip defines SSD_CAMERAS_TU and includes it for the device code alone: the kernels whose body stands in the
- * entry point itself become device functions there (SSD_ENTRY gives them their second name, SSD_BYVAL turns the by-value
- * constants into references), and the cameras entry points call them with the frame's camera record.
- * Without SSD_CAMERAS_TU both macros spell exactly what stood here before, so this translation unit's code does not change.
- * That rule - a kernel's code object stays byte for byte what it was - holds for the chain K0 - K5, which bench.py measures.  The
- * extension kernels K6 - K8 (labels, surface moments, the refit, the three riser passes) are written from shared pieces and held to
- * their results, their resources and their time instead: DESIGN.md section 7l. */
-#ifndef SSD_CAMERAS_TU
-#define SSD_ENTRY(bounds, kernel, block) __global__ bounds void kernel
-#define SSD_BYVAL(T) T
-#else
-#define SSD_ENTRY(bounds, kernel, block) __device__ __forceinline__ void block
-#define SSD_BYVAL(T) const T &
-#undef SSD_PHASE_TIMING       /* the tools' clocks and counters are this file's own translation unit's */
-#undef SSD_COUNT
-#endif
-#include "ssd_device.h"
-#include "ssd_moments.h"
-#include "ssd_math.h"
-#include "ssd_quadtest.h"
-#include "ssd_closing.h"
-#include "ssd_bestline.h"
-#include "ssd_sort.h"
-#include "ssd_predict.h"    /* k_predict's sample rule (predict_sample_run), shared with the tests */
-#include "ssd_refit.h"      /* the refit's gate rule (refit_keeps), shared with the host */
+/* What the stages share stands in headers that compile alone - ssd_k_entry.h (SSD_ENTRY / SSD_BYVAL and the tools builds' macros),
+ * ssd_k_point.h, ssd_k_cells.h, ssd_k_windows.h - and the launch rules in ssd_launch_rules.h; the stages' bodies, K1 to K6, stand here
+ * (DESIGN.md section 3b).  So this file is still compiled more than once: by itself it is the one-calibration path, and
+ * ssd_kernels_cams.hip and ssd_kernels_refit.hip define SSD_CAMERAS_TU and include it for the device code alone (ssd_k_entry.h says
+ * what the macro does to the kernels whose body stands in the entry point).  The entry points that only call a stage's *_block, and
+ * the launchers, stand in one stretch at the end of the file: what such an includer leaves out, and all that it leaves out. */
+#include "ssd_k_entry.h"
+#include "ssd_k_point.h"
+#include "ssd_k_cells.h"
+#include "ssd_k_windows.h"
 
 namespace ssd
 {
-
-#include "ssd_phase.h"      /* tools builds: clocks at the marks below; product build: empty macros */
-
-/* Bounds-checked tools build (-DSSD_CHECKED, tools/checked.sh; GPU sanitizers are not available on this pool): the index of every
- * store or atomic whose address comes from a point, a pixel, a window or a list is compared with the extent of what it writes
- * into FIRST; a violation is reported from the device (one line, "SSD_CHECK site ...") and the access is dropped.  In the
- * product build the macro is the constant `true`. */
-#ifdef SSD_CHECKED
-__device__ __noinline__ void ssd_chk_report(int site, unsigned long long idx, unsigned long long limit)
-{
-  printf("SSD_CHECK site %d index %llu limit %llu block (%u, %u) thread %u\n", site, idx, limit, blockIdx.x, blockIdx.y, threadIdx.x);
-}
-__device__ __forceinline__ bool ssd_chk(int site, unsigned long long idx, unsigned long long limit)
-{
-  if(idx < limit)
-    return true;
-  ssd_chk_report(site, idx, limit);
-  return false;
-}
-#define SSD_CHK(site, idx, limit) ssd_chk((site), static_cast<unsigned long long>(idx), static_cast<unsigned long long>(limit))
-#else
-#define SSD_CHK(site, idx, limit) (true)
-#endif
-
-/* Tools build (-DSSD_COUNT, tools/k1count.py): what K1's windows do - tiles with candidate points, window moves, words flushed,
- * pixels that missed the window.  In the product build the macros are empty. */
-#ifdef SSD_COUNT
-__device__ unsigned long long ssd_k1_counters[8];
-#define SSD_CNT(i, n) do { if(threadIdx.x % 64 == 0) atomicAdd(&ssd_k1_counters[i], static_cast<unsigned long long>(n)); } while(0)
-#define SSD_CNT_LANES(i, pred) do { const unsigned long long cnt_m = __ballot(pred); if(threadIdx.x % 64 == 0 && cnt_m) atomicAdd(&ssd_k1_counters[i], static_cast<unsigned long long>(__popcll(cnt_m))); } while(0)
-#else
-#define SSD_CNT(i, n) do { } while(0)
-#define SSD_CNT_LANES(i, pred) do { } while(0)
-#endif
-
-/* ========================================================================= */
-/* shared per-point arithmetic                                                */
-
-struct __attribute__((packed, aligned(4))) F3 { float x, y, z; };
-
-/* CameraToWorld (transformation.h:59-64, 79-87): a*x + b, float promoted to double, row sums left to right, then the
- * translation; followed by the non-zero test (pointcloud.cpp:143-146) and the six strict range compares of
- * getPointsInRange (pointcloud.cpp:150-165).  Flat code: all three rows, then the seven tests combined without short
- * circuit.  Early exits only pay when all 64 lanes of a wave take them, which a camera image next to never offers; as nested
- * branches they cost the default values of everything the point contributes, re-materialised at every level (9 moves per
- * point in K1's ISA).  (The throughput of K1 / K2 on float3 input did not move with it — they sit on the memory roof
- * of the GPU's current clock state — but the instruction count did: what 16-bit depth input, VALU-bound, runs on.) */
-__device__ __forceinline__ bool world_point_flat(const PointParams &P, const F3 &v, double &wx, double &wy, double &wz)
-{
-  const double x = v.x, y = v.y, z = v.z;
-  wx = (P.a[0] * x + P.a[1] * y) + P.a[2] * z;
-  wy = (P.a[3] * x + P.a[4] * y) + P.a[5] * z;
-  wz = (P.a[6] * x + P.a[7] * y) + P.a[8] * z;
-  wx = wx + P.b[0];
-  wy = wy + P.b[1];
-  wz = wz + P.b[2];
-  return (v.z > 0.0f) & (wx > P.xMin) & (wx < P.xMax) & (wy > P.yMin) & (wy < P.yMax) & (wz > P.zMin) & (wz < P.zMax);
-}
-
-/* The same decisions taken height first, for the passes that drop most points on their height bin: the z row
- * and the z tests, then (only for points whose bin matters) the x and y rows and their tests.  The
- * conjunction of tests and every operation are those of world_point_flat. */
-__device__ __forceinline__ bool world_z(const PointParams &P, const F3 &v, double &wz)
-{
-  if(!(v.z > 0.0f))
-    return false;
-  wz = (P.a[6] * static_cast<double>(v.x) + P.a[7] * static_cast<double>(v.y)) + P.a[8] * static_cast<double>(v.z);
-  wz = wz + P.b[2];
-  return wz > P.zMin && wz < P.zMax;
-}
-/* world_z without the early exit, for flat code (wz is meaningless when false is returned) */
-__device__ __forceinline__ bool world_z_flat(const PointParams &P, const F3 &v, double &wz)
-{
-  wz = (P.a[6] * static_cast<double>(v.x) + P.a[7] * static_cast<double>(v.y)) + P.a[8] * static_cast<double>(v.z);
-  wz = wz + P.b[2];
-  return v.z > 0.0f && wz > P.zMin && wz < P.zMax;
-}
-__device__ __forceinline__ bool world_xy(const PointParams &P, const F3 &v, double &wx, double &wy)
-{
-  const double x = v.x, y = v.y, z = v.z;
-  wx = (P.a[0] * x + P.a[1] * y) + P.a[2] * z;
-  wy = (P.a[3] * x + P.a[4] * y) + P.a[5] * z;
-  wx = wx + P.b[0];
-  wy = wy + P.b[1];
-  return wx > P.xMin && wx < P.xMax && wy > P.yMin && wy < P.yMax;
-}
-
-/* calcHeights (pointcloud.cpp:175): truncating conversion, value is in [0, nBins) */
-__device__ __forceinline__ int height_bin(const PointParams &P, double wz)
-{
-  return static_cast<int>((wz - P.zMin) * P.recip);
-}
-
-/* ========================================================================= */
-/* K1: histogram                                                              */
-
-/* k_raster is built for 6 waves per SIMD: 75 VGPRs, no scratch spills (round 2: 7 waves, 72 VGPRs, 3 spills).  Measured in
- * round 3, same box, alternating runs, XGA batch: 8 / 7 / 6 / 5 / 4 waves 0.848 / 0.823 / 0.800 / 0.801 / 0.799 ms; FHD stress:
- * 7 / 6 / 5 within 1 % — the walk is bound by instruction issue, not by latency: residency beyond four waves buys nothing */
-/* k_inquad (round 6: every decision in single precision first, the doubles out of line): 5 waves per SIMD - 92 vector registers,
- * no spill of either kind in the XGA instantiation; 6 waves spill 3 vector registers and run a third slower (0.64 -> 0.84 ms), 4 waves
- * the same as 5 (profiles/r06_k4_edges.txt).  Until round 6: 8 waves at 48 scalar spills in the loop. */
-#ifndef SSD_K4_WAVES
-#define SSD_K4_WAVES 5
-#endif
-#ifndef SSD_K2_WAVES
-#define SSD_K2_WAVES 6
-#endif
-constexpr int kThreads = 256;
-constexpr int kPts = 4;                 /* points per thread per iteration: four CONSECUTIVE points (48 B) */
-constexpr int kTile = kThreads * kPts;  /* 1024 points per block iteration */
-#ifndef SSD_HIST_COPIES
-#define SSD_HIST_COPIES 32
-#endif
-constexpr int kHistCopies = SSD_HIST_COPIES;         /* LDS histogram privatised by lane & 31: bank = copy, no conflicts */
-
-/* Point sources of the streaming kernels */
-constexpr int kSrcF3 = 0;          /* float xyz, 12-byte loads (unaligned frames, or a point count not divisible by 4) */
-constexpr int kSrcF3Aligned = 1;   /* float xyz, 16-byte loads */
-constexpr int kSrcDepth16 = 2;     /* 16-bit depth image + intrinsics: deprojected on the fly */
-
-/* Four consecutive points of one lane.  kSrcF3Aligned: three 16-byte loads (lanes 48 B apart; the three
- * instructions of a wave together cover 3 KiB contiguously — measured 6.2-6.3 TB/s on MI355X, the same as
- * a plain float4 stream, tools/loadbench.hip).  kSrcF3 (frame base/stride not 16-byte aligned, or the
- * tail of a frame whose point count is not a multiple of 4): 12-byte loads.  kSrcDepth16: four 16-bit depth
- * values (one 8-byte load) turned into points exactly as librealsense's pointcloud block does in float:
- * d = raw * depth_units; point = (d * xmap[u], d * ymap[v], d); raw = 0 gives the invalid point (0,0,0). */
-/* kSrcDepth16: the lane's four depth pixels and the maps' values for them -> four points, in float as librealsense does
- * (d = raw * depth_units; point = (d * xmap[u], d * ymap[v], d); raw = 0 gives the invalid point (0,0,0)) */
-__device__ __forceinline__ void deproject4(const uint2 raw, const float4 xm, const float ym, const float units, F3 (&v)[kPts])
-{
-  const float d0 = static_cast<float>(raw.x & 0xffffu) * units, d1 = static_cast<float>(raw.x >> 16) * units;
-  const float d2 = static_cast<float>(raw.y & 0xffffu) * units, d3 = static_cast<float>(raw.y >> 16) * units;
-  v[0] = F3{ d0 * xm.x, d0 * ym, d0 };
-  v[1] = F3{ d1 * xm.y, d1 * ym, d1 };
-  v[2] = F3{ d2 * xm.z, d2 * ym, d2 };
-  v[3] = F3{ d3 * xm.w, d3 * ym, d3 };
-}
-/* image row of point index idx (DepthSrc::rowMagic) */
-__device__ __forceinline__ int depth_row(const DepthSrc &D, int idx)
-{
-  return D.rowMagic ? static_cast<int>(__umulhi(static_cast<unsigned int>(idx), D.rowMagic) >> 7) : idx / D.W;
-}
-
-template<int SRC>
-__device__ __forceinline__ void load_points(const float *__restrict__ base, int idx0, int end, F3 (&v)[kPts], const DepthSrc &D)
-{
-  if(SRC == kSrcDepth16)
-  {
-    /* width % 4 == 0 and idx0 % 4 == 0 (ssd_enqueue_depth checks the first, every caller provides the second): the four
-     * pixels share the image row, lie wholly inside or wholly outside the frame, and their x-map entries are one aligned
-     * 16-byte load (round 3: four dependent 4-byte loads and a division per call) */
-    const unsigned short *depth = reinterpret_cast<const unsigned short *>(base);
-    const bool inside = idx0 + kPts <= end;
-    const uint2 raw = inside ? *reinterpret_cast<const uint2 *>(depth + idx0) : make_uint2(0u, 0u);
-    const int row = depth_row(D, idx0), col = idx0 - row * D.W;
-    const float ym = D.ymap[min(row, D.H - 1)];               /* lanes past the end of the frame (raw = 0) stay inside the map */
-    const float4 xm = *reinterpret_cast<const float4 *>(D.xmap + col);
-    deproject4(raw, xm, ym, D.depthUnits, v);
-    return;
-  }
-  if(SRC == kSrcF3Aligned && idx0 + kPts <= end)
-  {
-    const float4 *q = reinterpret_cast<const float4 *>(base + 3 * static_cast<size_t>(idx0));
-    const float4 a = q[0], b = q[1], c = q[2];
-    v[0] = F3{ a.x, a.y, a.z };
-    v[1] = F3{ a.w, b.x, b.y };
-    v[2] = F3{ b.z, b.w, c.x };
-    v[3] = F3{ c.y, c.z, c.w };
-    return;
-  }
-#pragma unroll
-  for(int j = 0; j < kPts; j++)
-  {
-    const int idx = idx0 + j;
-    v[j] = F3{ 0.0f, 0.0f, 0.0f };
-    if(idx < end)
-      v[j] = *reinterpret_cast<const F3 *>(base + 3 * static_cast<size_t>(idx));
-  }
-}
-
-/* The lane's four points of a tile that lies wholly inside the frame: no bounds, no branches, nothing between the loads and their
- * first use.  Round 5: load_points() has two paths (this one, and point by point at the frame's end); where they join the compiler
- * puts copies of the loaded registers INTO the fast path - an s_waitcnt vmcnt right behind the loads - and the "prefetch" of the
- * next tile waited for its data before the current tile was touched (found in the ISA of the single pass's K1, which a build fed
- * from the Infinity Cache had shown to be waiting for memory: 1.69 ms against 2.12 from HBM; tools/mkvariant.sh's SED_EXPR). */
-template<int SRC>
-__device__ __forceinline__ void load_points_full(const float *__restrict__ base, int idx0, F3 (&v)[kPts])
-{
-  if(SRC == kSrcDepth16)
-    return;                                     /* vertex input only: the depth stream has a loop of its own */
-  if(SRC == kSrcF3Aligned)
-  {
-    const float4 *q = reinterpret_cast<const float4 *>(base + 3 * static_cast<size_t>(idx0));
-#ifdef SSD_NT_LOADS           /* tools: the frames read as a stream that is not to be kept in the caches */
-    typedef float f4v __attribute__((ext_vector_type(4)));
-    const f4v *qv = reinterpret_cast<const f4v *>(q);
-    const f4v av = __builtin_nontemporal_load(qv), bv = __builtin_nontemporal_load(qv + 1), cv = __builtin_nontemporal_load(qv + 2);
-    const float4 a = make_float4(av.x, av.y, av.z, av.w), b = make_float4(bv.x, bv.y, bv.z, bv.w), c = make_float4(cv.x, cv.y, cv.z, cv.w);
-#else
-    const float4 a = q[0], b = q[1], c = q[2];
-#endif
-    v[0] = F3{ a.x, a.y, a.z };
-    v[1] = F3{ a.w, b.x, b.y };
-    v[2] = F3{ b.z, b.w, c.x };
-    v[3] = F3{ c.y, c.z, c.w };
-    return;
-  }
-#pragma unroll
-  for(int j = 0; j < kPts; j++)
-    v[j] = *reinterpret_cast<const F3 *>(base + 3 * static_cast<size_t>(idx0 + j));
-}
-
-/* The same without knowing that the tile is whole: the loads go to addresses clamped into [0, end) - no bounds, no branches, and so
- * nothing that uses the data behind the loads - and zero_beyond(), called where the points are first used, blanks the points at or
- * beyond `end` (z = 0: "no measurement", dropped by every consumer first).  end >= 4; vertex input only.  kSrcF3Aligned: idx0 and end
- * are multiples of 4 (points_aligned()), so a lane's four points lie wholly inside or wholly beyond. */
-template<int SRC>
-__device__ __forceinline__ void load_points_clamped(const float *__restrict__ base, int idx0, int end, F3 (&v)[kPts])
-{
-  if(SRC == kSrcDepth16)
-    return;
-  if(SRC == kSrcF3Aligned)
-  {
-    load_points_full<SRC>(base, min(idx0, end - kPts), v);
-    return;
-  }
-#pragma unroll
-  for(int j = 0; j < kPts; j++)
-    v[j] = *reinterpret_cast<const F3 *>(base + 3 * static_cast<size_t>(min(idx0 + j, end - 1)));
-}
-__device__ __forceinline__ void zero_beyond(F3 (&v)[kPts], int idx0, int end)
-{
-#pragma unroll
-  for(int j = 0; j < kPts; j++)
-    if(idx0 + j >= end)
-      v[j] = F3{ 0.0f, 0.0f, 0.0f };
-}
-
-/* "The loaded registers are first looked at HERE": an empty asm that takes and returns the twelve registers of a lane's four points.
- * Placed behind the tile the loads were issued in front of: without it the compiler builds the (x, y) register pairs of the next
- * tile's points (v_pk_fma_f32 and the fp64 conversions want them aligned) right behind the loads - and waits for the data there. */
-__device__ __forceinline__ void first_use(F3 (&v)[kPts])
-{
-  asm volatile("" : "+v"(v[0].x), "+v"(v[0].y), "+v"(v[0].z), "+v"(v[1].x), "+v"(v[1].y), "+v"(v[1].z),
-                    "+v"(v[2].x), "+v"(v[2].y), "+v"(v[2].z), "+v"(v[3].x), "+v"(v[3].y), "+v"(v[3].z));
-}
-
-/* The streaming kernels (K1, K2, K4) share one loop shape: a block owns a contiguous chunk of a frame and
- * walks it in tiles of 1024 points; the loads of the next tile are issued before the current tile is
- * processed (register double buffer), so that HBM requests stay in flight while the SIMDs do the fp64 work. */
-/* body(v) is called once per tile with the lane's four points.  Two register buffers used alternately (the loop is
- * unrolled by two tiles) instead of one copied into the other after every tile: 12 moves fewer per tile. */
-#define SSD_STREAM_LOOP(body)                                                                       \
-  {                                                                                                 \
-    F3 va[kPts], vb[kPts];                                                                          \
-    const int fullEnd = begin + (end - begin) / kTile * kTile;  /* tiles wholly inside the chunk */ \
-    if(begin < fullEnd)                                                                             \
-      load_points_full<SRC>(base, begin + kPts * tid, va);                                          \
-    for(int i0 = begin; i0 < fullEnd; i0 += 2 * kTile)                                              \
-    {                                                                                               \
-      const bool more1 = i0 + kTile < fullEnd;                                                      \
-      if(more1)                                                                                     \
-        load_points_full<SRC>(base, i0 + kTile + kPts * tid, vb);                                   \
-      body(va);                                                                                     \
-      if(!more1)                                                                                    \
-        break;                                                                                      \
-      first_use(vb);                                                                                \
-      const bool more2 = i0 + 2 * kTile < fullEnd;                                                  \
-      if(more2)                                                                                     \
-        load_points_full<SRC>(base, i0 + 2 * kTile + kPts * tid, va);                               \
-      body(vb);                                                                                     \
-      if(more2)                                                                                     \
-        first_use(va);                                                                              \
-    }                                                                                               \
-    if(fullEnd < end)                                                                               \
-    {                                                                                               \
-      load_points<SRC>(base, fullEnd + kPts * tid, end, va, D);       /* the frame's last, partial tile */ \
-      body(va);                                                                                     \
-    }                                                                                               \
-  }
-
-/* K2 and K4 run after frame-wide decisions (plateau table, outlines) and need only the points of a few
- * height bins.  Camera rows sweep one plateau at a time, so whole runs of consecutive points are irrelevant
- * to them.  K1 therefore leaves one 32-bit mask per CELL — 64 consecutive points = the 4 points of each of
- * the 16 lanes of one DPP row — saying which groups of 4 height bins occur in it (4 B per 768 B of input:
- * no measurable traffic, unlike a byte per point which costs K1 a third of its bandwidth,
- * tools/storebench.hip).  The later passes gather the cells that hold a bin they care about into a compact
- * list per block and walk only those (cell_list_build / SSD_CELL_LOOP below): nothing else is loaded, and
- * every wave iteration works on four wanted cells instead of on 256 consecutive points of which half are
- * somebody else's (wave-tile gating: 52 % of the tiles at 52 % lane use in K2; cells: 34 % at 79 %; tools/cell_analysis.py). */
-constexpr int kBinsPerGroup = 4;      /* 128 bins -> 32 groups: one 32-bit mask per cell */
-constexpr int kWavesPerBlock = kThreads / 64;
-constexpr int kCell = 64;                         /* points per cell */
-constexpr int kCellsPerTile = kTile / kCell;      /* 16 */
-/* a block's chunk is at most this many tiles (choose_chunk; ssd_launch.h holds the same numbers for the host): K1 keeps the
- * chunk's cell masks in LDS, K2 / K4 / K6 the list of its wanted cells.  K2 gets tall chunks: its waves walk down cell
- * columns and pay a window flush at every column change (measured, XGA batch: 2.5 ms with 8-row chunks, 1.5 with 16,
- * 1.0 with 32) */
-#ifndef SSD_MAX_TILES
-#define SSD_MAX_TILES 32
-#endif
-constexpr int kMaxTilesPerBlock = SSD_MAX_TILES;
-constexpr int kMaxCellsPerBlock = kMaxTilesPerBlock * kCellsPerTile;
-constexpr int kMaxTilesPerBlockRaster = 128;
-constexpr int kMaxCellsPerBlockRaster = kMaxTilesPerBlockRaster * kCellsPerTile;
-constexpr int kMaxTilesPerBlockInquad = 128;
-constexpr int kMaxCellsPerBlockInquad = kMaxTilesPerBlockInquad * kCellsPerTile;
-
-/* OR over the 16 lanes of a DPP row (row_ror 8, 4, 2, 1): every lane of the row gets the row's result */
-__device__ __forceinline__ unsigned int row_or_u32(unsigned int v)
-{
-  v |= static_cast<unsigned int>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x128, 0xf, 0xf, false));
-  v |= static_cast<unsigned int>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x124, 0xf, 0xf, false));
-  v |= static_cast<unsigned int>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x122, 0xf, 0xf, false));
-  v |= static_cast<unsigned int>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x121, 0xf, 0xf, false));
-  return v;
-}
-
-/* K1 also leaves, per cell, the bounding box of its in-range points in world x / y on a 256 x 256 grid over the measuring
- * range (one byte per bound: x0, x1, y0, y1; a cell with no in-range point has an empty mask and a meaningless box).
- * k_inquad decides from it, without loading the cell, that all its points lie outside the ground quadrilateral, or all
- * inside a tread's (its thresholds on this grid carry a margin far above any rounding: InquadLds::liveBox).
- *
- * Round 4: the extremes are tracked per point on the HIGH dwords of d = w - min (doubles, d > 0 for a point in range): for
- * positive doubles the high dword (exponent + 20 mantissa bits) orders like an unsigned integer, so a point costs two
- * subtractions and four 32-bit min / max (round 3: two subtractions, two multiplications, two conversions, a pack and two
- * packed min / max), and the reduction over the 16 lanes of a DPP row is one v_min_u32_dpp / v_max_u32_dpp per step and
- * value.  Only the cell's four results are turned into grid cells (lanes 0, 16, 32, 48): the minimum with the low dword 0
- * (rounded down), the maximum with the high dword + 1 (rounded up) - the box can only grow by that, never lose a point:
- * "a cell's box [x0, x1] x [y0, y1] holds points with xMin + x0 / boxX <= x < xMin + (x1 + 1) / boxX" (live_box_thresholds)
- * stays true. */
-__device__ __forceinline__ unsigned int row_min_u32(unsigned int v)
-{
-  v = min(v, static_cast<unsigned int>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x128, 0xf, 0xf, false)));
-  v = min(v, static_cast<unsigned int>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x124, 0xf, 0xf, false)));
-  v = min(v, static_cast<unsigned int>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x122, 0xf, 0xf, false)));
-  v = min(v, static_cast<unsigned int>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x121, 0xf, 0xf, false)));
-  return v;
-}
-__device__ __forceinline__ unsigned int row_max_u32(unsigned int v)
-{
-  v = max(v, static_cast<unsigned int>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x128, 0xf, 0xf, false)));
-  v = max(v, static_cast<unsigned int>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x124, 0xf, 0xf, false)));
-  v = max(v, static_cast<unsigned int>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x122, 0xf, 0xf, false)));
-  v = max(v, static_cast<unsigned int>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x121, 0xf, 0xf, false)));
-  return v;
-}
-/* The box of a cell from the four extremes' high dwords: a minimum with the low dword 0 is the lowest the distance can have
- * been (its cell is below 256: the distance is below the range), a maximum with the NEXT high dword the highest (clamped). */
-__device__ __forceinline__ unsigned int cell_box_from_high_dwords(unsigned int x0, unsigned int x1, unsigned int y0, unsigned int y1,
-                                                                  double boxX, double boxY)
-{
-  const unsigned int cx0 = static_cast<unsigned int>(__hiloint2double(static_cast<int>(x0), 0) * boxX);
-  const unsigned int cy0 = static_cast<unsigned int>(__hiloint2double(static_cast<int>(y0), 0) * boxY);
-  const unsigned int cx1 = min(static_cast<unsigned int>(__hiloint2double(static_cast<int>(x1 + 1u), 0) * boxX), 255u);
-  const unsigned int cy1 = min(static_cast<unsigned int>(__hiloint2double(static_cast<int>(y1 + 1u), 0) * boxY), 255u);
-  return (cx0 | (cx1 << 8)) | ((cy0 | (cy1 << 8)) << 16);
-}
-
-/* The list of the cells of a block's chunk whose mask meets `wanted`, in LDS, COLUMN-major: the cells of one
- * cell column (`cols` cells apart: vertically adjacent in the camera image) follow each other, so a wave that walks
- * the list stays on one patch of the top-down image that creeps down row by row — what its LDS write-combining
- * window needs — and jumps only at a column change.  Entries are cell indices relative to the chunk's first cell.
- * wantCell(record) decides from the cell's record (x = mask of the groups of 4 height bins that occur, y = bounding box,
- * x0 | x1 << 8 | y0 << 16 | y1 << 24 on the 256 x 256 grid) whether the cell is walked.
- * All threads of the block call it; returns the number of entries (block-uniform).  scratch: 2 * kWavesPerBlock words. */
-template<typename Want>
-__device__ __forceinline__ int cell_list_build(const uint2 *__restrict__ cellInfo, int nCells, int cols, Want wantCell,
-                                               unsigned short *list, unsigned int *scratch)
-{
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int rows = (nCells + cols - 1) / cols;
-  constexpr int kFastPasses = 2;                 /* chunks of up to 32 tiles: the product's geometry for batches */
-  if(rows * cols <= kFastPasses * kThreads)
-  {
-    /* All records of the chunk requested at once, every pass's ballot taken, ONE barrier for the counts, one for the list:
-     * two barriers and one memory round trip, where the loop below pays two of each per 256 cells (measured: the list was
-     * 11 % of a block's life in k_raster and k_inquad). */
-    int cidx[kFastPasses];
-    uint2 rec[kFastPasses];
-#pragma unroll
-    for(int p = 0; p < kFastPasses; p++)
-    {
-      const int i = p * kThreads + tid;
-      const int cx = i / rows, r = i - cx * rows;
-      const int c = r * cols + cx;
-      cidx[p] = (cx < cols && c < nCells) ? c : -1;
-      rec[p] = cidx[p] >= 0 ? cellInfo[c] : make_uint2(0u, 0u);
-    }
-    bool want[kFastPasses];
-    int pos[kFastPasses];
-#pragma unroll
-    for(int p = 0; p < kFastPasses; p++)
-    {
-      want[p] = cidx[p] >= 0 && wantCell(rec[p]);
-      const unsigned long long b = __ballot(want[p]);
-      pos[p] = __popcll(b & ((1ull << lane) - 1ull));
-      if(lane == 0)
-        scratch[p * kWavesPerBlock + wave] = static_cast<unsigned int>(__popcll(b));
-    }
-    __syncthreads();
-    int total = 0;
-#pragma unroll
-    for(int p = 0; p < kFastPasses; p++)
-    {
-      int before = total;
-#pragma unroll
-      for(int w = 0; w < kWavesPerBlock; w++)
-      {
-        const int n = static_cast<int>(scratch[p * kWavesPerBlock + w]);
-        before += w < wave ? n : 0;
-        total += n;
-      }
-      if(want[p])
-        list[before + pos[p]] = static_cast<unsigned short>(cidx[p]);
-    }
-    __syncthreads();
-    return total;
-  }
-  int total = 0;
-  for(int i0 = 0; i0 < rows * cols; i0 += kThreads)
-  {
-    const int i = i0 + tid;
-    const int cx = i / rows, r = i - cx * rows;
-    const int c = r * cols + cx;
-    const bool want = cx < cols && c < nCells && wantCell(cellInfo[c]);
-    const unsigned long long b = __ballot(want);
-    if(lane == 0)
-      scratch[wave] = static_cast<unsigned int>(__popcll(b));
-    __syncthreads();
-    int before = total;
-#pragma unroll
-    for(int w = 0; w < kWavesPerBlock; w++)
-    {
-      const int n = static_cast<int>(scratch[w]);
-      before += w < wave ? n : 0;
-      total += n;
-    }
-    if(want)
-      list[before + __popcll(b & ((1ull << lane) - 1ull))] = static_cast<unsigned short>(c);
-    __syncthreads();
-  }
-  return total;
-}
-
-/* A wave takes a contiguous run of GROUPS of four list entries; DPP row q (lanes 16q .. 16q+15) takes entry 4g + q:
- * its 16 lanes read the cell's 768 bytes contiguously, four consecutive points per lane.  Rows beyond the end of the
- * list get invalid points (z = 0), which every consumer drops first. */
-template<int SRC>
-__device__ __forceinline__ void load_cell(const float *__restrict__ base, int cell0, const unsigned short *list, int entry, int count,
-                                          int lane, int nPoints, F3 (&v)[kPts], const DepthSrc &D)
-{
-  if(entry < count)
-    load_points<SRC>(base, (cell0 + static_cast<int>(list[entry])) * kCell + kPts * (lane & 15), nPoints, v, D);
-  else
-  {
-#pragma unroll
-    for(int j = 0; j < kPts; j++)
-      v[j] = F3{ 0.0f, 0.0f, 0.0f };
-  }
-}
-
-/* ========================================================================= */
-/* LDS image windows, pixel keys, fixed-point z: shared by K1 (single pass), K2 and K4 */
-
-/* Write-combining LDS windows for the rasterising kernels — one per WAVE, no barriers.
- *
- * Setting one bit per point with global atomics costs more than the whole fp64 path (memory-side atomics:
- * ~1.9 ms of K2's 3.8 ms per 1024 XGA frames, profiles/r01).  A wave owns 256 consecutive camera pixels of
- * every camera row of its block's chunk; on one plateau those land on a patch of a few 64-bit word columns
- * that creeps down the top-down image by one or two rows per camera row.  So each wave keeps a window of
- * kWinRows x kWinCols words of ONE image (slot, row0, col0 — wave-uniform) in LDS, ORs bits into it with LDS
- * atomics (no global traffic, no vmcnt) and writes the non-zero words out with global atomics only when the
- * window moves and at the end.  Bits outside the window go straight to memory, so the result never depends
- * on where the window is; when more lanes missed than hit during a tile the wave flushes and re-anchors at
- * the lowest missing (image, row).  Everything is decided with ballots and shuffles inside the wave. */
-constexpr int kWinWords = 256;      /* 2 KiB per wave; shaped (256 >> winShift) rows x (1 << winShift) word columns, see PixelParams::winShift */
-
-struct ImageBox { int yMin, yMax, xMin, xMax; };
-
-struct WaveWindow
-{
-  int slot = -1, row0 = 0, col0 = 0;     /* wave-uniform */
-  unsigned int limitWords = 0xffffffffu; /* 64-bit words of the frame's images behind `images` (SSD_CHECKED builds compare) */
-};
-
-/* Bits that miss the window go straight to memory; their bounding box is kept per WAVE in LDS (wm[2..5] = row min /
- * max, word column min / max; wm[6] = the image slots touched; wm[0..1], wm[7] unused): four LDS
- * min/max per miss, no per-lane state.  One box for all slots of the wave: a wave that misses in several images
- * (outliers) widens each of them to the union — boxes only bound the region K3 / K5 visit and clear. */
-constexpr int kWaveMissWords = 8;
-__device__ __forceinline__ void wavemiss_init(unsigned int *wm)
-{
-  wm[0] = 0xffffffffu; wm[1] = 0u;
-  wm[2] = 0x7fffffffu; wm[3] = 0xffffffffu;              /* as int: INT_MAX, -1 */
-  wm[4] = 0x7fffffffu; wm[5] = 0xffffffffu;
-  wm[6] = 0u; wm[7] = 0u;
-}
-/* end of the kernel, whole wave: the wave's miss box into the block's per-slot boxes */
-__device__ __forceinline__ void wavemiss_flush(unsigned int *wm, ImageBox *boxes, int lane)
-{
-  const unsigned int slots = wm[6];
-  if(lane < 32 && ((slots >> lane) & 1u))
-  {
-    const int *b = reinterpret_cast<const int *>(wm);
-    atomicMin(&boxes[lane].yMin, b[2]); atomicMax(&boxes[lane].yMax, b[3]);
-    atomicMin(&boxes[lane].xMin, b[4]); atomicMax(&boxes[lane].xMax, b[5]);
-  }
-}
-
-/* signed minimum / maximum over the wave: rows by DPP, the four rows by v_readlane */
-__device__ __forceinline__ int wave_min_i(int v)
-{
-  v = min(v, __builtin_amdgcn_update_dpp(0x7fffffff, v, 0x128, 0xf, 0xf, false));
-  v = min(v, __builtin_amdgcn_update_dpp(0x7fffffff, v, 0x124, 0xf, 0xf, false));
-  v = min(v, __builtin_amdgcn_update_dpp(0x7fffffff, v, 0x122, 0xf, 0xf, false));
-  v = min(v, __builtin_amdgcn_update_dpp(0x7fffffff, v, 0x121, 0xf, 0xf, false));
-  return min(min(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)), min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
-}
-__device__ __forceinline__ int wave_max_i(int v)
-{
-  v = max(v, __builtin_amdgcn_update_dpp(static_cast<int>(0x80000000u), v, 0x128, 0xf, 0xf, false));
-  v = max(v, __builtin_amdgcn_update_dpp(static_cast<int>(0x80000000u), v, 0x124, 0xf, 0xf, false));
-  v = max(v, __builtin_amdgcn_update_dpp(static_cast<int>(0x80000000u), v, 0x122, 0xf, 0xf, false));
-  v = max(v, __builtin_amdgcn_update_dpp(static_cast<int>(0x80000000u), v, 0x121, 0xf, 0xf, false));
-  return max(max(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)), max(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
-}
-
-/* writes the wave's window out (non-zero words only), clears it, extends the image's bounding box; all 64 lanes */
-__device__ __forceinline__ void wavewin_flush(unsigned long long *ww, const WaveWindow &w, unsigned long long *__restrict__ images,
-                                              unsigned int imgWords, int W64, int winShift, ImageBox *boxes, int lane)
-{
-  if(w.slot < 0)
-    return;
-  unsigned long long *img = images + static_cast<size_t>(w.slot) * imgWords;
-  int y0 = 0x7fffffff, y1 = -1, x0 = 0x7fffffff, x1 = -1;
-#pragma unroll
-  for(int k = 0; k < kWinWords / 64; k++)
-  {
-    const int i = k * 64 + lane;
-    const unsigned long long v = ww[i];
-    if(v)
-    {
-      const int y = w.row0 + (i >> winShift), x = w.col0 + (i & ((1 << winShift) - 1));
-      if(SSD_CHK(1, static_cast<size_t>(w.slot) * imgWords + static_cast<size_t>(y) * W64 + x, w.limitWords) && SSD_CHK(2, x, W64))
-        atomicOr(img + static_cast<size_t>(y) * W64 + x, v);
-      ww[i] = 0ull;
-      y0 = min(y0, y); y1 = max(y1, y);
-      x0 = min(x0, x); x1 = max(x1, x);
-    }
-  }
-  y1 = wave_max_i(y1);
-  if(y1 >= 0)
-  {
-    y0 = wave_min_i(y0); x0 = wave_min_i(x0); x1 = wave_max_i(x1);
-    if(lane == 0)
-    {
-      atomicMin(&boxes[w.slot].yMin, y0); atomicMax(&boxes[w.slot].yMax, y1);
-      atomicMin(&boxes[w.slot].xMin, x0); atomicMax(&boxes[w.slot].xMax, x1);
-    }
-  }
-}
-
-/* A lit pixel as one sortable word: image slot (5 bits) | row (13) | column (13); width and height <= 8192 (ssd_create).
- * kNoPixel sorts last.  (key >> 6) names the pixel's 64-bit image word. */
-constexpr unsigned int kNoPixel = 0xffffffffu;
-__device__ __forceinline__ unsigned int pixel_key(int slot, int iy, int ix)
-{
-  return (static_cast<unsigned int>(slot) << 26) | (static_cast<unsigned int>(iy) << 13) | static_cast<unsigned int>(ix);
-}
-
-/* minimum over the wave, the same in every lane (and uniform to the compiler): the rows by DPP, the four rows by v_readlane
- * (round 4: six ds_bpermute steps per value) */
-__device__ __forceinline__ unsigned int wave_min_u32(unsigned int v)
-{
-  v = row_min_u32(v);
-  return min(min(static_cast<unsigned int>(__builtin_amdgcn_readlane(static_cast<int>(v), 0)), static_cast<unsigned int>(__builtin_amdgcn_readlane(static_cast<int>(v), 16))),
-             min(static_cast<unsigned int>(__builtin_amdgcn_readlane(static_cast<int>(v), 32)), static_cast<unsigned int>(__builtin_amdgcn_readlane(static_cast<int>(v), 48))));
-}
-
-/* The window's origin as a pixel_key (slot, row0, 64 * col0): for a pixel key k of the same image at or beyond the origin,
- * d = k - base is (row - row0) << 13 | (column - 64 * col0); a pixel of another image, a higher row, or a column left of
- * the origin borrows into the upper fields and fails the bounds below (64 * col0 + window width <= 8192), so one
- * subtraction and two compares decide "inside the window".  kNoWindow (bit 31, which no pixel key has) fails for all. */
-constexpr unsigned int kNoWindow = 0x80000000u;
-__device__ __forceinline__ unsigned int window_base(const WaveWindow &w)
-{
-  return w.slot < 0 ? kNoWindow : pixel_key(w.slot, w.row0, w.col0 << 6);
-}
-/* rows (kWinWords >> winShift) and pixel columns (64 << winShift) of a window are powers of two, so "row offset below the
- * rows and column offset below the columns" is "d has no bit outside the two offset fields": one AND and one compare with
- * zero (round 3: two shifts / masks and two compares) */
-__device__ __forceinline__ bool window_hit(unsigned int d, int winShift)
-{
-  const unsigned int inside = (((static_cast<unsigned int>(kWinWords) >> winShift) - 1u) << 13) | ((64u << winShift) - 1u);
-  return (d & ~inside) == 0u;
-}
-
-/* Before a tile's pixels go out, all 64 lanes; `first` = the lane's lowest pixel_key of this tile (kNoPixel: none).
- * When more than half of the lanes that have pixels would miss the window, it is flushed and re-anchored at the lowest
- * such key FIRST — deciding only after the tile had gone out (round 1 / 2a) sent every wave's first tile and the tile
- * after each change of cell column straight to memory: 10.5 % of all words, 2.2 % now (tools/window_sim.py). */
-__device__ __forceinline__ void wavewin_prepare(unsigned long long *ww, WaveWindow &w, unsigned long long *__restrict__ images,
-                                                unsigned int imgWords, int W64, int winShift, ImageBox *boxes, unsigned int first, int lane)
-{
-  const bool has = first != kNoPixel;
-  const bool miss = has && !window_hit(first - window_base(w), winShift);
-  const unsigned long long missing = __ballot(miss);
-  if(missing == 0ull || 2 * __popcll(missing) <= __popcll(__ballot(has)))
-    return;
-  const unsigned int lowest = __builtin_amdgcn_readfirstlane(wave_min_u32(miss ? first : kNoPixel));
-  wavewin_flush(ww, w, images, imgWords, W64, winShift, boxes, lane);
-  w.slot = static_cast<int>(lowest >> 26);
-  w.row0 = static_cast<int>((lowest >> 13) & 0x1fffu);
-  w.col0 = max(0, min(static_cast<int>((lowest & 0x1fffu) >> 6) - 1, W64 - (1 << winShift)));
-}
-
-/* A lane's (up to four) pixels of one tile, as keys; all 64 lanes (wavewin_prepare votes).  One 32-bit LDS atomic per pixel
- * (the window's 64-bit words as pairs of halves), no merging of the lane's neighbouring pixels first: with range noise
- * they shared a word only 1.4 to 1, and the bookkeeping for it cost more instructions than the atomics it saved.  A pixel
- * outside the window goes straight to memory (the bounding box of those is kept per wave, wavemiss_*), so the result never
- * depends on where the window is. */
-__device__ __forceinline__ void wavewin_emit(unsigned long long *ww, unsigned int *wm, WaveWindow &w, unsigned long long *__restrict__ images,
-                                             unsigned int imgWords, int W64, int winShift, ImageBox *boxes, const unsigned int (&key)[4], int lane)
-{
-  wavewin_prepare(ww, w, images, imgWords, W64, winShift, boxes, min(min(key[0], key[1]), min(key[2], key[3])), lane);
-  const unsigned int base = window_base(w);
-  unsigned int *ww32 = reinterpret_cast<unsigned int *>(ww);
-#pragma unroll
-  for(int j = 0; j < 4; j++)
-  {
-    const unsigned int k = key[j], d = k - base;
-    const unsigned int bit = 1u << (k & 31u);
-    if(window_hit(d, winShift))
-    {
-      if(SSD_CHK(3, ((d >> 13) << (winShift + 1)) + ((d & 0x1fffu) >> 5), 2 * kWinWords))
-        atomicOr(&ww32[((d >> 13) << (winShift + 1)) + ((d & 0x1fffu) >> 5)], bit);
-    }
-    else if(k != kNoPixel)
-    {
-      const unsigned int slot = k >> 26, iy = (k >> 13) & 0x1fffu, ix = k & 0x1fffu, xw = ix >> 6;
-      if(SSD_CHK(4, static_cast<unsigned long long>(slot) * imgWords + iy * static_cast<unsigned int>(W64) + xw, w.limitWords) && SSD_CHK(5, xw, W64))
-        atomicOr(reinterpret_cast<unsigned int *>(images + (slot * imgWords + iy * static_cast<unsigned int>(W64) + xw)) + ((ix >> 5) & 1u), bit);
-      int *b = reinterpret_cast<int *>(wm);
-      atomicMin(&b[2], static_cast<int>(iy)); atomicMax(&b[3], static_cast<int>(iy));
-      atomicMin(&b[4], static_cast<int>(xw)); atomicMax(&b[5], static_cast<int>(xw));
-      atomicOr(&wm[6], 1u << slot);
-    }
-  }
-}
-
-/* Projection2D::worldToImage (pointcloud.cpp:79-83); false = outside the image (quirk Q5) */
-__device__ __forceinline__ bool image_pixel(const PointParams &P, const PixelParams &X, double wx, double wy, int &ix, int &iy)
-{
-  ix = static_cast<int>((wx - P.xMin) * X.xToImage);
-  iy = static_cast<int>((P.yMax - wy) * X.yToImage);
-  /* two unsigned compares: a negative coordinate is a huge unsigned one */
-  return (static_cast<unsigned int>(ix) < static_cast<unsigned int>(X.W)) & (static_cast<unsigned int>(iy) < static_cast<unsigned int>(X.H));
-}
-
-/* round(z * 2^40) without a double->int64 conversion (a long software sequence on this ISA): adding
- * 1.5 * 2^12 puts z (|z| < 2048) on the 2^-40 grid of [4096, 8192), rounded to nearest even by the add;
- * the mantissa difference to the constant is the integer.  Same value as llrint(z * 2^40). */
-__device__ __forceinline__ long long z_to_fixed(double z)
-{
-  const double magic = 6144.0;
-  return __double_as_longlong(z + magic) - __double_as_longlong(magic);
-}
-/* the same in two halves for running sums: n values of z_plus_magic_bits minus n * kMagicBits */
-__device__ __forceinline__ long long z_plus_magic_bits(double z)
-{
-  return __double_as_longlong(z + 6144.0);
-}
-constexpr long long kMagicBits = 0x40B8000000000000ll;       /* bits of 6144.0 */
-
-/* ---- single pass: K1's window spans FOUR planes ----
- * K1 rasters the points of the bins k_predict chose, one bit image ("plane") per height bin: which two adjacent bins make a
- * plateau is only known once the histogram is complete (k_peaks), and range noise spreads a tread over two or three bins
- * whose pixels interleave.  A window over one image would send every pixel of the minority bins to memory; this one
- * holds the same patch of 2^kSpecPlaneBits consecutive planes, 2^kSpecRowBits rows x 8 words each (2 x 16 x 8: 2 KiB per wave;
- * 4 planes x 16 rows, 2 x 32 and 1 x 32 measured the same or slower, 4 x 32 - three blocks per CU - much slower:
- * profiles/r04_single_pass_ab.txt).  Keys as pixel_key with the plane in the slot field, "inside" by one subtraction and one
- * AND as window_hit.  Since k_predict gives a tread whose fuller neighbour bin is beyond doubt ONE plane for both bins, most
- * treads live in a single plane anyway. */
-#ifndef SSD_SPEC_PLANE_BITS
-#define SSD_SPEC_PLANE_BITS 1
-#endif
-#ifndef SSD_SPEC_ROW_BITS
-#define SSD_SPEC_ROW_BITS 4
-#endif
-constexpr int kSpecPlaneBits = SSD_SPEC_PLANE_BITS, kSpecRowBits = SSD_SPEC_ROW_BITS;
-constexpr int kSpecWinPlanes = 1 << kSpecPlaneBits, kSpecWinRows = 1 << kSpecRowBits, kSpecWinCols = 8;
-constexpr int kSpecWinWords = kSpecWinPlanes * kSpecWinRows * kSpecWinCols;
-constexpr unsigned int kSpecInside = (static_cast<unsigned int>(kSpecWinPlanes - 1) << 26) | (static_cast<unsigned int>(kSpecWinRows - 1) << 13)
-                                     | static_cast<unsigned int>(64 * kSpecWinCols - 1);
-static_assert(kSpecWinCols == 8, "the index arithmetic below is written for eight word columns");
-static_assert(kMaxPlanes <= 32 - kSpecWinPlanes, "a plane offset that borrows must fall outside the window's planes");
-
-struct SpecWindow
-{
-  int plane0 = -1, row0 = 0, col0 = 0;   /* wave-uniform */
-};
-__device__ __forceinline__ unsigned int specwin_base(const SpecWindow &w)
-{
-  return w.plane0 < 0 ? kNoWindow : pixel_key(w.plane0, w.row0, w.col0 << 6);
-}
-__device__ __forceinline__ bool specwin_hit(unsigned int d)
-{
-  return (d & ~kSpecInside) == 0u;
-}
-/* OR over the wave, result in every lane's SGPR copy: rows by DPP, the four rows by readlane */
-__device__ __forceinline__ unsigned int wave_or_u32(unsigned int v)
-{
-  v = row_or_u32(v);
-  return static_cast<unsigned int>(__builtin_amdgcn_readlane(static_cast<int>(v), 0) | __builtin_amdgcn_readlane(static_cast<int>(v), 16)
-                                   | __builtin_amdgcn_readlane(static_cast<int>(v), 32) | __builtin_amdgcn_readlane(static_cast<int>(v), 48));
-}
-/* Round 6: the window's rows are a RING - image row r of the window's range [row0, row0 + kSpecWinRows) lives in slot
- * r & (kSpecWinRows - 1) - so that the window can SLIDE down the image by half its height, writing out only the rows it leaves,
- * instead of standing still until more than half of a tile's pixels miss it and then being written out whole: measured on the
- * bench's frames, 98 % of the wave-tiles' pixels span fewer than 16 rows, yet 5 % of all pixels missed the standing window
- * "below" - in the tiles before each move - and went to memory one by one (tools/k1count.py, profiles/r06_k1_windows.txt).
- *
- * NROWS rows from image row rBegin (within the window's range) out - non-zero words only - and cleared.  One pass per plane
- * and 8 rows: lane = (row, word column).  The rows and columns that held bits come from the ballot of the non-zero words on the
- * scalar unit (no reductions over the wave), and extend the plane's box.  All 64 lanes. */
-template<int NROWS>
-__device__ __forceinline__ void specwin_flush_rows(unsigned long long *ww, const SpecWindow &w, const int rBegin, unsigned long long *__restrict__ planes,
-                                                   unsigned int imgWords, int W64, ImageBox *boxes, int lane)
-{
-  static_assert(NROWS % 8 == 0 && NROWS <= kSpecWinRows, "whole passes of 8 rows");
-  if(w.plane0 < 0)
-    return;
-#pragma unroll
-  for(int pl = 0; pl < kSpecWinPlanes; pl++)
-  {
-    unsigned long long *img = planes + static_cast<size_t>(w.plane0 + pl) * imgWords;
-#pragma unroll
-    for(int k = 0; k < NROWS / 8; k++)
-    {
-      const int y = rBegin + 8 * k + (lane >> 3), x = w.col0 + (lane & 7);
-      const int at = pl * (kSpecWinRows * kSpecWinCols) + ((y & (kSpecWinRows - 1)) << 3) + (lane & 7);
-      const unsigned long long v = ww[at];
-      const unsigned long long nz = __ballot(v != 0ull);         /* bit 8 r + c: row rBegin + 8 k + r, word column col0 + c */
-      SSD_CNT(3, __popcll(nz));
-      if(v)
-      {
-#if !(defined(SSD_ABL) && SSD_ABL == 3)
-        if(SSD_CHK(6, static_cast<size_t>(w.plane0 + pl) * imgWords + static_cast<size_t>(y) * W64 + x, static_cast<size_t>(kMaxPlanes) * imgWords) && SSD_CHK(7, x, W64))
-          atomicOr(img + static_cast<size_t>(y) * W64 + x, v);
-#endif
-        ww[at] = 0ull;
-      }
-      if(nz != 0ull)
-      {
-        unsigned long long r = nz | (nz >> 4);
-        r |= r >> 2;
-        r |= r >> 1;
-        r &= 0x0101010101010101ull;                               /* bit 8 r: row r held bits */
-        unsigned long long c = nz | (nz >> 32);
-        c |= c >> 16;
-        c |= c >> 8;
-        c &= 0xffull;                                             /* bit c: column c held bits */
-        const int rLo = (__ffsll(static_cast<long long>(r)) - 1) >> 3, rHi = (63 - __clzll(static_cast<long long>(r))) >> 3;
-        const int cLo = __ffsll(static_cast<long long>(c)) - 1, cHi = 63 - __clzll(static_cast<long long>(c));
-        if(lane == 0)
-        {
-          ImageBox &bx = boxes[w.plane0 + pl];
-          atomicMin(&bx.yMin, rBegin + 8 * k + rLo); atomicMax(&bx.yMax, rBegin + 8 * k + rHi);
-          atomicMin(&bx.xMin, w.col0 + cLo); atomicMax(&bx.xMax, w.col0 + cHi);
-        }
-      }
-    }
-  }
-}
-/* the whole window out (before it is re-anchored, and at the end of the block's loop) */
-__device__ __forceinline__ void specwin_flush(unsigned long long *ww, const SpecWindow &w, unsigned long long *__restrict__ planes,
-                                              unsigned int imgWords, int W64, ImageBox *boxes, int lane)
-{
-  specwin_flush_rows<kSpecWinRows>(ww, w, w.row0, planes, imgWords, W64, boxes, lane);
-}
-/* Before a tile's pixels go out, all 64 lanes; first / last: the lane's lowest and highest pixel_key of this tile (kNoPixel: none;
- * last as a signed number: kNoPixel is -1 and sorts below every key).
- *   - enough lanes (kSpecSlideLanes) whose last pixel lies in the half window BELOW the window - same planes, same columns -
- *     while no more than half of the lanes miss it altogether: the window slides down by half its height (the rows it leaves
- *     are written out);
- *   - more than half of the lanes that have pixels miss it: written out whole and re-anchored - one plane below the lowest
- *     plane of the tile's pixels (a tread's minority bin may lie on either side of the bin seen first), the lowest missing row,
- *     one word left of the lowest missing column. */
-constexpr int kSpecSlideLanes = 6;
-constexpr int kSpecSlideRows = kSpecWinRows / 2;
-static_assert(kSpecSlideRows % 8 == 0, "a slide writes whole passes of 8 rows");
-__device__ __forceinline__ void specwin_prepare(unsigned long long *ww, SpecWindow &w, unsigned long long *__restrict__ planes,
-                                                unsigned int imgWords, int W64, ImageBox *boxes, unsigned int first, int last, int lane)
-{
-  const unsigned int base = specwin_base(w);
-  const bool has = first != kNoPixel;
-  const bool miss = has && !specwin_hit(first - base);
-  /* "below": the difference to the origin has the row offset's next bit set and nothing else outside the window's fields, with
-   * the offset below 1.5 windows: rows [kSpecWinRows, kSpecWinRows + kSpecSlideRows) */
-  const unsigned int dl = static_cast<unsigned int>(last) - base;
-  const bool below = last >= 0 && (dl & ~(kSpecInside & ~(static_cast<unsigned int>(kSpecSlideRows) << 13))) == (static_cast<unsigned int>(kSpecWinRows) << 13);
-  const unsigned long long missing = __ballot(miss);
-  const int nMissing = __popcll(missing), nHas = __popcll(__ballot(has));
-  if(2 * nMissing <= nHas)
-  {
-    if(__popcll(__ballot(below)) >= kSpecSlideLanes)
-    {
-      SSD_CNT(2, 1);
-      specwin_flush_rows<kSpecSlideRows>(ww, w, w.row0, planes, imgWords, W64, boxes, lane);
-      w.row0 += kSpecSlideRows;
-    }
-    return;
-  }
-  const unsigned int loPlane = __builtin_amdgcn_readfirstlane(wave_min_u32(has ? first >> 26 : 31u));     /* of ALL the tile's pixels: the planes of a tread alternate */
-  const unsigned int loRow = __builtin_amdgcn_readfirstlane(wave_min_u32(miss ? (first >> 13) & 0x1fffu : 0x1fffu));
-  const unsigned int loCol = __builtin_amdgcn_readfirstlane(wave_min_u32(miss ? first & 0x1fffu : 0x1fffu));
-  SSD_CNT(2, 1);
-  specwin_flush(ww, w, planes, imgWords, W64, boxes, lane);
-  w.plane0 = max(0, min(static_cast<int>(loPlane) - (kSpecWinPlanes > 2 ? 1 : 0), kMaxPlanes - kSpecWinPlanes));
-  w.row0 = static_cast<int>(loRow);
-  w.col0 = max(0, min(static_cast<int>(loCol >> 6) - 1, W64 - kSpecWinCols));
-}
-/* The pixels a lane sent straight to memory because they missed the window: their bounding box and planes, in the lane's
- * registers (K2 / K4 keep them per wave in LDS with five LDS atomics per miss, wavemiss_*; here two or three times as many
- * pixels miss - the points of a candidate bin that lie elsewhere in the image, on a wall behind the stairs - and the lane
- * has registers to spare).  specmiss_flush, end of the block's loop: reduced over the wave, into the block's boxes. */
-struct SpecMiss
-{
-  int y0 = 0x7fffffff, y1 = -1, x0 = 0x7fffffff, x1 = -1;
-  unsigned int planes = 0u;
-};
-__device__ __forceinline__ void specmiss_flush(const SpecMiss &m, ImageBox *boxes, int lane)
-{
-  const unsigned int planes = wave_or_u32(m.planes);
-  if(planes == 0u)
-    return;
-  const int y0 = wave_min_i(m.y0), y1 = wave_max_i(m.y1), x0 = wave_min_i(m.x0), x1 = wave_max_i(m.x1);
-  if(lane < 32 && ((planes >> lane) & 1u))
-  {
-    atomicMin(&boxes[lane].yMin, y0); atomicMax(&boxes[lane].yMax, y1);
-    atomicMin(&boxes[lane].xMin, x0); atomicMax(&boxes[lane].xMax, x1);
-  }
-}
-/* as wavewin_emit; the window's word of a pixel: (plane offset, row slot = row & (rows - 1), half word) */
-__device__ __forceinline__ void specwin_emit(unsigned long long *ww, SpecMiss &miss, SpecWindow &w, unsigned long long *__restrict__ planes,
-                                             unsigned int imgWords, int W64, ImageBox *boxes, const unsigned int (&key)[4], int lane)
-{
-  specwin_prepare(ww, w, planes, imgWords, W64, boxes, min(min(key[0], key[1]), min(key[2], key[3])),
-                  max(max(static_cast<int>(key[0]), static_cast<int>(key[1])), max(static_cast<int>(key[2]), static_cast<int>(key[3]))), lane);
-  const unsigned int base = specwin_base(w);
-  unsigned int *ww32 = reinterpret_cast<unsigned int *>(ww);
-#pragma unroll
-  for(int j = 0; j < 4; j++)
-  {
-    const unsigned int k = key[j], d = k - base;
-    const unsigned int bit = 1u << (k & 31u);
-    SSD_CNT_LANES(4, k != kNoPixel);
-    SSD_CNT_LANES(5, k != kNoPixel && !specwin_hit(d));
-    if(specwin_hit(d))
-    {
-      const unsigned int at = ((d >> 26) << (kSpecRowBits + 4)) | (((k >> 13) & (kSpecWinRows - 1u)) << 4) | ((d & 0x1fffu) >> 5);
-      if(SSD_CHK(8, at, 2 * kSpecWinWords))
-        atomicOr(&ww32[at], bit);
-    }
-    else if(k != kNoPixel)
-    {
-      const unsigned int slot = k >> 26, iy = (k >> 13) & 0x1fffu, ix = k & 0x1fffu, xw = ix >> 6;
-      if(SSD_CHK(9, static_cast<unsigned long long>(slot) * imgWords + iy * static_cast<unsigned int>(W64) + xw, static_cast<unsigned long long>(kMaxPlanes) * imgWords) && SSD_CHK(10, xw, W64))
-        atomicOr(reinterpret_cast<unsigned int *>(planes + (slot * imgWords + iy * static_cast<unsigned int>(W64) + xw)) + ((ix >> 5) & 1u), bit);
-      miss.y0 = min(miss.y0, static_cast<int>(iy)); miss.y1 = max(miss.y1, static_cast<int>(iy));
-      miss.x0 = min(miss.x0, static_cast<int>(xw)); miss.x1 = max(miss.x1, static_cast<int>(xw));
-      miss.planes |= 1u << slot;
-    }
-  }
-}
 
 /* The streaming kernels are written as block bodies over an explicit LDS struct, (frame, chunk) given by the caller:
  * the kernels below pass blockIdx (tools and experiments have paired two bodies in one launch: DESIGN.md section 3). */
@@ -1155,11 +262,9 @@ __device__ __forceinline__ void hist_block(HistLds &L, SPECLDS &SL, const float 
       SSD_CNT(0, 1);
       SSD_CNT(1, __ballot(all4 != 0xffu) != 0ull ? 1 : 0);
       SSD_CNT_LANES(6, planes[0] != 0xffu); SSD_CNT_LANES(6, planes[1] != 0xffu); SSD_CNT_LANES(6, planes[2] != 0xffu); SSD_CNT_LANES(6, planes[3] != 0xffu);
-#if defined(SSD_ABL) && SSD_ABL == 2                  /* tools: timing without the candidates' work (results are wrong) */
-      if(false)
-#else
+      /* (timed without the candidates' work, without the window and with a flush that sends no global atomics: profiles/r06_k1_variants.txt (b);
+       * the three ablations' code: commit ad9a851) */
       if(__ballot(all4 != 0xffu) != 0ull)
-#endif
       {
 #pragma unroll
         for(int j = 0; j < kPts; j++)
@@ -1170,11 +275,7 @@ __device__ __forceinline__ void hist_block(HistLds &L, SPECLDS &SL, const float 
             key = candidatePoint(v[j], kKeepD ? dk[j] : pre_xy(Q, lc.c3xy, v[j].x, v[j].y, v[j].z), plane);
           keys[j] = key;
         }
-#if defined(SSD_ABL) && SSD_ABL == 1                  /* tools: timing without the window (results are wrong) */
-        asm volatile("" :: "v"(keys[0]), "v"(keys[1]), "v"(keys[2]), "v"(keys[3]));
-#else
         specwin_emit(SL.wins[tid >> 6], missed, win, frameImg, imgWords, X.W64, SL.boxes, keys, lane);
-#endif
       }
     }
     if constexpr(SPEC && STRIPS)
@@ -1256,7 +357,8 @@ __device__ __forceinline__ void hist_block(HistLds &L, SPECLDS &SL, const float 
     /* The depth stream: 8 bytes per lane and tile, and the maps.  A tile is 1024 consecutive pixels, so from tile to tile a
      * lane's row advances by 1024 / W and its column by 1024 % W (wrapping once at most): no division in the loop, and when
      * 1024 % W == 0 (XGA: a tile is one image row) the lane's four x-map entries never change - loaded once per block.  The
-     * next tile's pixels and map values are requested before the current tile is processed, as in SSD_STREAM_LOOP.
+     * next tile's pixels and map values are requested before the current tile is processed, as the vertex input's tile
+     * loop does ("one copy of the body", further down in this function).
      * (Round 3 went through load_points: per tile a division, five dependent map loads, ~90 instructions; K1 on depth input is
      * bound by instruction issue, not by its 2 bytes per point.) */
     const unsigned short *depth = reinterpret_cast<const unsigned short *>(base);
@@ -1299,13 +401,13 @@ __device__ __forceinline__ void hist_block(HistLds &L, SPECLDS &SL, const float 
       tileBody(v, it * kCellsPerTile + (tid >> 4));
       it++;
     };
-#ifndef SSD_K1_TWO_BODIES
     /* One copy of the body.  The next tile's loads go out before the current tile is processed and are first looked at behind it
      * (first_use: until round 5's end the compiler waited for them right where they were issued - see load_points_full()), then
      * moved into place: twelve moves per tile.  Tiles wholly inside the chunk take the branch-free loads; a frame that ends in a
-     * part of a tile gets that part by load_points().  Measured against two copies taken in turn (SSD_STREAM_LOOP, which keeps only
-     * one of its two prefetches in flight: the register allocator copies the other out of the loaded tuples at once), 1024 XGA
-     * frames: single pass 2.06 against 2.18 ms, two passes 1.59 against 1.60. */
+     * part of a tile gets that part by load_points().  Measured against two copies taken in turn (two register buffers used
+     * alternately, the loop unrolled by two tiles, which keeps only one of its two prefetches in flight: the register allocator
+     * copies the other out of the loaded tuples at once; the code: SSD_STREAM_LOOP in commit ad9a851), 1024 XGA frames: single pass
+     * 2.06 against 2.18 ms, two passes 1.59 against 1.60. */
     {
       const int fullEnd = begin + (end - begin) / kTile * kTile;
       F3 va[kPts], vb[kPts];
@@ -1331,9 +433,6 @@ __device__ __forceinline__ void hist_block(HistLds &L, SPECLDS &SL, const float 
         tileInOrder(va);
       }
     }
-#else
-    SSD_STREAM_LOOP(tileInOrder)
-#endif
   }
 
   if constexpr(SPEC)
@@ -1392,68 +491,14 @@ __device__ __forceinline__ void hist_block(HistLds &L, SPECLDS &SL, const float 
     const int n = nStore >= 0 ? nStore : it * kCellsPerTile;
     for(int i = tid; i < n; i += kThreads)
       if(SSD_CHK(16, static_cast<size_t>(begin / kCell) + i, tileMaskStride) && SSD_CHK(17, i, kMaxCellsPerBlock))
-#ifdef SSD_NT_STORES          /* tools: the records written past the caches */
-        {
-          __builtin_nontemporal_store(lInfo[i].x, &dst[i].x);
-          __builtin_nontemporal_store(lInfo[i].y, &dst[i].y);
-        }
-#else
-        dst[i] = lInfo[i];
-#endif
+        dst[i] = lInfo[i];       /* (written past the caches, __builtin_nontemporal_store: no cure, profiles/r06_box_spread.txt; K2 +0.12 ms, docs/HISTORY.md; the code: commit ad9a851) */
   }
 }
 
-#ifndef SSD_CAMERAS_TU
-template<int SRC, bool CHECKS>
-__global__ __launch_bounds__(kThreads, 6) void k_hist(const float *__restrict__ xyz, size_t strideFloats, PointParams P, PreXY Q,
-                                                   FrameState *__restrict__ st, uint2 *__restrict__ tileMasks,
-                                                   size_t tileMaskStride, int chunkPoints, DepthSrc D)
-{
-  __shared__ HistLds L;
-  NoSpecLds none;
-  hist_block<SRC, false, false, CHECKS>(L, none, xyz, strideFloats, P, Q, PixelParams{}, st, tileMasks, nullptr, tileMaskStride, chunkPoints, D, blockIdx.x, blockIdx.y);   /* frame on the fast grid axis: see launch note on XCD balance */
-}
-
-/* K1 of a single-pass batch: histogram, cell records AND the planes of the candidate bins.  31 KiB of LDS: five blocks per CU
- * (4 .. 6 measure the same). */
-#endif /* SSD_CAMERAS_TU */
+/* blocks per SIMD that K1's single-pass entry point, k_hist_planes, is built for */
 #ifndef SSD_K1S_WAVES
 #define SSD_K1S_WAVES 5
 #endif
-#ifndef SSD_CAMERAS_TU
-template<int SRC, bool STRIPS, bool CHECKS>
-__global__ __launch_bounds__(kThreads, SSD_K1S_WAVES) void k_hist_planes(const float *__restrict__ xyz, size_t strideFloats, PointParams P, PreXY Q, PixelParams X,
-                                                   FrameState *__restrict__ st, uint2 *__restrict__ tileMasks,
-                                                   unsigned long long *__restrict__ planeImg,
-                                                   size_t tileMaskStride, int chunkPoints, DepthSrc D)
-{
-  __shared__ HistLds L;
-  __shared__ SpecLds SL;
-#ifdef SSD_K1_ROTATE      /* tools: frames walk their chunks in different orders, so that a CU holds tread rows and ground rows at once */
-  const int chunkIdx = static_cast<int>((blockIdx.y + blockIdx.x * SSD_K1_ROTATE) % gridDim.y);
-  const int frameIdx = static_cast<int>(blockIdx.x);
-#elif defined(SSD_K1_ORDER)   /* tools: other walks of the (frame, chunk) grid than "frame fast" - 1: a frame's chunks in a row (over all XCDs); 2: each XCD a frame at a time */
-  const int nF = static_cast<int>(gridDim.x), nC = static_cast<int>(gridDim.y);
-  const int lin = static_cast<int>(blockIdx.y) * nF + static_cast<int>(blockIdx.x);
-  int frameIdx, chunkIdx;
-  if(SSD_K1_ORDER == 2 && (nF & 7) == 0)
-  {
-    const int xcd = lin & 7, i = lin >> 3;
-    frameIdx = xcd + 8 * (i / nC);
-    chunkIdx = i % nC;
-  }
-  else
-  {
-    frameIdx = lin / nC;
-    chunkIdx = lin % nC;
-  }
-#else
-  const int chunkIdx = static_cast<int>(blockIdx.y);
-  const int frameIdx = static_cast<int>(blockIdx.x);
-#endif
-  hist_block<SRC, true, STRIPS, CHECKS>(L, SL, xyz, strideFloats, P, Q, X, st, tileMasks, planeImg, tileMaskStride, chunkPoints, D, frameIdx, chunkIdx);
-}
-#endif /* SSD_CAMERAS_TU */
 
 /* K0 of a single-pass batch: which height bins may belong to a step plateau?  A histogram of a sample of the frame (vertex input: one
  * whole 128-byte line of every fifteen, at a place in its group that changes from group to group - ssd_predict.h; depth input: one run
@@ -1716,22 +761,6 @@ __device__ __forceinline__ void predict_block(const float *__restrict__ xyz, siz
     }
   }
 }
-
-/* the entry points of the one-calibration chain; launch_predict picks by needs_checks(), as launch_hist does */
-#ifndef SSD_CAMERAS_TU
-template<int SRC>
-__global__ __launch_bounds__(kThreads) void k_predict(const float *__restrict__ xyz, size_t strideFloats, PointParams P, PreXY Q, FrameState *__restrict__ st, DepthSrc D,
-                                                      int minHeight, int sabotage, int *__restrict__ fallback, int poolPlanes)
-{
-  predict_block<SRC, false>(xyz, strideFloats, P, Q, st, D, minHeight, sabotage, fallback, poolPlanes);
-}
-template<int SRC>
-__global__ __launch_bounds__(kThreads) void k_predict_checks(const float *__restrict__ xyz, size_t strideFloats, PointParams P, PreXY Q, FrameState *__restrict__ st, DepthSrc D,
-                                                             int minHeight, int sabotage, int *__restrict__ fallback, int poolPlanes)
-{
-  predict_block<SRC, true>(xyz, strideFloats, P, Q, st, D, minHeight, sabotage, fallback, poolPlanes);
-}
-#endif /* SSD_CAMERAS_TU */
 
 /* ========================================================================= */
 /* K1b: peaks, plateaus, LUT — one thread per frame (121 bins: trivial)        */
@@ -2222,35 +1251,6 @@ __device__ __forceinline__ void raster_block(RasterLds &L, const float *__restri
   ph.finish();
 }
 
-/* LIST (single pass): the grid's x blocks share the frames k_peaks listed in `fallback` (count, then frame indices) - the
- * frames whose step plateaus the planes did not cover; none, as a rule, and then every block leaves after one cached load.
- * A template flag, not a run-time test: with both forms in one kernel the two-pass instantiation - the one every depth-16,
- * small, backed-off or partial call takes - paid for the list's loop with 13 - 17 vector registers in scratch (round 4).  The
- * list's own instantiation runs a handful of frames per batch: built for five waves per SIMD, which leaves it the registers
- * its loop wants (no scratch either). */
-#ifndef SSD_CAMERAS_TU
-template<int SRC, bool LIST>
-__global__ __launch_bounds__(kThreads, LIST ? 5 : SSD_K2_WAVES) void k_raster(const float *__restrict__ xyz, size_t strideFloats, PointParams P,
-                                                        PixelParams X, FrameState *__restrict__ st,
-                                                        unsigned long long *__restrict__ stepImg,
-                                                        const uint2 *__restrict__ tileMasks, size_t tileMaskStride, int chunkPoints, DepthSrc D,
-                                                        const int *__restrict__ fallback)
-{
-  __shared__ RasterLds L;
-  if constexpr(LIST)
-  {
-    const int n = fallback[0];
-    for(int e = blockIdx.x; e < n; e += gridDim.x)
-    {
-      raster_block<SRC>(L, xyz, strideFloats, P, X, st, stepImg, tileMasks, tileMaskStride, chunkPoints, D, fallback[kFallbackList + e], blockIdx.y);
-      __syncthreads();
-    }
-  }
-  else
-    raster_block<SRC>(L, xyz, strideFloats, P, X, st, stepImg, tileMasks, tileMaskStride, chunkPoints, D, blockIdx.x, blockIdx.y);
-}
-#endif /* SSD_CAMERAS_TU */
-
 /* ========================================================================= */
 /* BestLine (segmentation.cpp:409-487): a pair of points per lane, the waves dealt out over the lists */
 
@@ -2331,22 +1331,7 @@ __device__ LineI wave_best_line(const int *px, const int *py, int m, int lane, b
 /* ========================================================================= */
 /* K3: outline of one step plateau image — one workgroup per (slot, frame)      */
 
-/* threads of the image kernels (K3, K5): one block per image, a chain of short phases.  More waves = fewer rows per
- * thread in the closing (latency), but the arithmetic phases (BestLine) run at the CU's rate whatever the count, and every
- * barrier and every per-wave preamble is paid per wave: measured on 1024 XGA frames, K3 takes 0.106 / 0.146 / 0.307 ms with
- * 256 / 512 / 1024 threads, on a single frame 30 / 26.5 / 28 us.  Hence two instantiations: 256 for batches, 512 for a few
- * frames. */
-/* (round 4, FHD stress batch of 256 frames, same box, alternating: k_outline with 256 / 512 / 1024 threads per image 0.310 / 0.363 /
- * 0.438 ms — the batch is bound by the images' total work, which more threads do not shrink; tools/mkvariant.sh with
- * -DSSD_IMG_THREADS_BATCH=..) */
-#ifndef SSD_IMG_THREADS_BATCH
-#define SSD_IMG_THREADS_BATCH 256
-#endif
-constexpr int kImgThreadsBatch = SSD_IMG_THREADS_BATCH, kImgThreadsFew = 512;   /* chosen per launch (launch_outline / launch_final) */
-constexpr int kMaxImgWaves = (kImgThreadsBatch > kImgThreadsFew ? kImgThreadsBatch : kImgThreadsFew) / 64;
-constexpr int kImgFewFrames = 64;
-constexpr int kMaxCols = SSD_MAX_SCANS;      /* scan columns per image (W/25 + 1 <= 128) */
-constexpr int kMaxProbe = SSD_MAX_EDGE_PTS;  /* probe rows per vertical edge: (H - 1)/10 + 1 <= 256, make_params refuses H > 2560 */
+/* (the image kernels' thread counts, kMaxCols and kMaxProbe: ssd_k_entry.h - the launch rules need them too) */
 
 struct OutlineShared
 {
@@ -3662,23 +2647,6 @@ __device__ __forceinline__ void inquad_block(InquadLds<FULL> &L, const float *__
   ph.finish();
 }
 
-#ifndef SSD_CAMERAS_TU
-template<int SRC, bool FULL, bool CHECKS>
-__global__ __launch_bounds__(kThreads, FULL ? 4 : SSD_K4_WAVES) void k_inquad(const float *__restrict__ xyz, size_t strideFloats, PointParams P, PreXY Q,
-                                                        PixelParams X, FrameState *__restrict__ st,
-                                                        unsigned long long *__restrict__ groundImg,
-                                                        const uint2 *__restrict__ tileMasks, size_t tileMaskStride, int chunkPoints, DepthSrc D)
-{
-  __shared__ InquadLds<FULL> L;
-  /* The chunks at the bottom of the camera image first (an eighth of them, bottom-most first): the ground nearest to the camera,
-   * whose pixels decide what the strip raster may leave out (see there); then the others top-down as ever.  (All chunks
-   * bottom-up: XGA 0.79 -> 0.73 ms like this order, FHD stress 0.55 -> 0.59 — its eight treads, the heavy blocks, came last.) */
-  const int nChunks = static_cast<int>(gridDim.y), first = max(1, nChunks / 8), by = static_cast<int>(blockIdx.y);
-  const int chunkIdx = by < first ? nChunks - 1 - by : by - first;
-  inquad_block<SRC, FULL, CHECKS>(L, xyz, strideFloats, P, Q, X, st, groundImg, tileMasks, tileMaskStride, chunkPoints, D, blockIdx.x, chunkIdx);
-}
-#endif /* SSD_CAMERAS_TU */
-
 /* ========================================================================= */
 /* K7 (extension): per-pixel surface labels                                    */
 
@@ -4074,18 +3042,6 @@ __device__ __forceinline__ void labelled_moments_block(SurfaceLds &S, ssd_frame_
     atomicAdd(reinterpret_cast<unsigned long long *>(out + frame) + 1 + k * kSurfaceSums + i, t);
   });
 }
-
-#ifndef SSD_CAMERAS_TU
-template<int SRC, bool CHECKS>
-__global__ __launch_bounds__(kThreads) void k_surface_moments(const float *__restrict__ xyz, size_t strideFloats, PointParams P, PreXY Q,
-                                                              const FrameState *__restrict__ st, const uint2 *__restrict__ tileMasks,
-                                                              size_t tileMaskStride, int chunkPoints, DepthSrc D,
-                                                              ssd_frame_moments *__restrict__ out)
-{
-  __shared__ SurfaceLds S;
-  labelled_moments_block<SRC, CHECKS, false>(S, nullptr, xyz, strideFloats, P, Q, st, tileMasks, tileMaskStride, chunkPoints, D, nullptr, out);
-}
-#endif /* SSD_CAMERAS_TU */
 
 /* ========================================================================= */
 /* K5: ground front edge and the per-frame result — one workgroup per frame     */
@@ -4778,117 +3734,107 @@ SSD_ENTRY(, k_riser_results, riser_results_block)(SSD_BYVAL(Params) P, const Fra
 
 } // namespace ssd
 
-/* ========================================================================= */
-/* launchers (declared in ssd_launch.h)                                        */
-#include "ssd_launch.h"
-#include <type_traits>
+#include "ssd_launch_rules.h"
 
-namespace ssd
-{
-/* What the three translation units' launchers share: every launch rule once, over the Batch.  A launcher below, in ssd_kernels_cams.hip
- * or in ssd_kernels_refit.hip names its __global__ and that kernel's arguments, nothing else.
- *
- * Grid layout of every per-frame kernel: FRAME on the fast axis (blockIdx.x), chunk / image slot on the slow
- * one.  Workgroups are dealt round-robin over the 8 XCDs in linear-id order; with the chunk (or the image
- * slot) on the fast axis every XCD would always get the same chunk positions of every frame — the stairs
- * for some XCDs, the skipped ground for others (measured: +30 % on K2, and K3 running on half of the XCDs
- * because only slots 0..3 hold images).  Frame-fastest gives each XCD whole frames: balanced, and a frame's
- * state and images stay in one XCD's L2. */
-static inline int chunks_for(int nPoints, int chunkPoints) { return (nPoints + chunkPoints - 1) / chunkPoints; }
-static inline dim3 grid_frames(const Batch &B) { return dim3(B.nframes); }                          /* a block per frame */
-static inline dim3 grid_frame_threads(const Batch &B) { return dim3((B.nframes + 63) / 64); }      /* a thread per frame, blocks of 64 */
-static inline dim3 grid_predict(const Batch &B) { return dim3(B.nframes, kPredictParts); }
-static inline dim3 grid_images(const Batch &B) { return dim3(B.nframes, B.P.maxStepImages); }
-static inline dim3 grid_stream(const Batch &B, int chunkPoints) { return dim3(B.nframes, chunks_for(B.P.nPoints, chunkPoints)); }
-/* k_raster with the single pass's list: a block takes every fourth listed frame in turn */
-static inline dim3 grid_raster(const Batch &B, int chunkPoints, bool listed)
-{
-  return dim3(listed ? (B.nframes + 3) / 4 : B.nframes, chunks_for(B.P.nPoints, chunkPoints));
-}
-/* K1 in the single pass - a tile a whole number of camera rows: the tile loop keeps every wave in its band of columns; else the sorted strips */
-static inline bool hist_strips(const Batch &B, const unsigned long long *planeImg) { return planeImg && kTile % B.P.W != 0; }
-
-/* a run-time bool as std::true_type / std::false_type */
-template<typename F>
-static inline void with_bool(bool b, F f)
-{
-  if(b)
-    f(std::true_type{});
-  else
-    f(std::false_type{});
-}
-/* The point source of a launch as a compile-time constant: f(std::integral_constant<int, kSrc...>, the DepthSrc to pass) */
-template<typename F>
-static inline void with_src(const Batch &B, F f)
-{
-  if(B.depthInput)
-    f(std::integral_constant<int, kSrcDepth16>{}, B.depth);
-  else if((reinterpret_cast<uintptr_t>(B.xyz) & 15u) == 0 && (B.strideFloats & 3u) == 0 && (B.P.nPoints & 3) == 0)
-    f(std::integral_constant<int, kSrcF3Aligned>{}, DepthSrc{});
-  else
-    f(std::integral_constant<int, kSrcF3>{}, DepthSrc{});
-}
-/* ... and CHECKS with it, f(src, checks, DepthSrc): a cameras batch by its table, a one-calibration batch by its constants */
-template<typename F>
-static inline void with_src_checks(const Batch &B, F f)
-{
-  with_src(B, [&](auto src, const DepthSrc &D) { with_bool(B.cams ? B.cams->checks : needs_checks(B.P), [&](auto checks) { f(src, checks, D); }); });
-}
-/* k_predict's: the depth loop has no pre-filter, so it has the one instantiation without CHECKS */
-template<typename F>
-static inline void with_predict(const Batch &B, F f)
-{
-  with_src_checks(B, [&](auto src, auto checks, const DepthSrc &D)
-  {
-    if constexpr(decltype(src)::value == kSrcDepth16)
-      f(src, std::false_type{}, D);
-    else
-      f(src, checks, D);
-  });
-}
-/* k_inquad's, f(src, full, checks, DepthSrc): debug capture (the whole ground image: the handle's, so the same for every camera) always
- * takes the instantiation with the rare configurations' tests */
-template<typename F>
-static inline void with_inquad(const Batch &B, F f)
-{
-  with_src_checks(B, [&](auto src, auto checks, const DepthSrc &D)
-  {
-    if(B.P.px.groundFull)
-      f(src, std::true_type{}, std::true_type{}, D);
-    else
-      f(src, std::false_type{}, checks, D);
-  });
-}
-/* k_outline's and k_final's threads, f(std::integral_constant<int, T>): while every image has a CU of its own, the block that gets
- * through its phases soonest; beyond that the cheapest */
-template<typename F>
-static inline void with_img_threads(const Batch &B, F f)
-{
-  if(B.nframes <= kImgFewFrames)
-    f(std::integral_constant<int, kImgThreadsFew>{});
-  else
-    f(std::integral_constant<int, kImgThreadsBatch>{});
-}
-
-/* the launchers of the cameras entry points (ssd_kernels_cams.hip): what launch_*(B, ...) hands a batch with B.cams to */
-void launch_predict_cams(const Batch &B, int *fallback, int poolPlanes, int sabotage);
-void launch_hist_cams(const Batch &B, int chunkPoints, unsigned long long *planeImg);
-void launch_peaks_cams(const Batch &B, DebugFrame *dbg, int *fallback);
-void launch_raster_cams(const Batch &B, int chunkPoints, unsigned long long *stepImg, const int *fallback);
-void launch_outline_cams(const Batch &B, unsigned long long *stepImg, unsigned long long *planeImg, DebugFrame *dbg, unsigned long long *dbgImg);
-void launch_quads_cams(const Batch &B, DebugFrame *dbg);
-void launch_inquad_cams(const Batch &B, int chunkPoints, unsigned long long *groundImg);
-void launch_final_cams(const Batch &B, unsigned long long *groundImg, ssd_frame_result *results, DebugFrame *dbg, unsigned long long *dbgImg);
-void launch_surface_moments_cams(const Batch &B, int chunkPoints, ssd_frame_moments *out);
-void launch_labels_cams(const Batch &B, int chunkPoints, unsigned char *labels, size_t labelStride);
-void launch_risers_cams(const Batch &B, int chunkPoints, ssd_frame_risers *out);
-void launch_riser_moments_cams(const Batch &B, int chunkPoints, ssd_frame_risers *out, ssd_frame_moments *moments);
-void launch_riser_labels_cams(const Batch &B, int chunkPoints, unsigned char *labels, size_t labelStride);
-} // namespace ssd
-
+/* What follows is the one-calibration path's own, and the one stretch that an including unit leaves out: the entry points that call a
+ * stage's *_block with blockIdx, as ssd_kernels_cams.hip's call it with the frame's camera record, and the launchers. */
 #ifndef SSD_CAMERAS_TU
 namespace ssd
 {
+
+template<int SRC, bool CHECKS>
+__global__ __launch_bounds__(kThreads, 6) void k_hist(const float *__restrict__ xyz, size_t strideFloats, PointParams P, PreXY Q,
+                                                   FrameState *__restrict__ st, uint2 *__restrict__ tileMasks,
+                                                   size_t tileMaskStride, int chunkPoints, DepthSrc D)
+{
+  __shared__ HistLds L;
+  NoSpecLds none;
+  hist_block<SRC, false, false, CHECKS>(L, none, xyz, strideFloats, P, Q, PixelParams{}, st, tileMasks, nullptr, tileMaskStride, chunkPoints, D, blockIdx.x, blockIdx.y);   /* frame on the fast grid axis: see launch note on XCD balance */
+}
+
+/* K1 of a single-pass batch: histogram, cell records AND the planes of the candidate bins.  31 KiB of LDS: five blocks per CU
+ * (4 .. 6 measure the same). */
+template<int SRC, bool STRIPS, bool CHECKS>
+__global__ __launch_bounds__(kThreads, SSD_K1S_WAVES) void k_hist_planes(const float *__restrict__ xyz, size_t strideFloats, PointParams P, PreXY Q, PixelParams X,
+                                                   FrameState *__restrict__ st, uint2 *__restrict__ tileMasks,
+                                                   unsigned long long *__restrict__ planeImg,
+                                                   size_t tileMaskStride, int chunkPoints, DepthSrc D)
+{
+  __shared__ HistLds L;
+  __shared__ SpecLds SL;
+  /* (other walks of the (frame, chunk) grid than "frame fast" - frames walking their chunks in rotated orders, a frame's chunks in a
+   * row over all XCDs, each XCD a frame at a time - changed nothing: profiles/r06_k1_variants.txt (d), profiles/r06_box_spread.txt;
+   * the code: commit ad9a851) */
+  const int chunkIdx = static_cast<int>(blockIdx.y);
+  const int frameIdx = static_cast<int>(blockIdx.x);
+  hist_block<SRC, true, STRIPS, CHECKS>(L, SL, xyz, strideFloats, P, Q, X, st, tileMasks, planeImg, tileMaskStride, chunkPoints, D, frameIdx, chunkIdx);
+}
+
+/* K0; launch_predict picks by needs_checks(), as launch_hist does */
+template<int SRC>
+__global__ __launch_bounds__(kThreads) void k_predict(const float *__restrict__ xyz, size_t strideFloats, PointParams P, PreXY Q, FrameState *__restrict__ st, DepthSrc D,
+                                                      int minHeight, int sabotage, int *__restrict__ fallback, int poolPlanes)
+{
+  predict_block<SRC, false>(xyz, strideFloats, P, Q, st, D, minHeight, sabotage, fallback, poolPlanes);
+}
+template<int SRC>
+__global__ __launch_bounds__(kThreads) void k_predict_checks(const float *__restrict__ xyz, size_t strideFloats, PointParams P, PreXY Q, FrameState *__restrict__ st, DepthSrc D,
+                                                             int minHeight, int sabotage, int *__restrict__ fallback, int poolPlanes)
+{
+  predict_block<SRC, true>(xyz, strideFloats, P, Q, st, D, minHeight, sabotage, fallback, poolPlanes);
+}
+
+/* LIST (single pass): the grid's x blocks share the frames k_peaks listed in `fallback` (count, then frame indices) - the
+ * frames whose step plateaus the planes did not cover; none, as a rule, and then every block leaves after one cached load.
+ * A template flag, not a run-time test: with both forms in one kernel the two-pass instantiation - the one every depth-16,
+ * small, backed-off or partial call takes - paid for the list's loop with 13 - 17 vector registers in scratch (round 4).  The
+ * list's own instantiation runs a handful of frames per batch: built for five waves per SIMD, which leaves it the registers
+ * its loop wants (no scratch either). */
+template<int SRC, bool LIST>
+__global__ __launch_bounds__(kThreads, LIST ? 5 : SSD_K2_WAVES) void k_raster(const float *__restrict__ xyz, size_t strideFloats, PointParams P,
+                                                        PixelParams X, FrameState *__restrict__ st,
+                                                        unsigned long long *__restrict__ stepImg,
+                                                        const uint2 *__restrict__ tileMasks, size_t tileMaskStride, int chunkPoints, DepthSrc D,
+                                                        const int *__restrict__ fallback)
+{
+  __shared__ RasterLds L;
+  if constexpr(LIST)
+  {
+    const int n = fallback[0];
+    for(int e = blockIdx.x; e < n; e += gridDim.x)
+    {
+      raster_block<SRC>(L, xyz, strideFloats, P, X, st, stepImg, tileMasks, tileMaskStride, chunkPoints, D, fallback[kFallbackList + e], blockIdx.y);
+      __syncthreads();
+    }
+  }
+  else
+    raster_block<SRC>(L, xyz, strideFloats, P, X, st, stepImg, tileMasks, tileMaskStride, chunkPoints, D, blockIdx.x, blockIdx.y);
+}
+
+template<int SRC, bool FULL, bool CHECKS>
+__global__ __launch_bounds__(kThreads, FULL ? 4 : SSD_K4_WAVES) void k_inquad(const float *__restrict__ xyz, size_t strideFloats, PointParams P, PreXY Q,
+                                                        PixelParams X, FrameState *__restrict__ st,
+                                                        unsigned long long *__restrict__ groundImg,
+                                                        const uint2 *__restrict__ tileMasks, size_t tileMaskStride, int chunkPoints, DepthSrc D)
+{
+  __shared__ InquadLds<FULL> L;
+  /* The chunks at the bottom of the camera image first (an eighth of them, bottom-most first): the ground nearest to the camera,
+   * whose pixels decide what the strip raster may leave out (see there); then the others top-down as ever.  (All chunks
+   * bottom-up: XGA 0.79 -> 0.73 ms like this order, FHD stress 0.55 -> 0.59 — its eight treads, the heavy blocks, came last.) */
+  const int nChunks = static_cast<int>(gridDim.y), first = max(1, nChunks / 8), by = static_cast<int>(blockIdx.y);
+  const int chunkIdx = by < first ? nChunks - 1 - by : by - first;
+  inquad_block<SRC, FULL, CHECKS>(L, xyz, strideFloats, P, Q, X, st, groundImg, tileMasks, tileMaskStride, chunkPoints, D, blockIdx.x, chunkIdx);
+}
+
+template<int SRC, bool CHECKS>
+__global__ __launch_bounds__(kThreads) void k_surface_moments(const float *__restrict__ xyz, size_t strideFloats, PointParams P, PreXY Q,
+                                                              const FrameState *__restrict__ st, const uint2 *__restrict__ tileMasks,
+                                                              size_t tileMaskStride, int chunkPoints, DepthSrc D,
+                                                              ssd_frame_moments *__restrict__ out)
+{
+  __shared__ SurfaceLds S;
+  labelled_moments_block<SRC, CHECKS, false>(S, nullptr, xyz, strideFloats, P, Q, st, tileMasks, tileMaskStride, chunkPoints, D, nullptr, out);
+}
 
 void launch_predict(const Batch &B, int *fallback, int poolPlanes, int sabotage)
 {

@@ -30,7 +30,6 @@ __global__ __launch_bounds__(kThreads, 6) void k_hist_cams(const float *__restri
   hist_block<SRC, false, false, CHECKS>(L, none, xyz, strideFloats, P, Q, PixelParams{}, st, tileMasks, nullptr, tileMaskStride, chunkPoints, D, blockIdx.x, blockIdx.y);
 }
 
-/* (the tools' other walks of the grid, SSD_K1_ROTATE / SSD_K1_ORDER, are the one-calibration entry point's alone) */
 template<int SRC, bool STRIPS, bool CHECKS>
 __global__ __launch_bounds__(kThreads, SSD_K1S_WAVES) void k_hist_planes_cams(const float *__restrict__ xyz, size_t strideFloats, const CameraRec *__restrict__ cams,
                                                    const int *__restrict__ camOf, FrameState *__restrict__ st, uint2 *__restrict__ tileMasks,

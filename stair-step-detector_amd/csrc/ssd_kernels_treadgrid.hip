@@ -47,26 +47,10 @@ struct TreadGridLds
 };
 
 /* A lane's kPts tread points (keys[j] >= 0: a slot of L.counts; the points are consecutive pixels, so mostly one cell): equal keys are
- * counted once, then one LDS add per distinct key.  SSD_TG_WAVE_KEYS (a tools build, for the comparison in profiles/tread_grid_time.txt)
- * combines equal keys across the wave per point slot instead: a ballot per distinct key, one LDS add by its first lane. */
+ * counted once, then one LDS add per distinct key.  (Combining equal keys across the wave per point slot instead - a ballot per distinct
+ * key, one LDS add by its first lane - was measured and lost: profiles/tread_grid_time.txt; the code: commit ad9a851.) */
 __device__ __forceinline__ void tread_grid_count(unsigned int *counts, int (&keys)[kPts], int lane, int limit)
 {
-#ifdef SSD_TG_WAVE_KEYS
-#pragma unroll
-  for(int j = 0; j < kPts; j++)
-  {
-    unsigned long long todo = __ballot(keys[j] >= 0);
-    while(todo != 0ull)
-    {
-      const int first = __ffsll(static_cast<long long>(todo)) - 1;
-      const int k = __builtin_amdgcn_readlane(keys[j], first);
-      const unsigned long long same = __ballot(keys[j] == k);
-      if(lane == first && SSD_CHK(35, k, limit))
-        atomicAdd(&counts[k], static_cast<unsigned int>(__popcll(same)));
-      todo &= ~same;
-    }
-  }
-#else
 #pragma unroll
   for(int j = 0; j < kPts; j++)
   {
@@ -81,7 +65,6 @@ __device__ __forceinline__ void tread_grid_count(unsigned int *counts, int (&key
     if(keys[j] >= 0 && SSD_CHK(35, keys[j], limit))
       atomicAdd(&counts[keys[j]], n);
   }
-#endif
 }
 
 /* Where a block's staircase comes from and where its counts go (tread_grid_block's `where`): index(frame) = which result and which record

@@ -180,9 +180,6 @@ __host__ __device__ inline void gnu_sort_on(const SortKeys &k, int n, int *stFir
     {
       if(depth == 0)
       {
-#ifdef SSD_SORT_TRACE
-        SSD_SORT_TRACE(first, last);
-#endif
         gs_heapsort(k, first, last);
         break;
       }
