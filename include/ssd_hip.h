@@ -1219,6 +1219,70 @@ int ssd_process_host_stair_pose(ssd_handle *h, const void *frames, int nframes, 
                                 const uint16_t *target_of_frame, const ssd_stair_pose_rule *rule, int min_points, double observable,
                                 ssd_stair_pose_moments *moments /* may be NULL */, ssd_stair_pose *out /* ntargets */);
 
+/* ---- depth fusion: one trimmed-median frame from n frames of a still camera -----------------------------------
+ * A group is n 16-bit depth frames (1 <= n <= SSD_FUSE_MAX_FRAMES) of the handle's width x height, taken while the camera stands still:
+ * along a pixel's ray its n samples measure one quantity.  Integers only.  For one pixel with samples d_0 .. d_(n-1):
+ *   1. a sample is valid iff it is not 0; m = the number of valid samples.  m == 0: output 0, the pixel is EMPTY.  0 < m < min_valid:
+ *      output 0, FEW.
+ *   2. med = the lower median of the valid samples: the (m - 1) / 2-th smallest, counted from 0.
+ *   3. a valid sample agrees iff |d_j - med| <= tol (no wrap); c = the number of agreeing samples (>= 1), s = their sum.
+ *   4. c < min_agree: output 0, SPLIT.
+ *   5. otherwise FUSED: output (2 s + c) / (2 c), the agreeing samples' mean rounded half up - within tol of med, never 0, never
+ *      above 65535.
+ *   6. the optional support byte is c for a fused pixel, else 0.
+ * With the defaults a majority has to agree: a pixel that flickers between two surfaces gives the majority's surface or nothing, never a
+ * depth between them.  Per group one exact record (the four counts add up to the pixel count; sum_abs_dev / sum_agree is the camera's
+ * noise in raw units).  Within a batch of nframes frames group g is frames g * hop .. g * hop + n - 1, 1 <= hop <= n, ngroups =
+ * (nframes - n) / hop + 1: hop == n gives disjoint groups (a batch of several cameras, each camera's frames together, gives one fused
+ * frame per camera), hop == 1 a sliding temporal filter at the full frame rate. */
+#define SSD_FUSE_MAX_FRAMES 16
+#define SSD_FUSE_TOL 40              /* the default tol, raw units: 1 cm at the L515's 0.00025 m */
+typedef struct
+{
+  int32_t min_valid, min_agree, tol, reserved;
+} ssd_depth_fuse_rule;
+typedef struct
+{
+  int64_t n_fused, n_empty, n_few, n_split;
+  int64_t sum_valid;            /* the sum of m over all pixels */
+  int64_t sum_agree;            /* the sum of c over fused pixels */
+  int64_t sum_abs_dev;          /* over fused pixels, the sum over agreeing samples of |d_j - output| */
+  int64_t reserved;
+} ssd_depth_fuse_stats;         /* 64 bytes */
+/* host only: min_valid = min_agree = (n + 1) / 2, tol = SSD_FUSE_TOL.  SSD_E_ARG: null, n outside 1 .. SSD_FUSE_MAX_FRAMES */
+int ssd_depth_fuse_default_rule(int n, ssd_depth_fuse_rule *rule);
+/* host only, no GPU needed: the rule over ONE group.  frames: frame j at frames + j * frame_stride_bytes (a multiple of 2 that holds a
+ * frame when n > 1); rule NULL: the defaults for n; out: width * height values; support (may be NULL): as many bytes; stats: the
+ * group's record.  SSD_E_ARG: a null pointer, width or height not positive, n out of range, a bad stride, a rule outside
+ * 1 <= min_valid <= n, 1 <= min_agree <= n, 0 <= tol <= 65535. */
+int ssd_depth_fuse_host(int width, int height, const uint16_t *frames, size_t frame_stride_bytes, int n, const ssd_depth_fuse_rule *rule,
+                        uint16_t *out, uint8_t *support /* may be NULL */, ssd_depth_fuse_stats *stats);
+/* The pass (k_depth_fuse) over depth frames resident in device memory, on the caller's stream, in order, without synchronising: the
+ * ground fit's contract - no detection workspace, nothing ssd_fetch* reads is touched, no intrinsics or calibration needed; calls on
+ * different streams run in call order.  Fused frame g goes to d_out + g * out_stride_bytes, its support bytes (d_support may be NULL) to
+ * d_support + g * support_stride_bytes, byte for byte ssd_depth_fuse_host's.  A depth-input enqueue on the same stream may read d_out
+ * with no host wait in between (one workspace or several: a lane's stream goes behind what the caller's stream holds).  The stats
+ * buffer (max_frames_per_batch records on the device and pinned) is made on the first call and counted in ssd_workspace_bytes from
+ * then on; a handle that never calls this allocates, creates and launches nothing for it.
+ * SSD_E_ARG before anything is launched or copied: a null handle, input or output; n outside 1 .. SSD_FUSE_MAX_FRAMES; hop outside
+ * 1 .. n; nframes < n, nframes or ngroups above max_frames_per_batch; a rule out of range; frames or output off 2-byte alignment or a
+ * stride that holds no frame (support: a stride below width * height with more than one group); an output or support range that
+ * overlaps the input range. */
+int ssd_enqueue_depth_fuse(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream,
+                           int n, int hop, const ssd_depth_fuse_rule *rule /* NULL: the defaults for n */,
+                           void *d_out, size_t out_stride_bytes, uint8_t *d_support /* may be NULL */, size_t support_stride_bytes);
+/* waits for the last ssd_enqueue_depth_fuse and hands over its groups' records; ngroups <= its */
+int ssd_fetch_depth_fuse(ssd_handle *h, ssd_depth_fuse_stats *out, int ngroups, void *stream);
+/* the device time of the last pass, the zeroing in front of it and the copy of its records behind it included (0 when timing was off for it) */
+int ssd_get_depth_fuse_time(ssd_handle *h, float *ms);
+/* depth frames in host memory (pinned or pageable), disjoint groups only: frames g * n .. g * n + n - 1 are fused on the device and
+ * the fused frame is detected, slice by slice through the staging buffers of ssd_process_depth_host.  results: nframes / n records, byte
+ * for byte ssd_process_depth_host's over ssd_depth_fuse_host's output; fused (may be NULL): nframes / n packed frames; stats (may be
+ * NULL): as many records.  SSD_E_ARG: nframes no multiple of n, n above max_frames_per_batch, no intrinsics, a rule out of range. */
+int ssd_process_depth_host_fused(ssd_handle *h, const uint16_t *depth, int nframes, int n, const ssd_depth_fuse_rule *rule,
+                                 ssd_frame_result *results /* nframes / n */, uint16_t *fused /* may be NULL */,
+                                 ssd_depth_fuse_stats *stats /* may be NULL */);
+
 /* stage selector for profiling / roofline measurement: runs only the chosen stage(s) of the pipeline */
 #define SSD_STAGE_HIST 1       /* K1: transform + crop + bin + histogram */
 #define SSD_STAGE_PEAKS 2

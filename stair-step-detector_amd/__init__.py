@@ -269,6 +269,22 @@ class StairPose(C.Structure):
                 ("eig", C.c_double * 6), ("rms_before", C.c_double), ("rms_after", C.c_double), ("cal", Calibration)]
 
 
+FUSE_MAX_FRAMES, FUSE_TOL = 16, 40   # SSD_FUSE_MAX_FRAMES, SSD_FUSE_TOL
+
+
+class FuseRule(C.Structure):
+    """ssd_depth_fuse_rule: how many of a pixel's samples must be valid (min_valid) and agree with their median (min_agree), and how
+    far from it, in raw units, a sample may lie to agree (tol)"""
+    _fields_ = [("min_valid", C.c_int32), ("min_agree", C.c_int32), ("tol", C.c_int32), ("reserved", C.c_int32)]
+
+
+class FuseStats(C.Structure):
+    """ssd_depth_fuse_stats: a group's record - its pixels by class (they add up to the pixel count), the sum of the valid samples'
+    count over all pixels, of the agreeing samples' count over the fused ones, and of their |sample - output| (raw units)"""
+    _fields_ = [("n_fused", C.c_int64), ("n_empty", C.c_int64), ("n_few", C.c_int64), ("n_split", C.c_int64), ("sum_valid", C.c_int64),
+                ("sum_agree", C.c_int64), ("sum_abs_dev", C.c_int64), ("reserved", C.c_int64)]
+
+
 class Foothold(C.Structure):
     """ssd_foothold: one surface's cells (TG_OUT / TG_FREE / TG_OCCUPIED / TG_UNSEEN) and the best free rectangle on it"""
     _fields_ = [("state", C.c_uint8 * TG_COLS * TG_ROWS), ("n_free", C.c_int32), ("n_occupied", C.c_int32), ("n_unseen", C.c_int32),
@@ -361,6 +377,8 @@ EXPORTS = [
     "ssd_get_stair_map_time", "ssd_process_host_stair_map", "ssd_process_host_cameras_stair_map",
     "ssd_stair_pose_host", "ssd_stair_pose_add", "ssd_stair_pose_solve", "ssd_enqueue_stair_pose", "ssd_fetch_stair_pose_moments",
     "ssd_fetch_stair_pose", "ssd_get_stair_pose_time", "ssd_process_host_stair_pose",
+    "ssd_depth_fuse_default_rule", "ssd_depth_fuse_host", "ssd_enqueue_depth_fuse", "ssd_fetch_depth_fuse", "ssd_get_depth_fuse_time",
+    "ssd_process_depth_host_fused",
 ]
 # libssd_source.so — the frame source standing in for the camera (include/ssd_source.h)
 SOURCE_EXPORTS = [
@@ -504,6 +522,12 @@ def lib():
     L.ssd_fetch_stair_pose_moments.argtypes = [vp, C.POINTER(StairPoseMoments), i32, vp]
     L.ssd_fetch_stair_pose.argtypes = [vp, C.POINTER(StairPose), i32, C.c_double, vp]
     L.ssd_get_stair_pose_time.argtypes = [vp, C.POINTER(C.c_float)]
+    L.ssd_depth_fuse_default_rule.argtypes = [i32, C.POINTER(FuseRule)]
+    L.ssd_depth_fuse_host.argtypes = [i32, i32, vp, sz, i32, C.POINTER(FuseRule), vp, vp, C.POINTER(FuseStats)]
+    L.ssd_enqueue_depth_fuse.argtypes = [vp, vp, sz, i32, vp, i32, i32, C.POINTER(FuseRule), vp, sz, vp, sz]
+    L.ssd_fetch_depth_fuse.argtypes = [vp, C.POINTER(FuseStats), i32, vp]
+    L.ssd_get_depth_fuse_time.argtypes = [vp, C.POINTER(C.c_float)]
+    L.ssd_process_depth_host_fused.argtypes = [vp, vp, i32, i32, C.POINTER(FuseRule), C.POINTER(FrameResult), vp, C.POINTER(FuseStats)]
     L.ssd_process_host_stair_pose.argtypes = [vp, vp, i32, i32, C.POINTER(StairPoseTarget), i32, C.POINTER(C.c_uint16), C.POINTER(StairPoseRule), i32,
                                               C.c_double, C.POINTER(StairPoseMoments), C.POINTER(StairPose)]
     L.ssd_enqueue_cameras_surface_refit_folded.argtypes = [vp, vp, sz, i32, vp, i32, vp, i32, C.c_double, C.c_double, i32, vp]
@@ -945,6 +969,28 @@ def stair_pose_solve(moments, target, min_points=200, observable=SP_OBSERVABLE):
     out = StairPose()
     _check(lib().ssd_stair_pose_solve(C.byref(moments), C.byref(target), int(min_points), float(observable), C.byref(out)))
     return out
+
+
+def depth_fuse_default_rule(n):
+    """ssd_depth_fuse_default_rule: min_valid = min_agree = (n + 1) // 2, tol = FUSE_TOL"""
+    rule = FuseRule()
+    _check(lib().ssd_depth_fuse_default_rule(int(n), C.byref(rule)))
+    return rule
+
+
+def depth_fuse_host(frames, rule=None, support=False, stride_bytes=None):
+    """ssd_depth_fuse_host: ONE group of depth frames, uint16 [n, H, W] (any strides along n that are a multiple of 2 bytes and hold a
+    frame), -> (fused uint16 [H, W], FuseStats), with support=True (fused, FuseStats, support uint8 [H, W]).  rule None: the defaults"""
+    a = frames if isinstance(frames, np.ndarray) else np.asarray(frames)
+    if a.dtype != np.uint16 or a.ndim != 3 or not a[0].flags.c_contiguous:
+        raise SsdError("depth_fuse_host: uint16 [n, H, W] with contiguous frames expected")
+    n, H, W = a.shape
+    stride = int(stride_bytes) if stride_bytes is not None else (a.strides[0] if n > 1 else H * W * 2)
+    out, stats = np.zeros((H, W), np.uint16), FuseStats()
+    sup = np.zeros((H, W), np.uint8) if support else None
+    _check(lib().ssd_depth_fuse_host(W, H, a.ctypes.data_as(C.c_void_p), stride, n, None if rule is None else C.byref(rule),
+                                     out.ctypes.data_as(C.c_void_p), None if sup is None else sup.ctypes.data_as(C.c_void_p), C.byref(stats)))
+    return (out, stats, sup) if support else (out, stats)
 
 
 def riser_fit_solve(moments, risers, cal, min_points=100):
@@ -1495,6 +1541,47 @@ class Detector:
         self._pose_targets = nt
         poses = [StairPose.from_buffer_copy(out[i]) for i in range(nt)]
         return (poses, [StairPoseMoments.from_buffer_copy(r) for r in recs]) if moments else poses
+
+    # ---- depth fusion: one trimmed-median frame from n frames of a still camera (include/ssd_hip.h)
+    def enqueue_depth_fuse(self, d_ptr, nframes, n, d_out, hop=None, rule=None, d_support=None, stride_bytes=None, out_stride_bytes=None,
+                           support_stride_bytes=None, stream=None):
+        """ssd_enqueue_depth_fuse: groups of n of the nframes uint16 depth frames at d_ptr, hop frames apart (None: n, disjoint groups),
+        fused on the caller's stream: frame g to d_out + g * out_stride_bytes, its support bytes (d_support None: none) likewise.
+        -> the number of groups.  A depth-input enqueue on the same stream may read d_out with no host wait in between."""
+        frame = self.cfg.width * self.cfg.height * 2
+        hop = int(n) if hop is None else int(hop)
+        _check(lib().ssd_enqueue_depth_fuse(self._h, C.c_void_p(d_ptr), stride_bytes or frame, int(nframes), C.c_void_p(stream or 0), int(n), hop,
+                                            None if rule is None else C.byref(rule), C.c_void_p(d_out), out_stride_bytes or frame,
+                                            C.c_void_p(d_support or 0), support_stride_bytes or frame // 2))
+        return (int(nframes) - int(n)) // hop + 1
+
+    def fetch_depth_fuse(self, ngroups, stream=None):
+        """ssd_fetch_depth_fuse: waits for the last enqueue_depth_fuse -> list of FuseStats (independent copies), one per group"""
+        out = (FuseStats * ngroups)()
+        _check(lib().ssd_fetch_depth_fuse(self._h, out, ngroups, C.c_void_p(stream or 0)))
+        return [FuseStats.from_buffer_copy(r) for r in out]
+
+    def depth_fuse_time_ms(self):
+        """the device time of the last fusion pass, its zeroing and its records' copy included (0 unless set_timing was on)"""
+        return _time_ms(lib().ssd_get_depth_fuse_time, self._h)
+
+    def process_depth_host_fused(self, depth, n, rule=None, fused=False, stats=False):
+        """ssd_process_depth_host_fused: depth frames on the host, uint16 [k * n, H, W]: every n of them fused on the device and the
+        fused frame detected -> list of k FrameResult; with fused=True / stats=True a tuple with the fused frames (uint16 [k, H, W])
+        and / or the list of k FuseStats behind it"""
+        a, total, _ = self._frames_arg("process_depth_host_fused", depth, True)
+        k = total // int(n) if int(n) > 0 else 0
+        res = (FrameResult * max(k, 1))()
+        f = np.zeros((max(k, 1), self.cfg.height, self.cfg.width), np.uint16) if fused else None
+        st = (FuseStats * max(k, 1))() if stats else None
+        _check(lib().ssd_process_depth_host_fused(self._h, a.ctypes.data_as(C.c_void_p), total, int(n), None if rule is None else C.byref(rule), res,
+                                                  None if f is None else f.ctypes.data_as(C.c_void_p), st))
+        out = [list(res)[:k]]
+        if fused:
+            out.append(f[:k])
+        if stats:
+            out.append([FuseStats.from_buffer_copy(st[i]) for i in range(k)])
+        return out[0] if len(out) == 1 else tuple(out)
 
     def locate_camera(self, frames, prior, stair_map, passes=3, rule=None, min_points=200, observable=SP_OBSERVABLE, depth=False):
         """process_host_stair_pose `passes` times over the same frames of ONE camera, each pass starting from the calibration the pass

@@ -13,6 +13,7 @@
 #include "ssd_prexy.h"
 #include "ssd_ground.h"
 #include "ssd_pose.h"
+#include "ssd_fuse.h"
 #include "ssd_refit.h"
 #include "ssd_clearance.h"
 #include "ssd_treadgrid.h"
@@ -99,6 +100,7 @@ void tuning_from_env(ssd_tuning &t)
   t.winShift = env_int("SSD_WIN_SHIFT", 0);
   t.winShiftGround = env_int("SSD_WIN_SHIFT_G", 0);
   t.recordPad = env_int("SSD_RECORD_PAD", t.recordPad);
+  t.fuseGroupFastest = env_int("SSD_FUSE_GROUP_FASTEST", t.fuseGroupFastest);
 }
 #endif
 
@@ -3093,6 +3095,170 @@ int ssd_process_host_stair_pose(ssd_handle *h, const void *frames, int nframes, 
   for(int t = 0; t < ntargets && !rc; t++)
     rc = ssd_stair_pose_solve(&folds[static_cast<size_t>(t)], targets + t, min_points, observable, out + t);
   return rc;
+}
+
+/* ---- depth fusion: one trimmed-median frame from n frames of a still camera (include/ssd_hip.h) ---------------- */
+
+/* the group records of the pass, on its first call */
+static int depth_fuse_prepare(ssd_handle *h)
+{
+  if(h->dFuse)
+    return SSD_OK;
+  const size_t recBytes = sizeof(ssd_depth_fuse_stats) * static_cast<size_t>(h->F);
+  DeviceBuf<ssd_depth_fuse_stats> d;
+  PinnedBuf<ssd_depth_fuse_stats> hh;
+  hipError_t e = d.alloc(recBytes, &h->bytes);
+  if(e == hipSuccess) e = hh.alloc(recBytes, &h->bytes);
+  if(e != hipSuccess)
+    return hip_fail(e, "ssd_enqueue_depth_fuse: its buffers: ");
+  h->dFuse = std::move(d); h->hFuse = std::move(hh);
+  return SSD_OK;
+}
+
+static bool ranges_overlap(const void *a, size_t aBytes, const void *b, size_t bBytes)
+{
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+  return a0 < b0 + bBytes && b0 < a0 + aBytes;
+}
+
+/* the refusals of a fusion call, before anything is launched or copied; *use: the rule to go by, *ngroups: its groups */
+static int check_depth_fuse(const ssd_handle *h, const std::string &me, const void *d_frames, size_t frame_stride_bytes, int nframes, int n, int hop,
+                            const ssd_depth_fuse_rule *rule, const void *d_out, size_t out_stride_bytes, const uint8_t *d_support,
+                            size_t support_stride_bytes, ssd_depth_fuse_rule *use, int *ngroups)
+{
+  if(!h || !d_frames || !d_out)
+    return fail(SSD_E_ARG, me + ": null argument");
+  int rc = check_fuse_rule(me, n, rule, use);
+  if(rc) return rc;
+  if(hop < 1 || hop > n)
+    return fail(SSD_E_ARG, me + ": hop must lie in 1 .. n");
+  if(nframes < n || nframes > h->F)
+    return fail(SSD_E_ARG, me + ": nframes must lie in n .. max_frames_per_batch");
+  const int groups = (nframes - n) / hop + 1;
+  if(groups > h->F)
+    return fail(SSD_E_ARG, me + ": more groups than max_frames_per_batch");
+  rc = check_device_frames(h, me.c_str(), d_frames, frame_stride_bytes, nframes, SSD_INPUT_DEPTH16);
+  if(!rc) rc = check_device_frames(h, me.c_str(), d_out, out_stride_bytes, groups, SSD_INPUT_DEPTH16);
+  if(rc) return rc;
+  const size_t nPoints = static_cast<size_t>(h->P.nPoints), frameBytes = nPoints * 2;
+  if(d_support && groups > 1 && support_stride_bytes < nPoints)
+    return fail(SSD_E_ARG, me + ": the support stride must hold a frame's bytes");
+  const size_t inBytes = static_cast<size_t>(nframes - 1) * frame_stride_bytes + frameBytes;
+  if(ranges_overlap(d_frames, inBytes, d_out, static_cast<size_t>(groups - 1) * out_stride_bytes + frameBytes) ||
+     (d_support && ranges_overlap(d_frames, inBytes, d_support, static_cast<size_t>(groups - 1) * support_stride_bytes + nPoints)))
+    return fail(SSD_E_ARG, me + ": the output and the support must not overlap the frames");
+  *ngroups = groups;
+  return SSD_OK;
+}
+
+/* arguments checked by the callers */
+static int enqueue_depth_fuse_impl(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, hipStream_t s, int n, int hop, int ngroups,
+                                   const ssd_depth_fuse_rule &rule, void *d_out, size_t out_stride_bytes, uint8_t *d_support, size_t support_stride_bytes)
+{
+  HIP_TRY(hipSetDevice(h->device));
+  int rc = depth_fuse_prepare(h);
+  if(rc) return rc;
+  const bool timing = h->timing;
+  rc = pass_open(h->fusePass, s, timing, "ssd_enqueue_depth_fuse");   /* another stream: behind the previous call */
+  if(!rc) rc = pass_start(h->fusePass, s, timing);
+  if(rc) return rc;
+  const size_t recBytes = sizeof(ssd_depth_fuse_stats) * static_cast<size_t>(ngroups);
+  HIP_TRY(hipMemsetAsync(h->dFuse, 0, recBytes, s));
+  launch_depth_fuse(d_frames, frame_stride_bytes, h->P.nPoints, n, hop, ngroups, rule, d_out, out_stride_bytes, d_support, support_stride_bytes,
+                    h->dFuse, h->tune.fuseGroupFastest != 0, s);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(h->hFuse, h->dFuse, recBytes, hipMemcpyDeviceToHost, s));
+  h->fuseGroups = ngroups;
+  return pass_close(h->fusePass, s, timing);
+}
+
+int ssd_enqueue_depth_fuse(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream, int n, int hop,
+                           const ssd_depth_fuse_rule *rule, void *d_out, size_t out_stride_bytes, uint8_t *d_support, size_t support_stride_bytes)
+{
+  ssd_depth_fuse_rule R;
+  int ngroups = 0;
+  const int rc = check_depth_fuse(h, "ssd_enqueue_depth_fuse", d_frames, frame_stride_bytes, nframes, n, hop, rule, d_out, out_stride_bytes, d_support,
+                                  support_stride_bytes, &R, &ngroups);
+  if(rc) return rc;
+  return enqueue_depth_fuse_impl(h, d_frames, frame_stride_bytes, static_cast<hipStream_t>(stream), n, hop, ngroups, R, d_out, out_stride_bytes,
+                                 d_support, support_stride_bytes);
+}
+
+int ssd_fetch_depth_fuse(ssd_handle *h, ssd_depth_fuse_stats *out, int ngroups, void *)
+{
+  if(!h || !out)
+    return fail(SSD_E_ARG, "ssd_fetch_depth_fuse: null argument");
+  if(!h->fusePass.haveLast || ngroups < 1 || ngroups > h->fuseGroups)
+    return fail(SSD_E_ARG, "ssd_fetch_depth_fuse: ngroups must be 1..the groups of the last ssd_enqueue_depth_fuse");
+  const int wait = pass_wait(h, &ssd_handle::fusePass, "ssd_fetch_depth_fuse", "");
+  if(wait) return wait;
+  std::memcpy(out, h->hFuse, sizeof(ssd_depth_fuse_stats) * static_cast<size_t>(ngroups));
+  return SSD_OK;
+}
+
+int ssd_get_depth_fuse_time(ssd_handle *h, float *ms)
+{
+  return pass_time(h, &ssd_handle::fusePass, "ssd_get_depth_fuse_time", "ssd_enqueue_depth_fuse", ms);
+}
+
+/* Host-fed, disjoint groups.  The stream arrangement is that of the other stand-alone frame passes (process_host_frames): slice c's copy
+ * goes out, slice c - 1 is collected - its results, which lie behind its detection and so behind its fusion, then its records and its
+ * fused frames -, and only then slice c is fused and detected.  So ONE buffer of fused frames and the pass's one set of records do: what
+ * overlaps is a slice's copy with the slice before it, not two slices' kernels. */
+int ssd_process_depth_host_fused(ssd_handle *h, const uint16_t *depth, int nframes, int n, const ssd_depth_fuse_rule *rule,
+                                 ssd_frame_result *results, uint16_t *fused, ssd_depth_fuse_stats *stats)
+{
+  const std::string me("ssd_process_depth_host_fused");
+  int rc = check_host_batch(h, me.c_str(), h && depth && results, nframes, SSD_INPUT_DEPTH16, kHandleCal);
+  ssd_depth_fuse_rule R;
+  if(!rc) rc = check_fuse_rule(me, n, rule, &R);
+  if(rc) return rc;
+  if(n > h->F || nframes % n != 0)
+    return fail(SSD_E_ARG, me + ": n must not exceed max_frames_per_batch and nframes must be a multiple of n");
+  if(h->P.W % 4 != 0)
+    return fail(SSD_E_ARG, me + ": width must be a multiple of 4 (ssd_enqueue_depth)");
+  HIP_TRY(hipSetDevice(h->device));
+  SliceFeed feed{ h, host_frames(h, SSD_INPUT_DEPTH16, kForGroundFit), depth, nframes };
+  rc = feed.prepare();
+  if(rc) return rc;
+  feed.slice = feed.slice / n * n;                                 /* a whole number of groups (n <= 16 <= a slice's frames, or n <= F) */
+  if(feed.slice < n)
+    return fail(SSD_E_ARG, me + ": n exceeds a slice's frames");
+  const size_t frameBytes = static_cast<size_t>(h->P.nPoints) * 2, fusedStride = feed.f.devFrameBytes;
+  const size_t stageBytes = static_cast<size_t>(feed.slice / n) * fusedStride;
+  if(h->fuseStageCap < stageBytes)
+  {
+    for(int k = 0; k < h->depth; k++)                                /* its readers are this handle's detections */
+      if(h->lane[k].haveLast)
+        HIP_TRY(hipEventSynchronize(h->lane[k].done));
+    h->fuseStage.reset();
+    h->fuseStageCap = 0;
+    const hipError_t e = h->fuseStage.alloc(stageBytes);
+    if(e != hipSuccess)
+      return hip_fail(e, "ssd_process_depth_host_fused: the fused frames' buffer: ");
+    h->fuseStageCap = stageBytes;
+  }
+  return process_host_frames(h, feed,
+    [&](const void *buf, int, int cnt)
+    {
+      const int groups = cnt / n;
+      int r = enqueue_depth_fuse_impl(h, buf, feed.f.devFrameBytes, h->ingestCompute, n, n, groups, R, h->fuseStage, fusedStride, nullptr, 0);
+      if(!r) r = enqueue_impl(h, h->fuseStage, fusedStride, groups, h->ingestCompute, SSD_STAGE_ALL, true);
+      return r;
+    },
+    [&](int at, int cnt)
+    {
+      const int g0 = at / n, groups = cnt / n;
+      int r = ssd_fetch_back(h, results + g0, groups, 0);
+      if(!r && stats) r = ssd_fetch_depth_fuse(h, stats + g0, groups, nullptr);
+      if(!r && fused)
+      {
+        HIP_TRY(hipMemcpy2DAsync(reinterpret_cast<unsigned char *>(fused) + static_cast<size_t>(g0) * frameBytes, frameBytes, h->fuseStage, fusedStride,
+                                 frameBytes, static_cast<size_t>(groups), hipMemcpyDeviceToHost, h->ingestCompute));
+        HIP_TRY(hipStreamSynchronize(h->ingestCompute));
+      }
+      return r;
+    });
 }
 
 /* pinned host memory for frames (DMA without a staging copy) */

@@ -17,7 +17,7 @@ namespace ssd { struct PoseTarget; }           /* ssd_pose.h */
 /* Launch-geometry constants of a handle.  The product uses the compiled defaults below (each one measured: ssd_capi.hip,
  * choose_chunk / enqueue_impl).  Only a tools build (make EXTRA=-DSSD_TUNING OUT=../lib_tuning, tools/exp*.sh) reads
  * overrides from the environment (SSD_CHUNK_POINTS, SSD_TARGET_BLOCKS, SSD_K1_BLOCKS_PER_FRAME, SSD_K24_MIN_BLOCKS,
- * SSD_K24_TALL_BLOCKS, SSD_K2_CHUNK_TILES, SSD_K4_CHUNK_TILES, SSD_WIN_SHIFT, SSD_WIN_SHIFT_G), and only once, in ssd_create:
+ * SSD_K24_TALL_BLOCKS, SSD_K2_CHUNK_TILES, SSD_K4_CHUNK_TILES, SSD_WIN_SHIFT, SSD_WIN_SHIFT_G, SSD_FUSE_GROUP_FASTEST), and only once, in ssd_create:
  * no entry point of the product library calls getenv. */
 struct ssd_tuning
 {
@@ -28,6 +28,7 @@ struct ssd_tuning
   int k2ChunkTiles = 32, k4ChunkTiles = 16;
   int winShift = 0, winShiftGround = 0;     /* > 0: shape of the waves' LDS image windows, forced */
   int recordPad = 0;              /* cell records per frame added to the stride between the frames' record arrays */
+  int fuseGroupFastest = 0;       /* k_depth_fuse's grid: 0 = neighbouring blocks take neighbouring chunks of one group, 1 = the same chunk of neighbouring groups */
 };
 
 /* The events around an optional pass (k_labels, k_riser_labels, k_surface_moments) of the timed enqueues: a ring of SSD_TIMING_SLOTS pairs,
@@ -246,6 +247,16 @@ struct ssd_handle
   int poseFrames = 0;                       /* frames of the last call */
   std::vector<ssd_stair_pose_target> poseTargets;   /* its targets and its index: what ssd_fetch_stair_pose folds and solves against */
   std::vector<int> poseIndex;
+  /* the depth fusion (ssd_enqueue_depth_fuse & co.): a record per group (F, on the device and pinned), made on the
+   * first call and counted as workspace.  One set, used in call order like the ground fit's; nothing of the lanes is touched */
+  ssd::DeviceBuf<ssd_depth_fuse_stats> dFuse;
+  ssd::PinnedBuf<ssd_depth_fuse_stats> hFuse;   /* pinned: a call's last step copies its records here */
+  ssd_ordered_pass fusePass;
+  int fuseGroups = 0;                       /* groups of the last call */
+  /* ssd_process_depth_host_fused: a slice's fused frames, which its detection reads; made on first use, staging like gridStage, not
+   * counted as workspace */
+  ssd::DeviceBuf<unsigned char> fuseStage;
+  size_t fuseStageCap = 0;
 };
 
 /* The single pass's planes - dPlaneImg and dFallback of every workspace and the pinned hFallback, zeroed - for ALL workspaces of the

@@ -8,6 +8,7 @@
  */
 #include "ssd_host.h"
 #include "ssd_pose.h"
+#include "ssd_fuse.h"
 #include "ssd_refit.h"
 #include "ssd_clearance.h"
 #include "ssd_treadgrid.h"
@@ -1487,6 +1488,90 @@ int pose_fold_frames(const char *who, const ssd_stair_pose_moments *records, con
     if(!pose_fold(records[i], folds[static_cast<size_t>(index[i])]))
       return fail(SSD_E_CAP, std::string(who) + ": the fold of target " + std::to_string(index[i]) + " would leave int64 at frame " + std::to_string(i));
   }
+  return SSD_OK;
+}
+
+/* ---- depth fusion: one trimmed-median frame from n frames of a still camera (include/ssd_hip.h) ---------------- */
+
+int ssd_depth_fuse_default_rule(int n, ssd_depth_fuse_rule *rule)
+{
+  if(!rule || n < 1 || n > SSD_FUSE_MAX_FRAMES)
+    return fail(SSD_E_ARG, "ssd_depth_fuse_default_rule: null rule, or n outside 1 .. SSD_FUSE_MAX_FRAMES");
+  rule->min_valid = rule->min_agree = (n + 1) / 2;
+  rule->tol = SSD_FUSE_TOL;
+  rule->reserved = 0;
+  return SSD_OK;
+}
+
+/* the refusals about n and the rule that the host statement, the enqueue and the host-fed form share; *use: the rule to go by (the
+ * defaults for n where the caller gave none) */
+int check_fuse_rule(const std::string &me, int n, const ssd_depth_fuse_rule *rule, ssd_depth_fuse_rule *use)
+{
+  if(n < 1 || n > SSD_FUSE_MAX_FRAMES)
+    return fail(SSD_E_ARG, me + ": n must lie in 1 .. SSD_FUSE_MAX_FRAMES");
+  if(rule)
+    *use = *rule;
+  else
+    ssd_depth_fuse_default_rule(n, use);
+  if(!fuse_rule_ok(n, *use))
+    return fail(SSD_E_ARG, me + ": the rule must hold 1 <= min_valid <= n, 1 <= min_agree <= n, 0 <= tol <= 65535");
+  return SSD_OK;
+}
+
+int ssd_depth_fuse_host(int width, int height, const uint16_t *frames, size_t frame_stride_bytes, int n, const ssd_depth_fuse_rule *rule,
+                        uint16_t *out, uint8_t *support, ssd_depth_fuse_stats *stats)
+{
+  const std::string me("ssd_depth_fuse_host");
+  if(!frames || !out || !stats || width <= 0 || height <= 0)
+    return fail(SSD_E_ARG, me + ": bad argument");
+  ssd_depth_fuse_rule R;
+  const int rc = check_fuse_rule(me, n, rule, &R);
+  if(rc) return rc;
+  const size_t nPoints = static_cast<size_t>(width) * height;
+  if(frame_stride_bytes % 2 != 0 || (n > 1 && frame_stride_bytes < nPoints * 2))
+    return fail(SSD_E_ARG, me + ": frames must be aligned to their element and the stride must hold a frame");
+  int64_t rec[kFuseWords] = {};
+  const unsigned char *base = reinterpret_cast<const unsigned char *>(frames);
+  for(size_t p = 0; p < nPoints; p++)
+  {
+    uint32_t d[SSD_FUSE_MAX_FRAMES], sorted[SSD_FUSE_MAX_FRAMES];
+    uint32_t m = 0;
+    for(int j = 0; j < n; j++)
+    {
+      uint16_t v;
+      std::memcpy(&v, base + static_cast<size_t>(j) * frame_stride_bytes + 2 * p, sizeof(v));
+      d[j] = v;
+      if(v != 0)
+        sorted[m++] = v;
+    }
+    uint32_t c = 0, s = 0, med = 0;
+    if(m > 0)
+    {
+      std::sort(sorted, sorted + m);
+      med = sorted[fuse_median_index(static_cast<int>(m))];
+      for(int j = 0; j < n; j++)
+        if(fuse_agrees(d[j], med, static_cast<uint32_t>(R.tol)))
+        {
+          c++;
+          s += d[j];
+        }
+    }
+    int cls;
+    const uint32_t o = fuse_output(m, c, s, R, cls);
+    out[p] = static_cast<uint16_t>(o);
+    if(support)
+      support[p] = cls == kFuseNFused ? static_cast<uint8_t>(c) : 0;
+    rec[cls]++;
+    rec[kFuseSumValid] += m;
+    if(cls == kFuseNFused)
+    {
+      rec[kFuseSumAgree] += c;
+      for(int j = 0; j < n; j++)
+        if(fuse_agrees(d[j], med, static_cast<uint32_t>(R.tol)))
+          rec[kFuseSumAbsDev] += fuse_dev(d[j], o);
+    }
+  }
+  std::memcpy(stats, rec, sizeof(*stats));
   return SSD_OK;
 }
 

@@ -162,3 +162,51 @@ void launch_ground_moments(const void *frames, size_t strideBytes, int W, int H,
 
 /* k_stair_pose stands on this kernel's skeleton and shares its translation unit */
 #include "ssd_kernels_pose.hip"
+
+/* k_depth_fuse, the third stand-alone frame pass: its body in a header, its launcher here */
+#include "ssd_k_fuse.h"
+
+namespace ssd
+{
+
+template<int NP>
+static void launch_depth_fuse_sized(const FuseArgs &A, bool wide, hipStream_t s)
+{
+  const dim3 grid(static_cast<unsigned int>(A.blocksPerGroup) * A.ngroups), block(kFuseThreads);
+  if(wide)
+    hipLaunchKernelGGL((k_depth_fuse<NP, true>), grid, block, kFuseLds, s, A);
+  else
+    hipLaunchKernelGGL((k_depth_fuse<NP, false>), grid, block, kFuseLds, s, A);
+}
+
+void launch_depth_fuse(const void *frames, size_t strideBytes, int nPoints, int n, int hop, int ngroups, const ssd_depth_fuse_rule &rule,
+                       void *out, size_t outStride, uint8_t *support, size_t supStride, ssd_depth_fuse_stats *stats, bool groupFastest,
+                       hipStream_t s)
+{
+  /* the wide body: 128-bit loads and stores of eight pixels, 64-bit stores of their support */
+  const bool wide = reinterpret_cast<size_t>(frames) % 16 == 0 && strideBytes % 16 == 0 && reinterpret_cast<size_t>(out) % 16 == 0 &&
+                    outStride % 16 == 0 && (!support || (reinterpret_cast<size_t>(support) % 8 == 0 && supStride % 8 == 0));
+  /* blocks per group: one step of the loop per lane (a step holds n loads in flight) until the grid passes 32768 blocks */
+  const int work = (nPoints + kFusePerLane * kFuseThreads - 1) / (kFusePerLane * kFuseThreads);
+  const long long all = static_cast<long long>(work) * ngroups;
+  const int steps = static_cast<int>((all + 32767) / 32768);
+  int blocks = (work + steps - 1) / steps;
+  if(blocks < 1) blocks = 1;
+  FuseArgs A;
+  A.frames = static_cast<const unsigned char *>(frames);
+  A.strideBytes = strideBytes;
+  A.out = static_cast<unsigned char *>(out);
+  A.outStride = outStride;
+  A.support = support;
+  A.supStride = supStride;
+  A.stats = reinterpret_cast<unsigned long long *>(stats);
+  A.nPoints = nPoints; A.n = n; A.hop = hop; A.ngroups = ngroups; A.blocksPerGroup = blocks; A.groupFastest = groupFastest ? 1 : 0;
+  A.rule = rule;
+  if(n > 8) launch_depth_fuse_sized<16>(A, wide, s);
+  else if(n > 4) launch_depth_fuse_sized<8>(A, wide, s);
+  else if(n > 2) launch_depth_fuse_sized<4>(A, wide, s);
+  else if(n > 1) launch_depth_fuse_sized<2>(A, wide, s);
+  else launch_depth_fuse_sized<1>(A, wide, s);
+}
+
+} // namespace ssd
