@@ -1283,6 +1283,67 @@ int ssd_process_depth_host_fused(ssd_handle *h, const uint16_t *depth, int nfram
                                  ssd_frame_result *results /* nframes / n */, uint16_t *fused /* may be NULL */,
                                  ssd_depth_fuse_stats *stats /* may be NULL */);
 
+/* ---- depth edge filter: mixed and lone pixels out of ONE frame, from its spatial neighbours ---------------------
+ * A frame is width x height 16-bit depth samples.  For the pixel with sample d, its neighbours are the up to eight pixels around it that
+ * lie inside the frame; nothing outside the frame exists.  The decision is taken from the INPUT frame alone, never from another pixel's
+ * output: the result does not depend on order.  Integers only:
+ *   t(d)  = min(65535, tol + ((d * slope) >> 12))                       (32 bits)
+ *   near(q): q exists, d_q != 0, |d_q - d| <= t(d)                      (the difference in 32 bits: it cannot wrap)
+ *   c     = the number of near neighbours, 0 .. 8
+ *   bridged: for one of the four opposite pairs (W/E, N/S, NW/SE, NE/SW) whose two pixels both exist and are valid (not 0),
+ *            (d_a + t < d and d + t < d_b) or (d_b + t < d and d + t < d_a)
+ * The classes, tested in this order: EMPTY d == 0 -> 0; LONE c < min_support -> 0; BRIDGE bridge != 0 and bridged -> 0; otherwise KEPT
+ * -> d.  So a pixel that lies more than t from valid pixels on both sides of it, on opposite sides in depth, always goes (a mixed pixel
+ * at a depth discontinuity), and a surface whose step from pixel to pixel is at most t loses nothing to BRIDGE.  slope lets t grow with
+ * the depth: a tread seen at a grazing angle steps from image row to image row in proportion to its depth.  The optional class byte is
+ * SSD_EDGE_KEPT / _EMPTY / _LONE / _BRIDGE; per frame one exact record whose four counts add up to the pixel count. */
+#define SSD_EDGE_KEPT 0
+#define SSD_EDGE_EMPTY 1
+#define SSD_EDGE_LONE 2
+#define SSD_EDGE_BRIDGE 3
+#define SSD_EDGE_SLOPE 0             /* the default slope, fixed by measurement (profiles/depth_edges_accuracy.txt) */
+typedef struct
+{
+  int32_t min_support;          /* 0 .. 8; 0 switches the LONE test off */
+  int32_t bridge;               /* 0 switches the BRIDGE test off */
+  int32_t tol;                  /* 0 .. 65535, raw units */
+  int32_t slope;                /* 0 .. 4096, in 1 / 4096 of the pixel's own depth */
+} ssd_depth_edge_rule;
+typedef struct
+{
+  int64_t n_kept, n_empty, n_lone, n_bridge;
+  int64_t sum_support;          /* the sum of c over kept pixels */
+  int64_t reserved[3];
+} ssd_depth_edge_stats;         /* 64 bytes */
+/* host only: min_support = 2, bridge = 1, tol = SSD_FUSE_TOL, slope = SSD_EDGE_SLOPE.  SSD_E_ARG: null */
+int ssd_depth_edge_default_rule(ssd_depth_edge_rule *rule);
+/* host only, no GPU needed: the rule over ONE packed frame.  rule NULL: the defaults; out: width * height values; cls (may be NULL): as
+ * many bytes; stats: the frame's record.  frame and out must not overlap.  SSD_E_ARG: a null pointer, width or height not positive, a
+ * rule outside 0 <= min_support <= 8, 0 <= tol <= 65535, 0 <= slope <= 4096. */
+int ssd_depth_edges_host(int width, int height, const uint16_t *frame, const ssd_depth_edge_rule *rule, uint16_t *out,
+                         uint8_t *cls /* may be NULL */, ssd_depth_edge_stats *stats);
+/* The pass (k_depth_edges) over depth frames resident in device memory, on the caller's stream, in order, without synchronising: the
+ * contract of ssd_enqueue_depth_fuse - no detection workspace, nothing ssd_fetch* reads is touched, no intrinsics or calibration needed;
+ * calls on different streams run in call order.  Filtered frame i goes to d_out + i * out_stride_bytes, its class bytes (d_cls may be
+ * NULL) to d_cls + i * cls_stride_bytes, byte for byte ssd_depth_edges_host's.  A depth-input enqueue on the same stream may read d_out
+ * with no host wait in between, and d_frames may be what ssd_enqueue_depth_fuse wrote on that stream.  The records
+ * (max_frames_per_batch on the device and pinned) are made on the first call and counted in ssd_workspace_bytes from then on.
+ * SSD_E_ARG before anything is launched or copied: a null handle, input or output; nframes outside 1 .. max_frames_per_batch; a rule
+ * out of range; frames or output off 2-byte alignment or a stride that holds no frame; a class stride below a frame's bytes (width *
+ * height) with more than one frame; ANY overlap of the output or class range with the input range (a stencil in place is a race). */
+int ssd_enqueue_depth_edges(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream,
+                            const ssd_depth_edge_rule *rule /* NULL: the defaults */, void *d_out, size_t out_stride_bytes,
+                            uint8_t *d_cls /* may be NULL */, size_t cls_stride_bytes);
+/* waits for the last ssd_enqueue_depth_edges and hands over its frames' records; nframes <= its */
+int ssd_fetch_depth_edges(ssd_handle *h, ssd_depth_edge_stats *out, int nframes, void *stream);
+/* the device time of the last pass, the zeroing in front of it and the copy of its records behind it included (0 when timing was off for it) */
+int ssd_get_depth_edges_time(ssd_handle *h, float *ms);
+/* depth frames in host memory (pinned or pageable): every frame is filtered on the device and the filtered frame is detected, slice by
+ * slice through the staging buffers of ssd_process_depth_host.  results: nframes records, byte for byte ssd_process_depth_host's over
+ * ssd_depth_edges_host's output; filtered (may be NULL): nframes packed frames; stats (may be NULL): as many records. */
+int ssd_process_depth_host_edges(ssd_handle *h, const uint16_t *depth, int nframes, const ssd_depth_edge_rule *rule,
+                                 ssd_frame_result *results, uint16_t *filtered /* may be NULL */, ssd_depth_edge_stats *stats /* may be NULL */);
+
 /* stage selector for profiling / roofline measurement: runs only the chosen stage(s) of the pipeline */
 #define SSD_STAGE_HIST 1       /* K1: transform + crop + bin + histogram */
 #define SSD_STAGE_PEAKS 2

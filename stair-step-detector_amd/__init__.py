@@ -285,6 +285,22 @@ class FuseStats(C.Structure):
                 ("sum_agree", C.c_int64), ("sum_abs_dev", C.c_int64), ("reserved", C.c_int64)]
 
 
+EDGE_KEPT, EDGE_EMPTY, EDGE_LONE, EDGE_BRIDGE, EDGE_SLOPE = 0, 1, 2, 3, 0   # SSD_EDGE_*
+
+
+class EdgeRule(C.Structure):
+    """ssd_depth_edge_rule: how many of a pixel's eight neighbours must be near it (min_support; 0: no LONE test), whether a pixel between
+    two opposite neighbours in depth goes (bridge), and how far a neighbour may lie to be near: tol + ((d * slope) >> 12) raw units"""
+    _fields_ = [("min_support", C.c_int32), ("bridge", C.c_int32), ("tol", C.c_int32), ("slope", C.c_int32)]
+
+
+class EdgeStats(C.Structure):
+    """ssd_depth_edge_stats: a frame's record - its pixels by class (they add up to the pixel count) and the sum of the near neighbours'
+    count over the kept ones"""
+    _fields_ = [("n_kept", C.c_int64), ("n_empty", C.c_int64), ("n_lone", C.c_int64), ("n_bridge", C.c_int64), ("sum_support", C.c_int64),
+                ("reserved", C.c_int64 * 3)]
+
+
 class Foothold(C.Structure):
     """ssd_foothold: one surface's cells (TG_OUT / TG_FREE / TG_OCCUPIED / TG_UNSEEN) and the best free rectangle on it"""
     _fields_ = [("state", C.c_uint8 * TG_COLS * TG_ROWS), ("n_free", C.c_int32), ("n_occupied", C.c_int32), ("n_unseen", C.c_int32),
@@ -379,6 +395,8 @@ EXPORTS = [
     "ssd_fetch_stair_pose", "ssd_get_stair_pose_time", "ssd_process_host_stair_pose",
     "ssd_depth_fuse_default_rule", "ssd_depth_fuse_host", "ssd_enqueue_depth_fuse", "ssd_fetch_depth_fuse", "ssd_get_depth_fuse_time",
     "ssd_process_depth_host_fused",
+    "ssd_depth_edge_default_rule", "ssd_depth_edges_host", "ssd_enqueue_depth_edges", "ssd_fetch_depth_edges", "ssd_get_depth_edges_time",
+    "ssd_process_depth_host_edges",
 ]
 # libssd_source.so — the frame source standing in for the camera (include/ssd_source.h)
 SOURCE_EXPORTS = [
@@ -528,6 +546,12 @@ def lib():
     L.ssd_fetch_depth_fuse.argtypes = [vp, C.POINTER(FuseStats), i32, vp]
     L.ssd_get_depth_fuse_time.argtypes = [vp, C.POINTER(C.c_float)]
     L.ssd_process_depth_host_fused.argtypes = [vp, vp, i32, i32, C.POINTER(FuseRule), C.POINTER(FrameResult), vp, C.POINTER(FuseStats)]
+    L.ssd_depth_edge_default_rule.argtypes = [C.POINTER(EdgeRule)]
+    L.ssd_depth_edges_host.argtypes = [i32, i32, vp, C.POINTER(EdgeRule), vp, vp, C.POINTER(EdgeStats)]
+    L.ssd_enqueue_depth_edges.argtypes = [vp, vp, sz, i32, vp, C.POINTER(EdgeRule), vp, sz, vp, sz]
+    L.ssd_fetch_depth_edges.argtypes = [vp, C.POINTER(EdgeStats), i32, vp]
+    L.ssd_get_depth_edges_time.argtypes = [vp, C.POINTER(C.c_float)]
+    L.ssd_process_depth_host_edges.argtypes = [vp, vp, i32, C.POINTER(EdgeRule), C.POINTER(FrameResult), vp, C.POINTER(EdgeStats)]
     L.ssd_process_host_stair_pose.argtypes = [vp, vp, i32, i32, C.POINTER(StairPoseTarget), i32, C.POINTER(C.c_uint16), C.POINTER(StairPoseRule), i32,
                                               C.c_double, C.POINTER(StairPoseMoments), C.POINTER(StairPose)]
     L.ssd_enqueue_cameras_surface_refit_folded.argtypes = [vp, vp, sz, i32, vp, i32, vp, i32, C.c_double, C.c_double, i32, vp]
@@ -991,6 +1015,27 @@ def depth_fuse_host(frames, rule=None, support=False, stride_bytes=None):
     _check(lib().ssd_depth_fuse_host(W, H, a.ctypes.data_as(C.c_void_p), stride, n, None if rule is None else C.byref(rule),
                                      out.ctypes.data_as(C.c_void_p), None if sup is None else sup.ctypes.data_as(C.c_void_p), C.byref(stats)))
     return (out, stats, sup) if support else (out, stats)
+
+
+def depth_edges_default_rule():
+    """ssd_depth_edge_default_rule: min_support 2, bridge on, tol = FUSE_TOL, slope = EDGE_SLOPE"""
+    rule = EdgeRule()
+    _check(lib().ssd_depth_edge_default_rule(C.byref(rule)))
+    return rule
+
+
+def depth_edges_host(frame, rule=None, classes=False):
+    """ssd_depth_edges_host: ONE depth frame, uint16 [H, W] -> (filtered uint16 [H, W], EdgeStats), with classes=True (filtered,
+    EdgeStats, classes uint8 [H, W]: EDGE_KEPT / EDGE_EMPTY / EDGE_LONE / EDGE_BRIDGE).  rule None: the defaults"""
+    a = np.ascontiguousarray(frame)
+    if a.dtype != np.uint16 or a.ndim != 2:
+        raise SsdError("depth_edges_host: uint16 [H, W] expected")
+    H, W = a.shape
+    out, stats = np.zeros((H, W), np.uint16), EdgeStats()
+    cls = np.zeros((H, W), np.uint8) if classes else None
+    _check(lib().ssd_depth_edges_host(W, H, a.ctypes.data_as(C.c_void_p), None if rule is None else C.byref(rule), out.ctypes.data_as(C.c_void_p),
+                                      None if cls is None else cls.ctypes.data_as(C.c_void_p), C.byref(stats)))
+    return (out, stats, cls) if classes else (out, stats)
 
 
 def riser_fit_solve(moments, risers, cal, min_points=100):
@@ -1581,6 +1626,45 @@ class Detector:
             out.append(f[:k])
         if stats:
             out.append([FuseStats.from_buffer_copy(st[i]) for i in range(k)])
+        return out[0] if len(out) == 1 else tuple(out)
+
+    # ---- depth edge filter: mixed and lone pixels out of one frame (include/ssd_hip.h)
+    def enqueue_depth_edges(self, d_ptr, nframes, d_out, rule=None, d_cls=None, stride_bytes=None, out_stride_bytes=None, cls_stride_bytes=None,
+                            stream=None):
+        """ssd_enqueue_depth_edges: the nframes uint16 depth frames at d_ptr filtered on the caller's stream: frame i to d_out + i *
+        out_stride_bytes, its class bytes (d_cls None: none) likewise.  -> nframes.  A depth-input enqueue on the same stream may read
+        d_out with no host wait in between.  The output must not overlap the input."""
+        frame = self.cfg.width * self.cfg.height * 2
+        _check(lib().ssd_enqueue_depth_edges(self._h, C.c_void_p(d_ptr), stride_bytes or frame, int(nframes), C.c_void_p(stream or 0),
+                                             None if rule is None else C.byref(rule), C.c_void_p(d_out), out_stride_bytes or frame,
+                                             C.c_void_p(d_cls or 0), cls_stride_bytes or frame // 2))
+        return int(nframes)
+
+    def fetch_depth_edges(self, nframes, stream=None):
+        """ssd_fetch_depth_edges: waits for the last enqueue_depth_edges -> list of EdgeStats (independent copies), one per frame"""
+        out = (EdgeStats * nframes)()
+        _check(lib().ssd_fetch_depth_edges(self._h, out, nframes, C.c_void_p(stream or 0)))
+        return [EdgeStats.from_buffer_copy(r) for r in out]
+
+    def depth_edges_time(self):
+        """the device time in ms of the last filter pass, its zeroing and its records' copy included (0 unless set_timing was on)"""
+        return _time_ms(lib().ssd_get_depth_edges_time, self._h)
+
+    def process_depth_host_edges(self, depth, rule=None, filtered=False, stats=False):
+        """ssd_process_depth_host_edges: depth frames on the host, uint16 [k, H, W]: every frame filtered on the device and the filtered
+        frame detected -> list of k FrameResult; with filtered=True / stats=True a tuple with the filtered frames (uint16 [k, H, W])
+        and / or the list of k EdgeStats behind it"""
+        a, total, _ = self._frames_arg("process_depth_host_edges", depth, True)
+        res = (FrameResult * max(total, 1))()
+        f = np.zeros((max(total, 1), self.cfg.height, self.cfg.width), np.uint16) if filtered else None
+        st = (EdgeStats * max(total, 1))() if stats else None
+        _check(lib().ssd_process_depth_host_edges(self._h, a.ctypes.data_as(C.c_void_p), total, None if rule is None else C.byref(rule), res,
+                                                  None if f is None else f.ctypes.data_as(C.c_void_p), st))
+        out = [list(res)[:total]]
+        if filtered:
+            out.append(f[:total])
+        if stats:
+            out.append([EdgeStats.from_buffer_copy(st[i]) for i in range(total)])
         return out[0] if len(out) == 1 else tuple(out)
 
     def locate_camera(self, frames, prior, stair_map, passes=3, rule=None, min_points=200, observable=SP_OBSERVABLE, depth=False):

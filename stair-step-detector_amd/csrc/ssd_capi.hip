@@ -14,6 +14,7 @@
 #include "ssd_ground.h"
 #include "ssd_pose.h"
 #include "ssd_fuse.h"
+#include "ssd_edges.h"
 #include "ssd_refit.h"
 #include "ssd_clearance.h"
 #include "ssd_treadgrid.h"
@@ -3255,6 +3256,150 @@ int ssd_process_depth_host_fused(ssd_handle *h, const uint16_t *depth, int nfram
       {
         HIP_TRY(hipMemcpy2DAsync(reinterpret_cast<unsigned char *>(fused) + static_cast<size_t>(g0) * frameBytes, frameBytes, h->fuseStage, fusedStride,
                                  frameBytes, static_cast<size_t>(groups), hipMemcpyDeviceToHost, h->ingestCompute));
+        HIP_TRY(hipStreamSynchronize(h->ingestCompute));
+      }
+      return r;
+    });
+}
+
+/* ---- depth edge filter: mixed and lone pixels out of one frame (include/ssd_hip.h) -------------------------------- */
+
+/* the frame records of the pass, on its first call */
+static int depth_edges_prepare(ssd_handle *h)
+{
+  if(h->dEdge)
+    return SSD_OK;
+  const size_t recBytes = sizeof(ssd_depth_edge_stats) * static_cast<size_t>(h->F);
+  DeviceBuf<ssd_depth_edge_stats> d;
+  PinnedBuf<ssd_depth_edge_stats> hh;
+  hipError_t e = d.alloc(recBytes, &h->bytes);
+  if(e == hipSuccess) e = hh.alloc(recBytes, &h->bytes);
+  if(e != hipSuccess)
+    return hip_fail(e, "ssd_enqueue_depth_edges: its buffers: ");
+  h->dEdge = std::move(d); h->hEdge = std::move(hh);
+  return SSD_OK;
+}
+
+/* the refusals of a filter call, before anything is launched or copied; *use: the rule to go by */
+static int check_depth_edges(const ssd_handle *h, const std::string &me, const void *d_frames, size_t frame_stride_bytes, int nframes,
+                             const ssd_depth_edge_rule *rule, const void *d_out, size_t out_stride_bytes, const uint8_t *d_cls, size_t cls_stride_bytes,
+                             ssd_depth_edge_rule *use)
+{
+  if(!h || !d_frames || !d_out)
+    return fail(SSD_E_ARG, me + ": null argument");
+  int rc = check_edge_rule(me, rule, use);
+  if(rc) return rc;
+  if(nframes < 1 || nframes > h->F)
+    return fail(SSD_E_ARG, me + ": nframes must lie in 1 .. max_frames_per_batch");
+  rc = check_device_frames(h, me.c_str(), d_frames, frame_stride_bytes, nframes, SSD_INPUT_DEPTH16);
+  if(!rc) rc = check_device_frames(h, me.c_str(), d_out, out_stride_bytes, nframes, SSD_INPUT_DEPTH16);
+  if(rc) return rc;
+  const size_t nPoints = static_cast<size_t>(h->P.nPoints), frameBytes = nPoints * 2;
+  if(d_cls && nframes > 1 && cls_stride_bytes < nPoints)
+    return fail(SSD_E_ARG, me + ": the class stride must hold a frame's bytes");
+  /* a stencil reads its neighbours' input: any overlap of what it writes with what it reads is a race */
+  const size_t inBytes = static_cast<size_t>(nframes - 1) * frame_stride_bytes + frameBytes;
+  if(ranges_overlap(d_frames, inBytes, d_out, static_cast<size_t>(nframes - 1) * out_stride_bytes + frameBytes) ||
+     (d_cls && ranges_overlap(d_frames, inBytes, d_cls, static_cast<size_t>(nframes - 1) * cls_stride_bytes + nPoints)))
+    return fail(SSD_E_ARG, me + ": the output and the class map must not overlap the frames");
+  return SSD_OK;
+}
+
+/* arguments checked by the callers */
+static int enqueue_depth_edges_impl(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, hipStream_t s,
+                                    const ssd_depth_edge_rule &rule, void *d_out, size_t out_stride_bytes, uint8_t *d_cls, size_t cls_stride_bytes)
+{
+  HIP_TRY(hipSetDevice(h->device));
+  int rc = depth_edges_prepare(h);
+  if(rc) return rc;
+  const bool timing = h->timing;
+  rc = pass_open(h->edgePass, s, timing, "ssd_enqueue_depth_edges");   /* another stream: behind the previous call */
+  if(!rc) rc = pass_start(h->edgePass, s, timing);
+  if(rc) return rc;
+  const size_t recBytes = sizeof(ssd_depth_edge_stats) * static_cast<size_t>(nframes);
+  HIP_TRY(hipMemsetAsync(h->dEdge, 0, recBytes, s));
+  launch_depth_edges(d_frames, frame_stride_bytes, h->P.W, h->P.H, nframes, rule, d_out, out_stride_bytes, d_cls, cls_stride_bytes, h->dEdge, s);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(h->hEdge, h->dEdge, recBytes, hipMemcpyDeviceToHost, s));
+  h->edgeFrames = nframes;
+  return pass_close(h->edgePass, s, timing);
+}
+
+int ssd_enqueue_depth_edges(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream, const ssd_depth_edge_rule *rule,
+                            void *d_out, size_t out_stride_bytes, uint8_t *d_cls, size_t cls_stride_bytes)
+{
+  ssd_depth_edge_rule R;
+  const int rc = check_depth_edges(h, "ssd_enqueue_depth_edges", d_frames, frame_stride_bytes, nframes, rule, d_out, out_stride_bytes, d_cls,
+                                   cls_stride_bytes, &R);
+  if(rc) return rc;
+  return enqueue_depth_edges_impl(h, d_frames, frame_stride_bytes, nframes, static_cast<hipStream_t>(stream), R, d_out, out_stride_bytes, d_cls,
+                                  cls_stride_bytes);
+}
+
+int ssd_fetch_depth_edges(ssd_handle *h, ssd_depth_edge_stats *out, int nframes, void *)
+{
+  if(!h || !out)
+    return fail(SSD_E_ARG, "ssd_fetch_depth_edges: null argument");
+  if(!h->edgePass.haveLast || nframes < 1 || nframes > h->edgeFrames)
+    return fail(SSD_E_ARG, "ssd_fetch_depth_edges: nframes must be 1..the frames of the last ssd_enqueue_depth_edges");
+  const int wait = pass_wait(h, &ssd_handle::edgePass, "ssd_fetch_depth_edges", "");
+  if(wait) return wait;
+  std::memcpy(out, h->hEdge, sizeof(ssd_depth_edge_stats) * static_cast<size_t>(nframes));
+  return SSD_OK;
+}
+
+int ssd_get_depth_edges_time(ssd_handle *h, float *ms)
+{
+  return pass_time(h, &ssd_handle::edgePass, "ssd_get_depth_edges_time", "ssd_enqueue_depth_edges", ms);
+}
+
+/* Host-fed.  The stream arrangement is ssd_process_depth_host_fused's: slice c's copy goes out, slice c - 1 is collected - its results,
+ * which lie behind its detection and so behind its filter, then its records and its filtered frames -, and only then slice c is
+ * filtered and detected.  So ONE buffer of filtered frames and the pass's one set of records do.  Slices are whole frames and the filter
+ * never looks across frames, so nothing is cut down. */
+int ssd_process_depth_host_edges(ssd_handle *h, const uint16_t *depth, int nframes, const ssd_depth_edge_rule *rule, ssd_frame_result *results,
+                                 uint16_t *filtered, ssd_depth_edge_stats *stats)
+{
+  const std::string me("ssd_process_depth_host_edges");
+  int rc = check_host_batch(h, me.c_str(), h && depth && results, nframes, SSD_INPUT_DEPTH16, kHandleCal);
+  ssd_depth_edge_rule R;
+  if(!rc) rc = check_edge_rule(me, rule, &R);
+  if(rc) return rc;
+  if(h->P.W % 4 != 0)
+    return fail(SSD_E_ARG, me + ": width must be a multiple of 4 (ssd_enqueue_depth)");
+  HIP_TRY(hipSetDevice(h->device));
+  SliceFeed feed{ h, host_frames(h, SSD_INPUT_DEPTH16, kForGroundFit), depth, nframes };
+  rc = feed.prepare();
+  if(rc) return rc;
+  const size_t frameBytes = static_cast<size_t>(h->P.nPoints) * 2, outStride = feed.f.devFrameBytes;
+  const size_t stageBytes = static_cast<size_t>(feed.slice) * outStride;
+  if(h->edgeStageCap < stageBytes)
+  {
+    for(int k = 0; k < h->depth; k++)                                /* its readers are this handle's detections */
+      if(h->lane[k].haveLast)
+        HIP_TRY(hipEventSynchronize(h->lane[k].done));
+    h->edgeStage.reset();
+    h->edgeStageCap = 0;
+    const hipError_t e = h->edgeStage.alloc(stageBytes);
+    if(e != hipSuccess)
+      return hip_fail(e, "ssd_process_depth_host_edges: the filtered frames' buffer: ");
+    h->edgeStageCap = stageBytes;
+  }
+  return process_host_frames(h, feed,
+    [&](const void *buf, int, int cnt)
+    {
+      int r = enqueue_depth_edges_impl(h, buf, feed.f.devFrameBytes, cnt, h->ingestCompute, R, h->edgeStage, outStride, nullptr, 0);
+      if(!r) r = enqueue_impl(h, h->edgeStage, outStride, cnt, h->ingestCompute, SSD_STAGE_ALL, true);
+      return r;
+    },
+    [&](int at, int cnt)
+    {
+      int r = ssd_fetch_back(h, results + at, cnt, 0);
+      if(!r && stats) r = ssd_fetch_depth_edges(h, stats + at, cnt, nullptr);
+      if(!r && filtered)
+      {
+        HIP_TRY(hipMemcpy2DAsync(reinterpret_cast<unsigned char *>(filtered) + static_cast<size_t>(at) * frameBytes, frameBytes, h->edgeStage, outStride,
+                                 frameBytes, static_cast<size_t>(cnt), hipMemcpyDeviceToHost, h->ingestCompute));
         HIP_TRY(hipStreamSynchronize(h->ingestCompute));
       }
       return r;

@@ -257,6 +257,15 @@ struct ssd_handle
    * counted as workspace */
   ssd::DeviceBuf<unsigned char> fuseStage;
   size_t fuseStageCap = 0;
+  /* the depth edge filter (ssd_enqueue_depth_edges & co.): a record per frame (F, on the device and pinned), made
+   * on the first call and counted as workspace.  One set, used in call order like the fusion's; nothing of the lanes is touched */
+  ssd::DeviceBuf<ssd_depth_edge_stats> dEdge;
+  ssd::PinnedBuf<ssd_depth_edge_stats> hEdge;   /* pinned: a call's last step copies its records here */
+  ssd_ordered_pass edgePass;
+  int edgeFrames = 0;                       /* frames of the last call */
+  /* ssd_process_depth_host_edges: a slice's filtered frames, which its detection reads; staging like fuseStage */
+  ssd::DeviceBuf<unsigned char> edgeStage;
+  size_t edgeStageCap = 0;
 };
 
 /* The single pass's planes - dPlaneImg and dFallback of every workspace and the pinned hFallback, zeroed - for ALL workspaces of the

@@ -9,6 +9,7 @@
 #include "ssd_host.h"
 #include "ssd_pose.h"
 #include "ssd_fuse.h"
+#include "ssd_edges.h"
 #include "ssd_refit.h"
 #include "ssd_clearance.h"
 #include "ssd_treadgrid.h"
@@ -1571,6 +1572,66 @@ int ssd_depth_fuse_host(int width, int height, const uint16_t *frames, size_t fr
           rec[kFuseSumAbsDev] += fuse_dev(d[j], o);
     }
   }
+  std::memcpy(stats, rec, sizeof(*stats));
+  return SSD_OK;
+}
+
+/* ---- depth edge filter: mixed and lone pixels out of one frame (include/ssd_hip.h) -------------------------------- */
+
+int ssd_depth_edge_default_rule(ssd_depth_edge_rule *rule)
+{
+  if(!rule)
+    return fail(SSD_E_ARG, "ssd_depth_edge_default_rule: null rule");
+  rule->min_support = 2;
+  rule->bridge = 1;
+  rule->tol = SSD_FUSE_TOL;
+  rule->slope = SSD_EDGE_SLOPE;
+  return SSD_OK;
+}
+
+/* the refusals about the rule that the host statement, the enqueue and the host-fed form share; *use: the rule to go by (the defaults
+ * where the caller gave none) */
+int check_edge_rule(const std::string &me, const ssd_depth_edge_rule *rule, ssd_depth_edge_rule *use)
+{
+  if(rule)
+    *use = *rule;
+  else
+    ssd_depth_edge_default_rule(use);
+  if(!edge_rule_ok(*use))
+    return fail(SSD_E_ARG, me + ": the rule must hold 0 <= min_support <= 8, 0 <= tol <= 65535, 0 <= slope <= 4096");
+  return SSD_OK;
+}
+
+int ssd_depth_edges_host(int width, int height, const uint16_t *frame, const ssd_depth_edge_rule *rule, uint16_t *out, uint8_t *cls,
+                         ssd_depth_edge_stats *stats)
+{
+  const std::string me("ssd_depth_edges_host");
+  if(!frame || !out || !stats || width <= 0 || height <= 0)
+    return fail(SSD_E_ARG, me + ": bad argument");
+  ssd_depth_edge_rule R;
+  const int rc = check_edge_rule(me, rule, &R);
+  if(rc) return rc;
+  int64_t rec[kEdgeWords] = {};
+  /* the sample at (x, y), 0 where the frame has no such pixel */
+  auto at = [&](int x, int y) -> uint32_t
+  {
+    return x >= 0 && x < width && y >= 0 && y < height ? frame[static_cast<size_t>(y) * width + x] : 0u;
+  };
+  for(int y = 0; y < height; y++)
+    for(int x = 0; x < width; x++)
+    {
+      const uint32_t q[8] = { at(x - 1, y - 1), at(x, y - 1), at(x + 1, y - 1), at(x - 1, y), at(x + 1, y), at(x - 1, y + 1), at(x, y + 1), at(x + 1, y + 1) };
+      const uint32_t d = at(x, y);
+      uint32_t c;
+      const int k = edge_pixel(d, q, R, &c);
+      const size_t p = static_cast<size_t>(y) * width + x;
+      out[p] = k == SSD_EDGE_KEPT ? static_cast<uint16_t>(d) : 0;
+      if(cls)
+        cls[p] = static_cast<uint8_t>(k);
+      rec[k]++;
+      if(k == SSD_EDGE_KEPT)
+        rec[kEdgeSumSupport] += c;
+    }
   std::memcpy(stats, rec, sizeof(*stats));
   return SSD_OK;
 }

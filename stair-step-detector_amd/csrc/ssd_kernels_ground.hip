@@ -210,3 +210,39 @@ void launch_depth_fuse(const void *frames, size_t strideBytes, int nPoints, int 
 }
 
 } // namespace ssd
+
+/* k_depth_edges, the fourth stand-alone frame pass and the first stencil: its body in a header, its launcher here */
+#include "ssd_k_edges.h"
+
+namespace ssd
+{
+
+void launch_depth_edges(const void *frames, size_t strideBytes, int W, int H, int nframes, const ssd_depth_edge_rule &rule, void *out,
+                        size_t outStride, uint8_t *cls, size_t clsStride, ssd_depth_edge_stats *stats, hipStream_t s)
+{
+  /* the wide body: 128-bit loads and stores of a strip, 64-bit stores of its classes.  Rows are packed, so a strip lies on a 16-byte
+   * boundary only where the width is a multiple of 8 */
+  const bool wide = W % kEdgeStrip == 0 && reinterpret_cast<size_t>(frames) % 16 == 0 && strideBytes % 16 == 0 &&
+                    reinterpret_cast<size_t>(out) % 16 == 0 && outStride % 16 == 0 &&
+                    (!cls || (reinterpret_cast<size_t>(cls) % 8 == 0 && clsStride % 8 == 0));
+  EdgeArgs A;
+  A.frames = static_cast<const unsigned char *>(frames);
+  A.strideBytes = strideBytes;
+  A.out = static_cast<unsigned char *>(out);
+  A.outStride = outStride;
+  A.cls = cls;
+  A.clsStride = clsStride;
+  A.stats = reinterpret_cast<unsigned long long *>(stats);
+  A.W = W; A.H = H; A.nframes = nframes;
+  A.spans = (W + kEdgeSpan - 1) / kEdgeSpan;
+  A.tasks = A.spans * ((H + kEdgeTile - 1) / kEdgeTile);
+  A.blocksPerFrame = (A.tasks + kEdgeWaves - 1) / kEdgeWaves;
+  A.rule = rule;
+  const dim3 grid(static_cast<unsigned int>(A.blocksPerFrame) * nframes), block(kEdgeThreads);
+  if(wide)
+    hipLaunchKernelGGL((k_depth_edges<true>), grid, block, kEdgeLds, s, A);
+  else
+    hipLaunchKernelGGL((k_depth_edges<false>), grid, block, kEdgeLds, s, A);
+}
+
+} // namespace ssd
