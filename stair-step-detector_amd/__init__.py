@@ -1297,6 +1297,29 @@ class Detector:
                                               inp, res, lab.ctypes.data_as(C.c_void_p) if labels else None))
         return (list(res), lab) if labels else list(res)
 
+    def _fetch_records(self, fn, Type, n, stream, *args):
+        """a record fetch of a stand-alone frame pass (fn(handle, out, n, *args, stream)) -> list of n Type (independent copies)"""
+        out = (Type * n)()
+        _check(fn(self._h, out, n, *args, C.c_void_p(stream or 0)))
+        return [Type.from_buffer_copy(r) for r in out]
+
+    def _depth_host_pre(self, who, depth, group, Stats, frames, stats, *args):
+        """a host-fed depth pre-pass (ssd_<who>(handle, depth, total, *args, results, frames, stats)): every `group` frames become one
+        and that one is detected -> its FrameResults, with the staged frames (uint16 [k, H, W]) and / or its k Stats behind them"""
+        a, total, _ = self._frames_arg(who, depth, True)
+        k = total // group if group > 0 else 0
+        res = (FrameResult * max(k, 1))()
+        f = np.zeros((max(k, 1), self.cfg.height, self.cfg.width), np.uint16) if frames else None
+        st = (Stats * max(k, 1))() if stats else None
+        _check(getattr(lib(), "ssd_" + who)(self._h, a.ctypes.data_as(C.c_void_p), total, *args, res,
+                                            None if f is None else f.ctypes.data_as(C.c_void_p), st))
+        out = [list(res)[:k]]
+        if frames:
+            out.append(f[:k])
+        if stats:
+            out.append([Stats.from_buffer_copy(st[i]) for i in range(k)])
+        return out[0] if len(out) == 1 else tuple(out)
+
     # ---- ground fit: a calibration refined from the floor in the frames (include/ssd_hip.h, DESIGN.md section 7c)
     def enqueue_ground_fit(self, d_ptr, nframes, tol, priors=None, depth=False, stride_bytes=None, stream=None):
         """ssd_enqueue_ground_fit: the floor moments of frames in device memory, on the caller's stream.  priors: None = the handle's
@@ -1308,9 +1331,7 @@ class Detector:
 
     def fetch_ground_fit(self, nframes, min_points=2000, stream=None):
         """ssd_fetch_ground_fit: waits for the last enqueue_ground_fit -> list of GroundFit (independent copies)"""
-        out = (GroundFit * nframes)()
-        _check(lib().ssd_fetch_ground_fit(self._h, out, nframes, int(min_points), C.c_void_p(stream or 0)))
-        return [GroundFit.from_buffer_copy(r) for r in out]
+        return self._fetch_records(lib().ssd_fetch_ground_fit, GroundFit, nframes, stream, int(min_points))
 
     def process_host_ground_fit(self, frames, tol, priors=None, depth=False, min_points=2000):
         """ssd_process_host_ground_fit: frames on the host (float32 [n, H, W, 3], or uint16 [n, H, W] with depth=True) -> list of GroundFit"""
@@ -1555,9 +1576,7 @@ class Detector:
 
     def fetch_stair_pose_moments(self, nframes, stream=None):
         """ssd_fetch_stair_pose_moments: waits for the last enqueue_stair_pose -> list of StairPoseMoments (independent copies)"""
-        out = (StairPoseMoments * nframes)()
-        _check(lib().ssd_fetch_stair_pose_moments(self._h, out, nframes, C.c_void_p(stream or 0)))
-        return [StairPoseMoments.from_buffer_copy(r) for r in out]
+        return self._fetch_records(lib().ssd_fetch_stair_pose_moments, StairPoseMoments, nframes, stream)
 
     def fetch_stair_pose(self, min_points=200, observable=SP_OBSERVABLE, stream=None):
         """ssd_fetch_stair_pose: waits likewise; per target the fold of its frames' records, solved -> list of StairPose"""
@@ -1602,9 +1621,7 @@ class Detector:
 
     def fetch_depth_fuse(self, ngroups, stream=None):
         """ssd_fetch_depth_fuse: waits for the last enqueue_depth_fuse -> list of FuseStats (independent copies), one per group"""
-        out = (FuseStats * ngroups)()
-        _check(lib().ssd_fetch_depth_fuse(self._h, out, ngroups, C.c_void_p(stream or 0)))
-        return [FuseStats.from_buffer_copy(r) for r in out]
+        return self._fetch_records(lib().ssd_fetch_depth_fuse, FuseStats, ngroups, stream)
 
     def depth_fuse_time_ms(self):
         """the device time of the last fusion pass, its zeroing and its records' copy included (0 unless set_timing was on)"""
@@ -1614,19 +1631,7 @@ class Detector:
         """ssd_process_depth_host_fused: depth frames on the host, uint16 [k * n, H, W]: every n of them fused on the device and the
         fused frame detected -> list of k FrameResult; with fused=True / stats=True a tuple with the fused frames (uint16 [k, H, W])
         and / or the list of k FuseStats behind it"""
-        a, total, _ = self._frames_arg("process_depth_host_fused", depth, True)
-        k = total // int(n) if int(n) > 0 else 0
-        res = (FrameResult * max(k, 1))()
-        f = np.zeros((max(k, 1), self.cfg.height, self.cfg.width), np.uint16) if fused else None
-        st = (FuseStats * max(k, 1))() if stats else None
-        _check(lib().ssd_process_depth_host_fused(self._h, a.ctypes.data_as(C.c_void_p), total, int(n), None if rule is None else C.byref(rule), res,
-                                                  None if f is None else f.ctypes.data_as(C.c_void_p), st))
-        out = [list(res)[:k]]
-        if fused:
-            out.append(f[:k])
-        if stats:
-            out.append([FuseStats.from_buffer_copy(st[i]) for i in range(k)])
-        return out[0] if len(out) == 1 else tuple(out)
+        return self._depth_host_pre("process_depth_host_fused", depth, int(n), FuseStats, fused, stats, int(n), None if rule is None else C.byref(rule))
 
     # ---- depth edge filter: mixed and lone pixels out of one frame (include/ssd_hip.h, DESIGN.md section 7t)
     def enqueue_depth_edges(self, d_ptr, nframes, d_out, rule=None, d_cls=None, stride_bytes=None, out_stride_bytes=None, cls_stride_bytes=None,
@@ -1642,30 +1647,19 @@ class Detector:
 
     def fetch_depth_edges(self, nframes, stream=None):
         """ssd_fetch_depth_edges: waits for the last enqueue_depth_edges -> list of EdgeStats (independent copies), one per frame"""
-        out = (EdgeStats * nframes)()
-        _check(lib().ssd_fetch_depth_edges(self._h, out, nframes, C.c_void_p(stream or 0)))
-        return [EdgeStats.from_buffer_copy(r) for r in out]
+        return self._fetch_records(lib().ssd_fetch_depth_edges, EdgeStats, nframes, stream)
 
-    def depth_edges_time(self):
-        """the device time in ms of the last filter pass, its zeroing and its records' copy included (0 unless set_timing was on)"""
+    def depth_edges_time_ms(self):
+        """the device time of the last filter pass, its zeroing and its records' copy included (0 unless set_timing was on)"""
         return _time_ms(lib().ssd_get_depth_edges_time, self._h)
+
+    depth_edges_time = depth_edges_time_ms                            # the name it was added under
 
     def process_depth_host_edges(self, depth, rule=None, filtered=False, stats=False):
         """ssd_process_depth_host_edges: depth frames on the host, uint16 [k, H, W]: every frame filtered on the device and the filtered
         frame detected -> list of k FrameResult; with filtered=True / stats=True a tuple with the filtered frames (uint16 [k, H, W])
         and / or the list of k EdgeStats behind it"""
-        a, total, _ = self._frames_arg("process_depth_host_edges", depth, True)
-        res = (FrameResult * max(total, 1))()
-        f = np.zeros((max(total, 1), self.cfg.height, self.cfg.width), np.uint16) if filtered else None
-        st = (EdgeStats * max(total, 1))() if stats else None
-        _check(lib().ssd_process_depth_host_edges(self._h, a.ctypes.data_as(C.c_void_p), total, None if rule is None else C.byref(rule), res,
-                                                  None if f is None else f.ctypes.data_as(C.c_void_p), st))
-        out = [list(res)[:total]]
-        if filtered:
-            out.append(f[:total])
-        if stats:
-            out.append([EdgeStats.from_buffer_copy(st[i]) for i in range(total)])
-        return out[0] if len(out) == 1 else tuple(out)
+        return self._depth_host_pre("process_depth_host_edges", depth, 1, EdgeStats, filtered, stats, None if rule is None else C.byref(rule))
 
     def locate_camera(self, frames, prior, stair_map, passes=3, rule=None, min_points=200, observable=SP_OBSERVABLE, depth=False):
         """process_host_stair_pose `passes` times over the same frames of ONE camera, each pass starting from the calibration the pass

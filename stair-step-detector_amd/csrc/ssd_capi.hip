@@ -1706,25 +1706,6 @@ int ssd_process_host_surfaces(ssd_handle *h, const void *frames, int nframes, in
 
 /* ---- trimmed surface refit (include/ssd_hip.h) ---------------------------------------------------------- */
 
-/* the buffers of the refit and the event behind their copy, on its first call */
-static int refit_prepare(ssd_handle *h)
-{
-  if(h->dRefitGates)
-    return SSD_OK;
-  const size_t bytes = sizeof(ssd_frame_gates) * static_cast<size_t>(h->F);
-  DeviceBuf<ssd_frame_gates> d;
-  PinnedBuf<ssd_frame_gates> hh;
-  Event copied;
-  hipError_t e = d.alloc(bytes, &h->bytes);
-  if(e == hipSuccess) e = hh.alloc(bytes, &h->bytes);
-  if(e == hipSuccess) e = copied.create(hipEventDisableTiming);
-  if(e != hipSuccess)
-    return hip_fail(e, "ssd_enqueue_surface_refit: its buffers: ");
-  h->dRefitGates = std::move(d); h->hRefitGates = std::move(hh);
-  h->refitGatesCopied = std::move(copied);
-  return SSD_OK;
-}
-
 /* where a pass's gates come from */
 struct GateSource
 {
@@ -1793,24 +1774,28 @@ static int pass_close(ssd_ordered_pass &p, hipStream_t s, bool timing)
   return SSD_OK;
 }
 
-/* the host waits for the last call (ssd_fetch_*; `none`: the refusal where there was no call) */
-static int pass_wait(ssd_handle *h, ssd_ordered_pass ssd_handle::*pass, const char *who, const char *none)
+/* the host waits for the last call (ssd_fetch_*; `none`: the refusal where there was no call); p: null with a null handle */
+static int pass_wait(ssd_handle *h, ssd_ordered_pass *p, const char *who, const char *none)
 {
   if(!h)
     return fail(SSD_E_ARG, std::string(who) + ": null handle");
-  if(!(h->*pass).haveLast)
+  if(!p->haveLast)
     return fail(SSD_E_ARG, std::string(who) + ": " + none);
   HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipEventSynchronize((h->*pass).done));
+  HIP_TRY(hipEventSynchronize(p->done));
   return SSD_OK;
+}
+static int pass_wait(ssd_handle *h, ssd_ordered_pass ssd_handle::*pass, const char *who, const char *none)
+{
+  return pass_wait(h, h ? &(h->*pass) : nullptr, who, none);
 }
 
 /* the milliseconds of the last call's timed span, 0 where it was not timed (ssd_get_*_time; enqueue: the pass's entry point, for the refusal) */
-static int pass_time(ssd_handle *h, ssd_ordered_pass ssd_handle::*pass, const char *who, const char *enqueue, float *ms)
+static int pass_time(ssd_handle *h, ssd_ordered_pass *pass, const char *who, const char *enqueue, float *ms)
 {
   if(!h || !ms)
     return fail(SSD_E_ARG, std::string(who) + ": null");
-  ssd_ordered_pass &p = h->*pass;
+  ssd_ordered_pass &p = *pass;
   if(!p.haveLast)
     return fail(SSD_E_ARG, std::string(who) + ": no " + enqueue + " yet");
   *ms = 0.0f;
@@ -1821,6 +1806,119 @@ static int pass_time(ssd_handle *h, ssd_ordered_pass ssd_handle::*pass, const ch
   HIP_TRY(hipEventElapsedTime(ms, p.ev[0], p.ev[1]));
   return SSD_OK;
 }
+static int pass_time(ssd_handle *h, ssd_ordered_pass ssd_handle::*pass, const char *who, const char *enqueue, float *ms)
+{
+  return pass_time(h, h ? &(h->*pass) : nullptr, who, enqueue, ms);
+}
+
+/* ---- stand-alone frame passes: their records and their uploaded tables (ssd_pass_records, ssd_upload_table) ---- */
+
+extern "C++"
+{
+/* the records' two buffers for F of them, on the pass's first call; countPinned: the pinned side goes into the workspace's bytes too */
+template<class Rec>
+static int records_prepare(ssd_handle *h, ssd_pass_records<Rec> &r, bool countPinned, const char *enqueue)
+{
+  if(r.d)
+    return SSD_OK;
+  const size_t bytes = sizeof(Rec) * static_cast<size_t>(h->F);
+  DeviceBuf<Rec> d;
+  PinnedBuf<Rec> hh;
+  hipError_t e = d.alloc(bytes, &h->bytes);
+  if(e == hipSuccess) e = hh.alloc(bytes, countPinned ? &h->bytes : nullptr);
+  if(e != hipSuccess)
+    return hip_fail(e, std::string(enqueue) + ": its buffers: ");
+  r.d = std::move(d); r.h = std::move(hh);
+  return SSD_OK;
+}
+
+/* n records zeroed on the stream, in front of the kernel that adds into them */
+template<class Rec>
+static int records_zero(ssd_pass_records<Rec> &r, int n, hipStream_t s)
+{
+  HIP_TRY(hipMemsetAsync(r.d, 0, sizeof(Rec) * static_cast<size_t>(n), s));
+  return SSD_OK;
+}
+
+/* ... and behind it: the launch's error, the n records on their way to the pinned side, the call's end */
+template<class Rec>
+static int records_finish(ssd_pass_records<Rec> &r, int n, hipStream_t s, bool timing)
+{
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(r.h, r.d, sizeof(Rec) * static_cast<size_t>(n), hipMemcpyDeviceToHost, s));
+  r.count = n;
+  return pass_close(r.pass, s, timing);
+}
+
+/* what a fetch begins with: the refusals (unit: what n counts, "frame" or "group"), then the host waits for the last call; the first n
+ * records then stand in r.h */
+template<class Rec>
+static int records_wait(ssd_handle *h, ssd_pass_records<Rec> ssd_handle::*recs, const void *out, int n, const char *who, const char *enqueue, const char *unit)
+{
+  if(!h || !out)
+    return fail(SSD_E_ARG, std::string(who) + ": null argument");
+  ssd_pass_records<Rec> &r = h->*recs;
+  if(!r.pass.haveLast || n < 1 || n > r.count)
+    return fail(SSD_E_ARG, std::string(who) + ": n" + unit + "s must be 1..the " + unit + "s of the last " + enqueue);
+  return pass_wait(h, &r.pass, who, "");
+}
+
+/* a whole fetch: the first n records of the last call, copied out */
+template<class Rec>
+static int records_fetch(ssd_handle *h, ssd_pass_records<Rec> ssd_handle::*recs, Rec *out, int n, const char *who, const char *enqueue, const char *unit)
+{
+  const int rc = records_wait(h, recs, out, n, who, enqueue, unit);
+  if(rc) return rc;
+  std::memcpy(out, (h->*recs).h, sizeof(Rec) * static_cast<size_t>(n));
+  return SSD_OK;
+}
+
+/* a table's two buffers for n entries and its event, on first use; countPinned as records_prepare's */
+template<class T>
+static int table_prepare(ssd_handle *h, ssd_upload_table<T> &t, size_t n, bool countPinned, const char *enqueue)
+{
+  if(t.d)
+    return SSD_OK;
+  ssd_upload_table<T> made;
+  hipError_t e = made.d.alloc(sizeof(T) * n, &h->bytes);
+  if(e == hipSuccess) e = made.h.alloc(sizeof(T) * n, countPinned ? &h->bytes : nullptr);
+  if(e == hipSuccess) e = made.copied.create(hipEventDisableTiming);
+  if(e != hipSuccess)
+    return hip_fail(e, std::string(enqueue) + ": its buffers: ");
+  t = std::move(made);
+  return SSD_OK;
+}
+
+/* before the pinned side is rewritten: the previous call's copy of it has gone over */
+template<class T>
+static int table_wait(ssd_upload_table<T> &t)
+{
+  if(t.sent)
+    HIP_TRY(hipEventSynchronize(t.copied));
+  return SSD_OK;
+}
+
+/* the first n entries to the device on the stream.  Alone only for the first table of a call that sends two, in front of the second one's
+ * table_send on the same stream: that event lies behind both copies, and the call waits for it alone (an event of its own costs the call
+ * microseconds) */
+template<class T>
+static int table_copy(ssd_upload_table<T> &t, size_t n, hipStream_t s)
+{
+  HIP_TRY(hipMemcpyAsync(t.d, t.h, sizeof(T) * n, hipMemcpyHostToDevice, s));
+  return SSD_OK;
+}
+
+/* ... and the event behind them */
+template<class T>
+static int table_send(ssd_upload_table<T> &t, size_t n, hipStream_t s)
+{
+  const int rc = table_copy(t, n, s);
+  if(rc) return rc;
+  HIP_TRY(hipEventRecord(t.copied, s));
+  t.sent = true;
+  return SSD_OK;
+}
+} // extern "C++"
 
 /* What a pass behind the handle's last whole enqueue is held to - the refit (section 7g, 7h), the clearance pass (section 7m) and the tread
  * grid (section 7n) alike: `cameras` = behind a whole cameras batch (wholeKind 2), under the table and the index that batch left in its
@@ -1944,22 +2042,19 @@ static int refit_enqueue_impl(ssd_handle *h, const char *who, bool cameras, cons
    * their calls, whatever workspace they follow.  Its own: the buffers, and the pinned gates of the previous call gone over */
   int rc = follow_enter(h, me, kRefitBehind, &ssd_handle::refitPass, cameras, d_frames, frame_stride_bytes, nframes, stream, input, f, [&](hipStream_t)
   {
-    int own = refit_prepare(h);
+    int own = table_prepare(h, h->refitGates, static_cast<size_t>(h->F), true, "ssd_enqueue_surface_refit");
     if(!own && gates.cameraGate) own = fold_prepare(h);
-    if(own) return own;
-    if(P.haveLast && gates.host)
-      HIP_TRY(hipEventSynchronize(h->refitGatesCopied));
-    return static_cast<int>(SSD_OK);
+    if(!own && gates.host) own = table_wait(h->refitGates);
+    return own;
   });
   if(rc) return rc;
   ssd_lane &L = *f.L;
   hipStream_t s = f.s;
   if(gates.host)
   {
-    std::memcpy(h->hRefitGates, gates.host, sizeof(ssd_frame_gates) * static_cast<size_t>(nframes));
-    HIP_TRY(hipMemcpyAsync(h->dRefitGates, h->hRefitGates, sizeof(ssd_frame_gates) * static_cast<size_t>(nframes), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipEventRecord(h->refitGatesCopied, s));
-    rc = pass_start(P, s, f.timing);
+    std::memcpy(h->refitGates.h, gates.host, sizeof(ssd_frame_gates) * static_cast<size_t>(nframes));
+    rc = table_send(h->refitGates, static_cast<size_t>(nframes), s);
+    if(!rc) rc = pass_start(P, s, f.timing);
     if(rc) return rc;
   }
   else
@@ -1967,7 +2062,7 @@ static int refit_enqueue_impl(ssd_handle *h, const char *who, bool cameras, cons
     /* the gates on the device, in front of the zeroing (d_prev may be d_out): no copy, no wait; the pass's time includes the kernel */
     rc = pass_start(P, s, f.timing);
     if(rc) return rc;
-    launch_surface_gates(gates.dPrev, nframes, gates.minPoints, gates.kSigma, gates.gateMin, h->dRefitGates, s);
+    launch_surface_gates(gates.dPrev, nframes, gates.minPoints, gates.kSigma, gates.gateMin, h->refitGates.d, s);
     HIP_TRY(hipGetLastError());
     if(gates.cameraGate)
     {
@@ -1976,12 +2071,12 @@ static int refit_enqueue_impl(ssd_handle *h, const char *who, bool cameras, cons
       const int ncams = static_cast<int>(h->camParams.size());
       launch_camera_fold(gates.dPrev, L.dCamIndex, nframes, ncams, false, h->dCamFold, s);
       HIP_TRY(hipGetLastError());
-      launch_camera_ground_gates(gates.dPrev, L.dCamIndex, nframes, h->dCamFold, ncams, gates.foldMinPoints, gates.kSigma, gates.gateMin, h->dRefitGates, s);
+      launch_camera_ground_gates(gates.dPrev, L.dCamIndex, nframes, h->dCamFold, ncams, gates.foldMinPoints, gates.kSigma, gates.gateMin, h->refitGates.d, s);
       HIP_TRY(hipGetLastError());
     }
   }
   HIP_TRY(hipMemsetAsync(d_out, 0, sizeof(ssd_frame_moments) * static_cast<size_t>(nframes), s));
-  launch_surface_refit(*f.B, f.chunk, h->dRefitGates, d_out);
+  launch_surface_refit(*f.B, f.chunk, h->refitGates.d, d_out);
   HIP_TRY(hipGetLastError());
   return follow_leave(h, &ssd_handle::refitPass, f);
 }
@@ -2595,30 +2690,6 @@ static int check_stair_maps(const std::string &me, const ssd_handle *h, const ss
   return SSD_OK;
 }
 
-/* the buffers of the pass and the event behind their copy, on its first call */
-static int stair_map_prepare(ssd_handle *h)
-{
-  if(h->dStairMaps)
-    return SSD_OK;
-  const size_t mapBytes = sizeof(ssd_stair_map) * static_cast<size_t>(SSD_MAX_STAIR_MAPS), indexBytes = sizeof(int) * static_cast<size_t>(h->F);
-  DeviceBuf<ssd_stair_map> dm;
-  PinnedBuf<ssd_stair_map> hm;
-  DeviceBuf<int> di;
-  PinnedBuf<int> hi;
-  Event copied;
-  hipError_t e = dm.alloc(mapBytes, &h->bytes);
-  if(e == hipSuccess) e = hm.alloc(mapBytes, &h->bytes);
-  if(e == hipSuccess) e = di.alloc(indexBytes, &h->bytes);
-  if(e == hipSuccess) e = hi.alloc(indexBytes, &h->bytes);
-  if(e == hipSuccess) e = copied.create(hipEventDisableTiming);
-  if(e != hipSuccess)
-    return hip_fail(e, "ssd_enqueue_stair_map: its buffers: ");
-  h->dStairMaps = std::move(dm); h->hStairMaps = std::move(hm);
-  h->dMapIndex = std::move(di); h->hMapIndex = std::move(hi);
-  h->mapsCopied = std::move(copied);
-  return SSD_OK;
-}
-
 static const BehindWhole kStairMapBehind{ "map", "ssd_enqueue_stair_map", "ssd_enqueue_cameras_stair_map", false };
 
 /* both entry points of the pass and the slices of the host forms (checked: the caller has held the maps and the whole call's index to
@@ -2645,25 +2716,23 @@ static int stair_map_enqueue_impl(ssd_handle *h, const char *who, bool cameras, 
    * behind that pass, which still reads them.  Its own: the buffers, and the pinned side of the previous call gone over */
   rc = follow_enter(h, me, kStairMapBehind, &ssd_handle::mapPass, cameras, d_frames, frame_stride_bytes, nframes, stream, input, f, [&](hipStream_t)
   {
-    const int own = stair_map_prepare(h);
-    if(own) return own;
-    if(P.haveLast)
-      HIP_TRY(hipEventSynchronize(h->mapsCopied));
-    return static_cast<int>(SSD_OK);
+    int own = table_prepare(h, h->stairMaps, static_cast<size_t>(SSD_MAX_STAIR_MAPS), true, "ssd_enqueue_stair_map");
+    if(!own) own = table_prepare(h, h->mapIndex, static_cast<size_t>(h->F), true, "ssd_enqueue_stair_map");
+    if(!own) own = table_wait(h->mapIndex);                   /* its event lies behind the maps' copy too */
+    return own;
   });
   if(rc) return rc;
   hipStream_t s = f.s;
-  std::memcpy(h->hStairMaps, maps, sizeof(ssd_stair_map) * static_cast<size_t>(nmaps));
+  std::memcpy(h->stairMaps.h, maps, sizeof(ssd_stair_map) * static_cast<size_t>(nmaps));
   for(int i = 0; i < nframes; i++)
-    h->hMapIndex[i] = map_of_frame ? static_cast<int>(map_of_frame[i]) : 0;
-  HIP_TRY(hipMemcpyAsync(h->dStairMaps, h->hStairMaps, sizeof(ssd_stair_map) * static_cast<size_t>(nmaps), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(h->dMapIndex, h->hMapIndex, sizeof(int) * static_cast<size_t>(nframes), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipEventRecord(h->mapsCopied, s));
-  rc = pass_start(P, s, f.timing);
+    h->mapIndex.h[i] = map_of_frame ? static_cast<int>(map_of_frame[i]) : 0;
+  rc = table_copy(h->stairMaps, static_cast<size_t>(nmaps), s);
+  if(!rc) rc = table_send(h->mapIndex, static_cast<size_t>(nframes), s);
+  if(!rc) rc = pass_start(P, s, f.timing);
   if(rc) return rc;
   if(!accumulate)
     HIP_TRY(hipMemsetAsync(d_out, 0, sizeof(ssd_frame_tread_grid) * static_cast<size_t>(nmaps), s));
-  launch_stair_map(*f.B, f.chunk, h->dStairMaps, h->dMapIndex, nmaps, *rule, d_out);
+  launch_stair_map(*f.B, f.chunk, h->stairMaps.d, h->mapIndex.d, nmaps, *rule, d_out);
   HIP_TRY(hipGetLastError());
   return follow_leave(h, &ssd_handle::mapPass, f);
 }
@@ -2809,28 +2878,13 @@ int ssd_process_host_cameras_riser_fits(ssd_handle *h, const void *frames, int n
   return rc ? rc : process_host_riser_fits_impl(h, "ssd_process_host_cameras_riser_fits", frames, nframes, camera_of_frame, input, results, risers, moments, min_points, out);
 }
 
-/* the buffers of the ground fit, on its first call */
+/* the records and the priors of the ground fit, on its first call.  The pinned sides of THIS pass are not counted as workspace (the other
+ * three passes' are: DESIGN.md section 7u) */
+static_assert(sizeof(ssd_ground_moments) == sizeof(long long) * kGroundSums, "ssd_ground_moments is k_ground_moments' record");
 static int ground_prepare(ssd_handle *h)
 {
-  if(h->dGround)
-    return SSD_OK;
-  const size_t recBytes = sizeof(long long) * kGroundSums * static_cast<size_t>(h->F), priorBytes = sizeof(GroundPrior) * static_cast<size_t>(h->F);
-  DeviceBuf<long long> d;
-  PinnedBuf<long long> hh;
-  DeviceBuf<GroundPrior> dPriors;
-  PinnedBuf<GroundPrior> hPriors;
-  Event copied;
-  hipError_t e = d.alloc(recBytes, &h->bytes);
-  if(e == hipSuccess) e = hh.alloc(recBytes);
-  if(e == hipSuccess) e = dPriors.alloc(priorBytes, &h->bytes);
-  if(e == hipSuccess) e = hPriors.alloc(priorBytes);
-  if(e == hipSuccess) e = copied.create(hipEventDisableTiming);
-  if(e != hipSuccess)
-    return hip_fail(e, "ssd_enqueue_ground_fit: its buffers: ");
-  h->dGround = std::move(d); h->hGround = std::move(hh);
-  h->dGroundPriors = std::move(dPriors); h->hGroundPriors = std::move(hPriors);
-  h->groundPriorsCopied = std::move(copied);
-  return SSD_OK;
+  const int rc = records_prepare(h, h->ground, false, "ssd_enqueue_ground_fit");
+  return rc ? rc : table_prepare(h, h->groundPriors, static_cast<size_t>(h->F), false, "ssd_enqueue_ground_fit");
 }
 
 /* the refusals of a ground-fit call, before anything is launched or copied */
@@ -2864,10 +2918,8 @@ static int enqueue_ground_fit_impl(ssd_handle *h, const void *d_frames, size_t f
   if(rc) return rc;
   HIP_TRY(hipSetDevice(h->device));
   rc = ground_prepare(h);
-  if(rc) return rc;
-  if(h->groundPass.haveLast)
-    HIP_TRY(hipEventSynchronize(h->groundPriorsCopied));          /* the pinned priors of the previous call have gone over */
-  rc = pass_open(h->groundPass, s, false, "ssd_enqueue_ground_fit");   /* another stream: behind the previous call */
+  if(!rc) rc = table_wait(h->groundPriors);
+  if(!rc) rc = pass_open(h->ground.pass, s, false, "ssd_enqueue_ground_fit");   /* another stream: behind the previous call */
   if(rc) return rc;
   const int np = npriors > 0 ? npriors : 1;
   h->groundPriorCal.resize(static_cast<size_t>(np));
@@ -2875,24 +2927,21 @@ static int enqueue_ground_fit_impl(ssd_handle *h, const void *d_frames, size_t f
   {
     ssd_calibration &c = h->groundPriorCal[0];
     c = handle_calibration(h);
-    ground_prior_fill(h->hGroundPriors[0], c, depth ? &h->intr : nullptr);
+    ground_prior_fill(h->groundPriors.h[0], c, depth ? &h->intr : nullptr);
   }
   else
     for(int i = 0; i < np; i++)
     {
       h->groundPriorCal[i] = priors[i].cal;
-      ground_prior_fill(h->hGroundPriors[i], priors[i].cal, depth ? &priors[i].intr : nullptr);
+      ground_prior_fill(h->groundPriors.h[i], priors[i].cal, depth ? &priors[i].intr : nullptr);
     }
-  const size_t recBytes = sizeof(long long) * kGroundSums * static_cast<size_t>(nframes);
-  HIP_TRY(hipMemcpyAsync(h->dGroundPriors, h->hGroundPriors, sizeof(GroundPrior) * static_cast<size_t>(np), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipEventRecord(h->groundPriorsCopied, s));
-  HIP_TRY(hipMemsetAsync(h->dGround, 0, recBytes, s));
+  rc = table_send(h->groundPriors, static_cast<size_t>(np), s);
+  if(!rc) rc = records_zero(h->ground, nframes, s);
+  if(rc) return rc;
   const GroundRange R{ h->cfg.x_min, h->cfg.x_max, h->cfg.y_min, h->cfg.y_max, tol };
-  launch_ground_moments(d_frames, frame_stride_bytes, h->P.W, h->P.H, nframes, depth, h->dGroundPriors, np > 1 ? 1 : 0, R, h->dGround, s);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(h->hGround, h->dGround, recBytes, hipMemcpyDeviceToHost, s));
-  h->groundFrames = nframes;
-  return pass_close(h->groundPass, s, false);
+  launch_ground_moments(d_frames, frame_stride_bytes, h->P.W, h->P.H, nframes, depth, h->groundPriors.d, np > 1 ? 1 : 0, R,
+                        reinterpret_cast<long long *>(h->ground.d.get()), s);
+  return records_finish(h->ground, nframes, s, false);
 }
 
 int ssd_enqueue_ground_fit(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream, int input,
@@ -2909,18 +2958,12 @@ int ssd_enqueue_ground_fit(ssd_handle *h, const void *d_frames, size_t frame_str
 
 int ssd_fetch_ground_fit(ssd_handle *h, ssd_ground_fit *out, int nframes, int min_points, void *)
 {
-  if(!h || !out)
-    return fail(SSD_E_ARG, "ssd_fetch_ground_fit: null argument");
-  if(!h->groundPass.haveLast || nframes < 1 || nframes > h->groundFrames)
-    return fail(SSD_E_ARG, "ssd_fetch_ground_fit: nframes must be 1..the frames of the last ssd_enqueue_ground_fit");
-  const int wait = pass_wait(h, &ssd_handle::groundPass, "ssd_fetch_ground_fit", "");
+  const int wait = records_wait(h, &ssd_handle::ground, out, nframes, "ssd_fetch_ground_fit", "ssd_enqueue_ground_fit", "frame");
   if(wait) return wait;
   const bool each = h->groundPriorCal.size() > 1;
   for(int i = 0; i < nframes; i++)
   {
-    ssd_ground_moments m;
-    std::memcpy(&m, h->hGround + static_cast<size_t>(i) * kGroundSums, sizeof(m));
-    const int rc = ssd_ground_fit_solve(&m, &h->groundPriorCal[each ? i : 0], min_points, out + i);
+    const int rc = ssd_ground_fit_solve(&h->ground.h[i], &h->groundPriorCal[each ? i : 0], min_points, out + i);
     if(rc) return rc;
   }
   return SSD_OK;
@@ -2947,34 +2990,13 @@ int ssd_process_host_ground_fit(ssd_handle *h, const void *frames, int nframes, 
 
 /* ---- stair pose: a camera located against a stair map (include/ssd_hip.h) ------------------------------------ */
 
-/* the buffers of the pass and the event behind their copy, on its first call */
+/* the records, the targets and the index of the pass, on its first call */
 static int stair_pose_prepare(ssd_handle *h)
 {
-  if(h->dPose)
-    return SSD_OK;
-  const size_t recBytes = sizeof(ssd_stair_pose_moments) * static_cast<size_t>(h->F), indexBytes = sizeof(int) * static_cast<size_t>(h->F);
-  const size_t targetBytes = sizeof(PoseTarget) * static_cast<size_t>(SSD_MAX_STAIR_MAPS);
-  DeviceBuf<ssd_stair_pose_moments> d;
-  PinnedBuf<ssd_stair_pose_moments> hh;
-  DeviceBuf<PoseTarget> dt;
-  PinnedBuf<PoseTarget> ht;
-  DeviceBuf<int> di;
-  PinnedBuf<int> hi;
-  Event copied;
-  hipError_t e = d.alloc(recBytes, &h->bytes);
-  if(e == hipSuccess) e = hh.alloc(recBytes, &h->bytes);
-  if(e == hipSuccess) e = dt.alloc(targetBytes, &h->bytes);
-  if(e == hipSuccess) e = ht.alloc(targetBytes, &h->bytes);
-  if(e == hipSuccess) e = di.alloc(indexBytes, &h->bytes);
-  if(e == hipSuccess) e = hi.alloc(indexBytes, &h->bytes);
-  if(e == hipSuccess) e = copied.create(hipEventDisableTiming);
-  if(e != hipSuccess)
-    return hip_fail(e, "ssd_enqueue_stair_pose: its buffers: ");
-  h->dPose = std::move(d); h->hPose = std::move(hh);
-  h->dPoseTargets = std::move(dt); h->hPoseTargets = std::move(ht);
-  h->dPoseIndex = std::move(di); h->hPoseIndex = std::move(hi);
-  h->poseCopied = std::move(copied);
-  return SSD_OK;
+  const char *me = "ssd_enqueue_stair_pose";
+  int rc = records_prepare(h, h->pose, true, me);
+  if(!rc) rc = table_prepare(h, h->poseTargetsUp, static_cast<size_t>(SSD_MAX_STAIR_MAPS), true, me);
+  return rc ? rc : table_prepare(h, h->poseIndexUp, static_cast<size_t>(h->F), true, me);
 }
 
 /* arguments checked by the callers */
@@ -2986,31 +3008,25 @@ static int enqueue_stair_pose_impl(ssd_handle *h, const void *d_frames, size_t f
   if(rc) return rc;
   HIP_TRY(hipSetDevice(h->device));
   rc = stair_pose_prepare(h);
+  if(!rc) rc = table_wait(h->poseIndexUp);                      /* its event lies behind the targets' copy too */
   if(rc) return rc;
-  if(h->posePass.haveLast)
-    HIP_TRY(hipEventSynchronize(h->poseCopied));                  /* the pinned side of the previous call has gone over */
   const bool timing = h->timing;
-  rc = pass_open(h->posePass, s, timing, "ssd_enqueue_stair_pose");   /* another stream: behind the previous call */
+  rc = pass_open(h->pose.pass, s, timing, "ssd_enqueue_stair_pose");   /* another stream: behind the previous call */
   if(rc) return rc;
   h->poseTargets.assign(targets, targets + ntargets);
   h->poseIndex.resize(static_cast<size_t>(nframes));
   for(int t = 0; t < ntargets; t++)
-    pose_target_fill(h->hPoseTargets[t], targets[t], depth, rule);
+    pose_target_fill(h->poseTargetsUp.h[t], targets[t], depth, rule);
   for(int i = 0; i < nframes; i++)
-    h->hPoseIndex[i] = h->poseIndex[i] = target_of_frame ? static_cast<int>(target_of_frame[i]) : 0;
-  const size_t recBytes = sizeof(ssd_stair_pose_moments) * static_cast<size_t>(nframes);
-  HIP_TRY(hipMemcpyAsync(h->dPoseTargets, h->hPoseTargets, sizeof(PoseTarget) * static_cast<size_t>(ntargets), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(h->dPoseIndex, h->hPoseIndex, sizeof(int) * static_cast<size_t>(nframes), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipEventRecord(h->poseCopied, s));
-  rc = pass_start(h->posePass, s, timing);
+    h->poseIndexUp.h[i] = h->poseIndex[i] = target_of_frame ? static_cast<int>(target_of_frame[i]) : 0;
+  rc = table_copy(h->poseTargetsUp, static_cast<size_t>(ntargets), s);
+  if(!rc) rc = table_send(h->poseIndexUp, static_cast<size_t>(nframes), s);
+  if(!rc) rc = pass_start(h->pose.pass, s, timing);         /* the timed span excludes the uploads */
+  if(!rc) rc = records_zero(h->pose, nframes, s);
   if(rc) return rc;
-  HIP_TRY(hipMemsetAsync(h->dPose, 0, recBytes, s));
   const PoseRange R{ h->cfg.x_min, h->cfg.x_max, h->cfg.y_min, h->cfg.y_max };
-  launch_stair_pose(d_frames, frame_stride_bytes, h->P.W, h->P.H, nframes, depth, h->dPoseTargets, ntargets, h->dPoseIndex, R, h->dPose, s);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(h->hPose, h->dPose, recBytes, hipMemcpyDeviceToHost, s));
-  h->poseFrames = nframes;
-  return pass_close(h->posePass, s, timing);
+  launch_stair_pose(d_frames, frame_stride_bytes, h->P.W, h->P.H, nframes, depth, h->poseTargetsUp.d, ntargets, h->poseIndexUp.d, R, h->pose.d, s);
+  return records_finish(h->pose, nframes, s, timing);
 }
 
 int ssd_enqueue_stair_pose(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream, int input,
@@ -3031,27 +3047,18 @@ int ssd_enqueue_stair_pose(ssd_handle *h, const void *d_frames, size_t frame_str
 
 int ssd_fetch_stair_pose_moments(ssd_handle *h, ssd_stair_pose_moments *out, int nframes, void *)
 {
-  if(!h || !out)
-    return fail(SSD_E_ARG, "ssd_fetch_stair_pose_moments: null argument");
-  if(!h->posePass.haveLast || nframes < 1 || nframes > h->poseFrames)
-    return fail(SSD_E_ARG, "ssd_fetch_stair_pose_moments: nframes must be 1..the frames of the last ssd_enqueue_stair_pose");
-  const int wait = pass_wait(h, &ssd_handle::posePass, "ssd_fetch_stair_pose_moments", "");
-  if(wait) return wait;
-  std::memcpy(out, h->hPose, sizeof(ssd_stair_pose_moments) * static_cast<size_t>(nframes));
-  return SSD_OK;
+  return records_fetch(h, &ssd_handle::pose, out, nframes, "ssd_fetch_stair_pose_moments", "ssd_enqueue_stair_pose", "frame");
 }
 
 int ssd_fetch_stair_pose(ssd_handle *h, ssd_stair_pose *out, int min_points, double observable, void *)
 {
   if(!h || !out)
     return fail(SSD_E_ARG, "ssd_fetch_stair_pose: null argument");
-  if(!h->posePass.haveLast)
-    return fail(SSD_E_ARG, "ssd_fetch_stair_pose: no ssd_enqueue_stair_pose to wait for");
-  const int wait = pass_wait(h, &ssd_handle::posePass, "ssd_fetch_stair_pose", "");
+  const int wait = pass_wait(h, &h->pose.pass, "ssd_fetch_stair_pose", "no ssd_enqueue_stair_pose to wait for");
   if(wait) return wait;
   std::vector<ssd_stair_pose_moments> folds(h->poseTargets.size());
   std::memset(folds.data(), 0, sizeof(ssd_stair_pose_moments) * folds.size());
-  int rc = pose_fold_frames("ssd_fetch_stair_pose", h->hPose, h->poseIndex.data(), h->poseFrames, folds);
+  int rc = pose_fold_frames("ssd_fetch_stair_pose", h->pose.h, h->poseIndex.data(), h->pose.count, folds);
   for(size_t t = 0; t < folds.size() && !rc; t++)
     rc = ssd_stair_pose_solve(&folds[t], &h->poseTargets[t], min_points, observable, out + t);
   return rc;
@@ -3059,7 +3066,7 @@ int ssd_fetch_stair_pose(ssd_handle *h, ssd_stair_pose *out, int min_points, dou
 
 int ssd_get_stair_pose_time(ssd_handle *h, float *ms)
 {
-  return pass_time(h, &ssd_handle::posePass, "ssd_get_stair_pose_time", "ssd_enqueue_stair_pose", ms);
+  return pass_time(h, h ? &h->pose.pass : nullptr, "ssd_get_stair_pose_time", "ssd_enqueue_stair_pose", ms);
 }
 
 int ssd_process_host_stair_pose(ssd_handle *h, const void *frames, int nframes, int input, const ssd_stair_pose_target *targets, int ntargets,
@@ -3100,26 +3107,29 @@ int ssd_process_host_stair_pose(ssd_handle *h, const void *frames, int nframes, 
 
 /* ---- depth fusion: one trimmed-median frame from n frames of a still camera (include/ssd_hip.h) ---------------- */
 
-/* the group records of the pass, on its first call */
-static int depth_fuse_prepare(ssd_handle *h)
-{
-  if(h->dFuse)
-    return SSD_OK;
-  const size_t recBytes = sizeof(ssd_depth_fuse_stats) * static_cast<size_t>(h->F);
-  DeviceBuf<ssd_depth_fuse_stats> d;
-  PinnedBuf<ssd_depth_fuse_stats> hh;
-  hipError_t e = d.alloc(recBytes, &h->bytes);
-  if(e == hipSuccess) e = hh.alloc(recBytes, &h->bytes);
-  if(e != hipSuccess)
-    return hip_fail(e, "ssd_enqueue_depth_fuse: its buffers: ");
-  h->dFuse = std::move(d); h->hFuse = std::move(hh);
-  return SSD_OK;
-}
-
 static bool ranges_overlap(const void *a, size_t aBytes, const void *b, size_t bBytes)
 {
   const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
   return a0 < b0 + bBytes && b0 < a0 + aBytes;
+}
+
+/* What a depth pre-pass reads and writes: nframes 16-bit frames in, `count` 16-bit frames out and, optionally, a byte map per output frame
+ * (noun / mapName: what the pass calls it, for the refusals).  Neither may overlap the input: a kernel that reads several frames, or its
+ * neighbours' pixels, races with any write into what it reads */
+static int check_depth_planes(const ssd_handle *h, const std::string &me, const void *d_frames, size_t frame_stride_bytes, int nframes, const void *d_out,
+                              size_t out_stride_bytes, const uint8_t *d_map, size_t map_stride_bytes, int count, const char *noun, const char *mapName)
+{
+  int rc = check_device_frames(h, me.c_str(), d_frames, frame_stride_bytes, nframes, SSD_INPUT_DEPTH16);
+  if(!rc) rc = check_device_frames(h, me.c_str(), d_out, out_stride_bytes, count, SSD_INPUT_DEPTH16);
+  if(rc) return rc;
+  const size_t nPoints = static_cast<size_t>(h->P.nPoints), frameBytes = nPoints * 2;
+  if(d_map && count > 1 && map_stride_bytes < nPoints)
+    return fail(SSD_E_ARG, me + ": the " + noun + " stride must hold a frame's bytes");
+  const size_t inBytes = static_cast<size_t>(nframes - 1) * frame_stride_bytes + frameBytes;
+  if(ranges_overlap(d_frames, inBytes, d_out, static_cast<size_t>(count - 1) * out_stride_bytes + frameBytes) ||
+     (d_map && ranges_overlap(d_frames, inBytes, d_map, static_cast<size_t>(count - 1) * map_stride_bytes + nPoints)))
+    return fail(SSD_E_ARG, me + ": the output and the " + mapName + " must not overlap the frames");
+  return SSD_OK;
 }
 
 /* the refusals of a fusion call, before anything is launched or copied; *use: the rule to go by, *ngroups: its groups */
@@ -3129,27 +3139,16 @@ static int check_depth_fuse(const ssd_handle *h, const std::string &me, const vo
 {
   if(!h || !d_frames || !d_out)
     return fail(SSD_E_ARG, me + ": null argument");
-  int rc = check_fuse_rule(me, n, rule, use);
+  const int rc = check_fuse_rule(me, n, rule, use);
   if(rc) return rc;
   if(hop < 1 || hop > n)
     return fail(SSD_E_ARG, me + ": hop must lie in 1 .. n");
   if(nframes < n || nframes > h->F)
     return fail(SSD_E_ARG, me + ": nframes must lie in n .. max_frames_per_batch");
-  const int groups = (nframes - n) / hop + 1;
-  if(groups > h->F)
+  *ngroups = (nframes - n) / hop + 1;
+  if(*ngroups > h->F)
     return fail(SSD_E_ARG, me + ": more groups than max_frames_per_batch");
-  rc = check_device_frames(h, me.c_str(), d_frames, frame_stride_bytes, nframes, SSD_INPUT_DEPTH16);
-  if(!rc) rc = check_device_frames(h, me.c_str(), d_out, out_stride_bytes, groups, SSD_INPUT_DEPTH16);
-  if(rc) return rc;
-  const size_t nPoints = static_cast<size_t>(h->P.nPoints), frameBytes = nPoints * 2;
-  if(d_support && groups > 1 && support_stride_bytes < nPoints)
-    return fail(SSD_E_ARG, me + ": the support stride must hold a frame's bytes");
-  const size_t inBytes = static_cast<size_t>(nframes - 1) * frame_stride_bytes + frameBytes;
-  if(ranges_overlap(d_frames, inBytes, d_out, static_cast<size_t>(groups - 1) * out_stride_bytes + frameBytes) ||
-     (d_support && ranges_overlap(d_frames, inBytes, d_support, static_cast<size_t>(groups - 1) * support_stride_bytes + nPoints)))
-    return fail(SSD_E_ARG, me + ": the output and the support must not overlap the frames");
-  *ngroups = groups;
-  return SSD_OK;
+  return check_depth_planes(h, me, d_frames, frame_stride_bytes, nframes, d_out, out_stride_bytes, d_support, support_stride_bytes, *ngroups, "support", "support");
 }
 
 /* arguments checked by the callers */
@@ -3157,20 +3156,16 @@ static int enqueue_depth_fuse_impl(ssd_handle *h, const void *d_frames, size_t f
                                    const ssd_depth_fuse_rule &rule, void *d_out, size_t out_stride_bytes, uint8_t *d_support, size_t support_stride_bytes)
 {
   HIP_TRY(hipSetDevice(h->device));
-  int rc = depth_fuse_prepare(h);
+  int rc = records_prepare(h, h->fuse, true, "ssd_enqueue_depth_fuse");
   if(rc) return rc;
   const bool timing = h->timing;
-  rc = pass_open(h->fusePass, s, timing, "ssd_enqueue_depth_fuse");   /* another stream: behind the previous call */
-  if(!rc) rc = pass_start(h->fusePass, s, timing);
+  rc = pass_open(h->fuse.pass, s, timing, "ssd_enqueue_depth_fuse");   /* another stream: behind the previous call */
+  if(!rc) rc = pass_start(h->fuse.pass, s, timing);
+  if(!rc) rc = records_zero(h->fuse, ngroups, s);
   if(rc) return rc;
-  const size_t recBytes = sizeof(ssd_depth_fuse_stats) * static_cast<size_t>(ngroups);
-  HIP_TRY(hipMemsetAsync(h->dFuse, 0, recBytes, s));
   launch_depth_fuse(d_frames, frame_stride_bytes, h->P.nPoints, n, hop, ngroups, rule, d_out, out_stride_bytes, d_support, support_stride_bytes,
-                    h->dFuse, h->tune.fuseGroupFastest != 0, s);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(h->hFuse, h->dFuse, recBytes, hipMemcpyDeviceToHost, s));
-  h->fuseGroups = ngroups;
-  return pass_close(h->fusePass, s, timing);
+                    h->fuse.d, h->tune.fuseGroupFastest != 0, s);
+  return records_finish(h->fuse, ngroups, s, timing);
 }
 
 int ssd_enqueue_depth_fuse(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream, int n, int hop,
@@ -3187,25 +3182,77 @@ int ssd_enqueue_depth_fuse(ssd_handle *h, const void *d_frames, size_t frame_str
 
 int ssd_fetch_depth_fuse(ssd_handle *h, ssd_depth_fuse_stats *out, int ngroups, void *)
 {
-  if(!h || !out)
-    return fail(SSD_E_ARG, "ssd_fetch_depth_fuse: null argument");
-  if(!h->fusePass.haveLast || ngroups < 1 || ngroups > h->fuseGroups)
-    return fail(SSD_E_ARG, "ssd_fetch_depth_fuse: ngroups must be 1..the groups of the last ssd_enqueue_depth_fuse");
-  const int wait = pass_wait(h, &ssd_handle::fusePass, "ssd_fetch_depth_fuse", "");
-  if(wait) return wait;
-  std::memcpy(out, h->hFuse, sizeof(ssd_depth_fuse_stats) * static_cast<size_t>(ngroups));
-  return SSD_OK;
+  return records_fetch(h, &ssd_handle::fuse, out, ngroups, "ssd_fetch_depth_fuse", "ssd_enqueue_depth_fuse", "group");
 }
 
 int ssd_get_depth_fuse_time(ssd_handle *h, float *ms)
 {
-  return pass_time(h, &ssd_handle::fusePass, "ssd_get_depth_fuse_time", "ssd_enqueue_depth_fuse", ms);
+  return pass_time(h, h ? &h->fuse.pass : nullptr, "ssd_get_depth_fuse_time", "ssd_enqueue_depth_fuse", ms);
 }
 
-/* Host-fed, disjoint groups.  The stream arrangement is that of the other stand-alone frame passes (process_host_frames): slice c's copy
- * goes out, slice c - 1 is collected - its results, which lie behind its detection and so behind its fusion, then its records and its
- * fused frames -, and only then slice c is fused and detected.  So ONE buffer of fused frames and the pass's one set of records do: what
- * overlaps is a slice's copy with the slice before it, not two slices' kernels. */
+extern "C++"
+{
+/* The host-fed form of a depth pre-pass: every n frames of the host's become one on the device (n = 1: each frame becomes another), and
+ * that one is detected.  pre(buf, stride, cnt, stage, stageStride) enqueues the pre-pass of a slice's cnt frames into the staging buffer
+ * on ingestCompute, stats(g0, groups) fetches its records where the caller wants them; `frames`, if any, takes the staged frames; kind:
+ * what they are, for the allocation's message.  The stream arrangement is that of the other stand-alone frame passes
+ * (process_host_frames): slice c's copy goes out, slice c - 1 is collected - its results, which lie behind its detection and so behind its
+ * pre-pass, then its records and its staged frames -, and only then slice c is pre-passed and detected.  So ONE staging buffer and the
+ * pass's one set of records do: what overlaps is a slice's copy with the slice before it, not two slices' kernels.  And one buffer does for
+ * every pre-pass of the handle: a call that succeeds has collected its last slice when it returns (process_host_frames ends with that
+ * slice's collect, whose ssd_fetch_back waits behind the detection that read the buffer), and the grow path below waits for every
+ * workspace's last enqueue before it gives the buffer back. */
+template<class Pre, class Stats>
+static int process_depth_host_pre(ssd_handle *h, const std::string &me, const char *kind, const uint16_t *depth, int nframes, int n,
+                                  ssd_frame_result *results, uint16_t *frames, Pre pre, Stats stats)
+{
+  if(h->P.W % 4 != 0)
+    return fail(SSD_E_ARG, me + ": width must be a multiple of 4 (ssd_enqueue_depth)");
+  HIP_TRY(hipSetDevice(h->device));
+  SliceFeed feed{ h, host_frames(h, SSD_INPUT_DEPTH16, kForGroundFit), depth, nframes };
+  const int rc = feed.prepare();
+  if(rc) return rc;
+  feed.slice = feed.slice / n * n;                                 /* a whole number of groups (n <= 16 <= a slice's frames, or n <= F) */
+  if(feed.slice < n)
+    return fail(SSD_E_ARG, me + ": n exceeds a slice's frames");
+  const size_t frameBytes = static_cast<size_t>(h->P.nPoints) * 2, stride = feed.f.devFrameBytes;
+  const size_t stageBytes = static_cast<size_t>(feed.slice / n) * stride;
+  if(h->depthStageCap < stageBytes)
+  {
+    for(int k = 0; k < h->depth; k++)                                /* its readers are this handle's detections */
+      if(h->lane[k].haveLast)
+        HIP_TRY(hipEventSynchronize(h->lane[k].done));
+    h->depthStage.reset();
+    h->depthStageCap = 0;
+    const hipError_t e = h->depthStage.alloc(stageBytes);
+    if(e != hipSuccess)
+      return hip_fail(e, me + ": the " + kind + " frames' buffer: ");
+    h->depthStageCap = stageBytes;
+  }
+  return process_host_frames(h, feed,
+    [&](const void *buf, int, int cnt)
+    {
+      int r = pre(buf, feed.f.devFrameBytes, cnt, h->depthStage.get(), stride);
+      if(!r) r = enqueue_impl(h, h->depthStage, stride, cnt / n, h->ingestCompute, SSD_STAGE_ALL, true);
+      return r;
+    },
+    [&](int at, int cnt)
+    {
+      const int g0 = at / n, groups = cnt / n;
+      int r = ssd_fetch_back(h, results + g0, groups, 0);
+      if(!r) r = stats(g0, groups);
+      if(!r && frames)
+      {
+        HIP_TRY(hipMemcpy2DAsync(reinterpret_cast<unsigned char *>(frames) + static_cast<size_t>(g0) * frameBytes, frameBytes, h->depthStage, stride,
+                                 frameBytes, static_cast<size_t>(groups), hipMemcpyDeviceToHost, h->ingestCompute));
+        HIP_TRY(hipStreamSynchronize(h->ingestCompute));
+      }
+      return r;
+    });
+}
+} // extern "C++"
+
+/* Host-fed, disjoint groups of n */
 int ssd_process_depth_host_fused(ssd_handle *h, const uint16_t *depth, int nframes, int n, const ssd_depth_fuse_rule *rule,
                                  ssd_frame_result *results, uint16_t *fused, ssd_depth_fuse_stats *stats)
 {
@@ -3216,69 +3263,15 @@ int ssd_process_depth_host_fused(ssd_handle *h, const uint16_t *depth, int nfram
   if(rc) return rc;
   if(n > h->F || nframes % n != 0)
     return fail(SSD_E_ARG, me + ": n must not exceed max_frames_per_batch and nframes must be a multiple of n");
-  if(h->P.W % 4 != 0)
-    return fail(SSD_E_ARG, me + ": width must be a multiple of 4 (ssd_enqueue_depth)");
-  HIP_TRY(hipSetDevice(h->device));
-  SliceFeed feed{ h, host_frames(h, SSD_INPUT_DEPTH16, kForGroundFit), depth, nframes };
-  rc = feed.prepare();
-  if(rc) return rc;
-  feed.slice = feed.slice / n * n;                                 /* a whole number of groups (n <= 16 <= a slice's frames, or n <= F) */
-  if(feed.slice < n)
-    return fail(SSD_E_ARG, me + ": n exceeds a slice's frames");
-  const size_t frameBytes = static_cast<size_t>(h->P.nPoints) * 2, fusedStride = feed.f.devFrameBytes;
-  const size_t stageBytes = static_cast<size_t>(feed.slice / n) * fusedStride;
-  if(h->fuseStageCap < stageBytes)
-  {
-    for(int k = 0; k < h->depth; k++)                                /* its readers are this handle's detections */
-      if(h->lane[k].haveLast)
-        HIP_TRY(hipEventSynchronize(h->lane[k].done));
-    h->fuseStage.reset();
-    h->fuseStageCap = 0;
-    const hipError_t e = h->fuseStage.alloc(stageBytes);
-    if(e != hipSuccess)
-      return hip_fail(e, "ssd_process_depth_host_fused: the fused frames' buffer: ");
-    h->fuseStageCap = stageBytes;
-  }
-  return process_host_frames(h, feed,
-    [&](const void *buf, int, int cnt)
+  return process_depth_host_pre(h, me, "fused", depth, nframes, n, results, fused,
+    [&](const void *buf, size_t stride, int cnt, unsigned char *stage, size_t stageStride)
     {
-      const int groups = cnt / n;
-      int r = enqueue_depth_fuse_impl(h, buf, feed.f.devFrameBytes, h->ingestCompute, n, n, groups, R, h->fuseStage, fusedStride, nullptr, 0);
-      if(!r) r = enqueue_impl(h, h->fuseStage, fusedStride, groups, h->ingestCompute, SSD_STAGE_ALL, true);
-      return r;
+      return enqueue_depth_fuse_impl(h, buf, stride, h->ingestCompute, n, n, cnt / n, R, stage, stageStride, nullptr, 0);
     },
-    [&](int at, int cnt)
-    {
-      const int g0 = at / n, groups = cnt / n;
-      int r = ssd_fetch_back(h, results + g0, groups, 0);
-      if(!r && stats) r = ssd_fetch_depth_fuse(h, stats + g0, groups, nullptr);
-      if(!r && fused)
-      {
-        HIP_TRY(hipMemcpy2DAsync(reinterpret_cast<unsigned char *>(fused) + static_cast<size_t>(g0) * frameBytes, frameBytes, h->fuseStage, fusedStride,
-                                 frameBytes, static_cast<size_t>(groups), hipMemcpyDeviceToHost, h->ingestCompute));
-        HIP_TRY(hipStreamSynchronize(h->ingestCompute));
-      }
-      return r;
-    });
+    [&](int g0, int groups) { return stats ? ssd_fetch_depth_fuse(h, stats + g0, groups, nullptr) : static_cast<int>(SSD_OK); });
 }
 
 /* ---- depth edge filter: mixed and lone pixels out of one frame (include/ssd_hip.h) -------------------------------- */
-
-/* the frame records of the pass, on its first call */
-static int depth_edges_prepare(ssd_handle *h)
-{
-  if(h->dEdge)
-    return SSD_OK;
-  const size_t recBytes = sizeof(ssd_depth_edge_stats) * static_cast<size_t>(h->F);
-  DeviceBuf<ssd_depth_edge_stats> d;
-  PinnedBuf<ssd_depth_edge_stats> hh;
-  hipError_t e = d.alloc(recBytes, &h->bytes);
-  if(e == hipSuccess) e = hh.alloc(recBytes, &h->bytes);
-  if(e != hipSuccess)
-    return hip_fail(e, "ssd_enqueue_depth_edges: its buffers: ");
-  h->dEdge = std::move(d); h->hEdge = std::move(hh);
-  return SSD_OK;
-}
 
 /* the refusals of a filter call, before anything is launched or copied; *use: the rule to go by */
 static int check_depth_edges(const ssd_handle *h, const std::string &me, const void *d_frames, size_t frame_stride_bytes, int nframes,
@@ -3287,22 +3280,11 @@ static int check_depth_edges(const ssd_handle *h, const std::string &me, const v
 {
   if(!h || !d_frames || !d_out)
     return fail(SSD_E_ARG, me + ": null argument");
-  int rc = check_edge_rule(me, rule, use);
+  const int rc = check_edge_rule(me, rule, use);
   if(rc) return rc;
   if(nframes < 1 || nframes > h->F)
     return fail(SSD_E_ARG, me + ": nframes must lie in 1 .. max_frames_per_batch");
-  rc = check_device_frames(h, me.c_str(), d_frames, frame_stride_bytes, nframes, SSD_INPUT_DEPTH16);
-  if(!rc) rc = check_device_frames(h, me.c_str(), d_out, out_stride_bytes, nframes, SSD_INPUT_DEPTH16);
-  if(rc) return rc;
-  const size_t nPoints = static_cast<size_t>(h->P.nPoints), frameBytes = nPoints * 2;
-  if(d_cls && nframes > 1 && cls_stride_bytes < nPoints)
-    return fail(SSD_E_ARG, me + ": the class stride must hold a frame's bytes");
-  /* a stencil reads its neighbours' input: any overlap of what it writes with what it reads is a race */
-  const size_t inBytes = static_cast<size_t>(nframes - 1) * frame_stride_bytes + frameBytes;
-  if(ranges_overlap(d_frames, inBytes, d_out, static_cast<size_t>(nframes - 1) * out_stride_bytes + frameBytes) ||
-     (d_cls && ranges_overlap(d_frames, inBytes, d_cls, static_cast<size_t>(nframes - 1) * cls_stride_bytes + nPoints)))
-    return fail(SSD_E_ARG, me + ": the output and the class map must not overlap the frames");
-  return SSD_OK;
+  return check_depth_planes(h, me, d_frames, frame_stride_bytes, nframes, d_out, out_stride_bytes, d_cls, cls_stride_bytes, nframes, "class", "class map");
 }
 
 /* arguments checked by the callers */
@@ -3310,19 +3292,15 @@ static int enqueue_depth_edges_impl(ssd_handle *h, const void *d_frames, size_t 
                                     const ssd_depth_edge_rule &rule, void *d_out, size_t out_stride_bytes, uint8_t *d_cls, size_t cls_stride_bytes)
 {
   HIP_TRY(hipSetDevice(h->device));
-  int rc = depth_edges_prepare(h);
+  int rc = records_prepare(h, h->edge, true, "ssd_enqueue_depth_edges");
   if(rc) return rc;
   const bool timing = h->timing;
-  rc = pass_open(h->edgePass, s, timing, "ssd_enqueue_depth_edges");   /* another stream: behind the previous call */
-  if(!rc) rc = pass_start(h->edgePass, s, timing);
+  rc = pass_open(h->edge.pass, s, timing, "ssd_enqueue_depth_edges");   /* another stream: behind the previous call */
+  if(!rc) rc = pass_start(h->edge.pass, s, timing);
+  if(!rc) rc = records_zero(h->edge, nframes, s);
   if(rc) return rc;
-  const size_t recBytes = sizeof(ssd_depth_edge_stats) * static_cast<size_t>(nframes);
-  HIP_TRY(hipMemsetAsync(h->dEdge, 0, recBytes, s));
-  launch_depth_edges(d_frames, frame_stride_bytes, h->P.W, h->P.H, nframes, rule, d_out, out_stride_bytes, d_cls, cls_stride_bytes, h->dEdge, s);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(h->hEdge, h->dEdge, recBytes, hipMemcpyDeviceToHost, s));
-  h->edgeFrames = nframes;
-  return pass_close(h->edgePass, s, timing);
+  launch_depth_edges(d_frames, frame_stride_bytes, h->P.W, h->P.H, nframes, rule, d_out, out_stride_bytes, d_cls, cls_stride_bytes, h->edge.d, s);
+  return records_finish(h->edge, nframes, s, timing);
 }
 
 int ssd_enqueue_depth_edges(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream, const ssd_depth_edge_rule *rule,
@@ -3338,25 +3316,16 @@ int ssd_enqueue_depth_edges(ssd_handle *h, const void *d_frames, size_t frame_st
 
 int ssd_fetch_depth_edges(ssd_handle *h, ssd_depth_edge_stats *out, int nframes, void *)
 {
-  if(!h || !out)
-    return fail(SSD_E_ARG, "ssd_fetch_depth_edges: null argument");
-  if(!h->edgePass.haveLast || nframes < 1 || nframes > h->edgeFrames)
-    return fail(SSD_E_ARG, "ssd_fetch_depth_edges: nframes must be 1..the frames of the last ssd_enqueue_depth_edges");
-  const int wait = pass_wait(h, &ssd_handle::edgePass, "ssd_fetch_depth_edges", "");
-  if(wait) return wait;
-  std::memcpy(out, h->hEdge, sizeof(ssd_depth_edge_stats) * static_cast<size_t>(nframes));
-  return SSD_OK;
+  return records_fetch(h, &ssd_handle::edge, out, nframes, "ssd_fetch_depth_edges", "ssd_enqueue_depth_edges", "frame");
 }
 
 int ssd_get_depth_edges_time(ssd_handle *h, float *ms)
 {
-  return pass_time(h, &ssd_handle::edgePass, "ssd_get_depth_edges_time", "ssd_enqueue_depth_edges", ms);
+  return pass_time(h, h ? &h->edge.pass : nullptr, "ssd_get_depth_edges_time", "ssd_enqueue_depth_edges", ms);
 }
 
-/* Host-fed.  The stream arrangement is ssd_process_depth_host_fused's: slice c's copy goes out, slice c - 1 is collected - its results,
- * which lie behind its detection and so behind its filter, then its records and its filtered frames -, and only then slice c is
- * filtered and detected.  So ONE buffer of filtered frames and the pass's one set of records do.  Slices are whole frames and the filter
- * never looks across frames, so nothing is cut down. */
+/* Host-fed: process_depth_host_pre with groups of one.  Slices are whole frames and the filter never looks across frames, so nothing is
+ * cut down */
 int ssd_process_depth_host_edges(ssd_handle *h, const uint16_t *depth, int nframes, const ssd_depth_edge_rule *rule, ssd_frame_result *results,
                                  uint16_t *filtered, ssd_depth_edge_stats *stats)
 {
@@ -3365,45 +3334,12 @@ int ssd_process_depth_host_edges(ssd_handle *h, const uint16_t *depth, int nfram
   ssd_depth_edge_rule R;
   if(!rc) rc = check_edge_rule(me, rule, &R);
   if(rc) return rc;
-  if(h->P.W % 4 != 0)
-    return fail(SSD_E_ARG, me + ": width must be a multiple of 4 (ssd_enqueue_depth)");
-  HIP_TRY(hipSetDevice(h->device));
-  SliceFeed feed{ h, host_frames(h, SSD_INPUT_DEPTH16, kForGroundFit), depth, nframes };
-  rc = feed.prepare();
-  if(rc) return rc;
-  const size_t frameBytes = static_cast<size_t>(h->P.nPoints) * 2, outStride = feed.f.devFrameBytes;
-  const size_t stageBytes = static_cast<size_t>(feed.slice) * outStride;
-  if(h->edgeStageCap < stageBytes)
-  {
-    for(int k = 0; k < h->depth; k++)                                /* its readers are this handle's detections */
-      if(h->lane[k].haveLast)
-        HIP_TRY(hipEventSynchronize(h->lane[k].done));
-    h->edgeStage.reset();
-    h->edgeStageCap = 0;
-    const hipError_t e = h->edgeStage.alloc(stageBytes);
-    if(e != hipSuccess)
-      return hip_fail(e, "ssd_process_depth_host_edges: the filtered frames' buffer: ");
-    h->edgeStageCap = stageBytes;
-  }
-  return process_host_frames(h, feed,
-    [&](const void *buf, int, int cnt)
+  return process_depth_host_pre(h, me, "filtered", depth, nframes, 1, results, filtered,
+    [&](const void *buf, size_t stride, int cnt, unsigned char *stage, size_t stageStride)
     {
-      int r = enqueue_depth_edges_impl(h, buf, feed.f.devFrameBytes, cnt, h->ingestCompute, R, h->edgeStage, outStride, nullptr, 0);
-      if(!r) r = enqueue_impl(h, h->edgeStage, outStride, cnt, h->ingestCompute, SSD_STAGE_ALL, true);
-      return r;
+      return enqueue_depth_edges_impl(h, buf, stride, cnt, h->ingestCompute, R, stage, stageStride, nullptr, 0);
     },
-    [&](int at, int cnt)
-    {
-      int r = ssd_fetch_back(h, results + at, cnt, 0);
-      if(!r && stats) r = ssd_fetch_depth_edges(h, stats + at, cnt, nullptr);
-      if(!r && filtered)
-      {
-        HIP_TRY(hipMemcpy2DAsync(reinterpret_cast<unsigned char *>(filtered) + static_cast<size_t>(at) * frameBytes, frameBytes, h->edgeStage, outStride,
-                                 frameBytes, static_cast<size_t>(cnt), hipMemcpyDeviceToHost, h->ingestCompute));
-        HIP_TRY(hipStreamSynchronize(h->ingestCompute));
-      }
-      return r;
-    });
+    [&](int at, int cnt) { return stats ? ssd_fetch_depth_edges(h, stats + at, cnt, nullptr) : static_cast<int>(SSD_OK); });
 }
 
 /* pinned host memory for frames (DMA without a staging copy) */

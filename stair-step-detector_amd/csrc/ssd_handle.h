@@ -63,6 +63,31 @@ struct ssd_ordered_pass
   bool timed = false;                       /* the last call was timed */
 };
 
+/* The per-frame (or per-group) records of a stand-alone frame pass: F of them on the device, where the kernel
+ * adds into them, and pinned, where the call's last step copies them; the pass's order record; how many the last call wrote.  Made on the
+ * pass's first call; one set, used in call order, nothing of the lanes is touched.  Only records_prepare, records_zero, records_finish,
+ * records_wait and records_fetch (ssd_capi.hip) touch it */
+template<typename Rec>
+struct ssd_pass_records
+{
+  ssd::DeviceBuf<Rec> d;
+  ssd::PinnedBuf<Rec> h;
+  ssd_ordered_pass pass;
+  int count = 0;
+};
+
+/* A table the caller's arguments are restated into on the pinned side and sent to the device during the call (section 7u): the event lies
+ * behind the copy, and the next call waits for it before it rewrites the pinned side.  Only table_prepare, table_wait and table_send
+ * (ssd_capi.hip) touch the event */
+template<typename T>
+struct ssd_upload_table
+{
+  ssd::DeviceBuf<T> d;
+  ssd::PinnedBuf<T> h;
+  ssd::Event copied;
+  bool sent = false;                        /* the event has been recorded */
+};
+
 /* One complete workspace of a handle: everything a batch in flight owns on the device.  A handle has `depth` of them
  * (ssd_config::batches_in_flight); successive enqueues take them in turn, each on the lane's own stream, so that the launches
  * of one batch fill the gaps the one-block-per-frame kernels of the others leave. */
@@ -185,16 +210,12 @@ struct ssd_handle
   bool camsNeedChecks = false;              /* some camera needs_checks(): its batches run the CHECKS instantiations */
   unsigned long long camCallKey = ~0ull;
   double camCallTol = 0.0;
-  /* the ground fit (ssd_enqueue_ground_fit & co.): made on its first call, so a handle that never fits holds
-   * none of them.  One set, used in stream order like a handle's one workspace; nothing of the lanes is touched. */
-  ssd::DeviceBuf<long long> dGround;        /* F records of kGroundSums int64 (ssd_ground_moments) */
-  ssd::PinnedBuf<long long> hGround;        /* pinned: a call's last step copies its records here */
-  ssd::DeviceBuf<ssd::GroundPrior> dGroundPriors;   /* F */
-  ssd::PinnedBuf<ssd::GroundPrior> hGroundPriors;   /* pinned: the caller's priors are restated here during the call */
-  ssd::Event groundPriorsCopied;            /* behind the copy pinned -> device: the pinned priors may be written again */
-  ssd_ordered_pass groundPass;              /* behind the call's last step; never timed */
-  int groundFrames = 0;                     /* frames of the last call */
-  std::vector<ssd_calibration> groundPriorCal;   /* its priors, one or one per frame: what ssd_fetch_ground_fit solves against */
+  /* the stand-alone frame passes, each made on its first call, so a handle that never runs one holds nothing of it.
+   * The ground fit (section 7c): a record per frame (the kernel's kGroundSums int64), never timed; the priors, F of them (the pinned sides of
+   * this pass alone are not counted as workspace) */
+  ssd_pass_records<ssd_ground_moments> ground;
+  ssd_upload_table<ssd::GroundPrior> groundPriors;
+  std::vector<ssd_calibration> groundPriorCal;   /* the last call's priors, one or one per frame: what ssd_fetch_ground_fit solves against */
   /* the trimmed surface refit (ssd_enqueue_surface_refit; ssd_enqueue_cameras_surface_refit, section 7h).  What the
    * last enqueue was, so that a refit can be held to it: wholeKind 0 = none / a partial run / a failed one / one withdrawn by
    * ssd_set_intrinsics (kind 1) or ssd_set_cameras (kind 2), 1 = a whole run under the handle's calibration, 2 = a cameras batch (its
@@ -205,10 +226,8 @@ struct ssd_handle
   size_t wholeStride = 0;
   const ssd_frame_result *wholeResults = nullptr;   /* its result records as the kernels address them (the slot k_final wrote) */
   /* the gates of a call, made on the first one, so a handle that never refits holds none of them.  One set, like the ground fit's */
-  ssd::DeviceBuf<ssd_frame_gates> dRefitGates;   /* F */
-  ssd::PinnedBuf<ssd_frame_gates> hRefitGates;   /* pinned: the caller's gates are copied here during the call */
-  ssd::Event refitGatesCopied;              /* behind the copy pinned -> device: the pinned gates may be written again */
-  ssd_ordered_pass refitPass;               /* a switch of streams is ordered by it: the device gates are single */
+  ssd_upload_table<ssd_frame_gates> refitGates;   /* F; the caller's gates are copied through it, or k_surface_gates writes the device side */
+  ssd_ordered_pass refitPass;              /* a switch of streams is ordered by it: the device gates are single */
   /* the camera fold (ssd_enqueue_cameras_surface_refit_folded, ssd_process_host_cameras_drift): SSD_MAX_CAMERAS
    * records, made on the first call of either.  One set: the refit orders its users as it orders the device gates' */
   ssd::DeviceBuf<ssd_camera_fold> dCamFold;
@@ -222,50 +241,28 @@ struct ssd_handle
   ssd::DeviceBuf<ssd_frame_tread_grid> gridStage;
   int gridStageFrames = 0;
   /* the stair map pass (ssd_enqueue_stair_map): the caller's maps (SSD_MAX_STAIR_MAPS records) and the batch's index
-   * frame -> map (F ints), each pinned and on the device, made on the first call and counted as workspace.  One set, like the refit's gates:
-   * mapPass orders the passes that read it, and a call waits for mapsCopied before it refills the pinned side */
-  ssd::DeviceBuf<ssd_stair_map> dStairMaps;
-  ssd::PinnedBuf<ssd_stair_map> hStairMaps;
-  ssd::DeviceBuf<int> dMapIndex;
-  ssd::PinnedBuf<int> hMapIndex;
-  ssd::Event mapsCopied;                    /* behind the copies pinned -> device: the pinned side may be written again */
+   * frame -> map (F ints), made on the first call and counted as workspace.  One set, like the refit's gates: mapPass orders the passes
+   * that read it */
+  ssd_upload_table<ssd_stair_map> stairMaps;
+  ssd_upload_table<int> mapIndex;
   ssd_ordered_pass mapPass;
   /* ssd_process_host_stair_map: the records its slices accumulate into (SSD_MAX_STAIR_MAPS of them), made on its first call; staging
    * like gridStage, not counted as workspace */
   ssd::DeviceBuf<ssd_frame_tread_grid> mapStage;
-  /* the stair pose pass (ssd_enqueue_stair_pose & co.): a record per frame (F, on the device and pinned), the
-   * call's targets as the kernel reads them (SSD_MAX_STAIR_MAPS) and its index frame -> target (F ints), each pinned and on the device,
-   * made on the first call and counted as workspace.  One set, used in call order like the ground fit's; nothing of the lanes is touched */
-  ssd::DeviceBuf<ssd_stair_pose_moments> dPose;
-  ssd::PinnedBuf<ssd_stair_pose_moments> hPose;  /* pinned: a call's last step copies its records here */
-  ssd::DeviceBuf<ssd::PoseTarget> dPoseTargets;
-  ssd::PinnedBuf<ssd::PoseTarget> hPoseTargets;
-  ssd::DeviceBuf<int> dPoseIndex;
-  ssd::PinnedBuf<int> hPoseIndex;
-  ssd::Event poseCopied;                    /* behind the copies pinned -> device: the pinned side may be written again */
-  ssd_ordered_pass posePass;
-  int poseFrames = 0;                       /* frames of the last call */
-  std::vector<ssd_stair_pose_target> poseTargets;   /* its targets and its index: what ssd_fetch_stair_pose folds and solves against */
+  /* the stair pose (section 7q): a record per frame; the call's targets as the kernel reads them (SSD_MAX_STAIR_MAPS) and its index
+   * frame -> target (F ints); all counted as workspace */
+  ssd_pass_records<ssd_stair_pose_moments> pose;
+  ssd_upload_table<ssd::PoseTarget> poseTargetsUp;
+  ssd_upload_table<int> poseIndexUp;
+  std::vector<ssd_stair_pose_target> poseTargets;   /* the last call's targets and index: what ssd_fetch_stair_pose folds and solves against */
   std::vector<int> poseIndex;
-  /* the depth fusion (ssd_enqueue_depth_fuse & co.): a record per group (F, on the device and pinned), made on the
-   * first call and counted as workspace.  One set, used in call order like the ground fit's; nothing of the lanes is touched */
-  ssd::DeviceBuf<ssd_depth_fuse_stats> dFuse;
-  ssd::PinnedBuf<ssd_depth_fuse_stats> hFuse;   /* pinned: a call's last step copies its records here */
-  ssd_ordered_pass fusePass;
-  int fuseGroups = 0;                       /* groups of the last call */
-  /* ssd_process_depth_host_fused: a slice's fused frames, which its detection reads; made on first use, staging like gridStage, not
-   * counted as workspace */
-  ssd::DeviceBuf<unsigned char> fuseStage;
-  size_t fuseStageCap = 0;
-  /* the depth edge filter (ssd_enqueue_depth_edges & co.): a record per frame (F, on the device and pinned), made
-   * on the first call and counted as workspace.  One set, used in call order like the fusion's; nothing of the lanes is touched */
-  ssd::DeviceBuf<ssd_depth_edge_stats> dEdge;
-  ssd::PinnedBuf<ssd_depth_edge_stats> hEdge;   /* pinned: a call's last step copies its records here */
-  ssd_ordered_pass edgePass;
-  int edgeFrames = 0;                       /* frames of the last call */
-  /* ssd_process_depth_host_edges: a slice's filtered frames, which its detection reads; staging like fuseStage */
-  ssd::DeviceBuf<unsigned char> edgeStage;
-  size_t edgeStageCap = 0;
+  /* the depth fusion (section 7s): a record per group; the depth edge filter (section 7t): a record per frame; counted as workspace */
+  ssd_pass_records<ssd_depth_fuse_stats> fuse;
+  ssd_pass_records<ssd_depth_edge_stats> edge;
+  /* ssd_process_depth_host_fused, ssd_process_depth_host_edges: a slice's fused or filtered frames, which its detection reads (section 7u:
+   * why one buffer does for both); made on first use, staging like gridStage, not counted as workspace */
+  ssd::DeviceBuf<unsigned char> depthStage;
+  size_t depthStageCap = 0;
 };
 
 /* The single pass's planes - dPlaneImg and dFallback of every workspace and the pinned hFallback, zeroed - for ALL workspaces of the

@@ -10,6 +10,7 @@
  * addition: the result does not depend on any order.  Overflow: see ground_point (ssd_ground.h).
  */
 #include "ssd_ground.h"
+#include "ssd_launch.h"                     /* aligned_to */
 
 namespace ssd
 {
@@ -131,7 +132,7 @@ void launch_ground_moments(const void *frames, size_t strideBytes, int W, int H,
 {
   const int nPoints = W * H;
   const int perLane = depthInput ? 8 : 4;
-  const bool wide = reinterpret_cast<size_t>(frames) % 16 == 0 && strideBytes % 16 == 0;
+  const bool wide = aligned_to(frames, strideBytes, 16);
   /* blocks per frame: enough blocks in all to fill the chip (256 CUs x 8 blocks) when the frames are few, at most 32 steps of the
    * wide loop per lane when they are large, never more blocks than there is work for */
   const int work = (nPoints + perLane * kGroundThreads - 1) / (perLane * kGroundThreads);
@@ -184,8 +185,7 @@ void launch_depth_fuse(const void *frames, size_t strideBytes, int nPoints, int 
                        hipStream_t s)
 {
   /* the wide body: 128-bit loads and stores of eight pixels, 64-bit stores of their support */
-  const bool wide = reinterpret_cast<size_t>(frames) % 16 == 0 && strideBytes % 16 == 0 && reinterpret_cast<size_t>(out) % 16 == 0 &&
-                    outStride % 16 == 0 && (!support || (reinterpret_cast<size_t>(support) % 8 == 0 && supStride % 8 == 0));
+  const bool wide = aligned_to(frames, strideBytes, 16) && aligned_to(out, outStride, 16) && (!support || aligned_to(support, supStride, 8));
   /* blocks per group: one step of the loop per lane (a step holds n loads in flight) until the grid passes 32768 blocks */
   const int work = (nPoints + kFusePerLane * kFuseThreads - 1) / (kFusePerLane * kFuseThreads);
   const long long all = static_cast<long long>(work) * ngroups;
@@ -222,9 +222,7 @@ void launch_depth_edges(const void *frames, size_t strideBytes, int W, int H, in
 {
   /* the wide body: 128-bit loads and stores of a strip, 64-bit stores of its classes.  Rows are packed, so a strip lies on a 16-byte
    * boundary only where the width is a multiple of 8 */
-  const bool wide = W % kEdgeStrip == 0 && reinterpret_cast<size_t>(frames) % 16 == 0 && strideBytes % 16 == 0 &&
-                    reinterpret_cast<size_t>(out) % 16 == 0 && outStride % 16 == 0 &&
-                    (!cls || (reinterpret_cast<size_t>(cls) % 8 == 0 && clsStride % 8 == 0));
+  const bool wide = W % kEdgeStrip == 0 && aligned_to(frames, strideBytes, 16) && aligned_to(out, outStride, 16) && (!cls || aligned_to(cls, clsStride, 8));
   EdgeArgs A;
   A.frames = static_cast<const unsigned char *>(frames);
   A.strideBytes = strideBytes;

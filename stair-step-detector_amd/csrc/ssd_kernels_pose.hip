@@ -200,7 +200,7 @@ void launch_stair_pose(const void *frames, size_t strideBytes, int W, int H, int
 {
   const int nPoints = W * H;
   const int perLane = depthInput ? 8 : 4;
-  const bool wide = reinterpret_cast<size_t>(frames) % 16 == 0 && strideBytes % 16 == 0;
+  const bool wide = aligned_to(frames, strideBytes, 16);
   /* blocks per frame: launch_ground_moments' rule - enough blocks in all to fill the chip when the frames are few, at most 32 steps of
    * the wide loop per lane when they are large, never more blocks than there is work for */
   const int work = (nPoints + perLane * kPoseThreads - 1) / (perLane * kPoseThreads);

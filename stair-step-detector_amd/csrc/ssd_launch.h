@@ -28,6 +28,8 @@ constexpr int kPredictParts = 4;            /* blocks of k_predict per frame */
  * a bin edge: ssd_prexy.h) live in instantiations of their own: as run-time flags they cost the common one two instructions per point */
 inline bool needs_checks(const Params &P) { return P.pre.checkInput != 0 || P.pre.zCheckTop != 0; }
 inline bool single_pass_geometry(int W, int H) { return W >= 64 && W <= 8192 && H >= 16 && H <= 4096; }
+/* a launcher's test for a wide body: frames at p, strideBytes apart, all lie on k-byte boundaries */
+inline bool aligned_to(const void *p, size_t strideBytes, size_t k) { return reinterpret_cast<size_t>(p) % k == 0 && strideBytes % k == 0; }
 
 /* What every launcher of the chain is given: the handle's constants, the batch's frames, the workspace's per-frame state, the stream.
  * cams: a cameras batch - every launcher then hands the batch to its *_cams entry point (ssd_kernels_cams.hip, ssd_kernels_refit.hip)

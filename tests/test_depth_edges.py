@@ -175,9 +175,9 @@ def test_the_recorded_accuracy_is_this_codes(ssd, oracle):
 
 
 def test_the_sanitizer_program_runs_clean():
-    """tools/depth_edges_sanitize.sh: csrc/ssd_host.cpp and a stand-alone program under AddressSanitizer and UBSan, on the CPU"""
+    """tools/host_sanitize.sh depth_edges: csrc/ssd_host.cpp and a stand-alone program under AddressSanitizer and UBSan, on the CPU"""
     import shutil
     if shutil.which("hipconfig") is None:
         pytest.skip("hipconfig is not installed")
-    run = subprocess.run(["bash", os.path.join(ROOT, "tools", "depth_edges_sanitize.sh")], capture_output=True, text=True, timeout=600)
+    run = subprocess.run(["bash", os.path.join(ROOT, "tools", "host_sanitize.sh"), "depth_edges"], capture_output=True, text=True, timeout=600)
     assert run.returncode == 0 and "depth edge filter host functions: clean" in run.stdout, run.stdout[-2000:] + run.stderr[-2000:]
