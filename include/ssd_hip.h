@@ -1344,6 +1344,76 @@ int ssd_get_depth_edges_time(ssd_handle *h, float *ms);
 int ssd_process_depth_host_edges(ssd_handle *h, const uint16_t *depth, int nframes, const ssd_depth_edge_rule *rule,
                                  ssd_frame_result *results, uint16_t *filtered /* may be NULL */, ssd_depth_edge_stats *stats /* may be NULL */);
 
+/* ---- depth warp: the frame another pose would have seen, so that frames of a moving camera can be fused ---------
+ * A view takes the source camera's coordinates to the target camera's (p_dst = r p_src + t, r row-major) and names the SOURCE frame's
+ * intrinsics; the target's intrinsics dst are one ssd_intrinsics per call.  For the source pixel (u, v) with sample d, no FMA anywhere:
+ *   1. d == 0: EMPTY.
+ *   2. (x, y, z) in float, bit-equal to ssd_deproject_host under src: dm = d * depth_units, x = dm * ((u - ppx) / fx), y likewise, z = dm.
+ *   3. in doubles, row sums left to right, then the translation: X = ((r0 x + r1 y) + r2 z) + t0, Y and Z likewise.
+ *   4. !(Z > 0): BEHIND.
+ *   5. q = floor(Z / double(dst.depth_units) + 0.5); !(q >= 1 && q <= 65535): RANGE.
+ *   6. uf = (X / Z) * double(dst.fx) + double(dst.ppx), vf likewise with fy and ppy; a = floor(uf + 0.5), b = floor(vf + 0.5);
+ *      a >= 0 && a < width && b >= 0 && b < height is tested in doubles before any conversion (a NaN fails it).  Not inside: OUTSIDE.
+ *   7. otherwise LANDED on the target pixel (a, b) with the value q.
+ * The output pixel is the smallest q that landed on it - the nearest surface wins -, 0 where none landed: the minimum is commutative, so
+ * the frame does not depend on any order.  One sample, one pixel: no splat.  The identity view with src == dst gives the input back
+ * byte for byte.  Per frame one exact record: the five classes add up to the pixel count, n_filled counts the output pixels that are
+ * not 0 (n_landed - n_filled samples shared a pixel with a nearer one).  Output frame i is source frame i under view i; the pass knows
+ * no groups - ssd_enqueue_depth_fuse behind it does. */
+typedef struct
+{
+  double r[9];                  /* source camera -> target camera, row-major rotation */
+  double t[3];                  /* ... and translation, metres */
+  ssd_intrinsics src;           /* the source frame's intrinsics */
+  int32_t reserved[1];
+} ssd_depth_warp_view;          /* 120 bytes */
+typedef struct
+{
+  int64_t n_empty, n_behind, n_range, n_outside, n_landed;
+  int64_t n_filled;             /* output pixels that are not 0 */
+  int64_t reserved[2];
+} ssd_depth_warp_stats;         /* 64 bytes */
+/* host only: the view between two cameras whose calibrations share one external world.  With e = T p + c a camera's affine map from
+ * camera coordinates to the external world (a and b, then r2 and t2 on x and y, world_z on z), r = T_dst^-1 T_src and t = T_dst^-1
+ * (c_src - c_dst); the inverse by cofactors, in doubles; out->src = src->intr.  SSD_E_ARG: null; src without (valid) intrinsics; a
+ * non-finite entry; |det T_dst| < 1e-9 (a calibration has |det| = 1). */
+int ssd_depth_warp_view_between(const ssd_camera *src, const ssd_camera *dst, ssd_depth_warp_view *out);
+/* host only, no GPU needed: the rule over ONE packed frame.  out: width * height values; stats: the frame's record.  frame and out must
+ * not overlap.  SSD_E_ARG: a null pointer, width or height not positive, a view with a non-finite entry or invalid intrinsics, dst
+ * invalid. */
+int ssd_depth_warp_host(int width, int height, const uint16_t *frame, const ssd_depth_warp_view *view, const ssd_intrinsics *dst,
+                        uint16_t *out, ssd_depth_warp_stats *stats);
+/* The pass (k_depth_warp) over depth frames resident in device memory, on the caller's stream, in order, without synchronising: the
+ * contract of ssd_enqueue_depth_fuse - no detection workspace, nothing ssd_fetch* reads is touched, the handle's intrinsics and
+ * calibration are not read; calls on different streams run in call order.  views: HOST memory, nframes entries, restated and copied
+ * during the call.  Warped frame i goes to d_out + i * out_stride_bytes, byte for byte ssd_depth_warp_host's; the pass zeroes the
+ * frames' own bytes first and writes no other byte.  ssd_enqueue_depth_fuse, ssd_enqueue_depth_edges or a depth-input enqueue on the
+ * same stream may read d_out with no host wait in between.  The records and the views' table (max_frames_per_batch of each on the
+ * device and pinned) are made on the first call and counted in ssd_workspace_bytes from then on; a handle that never calls this
+ * allocates, creates and launches nothing for it.
+ * The 16-bit output is written by compare-and-swap on the aligned 32-bit word that holds a pixel, so SSD_E_ARG, before anything is
+ * launched or copied, also for: d_out or out_stride_bytes no multiple of 4; width * height odd.  And for: a null handle, frames, views,
+ * dst or output; nframes outside 1 .. max_frames_per_batch; frames off 2-byte alignment or a stride that holds no frame; ANY overlap
+ * of the output and input ranges; a view with a non-finite entry or invalid intrinsics; dst invalid. */
+int ssd_enqueue_depth_warp(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream,
+                           const ssd_depth_warp_view *views /* HOST, nframes */, const ssd_intrinsics *dst, void *d_out,
+                           size_t out_stride_bytes);
+/* waits for the last ssd_enqueue_depth_warp and hands over its frames' records; nframes <= its */
+int ssd_fetch_depth_warp(ssd_handle *h, ssd_depth_warp_stats *out, int nframes, void *stream);
+/* the device time of the last pass: the zeroing in front of it and the copy of its records behind it included, the views' upload not
+ * (0 when timing was off for it) */
+int ssd_get_depth_warp_time(ssd_handle *h, float *ms);
+/* depth frames in host memory (pinned or pageable) of a moving camera, disjoint groups of n: frame i is warped under views[i] into the
+ * view dst - which must equal the intrinsics the handle detects under (ssd_set_intrinsics) -, every n warped frames are fused
+ * (fuse_rule NULL: the defaults for n) and the fused frame is detected, slice by slice through the staging buffers of
+ * ssd_process_depth_host.  results: nframes / n records, byte for byte ssd_process_depth_host's over ssd_depth_fuse_host's over
+ * ssd_depth_warp_host's output; fused (may be NULL): nframes / n packed frames; warp_stats (may be NULL): nframes records; fuse_stats
+ * (may be NULL): nframes / n.  SSD_E_ARG: as ssd_process_depth_host_fused, width * height odd, a bad view, dst not the handle's. */
+int ssd_process_depth_host_warp_fused(ssd_handle *h, const uint16_t *depth, int nframes, int n, const ssd_depth_warp_view *views,
+                                      const ssd_intrinsics *dst, const ssd_depth_fuse_rule *fuse_rule,
+                                      ssd_frame_result *results /* nframes / n */, uint16_t *fused /* may be NULL */,
+                                      ssd_depth_warp_stats *warp_stats /* may be NULL */, ssd_depth_fuse_stats *fuse_stats /* may be NULL */);
+
 /* stage selector for profiling / roofline measurement: runs only the chosen stage(s) of the pipeline */
 #define SSD_STAGE_HIST 1       /* K1: transform + crop + bin + histogram */
 #define SSD_STAGE_PEAKS 2

@@ -301,6 +301,19 @@ class EdgeStats(C.Structure):
                 ("reserved", C.c_int64 * 3)]
 
 
+class WarpView(C.Structure):
+    """ssd_depth_warp_view: source camera coordinates -> target camera coordinates (p_dst = r p_src + t, r row-major) and the SOURCE
+    frame's intrinsics (depth warp)"""
+    _fields_ = [("r", C.c_double * 9), ("t", C.c_double * 3), ("src", Intrinsics), ("reserved", C.c_int32 * 1)]
+
+
+class WarpStats(C.Structure):
+    """ssd_depth_warp_stats: a frame's record - its samples by class (they add up to the pixel count) and the output pixels that are
+    not 0 (n_landed - n_filled samples shared a pixel with a nearer one)"""
+    _fields_ = [("n_empty", C.c_int64), ("n_behind", C.c_int64), ("n_range", C.c_int64), ("n_outside", C.c_int64), ("n_landed", C.c_int64),
+                ("n_filled", C.c_int64), ("reserved", C.c_int64 * 2)]
+
+
 class Foothold(C.Structure):
     """ssd_foothold: one surface's cells (TG_OUT / TG_FREE / TG_OCCUPIED / TG_UNSEEN) and the best free rectangle on it"""
     _fields_ = [("state", C.c_uint8 * TG_COLS * TG_ROWS), ("n_free", C.c_int32), ("n_occupied", C.c_int32), ("n_unseen", C.c_int32),
@@ -397,6 +410,8 @@ EXPORTS = [
     "ssd_process_depth_host_fused",
     "ssd_depth_edge_default_rule", "ssd_depth_edges_host", "ssd_enqueue_depth_edges", "ssd_fetch_depth_edges", "ssd_get_depth_edges_time",
     "ssd_process_depth_host_edges",
+    "ssd_depth_warp_view_between", "ssd_depth_warp_host", "ssd_enqueue_depth_warp", "ssd_fetch_depth_warp", "ssd_get_depth_warp_time",
+    "ssd_process_depth_host_warp_fused",
 ]
 # libssd_source.so — the frame source standing in for the camera (include/ssd_source.h)
 SOURCE_EXPORTS = [
@@ -552,6 +567,13 @@ def lib():
     L.ssd_fetch_depth_edges.argtypes = [vp, C.POINTER(EdgeStats), i32, vp]
     L.ssd_get_depth_edges_time.argtypes = [vp, C.POINTER(C.c_float)]
     L.ssd_process_depth_host_edges.argtypes = [vp, vp, i32, C.POINTER(EdgeRule), C.POINTER(FrameResult), vp, C.POINTER(EdgeStats)]
+    L.ssd_depth_warp_view_between.argtypes = [C.POINTER(Camera), C.POINTER(Camera), C.POINTER(WarpView)]
+    L.ssd_depth_warp_host.argtypes = [i32, i32, vp, C.POINTER(WarpView), C.POINTER(Intrinsics), vp, C.POINTER(WarpStats)]
+    L.ssd_enqueue_depth_warp.argtypes = [vp, vp, sz, i32, vp, C.POINTER(WarpView), C.POINTER(Intrinsics), vp, sz]
+    L.ssd_fetch_depth_warp.argtypes = [vp, C.POINTER(WarpStats), i32, vp]
+    L.ssd_get_depth_warp_time.argtypes = [vp, C.POINTER(C.c_float)]
+    L.ssd_process_depth_host_warp_fused.argtypes = [vp, vp, i32, i32, C.POINTER(WarpView), C.POINTER(Intrinsics), C.POINTER(FuseRule),
+                                                    C.POINTER(FrameResult), vp, C.POINTER(WarpStats), C.POINTER(FuseStats)]
     L.ssd_process_host_stair_pose.argtypes = [vp, vp, i32, i32, C.POINTER(StairPoseTarget), i32, C.POINTER(C.c_uint16), C.POINTER(StairPoseRule), i32,
                                               C.c_double, C.POINTER(StairPoseMoments), C.POINTER(StairPose)]
     L.ssd_enqueue_cameras_surface_refit_folded.argtypes = [vp, vp, sz, i32, vp, i32, vp, i32, C.c_double, C.c_double, i32, vp]
@@ -1038,6 +1060,38 @@ def depth_edges_host(frame, rule=None, classes=False):
     return (out, stats, cls) if classes else (out, stats)
 
 
+def depth_warp_view_between(src, dst):
+    """ssd_depth_warp_view_between: two cameras (each a Camera or anything set_cameras takes; src with intrinsics) whose calibrations
+    share one external world -> the WarpView from src's camera coordinates to dst's"""
+    out = WarpView()
+    _check(lib().ssd_depth_warp_view_between(None if src is None else C.byref(_as_camera(src)), None if dst is None else C.byref(_as_camera(dst)),
+                                             C.byref(out)))
+    return out
+
+
+def _warp_views(views, n=None):
+    """one WarpView, or a sequence of them -> a ctypes array (one is handed on as it is)"""
+    if isinstance(views, C.Array) and views._type_ is WarpView and (n is None or len(views) == n):
+        return views
+    seq = [views] if isinstance(views, WarpView) else list(views)
+    if n is not None and len(seq) != n:
+        raise SsdError("depth warp: %d views for %d frames" % (len(seq), n))
+    return (WarpView * max(len(seq), 1))(*seq)
+
+
+def depth_warp_host(frame, view, dst):
+    """ssd_depth_warp_host: ONE depth frame, uint16 [H, W], seen under view.src, as the target camera with the Intrinsics dst would
+    have seen it -> (warped uint16 [H, W], WarpStats)"""
+    a = np.ascontiguousarray(frame)
+    if a.dtype != np.uint16 or a.ndim != 2:
+        raise SsdError("depth_warp_host: uint16 [H, W] expected")
+    H, W = a.shape
+    out, stats = np.zeros((H, W), np.uint16), WarpStats()
+    _check(lib().ssd_depth_warp_host(W, H, a.ctypes.data_as(C.c_void_p), None if view is None else C.byref(view),
+                                     None if dst is None else C.byref(dst), out.ctypes.data_as(C.c_void_p), C.byref(stats)))
+    return out, stats
+
+
 def riser_fit_solve(moments, risers, cal, min_points=100):
     """ssd_riser_fit_solve: a frame's riser moments (FrameMoments, record i = riser i) and its FrameRisers -> a plane per riser
     (FrameRiserFits; per riser GF_OK / GF_FEW / GF_DEGENERATE, lean, skew, rise and going)"""
@@ -1303,19 +1357,24 @@ class Detector:
         _check(fn(self._h, out, n, *args, C.c_void_p(stream or 0)))
         return [Type.from_buffer_copy(r) for r in out]
 
-    def _depth_host_pre(self, who, depth, group, Stats, frames, stats, *args):
-        """a host-fed depth pre-pass (ssd_<who>(handle, depth, total, *args, results, frames, stats)): every `group` frames become one
-        and that one is detected -> its FrameResults, with the staged frames (uint16 [k, H, W]) and / or its k Stats behind them"""
+    def _depth_host_pre(self, who, depth, group, Stats, frames, stats, *args, first=None):
+        """a host-fed depth pre-pass (ssd_<who>(handle, depth, total, *args, results, frames, [first's,] stats)): every `group` frames
+        become one and that one is detected -> its FrameResults, with the staged frames (uint16 [k, H, W]) and / or its k Stats behind
+        them.  first = (Type, wanted): a pre-pass of two passes, whose first leaves a record per INPUT frame - they go in front of the
+        k Stats"""
         a, total, _ = self._frames_arg(who, depth, True)
         k = total // group if group > 0 else 0
         res = (FrameResult * max(k, 1))()
         f = np.zeros((max(k, 1), self.cfg.height, self.cfg.width), np.uint16) if frames else None
         st = (Stats * max(k, 1))() if stats else None
+        fst = (first[0] * max(total, 1))() if first and first[1] else None
         _check(getattr(lib(), "ssd_" + who)(self._h, a.ctypes.data_as(C.c_void_p), total, *args, res,
-                                            None if f is None else f.ctypes.data_as(C.c_void_p), st))
+                                            None if f is None else f.ctypes.data_as(C.c_void_p), *((fst,) if first else ()), st))
         out = [list(res)[:k]]
         if frames:
             out.append(f[:k])
+        if fst is not None:
+            out.append([first[0].from_buffer_copy(fst[i]) for i in range(total)])
         if stats:
             out.append([Stats.from_buffer_copy(st[i]) for i in range(k)])
         return out[0] if len(out) == 1 else tuple(out)
@@ -1660,6 +1719,37 @@ class Detector:
         frame detected -> list of k FrameResult; with filtered=True / stats=True a tuple with the filtered frames (uint16 [k, H, W])
         and / or the list of k EdgeStats behind it"""
         return self._depth_host_pre("process_depth_host_edges", depth, 1, EdgeStats, filtered, stats, None if rule is None else C.byref(rule))
+
+    # ---- depth warp: the frame another pose would have seen (include/ssd_hip.h, DESIGN.md section 7v)
+    def enqueue_depth_warp(self, d_ptr, nframes, views, dst, d_out, stride_bytes=None, out_stride_bytes=None, stream=None):
+        """ssd_enqueue_depth_warp: the nframes uint16 depth frames at d_ptr, frame i warped under views[i] (a list of WarpView on the
+        host, or one for a single frame) into the view with the Intrinsics dst, on the caller's stream: frame i to d_out + i *
+        out_stride_bytes.  -> nframes.  enqueue_depth_fuse, enqueue_depth_edges or a depth-input enqueue on the same stream may read
+        d_out with no host wait in between.  d_out and its stride are multiples of 4; the output must not overlap the input."""
+        frame = self.cfg.width * self.cfg.height * 2
+        arr = _warp_views(views, int(nframes))
+        _check(lib().ssd_enqueue_depth_warp(self._h, C.c_void_p(d_ptr), stride_bytes or frame, int(nframes), C.c_void_p(stream or 0), arr,
+                                            None if dst is None else C.byref(dst), C.c_void_p(d_out), out_stride_bytes or frame))
+        return int(nframes)
+
+    def fetch_depth_warp(self, nframes, stream=None):
+        """ssd_fetch_depth_warp: waits for the last enqueue_depth_warp -> list of WarpStats (independent copies), one per frame"""
+        return self._fetch_records(lib().ssd_fetch_depth_warp, WarpStats, nframes, stream)
+
+    def depth_warp_time_ms(self):
+        """the device time of the last warp pass, its zeroing and its records' copy included (0 unless set_timing was on)"""
+        return _time_ms(lib().ssd_get_depth_warp_time, self._h)
+
+    def process_depth_host_warp_fused(self, depth, n, views, dst, fuse_rule=None, fused=False, warp_stats=False, fuse_stats=False):
+        """ssd_process_depth_host_warp_fused: depth frames of a moving camera on the host, uint16 [k * n, H, W]: frame i warped under
+        views[i] into the view dst (the handle's intrinsics), every n warped frames fused and the fused frame detected -> list of k
+        FrameResult; with fused=True / warp_stats=True / fuse_stats=True a tuple with the fused frames (uint16 [k, H, W]), the list of
+        k * n WarpStats and / or the list of k FuseStats behind it, in this order"""
+        total = len(depth)
+        arr = _warp_views(views, total)
+        return self._depth_host_pre("process_depth_host_warp_fused", depth, int(n), FuseStats, fused, fuse_stats, int(n), arr,
+                                    None if dst is None else C.byref(dst), None if fuse_rule is None else C.byref(fuse_rule),
+                                    first=(WarpStats, warp_stats))
 
     def locate_camera(self, frames, prior, stair_map, passes=3, rule=None, min_points=200, observable=SP_OBSERVABLE, depth=False):
         """process_host_stair_pose `passes` times over the same frames of ONE camera, each pass starting from the calibration the pass

@@ -15,6 +15,7 @@
 #include "ssd_pose.h"
 #include "ssd_fuse.h"
 #include "ssd_edges.h"
+#include "ssd_warp.h"
 #include "ssd_refit.h"
 #include "ssd_clearance.h"
 #include "ssd_treadgrid.h"
@@ -3193,8 +3194,8 @@ int ssd_get_depth_fuse_time(ssd_handle *h, float *ms)
 extern "C++"
 {
 /* The host-fed form of a depth pre-pass: every n frames of the host's become one on the device (n = 1: each frame becomes another), and
- * that one is detected.  pre(buf, stride, cnt, stage, stageStride) enqueues the pre-pass of a slice's cnt frames into the staging buffer
- * on ingestCompute, stats(g0, groups) fetches its records where the caller wants them; `frames`, if any, takes the staged frames; kind:
+ * that one is detected.  pre(buf, stride, at, cnt, stage, stageStride) enqueues the pre-pass of a slice's cnt frames, the batch's
+ * frames at .. at + cnt - 1, into the staging buffer on ingestCompute, stats(g0, groups) fetches its records where the caller wants them; `frames`, if any, takes the staged frames; kind:
  * what they are, for the allocation's message.  The stream arrangement is that of the other stand-alone frame passes
  * (process_host_frames): slice c's copy goes out, slice c - 1 is collected - its results, which lie behind its detection and so behind its
  * pre-pass, then its records and its staged frames -, and only then slice c is pre-passed and detected.  So ONE staging buffer and the
@@ -3230,9 +3231,9 @@ static int process_depth_host_pre(ssd_handle *h, const std::string &me, const ch
     h->depthStageCap = stageBytes;
   }
   return process_host_frames(h, feed,
-    [&](const void *buf, int, int cnt)
+    [&](const void *buf, int at, int cnt)
     {
-      int r = pre(buf, feed.f.devFrameBytes, cnt, h->depthStage.get(), stride);
+      int r = pre(buf, feed.f.devFrameBytes, at, cnt, h->depthStage.get(), stride);
       if(!r) r = enqueue_impl(h, h->depthStage, stride, cnt / n, h->ingestCompute, SSD_STAGE_ALL, true);
       return r;
     },
@@ -3264,7 +3265,7 @@ int ssd_process_depth_host_fused(ssd_handle *h, const uint16_t *depth, int nfram
   if(n > h->F || nframes % n != 0)
     return fail(SSD_E_ARG, me + ": n must not exceed max_frames_per_batch and nframes must be a multiple of n");
   return process_depth_host_pre(h, me, "fused", depth, nframes, n, results, fused,
-    [&](const void *buf, size_t stride, int cnt, unsigned char *stage, size_t stageStride)
+    [&](const void *buf, size_t stride, int, int cnt, unsigned char *stage, size_t stageStride)
     {
       return enqueue_depth_fuse_impl(h, buf, stride, h->ingestCompute, n, n, cnt / n, R, stage, stageStride, nullptr, 0);
     },
@@ -3335,11 +3336,135 @@ int ssd_process_depth_host_edges(ssd_handle *h, const uint16_t *depth, int nfram
   if(!rc) rc = check_edge_rule(me, rule, &R);
   if(rc) return rc;
   return process_depth_host_pre(h, me, "filtered", depth, nframes, 1, results, filtered,
-    [&](const void *buf, size_t stride, int cnt, unsigned char *stage, size_t stageStride)
+    [&](const void *buf, size_t stride, int, int cnt, unsigned char *stage, size_t stageStride)
     {
       return enqueue_depth_edges_impl(h, buf, stride, cnt, h->ingestCompute, R, stage, stageStride, nullptr, 0);
     },
     [&](int at, int cnt) { return stats ? ssd_fetch_depth_edges(h, stats + at, cnt, nullptr) : static_cast<int>(SSD_OK); });
+}
+
+/* ---- depth warp: the frame another pose would have seen (include/ssd_hip.h) ----------------------------------- */
+
+/* Word safety: k_depth_warp swaps the aligned 32-bit word that holds a pixel, so every such word must be the frame's own - an even
+ * number of pixels, the output and its stride multiples of 4.  Every caller of enqueue_depth_warp_impl goes through this */
+static int check_warp_words(const ssd_handle *h, const std::string &me, const void *d_out, size_t out_stride_bytes)
+{
+  if(h->P.nPoints % 2 != 0)
+    return fail(SSD_E_ARG, me + ": width * height must be even (the output is written in 32-bit words)");
+  if(reinterpret_cast<size_t>(d_out) % 4 != 0 || out_stride_bytes % 4 != 0)
+    return fail(SSD_E_ARG, me + ": the output and its stride must be multiples of 4 bytes (the output is written in 32-bit words)");
+  return SSD_OK;
+}
+
+/* the refusals of a warp call, before anything is launched or copied */
+static int check_depth_warp(const ssd_handle *h, const std::string &me, const void *d_frames, size_t frame_stride_bytes, int nframes,
+                            const ssd_depth_warp_view *views, const ssd_intrinsics *dst, const void *d_out, size_t out_stride_bytes)
+{
+  if(!h || !d_frames || !views || !dst || !d_out)
+    return fail(SSD_E_ARG, me + ": null argument");
+  if(nframes < 1 || nframes > h->F)
+    return fail(SSD_E_ARG, me + ": nframes must lie in 1 .. max_frames_per_batch");
+  int rc = check_warp_views(me, views, nframes, dst);
+  if(!rc) rc = check_device_frames(h, me.c_str(), d_frames, frame_stride_bytes, nframes, SSD_INPUT_DEPTH16);
+  if(!rc) rc = check_device_frames(h, me.c_str(), d_out, out_stride_bytes, nframes, SSD_INPUT_DEPTH16);
+  if(rc) return rc;
+  rc = check_warp_words(h, me, d_out, out_stride_bytes);
+  if(rc) return rc;
+  const size_t frameBytes = static_cast<size_t>(h->P.nPoints) * 2;
+  if(ranges_overlap(d_frames, static_cast<size_t>(nframes - 1) * frame_stride_bytes + frameBytes, d_out,
+                    static_cast<size_t>(nframes - 1) * out_stride_bytes + frameBytes))
+    return fail(SSD_E_ARG, me + ": the output must not overlap the frames");
+  return SSD_OK;
+}
+
+/* arguments checked by the callers */
+static int enqueue_depth_warp_impl(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, hipStream_t s,
+                                   const ssd_depth_warp_view *views, const ssd_intrinsics &dst, void *d_out, size_t out_stride_bytes)
+{
+  const char *me = "ssd_enqueue_depth_warp";
+  HIP_TRY(hipSetDevice(h->device));
+  int rc = records_prepare(h, h->warp, true, me);
+  if(!rc) rc = table_prepare(h, h->warpViews, static_cast<size_t>(h->F), true, me);
+  if(!rc) rc = table_wait(h->warpViews);
+  if(rc) return rc;
+  const bool timing = h->timing;
+  rc = pass_open(h->warp.pass, s, timing, me);                  /* another stream: behind the previous call */
+  if(rc) return rc;
+  std::memcpy(h->warpViews.h, views, sizeof(ssd_depth_warp_view) * static_cast<size_t>(nframes));
+  rc = table_send(h->warpViews, static_cast<size_t>(nframes), s);
+  if(!rc) rc = pass_start(h->warp.pass, s, timing);             /* the timed span excludes the upload */
+  if(!rc) rc = records_zero(h->warp, nframes, s);
+  if(rc) return rc;
+  /* the frames' own bytes to 0, "nothing landed": the bytes between and behind the frames are not the pass's */
+  const size_t frameBytes = static_cast<size_t>(h->P.nPoints) * 2;
+  HIP_TRY(hipMemset2DAsync(d_out, nframes > 1 ? out_stride_bytes : frameBytes, 0, frameBytes, static_cast<size_t>(nframes), s));
+  launch_depth_warp(d_frames, frame_stride_bytes, h->P.W, h->P.H, nframes, h->warpViews.d, dst, d_out, out_stride_bytes, h->warp.d, s);
+  return records_finish(h->warp, nframes, s, timing);
+}
+
+int ssd_enqueue_depth_warp(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream,
+                           const ssd_depth_warp_view *views, const ssd_intrinsics *dst, void *d_out, size_t out_stride_bytes)
+{
+  const int rc = check_depth_warp(h, "ssd_enqueue_depth_warp", d_frames, frame_stride_bytes, nframes, views, dst, d_out, out_stride_bytes);
+  if(rc) return rc;
+  return enqueue_depth_warp_impl(h, d_frames, frame_stride_bytes, nframes, static_cast<hipStream_t>(stream), views, *dst, d_out, out_stride_bytes);
+}
+
+int ssd_fetch_depth_warp(ssd_handle *h, ssd_depth_warp_stats *out, int nframes, void *)
+{
+  return records_fetch(h, &ssd_handle::warp, out, nframes, "ssd_fetch_depth_warp", "ssd_enqueue_depth_warp", "frame");
+}
+
+int ssd_get_depth_warp_time(ssd_handle *h, float *ms)
+{
+  return pass_time(h, h ? &h->warp.pass : nullptr, "ssd_get_depth_warp_time", "ssd_enqueue_depth_warp", ms);
+}
+
+/* Host-fed, disjoint groups of n: process_depth_host_pre, whose pre-pass is two - the slice warped into warpStage, that fused into the
+ * staging buffer the detection reads.  Both run on ingestCompute, so the fusion lies behind the warp and the next slice's warp behind
+ * this slice's fusion; warpStage grows only behind what that stream holds */
+int ssd_process_depth_host_warp_fused(ssd_handle *h, const uint16_t *depth, int nframes, int n, const ssd_depth_warp_view *views,
+                                      const ssd_intrinsics *dst, const ssd_depth_fuse_rule *fuse_rule, ssd_frame_result *results,
+                                      uint16_t *fused, ssd_depth_warp_stats *warp_stats, ssd_depth_fuse_stats *fuse_stats)
+{
+  const std::string me("ssd_process_depth_host_warp_fused");
+  int rc = check_host_batch(h, me.c_str(), h && depth && results, nframes, SSD_INPUT_DEPTH16, kHandleCal);
+  ssd_depth_fuse_rule R;
+  if(!rc) rc = check_fuse_rule(me, n, fuse_rule, &R);
+  if(!rc) rc = check_warp_views(me, views, nframes, dst);
+  if(rc) return rc;
+  if(n > h->F || nframes % n != 0)
+    return fail(SSD_E_ARG, me + ": n must not exceed max_frames_per_batch and nframes must be a multiple of n");
+  if(h->P.nPoints % 2 != 0)
+    return fail(SSD_E_ARG, me + ": width * height must be even (the output is written in 32-bit words)");
+  if(std::memcmp(dst, &h->intr, sizeof(*dst)) != 0)
+    return fail(SSD_E_ARG, me + ": dst must be the intrinsics the handle detects under (ssd_set_intrinsics)");
+  return process_depth_host_pre(h, me, "fused", depth, nframes, n, results, fused,
+    [&](const void *buf, size_t stride, int at, int cnt, unsigned char *stage, size_t stageStride)
+    {
+      const size_t need = static_cast<size_t>(cnt) * stride;
+      if(h->warpStageCap < need)
+      {
+        HIP_TRY(hipStreamSynchronize(h->ingestCompute));            /* its readers are this handle's fusions on that stream */
+        h->warpStage.reset();
+        h->warpStageCap = 0;
+        const hipError_t e = h->warpStage.alloc(need);
+        if(e != hipSuccess)
+          return hip_fail(e, me + ": the warped frames' buffer: ");
+        h->warpStageCap = need;
+      }
+      /* the stage's words are its own: the allocation is aligned and the slices' stride a multiple of 16 - checked all the same */
+      int r = check_warp_words(h, me, h->warpStage.get(), stride);
+      if(!r) r = enqueue_depth_warp_impl(h, buf, stride, cnt, h->ingestCompute, views + at, *dst, h->warpStage.get(), stride);
+      if(!r) r = enqueue_depth_fuse_impl(h, h->warpStage.get(), stride, h->ingestCompute, n, n, cnt / n, R, stage, stageStride, nullptr, 0);
+      return r;
+    },
+    [&](int g0, int groups)
+    {
+      int r = warp_stats ? ssd_fetch_depth_warp(h, warp_stats + static_cast<size_t>(g0) * n, groups * n, nullptr) : static_cast<int>(SSD_OK);
+      if(!r && fuse_stats) r = ssd_fetch_depth_fuse(h, fuse_stats + g0, groups, nullptr);
+      return r;
+    });
 }
 
 /* pinned host memory for frames (DMA without a staging copy) */

@@ -263,6 +263,13 @@ struct ssd_handle
    * why one buffer does for both); made on first use, staging like gridStage, not counted as workspace */
   ssd::DeviceBuf<unsigned char> depthStage;
   size_t depthStageCap = 0;
+  /* the depth warp (section 7v): a record per frame and the call's views, one per frame; counted as workspace */
+  ssd_pass_records<ssd_depth_warp_stats> warp;
+  ssd_upload_table<ssd_depth_warp_view> warpViews;
+  /* ssd_process_depth_host_warp_fused: a slice's warped frames, which its fusion reads into depthStage; staging like depthStage, not
+   * counted as workspace */
+  ssd::DeviceBuf<unsigned char> warpStage;
+  size_t warpStageCap = 0;
 };
 
 /* The single pass's planes - dPlaneImg and dFallback of every workspace and the pinned hFallback, zeroed - for ALL workspaces of the

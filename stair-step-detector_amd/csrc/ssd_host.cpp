@@ -10,6 +10,7 @@
 #include "ssd_pose.h"
 #include "ssd_fuse.h"
 #include "ssd_edges.h"
+#include "ssd_warp.h"
 #include "ssd_refit.h"
 #include "ssd_clearance.h"
 #include "ssd_treadgrid.h"
@@ -1295,6 +1296,21 @@ static void rodrigues(const double w[3], double R[3][3])
     }
 }
 
+/* e = T p + c: ToExternalWorld behind CameraToWorld, a calibration as the affine map camera -> external world (ssd_stair_pose_solve,
+ * ssd_depth_warp_view_between) */
+static void camera_to_external(const ssd_calibration &cal, double (&T)[3][3], double (&c)[3])
+{
+  for(int j = 0; j < 3; j++)
+  {
+    T[0][j] = cal.r2[0] * cal.a[j] + cal.r2[1] * cal.a[3 + j];
+    T[1][j] = cal.r2[2] * cal.a[j] + cal.r2[3] * cal.a[3 + j];
+    T[2][j] = cal.a[6 + j];
+  }
+  c[0] = (cal.r2[0] * cal.b[0] + cal.r2[1] * cal.b[1]) + cal.t2[0];
+  c[1] = (cal.r2[2] * cal.b[0] + cal.r2[3] * cal.b[1]) + cal.t2[1];
+  c[2] = cal.b[2] + cal.world_z;
+}
+
 int ssd_stair_pose_solve(const ssd_stair_pose_moments *moments, const ssd_stair_pose_target *target, int min_points, double observable,
                          ssd_stair_pose *out)
 {
@@ -1311,17 +1327,8 @@ int ssd_stair_pose_solve(const ssd_stair_pose_moments *moments, const ssd_stair_
   out->status = SSD_GF_FEW;
   const int64_t need = min_points > 1 ? min_points : 1;
   const int nSteps = (st.status & SSD_ST_THROW) ? 0 : st.n_steps;
-  /* e = T p + c: ToExternalWorld behind CameraToWorld */
   double T[3][3], c[3];
-  for(int j = 0; j < 3; j++)
-  {
-    T[0][j] = prior.r2[0] * prior.a[j] + prior.r2[1] * prior.a[3 + j];
-    T[1][j] = prior.r2[2] * prior.a[j] + prior.r2[3] * prior.a[3 + j];
-    T[2][j] = prior.a[6 + j];
-  }
-  c[0] = (prior.r2[0] * prior.b[0] + prior.r2[1] * prior.b[1]) + prior.t2[0];
-  c[1] = (prior.r2[2] * prior.b[0] + prior.r2[3] * prior.b[1]) + prior.t2[1];
-  c[2] = prior.b[2] + prior.world_z;
+  camera_to_external(prior, T, c);
   std::vector<PoseClassFit> used;
   for(int k = 0; k < nSteps; k++)
   {
@@ -1633,6 +1640,108 @@ int ssd_depth_edges_host(int width, int height, const uint16_t *frame, const ssd
         rec[kEdgeSumSupport] += c;
     }
   std::memcpy(stats, rec, sizeof(*stats));
+  return SSD_OK;
+}
+
+/* ---- depth warp: the frame another pose would have seen (include/ssd_hip.h) ---------------------------------- */
+
+/* the refusals about the views and the target that the host statement, the enqueue and the host-fed form share */
+int check_warp_views(const std::string &me, const ssd_depth_warp_view *views, int nviews, const ssd_intrinsics *dst)
+{
+  if(!views || !dst)
+    return fail(SSD_E_ARG, me + ": null views or dst");
+  if(!good_intrinsics(*dst))
+    return fail(SSD_E_ARG, me + ": dst holds no valid intrinsics");
+  for(int i = 0; i < nviews; i++)
+  {
+    bool finite = true;
+    for(int k = 0; k < 9; k++) finite = finite && std::isfinite(views[i].r[k]);
+    for(int k = 0; k < 3; k++) finite = finite && std::isfinite(views[i].t[k]);
+    if(!finite || !good_intrinsics(views[i].src))
+      return fail(SSD_E_ARG, me + ": view " + std::to_string(i) + " has a non-finite entry or no valid intrinsics");
+  }
+  return SSD_OK;
+}
+
+int ssd_depth_warp_host(int width, int height, const uint16_t *frame, const ssd_depth_warp_view *view, const ssd_intrinsics *dst, uint16_t *out,
+                        ssd_depth_warp_stats *stats)
+{
+  const std::string me("ssd_depth_warp_host");
+  if(!frame || !out || !stats || width <= 0 || height <= 0)
+    return fail(SSD_E_ARG, me + ": bad argument");
+  const int rc = check_warp_views(me, view, 1, dst);
+  if(rc) return rc;
+  const WarpTarget T = warp_target(*dst);
+  const size_t n = static_cast<size_t>(width) * height;
+  std::memset(out, 0, n * sizeof(uint16_t));
+  std::vector<float> xm(static_cast<size_t>(width));
+  for(int u = 0; u < width; u++)
+    xm[u] = warp_map_x(view->src, u);
+  int64_t rec[kWarpWords] = {};
+  for(int v = 0; v < height; v++)
+  {
+    const float ym = warp_map_y(view->src, v);
+    for(int u = 0; u < width; u++)
+    {
+      int a, b;
+      uint32_t q;
+      const int cls = warp_sample(*view, T, width, height, frame[static_cast<size_t>(v) * width + u], xm[u], ym, a, b, q);
+      rec[cls]++;
+      if(cls != kWarpNLanded)
+        continue;
+      uint16_t &o = out[static_cast<size_t>(b) * width + a];
+      if(o == 0)
+        rec[kWarpNFilled]++;
+      o = static_cast<uint16_t>(warp_min(o, q));
+    }
+  }
+  std::memcpy(stats, rec, sizeof(*stats));
+  return SSD_OK;
+}
+
+int ssd_depth_warp_view_between(const ssd_camera *src, const ssd_camera *dst, ssd_depth_warp_view *out)
+{
+  const std::string me("ssd_depth_warp_view_between");
+  if(!src || !dst || !out)
+    return fail(SSD_E_ARG, me + ": null");
+  if(!src->has_intrinsics || !good_intrinsics(src->intr))
+    return fail(SSD_E_ARG, me + ": src has no (valid) intrinsics");
+  double Ts[3][3], cs[3], Td[3][3], cd[3];
+  camera_to_external(src->cal, Ts, cs);
+  camera_to_external(dst->cal, Td, cd);
+  bool finite = true;
+  for(int i = 0; i < 3; i++)
+  {
+    finite = finite && std::isfinite(cs[i]) && std::isfinite(cd[i]);
+    for(int j = 0; j < 3; j++)
+      finite = finite && std::isfinite(Ts[i][j]) && std::isfinite(Td[i][j]);
+  }
+  if(!finite)
+    return fail(SSD_E_ARG, me + ": a calibration has a non-finite entry");
+  /* T_dst^-1 by cofactors */
+  double co[3][3];
+  for(int i = 0; i < 3; i++)
+    for(int j = 0; j < 3; j++)
+    {
+      const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+      co[i][j] = Td[i1][j1] * Td[i2][j2] - Td[i1][j2] * Td[i2][j1];
+    }
+  const double det = (Td[0][0] * co[0][0] + Td[0][1] * co[0][1]) + Td[0][2] * co[0][2];
+  if(!(std::fabs(det) >= 1e-9) || !std::isfinite(det))
+    return fail(SSD_E_ARG, me + ": dst's calibration is singular (|det| < 1e-9)");
+  double inv[3][3];
+  for(int i = 0; i < 3; i++)
+    for(int j = 0; j < 3; j++)
+      inv[i][j] = co[j][i] / det;
+  std::memset(out, 0, sizeof(*out));
+  const double dc[3] = { cs[0] - cd[0], cs[1] - cd[1], cs[2] - cd[2] };
+  for(int i = 0; i < 3; i++)
+  {
+    for(int j = 0; j < 3; j++)
+      out->r[3 * i + j] = (inv[i][0] * Ts[0][j] + inv[i][1] * Ts[1][j]) + inv[i][2] * Ts[2][j];
+    out->t[i] = (inv[i][0] * dc[0] + inv[i][1] * dc[1]) + inv[i][2] * dc[2];
+  }
+  out->src = src->intr;
   return SSD_OK;
 }
 

@@ -244,3 +244,42 @@ void launch_depth_edges(const void *frames, size_t strideBytes, int W, int H, in
 }
 
 } // namespace ssd
+
+/* k_depth_warp, the fifth stand-alone frame pass and the first scatter: its body in a header, its launcher here */
+#include "ssd_k_warp.h"
+
+namespace ssd
+{
+
+void launch_depth_warp(const void *frames, size_t strideBytes, int W, int H, int nframes, const ssd_depth_warp_view *views,
+                       const ssd_intrinsics &dst, void *out, size_t outStride, ssd_depth_warp_stats *stats, hipStream_t s)
+{
+  const int nPoints = W * H;
+  /* the wide body: 128-bit loads of eight pixels.  The scatter goes word by word whatever the output's alignment */
+  const bool wide = aligned_to(frames, strideBytes, 16);
+  /* blocks per frame: a block makes the maps (W + H divisions) before its first step, so it takes up to eight steps of the loop per lane
+   * where that still leaves 2048 blocks in all (256 CUs x 8), never fewer than one step */
+  const int work = (nPoints + kWarpPerLane * kWarpThreads - 1) / (kWarpPerLane * kWarpThreads);
+  int steps = static_cast<int>(static_cast<long long>(work) * nframes / 2048);
+  if(steps > 8) steps = 8;
+  if(steps < 1) steps = 1;
+  int blocks = (work + steps - 1) / steps;
+  if(blocks < 1) blocks = 1;
+  WarpArgs A;
+  A.frames = static_cast<const unsigned char *>(frames);
+  A.strideBytes = strideBytes;
+  A.out = static_cast<unsigned char *>(out);
+  A.outStride = outStride;
+  A.views = views;
+  A.stats = reinterpret_cast<unsigned long long *>(stats);
+  A.W = W; A.H = H; A.nframes = nframes; A.blocksPerFrame = blocks;
+  A.dst = dst;
+  const dim3 grid(static_cast<unsigned int>(blocks) * nframes), block(kWarpThreads);
+  const size_t lds = warp_lds_bytes(W, H);
+  if(wide)
+    hipLaunchKernelGGL((k_depth_warp<true>), grid, block, lds, s, A);
+  else
+    hipLaunchKernelGGL((k_depth_warp<false>), grid, block, lds, s, A);
+}
+
+} // namespace ssd
