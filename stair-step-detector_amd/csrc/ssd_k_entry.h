@@ -4,11 +4,11 @@
 #ifndef SSD_K_ENTRY_H_
 #define SSD_K_ENTRY_H_
 /* The device code is compiled in more than one translation unit.  In ssd_kernels.hip it is the one-calibration path: every
- * kernel takes the handle's constants by value.  ssd_kernels_cams.hip and ssd_kernels_refit.hip define SSD_CAMERAS_TU before
- * their first include (this is the one place that spells the macros by it): the kernels whose body stands in the entry point
- * itself become device functions there (SSD_ENTRY gives them
- * their second name, SSD_BYVAL turns the by-value constants into references), and the cameras entry points
- * call them with the frame's camera record.
+ * kernel takes the handle's constants by value.  ssd_kernels_cams.hip, which includes that file for the stages' bodies, and
+ * ssd_kernels_refit.hip, which includes only the stage headers it builds on, define SSD_CAMERAS_TU before their first include (this
+ * is the one place that spells the macros by it): the kernels whose body stands in the entry point itself become device functions
+ * there (SSD_ENTRY gives them their second name, SSD_BYVAL turns the by-value constants into references), and the cameras entry
+ * points call them with the frame's camera record.
  * Without SSD_CAMERAS_TU both macros spell exactly the entry point, so ssd_kernels.hip's code does not change.
  * That rule - a kernel's code object stays byte for byte what it was - holds for the chain K0 - K5, which bench.py measures.  The
  * extension kernels K6 - K8 (labels, surface moments, the refit, the three riser passes) are written from shared pieces and held to

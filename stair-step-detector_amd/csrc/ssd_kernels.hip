@@ -25,23 +25,26 @@
  * Nothing the predictor says can change a result ("The single pass").
  */
 /* What the stages share stands in headers that compile alone - ssd_k_entry.h (SSD_ENTRY / SSD_BYVAL and the tools builds' macros),
- * ssd_k_point.h, ssd_k_cells.h, ssd_k_windows.h - and the launch rules in ssd_launch_rules.h; the stages' bodies, K1 to K6, stand here
- * (DESIGN.md section 3b).  So this file is still compiled more than once: by itself it is the one-calibration path, and
- * ssd_kernels_cams.hip and ssd_kernels_refit.hip define SSD_CAMERAS_TU and include it for the device code alone (ssd_k_entry.h says
- * what the macro does to the kernels whose body stands in the entry point).  The entry points that only call a stage's *_block, and
- * the launchers, stand in one stretch at the end of the file: what such an includer leaves out, and all that it leaves out. */
+ * ssd_k_point.h, ssd_k_cells.h, ssd_k_windows.h, ssd_prefilter.h - and the launch rules in ssd_launch_rules.h.  The chain's bodies,
+ * K1, K0, K1b, K2, K3, K3b, K4 and K5, stand here; the extension stages are headers too, included where their text stood:
+ * ssd_k_decide.h (quad_decide, K4's and the labels'), ssd_k_labels.h (K7) and ssd_k_moments.h (K8) behind K4, ssd_k_risers.h (K6) behind
+ * K5 (with the reason why the place matters).  For the chain's bodies this file is still compiled twice: by itself
+ * it is the one-calibration path, and ssd_kernels_cams.hip defines SSD_CAMERAS_TU and includes it for the device code alone
+ * (ssd_k_entry.h says what the macro does to the kernels whose body stands in the entry point).  The entry points that only call a
+ * stage's *_block, and the launchers, stand in one stretch at the end of the file: what that includer leaves out, and all that it
+ * leaves out. */
 #include "ssd_k_entry.h"
 #include "ssd_k_point.h"
 #include "ssd_k_cells.h"
 #include "ssd_k_windows.h"
+#include "ssd_prefilter.h"   /* the per-point pre-filter: pre_range, the doubles' rows from K1Consts, pre_pixel, the edge table */
+#include "ssd_k_decide.h"    /* quad_decide: a template, so its place among the kernels is free */
 
 namespace ssd
 {
 
 /* The streaming kernels are written as block bodies over an explicit LDS struct, (frame, chunk) given by the caller:
  * the kernels below pass blockIdx (tools and experiments have paired two bodies in one launch: DESIGN.md section 3). */
-
-#include "ssd_prefilter.h"   /* the per-point pre-filter: pre_range, the doubles' rows from K1Consts, pre_pixel, the edge table */
 
 /* the cell's five reductions over the 16 lanes of a DPP row (groups: OR; the box: two minima, two maxima of the lanes' d), in one
  * block of twenty instructions behind a two-cycle no-op, the five chains interleaved so that no DPP operand is read within two instructions of its write
@@ -2208,89 +2211,6 @@ struct InquadLds
   int stripMax[kMaxGroundStrips];               /* FrameState::groundStripMax as the block found it, raised by its own centre-column pixels */
 };
 
-/* The per-point decision of k_inquad and k_labels, for one point slot of the wave: the live quadrilateral of the point's height bin
- * (q; kMaxLive = none) and whether the point counts.  LABELS = false (k_inquad): a ground point inside the ground quadrilateral, a
- * tread point outside its tread's; LABELS = true (k_labels): a point inside the quadrilateral of its bin, ground and treads alike.
- * Also d (the point on K1's grid), M / M3 (the magnitudes the bounds use), mSlow (the lanes that went through the doubles) and
- * mGround (the lanes whose bin is the ground's), which k_inquad's ground raster reads after it. */
-template<bool CHECKS, bool LABELS>
-__device__ __forceinline__ void quad_decide(const F3 &p, const PreXY &Q, const PreLane lc, const QuadEdgesF *edges,
-                                            const unsigned char *lut, const QuadTest *qts, const K1Consts &kc,
-                                            const int gSlot, f32x2 &dOut, float &MOut, float &M3Out, unsigned int &qOut,
-                                            unsigned long long &mSlowOut, unsigned long long &mCountOut, unsigned long long &mGroundOut)
-{
-  /* Round 6: every decision in single precision first, as K1 takes them (ssd_prexy.h) - the x / y range, the z range and the
-   * height bin, then the quadrilateral as four half-planes on the same d (ssd_quadtest.h, build_quad_edges) - and kept as the
-   * wave's lane masks; the reference's doubles - all three rows, the compares, the bin, QuadrilateralTest with its box, map and
-   * segments - only for the points within a bound of a limit, a bin edge or a quadrilateral's edge: one wave-uniform block, a wave
-   * slot in twenty.  (Until here that test ran for every point of every cell an edge passes through, nested and divergent:
-   * 169 vector instructions per point slot, two thirds of the kernel - profiles/r06_k4_ground_kernel.txt.) */
-  const PreRange r = pre_range<CHECKS, LABELS>(p, Q, lc);
-  const float M3 = r.M3;
-  f32x2 d = r.d;
-  unsigned long long mSlow = r.mSlow;
-  /* the bin's quadrilateral (row kMaxLive: none) and its four edges on d */
-  unsigned int q = kMaxLive;
-  if(__builtin_amdgcn_inverse_ballot_w64(r.mInSure))
-    q = SSD_CHK(28, r.b, kMaxBins) ? lut[r.b] : kMaxLive;
-  const unsigned long long mLive = __ballot(q != static_cast<unsigned int>(kMaxLive));
-  const QuadEdgesF &E = edges[q];
-  const float4 gx = *reinterpret_cast<const float4 *>(E.gx), gy = *reinterpret_cast<const float4 *>(E.gy), g2 = *reinterpret_cast<const float4 *>(E.g2);
-  f32x2 e01 = __builtin_elementwise_fma(f32x2{ gx.x, gx.y }, f32x2{ d.x, d.x }, f32x2{ g2.x, g2.y });
-  f32x2 e23 = __builtin_elementwise_fma(f32x2{ gx.z, gx.w }, f32x2{ d.x, d.x }, f32x2{ g2.z, g2.w });
-  e01 = __builtin_elementwise_fma(f32x2{ gy.x, gy.y }, f32x2{ d.y, d.y }, e01);
-  e23 = __builtin_elementwise_fma(f32x2{ gy.z, gy.w }, f32x2{ d.y, d.y }, e23);
-  const float emin = min3_f32(e01.x, e01.y, min_f32(e23.x, e23.y));
-  const float hq = __builtin_fmaf(M3, Q.dK, E.m);              /* infinity for the row "none" and for a quadrilateral single precision does not serve */
-  /* (Measured and not kept: a flag on the list for the cells that lie wholly inside their quadrilaterals - the ground's interior,
-   * 58 % of the cells walked - and a wave-uniform branch around these twelve instructions: 0.62 -> 0.70 ms, the branch costs more
-   * than it skips.) */
-#if defined(SSD_SABOTAGE_PRE) && (SSD_SABOTAGE_PRE & 4)   /* tools: the band along the edges NOT handed to the doubles - the tests built for it must fail */
-  const unsigned long long mSureQ = mLive;
-#elif defined(SSD_SABOTAGE_PRE) && (SSD_SABOTAGE_PRE & 32)  /* tools: k_labels alone keeps the half-planes' answer inside the quadrilateral band */
-  const unsigned long long mSureQ = LABELS ? mLive : __ballot(__builtin_fabsf(emin) > hq);
-#else
-  const unsigned long long mSureQ = __ballot(__builtin_fabsf(emin) > hq);
-#endif
-  const unsigned long long mOutQ = __ballot(emin < 0.0f);
-  unsigned long long mGround = __ballot(q == static_cast<unsigned int>(gSlot));
-  /* k_inquad: for the ground the points inside its quadrilateral count, for treads the points outside theirs (k_raster summed
-   * the plateau whole); k_labels: the points inside, ground and treads alike */
-  unsigned long long mCount = mSureQ & (LABELS ? ~mOutQ : (mGround ^ mOutQ));
-  mSlow |= mLive & ~mSureQ;
-  if(__builtin_expect(mSlow != 0ull, 0))
-  {
-    /* rare, wave-uniform so that the masks stay scalars: the reference's arithmetic, all of it, for the lanes it is for */
-    const K1ConstsLds c = k1_consts(kc);
-    const World3 w = world_rows(c, p);
-    const bool mine = __builtin_amdgcn_inverse_ballot_w64(mSlow);
-    const bool inRange = world_in_range(c, w);
-    unsigned int qD = kMaxLive;
-    bool counts = false;
-    if(mine && inRange)
-    {
-      const int bD = world_bin(c, w);
-      qD = SSD_CHK(29, bD, kMaxBins) ? lut[bD] : kMaxLive;
-      if(qD != static_cast<unsigned int>(kMaxLive))
-      {
-        const QuadTest &tq = qts[qD];
-        const bool fast = w.x >= tq.fx0 && w.x < tq.fx1 && w.y >= tq.fy0 && w.y < tq.fy1;
-        const bool inside = fast || quad_test(tq, w.x, w.y);
-        counts = LABELS ? inside : inside == (qD == static_cast<unsigned int>(gSlot));
-      }
-    }
-    mCount = (mCount & ~mSlow) | __ballot(counts);
-    mGround = (mGround & ~mSlow) | __ballot(qD == static_cast<unsigned int>(gSlot));
-    q = mine ? qD : q;
-    /* (each component inside its own conditional, as written: taken whole in front of them the wave's rare block costs
-     * k_inquad four more vector registers) */
-    d.x = mine ? d_from_world(c, w).x : d.x;
-    d.y = mine ? d_from_world(c, w).y : d.y;
-  }
-  dOut = d; MOut = r.M; M3Out = M3; qOut = q;
-  mSlowOut = mSlow; mCountOut = mCount; mGroundOut = mGround;
-}
-
 template<int SRC, bool FULL, bool CHECKS>
 __device__ __forceinline__ void inquad_block(InquadLds<FULL> &L, const float *__restrict__ xyz, size_t strideFloats, const PointParams &P,
                                              const PreXY &Q, const PixelParams &X, FrameState *__restrict__ st,
@@ -2647,401 +2567,14 @@ __device__ __forceinline__ void inquad_block(InquadLds<FULL> &L, const float *__
   ph.finish();
 }
 
-/* ========================================================================= */
-/* K7 (extension): per-pixel surface labels                                    */
+} // namespace ssd
 
-/* Label of point i of a frame (= camera pixel v W + u): k + 1 if the point is one of those whose mean is surface k of the frame's
- * result (ground first, then the valid steps ascending: k_final's order), else 0 (include/ssd_hip.h, SSD_LABEL_NONE).  That is
- * k_inquad's decision taken for every point of a live quadrilateral's bins: quad_decide<.., true>.  Runs after k_final (it reads
- * the frame's status) on the same FrameState; writes every byte of [0, W H) of the frame's row once, nothing else. */
-struct LabelsLds
+/* K7 and K8 (extensions), at their place in the order of definitions: the labels, then the surface moments */
+#include "ssd_k_labels.h"
+#include "ssd_k_moments.h"
+
+namespace ssd
 {
-  QuadTest qts[kMaxLive];                       /* as InquadLds */
-  QuadEdgesF edges[kMaxLive + 1];
-  K1Consts kc;
-  unsigned char lut[kMaxBins];                  /* bin -> live slot, kMaxLive = none */
-  unsigned char label[kMaxLive + 1];            /* live slot -> label (the surface's place in the result + 1); row kMaxLive: 0 */
-  unsigned short cellList[kMaxCellsPerBlock];
-  unsigned int listScratch[2 * kWavesPerBlock];
-};
-
-/* four labels of the points idx .. idx + 3 (idx a multiple of 4): one 32-bit store where the row is 4-byte aligned and whole */
-__device__ __forceinline__ void store_labels4(unsigned char *__restrict__ row, bool aligned4, int idx, int nPoints, unsigned int word)
-{
-  if(aligned4 && idx + 4 <= nPoints)
-    *reinterpret_cast<unsigned int *>(row + idx) = word;
-  else
-  {
-#pragma unroll
-    for(int k = 0; k < 4; k++)
-      if(idx + k < nPoints)
-        row[idx + k] = static_cast<unsigned char>(word >> (8 * k));
-  }
-}
-
-/* ---- what K6 - K8 share (the labels, the surface moments and the refit here; the three riser passes below) ---- */
-
-/* A block's chunk of a frame: the frame's points, and K1's records of the chunk's cells. */
-struct Chunk
-{
-  const float *base;
-  const uint2 *cells;
-  int cell0, nCells;
-};
-template<int SRC>
-__device__ __forceinline__ Chunk chunk_of(const float *__restrict__ xyz, size_t strideFloats, const uint2 *__restrict__ tileMasks, size_t tileMaskStride,
-                                          int chunkPoints, int nPoints)
-{
-  const int frame = blockIdx.x;
-  Chunk c;
-  c.base = SRC == kSrcDepth16
-    ? reinterpret_cast<const float *>(reinterpret_cast<const unsigned short *>(xyz) + static_cast<size_t>(frame) * strideFloats)
-    : xyz + static_cast<size_t>(frame) * strideFloats;
-  const int begin = blockIdx.y * chunkPoints;
-  const int end = min(begin + chunkPoints, nPoints);
-  c.cell0 = begin / kCell;
-  c.nCells = (end - begin + kCell - 1) / kCell;
-  c.cells = tileMasks + static_cast<size_t>(frame) * tileMaskStride + c.cell0;
-  return c;
-}
-
-/* The chunk's cells that hold a bin of `wanted`, listed in order, and the wave's share of the list: groups g .. gEnd - 1 of four cells,
- * entry 4 g + (lane >> 4) of the list for each row of sixteen lanes (load_cell). */
-struct CellWalk { int count, g, gEnd; };
-__device__ __forceinline__ CellWalk wanted_cells(const Chunk &c, int cols, unsigned int wanted, unsigned short *cellList, unsigned int *listScratch)
-{
-  CellWalk w;
-  w.count = cell_list_build(c.cells, c.nCells, cols, [&](const uint2 info) { return (info.x & wanted) != 0u; }, cellList, listScratch);
-  const int nGroups = (w.count + 3) >> 2, wave = threadIdx.x >> 6;
-  w.g = wave * nGroups / kWavesPerBlock;
-  w.gEnd = (wave + 1) * nGroups / kWavesPerBlock;
-  return w;
-}
-
-/* The frame's live state into the block's LabelsLds, for every kernel that takes k_inquad's decision once more (quad_decide<.., true>);
- * the caller's barrier follows.  Nothing of a frame k_quads found no live quadrilateral in, or whose quadrilaterals the reference would
- * have thrown on, is labelled: wanted = 0 then (block-uniform), and nothing is staged. */
-struct LiveFrame
-{
-  bool live;
-  unsigned int wanted;                          /* the bin groups of the live quadrilaterals */
-  int nLive, gSlot;                             /* the live slots, and the ground's among them (-1: none) */
-};
-__device__ __forceinline__ LiveFrame labels_stage(LabelsLds &L, const FrameState &fs, const PointParams &P, const PreXY &Q)
-{
-  const int tid = threadIdx.x;
-  LiveFrame f;
-  f.live = fs.anyActive != 0u && (fs.status & SSD_ST_THROW) == 0u;
-  f.wanted = f.live ? fs.wantedQuads : 0u;
-  f.nLive = 0;
-  f.gSlot = -1;
-  if(f.live)
-  {
-    f.nLive = fs.nLive;
-    f.gSlot = (f.nLive > 0 && fs.accActive[kGroundAcc]) ? f.nLive - 1 : -1;           /* the ground is the last live slot */
-    if(tid < kMaxBins)
-    {
-      const unsigned char s = fs.lutLive[tid];
-      L.lut[tid] = s == 0xff ? static_cast<unsigned char>(kMaxLive) : s;
-    }
-    if(tid <= kMaxLive)
-    {
-      /* slot order = accumulator order (treads ascending, the ground last); the result has the ground first */
-      int lab = 0;
-      if(tid < f.nLive)
-        lab = tid == f.gSlot ? 1 : tid + 1 + (f.gSlot >= 0 ? 1 : 0);
-      L.label[tid] = static_cast<unsigned char>(lab <= SSD_MAX_STEPS ? lab : 0);
-    }
-    constexpr int qtWords = kMaxLive * static_cast<int>(sizeof(QuadTest) / 4);
-    constexpr int egWords = kMaxLive * static_cast<int>(sizeof(QuadEdgesF) / 4);
-    for(int w = tid; w < qtWords; w += kThreads)
-      reinterpret_cast<unsigned int *>(L.qts)[w] = reinterpret_cast<const unsigned int *>(fs.qtLive)[w];
-    stage_quad_edges(L.edges, fs.edgeLive, egWords, Q.dE0);
-    if(tid == 0)
-      k1_consts_fill(L.kc, P, nullptr);
-  }
-  return f;
-}
-
-/* the point's label by the decision of quad_decide<.., true>: the live slot's, 0 where the point is in none */
-template<bool CHECKS>
-__device__ __forceinline__ unsigned int label_of(const F3 &p, const PreXY &Q, const PreLane lc, const LabelsLds &L)
-{
-  f32x2 d;
-  float M, M3;
-  unsigned int q;
-  unsigned long long mSlow, mIn, mGround;
-  quad_decide<CHECKS, true>(p, Q, lc, L.edges, L.lut, L.qts, L.kc, -1, d, M, M3, q, mSlow, mIn, mGround);
-  return __builtin_amdgcn_inverse_ballot_w64(mIn) ? L.label[min(q, static_cast<unsigned int>(kMaxLive))] : 0u;
-}
-
-template<int SRC, bool CHECKS>
-SSD_ENTRY(__launch_bounds__(kThreads), k_labels, labels_block)(const float *__restrict__ xyz, size_t strideFloats, SSD_BYVAL(PointParams) P, SSD_BYVAL(PreXY) Q,
-                                                     const FrameState *__restrict__ st, const uint2 *__restrict__ tileMasks,
-                                                     size_t tileMaskStride, int chunkPoints, SSD_BYVAL(DepthSrc) D,
-                                                     unsigned char *__restrict__ labels, size_t labelStride)
-{
-  __shared__ LabelsLds L;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int frame = blockIdx.x;
-  /* labels_stage's text, and not a call of it: staged through the function this kernel takes 95 scalar registers for 71 and its
-   * 16-bit depth instantiations 5 to 8 % longer on an MI355X (profiles/extension_kernels_shared.txt) */
-  const FrameState &fs = st[frame];
-  const bool live = fs.anyActive != 0u && (fs.status & SSD_ST_THROW) == 0u;
-  const unsigned int wanted = live ? fs.wantedQuads : 0u;
-  if(live)
-  {
-    const int nLive = fs.nLive;
-    const int gSlot = (nLive > 0 && fs.accActive[kGroundAcc]) ? nLive - 1 : -1;
-    if(tid < kMaxBins)
-    {
-      const unsigned char s = fs.lutLive[tid];
-      L.lut[tid] = s == 0xff ? static_cast<unsigned char>(kMaxLive) : s;
-    }
-    if(tid <= kMaxLive)
-    {
-      int lab = 0;
-      if(tid < nLive)
-        lab = tid == gSlot ? 1 : tid + 1 + (gSlot >= 0 ? 1 : 0);
-      L.label[tid] = static_cast<unsigned char>(lab <= SSD_MAX_STEPS ? lab : 0);
-    }
-    constexpr int qtWords = kMaxLive * static_cast<int>(sizeof(QuadTest) / 4);
-    constexpr int egWords = kMaxLive * static_cast<int>(sizeof(QuadEdgesF) / 4);
-    for(int w = tid; w < qtWords; w += kThreads)
-      reinterpret_cast<unsigned int *>(L.qts)[w] = reinterpret_cast<const unsigned int *>(fs.qtLive)[w];
-    stage_quad_edges(L.edges, fs.edgeLive, egWords, Q.dE0);
-    if(tid == 0)
-    {
-      K1Consts &c = L.kc;
-      for(int i = 0; i < 9; i++)
-        c.a[i] = P.a[i];
-      c.b[0] = P.b[0]; c.b[1] = P.b[1]; c.b[2] = P.b[2];
-      c.xMin = P.xMin; c.xMax = P.xMax; c.yMin = P.yMin; c.yMax = P.yMax; c.zMin = P.zMin; c.zMax = P.zMax;
-      c.boxX = P.boxX; c.boxY = P.boxY;
-      c.recip = P.recip;
-      c.xToImage = 0.0; c.yToImage = 0.0;
-    }
-  }
-  __syncthreads();
-
-  const Chunk c = chunk_of<SRC>(xyz, strideFloats, tileMasks, tileMaskStride, chunkPoints, P.nPoints);
-  unsigned char *row = labels + static_cast<size_t>(frame) * labelStride;
-
-  /* the cells that hold no bin of a live quadrilateral: zeros, without a look at their points (16 bytes a lane where the row allows) */
-  const bool aligned16 = (reinterpret_cast<uintptr_t>(row) & 15u) == 0;
-  constexpr int kUnits = kCell / 16;
-  for(int u = tid; u < c.nCells * kUnits; u += kThreads)
-  {
-    const int cell = u / kUnits;
-    if((c.cells[cell].x & wanted) != 0u)
-      continue;
-    const int idx = (c.cell0 + cell) * kCell + 16 * (u - cell * kUnits);
-    if(aligned16 && idx + 16 <= P.nPoints)
-      *reinterpret_cast<uint4 *>(row + idx) = make_uint4(0u, 0u, 0u, 0u);
-    else
-      for(int k = 0; k < 16 && idx + k < P.nPoints; k++)
-        row[idx + k] = 0;
-  }
-  if(wanted == 0u)
-    return;
-
-  /* the others, in order (one column of cells: the list is the chunk's cells ascending), four cells per wave iteration */
-  const CellWalk w = wanted_cells(c, 1, wanted, L.cellList, L.listScratch);
-  const bool aligned4 = (reinterpret_cast<uintptr_t>(row) & 3u) == 0;
-  const PreLane lc(Q);
-  for(int g = w.g; g < w.gEnd; g++)
-  {
-    const int entry = 4 * g + (lane >> 4);
-    F3 v[kPts];
-    load_cell<SRC>(c.base, c.cell0, L.cellList, entry, w.count, lane, P.nPoints, v, D);
-    unsigned int word = 0u;
-#pragma unroll
-    for(int j = 0; j < kPts; j++)
-      word |= label_of<CHECKS>(v[j], Q, lc, L) << (8 * j);
-    if(entry < w.count)
-      store_labels4(row, aligned4, (c.cell0 + static_cast<int>(L.cellList[entry])) * kCell + kPts * (lane & 15), P.nPoints, word);
-  }
-}
-
-/* ========================================================================= */
-/* K8 (extension): per-surface integer moments (the surface fit)                */
-
-/* k_labels' sibling: the same cells, the same decision (quad_decide<.., true>), and in place of a byte per point the ten integer sums
- * of ssd_ground_moments (ssd_moments.h) per surface - surface k's over exactly the points k_labels gives label k + 1 - plus n_far, the
- * labelled points the fixed-point rule leaves out.  A cell holding no bin of a live quadrilateral is neither read nor touched.
- * A lane keeps the sums of ONE surface in registers, the wave's current one (wave-uniform; rows of the camera image mostly lie on one
- * surface).  When no lane of a point slot has the current surface and some have another, the wave's sums go to the block's LDS table
- * (shuffles, then 64-bit LDS adds by lane 0) and the wave changes over; the lanes of a mixed slot that hold another surface than the
- * current one add their point to the LDS table directly.  At the block's end one 64-bit atomicAdd per non-zero entry of the table goes
- * to the frame's record, which the caller zeroed on the stream.  Integer addition throughout: no result depends on an order.
- * Camera batches: k_surface_moments_cams (ssd_kernels_cams.hip) runs this body with the frame's own constants. */
-constexpr int kSurfaceSums = kGroundSums + 1;       /* ssd_surface_moments as 11 int64: the ten sums, n_far */
-static_assert(sizeof(ssd_surface_moments) == 8 * kSurfaceSums && sizeof(ssd_frame_moments) == 8 + SSD_MAX_STEPS * 8 * kSurfaceSums,
-              "ssd_frame_moments is the kernel's record: a header of two int32, then kSurfaceSums int64 per surface");
-static_assert(SSD_MAX_STEPS * kSurfaceSums <= kThreads, "one thread per entry of the block's table");
-
-struct SurfaceLds
-{
-  LabelsLds l;
-  unsigned long long sums[SSD_MAX_STEPS][kSurfaceSums];
-};
-
-/* Integer sums keyed by a wave-uniform current key (a surface, a riser), for k_surface_moments, k_surface_refit and k_riser_moments: N
- * sums per key, the first kGroundSums those of ssd_ground_moments, then n_far; what lies behind is the caller's.  A lane's key is
- * 0 .. or -1 for a point that counts nowhere. */
-template<int N>
-struct KeyedSums
-{
-  long long acc[N] = {};
-  int cur = -1;                                  /* the key whose sums the wave's registers hold (-1: none yet) */
-
-  /* the wave's sums into the block's table: shuffles, then lane 0's 64-bit LDS adds */
-  __device__ __forceinline__ void flush(unsigned long long (*table)[N], int lane)
-  {
-    if(cur < 0)
-      return;
-#pragma unroll
-    for(int i = 0; i < N; i++)
-    {
-#pragma unroll
-      for(int o = 32; o >= 1; o >>= 1)
-        acc[i] += __shfl_xor(acc[i], o);
-    }
-    if(lane == 0)
-    {
-#pragma unroll
-      for(int i = 0; i < N; i++)
-        if(acc[i] != 0)
-          atomicAdd(&table[cur][i], static_cast<unsigned long long>(acc[i]));
-    }
-#pragma unroll
-    for(int i = 0; i < N; i++)
-      acc[i] = 0;
-  }
-
-  /* a point slot some of whose lanes hold a key (mKeyed, not 0): when none of them holds the current one, the wave changes over */
-  __device__ __forceinline__ void changeover(int key, unsigned long long mKeyed, unsigned long long (*table)[N], int lane)
-  {
-    if(cur < 0 || __ballot(key == cur) == 0ull)
-    {
-      flush(table, lane);
-      cur = __builtin_amdgcn_readlane(key, __ffsll(static_cast<long long>(mKeyed)) - 1);
-    }
-  }
-
-  /* the lane's point by the fixed-point rule (ssd_moments.h) on the float camera coordinates: to the wave's sums under the current key,
-   * straight to the table under another (a cell two keys share: rare), nowhere for key < 0 */
-  __device__ __forceinline__ void add(int key, const F3 &p, unsigned long long (*table)[N])
-  {
-    const double rx = moment_round(static_cast<double>(p.x)), ry = moment_round(static_cast<double>(p.y)), rz = moment_round(static_cast<double>(p.z));
-    const bool fits = moment_near(rx) && moment_near(ry) && moment_near(rz);
-    if(key == cur)
-    {
-      if(fits)
-        moment_add(rx, ry, rz, acc);
-      else
-        acc[kGroundSums] += 1;
-    }
-    else if(key >= 0)
-    {
-      unsigned long long *t = table[key];
-      if(fits)
-      {
-        long long one[kGroundSums] = {};
-        moment_add(rx, ry, rz, one);
-#pragma unroll
-        for(int i = 0; i < kGroundSums; i++)
-          atomicAdd(&t[i], static_cast<unsigned long long>(one[i]));
-      }
-      else
-        atomicAdd(&t[kGroundSums], 1ull);
-    }
-  }
-};
-
-/* the block's end, behind a barrier: a thread per entry of the table, give(key, i, sum) for every one that is not 0 */
-template<int N, typename Give>
-__device__ __forceinline__ void keyed_sums_give(const unsigned long long (*table)[N], int nKeys, Give give)
-{
-  const int tid = threadIdx.x;
-  if(tid < nKeys * N)
-  {
-    const int key = tid / N, i = tid - key * N;
-    const unsigned long long t = table[key][i];
-    if(t != 0ull)
-      give(key, i, t);
-  }
-}
-
-/* The body of k_surface_moments and, GATED, of k_surface_refit (ssd_kernels_refit.hip), for one calibration and for
- * camera batches alike.  GATED: `gates` is the batch's, G the block's copy of the frame's in LDS, and on the lane's own label the gate
- * test of ssd_refit.h - a labelled point outside its surface's gate becomes an unlabelled one BEHIND the wave-uniform skip of the slots
- * that label nothing, so the three double products are spent only where some lane has a label; a point trimmed so is counted nowhere. */
-template<int SRC, bool CHECKS, bool GATED>
-__device__ __forceinline__ void labelled_moments_block(SurfaceLds &S, ssd_frame_gates *G, const float *__restrict__ xyz, size_t strideFloats,
-                                                       const PointParams &P, const PreXY &Q, const FrameState *__restrict__ st,
-                                                       const uint2 *__restrict__ tileMasks, size_t tileMaskStride, int chunkPoints, const DepthSrc &D,
-                                                       const ssd_frame_gates *__restrict__ gates, ssd_frame_moments *__restrict__ out)
-{
-  LabelsLds &L = S.l;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int frame = blockIdx.x;
-  const LiveFrame f = labels_stage(L, st[frame], P, Q);
-  if(f.live)
-  {
-    if constexpr(GATED)
-    {
-      /* the frame's gates: 86 words, once per block */
-      static_assert(sizeof(ssd_frame_gates) % 8 == 0 && sizeof(ssd_frame_gates) / 8 <= kThreads, "one thread per 64-bit word of the frame's gates");
-      if(tid < static_cast<int>(sizeof(ssd_frame_gates) / 8))
-        reinterpret_cast<unsigned long long *>(G)[tid] = reinterpret_cast<const unsigned long long *>(gates + frame)[tid];
-    }
-    /* the record's header, by the frame's first block: the surfaces labels can name, and whether the first is the ground */
-    if(tid == 0 && blockIdx.y == 0)
-    {
-      out[frame].n_surfaces = min(f.nLive, SSD_MAX_STEPS);
-      out[frame].ground = f.gSlot >= 0 ? 1 : 0;
-    }
-  }
-  if(tid < SSD_MAX_STEPS * kSurfaceSums)
-    (&S.sums[0][0])[tid] = 0ull;
-  __syncthreads();
-  if(f.wanted == 0u)
-    return;
-
-  const Chunk c = chunk_of<SRC>(xyz, strideFloats, tileMasks, tileMaskStride, chunkPoints, P.nPoints);
-  const CellWalk w = wanted_cells(c, 1, f.wanted, L.cellList, L.listScratch);
-  const PreLane lc(Q);
-  KeyedSums<kSurfaceSums> sums;                  /* keyed by the surface: the label - 1 */
-  for(int g = w.g; g < w.gEnd; g++)
-  {
-    const int entry = 4 * g + (lane >> 4);
-    F3 v[kPts];
-    load_cell<SRC>(c.base, c.cell0, L.cellList, entry, w.count, lane, P.nPoints, v, D);
-#pragma unroll
-    for(int j = 0; j < kPts; j++)
-    {
-      const unsigned int lab = label_of<CHECKS>(v[j], Q, lc, L);
-      int k = entry < w.count ? static_cast<int>(lab) - 1 : -1;
-      if(__ballot(k >= 0) == 0ull)               /* wave-uniform: a slot none of whose points is labelled */
-        continue;
-      if constexpr(GATED)
-        k = (k >= 0 && refit_keeps(*G, k, v[j].x, v[j].y, v[j].z)) ? k : -1;
-      const unsigned long long mKeyed = __ballot(k >= 0);
-      if(mKeyed == 0ull)                         /* wave-uniform: every labelled point of the slot was trimmed */
-        continue;
-      sums.changeover(k, mKeyed, S.sums, lane);
-      sums.add(k, v[j], S.sums);
-    }
-  }
-  sums.flush(S.sums, lane);
-  __syncthreads();
-  /* one 64-bit atomicAdd per non-zero entry to the frame's record, which the caller zeroed on the stream */
-  keyed_sums_give<kSurfaceSums>(S.sums, SSD_MAX_STEPS, [&](int k, int i, unsigned long long t)
-  {
-    atomicAdd(reinterpret_cast<unsigned long long *>(out + frame) + 1 + k * kSurfaceSums + i, t);
-  });
-}
 
 /* ========================================================================= */
 /* K5: ground front edge and the per-frame result — one workgroup per frame     */
@@ -3442,297 +2975,11 @@ SSD_ENTRY(__launch_bounds__(T), k_final, final_block)(SSD_BYVAL(Params) P, Frame
   SSD_PHASE(2, 6);
 }
 
-/* ========================================================================= */
-/* K6 (extension): evidence of the vertical faces                              */
-
-/* What the three riser passes share: the block's copy of the frame's riser state with the cell list, the way into the walk, and the
- * evidence rule.  Each kernel's own table lies beside or behind the record. */
-struct RiserLds
-{
-  unsigned short cellList[kMaxCellsPerBlock];
-  unsigned int listScratch[2 * kWavesPerBlock];
-  RiserState rs[kMaxRisers];
-  signed char riserOfBin[kMaxBins];
-};
-
-/* false for a frame without risers (block-uniform: wantedRisers is set by k_final); else the frame's riser state in L, behind a barrier
- * (what the caller zeroed in front of the call is zero behind it), and the chunk's cells that hold a bin of a riser, which alone are
- * walked (as k_raster / k_inquad).  fs.nRisers is k_final's count of emitted surfaces less one: at most kMaxRisers. */
-template<int SRC>
-__device__ __forceinline__ bool riser_walk(RiserLds &L, const FrameState &fs, const float *__restrict__ xyz, size_t strideFloats, int nPoints,
-                                           const uint2 *__restrict__ tileMasks, size_t tileMaskStride, int chunkPoints, int cellCols, Chunk &c, CellWalk &w)
-{
-  const int tid = threadIdx.x;
-  const unsigned int wanted = fs.wantedRisers;
-  if(wanted == 0u)
-    return false;
-  if(tid < kMaxBins)
-    L.riserOfBin[tid] = fs.riserOfBin[tid];
-  if(tid < fs.nRisers)
-    L.rs[tid] = fs.riser[tid];
-  __syncthreads();
-  c = chunk_of<SRC>(xyz, strideFloats, tileMasks, tileMaskStride, chunkPoints, nPoints);
-  w = wanted_cells(c, cellCols, wanted, L.cellList, L.listScratch);
-  return true;
-}
-
-/* The evidence rule: then(r, sd) for a point that is evidence of riser r, sd its signed distance from the riser's edge line; nothing
- * for any other point.  The point's height lies in a bin of the riser (a bin of no plateau between the two surfaces) and strictly inside
- * its band, the point within tol of the edge line and along the edge.  (load_points gives a point beyond nPoints z = 0, and world_z
- * drops it: an evidence point lies inside the frame.)  The caller's continuation and not a returned index: returned, the 16-bit depth
- * k_risers spills 42 scalar registers to lanes for 27 and runs a third longer (profiles/extension_kernels_shared.txt). */
-template<typename Then>
-__device__ __forceinline__ void riser_evidence(const PointParams &P, const F3 &p, const RiserLds &L, double tol, Then then)
-{
-  double wx, wy, wz;
-  if(!world_z(P, p, wz))
-    return;
-  const int r = L.riserOfBin[height_bin(P, wz)];
-  if(r < 0)
-    return;
-  const RiserState &R = L.rs[r];
-  if(!(wz > R.zLo && wz < R.zHi))
-    return;
-  if(!world_xy(P, p, wx, wy))
-    return;
-  const double a = wx - R.ox, b = wy - R.oy;
-  const double sd = b * R.ux - a * R.uy;                 /* signed distance from the edge line */
-  const double t = a * R.ux + b * R.uy;                  /* position along the edge */
-  if(fabs(sd) <= tol && t >= 0.0 && t <= R.len)
-    then(r, sd);
-}
-
-template<int SRC>
-SSD_ENTRY(__launch_bounds__(kThreads, 8), k_risers, risers_block)(const float *__restrict__ xyz, size_t strideFloats, SSD_BYVAL(PointParams) P, double tol,
-                                                        FrameState *__restrict__ st, const uint2 *__restrict__ tileMasks,
-                                                        size_t tileMaskStride, int chunkPoints, int cellCols, SSD_BYVAL(DepthSrc) D)
-{
-  __shared__ RiserLds L;
-  __shared__ unsigned long long lsum[kMaxRisers][8];
-  __shared__ unsigned int lcnt[kMaxRisers][8];
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  FrameState &fs = st[blockIdx.x];
-  for(int i = tid; i < kMaxRisers * 8; i += kThreads)
-  {
-    (&lsum[0][0])[i] = 0ull;
-    (&lcnt[0][0])[i] = 0u;
-  }
-  Chunk c;
-  CellWalk w;
-  if(!riser_walk<SRC>(L, fs, xyz, strideFloats, P.nPoints, tileMasks, tileMaskStride, chunkPoints, cellCols, c, w))
-    return;
-
-  const int copy = lane & 7;
-  int curR = -1;
-  long long accS = 0;
-  unsigned int accN = 0;
-  auto flushAcc = [&]()
-  {
-    if(curR >= 0 && accN)
-    {
-      atomicAdd(&lsum[curR][copy], static_cast<unsigned long long>(accS));
-      atomicAdd(&lcnt[curR][copy], accN);
-    }
-  };
-  for(int g = w.g; g < w.gEnd; g++)
-  {
-    F3 v[kPts];
-    load_cell<SRC>(c.base, c.cell0, L.cellList, 4 * g + (lane >> 4), w.count, lane, P.nPoints, v, D);
-    #pragma unroll
-    for(int j = 0; j < kPts; j++)
-    {
-      riser_evidence(P, v[j], L, tol, [&](int r, double sd)
-      {
-        if(r != curR)
-        {
-          flushAcc();
-          curR = r; accS = 0; accN = 0;
-        }
-        accS += z_to_fixed(sd);
-        accN++;
-      });
-    }
-  }
-  flushAcc();
-  __syncthreads();
-  if(tid < fs.nRisers)
-  {
-    unsigned long long sum = 0;
-    unsigned int n = 0;
-    for(int k = 0; k < 8; k++)
-    {
-      sum += lsum[tid][k];
-      n += lcnt[tid][k];
-    }
-    if(n)
-    {
-      atomicAdd(reinterpret_cast<unsigned long long *>(&fs.rSum[tid]), sum);
-      atomicAdd(&fs.rCnt[tid], n);
-    }
-  }
-}
-
-/* k_risers' sibling (the riser fit): the same walk (riser_walk) and the same evidence rule (riser_evidence), walked
- * ONCE, and beside the count and the offset sum of every riser the ten integer sums of ssd_ground_moments (ssd_moments.h) over its evidence
- * points plus n_far, the evidence points the fixed-point rule leaves out - riser i's in record s[i] of the frame's ssd_frame_moments.
- * Accumulation is k_surface_moments' (KeyedSums, keyed by the riser) with one more sum, the offset's.  At the block's end one 64-bit
- * atomicAdd per non-zero entry goes to the frame's record, which the caller zeroed on the stream, and to k_risers' own rSum / rCnt (the
- * count is n + n_far).  Integer addition throughout: no result depends on an order, and rSum / rCnt are what k_risers leaves.
- * Camera batches: k_riser_moments_cams (ssd_kernels_cams.hip) runs this body with the frame's own constants. */
-constexpr int kRiserSums = kSurfaceSums + 1;        /* the eleven int64 of ssd_surface_moments, then the offset sum (2^-40 m) */
-constexpr int kRiserOffsetSum = kSurfaceSums;
-static_assert(kMaxRisers <= SSD_MAX_STEPS, "riser i's sums are record s[i] of an ssd_frame_moments");
-static_assert(kMaxRisers * kRiserSums <= kThreads, "one thread per entry of the block's table");
-
-struct RiserMomentsLds
-{
-  RiserLds r;
-  unsigned long long sums[kMaxRisers][kRiserSums];
-};
-
-template<int SRC>
-SSD_ENTRY(__launch_bounds__(kThreads), k_riser_moments, riser_moments_block)(const float *__restrict__ xyz, size_t strideFloats, SSD_BYVAL(PointParams) P, double tol,
-                                                        FrameState *__restrict__ st, const uint2 *__restrict__ tileMasks,
-                                                        size_t tileMaskStride, int chunkPoints, int cellCols, SSD_BYVAL(DepthSrc) D,
-                                                        ssd_frame_moments *__restrict__ out)
-{
-  __shared__ RiserMomentsLds S;
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int frame = blockIdx.x;
-  FrameState &fs = st[frame];
-  const int nR = fs.nRisers;
-  /* the record's header, by the frame's first block (also of a frame none of whose cells holds a riser's bin) */
-  if(blockIdx.y == 0 && tid == 0)
-  {
-    out[frame].n_surfaces = nR;
-    out[frame].ground = 0;
-  }
-  if(tid < kMaxRisers * kRiserSums)
-    (&S.sums[0][0])[tid] = 0ull;
-  Chunk c;
-  CellWalk w;
-  if(!riser_walk<SRC>(S.r, fs, xyz, strideFloats, P.nPoints, tileMasks, tileMaskStride, chunkPoints, cellCols, c, w))
-    return;
-
-  KeyedSums<kRiserSums> sums;                    /* keyed by the riser */
-  for(int g = w.g; g < w.gEnd; g++)
-  {
-    F3 v[kPts];
-    load_cell<SRC>(c.base, c.cell0, S.r.cellList, 4 * g + (lane >> 4), w.count, lane, P.nPoints, v, D);
-#pragma unroll
-    for(int j = 0; j < kPts; j++)
-    {
-      int r = -1;                                /* the point's riser, -1: no evidence */
-      long long sdFix = 0;
-      riser_evidence(P, v[j], S.r, tol, [&](int rb, double sd) { r = rb; sdFix = z_to_fixed(sd); });
-      const unsigned long long mEv = __ballot(r >= 0);
-      if(mEv == 0ull)                            /* wave-uniform: a slot none of whose points is evidence */
-        continue;
-      sums.changeover(r, mEv, S.sums, lane);
-      sums.add(r, v[j], S.sums);
-      /* the offset sum beside the moments */
-      if(r == sums.cur)
-        sums.acc[kRiserOffsetSum] += sdFix;
-      else if(r >= 0)
-        atomicAdd(&S.sums[r][kRiserOffsetSum], static_cast<unsigned long long>(sdFix));
-    }
-  }
-  sums.flush(S.sums, lane);
-  __syncthreads();
-  /* one 64-bit atomicAdd per non-zero entry to the frame's record, which the caller zeroed on the stream, and to k_risers' own sums */
-  keyed_sums_give<kRiserSums>(S.sums, nR, [&](int r, int i, unsigned long long t)
-  {
-    if(i == kRiserOffsetSum)
-      atomicAdd(reinterpret_cast<unsigned long long *>(&fs.rSum[r]), t);
-    else
-    {
-      atomicAdd(reinterpret_cast<unsigned long long *>(out + frame) + 1 + r * kSurfaceSums + i, t);
-      if(i == 0 || i == kGroundSums)             /* every evidence point is in n or in n_far */
-        atomicAdd(&fs.rCnt[r], static_cast<unsigned int>(t));
-    }
-  });
-}
-
-/* The riser labels (ssd_set_riser_labels): k_risers' cells (riser_walk) and k_risers' evidence rule (riser_evidence),
- * and in place of any sum one byte per evidence point, SSD_LABEL_RISER_BASE + r, at the index k_labels gives the point.  It runs behind
- * k_labels on the same stream, which has written every byte of the frame; an evidence point's bin is a bin of no plateau, so its byte
- * is a zero of k_labels' and belongs to this lane alone: single byte stores, nothing read, nothing else rewritten (the neighbouring
- * bytes are other lanes').  No sums, no atomics, no LDS beyond the frame's riser state and the cell list.  Camera batches:
- * k_riser_labels_cams (ssd_kernels_cams.hip) runs this body with the frame's own constants. */
-static_assert(SSD_LABEL_RISER_BASE > SSD_MAX_STEPS && SSD_LABEL_RISER_BASE + kMaxRisers - 1 <= 0xff, "surface and riser labels share a byte");
-
-template<int SRC>
-SSD_ENTRY(__launch_bounds__(kThreads, 8), k_riser_labels, riser_labels_block)(const float *__restrict__ xyz, size_t strideFloats, SSD_BYVAL(PointParams) P, double tol,
-                                                        const FrameState *__restrict__ st, const uint2 *__restrict__ tileMasks,
-                                                        size_t tileMaskStride, int chunkPoints, int cellCols, SSD_BYVAL(DepthSrc) D,
-                                                        unsigned char *__restrict__ labels, size_t labelStride)
-{
-  __shared__ RiserLds L;
-
-  const int lane = threadIdx.x & 63;
-  const int frame = blockIdx.x;
-  Chunk c;
-  CellWalk w;
-  if(!riser_walk<SRC>(L, st[frame], xyz, strideFloats, P.nPoints, tileMasks, tileMaskStride, chunkPoints, cellCols, c, w))
-    return;
-  unsigned char *row = labels + static_cast<size_t>(frame) * labelStride;
-  for(int g = w.g; g < w.gEnd; g++)
-  {
-    const int entry = 4 * g + (lane >> 4);
-    F3 v[kPts];
-    load_cell<SRC>(c.base, c.cell0, L.cellList, entry, w.count, lane, P.nPoints, v, D);
-    if(entry >= w.count)                                    /* a row past the end of the list: its points are invalid, its cell is nobody's */
-      continue;
-    const int idx = (c.cell0 + static_cast<int>(L.cellList[entry])) * kCell + kPts * (lane & 15);
-    #pragma unroll
-    for(int j = 0; j < kPts; j++)
-    {
-      riser_evidence(P, v[j], L, tol, [&](int r, double)
-      {
-        if(SSD_CHK(33, idx + j, P.nPoints))
-          row[idx + j] = static_cast<unsigned char>(SSD_LABEL_RISER_BASE + r);
-      });
-    }
-  }
-}
-
-/* one thread per frame: the riser records in external world coordinates (ToExternalWorld as in k_final) */
-SSD_ENTRY(, k_riser_results, riser_results_block)(SSD_BYVAL(Params) P, const FrameState *__restrict__ st, ssd_frame_risers *__restrict__ out, int nframes)
-{
-  const int frame = blockIdx.x * blockDim.x + threadIdx.x;
-  if(frame >= nframes)
-    return;
-  const FrameState &fs = st[frame];
-  ssd_frame_risers &o = out[frame];
-  const int nR = fs.nRisers;
-  o.n_risers = nR;
-  o.reserved = 0;
-  for(int i = 0; i < kMaxRisers; i++)
-  {
-    ssd_riser &q = o.risers[i];
-    if(i >= nR)
-    {
-      q.n_points = 0; q.detected = 0; q.height_bottom = 0.0; q.height_top = 0.0;
-      q.left[0] = q.left[1] = q.right[0] = q.right[1] = 0.0; q.mean_offset = 0.0;
-      continue;
-    }
-    const RiserState &R = fs.riser[i];
-    const unsigned int c = fs.rCnt[i];
-    q.n_points = static_cast<int>(c);
-    q.detected = c >= static_cast<unsigned int>(P.riserMinSupport) ? 1 : 0;
-    q.height_bottom = P.worldZ + R.zBottom;
-    q.height_top = P.worldZ + R.zTop;
-    double ex = P.r2[0] * R.leftX + P.r2[1] * R.leftY, ey = P.r2[2] * R.leftX + P.r2[3] * R.leftY;
-    q.left[0] = ex + P.t2[0]; q.left[1] = ey + P.t2[1];
-    ex = P.r2[0] * R.rightX + P.r2[1] * R.rightY; ey = P.r2[2] * R.rightX + P.r2[3] * R.rightY;
-    q.right[0] = ex + P.t2[0]; q.right[1] = ey + P.t2[1];
-    q.mean_offset = c ? (static_cast<double>(fs.rSum[i]) / static_cast<double>(1ll << kZFixShift)) / c : 0.0;
-  }
-}
-
 } // namespace ssd
+
+/* K6 (extension), the riser passes: behind every other stage, so that k_riser_results stays the unit's last kernel that is no template */
+#include "ssd_k_risers.h"
+
 
 #include "ssd_launch_rules.h"
 

@@ -5,15 +5,12 @@
  * What stands ON each reported surface: the points of no plateau - the reference's `remainder`, which it drops - that lie in a band above a
  * surface's height and inside its quadrilateral shrunk by a margin (the rule: ssd_clearance.h, one text with ssd_clearance_host).  The pass
  * reads the frame's RESULT record as k_final wrote it, K1's cell records and the points again; it writes the caller's two buffers alone.
- * The walk is the extension kernels' (chunk_of, wanted_cells, load_cell, KeyedSums: ssd_kernels.hip), keyed by the surface.  The file
- * includes ssd_kernels.hip with SSD_CAMERAS_TU defined, as ssd_kernels_refit.hip does, so that no kernel of the chain is touched by what
- * is instantiated here.  The build compiles it at the end of ssd_kernels_refit.hip: the two passes that run behind a whole enqueue are
- * one translation unit and share one parse of ssd_kernels.hip, which is then here already.
+ * The walk is the extension kernels' (chunk_of, wanted_cells, KeyedSums: ssd_k_walk.h; load_cell: ssd_k_cells.h), keyed by the surface.
+ * The file includes that header, the launch rules and its own rule, and no kernel of the chain.  The build compiles it at the end of
+ * ssd_kernels_refit.hip: the passes that run behind a whole enqueue are one translation unit, and what they share is parsed once.
  */
-#ifndef SSD_CAMERAS_TU
-#define SSD_CAMERAS_TU
-#include "ssd_kernels.hip"
-#endif
+#include "ssd_k_walk.h"
+#include "ssd_launch_rules.h"
 #include "ssd_clearance.h"
 
 namespace ssd

@@ -2,14 +2,16 @@
  * ssd_kernels_refit.hip - the trimmed surface refit's kernels (ssd_enqueue_surface_refit, DESIGN.md section 7g;
  * ssd_enqueue_cameras_surface_refit, section 7h) and their launchers.
  *
- * k_surface_refit is k_surface_moments' body, labelled_moments_block (ssd_kernels.hip), with GATED on: the same cells from K1's records,
+ * k_surface_refit is k_surface_moments' body, labelled_moments_block (ssd_k_moments.h), with GATED on: the same cells from K1's records,
  * the same decision (quad_decide<.., true>), the same load, the same accumulation - and a gate test between the label and the sums;
- * k_surface_refit_cams runs it with the frame's camera record in place of the handle's by-value constants.  The file includes
- * ssd_kernels.hip with SSD_CAMERAS_TU defined, as ssd_kernels_cams.hip does, which gives that file's device code without its entry points
- * and launchers: a translation unit of its own, so that no kernel of the chain is touched by what is instantiated here.
+ * k_surface_refit_cams runs it with the frame's camera record in place of the handle's by-value constants.  A translation unit of its
+ * own, so that no kernel of the chain is touched by what is instantiated here; it includes the stage headers it builds on and the launch
+ * rules, and nothing of the chain.  SSD_CAMERAS_TU is defined in front as in ssd_kernels_cams.hip: the unit has _cams entry points, k_labels
+ * stays a device function here, and the tools builds' clocks and counters stay off (ssd_k_entry.h).
  */
 #define SSD_CAMERAS_TU
-#include "ssd_kernels.hip"
+#include "ssd_k_moments.h"
+#include "ssd_launch_rules.h"
 
 namespace ssd
 {
@@ -50,7 +52,7 @@ __global__ __launch_bounds__(kThreads) void k_surface_refit_cams(const float *__
   labelled_moments_block<SRC, CHECKS, true>(R.s, &R.gates, xyz, strideFloats, P, Q, st, tileMasks, tileMaskStride, chunkPoints, D, gates, out);
 }
 
-/* grid, block size and instantiations are launch_surface_moments' (the launch rules of ssd_kernels.hip); a cameras batch: CHECKS by the
+/* grid, block size and instantiations are launch_surface_moments' (ssd_launch_rules.h); a cameras batch: CHECKS by the
  * table, and B.depthInput only says that the source is 16-bit depth - each frame's DepthSrc is its camera's */
 void launch_surface_refit(const Batch &B, int chunkPoints, const ssd_frame_gates *gates, ssd_frame_moments *out)
 {
@@ -67,7 +69,7 @@ void launch_surface_refit(const Batch &B, int chunkPoints, const ssd_frame_gates
 
 } // namespace ssd
 
-/* the other pass behind a whole enqueue, the tread clearance, in this translation unit: one parse of ssd_kernels.hip */
+/* the other pass behind a whole enqueue, the tread clearance, in this translation unit: one parse of the shared headers */
 #include "ssd_kernels_clearance.hip"
 /* ... and the tread grid (section 7n), which is built on it */
 #include "ssd_kernels_treadgrid.hip"

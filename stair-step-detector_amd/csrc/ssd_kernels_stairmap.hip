@@ -13,10 +13,8 @@
  * map's surfaces against those bins and are supersets as before.
  * The file is compiled at the end of ssd_kernels_refit.hip, behind ssd_kernels_treadgrid.hip.
  */
-#ifndef SSD_CAMERAS_TU
-#define SSD_CAMERAS_TU
-#include "ssd_kernels.hip"
-#endif
+#include "ssd_k_walk.h"     /* tread_grid_block's walk */
+#include "ssd_launch_rules.h"
 #include "ssd_treadgrid.h"
 
 namespace ssd

@@ -6,7 +6,8 @@
  * the surface's own frame, per cell the tread points, the occupants and the tallest occupant (the rule: ssd_treadgrid.h, one text with
  * ssd_tread_grid_host, on the clearance rule of ssd_clearance.h).  The pass reads what k_clearance reads - the frame's RESULT record,
  * K1's cell records, the points - and writes the caller's record alone.  The file is compiled at the end of ssd_kernels_refit.hip, behind
- * ssd_kernels_clearance.hip: the passes that run behind a whole enqueue are one translation unit.
+ * ssd_kernels_clearance.hip (clearance_bin is that file's): the passes that run behind a whole enqueue are one translation unit.  The
+ * walk is ssd_k_walk.h's (chunk_of, wanted_cells).
  *
  * Accumulation.  Unlike clearance, nearly every point of a stair frame counts (it is a tread point), so the counts are staged in LDS:
  * per surface one word per cell that packs the tread points (low half) and the occupants (high half) - a block's chunk is fewer than
@@ -20,10 +21,8 @@
  * block's end one global atomic per non-zero count goes to the frame's record, which the caller zeroed on the stream.  Integer adds and
  * maxima: no byte depends on an order.
  */
-#ifndef SSD_CAMERAS_TU
-#define SSD_CAMERAS_TU
-#include "ssd_kernels.hip"
-#endif
+#include "ssd_k_walk.h"
+#include "ssd_launch_rules.h"
 #include "ssd_treadgrid.h"
 
 namespace ssd

@@ -2,7 +2,7 @@
  * ssd_phase.h — instrumentation of the tools builds only (make EXTRA=-DSSD_PHASE_TIMING OUT=../lib_phase; tools/phases.py,
  * tools/blockphases.py): clocks left at marked places of the kernels.  In the product build every macro and method here is
  * empty; the kernels keep only the marks (SSD_PHASE(k, i), BlockPhase::mark), which then compile to nothing.
- * Included by ssd_kernels.hip inside namespace ssd; ssd_phase_readers.h (at the end of that file) holds the two entry points
+ * Included by ssd_k_entry.h inside namespace ssd; ssd_phase_readers.h (at the end of ssd_kernels.hip) holds the two entry points
  * the tools read the clocks through.
  */
 #ifndef SSD_PHASE_H_

@@ -8,11 +8,15 @@
  * logic as one Python function.  The tools' switches that leave a band with single precision (-DSSD_SABOTAGE_PRE, bits 1, 2, 8, 16
  * and the bin half of 32) stand here and nowhere else; the half-planes of a quadrilateral (bits 4 and 32) are quad_decide's.
  *
- * Included by ssd_kernels.hip inside namespace ssd, behind F3 and kThreads.  Everything is inlined into its caller: the masks are
+ * A header in its own right: F3 and kThreads are ssd_k_point.h's.  Everything is inlined into its caller: the masks are
  * the wave's 64-bit lane masks in scalar registers, the helpers take values and return values.
  */
 #ifndef SSD_PREFILTER_H_
 #define SSD_PREFILTER_H_
+#include "ssd_k_point.h"
+
+namespace ssd
+{
 
 /* ---- single instructions ---- */
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -261,5 +265,7 @@ __device__ __forceinline__ void stage_quad_edges(QuadEdgesF *dst, const QuadEdge
   for(int w = threadIdx.x; w < egWords + 16; w += kThreads)
     reinterpret_cast<float *>(dst)[w] = quad_edge_word(w, egWords, w < egWords ? reinterpret_cast<const float *>(src)[w] : 0.0f, dE0);
 }
+
+} // namespace ssd
 
 #endif /* SSD_PREFILTER_H_ */

@@ -1,12 +1,15 @@
-"""csrc/ssd_k_*.h and ssd_launch_rules.h: what the stages of the per-frame path share, in headers.
+"""csrc/ssd_k_*.h, ssd_prefilter.h and ssd_launch_rules.h: what the stages of the per-frame path share, and the extension stages
+themselves (the per-point decision, the walk, K7, K8, K6), in headers.
 
 Every one of them includes what it uses: a file that includes only that header compiles (syntax only, gfx950 device pass, the
 product's language flags); ssd_launch_rules.h, which the launchers read, for the host as well.  No GPU is needed; without hipcc the
 compiles are skipped.
 
-Which file includes which .hip is held to the list below.  The stages' bodies still stand in ssd_kernels.hip, so the units that
-instantiate from them include it; when the bodies are cut into headers too, its entry leaves INCLUDED_HIP and what remains is the
-rule the layout aims at: no file includes a .hip but the three passes the refit unit pulls in and the stair pose in the ground unit."""
+Which file includes which .hip is held to the list below.  The refit unit and its three passes take what they build on from
+headers and include no body of the chain.  What is left: the chain's bodies, K1 to K5, still stand in ssd_kernels.hip, and
+ssd_kernels_cams.hip, which instantiates every stage, is the one file that includes it; when those bodies are cut into headers too,
+its entry leaves INCLUDED_HIP and what remains is the rule the layout aims at: no file includes a .hip but the three passes the refit
+unit pulls in and the stair pose in the ground unit."""
 import glob
 import os
 import re
@@ -19,14 +22,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(ROOT, "stair-step-detector_amd", "csrc")
 HIPCC = shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
-HEADERS = sorted(os.path.basename(p) for p in glob.glob(os.path.join(CSRC, "ssd_k_*.h"))) + ["ssd_launch_rules.h"]
+HEADERS = sorted(os.path.basename(p) for p in glob.glob(os.path.join(CSRC, "ssd_k_*.h"))) + ["ssd_prefilter.h", "ssd_launch_rules.h"]
 FLAGS = ["-std=c++17", "-ffp-contract=off", "--offload-arch=gfx950", "-fsyntax-only", "-I", CSRC, "-x", "hip"]
 BODIES = "ssd_kernels.hip"
 INCLUDED_HIP = {"ssd_kernels_cams.hip": {BODIES},
-                "ssd_kernels_refit.hip": {BODIES, "ssd_kernels_clearance.hip", "ssd_kernels_treadgrid.hip", "ssd_kernels_stairmap.hip"},
-                "ssd_kernels_clearance.hip": {BODIES},
-                "ssd_kernels_treadgrid.hip": {BODIES},
-                "ssd_kernels_stairmap.hip": {BODIES},
+                "ssd_kernels_refit.hip": {"ssd_kernels_clearance.hip", "ssd_kernels_treadgrid.hip", "ssd_kernels_stairmap.hip"},
                 "ssd_kernels_ground.hip": {"ssd_kernels_pose.hip"}}
 
 
@@ -38,7 +38,8 @@ def compile_alone(header, tmp_path, side):
 
 
 def test_the_shared_headers_are_there():
-    assert {"ssd_k_entry.h", "ssd_k_point.h", "ssd_k_cells.h", "ssd_k_windows.h", "ssd_launch_rules.h"} <= set(HEADERS), HEADERS
+    assert {"ssd_k_entry.h", "ssd_k_point.h", "ssd_k_cells.h", "ssd_k_windows.h", "ssd_launch_rules.h", "ssd_prefilter.h",
+            "ssd_k_decide.h", "ssd_k_walk.h", "ssd_k_labels.h", "ssd_k_moments.h", "ssd_k_risers.h"} <= set(HEADERS), HEADERS
 
 
 @pytest.mark.skipif(HIPCC is None, reason="hipcc is not installed")
