@@ -5,11 +5,14 @@
  * the CPU oracle: if no HIP device is present every compute entry fails with
  * SSD_E_NODEVICE.  The entry points that need no handle, no stream and no HIP
  * call - configuration, calibrations, host statements, solvers, folds - are
- * ssd_host.cpp's, plain C++; ssd_host.h holds what the two files share.
+ * ssd_host.cpp's, plain C++; ssd_host.h holds what the two files share.  Those that
+ * call HIP without a handle are ssd_capi_device.cpp's; ssd_capi.h holds HIP_TRY and
+ * hip_fail for both, and the layers of this file.
  */
 #include "ssd_launch.h"
 #include "ssd_handle.h"
-#include "ssd_host.h"
+#include "ssd_chunks.h"
+#include "ssd_capi.h"
 #include "ssd_prexy.h"
 #include "ssd_ground.h"
 #include "ssd_pose.h"
@@ -28,30 +31,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <fstream>
 #include <optional>
 #include <string>
 #include <vector>
-#include <sched.h>
 
 using namespace ssd;
 
 namespace
 {
-
-#define HIP_TRY(expr)                                                                                   \
-  do                                                                                                    \
-  {                                                                                                     \
-    const hipError_t e_ = (expr);                                                                       \
-    if(e_ != hipSuccess)                                                                                \
-      return fail(SSD_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));                        \
-  } while(0)
-
-/* a failed HIP call as a return code: SSD_E_NOMEM or SSD_E_HIP (ssd_owned.h), `what` in front of HIP's text */
-int hip_fail(hipError_t e, const std::string &what)
-{
-  return fail(hip_error_code(e), what + hipGetErrorString(e));
-}
 
 /* the riser pass's records and the riser moments': a zeroed device buffer (counted) and its pinned mirror, both or neither */
 template<typename T>
@@ -123,14 +110,6 @@ constexpr int kOverlapDepth = SSD_BATCHES_IN_FLIGHT_THROUGHPUT;
 
 extern "C"
 {
-
-int ssd_device_count(void)
-{
-  int n = 0;
-  if(hipGetDeviceCount(&n) != hipSuccess)
-    return 0;
-  return n;
-}
 
 static int make_params(const ssd_config &c, const ssd_calibration &k, Params &P)
 {
@@ -524,35 +503,6 @@ int ssd_set_timing(ssd_handle *h, int enable)
   return SSD_OK;
 }
 
-static int choose_chunk(const ssd_tuning &tune, int nPoints, int nframes)
-{
-  const int forced = tune.chunkPoints;
-  if(forced > 0)
-  {
-    const int c = ((forced + kTileHost - 1) / kTileHost) * kTileHost;
-    return c > kMaxTilesPerBlockHost * kTileHost ? kMaxTilesPerBlockHost * kTileHost : c;
-  }
-  const int target = tune.targetBlocks;
-  int cpf = (target + nframes - 1) / nframes;
-  const int maxCpf = (nPoints + kTileHost - 1) / kTileHost;
-  if(cpf > maxCpf) cpf = maxCpf;
-  if(cpf < 1) cpf = 1;
-  const int per = (nPoints + cpf - 1) / cpf;
-  int chunk = ((per + kTileHost - 1) / kTileHost) * kTileHost;
-  /* a block should stream at least 32 tiles (its prologue copies the frame's tables, its epilogue flushes the LDS
-   * histogram / windows): measured +0.5 % on the XGA batch, +6.5 % on the FHD stress batch (tools/target_blocks.sh) —
-   * as long as that leaves the machine at least 8192 blocks (small batches, single frames: latency first) */
-  long long minChunk = static_cast<long long>(kMaxTilesPerBlockHost) * kTileHost;
-  const long long total = static_cast<long long>(nPoints) * nframes;
-  if(total / minChunk < 8192)
-    minChunk = total / 8192 / kTileHost * kTileHost;
-  if(chunk < minChunk)
-    chunk = static_cast<int>(minChunk);
-  if(chunk > kMaxTilesPerBlockHost * kTileHost)
-    chunk = kMaxTilesPerBlockHost * kTileHost;
-  return chunk;
-}
-
 static constexpr int kDirectResultFrames = 64;
 static int cameras_upload(ssd_handle *h, unsigned long long key, double tol);
 /* what a call decides for the whole handle and the cameras' device records carry (ssd_handle::camCallKey) */
@@ -579,10 +529,11 @@ static Batch make_batch(const ssd_handle *h, const Params &P, ssd_lane &L, const
                 L.dState, L.dTileMasks, h->tileMaskStride, nframes, s, cams };
 }
 
-/* camOf (host, nframes entries; ssd_enqueue_cameras has checked them): a cameras batch - frame i takes camera camOf[i] of the table;
- * moments (device, nframes records): the surface moments of the batch (of a cameras batch too: each frame under its own camera) */
-static int enqueue_impl(ssd_handle *h, const void *d_xyz, size_t frame_stride_bytes, int nframes, void *stream, int stages, bool depthInput,
-                        unsigned char *labels = nullptr, size_t labelStride = 0, const uint16_t *camOf = nullptr, ssd_frame_moments *moments = nullptr)
+/* ---- enqueue_impl and its steps, in the order of events ------------------------------------------------------------------------------ */
+
+/* the argument refusals, in front of anything that touches the device or the handle */
+static int check_enqueue_args(const ssd_handle *h, const void *d_xyz, size_t frame_stride_bytes, int nframes, int stages, bool depthInput,
+                              const uint16_t *camOf, const ssd_frame_moments *moments)
 {
   if(!h || !d_xyz)
     return fail(SSD_E_ARG, "ssd_enqueue: null argument");
@@ -605,19 +556,16 @@ static int enqueue_impl(ssd_handle *h, const void *d_xyz, size_t frame_stride_by
     if((reinterpret_cast<uintptr_t>(d_xyz) & 3u) != 0)
       return fail(SSD_E_ARG, "ssd_enqueue: frame pointer must be 4-byte aligned");
   }
-  HIP_TRY(hipSetDevice(h->device));
-  h->wholeKind = 0;                            /* what a refit may be held to (ssd_enqueue_surface_refit): set again when this call has gone out whole */
-  Params P = h->P;
-  P.px.groundFull = h->debug == 1 ? 1 : 0;     /* image capture compares the whole ground image; otherwise only what k_final reads is rastered */
-  /* Which workspace.  A handle with one runs on the caller's stream (a switch of streams is ordered by the lane's event: the
-   * workspace is single-buffered).  With several, successive batches take them in turn, each on the lane's own stream behind
-   * an event recorded on the caller's stream now: the batch starts after the work the caller's stream holds, but the caller's
-   * stream does not wait for the batch (ssd_fetch* / ssd_stream_wait do).  Debug capture, the riser pass and partial runs
-   * (ssd_enqueue_stages) own single buffers / leave state behind for the next call: they stay in lane 0. */
-  const bool pinned = h->debug != 0 || P.risers || stages != SSD_STAGE_ALL;
-  const int li = h->depth == 1 || pinned ? 0 : static_cast<int>(h->laneTurn++ % static_cast<unsigned long long>(h->depth));
-  ssd_lane &L = h->lane[li];
-  hipStream_t s = static_cast<hipStream_t>(stream);
+  return SSD_OK;
+}
+
+/* The stream a call on workspace L runs on, in s: enqueue_impl's rule and follow_enter's.  A handle with one workspace runs on the
+ * caller's stream (a switch of streams is ordered by the lane's event: the workspace is single-buffered).  With several, the call runs
+ * on the lane's own stream behind an event recorded on the caller's stream now: it starts after the work the caller's stream holds, but
+ * the caller's stream does not wait for it */
+static int lane_stream(ssd_handle *h, ssd_lane &L, hipStream_t caller, hipStream_t &s)
+{
+  s = caller;
   if(h->depth == 1)
   {
     if(L.haveLast && s != L.lastStream)
@@ -628,86 +576,273 @@ static int enqueue_impl(ssd_handle *h, const void *d_xyz, size_t frame_stride_by
     HIP_TRY(hipEventRecord(L.in, s));
     s = L.stream;
     HIP_TRY(hipStreamWaitEvent(s, L.in, 0));
-    /* the single debug / riser buffers: a pinned call after free-running ones (or the other way round) must not overtake
-     * what the other lanes still hold — rare (a switch of mode), so simply wait for all of them */
-    if(pinned != h->lastPinned)
-      for(int k = 0; k < h->depth; k++)
-        if(k != li && h->lane[k].haveLast)
-          HIP_TRY(hipStreamWaitEvent(s, h->lane[k].done, 0));
   }
+  return SSD_OK;
+}
+
+/* Which workspace, and its stream (lane_stream).  Successive batches take the workspaces in turn (ssd_fetch* / ssd_stream_wait wait for
+ * them).  Debug capture, the riser pass and partial runs (ssd_enqueue_stages) own single buffers / leave state behind for the next
+ * call: they stay in lane 0 (`pinned`). */
+static int take_workspace(ssd_handle *h, bool pinned, hipStream_t caller, int &li, hipStream_t &s)
+{
+  li = h->depth == 1 || pinned ? 0 : static_cast<int>(h->laneTurn++ % static_cast<unsigned long long>(h->depth));
+  const int rc = lane_stream(h, h->lane[li], caller, s);
+  if(rc) return rc;
+  /* the single debug / riser buffers: a pinned call after free-running ones (or the other way round) must not overtake
+   * what the other lanes still hold — rare (a switch of mode), so simply wait for all of them */
+  if(h->depth > 1 && pinned != h->lastPinned)
+    for(int k = 0; k < h->depth; k++)
+      if(k != li && h->lane[k].haveLast)
+        HIP_TRY(hipStreamWaitEvent(s, h->lane[k].done, 0));
   h->lastPinned = pinned;
-  /* A cameras batch: the index goes through the workspace's pinned slot to its device array, on the batch's stream in front of its
-   * kernels (the caller's array is free when this call returns; the slot is free once the previous copy out of it has run). */
-  CameraSel camSel{};
-  const CameraSel *cams = nullptr;
-  if(camOf)
+  return SSD_OK;
+}
+
+/* A cameras batch: the index goes through the workspace's pinned slot to its device array, on the batch's stream in front of its
+ * kernels (the caller's array is free when this call returns; the slot is free once the previous copy out of it has run). */
+static int send_camera_index(ssd_handle *h, ssd_lane &L, const Params &P, const uint16_t *camOf, int nframes, hipStream_t s, CameraSel &camSel)
+{
+  if(!h->dCams || !L.dCamIndex || !L.hCamIndex || !L.camCopied)
+    return fail(SSD_E_HIP, "ssd_enqueue_cameras: the camera table is incomplete (internal)");
+  if(cameras_call_key(P) != h->camCallKey || P.riserTol != h->camCallTol)
   {
-    if(!h->dCams || !L.dCamIndex || !L.hCamIndex || !L.camCopied)
-      return fail(SSD_E_HIP, "ssd_enqueue_cameras: the camera table is incomplete (internal)");
-    if(cameras_call_key(P) != h->camCallKey || P.riserTol != h->camCallTol)
-    {
-      const int rcUp = cameras_upload(h, cameras_call_key(P), P.riserTol);
-      if(rcUp) return rcUp;
-    }
-    HIP_TRY(hipEventSynchronize(L.camCopied));
-    for(int i = 0; i < nframes; i++)
-      L.hCamIndex[i] = camOf[i];
-    HIP_TRY(hipMemcpyAsync(L.dCamIndex, L.hCamIndex, sizeof(int) * static_cast<size_t>(nframes), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipEventRecord(L.camCopied, s));
-    camSel = CameraSel{ h->dCams, L.dCamIndex, h->camsNeedChecks };
-    cams = &camSel;
+    const int rcUp = cameras_upload(h, cameras_call_key(P), P.riserTol);
+    if(rcUp) return rcUp;
   }
-  const Batch B = make_batch(h, P, L, d_xyz, frame_stride_bytes, nframes, depthInput, s, cams);
-  const int chunk = choose_chunk(h->tune, P.nPoints, nframes);
-  /* K2 and K4 walk cell columns: the taller a block's chunk, the fewer window flushes and block starts per cell (below) */
-  /* K1 ends every block with up to 121 global atomics into the frame's histogram: with one-tile chunks (single frames) 768
-   * blocks queue up on the same addresses; at most ssd_tuning::k1BlocksPerFrame blocks per frame keeps that short */
-  int chunkHist = chunk;
-  {
-    const int perFrame = h->tune.k1BlocksPerFrame;
-    const int tilesPerFrame = (P.nPoints + kTileHost - 1) / kTileHost;
-    int t = (tilesPerFrame + perFrame - 1) / perFrame;
-    if(t > kMaxTilesPerBlockHost) t = kMaxTilesPerBlockHost;
-    if(t * kTileHost > chunkHist) chunkHist = t * kTileHost;
-  }
-  int chunkRaster = chunk, chunkInquad = chunk;
-  {
-    /* Blocks of K2 / K4 by batch size (XGA, tools/exp_frames.sh, 1-128 frames swept): what a block pays per start (state,
-     * LDS, cell list, window flush, final atomics) wants tall chunks, the 2048 block slots of the chip want >= ~1536 blocks,
-     * and a grid of one to two rounds of slots wants more, smaller blocks for its tail.  Rule: chunks of more than 8 tiles
-     * only while they leave >= 6144 blocks (three rounds); else as tall as leaves >= 1536 blocks, K2 never below 2 tiles.
-     * Against the former ">= 600 blocks": 8 / 16 / 32 / 64 frames 46 -> 49 k, 73 -> 82 k, 113 -> 124 k, 159 -> 172 k frames/s. */
-    const long long totalTiles = (static_cast<long long>(P.nPoints) + kTileHost - 1) / kTileHost * nframes;
-    const int minBlocks = h->tune.k24MinBlocks, tallBlocks = h->tune.k24TallBlocks;
-    int t2 = h->tune.k2ChunkTiles, t4 = h->tune.k4ChunkTiles;
-    if(t2 > kMaxTilesPerBlockRasterHost) t2 = kMaxTilesPerBlockRasterHost;
-    if(t4 > kMaxTilesPerBlockInquadHost) t4 = kMaxTilesPerBlockInquadHost;
-    auto pick = [&](int t, int tMin)
-    {
-      while(t > 8 && totalTiles / t < tallBlocks) t /= 2;
-      while(t > tMin && totalTiles / t < minBlocks) t /= 2;
-      return t;
-    };
-    t2 = pick(t2, 2);
-    t4 = pick(t4, 1);
-    if(t2 * kTileHost > chunkRaster) chunkRaster = t2 * kTileHost;
-    if(t4 * kTileHost > chunkInquad) chunkInquad = t4 * kTileHost;
-  }
-  DebugFrame *dbg = h->debug ? h->dDebug : nullptr;
-  unsigned long long *dbgImg = h->debug == 1 ? h->dDebugImg : nullptr;
-  /* The single pass: K1 rasters the step plateaus while it counts, into planes of the height bins k_predict expects them in;
-   * k_peaks checks that against the complete histogram, frame by frame, and k_raster does the frames it does not cover.  Only
-   * the whole pipeline in one call (the planes are set in the first stage and consumed in the fourth), only batches. */
+  HIP_TRY(hipEventSynchronize(L.camCopied));
+  for(int i = 0; i < nframes; i++)
+    L.hCamIndex[i] = camOf[i];
+  HIP_TRY(hipMemcpyAsync(L.dCamIndex, L.hCamIndex, sizeof(int) * static_cast<size_t>(nframes), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipEventRecord(L.camCopied, s));
+  camSel = CameraSel{ h->dCams, L.dCamIndex, h->camsNeedChecks };
+  return SSD_OK;
+}
+
+/* The single pass: K1 rasters the step plateaus while it counts, into planes of the height bins k_predict expects them in;
+ * k_peaks checks that against the complete histogram, frame by frame, and k_raster does the frames it does not cover.  Only
+ * the whole pipeline in one call (the planes are set in the first stage and consumed in the fourth), only batches.  The planes
+ * of a call that runs it, null for one that runs two passes. */
+static unsigned long long *single_pass_planes(ssd_handle *h, ssd_lane &L, int nPoints, int stages, int nframes, bool depthInput)
+{
   unsigned long long *planeImg = nullptr;
   /* (not on 16-bit depth input: K1 is bound by instruction issue there, not by the bytes a second pass would re-read - k_raster
    * reads a sixth of them -, and the raster's instructions cost K1 what k_raster took: 384.6 k against 386.8 k frames/s) */
-  if(L.dPlaneImg && stages == SSD_STAGE_ALL && h->singlePassMode != 0 && (h->singlePassMode == 1 || (single_pass_batch(nframes, P.nPoints) && !depthInput)))
+  if(L.dPlaneImg && stages == SSD_STAGE_ALL && h->singlePassMode != 0 && (h->singlePassMode == 1 || (single_pass_batch(nframes, nPoints) && !depthInput)))
   {
     if(h->singlePassMode == 1 || h->singlePassBackoff == 0)
       planeImg = L.dPlaneImg;
     else
       h->singlePassBackoff--;                            /* see ssd_fetch_back */
   }
+  return planeImg;
+}
+
+/* the timing slot of this enqueue: which optional passes it times, their events on the first timed enqueue that runs them */
+static int timing_slots(ssd_handle *h, bool timing, int timingSlot, bool labels, bool moments, bool riserLabels)
+{
+  if(labels && timing)
+  {
+    /* the label kernel's events, on the first timed enqueue that labels */
+    const int rcEv = timed_pass_make(h->labelsPass, "hipEventCreate (labels): ");
+    if(rcEv) return rcEv;
+  }
+  h->labelsPass.timed[timingSlot] = labels && timing;
+  if(moments && timing)
+  {
+    const int rcEv = timed_pass_make(h->surfacePass, "hipEventCreate (surface moments): ");
+    if(rcEv) return rcEv;
+  }
+  h->surfacePass.timed[timingSlot] = moments && timing;
+  h->riserLabelsPass.timed[timingSlot] = riserLabels && timing;
+  return SSD_OK;
+}
+
+/* what enqueue_impl has decided for the call, beside what the Batch holds (constants, frames, stream): read by the chain and by the
+ * book-keeping behind it */
+struct EnqueueCall
+{
+  ChunkPlan chunks;
+  int stages;
+  unsigned long long *planeImg;                  /* the single pass's planes; null: two passes */
+  unsigned char *labels;
+  size_t labelStride;
+  ssd_frame_moments *moments;
+  bool riserMoments, riserLabels;
+};
+
+/* the result slot the next enqueue that runs the last stage takes, and its records as k_final addresses them: a few frames go straight
+ * into the pinned side (run_chain) */
+static int result_slot(const ssd_handle *h)
+{
+  return static_cast<int>(h->finalCount % static_cast<unsigned long long>(h->nSlots));
+}
+static bool results_direct(const ssd_handle *h, int nframes)
+{
+  return nframes <= kDirectResultFrames && h->hResultsDev != nullptr;
+}
+static ssd_frame_result *result_records(ssd_handle *h, int nframes, int slot)
+{
+  return (results_direct(h, nframes) ? h->hResultsDev : h->dResults) + static_cast<size_t>(slot) * h->F;
+}
+
+/* the kernels of the chosen stages on the batch's stream, in order */
+static void run_chain(ssd_handle *h, ssd_lane &L, const Batch &B, const EnqueueCall &c, bool marks)
+{
+  const Params &P = B.P;
+  hipStream_t s = B.s;
+  const int stages = c.stages, nframes = B.nframes, chunk = c.chunks.chunk, timingSlot = static_cast<int>(h->enqueueCount % SSD_TIMING_SLOTS);
+  unsigned long long *planeImg = c.planeImg;
+  DebugFrame *dbg = h->debug ? h->dDebug : nullptr;
+  unsigned long long *dbgImg = h->debug == 1 ? h->dDebugImg : nullptr;
+  int evi = timingSlot * 8;
+  auto mk = [&]() { if(marks) (void)hipEventRecord(h->ev[evi++], s); };
+  if(planeImg)
+  {
+    /* k_predict in front of the seven stages, timed by itself (ssd_get_predict_time_back) */
+    if(marks) (void)hipEventRecord(h->evPredict[timingSlot], s);
+    launch_predict(B, L.dFallback, h->planePool, h->singlePassSabotage);
+  }
+  mk();
+  if(stages & SSD_STAGE_HIST)
+    launch_hist(B, c.chunks.hist, planeImg);
+  mk();
+  if(stages & SSD_STAGE_PEAKS)
+    launch_peaks(B, dbg, planeImg ? L.dFallback : nullptr);
+  mk();
+  if(stages & SSD_STAGE_RASTER)
+    launch_raster(B, c.chunks.raster, L.dStepImg, planeImg ? L.dFallback : nullptr);
+  mk();
+  if(stages & SSD_STAGE_OUTLINE)
+    launch_outline(B, L.dStepImg, planeImg, dbg, dbgImg);
+  mk();
+  if(stages & SSD_STAGE_QUADS)
+    launch_quads(B, dbg);
+  mk();
+  if(stages & SSD_STAGE_INQUAD)
+    launch_inquad(B, c.chunks.inquad, L.dGroundImg);
+  mk();
+  /* The results leave with the batch, into this enqueue's pinned slot (event for ssd_fetch / ssd_fetch_back).  A few frames:
+   * k_final stores them there itself — a kilobyte per frame of posted writes, visible to the host once the event has
+   * fired — instead of a device-to-host copy command behind the kernel (single frame: one command less in the chain).
+   * Batches go through device memory and one copy: a megabyte of scattered stores over PCIe would hold k_final's blocks. */
+  if(stages & SSD_STAGE_FINAL)
+  {
+    launch_final(B, L.dGroundImg, result_records(h, nframes, result_slot(h)), dbg, dbgImg);
+    if(P.risers && c.riserMoments)
+    {
+      /* the riser fit: k_riser_moments in place of k_risers - one walk, both results; the records are zeroed in front of it, it only adds */
+      (void)hipMemsetAsync(h->dRiserMoments, 0, sizeof(ssd_frame_moments) * static_cast<size_t>(nframes), s);
+      launch_riser_moments(B, chunk, h->dRisers, h->dRiserMoments);
+    }
+    else if(P.risers)
+      launch_risers(B, chunk, h->dRisers);
+  }
+  mk();
+  /* per-pixel labels: behind the seven stages (and their timing), in front of the batch's completion event */
+  if(c.labels)
+  {
+    if(marks) h->labelsPass.begin(timingSlot, s);
+    launch_labels(B, chunk, c.labels, c.labelStride);
+    if(marks) h->labelsPass.end(timingSlot, s);
+    /* the riser labels: behind k_labels (which has written every byte) and behind the riser pass above, outside k_labels' timing */
+    if(c.riserLabels)
+    {
+      if(marks) h->riserLabelsPass.begin(timingSlot, s);
+      launch_riser_labels(B, chunk, c.labels, c.labelStride);
+      if(marks) h->riserLabelsPass.end(timingSlot, s);
+    }
+  }
+  /* per-surface moments: likewise; the records are zeroed on the batch's stream in front of the kernel, which only adds */
+  if(c.moments)
+  {
+    if(marks) h->surfacePass.begin(timingSlot, s);
+    (void)hipMemsetAsync(c.moments, 0, sizeof(ssd_frame_moments) * static_cast<size_t>(nframes), s);
+    launch_surface_moments(B, chunk, c.moments);
+    if(marks) h->surfacePass.end(timingSlot, s);
+  }
+}
+
+/* the book-keeping behind the chain: the results on their way to the pinned slot with their event, the lane's completion event, what
+ * the workspace and the handle remember of the call - and, for a whole run, what a follow-on pass may be held to */
+static int close_enqueue(ssd_handle *h, ssd_lane &L, const Batch &B, const EnqueueCall &c, const void *d_xyz, size_t frame_stride_bytes, bool cameras)
+{
+  hipStream_t s = B.s;
+  const int stages = c.stages, nframes = B.nframes, slot = result_slot(h), li = static_cast<int>(&L - h->lane);
+  if(stages & SSD_STAGE_HIST)
+    L.dirtyFrames = nframes;
+  if(stages & SSD_STAGE_FINAL)
+  {
+    if(!results_direct(h, nframes))
+      HIP_TRY(hipMemcpyAsync(h->hResults + static_cast<size_t>(slot) * h->F, h->dResults + static_cast<size_t>(slot) * h->F,
+                             sizeof(ssd_frame_result) * nframes, hipMemcpyDeviceToHost, s));
+    /* single pass: how many frames k_raster had to do travels with the results (ssd_fetch_back adapts to it) */
+    h->resultsFallback[slot] = -1;
+    if(c.planeImg && h->hFallback)
+    {
+      HIP_TRY(hipMemcpyAsync(h->hFallback + 2 * slot, L.dFallback, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+      h->resultsFallback[slot] = 0;
+    }
+    HIP_TRY(hipEventRecord(h->resultsReady[slot], s));
+    h->resultsFrames[slot] = nframes;
+    h->resultsLane[slot] = li;
+    h->finalCount++;
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(L.done, s));
+  if((stages & SSD_STAGE_PEAKS) && nframes >= L.dirtyFrames)
+    L.dirtyFrames = 0;
+  L.lastStream = s;
+  L.haveLast = true;
+  /* a raster without its consumer leaves bits behind; the consumer clears what it read */
+  if(stages & SSD_STAGE_RASTER) L.stepImagesDirty = true;
+  if(stages & SSD_STAGE_OUTLINE) L.stepImagesDirty = false;
+  if(stages & SSD_STAGE_INQUAD) L.groundImageDirty = true;
+  if(stages & SSD_STAGE_FINAL) L.groundImageDirty = false;
+  h->lastFrames = nframes;
+  h->lastLane = li;
+  h->hRisersBatchFrames = 0;
+  h->riserMomentsFrames = c.riserMoments ? nframes : 0;
+  h->hRiserMomentsBatchFrames = 0;
+  h->enqueueCount++;
+  if(stages == SSD_STAGE_ALL)
+  {
+    h->wholeKind = cameras ? 2 : 1;
+    h->wholeDepth = B.depthInput;
+    h->wholeFrames = d_xyz;
+    h->wholeStride = frame_stride_bytes;
+    h->wholeResults = result_records(h, nframes, slot);   /* where k_final left its records */
+  }
+  return SSD_OK;
+}
+
+/* camOf (host, nframes entries; ssd_enqueue_cameras has checked them): a cameras batch - frame i takes camera camOf[i] of the table;
+ * moments (device, nframes records): the surface moments of the batch (of a cameras batch too: each frame under its own camera) */
+static int enqueue_impl(ssd_handle *h, const void *d_xyz, size_t frame_stride_bytes, int nframes, void *stream, int stages, bool depthInput,
+                        unsigned char *labels = nullptr, size_t labelStride = 0, const uint16_t *camOf = nullptr, ssd_frame_moments *moments = nullptr)
+{
+  int rc = check_enqueue_args(h, d_xyz, frame_stride_bytes, nframes, stages, depthInput, camOf, moments);
+  if(rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  h->wholeKind = 0;                            /* what a refit may be held to (ssd_enqueue_surface_refit): set again when this call has gone out whole */
+  Params P = h->P;
+  P.px.groundFull = h->debug == 1 ? 1 : 0;     /* image capture compares the whole ground image; otherwise only what k_final reads is rastered */
+  const bool pinned = h->debug != 0 || P.risers || stages != SSD_STAGE_ALL;
+  int li = 0;
+  hipStream_t s = nullptr;
+  rc = take_workspace(h, pinned, static_cast<hipStream_t>(stream), li, s);
+  if(rc) return rc;
+  ssd_lane &L = h->lane[li];
+  CameraSel camSel{};
+  const CameraSel *cams = nullptr;
+  if(camOf)
+  {
+    rc = send_camera_index(h, L, P, camOf, nframes, s, camSel);
+    if(rc) return rc;
+    cams = &camSel;
+  }
+  const Batch B = make_batch(h, P, L, d_xyz, frame_stride_bytes, nframes, depthInput, s, cams);
+  const ChunkPlan chunks = chunk_plan(h->tune, P.nPoints, nframes);
+  unsigned long long *planeImg = single_pass_planes(h, L, P.nPoints, stages, nframes, depthInput);
   /* the optional device buffers the kernels dereference without a test of their own: a handle that lacks one
    * fails here, loudly, instead of faulting on the device at a null address */
   if(planeImg && !L.dFallback)
@@ -720,101 +855,17 @@ static int enqueue_impl(ssd_handle *h, const void *d_xyz, size_t frame_stride_by
   h->predictTimed[h->enqueueCount % SSD_TIMING_SLOTS] = planeImg != nullptr;
   const bool timing = h->timing && !h->ev.empty();
   const int timingSlot = static_cast<int>(h->enqueueCount % SSD_TIMING_SLOTS);
-  if(labels && timing)
-  {
-    /* the label kernel's events, on the first timed enqueue that labels */
-    const int rcEv = timed_pass_make(h->labelsPass, "hipEventCreate (labels): ");
-    if(rcEv) return rcEv;
-  }
-  h->labelsPass.timed[timingSlot] = labels != nullptr && timing;
-  if(moments && timing)
-  {
-    const int rcEv = timed_pass_make(h->surfacePass, "hipEventCreate (surface moments): ");
-    if(rcEv) return rcEv;
-  }
-  h->surfacePass.timed[timingSlot] = moments != nullptr && timing;
-  int evi = timingSlot * 8;
   /* riser moments: whole runs only (ssd_enqueue_stages takes none), and only with the riser pass they ride on */
   const bool riserMoments = P.risers && h->riserMoments && h->dRiserMoments && h->dRisers && stages == SSD_STAGE_ALL;
   /* riser labels: only where labels are written, and only with the riser pass (k_final refreshes wantedRisers / riserOfBin only then) */
   const bool riserLabels = labels != nullptr && P.risers && h->riserLabels && !h->riserLabelsPass.ev.empty() && stages == SSD_STAGE_ALL;
-  h->riserLabelsPass.timed[timingSlot] = riserLabels && timing;
+  rc = timing_slots(h, timing, timingSlot, labels != nullptr, moments != nullptr, riserLabels);
+  if(rc) return rc;
 
-  const int slot = static_cast<int>(h->finalCount % static_cast<unsigned long long>(h->nSlots));
-  const bool direct = nframes <= kDirectResultFrames && h->hResultsDev != nullptr;
+  const int slot = result_slot(h);
   if((stages & SSD_STAGE_FINAL) && h->depth > 1 && h->resultsLane[slot] != li && h->lane[h->resultsLane[slot]].haveLast)
     HIP_TRY(hipStreamWaitEvent(s, h->lane[h->resultsLane[slot]].done, 0));     /* the slot's previous writer was another lane */
-
-  /* the kernels of the chosen stages on the batch's stream, in order */
-  auto chain = [&](bool marks)
-  {
-    auto mk = [&]() { if(marks) (void)hipEventRecord(h->ev[evi++], s); };
-    if(planeImg)
-    {
-      /* k_predict in front of the seven stages, timed by itself (ssd_get_predict_time_back) */
-      if(marks) (void)hipEventRecord(h->evPredict[timingSlot], s);
-      launch_predict(B, L.dFallback, h->planePool, h->singlePassSabotage);
-    }
-    mk();
-    if(stages & SSD_STAGE_HIST)
-      launch_hist(B, chunkHist, planeImg);
-    mk();
-    if(stages & SSD_STAGE_PEAKS)
-      launch_peaks(B, dbg, planeImg ? L.dFallback : nullptr);
-    mk();
-    if(stages & SSD_STAGE_RASTER)
-      launch_raster(B, chunkRaster, L.dStepImg, planeImg ? L.dFallback : nullptr);
-    mk();
-    if(stages & SSD_STAGE_OUTLINE)
-      launch_outline(B, L.dStepImg, planeImg, dbg, dbgImg);
-    mk();
-    if(stages & SSD_STAGE_QUADS)
-      launch_quads(B, dbg);
-    mk();
-    if(stages & SSD_STAGE_INQUAD)
-      launch_inquad(B, chunkInquad, L.dGroundImg);
-    mk();
-    /* The results leave with the batch, into this enqueue's pinned slot (event for ssd_fetch / ssd_fetch_back).  A few frames:
-     * k_final stores them there itself — a kilobyte per frame of posted writes, visible to the host once the event has
-     * fired — instead of a device-to-host copy command behind the kernel (single frame: one command less in the chain).
-     * Batches go through device memory and one copy: a megabyte of scattered stores over PCIe would hold k_final's blocks. */
-    if(stages & SSD_STAGE_FINAL)
-    {
-      ssd_frame_result *out = (direct ? h->hResultsDev : h->dResults) + static_cast<size_t>(slot) * h->F;
-      launch_final(B, L.dGroundImg, out, dbg, dbgImg);
-      if(P.risers && riserMoments)
-      {
-        /* the riser fit: k_riser_moments in place of k_risers - one walk, both results; the records are zeroed in front of it, it only adds */
-        (void)hipMemsetAsync(h->dRiserMoments, 0, sizeof(ssd_frame_moments) * static_cast<size_t>(nframes), s);
-        launch_riser_moments(B, chunk, h->dRisers, h->dRiserMoments);
-      }
-      else if(P.risers)
-        launch_risers(B, chunk, h->dRisers);
-    }
-    mk();
-    /* per-pixel labels: behind the seven stages (and their timing), in front of the batch's completion event */
-    if(labels)
-    {
-      if(marks) h->labelsPass.begin(timingSlot, s);
-      launch_labels(B, chunk, labels, labelStride);
-      if(marks) h->labelsPass.end(timingSlot, s);
-      /* the riser labels: behind k_labels (which has written every byte) and behind the riser pass above, outside k_labels' timing */
-      if(riserLabels)
-      {
-        if(marks) h->riserLabelsPass.begin(timingSlot, s);
-        launch_riser_labels(B, chunk, labels, labelStride);
-        if(marks) h->riserLabelsPass.end(timingSlot, s);
-      }
-    }
-    /* per-surface moments: likewise; the records are zeroed on the batch's stream in front of the kernel, which only adds */
-    if(moments)
-    {
-      if(marks) h->surfacePass.begin(timingSlot, s);
-      (void)hipMemsetAsync(moments, 0, sizeof(ssd_frame_moments) * static_cast<size_t>(nframes), s);
-      launch_surface_moments(B, chunk, moments);
-      if(marks) h->surfacePass.end(timingSlot, s);
-    }
-  };
+  const EnqueueCall call{ chunks, stages, planeImg, labels, labelStride, moments, riserMoments, riserLabels };
 
   /* (A call of a few frames replayed from a captured HIP graph — one submission instead of seven launches — was measured in
    * round 3 and is slower on ROCm 7.2: one resident XGA frame 100 -> 200 us per ssd_enqueue + ssd_fetch, eight frames 134 ->
@@ -839,56 +890,12 @@ static int enqueue_impl(ssd_handle *h, const void *d_xyz, size_t frame_stride_by
        * ran K1 without k_peaks (ssd_enqueue_stages), or one that failed half way, the state is zeroed here. */
       if(L.dirtyFrames > 0)
         HIP_TRY(hipMemsetAsync(L.dState, 0, sizeof(FrameState) * L.dirtyFrames, s));
-      if(dbg)
-        HIP_TRY(hipMemsetAsync(dbg, 0, sizeof(DebugFrame) * nframes, s));
+      if(h->debug && h->dDebug)
+        HIP_TRY(hipMemsetAsync(h->dDebug, 0, sizeof(DebugFrame) * nframes, s));
     }
-    chain(timing);
+    run_chain(h, L, B, call, timing);
   }
-  if(stages & SSD_STAGE_HIST)
-    L.dirtyFrames = nframes;
-  if(stages & SSD_STAGE_FINAL)
-  {
-    if(!direct)
-      HIP_TRY(hipMemcpyAsync(h->hResults + static_cast<size_t>(slot) * h->F, h->dResults + static_cast<size_t>(slot) * h->F,
-                             sizeof(ssd_frame_result) * nframes, hipMemcpyDeviceToHost, s));
-    /* single pass: how many frames k_raster had to do travels with the results (ssd_fetch_back adapts to it) */
-    h->resultsFallback[slot] = -1;
-    if(planeImg && h->hFallback)
-    {
-      HIP_TRY(hipMemcpyAsync(h->hFallback + 2 * slot, L.dFallback, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
-      h->resultsFallback[slot] = 0;
-    }
-    HIP_TRY(hipEventRecord(h->resultsReady[slot], s));
-    h->resultsFrames[slot] = nframes;
-    h->resultsLane[slot] = li;
-    h->finalCount++;
-  }
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(L.done, s));
-  if((stages & SSD_STAGE_PEAKS) && nframes >= L.dirtyFrames)
-    L.dirtyFrames = 0;
-  L.lastStream = s;
-  L.haveLast = true;
-  /* a raster without its consumer leaves bits behind; the consumer clears what it read */
-  if(stages & SSD_STAGE_RASTER) L.stepImagesDirty = true;
-  if(stages & SSD_STAGE_OUTLINE) L.stepImagesDirty = false;
-  if(stages & SSD_STAGE_INQUAD) L.groundImageDirty = true;
-  if(stages & SSD_STAGE_FINAL) L.groundImageDirty = false;
-  h->lastFrames = nframes;
-  h->lastLane = li;
-  h->hRisersBatchFrames = 0;
-  h->riserMomentsFrames = riserMoments ? nframes : 0;
-  h->hRiserMomentsBatchFrames = 0;
-  h->enqueueCount++;
-  if(stages == SSD_STAGE_ALL)
-  {
-    h->wholeKind = camOf ? 2 : 1;
-    h->wholeDepth = depthInput;
-    h->wholeFrames = d_xyz;
-    h->wholeStride = frame_stride_bytes;
-    h->wholeResults = (direct ? h->hResultsDev : h->dResults) + static_cast<size_t>(slot) * h->F;   /* where k_final left its records */
-  }
-  return SSD_OK;
+  return close_enqueue(h, L, B, call, d_xyz, frame_stride_bytes, camOf != nullptr);
 }
 
 int ssd_enqueue_stages(ssd_handle *h, const void *d_xyz, size_t frame_stride_bytes, int nframes, void *stream, int stages)
@@ -1985,25 +1992,15 @@ static int follow_enter(ssd_handle *h, const std::string &me, const BehindWhole 
   f.timing = h->timing && !h->ev.empty();
   int rc = pass_make(h->*pass, f.timing, me);
   if(rc) return rc;
-  f.s = static_cast<hipStream_t>(stream);
-  if(h->depth == 1)
-  {
-    if(f.s != L.lastStream)
-      HIP_TRY(hipStreamWaitEvent(f.s, L.done, 0));
-  }
-  else
-  {
-    HIP_TRY(hipEventRecord(L.in, f.s));
-    f.s = L.stream;
-    HIP_TRY(hipStreamWaitEvent(f.s, L.in, 0));
-  }
+  rc = lane_stream(h, L, static_cast<hipStream_t>(stream), f.s);       /* (L.haveLast: refused above otherwise) */
+  if(rc) return rc;
   rc = first(f.s);
   if(!rc) rc = pass_open(h->*pass, f.s, f.timing, me);
   if(rc) return rc;
   /* a cameras batch: the table as the batch read it, the index where the batch's own copy left it */
   f.camSel = CameraSel{ h->dCams, L.dCamIndex, h->camsNeedChecks };
   f.B.emplace(make_batch(h, h->P, L, d_frames, frame_stride_bytes, nframes, depthInput, f.s, cameras ? &f.camSel : nullptr));
-  f.chunk = choose_chunk(h->tune, h->P.nPoints, nframes);
+  f.chunk = chunk_plan(h->tune, h->P.nPoints, nframes).chunk;
   return SSD_OK;
 }
 
@@ -3467,27 +3464,6 @@ int ssd_process_depth_host_warp_fused(ssd_handle *h, const uint16_t *depth, int 
     });
 }
 
-/* pinned host memory for frames (DMA without a staging copy) */
-int ssd_host_alloc(size_t bytes, void **ptr)
-{
-  if(!ptr || bytes == 0)
-    return fail(SSD_E_ARG, "ssd_host_alloc: bad argument");
-  if(ssd_device_count() <= 0)
-    return fail(SSD_E_NODEVICE, "ssd_host_alloc: no HIP device");
-  *ptr = nullptr;
-  const hipError_t e = hipHostMalloc(ptr, bytes, hipHostMallocDefault);
-  if(e != hipSuccess)
-    return hip_fail(e, "hipHostMalloc: ");
-  return SSD_OK;
-}
-
-int ssd_host_free(void *ptr)
-{
-  if(ptr)
-    HIP_TRY(hipHostFree(ptr));
-  return SSD_OK;
-}
-
 int ssd_get_debug(ssd_handle *h, int frame, ssd_debug_frame *out)
 {
   if(!h || !out)
@@ -3518,169 +3494,6 @@ int ssd_get_debug_image(ssd_handle *h, int frame, int step_slot, int closed, uin
     for(int x = 0; x < W; x++)
       out[static_cast<size_t>(y) * W + x] = ((words[static_cast<size_t>(y) * W64 + (x >> 6)] >> (x & 63)) & 1ull) ? 0xff : 0;
   return SSD_OK;
-}
-
-/* ---- plain device-memory helpers --------------------------------------------- */
-
-int ssd_device_alloc(int device, size_t bytes, void **d_ptr)
-{
-  if(!d_ptr)
-    return fail(SSD_E_ARG, "ssd_device_alloc: null");
-  if(ssd_device_count() <= 0)
-    return fail(SSD_E_NODEVICE, "ssd_device_alloc: no HIP device");
-  HIP_TRY(hipSetDevice(device));
-  HIP_TRY(hipMalloc(d_ptr, bytes));
-  return SSD_OK;
-}
-int ssd_device_free(int device, void *d_ptr)
-{
-  HIP_TRY(hipSetDevice(device));
-  HIP_TRY(hipFree(d_ptr));
-  return SSD_OK;
-}
-int ssd_device_upload(int device, void *d_dst, const void *src, size_t bytes)
-{
-  HIP_TRY(hipSetDevice(device));
-  HIP_TRY(hipMemcpy(d_dst, src, bytes, hipMemcpyHostToDevice));
-  return SSD_OK;
-}
-int ssd_device_download(int device, void *dst, const void *d_src, size_t bytes)
-{
-  HIP_TRY(hipSetDevice(device));
-  HIP_TRY(hipMemcpy(dst, d_src, bytes, hipMemcpyDeviceToHost));
-  return SSD_OK;
-}
-int ssd_device_sync(int device)
-{
-  HIP_TRY(hipSetDevice(device));
-  HIP_TRY(hipDeviceSynchronize());
-  return SSD_OK;
-}
-
-extern "C++"
-{
-namespace
-{
-/* first line of a sysfs attribute, without the newline; empty when it cannot be read */
-std::string sysfs_line(const std::string &path)
-{
-  std::ifstream f(path);
-  std::string s;
-  if(f)
-    std::getline(f, s);
-  return s;
-}
-/* "0-15,128-143" -> CPU numbers; anything malformed ends the list there */
-std::vector<int> parse_cpu_list(const std::string &list)
-{
-  std::vector<int> cpus;
-  const char *p = list.c_str();
-  while(*p)
-  {
-    char *end = nullptr;
-    const long a = std::strtol(p, &end, 10);
-    if(end == p || a < 0)
-      break;
-    long b = a;
-    p = end;
-    if(*p == '-')
-    {
-      b = std::strtol(p + 1, &end, 10);
-      if(end == p + 1 || b < a)
-        break;
-      p = end;
-    }
-    for(long c = a; c <= b && cpus.size() < 4096; c++)
-      cpus.push_back(static_cast<int>(c));
-    if(*p == ',')
-      p++;
-    else
-      break;
-  }
-  return cpus;
-}
-} // namespace
-} // extern "C++"
-
-/* the device's report, and (full != nullptr) its local CPU list as sysfs spells it - the report's field holds 255 characters of it */
-static int device_info_impl(int device, ssd_device_info *out, std::string *full)
-{
-  if(!out)
-    return fail(SSD_E_ARG, "ssd_device_info_get: null");
-  const int n = ssd_device_count();
-  if(n <= 0)
-    return fail(SSD_E_NODEVICE, "ssd_device_info_get: no HIP device");
-  if(device < 0 || device >= n)
-    return fail(SSD_E_ARG, "ssd_device_info_get: device index out of range");
-  std::memset(out, 0, sizeof(*out));
-  out->numa_node = -1;
-  HIP_TRY(hipDeviceGetPCIBusId(out->pci_bus_id, static_cast<int>(sizeof(out->pci_bus_id)), device));
-  for(char *c = out->pci_bus_id; *c; c++)
-    if(*c >= 'A' && *c <= 'F')
-      *c = static_cast<char>(*c - 'A' + 'a');                 /* sysfs spells bus ids in lower case */
-  hipUUID uuid;
-  hipDevice_t dev;
-  if(hipDeviceGet(&dev, device) == hipSuccess && hipDeviceGetUuid(&uuid, dev) == hipSuccess)
-  {
-    static const char hex[] = "0123456789abcdef";
-    for(int i = 0; i < 16; i++)
-    {
-      const unsigned char b = static_cast<unsigned char>(uuid.bytes[i]);
-      out->uuid[2 * i] = hex[b >> 4];
-      out->uuid[2 * i + 1] = hex[b & 15];
-    }
-  }
-  else
-    (void)hipGetLastError();
-  const std::string dir = std::string("/sys/bus/pci/devices/") + out->pci_bus_id + "/";
-  const std::string node = sysfs_line(dir + "numa_node");
-  if(!node.empty())
-    out->numa_node = std::atoi(node.c_str());
-  const std::string cpus = sysfs_line(dir + "local_cpulist");
-  std::snprintf(out->cpu_list, sizeof(out->cpu_list), "%s", cpus.c_str());
-  out->n_local_cpus = static_cast<int32_t>(parse_cpu_list(cpus).size());
-  if(full)
-    *full = cpus;
-  return SSD_OK;
-}
-
-int ssd_device_info_get(int device, ssd_device_info *out)
-{
-  return device_info_impl(device, out, nullptr);
-}
-
-int ssd_bind_thread_to_device(int device)
-{
-  ssd_device_info info;
-  std::string list;               /* the whole sysfs line: the report's copy may end in the middle of a number ("128-143" cut to "12") */
-  const int rc = device_info_impl(device, &info, &list);
-  if(rc != SSD_OK)
-    return rc;
-  const std::vector<int> cpus = parse_cpu_list(list);
-  if(cpus.empty())
-    return 0;
-  cpu_set_t *set = CPU_ALLOC(4096);
-  if(!set)
-    return fail(SSD_E_NOMEM, "ssd_bind_thread_to_device: CPU_ALLOC");
-  const size_t bytes = CPU_ALLOC_SIZE(4096);
-  /* only CPUs this thread may run on (a container's cpuset can be narrower than the node): an empty intersection changes nothing */
-  cpu_set_t *allowed = CPU_ALLOC(4096);
-  int bound = 0;
-  if(allowed && sched_getaffinity(0, bytes, allowed) == 0)
-  {
-    CPU_ZERO_S(bytes, set);
-    for(int c : cpus)
-      if(c < 4096 && CPU_ISSET_S(c, bytes, allowed))
-      {
-        CPU_SET_S(c, bytes, set);
-        bound++;
-      }
-    if(bound > 0 && sched_setaffinity(0, bytes, set) != 0)
-      bound = 0;
-  }
-  if(allowed) CPU_FREE(allowed);
-  CPU_FREE(set);
-  return bound;
 }
 
 } // extern "C"

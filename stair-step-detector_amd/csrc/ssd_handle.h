@@ -7,29 +7,13 @@
 
 #include "ssd_device.h"
 #include "ssd_owned.h"
+#include "ssd_chunks.h"                     /* ssd_tuning: the launch-geometry constants of a handle, beside the chunk rules that read them */
 #include <cstring>
 #include <string>
 #include <vector>
 
 namespace ssd { struct GroundPrior; }          /* ssd_ground.h */
 namespace ssd { struct PoseTarget; }           /* ssd_pose.h */
-
-/* Launch-geometry constants of a handle.  The product uses the compiled defaults below (each one measured: ssd_capi.hip,
- * choose_chunk / enqueue_impl).  Only a tools build (make EXTRA=-DSSD_TUNING OUT=../lib_tuning, tools/exp*.sh) reads
- * overrides from the environment (SSD_CHUNK_POINTS, SSD_TARGET_BLOCKS, SSD_K1_BLOCKS_PER_FRAME, SSD_K24_MIN_BLOCKS,
- * SSD_K24_TALL_BLOCKS, SSD_K2_CHUNK_TILES, SSD_K4_CHUNK_TILES, SSD_WIN_SHIFT, SSD_WIN_SHIFT_G, SSD_FUSE_GROUP_FASTEST), and only once, in ssd_create:
- * no entry point of the product library calls getenv. */
-struct ssd_tuning
-{
-  int chunkPoints = 0;            /* > 0: the general chunk, forced */
-  int targetBlocks = 32768;       /* blocks a streaming launch aims at */
-  int k1BlocksPerFrame = 256;     /* K1: at most this many blocks per frame (their final atomics share the frame's histogram) */
-  int k24MinBlocks = 1536, k24TallBlocks = 6144;
-  int k2ChunkTiles = 32, k4ChunkTiles = 16;
-  int winShift = 0, winShiftGround = 0;     /* > 0: shape of the waves' LDS image windows, forced */
-  int recordPad = 0;              /* cell records per frame added to the stride between the frames' record arrays */
-  int fuseGroupFastest = 0;       /* k_depth_fuse's grid: 0 = neighbouring blocks take neighbouring chunks of one group, 1 = the same chunk of neighbouring groups */
-};
 
 /* The events around an optional pass (k_labels, k_riser_labels, k_surface_moments) of the timed enqueues: a ring of SSD_TIMING_SLOTS pairs,
  * all of them or none, and whether the enqueue of a slot ran the pass between its pair */

@@ -3,19 +3,11 @@
 #define SSD_LAUNCH_H_
 
 #include "ssd_device.h"
+#include "ssd_chunks.h"                     /* kTileHost and the kMaxTilesPerBlock*Host bounds, beside the chunk rules that read them */
 
 namespace ssd
 {
-constexpr int kTileHost = 1024;
-/* kTileHost = kThreads * kPts of ssd_kernels.hip: chunk sizes are multiples of it; a block's chunk is at most
- * kMaxTilesPerBlockHost tiles (K1 keeps the chunk's cell masks, K2/K4/K6 the list of its wanted cells, in LDS) */
-#ifndef SSD_MAX_TILES
-#define SSD_MAX_TILES 32
-#endif
-constexpr int kMaxTilesPerBlockHost = SSD_MAX_TILES;
-constexpr int kMaxTilesPerBlockRasterHost = 128;   /* K2 only */
-constexpr int kMaxTilesPerBlockInquadHost = 128;   /* K4 only */
-constexpr int kCellHost = 64;               /* points per cell (one gating mask each) */
+constexpr int kCellHost = 64;              /* points per cell (one gating mask each) */
 /* The single pass (k_hist rasters the step plateaus itself) pays a kernel (k_predict) that a few frames do
  * not earn back; its keys hold 13 bits of row and its windows must fit the image. */
 /* from 64 XGA frames per batch on (tools/sp_frames.py: 48 frames 3 % slower, 64 frames 4 % faster; VGA between 128 and 192

@@ -168,7 +168,7 @@ TILE_CELLS = 16                                        # kTileHost / kCell: a la
 def census(labels, listed=None, cols=1, chunk_cells=None):
     """The slot composition of a walk over `labels` (uint8, one per point, 0 = none), following load_cell and cell_list_build
     (csrc/ssd_kernels.hip).  The frame is cut into chunks of chunk_cells 64-point cells (a block's share; a multiple of TILE_CELLS in
-    a launch, csrc/ssd_capi.hip choose_chunk; None: one chunk spans the frame).  Per chunk: the listed cells in cell_list_build's
+    a launch, csrc/ssd_chunks.h choose_chunk; None: one chunk spans the frame).  Per chunk: the listed cells in cell_list_build's
     order (cols = 1: ascending, as k_labels, k_surface_moments and k_surface_refit build it; cols > 1: column-major over rows of `cols`
     cells counted from the chunk's first, as k_risers and k_riser_moments do), four consecutive entries per group, the last group
     filled up with invalid points, and in a group lane l's point j = point 4 (l & 15) + j of entry l >> 4: slot j of a group holds the

@@ -112,7 +112,7 @@ def test_the_slot_census_of_every_layout(ssd, oracle, f):
         for cells in (most, least):
             per_block = np.bincount(cells // fw.GROUP)
             assert set(per_block.tolist()) <= {0, fw.GROUP}, "a block of four cells is listed in part"
-    # one tile per block (what a batch of 8 VGA frames gets: csrc/ssd_capi.hip choose_chunk), 32 tiles, and the frame as one chunk
+    # one tile per block (what a batch of 8 VGA frames gets: csrc/ssd_chunks.h choose_chunk), 32 tiles, and the frame as one chunk
     for chunk in (fw.TILE_CELLS, 32 * fw.TILE_CELLS, None):
         for cells in (most, least):
             n_labels, first = fw.census(r.labels, cells, chunk_cells=chunk)

@@ -53,6 +53,25 @@ def test_launch_rules_compile_alone_for_the_host(tmp_path):
     compile_alone("ssd_launch_rules.h", tmp_path, "--offload-host-only")
 
 
+def test_chunk_rules_compile_alone_without_hip(tmp_path):
+    """The chunk rules (ssd_chunks.h) are a plain header: g++ alone compiles a file that includes nothing else."""
+    src = tmp_path / "only_ssd_chunks.cpp"
+    src.write_text('#include "ssd_chunks.h"\n')
+    run = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only", "-I", CSRC, str(src)], capture_output=True, text=True, timeout=60)
+    assert run.returncode == 0, run.stderr[-4000:]
+
+
+@pytest.mark.skipif(HIPCC is None, reason="hipcc is not installed")
+def test_capi_header_compiles_alone_as_plain_cxx(tmp_path):
+    """What the units of the C ABI that call HIP share (ssd_capi.h), under the compiler line of the Makefile's HOSTFLAGS."""
+    rocm = subprocess.run([os.path.join(os.path.dirname(HIPCC), "hipconfig"), "--rocmpath"], check=True, capture_output=True, text=True).stdout.strip()
+    src = tmp_path / "only_ssd_capi.cpp"
+    src.write_text('#include "ssd_capi.h"\n')
+    run = subprocess.run([HIPCC, "-x", "c++", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"),
+                          "-Wall", "-Wno-unused-function", "-fsyntax-only", "-I", CSRC, str(src)], capture_output=True, text=True, timeout=300)
+    assert run.returncode == 0, run.stderr[-4000:]
+
+
 def test_which_file_includes_which_hip():
     found = {}
     for path in sorted(glob.glob(os.path.join(CSRC, "*"))):
