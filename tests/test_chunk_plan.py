@@ -1,5 +1,5 @@
 """csrc/ssd_chunks.h by itself: chunk_plan, the points per block of the general chunk and of K1, K2 and K4 that every enqueue takes
-(DESIGN.md section 7r), through tests/chunk_plan_main.cpp - a program of its own, built with g++ and run.  Neither a GPU nor the HIP
+(DESIGN.md section 7r), through tests/chunk_plan_main.cpp - a program of its own, built with g++ and run (tests/follow_geometry.py).  Neither a GPU nor the HIP
 toolchain is needed: the header includes nothing.
 
 The default tuning over six frame shapes and eight batch sizes.  Every chunk is a whole number of tiles and within its kernel's
@@ -7,30 +7,20 @@ bound (the program prints the header's constants: none is copied here), and equa
 stood inline in enqueue_impl before they had a header, recorded once from that text."""
 import json
 import os
-import subprocess
 
 import pytest
 
+from follow_geometry import build_chunk_plan, chunk_plans
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "stair-step-detector_amd", "csrc")
 SHAPES = [64 * 16, 96 * 16, 640 * 480, 848 * 480, 1024 * 768, 1920 * 1080]
 FRAMES = [1, 2, 8, 16, 64, 65, 256, 1024]
 
 
 @pytest.fixture(scope="module")
 def plans(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("chunk_plan") / "chunk_plan_main")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", CSRC, os.path.join(HERE, "chunk_plan_main.cpp"), "-o", exe], check=True)
-    args = [str(v) for n in SHAPES for f in FRAMES for v in (n, f)]
-    lines = subprocess.run([exe] + args, check=True, capture_output=True, text=True, timeout=60).stdout.splitlines()
-    tile, max_tiles, max_raster, max_inquad = (int(x) for x in lines[0].split())
-    bounds = {"chunk": max_tiles * tile, "hist": max_tiles * tile, "raster": max_raster * tile, "inquad": max_inquad * tile}
-    got = {}
-    for line in lines[1:]:
-        n, f, chunk, hist, raster, inquad = (int(x) for x in line.split())
-        got[(n, f)] = {"chunk": chunk, "hist": hist, "raster": raster, "inquad": inquad}
-    return tile, bounds, got
+    exe = build_chunk_plan(tmp_path_factory.mktemp("chunk_plan"))
+    return chunk_plans(exe, [(n, f) for n in SHAPES for f in FRAMES])
 
 
 def test_every_case_has_a_plan(plans):

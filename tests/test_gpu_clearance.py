@@ -25,7 +25,7 @@ TWO_PASSES, SINGLE_PASS, NO_PLANES = (0, 0), (1, 0), (1, 2)     # Detector.singl
 class Resident:
     """frames resident on the device behind one detector; every pass into freshly poisoned buffers"""
 
-    def __init__(self, ssd, device, cfg, trans, frames, depth=False, intr=None, mode=None, cameras=None, order=None, pad=None):
+    def __init__(self, ssd, device, cfg, trans, frames, depth=False, intr=None, mode=None, cameras=None, order=None, pad=None, fill=None):
         self.ssd, self.cfg, self.depth, self.intr, self.order = ssd, cfg, depth, intr, order
         self.frames, self.n, self.wh = frames, len(frames), cfg.width * cfg.height
         self.cal = trans.constants
@@ -43,8 +43,11 @@ class Resident:
         assert self.stride % 16 != 0
         self.src = ssd.DeviceBuffer(self.stride * self.n, device)
         self.bufs.append(self.src)
-        for i, f in enumerate(frames):
-            self.src.upload(np.ascontiguousarray(f), offset=i * self.stride)
+        if fill is not None:                                           # a large batch: fill(buffer, stride) makes the frames on the device
+            fill(self.src, self.stride)
+        else:
+            for i, f in enumerate(frames):
+                self.src.upload(np.ascontiguousarray(f), offset=i * self.stride)
         self.rec = C.sizeof(ssd.FrameMoments)
         self.mstride = self.wh + MASK_PAD
         self.out = ssd.DeviceBuffer(self.rec * (self.n + 1), device)
