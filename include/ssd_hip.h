@@ -1414,6 +1414,80 @@ int ssd_process_depth_host_warp_fused(ssd_handle *h, const uint16_t *depth, int 
                                       ssd_frame_result *results /* nframes / n */, uint16_t *fused /* may be NULL */,
                                       ssd_depth_warp_stats *warp_stats /* may be NULL */, ssd_depth_fuse_stats *fuse_stats /* may be NULL */);
 
+/* ---- depth fill: the holes and the one-pixel see-through that the forward warp leaves, closed from ONE frame ------
+ * A frame is width x height 16-bit depth samples; a pixel outside the frame is the sample 0.  The decision for the pixel with sample d is
+ * taken from the INPUT frame alone, never from another pixel's output: the result does not depend on order.  Integers only.  The four
+ * opposite pairs (a, b) of its neighbours are taken in the order W/E, N/S, NW/SE, NE/SW:
+ *   lo = min(a, b), hi = max(a, b), t = min(65535, tol + ((lo * slope) >> 12))      (32 bits)
+ *   agrees: a != 0 and b != 0 and hi - lo <= t
+ *   m     = (a + b + 1) >> 1                      (= lo + ((hi - lo + 1) >> 1): it fits 16 bits and lies in lo .. hi)
+ *   covers: agrees and hi + t < d                 (32 bits, cannot wrap)
+ * The classes, tested in this order: EMPTY d == 0 and fewer than min_pairs agreeing pairs -> 0; FILLED d == 0 otherwise -> the m of the
+ * agreeing pair with the smallest hi - lo, the first in the order above on a tie; COVERED d != 0, cover != 0 and at least cover covering
+ * pairs -> the m of the covering pair with the smallest hi - lo, the first on a tie (a background sample seen through a one-pixel crack
+ * of a nearer surface); otherwise KEPT -> d.  So a sample is only ever put between two samples that agree on opposite sides of the
+ * pixel, never nearer than both or farther than both: a rim is not fattened.  With cover 0 a frame without zeros comes back byte for
+ * byte.  The optional class byte is SSD_FILL_KEPT / _EMPTY / _FILLED / _COVERED; per frame one exact record whose four counts add up to
+ * the pixel count. */
+#define SSD_FILL_KEPT 0
+#define SSD_FILL_EMPTY 1
+#define SSD_FILL_FILLED 2
+#define SSD_FILL_COVERED 3
+typedef struct
+{
+  int32_t min_pairs;            /* 1 .. 4: the agreeing pairs a hole needs */
+  int32_t cover;                /* 0 .. 4: the covering pairs a valid pixel needs to be replaced; 0 switches the COVERED test off */
+  int32_t tol;                  /* 0 .. 65535, raw units */
+  int32_t slope;                /* 0 .. 4096, in 1 / 4096 of the pair's lower sample */
+} ssd_depth_fill_rule;          /* 16 bytes */
+typedef struct
+{
+  int64_t n_kept, n_empty, n_filled, n_covered;
+  int64_t sum_pairs;            /* the agreeing pairs of FILLED pixels plus the covering pairs of COVERED pixels */
+  int64_t sum_spread;           /* the hi - lo of every pair used: per FILLED or COVERED pixel, that of the pair whose m it took */
+  int64_t reserved[2];
+} ssd_depth_fill_stats;         /* 64 bytes */
+/* host only: min_pairs = 1, cover = 1, tol = SSD_FUSE_TOL, slope = 0.  SSD_E_ARG: null */
+int ssd_depth_fill_default_rule(ssd_depth_fill_rule *rule);
+/* host only, no GPU needed: the rule over ONE packed frame.  rule NULL: the defaults; out: width * height values; cls (may be NULL): as
+ * many bytes; stats: the frame's record.  frame and out must not overlap.  SSD_E_ARG: a null pointer, width or height not positive, a
+ * rule outside 1 <= min_pairs <= 4, 0 <= cover <= 4, 0 <= tol <= 65535, 0 <= slope <= 4096. */
+int ssd_depth_fill_host(int width, int height, const uint16_t *frame, const ssd_depth_fill_rule *rule, uint16_t *out,
+                        uint8_t *cls /* may be NULL */, ssd_depth_fill_stats *stats);
+/* The pass (k_depth_fill) over depth frames resident in device memory, on the caller's stream, in order, without synchronising: the
+ * contract of ssd_enqueue_depth_edges - no detection workspace, nothing ssd_fetch* reads is touched, no intrinsics or calibration needed;
+ * calls on different streams run in call order.  Filled frame i goes to d_out + i * out_stride_bytes, its class bytes (d_cls may be
+ * NULL) to d_cls + i * cls_stride_bytes, byte for byte ssd_depth_fill_host's.  d_frames may be what ssd_enqueue_depth_warp wrote on
+ * that stream, and ssd_enqueue_depth_fuse, ssd_enqueue_depth_edges or a depth-input enqueue on it may read d_out, with no host wait in
+ * between.  The records (max_frames_per_batch on the device and pinned) are made on the first call and counted in ssd_workspace_bytes
+ * from then on; a handle that never calls this allocates, creates and launches nothing for it.
+ * SSD_E_ARG before anything is launched or copied: a null handle, input or output; nframes outside 1 .. max_frames_per_batch; a rule
+ * out of range; frames or output off 2-byte alignment or a stride that holds no frame; a class stride below a frame's bytes (width *
+ * height) with more than one frame; ANY overlap of the output or class range with the input range (a stencil in place is a race). */
+int ssd_enqueue_depth_fill(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream,
+                           const ssd_depth_fill_rule *rule /* NULL: the defaults */, void *d_out, size_t out_stride_bytes,
+                           uint8_t *d_cls /* may be NULL */, size_t cls_stride_bytes);
+/* waits for the last ssd_enqueue_depth_fill and hands over its frames' records; nframes <= its */
+int ssd_fetch_depth_fill(ssd_handle *h, ssd_depth_fill_stats *out, int nframes, void *stream);
+/* the device time of the last pass, the zeroing in front of it and the copy of its records behind it included (0 when timing was off for it) */
+int ssd_get_depth_fill_time(ssd_handle *h, float *ms);
+/* depth frames in host memory (pinned or pageable): every frame is filled on the device and the filled frame is detected, slice by
+ * slice through the staging buffers of ssd_process_depth_host.  results: nframes records, byte for byte ssd_process_depth_host's over
+ * ssd_depth_fill_host's output; filled (may be NULL): nframes packed frames; stats (may be NULL): as many records. */
+int ssd_process_depth_host_fill(ssd_handle *h, const uint16_t *depth, int nframes, const ssd_depth_fill_rule *rule,
+                                ssd_frame_result *results, uint16_t *filled /* may be NULL */, ssd_depth_fill_stats *stats /* may be NULL */);
+/* ssd_process_depth_host_warp_fused with the fill between the warp and the fusion: frame i is warped under views[i], the warped frame
+ * filled (fill_rule NULL: the defaults), every n filled frames fused and the fused frame detected.  results: nframes / n records, byte
+ * for byte ssd_process_depth_host's over ssd_depth_fuse_host's over ssd_depth_fill_host's over ssd_depth_warp_host's output; fused (may
+ * be NULL): nframes / n packed frames; warp_stats and fill_stats (may be NULL): nframes records each; fuse_stats (may be NULL): nframes
+ * / n.  SSD_E_ARG: as ssd_process_depth_host_warp_fused, a fill rule out of range. */
+int ssd_process_depth_host_warp_fill_fused(ssd_handle *h, const uint16_t *depth, int nframes, int n, const ssd_depth_warp_view *views,
+                                           const ssd_intrinsics *dst, const ssd_depth_fill_rule *fill_rule,
+                                           const ssd_depth_fuse_rule *fuse_rule, ssd_frame_result *results /* nframes / n */,
+                                           uint16_t *fused /* may be NULL */, ssd_depth_warp_stats *warp_stats /* may be NULL */,
+                                           ssd_depth_fill_stats *fill_stats /* may be NULL */,
+                                           ssd_depth_fuse_stats *fuse_stats /* may be NULL */);
+
 /* stage selector for profiling / roofline measurement: runs only the chosen stage(s) of the pipeline */
 #define SSD_STAGE_HIST 1       /* K1: transform + crop + bin + histogram */
 #define SSD_STAGE_PEAKS 2

@@ -314,6 +314,23 @@ class WarpStats(C.Structure):
                 ("n_filled", C.c_int64), ("reserved", C.c_int64 * 2)]
 
 
+FILL_KEPT, FILL_EMPTY, FILL_FILLED, FILL_COVERED = 0, 1, 2, 3          # SSD_FILL_*
+
+
+class FillRule(C.Structure):
+    """ssd_depth_fill_rule: how many of a hole's four opposite neighbour pairs must agree for it to be filled (min_pairs), how many
+    agreeing pairs must lie more than t in front of a valid pixel for it to be replaced (cover; 0: never), and how far apart a pair's
+    two samples may lie to agree: t = tol + ((lo * slope) >> 12) raw units (depth fill)"""
+    _fields_ = [("min_pairs", C.c_int32), ("cover", C.c_int32), ("tol", C.c_int32), ("slope", C.c_int32)]
+
+
+class FillStats(C.Structure):
+    """ssd_depth_fill_stats: a frame's record - its pixels by class (they add up to the pixel count), the pairs that made pixels FILLED
+    or COVERED, and the spreads hi - lo of the pairs whose middle was written"""
+    _fields_ = [("n_kept", C.c_int64), ("n_empty", C.c_int64), ("n_filled", C.c_int64), ("n_covered", C.c_int64), ("sum_pairs", C.c_int64),
+                ("sum_spread", C.c_int64), ("reserved", C.c_int64 * 2)]
+
+
 class Foothold(C.Structure):
     """ssd_foothold: one surface's cells (TG_OUT / TG_FREE / TG_OCCUPIED / TG_UNSEEN) and the best free rectangle on it"""
     _fields_ = [("state", C.c_uint8 * TG_COLS * TG_ROWS), ("n_free", C.c_int32), ("n_occupied", C.c_int32), ("n_unseen", C.c_int32),
@@ -412,6 +429,8 @@ EXPORTS = [
     "ssd_process_depth_host_edges",
     "ssd_depth_warp_view_between", "ssd_depth_warp_host", "ssd_enqueue_depth_warp", "ssd_fetch_depth_warp", "ssd_get_depth_warp_time",
     "ssd_process_depth_host_warp_fused",
+    "ssd_depth_fill_default_rule", "ssd_depth_fill_host", "ssd_enqueue_depth_fill", "ssd_fetch_depth_fill", "ssd_get_depth_fill_time",
+    "ssd_process_depth_host_fill", "ssd_process_depth_host_warp_fill_fused",
 ]
 # libssd_source.so — the frame source standing in for the camera (include/ssd_source.h)
 SOURCE_EXPORTS = [
@@ -574,6 +593,15 @@ def lib():
     L.ssd_get_depth_warp_time.argtypes = [vp, C.POINTER(C.c_float)]
     L.ssd_process_depth_host_warp_fused.argtypes = [vp, vp, i32, i32, C.POINTER(WarpView), C.POINTER(Intrinsics), C.POINTER(FuseRule),
                                                     C.POINTER(FrameResult), vp, C.POINTER(WarpStats), C.POINTER(FuseStats)]
+    L.ssd_depth_fill_default_rule.argtypes = [C.POINTER(FillRule)]
+    L.ssd_depth_fill_host.argtypes = [i32, i32, vp, C.POINTER(FillRule), vp, vp, C.POINTER(FillStats)]
+    L.ssd_enqueue_depth_fill.argtypes = [vp, vp, sz, i32, vp, C.POINTER(FillRule), vp, sz, vp, sz]
+    L.ssd_fetch_depth_fill.argtypes = [vp, C.POINTER(FillStats), i32, vp]
+    L.ssd_get_depth_fill_time.argtypes = [vp, C.POINTER(C.c_float)]
+    L.ssd_process_depth_host_fill.argtypes = [vp, vp, i32, C.POINTER(FillRule), C.POINTER(FrameResult), vp, C.POINTER(FillStats)]
+    L.ssd_process_depth_host_warp_fill_fused.argtypes = [vp, vp, i32, i32, C.POINTER(WarpView), C.POINTER(Intrinsics), C.POINTER(FillRule),
+                                                         C.POINTER(FuseRule), C.POINTER(FrameResult), vp, C.POINTER(WarpStats),
+                                                         C.POINTER(FillStats), C.POINTER(FuseStats)]
     L.ssd_process_host_stair_pose.argtypes = [vp, vp, i32, i32, C.POINTER(StairPoseTarget), i32, C.POINTER(C.c_uint16), C.POINTER(StairPoseRule), i32,
                                               C.c_double, C.POINTER(StairPoseMoments), C.POINTER(StairPose)]
     L.ssd_enqueue_cameras_surface_refit_folded.argtypes = [vp, vp, sz, i32, vp, i32, vp, i32, C.c_double, C.c_double, i32, vp]
@@ -1092,6 +1120,27 @@ def depth_warp_host(frame, view, dst):
     return out, stats
 
 
+def depth_fill_default_rule():
+    """ssd_depth_fill_default_rule: min_pairs 1, cover 1, tol = FUSE_TOL, slope 0"""
+    rule = FillRule()
+    _check(lib().ssd_depth_fill_default_rule(C.byref(rule)))
+    return rule
+
+
+def depth_fill_host(frame, rule=None, classes=False):
+    """ssd_depth_fill_host: ONE depth frame, uint16 [H, W] -> (filled uint16 [H, W], FillStats), with classes=True (filled, FillStats,
+    classes uint8 [H, W]: FILL_KEPT / FILL_EMPTY / FILL_FILLED / FILL_COVERED).  rule None: the defaults"""
+    a = np.ascontiguousarray(frame)
+    if a.dtype != np.uint16 or a.ndim != 2:
+        raise SsdError("depth_fill_host: uint16 [H, W] expected")
+    H, W = a.shape
+    out, stats = np.zeros((H, W), np.uint16), FillStats()
+    cls = np.zeros((H, W), np.uint8) if classes else None
+    _check(lib().ssd_depth_fill_host(W, H, a.ctypes.data_as(C.c_void_p), None if rule is None else C.byref(rule), out.ctypes.data_as(C.c_void_p),
+                                     None if cls is None else cls.ctypes.data_as(C.c_void_p), C.byref(stats)))
+    return (out, stats, cls) if classes else (out, stats)
+
+
 def riser_fit_solve(moments, risers, cal, min_points=100):
     """ssd_riser_fit_solve: a frame's riser moments (FrameMoments, record i = riser i) and its FrameRisers -> a plane per riser
     (FrameRiserFits; per riser GF_OK / GF_FEW / GF_DEGENERATE, lean, skew, rise and going)"""
@@ -1361,20 +1410,22 @@ class Detector:
         """a host-fed depth pre-pass (ssd_<who>(handle, depth, total, *args, results, frames, [first's,] stats)): every `group` frames
         become one and that one is detected -> its FrameResults, with the staged frames (uint16 [k, H, W]) and / or its k Stats behind
         them.  first = (Type, wanted): a pre-pass of two passes, whose first leaves a record per INPUT frame - they go in front of the
-        k Stats"""
+        k Stats; a list of such pairs: a pre-pass of more passes, each but the last leaving a record per input frame, in that order"""
         a, total, _ = self._frames_arg(who, depth, True)
         k = total // group if group > 0 else 0
         res = (FrameResult * max(k, 1))()
         f = np.zeros((max(k, 1), self.cfg.height, self.cfg.width), np.uint16) if frames else None
         st = (Stats * max(k, 1))() if stats else None
-        fst = (first[0] * max(total, 1))() if first and first[1] else None
+        firsts = [] if not first else [first] if isinstance(first, tuple) else list(first)
+        fsts = [(T * max(total, 1))() if wanted else None for T, wanted in firsts]
         _check(getattr(lib(), "ssd_" + who)(self._h, a.ctypes.data_as(C.c_void_p), total, *args, res,
-                                            None if f is None else f.ctypes.data_as(C.c_void_p), *((fst,) if first else ()), st))
+                                            None if f is None else f.ctypes.data_as(C.c_void_p), *fsts, st))
         out = [list(res)[:k]]
         if frames:
             out.append(f[:k])
-        if fst is not None:
-            out.append([first[0].from_buffer_copy(fst[i]) for i in range(total)])
+        for (T, _), fst in zip(firsts, fsts):
+            if fst is not None:
+                out.append([T.from_buffer_copy(fst[i]) for i in range(total)])
         if stats:
             out.append([Stats.from_buffer_copy(st[i]) for i in range(k)])
         return out[0] if len(out) == 1 else tuple(out)
@@ -1750,6 +1801,45 @@ class Detector:
         return self._depth_host_pre("process_depth_host_warp_fused", depth, int(n), FuseStats, fused, fuse_stats, int(n), arr,
                                     None if dst is None else C.byref(dst), None if fuse_rule is None else C.byref(fuse_rule),
                                     first=(WarpStats, warp_stats))
+
+    # ---- depth fill: holes and one-pixel see-through closed between agreeing samples (include/ssd_hip.h)
+    def enqueue_depth_fill(self, d_ptr, nframes, d_out, rule=None, d_cls=None, stride_bytes=None, out_stride_bytes=None, cls_stride_bytes=None,
+                           stream=None):
+        """ssd_enqueue_depth_fill: the nframes uint16 depth frames at d_ptr filled on the caller's stream: frame i to d_out + i *
+        out_stride_bytes, its class bytes (d_cls None: none) likewise.  -> nframes.  d_ptr may be what enqueue_depth_warp wrote on that
+        stream, and enqueue_depth_fuse, enqueue_depth_edges or a depth-input enqueue on it may read d_out, with no host wait in
+        between.  The output must not overlap the input."""
+        frame = self.cfg.width * self.cfg.height * 2
+        _check(lib().ssd_enqueue_depth_fill(self._h, C.c_void_p(d_ptr), stride_bytes or frame, int(nframes), C.c_void_p(stream or 0),
+                                            None if rule is None else C.byref(rule), C.c_void_p(d_out), out_stride_bytes or frame,
+                                            C.c_void_p(d_cls or 0), cls_stride_bytes or frame // 2))
+        return int(nframes)
+
+    def fetch_depth_fill(self, nframes, stream=None):
+        """ssd_fetch_depth_fill: waits for the last enqueue_depth_fill -> list of FillStats (independent copies), one per frame"""
+        return self._fetch_records(lib().ssd_fetch_depth_fill, FillStats, nframes, stream)
+
+    def depth_fill_time_ms(self):
+        """the device time of the last fill pass, its zeroing and its records' copy included (0 unless set_timing was on)"""
+        return _time_ms(lib().ssd_get_depth_fill_time, self._h)
+
+    def process_depth_host_fill(self, depth, rule=None, filled=False, stats=False):
+        """ssd_process_depth_host_fill: depth frames on the host, uint16 [k, H, W]: every frame filled on the device and the filled
+        frame detected -> list of k FrameResult; with filled=True / stats=True a tuple with the filled frames (uint16 [k, H, W]) and /
+        or the list of k FillStats behind it"""
+        return self._depth_host_pre("process_depth_host_fill", depth, 1, FillStats, filled, stats, None if rule is None else C.byref(rule))
+
+    def process_depth_host_warp_fill_fused(self, depth, n, views, dst, fill_rule=None, fuse_rule=None, fused=False, warp_stats=False,
+                                           fill_stats=False, fuse_stats=False):
+        """ssd_process_depth_host_warp_fill_fused: process_depth_host_warp_fused with every warped frame filled before the fusion ->
+        list of k FrameResult; with fused=True / warp_stats=True / fill_stats=True / fuse_stats=True a tuple with the fused frames
+        (uint16 [k, H, W]), the list of k * n WarpStats, the list of k * n FillStats and / or the list of k FuseStats behind it, in this
+        order"""
+        total = len(depth)
+        arr = _warp_views(views, total)
+        return self._depth_host_pre("process_depth_host_warp_fill_fused", depth, int(n), FuseStats, fused, fuse_stats, int(n), arr,
+                                    None if dst is None else C.byref(dst), None if fill_rule is None else C.byref(fill_rule),
+                                    None if fuse_rule is None else C.byref(fuse_rule), first=[(WarpStats, warp_stats), (FillStats, fill_stats)])
 
     def locate_camera(self, frames, prior, stair_map, passes=3, rule=None, min_points=200, observable=SP_OBSERVABLE, depth=False):
         """process_host_stair_pose `passes` times over the same frames of ONE camera, each pass starting from the calibration the pass

@@ -19,6 +19,7 @@
 #include "ssd_fuse.h"
 #include "ssd_edges.h"
 #include "ssd_warp.h"
+#include "ssd_fill.h"
 #include "ssd_refit.h"
 #include "ssd_clearance.h"
 #include "ssd_treadgrid.h"
@@ -3459,6 +3460,135 @@ int ssd_process_depth_host_warp_fused(ssd_handle *h, const uint16_t *depth, int 
     [&](int g0, int groups)
     {
       int r = warp_stats ? ssd_fetch_depth_warp(h, warp_stats + static_cast<size_t>(g0) * n, groups * n, nullptr) : static_cast<int>(SSD_OK);
+      if(!r && fuse_stats) r = ssd_fetch_depth_fuse(h, fuse_stats + g0, groups, nullptr);
+      return r;
+    });
+}
+
+/* ---- depth fill: holes and one-pixel see-through closed between agreeing samples (include/ssd_hip.h) ----------------- */
+
+/* the refusals of a fill call, before anything is launched or copied; *use: the rule to go by */
+static int check_depth_fill(const ssd_handle *h, const std::string &me, const void *d_frames, size_t frame_stride_bytes, int nframes,
+                            const ssd_depth_fill_rule *rule, const void *d_out, size_t out_stride_bytes, const uint8_t *d_cls, size_t cls_stride_bytes,
+                            ssd_depth_fill_rule *use)
+{
+  if(!h || !d_frames || !d_out)
+    return fail(SSD_E_ARG, me + ": null argument");
+  const int rc = check_fill_rule(me, rule, use);
+  if(rc) return rc;
+  if(nframes < 1 || nframes > h->F)
+    return fail(SSD_E_ARG, me + ": nframes must lie in 1 .. max_frames_per_batch");
+  return check_depth_planes(h, me, d_frames, frame_stride_bytes, nframes, d_out, out_stride_bytes, d_cls, cls_stride_bytes, nframes, "class", "class map");
+}
+
+/* arguments checked by the callers */
+static int enqueue_depth_fill_impl(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, hipStream_t s,
+                                   const ssd_depth_fill_rule &rule, void *d_out, size_t out_stride_bytes, uint8_t *d_cls, size_t cls_stride_bytes)
+{
+  HIP_TRY(hipSetDevice(h->device));
+  int rc = records_prepare(h, h->fill, true, "ssd_enqueue_depth_fill");
+  if(rc) return rc;
+  const bool timing = h->timing;
+  rc = pass_open(h->fill.pass, s, timing, "ssd_enqueue_depth_fill");    /* another stream: behind the previous call */
+  if(!rc) rc = pass_start(h->fill.pass, s, timing);
+  if(!rc) rc = records_zero(h->fill, nframes, s);
+  if(rc) return rc;
+  launch_depth_fill(d_frames, frame_stride_bytes, h->P.W, h->P.H, nframes, rule, d_out, out_stride_bytes, d_cls, cls_stride_bytes, h->fill.d, s);
+  return records_finish(h->fill, nframes, s, timing);
+}
+
+int ssd_enqueue_depth_fill(ssd_handle *h, const void *d_frames, size_t frame_stride_bytes, int nframes, void *stream, const ssd_depth_fill_rule *rule,
+                           void *d_out, size_t out_stride_bytes, uint8_t *d_cls, size_t cls_stride_bytes)
+{
+  ssd_depth_fill_rule R;
+  const int rc = check_depth_fill(h, "ssd_enqueue_depth_fill", d_frames, frame_stride_bytes, nframes, rule, d_out, out_stride_bytes, d_cls,
+                                  cls_stride_bytes, &R);
+  if(rc) return rc;
+  return enqueue_depth_fill_impl(h, d_frames, frame_stride_bytes, nframes, static_cast<hipStream_t>(stream), R, d_out, out_stride_bytes, d_cls,
+                                 cls_stride_bytes);
+}
+
+int ssd_fetch_depth_fill(ssd_handle *h, ssd_depth_fill_stats *out, int nframes, void *)
+{
+  return records_fetch(h, &ssd_handle::fill, out, nframes, "ssd_fetch_depth_fill", "ssd_enqueue_depth_fill", "frame");
+}
+
+int ssd_get_depth_fill_time(ssd_handle *h, float *ms)
+{
+  return pass_time(h, h ? &h->fill.pass : nullptr, "ssd_get_depth_fill_time", "ssd_enqueue_depth_fill", ms);
+}
+
+/* Host-fed: process_depth_host_pre with groups of one, as the edge filter's form */
+int ssd_process_depth_host_fill(ssd_handle *h, const uint16_t *depth, int nframes, const ssd_depth_fill_rule *rule, ssd_frame_result *results,
+                                uint16_t *filled, ssd_depth_fill_stats *stats)
+{
+  const std::string me("ssd_process_depth_host_fill");
+  int rc = check_host_batch(h, me.c_str(), h && depth && results, nframes, SSD_INPUT_DEPTH16, kHandleCal);
+  ssd_depth_fill_rule R;
+  if(!rc) rc = check_fill_rule(me, rule, &R);
+  if(rc) return rc;
+  return process_depth_host_pre(h, me, "filled", depth, nframes, 1, results, filled,
+    [&](const void *buf, size_t stride, int, int cnt, unsigned char *stage, size_t stageStride)
+    {
+      return enqueue_depth_fill_impl(h, buf, stride, cnt, h->ingestCompute, R, stage, stageStride, nullptr, 0);
+    },
+    [&](int at, int cnt) { return stats ? ssd_fetch_depth_fill(h, stats + at, cnt, nullptr) : static_cast<int>(SSD_OK); });
+}
+
+/* a slice's scratch plane between two pre-passes on ingestCompute (warpStage, fillStage): at least `need` bytes; it grows only behind
+ * what that stream holds, which is all that reads it */
+static int slice_stage_grow(ssd_handle *h, ssd::DeviceBuf<unsigned char> &buf, size_t &cap, size_t need, const std::string &me, const char *kind)
+{
+  if(cap >= need)
+    return SSD_OK;
+  HIP_TRY(hipStreamSynchronize(h->ingestCompute));
+  buf.reset();
+  cap = 0;
+  const hipError_t e = buf.alloc(need);
+  if(e != hipSuccess)
+    return hip_fail(e, me + ": the " + kind + " frames' buffer: ");
+  cap = need;
+  return SSD_OK;
+}
+
+/* Host-fed, disjoint groups of n: ssd_process_depth_host_warp_fused with the fill between its two pre-passes.  The slice is warped into
+ * warpStage, that filled into fillStage (the fill reads its neighbours, so it cannot run in place), that fused into the staging buffer
+ * the detection reads.  All three run on ingestCompute, each behind the one before and the next slice's warp behind this slice's fusion */
+int ssd_process_depth_host_warp_fill_fused(ssd_handle *h, const uint16_t *depth, int nframes, int n, const ssd_depth_warp_view *views,
+                                           const ssd_intrinsics *dst, const ssd_depth_fill_rule *fill_rule, const ssd_depth_fuse_rule *fuse_rule,
+                                           ssd_frame_result *results, uint16_t *fused, ssd_depth_warp_stats *warp_stats,
+                                           ssd_depth_fill_stats *fill_stats, ssd_depth_fuse_stats *fuse_stats)
+{
+  const std::string me("ssd_process_depth_host_warp_fill_fused");
+  int rc = check_host_batch(h, me.c_str(), h && depth && results, nframes, SSD_INPUT_DEPTH16, kHandleCal);
+  ssd_depth_fuse_rule R;
+  ssd_depth_fill_rule Q;
+  if(!rc) rc = check_fuse_rule(me, n, fuse_rule, &R);
+  if(!rc) rc = check_fill_rule(me, fill_rule, &Q);
+  if(!rc) rc = check_warp_views(me, views, nframes, dst);
+  if(rc) return rc;
+  if(n > h->F || nframes % n != 0)
+    return fail(SSD_E_ARG, me + ": n must not exceed max_frames_per_batch and nframes must be a multiple of n");
+  if(h->P.nPoints % 2 != 0)
+    return fail(SSD_E_ARG, me + ": width * height must be even (the output is written in 32-bit words)");
+  if(std::memcmp(dst, &h->intr, sizeof(*dst)) != 0)
+    return fail(SSD_E_ARG, me + ": dst must be the intrinsics the handle detects under (ssd_set_intrinsics)");
+  return process_depth_host_pre(h, me, "fused", depth, nframes, n, results, fused,
+    [&](const void *buf, size_t stride, int at, int cnt, unsigned char *stage, size_t stageStride)
+    {
+      const size_t need = static_cast<size_t>(cnt) * stride;
+      int r = slice_stage_grow(h, h->warpStage, h->warpStageCap, need, me, "warped");
+      if(!r) r = slice_stage_grow(h, h->fillStage, h->fillStageCap, need, me, "filled");
+      if(!r) r = check_warp_words(h, me, h->warpStage.get(), stride);
+      if(!r) r = enqueue_depth_warp_impl(h, buf, stride, cnt, h->ingestCompute, views + at, *dst, h->warpStage.get(), stride);
+      if(!r) r = enqueue_depth_fill_impl(h, h->warpStage.get(), stride, cnt, h->ingestCompute, Q, h->fillStage.get(), stride, nullptr, 0);
+      if(!r) r = enqueue_depth_fuse_impl(h, h->fillStage.get(), stride, h->ingestCompute, n, n, cnt / n, R, stage, stageStride, nullptr, 0);
+      return r;
+    },
+    [&](int g0, int groups)
+    {
+      int r = warp_stats ? ssd_fetch_depth_warp(h, warp_stats + static_cast<size_t>(g0) * n, groups * n, nullptr) : static_cast<int>(SSD_OK);
+      if(!r && fill_stats) r = ssd_fetch_depth_fill(h, fill_stats + static_cast<size_t>(g0) * n, groups * n, nullptr);
       if(!r && fuse_stats) r = ssd_fetch_depth_fuse(h, fuse_stats + g0, groups, nullptr);
       return r;
     });

@@ -254,6 +254,12 @@ struct ssd_handle
    * counted as workspace */
   ssd::DeviceBuf<unsigned char> warpStage;
   size_t warpStageCap = 0;
+  /* the depth fill (section 7w): a record per frame; counted as workspace */
+  ssd_pass_records<ssd_depth_fill_stats> fill;
+  /* ssd_process_depth_host_warp_fill_fused: a slice's filled frames between warpStage and the fusion (the fill cannot run in place);
+   * managed exactly like warpStage, not counted as workspace */
+  ssd::DeviceBuf<unsigned char> fillStage;
+  size_t fillStageCap = 0;
 };
 
 /* The single pass's planes - dPlaneImg and dFallback of every workspace and the pinned hFallback, zeroed - for ALL workspaces of the

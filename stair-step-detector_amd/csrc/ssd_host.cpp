@@ -10,6 +10,7 @@
 #include "ssd_pose.h"
 #include "ssd_fuse.h"
 #include "ssd_edges.h"
+#include "ssd_fill.h"
 #include "ssd_warp.h"
 #include "ssd_refit.h"
 #include "ssd_clearance.h"
@@ -1742,6 +1743,65 @@ int ssd_depth_warp_view_between(const ssd_camera *src, const ssd_camera *dst, ss
     out->t[i] = (inv[i][0] * dc[0] + inv[i][1] * dc[1]) + inv[i][2] * dc[2];
   }
   out->src = src->intr;
+  return SSD_OK;
+}
+
+/* ---- depth fill: holes and one-pixel see-through closed between agreeing samples (include/ssd_hip.h) ----------------- */
+
+int ssd_depth_fill_default_rule(ssd_depth_fill_rule *rule)
+{
+  if(!rule)
+    return fail(SSD_E_ARG, "ssd_depth_fill_default_rule: null rule");
+  rule->min_pairs = 1;
+  rule->cover = 1;
+  rule->tol = SSD_FUSE_TOL;
+  rule->slope = 0;
+  return SSD_OK;
+}
+
+/* the refusals about the rule that the host statement, the enqueue and the host-fed forms share; *use: the rule to go by (the defaults
+ * where the caller gave none) */
+int check_fill_rule(const std::string &me, const ssd_depth_fill_rule *rule, ssd_depth_fill_rule *use)
+{
+  if(rule)
+    *use = *rule;
+  else
+    ssd_depth_fill_default_rule(use);
+  if(!fill_rule_ok(*use))
+    return fail(SSD_E_ARG, me + ": the rule must hold 1 <= min_pairs <= 4, 0 <= cover <= 4, 0 <= tol <= 65535, 0 <= slope <= 4096");
+  return SSD_OK;
+}
+
+int ssd_depth_fill_host(int width, int height, const uint16_t *frame, const ssd_depth_fill_rule *rule, uint16_t *out, uint8_t *cls,
+                        ssd_depth_fill_stats *stats)
+{
+  const std::string me("ssd_depth_fill_host");
+  if(!frame || !out || !stats || width <= 0 || height <= 0)
+    return fail(SSD_E_ARG, me + ": bad argument");
+  ssd_depth_fill_rule R;
+  const int rc = check_fill_rule(me, rule, &R);
+  if(rc) return rc;
+  int64_t rec[kFillWords] = {};
+  /* the sample at (x, y), 0 where the frame has no such pixel */
+  auto at = [&](int x, int y) -> uint32_t
+  {
+    return x >= 0 && x < width && y >= 0 && y < height ? frame[static_cast<size_t>(y) * width + x] : 0u;
+  };
+  for(int y = 0; y < height; y++)
+    for(int x = 0; x < width; x++)
+    {
+      const uint32_t q[8] = { at(x - 1, y - 1), at(x, y - 1), at(x + 1, y - 1), at(x - 1, y), at(x + 1, y), at(x - 1, y + 1), at(x, y + 1), at(x + 1, y + 1) };
+      uint32_t o, pairs, spread;
+      const int k = fill_pixel(at(x, y), q, R, &o, &pairs, &spread);
+      const size_t p = static_cast<size_t>(y) * width + x;
+      out[p] = static_cast<uint16_t>(o);
+      if(cls)
+        cls[p] = static_cast<uint8_t>(k);
+      rec[k]++;
+      rec[kFillSumPairs] += pairs;
+      rec[kFillSumSpread] += spread;
+    }
+  std::memcpy(stats, rec, sizeof(*stats));
   return SSD_OK;
 }
 

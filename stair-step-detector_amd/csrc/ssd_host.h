@@ -30,6 +30,7 @@ int check_pose_rule(const std::string &me, const ssd_stair_pose_rule *rule);
 int check_fuse_rule(const std::string &me, int n, const ssd_depth_fuse_rule *rule, ssd_depth_fuse_rule *use);
 int check_edge_rule(const std::string &me, const ssd_depth_edge_rule *rule, ssd_depth_edge_rule *use);
 int check_warp_views(const std::string &me, const ssd_depth_warp_view *views, int nviews, const ssd_intrinsics *dst);
+int check_fill_rule(const std::string &me, const ssd_depth_fill_rule *rule, ssd_depth_fill_rule *use);
 int check_pose_targets(const std::string &me, const ssd_stair_pose_target *targets, int ntargets, const uint16_t *target_of_frame, int nframes, int input);
 
 int pose_fold_frames(const char *who, const ssd_stair_pose_moments *records, const int *index, int nframes, std::vector<ssd_stair_pose_moments> &folds);

@@ -283,3 +283,37 @@ void launch_depth_warp(const void *frames, size_t strideBytes, int W, int H, int
 }
 
 } // namespace ssd
+
+/* k_depth_fill, the sixth stand-alone frame pass and the second stencil, on the edge filter's row machinery: its
+ * body in a header, its launcher here */
+#include "ssd_k_fill.h"
+
+namespace ssd
+{
+
+void launch_depth_fill(const void *frames, size_t strideBytes, int W, int H, int nframes, const ssd_depth_fill_rule &rule, void *out,
+                       size_t outStride, uint8_t *cls, size_t clsStride, ssd_depth_fill_stats *stats, hipStream_t s)
+{
+  /* the wide body: k_depth_edges' condition, for its loads and stores */
+  const bool wide = W % kEdgeStrip == 0 && aligned_to(frames, strideBytes, 16) && aligned_to(out, outStride, 16) && (!cls || aligned_to(cls, clsStride, 8));
+  FillArgs A;
+  A.frames = static_cast<const unsigned char *>(frames);
+  A.strideBytes = strideBytes;
+  A.out = static_cast<unsigned char *>(out);
+  A.outStride = outStride;
+  A.cls = cls;
+  A.clsStride = clsStride;
+  A.stats = reinterpret_cast<unsigned long long *>(stats);
+  A.W = W; A.H = H; A.nframes = nframes;
+  A.spans = (W + kEdgeSpan - 1) / kEdgeSpan;
+  A.tasks = A.spans * ((H + kEdgeTile - 1) / kEdgeTile);
+  A.blocksPerFrame = (A.tasks + kEdgeWaves - 1) / kEdgeWaves;
+  A.rule = rule;
+  const dim3 grid(static_cast<unsigned int>(A.blocksPerFrame) * nframes), block(kEdgeThreads);
+  if(wide)
+    hipLaunchKernelGGL((k_depth_fill<true>), grid, block, kFillLds, s, A);
+  else
+    hipLaunchKernelGGL((k_depth_fill<false>), grid, block, kFillLds, s, A);
+}
+
+} // namespace ssd
